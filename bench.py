@@ -252,6 +252,19 @@ def local_mapping_step(capi, torch, wl, steps=12):
     return out
 
 
+def last_call_outputs(ctx, poses0, steps):
+    """What the timed loop's last damping_iter call hands its caller: refined poses, *hess (before gauge fixing), [first, last]
+    residual and the LM trace (rows r1, r2, u, v, q1).  The timed calls end without a fetch (lm_end(fetch=False) leaves nothing to
+    read back), so the last call is run once more with one: it starts from poses0 on the same factor store with the eigen state
+    re-created there (lm_begin + lm_refresh_eigen) and runs the same number of iterations, i.e. it is the same computation."""
+    ctx.lm_begin(poses0, thd_num=2)
+    ctx.lm_refresh_eigen()
+    for _ in range(steps % 3 or 3):
+        ctx.lm_iterate(sync=False)
+    poses, hess, resis = ctx.lm_end(fetch=True)
+    return {"poses": poses, "hess": hess, "resis": resis, "trace": ctx.last_trace()}
+
+
 def cold_residual_pass(ctx, torch, poses0, V, occ, W, reps=12):
     """K4 with the caches flushed between repetitions (a 1 GiB scratch buffer is rewritten before every launch)."""
     scratch = torch.empty(1 << 27, dtype=torch.float64, device="cuda")
@@ -508,7 +521,10 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-scaled", action="store_true")
     ap.add_argument("--scene-copies", type=int, default=56)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed loop's last step computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launcher(args))
@@ -631,6 +647,12 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     t_res, n_res = ctx.timing_get("residual")
+    if args.dump_outputs:
+        dump = last_call_outputs(ctx, poses0, args.steps)      # every rank takes part (the LM loop all-reduces); rank 0 writes
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dump.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, dtype=np.float64))
     ctx.timing_sample_every(1)
     null_us = ctx.timing_null_spans(64)      # what an event pair costs when it brackets nothing (subtracted below)
     # second pass (not part of `value`): events around every kernel family; the trace tells how many steps were rejected ones
