@@ -42,7 +42,7 @@ __device__ __forceinline__ void so3_exp_dev(const double *w, double *R) {   // t
 // `red` = the reduced [H | g | r] of the last Hessian pass.  It is never modified here: the gauge (first 6 rows/cols ->
 // identity, JacT.head(6) = 0, VM:452-455) and the damping u*diag are applied while the system is loaded, so a rejected
 // step re-reads the same H with a new u (VM:443) and `red[0..n^2)` doubles as *hess (VM:446).  With more than one rank
-// the exchange step all-reduces `red` in place on every iteration, so the valid copy is kept in `raw` (copy_raw != 0).
+// the exchange step all-reduces `red` in place on every iteration, so the valid copy is kept in `raw` (COPY_RAW).
 // Elimination order = Eigen's LDLT pivoting: largest |diagonal| of the *stored* matrix first (ldlt_inplace::unblocked),
 // realised as a rank computation (first index wins ties).
 // (History, measured on MI355X at n = 60: unblocked LDS rows 58 us -> one wave blocked by pose 30.8 us -> this kernel 24 us,
@@ -50,7 +50,17 @@ __device__ __forceinline__ void so3_exp_dev(const double *w, double *R) {   // t
 //
 // Blocked variant (vba_ldlt.hpp) for every supported window (n = 6W <= 96): trailing matrix in MFMA accumulators, panels
 // of 8 columns, two barriers per panel.  Everything the kernel reads was written by other kernels (in general on another
-// XCD, ~2 us per dependent trip), so the whole reduced system is requested up front and staged in LDS before the first branch.
+// XCD, ~2 us per dependent trip), so the launch is one round trip deep before the factorisation:
+//   * COPY_RAW (more than one rank, see above) is a template parameter, so that no control-flow join merges the two load orders
+//     (the wait at such a join covers the longer queue of the two: vmcnt(0));
+//   * the state flags are requested first (read before any store, they come in as scalar loads) and the reduced system right
+//     behind them; the gate waits on lgkmcnt only, not on the system's vmcnt, so a gated launch costs one round trip;
+//   * the system is read in its tile layout (coalesced, one load per upper-triangle tile per thread, plus the E-block remainder
+//     at a clamped index: no load sits behind a branch, so none waits for another);
+//   * every wave ranks the diagonal itself from registers (readlanes, no LDS, no barrier) while the system is in flight, and the
+//     system is written straight into its PERMUTED position in a packed LDS image, so the tile build reads one LDS word per
+//     element with no index indirection;
+//   * the retraction runs on the last wave beside the q1 reduction of the first two.
 //
 // Speculative damping.  The solve is one workgroup on a 256-CU chip and the longest kernel of an iteration, and a REJECTED step
 // repeats it on the same H and x with a damping that is known in advance (u <- u v, v <- 2 v, VM:485-486).  So the launch has
@@ -59,96 +69,145 @@ __device__ __forceinline__ void so3_exp_dev(const double *w, double *R) {   // t
 // xt_spec[b] / q1_spec[b].  When the update rejects a step and a candidate is left it copies that candidate into xt / q1 and
 // sets use_spec; the next launch of this kernel then returns at once.  An accepted step discards the candidates.  No field a
 // workgroup reads on entry is written inside this kernel, so the workgroups need no ordering among themselves.
+
+// Index of the diagonal-block remainder E that tl_fetch adds to H(row, col), row <= col < 6W; -1 outside the frame's 6 x 6 block.
 template <int W>
-__global__ __launch_bounds__(256) void k_lm_solve_m(LmDev *s, const double *__restrict__ red, double *__restrict__ raw, int copy_raw) {
+__device__ __forceinline__ int tl_eidx(int row, int col) {
+  using C = HessCfg2<W>;
+  const int fr = row / 6;
+  if (col / 6 != fr) return -1;
+  const int a = row - 6 * fr, b = col - 6 * fr;
+  int idx;
+  if (b < 3) idx = a * 3 - a * (a - 1) / 2 + (b - a);
+  else if (a < 3) idx = 6 + 3 * a + (b - 3);
+  else { const int a2 = a - 3, b2 = b - 3; idx = 15 + a2 * 3 - a2 * (a2 - 1) / 2 + (b2 - a2); }
+  return C::EB + 21 * fr + idx;
+}
+
+template <int W, bool COPY_RAW>
+__global__ __launch_bounds__(256) void k_lm_solve_m(LmDev *s, const double *__restrict__ red, double *__restrict__ raw) {
   const int sb = blockIdx.x;
   using C2 = HessCfg2<W>;
-  constexpr int n = 6 * W, NT = 256, NP = ((n + 1 + 15) / 16) * 16;
+  constexpr int n = 6 * W, NT = 256, NP = ((n + 1 + 15) / 16) * 16, NH = (n + 63) / 64, NU = C2::NU, T16 = C2::NT16;
   using LC = LdltCfg<NP>;
-  constexpr int STG = n * (n + 1) / 2;
-  __shared__ __attribute__((aligned(16))) double lds[LC::DOUBLES > STG ? LC::DOUBLES : STG];
-  __shared__ double hd[n], gs[n], dsh[n], xs[NP], dxs[n], red8[8];
+  // image of the whole NP x NP system ldlt_mfma factorises, packed lower triangle: P (Hess + u D) P^T, row n = -g, identity on the
+  // padding (NP >= n + 2: row n + 1 is zero left of its diagonal, and (n + 1, 0) serves the upper triangle of the diagonal tiles)
+  constexpr int IMG = NP * (NP + 1) / 2, ZERO = (n + 1) * (n + 2) / 2;
+  static_assert(IMG <= LC::LTOT && NP >= n + 2, "the image must lie in the L region: ldlt_mfma writes P while the tiles are read");
+  __shared__ __attribute__((aligned(16))) double lds[LC::DOUBLES];
+  __shared__ double hd[n], gs[n], xs[NP], dxs[n], red8[8];
   __shared__ int ord[n];
-  double *Lst = lds, *Tp = Lst + LC::LTOT, *P = Tp + NP * LC::LS, *stage = lds;
-  const int tid = threadIdx.x;
-  constexpr int NL = n * n, QL = (NL + NT - 1) / NT;
-  double lv[QL];
-  if (!copy_raw) {
+  double *Lst = lds, *Tp = Lst + LC::LTOT, *P = Tp + NP * LC::LS, *img = lds;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  // flags first: the gate below waits for these loads only
+  const int use_spec = s->use_spec, stop = s->stop, calc = s->is_calc_hess;
+  const double u0 = s->u, v0 = s->v;
+  __builtin_amdgcn_sched_barrier(0);
+  // lane k of every wave: H(k, k) (tile value, E remainder) and g[k], k = lane + 64 h
+  double dgt[NH], dge[NH], gv[NH];
+  auto load_diag = [&](const double *__restrict__ src) {
 #pragma unroll
-    for (int q = 0; q < QL; q++) {
-      const int e = tid + NT * q, ec = e < NL ? e : NL - 1;
-      const int row = ec / n, col = ec - row * n;
-      lv[q] = tl_fetch<W>(red, row, col);
+    for (int h = 0; h < NH; h++) {
+      const int k = lane + 64 * h, kc = k < n ? k : n - 1, ta = kc >> 4, rt = kc & 15;
+      dgt[h] = src[(ta * T16 - ta * (ta - 1) / 2) * 256 + (rt >> 2) * 64 + (rt & 3) * 16 + rt];
+      dge[h] = src[tl_eidx<W>(kc, kc)];
+      gv[h] = src[C2::GB + kc];
     }
-  }
-  double g_v = (!copy_raw && tid < n) ? red[C2::GB + tid] : 0.0;
-  double xr[12];
-  if (tid < W)
+  };
+  // thread tid, upper-triangle tile u = (ta, tb): H(16 ta + ru, 16 tb + cu) = tile value (+ E remainder inside a frame's block)
+  const int ru = (lane >> 4) + 4 * wv, cu = lane & 15;
+  double tv[NU], ev[NU];
+  bool eon[NU];
+  auto load_bulk = [&](const double *__restrict__ src) {
+    int u = 0;
 #pragma unroll
-    for (int k = 0; k < 12; k++) xr[k] = s->x[12 * tid + k];
+    for (int ta = 0; ta < T16; ta++)
+#pragma unroll
+      for (int tb = ta; tb < T16; tb++, u++) {
+        const int row = 16 * ta + ru, col = 16 * tb + cu;
+        const int e = (row <= col && col < n) ? tl_eidx<W>(row, col) : -1;
+        eon[u] = e >= 0;
+        tv[u] = src[u * 256 + tid];
+        ev[u] = src[e >= 0 ? e : C2::EB];
+      }
+  };
+  if constexpr (!COPY_RAW) { load_diag(red); load_bulk(red); }
+  const double r_v = COPY_RAW ? 0.0 : red[C2::RB];
+  double xr[12];
+  if (wv == 3 && lane < W)
+#pragma unroll
+    for (int k = 0; k < 12; k++) xr[k] = s->x[12 * lane + k];
   const long long t_begin = clock64();
-  const int stop = s->stop, calc = s->is_calc_hess, iter0 = s->iter, dbg = s->pad, use_spec = s->use_spec;
-  const double u0 = s->u, v0 = s->v, r_v = copy_raw ? 0.0 : red[C2::RB];
   if (stop || use_spec) return;
   double u = u0;
   { double vb = v0; for (int k = 0; k < sb; k++) { u = u * vb; vb = 2 * vb; } }                         // VM:485-486, sb times
-  long long *stamps = ((dbg & 16) && tid == 0 && sb == 0) ? s->stamps : nullptr;
-  if (stamps) stamps[0] = t_begin;
-  const double *__restrict__ src = (copy_raw && !calc) ? raw : red;
-  if (copy_raw) {
+  if constexpr (COPY_RAW) {
+    const double *__restrict__ src = calc ? red : raw;
     if (calc && sb == 0)
       for (int t = tid; t < C2::NOUT2; t += NT) raw[t] = src[t];
+    load_diag(src); load_bulk(src);
+  }
+  // rank of row k = its position in the elimination order, computed by every wave for its own lanes
+  double hk[NH], dk[NH];
+  int rk[NH];
 #pragma unroll
-    for (int q = 0; q < QL; q++) {
-      const int e = tid + NT * q, ec = e < NL ? e : NL - 1;
-      const int row = ec / n, col = ec - row * n;
-      lv[q] = tl_fetch<W>(src, row, col);
-    }
-    if (tid < n) g_v = src[C2::GB + tid];
+  for (int h = 0; h < NH; h++) {
+    const int k = lane + 64 * h;
+    hk[h] = k < 6 ? 1.0 : dgt[h] + dge[h];                                                              // gauge VM:452-455
+    dk[h] = fabs(hk[h] + u * hk[h]);
+    rk[h] = 0;
   }
-  if (tid == 0 && calc && sb == 0) { const double r = copy_raw ? src[C2::RB] : r_v; s->r1 = r; if (iter0 == 0) s->resis_first = r; }   // VM:445, 449-450
 #pragma unroll
-  for (int q = 0; q < QL; q++) {
-    const int e = tid + NT * q;
-    const int row = e / n, col = e - row * n;
-    if (e < NL && col <= row) stage[row * (row + 1) / 2 + col] = lv[q];
+  for (int j = 0; j < n; j++) {
+    const double o = readlane_f64(dk[j >> 6], j & 63);
+#pragma unroll
+    for (int h = 0; h < NH; h++) rk[h] += (o > dk[h] || (o == dk[h] && j < lane + 64 * h)) ? 1 : 0;
   }
-  __syncthreads();
-  if (tid < n) {
-    const double h = tid < 6 ? 1.0 : stage[tid * (tid + 1) / 2 + tid];                                  // gauge VM:452-455
-    hd[tid] = h; gs[tid] = tid < 6 ? 0.0 : g_v;
-    dsh[tid] = fabs(h + u * h);
-    ord[tid] = 0;
+  // scatter the (gauged, damped) system to its permuted position
+  int prow[T16], pcol[T16];
+#pragma unroll
+  for (int t = 0; t < T16; t++) {                   // 16 t < n, so a clamped row stays in the 64-row half of 16 t
+    const int r = 16 * t + ru, c = 16 * t + cu;
+    prow[t] = __shfl(rk[(16 * t) >> 6], (r < n ? r : n - 1) & 63);
+    pcol[t] = __shfl(rk[(16 * t) >> 6], (c < n ? c : n - 1) & 63);
   }
-  __syncthreads();
   {
-    constexpr int parts = NT / n;
-    const int i = tid % n, part = tid / n;
-    if (part < parts) {
-      const double me = dsh[i];
-      constexpr int seg = (n + parts - 1) / parts;
-      const int j0 = part * seg, j1 = (j0 + seg < n) ? j0 + seg : n;
-      int cnt = 0;
-#pragma unroll 8
-      for (int j = j0; j < j1; j++) { const double o = dsh[j]; cnt += (o > me || (o == me && j < i)) ? 1 : 0; }
-      atomicAdd(&ord[i], cnt);
-    }
+    int uu = 0;
+#pragma unroll
+    for (int ta = 0; ta < T16; ta++)
+#pragma unroll
+      for (int tb = ta; tb < T16; tb++, uu++) {
+        const int row = 16 * ta + ru, col = 16 * tb + cu;
+        if (row <= col && col < n) {
+          double a = eon[uu] ? tv[uu] + ev[uu] : tv[uu];
+          a = (row < 6) ? ((row == col) ? 1.0 : 0.0) : a;
+          a = (row == col) ? a + u * a : a;
+          const int pr = prow[ta], pc = pcol[tb], hi = pr > pc ? pr : pc, lo = pr > pc ? pc : pr;
+          img[hi * (hi + 1) / 2 + lo] = a;
+        }
+      }
   }
+  if (wv == 0)
+#pragma unroll
+    for (int h = 0; h < NH; h++) {
+      const int k = lane + 64 * h;
+      if (k < n) {
+        const double g = k < 6 ? 0.0 : gv[h];
+        hd[k] = hk[h]; gs[k] = g; ord[rk[h]] = k;
+        img[n * (n + 1) / 2 + rk[h]] = -g;
+      }
+    }
+#pragma unroll
+  for (int i = n; i < NP; i++)                      // padding rows (NP <= 112 < NT: one element per thread and row)
+    if (tid <= i && (i > n || tid >= n)) img[i * (i + 1) / 2 + tid] = (tid == i) ? 1.0 : 0.0;
+  // (read after the gate and used only here, behind the system: in-order vmcnt)
+  const int iter0 = s->iter, dbg = s->pad;
+  if (tid == 0 && calc && sb == 0) { const double r = COPY_RAW ? red[C2::RB] : r_v; s->r1 = r; if (iter0 == 0) s->resis_first = r; }   // VM:445, 449-450
+  long long *stamps = ((dbg & 16) && tid == 0 && sb == 0) ? s->stamps : nullptr;
+  if (stamps) stamps[0] = t_begin;
   __syncthreads();
-  const int my_rank = (tid < n) ? ord[tid] : 0;
-  __syncthreads();
-  if (tid < n) ord[my_rank] = tid;
-  __syncthreads();
-  auto elem = [&](int i, int j) -> double {        // P (Hess + u D) P^T lower triangle, row n = -g, identity on the padding
-    const int jc = j < n ? j : n - 1, ic = i < n ? i : n - 1;
-    const int pj = ord[jc], pi = ord[ic];
-    const int rr = pi > pj ? pi : pj, cc = pi > pj ? pj : pi;
-    double a = stage[rr * (rr + 1) / 2 + cc];
-    a = (rr < 6 || cc < 6) ? ((rr == cc) ? 1.0 : 0.0) : a;
-    a = (i == j) ? a + u * a : a;
-    a = (i == n) ? -gs[pj] : a;
-    a = (i > n || i < j) ? 0.0 : a;
-    return (j >= n) ? ((i == j) ? 1.0 : 0.0) : a;
+  auto elem = [&](int i, int j) -> double {        // one unconditional LDS read per element: no branch, no wait between elements
+    return img[i >= j ? i * (i + 1) / 2 + j : ZERO];
   };
   if (stamps) stamps[1] = clock64();
   ldlt_mfma<NP, NT>(Lst, Tp, P, n, elem, ((dbg & 16) && sb == 0) ? s->stamps : nullptr);
@@ -159,21 +218,25 @@ __global__ __launch_bounds__(256) void k_lm_solve_m(LmDev *s, const double *__re
   if (stamps) stamps[4] = clock64();
   if (tid < n) dxs[ord[tid]] = x;
   __syncthreads();
-  if (tid < W) {                                                                                        // VM:460-464
-    double E[9];
-    so3_exp_dev(dxs + 6 * tid, E);
-    const double *R = xr;
-    double *Rt = (sb == 0 ? s->xt : s->xt_spec[sb]) + 12 * tid;
+  if (wv == 3) {                                                                                        // VM:460-464
+    if (lane < W) {
+      double E[9];
+      so3_exp_dev(dxs + 6 * lane, E);
+      const double *R = xr;
+      double *Rt = (sb == 0 ? s->xt : s->xt_spec[sb]) + 12 * lane;
 #pragma unroll
-    for (int r = 0; r < 3; r++)
+      for (int r = 0; r < 3; r++)
 #pragma unroll
-      for (int c = 0; c < 3; c++) Rt[3 * r + c] = R[3 * r] * E[c] + R[3 * r + 1] * E[3 + c] + R[3 * r + 2] * E[6 + c];
+        for (int c = 0; c < 3; c++) Rt[3 * r + c] = R[3 * r] * E[c] + R[3 * r + 1] * E[3 + c] + R[3 * r + 2] * E[6 + c];
 #pragma unroll
-    for (int k = 0; k < 3; k++) Rt[9 + k] = R[9 + k] + dxs[6 * tid + 3 + k];
+      for (int k = 0; k < 3; k++) Rt[9 + k] = R[9 + k] + dxs[6 * lane + 3 + k];
+    }
+    if (lane == 63) red8[3] = 0.0;                 // (the wave sum of no rows)
+  } else {
+    double q = tid < n ? dxs[tid] * (u * hd[tid] * dxs[tid] - gs[tid]) : 0.0;                          // VM:465
+    q = wave_sum_to_lane63(q);                                  // DPP adds (vba_kernels_factor.hpp), no LDS round trips
+    if (lane == 63) red8[wv] = q;
   }
-  double q = tid < n ? dxs[tid] * (u * hd[tid] * dxs[tid] - gs[tid]) : 0.0;                              // VM:465
-  q = wave_sum_to_lane63(q);                                  // DPP adds (vba_kernels_factor.hpp), no LDS round trips
-  if ((tid & 63) == 63) red8[tid >> 6] = q;
   __syncthreads();
   if (tid == 0) {
     const double q1 = 0.5 * (red8[0] + red8[1] + red8[2] + red8[3]);

@@ -858,7 +858,10 @@ int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
   TimedSpan sp{};
   span_begin(c, "solve", sp);
   switch (W) {
-#define VBA_SM_CASE(WW) case WW: hipLaunchKernelGGL(k_lm_solve_m<WW>, dim3(c->lm_spec), dim3(256), 0, c->stream, c->d_lm, c->d_out, c->d_raw, copy_raw); break;
+#define VBA_SM_CASE(WW) case WW: \
+    if (copy_raw) hipLaunchKernelGGL((k_lm_solve_m<WW, true>), dim3(c->lm_spec), dim3(256), 0, c->stream, c->d_lm, c->d_out, c->d_raw); \
+    else hipLaunchKernelGGL((k_lm_solve_m<WW, false>), dim3(c->lm_spec), dim3(256), 0, c->stream, c->d_lm, c->d_out, c->d_raw); \
+    break;
     VBA_SM_CASE(2) VBA_SM_CASE(3) VBA_SM_CASE(4) VBA_SM_CASE(5) VBA_SM_CASE(6) VBA_SM_CASE(7) VBA_SM_CASE(8) VBA_SM_CASE(9) VBA_SM_CASE(10)
     VBA_SM_CASE(11) VBA_SM_CASE(12) VBA_SM_CASE(13) VBA_SM_CASE(14) VBA_SM_CASE(15) VBA_SM_CASE(16)
 #undef VBA_SM_CASE
