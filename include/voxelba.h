@@ -246,6 +246,57 @@ int vba_odom_kdtree_size(vba_ctx *ctx);    /* pl_tree->size() */
 int vba_odom_kdtree_points(vba_ctx *ctx, double *xyz_out /* [size][3] */);
 
 /* ------------------------------------------------------------------------------------------------
+ * LiDAR-inertial initialisation: int Initialization::motion_init(pl_origs, vec_imus, beg_times, hess, voxhess, x_buf, surf_map,
+ * surf_map_slide, pvec_buf, win_size, sws, x_curr, imu_pre_buf, extrin_para) (VS:617-819, called from initialization at VS:1524).
+ * Up to 10 rounds of {map teardown (VS:650-661), motion blur of every scan with its own IMU deque (VS:506-601, VS:668), cut_voxel
+ * with win_count = i (VM:1896, VS:688), recut + tras_opt with multi = 0 (VS:695-703), break if fewer than 10 factors (VS:706-707),
+ * LI_BA_OptimizerGravity::damping_iter(.., 3) (VS:711), re-preintegration of scan i's deque with x_buf[i-1].bg/ba (VS:719-730),
+ * convergence / degeneracy test (VS:733-758, align_gravity on the first hit)}; failure (VS:764-786) tears the map down, success
+ * leaves map and factor store on the context as surf_map / voxhess are left for the first steady-state step.
+ * The clouds are uploaded once per call and stay in HBM; per round only the factor count, resis, the states and eigvalue3 cross.
+ * The relaxed thresholds of VS:624-630 (min_eigen_value 0.02, plane_eigen_value_thre 1/4) apply through a per-call override of the
+ * map's parameters until the round after the first convergence (VS:643-647); the context's vba_options are never written.
+ *   win_size                   W = vba_options::win_size (win_size)
+ *   pt_offsets [W+1], pnt [][3], curv []   pl_origs: ragged raw clouds, rows pt_offsets[i]..pt_offsets[i+1] of scan i, lidar-frame
+ *                              xyz (PCL float values in doubles) and PointType::curvature, ascending per scan (VS:1510-1512)
+ *   imu_offsets [W+1], imu [][7]   vec_imus: ragged deques, rows [t, gyr(3), acc(3)] as the deques hold them (VS:1513)
+ *   beg_times [W]              beg_times (odom_ekf.pcl_beg_time per scan, VS:1514)
+ *   ext_pose [12]              extrin_para (R row-major, p)
+ *   dept_err, beam_err         globals of calcBodyVar (VH:179), applied after the first convergence (VS:675-681)
+ *   scale_gravity              imupre_scale_gravity (PI:9): motion_blur (VS:522) and the re-preintegration
+ *   point_notime               global point_notime (VS:550)
+ *   noise_meas_diag6, noise_walk_diag6   noiseMeas / noiseWalk diagonals as for vba_imu_preintegrate
+ *   states [W][25] in/out      x_buf;  covs [W][225] in: x_buf[i].cov (pvec_update, VS:680)
+ *   imus [W-1][304] in/out     imu_pre_buf
+ *   hess ((15W+3)^2) out       hess: the last damping_iter's Hessian (may be NULL)
+ *   *converged                 the int return value of motion_init (converge_flag)
+ *   eigvalue3 [3]              eigvalue of VS:744-745 (ascending; zeros if the convergence test never passed)
+ *   *iterations                outer rounds started (iterCnt + 1 at the exit of the loop)
+ *   *thresholds_left_relaxed   1 if the reference would leave the relaxed thresholds in its globals (the loop ended before the
+ *                              round after the first convergence); the context keeps its own options either way
+ *   round_log [max_rounds][5]  per round: [factor count, resis[0], resis[1], |x_buf[0].g|, converge_flag] after the round (may be
+ *                              NULL; resis stay 0 in a round that breaks before the LM)
+ *   pnt_out [pvec_cap][3], var_out [pvec_cap][9], pvec_offsets [W+1]   pvec_buf after the last round: compensated body points in the
+ *                              reference's push order and their var (identity before the first convergence, world-frame pvec_update
+ *                              after it); NULL pnt_out skips them.  pvec_offsets is always written when given; VBA_ERR_CAPACITY
+ *                              when the rows exceed pvec_cap (checked before any work).
+ * Argument errors are found before any device work and leave the context untouched.  Any other non-zero return leaves states, imus
+ * and the other outputs undefined and the context with an empty map and factor store. */
+int vba_motion_init(vba_ctx *ctx, int win_size, const int *pt_offsets, const double *pnt, const double *curv, const int *imu_offsets,
+                    const double *imu, const double *beg_times, const double *ext_pose, double dept_err, double beam_err,
+                    double scale_gravity, int point_notime, const double *noise_meas_diag6, const double *noise_walk_diag6,
+                    double *states, const double *covs, double *imus, double *hess, int *converged, double *eigvalue3, int *iterations,
+                    int *thresholds_left_relaxed, double *round_log, int max_rounds, double *pnt_out, double *var_out, int *pvec_offsets,
+                    int pvec_cap);
+/* Host only, no context.  The backward IMU propagation of Initialization::motion_blur (VS:508-544): xc = state_c with the biases of
+ * state_l (VS:508-509), m deque rows imu [m][7] -> out [m-1][22] rows [offt, R(9), p(3), v(3), angvel_avr(3), acc_imu(3)] in push
+ * order (time descending, offt = head time - beg_time): the table the initialisation blur reads. */
+int vba_init_imu_poses(int m, const double *imu, const double *state_c, const double *state_l, double beg_time, double scale_gravity,
+                       double *out);
+/* Host only.  Initialization::align_gravity (VS:470-497) on states [n][25] in place. */
+int vba_init_align_gravity(int n, double *states);
+
+/* ------------------------------------------------------------------------------------------------
  * Hierarchical global BA ("next #3"), one keyframe window per call.  vba_hba_add_edge accepts any
  * wdsize >= 2: a window of the context's win_size (the bottom layers use 10, VS:3033) runs on the templated device
  * kernels; any other size — the top-level BA over all submaps, VS:3103-3113 — takes the sparse path (hashed per-keyframe
@@ -318,7 +369,8 @@ int vba_timing_sample_every(vba_ctx *ctx, int n);
 /* Records an event pair around no work under the name "null": the overhead that every bracketed launch carries. */
 int vba_timing_null_span(vba_ctx *ctx);
 int vba_timing_reset(vba_ctx *ctx);
-/* name in {"residual","hessian","reduce","solve","insert","recut","margi"}; returns launches in *count. */
+/* name in {"residual","hessian","reduce","solve","insert","recut","margi","init"} ("init": the blur and normal-scatter launches of
+ * vba_motion_init); returns launches in *count. */
 int vba_timing_get(vba_ctx *ctx, const char *name, double *total_us, int *count);
 
 /* LM building blocks on device state (used by bench.py to time exactly K LM iterations, and by the

@@ -9,6 +9,7 @@
 //   class LI_BA_OptimizerGravity VM:717-976  (damping_iter :878)    vba::LI_BA_OptimizerGravity
 //   cut_voxel / cut_voxel_multi / cut_voxel(fix)  VM:1896/1964/2108 vba::VoxelMap::cut_voxel[_multi|_fix]
 //   multi_recut / multi_margi    VS:1682 / VS:1590                  vba::VoxelMap::multi_recut / multi_margi
+//   Initialization::motion_init  VS:617-819                         vba::Initialization::motion_init
 //
 // The reference's types are Eigen-based (tools.hpp:4).  This header compiles without Eigen (plain-array structs that
 // mirror PointCluster / IMUST / IMU_PRE field for field); when <Eigen/Core> is available the Eigen-typed overloads
@@ -17,6 +18,7 @@
 #include "voxelba.h"
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -224,6 +226,82 @@ class VoxelMap {
     check(c_, vba_map_cut_voxel(c_, win_count, (int)n, p.data(), with_var ? v.data() : nullptr, pose, multi));
   }
   vba_ctx *c_;
+};
+
+// ---- LiDAR-inertial initialisation: class Initialization (voxelslam.cpp:460-820)
+struct PointXYZC { float x, y, z, curvature; };   // the fields of a PointType (pcl::PointXYZINormal) that motion_init reads
+struct ImuSample { double t, gyr[3], acc[3]; };   // one sensor_msgs::Imu of a deque: stamp, angular_velocity, linear_acceleration
+
+class Initialization {
+ public:
+  // the reference's globals that motion_init reads: dept_err / beam_err (VH:179), imupre_scale_gravity / noiseMeas / noiseWalk (PI:8-9),
+  // point_notime (VS:550)
+  double dept_err = 0.02, beam_err = 0.05, scale_gravity = 1.0;
+  double noise_meas[6] = {0, 0, 0, 0, 0, 0}, noise_walk[6] = {0, 0, 0, 0, 0, 0};
+  int point_notime = 0;
+  // filled by each call: eigvalue (VS:744), outer rounds run, and whether the reference would leave its relaxed thresholds in force
+  double eigvalue[3] = {0, 0, 0};
+  int iterations = 0, thresholds_left_relaxed = 0;
+
+  // int motion_init(pl_origs, vec_imus, beg_times, hess, voxhess, x_buf, surf_map, surf_map_slide, pvec_buf, win_size, sws, x_curr,
+  //                 imu_pre_buf, extrin_para)  VS:617.  surf_map stands for surf_map + surf_map_slide (one device map); sws has no
+  // counterpart (the device map recycles its own nodes).  imu_pre_buf must hold win_size - 1 factors; they are rebuilt in place
+  // (VS:719-730).  As in the reference, pl_origs / vec_imus / beg_times are cleared on return (VS:795-797).
+  int motion_init(std::vector<std::vector<PointXYZC>> &pl_origs, std::vector<std::vector<ImuSample>> &vec_imus, std::vector<double> &beg_times,
+                  std::vector<double> *hess, LidarFactor &voxhess, std::vector<IMUST> &x_buf, VoxelMap &surf_map,
+                  std::vector<std::shared_ptr<PVec>> &pvec_buf, int win_size, IMUST &x_curr, std::deque<IMU_PRE *> &imu_pre_buf,
+                  const IMUST &extrin_para) {
+    const int W = win_size;
+    if ((int)pl_origs.size() < W || (int)vec_imus.size() < W || (int)beg_times.size() < W || (int)x_buf.size() < W ||
+        (int)imu_pre_buf.size() < W - 1)
+      throw std::runtime_error("libvoxelba: motion_init: fewer than win_size scans / states / IMU factors");
+    std::vector<int> pto(W + 1, 0), imo(W + 1, 0);
+    for (int i = 0; i < W; i++) { pto[i + 1] = pto[i] + (int)pl_origs[i].size(); imo[i + 1] = imo[i] + (int)vec_imus[i].size(); }
+    std::vector<double> pnt((size_t)pto[W] * 3 + 3), curv((size_t)pto[W] + 1), imu((size_t)imo[W] * 7 + 7);
+    for (int i = 0; i < W; i++) {
+      for (size_t k = 0; k < pl_origs[i].size(); k++) {
+        const PointXYZC &a = pl_origs[i][k];
+        const size_t r = (size_t)pto[i] + k;
+        pnt[3 * r] = a.x; pnt[3 * r + 1] = a.y; pnt[3 * r + 2] = a.z; curv[r] = a.curvature;
+      }
+      for (size_t k = 0; k < vec_imus[i].size(); k++) std::memcpy(&imu[((size_t)imo[i] + k) * 7], &vec_imus[i][k], 7 * sizeof(double));
+    }
+    std::vector<double> st((size_t)W * 25), cov((size_t)W * 225), im((size_t)(W - 1) * VBA_IMU_PRE_LEN);
+    for (int i = 0; i < W; i++) { std::memcpy(&st[(size_t)i * 25], &x_buf[i].t, 25 * sizeof(double)); std::memcpy(&cov[(size_t)i * 225], x_buf[i].cov, 225 * sizeof(double)); }
+    for (int i = 0; i < W - 1; i++) std::memcpy(&im[(size_t)i * VBA_IMU_PRE_LEN], imu_pre_buf[i]->f, sizeof(imu_pre_buf[i]->f));
+    double ext[12];
+    std::memcpy(ext, extrin_para.R, 72); std::memcpy(ext + 9, extrin_para.p, 24);
+    const int nh = 15 * W + 3;
+    if (hess) hess->assign((size_t)nh * nh, 0.0);
+    const int cap = pto[W] + imo[W];
+    std::vector<double> po((size_t)cap * 3 + 3), vo((size_t)cap * 9 + 9);
+    std::vector<int> pvo(W + 1);
+    int converged = 0;
+    check(voxhess.ctx(), vba_motion_init(voxhess.ctx(), W, pto.data(), pnt.data(), curv.data(), imo.data(), imu.data(), beg_times.data(), ext, dept_err,
+                                         beam_err, scale_gravity, point_notime, noise_meas, noise_walk, st.data(), cov.data(), im.data(),
+                                         hess ? hess->data() : nullptr, &converged, eigvalue, &iterations, &thresholds_left_relaxed, nullptr, 0,
+                                         po.data(), vo.data(), pvo.data(), cap));
+    (void)surf_map;   // the map (and voxhess) stay on the context, as surf_map / voxhess in the reference
+    for (int i = 0; i < W; i++) std::memcpy(&x_buf[i].t, &st[(size_t)i * 25], 25 * sizeof(double));
+    for (int i = 1; i < W; i++) {                                  // IMU_PRE(x_buf[i-1].bg, x_buf[i-1].ba) + push_imu (VS:724-730)
+      IMU_PRE *f = imu_pre_buf[i - 1];
+      std::memcpy(f->f, &im[(size_t)(i - 1) * VBA_IMU_PRE_LEN], sizeof(f->f));
+      std::memcpy(f->bg0, x_buf[i - 1].bg, 24); std::memcpy(f->ba0, x_buf[i - 1].ba, 24);
+    }
+    if ((int)pvec_buf.size() < W) pvec_buf.resize(W);
+    for (int i = 0; i < W; i++) {
+      if (!pvec_buf[i]) pvec_buf[i].reset(new PVec);
+      PVec &pv = *pvec_buf[i];
+      pv.resize((size_t)(pvo[i + 1] - pvo[i]));
+      for (size_t k = 0; k < pv.size(); k++) {
+        std::memcpy(pv[k].pnt, &po[((size_t)pvo[i] + k) * 3], 24);
+        std::memcpy(pv[k].var, &vo[((size_t)pvo[i] + k) * 9], 72);
+      }
+    }
+    x_curr = x_buf[W - 1];                                         // VS:761
+    pl_origs.clear(); vec_imus.clear(); beg_times.clear();         // VS:795-797
+    return converged;
+  }
 };
 
 // ---- scan pre-processing and hierarchical global BA (free functions of the reference: tools.hpp / voxelslam.cpp)

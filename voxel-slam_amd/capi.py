@@ -32,6 +32,7 @@ EXPORTS = [
     "vba_timing_enable", "vba_timing_calibration_read", "vba_timing_select", "vba_timing_sample_every", "vba_timing_launch_hessian", "vba_timing_null_span", "vba_timing_reset", "vba_timing_get",
     "vba_lm_begin", "vba_lm_refresh_eigen", "vba_lm_iterate", "vba_lm_end",
     "vba_io_save_pcd", "vba_io_load_pcd", "vba_io_save_pose", "vba_io_read_lidarstate",
+    "vba_motion_init", "vba_init_imu_poses", "vba_init_align_gravity",
 ]
 
 
@@ -136,6 +137,26 @@ def imu_give_evaluate(imu, st1, st2, with_g=False, jac=True):
     if st:
         raise VbaError(st)
     return r.value, jtj, gg
+
+
+def init_imu_poses(imu, state_c, state_l, beg_time, scale_gravity=1.0):
+    """Backward IMU pose table of Initialization::motion_blur (voxelslam.cpp:508-544): rows [t, R(9), p(3), v(3), angvel(3), acc(3)]."""
+    imu = _c(imu).reshape(-1, 7); xc = _c(state_c); xl = _c(state_l)
+    m = len(imu)
+    out = np.zeros((max(m - 1, 0), 22))
+    st = load().vba_init_imu_poses(C.c_int(m), _p(imu), _p(xc), _p(xl), C.c_double(beg_time), C.c_double(scale_gravity), _p(out))
+    if st:
+        raise VbaError(st)
+    return out
+
+
+def init_align_gravity(states):
+    """Initialization::align_gravity (voxelslam.cpp:470-497) on a copy of states [n][25]."""
+    xs = _c(states).copy()
+    st = load().vba_init_align_gravity(C.c_int(len(xs)), _p(xs))
+    if st:
+        raise VbaError(st)
+    return xs
 
 
 def _io_chk(st):
@@ -301,6 +322,39 @@ class Context:
         poses = np.empty((self.W, 12)); H = np.empty((n, n)); resis = np.zeros(2)
         self._chk(self.lib.vba_lm_end(self.h, _p(poses), _p(H), _p(resis)))
         return poses, H, resis
+
+    # ---- LiDAR-inertial initialisation (voxelslam.cpp:617-819)
+    def motion_init(self, clouds, curvs, imus_raw, beg_times, ext_pose12, dept_err, beam_err, scale_gravity, noise_meas, noise_walk,
+                    states, covs, imu_pre, point_notime=False, want_hess=False, want_pvec=True):
+        """Initialization::motion_init on the context's map and factor store.  clouds / curvs / imus_raw: per-scan lists ([n][3], [n],
+        [m][7]).  Returns a dict: converged, eigvalue3, iterations, thresholds_left_relaxed, round_log [rounds][5], states, imu_pre,
+        hess (want_hess), pvec (list of (pnt [k][3], var [k][3][3]) per scan, want_pvec)."""
+        W = len(clouds)
+        pto = np.zeros(W + 1, dtype=np.int32); imo = np.zeros(W + 1, dtype=np.int32)
+        pto[1:] = np.cumsum([len(x) for x in clouds]); imo[1:] = np.cumsum([len(x) for x in imus_raw])
+        pnt = _c(np.concatenate([np.reshape(x, (-1, 3)) for x in clouds])) if pto[-1] else np.zeros((1, 3))
+        cv = _c(np.concatenate([np.ravel(x) for x in curvs])) if pto[-1] else np.zeros(1)
+        imu = _c(np.concatenate([np.reshape(x, (-1, 7)) for x in imus_raw])) if imo[-1] else np.zeros((1, 7))
+        bt, ext, nm, nw = _c(beg_times), _c(ext_pose12), _c(noise_meas), _c(noise_walk)
+        xs = _c(states).copy(); cov = _c(covs); ip = _c(imu_pre).copy()
+        n = 15 * W + 3
+        H = np.zeros((n, n)) if want_hess else None
+        conv = C.c_int(0); iters = C.c_int(0); relax = C.c_int(0); eig = np.zeros(3); log = np.zeros((10, 5))
+        ip_ = C.POINTER(C.c_int)
+        pvo = np.zeros(W + 1, dtype=np.int32)
+        cap = int(pto[-1] + imo[-1]) + 1 if want_pvec else 0
+        po = np.zeros((cap, 3)) if want_pvec else None
+        vo = np.zeros((cap, 9)) if want_pvec else None
+        self._chk(self.lib.vba_motion_init(
+            self.h, C.c_int(W), pto.ctypes.data_as(ip_), _p(pnt), _p(cv), imo.ctypes.data_as(ip_), _p(imu), _p(bt), _p(ext),
+            C.c_double(dept_err), C.c_double(beam_err), C.c_double(scale_gravity), C.c_int(int(point_notime)), _p(nm), _p(nw),
+            _p(xs), _p(cov), _p(ip), _p(H), C.byref(conv), _p(eig), C.byref(iters), C.byref(relax), _p(log), C.c_int(10),
+            _p(po), _p(vo), pvo.ctypes.data_as(ip_), C.c_int(cap)))
+        out = dict(converged=conv.value, eigvalue3=eig, iterations=iters.value, thresholds_left_relaxed=relax.value,
+                   round_log=log[:iters.value].copy(), states=xs, imu_pre=ip, hess=H, pvec_offsets=pvo)
+        if want_pvec:
+            out["pvec"] = [(po[pvo[i]:pvo[i + 1]].copy(), vo[pvo[i]:pvo[i + 1]].reshape(-1, 3, 3).copy()) for i in range(W)]
+        return out
 
     # ---- voxel map
     def cut_voxel(self, win_count, pnt_body, pose12, var=None, multi=False):

@@ -1777,6 +1777,9 @@ struct MapStore {
   // sharded map: SUM all-reduce of n doubles in HBM over the ranks, stream-ordered (set by the context); d_gc = its 2-double scratch
   std::function<int(double *, size_t)> allreduce;
   double *d_gc = nullptr;
+  // per-call plane thresholds (vba_motion_init's relaxed values, VS:624-630): when set they replace opt's in every MapParams
+  bool thr_override = false;
+  double ovr_min_eigen_value = 0.0, ovr_plane_thre[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 inline void map_init(MapStore &s, const vba_options &o) {
@@ -1795,6 +1798,10 @@ inline MapParams map_params(const MapStore &s) {
   P.W = s.opt.win_size; P.max_layer = s.opt.max_layer; P.max_points = s.opt.max_points; P.thread_num = s.opt.thread_num;
   P.voxel_size = s.opt.voxel_size; P.min_eigen_value = s.opt.min_eigen_value;
   for (int i = 0; i < 4; i++) { P.plane_thre[i] = s.opt.plane_eigen_value_thre[i]; P.min_point[i] = s.opt.min_point[i]; }
+  if (s.thr_override) {
+    P.min_eigen_value = s.ovr_min_eigen_value;
+    for (int i = 0; i < 4; i++) P.plane_thre[i] = s.ovr_plane_thre[i];
+  }
   for (int i = 0; i < VBA_MAX_WIN; i++) P.mp[i] = s.mp[i];
   P.rank = s.rank; P.n_ranks = s.n_ranks;
   return P;

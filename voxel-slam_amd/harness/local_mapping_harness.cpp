@@ -10,6 +10,12 @@
 //           per scan : [n, x_curr (25 state doubles), x_curr.cov (225), n_imu] points[n][3] var_body[n][9]
 //                      imu samples of the interval BEFORE this scan: t[n_imu] gyr[n_imu][3] acc[n_imu][3]
 //           noise_meas[6] noise_walk[6]
+//   mode 3 (motion_init, VS:1524, then the steady-state loop of mode 1): after the header an initialisation block
+//           [point_notime, dept_err, beam_err, scale_gravity, extrin_para R(9) p(3)]
+//           per scan of the first win_size : [n, n_imu, beg_time, x_buf state (25), cov (225)] pnt[n][3] curvature[n] imu[n_imu][7]
+//           then the remaining n_scans - win_size scans in the per-scan layout above (their IMU samples use scale_gravity);
+//           output starts with [-2, converge_flag, iterations, thresholds_left_relaxed, eigvalue(3), W x 25 states], then as above
+//           (the first window record is the initialised window's step, VS:1951 reached with win_count = win_size)
 //   output: per optimised window [scan index, W x 25 states, v6[6]] ... then [-1, n_leaves] leaf dump [n][39] plane_var dump [n][86]
 #include "../../include/voxelba_adapter.hpp"
 #include <cmath>
@@ -62,34 +68,10 @@ int main(int argc, char **argv) {
     double jour = 0;
     // the noise globals of preintegration.hpp:8-9 travel at the end of the file
     const double *noise = &in[in.size() - 12];
+    double scale_gravity = 1.0;                  // imupre_scale_gravity (PI:9)
 
-    for (int k = 0; k < n_scans; k++) {
-      const int n = (int)next();
-      IMUST x_curr;
-      std::memcpy(&x_curr.t, &in.at(q), 25 * sizeof(double)); q += 25;
-      std::memcpy(x_curr.cov, &in.at(q), 225 * sizeof(double)); q += 225;
-      const int n_imu = (int)next();
-      std::shared_ptr<PVec> pptr(new PVec((size_t)n));
-      for (int i = 0; i < n; i++) { std::memcpy((*pptr)[i].pnt, &in.at(q), 24); q += 3; }
-      for (int i = 0; i < n; i++) { std::memcpy((*pptr)[i].var, &in.at(q), 72); q += 9; }
-      const double *imu_t = &in[q]; q += (size_t)n_imu;
-      const double *imu_g = &in[q]; q += (size_t)n_imu * 3;
-      const double *imu_a = &in[q]; q += (size_t)n_imu * 3;
-
-      // VS:1905-1913
-      win_count++;
-      x_buf.push_back(x_curr);
-      pvec_buf.push_back(pptr);
-      if (win_count > 1) {
-        imu_pre_buf.push_back(new IMU_PRE(x_buf[win_count - 2].bg, x_buf[win_count - 2].ba));
-        imu_pre_buf[win_count - 2]->push_imu(n_imu, imu_t, imu_g, imu_a, noise, noise + 6);
-      }
-      // VS:1918-1926: pvec_update (VS:1901) rides in the insert, as the device path fuses the two
-      voxhess.clear();
-      surf_map.pvec_update_cut_voxel_multi(*pvec_buf[win_count - 1], win_count - 1, x_curr);
-      surf_map.multi_recut(win_count, x_buf);
-
-      if (win_count >= win_size) {                               // VS:1951
+    // VS:1951-2043: optimise the full window, then marginalise and slide
+    auto window_step = [&](int k) {
         if (mode == 0) {                                         // lidar-only windows (what HBA_add_edge runs, VS:2895-2899)
           Lidar_BA_Optimizer opt_lsv;
           std::vector<double> resis;
@@ -127,7 +109,77 @@ int main(int argc, char **argv) {
         }
         win_base += mgsize;
         win_count -= mgsize;
+    };
+
+    int k_first = 0;
+    if (mode == 3) {                                             // VS:1450-1534: the window the initialisation collected
+      Initialization init;
+      init.point_notime = (int)next(); init.dept_err = next(); init.beam_err = next(); init.scale_gravity = scale_gravity = next();
+      std::memcpy(init.noise_meas, noise, 48); std::memcpy(init.noise_walk, noise + 6, 48);
+      IMUST extrin_para;
+      for (int i = 0; i < 9; i++) extrin_para.R[i] = next();
+      for (int i = 0; i < 3; i++) extrin_para.p[i] = next();
+      std::vector<std::vector<PointXYZC>> pl_origs(win_size);
+      std::vector<std::vector<ImuSample>> vec_imus(win_size);
+      std::vector<double> beg_times(win_size);
+      for (int i = 0; i < win_size; i++) {
+        const int n = (int)next(), n_imu = (int)next();
+        beg_times[i] = next();
+        IMUST x;
+        std::memcpy(&x.t, &in.at(q), 25 * sizeof(double)); q += 25;
+        std::memcpy(x.cov, &in.at(q), 225 * sizeof(double)); q += 225;
+        x_buf.push_back(x);
+        pl_origs[i].resize((size_t)n);
+        for (int j = 0; j < n; j++) { pl_origs[i][j].x = (float)next(); pl_origs[i][j].y = (float)next(); pl_origs[i][j].z = (float)next(); }
+        for (int j = 0; j < n; j++) pl_origs[i][j].curvature = (float)next();
+        vec_imus[i].resize((size_t)n_imu);
+        for (int j = 0; j < n_imu; j++) { std::memcpy(&vec_imus[i][j], &in.at(q), 7 * sizeof(double)); q += 7; }
       }
+      for (int i = 1; i < win_size; i++) {                       // imu_pre_buf as the accumulation leaves it (VS:1505-1509)
+        std::vector<double> t, g, a;
+        for (const ImuSample &m : vec_imus[i]) { t.push_back(m.t); g.insert(g.end(), m.gyr, m.gyr + 3); a.insert(a.end(), m.acc, m.acc + 3); }
+        imu_pre_buf.push_back(new IMU_PRE(x_buf[i - 1].bg, x_buf[i - 1].ba));
+        imu_pre_buf.back()->push_imu((int)t.size(), t.data(), g.data(), a.data(), noise, noise + 6, scale_gravity);
+      }
+      IMUST x_curr;
+      const int ok = init.motion_init(pl_origs, vec_imus, beg_times, &hess, voxhess, x_buf, surf_map, pvec_buf, win_size, x_curr, imu_pre_buf,
+                                      extrin_para);
+      out.push_back(-2.0); out.push_back(ok); out.push_back(init.iterations); out.push_back(init.thresholds_left_relaxed);
+      out.insert(out.end(), init.eigvalue, init.eigvalue + 3);
+      for (int i = 0; i < win_size; i++) out.insert(out.end(), &x_buf[i].t, &x_buf[i].t + 25);
+      if (!ok) throw std::runtime_error("motion_init did not converge");
+      win_count = win_size;
+      window_step(win_size - 1);                                 // VS:1951 with the initialised window
+      k_first = win_size;
+    }
+
+    for (int k = k_first; k < n_scans; k++) {
+      const int n = (int)next();
+      IMUST x_curr;
+      std::memcpy(&x_curr.t, &in.at(q), 25 * sizeof(double)); q += 25;
+      std::memcpy(x_curr.cov, &in.at(q), 225 * sizeof(double)); q += 225;
+      const int n_imu = (int)next();
+      std::shared_ptr<PVec> pptr(new PVec((size_t)n));
+      for (int i = 0; i < n; i++) { std::memcpy((*pptr)[i].pnt, &in.at(q), 24); q += 3; }
+      for (int i = 0; i < n; i++) { std::memcpy((*pptr)[i].var, &in.at(q), 72); q += 9; }
+      const double *imu_t = &in[q]; q += (size_t)n_imu;
+      const double *imu_g = &in[q]; q += (size_t)n_imu * 3;
+      const double *imu_a = &in[q]; q += (size_t)n_imu * 3;
+
+      // VS:1905-1913
+      win_count++;
+      x_buf.push_back(x_curr);
+      pvec_buf.push_back(pptr);
+      if (win_count > 1) {
+        imu_pre_buf.push_back(new IMU_PRE(x_buf[win_count - 2].bg, x_buf[win_count - 2].ba));
+        imu_pre_buf[win_count - 2]->push_imu(n_imu, imu_t, imu_g, imu_a, noise, noise + 6, scale_gravity);
+      }
+      // VS:1918-1926: pvec_update (VS:1901) rides in the insert, as the device path fuses the two
+      voxhess.clear();
+      surf_map.pvec_update_cut_voxel_multi(*pvec_buf[win_count - 1], win_count - 1, x_curr);
+      surf_map.multi_recut(win_count, x_buf);
+
+      if (win_count >= win_size) window_step(k);                // VS:1951
     }
     while (!imu_pre_buf.empty()) { delete imu_pre_buf.front(); imu_pre_buf.pop_front(); }
     // final map: leaves + plane covariances

@@ -274,3 +274,116 @@ def root_factors(points: List[np.ndarray], R: np.ndarray, p: np.ndarray, wl: Wor
     if with_keys:
         out["keys"] = np.ascontiguousarray(ukeys[sel])
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# Initialisation window (vba_motion_init, voxelslam.cpp:617-819): raw lidar-frame clouds whose points carry their own capture time
+# (PointType::curvature, ascending), distorted by the moving ground truth; per-scan IMU deques; perturbed states with a tilted,
+# mis-scaled gravity.
+
+def corridor_planes(length: float = 40.0, width: float = 3.0, height: float = 3.0):
+    """Floor, ceiling and two parallel walls along x, open ends: every normal is perpendicular to x (degenerate along x)."""
+    lo = np.array([-length / 2, -width / 2, 0.0])
+    hi = np.array([length / 2, width / 2, height])
+    return [(ax, float(c), lo.copy(), hi.copy()) for ax in (1, 2) for c in (lo[ax], hi[ax])]
+
+
+def _ray_cast_many(org: np.ndarray, dirs_w: np.ndarray, planes) -> np.ndarray:
+    """ray_cast with one origin per ray."""
+    t_best = np.full(dirs_w.shape[0], np.inf)
+    for ax, c, lo, hi in planes:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = (c - org[:, ax]) / dirs_w[:, ax]
+        ok = np.isfinite(t) & (t > 1e-3)
+        t = np.where(ok, t, 0.0)
+        hit = org + t[:, None] * dirs_w
+        for k in range(3):
+            if k != ax:
+                ok &= (hit[:, k] >= lo[k] - 1e-9) & (hit[:, k] <= hi[k] + 1e-9)
+        t_best = np.where(ok & (t < t_best), t, t_best)
+    return t_best
+
+
+def make_init_window(win_size: int = 10, n_pts: int = 20000, scene: str = "room", seed: int = SEED_BASE + 40,
+                     lead: Tuple[int, ...] = (3, -2), imu_rate: float = 200.0, scan_dt: float = 0.1, g_tilt_deg: float = 2.0,
+                     g_scale: float = 0.98, acc_unit_g: bool = True, ext_t: Tuple[float, float, float] = (0.04, 0.0, 0.03),
+                     range_noise: float = 0.005, yaw_rate: float = 0.3, pitch_amp: float = 0.05) -> dict:
+    """Returns dict(clouds, curvs, imus, beg_times, states, covs, ext, scale_gravity, gt_states).
+
+    State i sits at T_i = scan_dt * (i + 1); deque i holds the IMU samples of [T_{i-1}, T_i] (deque 0: [T_0 - scan_dt, T_0]), so the
+    pre-integration between states is consistent.  Scan i starts at beg_i = T_{i-1} + lead[i % len(lead)] / imu_rate and ends at T_i:
+    a positive lead puts IMU samples before beg_time (point 0 is pushed again for every older pose), a negative one starts the deque
+    after it (the points before the oldest pose are dropped)."""
+    rng = np.random.default_rng(seed)
+    if scene == "room":
+        planes = scene_planes(Workload("init_room", win_size, 0.5, n_pts, "spin32", (10.0, 8.0, 3.0), 2, seed))
+    elif scene == "corridor":
+        planes = corridor_planes()
+    else:
+        raise ValueError(scene)
+    G = 9.81
+    g_w = np.array([0.0, 0.0, -G])
+    vel = np.array([0.6, 0.25, 0.0])
+    p_start = np.array([-1.0, -0.3, 1.4])
+
+    def pose(t):   # yaw ramp + small pitch oscillation (the accelerometer then sees gravity from changing directions)
+        R = rot_z(yaw_rate * t) @ so3_exp(np.array([0.0, pitch_amp * math.sin(2.0 * math.pi * t), 0.0]))
+        return R, p_start + vel * t
+
+    def ang_vel_body(t, h=1e-5):
+        R0, _ = pose(t - h); R1, _ = pose(t + h)
+        S = R0.T @ R1
+        w = np.array([S[2, 1] - S[1, 2], S[0, 2] - S[2, 0], S[1, 0] - S[0, 1]]) * 0.5
+        return w / (2 * h)
+
+    def acc_body(t):
+        R, _ = pose(t)
+        return R.T @ (np.zeros(3) - g_w)     # constant velocity: specific force = -g
+
+    R_ext = np.eye(3)
+    t_ext = np.array(ext_t)
+    ext = np.concatenate([R_ext.ravel(), t_ext])
+    imu_dt = 1.0 / imu_rate
+    per = int(round(scan_dt * imu_rate))
+    T = scan_dt * (np.arange(win_size) + 1)
+    clouds, curvs, imus, begs = [], [], [], []
+    for i in range(win_size):
+        t_prev = T[i] - scan_dt
+        ts = t_prev + np.arange(per + 1) * imu_dt
+        gyr = np.stack([ang_vel_body(t) for t in ts])
+        acc = np.stack([acc_body(t) for t in ts]) / (G if acc_unit_g else 1.0)
+        imus.append(np.column_stack([ts, gyr, acc]))
+        beg = t_prev + lead[i % len(lead)] * imu_dt
+        begs.append(beg)
+        span = T[i] - beg
+        cv = np.sort(rng.uniform(0.0, span, n_pts).astype(np.float32)).astype(np.float64)
+        az = rng.uniform(-math.pi, math.pi, n_pts)
+        el = rng.uniform(math.radians(-30.0), math.radians(30.0), n_pts)
+        dirs = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], axis=1)
+        Rs, ps = zip(*[pose(beg + c) for c in cv])       # each point from the lidar pose at its own time
+        Rs, ps = np.stack(Rs), np.stack(ps)
+        org = np.einsum("nij,j->ni", Rs, t_ext) + ps
+        d_w = np.einsum("nij,nj->ni", Rs, dirs @ R_ext.T)
+        tt = _ray_cast_many(org, d_w, planes)
+        ok = np.isfinite(tt) & (tt > 0.3) & (tt < 80.0)
+        pts = dirs * (tt + rng.normal(0.0, range_noise, n_pts))[:, None]
+        clouds.append(pts[ok].astype(np.float32).astype(np.float64))
+        curvs.append(cv[ok])
+        begs[-1] = beg
+    gt = np.zeros((win_size, 25))
+    for i in range(win_size):
+        R, p = pose(T[i])
+        gt[i, 0] = T[i]; gt[i, 1:10] = R.ravel(); gt[i, 10:13] = p; gt[i, 13:16] = vel; gt[i, 22:25] = g_w
+    states = gt.copy()
+    tilt = so3_exp(np.array([math.radians(g_tilt_deg), -math.radians(g_tilt_deg) * 0.5, 0.0]))
+    for i in range(win_size):
+        if i > 0:
+            states[i, 1:10] = (gt[i, 1:10].reshape(3, 3) @ so3_exp(rng.normal(0.0, math.radians(0.2), 3))).ravel()
+            states[i, 10:13] = gt[i, 10:13] + rng.normal(0.0, 0.01, 3)
+        states[i, 13:16] = vel + rng.normal(0.0, 0.05, 3)
+        states[i, 22:25] = g_scale * (tilt @ g_w)
+    covs = np.zeros((win_size, 15, 15))
+    for i in range(win_size):
+        covs[i] = np.diag([1e-5] * 3 + [1e-4] * 3 + [1e-3] * 3 + [1e-6] * 6)
+    return dict(clouds=clouds, curvs=curvs, imus=imus, beg_times=np.array(begs), states=states, covs=covs.reshape(win_size, 225),
+                ext=ext, scale_gravity=G if acc_unit_g else 1.0, gt_states=gt)
