@@ -83,6 +83,15 @@ typedef struct vba_options {
   size_t max_map_nodes;             /* map capacity hints (0 = grow on demand): octree nodes and fixed (marginalised) points the map is */
   size_t max_fix_points;            /* sized for at the first insertion — a session that stays below them never re-allocates (no stalls) */
   int hba_workers;                  /* vba_hba_global on one rank: bottom-layer windows optimised side by side by this many worker contexts (0 = default 4, 1 = one after the other) */
+  /* != 0: deterministic mode.  Given identical inputs, options, call sequence and hessian_workgroups, every call
+     below returns bit-identical results in every run: node ids are handed out in a canonical order (new roots by the first input
+     point of their voxel, child blocks by parent id, free ids ascending), the factor store is ordered by (occupancy bucket, node
+     id), dumps list leaves by node id, down-sampling adds each voxel's points in input order; hessian_compact_tiles is ignored.
+     Covered: map insert / fixed insert / recut / extraction / margi / slide / prune / reset / dumps, acc_evaluate2,
+     evaluate_only_residual, the lidar, LI and LI-gravity damping_iter and lm_* entry points, both odometry variants, scan var_init /
+     down-sampling / undistortion, vba_motion_init.  NOT covered: vba_gba_build, vba_hba_* and the large-window store (they add with
+     f64 atomics), and multi-rank runs (the collective's order belongs to RCCL or the hook).  0 (default): today's kernels. */
+  int deterministic;
 } vba_options;
 
 void vba_default_options(vba_options *opt); /* values of config/avia.yaml:26-47 */

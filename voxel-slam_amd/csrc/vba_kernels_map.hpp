@@ -76,6 +76,8 @@ struct MapView {
   int cap;
   unsigned long long *nkey; int *nroot; int *nparent; int *nchild; int *npath; int *nopt; int *nflist /* factor index -> leaf (tras_opt order) */; int *nfl2 /* the same before the occupancy sort */; unsigned int *nfkey; int *fhist /* [EXTRACT_NB_MAX] */; int *nlast; int *nstamp; int *nsplit; int *ntake; int *nclear; int *ndead;
   int *nfree_root, *nfree_blk;   // stacks of recycled node ids: single root nodes / bases of 8-node child blocks (map_prune)
+  int *ndet, *dblk;              // deterministic mode: [cap] split flags of a recut level / [cap] per-workgroup counts of a compaction
+  unsigned int *hfirst;          // deterministic mode: [hash cap] smallest index of an input point of a root created by the current insert
   int *nseg_a, *nseg_b;          // [W][cap]: the points a scan slot gave to a leaf AT INSERTION = perm[slot][nseg_a .. nseg_b) (scan order)
   int *ncnt;                     // [cap] points of the scan being inserted per leaf, then the scatter cursor; zero between inserts
   int *nsl;                      // [cap] leaves split by the current recut level (margi: leaves whose oldest frame joins the fixed points)
@@ -203,6 +205,86 @@ __device__ __forceinline__ int alloc_nodes(const MapView &m, int which_cnt, cons
   return atomicAdd(&m.cnt[CNT_NODES], count);
 }
 
+// ------------------------------------------------------------------------------------------------ deterministic mode
+// Every id, list position and store position that the default kernels draw from a returning atomic is, in deterministic mode, the
+// rank of its owner in a STABLE COMPACTION: a count pass writes one count per 256-thread workgroup (dblk), k_det_scan turns the
+// counts into exclusive offsets (and the total into a counter), an emit pass adds the thread's rank inside its workgroup (ballot /
+// popcount in lane order, wave totals in LDS).  Owners are ranked by the index they are launched over (point index, node id).
+constexpr unsigned int DET_NONE = 0x7F7F7F7Fu;   // hfirst of a slot that no insert is creating a root in (a byte fill)
+
+// rank of a flagged thread among the flagged threads of its 256-thread workgroup (lane order) and the workgroup's count.  Every
+// thread of the workgroup must call it (it synchronises).
+__device__ __forceinline__ int det_wg_rank(bool f, int *wsum, int &tot) {
+  const unsigned long long mask = __ballot(f);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) wsum[wave] = __popcll(mask);
+  __syncthreads();
+  int before = 0;
+  tot = 0;
+  for (int w = 0; w < 4; w++) { const int c = wsum[w]; before += w < wave ? c : 0; tot += c; }
+  return before + __popcll(mask & ((1ull << lane) - 1ull));
+}
+__device__ __forceinline__ void det_count(bool f, int *wsum, int *blk) {
+  int tot;
+  det_wg_rank(f, wsum, tot);
+  if (threadIdx.x == 0) blk[blockIdx.x] = tot;
+}
+
+// Exclusive scan of a[0 .. n) in place by one workgroup of 1024: chunks of 8192 entries go through LDS (coalesced loads and stores;
+// thread t scans entries 8t .. 8t+7 of the chunk, wave shuffles and LDS combine the 1024 runs, a carry links the chunks); the total
+// goes to cnt[which_out] (which_out < 0: nowhere).  n = n_max, or (which_n >= 0) the number of 256-thread workgroups that covered
+// min(cnt[which_n], cap_n) items — workgroups beyond the live count return before they write their count.
+__global__ __launch_bounds__(1024) void k_det_scan(int *a, int n_max, int *cnt, int which_n, int cap_n, int which_out) {
+  constexpr int K = 8, CH = 1024 * K;
+  __shared__ int buf[CH];
+  __shared__ int wsum[16];
+  int n = n_max;
+  if (which_n >= 0) { const int c = cnt[which_n] < cap_n ? cnt[which_n] : cap_n; const int nb = (c + 255) / 256; n = nb < n_max ? nb : n_max; }
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int carry = 0;
+  for (int c0 = 0; c0 < n; c0 += CH) {
+#pragma unroll
+    for (int j = 0; j < K; j++) { const int i = c0 + j * 1024 + tid; buf[j * 1024 + tid] = i < n ? a[i] : 0; }
+    __syncthreads();
+    int v[K], loc = 0;
+#pragma unroll
+    for (int j = 0; j < K; j++) { v[j] = buf[tid * K + j]; loc += v[j]; }
+    int incl = loc;
+    for (int off = 1; off < 64; off <<= 1) { const int u = __shfl_up(incl, off, 64); if (lane >= off) incl += u; }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int run = carry + incl - loc, tot = 0;
+    for (int w = 0; w < 16; w++) { const int c = wsum[w]; run += w < wave ? c : 0; tot += c; }
+#pragma unroll
+    for (int j = 0; j < K; j++) { buf[tid * K + j] = run; run += v[j]; }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < K; j++) { const int i = c0 + j * 1024 + tid; if (i < n) a[i] = buf[j * 1024 + tid]; }
+    carry += tot;
+    __syncthreads();   // (buf and wsum are rewritten by the next chunk)
+  }
+  if (tid == 0 && which_out >= 0) cnt[which_out] = carry;
+}
+
+// After a ranked allocation of cnt[which_n] owners (r-th owner: the r-th entry from the top of the free stack, then fresh storage
+// of `unit` nodes each): the stack shrinks and the node count grows by what was taken from each.  Roots (unit 1) also update the
+// root counts k_ins_newroots bumps one by one; child blocks (unit 8) keep on the split list only the prefix that fitted in the
+// capacity (the rest set the overflow flag; the host grows the map and runs the pass again).
+__global__ void k_det_commit(MapView m, int which_n, int which_free, int unit, int is_fix) {
+  int *cnt = m.cnt;
+  const int R = cnt[which_n], F = cnt[which_free], take = R < F ? R : F, nodes = cnt[CNT_NODES];
+  cnt[which_free] = F - take;
+  cnt[CNT_NODES] = nodes + unit * (R - take);
+  if (unit == 1) {
+    cnt[CNT_ROOTS] += R;
+    if (!is_fix) { cnt[CNT_SLIDE] += R; cnt[CNT_TOUCH] += R; }
+  } else {
+    const long long room = nodes <= m.cap ? (long long)(m.cap - nodes) / unit : 0;
+    const long long ok = (long long)F + room;
+    if (ok < R) cnt[CNT_SPLIT] = (int)ok;
+  }
+}
+
 // The reference tests "#voxels < thread_num" on the whole map (VM:2044, VS:1616, VS:1693).  A sharded rank holds only its bucket
 // range, so those tests read the counts summed over the ranks (refreshed by a tiny all-reduce before the kernels that test them).
 __device__ __forceinline__ int slide_count(const MapView &m, const MapParams &P) { return P.n_ranks > 1 ? m.cnt[CNT_SLIDE_G] : m.cnt[CNT_SLIDE]; }
@@ -212,6 +294,9 @@ __global__ void k_f64_to_cnt(const double *in, int *cnt, int which) { cnt[which]
 
 // ------------------------------------------------------------------------------------------------ K1: insert
 // Phase 1: world transform, key, find-or-claim the hash slot of the root voxel.
+// DET: new slots are not listed here; a root created by this call is ranked by its first point (the smallest index among the points
+// that fall into it, an integer atomicMin per run of equal slots) and k_ins_newroots_det hands out its id.
+template <bool DET>
 __global__ __launch_bounds__(256) void k_ins_keys(MapView m, MapParams P, int slot, int n, int world_given, int stamp) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (!world_given) {   // the slot's previous occupant is gone: its insertion segments are cleared here (k_ins_scan writes the new ones)
@@ -277,7 +362,14 @@ __global__ __launch_bounds__(256) void k_ins_keys(MapView m, MapParams P, int sl
     }
     m.phash[p] = hslot;
   }
-  {  // the new slots join the list of k_ins_newroots: one returning atomic per wave (thousands of them on one address serialise in L2)
+  if (DET) {
+    // (hvals is only written by the next kernels: a slot without an id is a root this call creates)
+    const bool fresh = hslot >= 0 && m.hvals[hslot] < 0;
+    const int prev_h = __shfl_up(hslot, 1, 64);
+    if (fresh && ((threadIdx.x & 63) == 0 || prev_h != hslot)) atomicMin(&m.hfirst[hslot], (unsigned int)p);
+    const unsigned long long me = __ballot(claimed >= 0 && !(claimed & 0x40000000));   // formerly EMPTY slots (tombstones were counted)
+    if ((threadIdx.x & 63) == 0 && me) atomicAdd(&m.cnt[CNT_USED], __popcll(me));
+  } else {  // the new slots join the list of k_ins_newroots: one returning atomic per wave (thousands of them on one address serialise in L2)
     const unsigned long long mc = __ballot(claimed >= 0);
     if (mc) {
       const int ln = threadIdx.x & 63, lead = __ffsll((long long)mc) - 1;
@@ -329,6 +421,32 @@ __global__ void k_ins_newroots(MapView m, MapParams P, int is_fix, double jour, 
   }
   m.hvals[h] = id;
   atomicAdd(&m.cnt[CNT_ROOTS], 1);
+}
+
+// Phase 2, deterministic mode: one thread per POINT; the first point of each new root's voxel creates it.  PH 0 counts them per
+// workgroup, PH 1 gives the r-th one (in point order) the r-th id of the fixed sequence: the free-root stack from the top (it holds
+// the free ids in descending order, map_prune), then CNT_NODES, CNT_NODES + 1, ...  k_det_commit then moves the counters.
+template <int PH>
+__global__ __launch_bounds__(256) void k_ins_newroots_det(MapView m, MapParams P, int n, int is_fix, double jour, int stamp) {
+  __shared__ int wsum[4];
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  const int h = p < n ? m.phash[p] : -1;
+  const bool first = h >= 0 && m.hfirst[h] == (unsigned int)p;
+  if (PH == 0) { det_count(first, wsum, m.dblk); return; }
+  int tot;
+  const int r = m.dblk[blockIdx.x] + det_wg_rank(first, wsum, tot);
+  if (!first) return;
+  m.hfirst[h] = DET_NONE;
+  const int F = m.cnt[CNT_FREE_ROOTS];
+  const int id = r < F ? m.nfree_root[F - 1 - r] : m.cnt[CNT_NODES] + (r - F);
+  if (id >= m.cap) { atomicMax(&m.cnt[CNT_OVERFLOW], 1); return; }
+  long long kx, ky, kz;
+  const unsigned long long key = m.hkeys[h];
+  unpack_key(key, kx, ky, kz);
+  init_node(m, P.W, id, key, id, -1, 0, 0, (0.5 + kx) * P.voxel_size, (0.5 + ky) * P.voxel_size, (0.5 + kz) * P.voxel_size, (float)(P.voxel_size / 4.0));
+  if (is_fix) m.njour[id] = jour;   // VM:2147
+  else { m.f_exist[id] = 1; m.f_slide[id] = 1; m.nstamp[id] = stamp; }   // VM:2016-2017 (the counters: k_det_commit)
+  m.hvals[h] = id;
 }
 
 // Phase 3: descend to the leaf (OctoTree::allocate VM:1204-1237) and count the leaf's points.  Grouping by leaf needs no global
@@ -695,10 +813,30 @@ __device__ __forceinline__ bool in_scope(const MapView &m, const MapParams &P, i
   return m.f_slide[m.nroot[node]] != 0;
 }
 
+// children are created as a block of 8 at `base` (untouched octants stay empty leaves, which every traversal skips)
+__device__ __forceinline__ void subdivide_leaf(const MapView &m, const MapParams &P, int L, int epoch, int id, int base) {
+  const size_t cp = (size_t)m.cap;
+  const double cx = m.ncenter[id], cy = m.ncenter[cp + id], cz = m.ncenter[2 * cp + id];
+  const float ql = m.nql[id];
+  for (int o = 0; o < 8; o++) {
+    const int ox = o >> 2, oy = (o >> 1) & 1, oz = o & 1;
+    // VM:1227-1231: double + int * float
+    init_node(m, P.W, base + o, m.nkey[id], m.nroot[id], id, L + 1, (L == 0 ? o : m.npath[id] * 8 + o), cx + (2 * ox - 1) * ql, cy + (2 * oy - 1) * ql,
+              cz + (2 * oz - 1) * ql, ql / 2);
+  }
+  m.nchild[id] = base;
+  m.nsplit[id] = epoch;    // the point kernels of this pass move this leaf's points to the children
+  m.nstate[id] = 1;        // VM:1449
+  m.f_sw[id] = 0;          // sw->clear(); sws.push_back(sw); sw = nullptr  VM:1445-1447
+  for (int k = 0; k < 10 * P.W; k++) m.nlc[(size_t)id * 10 * P.W + k] = 0.0;
+}
+
 // One thread per node of layer L: leaf logic of OctoTree::recut VM:1399-1450.
 // The grid covers the node CAPACITY; the live range is the node count snapshotted on the device before the launch
 // (CNT_SNAP) — nodes created by this launch's own splits must not be visited by it, and reading the count back to size
 // the grid cost one ~18 us host round trip per level.
+// DET: a leaf that splits only raises its flag (ndet) and the workgroup writes its count; k_recut_split_det allocates in id order.
+template <bool DET>
 __global__ __launch_bounds__(256) void k_recut_leaf(MapView m, MapParams P, int L, int multi, int epoch) {
   __shared__ int wbase[4];
   const int id = blockIdx.x * blockDim.x + threadIdx.x;
@@ -725,24 +863,14 @@ __global__ __launch_bounds__(256) void k_recut_leaf(MapView m, MapParams P, int 
     const bool plane = (w0 < P.min_eigen_value) && ((w0 / w2) < P.plane_thre[L]);   // plane_judge VM:1194
     m.f_plane[id] = plane ? 1 : 0;
     if (plane || L >= P.max_layer) break;
+    if (DET) { m.ndet[id] = 1; split = true; break; }
     // subdivide: children are created as a block of 8 (untouched octants stay empty leaves, which every traversal skips)
     const int base = alloc_nodes(m, CNT_FREE_BLOCKS, m.nfree_blk, 8);
     if (base + 8 > m.cap) { atomicMax(&m.cnt[CNT_OVERFLOW], 1); break; }
-    const double cx = m.ncenter[id], cy = m.ncenter[cp + id], cz = m.ncenter[2 * cp + id];
-    const float ql = m.nql[id];
-    for (int o = 0; o < 8; o++) {
-      const int ox = o >> 2, oy = (o >> 1) & 1, oz = o & 1;
-      // VM:1227-1231: double + int * float
-      init_node(m, P.W, base + o, m.nkey[id], m.nroot[id], id, L + 1, (L == 0 ? o : m.npath[id] * 8 + o), cx + (2 * ox - 1) * ql, cy + (2 * oy - 1) * ql,
-                cz + (2 * oz - 1) * ql, ql / 2);
-    }
-    m.nchild[id] = base;
-    m.nsplit[id] = epoch;    // the point kernels of this pass move this leaf's points to the children
-    m.nstate[id] = 1;        // VM:1449
-    m.f_sw[id] = 0;          // sw->clear(); sws.push_back(sw); sw = nullptr  VM:1445-1447
-    for (int k = 0; k < 10 * P.W; k++) m.nlc[(size_t)id * 10 * P.W + k] = 0.0;
+    subdivide_leaf(m, P, L, epoch, id, base);
     split = true;
   } while (false);
+  if (DET) { det_count(split, wbase, m.dblk); return; }
   // the leaves this level split form the work list of k_recut_push (one returning atomic per workgroup; the order carries no meaning)
   const unsigned long long mask = __ballot(split);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -756,6 +884,26 @@ __global__ __launch_bounds__(256) void k_recut_leaf(MapView m, MapParams P, int 
   }
   __syncthreads();
   if (split) m.nsl[wbase[wave] + __popcll(mask & ((1ull << lane) - 1ull))] = id;
+}
+
+// Deterministic mode: the leaves this level splits, in ascending id; the r-th takes the r-th block of the fixed sequence (the free-block
+// stack from the top — free blocks in ascending order — then fresh storage) and is the r-th entry of the split list.  A block that
+// does not fit raises the overflow flag; k_det_commit cuts the split list to the blocks that fitted (a prefix: fresh bases grow with r).
+__global__ __launch_bounds__(256) void k_recut_split_det(MapView m, MapParams P, int L, int epoch) {
+  __shared__ int wsum[4];
+  const int id = blockIdx.x * blockDim.x + threadIdx.x;
+  const int nn = m.cnt[CNT_SNAP] < m.cap ? m.cnt[CNT_SNAP] : m.cap;
+  if ((int)(blockIdx.x * blockDim.x) >= nn) return;
+  const bool f = id < nn && m.ndet[id] != 0;
+  int tot;
+  const int r = m.dblk[blockIdx.x] + det_wg_rank(f, wsum, tot);
+  if (!f) return;
+  m.ndet[id] = 0;
+  const int FB = m.cnt[CNT_FREE_BLOCKS];
+  const int base = r < FB ? m.nfree_blk[FB - 1 - r] : m.cnt[CNT_NODES] + 8 * (r - FB);
+  if (base + 8 > m.cap) { atomicMax(&m.cnt[CNT_OVERFLOW], 1); return; }
+  subdivide_leaf(m, P, L, epoch, id, base);
+  m.nsl[r] = id;
 }
 
 // Window points of split leaves -> children, keyed with the CURRENT poses (subdivide VM:1307-1338 + push VM:1105-1143), in the
@@ -976,6 +1124,8 @@ __global__ __launch_bounds__(256) void k_recut_push(MapView m, MapParams P, int 
 
 // tras_opt VM:1605-1638, pass 1: assign factor indices.
 // (one returning atomic per workgroup on the factor counter, as k_margi_points)
+// DET 1 / 2 (deterministic mode): count per workgroup / factor index = rank in node-id order (k_det_scan between the two).
+template <int DET>
 __global__ __launch_bounds__(256) void k_extract_count(MapView m, MapParams P, int multi) {
   __shared__ int wbase[4];
   const int id = blockIdx.x * blockDim.x + threadIdx.x;
@@ -987,6 +1137,13 @@ __global__ __launch_bounds__(256) void k_extract_count(MapView m, MapParams P, i
   if (take && !(m.f_exist[id] && m.f_plane[id] && m.f_sw[id])) take = false;
   const size_t cp = (size_t)m.cap;
   if (take && neval_at(m, 0, id) / neval_at(m, 1, id) > 0.12) take = false;   // VM:1615
+  if (DET == 1) { det_count(take, wbase, m.dblk); return; }
+  if (DET == 2) {
+    int tot;
+    const int a = m.dblk[blockIdx.x] + det_wg_rank(take, wbase, tot);
+    if (take) { m.nopt[id] = a; m.nflist[a] = id; }
+    return;
+  }
   const unsigned long long mask = __ballot(take);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) wbase[wave] = __popcll(mask);
@@ -1013,7 +1170,10 @@ __global__ __launch_bounds__(256) void k_extract_count(MapView m, MapParams P, i
 // scatter.  Both atomic stages aggregate in LDS first: thousands of factors share the popular masks and returning atomics on one
 // address serialise in L2 (~10 ns each) — the direct form took 24 + 20 us for 18k factors.
 constexpr int EXTRACT_NB_MAX = 1024;
-__global__ __launch_bounds__(256) void k_extract_key(MapView m, MapParams P, int nfac, int nb) {
+// DET (deterministic mode): the workgroup's histogram goes to whist[bucket][workgroup] instead of the global one; k_det_scan over it
+// in (bucket, workgroup) order gives every workgroup its range per bucket, k_extract_scatter_det ranks in lane order: a stable sort.
+template <bool DET>
+__global__ __launch_bounds__(256) void k_extract_key(MapView m, MapParams P, int nfac, int nb, int *whist) {
   __shared__ int lh[EXTRACT_NB_MAX];
   for (int t = threadIdx.x; t < nb; t += 256) lh[t] = 0;
   __syncthreads();
@@ -1029,6 +1189,7 @@ __global__ __launch_bounds__(256) void k_extract_key(MapView m, MapParams P, int
     atomicAdd(&lh[key], 1);
   }
   __syncthreads();
+  if (DET) { for (int t = threadIdx.x; t < nb; t += 256) whist[(size_t)t * gridDim.x + blockIdx.x] = lh[t]; return; }
   for (int t = threadIdx.x; t < nb; t += 256) { const int c = lh[t]; if (c) atomicAdd(&m.fhist[t], c); }
 }
 __global__ __launch_bounds__(1024) void k_extract_scan(MapView m, int nbuckets) {   // fhist[k] <- number of factors with a smaller mask
@@ -1062,6 +1223,33 @@ __global__ __launch_bounds__(256) void k_extract_scatter(MapView m, int nfac, in
     m.nflist[pos] = id;
     m.nopt[id] = pos;                                        // opt_state  VM:1626
   }
+}
+__global__ __launch_bounds__(256) void k_extract_scatter_det(MapView m, const int *whist, int nfac, int nb) {
+  __shared__ int wc[4][EXTRACT_NB_MAX];      // per wave: factors of each bucket
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int a = blockIdx.x * blockDim.x + tid;
+  const bool act = a < nfac;
+  const unsigned int key = act ? m.nfkey[a] : 0u;
+  for (int t = tid; t < 4 * nb; t += 256) wc[t / nb][t % nb] = 0;
+  __syncthreads();
+  // the lanes of this wave with the same bucket: one ballot per distinct bucket of the wave
+  unsigned long long rem = __ballot(act), peers = 0;
+  while (rem) {
+    const int lead = __ffsll((long long)rem) - 1;
+    const unsigned int k = __shfl(key, lead, 64);
+    const bool mine = act && key == k;
+    const unsigned long long mk = __ballot(mine);
+    if (mine) peers = mk;
+    if (lane == lead) wc[wave][k] = __popcll(mk);
+    rem &= ~mk;
+  }
+  __syncthreads();
+  if (!act) return;
+  int pos = whist[(size_t)key * gridDim.x + blockIdx.x] + __popcll(peers & ((1ull << lane) - 1ull));
+  for (int w = 0; w < wave; w++) pos += wc[w][key];
+  const int id = m.nfl2[a];
+  m.nflist[pos] = id;
+  m.nopt[id] = pos;                                          // opt_state  VM:1626
 }
 // pass 2: write the SoA factor store (push_voxel VM:139-147), frames in ring order pcrs[i] = pcrs_local[mp[i]] VM:1623-1624.
 // A node's record (body clusters of all slots, fix, pcr) is contiguous, the store is component-major: a workgroup moves 32 factors
@@ -1421,11 +1609,14 @@ __global__ void k_prune_roots(MapView m, double jour, int dist, int epoch) {
 }
 // Freed nodes go onto the free stacks: an internal node hands back its child block, a root itself.  (Every node of a dead
 // subtree is visited: children are freed by their parent, so a child never pushes itself.)
+// (DET: no pushes; k_prune_free_det rebuilds both stacks afterwards)
+template <bool DET>
 __global__ void k_prune_nodes(MapView m, int epoch) {
   const int id = blockIdx.x * blockDim.x + threadIdx.x;
   const int nn = m.cnt[CNT_NODES] < m.cap ? m.cnt[CNT_NODES] : m.cap;
   if (id >= nn) return;
   if (m.nlayer[id] < 0 || m.ndead[m.nroot[id]] != epoch) return;
+  if (DET) { if (m.nroot[id] != id) m.nlayer[id] = -1; return; }
   if (m.nstate[id] == 1) { const int k = atomicAdd(&m.cnt[CNT_FREE_BLOCKS], 1); m.nfree_blk[k] = m.nchild[id]; }
   if (m.nroot[id] == id) { const int k = atomicAdd(&m.cnt[CNT_FREE_ROOTS], 1); m.nfree_root[k] = id; }
   else m.nlayer[id] = -1;                       // children first become unreachable ...
@@ -1435,6 +1626,24 @@ __global__ void k_prune_finish(MapView m, int epoch) {
   const int nn = m.cnt[CNT_NODES] < m.cap ? m.cnt[CNT_NODES] : m.cap;
   if (id >= nn) return;
   if (m.nroot[id] == id && m.ndead[id] == epoch && m.nlayer[id] >= 0) m.nlayer[id] = -1;   // ... then the roots themselves
+}
+// Deterministic mode: after pruning, the free stacks are rebuilt from scratch by one compaction over the nodes — every free root
+// (pruned, nroot == id) / every free block (pruned non-root whose octant is 0: the block's base), stored in DESCENDING order so that
+// the pops of the next insert / recut take them in ascending order.  KIND 0 roots, 1 blocks; PH 0 count, PH 1 emit.
+template <int KIND, int PH>
+__global__ __launch_bounds__(256) void k_prune_free_det(MapView m) {
+  __shared__ int wsum[4];
+  const int id = blockIdx.x * blockDim.x + threadIdx.x;
+  const int nn = m.cnt[CNT_NODES] < m.cap ? m.cnt[CNT_NODES] : m.cap;
+  if ((int)(blockIdx.x * blockDim.x) >= nn) return;
+  bool f = id < nn && m.nlayer[id] < 0;
+  if (f) f = KIND == 0 ? m.nroot[id] == id : (m.nroot[id] != id && (m.npath[id] & 7) == 0);
+  if (PH == 0) { det_count(f, wsum, m.dblk); return; }
+  int tot;
+  const int r = m.dblk[blockIdx.x] + det_wg_rank(f, wsum, tot);
+  if (!f) return;
+  const int F = m.cnt[KIND == 0 ? CNT_FREE_ROOTS : CNT_FREE_BLOCKS];
+  (KIND == 0 ? m.nfree_root : m.nfree_blk)[F - 1 - r] = id;
 }
 // The accumulators of a freed node are zeroed so that its next owner starts like fresh storage (which is zero-filled at
 // allocation): one thread per (node, row) of [pcr_add 10 | pcr_fix 10 | cov_add 45 | eig 12 | plane 43 | local clusters 10 W].
@@ -1582,14 +1791,29 @@ __global__ __launch_bounds__(256) void k_odom_match(MapView m, MapParams P, Odom
 }
 
 // ------------------------------------------------------------------------------------------------ dumps
-__global__ void k_dump_leaves(MapView m, double *out, int max_leaves) {
+__device__ __forceinline__ bool dump_row(const MapView &m, int id, int nn) {
+  if (id >= nn) return false;
+  if (m.nstate[id] != 0 || m.nlayer[id] < 0) return false;  // internal node, or pruned
+  return !(m.nlayer[id] > 0 && !m.f_touched[id]);          // never-touched octants do not exist in the reference tree
+}
+// row of a dumped leaf: arrival order (DET 0), or (deterministic mode) count per workgroup (DET 1) / rank in node-id order (DET 2)
+template <int DET>
+__device__ __forceinline__ int dump_slot(const MapView &m, int id, int nn, int *wsum) {
+  const bool f = dump_row(m, id, nn);
+  if (DET == 0) return f ? atomicAdd(&m.cnt[CNT_LEAVES], 1) : -1;
+  if (DET == 1) { det_count(f, wsum, m.dblk); return -1; }
+  int tot;
+  const int r = m.dblk[blockIdx.x] + det_wg_rank(f, wsum, tot);
+  return f ? r : -1;
+}
+template <int DET>
+__global__ __launch_bounds__(256) void k_dump_leaves(MapView m, double *out, int max_leaves) {
+  __shared__ int wsum[4];
   const int id = blockIdx.x * blockDim.x + threadIdx.x;
   const int nn = m.cnt[CNT_NODES] < m.cap ? m.cnt[CNT_NODES] : m.cap;
-  if (id >= nn) return;
-  if (m.nstate[id] != 0 || m.nlayer[id] < 0) return;  // internal node, or pruned
-  if (m.nlayer[id] > 0 && !m.f_touched[id]) return;   // never-touched octants do not exist in the reference tree
-  const int i = atomicAdd(&m.cnt[CNT_LEAVES], 1);
-  if (i >= max_leaves) return;
+  if ((int)(blockIdx.x * blockDim.x) >= nn) return;
+  const int i = dump_slot<DET>(m, id, nn, wsum);
+  if (i < 0 || i >= max_leaves) return;
   const size_t cp = (size_t)m.cap;
   double *o = out + (size_t)i * 39;
   long long kx, ky, kz;
@@ -1604,14 +1828,14 @@ __global__ void k_dump_leaves(MapView m, double *out, int max_leaves) {
 
 // plane.plane_var (6x6, VM:1356-1383) and cov_add (9x9 symmetric, upper triangle; VM:106-121, 1138-1140) of every leaf, keyed like
 // k_dump_leaves: [kx,ky,kz, layer, path, plane_var(36 row-major), cov_add upper triangle (45)] = 86 doubles.
-__global__ void k_dump_plane_var(MapView m, double *out, int max_leaves) {
+template <int DET>
+__global__ __launch_bounds__(256) void k_dump_plane_var(MapView m, double *out, int max_leaves) {
+  __shared__ int wsum[4];
   const int id = blockIdx.x * blockDim.x + threadIdx.x;
   const int nn = m.cnt[CNT_NODES] < m.cap ? m.cnt[CNT_NODES] : m.cap;
-  if (id >= nn) return;
-  if (m.nstate[id] != 0 || m.nlayer[id] < 0) return;
-  if (m.nlayer[id] > 0 && !m.f_touched[id]) return;
-  const int i = atomicAdd(&m.cnt[CNT_LEAVES], 1);
-  if (i >= max_leaves) return;
+  if ((int)(blockIdx.x * blockDim.x) >= nn) return;
+  const int i = dump_slot<DET>(m, id, nn, wsum);
+  if (i < 0 || i >= max_leaves) return;
   const size_t cp = (size_t)m.cap;
   double *o = out + (size_t)i * 86;
   long long kx, ky, kz;
@@ -1780,10 +2004,14 @@ struct MapStore {
   // per-call plane thresholds (vba_motion_init's relaxed values, VS:624-630): when set they replace opt's in every MapParams
   bool thr_override = false;
   double ovr_min_eigen_value = 0.0, ovr_plane_thre[4] = {0.0, 0.0, 0.0, 0.0};
+  // deterministic mode (vba_options::deterministic); d_whist = the per-workgroup bucket histograms of the stable sort
+  bool det = false;
+  int *d_whist = nullptr; size_t whist_cap = 0;
 };
 
 inline void map_init(MapStore &s, const vba_options &o) {
   s.opt = o;
+  s.det = o.deterministic != 0;
   for (int i = 0; i < VBA_MAX_WIN; i++) { s.mp[i] = i; s.npts[i] = 0; }   // VS:3158-3160
 }
 
@@ -1811,7 +2039,7 @@ inline std::vector<DevArr> node_arrays(MapView &v, int W) {
   return {
       {(void **)&v.nkey, 8, 1}, {(void **)&v.nroot, 4, 1}, {(void **)&v.nparent, 4, 1}, {(void **)&v.nchild, 4, 1}, {(void **)&v.npath, 4, 1},
       {(void **)&v.nopt, 4, 1}, {(void **)&v.nflist, 4, 1}, {(void **)&v.nfl2, 4, 1}, {(void **)&v.nfkey, 4, 1}, {(void **)&v.nlast, 4, 1}, {(void **)&v.nstamp, 4, 1}, {(void **)&v.nsplit, 4, 1}, {(void **)&v.ntake, 4, 1},
-      {(void **)&v.nclear, 4, 1}, {(void **)&v.ndead, 4, 1}, {(void **)&v.nfree_root, 4, 1}, {(void **)&v.nfree_blk, 4, 1},
+      {(void **)&v.nclear, 4, 1}, {(void **)&v.ndead, 4, 1}, {(void **)&v.nfree_root, 4, 1}, {(void **)&v.nfree_blk, 4, 1}, {(void **)&v.ndet, 4, 1}, {(void **)&v.dblk, 4, 1},
       {(void **)&v.nseg_a, 4, (size_t)W}, {(void **)&v.nseg_b, 4, (size_t)W}, {(void **)&v.nsl, 4, 1}, {(void **)&v.ncnt, 4, 1}, {(void **)&v.nfb_head, 4, 1}, {(void **)&v.nfb_tail, 4, 1}, {(void **)&v.nlayer, 1, 1}, {(void **)&v.nstate, 1, 1}, {(void **)&v.f_exist, 1, 1},
       {(void **)&v.f_sw, 1, 1}, {(void **)&v.f_plane, 1, 1}, {(void **)&v.f_touched, 1, 1}, {(void **)&v.f_slide, 4, 1}, {(void **)&v.nql, 4, 1},
       {(void **)&v.ncenter, 8, 3}, {(void **)&v.njour, 8, 1}, {(void **)&v.nadd, 80, 1}, {(void **)&v.nfix, 80, 1}, {(void **)&v.ncov, 360, 1},
@@ -1858,6 +2086,13 @@ inline int map_hash_alloc(MapStore &s, unsigned int cap, hipStream_t st, std::st
   unsigned long long *nk = nullptr; int *nv = nullptr;
   MAPCHK(hipMalloc((void **)&nk, (size_t)cap * 8));
   MAPCHK(hipMalloc((void **)&nv, (size_t)cap * 4));
+  if (s.det) {   // (no insert is in flight between calls: every slot reads DET_NONE)
+    unsigned int *nf = nullptr;
+    MAPCHK(hipMalloc((void **)&nf, (size_t)cap * 4));
+    MAPCHK(hipMemsetAsync(nf, 0x7F, (size_t)cap * 4, st));
+    if (s.v.hfirst) { MAPCHK(hipStreamSynchronize(st)); hipFree(s.v.hfirst); }
+    s.v.hfirst = nf;
+  }
   hipLaunchKernelGGL(k_fill_u64, dim3(1024), dim3(256), 0, st, nk, KEY_EMPTY, (size_t)cap);
   MAPCHK(hipMemsetAsync(nv, 0xFF, (size_t)cap * 4, st));
   if (s.v.hkeys) {
@@ -1946,6 +2181,8 @@ inline void map_free(MapStore &s) {
   for (auto &a : fix_arrays(s.v)) if (*a.slot) hipFree(*a.slot);
   if (s.v.hkeys) hipFree(s.v.hkeys);
   if (s.v.hvals) hipFree(s.v.hvals);
+  if (s.v.hfirst) hipFree(s.v.hfirst);
+  if (s.d_whist) { hipFree(s.d_whist); s.d_whist = nullptr; s.whist_cap = 0; }
   if (s.v.cnt) hipFree(s.v.cnt);
   if (s.v.fhist) hipFree(s.v.fhist);
   if (s.v.poses) hipFree(s.v.poses);
@@ -2011,6 +2248,21 @@ inline unsigned int map_key_bits(const MapStore &s) {
   return bits;
 }
 
+// phases 1-2 of an insertion of n points (root keys, new roots); deterministic mode ranks the new roots by their first point
+inline void map_ins_roots(MapStore &s, hipStream_t st, const MapParams &P, int slot, int n, int is_fix, double jour, int stamp) {
+  const int nb = (n + 255) / 256;
+  if (!s.det) {
+    hipLaunchKernelGGL(k_ins_keys<false>, dim3(nb), dim3(256), 0, st, s.v, P, slot, n, is_fix, stamp);
+    hipLaunchKernelGGL(k_ins_newroots, dim3(nb), dim3(256), 0, st, s.v, P, is_fix, jour, stamp);
+    return;
+  }
+  hipLaunchKernelGGL(k_ins_keys<true>, dim3(nb), dim3(256), 0, st, s.v, P, slot, n, is_fix, stamp);
+  hipLaunchKernelGGL(k_ins_newroots_det<0>, dim3(nb), dim3(256), 0, st, s.v, P, n, is_fix, jour, stamp);
+  hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(1024), 0, st, s.v.dblk, nb, s.v.cnt, -1, 0, (int)CNT_NEWSLOTS);
+  hipLaunchKernelGGL(k_ins_newroots_det<1>, dim3(nb), dim3(256), 0, st, s.v, P, n, is_fix, jour, stamp);
+  hipLaunchKernelGGL(k_det_commit, dim3(1), dim3(1), 0, st, s.v, (int)CNT_NEWSLOTS, (int)CNT_FREE_ROOTS, 1, is_fix);
+}
+
 // cut_voxel / cut_voxel_multi for one scan
 inline int map_cut_voxel(MapStore &s, hipStream_t st, int win_count, int n, const double *pnt_body, const double *var, const double *pose,
                          bool multi, std::string &err, const double *cov6 = nullptr) {
@@ -2057,8 +2309,7 @@ inline int map_cut_voxel(MapStore &s, hipStream_t st, int win_count, int n, cons
   if (cov6 && var) hipLaunchKernelGGL(k_scan_to_soa_pvec_update, dim3(nb), dim3(256), 0, st, s.v, W, slot, n, d_pts, d_var, s.v.poses, s.v.poses + 16);
   else hipLaunchKernelGGL(k_scan_to_soa, dim3(nb), dim3(256), 0, st, s.v, W, slot, n, d_pts, d_var);
   s.stamp++;
-  hipLaunchKernelGGL(k_ins_keys, dim3(nb), dim3(256), 0, st, s.v, P, slot, n, 0, s.stamp);
-  hipLaunchKernelGGL(k_ins_newroots, dim3(nb), dim3(256), 0, st, s.v, P, 0, 0.0, s.stamp);
+  map_ins_roots(s, st, P, slot, n, 0, 0.0, s.stamp);
   if (multi) { r = map_global_count(s, st, CNT_TOUCH, CNT_TOUCH_G, err); if (r) return r; }   // VM:2044 tests the whole scan's voxel count
   // order-preserving accumulation: leaf of every point + per-leaf counts -> segments (scan over the touched leaves) -> scatter ->
   // one wave (workgroup for big leaves) per leaf puts its segment into scan order and adds in that order
@@ -2117,8 +2368,7 @@ inline int map_cut_voxel_fix(MapStore &s, hipStream_t st, int n, const double *p
   hipLaunchKernelGGL(k_fix_to_soa, dim3(nb), dim3(256), 0, st, s.v, base, n, d_pts);
   r = map_set_counter(s, st, CNT_NEWSLOTS, 0, err); if (r) return r;
   r = map_set_counter(s, st, CNT_FIX, base + n, err); if (r) return r;
-  hipLaunchKernelGGL(k_ins_keys, dim3(nb), dim3(256), 0, st, s.v, P, base, n, 1, 0);
-  hipLaunchKernelGGL(k_ins_newroots, dim3(nb), dim3(256), 0, st, s.v, P, 1, jour, 0);
+  map_ins_roots(s, st, P, base, n, 1, jour, 0);
   r = map_sort_reserve(s, st, err); if (r) return r;
   r = map_set_counter(s, st, CNT_WL, 0, err); if (r) return r;
   hipLaunchKernelGGL(k_fix_leaf, dim3(nb), dim3(256), 0, st, s.v, P, base, n);
@@ -2161,7 +2411,14 @@ inline int map_recut(MapStore &s, hipStream_t st, int win_count, const double *p
       for (int L = 0; L <= s.opt.max_layer; L++) {
         s.epoch++;
         hipLaunchKernelGGL(k_recut_prep, dim3(1), dim3(1), 0, st, s.v.cnt, L == 0 ? 1 : 0, L == s.opt.max_layer ? 1 : 0);
-        hipLaunchKernelGGL(k_recut_leaf, dim3(grid_nodes), dim3(256), 0, st, s.v, P, L, multi ? 1 : 0, s.epoch);
+        if (s.det) {
+          hipLaunchKernelGGL(k_recut_leaf<true>, dim3(grid_nodes), dim3(256), 0, st, s.v, P, L, multi ? 1 : 0, s.epoch);
+          hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(1024), 0, st, s.v.dblk, grid_nodes, s.v.cnt, (int)CNT_SNAP, s.v.cap, (int)CNT_SPLIT);
+          hipLaunchKernelGGL(k_recut_split_det, dim3(grid_nodes), dim3(256), 0, st, s.v, P, L, s.epoch);
+          hipLaunchKernelGGL(k_det_commit, dim3(1), dim3(1), 0, st, s.v, (int)CNT_SPLIT, (int)CNT_FREE_BLOCKS, 8, 0);
+        } else {
+          hipLaunchKernelGGL(k_recut_leaf<false>, dim3(grid_nodes), dim3(256), 0, st, s.v, P, L, multi ? 1 : 0, s.epoch);
+        }
         if (L < s.opt.max_layer) {
           if (s.have_var) hipLaunchKernelGGL((k_recut_push<true>), dim3(4096), dim3(256), 0, st, s.v, P, win_count, L + 1);
           else hipLaunchKernelGGL((k_recut_push<false>), dim3(4096), dim3(256), 0, st, s.v, P, win_count, L + 1);
@@ -2178,7 +2435,13 @@ inline int map_recut(MapStore &s, hipStream_t st, int win_count, const double *p
 #endif
       }
       // tras_opt pass 1 rides in the same submission: one counter read-back serves the overflow check and the factor count
-      hipLaunchKernelGGL(k_extract_count, dim3(grid_nodes), dim3(256), 0, st, s.v, P, multi ? 1 : 0);
+      if (s.det) {
+        hipLaunchKernelGGL(k_extract_count<1>, dim3(grid_nodes), dim3(256), 0, st, s.v, P, multi ? 1 : 0);
+        hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(1024), 0, st, s.v.dblk, grid_nodes, s.v.cnt, (int)CNT_NODES, s.v.cap, (int)CNT_FACTORS);
+        hipLaunchKernelGGL(k_extract_count<2>, dim3(grid_nodes), dim3(256), 0, st, s.v, P, multi ? 1 : 0);
+      } else {
+        hipLaunchKernelGGL(k_extract_count<0>, dim3(grid_nodes), dim3(256), 0, st, s.v, P, multi ? 1 : 0);
+      }
     }
     MAPCHK(hipGetLastError());
     r = map_read_counters(s, st, err);
@@ -2202,10 +2465,25 @@ inline int map_extract_factors(MapStore &s, hipStream_t st, FactorView f, std::s
   const int nfac = s.h_cnt[CNT_NODES] > 0 ? s.h_cnt[CNT_FACTORS] : 0;
   if (nfac > 1) {
     const int nbuckets = 1 << (s.opt.win_size < 10 ? s.opt.win_size : 10);
-    MAPCHK(hipMemsetAsync(s.v.fhist, 0, (size_t)nbuckets * sizeof(int), st));
-    hipLaunchKernelGGL(k_extract_key, dim3((nfac + 255) / 256), dim3(256), 0, st, s.v, P, nfac, nbuckets);
-    hipLaunchKernelGGL(k_extract_scan, dim3(1), dim3(1024), 0, st, s.v, nbuckets);
-    hipLaunchKernelGGL(k_extract_scatter, dim3((nfac + 255) / 256), dim3(256), 0, st, s.v, nfac, nbuckets);
+    const int nwg = (nfac + 255) / 256;
+    if (s.det) {   // stable: (bucket, node id)
+      const size_t need = (size_t)nbuckets * nwg;
+      if (need > s.whist_cap) {
+        MAPCHK(hipStreamSynchronize(st));
+        if (s.d_whist) hipFree(s.d_whist);
+        s.d_whist = nullptr; s.whist_cap = 0;
+        MAPCHK(hipMalloc((void **)&s.d_whist, need * sizeof(int)));
+        s.whist_cap = need;
+      }
+      hipLaunchKernelGGL(k_extract_key<true>, dim3(nwg), dim3(256), 0, st, s.v, P, nfac, nbuckets, s.d_whist);
+      hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(1024), 0, st, s.d_whist, (int)need, s.v.cnt, -1, 0, -1);
+      hipLaunchKernelGGL(k_extract_scatter_det, dim3(nwg), dim3(256), 0, st, s.v, (const int *)s.d_whist, nfac, nbuckets);
+    } else {
+      MAPCHK(hipMemsetAsync(s.v.fhist, 0, (size_t)nbuckets * sizeof(int), st));
+      hipLaunchKernelGGL(k_extract_key<false>, dim3(nwg), dim3(256), 0, st, s.v, P, nfac, nbuckets, (int *)nullptr);
+      hipLaunchKernelGGL(k_extract_scan, dim3(1), dim3(1024), 0, st, s.v, nbuckets);
+      hipLaunchKernelGGL(k_extract_scatter, dim3(nwg), dim3(256), 0, st, s.v, nfac, nbuckets);
+    }
   }
   if (nfac > 0) hipLaunchKernelGGL(k_extract_write, dim3((nfac + XW_F - 1) / XW_F), dim3(256), (size_t)(10 * s.opt.win_size + 33) * (XW_F + 1) * 8, st, s.v, P, f, nfac);
   MAPCHK(hipGetLastError());
@@ -2269,6 +2547,7 @@ inline int map_reset(MapStore &s, hipStream_t st, std::string &err) {
   if (s.v.fnode) MAPCHK(hipMemsetAsync(s.v.fnode, 0xFF, (size_t)s.v.cap_fix * 4, st));
   hipLaunchKernelGGL(k_fill_u64, dim3(1024), dim3(256), 0, st, s.v.hkeys, KEY_EMPTY, (size_t)s.hcap);
   MAPCHK(hipMemsetAsync(s.v.hvals, 0xFF, (size_t)s.hcap * 4, st));
+  if (s.v.hfirst) MAPCHK(hipMemsetAsync(s.v.hfirst, 0x7F, (size_t)s.hcap * 4, st));
   MAPCHK(hipMemsetAsync(s.v.cnt, 0, CNT_N * sizeof(int), st));
   MAPCHK(hipStreamSynchronize(st));
   std::memset(s.h_cnt, 0, CNT_N * sizeof(int));
@@ -2305,7 +2584,13 @@ inline int map_dump_leaves(MapStore &s, hipStream_t st, double *out, int max_lea
   double *d_out = nullptr;
   if (cap_out > 0 && hipMalloc((void **)&d_out, (size_t)cap_out * 39 * 8) != hipSuccess) return -1;
   if (map_set_counter(s, st, CNT_LEAVES, 0, err)) return -1;
-  hipLaunchKernelGGL(k_dump_leaves, dim3((nn + 255) / 256), dim3(256), 0, st, s.v, d_out, cap_out);
+  if (s.det) {   // rows in ascending node id
+    hipLaunchKernelGGL(k_dump_leaves<1>, dim3((nn + 255) / 256), dim3(256), 0, st, s.v, d_out, cap_out);
+    hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(1024), 0, st, s.v.dblk, (nn + 255) / 256, s.v.cnt, -1, 0, (int)CNT_LEAVES);
+    hipLaunchKernelGGL(k_dump_leaves<2>, dim3((nn + 255) / 256), dim3(256), 0, st, s.v, d_out, cap_out);
+  } else {
+    hipLaunchKernelGGL(k_dump_leaves<0>, dim3((nn + 255) / 256), dim3(256), 0, st, s.v, d_out, cap_out);
+  }
   if (map_read_counters(s, st, err)) return -1;
   const int n = s.h_cnt[CNT_LEAVES];
   if (cap_out > 0) {
@@ -2324,7 +2609,13 @@ inline int map_dump_plane_var(MapStore &s, hipStream_t st, double *out, int max_
   double *d_out = nullptr;
   if (cap_out > 0 && hipMalloc((void **)&d_out, (size_t)cap_out * 86 * 8) != hipSuccess) return -1;
   if (map_set_counter(s, st, CNT_LEAVES, 0, err)) return -1;
-  hipLaunchKernelGGL(k_dump_plane_var, dim3((nn + 255) / 256), dim3(256), 0, st, s.v, d_out, cap_out);
+  if (s.det) {   // rows in ascending node id
+    hipLaunchKernelGGL(k_dump_plane_var<1>, dim3((nn + 255) / 256), dim3(256), 0, st, s.v, d_out, cap_out);
+    hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(1024), 0, st, s.v.dblk, (nn + 255) / 256, s.v.cnt, -1, 0, (int)CNT_LEAVES);
+    hipLaunchKernelGGL(k_dump_plane_var<2>, dim3((nn + 255) / 256), dim3(256), 0, st, s.v, d_out, cap_out);
+  } else {
+    hipLaunchKernelGGL(k_dump_plane_var<0>, dim3((nn + 255) / 256), dim3(256), 0, st, s.v, d_out, cap_out);
+  }
   if (map_read_counters(s, st, err)) return -1;
   const int n = s.h_cnt[CNT_LEAVES];
   if (cap_out > 0) {
@@ -2342,8 +2633,18 @@ inline int map_prune(MapStore &s, hipStream_t st, double jour, int dist, std::st
   if (nn == 0) return VBA_OK;
   s.epoch++;
   hipLaunchKernelGGL(k_prune_roots, dim3((s.hcap + 255) / 256), dim3(256), 0, st, s.v, jour, dist, s.epoch);
-  hipLaunchKernelGGL(k_prune_nodes, dim3((nn + 255) / 256), dim3(256), 0, st, s.v, s.epoch);
+  if (s.det) hipLaunchKernelGGL(k_prune_nodes<true>, dim3((nn + 255) / 256), dim3(256), 0, st, s.v, s.epoch);
+  else hipLaunchKernelGGL(k_prune_nodes<false>, dim3((nn + 255) / 256), dim3(256), 0, st, s.v, s.epoch);
   hipLaunchKernelGGL(k_prune_finish, dim3((nn + 255) / 256), dim3(256), 0, st, s.v, s.epoch);
+  if (s.det) {   // both free stacks rebuilt in id order (descending, so that the pops come out ascending)
+    const int nb = (nn + 255) / 256;
+    hipLaunchKernelGGL((k_prune_free_det<0, 0>), dim3(nb), dim3(256), 0, st, s.v);
+    hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(1024), 0, st, s.v.dblk, nb, s.v.cnt, -1, 0, (int)CNT_FREE_ROOTS);
+    hipLaunchKernelGGL((k_prune_free_det<0, 1>), dim3(nb), dim3(256), 0, st, s.v);
+    hipLaunchKernelGGL((k_prune_free_det<1, 0>), dim3(nb), dim3(256), 0, st, s.v);
+    hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(1024), 0, st, s.v.dblk, nb, s.v.cnt, -1, 0, (int)CNT_FREE_BLOCKS);
+    hipLaunchKernelGGL((k_prune_free_det<1, 1>), dim3(nb), dim3(256), 0, st, s.v);
+  }
   hipLaunchKernelGGL(k_prune_zero, dim3((nn + 255) / 256, 130 + 10 * s.opt.win_size), dim3(256), 0, st, s.v, s.opt.win_size, s.epoch);
   if (s.h_cnt[CNT_FIX] > 0) hipLaunchKernelGGL(k_prune_fix, dim3((s.h_cnt[CNT_FIX] + 255) / 256), dim3(256), 0, st, s.v);
   MAPCHK(hipGetLastError());

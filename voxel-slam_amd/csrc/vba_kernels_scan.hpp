@@ -40,6 +40,8 @@ __global__ void k_ds_clear(DsSlot *__restrict__ tab, int cap) {
 
 // point -> slot (open addressing, linear probing), sums, count, first point of the voxel
 // var != nullptr: pointVar input (down_sampling_pvec, VM:39-83): double coordinates, the covariance diagonal is averaged too
+// DET (deterministic mode): no f64 atomics; the sums are added by k_ds_sum_det in input order
+template <bool DET>
 __global__ void k_ds_insert(int n, const double *__restrict__ pnt, const double *__restrict__ var, double voxel_size, DsSlot *__restrict__ tab, int cap_mask,
                             int *__restrict__ slot_of) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -53,13 +55,45 @@ __global__ void k_ds_insert(int n, const double *__restrict__ pnt, const double 
     if (old == DS_EMPTY || old == key) break;
     h = (h + 1) & cap_mask;
   }
-  atomicAdd(&tab[h].sx, dbl ? x : (double)(float)x);
-  atomicAdd(&tab[h].sy, dbl ? y : (double)(float)y);
-  atomicAdd(&tab[h].sz, dbl ? z : (double)(float)z);
-  if (dbl) { atomicAdd(&tab[h].vx, var[9 * (size_t)i]); atomicAdd(&tab[h].vy, var[9 * (size_t)i + 4]); atomicAdd(&tab[h].vz, var[9 * (size_t)i + 8]); }
+  if (!DET) {
+    atomicAdd(&tab[h].sx, dbl ? x : (double)(float)x);
+    atomicAdd(&tab[h].sy, dbl ? y : (double)(float)y);
+    atomicAdd(&tab[h].sz, dbl ? z : (double)(float)z);
+    if (dbl) { atomicAdd(&tab[h].vx, var[9 * (size_t)i]); atomicAdd(&tab[h].vy, var[9 * (size_t)i + 4]); atomicAdd(&tab[h].vz, var[9 * (size_t)i + 8]); }
+  }
   atomicAdd(&tab[h].cnt, 1);
   atomicMin(&tab[h].first, i);
   slot_of[i] = h;
+}
+
+// Deterministic mode: the points are grouped by voxel with a stable radix sort of (slot, index) pairs (index order survives inside a
+// group); k_ds_segstart marks where each voxel's group starts (in DsSlot::pad), k_ds_sum_det lets the voxel's first point add the
+// group's coordinates (and covariance diagonals) in index order, as the chains the host replays: ((0 + a_0) + a_1) + ...
+__global__ void k_iota(int *__restrict__ a, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) a[i] = i;
+}
+__global__ void k_ds_segstart(int n, const unsigned int *__restrict__ skey, DsSlot *__restrict__ tab) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  if (j == 0 || skey[j] != skey[j - 1]) tab[skey[j]].pad = j;
+}
+__global__ void k_ds_sum_det(int n, const double *__restrict__ pnt, const double *__restrict__ var, const int *__restrict__ sidx, DsSlot *__restrict__ tab,
+                             const int *__restrict__ slot_of) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  DsSlot *s = tab + slot_of[i];
+  if (s->first != i) return;
+  const int dbl = var != nullptr, a = s->pad, c = s->cnt;
+  double sx = 0.0, sy = 0.0, sz = 0.0, vx = 0.0, vy = 0.0, vz = 0.0;
+  for (int j = a; j < a + c; j++) {
+    const size_t q = (size_t)sidx[j];
+    const double x = pnt[3 * q], y = pnt[3 * q + 1], z = pnt[3 * q + 2];
+    sx += dbl ? x : (double)(float)x; sy += dbl ? y : (double)(float)y; sz += dbl ? z : (double)(float)z;
+    if (dbl) { vx += var[9 * q]; vy += var[9 * q + 4]; vz += var[9 * q + 8]; }
+  }
+  s->sx = sx; s->sy = sy; s->sz = sz;
+  if (dbl) { s->vx = vx; s->vy = vy; s->vz = vz; }
 }
 
 // block-level count of "first point of its voxel" flags; blk[b] = count of block b

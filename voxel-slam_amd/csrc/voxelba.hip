@@ -604,7 +604,7 @@ int vba_create(const vba_options *opt, vba_ctx **out) {
   c->max_blocks_hess = opt->hessian_workgroups > 0 ? std::min(opt->hessian_workgroups, kMaxBlocksHess) : kMaxBlocksHess;
   if (c->max_blocks_hess < 2) c->max_blocks_hess = 2;      // (LI-BA gives one workgroup's CU to the IMU factors)
   c->residual_vpl_from = opt->residual_vpl_from > 0 ? opt->residual_vpl_from : 45000;
-  c->use_h3 = opt->hessian_compact_tiles != 0;
+  c->use_h3 = opt->hessian_compact_tiles != 0 && opt->deterministic == 0;   // (k_hessian3 adds into LDS with f64 atomics)
   if (opt->stream) { c->stream = (hipStream_t)opt->stream; c->own_stream = false; }
   else {
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return VBA_ERR_HIP; }
@@ -1945,10 +1945,19 @@ static int ds_common(vba_ctx *c, int mode, int n, const double *pnt, const doubl
   int cap = 1024;
   while (cap < 2 * n) cap <<= 1;
   const int nb = (n + 255) / 256;
+  const bool det = c->opt.deterministic != 0;
+  unsigned int key_bits = 1;
+  while ((1u << key_bits) < (unsigned)cap) key_bits++;
+  size_t b_sort = 0;   // deterministic mode: sorted slot keys, index values in / out, rocPRIM scratch
+  if (det) {
+    size_t tmp = 0;
+    HIPCHK(c, sort_pairs_u32(nullptr, tmp, nullptr, nullptr, nullptr, nullptr, (size_t)n, key_bits, c->stream));
+    b_sort = 3 * ((((size_t)n * sizeof(int)) + 15) & ~(size_t)15) + ((tmp + 255) & ~(size_t)255);
+  }
   const size_t b_tab = (size_t)cap * sizeof(DsSlot), b_pnt = (size_t)n * 3 * sizeof(double), b_i = (((size_t)n * sizeof(int)) + 15) & ~(size_t)15,
                b_blk = (((size_t)nb + 1) * sizeof(int) + 15) & ~(size_t)15, b_var = mode == 1 ? (size_t)n * 9 * sizeof(double) : 0,
                b_dist = mode == 2 ? (size_t)n * sizeof(double) : 0;
-  int st = ensure_stage(c, b_tab + 3 * b_pnt + b_var + b_dist + 3 * b_i + b_blk + 64);
+  int st = ensure_stage(c, b_tab + 3 * b_pnt + b_var + b_dist + 3 * b_i + b_blk + 64 + b_sort + 256);
   if (st) return st;
   char *base = (char *)c->d_stage;
   DsSlot *tab = (DsSlot *)base;
@@ -1961,7 +1970,20 @@ static int ds_common(vba_ctx *c, int mode, int n, const double *pnt, const doubl
   TimedSpan sp{};
   span_begin(c, "downsample", sp);
   hipLaunchKernelGGL(k_ds_clear, dim3((cap + 255) / 256), dim3(256), 0, c->stream, tab, cap);
-  hipLaunchKernelGGL(k_ds_insert, dim3(nb), dim3(256), 0, c->stream, n, d_in, mode == 1 ? d_var : nullptr, voxel_size, tab, cap - 1, d_slot);
+  if (det) {
+    char *sb = (char *)(((uintptr_t)((char *)d_n + 64) + 255) & ~(uintptr_t)255);
+    unsigned int *d_skey = (unsigned int *)sb;
+    int *d_idx = (int *)(sb + b_i), *d_sidx = (int *)(sb + 2 * b_i);
+    void *d_tmp = sb + 3 * b_i;
+    size_t tmp = b_sort - 3 * b_i;
+    hipLaunchKernelGGL(k_ds_insert<true>, dim3(nb), dim3(256), 0, c->stream, n, d_in, mode == 1 ? d_var : nullptr, voxel_size, tab, cap - 1, d_slot);
+    hipLaunchKernelGGL(k_iota, dim3(nb), dim3(256), 0, c->stream, d_idx, n);
+    HIPCHK(c, sort_pairs_u32(d_tmp, tmp, (const unsigned int *)d_slot, d_skey, d_idx, d_sidx, (size_t)n, key_bits, c->stream));
+    hipLaunchKernelGGL(k_ds_segstart, dim3(nb), dim3(256), 0, c->stream, n, d_skey, tab);
+    hipLaunchKernelGGL(k_ds_sum_det, dim3(nb), dim3(256), 0, c->stream, n, d_in, mode == 1 ? d_var : nullptr, d_sidx, tab, d_slot);
+  } else {
+    hipLaunchKernelGGL(k_ds_insert<false>, dim3(nb), dim3(256), 0, c->stream, n, d_in, mode == 1 ? d_var : nullptr, voxel_size, tab, cap - 1, d_slot);
+  }
   if (mode == 2) {
     hipLaunchKernelGGL(k_ds_close_min, dim3(nb), dim3(256), 0, c->stream, n, d_in, tab, d_slot, d_dist);
     hipLaunchKernelGGL(k_ds_close_arg, dim3(nb), dim3(256), 0, c->stream, n, tab, d_slot, d_dist);

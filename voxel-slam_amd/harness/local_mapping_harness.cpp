@@ -21,6 +21,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <deque>
 #include <memory>
 #include <vector>
@@ -40,7 +41,9 @@ static std::vector<double> read_all(const char *path) {
 }
 
 int main(int argc, char **argv) {
-  if (argc < 3) { std::fprintf(stderr, "usage: %s <input.bin> <output.bin>\n", argv[0]); return 2; }
+  // optional third argument --deterministic: vba_options::deterministic = 1 (bit-identical output run to run)
+  const bool det = argc == 4 && std::strcmp(argv[3], "--deterministic") == 0;
+  if (argc < 3 || (argc == 4 && !det) || argc > 4) { std::fprintf(stderr, "usage: %s <input.bin> <output.bin> [--deterministic]\n", argv[0]); return 2; }
   const std::vector<double> in = read_all(argv[1]);
   size_t q = 0;
   auto next = [&]() { return in.at(q++); };
@@ -53,6 +56,7 @@ int main(int argc, char **argv) {
   for (int i = 0; i < 4; i++) opt.plane_eigen_value_thre[i] = next();
   for (int i = 0; i < 4; i++) opt.min_point[i] = next();
   opt.imu_coef = next(); opt.thread_num = (int)next();
+  opt.deterministic = det ? 1 : 0;
 
   std::vector<double> out;
   try {
