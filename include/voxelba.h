@@ -378,8 +378,8 @@ int vba_timing_sample_every(vba_ctx *ctx, int n);
 /* Records an event pair around no work under the name "null": the overhead that every bracketed launch carries. */
 int vba_timing_null_span(vba_ctx *ctx);
 int vba_timing_reset(vba_ctx *ctx);
-/* name in {"residual","hessian","reduce","solve","insert","recut","margi","init"} ("init": the blur and normal-scatter launches of
- * vba_motion_init); returns launches in *count. */
+/* name in {"residual","hessian","reduce","solve","insert","recut","margi","init","loop"} ("init": the blur and normal-scatter launches of
+ * vba_motion_init; "loop": one span per vba_btc_search_loop[_sessions] call and per vba_btc_icp_normal call); returns launches in *count. */
 int vba_timing_get(vba_ctx *ctx, const char *name, double *total_us, int *count);
 
 /* LM building blocks on device state (used by bench.py to time exactly K LM iterations, and by the
@@ -407,6 +407,84 @@ int vba_io_save_pcd(const char *path, int n, const double *xyz);
 int vba_io_load_pcd(const char *path, int cap, double *xyz, double *intensity /* may be NULL */, int *n_out);
 int vba_io_save_pose(const char *path, int n, const double *states, const double *v6);
 int vba_io_read_lidarstate(const char *path, int cap, double *states, double *v6 /* may be NULL */, int *n_out);
+
+/* ------------------------------------------------------------------------------------------------
+ * Loop retrieval and verification of the loop-closure thread (VS:2404-2541): the database half of
+ * STDescManager (BTC.h, BTC.cpp) and icp_normal (loop_refine.hpp = LR).  Descriptor GENERATION (GenerateSTDescs,
+ * BTC.cpp:279-980) stays with the caller, which hands over descriptors and plane clouds.  A database hangs off a context
+ * and runs on its stream; the loop-closure thread owns its own context.  Every result is the same bits
+ * in every run; vba_options::deterministic plays no part here.  DESIGN.md §11.
+ *
+ * Descriptor row (STD, BTC.h:73-84), VBA_BTC_ROW_LEN doubles:
+ *   [triangle_(3) center_(3) frame_number_ A.location_(3) B.location_(3) C.location_(3) A.summary_ B.summary_ C.summary_]
+ * with the occupy_array_ of A, B, C as three 64-bit masks (bit k = entry k) in a separate uint64 [n][3] array.  angle_ is
+ * not read by retrieval and is not passed.  summary_ must be an integer in [0, 255] (unsigned char), a mask may not set a bit
+ * at or above vba_btc_config::occupy_len.
+ * Plane cloud (PointXYZINormal): float [n][6] = x y z normal_x normal_y normal_z.
+ * loop_std_pair is not returned: it is always empty in the reference (the push at BTC.cpp:1370-1388 is commented out). */
+#define VBA_BTC_ROW_LEN 19
+
+typedef struct vba_btc_config {   /* the fields of ConfigSetting (BTC.h:22-57) that retrieval reads, with their types */
+  int skip_near_num;              /* skip_near_num_ */
+  int candidate_num;              /* candidate_num_ (1..256; vba_btc_create refuses anything else) */
+  float rough_dis_threshold;      /* rough_dis_threshold_ */
+  float similarity_threshold;     /* similarity_threshold_ */
+  float icp_threshold;            /* icp_threshold_ */
+  float normal_threshold;         /* normal_threshold_ */
+  float dis_threshold;            /* dis_threshold_ */
+  int occupy_len;                 /* entries of occupy_array_ ((proj_dis_max_ - proj_dis_min_) / proj_image_high_inc_ = 50), <= 64 */
+} vba_btc_config;
+
+typedef struct vba_btc_db vba_btc_db;
+
+typedef struct vba_btc_result {   /* SearchLoop's out-parameters */
+  int loop_id;                    /* loop_result.first: the matched frame, -1 = none */
+  double score;                   /* loop_result.second (0 with loop_id -1) */
+  double t[3];                    /* loop_transform.first  (valid when loop_id >= 0) */
+  double R[9];                    /* loop_transform.second, row-major */
+} vba_btc_result;
+
+typedef struct vba_btc_candidate {/* one entry of candidate_matcher_vec of the last search, for tests */
+  int frame;                      /* match_id_.second */
+  int votes;                      /* match_array[frame] */
+  int match_len;                  /* match_list_.size() (equals votes) */
+  int max_vote_index;             /* winning sampled index of candidate_verify */
+  int max_vote;
+  double score;                   /* verify_score (-1 when max_vote < 4) */
+} vba_btc_candidate;
+
+/* read_parameters (BTC.cpp:3-68), the retrieval fields only.  Host only. */
+int vba_btc_default_config(int is_high_fly, vba_btc_config *cfg);
+/* new STDescManager(config_setting).  VBA_ERR_NO_DEVICE without a HIP device; VBA_ERR_BAD_ARG for occupy_len > 64. */
+int vba_btc_create(vba_ctx *ctx, const vba_btc_config *cfg, vba_btc_db **out);
+/* A database belongs to its context: destroy every database of a context before vba_destroy(ctx). */
+void vba_btc_destroy(vba_btc_db *db);
+/* Capacity hint (no reference counterpart): size the database for `stds` descriptors (rows, cell table, chunks), `frames` plane
+ * clouds of `cloud_points` points in all and a match list of `matches` pairs, so that a session that stays below them never
+ * re-allocates.  Results do not depend on it.  Databases grow by doubling without it. */
+int vba_btc_reserve(vba_btc_db *db, int stds, int frames, int64_t cloud_points, int matches);
+/* config_setting_.skip_near_num_ = v: the writes that close a session (VS:410, VS:2242) */
+int vba_btc_set_skip_near_num(vba_btc_db *db, int v);
+/* plane_cloud_vec_.push_back + header.seq inside GenerateSTDescs (BTC.cpp:156-168).  Frame index = number pushed before. */
+int vba_btc_push_plane_cloud(vba_btc_db *db, int n, const float *xyz_normal, int seq);
+int vba_btc_num_frames(vba_btc_db *db);
+int vba_btc_frame_seq(vba_btc_db *db, int frame, int *seq);
+/* AddSTDescs (BTC.cpp:258-277).  A frame_number_ outside [0, frames pushed) is VBA_ERR_BAD_ARG. */
+int vba_btc_add_stds(vba_btc_db *db, int n, const double *rows, const uint64_t *bits);
+/* SearchLoop (BTC.cpp:205-256) of the n query rows against db; pl_cur = plane cloud cur_frame of cur_db (VS:2421 passes
+ * std_manager->plane_cloud_vec_.back()).  n == 0 gives (-1, 0). */
+int vba_btc_search_loop(vba_btc_db *db, int n, const double *rows, const uint64_t *bits, const vba_btc_db *cur_db, int cur_frame,
+                        vba_btc_result *result);
+/* the loop `for (id = 0; id <= cur_id; id++) SearchLoop(...)` (VS:2417-2421): one query upload, every database enqueued, one host
+ * synchronisation; results[k] is the result of dbs[k].  All databases must hang off the same context. */
+int vba_btc_search_loop_sessions(int n_db, vba_btc_db *const *dbs, int n, const double *rows, const uint64_t *bits,
+                                 const vba_btc_db *cur_db, int cur_frame, vba_btc_result *results);
+/* icp_normal(pl_src, pl_tar, pose, icp_eigval) (LR:47-139) at its call site VS:2434, both clouds resident: t, R (row-major) are
+ * the pose, updated in place; *ok = the return value, eig = eigenvalues of mat_norm (ascending), *iters = iterations run. */
+int vba_btc_icp_normal(vba_btc_db *src_db, int src_frame, vba_btc_db *tar_db, int tar_frame, double *t, double *R, double icp_eigval,
+                       int *ok, double *eig, int *iters);
+/* candidates of the last search on db (*n = how many; at most cap written) */
+int vba_btc_last_candidates(vba_btc_db *db, int cap, vba_btc_candidate *out, int *n);
 
 #ifdef __cplusplus
 }

@@ -407,6 +407,100 @@ inline std::vector<ScanPoseRec> read_lidarstate(const std::string &filename) {
   return out;
 }
 
+// ---- loop retrieval: the database half of STDescManager (BTC.h:228-300; AddSTDescs / SearchLoop, BTC.cpp:205-277) and icp_normal
+// (loop_refine.hpp:47-139).  Descriptors stay generated on the host (GenerateSTDescs); the structs below mirror STD and
+// BinaryDescriptor (BTC.h:59-84) with the occupancy array as a bit mask (entry k = bit k) and angle_ left out (retrieval never
+// reads it).  A loop transform is (t, R row-major), the pair<Vector3d, Matrix3d> of the reference.
+struct BinaryDescriptor {
+  uint64_t occupy_bits = 0;        // occupy_array_
+  unsigned char summary_ = 0;
+  double location_[3] = {0, 0, 0};
+};
+struct STD {
+  double triangle_[3] = {0, 0, 0};
+  double center_[3] = {0, 0, 0};
+  int frame_number_ = 0;
+  BinaryDescriptor binary_A_, binary_B_, binary_C_;
+};
+struct LoopTransform { double t[3] = {0, 0, 0}; double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}; };
+
+inline void pack_stds(const std::vector<STD> &v, std::vector<double> &rows, std::vector<uint64_t> &bits) {
+  rows.assign(v.size() * VBA_BTC_ROW_LEN, 0.0);
+  bits.assign(v.size() * 3, 0);
+  for (size_t i = 0; i < v.size(); i++) {
+    double *r = rows.data() + i * VBA_BTC_ROW_LEN;
+    const BinaryDescriptor *b[3] = {&v[i].binary_A_, &v[i].binary_B_, &v[i].binary_C_};
+    for (int k = 0; k < 3; k++) { r[k] = v[i].triangle_[k]; r[3 + k] = v[i].center_[k]; }
+    r[6] = v[i].frame_number_;
+    for (int e = 0; e < 3; e++) {
+      for (int k = 0; k < 3; k++) r[7 + 3 * e + k] = b[e]->location_[k];
+      r[16 + e] = b[e]->summary_;
+      bits[3 * i + e] = b[e]->occupy_bits;
+    }
+  }
+}
+
+// STDescManager's database: one per session, on the loop-closure thread's context.  Destroy it before its Context.
+class BtcDatabase {
+ public:
+  struct ConfigSetting { int skip_near_num_; };   // the field the node writes to close a session (VS:410, VS:2242)
+  ConfigSetting config_setting_;
+  BtcDatabase(Context &ctx, const vba_btc_config &cfg) : ctx_(ctx.get()) {
+    check(ctx_, vba_btc_create(ctx_, &cfg, &db_));
+    config_setting_.skip_near_num_ = cfg.skip_near_num;
+  }
+  ~BtcDatabase() { vba_btc_destroy(db_); }
+  BtcDatabase(const BtcDatabase &) = delete;
+  BtcDatabase &operator=(const BtcDatabase &) = delete;
+  vba_btc_db *get() const { return db_; }
+  // plane_cloud_vec_.push_back(plane_cloud) with header.seq = seq (BTC.cpp:156-168); xyz_normal: n x 6 floats
+  void push_plane_cloud(const std::vector<float> &xyz_normal, int seq) {
+    check(ctx_, vba_btc_push_plane_cloud(db_, (int)(xyz_normal.size() / 6), xyz_normal.data(), seq));
+  }
+  int plane_cloud_num() const { return vba_btc_num_frames(db_); }      // plane_cloud_vec_.size()
+  int plane_cloud_seq(int frame) const { int s = 0; check(ctx_, vba_btc_frame_seq(db_, frame, &s)); return s; }
+  void AddSTDescs(const std::vector<STD> &stds) {                          // BTC.cpp:258-277
+    std::vector<double> rows; std::vector<uint64_t> bits;
+    pack_stds(stds, rows, bits);
+    check(ctx_, vba_btc_add_stds(db_, (int)stds.size(), rows.data(), bits.data()));
+  }
+  // SearchLoop(stds_vec, loop_result, loop_transform, loop_std_pair, pl_cur) (BTC.cpp:205-256) with pl_cur = plane cloud cur_frame
+  // of cur (VS:2421 passes std_manager->plane_cloud_vec_.back()).  loop_std_pair is cleared: it is always empty in the reference.
+  void SearchLoop(const std::vector<STD> &stds, std::pair<int, double> &loop_result, LoopTransform &loop_transform,
+                  std::vector<std::pair<STD, STD>> &loop_std_pair, const BtcDatabase &cur, int cur_frame) {
+    std::vector<BtcDatabase *> one{this};
+    std::vector<vba_btc_result> r;
+    search_loop_sessions(one, stds, cur, cur_frame, r);
+    loop_std_pair.clear();
+    loop_result = std::make_pair(r[0].loop_id, r[0].score);
+    if (r[0].loop_id >= 0) { std::memcpy(loop_transform.t, r[0].t, 24); std::memcpy(loop_transform.R, r[0].R, 72); }
+  }
+  // the loop over sessions `for (id = 0; id <= cur_id; id++) SearchLoop(...)` (VS:2417-2421) as one batched call
+  static void search_loop_sessions(const std::vector<BtcDatabase *> &dbs, const std::vector<STD> &stds, const BtcDatabase &cur, int cur_frame,
+                                   std::vector<vba_btc_result> &results) {
+    std::vector<double> rows; std::vector<uint64_t> bits;
+    pack_stds(stds, rows, bits);
+    std::vector<vba_btc_db *> h(dbs.size());
+    for (size_t k = 0; k < dbs.size(); k++) { h[k] = dbs[k]->db_; vba_btc_set_skip_near_num(h[k], dbs[k]->config_setting_.skip_near_num_); }
+    results.assign(dbs.size(), vba_btc_result{});
+    check(cur.ctx_, vba_btc_search_loop_sessions((int)dbs.size(), h.data(), (int)stds.size(), rows.data(), bits.data(), cur.db_, cur_frame,
+                                                 results.data()));
+  }
+ private:
+  vba_ctx *ctx_ = nullptr;
+  vba_btc_db *db_ = nullptr;
+};
+
+// icp_normal(pl_src, pl_tar, pose, icp_eigval) (loop_refine.hpp:47-139) at its call site VS:2434, both clouds resident: pose
+// updated in place, the return value of the reference; eig / iters optional.
+inline bool icp_normal(BtcDatabase &src, int src_frame, BtcDatabase &tar, int tar_frame, LoopTransform &pose, double icp_eigval,
+                       double *eig = nullptr, int *iters = nullptr) {
+  int ok = 0;
+  const int st = vba_btc_icp_normal(src.get(), src_frame, tar.get(), tar_frame, pose.t, pose.R, icp_eigval, &ok, eig, iters);
+  if (st != VBA_OK) throw std::runtime_error(std::string("libvoxelba: icp_normal: ") + vba_status_string(st));
+  return ok != 0;
+}
+
 #ifdef VBA_ADAPTER_HAVE_EIGEN
 // Eigen-typed conveniences so reference call sites keep their argument types (Eigen is column-major: converted here).
 inline void to_rowmajor3(const Eigen::Matrix3d &M, double *r) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) r[3 * i + j] = M(i, j); }

@@ -33,6 +33,9 @@ EXPORTS = [
     "vba_lm_begin", "vba_lm_refresh_eigen", "vba_lm_iterate", "vba_lm_end",
     "vba_io_save_pcd", "vba_io_load_pcd", "vba_io_save_pose", "vba_io_read_lidarstate",
     "vba_motion_init", "vba_init_imu_poses", "vba_init_align_gravity",
+    "vba_btc_default_config", "vba_btc_create", "vba_btc_destroy", "vba_btc_set_skip_near_num", "vba_btc_push_plane_cloud",
+    "vba_btc_num_frames", "vba_btc_frame_seq", "vba_btc_add_stds", "vba_btc_search_loop", "vba_btc_search_loop_sessions",
+    "vba_btc_icp_normal", "vba_btc_last_candidates", "vba_btc_reserve",
 ]
 
 
@@ -46,6 +49,116 @@ class Options(C.Structure):
         ("max_map_nodes", C.c_size_t), ("max_fix_points", C.c_size_t), ("hba_workers", C.c_int),
         ("deterministic", C.c_int),
     ]
+
+
+class BtcConfig(C.Structure):
+    """vba_btc_config: the retrieval fields of ConfigSetting (BTC.h:22-57), with the reference's float types."""
+    _fields_ = [
+        ("skip_near_num", C.c_int), ("candidate_num", C.c_int), ("rough_dis_threshold", C.c_float),
+        ("similarity_threshold", C.c_float), ("icp_threshold", C.c_float), ("normal_threshold", C.c_float),
+        ("dis_threshold", C.c_float), ("occupy_len", C.c_int),
+    ]
+
+
+class BtcResult(C.Structure):
+    _fields_ = [("loop_id", C.c_int), ("score", C.c_double), ("t", C.c_double * 3), ("R", C.c_double * 9)]
+
+
+class BtcCandidate(C.Structure):
+    _fields_ = [("frame", C.c_int), ("votes", C.c_int), ("match_len", C.c_int), ("max_vote_index", C.c_int),
+                ("max_vote", C.c_int), ("score", C.c_double)]
+
+
+BTC_ROW_LEN = 19
+
+
+def btc_default_config(is_high_fly=0) -> BtcConfig:
+    """read_parameters (BTC.cpp:3-68), retrieval fields only."""
+    f = BtcConfig()
+    st = load().vba_btc_default_config(C.c_int(int(is_high_fly)), C.byref(f))
+    if st:
+        raise VbaError(st)
+    return f
+
+
+def _btc_query(rows, bits):
+    rows = np.ascontiguousarray(np.reshape(rows, (-1, BTC_ROW_LEN)), dtype=np.float64)
+    bits = np.ascontiguousarray(np.reshape(bits, (-1, 3)), dtype=np.uint64)
+    if len(rows) != len(bits):
+        raise ValueError("rows and bits differ in length")
+    return rows, bits, bits.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def _btc_result(r):
+    return dict(loop_id=r.loop_id, score=r.score, t=np.array(r.t[:]), R=np.array(r.R[:]).reshape(3, 3))
+
+
+class BtcDb:
+    """One vba_btc_db: the database half of STDescManager (descriptors + plane clouds) on a context."""
+
+    def __init__(self, ctx, config):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx._chk(self.lib.vba_btc_create(ctx.h, C.byref(config), C.byref(h)))
+        self.h = h
+        ctx._btc.append(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.vba_btc_destroy(self.h)
+            self.h = None
+        btc = getattr(self.ctx, "_btc", None)
+        if btc is not None and self in btc:
+            btc.remove(self)
+
+    def reserve(self, stds=0, frames=0, cloud_points=0, matches=0):
+        """capacity hint: a database sized for these never re-allocates (results do not depend on it)"""
+        self.ctx._chk(self.lib.vba_btc_reserve(self.h, C.c_int(stds), C.c_int(frames), C.c_int64(cloud_points), C.c_int(matches)))
+
+    def set_skip_near_num(self, v):
+        self.ctx._chk(self.lib.vba_btc_set_skip_near_num(self.h, C.c_int(int(v))))
+
+    def push_plane_cloud(self, xyz_normal, seq):
+        a = np.ascontiguousarray(np.reshape(xyz_normal, (-1, 6)), dtype=np.float32)
+        self.ctx._chk(self.lib.vba_btc_push_plane_cloud(self.h, C.c_int(len(a)), a.ctypes.data_as(C.POINTER(C.c_float)), C.c_int(int(seq))))
+
+    def num_frames(self):
+        return self.lib.vba_btc_num_frames(self.h)
+
+    def frame_seq(self, frame):
+        s = C.c_int()
+        self.ctx._chk(self.lib.vba_btc_frame_seq(self.h, C.c_int(frame), C.byref(s)))
+        return s.value
+
+    def add_stds(self, rows, bits):
+        rows, bits, bp = _btc_query(rows, bits)
+        self.ctx._chk(self.lib.vba_btc_add_stds(self.h, C.c_int(len(rows)), _p(rows), bp))
+
+    def search_loop(self, rows, bits, cur_db, cur_frame=-1):
+        """SearchLoop against this database; pl_cur = plane cloud cur_frame of cur_db (-1: its last)."""
+        rows, bits, bp = _btc_query(rows, bits)
+        if cur_frame < 0:
+            cur_frame = cur_db.num_frames() + cur_frame
+        r = BtcResult()
+        self.ctx._chk(self.lib.vba_btc_search_loop(self.h, C.c_int(len(rows)), _p(rows), bp, cur_db.h, C.c_int(cur_frame), C.byref(r)))
+        return _btc_result(r)
+
+    def last_candidates(self):
+        """list of dicts (frame, votes, match_len, max_vote_index, max_vote, score) of the last search"""
+        n = C.c_int()
+        out = (BtcCandidate * 256)()
+        self.ctx._chk(self.lib.vba_btc_last_candidates(self.h, C.c_int(256), out, C.byref(n)))
+        return [dict(frame=o.frame, votes=o.votes, match_len=o.match_len, max_vote_index=o.max_vote_index, max_vote=o.max_vote,
+                     score=o.score) for o in out[:n.value]]
+
+    def icp_normal(self, src_frame, tar_db, tar_frame, t, R, icp_eigval):
+        """icp_normal(plane cloud src_frame of this db, plane cloud tar_frame of tar_db, (t, R), icp_eigval)"""
+        tt = _c(t).copy(); RR = _c(R).reshape(3, 3).copy()
+        ok = C.c_int(); it = C.c_int(); eig = np.zeros(3)
+        self.ctx._chk(self.lib.vba_btc_icp_normal(self.h, C.c_int(src_frame), tar_db.h, C.c_int(tar_frame), _p(tt), _p(RR),
+                                                  C.c_double(icp_eigval), C.byref(ok), _p(eig), C.byref(it)))
+        return dict(ok=ok.value, t=tt, R=RR, eig=eig, iters=it.value)
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -212,8 +325,11 @@ class Context:
             raise VbaError(st, self.lib.vba_status_string(st).decode())
         self.h = h
         self._cb = None
+        self._btc = []
 
     def close(self):
+        for db in list(getattr(self, "_btc", [])):     # (a database belongs to its context: destroyed first)
+            db.close()
         if getattr(self, "h", None):
             self.lib.vba_destroy(self.h)
             self.h = None
@@ -356,6 +472,21 @@ class Context:
         if want_pvec:
             out["pvec"] = [(po[pvo[i]:pvo[i + 1]].copy(), vo[pvo[i]:pvo[i + 1]].reshape(-1, 3, 3).copy()) for i in range(W)]
         return out
+
+    # ---- loop retrieval (BTC.cpp, loop_refine.hpp)
+    def btc_db(self, config=None) -> "BtcDb":
+        return BtcDb(self, config if config is not None else btc_default_config(0))
+
+    def btc_search_loop_sessions(self, dbs, rows, bits, cur_db, cur_frame=-1):
+        """SearchLoop of one query against every database (VS:2417-2421): one upload, one synchronisation."""
+        rows, bits, bp = _btc_query(rows, bits)
+        if cur_frame < 0:
+            cur_frame = cur_db.num_frames() + cur_frame
+        arr = (C.c_void_p * max(len(dbs), 1))(*[d.h.value for d in dbs])
+        res = (BtcResult * max(len(dbs), 1))()
+        self._chk(self.lib.vba_btc_search_loop_sessions(C.c_int(len(dbs)), arr, C.c_int(len(rows)), _p(rows), bp, cur_db.h,
+                                                        C.c_int(cur_frame), res))
+        return [_btc_result(res[k]) for k in range(len(dbs))]
 
     # ---- voxel map
     def cut_voxel(self, win_count, pnt_body, pose12, var=None, multi=False):

@@ -16,6 +16,12 @@
 //           then the remaining n_scans - win_size scans in the per-scan layout above (their IMU samples use scale_gravity);
 //           output starts with [-2, converge_flag, iterations, thresholds_left_relaxed, eigvalue(3), W x 25 states], then as above
 //           (the first window record is the initialised window's step, VS:1951 reached with win_count = win_size)
+//   mode 4 (loop detection, VS:2404-2541, through vba::BtcDatabase / vba::icp_normal): the header is only
+//           [magic, 0, n_keyframes, 4, is_high_fly, icp_eigval, n_sessions, juds[n_sessions]], then per keyframe
+//           [session, n_desc, n_pts] rows[n_desc][19] bits[n_desc][3] (occupancy masks as doubles, < 2^53) cloud[n_pts][6];
+//           sessions come in order; a new session closes the previous one (skip_near_num_ = -(clouds + 10), VS:2242).
+//           output per keyframe and per session id <= cur: [cur session, keyframe, id, loop_id, score, icp_ran, icp_ok, iters,
+//           t(3), R(9), eig(3)] (23 doubles; the pose is the ICP result when icp_ran, else SearchLoop's transform)
 //   output: per optimised window [scan index, W x 25 states, v6[6]] ... then [-1, n_leaves] leaf dump [n][39] plane_var dump [n][86]
 #include "../../include/voxelba_adapter.hpp"
 #include <cmath>
@@ -40,6 +46,80 @@ static std::vector<double> read_all(const char *path) {
   return v;
 }
 
+// VS:2404-2541 over a multi-session stream: push the keyframe's plane cloud, SearchLoop against every session (one batched call),
+// icp_normal where score > juds[id], AddSTDescs; a new session closes the previous database
+static int run_loop_detection(const std::vector<double> &in, size_t q, int n_kf, const char *out_path) {
+  auto next = [&]() { return in.at(q++); };
+  const int is_high_fly = (int)next();
+  const double icp_eigval = next();
+  const int n_sessions = (int)next();
+  std::vector<double> juds(n_sessions);
+  for (double &j : juds) j = next();
+  vba_options opt;
+  vba_default_options(&opt);
+  opt.device = 0;
+  std::vector<double> out;
+  {
+    Context ctx(opt);
+    vba_btc_config cfg;
+    vba_btc_default_config(is_high_fly, &cfg);
+    std::vector<std::unique_ptr<BtcDatabase>> managers;
+    int cur_session = -1, kf_in_session = 0;
+    for (int k = 0; k < n_kf; k++) {
+      const int session = (int)next(), nd = (int)next(), np = (int)next();
+      if (session != cur_session) {
+        if (!managers.empty()) managers.back()->config_setting_.skip_near_num_ = -(managers.back()->plane_cloud_num() + 10);   // VS:2242
+        managers.emplace_back(new BtcDatabase(ctx, cfg));
+        cur_session = session; kf_in_session = 0;
+      }
+      std::vector<STD> stds(nd);
+      for (int i = 0; i < nd; i++) {
+        STD &d = stds[i];
+        double r[19];
+        for (int u = 0; u < 19; u++) r[u] = next();
+        BinaryDescriptor *b[3] = {&d.binary_A_, &d.binary_B_, &d.binary_C_};
+        for (int u = 0; u < 3; u++) { d.triangle_[u] = r[u]; d.center_[u] = r[3 + u]; }
+        d.frame_number_ = (int)r[6];
+        for (int e = 0; e < 3; e++) { for (int u = 0; u < 3; u++) b[e]->location_[u] = r[7 + 3 * e + u]; b[e]->summary_ = (unsigned char)r[16 + e]; }
+      }
+      for (int i = 0; i < nd; i++) {
+        stds[i].binary_A_.occupy_bits = (uint64_t)next(); stds[i].binary_B_.occupy_bits = (uint64_t)next(); stds[i].binary_C_.occupy_bits = (uint64_t)next();
+      }
+      std::vector<float> cloud((size_t)np * 6);
+      for (float &f : cloud) f = (float)next();
+      BtcDatabase &cur = *managers.back();
+      cur.push_plane_cloud(cloud, kf_in_session);                                          // GenerateSTDescs' push (BTC.cpp:164-165)
+      const int last = cur.plane_cloud_num() - 1;
+      std::vector<BtcDatabase *> dbs;
+      for (auto &m : managers) dbs.push_back(m.get());
+      std::vector<vba_btc_result> res;
+      BtcDatabase::search_loop_sessions(dbs, stds, cur, last, res);                          // VS:2417-2421
+      for (size_t id = 0; id < dbs.size(); id++) {
+        LoopTransform pose;
+        std::memcpy(pose.t, res[id].t, 24); std::memcpy(pose.R, res[id].R, 72);
+        double eig[3] = {0, 0, 0};
+        int iters = 0, ran = 0, ok = 0;
+        if (res[id].loop_id >= 0 && res[id].score > juds[id]) {                              // VS:2431-2434
+          ran = 1;
+          ok = icp_normal(cur, last, *dbs[id], res[id].loop_id, pose, icp_eigval, eig, &iters) ? 1 : 0;
+        }
+        const double rec[8] = {(double)session, (double)kf_in_session, (double)id, (double)res[id].loop_id, res[id].score, (double)ran, (double)ok, (double)iters};
+        out.insert(out.end(), rec, rec + 8);
+        out.insert(out.end(), pose.t, pose.t + 3);
+        out.insert(out.end(), pose.R, pose.R + 9);
+        out.insert(out.end(), eig, eig + 3);
+      }
+      cur.AddSTDescs(stds);                                                                  // VS:2541
+      kf_in_session++;
+    }
+  }
+  FILE *f = std::fopen(out_path, "wb");
+  if (!f) return 2;
+  std::fwrite(out.data(), 8, out.size(), f);
+  std::fclose(f);
+  return 0;
+}
+
 int main(int argc, char **argv) {
   // optional third argument --deterministic: vba_options::deterministic = 1 (bit-identical output run to run)
   const bool det = argc == 4 && std::strcmp(argv[3], "--deterministic") == 0;
@@ -49,6 +129,7 @@ int main(int argc, char **argv) {
   auto next = [&]() { return in.at(q++); };
   if (next() != 20241004.0) { std::fprintf(stderr, "harness: bad magic\n"); return 2; }
   const int win_size = (int)next(), n_scans = (int)next(), mode = (int)next();
+  if (mode == 4) return run_loop_detection(in, q, n_scans, argv[2]);
   vba_options opt;
   vba_default_options(&opt);
   opt.win_size = win_size;

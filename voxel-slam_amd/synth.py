@@ -387,3 +387,100 @@ def make_init_window(win_size: int = 10, n_pts: int = 20000, scene: str = "room"
         covs[i] = np.diag([1e-5] * 3 + [1e-4] * 3 + [1e-3] * 3 + [1e-6] * 6)
     return dict(clouds=clouds, curvs=curvs, imus=imus, beg_times=np.array(begs), states=states, covs=covs.reshape(win_size, 225),
                 ext=ext, scale_gravity=G if acc_unit_g else 1.0, gt_states=gt)
+
+
+# ------------------------------------------------------------------------------------------------ loop retrieval (vba_btc_*)
+def _rot_z(a):
+    c, s = np.cos(a), np.sin(a)
+    return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+
+
+def make_btc_sessions(n_sessions=2, n_kf=200, n_keypoints=900, max_desc=120, n_planes=60, plane_pts=4, view=30.0, seed=0,
+                      loc_noise=0.01, flip_bits=2, occupy_len=50, std_side_resolution=0.2, min_len=2.0, max_len=50.0):
+    """Sessions as the loop-closure thread sees them (VS:2404-2541), deterministic in `seed`.
+
+    World: corner keypoints with a `occupy_len`-bit occupancy pattern each; planar voxels (centre, normal).  Each session drives a
+    closed circuit around the same area (session k starts 2 pi k / n_sessions further on and turns once round), so it revisits its
+    own start and the places of the other sessions.  Per keyframe: triangles of visible keypoints (a fixed global list, so a
+    revisit regenerates the same triangles), as descriptor rows of include/voxelba.h (sides sorted and scaled by
+    1 / std_side_resolution, A / B / C = the vertices opposite the shortest / middle / longest side, centre = centroid,
+    frame_number = keyframe index in the session), with `flip_bits` occupancy bits flipped per observation; the plane cloud =
+    visible planar voxels in the keyframe frame (float32 x y z nx ny nz).  Returns a list of sessions, each a dict of lists:
+    rows, bits, cloud, R, p (keyframe pose in the world)."""
+    rng = np.random.default_rng(seed)
+    kp = np.column_stack([rng.uniform(-60, 60, n_keypoints), rng.uniform(-60, 60, n_keypoints), rng.uniform(0, 8, n_keypoints)])
+    pat = rng.integers(0, 2, size=(n_keypoints, occupy_len)).astype(np.uint64)
+    # global triangle list: each keypoint with pairs of its 6 nearest neighbours, sides within [min_len, max_len]
+    d2 = ((kp[:, None, :] - kp[None, :, :]) ** 2).sum(-1)
+    nn = np.argsort(d2, axis=1)[:, 1:7]
+    tris = set()
+    for a in range(n_keypoints):
+        for u in range(6):
+            for v in range(u + 1, 6):
+                t = tuple(sorted((a, int(nn[a, u]), int(nn[a, v]))))
+                if len(set(t)) == 3:
+                    tris.add(t)
+    tris = np.array(sorted(tris), dtype=np.int64)
+    L = lambda i, j: np.linalg.norm(kp[tris[:, i]] - kp[tris[:, j]], axis=1)
+    sides = np.stack([L(1, 2), L(0, 2), L(0, 1)], axis=1)          # side opposite vertex 0, 1, 2
+    keep = (sides.min(1) >= min_len) & (sides.max(1) <= max_len) & (np.abs(np.diff(np.sort(sides, 1), axis=1)).min(1) > 0.3)
+    tris, sides = tris[keep], sides[keep]
+    order = np.argsort(sides, axis=1)                               # A, B, C = opposite the shortest, middle, longest side
+    tris = np.take_along_axis(tris, order, axis=1)
+    sides = np.take_along_axis(sides, order, axis=1)
+    # planar voxels: centres on the ground and on vertical walls, unit normals
+    pc = np.column_stack([rng.uniform(-60, 60, n_planes * 8), rng.uniform(-60, 60, n_planes * 8), np.zeros(n_planes * 8)])
+    pn = np.tile([0.0, 0.0, 1.0], (n_planes * 8, 1))
+    wall_a = rng.uniform(0, np.pi, n_planes)
+    wc = np.column_stack([rng.uniform(-60, 60, n_planes), rng.uniform(-60, 60, n_planes), rng.uniform(1, 6, n_planes)])
+    wn = np.column_stack([np.cos(wall_a), np.sin(wall_a), np.zeros(n_planes)])
+    off = rng.uniform(-3, 3, (n_planes, plane_pts * 4))
+    wpts = (wc[:, None, :] + off[..., None] * np.stack([-wn[:, 1], wn[:, 0], np.zeros(n_planes)], 1)[:, None, :]).reshape(-1, 3)
+    wpts[:, 2] += rng.uniform(-2, 2, len(wpts))
+    pc = np.concatenate([pc, wpts]); pn = np.concatenate([pn, np.repeat(wn, plane_pts * 4, axis=0)])
+    sessions = []
+    for s in range(n_sessions):
+        out = dict(rows=[], bits=[], cloud=[], R=[], p=[])
+        ph0 = 2 * np.pi * s / max(n_sessions, 1)
+        for k in range(n_kf):
+            ph = ph0 + 2 * np.pi * 1.25 * k / n_kf                   # 1.25 turns: the last quarter revisits the start
+            pos = np.array([35 * np.cos(ph), 35 * np.sin(ph), 1.5])
+            R = _rot_z(ph + np.pi / 2 + 0.05 * np.sin(3 * ph))
+            vis = np.linalg.norm(kp[:, :2] - pos[:2], axis=1) < view
+            tv = np.flatnonzero(vis[tris].all(1))[:max_desc]
+            local = (kp - pos) @ R + rng.normal(0, loc_noise, kp.shape)
+            rows = np.zeros((len(tv), 19))
+            bits = np.zeros((len(tv), 3), dtype=np.uint64)
+            for m, ti in enumerate(tv):
+                vtx = tris[ti]
+                rows[m, 0:3] = sides[ti] / std_side_resolution
+                rows[m, 3:6] = local[vtx].mean(0)
+                rows[m, 6] = k
+                rows[m, 7:16] = local[vtx].reshape(-1)
+                for e in range(3):
+                    b = pat[vtx[e]].copy()
+                    fl = rng.integers(0, occupy_len, flip_bits)
+                    b[fl] ^= np.uint64(1)
+                    rows[m, 16 + e] = float(b.sum())
+                    bits[m, e] = np.bitwise_or.reduce(b << np.arange(occupy_len, dtype=np.uint64))
+            pv = np.linalg.norm(pc[:, :2] - pos[:2], axis=1) < view
+            cl = np.zeros((int(pv.sum()), 6), dtype=np.float32)
+            cl[:, 0:3] = (pc[pv] - pos) @ R + rng.normal(0, 0.01, (int(pv.sum()), 3))
+            cl[:, 3:6] = pn[pv] @ R
+            out["rows"].append(rows); out["bits"].append(bits); out["cloud"].append(cl); out["R"].append(R); out["p"].append(pos)
+        sessions.append(out)
+    return sessions
+
+
+def btc_plane_cloud(n, seed=0):
+    """a float32 plane cloud of n points on five planes (x y z nx ny nz) for the ICP tests"""
+    rng = np.random.default_rng(seed)
+    normals = np.array([[0, 0, 1], [1, 0, 0], [0, 1, 0], [0.6, 0.8, 0], [0, 0.6, 0.8]], dtype=np.float64)
+    ds = np.array([0.0, 8.0, -6.0, 4.0, 3.0])
+    k = rng.integers(0, 5, n)
+    nrm = normals[k]
+    u = np.cross(nrm, [0.3, 0.5, 0.81]); u /= np.linalg.norm(u, axis=1, keepdims=True)
+    v = np.cross(nrm, u)
+    a, b = rng.uniform(-10, 10, (2, n))
+    pts = nrm * ds[k][:, None] + a[:, None] * u + b[:, None] * v + rng.normal(0, 0.005, (n, 3))
+    return np.column_stack([pts, nrm]).astype(np.float32)
