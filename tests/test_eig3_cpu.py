@@ -1,6 +1,7 @@
 """Host-side check of the product's direct symmetric 3x3 eigen-solver (csrc/vba_eig3.hpp, the plane fit of K2/K4/K5) against
 numpy.linalg.eigh: the KAT-3 fixture, plane-like covariances with world-sized second moments, and the cases that must be
-handed to the iterative solver.  The same header is compiled for the device by hipcc; here g++ builds it for the CPU."""
+handed to the iterative solver; and against the 50-digit reference of tests/eig3_ref.py on its corpus, with its bars.  The same
+header is compiled for the device by hipcc; here g++ builds it for the CPU."""
 import ctypes as C
 import os
 import subprocess
@@ -8,6 +9,8 @@ import tempfile
 
 import numpy as np
 import pytest
+
+import eig3_ref as R
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -99,3 +102,56 @@ def test_degenerate_inputs_are_refused(eig):
     # exactly diagonal with distinct entries is fine
     ok, w, V = eig(np.diag([3.0, 1.0, 2.0]))
     assert ok and np.allclose(w, [1, 2, 3]) and np.allclose(np.abs(V), np.array([[0, 0, 1], [1, 0, 0], [0, 1, 0]]), atol=1e-15)
+
+
+@pytest.fixture(scope="module")
+def corpus_run(eig):
+    items = R.corpus()
+    refs = R.refs(items)
+    res = [eig(A) for _, A in items]
+    return items, refs, res
+
+
+def test_corpus_coverage(corpus_run):
+    """The corpus exercises both sides of the direct path's fallback test: >= 200 matrices refused (the device runs Jacobi on them)
+    and >= 200 accepted within 10x of the threshold."""
+    items, refs, res = corpus_run
+    refused = sum(1 for ok, _, _ in res if not ok)
+    near = sum(1 for (ok, _, _), r in zip(res, refs) if ok and r.dc1() <= 10 * R.THRESH)
+    assert refused >= 200, refused
+    assert near >= 200, near
+    # the direct path sees planes, top pairs, diagonal / rank-2 and scaled matrices; line-like covariances (class c) all fall back
+    acc = {cls for (cls, _), (ok, _, _) in zip(items, res) if ok}
+    assert {"a", "b", "d", "e"} <= acc, acc
+    assert not any(ok for (cls, _), (ok, _, _) in zip(items, res) if cls == "c")
+
+
+def test_corpus_bars(corpus_run):
+    """Every matrix the direct path accepts meets the bars of eig3_ref against the 50-digit reference, the eigenvectors of a close
+    pair included (the deflated-quadratic form missed them by up to ~eps / relgap^2)."""
+    items, refs, res = corpus_run
+    worst = {}
+    bad = []
+    for (cls, A), r, (ok, w, V) in zip(items, refs, res):
+        if not ok:
+            continue
+        q = R.check(r, w, V)
+        for k, v in q.items():
+            worst[(cls, k)] = max(worst.get((cls, k), 0.0), v)
+        if R.worst(q) > 1.0:
+            bad.append((cls, r.w.tolist(), q))
+    print("host direct, worst ratio to bar:", {k: "%.3g" % v for k, v in sorted(worst.items())})
+    assert not bad, (len(bad), bad[:5])
+
+
+def test_pair_eigenvectors_near_threshold(eig):
+    """lambda = (1e-4, 1, 1 + g), the pair just above the fallback threshold: each of the pair's vectors within 16 eps / g of the
+    reference (the deflated-quadratic form gave ~eps / g^2: 1e-6 at g = 1e-5)."""
+    rng = np.random.default_rng(5)
+    for g in (1e-2, 1e-3, 1e-4, 1.1e-5):
+        for _ in range(20):
+            A = R._spec(R._rot(rng), [1e-4, 1.0, 1.0 + g])
+            ok, w, V = eig(A)
+            assert ok
+            q = R.check(R.Ref(A), w, V)
+            assert q["vec"] <= 1.0 and R.worst(q) <= 1.0, (g, q)

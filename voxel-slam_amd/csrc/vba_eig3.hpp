@@ -1,21 +1,24 @@
 // Symmetric 3x3 eigen-decomposition of the plane fit (replaces Eigen::SelfAdjointEigenSolver<Matrix3d> at
 // voxel_map.hpp:312 / :1416 / :1525 / :1771, loop_refine.hpp:363): ascending eigenvalues, orthonormal eigenvectors in the
-// columns of V (row-major), result equal to the iterative solver up to rounding and eigenvector sign.
+// columns of V (row-major).  Accuracy is that of a backward-stable solver: eigenvalues to a few eps of the matrix scale s = |A|_2,
+// eigenvector i to ~eps s / gap_i (gap_i = distance to the nearest other eigenvalue), and for a close pair its invariant subspace
+// to ~eps s / (distance to the third); tests/eig3_ref.py states the bars and tests/test_eig3_cpu.py, tests/test_gpu_eig3.py check them
+// against a 50-digit reference.
 //
 // Why not Jacobi: in the residual pass (K4) every lane owns one voxel and the eigen-solve is ONE dependent chain per lane; the
 // cyclic-Jacobi version (f32 pre-pass + two f64 sweeps, vba_kernels_factor.hpp) measured 8.5k of the pass's 22k cycles on
 // MI355X.  This solver is direct (no sweeps), ~330 f64 operations with short chains:
 //   1. exact power-of-two scaling, B = A - (tr A / 3) I, characteristic cubic x^3 - c1 x - c0 (c1 = |B|_F^2 / 2, c0 = det B);
 //   2. the ISOLATED root (largest if c0 >= 0, else smallest: its distance to the other two is >= sqrt(3 c1 / 3)...) from an f32
-//      trigonometric seed + three f64 Newton steps (two with the raw reciprocal, one exact); the other two roots from the deflated quadratic
-//      x^2 + x_a x + (x_a^2 - c1) = 0, whose discriminant is (x_b - x_c)^2;
-//   3. eigenvectors without iteration (Eberly, "A Robust Eigensolver for 3x3 Symmetric Matrices"): v_a = largest cross product
-//      of two rows of B - x_a I; {U, V} an orthonormal basis of its complement; the eigenvector of the OTHER EXTREME eigenvalue
-//      as the null vector of the 2x2 matrix [U V]^T (B - x_b I) [U V]; the middle one as a cross product.
-// When the two non-isolated eigenvalues are closer than ~1e-5 of the matrix scale the deflated discriminant loses digits
-// (the eigenvalues would still be good to ~1e-11 of the scale) and the caller falls back to the Jacobi solver; for planar
-// voxels this concerns ~1e-5 of the matrices.  Compiles for the host too (tests/test_eig3_cpu.py checks it against
-// numpy.linalg.eigh on the KAT-3 fixture without a GPU).
+//      trigonometric seed + three f64 Newton steps (two with the raw reciprocal, one exact);
+//   3. its eigenvector without iteration (Eberly, "A Robust Eigensolver for 3x3 Symmetric Matrices"): v_a = largest cross product
+//      of two rows of B - x_a I; {U, W} an orthonormal basis of its complement;
+//   4. the other two eigenpairs from the symmetric 2x2 M = [U W]^T B [U W] by one stable Jacobi rotation.
+// When the two non-isolated eigenvalues are closer than ~1e-5 of the matrix scale (the discriminant of the deflated quadratic,
+// (x_b - x_c)^2 = 4 c1 - 3 x_a^2, below 1e-10 c1) the caller falls back to the Jacobi solver (vba_kernels_factor.hpp), as it does
+// for zero, non-finite and A = qI input.  For planar voxels (lambda0 << lambda1 ~ lambda2 spread over a patch) that is rare; every
+// line-like covariance (lambda0 ~ lambda1 << lambda2: a pole, an edge, one ring of points on a wall) takes the fallback, because
+// the test measures the pair's gap against the matrix scale.  Compiles for the host too (tests/test_eig3_cpu.py).
 #pragma once
 #include <cmath>
 
@@ -113,17 +116,11 @@ VBE_HD bool eig3_direct(double a00, double a01, double a02, double a11, double a
     ri = ri * (2.0 - fp * ri);
     xa -= f * ri;
   }
-  // deflation: the other two roots of the |c0| cubic are (-x_a -+ sqrt(D)) / 2 with D = 4 c1 - 3 x_a^2 = (x_b - x_c)^2
+  // near-double pair test: D = 4 c1 - 3 x_a^2 = (x_b - x_c)^2, the discriminant of the deflated quadratic
   const double D = 4.0 * c1 - 3.0 * xa * xa;
   if (!(D > 1e-10 * c1)) return false;                       // near-double pair (or NaN): iterative solver
-  const double sD = D * eig_rsqrt(D);
   const bool neg = c0 < 0.0;
-  // roots of the actual cubic, ascending
-  double x0, x1, x2r;
-  if (!neg) { x2r = xa; x0 = 0.5 * (-xa - sD); x1 = 0.5 * (-xa + sD); }
-  else { x0 = -xa; x1 = 0.5 * (xa - sD); x2r = 0.5 * (xa + sD); }
-  const double xiso = neg ? x0 : x2r;                        // isolated root: eigenvector from cross products
-  const double xoth = neg ? x2r : x0;                        // the other extreme: eigenvector from the 2x2 complement problem
+  const double xiso = neg ? -xa : xa;                        // isolated root: eigenvector from cross products
   // v_a: best cross product of two rows of B - x_iso I
   const double r00 = b00 - xiso, r11 = b11 - xiso, r22 = b22 - xiso;
   const double p0x = a01 * a12 - a02 * r11, p0y = a02 * a01 - r00 * a12, p0z = r00 * r11 - a01 * a01;   // row0 x row1
@@ -140,26 +137,43 @@ VBE_HD bool eig3_direct(double a00, double a01, double a02, double a11, double a
   if (fabs(ax) > fabs(ay)) { const double ri = eig_rsqrt(ax * ax + az * az); ux = -az * ri; uy = 0.0; uz = ax * ri; }
   else { const double ri = eig_rsqrt(ay * ay + az * az); ux = 0.0; uy = az * ri; uz = -ay * ri; }
   const double wx = ay * uz - az * uy, wy = az * ux - ax * uz, wz = ax * uy - ay * ux;
-  // M = [U W]^T (B - x_oth I) [U W]
+  // M = [U W]^T B [U W]: the pair is its eigen-decomposition.  One Jacobi rotation diagonalises it backward-stably (pair eigenvalues
+  // to ~eps of the scale, their vectors to ~eps / relative gap); the null vector of M - x_oth I with x_oth from the deflated
+  // quadratic, as before, carried that root's cancellation error (~eps / gap) into the vectors and lost ~eps / gap^2.
   const double bux = b00 * ux + a01 * uy + a02 * uz, buy = a01 * ux + b11 * uy + a12 * uz, buz = a02 * ux + a12 * uy + b22 * uz;
   const double bwx = b00 * wx + a01 * wy + a02 * wz, bwy = a01 * wx + b11 * wy + a12 * wz, bwz = a02 * wx + a12 * wy + b22 * wz;
-  const double m00 = (ux * bux + uy * buy + uz * buz) - xoth;
+  const double m00 = ux * bux + uy * buy + uz * buz;
   const double m01 = ux * bwx + uy * bwy + uz * bwz;
-  const double m11 = (wx * bwx + wy * bwy + wz * bwz) - xoth;
-  // null vector of M from its larger row (p, q): (q, -p)
-  const bool first = fabs(m00) + fabs(m01) >= fabs(m01) + fabs(m11);
-  const double pp = first ? m00 : m01, qq = first ? m01 : m11;
-  const double nn = pp * pp + qq * qq;
-  double cu = 1.0, cw = 0.0;
-  if (nn > 0.0) { const double ri = eig_rsqrt(nn); cu = qq * ri; cw = -pp * ri; }
-  const double bx = cu * ux + cw * wx, by = cu * uy + cw * wy, bz = cu * uz + cw * wz;
-  // middle eigenvector
-  const double mx = ay * bz - az * by, my = az * bx - ax * bz, mz = ax * by - ay * bx;
+  const double m11 = wx * bwx + wy * bwy + wz * bwz;
+  // t = tan(angle) = 2 m01 sgn(h) / (|h| + sqrt(h^2 + 4 m01^2)), h = m11 - m00 (the smaller root of t^2 + (h / m01) t - 1 = 0);
+  // the entries are O(1) after the scaling and the pair's gap is >= 1e-5 of it here, so nothing over- or underflows
+  const double h = m11 - m00, tw = 2.0 * m01;
+  double t = 0.0;
+  if (tw != 0.0) {
+    const double hh = h * h + tw * tw;
+    const double den = fabs(h) + hh * eig_rsqrt(hh);
+    double ri = eig_rcp_approx(den);
+    ri = ri * (2.0 - den * ri);
+    const double num = h < 0.0 ? -tw : tw;
+    t = num * ri;
+    t += ri * (num - den * t);                                 // quotient to ~1 ulp
+  }
+  const double cr = eig_rsqrt(1.0 + t * t), sr = t * cr;
+  // M <- J^T M J with J = [c s; -s c]: diagonal (m00 - t m01, m11 + t m01), eigenvectors c U - s W and s U + c W
+  double e1 = m00 - t * m01, e2 = m11 + t * m01;
+  double px = cr * ux - sr * wx, py = cr * uy - sr * wy, pz = cr * uz - sr * wz;
+  double qx = sr * ux + cr * wx, qy = sr * uy + cr * wy, qz = sr * uz + cr * wz;
+  if (e2 < e1) {
+    const double te = e1; e1 = e2; e2 = te;
+    double tv = px; px = qx; qx = tv; tv = py; py = qy; qy = tv; tv = pz; pz = qz; qz = tv;
+  }
+  // roots ascending (the isolated one lies >= sqrt(c1) away from the pair, on the far side)
+  const double x0 = neg ? xiso : e1, x1 = neg ? e1 : e2, x2r = neg ? e2 : xiso;
   const double un = ldexp(1.0, e);
   o.w0 = (q + x0) * un; o.w1 = (q + x1) * un; o.w2 = (q + x2r) * un;
-  o.v00 = neg ? ax : bx; o.v10 = neg ? ay : by; o.v20 = neg ? az : bz;
-  o.v02 = neg ? bx : ax; o.v12 = neg ? by : ay; o.v22 = neg ? bz : az;
-  o.v01 = mx; o.v11 = my; o.v21 = mz;
+  o.v00 = neg ? ax : px; o.v10 = neg ? ay : py; o.v20 = neg ? az : pz;
+  o.v01 = neg ? px : qx; o.v11 = neg ? py : qy; o.v21 = neg ? pz : qz;
+  o.v02 = neg ? qx : ax; o.v12 = neg ? qy : ay; o.v22 = neg ? qz : az;
   return true;
 }
 

@@ -58,10 +58,12 @@ __device__ __forceinline__ void jacobi_rot(double &app, double &aqq, double &apq
   // an off-diagonal below ulp/200 of both diagonals cannot change them any more: drop it (at any sweep)
   if (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq)) { apq = 0.0; return; }
   // t = sgn(a) b / (|a| + sqrt(a^2 + b^2)),  a = (aqq - app) / 2, b = apq   (the smaller root of t^2 + 2 theta t - 1 = 0);
-  // operands are scaled by the larger magnitude first so that the f32 range cannot over/underflow
+  // operands are scaled by the exponent of the larger magnitude first (exact, and defined for subnormal operands, where a
+  // reciprocal overflows) so that the f32 range cannot over/underflow
   const double a = 0.5 * (aqq - app);
-  const double inv_scale = __builtin_amdgcn_rcp(fmax(fabs(a), fabs(apq)));   // raw v_rcp_f64: only the ratio a : b matters
-  const float af = (float)(a * inv_scale), bf = (float)(apq * inv_scale);
+  int ex;
+  (void)frexp(fmax(fabs(a), fabs(apq)), &ex);
+  const float af = (float)ldexp(a, -ex), bf = (float)ldexp(apq, -ex);
   const float tf = bf * __builtin_amdgcn_rcpf(fabsf(af) + __builtin_amdgcn_sqrtf(af * af + bf * bf));   // raw v_sqrt_f32 / v_rcp_f32
   const double t = (af < 0.0f) ? -(double)tf : (double)tf;
   const double x = 1.0 + t * t;
@@ -85,9 +87,17 @@ __device__ __forceinline__ void jacobi_rot(double &app, double &aqq, double &apq
 #define VBA_SWAP(a, b) { double _t = a; a = b; b = _t; }
 
 // in: lower triangle a00,a10,a20,a11,a21,a22.  out: w0<=w1<=w2, V (row-major, columns = eigenvectors).  Plain cyclic sweeps in f64:
-// this is the rare fallback of eig3_sym_dev below (near-double eigenvalue pairs, multiples of the identity, degenerate input),
-// so it is written for few registers, not for speed (the sweep loop is not unrolled).
+// this is the fallback of eig3_sym_dev below (near-double eigenvalue pairs — every line-like covariance among them —, multiples of
+// the identity, degenerate input), written for few registers, not for speed (the sweep loop is not unrolled).
 __device__ __forceinline__ Eig3 eig3_jacobi_dev(double a00, double a01, double a02, double a11, double a12, double a22) {
+  // exact power-of-two scaling of the largest entry into [0.5, 1), as the direct path does: subnormal and huge matrices run in the
+  // normal range (NaN input stays NaN)
+  int e = 0;
+  {
+    const double s = fmax(fmax(fmax(fabs(a00), fabs(a11)), fabs(a22)), fmax(fmax(fabs(a01), fabs(a02)), fabs(a12)));
+    if (s > 0.0 && s <= 1.7976931348623157e308) (void)frexp(s, &e);
+  }
+  a00 = ldexp(a00, -e); a01 = ldexp(a01, -e); a02 = ldexp(a02, -e); a11 = ldexp(a11, -e); a12 = ldexp(a12, -e); a22 = ldexp(a22, -e);
   double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;
 #pragma unroll 1
   for (int sweep = 0; sweep < 30; sweep++) {
@@ -100,13 +110,13 @@ __device__ __forceinline__ Eig3 eig3_jacobi_dev(double a00, double a01, double a
   if (a22 < a00) { VBA_SWAP(a00, a22); VBA_SWAP(v00, v02); VBA_SWAP(v10, v12); VBA_SWAP(v20, v22); }
   if (a22 < a11) { VBA_SWAP(a11, a22); VBA_SWAP(v01, v02); VBA_SWAP(v11, v12); VBA_SWAP(v21, v22); }
   Eig3 o;
-  o.w0 = a00; o.w1 = a11; o.w2 = a22;
+  o.w0 = ldexp(a00, e); o.w1 = ldexp(a11, e); o.w2 = ldexp(a22, e);
   o.v00 = v00; o.v01 = v01; o.v02 = v02; o.v10 = v10; o.v11 = v11; o.v12 = v12; o.v20 = v20; o.v21 = v21; o.v22 = v22;
   return o;
 }
 
-// The plane fit's eigen-solver: direct (vba_eig3.hpp: trigonometric seed + Newton for the isolated root, deflation, eigenvectors
-// from cross products and a 2x2 complement problem); matrices with a near-double eigenvalue pair, multiples of the identity and
+// The plane fit's eigen-solver: direct (vba_eig3.hpp: trigonometric seed + Newton for the isolated root, its eigenvector from cross
+// products, the pair by one Jacobi rotation of the 2x2 complement problem); matrices with a near-double eigenvalue pair, multiples of the identity and
 // non-finite input take the Jacobi sweeps above.
 __device__ __forceinline__ void eig3_sym_dev(double a00, double a01, double a02, double a11, double a12, double a22,
                                              double &w0, double &w1, double &w2, double *V) {
