@@ -410,8 +410,8 @@ int vba_io_read_lidarstate(const char *path, int cap, double *states, double *v6
 
 /* ------------------------------------------------------------------------------------------------
  * Loop retrieval and verification of the loop-closure thread (VS:2404-2541): the database half of
- * STDescManager (BTC.h, BTC.cpp) and icp_normal (loop_refine.hpp = LR).  Descriptor GENERATION (GenerateSTDescs,
- * BTC.cpp:279-980) stays with the caller, which hands over descriptors and plane clouds.  A database hangs off a context
+ * STDescManager (BTC.h, BTC.cpp) and icp_normal (loop_refine.hpp = LR).  Descriptors and plane clouds come from the caller or
+ * from vba_btc_generate_stds below (GenerateSTDescs on the device).  A database hangs off a context
  * and runs on its stream; the loop-closure thread owns its own context.  Every result is the same bits
  * in every run; vba_options::deterministic plays no part here.  DESIGN.md §11.
  *
@@ -485,6 +485,67 @@ int vba_btc_icp_normal(vba_btc_db *src_db, int src_frame, vba_btc_db *tar_db, in
                        int *ok, double *eig, int *iters);
 /* candidates of the last search on db (*n = how many; at most cap written) */
 int vba_btc_last_candidates(vba_btc_db *db, int cap, vba_btc_candidate *out, int *n);
+
+/* ------------------------------------------------------------------------------------------------
+ * Descriptor generation (GenerateSTDescs, BTC.cpp:156-203, with BTC.cpp:279-1126) on the device.  The input is the keyframe's
+ * merged cloud (PointXYZI x y z as float [n][3], host memory, finite).  One call is one stream-ordered sequence with a single host
+ * synchronisation at the end (unless it outgrows its buffers: vba_btc_gen_reserve); the plane cloud goes straight into the
+ * database's cloud storage.  DESIGN.md §11a.
+ *
+ * Order contract (the reference iterates unordered_maps; this fixes the order, and results are the same bits in every run):
+ *  1. voxel key (int64_t)(p / voxel_size - (p / voxel_size < 0 ? 1 : 0)) in double from the float point (|key| < 2^20, else
+ *     VBA_ERR_BAD_ARG); voxels ordered by the index of their first point; a voxel's points in input order; centre and covariance
+ *     are the sequential sums in that order (sum p p^T / N - c c^T); a voxel is fitted when it has MORE than voxel_init_num points.
+ *  2. plane fit: the project's symmetric 3x3 solver (direct path + Jacobi fallback, correctly rounded primitives); normal sign:
+ *     the component of largest magnitude is positive, the lowest index wins a tie (Eigen's EigenSolver sign is not reproduced:
+ *     a deviation; the sign decides the projection image's y axis).
+ *  3. plane cloud and origin_list in voxel order; get_project_plane / merge_plane replay the greedy id assignment (iter
+ *     descending, iter2 ascending); each group folds its members in ascending index from its first; both sorts by points_size_
+ *     are stable.
+ *  4. extract_binary: per-cell sums in the order of the kept points; the first strict maximum of a 5x5 segment in x-then-y
+ *     order; corners in (x segment, y segment) order.  A point whose height index equals cut_num (dis near proj_dis_max) counts
+ *     in the cell but sets no occupancy bit.
+ *  5. neighbours (NMS radius search, generate_std kNN) exact in float: squared L2 over x then y then z, ties to the earlier index,
+ *     radius test d^2 < (float)(r r); kNN takes min(K, corners) neighbours.
+ *  6. triangles: the key is (int64_t)(float)(side * 1000); the first in (i, m, n) order wins; output in emission order.
+ * An empty origin_list takes the single_plane branch (normal (0, 0, 1) through the first point); n == 0 pushes an empty plane
+ * cloud and gives no descriptors.  angle_ is not produced. */
+typedef struct vba_btc_gen_config {   /* the ConfigSetting fields (BTC.h:22-46) GenerateSTDescs reads, with the reference's types */
+  int useful_corner_num;
+  float plane_merge_normal_thre, plane_merge_dis_thre, plane_detection_thre, voxel_size;
+  int voxel_init_num, proj_plane_num;
+  float proj_image_resolution, proj_image_high_inc, proj_dis_min, proj_dis_max, summary_min_thre;
+  int line_filter_enable, touch_filter_enable;
+  float descriptor_near_num, descriptor_min_len, descriptor_max_len, non_max_suppression_radius, std_side_resolution;
+} vba_btc_gen_config;
+
+/* read_parameters (BTC.cpp:3-68), the generation fields.  Host only. */
+int vba_btc_default_gen_config(int is_high_fly, vba_btc_gen_config *cfg);
+/* vba_btc_get_gen_config reads the current one back.  A database starts with vba_btc_default_gen_config(0).  VBA_ERR_BAD_ARG outside the supported range: useful_corner_num >= 1,
+ * voxel_size > 0, voxel_init_num >= 0, 1 <= proj_plane_num <= 8, proj_image_resolution > 0, proj_image_high_inc > 0,
+ * 3 <= (int)descriptor_near_num <= 32, 0 <= descriptor_min_len, descriptor_max_len <= 2000, std_side_resolution > 0. */
+int vba_btc_set_gen_config(vba_btc_db *db, const vba_btc_gen_config *cfg);
+int vba_btc_get_gen_config(const vba_btc_db *db, vba_btc_gen_config *cfg);
+/* GenerateSTDescs(input_cloud, stds_vec, id): pushes the plane cloud with seq = id (as vba_btc_push_plane_cloud would) and writes
+ * *n_stds descriptor rows and masks in the layout vba_btc_add_stds / vba_btc_search_loop* take, frame_number_ = current_frame_id_
+ * = the number of vba_btc_add_stds calls on db so far.  cap (rows) must be >= useful_corner_num * C(K - 1, 2), K =
+ * (int)descriptor_near_num, and cut_num = (int)((proj_dis_max - proj_dis_min) / proj_image_high_inc) (49 for both shipped
+ * configurations) must be <= the database's occupy_len; otherwise VBA_ERR_BAD_ARG with no side effect (no plane cloud pushed). */
+int vba_btc_generate_stds(vba_btc_db *db, int n, const float *xyz, int id, int cap, double *rows, uint64_t *bits, int *n_stds);
+/* read back plane cloud `frame` (float [n][6]); *n = its size, at most cap points written */
+int vba_btc_plane_cloud(vba_btc_db *db, int frame, int cap, float *xyz_normal, int *n);
+/* binary_list of the last vba_btc_generate_stds (for tests): loc_summary [n][4] = location_ x y z, summary_; bits [n] */
+int vba_btc_last_corners(vba_btc_db *db, int cap, double *loc_summary, uint64_t *bits, int *n);
+/* Capacity hint for generation (no reference counterpart): buffers for clouds of up to `points` points (voxel buffers are bounded
+ * by it), projection images of `cells` cells (<= 2^24), and database room for the plane clouds and offsets of `frames` more calls,
+ * so that such calls make no device or pinned-host allocation.  Results do not depend on it.  Without it buffers grow by doubling;
+ * a call whose projection image or corner list outgrows its buffer grows it and runs its sequence once more (a second
+ * synchronisation).  A projection image above 2^24 cells (points far out in the plane within proj_dis_max of it) is refused with
+ * VBA_ERR_CAPACITY before anything is allocated for it. */
+int vba_btc_gen_reserve(vba_btc_db *db, int64_t points, int64_t cells, int frames);
+/* device and pinned-host allocations made by generation on db so far (its own buffers and the growth of the database's plane-cloud
+ * storage and offset table in vba_btc_generate_stds), and the bytes of the generator's device buffers */
+int vba_btc_gen_allocations(vba_btc_db *db, int *count, int64_t *bytes);
 
 #ifdef __cplusplus
 }

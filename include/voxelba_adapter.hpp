@@ -408,7 +408,7 @@ inline std::vector<ScanPoseRec> read_lidarstate(const std::string &filename) {
 }
 
 // ---- loop retrieval: the database half of STDescManager (BTC.h:228-300; AddSTDescs / SearchLoop, BTC.cpp:205-277) and icp_normal
-// (loop_refine.hpp:47-139).  Descriptors stay generated on the host (GenerateSTDescs); the structs below mirror STD and
+// (loop_refine.hpp:47-139), and descriptor generation (GenerateSTDescs, BTC.cpp:156-203) on the device.  The structs below mirror STD and
 // BinaryDescriptor (BTC.h:59-84) with the occupancy array as a bit mask (entry k = bit k) and angle_ left out (retrieval never
 // reads it).  A loop transform is (t, R row-major), the pair<Vector3d, Matrix3d> of the reference.
 struct BinaryDescriptor {
@@ -445,9 +445,14 @@ class BtcDatabase {
  public:
   struct ConfigSetting { int skip_near_num_; };   // the field the node writes to close a session (VS:410, VS:2242)
   ConfigSetting config_setting_;
-  BtcDatabase(Context &ctx, const vba_btc_config &cfg) : ctx_(ctx.get()) {
+  BtcDatabase(Context &ctx, const vba_btc_config &cfg, const vba_btc_gen_config *gen_cfg = nullptr) : ctx_(ctx.get()) {
     check(ctx_, vba_btc_create(ctx_, &cfg, &db_));
     config_setting_.skip_near_num_ = cfg.skip_near_num;
+    if (gen_cfg) check(ctx_, vba_btc_set_gen_config(db_, gen_cfg));
+    vba_btc_gen_config g;
+    check(ctx_, vba_btc_get_gen_config(db_, &g));
+    const int k1 = (int)g.descriptor_near_num - 1;
+    gen_cap_ = g.useful_corner_num * (k1 * (k1 - 1) / 2);
   }
   ~BtcDatabase() { vba_btc_destroy(db_); }
   BtcDatabase(const BtcDatabase &) = delete;
@@ -458,6 +463,27 @@ class BtcDatabase {
     check(ctx_, vba_btc_push_plane_cloud(db_, (int)(xyz_normal.size() / 6), xyz_normal.data(), seq));
   }
   int plane_cloud_num() const { return vba_btc_num_frames(db_); }      // plane_cloud_vec_.size()
+  // GenerateSTDescs(input_cloud, stds_vec, id) (BTC.cpp:156-203): xyz = the PointXYZI cloud's x y z (n x 3 floats); pushes the plane
+  // cloud with header.seq = id; frame_number_ = current_frame_id_ (the AddSTDescs count)
+  void GenerateSTDescs(const std::vector<float> &xyz, std::vector<STD> &stds_vec, int id) {
+    std::vector<double> rows((size_t)(gen_cap_ > 0 ? gen_cap_ : 1) * VBA_BTC_ROW_LEN);
+    std::vector<uint64_t> bits((size_t)(gen_cap_ > 0 ? gen_cap_ : 1) * 3);
+    int n = 0;
+    check(ctx_, vba_btc_generate_stds(db_, (int)(xyz.size() / 3), xyz.data(), id, gen_cap_, rows.data(), bits.data(), &n));
+    stds_vec.assign(n, STD{});
+    for (int i = 0; i < n; i++) {
+      const double *r = rows.data() + (size_t)i * VBA_BTC_ROW_LEN;
+      STD &d = stds_vec[i];
+      BinaryDescriptor *b[3] = {&d.binary_A_, &d.binary_B_, &d.binary_C_};
+      for (int u = 0; u < 3; u++) { d.triangle_[u] = r[u]; d.center_[u] = r[3 + u]; }
+      d.frame_number_ = (int)r[6];
+      for (int e = 0; e < 3; e++) {
+        for (int u = 0; u < 3; u++) b[e]->location_[u] = r[7 + 3 * e + u];
+        b[e]->summary_ = (unsigned char)r[16 + e];
+        b[e]->occupy_bits = bits[3 * (size_t)i + e];
+      }
+    }
+  }
   int plane_cloud_seq(int frame) const { int s = 0; check(ctx_, vba_btc_frame_seq(db_, frame, &s)); return s; }
   void AddSTDescs(const std::vector<STD> &stds) {                          // BTC.cpp:258-277
     std::vector<double> rows; std::vector<uint64_t> bits;
@@ -489,6 +515,7 @@ class BtcDatabase {
  private:
   vba_ctx *ctx_ = nullptr;
   vba_btc_db *db_ = nullptr;
+  int gen_cap_ = 0;                // row capacity GenerateSTDescs needs: useful_corner_num * C(K - 1, 2)
 };
 
 // icp_normal(pl_src, pl_tar, pose, icp_eigval) (loop_refine.hpp:47-139) at its call site VS:2434, both clouds resident: pose

@@ -36,6 +36,8 @@ EXPORTS = [
     "vba_btc_default_config", "vba_btc_create", "vba_btc_destroy", "vba_btc_set_skip_near_num", "vba_btc_push_plane_cloud",
     "vba_btc_num_frames", "vba_btc_frame_seq", "vba_btc_add_stds", "vba_btc_search_loop", "vba_btc_search_loop_sessions",
     "vba_btc_icp_normal", "vba_btc_last_candidates", "vba_btc_reserve",
+    "vba_btc_default_gen_config", "vba_btc_set_gen_config", "vba_btc_generate_stds", "vba_btc_plane_cloud", "vba_btc_last_corners",
+    "vba_btc_gen_reserve", "vba_btc_gen_allocations", "vba_btc_get_gen_config",
 ]
 
 
@@ -70,6 +72,33 @@ class BtcCandidate(C.Structure):
 
 
 BTC_ROW_LEN = 19
+
+
+class BtcGenConfig(C.Structure):
+    """vba_btc_gen_config: the ConfigSetting fields (BTC.h:22-46) GenerateSTDescs reads, with the reference's float types."""
+    _fields_ = [
+        ("useful_corner_num", C.c_int), ("plane_merge_normal_thre", C.c_float), ("plane_merge_dis_thre", C.c_float),
+        ("plane_detection_thre", C.c_float), ("voxel_size", C.c_float), ("voxel_init_num", C.c_int), ("proj_plane_num", C.c_int),
+        ("proj_image_resolution", C.c_float), ("proj_image_high_inc", C.c_float), ("proj_dis_min", C.c_float),
+        ("proj_dis_max", C.c_float), ("summary_min_thre", C.c_float), ("line_filter_enable", C.c_int),
+        ("touch_filter_enable", C.c_int), ("descriptor_near_num", C.c_float), ("descriptor_min_len", C.c_float),
+        ("descriptor_max_len", C.c_float), ("non_max_suppression_radius", C.c_float), ("std_side_resolution", C.c_float),
+    ]
+
+
+def btc_default_gen_config(is_high_fly=0) -> BtcGenConfig:
+    """read_parameters (BTC.cpp:3-68), generation fields."""
+    f = BtcGenConfig()
+    st = load().vba_btc_default_gen_config(C.c_int(int(is_high_fly)), C.byref(f))
+    if st:
+        raise VbaError(st)
+    return f
+
+
+def btc_max_stds(gcfg) -> int:
+    """useful_corner_num * C(K - 1, 2), K = (int)descriptor_near_num: the row capacity generate_stds needs"""
+    k1 = int(gcfg.descriptor_near_num) - 1
+    return int(gcfg.useful_corner_num) * (k1 * (k1 - 1) // 2)
 
 
 def btc_default_config(is_high_fly=0) -> BtcConfig:
@@ -151,6 +180,46 @@ class BtcDb:
         self.ctx._chk(self.lib.vba_btc_last_candidates(self.h, C.c_int(256), out, C.byref(n)))
         return [dict(frame=o.frame, votes=o.votes, match_len=o.match_len, max_vote_index=o.max_vote_index, max_vote=o.max_vote,
                      score=o.score) for o in out[:n.value]]
+
+    def set_gen_config(self, gcfg):
+        self.ctx._chk(self.lib.vba_btc_set_gen_config(self.h, C.byref(gcfg)))
+        self.gcfg = gcfg
+
+    def gen_reserve(self, points=0, cells=0, frames=1):
+        """capacity hint for generate_stds: clouds of `points` points, projection images of `cells` cells, `frames` more calls"""
+        self.ctx._chk(self.lib.vba_btc_gen_reserve(self.h, C.c_int64(points), C.c_int64(cells), C.c_int(frames)))
+
+    def gen_allocations(self):
+        n = C.c_int(); b = C.c_int64()
+        self.ctx._chk(self.lib.vba_btc_gen_allocations(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def generate_stds(self, xyz, id, cap=None):
+        """GenerateSTDescs(cloud, stds, id): pushes the plane cloud (seq = id); returns (rows [n][19], bits [n][3])"""
+        a = np.ascontiguousarray(np.reshape(xyz, (-1, 3)), dtype=np.float32)
+        if cap is None:
+            cap = btc_max_stds(getattr(self, "gcfg", None) or btc_default_gen_config(0))
+        rows = np.zeros((max(cap, 1), BTC_ROW_LEN)); bits = np.zeros((max(cap, 1), 3), dtype=np.uint64)
+        n = C.c_int()
+        self.ctx._chk(self.lib.vba_btc_generate_stds(self.h, C.c_int(len(a)), a.ctypes.data_as(C.POINTER(C.c_float)), C.c_int(int(id)),
+                                                     C.c_int(cap), _p(rows), bits.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)))
+        return rows[:n.value].copy(), bits[:n.value].copy()
+
+    def plane_cloud(self, frame):
+        n = C.c_int()
+        self.ctx._chk(self.lib.vba_btc_plane_cloud(self.h, C.c_int(frame), C.c_int(0), None, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 6), dtype=np.float32)
+        self.ctx._chk(self.lib.vba_btc_plane_cloud(self.h, C.c_int(frame), C.c_int(n.value), out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n)))
+        return out[:n.value].copy()
+
+    def last_corners(self):
+        """binary_list of the last generate_stds: (locations [n][3], summaries [n], masks [n])"""
+        n = C.c_int()
+        self.ctx._chk(self.lib.vba_btc_last_corners(self.h, C.c_int(0), None, None, C.byref(n)))
+        ls = np.zeros((max(n.value, 1), 4)); b = np.zeros(max(n.value, 1), dtype=np.uint64)
+        self.ctx._chk(self.lib.vba_btc_last_corners(self.h, C.c_int(n.value), _p(ls), b.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)))
+        k = n.value
+        return ls[:k, :3].copy(), ls[:k, 3].astype(np.int64), b[:k].copy()
 
     def icp_normal(self, src_frame, tar_db, tar_frame, t, R, icp_eigval):
         """icp_normal(plane cloud src_frame of this db, plane cloud tar_frame of tar_db, (t, R), icp_eigval)"""

@@ -31,9 +31,14 @@
 
 namespace vba {
 
+// The primitives below take IEEE = true for a variant built from correctly rounded operations only (division, sqrt, and an f32
+// polynomial for the cosine seed), whose host and device builds give the same bits (the plane fit of descriptor generation,
+// vba_btcgen_fit.hpp / vba_btcgen.hip, checked bit for bit against a host build).  IEEE = false is the fast device form every other caller uses.
 // reciprocal square root to full f64 precision: v_rsq_f64 (~26 bits) + two Newton steps on the device
+template <bool IEEE = false>
 VBE_HD double eig_rsqrt(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  if (IEEE) return 1.0 / sqrt(x);
   double c = __builtin_amdgcn_rsq(x);
   c = c * (1.5 - 0.5 * x * c * c);
   c = c * (1.5 - 0.5 * x * c * c);
@@ -43,29 +48,40 @@ VBE_HD double eig_rsqrt(double x) {
 #endif
 }
 // reciprocal good to ~26 bits: enough inside a Newton iteration that corrects itself
+template <bool IEEE = false>
 VBE_HD double eig_rcp_approx(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  if (IEEE) return 1.0 / x;
   return __builtin_amdgcn_rcp(x);
 #else
   return 1.0 / x;
 #endif
 }
+template <bool IEEE = false>
 VBE_HD float eig_cos_f32(float x) {   // cos(x), |x| <= pi/3
+  if (IEEE) {                         // Taylor to x^8: |error| < 1e-9 on [0, pi/6], the range of the seed
+    const float x2 = x * x;
+    return 1.0f + x2 * (-0.5f + x2 * (4.16666679e-2f + x2 * (-1.38888892e-3f + x2 * 2.48015876e-5f)));
+  }
 #if defined(__HIP_DEVICE_COMPILE__)
   return __builtin_amdgcn_cosf(x * 0.15915494309189535f);   // v_cos_f32 takes revolutions
 #else
   return std::cos(x);
 #endif
 }
+template <bool IEEE = false>
 VBE_HD float eig_sqrt_f32(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  if (IEEE) return sqrtf(x);
   return __builtin_amdgcn_sqrtf(x);
 #else
   return std::sqrt(x);
 #endif
 }
+template <bool IEEE = false>
 VBE_HD float eig_rcp_f32(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  if (IEEE) return 1.0f / x;
   return __builtin_amdgcn_rcpf(x);
 #else
   return 1.0f / x;
@@ -78,6 +94,7 @@ struct Eig3 { double w0, w1, w2, v00, v01, v02, v10, v11, v12, v20, v21, v22; };
 
 // (results in a struct of scalars, not through a pointer to the caller's array: merged with the fallback's results they stay in
 //  registers, whereas stores through the shared pointer were turned into a run-time indexed private array, i.e. scratch memory)
+template <bool IEEE = false>
 VBE_HD bool eig3_direct(double a00, double a01, double a02, double a11, double a12, double a22, Eig3 &o) {
   const double s = fmax(fmax(fmax(fabs(a00), fabs(a11)), fabs(a22)), fmax(fmax(fabs(a01), fabs(a02)), fabs(a12)));
   if (!(s > 1e-290 && s < 1e290)) return false;
@@ -93,12 +110,12 @@ VBE_HD bool eig3_direct(double a00, double a01, double a02, double a11, double a
   // f32 seed of the isolated root: x = 2 m cos(acos(r) / 3), m = sqrt(c1 / 3), r = |c0| / (2 m^3)  (the largest root of the cubic
   // with c0 replaced by |c0|; for c0 < 0 the smallest root is its negative)
   const float c1f = (float)c1, c0f = fabsf((float)c0);
-  const float m = eig_sqrt_f32(c1f * (1.0f / 3.0f));
-  float r = c0f * eig_rcp_f32(2.0f * m * m * m);
+  const float m = eig_sqrt_f32<IEEE>(c1f * (1.0f / 3.0f));
+  float r = c0f * eig_rcp_f32<IEEE>(2.0f * m * m * m);
   r = fminf(r, 1.0f);
   // acos(r), 0 <= r <= 1: sqrt(1 - r) * P(r)   (Abramowitz & Stegun 4.4.45, |error| <= 7e-5)
-  const float ac = eig_sqrt_f32(1.0f - r) * (1.5707288f + r * (-0.2121144f + r * (0.0742610f - 0.0187293f * r)));
-  double xa = (double)(2.0f * m * eig_cos_f32(ac * (1.0f / 3.0f)));
+  const float ac = eig_sqrt_f32<IEEE>(1.0f - r) * (1.5707288f + r * (-0.2121144f + r * (0.0742610f - 0.0187293f * r)));
+  double xa = (double)(2.0f * m * eig_cos_f32<IEEE>(ac * (1.0f / 3.0f)));
   const double c0a = fabs(c0);
   // Newton on f(x) = (x^2 - c1) x - |c0|, f' = 3 x^2 - c1 >= 2 c1 at the isolated root (x_a >= sqrt(c1))
 #pragma unroll
@@ -106,13 +123,13 @@ VBE_HD bool eig3_direct(double a00, double a01, double a02, double a11, double a
     const double x2 = xa * xa;
     const double f = (x2 - c1) * xa - c0a;
     const double fp = 3.0 * x2 - c1;
-    xa -= f * eig_rcp_approx(fp);
+    xa -= f * eig_rcp_approx<IEEE>(fp);
   }
   {   // one last step with an accurate quotient: f / fp by one Newton refinement of the reciprocal
     const double x2 = xa * xa;
     const double f = (x2 - c1) * xa - c0a;
     const double fp = 3.0 * x2 - c1;
-    double ri = eig_rcp_approx(fp);
+    double ri = eig_rcp_approx<IEEE>(fp);
     ri = ri * (2.0 - fp * ri);
     xa -= f * ri;
   }
@@ -131,11 +148,11 @@ VBE_HD bool eig3_direct(double a00, double a01, double a02, double a11, double a
   if (n1 > an) { ax = p1x; ay = p1y; az = p1z; an = n1; }
   if (n2 > an) { ax = p2x; ay = p2y; az = p2z; an = n2; }
   if (!(an > 0.0)) return false;
-  { const double ri = eig_rsqrt(an); ax *= ri; ay *= ri; az *= ri; }
+  { const double ri = eig_rsqrt<IEEE>(an); ax *= ri; ay *= ri; az *= ri; }
   // orthonormal basis {U, W} of the complement of v_a
   double ux, uy, uz;
-  if (fabs(ax) > fabs(ay)) { const double ri = eig_rsqrt(ax * ax + az * az); ux = -az * ri; uy = 0.0; uz = ax * ri; }
-  else { const double ri = eig_rsqrt(ay * ay + az * az); ux = 0.0; uy = az * ri; uz = -ay * ri; }
+  if (fabs(ax) > fabs(ay)) { const double ri = eig_rsqrt<IEEE>(ax * ax + az * az); ux = -az * ri; uy = 0.0; uz = ax * ri; }
+  else { const double ri = eig_rsqrt<IEEE>(ay * ay + az * az); ux = 0.0; uy = az * ri; uz = -ay * ri; }
   const double wx = ay * uz - az * uy, wy = az * ux - ax * uz, wz = ax * uy - ay * ux;
   // M = [U W]^T B [U W]: the pair is its eigen-decomposition.  One Jacobi rotation diagonalises it backward-stably (pair eigenvalues
   // to ~eps of the scale, their vectors to ~eps / relative gap); the null vector of M - x_oth I with x_oth from the deflated
@@ -151,14 +168,14 @@ VBE_HD bool eig3_direct(double a00, double a01, double a02, double a11, double a
   double t = 0.0;
   if (tw != 0.0) {
     const double hh = h * h + tw * tw;
-    const double den = fabs(h) + hh * eig_rsqrt(hh);
-    double ri = eig_rcp_approx(den);
+    const double den = fabs(h) + hh * eig_rsqrt<IEEE>(hh);
+    double ri = eig_rcp_approx<IEEE>(den);
     ri = ri * (2.0 - den * ri);
     const double num = h < 0.0 ? -tw : tw;
     t = num * ri;
     t += ri * (num - den * t);                                 // quotient to ~1 ulp
   }
-  const double cr = eig_rsqrt(1.0 + t * t), sr = t * cr;
+  const double cr = eig_rsqrt<IEEE>(1.0 + t * t), sr = t * cr;
   // M <- J^T M J with J = [c s; -s c]: diagonal (m00 - t m01, m11 + t m01), eigenvectors c U - s W and s U + c W
   double e1 = m00 - t * m01, e2 = m11 + t * m01;
   double px = cr * ux - sr * wx, py = cr * uy - sr * wy, pz = cr * uz - sr * wz;

@@ -16,4 +16,11 @@ hipError_t sort_pairs_u32(void *tmp, size_t &tmp_bytes, const unsigned int *keys
   return rocprim::radix_sort_pairs<config>(tmp, tmp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, end_bit, stream, false);
 }
 
+// The same stable radix sort on 64-bit keys (the voxel keys of descriptor generation, vba_btcgen.hip)
+hipError_t sort_pairs_u64(void *tmp, size_t &tmp_bytes, const unsigned long long *keys_in, unsigned long long *keys_out, const int *vals_in,
+                          int *vals_out, size_t n, unsigned int end_bit, hipStream_t stream) {
+  using config = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 8192>;
+  return rocprim::radix_sort_pairs<config>(tmp, tmp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, end_bit, stream, false);
+}
+
 }  // namespace vba

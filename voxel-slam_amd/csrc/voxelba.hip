@@ -15,6 +15,7 @@
 #include "vba_kernels_kd.hpp"
 #include "vba_kernels_init.hpp"
 #include "vba_kernels_btc.hpp"
+#include "vba_btcgen.hpp"
 #include "vba_io.hpp"
 #include <cstddef>
 #include "vba_hostmath.hpp"
@@ -2591,6 +2592,12 @@ struct vba_btc_db {
   int vcap = 0; int *d_votes = nullptr;
   int *d_cand = nullptr, *d_total = nullptr; double *d_cres = nullptr, *d_res = nullptr, *h_res = nullptr;
   bool have_search = false;                  // the last search ran the kernels (n > 0)
+  // descriptor generation (vba_btc_generate_stds): its configuration, device buffers, the AddSTDescs count (current_frame_id_)
+  // and the corners of the last call
+  vba_btc_gen_config gcfg{};
+  BtcGen *gen = nullptr;
+  int n_add = 0;
+  std::vector<double> last_loc; std::vector<uint64_t> last_bits;
   BtcCfgDev dev_cfg() const {
     BtcCfgDev f;
     f.skip_near = cfg.skip_near_num; f.cand_num = cfg.candidate_num; f.rough = cfg.rough_dis_threshold; f.sim = cfg.similarity_threshold;
@@ -2840,6 +2847,7 @@ int vba_btc_create(vba_ctx *c, const vba_btc_config *cfg, vba_btc_db **out) {
   HIPCHK(c, hipSetDevice(c->device));
   vba_btc_db *db = new vba_btc_db();
   db->ctx = c; db->cfg = *cfg;
+  vba_btc_default_gen_config(0, &db->gcfg);
   btc_table_init(db->tab, 1024);
   db->tab_mask = 1023;
   int st = btc_table_upload(db);
@@ -2872,6 +2880,7 @@ void vba_btc_destroy(vba_btc_db *db) {
                db->d_m, db->d_votes, db->d_cand, db->d_total, db->d_cres, db->d_res};
   for (void *q : p) if (q) hipFree(q);
   if (db->h_res) hipHostFree(db->h_res);
+  if (db->gen) { btcgen_free(*db->gen); delete db->gen; }
   delete db;
 }
 
@@ -2959,7 +2968,7 @@ int vba_btc_push_plane_cloud(vba_btc_db *db, int n, const float *xyz_normal, int
 
 int vba_btc_add_stds(vba_btc_db *db, int n, const double *rows, const uint64_t *bits) {   // BTC.cpp:258-277
   if (!db || n < 0 || (n > 0 && (!rows || !bits))) return VBA_ERR_BAD_ARG;
-  if (n == 0) return VBA_OK;
+  if (n == 0) { db->n_add++; return VBA_OK; }
   vba_ctx *c = db->ctx;
   int st = btc_check_rows(n, rows, bits, db->cfg.occupy_len);
   if (st) return st;
@@ -3040,6 +3049,7 @@ int vba_btc_add_stds(vba_btc_db *db, int n, const double *rows, const uint64_t *
   if (nt) k_btc_scatter<<<(nt + 255) / 256, 256, 0, c->stream>>>(nt, ds + 2 * (ne + nn), db->d_tab);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  db->n_add++;
   return VBA_OK;
 }
 
@@ -3130,6 +3140,208 @@ int vba_btc_icp_normal(vba_btc_db *src_db, int src_frame, vba_btc_db *tar_db, in
   if (eig) for (int k = 0; k < 3; k++) eig[k] = h->eig[k];
   if (iters) *iters = h->iters;
   if (ok) *ok = (h->eig[0] > icp_eigval && h->is_conv == 1) ? 1 : 0;
+  return VBA_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------ descriptor generation
+int vba_btc_default_gen_config(int is_high_fly, vba_btc_gen_config *f) {   // BTC.cpp:3-68
+  if (!f) return VBA_ERR_BAD_ARG;
+  std::memset(f, 0, sizeof(*f));
+  f->useful_corner_num = is_high_fly ? 200 : 100;
+  f->plane_merge_normal_thre = is_high_fly ? 0.3f : 0.1f;
+  f->plane_merge_dis_thre = is_high_fly ? 0.6f : 0.3f;
+  f->plane_detection_thre = is_high_fly ? 0.05f : 0.01f;
+  f->voxel_size = is_high_fly ? 2.0f : 1.0f;
+  f->voxel_init_num = 10;
+  f->proj_plane_num = is_high_fly ? 1 : 2;
+  f->proj_image_resolution = 0.5f;
+  f->proj_image_high_inc = is_high_fly ? 0.2f : 0.1f;
+  f->proj_dis_min = 0.0f;
+  f->proj_dis_max = is_high_fly ? 10.0f : 5.0f;
+  f->summary_min_thre = is_high_fly ? 6.0f : 10.0f;
+  f->line_filter_enable = is_high_fly ? 0 : 1;
+  f->touch_filter_enable = 0;
+  f->descriptor_near_num = 15.0f;
+  f->descriptor_min_len = is_high_fly ? 3.0f : 2.0f;
+  f->descriptor_max_len = 50.0f;
+  f->non_max_suppression_radius = is_high_fly ? 3.0f : 2.0f;
+  f->std_side_resolution = 0.2f;
+  return VBA_OK;
+}
+
+namespace {
+// cut_num of extract_binary: (int)((proj_dis_max_ - proj_dis_min_) / proj_image_high_inc_), the float fields promoted to double
+int btc_cut_num(const vba_btc_gen_config &g) {
+  return (int)(((double)g.proj_dis_max - (double)g.proj_dis_min) / (double)g.proj_image_high_inc);
+}
+size_t btc_max_stds(const vba_btc_gen_config &g) {      // useful_corner_num * C(K - 1, 2)
+  const size_t K1 = (size_t)((int)g.descriptor_near_num - 1);
+  return (size_t)g.useful_corner_num * (K1 * (K1 - 1) / 2);
+}
+BgCfg btc_bg_cfg(const vba_btc_gen_config &g) {
+  BgCfg f;
+  f.useful = g.useful_corner_num; f.vinit = g.voxel_init_num; f.proj_num = g.proj_plane_num; f.line_filter = g.line_filter_enable;
+  f.touch_filter = g.touch_filter_enable; f.K = (int)g.descriptor_near_num; f.cut_num = btc_cut_num(g);
+  f.merge_n = g.plane_merge_normal_thre; f.merge_d = g.plane_merge_dis_thre; f.detect = g.plane_detection_thre; f.vsize = g.voxel_size;
+  f.res = g.proj_image_resolution; f.high_inc = g.proj_image_high_inc; f.dmin = g.proj_dis_min; f.dmax = g.proj_dis_max;
+  f.summ_min = g.summary_min_thre; f.min_len = g.descriptor_min_len; f.max_len = g.descriptor_max_len;
+  f.scale = 1.0 / (double)g.std_side_resolution;
+  const double r = g.non_max_suppression_radius;
+  f.nms_r2 = (float)(r * r);
+  return f;
+}
+int btc_gen_check(const vba_btc_gen_config &g) {
+  const int K = (int)g.descriptor_near_num;
+  if (!(g.useful_corner_num >= 1 && g.voxel_size > 0 && g.voxel_init_num >= 0 && g.proj_plane_num >= 1 && g.proj_plane_num <= BG_MAX_PROJ &&
+        g.proj_image_resolution > 0 && g.proj_image_high_inc > 0 && g.descriptor_near_num >= 3 && K <= BG_MAX_K &&
+        g.descriptor_min_len >= 0 && g.descriptor_max_len <= 2000 && g.std_side_resolution > 0 && g.proj_dis_max >= g.proj_dis_min &&
+        btc_cut_num(g) >= 0 && btc_cut_num(g) <= 64 && btc_max_stds(g) < (size_t)(1 << 26)))
+    return VBA_ERR_BAD_ARG;
+  return VBA_OK;
+}
+int btc_gen_ensure(vba_btc_db *db, int64_t points, int64_t cells, size_t corners) {
+  vba_ctx *c = db->ctx;
+  if (!db->gen) db->gen = new BtcGen();
+  const BtcGen &g = *db->gen;
+  const size_t stds = btc_max_stds(db->gcfg);
+  if ((size_t)points <= g.pts_cap && (size_t)cells <= g.cell_cap && corners <= g.corn_cap && stds <= g.cand_cap &&
+      g.pts_cap / (size_t)(db->gcfg.voxel_init_num + 1) + 1 <= g.plane_cap && g.cnt)
+    return VBA_OK;
+  HIPCHK(c, btcgen_reserve(*db->gen, (size_t)points, (size_t)cells, corners, stds, db->gcfg.voxel_init_num, c->stream));
+  return VBA_OK;
+}
+}  // namespace
+
+int vba_btc_set_gen_config(vba_btc_db *db, const vba_btc_gen_config *cfg) {
+  if (!db || !cfg || btc_gen_check(*cfg)) return VBA_ERR_BAD_ARG;
+  db->gcfg = *cfg;
+  return VBA_OK;
+}
+
+int vba_btc_get_gen_config(const vba_btc_db *db, vba_btc_gen_config *cfg) {
+  if (!db || !cfg) return VBA_ERR_BAD_ARG;
+  *cfg = db->gcfg;
+  return VBA_OK;
+}
+
+int vba_btc_gen_reserve(vba_btc_db *db, int64_t points, int64_t cells, int frames) {
+  if (!db || points < 0 || cells < 0 || frames < 0 || points > (1 << 28) || cells > BG_MAX_CELLS || frames > (1 << 20)) return VBA_ERR_BAD_ARG;
+  vba_ctx *c = db->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  int st;
+  if ((st = btc_gen_ensure(db, points, cells, 0))) return st;
+  // plane-cloud room for `frames` more calls at the bound a call reserves (points / (voxel_init_num + 1) + 1 planes each)
+  const int64_t planes = (int64_t)(points / (db->gcfg.voxel_init_num + 1) + 1) * frames;
+  if ((st = vba_btc_reserve(db, 0, (int)db->off.size() - 1 + frames + 1, (int64_t)db->off.back() + planes, 0))) return st;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VBA_OK;
+}
+
+int vba_btc_gen_allocations(vba_btc_db *db, int *count, int64_t *bytes) {
+  if (!db || !count || !bytes) return VBA_ERR_BAD_ARG;
+  *count = db->gen ? db->gen->allocs : 0;
+  *bytes = db->gen ? (int64_t)db->gen->dev_bytes : 0;
+  return VBA_OK;
+}
+
+int vba_btc_generate_stds(vba_btc_db *db, int n, const float *xyz, int id, int cap, double *rows, uint64_t *bits, int *n_stds) {
+  if (!db || n < 0 || n > (1 << 28) || (n > 0 && !xyz) || !n_stds || cap < 0 || (cap > 0 && (!rows || !bits))) return VBA_ERR_BAD_ARG;
+  const vba_btc_gen_config &g = db->gcfg;
+  if ((size_t)cap < btc_max_stds(g) || btc_cut_num(g) > db->cfg.occupy_len) return VBA_ERR_BAD_ARG;
+  vba_ctx *c = db->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  *n_stds = 0;
+  if (n == 0) {                                 // empty cloud: an empty plane cloud, no corners, no descriptors
+    db->last_loc.clear(); db->last_bits.clear();
+    return vba_btc_push_plane_cloud(db, 0, nullptr, id);
+  }
+  BtcSpan sp(c);
+  int st;
+  const size_t planes = (size_t)n / (size_t)(g.voxel_init_num + 1) + 1;
+  const size_t have = (size_t)db->off.back();
+  if (have + planes > (size_t)INT32_MAX) return VBA_ERR_CAPACITY;
+  if ((st = btc_gen_ensure(db, n, 0, 0))) return st;
+  // room for this frame's plane cloud and offset (the same growth as vba_btc_push_plane_cloud), counted with the generator's own
+  if (have + planes > db->pc_cap) {
+    size_t m = db->pc_cap ? db->pc_cap : 65536;
+    while (m < have + planes) m *= 2;
+    if ((st = btc_grow(c, &db->d_pc, 6 * have, 6 * m))) return st;
+    db->pc_cap = m;
+    db->gen->allocs++;
+  }
+  const int nf = (int)db->off.size();
+  if (nf + 1 > db->off_cap) {
+    int m = db->off_cap * 2;
+    while (m < nf + 1) m *= 2;
+    if ((st = btc_grow(c, &db->d_off, (size_t)nf, (size_t)m))) return st;
+    db->off_cap = m;
+    db->gen->allocs++;
+  }
+  const BgCfg cf = btc_bg_cfg(g);
+  // the image and the corner list grow on overflow and the call runs again (nothing is committed before it succeeds)
+  for (int attempt = 0;; attempt++) {
+    BtcGen &G = *db->gen;
+    HIPCHK(c, btcgen_enqueue(G, cf, n, xyz, db->d_pc + 6 * have, db->d_off + nf, (int)have, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int *h = G.h_cnt;
+    if (h[BGC_ERR] & 1) return VBA_ERR_BAD_ARG;
+    if (h[BGC_ERR] & 4) return VBA_ERR_CAPACITY;           // a projection image above BG_MAX_CELLS: refused before allocating
+    const bool cells_over = (h[BGC_ERR] & 2) != 0, corn_over = (size_t)h[BGC_NTEMP] > G.corn_cap;
+    if (!cells_over && !corn_over) break;
+    if (attempt >= 2) return VBA_ERR_CAPACITY;
+    if ((st = btc_gen_ensure(db, n, cells_over ? (int64_t)h[BGC_CELLS] : 0, corn_over ? (size_t)h[BGC_NTEMP] : 0))) return st;
+  }
+  const BtcGen &G = *db->gen;
+  const int np = G.h_cnt[BGC_NPL], ns = G.h_cnt[BGC_NSTD], nc = G.h_cnt[BGC_NCORN];
+  db->off.push_back((int)(have + (size_t)np));
+  db->seq.push_back(id);
+  db->last_loc.resize(4 * (size_t)nc); db->last_bits.resize(nc);
+  for (int i = 0; i < nc; i++) {
+    const BgCorner &k = G.h_corn[i];
+    for (int j = 0; j < 3; j++) db->last_loc[4 * (size_t)i + j] = k.loc[j];
+    db->last_loc[4 * (size_t)i + 3] = (double)k.summ;
+    db->last_bits[i] = k.bits;
+  }
+  // rows: [triangle center frame A.loc B.loc C.loc A.summ B.summ C.summ], masks of A, B, C
+  for (int i = 0; i < ns; i++) {
+    const BgStd &t = G.h_stds[i];
+    double *r = rows + (size_t)i * VBA_BTC_ROW_LEN;
+    const int v[3] = {t.a, t.b, t.c};
+    for (int j = 0; j < 3; j++) { r[j] = t.tri[j]; r[3 + j] = t.cen[j]; }
+    r[6] = (double)db->n_add;
+    for (int u = 0; u < 3; u++) {
+      const BgCorner &k = G.h_corn[v[u]];
+      for (int j = 0; j < 3; j++) r[7 + 3 * u + j] = k.loc[j];
+      r[16 + u] = (double)k.summ;
+      bits[3 * (size_t)i + u] = k.bits;
+    }
+  }
+  *n_stds = ns;
+  return VBA_OK;
+}
+
+int vba_btc_plane_cloud(vba_btc_db *db, int frame, int cap, float *xyz_normal, int *n) {
+  if (!db || !n || frame < 0 || frame >= (int)db->off.size() - 1 || cap < 0 || (cap > 0 && !xyz_normal)) return VBA_ERR_BAD_ARG;
+  vba_ctx *c = db->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int b = db->off[frame], e = db->off[frame + 1];
+  *n = e - b;
+  const int w = (e - b) < cap ? (e - b) : cap;
+  if (w > 0) HIPCHK(c, hipMemcpyAsync(xyz_normal, db->d_pc + 6 * (size_t)b, (size_t)w * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VBA_OK;
+}
+
+int vba_btc_last_corners(vba_btc_db *db, int cap, double *loc_summary, uint64_t *bits, int *n) {
+  if (!db || !n || cap < 0 || (cap > 0 && (!loc_summary || !bits))) return VBA_ERR_BAD_ARG;
+  const int k = (int)db->last_bits.size();
+  *n = k;
+  const int w = k < cap ? k : cap;
+  for (int i = 0; i < w; i++) {
+    for (int j = 0; j < 4; j++) loc_summary[4 * (size_t)i + j] = db->last_loc[4 * (size_t)i + j];
+    bits[i] = db->last_bits[i];
+  }
   return VBA_OK;
 }
 

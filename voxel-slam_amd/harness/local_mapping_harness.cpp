@@ -22,6 +22,10 @@
 //           sessions come in order; a new session closes the previous one (skip_near_num_ = -(clouds + 10), VS:2242).
 //           output per keyframe and per session id <= cur: [cur session, keyframe, id, loop_id, score, icp_ran, icp_ok, iters,
 //           t(3), R(9), eig(3)] (23 doubles; the pose is the ICP result when icp_ran, else SearchLoop's transform)
+//   mode 5 (the same step with descriptor generation, VS:2404-2541: GenerateSTDescs -> SearchLoop over sessions -> icp_normal ->
+//           AddSTDescs, through vba::BtcDatabase::GenerateSTDescs): the header of mode 4 with mode 5, then per keyframe
+//           [session, n_pts] cloud[n_pts][3] (the keyframe's merged cloud); GenerateSTDescs gets id = the keyframe's index in its
+//           session; output as mode 4
 //   output: per optimised window [scan index, W x 25 states, v6[6]] ... then [-1, n_leaves] leaf dump [n][39] plane_var dump [n][86]
 #include "../../include/voxelba_adapter.hpp"
 #include <cmath>
@@ -48,7 +52,7 @@ static std::vector<double> read_all(const char *path) {
 
 // VS:2404-2541 over a multi-session stream: push the keyframe's plane cloud, SearchLoop against every session (one batched call),
 // icp_normal where score > juds[id], AddSTDescs; a new session closes the previous database
-static int run_loop_detection(const std::vector<double> &in, size_t q, int n_kf, const char *out_path) {
+static int run_loop_detection(const std::vector<double> &in, size_t q, int n_kf, const char *out_path, bool generate) {
   auto next = [&]() { return in.at(q++); };
   const int is_high_fly = (int)next();
   const double icp_eigval = next();
@@ -63,15 +67,18 @@ static int run_loop_detection(const std::vector<double> &in, size_t q, int n_kf,
     Context ctx(opt);
     vba_btc_config cfg;
     vba_btc_default_config(is_high_fly, &cfg);
+    vba_btc_gen_config gcfg;
+    vba_btc_default_gen_config(is_high_fly, &gcfg);
     std::vector<std::unique_ptr<BtcDatabase>> managers;
     int cur_session = -1, kf_in_session = 0;
     for (int k = 0; k < n_kf; k++) {
-      const int session = (int)next(), nd = (int)next(), np = (int)next();
+      const int session = (int)next(), nd = generate ? 0 : (int)next(), np = (int)next();
       if (session != cur_session) {
         if (!managers.empty()) managers.back()->config_setting_.skip_near_num_ = -(managers.back()->plane_cloud_num() + 10);   // VS:2242
-        managers.emplace_back(new BtcDatabase(ctx, cfg));
+        managers.emplace_back(new BtcDatabase(ctx, cfg, &gcfg));
         cur_session = session; kf_in_session = 0;
       }
+      BtcDatabase &cur = *managers.back();
       std::vector<STD> stds(nd);
       for (int i = 0; i < nd; i++) {
         STD &d = stds[i];
@@ -85,10 +92,15 @@ static int run_loop_detection(const std::vector<double> &in, size_t q, int n_kf,
       for (int i = 0; i < nd; i++) {
         stds[i].binary_A_.occupy_bits = (uint64_t)next(); stds[i].binary_B_.occupy_bits = (uint64_t)next(); stds[i].binary_C_.occupy_bits = (uint64_t)next();
       }
-      std::vector<float> cloud((size_t)np * 6);
-      for (float &f : cloud) f = (float)next();
-      BtcDatabase &cur = *managers.back();
-      cur.push_plane_cloud(cloud, kf_in_session);                                          // GenerateSTDescs' push (BTC.cpp:164-165)
+      if (generate) {
+        std::vector<float> xyz((size_t)np * 3);
+        for (float &f : xyz) f = (float)next();
+        cur.GenerateSTDescs(xyz, stds, kf_in_session);                                     // VS:2406
+      } else {
+        std::vector<float> cloud((size_t)np * 6);
+        for (float &f : cloud) f = (float)next();
+        cur.push_plane_cloud(cloud, kf_in_session);                                        // GenerateSTDescs' push (BTC.cpp:164-165)
+      }
       const int last = cur.plane_cloud_num() - 1;
       std::vector<BtcDatabase *> dbs;
       for (auto &m : managers) dbs.push_back(m.get());
@@ -129,7 +141,7 @@ int main(int argc, char **argv) {
   auto next = [&]() { return in.at(q++); };
   if (next() != 20241004.0) { std::fprintf(stderr, "harness: bad magic\n"); return 2; }
   const int win_size = (int)next(), n_scans = (int)next(), mode = (int)next();
-  if (mode == 4) return run_loop_detection(in, q, n_scans, argv[2]);
+  if (mode == 4 || mode == 5) return run_loop_detection(in, q, n_scans, argv[2], mode == 5);
   vba_options opt;
   vba_default_options(&opt);
   opt.win_size = win_size;

@@ -484,3 +484,56 @@ def btc_plane_cloud(n, seed=0):
     a, b = rng.uniform(-10, 10, (2, n))
     pts = nrm * ds[k][:, None] + a[:, None] * u + b[:, None] * v + rng.normal(0, 0.005, (n, 3))
     return np.column_stack([pts, nrm]).astype(np.float32)
+
+
+def _btc_world(rng, extent=70.0, n_boxes=40, n_poles=60, density=40.0):
+    """surface points of a keyframe world: ground, a perimeter wall, boxes and poles of varied heights (world frame, float64)"""
+    parts = []
+    def rect(o, u, v, lu, lv):                       # points on the rectangle o + s u + t v, s in [0, lu], t in [0, lv]
+        k = max(int(lu * lv * density), 8)
+        s = rng.uniform(0, lu, k); t = rng.uniform(0, lv, k)
+        return o + s[:, None] * u + t[:, None] * v
+    ex, ey, ez = np.eye(3)
+    parts.append(rect(np.array([-extent, -extent, 0.0]), ex, ey, 2 * extent, 2 * extent) * [1, 1, 0])
+    for o, u in (((-extent, -extent), ex), ((-extent, extent), ex), ((-extent, -extent), ey), ((extent, -extent), ey)):
+        parts.append(rect(np.array([o[0], o[1], 0.0]), u, ez, 2 * extent, 4.0))
+    for _ in range(n_boxes):
+        c = rng.uniform(-extent + 8, extent - 8, 2); w, d, h = rng.uniform(2, 7), rng.uniform(2, 7), rng.uniform(1.5, 9)
+        yaw = rng.uniform(0, np.pi); R = _rot_z(yaw); a, b = R[:, 0], R[:, 1]
+        o = np.array([c[0], c[1], 0.0]) - 0.5 * w * a - 0.5 * d * b
+        parts += [rect(o, a, ez, w, h), rect(o + d * b, a, ez, w, h), rect(o, b, ez, d, h), rect(o + w * a, b, ez, d, h),
+                  rect(o + h * ez, a, b, w, d)]
+    for _ in range(n_poles):
+        c = rng.uniform(-extent + 5, extent - 5, 2); r, h = rng.uniform(0.1, 0.3), rng.uniform(2, 8)
+        k = int(2 * np.pi * r * h * density * 4) + 16
+        th = rng.uniform(0, 2 * np.pi, k); z = rng.uniform(0, h, k)
+        parts.append(np.column_stack([c[0] + r * np.cos(th), c[1] + r * np.sin(th), z]))
+    return np.concatenate(parts)
+
+
+def make_btc_keyframe_sessions(n_sessions=2, n_kf=20, n_points=200000, radius=20.0, view=45.0, noise=0.02, seed=0, extent=70.0):
+    """Keyframe point clouds for descriptor generation (GenerateSTDescs input), deterministic in `seed`.
+
+    World: ground, a perimeter wall, boxes and poles of varied heights (_btc_world).  Each session drives the same closed circuit
+    of radius `radius` (session k starts 2 pi k / n_sessions further on and runs once round, so keyframes of different sessions
+    revisit the same places); per keyframe: `n_points` world points within `view` metres (sampled with replacement), moved into
+    the keyframe frame (p_k = R^T (p_w - t)) with Gaussian noise `noise`, as float32 [n_points][3].  The world spans
+    [-extent, extent]^2, with boxes and poles in proportion to its area.  Returns a list of sessions, each a dict with lists
+    cloud, R, t (the ground-truth keyframe poses in the world)."""
+    rng = np.random.default_rng(seed)
+    a = (extent / 70.0) ** 2
+    world = _btc_world(rng, extent=extent, n_boxes=int(round(40 * a)), n_poles=int(round(60 * a)))
+    out = []
+    for s in range(n_sessions):
+        ses = dict(cloud=[], R=[], t=[])
+        for k in range(n_kf):
+            a = 2 * np.pi * (s / n_sessions + k / n_kf)
+            t = np.array([radius * np.cos(a), radius * np.sin(a), 1.5])
+            R = _rot_z(a + np.pi / 2 + rng.normal(0, 0.05))
+            t = t + np.append(rng.normal(0, 0.3, 2), 0.0)
+            near = np.flatnonzero(np.sum((world[:, :2] - t[:2]) ** 2, axis=1) < view * view)
+            pick = world[rng.choice(near, n_points, replace=len(near) < n_points)]
+            loc = (pick - t) @ R + rng.normal(0, noise, (n_points, 3))
+            ses["cloud"].append(loc.astype(np.float32)); ses["R"].append(R); ses["t"].append(t)
+        out.append(ses)
+    return out
