@@ -51,7 +51,8 @@ enum vba_status {
   VBA_ERR_HIP = 6,
   VBA_ERR_CAPACITY = 7,
   VBA_ERR_IO = 8,              /* file missing / malformed (read_lidarstate prints "not found" and exits, VH:271-275) */
-  VBA_ERR_UNSUPPORTED = 9      /* the in-library RCCL exchange step was asked for but librccl.so.1 cannot be resolved in this process */
+  VBA_ERR_UNSUPPORTED = 9,     /* the in-library RCCL exchange step was asked for but librccl.so.1 cannot be resolved in this process */
+  VBA_ERR_SINGULAR = 10        /* vba_pgo_optimize: a connected component without a prior, or a non-positive pivot */
 };
 
 typedef struct vba_ctx vba_ctx;
@@ -343,6 +344,22 @@ int vba_hba_global(vba_ctx *ctx, int n_kf, const int *offsets, const double *pnt
                    const double *poses_now, double gba_voxel_size, double gba_min_eigen_value,
                    const double *gba_eigen_value_array, int total_max_iter, int wdsize, int mgsize, double *edges1_out, int cap1,
                    int *n_edges1, double *edges2_out, int cap2, int *n_edges2);
+
+/* ------------------------------------------------------------------------------------------------
+ * Pose-graph optimisation: the two GTSAM call sites of the loop-closure thread on the device.
+ * build_graph (VS:2078-2156) + ISAM2 {relinearizeThreshold, relinearizeSkip 1}: update(graph, initial) + (n_updates - 1) x update()
+ * + calculateEstimate() (VS:2550-2561, VS:2769-2777), with the semantics of DESIGN.md §12.  poses [n][12] in/out (initial -> result).
+ * edges [m][20] = i, j, rot[9], tra[3], var[6]: the row layout vba_hba_add_edge / vba_hba_global emit (indices remapped by the
+ * caller to node ids, stepsizes[..] + id as VS:2144-2147).  priors [n_prior][19] = k, R[9], p[3], var[6].
+ * stats (optional) [n_updates][3] = relinearised nodes, cost at θ before the solve, max ‖δ‖∞.
+ * VBA_ERR_BAD_ARG: index out of range, i == j, var <= 0 or not finite, n_updates < 1.  VBA_ERR_SINGULAR: a connected component
+ * without a prior, or a non-positive pivot (GTSAM throws IndeterminantLinearSystemException).  On any error poses are untouched.
+ * Bit-identical run to run whatever vba_options::deterministic says (no floating-point atomics).
+ * Device memory: the dense skeleton system over the K prior-holding or branching nodes takes 8 (6K)^2 bytes (1.15 GB at K = 2000,
+ * 29 GB at K = 10000) on top of O(n + m) for the graph; both buffers are grow-only and stay with the context until vba_destroy.
+ * VBA_ERR_CAPACITY (context still usable) when the device cannot hold them. */
+int vba_pgo_optimize(vba_ctx *ctx, int n, double *poses, int m, const double *edges, int n_prior, const double *priors,
+                     int n_updates, double relin_threshold, double *stats);
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-GPU: voxels are sharded by root-voxel hash bucket; each rank evaluates its

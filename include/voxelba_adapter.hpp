@@ -10,6 +10,7 @@
 //   cut_voxel / cut_voxel_multi / cut_voxel(fix)  VM:1896/1964/2108 vba::VoxelMap::cut_voxel[_multi|_fix]
 //   multi_recut / multi_margi    VS:1682 / VS:1590                  vba::VoxelMap::multi_recut / multi_margi
 //   Initialization::motion_init  VS:617-819                         vba::Initialization::motion_init
+//   build_graph + gtsam::ISAM2   VS:2078-2156, VS:2550-2561          vba::PoseGraph (add_edge LR:147-161, set_state LR:36-43)
 //
 // The reference's types are Eigen-based (tools.hpp:4).  This header compiles without Eigen (plain-array structs that
 // mirror PointCluster / IMUST / IMU_PRE field for field); when <Eigen/Core> is available the Eigen-typed overloads
@@ -356,6 +357,68 @@ inline std::vector<GbaEdge> HBA_add_edge(Context &ctx, std::vector<IMUST> &xs, c
   }
   if (submap) { submap->resize(nc); for (int k = 0; k < nc; k++) (*submap)[k] = XYZ{(float)cloud[3 * k], (float)cloud[3 * k + 1], (float)cloud[3 * k + 2]}; }
   return out;
+}
+
+// The pose graph of build_graph (VS:2078-2156) and topDownProcess (VS:2717-2812): gtsam::Values initial + NonlinearFactorGraph
+// graph, solved by vba_pgo_optimize with the ISAM2 schedule of VS:2550-2561.  Keys are the node ids 0..n-1 the
+// reference uses (stepsizes[..] + scan index).  Variances take the place of noiseModel::Diagonal::Variances(v6).
+class PoseGraph {
+ public:
+  void insert(int key, const IMUST &x) {                                            // initial.insert(j, Pose3(Rot3(x.R), x.p))
+    if (key < 0) throw std::runtime_error("libvoxelba: PoseGraph::insert: negative key");
+    if ((size_t)key >= have_.size()) { poses_.resize(12 * (size_t)(key + 1), 0.0); have_.resize(key + 1, 0); }
+    std::memcpy(&poses_[12 * (size_t)key], x.R, 72); std::memcpy(&poses_[12 * (size_t)key + 9], x.p, 24);
+    have_[key] = 1;
+  }
+  // add_edge(pos1, pos2, x1, x2, graph, noise) LR:147-153: the relative pose of x2 seen from x1
+  void add_edge(int pos1, int pos2, const IMUST &x1, const IMUST &x2, const double *v6) {
+    double rot[9], tra[3], d[3] = {x2.p[0] - x1.p[0], x2.p[1] - x1.p[1], x2.p[2] - x1.p[2]};
+    for (int i = 0; i < 3; i++) {
+      tra[i] = x1.R[i] * d[0] + x1.R[3 + i] * d[1] + x1.R[6 + i] * d[2];
+      for (int j = 0; j < 3; j++) rot[3 * i + j] = x1.R[i] * x2.R[j] + x1.R[3 + i] * x2.R[3 + j] + x1.R[6 + i] * x2.R[6 + j];
+    }
+    add_edge(pos1, pos2, rot, tra, v6);
+  }
+  // add_edge(pos1, pos2, rot, tra, graph, noise) LR:155-161
+  void add_edge(int pos1, int pos2, const double *rot, const double *tra, const double *v6) {
+    edges_.push_back(pos1); edges_.push_back(pos2);
+    edges_.insert(edges_.end(), rot, rot + 9); edges_.insert(edges_.end(), tra, tra + 3); edges_.insert(edges_.end(), v6, v6 + 6);
+  }
+  // graph.add(PriorFactor<Pose3>(key, Pose3(x.R, x.p), Variances(v6))) VS:2122-2133
+  void add_prior(int key, const IMUST &x, const double *v6) {
+    priors_.push_back(key);
+    priors_.insert(priors_.end(), x.R, x.R + 9); priors_.insert(priors_.end(), x.p, x.p + 3); priors_.insert(priors_.end(), v6, v6 + 6);
+  }
+  // ISAM2 {relinearizeThreshold thr, relinearizeSkip 1}: update(graph, initial) + (updates - 1) x update(); calculateEstimate()
+  // replaces the inserted poses.  Returns results.size().
+  int optimize(Context &ctx, int updates = 6, double thr = 0.01) {
+    for (size_t k = 0; k < have_.size(); k++)
+      if (!have_[k]) throw std::runtime_error("libvoxelba: PoseGraph::optimize: key " + std::to_string(k) + " was never inserted");
+    stats.assign(3 * (size_t)(updates > 0 ? updates : 1), 0.0);
+    check(ctx.get(), vba_pgo_optimize(ctx.get(), (int)have_.size(), poses_.data(), (int)num_edges(), edges_.data(), (int)num_priors(),
+                                      priors_.data(), updates, thr, stats.data()));
+    return (int)have_.size();
+  }
+  const double *pose(int key) const { return &poses_.at(12 * (size_t)key); }   // results.at(key): [R(9) row-major, p(3)]
+  size_t size() const { return have_.size(); }
+  size_t num_edges() const { return edges_.size() / 20; }
+  size_t num_priors() const { return priors_.size() / 19; }
+  const std::vector<double> &edges() const { return edges_; }
+  void clear() { poses_.clear(); have_.clear(); edges_.clear(); priors_.clear(); }   // initial.clear(); graph = NonlinearFactorGraph()
+  std::vector<double> stats;   // [updates][3] of the last optimize: relinearised nodes, cost, max |delta|_inf
+ private:
+  std::vector<double> poses_, edges_, priors_;
+  std::vector<char> have_;
+};
+
+// ScanPose::set_state(const gtsam::Pose3 &) LR:36-43: the velocity turns with the rotation change R_new R_old^T.
+inline void set_state(IMUST &x, const double *pose12) {
+  double rot[9], v[3];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) rot[3 * i + j] = pose12[3 * i] * x.R[3 * j] + pose12[3 * i + 1] * x.R[3 * j + 1] + pose12[3 * i + 2] * x.R[3 * j + 2];
+  std::memcpy(x.R, pose12, 72); std::memcpy(x.p, pose12 + 9, 24);
+  for (int i = 0; i < 3; i++) v[i] = rot[3 * i] * x.v[0] + rot[3 * i + 1] * x.v[1] + rot[3 * i + 2] * x.v[2];
+  std::memcpy(x.v, v, 24);
 }
 
 // VOXEL_SLAM::lio_state_estimation_kdtree(pptr) VS:1102-1252: x_curr (state + cov) in/out, the point-cloud map (pl_tree) lives in

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("VBA_LIB") or os.path.join(_PKG, "libvoxelba.so")   # 
 _dp = C.POINTER(C.c_double)
 
 OK = 0
-ERR_NO_DEVICE, ERR_BAD_ARG, ERR_UNSUPPORTED_WINDOW, ERR_TOO_FEW_VOXELS, ERR_OPT_STATE, ERR_HIP, ERR_CAPACITY, ERR_IO, ERR_UNSUPPORTED = range(1, 10)
+ERR_NO_DEVICE, ERR_BAD_ARG, ERR_UNSUPPORTED_WINDOW, ERR_TOO_FEW_VOXELS, ERR_OPT_STATE, ERR_HIP, ERR_CAPACITY, ERR_IO, ERR_UNSUPPORTED, ERR_SINGULAR = range(1, 11)
 
 EXPORTS = [
     "vba_default_options", "vba_create", "vba_destroy", "vba_status_string", "vba_last_error", "vba_synchronize",
@@ -38,6 +38,7 @@ EXPORTS = [
     "vba_btc_icp_normal", "vba_btc_last_candidates", "vba_btc_reserve",
     "vba_btc_default_gen_config", "vba_btc_set_gen_config", "vba_btc_generate_stds", "vba_btc_plane_cloud", "vba_btc_last_corners",
     "vba_btc_gen_reserve", "vba_btc_gen_allocations", "vba_btc_get_gen_config",
+    "vba_pgo_optimize",
 ]
 
 
@@ -715,6 +716,18 @@ class Context:
                                           C.c_double(gba_voxel_size), C.c_double(gba_min_eigen_value), _p(_c(gba_eig)), C.c_int(total_max_iter),
                                           C.c_int(wdsize), C.c_int(mgsize), _p(e1), C.c_int(cap1), C.byref(n1), _p(e2), C.c_int(cap2), C.byref(n2)))
         return e1[:n1.value].copy(), e2[:n2.value].copy()
+
+    def pgo_optimize(self, poses, edges, priors, n_updates=6, relin_threshold=0.01):
+        """build_graph + ISAM2 update() x n_updates + calculateEstimate() (VS:2078-2156, VS:2550-2561, VS:2769-2777):
+        poses [n][12], edges [m][20] = i, j, rot(9), tra(3), var(6), priors [k][19] = k, R(9), p(3), var(6)
+        -> (optimised poses [n][12], stats [n_updates][3] = relinearised nodes, cost at theta, max |delta|_inf)."""
+        x = _c(poses).reshape(-1, 12).copy()
+        e = _c(edges).reshape(-1, 20)
+        pr = _c(priors).reshape(-1, 19)
+        stats = np.zeros((max(int(n_updates), 1), 3))
+        self._chk(self.lib.vba_pgo_optimize(self.h, C.c_int(len(x)), _p(x), C.c_int(len(e)), _p(e) if len(e) else None, C.c_int(len(pr)),
+                                            _p(pr) if len(pr) else None, C.c_int(int(n_updates)), C.c_double(relin_threshold), _p(stats)))
+        return x, stats
 
     def set_shard(self, rank, n_ranks):
         self._chk(self.lib.vba_set_shard(self.h, C.c_int(rank), C.c_int(n_ranks)))

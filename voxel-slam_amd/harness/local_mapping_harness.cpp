@@ -26,6 +26,11 @@
 //           AddSTDescs, through vba::BtcDatabase::GenerateSTDescs): the header of mode 4 with mode 5, then per keyframe
 //           [session, n_pts] cloud[n_pts][3] (the keyframe's merged cloud); GenerateSTDescs gets id = the keyframe's index in its
 //           session; output as mode 4
+//   mode 6 (pose-graph optimisation, build_graph VS:2078-2156 + topDownProcess VS:2717-2812 + ISAM2, through vba::PoseGraph):
+//           header [magic, 0, n_sessions, 6, lpedge_enable, n_updates, relin_threshold], per session [n_scans] states[n][25] v6[n][6],
+//           then [n_loop] rows [m1, m2, id1, id2, rot(9), tra(3)] (noise v6_init = 1e-4), then [n_gba] rows [m1, m2, id1, id2, rot(9),
+//           tra(3), v6(6)] (gba_edges1 + gba_edges2 with scan ids); output: the states of every session after set_state, then the
+//           stats [n_updates][3]
 //   output: per optimised window [scan index, W x 25 states, v6[6]] ... then [-1, n_leaves] leaf dump [n][39] plane_var dump [n][86]
 #include "../../include/voxelba_adapter.hpp"
 #include <cmath>
@@ -132,6 +137,71 @@ static int run_loop_detection(const std::vector<double> &in, size_t q, int n_kf,
   return 0;
 }
 
+// build_graph (VS:2078-2156) over all sessions (ids = 0..n_sessions-1, stepsizes from their sizes), the gba_edges of
+// topDownProcess (VS:2733-2764), ISAM2 (VS:2766-2773) and the set_state write-back (VS:2778-2786)
+static int run_pose_graph(const std::vector<double> &in, size_t q, int n_sessions, const char *out_path) {
+  auto next = [&]() { return in.at(q++); };
+  const int lpedge_enable = (int)next(), n_updates = (int)next();
+  const double relin = next();
+  std::vector<std::vector<ScanPoseRec>> scans(n_sessions);
+  std::vector<int> stepsizes(1, 0);
+  for (int s = 0; s < n_sessions; s++) {
+    const int n = (int)next();
+    scans[s].resize(n);
+    for (int k = 0; k < n; k++) { double *st = &scans[s][k].x.t; for (int f = 0; f < VBA_STATE_LEN; f++) st[f] = next(); }
+    for (int k = 0; k < n; k++) for (int f = 0; f < 6; f++) scans[s][k].v6[f] = next();
+    stepsizes.push_back(stepsizes.back() + n);
+  }
+  vba_options opt;
+  vba_default_options(&opt);
+  std::vector<double> out;
+  try {
+    Context ctx(opt);
+    PoseGraph graph;
+    for (int ii = 0; ii < n_sessions; ii++) {                          // VS:2099-2118
+      const int bsize = stepsizes[ii];
+      for (int j = bsize; j < stepsizes[ii + 1]; j++) {
+        graph.insert(j, scans[ii][j - bsize].x);
+        if (j > bsize) graph.add_edge(j - 1, j, scans[ii][j - 1 - bsize].x, scans[ii][j - bsize].x, scans[ii][j - 1 - bsize].v6);
+      }
+    }
+    if (n_sessions > 0 && !scans[0].empty()) {                          // VS:2121-2134
+      const double v6_fixd[6] = {1e-9, 1e-9, 1e-9, 1e-9, 1e-9, 1e-9};
+      graph.add_prior(0, scans[0][0].x, v6_fixd);
+    }
+    const int n_loop = (int)next();
+    const double v6_init[6] = {1e-4, 1e-4, 1e-4, 1e-4, 1e-4, 1e-4};
+    for (int e = 0; e < n_loop; e++) {                                 // VS:2137-2154 (default_noise)
+      double r[16];
+      for (int f = 0; f < 16; f++) r[f] = next();
+      if (lpedge_enable == 1) graph.add_edge(stepsizes[(int)r[0]] + (int)r[2], stepsizes[(int)r[1]] + (int)r[3], r + 4, r + 13, v6_init);
+    }
+    const int n_gba = (int)next();
+    for (int e = 0; e < n_gba; e++) {                                  // VS:2733-2764
+      double r[22];
+      for (int f = 0; f < 22; f++) r[f] = next();
+      graph.add_edge(stepsizes[(int)r[0]] + (int)r[2], stepsizes[(int)r[1]] + (int)r[3], r + 4, r + 13, r + 16);
+    }
+    graph.optimize(ctx, n_updates, relin);                             // VS:2766-2773
+    for (int ii = 0; ii < n_sessions; ii++)                            // VS:2778-2786
+      for (int j = stepsizes[ii]; j < stepsizes[ii + 1]; j++) {
+        IMUST &x = scans[ii][j - stepsizes[ii]].x;
+        set_state(x, graph.pose(j));
+        const double *st = &x.t;
+        out.insert(out.end(), st, st + VBA_STATE_LEN);
+      }
+    out.insert(out.end(), graph.stats.begin(), graph.stats.end());
+  } catch (const std::exception &e) {
+    std::fprintf(stderr, "harness: %s\n", e.what());
+    return 1;
+  }
+  FILE *f = std::fopen(out_path, "wb");
+  if (!f) return 2;
+  std::fwrite(out.data(), 8, out.size(), f);
+  std::fclose(f);
+  return 0;
+}
+
 int main(int argc, char **argv) {
   // optional third argument --deterministic: vba_options::deterministic = 1 (bit-identical output run to run)
   const bool det = argc == 4 && std::strcmp(argv[3], "--deterministic") == 0;
@@ -142,6 +212,7 @@ int main(int argc, char **argv) {
   if (next() != 20241004.0) { std::fprintf(stderr, "harness: bad magic\n"); return 2; }
   const int win_size = (int)next(), n_scans = (int)next(), mode = (int)next();
   if (mode == 4 || mode == 5) return run_loop_detection(in, q, n_scans, argv[2], mode == 5);
+  if (mode == 6) return run_pose_graph(in, q, n_scans, argv[2]);
   vba_options opt;
   vba_default_options(&opt);
   opt.win_size = win_size;
