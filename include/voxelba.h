@@ -409,6 +409,32 @@ int vba_lm_refresh_eigen(vba_ctx *ctx); /* device-side residual pass at the begi
 int vba_timing_launch_hessian(vba_ctx *ctx);
 int vba_lm_iterate(vba_ctx *ctx, int *accepted, int *stop); /* NULL, NULL: enqueue only (no host synchronisation) */
 int vba_lm_end(vba_ctx *ctx, double *poses, double *hess, double *resis2);
+/* Diagnostic: one linear solve of an LM iteration on a system of the caller's choosing (tests/test_gpu_solve.py).  H (n x n,
+ * row-major, exactly symmetric) and g (n) are the Hessian and gradient before the gauge; the production kernel solves
+ * (H + u diag(H)) dx = -g with the loop's gauge rows (identity, zero right-hand side) and returns dx and the model decrease
+ * q1 = 0.5 dx^T (u diag(H) dx - g) of every damping candidate b, candidate b using the damping b consecutive rejections lead to
+ * (u <- u v, v <- 2 v): dx[b n + i], q1[b].
+ *   VBA_SOLVE_LIDAR  k_lm_solve_m, n = 6W (W = 2..16), gauge rows 0..5, lm_spec candidates.  The system goes into the tile image
+ *                    of the Hessian pass: every entry in the tiles, or (VBA_SOLVE_E_PACKED) each frame's 6 x 6 diagonal block in
+ *                    the per-frame remainders only.
+ *   VBA_SOLVE_LI     k_li_solve, n = 15W (+3 with VBA_SOLVE_GRAVITY), W = 2..16, gauge rows 0..14 (0..5 with gravity), lm_spec
+ *                    candidates.  Pose-pose entries go into the lidar tiles, the rest into the compact IMU image (coefficient 1);
+ *                    an entry coupling frames more than one apart that is not pose-pose is VBA_ERR_BAD_ARG.
+ *                    VBA_SOLVE_DENSE_MASK updates every tile in every panel instead of skipping by structure.
+ *   VBA_SOLVE_DENSE  big_damping_iter's solve (host pivot order, k_bigl_* on the device), n = 6W (W = 2..1024), gauge rows 0..5,
+ *                    one candidate.
+ * VBA_SOLVE_COPY_RAW launches the multi-rank form of the lidar / LI kernel (system read from the reduced buffer and saved), with
+ * VBA_SOLVE_FROM_RAW the form that reads the saved copy after a rejected step.  Non-finite input, a W out of range or an
+ * asymmetric H: VBA_ERR_BAD_ARG with nothing launched.  The context's LM state is not touched. */
+#define VBA_SOLVE_LIDAR 0
+#define VBA_SOLVE_LI 1
+#define VBA_SOLVE_DENSE 2
+#define VBA_SOLVE_E_PACKED 1
+#define VBA_SOLVE_COPY_RAW 2
+#define VBA_SOLVE_FROM_RAW 4
+#define VBA_SOLVE_GRAVITY 8
+#define VBA_SOLVE_DENSE_MASK 16
+int vba_debug_solve(vba_ctx *ctx, int kind, int W, int flags, const double *H, const double *g, double u, double v, double *dx, double *q1);
 
 /* ------------------------------------------------------------------------------------------------
  * Session-store formats either side of the path.  Host only, no context.

@@ -30,7 +30,7 @@ EXPORTS = [
     "vba_map_num_roots", "vba_map_num_slide_roots", "vba_map_stats", "vba_map_dump_leaves", "vba_map_dump_plane_var", "vba_odom_lio_state_estimation",
     "vba_set_allreduce", "vba_rccl_get_unique_id", "vba_rccl_init", "vba_set_rccl_comm", "vba_shard_owner", "vba_set_shard",
     "vba_timing_enable", "vba_timing_calibration_read", "vba_timing_select", "vba_timing_sample_every", "vba_timing_launch_hessian", "vba_timing_null_span", "vba_timing_reset", "vba_timing_get",
-    "vba_lm_begin", "vba_lm_refresh_eigen", "vba_lm_iterate", "vba_lm_end",
+    "vba_lm_begin", "vba_lm_refresh_eigen", "vba_lm_iterate", "vba_lm_end", "vba_debug_solve",
     "vba_io_save_pcd", "vba_io_load_pcd", "vba_io_save_pose", "vba_io_read_lidarstate",
     "vba_motion_init", "vba_init_imu_poses", "vba_init_align_gravity",
     "vba_btc_default_config", "vba_btc_create", "vba_btc_destroy", "vba_btc_set_skip_near_num", "vba_btc_push_plane_cloud",
@@ -484,6 +484,22 @@ class Context:
         H = np.empty((n, n)); resis = np.zeros(2)
         self._chk(self.lib.vba_li_ba_damping_iter(self.h, _p(states), _p(imus), C.c_int(int(gravity)), C.c_int(max_iter), _p(H), _p(resis)))
         return dict(states=states, imus=imus, hess=H, resis=resis, trace=self.last_trace())
+
+    SOLVE_KINDS = {"lidar": 0, "li": 1, "dense": 2}
+    SOLVE_FLAGS = {"e_packed": 1, "copy_raw": 2, "from_raw": 4, "gravity": 8, "dense_mask": 16}
+
+    def debug_solve(self, kind, W, H, g, u, v=2.0, **flags):
+        """vba_debug_solve: one linear solve of the LM loop through the production kernel on the system (H, g) (before the gauge).
+        kind in SOLVE_KINDS, flags = names of SOLVE_FLAGS set to True.  Returns (dx [candidates][n], q1 [candidates])."""
+        f = 0
+        for k, on in flags.items():
+            f |= self.SOLVE_FLAGS[k] if on else 0
+        H = _c(H); g = _c(g); n = len(g)
+        nc = 1 if kind == "dense" else (self.opt.lm_spec if 0 < self.opt.lm_spec < 4 else 4)
+        dx = np.zeros((nc, n)); q1 = np.zeros(nc)
+        self._chk(self.lib.vba_debug_solve(self.h, C.c_int(self.SOLVE_KINDS[kind]), C.c_int(W), C.c_int(f), _p(H), _p(g),
+                                           C.c_double(u), C.c_double(v), _p(dx), _p(q1)))
+        return dx, q1
 
     def lm_begin(self, poses, thd_num=2):
         poses = _c(poses)

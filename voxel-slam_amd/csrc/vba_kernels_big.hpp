@@ -12,6 +12,8 @@
 //     the O(n^2) back substitution and the edge extraction stay on the host.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -774,6 +776,19 @@ inline int big_residual(BigStore &s, hipStream_t st, const double *poses, double
   BIGCHK(hipMemcpyAsync(r, b.r, 8, hipMemcpyDeviceToHost, st));
   BIGCHK(hipStreamSynchronize(st));
   return VBA_OK;
+}
+
+// Eigen's LDLT pivot order for (H + u D): largest |stored diagonal| first, first index wins ties.  hd = diag(H) after the gauge.
+inline void big_pivot_order(const double *hd, double u, int n, int *ord) {
+  std::vector<double> dabs(n);
+  for (int r = 0; r < n; r++) { ord[r] = r; dabs[r] = std::fabs(hd[r] + u * hd[r]); }
+  std::stable_sort(ord, ord + n, [&](int a, int b) { return dabs[a] > dabs[b]; });
+}
+// the model decrease q1 = 0.5 dx^T (u D dx - g) of VM:465 (hd, g after the gauge), summed in row order
+inline double big_q1(const double *dxi, const double *hd, const double *g, double u, int n) {
+  double q1 = 0;
+  for (int r = 0; r < n; r++) q1 += dxi[r] * (u * hd[r] * dxi[r] - g[r]);
+  return 0.5 * q1;
 }
 
 // (H + u D) dxi = -g with the gauge of VM:452-455, H / g = the device buffers of the last big_hessian (before the gauge).

@@ -8,6 +8,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vba_hostmath.hpp"
+#include "vba_li_order.hpp"
 
 namespace vba {
 
@@ -211,11 +212,13 @@ __device__ __forceinline__ double li_hfull(const double *__restrict__ himu, cons
   return coef * vi + (lid ? v1 + (dg ? v2 : 0.0) : 0.0);
 }
 
-// (H + u D) dxi = -g for the 15W(+3) system in Eigen-LDLT pivot order, then the retraction of VM:661-671 / 921-934.
-template <int W, int NT, bool GL>
+// (H + u D) dxi = -g for the 15W(+3) system in the structure order of vba_li_order.hpp, then the retraction of VM:661-671 / 921-934.
+// dx_out (NULL in the LM loop): dxi of candidate b to dx_out[b n ..] (vba_debug_solve).  DENSE_MASK (vba_debug_solve only): every
+// tile updated in every panel (LdltDense) instead of the structure mask li_live.
+template <int W, int NT, bool GL, bool DENSE_MASK = false>
 __global__ __launch_bounds__(NT) void k_li_solve(LmDev *s, LiDev *li, const double *__restrict__ red, double *__restrict__ raw, int copy_raw,
                                                  const double *__restrict__ himu, const double *__restrict__ gimu, double *__restrict__ imu,
-                                                 int n, int gauge, int grav, double coef, double *__restrict__ lscratch) {
+                                                 int n, int gauge, int grav, double coef, double *__restrict__ lscratch, double *__restrict__ dx_out) {
   using C2 = HessCfg2<W>;
   constexpr int NMAX = 15 * W + 3, NP = ((NMAX + 1 + 15) / 16) * 16;
   using LC = LdltCfg<NP>;
@@ -318,19 +321,8 @@ __global__ __launch_bounds__(NT) void k_li_solve(LmDev *s, LiDev *li, const doub
   }
   __syncthreads();
   if ((dbg & 16) && tid == 0) s->stamps[52] = clock64();
-  // Elimination order = the STRUCTURE of the system ("eliminate the 9W velocity / bias block first"): the v, bg, ba
-  // of frame 0, 1, ... W-1 (block-tridiagonal through the IMU factors, VM:551-567), then the 6W pose scalars (dense through the
-  // lidar part), then gravity.  Column c of frame i's block then reaches only the rest of its block, frame i+1's block, the poses
-  // of frames 0..i+1 (i-1, i, i+1 directly, the older ones as fill of the chain), gravity and the right-hand side: the trailing
-  // update of most tiles is skipped (li_live_rows).  The reference's Eigen LDLT pivots by the largest remaining diagonal (VM:659);
-  // the system is symmetric positive definite (damped), for which every order is backward stable — the results move in the last
-  // digits, inside the bars of the LI parity tests (same bars as before).
-  if (tid < n) {
-    int o = tid;
-    if (tid < 9 * W) { const int i = tid / 9; o = 15 * i + 6 + (tid - 9 * i); }
-    else if (tid < 15 * W) { const int q = tid - 9 * W, i = q / 6; o = 15 * i + (q - 6 * i); }
-    ord[tid] = o;
-  }
+  // elimination order: vba_li_order.hpp (the structure of the system, not Eigen's pivoting)
+  if (tid < n) ord[tid] = li_ord(tid, W);
   __syncthreads();
   // element (i, j) of the padded system: P (H + u D) P^T lower triangle, row n = -g, identity on the padding
   auto elem = [&](int i, int j) -> double {
@@ -346,18 +338,9 @@ __global__ __launch_bounds__(NT) void k_li_solve(LmDev *s, LiDev *li, const doub
   };
   long long *stamps = ((dbg & 16) != 0) ? s->stamps : nullptr;
   if (stamps && tid == 0) stamps[1] = clock64();
-  auto live = [&](int kb) -> unsigned {               // 16-row blocks that can hold a non-zero of L in the columns [8 kb, 8 kb + 8)
-    const int c0 = 8 * kb, c1 = c0 + 7;
-    auto span = [](int a, int b) -> unsigned { return (a < b) ? ((2u << ((b - 1) >> 4)) - 1u) & ~((1u << (a >> 4)) - 1u) : 0u; };   // rows [a, b)
-    if (c0 >= 9 * W) return span(c0, NP);
-    const int ihi = (c1 < 9 * W ? c1 : 9 * W - 1) / 9;                                   // last frame the panel touches
-    unsigned m = span(c0, (9 * (ihi + 2) < 9 * W) ? 9 * (ihi + 2) : 9 * W);            // its own blocks and the next frame's
-    m |= span(9 * W, (6 * (ihi + 2) < 6 * W) ? 9 * W + 6 * (ihi + 2) : 15 * W);        // poses of frames 0 .. ihi + 1
-    m |= span(15 * W, n + 1);                                                            // gravity, right-hand side row
-    if (c1 >= 9 * W) m |= span(9 * W, NP);                                               // a panel that straddles into the pose block
-    return m;
-  };
-  ldlt_mfma<NP, NT>(Lst, Tp, P, n, elem, stamps, live);
+  auto live = [&](int kb) -> unsigned { return li_live(kb, W, n, NP); };
+  if constexpr (DENSE_MASK) ldlt_mfma<NP, NT>(Lst, Tp, P, n, elem, stamps, LdltDense());
+  else ldlt_mfma<NP, NT>(Lst, Tp, P, n, elem, stamps, live);
   if (stamps && tid == 0) stamps[3] = clock64();
   if (tid < n) xs[tid] = Lst[LC::lat(n, tid)];                                  // z = D^-1 L^-1 P (-g)
   __syncthreads();
@@ -401,6 +384,7 @@ __global__ __launch_bounds__(NT) void k_li_solve(LmDev *s, LiDev *li, const doub
   for (int m = 32; m >= 1; m >>= 1) q += __shfl_xor(q, m, 64);
   if ((tid & 63) == 0) red8[tid >> 6] = q;
   __syncthreads();
+  if (dx_out && tid < n) dx_out[(size_t)sb * n + tid] = dxs[tid];
   if (tid == 0) {
     double t = 0;
     for (int w2 = 0; w2 < NT / 64; w2++) t += red8[w2];

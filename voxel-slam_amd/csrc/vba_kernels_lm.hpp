@@ -72,7 +72,7 @@ __device__ __forceinline__ void so3_exp_dev(const double *w, double *R) {   // t
 
 // Index of the diagonal-block remainder E that tl_fetch adds to H(row, col), row <= col < 6W; -1 outside the frame's 6 x 6 block.
 template <int W>
-__device__ __forceinline__ int tl_eidx(int row, int col) {
+__host__ __device__ __forceinline__ int tl_eidx(int row, int col) {
   using C = HessCfg2<W>;
   const int fr = row / 6;
   if (col / 6 != fr) return -1;
@@ -84,8 +84,9 @@ __device__ __forceinline__ int tl_eidx(int row, int col) {
   return C::EB + 21 * fr + idx;
 }
 
+// dx_out (NULL in the LM loop): dx of candidate b to dx_out[b n ..] (vba_debug_solve).
 template <int W, bool COPY_RAW>
-__global__ __launch_bounds__(256) void k_lm_solve_m(LmDev *s, const double *__restrict__ red, double *__restrict__ raw) {
+__global__ __launch_bounds__(256) void k_lm_solve_m(LmDev *s, const double *__restrict__ red, double *__restrict__ raw, double *__restrict__ dx_out) {
   const int sb = blockIdx.x;
   using C2 = HessCfg2<W>;
   constexpr int n = 6 * W, NT = 256, NP = ((n + 1 + 15) / 16) * 16, NH = (n + 63) / 64, NU = C2::NU, T16 = C2::NT16;
@@ -238,6 +239,7 @@ __global__ __launch_bounds__(256) void k_lm_solve_m(LmDev *s, const double *__re
     if (lane == 63) red8[wv] = q;
   }
   __syncthreads();
+  if (dx_out && tid < n) dx_out[sb * n + tid] = dxs[tid];
   if (tid == 0) {
     const double q1 = 0.5 * (red8[0] + red8[1] + red8[2] + red8[3]);
     s->q1_spec[sb] = q1;

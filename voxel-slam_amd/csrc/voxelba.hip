@@ -886,8 +886,8 @@ int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
   span_begin(c, "solve", sp);
   switch (W) {
 #define VBA_SM_CASE(WW) case WW: \
-    if (copy_raw) hipLaunchKernelGGL((k_lm_solve_m<WW, true>), dim3(c->lm_spec), dim3(256), 0, c->stream, c->d_lm, c->d_out, c->d_raw); \
-    else hipLaunchKernelGGL((k_lm_solve_m<WW, false>), dim3(c->lm_spec), dim3(256), 0, c->stream, c->d_lm, c->d_out, c->d_raw); \
+    if (copy_raw) hipLaunchKernelGGL((k_lm_solve_m<WW, true>), dim3(c->lm_spec), dim3(256), 0, c->stream, c->d_lm, c->d_out, c->d_raw, nullptr); \
+    else hipLaunchKernelGGL((k_lm_solve_m<WW, false>), dim3(c->lm_spec), dim3(256), 0, c->stream, c->d_lm, c->d_out, c->d_raw, nullptr); \
     break;
     VBA_SM_CASE(2) VBA_SM_CASE(3) VBA_SM_CASE(4) VBA_SM_CASE(5) VBA_SM_CASE(6) VBA_SM_CASE(7) VBA_SM_CASE(8) VBA_SM_CASE(9) VBA_SM_CASE(10)
     VBA_SM_CASE(11) VBA_SM_CASE(12) VBA_SM_CASE(13) VBA_SM_CASE(14) VBA_SM_CASE(15) VBA_SM_CASE(16)
@@ -985,13 +985,18 @@ int vba_last_lm_trace(vba_ctx *c, double *rows, int max_rows) {
 
 // ---------------------------------------------------------------- LI_BA_Optimizer / LI_BA_OptimizerGravity on the device
 extern "C++" {
+template <int W>
+struct LiSolveCfg {
+  static constexpr int NMAX = 15 * W + 3, NP = ((NMAX + 1 + 15) / 16) * 16;
+  static constexpr bool GL = W > 10;             // L of the 15 W + 3 system exceeds the LDS: it lives in c->d_liscr
+  static constexpr size_t l_doubles = (size_t)LdltCfg<NP>::LTOT > (size_t)NMAX * (NMAX + 1) / 2 ? (size_t)LdltCfg<NP>::LTOT : (size_t)NMAX * (NMAX + 1) / 2;
+  static constexpr size_t lds = ((GL ? (size_t)LdltCfg<NP>::DOUBLES - LdltCfg<NP>::LTOT : (size_t)LdltCfg<NP>::DOUBLES) + 4 * NMAX + NP + 32) * 8 + (size_t)NMAX * 4 + 64;
+  static_assert(GL || l_doubles == (size_t)LdltCfg<NP>::LTOT, "the staged triangle must fit the region of L");
+};
 template <int W, int NT = (W > 10 ? 1024 : 512)>
 static int launch_li_solve(vba_ctx *c, int copy_raw, int n, int gauge, int grav) {
-  constexpr int NMAX = 15 * W + 3, NP = ((NMAX + 1 + 15) / 16) * 16;
-  constexpr bool GL = W > 10;                    // L of the 15 W + 3 system exceeds the LDS: it lives in c->d_liscr
-  constexpr size_t l_doubles = (size_t)LdltCfg<NP>::LTOT > (size_t)NMAX * (NMAX + 1) / 2 ? (size_t)LdltCfg<NP>::LTOT : (size_t)NMAX * (NMAX + 1) / 2;
-  constexpr size_t lds = ((GL ? (size_t)LdltCfg<NP>::DOUBLES - LdltCfg<NP>::LTOT : (size_t)LdltCfg<NP>::DOUBLES) + 4 * NMAX + NP + 32) * 8 + (size_t)NMAX * 4 + 64;
-  static_assert(GL || l_doubles == (size_t)LdltCfg<NP>::LTOT, "the staged triangle must fit the region of L");
+  constexpr bool GL = LiSolveCfg<W>::GL;
+  constexpr size_t l_doubles = LiSolveCfg<W>::l_doubles, lds = LiSolveCfg<W>::lds;
   static bool attr_set[kMaxDevices] = {false};
   if (!attr_set[c->device % kMaxDevices]) { hipFuncSetAttribute((const void *)k_li_solve<W, NT, GL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set[c->device % kMaxDevices] = true; }
   if (GL && c->liscr_doubles < l_doubles * LM_SPEC) {           // one region per damping candidate; W is fixed per context, so this runs once
@@ -1002,7 +1007,7 @@ static int launch_li_solve(vba_ctx *c, int copy_raw, int n, int gauge, int grav)
     c->liscr_doubles = l_doubles * LM_SPEC;
   }
   hipLaunchKernelGGL((k_li_solve<W, NT, GL>), dim3(c->lm_spec), dim3(NT), lds, c->stream, c->d_lm, c->d_li, c->d_out, c->d_raw, copy_raw, c->d_himu, c->d_gimu, c->d_imu, n, gauge, grav,
-                     c->opt.imu_coef, c->d_liscr);
+                     c->opt.imu_coef, c->d_liscr, nullptr);
   return VBA_OK;
 }
 }  // extern "C++"
@@ -1408,10 +1413,7 @@ static int big_damping_iter(vba_ctx *c, int W, double *poses, std::vector<double
     {
       // pivot order of Eigen's LDLT (largest |stored diagonal| first, first index wins ties), then the device factorisation
       std::vector<int> ord(n);
-      for (int r = 0; r < n; r++) ord[r] = r;
-      std::vector<double> dabs(n);
-      for (int r = 0; r < n; r++) dabs[r] = std::fabs(hd[r] + u * hd[r]);
-      std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return dabs[a] > dabs[b]; });
+      big_pivot_order(hd.data(), u, n, ord.data());
       int st2 = big_solve(S, c->stream, ord.data(), u, dxi.data(), c->err);
       if (st2) return st2;
     }
@@ -1421,9 +1423,7 @@ static int big_damping_iter(vba_ctx *c, int W, double *poses, std::vector<double
       vbh::m3_mul(&x[12 * j], E, &xt[12 * j]);
       for (int k = 0; k < 3; k++) xt[12 * j + 9 + k] = x[12 * j + 9 + k] + dxi[6 * j + 3 + k];
     }
-    double q1 = 0;
-    for (int r = 0; r < n; r++) q1 += dxi[r] * (u * hd[r] * dxi[r] - JacT[r]);
-    q1 *= 0.5;
+    const double q1 = big_q1(dxi.data(), hd.data(), JacT.data(), u, n);
     int st = big_residual(S, c->stream, xt.data(), &residual2, c->err);
     if (st) return st;
     double q = residual1 - residual2;
@@ -3607,6 +3607,182 @@ int vba_pgo_optimize(vba_ctx *c, int n, double *poses, int m, const double *edge
       std::memcpy(&cnt, res.data() + (size_t)U * 16 + (size_t)u * 4, 4);
       stats[3 * u] = cnt; stats[3 * u + 1] = cost; stats[3 * u + 2] = mx;
     }
+  return VBA_OK;
+}
+
+// ---------------------------------------------------------------- diagnostic: one LM linear solve through the production kernels
+// The caller's system is written into the buffers the solve kernel reads, in their production layout, and the kernel is launched
+// as the LM loop launches it (lm_spec workgroups); every buffer belongs to this call, so the context's LM state is untouched.
+extern "C++" {
+namespace {
+struct DbgBufs {                      // device buffers of one call; drained and freed on every exit path
+  hipStream_t st;
+  std::vector<void *> p;
+  explicit DbgBufs(hipStream_t s) : st(s) {}
+  ~DbgBufs() { if (!p.empty()) hipStreamSynchronize(st); for (void *q : p) hipFree(q); }
+  template <typename T> hipError_t alloc(T **out, size_t count) {
+    void *q = nullptr;
+    const hipError_t e = hipMalloc(&q, (count ? count : 1) * sizeof(T));
+    if (e == hipSuccess) { p.push_back(q); *out = (T *)q; }
+    return e;
+  }
+};
+// HessCfg2<W> tile image [tiles | E | g | r] of (H, g): E remainders zero, or (epack) each frame's 6 x 6 diagonal block held in E only
+template <int W>
+void dbg_lidar_image(const double *H, const double *g, bool epack, std::vector<double> &img) {
+  using C2 = HessCfg2<W>;
+  constexpr int n = 6 * W;
+  img.assign(C2::NOUT2, 0.0);
+  for (int row = 0; row < n; row++)
+    for (int col = row; col < n; col++) {
+      const double a = H[(size_t)row * n + col];
+      const int e = tl_eidx<W>(row, col);
+      if (epack && e >= 0) { img[e] = a; continue; }
+      const int ta = row >> 4, tb = col >> 4, ut = ta * C2::NT16 - ta * (ta - 1) / 2 + (tb - ta);
+      img[(size_t)ut * 256 + 16 * (row & 15) + (col & 15)] = a;
+    }
+  for (int k = 0; k < n; k++) img[C2::GB + k] = g[k];
+}
+template <int W>
+int dbg_lidar(vba_ctx *c, DbgBufs &B, const double *H, const double *g, int flags, LmDev &h, double *d_dx) {
+  using C2 = HessCfg2<W>;
+  std::vector<double> img;
+  dbg_lidar_image<W>(H, g, (flags & VBA_SOLVE_E_PACKED) != 0, img);
+  const bool copy_raw = (flags & VBA_SOLVE_COPY_RAW) != 0, from_raw = copy_raw && (flags & VBA_SOLVE_FROM_RAW);
+  double *red = nullptr, *raw = nullptr;
+  LmDev *s = nullptr;
+  HIPCHK(c, B.alloc(&red, C2::NOUT2)); HIPCHK(c, B.alloc(&raw, C2::NOUT2)); HIPCHK(c, B.alloc(&s, 1));
+  h.is_calc_hess = from_raw ? 0 : 1;
+  HIPCHK(c, hipMemsetAsync(red, 0, C2::NOUT2 * sizeof(double), c->stream));
+  HIPCHK(c, hipMemsetAsync(raw, 0, C2::NOUT2 * sizeof(double), c->stream));
+  HIPCHK(c, hipMemcpyAsync(from_raw ? raw : red, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(s, &h, sizeof(LmDev), hipMemcpyHostToDevice, c->stream));
+  if (copy_raw) hipLaunchKernelGGL((k_lm_solve_m<W, true>), dim3(c->lm_spec), dim3(256), 0, c->stream, s, red, raw, d_dx);
+  else hipLaunchKernelGGL((k_lm_solve_m<W, false>), dim3(c->lm_spec), dim3(256), 0, c->stream, s, red, raw, d_dx);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(&h, s, sizeof(LmDev), hipMemcpyDeviceToHost, c->stream));
+  return VBA_OK;
+}
+// LI system: pose-pose entries to the lidar tiles, everything else to the compact IMU image (coef = 1); VBA_ERR_BAD_ARG for an
+// entry outside the structure k_li_solve assumes (a coupling of frames more than one apart that is not pose-pose)
+template <int W>
+int dbg_li(vba_ctx *c, DbgBufs &B, const double *H, const double *g, int flags, LmDev &h, double *d_dx) {
+  using C2 = HessCfg2<W>;
+  using LC = LiSolveCfg<W>;
+  constexpr int NT = W > 10 ? 1024 : 512, nw = 15 * W, nl = 6 * W;
+  const int grav = (flags & VBA_SOLVE_GRAVITY) ? 1 : 0, n = nw + 3 * grav, gauge = grav ? 6 : 15, ne1 = li_hb_ne1(W);
+  std::vector<double> hl((size_t)nl * nl, 0.0), hb(li_hb_size(W, 1), 0.0), gi(n, 0.0), gl(nl, 0.0);
+  for (int R = 0; R < n; R++)
+    for (int C = 0; C < n; C++) {
+      const double a = H[(size_t)R * n + C];
+      if (R < nw && C < nw) {
+        const int fa = R / 15, fb = C / 15, ra = R - 15 * fa, cb = C - 15 * fb;
+        if (ra < 6 && cb < 6) hl[(size_t)(6 * fa + ra) * nl + 6 * fb + cb] = a;
+        else if (fa - fb > 1 || fb - fa > 1) { if (a != 0.0) return VBA_ERR_BAD_ARG; }
+        else hb[li_hb_pair(fa, fb) + ra * 15 + cb] = a;
+      } else if (R < nw) hb[ne1 + R * 3 + (C - nw)] = a;
+      else if (C < nw) hb[ne1 + 45 * W + (R - nw) * nw + C] = a;
+      else hb[ne1 + 90 * W + (R - nw) * 3 + (C - nw)] = a;
+    }
+  for (int R = 0; R < n; R++) {
+    const int fa = R / 15, ra = R - 15 * fa;
+    if (R < nw && ra < 6) gl[6 * fa + ra] = g[R]; else gi[R] = g[R];
+  }
+  std::vector<double> img;
+  dbg_lidar_image<W>(hl.data(), gl.data(), false, img);
+  const int copy_raw = (flags & VBA_SOLVE_COPY_RAW) ? 1 : 0, from_raw = copy_raw && (flags & VBA_SOLVE_FROM_RAW);
+  LiDev li{};
+  li.W = W; li.n = n; li.nb = n; li.gravity = grav; li.gauge = gauge; li.F = W - 1; li.imu_coef = 1.0;
+  double *red = nullptr, *raw = nullptr, *himu = nullptr, *gimu = nullptr, *imu = nullptr, *scr = nullptr;
+  LmDev *s = nullptr;
+  LiDev *d_li = nullptr;
+  HIPCHK(c, B.alloc(&red, C2::NOUT2)); HIPCHK(c, B.alloc(&raw, C2::NOUT2)); HIPCHK(c, B.alloc(&s, 1)); HIPCHK(c, B.alloc(&d_li, 1));
+  HIPCHK(c, B.alloc(&himu, hb.size())); HIPCHK(c, B.alloc(&gimu, (size_t)n)); HIPCHK(c, B.alloc(&imu, (size_t)304 * W));
+  if (LC::GL) HIPCHK(c, B.alloc(&scr, LC::l_doubles * LM_SPEC));
+  h.is_calc_hess = from_raw ? 0 : 1;
+  HIPCHK(c, hipMemsetAsync(red, 0, C2::NOUT2 * sizeof(double), c->stream));
+  HIPCHK(c, hipMemsetAsync(raw, 0, C2::NOUT2 * sizeof(double), c->stream));
+  HIPCHK(c, hipMemsetAsync(imu, 0, (size_t)304 * W * sizeof(double), c->stream));
+  HIPCHK(c, hipMemcpyAsync(from_raw ? raw : red, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(himu, hb.data(), hb.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(gimu, gi.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(s, &h, sizeof(LmDev), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d_li, &li, sizeof(LiDev), hipMemcpyHostToDevice, c->stream));
+  if (flags & VBA_SOLVE_DENSE_MASK) {
+    HIPCHK(c, hipFuncSetAttribute((const void *)k_li_solve<W, NT, LC::GL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LC::lds));
+    hipLaunchKernelGGL((k_li_solve<W, NT, LC::GL, true>), dim3(c->lm_spec), dim3(NT), LC::lds, c->stream, s, d_li, red, raw, copy_raw, himu, gimu, imu, n, gauge, grav,
+                       1.0, scr, d_dx);
+  } else {
+    HIPCHK(c, hipFuncSetAttribute((const void *)k_li_solve<W, NT, LC::GL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LC::lds));
+    hipLaunchKernelGGL((k_li_solve<W, NT, LC::GL>), dim3(c->lm_spec), dim3(NT), LC::lds, c->stream, s, d_li, red, raw, copy_raw, himu, gimu, imu, n, gauge, grav,
+                       1.0, scr, d_dx);
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(&h, s, sizeof(LmDev), hipMemcpyDeviceToHost, c->stream));
+  return VBA_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int vba_debug_solve(vba_ctx *c, int kind, int W, int flags, const double *H, const double *g, double u, double v, double *dx, double *q1) {
+  if (!c || !H || !g || !dx || !q1) return VBA_ERR_BAD_ARG;
+  int n;
+  if (kind == VBA_SOLVE_LIDAR) { if (W < 2 || W > 16) return VBA_ERR_BAD_ARG; n = 6 * W; }
+  else if (kind == VBA_SOLVE_LI) { if (W < 2 || W > LI_MAX_W) return VBA_ERR_BAD_ARG; n = 15 * W + ((flags & VBA_SOLVE_GRAVITY) ? 3 : 0); }
+  else if (kind == VBA_SOLVE_DENSE) { if (W < 2 || W > 1024) return VBA_ERR_BAD_ARG; n = 6 * W; }
+  else return VBA_ERR_BAD_ARG;
+  // finite, symmetric input; the damping of every candidate finite (no non-finite value reaches the device)
+  for (int r = 0; r < n; r++) {
+    if (!std::isfinite(g[r])) return VBA_ERR_BAD_ARG;
+    for (int k = 0; k < n; k++) {
+      const double a = H[(size_t)r * n + k];
+      if (!std::isfinite(a) || a != H[(size_t)k * n + r]) return VBA_ERR_BAD_ARG;
+    }
+  }
+  const int ncand = kind == VBA_SOLVE_DENSE ? 1 : c->lm_spec;
+  {
+    double ub = u, vb = v;
+    if (!std::isfinite(u) || !std::isfinite(v)) return VBA_ERR_BAD_ARG;
+    for (int k = 1; k < ncand; k++) { ub = ub * vb; vb = 2 * vb; if (!std::isfinite(ub) || !std::isfinite(vb)) return VBA_ERR_BAD_ARG; }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<LmDev> hv(1);                      // (declared before the buffers: their destructor drains the stream first)
+  DbgBufs B(c->stream);
+  if (kind == VBA_SOLVE_DENSE) {                 // big_damping_iter's solve: host pivot order, k_bigl_* on the device
+    BigStore S;
+    S.b.W = W; S.NP = (n + 7) / 8 * 8; S.ld = (S.NP + 63) / 64 * 64;
+    HIPCHK(c, B.alloc(&S.b.H, (size_t)n * n)); HIPCHK(c, B.alloc(&S.b.g, (size_t)n));
+    HIPCHK(c, B.alloc(&S.d_Ab, (size_t)(S.NP + 1) * S.ld)); HIPCHK(c, B.alloc(&S.d_Tb, (size_t)(S.NP + 1) * 8));
+    HIPCHK(c, B.alloc(&S.d_ord, (size_t)n)); HIPCHK(c, B.alloc(&S.d_vec, (size_t)3 * n));
+    HIPCHK(c, hipMemcpyAsync(S.b.H, H, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(S.b.g, g, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    std::vector<double> hd(n), jt(g, g + n);
+    std::vector<int> ord(n);
+    for (int r = 0; r < n; r++) hd[r] = H[(size_t)r * n + r];
+    for (int r = 0; r < 6; r++) { hd[r] = 1.0; jt[r] = 0.0; }       // gauge VM:452-455
+    big_pivot_order(hd.data(), u, n, ord.data());
+    const int st = big_solve(S, c->stream, ord.data(), u, dx, c->err);
+    if (st) return st;
+    q1[0] = big_q1(dx, hd.data(), jt.data(), u, n);
+    return VBA_OK;
+  }
+  LmDev *h = hv.data();
+  std::memset(h, 0, sizeof(LmDev));
+  for (int f = 0; f < W; f++) { h->x[12 * f] = h->x[12 * f + 4] = h->x[12 * f + 8] = 1.0; }
+  h->u = u; h->v = v;
+  double *d_dx = nullptr;
+  HIPCHK(c, B.alloc(&d_dx, (size_t)ncand * n));
+  int st = VBA_ERR_BAD_ARG;
+  switch (W) {
+#define VBA_DS_CASE(WW) case WW: st = kind == VBA_SOLVE_LIDAR ? dbg_lidar<WW>(c, B, H, g, flags, *h, d_dx) : dbg_li<WW>(c, B, H, g, flags, *h, d_dx); break;
+    VBA_DS_CASE(2) VBA_DS_CASE(3) VBA_DS_CASE(4) VBA_DS_CASE(5) VBA_DS_CASE(6) VBA_DS_CASE(7) VBA_DS_CASE(8) VBA_DS_CASE(9) VBA_DS_CASE(10)
+    VBA_DS_CASE(11) VBA_DS_CASE(12) VBA_DS_CASE(13) VBA_DS_CASE(14) VBA_DS_CASE(15) VBA_DS_CASE(16)
+#undef VBA_DS_CASE
+  }
+  if (st) return st;
+  HIPCHK(c, hipMemcpyAsync(dx, d_dx, (size_t)ncand * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int b = 0; b < ncand; b++) q1[b] = h->q1_spec[b];
   return VBA_OK;
 }
 
