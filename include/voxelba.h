@@ -590,6 +590,88 @@ int vba_btc_gen_reserve(vba_btc_db *db, int64_t points, int64_t cells, int frame
  * storage and offset table in vba_btc_generate_stds), and the bytes of the generator's device buffers */
 int vba_btc_gen_allocations(vba_btc_db *db, int *count, int64_t *bytes);
 
+/* ------------------------------------------------------------------------------------------------
+ * Keyframe store: the counterpart of `vector<Keyframe*> *keyframes`, one store per session, resident in HBM.
+ * A keyframe is built on the device from the scans of its window, kept there, and read from there by keyframe_loading
+ * (VS:1379-1438), descriptor generation (VS:2387-2406, VS:384-409) and the hierarchical BA (VS:2888): points cross the host
+ * boundary once, as scans.
+ *
+ * Layout: one contiguous ragged array double [N][3] of keyframe points in the keyframe's own frame (PCL float values carried in
+ * doubles: the form vba_hba_* and vba_map_cut_voxel_fix take), a parallel float [N][3] of covariance diagonals (normal_x/y/z);
+ * on the host int offsets[n_kf + 1] and per keyframe x0 (pose layout), id, jour, exist.
+ *
+ * Growth and locking: the device arrays are grow-only; growing allocates new blocks, copies device to device and frees the old
+ * ones after a synchronise, so THE ARRAYS MOVE.  A store is not synchronised internally: calls on one store, and any reader of
+ * the pointers vba_kf_clouds returned, must be excluded from vba_kf_build / vba_kf_reserve / vba_kf_load* by the caller's lock,
+ * as mtx_keyframe does for the reference's vector.  After vba_kf_reserve(points, keyframes, merge_points) no call below
+ * allocates device or pinned-host memory of the store while the session holds at most `points` kept points in `keyframes`
+ * keyframes, no merge (a build's scans, a window of vba_kf_generate_stds, a keyframe of vba_kf_load) exceeds `merge_points`
+ * points and no build merges more than 64 scans (vba_kf_allocations counts them, as vba_btc_gen_allocations does).  The store
+ * owns its buffers and nothing else; destroy it before its context.
+ *
+ * Order of operations of the merge (part of the interface; no product below is fused with a sum, on either side).
+ * With xc = the pose of the last cloud, on the host per cloud i:
+ *   dR[r][c] = (xcR[0][r]*R_i[0][c] + xcR[1][r]*R_i[1][c]) + xcR[2][r]*R_i[2][c]
+ *   d_k = p_i[k] - xc_p[k];   dp[r] = (xcR[0][r]*d_0 + xcR[1][r]*d_1) + xcR[2][r]*d_2
+ * on the device per point: q[r] = ((dR[r][0]*x + dR[r][1]*y) + dR[r][2]*z) + dp[r].  The covariance is carried over unrotated,
+ * as the reference does (VS:2366-2370); clouds are concatenated in order i = 0..k-1. */
+typedef struct vba_kf_store vba_kf_store;
+int vba_kf_create(vba_ctx *ctx, vba_kf_store **out);
+void vba_kf_destroy(vba_kf_store *s);
+int vba_kf_reserve(vba_kf_store *s, int64_t points, int keyframes, int64_t merge_points);
+int vba_kf_allocations(vba_kf_store *s, int *count, int64_t *bytes);
+int vba_kf_size(vba_kf_store *s);   /* keyframes->size() */
+/* The keyframe of VS:2354-2397 (online, var != NULL) or VS:348-372 (offline, var == NULL) from k scans: rows offsets[i]..offsets[i+1]
+ * of pnt [][3] (and var [][9]) are scan i, body frame, HOST or DEVICE memory as for vba_map_cut_voxel; poses [k][12], xc = poses[k-1]
+ * becomes the keyframe's x0.  Of a host var only the three diagonal doubles per point are uploaded.
+ * Kept cloud: var != NULL: down_sampling_pvec (VM:39-81) of the merged doubles at voxel_size (the caller passes voxel_size / 10);
+ * var == NULL: down_sampling_voxel (TL:201) of the merged points narrowed to float, diagonals zero (voxel_size >= 0.001).  Both
+ * follow the contract of vba_scan_down_sampling_*: float-narrowed key, voxels in first-occurrence order, mean rounded once to
+ * float, vba_options::deterministic of the store's context honoured.  The result is written straight into the store; *n_points =
+ * its size.
+ * Descriptors: with db != NULL (same device) the merged cloud is narrowed to float (VS:2390-2397) straight into the generator's
+ * point buffer and vba_btc_generate_stds(db, n, ., id, cap, rows, bits, n_stds) runs on it: outputs, side effects, capacity rules
+ * and errors are that call's.  The merged cloud never reaches the host.
+ * Stream-ordered; synchronises once before returning (twice when a generator buffer has to grow; once more when db hangs off
+ * another context, whose stream waits for the merge through an event).  After it returns other contexts on the device may read the
+ * keyframe.  The keyframe is committed (offset, x0, id, jour, exist = 0) only after success; argument errors (k < 1, offsets not
+ * non-decreasing, a non-finite pose, cap below the generator's bound) are found before any device work, and any error leaves
+ * the store and db as they were. */
+int vba_kf_build(vba_kf_store *s, int k, const int *offsets, const double *pnt, const double *var, const double *poses, double voxel_size,
+                 int id, double jour, vba_btc_db *db, int cap, double *rows, uint64_t *bits, int *n_stds, int *n_points);
+/* per-voxel point counts of the last vba_kf_build, in the kept cloud's order (for tests); *n = their number, at most cap written */
+int vba_kf_last_counts(vba_kf_store *s, int cap, int *counts, int *n);
+/* Descriptors of a window of stored keyframes (VS:384-409): keyframes [first, first + count) merged from the store into the frame of
+ * keyframe first+count-1's x0 (the arithmetic above, on the stored float values), narrowed to float and generated with that
+ * keyframe's id.  No point crosses the host boundary.  Otherwise as vba_btc_generate_stds. */
+int vba_kf_generate_stds(vba_kf_store *s, int first, int count, vba_btc_db *db, int cap, double *rows, uint64_t *bits, int *n_stds);
+/* kf->x0 = scanPoses[kf->id]->x for keyframes [first, first + n) (VS:2582-2587, VS:2798-2803) */
+int vba_kf_set_poses(vba_kf_store *s, int first, int n, const double *poses /* [n][12] */);
+int vba_kf_get(vba_kf_store *s, int k, double *pose12, int *id, double *jour, int *exist, int *n_points);   /* any output may be NULL */
+/* VS:2628-2647: exist = 1 for keyframes below n_hist and 0 for the rest, the positions x0.p of the first n_hist keyframes
+ * snapshot as floats (pl_kdmap), history_kfsize = n_hist.  n_hist = 0 switches loading off (the subsize <= init_num case). */
+int vba_kf_set_history(vba_kf_store *s, int n_hist);
+int vba_kf_history_size(vba_kf_store *s);   /* history_kfsize */
+/* The body of keyframe_loading for keyframe k (VS:1407-1432): world = x0.R p + x0.p in the operation order above from the stored
+ * values, inserted in stored order as fixed points with vba_map_cut_voxel_fix's semantics into map_ctx's map, from HBM; exist = 0.
+ * map_ctx may be another context on the same device (VBA_ERR_BAD_ARG for another device); the work runs on ITS stream and the call
+ * synchronises it once (the map's counter read-back). */
+int vba_kf_load(vba_kf_store *s, int k, vba_ctx *map_ctx, double jour);
+/* keyframe_loading(jour) (VS:1379-1438) around p3 = x_curr.p: returns at once while history_kfsize <= 0; otherwise the snapshot
+ * positions within `radius` (10 in the reference), nearest first, and the first one whose keyframe has exist != 0 is loaded
+ * (vba_kf_load) and history_kfsize decremented: at most one load per call.  *loaded = its index, -1 = none.
+ * Rule chosen here (the reference leaves it to FLANN, which is not restated): the squared distance is accumulated x, y, z in float
+ * between the float snapshot and (float)p3; a position is inside when d2 < (float)(radius * radius), so a point exactly on the
+ * sphere is outside; equal distances are taken in ascending keyframe index.  The search runs on the host, the load on the device. */
+int vba_kf_load_nearby(vba_kf_store *s, vba_ctx *map_ctx, const double *p3, double radius, double jour, int *loaded);
+/* keyframe k to the host (tests, save_pcd): xyz [cap][3], vardiag [cap][3] (either may be NULL); *n = its size */
+int vba_kf_read(vba_kf_store *s, int k, int cap, double *xyz, float *vardiag, int *n);
+/* Zero copy: the store's device array and host offsets are the (offsets, pnt_local) arguments of vba_gba_build / vba_hba_add_edge /
+ * vba_hba_global, which accept a device pnt_local: vba_hba_global(ctx, n, offsets, d_pnt, ...) on these pointers replaces the
+ * upload of the keyframe clouds.  For a window starting at keyframe f pass d_pnt + 3 * offsets[f] and offsets rebased to
+ * offsets[f].  The pointers are valid until the next call that may grow the store (see "Growth and locking"). */
+int vba_kf_clouds(vba_kf_store *s, const double **d_pnt, const int **offsets, int *n_kf);
+
 #ifdef __cplusplus
 }
 #endif

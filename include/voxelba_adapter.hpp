@@ -503,6 +503,22 @@ inline void pack_stds(const std::vector<STD> &v, std::vector<double> &rows, std:
   }
 }
 
+inline void unpack_stds(const std::vector<double> &rows, const std::vector<uint64_t> &bits, int n, std::vector<STD> &stds_vec) {
+  stds_vec.assign(n, STD{});
+  for (int i = 0; i < n; i++) {
+    const double *r = rows.data() + (size_t)i * VBA_BTC_ROW_LEN;
+    STD &d = stds_vec[i];
+    BinaryDescriptor *b[3] = {&d.binary_A_, &d.binary_B_, &d.binary_C_};
+    for (int u = 0; u < 3; u++) { d.triangle_[u] = r[u]; d.center_[u] = r[3 + u]; }
+    d.frame_number_ = (int)r[6];
+    for (int e = 0; e < 3; e++) {
+      for (int u = 0; u < 3; u++) b[e]->location_[u] = r[7 + 3 * e + u];
+      b[e]->summary_ = (unsigned char)r[16 + e];
+      b[e]->occupy_bits = bits[3 * (size_t)i + e];
+    }
+  }
+}
+
 // STDescManager's database: one per session, on the loop-closure thread's context.  Destroy it before its Context.
 class BtcDatabase {
  public:
@@ -533,20 +549,9 @@ class BtcDatabase {
     std::vector<uint64_t> bits((size_t)(gen_cap_ > 0 ? gen_cap_ : 1) * 3);
     int n = 0;
     check(ctx_, vba_btc_generate_stds(db_, (int)(xyz.size() / 3), xyz.data(), id, gen_cap_, rows.data(), bits.data(), &n));
-    stds_vec.assign(n, STD{});
-    for (int i = 0; i < n; i++) {
-      const double *r = rows.data() + (size_t)i * VBA_BTC_ROW_LEN;
-      STD &d = stds_vec[i];
-      BinaryDescriptor *b[3] = {&d.binary_A_, &d.binary_B_, &d.binary_C_};
-      for (int u = 0; u < 3; u++) { d.triangle_[u] = r[u]; d.center_[u] = r[3 + u]; }
-      d.frame_number_ = (int)r[6];
-      for (int e = 0; e < 3; e++) {
-        for (int u = 0; u < 3; u++) b[e]->location_[u] = r[7 + 3 * e + u];
-        b[e]->summary_ = (unsigned char)r[16 + e];
-        b[e]->occupy_bits = bits[3 * (size_t)i + e];
-      }
-    }
+    unpack_stds(rows, bits, n, stds_vec);
   }
+  int gen_cap() const { return gen_cap_; }
   int plane_cloud_seq(int frame) const { int s = 0; check(ctx_, vba_btc_frame_seq(db_, frame, &s)); return s; }
   void AddSTDescs(const std::vector<STD> &stds) {                          // BTC.cpp:258-277
     std::vector<double> rows; std::vector<uint64_t> bits;
@@ -590,6 +595,85 @@ inline bool icp_normal(BtcDatabase &src, int src_frame, BtcDatabase &tar, int ta
   if (st != VBA_OK) throw std::runtime_error(std::string("libvoxelba: icp_normal: ") + vba_status_string(st));
   return ok != 0;
 }
+
+// `vector<Keyframe*> *keyframes` of one session, resident in HBM (voxelba.h "Keyframe store").  The caller's
+// mtx_keyframe excludes readers while build / reserve / keyframe_loading run: growing the store moves its arrays.  Destroy it
+// before its Context.
+struct ScanPoseRef { const IMUST *x; const PVec *pvec; };   // what VS:2357-2371 reads of a ScanPose: bl.x and *bl.pvec
+class KeyframeStore {
+ public:
+  explicit KeyframeStore(Context &ctx) : ctx_(ctx.get()) { check(ctx_, vba_kf_create(ctx_, &s_)); }
+  ~KeyframeStore() { vba_kf_destroy(s_); }
+  KeyframeStore(const KeyframeStore &) = delete;
+  KeyframeStore &operator=(const KeyframeStore &) = delete;
+  vba_kf_store *get() const { return s_; }
+  void reserve(int64_t points, int keyframes, int64_t merge_points) { check(ctx_, vba_kf_reserve(s_, points, keyframes, merge_points)); }
+  int size() const { return vba_kf_size(s_); }                                  // keyframes->size()
+  // VS:2354-2406: the scans of bl_local merged into the frame of the last one (its x becomes the keyframe's x0),
+  // down_sampling_pvec(voxel_size / 10) kept as the keyframe's cloud, and, with a database, GenerateSTDescs(plbtc, stds_vec, id) on
+  // the merged cloud.  Returns the size of the kept cloud.
+  int build(const std::vector<ScanPoseRef> &bl_local, double voxel_size_10, int id, double jour, BtcDatabase *db = nullptr,
+            std::vector<STD> *stds_vec = nullptr) {
+    const int k = (int)bl_local.size();
+    std::vector<int> off(k + 1, 0);
+    for (int i = 0; i < k; i++) off[i + 1] = off[i] + (int)bl_local[i].pvec->size();
+    std::vector<double> pnt((size_t)off[k] * 3), var((size_t)off[k] * 9), poses((size_t)k * 12);
+    for (int i = 0; i < k; i++) {
+      std::memcpy(&poses[(size_t)i * 12], bl_local[i].x->R, 72); std::memcpy(&poses[(size_t)i * 12 + 9], bl_local[i].x->p, 24);
+      size_t r = (size_t)off[i];
+      for (const pointVar &pv : *bl_local[i].pvec) { std::memcpy(&pnt[3 * r], pv.pnt, 24); std::memcpy(&var[9 * r], pv.var, 72); r++; }
+    }
+    const int cap = db ? db->gen_cap() : 0;
+    std::vector<double> rows((size_t)(cap > 0 ? cap : 1) * VBA_BTC_ROW_LEN);
+    std::vector<uint64_t> bits((size_t)(cap > 0 ? cap : 1) * 3);
+    int n = 0, kept = 0;
+    check(ctx_, vba_kf_build(s_, k, off.data(), pnt.data(), var.data(), poses.data(), voxel_size_10, id, jour, db ? db->get() : nullptr, cap,
+                             rows.data(), bits.data(), &n, &kept));
+    if (db && stds_vec) unpack_stds(rows, bits, n, *stds_vec);
+    return kept;
+  }
+  // VS:384-409: descriptors of keyframes [first, first + count) merged into the last one's frame, from the store
+  void GenerateSTDescs(int first, int count, BtcDatabase &db, std::vector<STD> &stds_vec) {
+    const int cap = db.gen_cap();
+    std::vector<double> rows((size_t)(cap > 0 ? cap : 1) * VBA_BTC_ROW_LEN);
+    std::vector<uint64_t> bits((size_t)(cap > 0 ? cap : 1) * 3);
+    int n = 0;
+    check(ctx_, vba_kf_generate_stds(s_, first, count, db.get(), cap, rows.data(), bits.data(), &n));
+    unpack_stds(rows, bits, n, stds_vec);
+  }
+  // kf->x0 = scanPoses[kf->id]->x (VS:2582-2587): xs[i] is the new pose of keyframe first + i
+  void set_poses(int first, const std::vector<IMUST> &xs) {
+    const std::vector<double> p = LidarFactor::poses_of(xs);
+    check(ctx_, vba_kf_set_poses(s_, first, (int)xs.size(), p.data()));
+  }
+  void set_history(int n_hist) { check(ctx_, vba_kf_set_history(s_, n_hist)); }  // VS:2628-2647
+  int history_kfsize() const { return vba_kf_history_size(s_); }
+  // keyframe_loading(jour) (VS:1379-1438) into the map of `map` around x_curr.p; returns the loaded keyframe or -1
+  int keyframe_loading(Context &map, const IMUST &x_curr, double jour, double radius = 10) {
+    int k = -1;
+    check(ctx_, vba_kf_load_nearby(s_, map.get(), x_curr.p, radius, jour, &k));
+    return k;
+  }
+  // the (offsets, pnt_local) arguments of vba_hba_add_edge / vba_hba_global / vba_gba_build, zero copy: pnt_local is DEVICE memory
+  void clouds(const double *&d_pnt, const int *&offsets, int &n_kf) const { check(ctx_, vba_kf_clouds(s_, &d_pnt, &offsets, &n_kf)); }
+  // keyframe k's plptr on the host (save_pcd, tests): x y z and normal_x/y/z
+  void read(int k, std::vector<XYZ> &xyz, std::vector<XYZ> *normal = nullptr) const {
+    int n = 0;
+    check(ctx_, vba_kf_read(s_, k, 0, nullptr, nullptr, &n));
+    std::vector<double> p((size_t)(n > 0 ? n : 1) * 3);
+    std::vector<float> v((size_t)(n > 0 ? n : 1) * 3);
+    check(ctx_, vba_kf_read(s_, k, n, p.data(), v.data(), &n));
+    xyz.resize(n);
+    if (normal) normal->resize(n);
+    for (int i = 0; i < n; i++) {
+      xyz[i] = XYZ{(float)p[3 * (size_t)i], (float)p[3 * (size_t)i + 1], (float)p[3 * (size_t)i + 2]};
+      if (normal) (*normal)[i] = XYZ{v[3 * (size_t)i], v[3 * (size_t)i + 1], v[3 * (size_t)i + 2]};
+    }
+  }
+ private:
+  vba_ctx *ctx_ = nullptr;
+  vba_kf_store *s_ = nullptr;
+};
 
 #ifdef VBA_ADAPTER_HAVE_EIGEN
 // Eigen-typed conveniences so reference call sites keep their argument types (Eigen is column-major: converted here).

@@ -39,6 +39,9 @@ EXPORTS = [
     "vba_btc_default_gen_config", "vba_btc_set_gen_config", "vba_btc_generate_stds", "vba_btc_plane_cloud", "vba_btc_last_corners",
     "vba_btc_gen_reserve", "vba_btc_gen_allocations", "vba_btc_get_gen_config",
     "vba_pgo_optimize",
+    "vba_kf_create", "vba_kf_destroy", "vba_kf_reserve", "vba_kf_allocations", "vba_kf_size", "vba_kf_build", "vba_kf_last_counts",
+    "vba_kf_generate_stds", "vba_kf_set_poses", "vba_kf_get", "vba_kf_set_history", "vba_kf_history_size", "vba_kf_load",
+    "vba_kf_load_nearby", "vba_kf_read", "vba_kf_clouds",
 ]
 
 
@@ -231,6 +234,137 @@ class BtcDb:
         return dict(ok=ok.value, t=tt, R=RR, eig=eig, iters=it.value)
 
 
+class KeyframeStore:
+    """One vba_kf_store: the session's keyframes (``vector<Keyframe*> *keyframes``) resident in HBM."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx._chk(self.lib.vba_kf_create(ctx.h, C.byref(h)))
+        self.h = h
+        ctx._kf.append(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.vba_kf_destroy(self.h)
+            self.h = None
+        kf = getattr(self.ctx, "_kf", None)
+        if kf is not None and self in kf:
+            kf.remove(self)
+
+    def reserve(self, points=0, keyframes=0, merge_points=0):
+        self.ctx._chk(self.lib.vba_kf_reserve(self.h, C.c_int64(points), C.c_int(keyframes), C.c_int64(merge_points)))
+
+    def allocations(self):
+        n = C.c_int(); b = C.c_int64()
+        self.ctx._chk(self.lib.vba_kf_allocations(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def size(self):
+        return self.lib.vba_kf_size(self.h)
+
+    def build(self, scans, poses, voxel_size, id, jour=0.0, vars=None, db=None, cap=None, offsets=None):
+        """The keyframe of VS:2354-2397 from ``scans`` (list of [n_i][3], or one [N][3] array with ``offsets``), ``vars`` the
+        matching [n_i][9] covariances or None (the offline form), ``poses`` [k][12]; with ``db`` the descriptors of the merged cloud
+        are generated too.  Returns (kept points, rows, bits); rows / bits are None without a database."""
+        if offsets is None:
+            off, pnt = Context._ragged(scans)
+            var = np.ascontiguousarray(np.concatenate([np.reshape(v, (-1, 9)) for v in vars]), dtype=np.float64) if vars is not None else None
+        else:
+            off = np.ascontiguousarray(offsets, dtype=np.int32); pnt = _c(scans)
+            var = _c(vars) if vars is not None else None
+        poses = _c(poses).reshape(-1, 12)
+        k = len(off) - 1
+        if len(poses) != k:
+            raise ValueError("one pose per scan")
+        rows = bits = None; ns = C.c_int(); npt = C.c_int()
+        if db is not None:
+            if cap is None:
+                cap = btc_max_stds(getattr(db, "gcfg", None) or btc_default_gen_config(0))
+            rows = np.zeros((max(cap, 1), BTC_ROW_LEN)); bits = np.zeros((max(cap, 1), 3), dtype=np.uint64)
+        self.ctx._chk(self.lib.vba_kf_build(self.h, C.c_int(k), off.ctypes.data_as(C.POINTER(C.c_int)), _p(pnt), _p(var), _p(poses),
+                                            C.c_double(voxel_size), C.c_int(int(id)), C.c_double(jour), db.h if db is not None else None,
+                                            C.c_int(cap if db is not None else 0), _p(rows),
+                                            bits.ctypes.data_as(C.POINTER(C.c_uint64)) if bits is not None else None, C.byref(ns), C.byref(npt)))
+        if db is None:
+            return npt.value, None, None
+        return npt.value, rows[:ns.value].copy(), bits[:ns.value].copy()
+
+    def last_counts(self):
+        n = C.c_int()
+        self.ctx._chk(self.lib.vba_kf_last_counts(self.h, C.c_int(0), None, C.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.int32)
+        self.ctx._chk(self.lib.vba_kf_last_counts(self.h, C.c_int(n.value), out.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n)))
+        return out[:n.value].copy()
+
+    def generate_stds(self, first, count, db, cap=None):
+        """descriptors of keyframes [first, first + count) merged into the last one's frame (VS:384-409) -> (rows, bits)"""
+        if cap is None:
+            cap = btc_max_stds(getattr(db, "gcfg", None) or btc_default_gen_config(0))
+        rows = np.zeros((max(cap, 1), BTC_ROW_LEN)); bits = np.zeros((max(cap, 1), 3), dtype=np.uint64); n = C.c_int()
+        self.ctx._chk(self.lib.vba_kf_generate_stds(self.h, C.c_int(first), C.c_int(count), db.h, C.c_int(cap), _p(rows),
+                                                    bits.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)))
+        return rows[:n.value].copy(), bits[:n.value].copy()
+
+    def set_poses(self, first, poses):
+        poses = _c(poses).reshape(-1, 12)
+        self.ctx._chk(self.lib.vba_kf_set_poses(self.h, C.c_int(first), C.c_int(len(poses)), _p(poses)))
+
+    def get(self, k):
+        pose = np.zeros(12); i = C.c_int(); j = C.c_double(); e = C.c_int(); n = C.c_int()
+        self.ctx._chk(self.lib.vba_kf_get(self.h, C.c_int(k), _p(pose), C.byref(i), C.byref(j), C.byref(e), C.byref(n)))
+        return dict(x0=pose, id=i.value, jour=j.value, exist=e.value, n_points=n.value)
+
+    def set_history(self, n_hist):
+        self.ctx._chk(self.lib.vba_kf_set_history(self.h, C.c_int(n_hist)))
+
+    def history_size(self):
+        return self.lib.vba_kf_history_size(self.h)
+
+    def load(self, k, map_ctx, jour=0.0):
+        self.ctx._chk(self.lib.vba_kf_load(self.h, C.c_int(k), map_ctx.h, C.c_double(jour)))
+
+    def load_nearby(self, map_ctx, p3, radius=10.0, jour=0.0):
+        """keyframe_loading(jour) around p3 -> index of the loaded keyframe, -1 = none"""
+        k = C.c_int(-1)
+        self.ctx._chk(self.lib.vba_kf_load_nearby(self.h, map_ctx.h, _p(_c(p3)), C.c_double(radius), C.c_double(jour), C.byref(k)))
+        return k.value
+
+    def read(self, k):
+        """keyframe k -> (xyz [n][3] float values in doubles, covariance diagonals float32 [n][3])"""
+        n = C.c_int()
+        self.ctx._chk(self.lib.vba_kf_read(self.h, C.c_int(k), C.c_int(0), None, None, C.byref(n)))
+        xyz = np.zeros((max(n.value, 1), 3)); vd = np.zeros((max(n.value, 1), 3), dtype=np.float32)
+        self.ctx._chk(self.lib.vba_kf_read(self.h, C.c_int(k), C.c_int(n.value), _p(xyz), vd.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n)))
+        return xyz[:n.value].copy(), vd[:n.value].copy()
+
+    def hba_add_edge(self, ctx, first, count, poses, gba_voxel_size, gba_min_eigen_value, gba_eig, max_iter, thread_num):
+        """vba_hba_add_edge on ``ctx`` over keyframes [first, first + count) read in place from the store (no upload of the clouds);
+        poses [count][12] are the poses to optimise (the reference passes the keyframes' x0).  Result as Context.hba_add_edge."""
+        d, off, _ = self.clouds()
+        rel = np.ascontiguousarray(off[first:first + count + 1] - off[first], dtype=np.int32)
+        base = C.c_void_p(d + 24 * int(off[first]))
+        poses = _c(poses).reshape(count, 12).copy()
+        npt = int(rel[-1])
+        edges = np.zeros((count * (count - 1) // 2 + 1, 20)); ne = C.c_int(0)
+        cloud = np.zeros((max(npt, 1), 3)); ccnt = np.zeros(max(npt, 1), dtype=np.int32); nc = C.c_int(0)
+        rl = np.zeros((max_iter + 1, 2)); nl = C.c_int(0)
+        ctx._chk(self.lib.vba_hba_add_edge(ctx.h, C.c_int(count), rel.ctypes.data_as(C.POINTER(C.c_int)), base, _p(poses),
+                                           C.c_double(gba_voxel_size), C.c_double(gba_min_eigen_value), _p(_c(gba_eig)), C.c_int(max_iter),
+                                           C.c_int(thread_num), _p(edges), C.byref(ne), _p(cloud), ccnt.ctypes.data_as(C.POINTER(C.c_int)),
+                                           C.byref(nc), _p(rl), C.byref(nl)))
+        return dict(poses=poses, edges=edges[:ne.value].copy(), cloud=cloud[:nc.value].copy(), cloud_count=ccnt[:nc.value].copy(),
+                    resis=rl[:nl.value].copy())
+
+    def clouds(self):
+        """(device address of the point array, host offsets [n_kf + 1] (a copy), n_kf): the arguments of vba_hba_*"""
+        d = C.c_void_p(); o = C.POINTER(C.c_int)(); n = C.c_int()
+        self.ctx._chk(self.lib.vba_kf_clouds(self.h, C.byref(d), C.byref(o), C.byref(n)))
+        off = np.array([o[i] for i in range(n.value + 1)], dtype=np.int32)
+        return (d.value or 0), off, n.value
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 
@@ -396,9 +530,12 @@ class Context:
         self.h = h
         self._cb = None
         self._btc = []
+        self._kf = []
 
     def close(self):
-        for db in list(getattr(self, "_btc", [])):     # (a database belongs to its context: destroyed first)
+        for kf in list(getattr(self, "_kf", [])):      # (stores and databases belong to their context: destroyed first)
+            kf.close()
+        for db in list(getattr(self, "_btc", [])):
             db.close()
         if getattr(self, "h", None):
             self.lib.vba_destroy(self.h)
@@ -562,6 +699,9 @@ class Context:
     # ---- loop retrieval (BTC.cpp, loop_refine.hpp)
     def btc_db(self, config=None) -> "BtcDb":
         return BtcDb(self, config if config is not None else btc_default_config(0))
+
+    def kf_store(self) -> "KeyframeStore":
+        return KeyframeStore(self)
 
     def btc_search_loop_sessions(self, dbs, rows, bits, cur_db, cur_frame=-1):
         """SearchLoop of one query against every database (VS:2417-2421): one upload, one synchronisation."""

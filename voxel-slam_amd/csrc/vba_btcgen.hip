@@ -697,7 +697,7 @@ hipError_t btcgen_enqueue(BtcGen &g, const BgCfg &cf, int n, const float *h_xyz,
   BgPlane *cpl = (BgPlane *)g.planes, *pl = cpl + pc, *grp = pl + pc, *srt = grp + pc, *mrg = srt + pc;
   BgPlane *fin = cpl;                                     // the candidates are dead once the planes are compacted
   BGCHK(hipMemsetAsync(g.cnt, 0, BGC_N * sizeof(int), st));
-  BGCHK(hipMemcpyAsync(g.xyz, h_xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+  if (h_xyz) BGCHK(hipMemcpyAsync(g.xyz, h_xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, st));   // nullptr: g.xyz was filled on the device
   // voxels
   k_bg_key<<<nb, 256, 0, st>>>(n, g.xyz, cf.vsize, g.key, g.idx, g.cnt);
   size_t tb = g.sort_bytes;

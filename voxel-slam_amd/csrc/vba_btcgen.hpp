@@ -54,7 +54,8 @@ struct BtcGen {
 
 // grow the buffers for n points, `cells` image cells, `corners` temporary corners and `stds` triangle candidates (0 keeps a size)
 hipError_t btcgen_reserve(BtcGen &g, size_t n, size_t cells, size_t corners, size_t stds, int vinit, hipStream_t st);
-// enqueue one GenerateSTDescs over n >= 1 host points; the plane cloud goes to pc_dst (room for n / (vinit + 1) + 1 points) and
+// enqueue one GenerateSTDescs over n >= 1 host points (h_xyz == nullptr: the caller has already enqueued the writes of the
+// points into g.xyz on st); the plane cloud goes to pc_dst (room for n / (vinit + 1) + 1 points) and
 // its end offset (have + planes) to *off_slot; the counters, triangles and corners land in g.h_cnt / h_stds / h_corn after the
 // caller synchronises the stream
 hipError_t btcgen_enqueue(BtcGen &g, const BgCfg &cfg, int n, const float *h_xyz, float *pc_dst, int *off_slot, int have, hipStream_t st);

@@ -1,0 +1,78 @@
+// Keyframe store (vba_kf_*): the merge of K clouds into the frame of the last one's pose (VS:2354-2371, VS:348-372,
+// VS:384-398), the emit of the kept cloud into the store, and the keyframe -> world transform of keyframe_loading (VS:1418-1427).
+// One thread per point, lanes on consecutive points.  Every product and sum below is rounded on its own (no contraction): the
+// order of operations is part of the interface (include/voxelba.h).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "vba_kernels_scan.hpp"
+
+namespace vba {
+
+// q = ((T[0] x + T[1] y) + T[2] z) + T[9], ... with T = [dR row-major (9), dp (3)]
+__device__ __forceinline__ void kf_apply(const double *__restrict__ T, double x, double y, double z, double &qx, double &qy, double &qz) {
+#pragma clang fp contract(off)
+  qx = ((T[0] * x + T[1] * y) + T[2] * z) + T[9];
+  qy = ((T[3] * x + T[4] * y) + T[5] * z) + T[10];
+  qz = ((T[6] * x + T[7] * y) + T[8] * z) + T[11];
+}
+
+// Merge: point i of the concatenated input belongs to scan j with off[j] <= i < off[j + 1] and moves by xf[j] ([k][12]).
+//   out   double [n][3]  the merged cloud (down-sampler input), may be nullptr
+//   outf  float  [n][3]  the same narrowed to float (the descriptor generator's point buffer), may be nullptr
+//   var / vout           covariance rows (vrow doubles apart, diagonal entries vstep apart) -> double [n][3] diagonals, unrotated
+__global__ __launch_bounds__(256) void k_kf_merge(int n, int k, const int *__restrict__ off, const double *__restrict__ xf, const double *__restrict__ pnt,
+                                                  const double *__restrict__ var, int vrow, int vstep, double *__restrict__ out, float *__restrict__ outf,
+                                                  double *__restrict__ vout) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  int lo = 0, hi = k - 1;                                   // last j with off[j] <= i (empty scans are skipped by the <=)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  const double *T = xf + 12 * lo;
+  const size_t b = 3 * (size_t)i;
+  double qx, qy, qz;
+  kf_apply(T, pnt[b], pnt[b + 1], pnt[b + 2], qx, qy, qz);
+  if (out) { out[b] = qx; out[b + 1] = qy; out[b + 2] = qz; }
+  if (outf) { outf[b] = (float)qx; outf[b + 1] = (float)qy; outf[b + 2] = (float)qz; }
+  if (vout) {
+    const double *v = var + (size_t)vrow * (size_t)i;
+    vout[b] = v[0]; vout[b + 1] = v[vstep]; vout[b + 2] = v[2 * vstep];
+  }
+}
+
+// keyframe_loading: world = x0.R p + x0.p in the same operation order, T = the keyframe's x0 ([12])
+__global__ __launch_bounds__(256) void k_kf_world(int n, const double *__restrict__ T, const double *__restrict__ pnt, double *__restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const size_t b = 3 * (size_t)i;
+  double qx, qy, qz;
+  kf_apply(T, pnt[b], pnt[b + 1], pnt[b + 2], qx, qy, qz);
+  out[b] = qx; out[b + 1] = qy; out[b + 2] = qz;
+}
+
+// k_ds_emit for the store: centroid rounded once to float and carried in doubles, the mean covariance diagonal as float (zero
+// without covariances), the voxel's point count; first-occurrence order
+__global__ __launch_bounds__(256) void k_kf_emit(int n, const DsSlot *__restrict__ tab, const int *__restrict__ slot_of, const int *__restrict__ blk,
+                                                 double *__restrict__ out, float *__restrict__ vout, int *__restrict__ count, int have_var) {
+  __shared__ int wsum[4];
+  const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  DsSlot s;
+  int f = 0;
+  if (i < n) { s = tab[slot_of[i]]; f = (s.first == i) ? 1 : 0; }
+  const unsigned long long m = __ballot(f);
+  if (lane == 0) wsum[w] = __popcll(m);
+  __syncthreads();
+  if (!f) return;
+  int pos = blk[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+  for (int k = 0; k < w; k++) pos += wsum[k];
+  const double inv = 1.0 / (double)s.cnt;
+  const size_t b = 3 * (size_t)pos;
+  out[b] = (double)(float)(s.sx * inv); out[b + 1] = (double)(float)(s.sy * inv); out[b + 2] = (double)(float)(s.sz * inv);
+  vout[b] = have_var ? (float)(s.vx * inv) : 0.0f; vout[b + 1] = have_var ? (float)(s.vy * inv) : 0.0f; vout[b + 2] = have_var ? (float)(s.vz * inv) : 0.0f;
+  count[pos] = s.cnt;
+}
+
+}  // namespace vba

@@ -39,11 +39,12 @@ __global__ void k_ds_clear(DsSlot *__restrict__ tab, int cap) {
 }
 
 // point -> slot (open addressing, linear probing), sums, count, first point of the voxel
+// the covariance diagonal of point i is var[vrow * i + {0, vstep, 2 vstep}]: (9, 4) for [n][9] matrices, (3, 1) for gathered diagonals
 // var != nullptr: pointVar input (down_sampling_pvec, VM:39-83): double coordinates, the covariance diagonal is averaged too
 // DET (deterministic mode): no f64 atomics; the sums are added by k_ds_sum_det in input order
 template <bool DET>
 __global__ void k_ds_insert(int n, const double *__restrict__ pnt, const double *__restrict__ var, double voxel_size, DsSlot *__restrict__ tab, int cap_mask,
-                            int *__restrict__ slot_of) {
+                            int *__restrict__ slot_of, int vrow = 9, int vstep = 4) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int dbl = var != nullptr;
@@ -59,7 +60,7 @@ __global__ void k_ds_insert(int n, const double *__restrict__ pnt, const double 
     atomicAdd(&tab[h].sx, dbl ? x : (double)(float)x);
     atomicAdd(&tab[h].sy, dbl ? y : (double)(float)y);
     atomicAdd(&tab[h].sz, dbl ? z : (double)(float)z);
-    if (dbl) { atomicAdd(&tab[h].vx, var[9 * (size_t)i]); atomicAdd(&tab[h].vy, var[9 * (size_t)i + 4]); atomicAdd(&tab[h].vz, var[9 * (size_t)i + 8]); }
+    if (dbl) { const double *v = var + (size_t)vrow * (size_t)i; atomicAdd(&tab[h].vx, v[0]); atomicAdd(&tab[h].vy, v[vstep]); atomicAdd(&tab[h].vz, v[2 * vstep]); }
   }
   atomicAdd(&tab[h].cnt, 1);
   atomicMin(&tab[h].first, i);
@@ -79,7 +80,7 @@ __global__ void k_ds_segstart(int n, const unsigned int *__restrict__ skey, DsSl
   if (j == 0 || skey[j] != skey[j - 1]) tab[skey[j]].pad = j;
 }
 __global__ void k_ds_sum_det(int n, const double *__restrict__ pnt, const double *__restrict__ var, const int *__restrict__ sidx, DsSlot *__restrict__ tab,
-                             const int *__restrict__ slot_of) {
+                             const int *__restrict__ slot_of, int vrow = 9, int vstep = 4) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   DsSlot *s = tab + slot_of[i];
@@ -90,7 +91,7 @@ __global__ void k_ds_sum_det(int n, const double *__restrict__ pnt, const double
     const size_t q = (size_t)sidx[j];
     const double x = pnt[3 * q], y = pnt[3 * q + 1], z = pnt[3 * q + 2];
     sx += dbl ? x : (double)(float)x; sy += dbl ? y : (double)(float)y; sz += dbl ? z : (double)(float)z;
-    if (dbl) { vx += var[9 * q]; vy += var[9 * q + 4]; vz += var[9 * q + 8]; }
+    if (dbl) { const double *v = var + (size_t)vrow * q; vx += v[0]; vy += v[vstep]; vz += v[2 * vstep]; }
   }
   s->sx = sx; s->sy = sy; s->sz = sz;
   if (dbl) { s->vx = vx; s->vy = vy; s->vz = vz; }

@@ -1949,6 +1949,38 @@ int vba_scan_var_init(vba_ctx *c, int n, const double *pnt_in, const double *ext
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return VBA_OK;
 }
+// The device half of the down-samplers: everything between the input and the emit, on buffers the caller owns.
+//   tab [cap] slots (cap a power of two >= 2n), slot [n], blk [(n + 255) / 256], n_out [1]; dist [n] for mode 2;
+//   deterministic mode: skey / idx / sidx [n] and rocPRIM scratch tmp (sort_pairs_u32 over n keys of key_bits bits).
+// After it the table holds every voxel's sums, count and first point, blk the exclusive scan of the per-block voxel counts and
+// *n_out the number of voxels: what k_ds_emit (and the keyframe store's k_kf_emit) compact in first-occurrence order.
+struct DsWork {
+  DsSlot *tab = nullptr; int cap = 0; unsigned int key_bits = 0;
+  int *slot = nullptr, *blk = nullptr, *n_out = nullptr; double *dist = nullptr;
+  unsigned int *skey = nullptr; int *idx = nullptr, *sidx = nullptr; void *tmp = nullptr; size_t tmp_bytes = 0;
+};
+static int ds_core(vba_ctx *c, hipStream_t stream, int mode, int n, const double *d_in, const double *d_var, int vrow, int vstep, double voxel_size,
+                   bool det, const DsWork &w) {
+  const int nb = (n + 255) / 256;
+  hipLaunchKernelGGL(k_ds_clear, dim3((w.cap + 255) / 256), dim3(256), 0, stream, w.tab, w.cap);
+  if (det) {
+    hipLaunchKernelGGL(k_ds_insert<true>, dim3(nb), dim3(256), 0, stream, n, d_in, d_var, voxel_size, w.tab, w.cap - 1, w.slot, vrow, vstep);
+    hipLaunchKernelGGL(k_iota, dim3(nb), dim3(256), 0, stream, w.idx, n);
+    size_t tmp = w.tmp_bytes;
+    HIPCHK(c, sort_pairs_u32(w.tmp, tmp, (const unsigned int *)w.slot, w.skey, w.idx, w.sidx, (size_t)n, w.key_bits, stream));
+    hipLaunchKernelGGL(k_ds_segstart, dim3(nb), dim3(256), 0, stream, n, w.skey, w.tab);
+    hipLaunchKernelGGL(k_ds_sum_det, dim3(nb), dim3(256), 0, stream, n, d_in, d_var, w.sidx, w.tab, w.slot, vrow, vstep);
+  } else {
+    hipLaunchKernelGGL(k_ds_insert<false>, dim3(nb), dim3(256), 0, stream, n, d_in, d_var, voxel_size, w.tab, w.cap - 1, w.slot, vrow, vstep);
+  }
+  if (mode == 2) {
+    hipLaunchKernelGGL(k_ds_close_min, dim3(nb), dim3(256), 0, stream, n, d_in, w.tab, w.slot, w.dist);
+    hipLaunchKernelGGL(k_ds_close_arg, dim3(nb), dim3(256), 0, stream, n, w.tab, w.slot, w.dist);
+  }
+  hipLaunchKernelGGL(k_ds_count, dim3(nb), dim3(256), 0, stream, n, w.tab, w.slot, w.blk);
+  hipLaunchKernelGGL(k_ds_scan, dim3(1), dim3(256), 0, stream, nb, w.blk, w.n_out);
+  return VBA_OK;
+}
 // mode 0 down_sampling_voxel, 1 down_sampling_pvec (var in, vout out), 2 down_sampling_close (first_out = chosen indices)
 static int ds_common(vba_ctx *c, int mode, int n, const double *pnt, const double *var, double voxel_size, double *pnt_out, double *vout, int *count_out,
                      int *first_out, int *n_out) {
@@ -1993,27 +2025,15 @@ static int ds_common(vba_ctx *c, int mode, int n, const double *pnt, const doubl
   if (mode == 1) HIPCHK(c, hipMemcpyAsync(d_var, var, b_var, hipMemcpyDefault, c->stream));
   TimedSpan sp{};
   span_begin(c, "downsample", sp);
-  hipLaunchKernelGGL(k_ds_clear, dim3((cap + 255) / 256), dim3(256), 0, c->stream, tab, cap);
+  DsWork w{};
+  w.tab = tab; w.cap = cap; w.key_bits = key_bits; w.slot = d_slot; w.blk = d_blk; w.n_out = d_n; w.dist = d_dist;
   if (det) {
     char *sb = (char *)(((uintptr_t)((char *)d_n + 64) + 255) & ~(uintptr_t)255);
-    unsigned int *d_skey = (unsigned int *)sb;
-    int *d_idx = (int *)(sb + b_i), *d_sidx = (int *)(sb + 2 * b_i);
-    void *d_tmp = sb + 3 * b_i;
-    size_t tmp = b_sort - 3 * b_i;
-    hipLaunchKernelGGL(k_ds_insert<true>, dim3(nb), dim3(256), 0, c->stream, n, d_in, mode == 1 ? d_var : nullptr, voxel_size, tab, cap - 1, d_slot);
-    hipLaunchKernelGGL(k_iota, dim3(nb), dim3(256), 0, c->stream, d_idx, n);
-    HIPCHK(c, sort_pairs_u32(d_tmp, tmp, (const unsigned int *)d_slot, d_skey, d_idx, d_sidx, (size_t)n, key_bits, c->stream));
-    hipLaunchKernelGGL(k_ds_segstart, dim3(nb), dim3(256), 0, c->stream, n, d_skey, tab);
-    hipLaunchKernelGGL(k_ds_sum_det, dim3(nb), dim3(256), 0, c->stream, n, d_in, mode == 1 ? d_var : nullptr, d_sidx, tab, d_slot);
-  } else {
-    hipLaunchKernelGGL(k_ds_insert<false>, dim3(nb), dim3(256), 0, c->stream, n, d_in, mode == 1 ? d_var : nullptr, voxel_size, tab, cap - 1, d_slot);
+    w.skey = (unsigned int *)sb; w.idx = (int *)(sb + b_i); w.sidx = (int *)(sb + 2 * b_i);
+    w.tmp = sb + 3 * b_i; w.tmp_bytes = b_sort - 3 * b_i;
   }
-  if (mode == 2) {
-    hipLaunchKernelGGL(k_ds_close_min, dim3(nb), dim3(256), 0, c->stream, n, d_in, tab, d_slot, d_dist);
-    hipLaunchKernelGGL(k_ds_close_arg, dim3(nb), dim3(256), 0, c->stream, n, tab, d_slot, d_dist);
-  }
-  hipLaunchKernelGGL(k_ds_count, dim3(nb), dim3(256), 0, c->stream, n, tab, d_slot, d_blk);
-  hipLaunchKernelGGL(k_ds_scan, dim3(1), dim3(256), 0, c->stream, nb, d_blk, d_n);
+  st = ds_core(c, c->stream, mode, n, d_in, mode == 1 ? d_var : nullptr, 9, 4, voxel_size, det, w);
+  if (st) return st;
   hipLaunchKernelGGL(k_ds_emit, dim3(nb), dim3(256), 0, c->stream, n, tab, d_slot, d_blk, d_out, d_cnt, d_first, d_vout, mode);
   span_end(c, "downsample", sp);
   HIPCHK(c, hipGetLastError());
@@ -3254,10 +3274,20 @@ int vba_btc_gen_allocations(vba_btc_db *db, int *count, int64_t *bytes) {
   return VBA_OK;
 }
 
-int vba_btc_generate_stds(vba_btc_db *db, int n, const float *xyz, int id, int cap, double *rows, uint64_t *bits, int *n_stds) {
-  if (!db || n < 0 || n > (1 << 28) || (n > 0 && !xyz) || !n_stds || cap < 0 || (cap > 0 && (!rows || !bits))) return VBA_ERR_BAD_ARG;
+// the argument checks of vba_btc_generate_stds that do not concern the cloud itself (no side effect)
+static int btc_generate_check(vba_btc_db *db, int n, int cap, double *rows, uint64_t *bits, int *n_stds) {
+  if (!db || n < 0 || n > (1 << 28) || !n_stds || cap < 0 || (cap > 0 && (!rows || !bits))) return VBA_ERR_BAD_ARG;
   const vba_btc_gen_config &g = db->gcfg;
   if ((size_t)cap < btc_max_stds(g) || btc_cut_num(g) > db->cfg.occupy_len) return VBA_ERR_BAD_ARG;
+  return VBA_OK;
+}
+// GenerateSTDescs on a cloud from host memory (xyz) or from the device: with xyz == nullptr and n > 0 the caller has sized the
+// generator for n points (btc_gen_ensure) and enqueued, ahead of the database's stream, the writes of float [n][3] into its point
+// buffer db->gen->xyz; the generator only reads that buffer, so a second attempt after a buffer grew finds it intact
+static int btc_generate_impl(vba_btc_db *db, int n, const float *xyz, int id, int cap, double *rows, uint64_t *bits, int *n_stds) {
+  int chk = btc_generate_check(db, n, cap, rows, bits, n_stds);
+  if (chk) return chk;
+  const vba_btc_gen_config &g = db->gcfg;
   vba_ctx *c = db->ctx;
   HIPCHK(c, hipSetDevice(c->device));
   *n_stds = 0;
@@ -3328,6 +3358,11 @@ int vba_btc_generate_stds(vba_btc_db *db, int n, const float *xyz, int id, int c
   }
   *n_stds = ns;
   return VBA_OK;
+}
+
+int vba_btc_generate_stds(vba_btc_db *db, int n, const float *xyz, int id, int cap, double *rows, uint64_t *bits, int *n_stds) {
+  if (n > 0 && !xyz) return VBA_ERR_BAD_ARG;
+  return btc_generate_impl(db, n, xyz, id, cap, rows, bits, n_stds);
 }
 
 int vba_btc_plane_cloud(vba_btc_db *db, int frame, int cap, float *xyz_normal, int *n) {
@@ -3783,6 +3818,426 @@ int vba_debug_solve(vba_ctx *c, int kind, int W, int flags, const double *H, con
   HIPCHK(c, hipMemcpyAsync(dx, d_dx, (size_t)ncand * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int b = 0; b < ncand; b++) q1[b] = h->q1_spec[b];
+  return VBA_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ keyframe store (vba_kf_*)
+#include "vba_kernels_kf.hpp"
+
+struct vba_kf_store {
+  vba_ctx *ctx = nullptr;
+  // the keyframes: points (their own frame, float values in doubles) and covariance diagonals, ragged by off
+  double *d_pnt = nullptr; float *d_var = nullptr; size_t cap = 0;
+  std::vector<int> off{0};
+  struct Meta { double x0[12]; int id; double jour; int exist; };
+  std::vector<Meta> kf;
+  // scratch of one merge of up to mcap points: staged host input, merged cloud (also the world points of a load), gathered covariance
+  // diagonals, per-voxel counts, the down-sampler's work area; pinned: gathered diagonals of a host covariance array
+  size_t mcap = 0;
+  double *d_src = nullptr, *d_merge = nullptr, *d_mdiag = nullptr, *h_diag = nullptr;
+  int *d_cnt = nullptr; char *d_ws = nullptr; size_t ws_bytes = 0;
+  // per-scan transforms [tcap][12] and offsets [tcap + 1]: pinned image and device copy; the voxel count of a build (pinned)
+  int tcap = 0; char *h_tab = nullptr, *d_tab = nullptr; int *h_n = nullptr;
+  hipEvent_t ev = nullptr;
+  int allocs = 0; int64_t bytes = 0;
+  int hist = 0; std::vector<float> hist_pos;   // history_kfsize, pl_kdmap
+  int last_m = 0;                              // voxels of the last build (their counts stay in d_cnt)
+};
+
+namespace {
+
+size_t kf_tab_bytes(int t) { return (size_t)t * 12 * sizeof(double) + (((size_t)t + 1) * sizeof(int) + 15 & ~(size_t)15); }
+
+template <class T>
+int kf_alloc(vba_kf_store *s, T **p, size_t n) {
+  vba_ctx *c = s->ctx;
+  if (*p) hipFree(*p);
+  *p = nullptr;
+  HIPCHK(c, hipMalloc((void **)p, (n ? n : 1) * sizeof(T)));
+  s->allocs++; s->bytes += (int64_t)(n * sizeof(T));
+  return VBA_OK;
+}
+
+// layout of the down-sampler's work area for n points
+size_t kf_ws_layout(vba_ctx *c, int n, bool det, char *base, DsWork *w, int *status) {
+  int cap = 1024;
+  while (cap < 2 * n) cap <<= 1;
+  unsigned int key_bits = 1;
+  while ((1u << key_bits) < (unsigned)cap) key_bits++;
+  const int nb = (n + 255) / 256;
+  const size_t b_i = (((size_t)n * sizeof(int)) + 255) & ~(size_t)255, b_tab = (size_t)cap * sizeof(DsSlot),
+               b_blk = (((size_t)nb + 2) * sizeof(int) + 255) & ~(size_t)255;
+  size_t tmp = 0;
+  if (det && sort_pairs_u32(nullptr, tmp, nullptr, nullptr, nullptr, nullptr, (size_t)n, key_bits, c->stream) != hipSuccess) { *status = VBA_ERR_HIP; return 0; }
+  tmp = (tmp + 255) & ~(size_t)255;
+  if (w) {
+    w->tab = (DsSlot *)base; w->cap = cap; w->key_bits = key_bits;
+    w->slot = (int *)(base + b_tab); w->blk = (int *)(base + b_tab + b_i); w->n_out = w->blk + nb;
+    if (det) {
+      char *sb = base + b_tab + b_i + b_blk;
+      w->skey = (unsigned int *)sb; w->idx = (int *)(sb + b_i); w->sidx = (int *)(sb + 2 * b_i); w->tmp = sb + 3 * b_i; w->tmp_bytes = tmp;
+    }
+  }
+  *status = VBA_OK;
+  return b_tab + b_i + b_blk + (det ? 3 * b_i + tmp : 0);
+}
+
+// grow-only: the keyframe arrays move (device-to-device copy, the old blocks are freed after a synchronise)
+int kf_ensure_rows(vba_kf_store *s, size_t need) {
+  if (need <= s->cap) return VBA_OK;
+  vba_ctx *c = s->ctx;
+  size_t m = s->cap ? s->cap : 65536;
+  while (m < need) m *= 2;
+  double *np = nullptr; float *nv = nullptr;
+  HIPCHK(c, hipMalloc((void **)&np, m * 3 * sizeof(double)));
+  if (hipMalloc((void **)&nv, m * 3 * sizeof(float)) != hipSuccess) { hipFree(np); c->set_error("keyframe store: out of device memory"); return VBA_ERR_HIP; }
+  const size_t have = (size_t)s->off.back();
+  if (have) {
+    HIPCHK(c, hipMemcpyAsync(np, s->d_pnt, have * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(nv, s->d_var, have * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (s->d_pnt) hipFree(s->d_pnt);
+  if (s->d_var) hipFree(s->d_var);
+  s->d_pnt = np; s->d_var = nv; s->cap = m;
+  s->allocs += 2; s->bytes += (int64_t)(m * 3 * (sizeof(double) + sizeof(float)));
+  return VBA_OK;
+}
+
+int kf_ensure_merge(vba_kf_store *s, size_t need) {
+  if (need <= s->mcap) return VBA_OK;
+  vba_ctx *c = s->ctx;
+  size_t m = s->mcap ? s->mcap : 65536;
+  while (m < need) m *= 2;
+  if (m > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  int st = VBA_OK;
+  const size_t ws = kf_ws_layout(c, (int)m, true, nullptr, nullptr, &st);
+  if (st) return st;
+  if ((st = kf_alloc(s, &s->d_src, 3 * m)) || (st = kf_alloc(s, &s->d_merge, 3 * m)) || (st = kf_alloc(s, &s->d_mdiag, 3 * m)) ||
+      (st = kf_alloc(s, &s->d_cnt, m)) || (st = kf_alloc(s, &s->d_ws, ws)))
+    return st;
+  if (s->h_diag) hipHostFree(s->h_diag);
+  s->h_diag = nullptr;
+  HIPCHK(c, hipHostMalloc((void **)&s->h_diag, 3 * m * sizeof(double), hipHostMallocDefault));
+  s->allocs++;
+  s->ws_bytes = ws; s->mcap = m;
+  return VBA_OK;
+}
+
+int kf_ensure_tab(vba_kf_store *s, int k) {
+  if (k <= s->tcap) return VBA_OK;
+  vba_ctx *c = s->ctx;
+  int t = s->tcap ? s->tcap : 64;
+  while (t < k) t *= 2;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (s->h_tab) hipHostFree(s->h_tab);
+  s->h_tab = nullptr;
+  HIPCHK(c, hipHostMalloc((void **)&s->h_tab, kf_tab_bytes(t), hipHostMallocDefault));
+  s->allocs++;
+  int st = kf_alloc(s, &s->d_tab, kf_tab_bytes(t));
+  if (st) return st;
+  s->tcap = t;
+  return VBA_OK;
+}
+
+// Host half of the merge (include/voxelba.h, "order of operations"): T = [dR, dp] of a cloud at pose x into the frame of pose xc
+void kf_delta(const double *xc, const double *x, double *T) {
+  volatile double a, b, e;     // every product and sum rounded on its own, whatever the host compiler would contract
+  for (int r = 0; r < 3; r++)
+    for (int cc = 0; cc < 3; cc++) {
+      a = xc[0 * 3 + r] * x[0 * 3 + cc]; b = xc[1 * 3 + r] * x[1 * 3 + cc]; a = a + b; e = xc[2 * 3 + r] * x[2 * 3 + cc];
+      T[3 * r + cc] = a + e;
+    }
+  const double d0 = x[9] - xc[9], d1 = x[10] - xc[10], d2 = x[11] - xc[11];
+  for (int r = 0; r < 3; r++) {
+    a = xc[0 * 3 + r] * d0; b = xc[1 * 3 + r] * d1; a = a + b; e = xc[2 * 3 + r] * d2;
+    T[9 + r] = a + e;
+  }
+}
+
+// the transform table of k clouds with poses [k][12] (xc = the last) and row offsets rel [k + 1] -> pinned image -> device, on st
+int kf_upload_tab(vba_kf_store *s, int k, const double *const *poses, const int *rel, hipStream_t st) {
+  vba_ctx *c = s->ctx;
+  double *T = (double *)s->h_tab;
+  int *o = (int *)(s->h_tab + (size_t)s->tcap * 12 * sizeof(double));
+  for (int i = 0; i < k; i++) kf_delta(poses[k - 1], poses[i], T + 12 * i);
+  for (int i = 0; i <= k; i++) o[i] = rel[i];
+  HIPCHK(c, hipMemcpyAsync(s->d_tab, s->h_tab, kf_tab_bytes(s->tcap), hipMemcpyHostToDevice, st));
+  return VBA_OK;
+}
+const double *kf_dev_xf(const vba_kf_store *s) { return (const double *)s->d_tab; }
+const int *kf_dev_off(const vba_kf_store *s) { return (const int *)(s->d_tab + (size_t)s->tcap * 12 * sizeof(double)); }
+
+bool kf_pose_ok(const double *p) { for (int i = 0; i < 12; i++) if (!std::isfinite(p[i])) return false; return true; }
+
+}  // namespace
+
+extern "C" {
+
+int vba_kf_create(vba_ctx *c, vba_kf_store **out) {
+  if (!c || !out) return VBA_ERR_BAD_ARG;
+  *out = nullptr;
+  HIPCHK(c, hipSetDevice(c->device));
+  vba_kf_store *s = new vba_kf_store();
+  s->ctx = c;
+  int st = kf_ensure_tab(s, 64);
+  if (!st && hipHostMalloc((void **)&s->h_n, 64, hipHostMallocDefault) != hipSuccess) st = VBA_ERR_HIP;
+  if (!st && hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) st = VBA_ERR_HIP;
+  if (st) { vba_kf_destroy(s); return st; }
+  s->allocs++;
+  *out = s;
+  return VBA_OK;
+}
+
+void vba_kf_destroy(vba_kf_store *s) {
+  if (!s) return;
+  hipSetDevice(s->ctx->device);
+  hipStreamSynchronize(s->ctx->stream);
+  void *d[] = {s->d_pnt, s->d_var, s->d_src, s->d_merge, s->d_mdiag, s->d_cnt, s->d_ws, s->d_tab};
+  for (void *p : d) if (p) hipFree(p);
+  if (s->h_diag) hipHostFree(s->h_diag);
+  if (s->h_tab) hipHostFree(s->h_tab);
+  if (s->h_n) hipHostFree(s->h_n);
+  if (s->ev) hipEventDestroy(s->ev);
+  delete s;
+}
+
+int vba_kf_reserve(vba_kf_store *s, int64_t points, int keyframes, int64_t merge_points) {
+  if (!s || points < 0 || keyframes < 0 || merge_points < 0 || points > ((int64_t)1 << 30) || merge_points > ((int64_t)1 << 28) || keyframes > (1 << 24))
+    return VBA_ERR_BAD_ARG;
+  vba_ctx *c = s->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  int st;
+  if (merge_points > 0 && (st = kf_ensure_merge(s, (size_t)merge_points))) return st;
+  // a build writes its kept cloud straight behind the last keyframe, and that cloud is bounded only by the merged one
+  if (points + merge_points > 0 && (st = kf_ensure_rows(s, (size_t)(points + merge_points)))) return st;
+  s->off.reserve((size_t)keyframes + 1); s->kf.reserve((size_t)keyframes); s->hist_pos.reserve(3 * (size_t)keyframes);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VBA_OK;
+}
+
+int vba_kf_allocations(vba_kf_store *s, int *count, int64_t *bytes) {
+  if (!s || !count || !bytes) return VBA_ERR_BAD_ARG;
+  *count = s->allocs; *bytes = s->bytes;
+  return VBA_OK;
+}
+
+int vba_kf_size(vba_kf_store *s) { return s ? (int)s->kf.size() : 0; }
+
+int vba_kf_build(vba_kf_store *s, int k, const int *offsets, const double *pnt, const double *var, const double *poses, double voxel_size, int id,
+                 double jour, vba_btc_db *db, int cap, double *rows, uint64_t *bits, int *n_stds, int *n_points) {
+  if (!s || k < 1 || !offsets || !poses || !n_points || !(voxel_size > 0) || (!var && voxel_size < 0.001)) return VBA_ERR_BAD_ARG;
+  for (int i = 0; i < k; i++) if (offsets[i] < 0 || offsets[i + 1] < offsets[i]) return VBA_ERR_BAD_ARG;
+  const int off0 = offsets[0], n = offsets[k] - off0;
+  if (n > (1 << 28) || (n > 0 && !pnt)) return VBA_ERR_BAD_ARG;
+  for (int i = 0; i < k; i++) if (!kf_pose_ok(poses + 12 * i)) return VBA_ERR_BAD_ARG;
+  vba_ctx *c = s->ctx;
+  const size_t N = (size_t)s->off.back();
+  if (N + (size_t)n > (size_t)INT32_MAX) return VBA_ERR_CAPACITY;
+  int st;
+  if (db) {
+    if (db->ctx->device != c->device) return VBA_ERR_BAD_ARG;
+    if ((st = btc_generate_check(db, n, cap, rows, bits, n_stds))) return st;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((st = kf_ensure_tab(s, k)) || (st = kf_ensure_merge(s, (size_t)n)) || (st = kf_ensure_rows(s, N + (size_t)n))) return st;
+  if (db && n > 0 && (st = btc_gen_ensure(db, n, 0, 0))) return st;
+  int m = 0;
+  if (n > 0) {
+    std::vector<const double *> pp(k);
+    std::vector<int> rel(k + 1);
+    for (int i = 0; i < k; i++) pp[i] = poses + 12 * i;
+    for (int i = 0; i <= k; i++) rel[i] = offsets[i] - off0;
+    if ((st = kf_upload_tab(s, k, pp.data(), rel.data(), c->stream))) return st;
+    const double *src = pnt + 3 * (size_t)off0, *dvar = nullptr;
+    if (!is_device_ptr(pnt)) {
+      HIPCHK(c, hipMemcpyAsync(s->d_src, src, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+      src = s->d_src;
+    }
+    if (var) {
+      if (is_device_ptr(var)) dvar = var + 9 * (size_t)off0;      // gathered by the merge kernel, 72 bytes apart
+      else {                                                       // host array: only the three diagonal doubles per point cross
+        const double *v = var + 9 * (size_t)off0;
+        for (size_t i = 0; i < (size_t)n; i++) { s->h_diag[3 * i] = v[9 * i]; s->h_diag[3 * i + 1] = v[9 * i + 4]; s->h_diag[3 * i + 2] = v[9 * i + 8]; }
+        HIPCHK(c, hipMemcpyAsync(s->d_mdiag, s->h_diag, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+      }
+    }
+    const int nb = (n + 255) / 256;
+    hipLaunchKernelGGL(k_kf_merge, dim3(nb), dim3(256), 0, c->stream, n, k, kf_dev_off(s), kf_dev_xf(s), src, dvar, 9, 4, s->d_merge,
+                       db ? db->gen->xyz : (float *)nullptr, dvar ? s->d_mdiag : (double *)nullptr);
+    if (db && db->ctx->stream != c->stream) {                      // the generator runs on its database's stream, behind the merge
+      HIPCHK(c, hipEventRecord(s->ev, c->stream));
+      HIPCHK(c, hipStreamWaitEvent(db->ctx->stream, s->ev, 0));
+    }
+    const bool det = c->opt.deterministic != 0;
+    DsWork w{};
+    kf_ws_layout(c, n, det, s->d_ws, &w, &st);
+    if (st) return st;
+    TimedSpan sp{};
+    span_begin(c, "downsample", sp);
+    if ((st = ds_core(c, c->stream, var ? 1 : 0, n, s->d_merge, var ? s->d_mdiag : nullptr, 3, 1, voxel_size, det, w))) return st;
+    hipLaunchKernelGGL(k_kf_emit, dim3(nb), dim3(256), 0, c->stream, n, w.tab, w.slot, w.blk, s->d_pnt + 3 * N, s->d_var + 3 * N, s->d_cnt, var ? 1 : 0);
+    span_end(c, "downsample", sp);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(s->h_n, w.n_out, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (db) {
+    st = btc_generate_impl(db, n, nullptr, id, cap, rows, bits, n_stds);
+    if (st) { hipStreamSynchronize(c->stream); return st; }
+  }
+  if (n > 0) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    m = s->h_n[0];
+  }
+  // commit
+  vba_kf_store::Meta me{};
+  std::memcpy(me.x0, poses + 12 * (size_t)(k - 1), 12 * sizeof(double));
+  me.id = id; me.jour = jour; me.exist = 0;
+  s->kf.push_back(me);
+  s->off.push_back((int)(N + (size_t)m));
+  s->last_m = m;
+  *n_points = m;
+  return VBA_OK;
+}
+
+int vba_kf_last_counts(vba_kf_store *s, int cap, int *counts, int *n) {
+  if (!s || !n || cap < 0 || (cap > 0 && !counts)) return VBA_ERR_BAD_ARG;
+  vba_ctx *c = s->ctx;
+  *n = s->last_m;
+  const int w = s->last_m < cap ? s->last_m : cap;
+  if (w > 0) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(counts, s->d_cnt, (size_t)w * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return VBA_OK;
+}
+
+int vba_kf_generate_stds(vba_kf_store *s, int first, int count, vba_btc_db *db, int cap, double *rows, uint64_t *bits, int *n_stds) {
+  if (!s || !db || first < 0 || count < 1 || (size_t)first + (size_t)count > s->kf.size()) return VBA_ERR_BAD_ARG;
+  vba_ctx *c = s->ctx;
+  if (db->ctx->device != c->device) return VBA_ERR_BAD_ARG;
+  const int b = s->off[first], n = s->off[first + count] - b;
+  int st;
+  if ((st = btc_generate_check(db, n, cap, rows, bits, n_stds))) return st;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((st = kf_ensure_tab(s, count))) return st;
+  const int id = s->kf[first + count - 1].id;
+  if (n > 0) {
+    if ((st = btc_gen_ensure(db, n, 0, 0))) return st;
+    std::vector<const double *> pp(count);
+    std::vector<int> rel(count + 1);
+    for (int i = 0; i < count; i++) pp[i] = s->kf[first + i].x0;
+    for (int i = 0; i <= count; i++) rel[i] = s->off[first + i] - b;
+    hipStream_t q = db->ctx->stream;                               // the store is quiescent between calls: everything on the database's stream
+    if ((st = kf_upload_tab(s, count, pp.data(), rel.data(), q))) return st;
+    hipLaunchKernelGGL(k_kf_merge, dim3((n + 255) / 256), dim3(256), 0, q, n, count, kf_dev_off(s), kf_dev_xf(s), s->d_pnt + 3 * (size_t)b,
+                       (const double *)nullptr, 9, 4, (double *)nullptr, db->gen->xyz, (double *)nullptr);
+    HIPCHK(c, hipGetLastError());
+  }
+  st = btc_generate_impl(db, n, nullptr, id, cap, rows, bits, n_stds);
+  if (st) hipStreamSynchronize(db->ctx->stream);
+  return st;
+}
+
+int vba_kf_set_poses(vba_kf_store *s, int first, int n, const double *poses) {
+  if (!s || first < 0 || n < 0 || (size_t)first + (size_t)n > s->kf.size() || (n > 0 && !poses)) return VBA_ERR_BAD_ARG;
+  for (int i = 0; i < n; i++) if (!kf_pose_ok(poses + 12 * i)) return VBA_ERR_BAD_ARG;
+  for (int i = 0; i < n; i++) std::memcpy(s->kf[first + i].x0, poses + 12 * (size_t)i, 12 * sizeof(double));
+  return VBA_OK;
+}
+
+int vba_kf_get(vba_kf_store *s, int k, double *pose12, int *id, double *jour, int *exist, int *n_points) {
+  if (!s || k < 0 || (size_t)k >= s->kf.size()) return VBA_ERR_BAD_ARG;
+  const vba_kf_store::Meta &m = s->kf[k];
+  if (pose12) std::memcpy(pose12, m.x0, 12 * sizeof(double));
+  if (id) *id = m.id;
+  if (jour) *jour = m.jour;
+  if (exist) *exist = m.exist;
+  if (n_points) *n_points = s->off[k + 1] - s->off[k];
+  return VBA_OK;
+}
+
+int vba_kf_set_history(vba_kf_store *s, int n_hist) {
+  if (!s || n_hist < 0 || (size_t)n_hist > s->kf.size()) return VBA_ERR_BAD_ARG;
+  s->hist_pos.resize(3 * (size_t)n_hist);
+  for (size_t i = 0; i < s->kf.size(); i++) {
+    s->kf[i].exist = (int)i < n_hist ? 1 : 0;
+    if ((int)i < n_hist) for (int j = 0; j < 3; j++) s->hist_pos[3 * i + j] = (float)s->kf[i].x0[9 + j];
+  }
+  s->hist = n_hist;
+  return VBA_OK;
+}
+
+int vba_kf_history_size(vba_kf_store *s) { return s ? s->hist : 0; }
+
+int vba_kf_load(vba_kf_store *s, int k, vba_ctx *mc, double jour) {
+  if (!s || !mc || k < 0 || (size_t)k >= s->kf.size()) return VBA_ERR_BAD_ARG;
+  vba_ctx *c = s->ctx;
+  if (mc->device != c->device) return VBA_ERR_BAD_ARG;
+  const int b = s->off[k], n = s->off[k + 1] - b;
+  if (n > 0) {
+    HIPCHK(c, hipSetDevice(c->device));
+    int st;
+    if ((st = kf_ensure_merge(s, (size_t)n))) return st;
+    // the keyframe's x0 goes through the pinned table; the world points into the merge scratch, on the map context's stream
+    std::memcpy(s->h_tab, s->kf[k].x0, 12 * sizeof(double));
+    HIPCHK(mc, hipMemcpyAsync(s->d_tab, s->h_tab, 12 * sizeof(double), hipMemcpyHostToDevice, mc->stream));
+    hipLaunchKernelGGL(k_kf_world, dim3((n + 255) / 256), dim3(256), 0, mc->stream, n, (const double *)s->d_tab, s->d_pnt + 3 * (size_t)b, s->d_merge);
+    HIPCHK(mc, hipGetLastError());
+    st = map_cut_voxel_fix(mc->map, mc->stream, n, s->d_merge, jour, mc->err);   // ends with the map's counter read-back: one synchronise
+    if (st) { hipStreamSynchronize(mc->stream); return st; }
+  }
+  s->kf[k].exist = 0;
+  return VBA_OK;
+}
+
+int vba_kf_load_nearby(vba_kf_store *s, vba_ctx *mc, const double *p3, double radius, double jour, int *loaded) {
+  if (!s || !mc || !p3 || !loaded || !(radius >= 0)) return VBA_ERR_BAD_ARG;
+  *loaded = -1;
+  if (s->hist <= 0) return VBA_OK;                                   // VS:1382
+  const float q[3] = {(float)p3[0], (float)p3[1], (float)p3[2]};
+  const float r2 = (float)(radius * radius);
+  std::vector<std::pair<float, int>> hit;
+  const int nh = (int)(s->hist_pos.size() / 3);
+  for (int i = 0; i < nh; i++) {
+    volatile float d2 = 0.0f, t;                                     // x, then y, then z, each product and sum rounded to float
+    for (int j = 0; j < 3; j++) { t = s->hist_pos[3 * (size_t)i + j] - q[j]; t = t * t; d2 = d2 + t; }
+    if (d2 < r2) hit.emplace_back((float)d2, i);
+  }
+  std::sort(hit.begin(), hit.end());                                 // ascending distance, the lower index on a tie
+  for (const auto &h : hit) {
+    if (!s->kf[h.second].exist) continue;
+    const int st = vba_kf_load(s, h.second, mc, jour);
+    if (st) return st;
+    s->hist--;
+    *loaded = h.second;
+    break;
+  }
+  return VBA_OK;
+}
+
+int vba_kf_read(vba_kf_store *s, int k, int cap, double *xyz, float *vardiag, int *n) {
+  if (!s || !n || k < 0 || (size_t)k >= s->kf.size() || cap < 0) return VBA_ERR_BAD_ARG;
+  vba_ctx *c = s->ctx;
+  const int b = s->off[k], m = s->off[k + 1] - b;
+  *n = m;
+  const int w = m < cap ? m : cap;
+  if (w > 0 && (xyz || vardiag)) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (xyz) HIPCHK(c, hipMemcpyAsync(xyz, s->d_pnt + 3 * (size_t)b, (size_t)w * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (vardiag) HIPCHK(c, hipMemcpyAsync(vardiag, s->d_var + 3 * (size_t)b, (size_t)w * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return VBA_OK;
+}
+
+int vba_kf_clouds(vba_kf_store *s, const double **d_pnt, const int **offsets, int *n_kf) {
+  if (!s || !d_pnt || !offsets || !n_kf) return VBA_ERR_BAD_ARG;
+  *d_pnt = s->d_pnt; *offsets = s->off.data(); *n_kf = (int)s->kf.size();
   return VBA_OK;
 }
 

@@ -537,3 +537,35 @@ def make_btc_keyframe_sessions(n_sessions=2, n_kf=20, n_points=200000, radius=20
             ses["cloud"].append(loc.astype(np.float32)); ses["R"].append(R); ses["t"].append(t)
         out.append(ses)
     return out
+
+
+def make_keyframe_path(n_kf=30, scans_per_kf=10, n_pts=20000, scan_step=None, seed=SEED_BASE + 60, with_var=True):
+    """Keyframe windows for the keyframe store (vba_kf_*): n_kf * scans_per_kf spinning-sensor scans of the partitioned 40 x 30 x 6
+    hall on a curved trajectory (an ellipse of 6 m x 4 m around the hall's centre with a little roll, pitch and height change;
+    scan_step = the angle between scans, default: 300 degrees over the whole path).  Returns a list of keyframes, each a dict of
+    points = [k arrays (n_i, 3), body frame], vars = [k arrays (n_i, 9)] from calc_body_var (None without with_var) and
+    poses [k][12]."""
+    wl = dataclasses.replace(CONFIGS["hesai200k_w10"], name="kf_path", n_pts=n_pts, win_size=scans_per_kf, seed=seed)
+    rng = np.random.default_rng(seed)
+    planes = scene_planes(wl)
+    total = n_kf * scans_per_kf
+    if scan_step is None:
+        scan_step = math.radians(300.0) / max(total - 1, 1)
+    out = []
+    for k in range(n_kf):
+        pts_k, var_k, poses = [], [], np.empty((scans_per_kf, 12))
+        for i in range(scans_per_kf):
+            a = scan_step * (k * scans_per_kf + i)
+            p = np.array([6.0 * math.cos(a), 4.0 * math.sin(a), 1.5 + 0.2 * math.sin(3.0 * a)])
+            R = rot_z(a + math.pi / 2) @ so3_exp(np.array([0.03 * math.sin(2.0 * a), 0.02 * math.cos(3.0 * a), 0.0]))
+            d_b = scan_dirs(wl, rng)
+            t = ray_cast(p, d_b @ R.T, planes)
+            ok = np.isfinite(t) & (t > 0.3) & (t < 80.0)
+            t = t + rng.normal(0.0, wl.range_noise, t.shape[0])
+            pts = np.ascontiguousarray(d_b[ok] * t[ok, None])
+            pts_k.append(pts)
+            if with_var:
+                var_k.append(np.ascontiguousarray(calc_body_var(pts, wl.dept_err, wl.beam_err).reshape(-1, 9)))
+            poses[i, :9] = R.ravel(); poses[i, 9:] = p
+        out.append(dict(points=pts_k, vars=var_k if with_var else None, poses=poses))
+    return out
