@@ -672,6 +672,70 @@ int vba_kf_read(vba_kf_store *s, int k, int cap, double *xyz, float *vardiag, in
  * offsets[f].  The pointers are valid until the next call that may grow the store (see "Growth and locking"). */
 int vba_kf_clouds(vba_kf_store *s, const double **d_pnt, const int **offsets, int *n_kf);
 
+/* ------------------------------------------------------------------------------------------------
+ * Loop-closure map: the counterpart of `map_loop` (VS:2601-2625) and loop_update() (VS:1255-1373), the step that
+ * carries a loop closure back into local mapping.  A vba_loop_map owns one second voxel map, created from its context's options
+ * and working on that context's stream; like the keyframe store it may hang off the loop-closure thread's context.
+ *
+ * Both halves are fixed-point insertions of clouds that are in HBM already.  Fixed-point cut_voxel (VM:2108-2152) is a per-point
+ * loop whose only per-call state is jour, so the reference's sequence of calls at jour = 0 is ONE insertion of the concatenated
+ * clouds; the device runs it as one, with one counter read-back.  Unlike vba_map_cut_voxel_fix these insertions carry the points'
+ * covariances into point_fix (push_fix_novar stores pv whole, VM:1168; push_fix adds Bf_var(pv) to cov_add at the first recut,
+ * VM:1149-1162): the keyframes' normal_x/y/z as a diagonal (VS:2620-2621), the buf_lba2loop scans' full 3x3 rows unrotated
+ * (VS:1341-1344).
+ *
+ * Order of operations (part of the interface): pw[r] = ((R[r][0]*x + R[r][1]*y) + R[r][2]*z) + t[r], no product fused with a sum.
+ *
+ * Residency: after vba_loop_map_reserve(fix_points, nodes) no call below allocates for the loop map while one insertion and the
+ * map's fixed-point pool stay within fix_points points and the map within `nodes` octree nodes.  vba_loop_update trades the two
+ * maps: the object then owns the map the context gave up, with that map's allocations (ping-pong); the reservation is applied to
+ * it and both root tables are brought to the larger size, so from the second loop closure on nothing is allocated.
+ * vba_loop_map_allocations: count = calls on this object that allocated (vba_loop_update counts growth of either map), bytes =
+ * what they allocated. */
+typedef struct vba_loop_map vba_loop_map;
+int vba_loop_map_create(vba_ctx *ctx, vba_loop_map **out);
+void vba_loop_map_destroy(vba_loop_map *lm);   /* before its context */
+int vba_loop_map_reserve(vba_loop_map *lm, int64_t fix_points, int64_t nodes);
+int vba_loop_map_allocations(vba_loop_map *lm, int *count, int64_t *bytes);
+/* The block VS:2601-2625.  The loop map is reset; keyframes max(0, size - init_num) .. size - 1 of `store` (same device) are moved
+ * to the world with their CURRENT x0 (the caller has run vba_kf_set_poses) and inserted as fixed points with their covariance
+ * diagonals at jour = 0; their exist flags are cleared (VS:2612).
+ * cumulative = 1 is THE REFERENCE: pvec_tem (VS:2602) is never cleared, so insertion j holds keyframes 0 .. j again; with five
+ * keyframes the oldest goes in five times and the newest once.  cumulative = 0 is the corrected form: every keyframe once.
+ * *n_inserted = points of the expanded sequence.  One gather over the store's arrays, one fixed insertion; the call ends with that
+ * insertion's counter read-back (one synchronise of the loop map's stream), so the map is complete when it returns.  The caller
+ * holds the store's lock (mtx_keyframe) around the call.  An empty store gives an empty map.  On error the loop map is empty. */
+int vba_loop_map_build(vba_loop_map *lm, vba_kf_store *store, int init_num /* 5 */, int cumulative, int *n_inserted);
+/* row formats of vba_map_num_roots / vba_map_dump_leaves / vba_map_dump_plane_var */
+int vba_loop_map_num_roots(vba_loop_map *lm);
+int vba_loop_map_dump_leaves(vba_loop_map *lm, double *out, int max_leaves);
+int vba_loop_map_dump_plane_var(vba_loop_map *lm, double *out, int max_leaves);
+/* loop_update() on the local-mapping context: VS:1262-1277 and VS:1334-1363.  The pose algebra of VS:1296-1331 stays with the caller
+ * (vba::VoxelMap::loop_update in voxelba_adapter.hpp): every pose below is ALREADY moved by dx; dx12 (may be NULL) is only checked
+ * to be finite.
+ *  1. Arguments are checked before any device work: VBA_ERR_BAD_ARG for win_count outside 1..win_size, a loop map whose map
+ *     options (win_size, voxel_size, max_layer, max_points, min_eigen_value, plane thresholds, min_point, thread_num,
+ *     deterministic) differ from ctx's or that lives on another device, bad offsets, non-finite poses; VBA_ERR_UNSUPPORTED when ctx
+ *     is sharded (vba_set_shard with n_ranks > 1): sharded maps are not covered.
+ *  2. ctx adopts the loop map (surf_map = map_loop) with mp[i] = i; lm takes the outgoing map, which stays readable until step 6.
+ *  3. The k buf_lba2loop scans, rows offsets[i] .. offsets[i+1] of pnt [][3] (body frame) and var [][9] (NULL: zeros), HOST or
+ *     DEVICE memory as for vba_kf_build, at poses_bl [k][12]: one fixed insertion with covariances at jour = 0.  k = 0 skips it.
+ *  4. For i < win_count the sliding insert (vba_map_cut_voxel, multi = 0) at frame i with poses_win[i].  win_pnt == NULL: the
+ *     source is the OUTGOING map's own scan ring (the raw body points, the world covariances and the count of frame i exactly as
+ *     they were inserted, including covariances formed on the device by vba_map_pvec_update_cut_voxel): device to device, no point
+ *     crosses the host boundary.  Otherwise rows win_offsets[i] .. win_offsets[i+1] of win_pnt / win_var (NULL: none), host or
+ *     device.
+ *  5. vba_map_recut(ctx, win_count, poses_win, 0) over all roots; *n_factors = its factor count.  The reference's loop (VS:1362-1363)
+ *     does not run tras_opt; filling the factor store here is unobservable, because the next step's multi_recut clears and
+ *     refills it.
+ *  6. The outgoing map is reset and kept by lm with its allocations.
+ * On an error return after step 1 the context's map is the one it had before the call (the maps are traded back; the loop map is
+ * reset and has to be built again), unless vba_last_error says otherwise (only a failure of step 6 leaves the new map in place).
+ * Synchronises as its parts do: once per fixed insertion, once for the recut, plus the reset. */
+int vba_loop_update(vba_ctx *ctx, vba_loop_map *lm, const double *dx12, int k, const int *offsets, const double *pnt, const double *var,
+                    const double *poses_bl, int win_count, const double *win_pnt, const double *win_var, const int *win_offsets,
+                    const double *poses_win, int *n_factors);
+
 #ifdef __cplusplus
 }
 #endif

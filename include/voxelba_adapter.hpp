@@ -180,6 +180,8 @@ class LI_BA_OptimizerGravity {
 struct pointVar { double pnt[3]; double var[9]; };   // VM:18-34
 typedef std::vector<pointVar> PVec;
 
+class LoopMap;
+struct ScanPose;
 class VoxelMap {
  public:
   explicit VoxelMap(Context &ctx) : c_(ctx.get()) {}
@@ -215,6 +217,9 @@ class VoxelMap {
   }
   void slide(int mgsize) { check(c_, vba_map_slide(c_, mgsize)); }   // VS:2014-2019
   void reset() { check(c_, vba_map_reset(c_)); }
+  // loop_update() VS:1255-1373 (defined below, after LoopMap): returns the factor count of the closing recut
+  inline int loop_update(LoopMap &map_loop, const IMUST &dx, std::vector<ScanPose *> &buf_lba2loop, std::vector<IMUST> &x_buf, int win_count,
+                         IMUST &x_curr, int &g_update, const std::vector<const PVec *> *pvec_buf = nullptr);
   size_t size() const { return (size_t)vba_map_num_roots(c_); }
   size_t slide_size() const { return (size_t)vba_map_num_slide_roots(c_); }
  private:
@@ -674,6 +679,115 @@ class KeyframeStore {
   vba_ctx *ctx_ = nullptr;
   vba_kf_store *s_ = nullptr;
 };
+
+// ---- loop closure -> local mapping (voxelba.h "Loop-closure map").  The pose algebra runs here, on the host, one
+// separately rounded product and sum after the other in the order  s = a0*b0; s += a1*b1; s += a2*b2  (compile without contraction
+// to keep it so); the device sees poses that are already moved.
+namespace detail {
+inline void mat3_mul(const double *A, const double *B, double *C) {          // C = A B, may alias neither
+  for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) { double s = A[3 * r] * B[c]; s += A[3 * r + 1] * B[3 + c]; s += A[3 * r + 2] * B[6 + c]; C[3 * r + c] = s; }
+}
+inline void mat3_vec(const double *A, const double *v, double *o) {          // o = A v, may not alias
+  for (int r = 0; r < 3; r++) { double s = A[3 * r] * v[0]; s += A[3 * r + 1] * v[1]; s += A[3 * r + 2] * v[2]; o[r] = s; }
+}
+}  // namespace detail
+
+// VS:2597-2598: dx.R = x3.R x1.R^T, dx.p = x3.p - (x3.R x1.R^T) x1.p, with x1 the pose before and x3 after the optimisation
+inline IMUST loop_dx(const IMUST &x1, const IMUST &x3) {
+  IMUST dx;
+  double Rt[9], q[3];
+  for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) Rt[3 * r + c] = x1.R[3 * c + r];
+  detail::mat3_mul(x3.R, Rt, dx.R);
+  detail::mat3_vec(dx.R, x1.p, q);
+  for (int k = 0; k < 3; k++) dx.p[k] = x3.p[k] - q[k];
+  return dx;
+}
+// x.v = dx.R x.v; x.p = dx.R x.p + dx.p; x.R = dx.R x.R  (LR:29-34, VS:1299-1305)
+inline void apply_dx(IMUST &x, const IMUST &dx) {
+  double v[3], p[3], R[9];
+  detail::mat3_vec(dx.R, x.v, v); detail::mat3_vec(dx.R, x.p, p); detail::mat3_mul(dx.R, x.R, R);
+  for (int k = 0; k < 3; k++) { x.v[k] = v[k]; x.p[k] = p[k] + dx.p[k]; }
+  std::memcpy(x.R, R, 72);
+}
+struct ScanPose {   // LR:17-34
+  IMUST x; std::shared_ptr<PVec> pvec; double v6[6] = {0, 0, 0, 0, 0, 0};
+  ScanPose(const IMUST &x_, std::shared_ptr<PVec> pvec_) : x(x_), pvec(std::move(pvec_)) {}
+  void update(const IMUST &dx) { apply_dx(x, dx); }
+};
+
+// `map_loop` (VS:2601-2625): a second voxel map in HBM.  Destroy it before its Context.
+class LoopMap {
+ public:
+  explicit LoopMap(Context &ctx) : ctx_(ctx.get()) { check(ctx_, vba_loop_map_create(ctx_, &lm_)); }
+  ~LoopMap() { vba_loop_map_destroy(lm_); }
+  LoopMap(const LoopMap &) = delete;
+  LoopMap &operator=(const LoopMap &) = delete;
+  vba_loop_map *get() const { return lm_; }
+  void reserve(int64_t fix_points, int64_t nodes) { check(ctx_, vba_loop_map_reserve(lm_, fix_points, nodes)); }
+  // the block VS:2601-2625 from the store's last init_num keyframes at their current x0 (run KeyframeStore::set_poses first; hold
+  // mtx_keyframe).  cumulative = true is the reference: pvec_tem is never cleared, keyframe 0 goes in init_num times.
+  int build(KeyframeStore &keyframes, int init_num = 5, bool cumulative = true) {
+    int n = 0;
+    check(ctx_, vba_loop_map_build(lm_, keyframes.get(), init_num, cumulative ? 1 : 0, &n));
+    return n;
+  }
+  size_t size() const { return (size_t)vba_loop_map_num_roots(lm_); }
+ private:
+  vba_ctx *ctx_ = nullptr;
+  vba_loop_map *lm_ = nullptr;
+};
+
+// loop_update() on the local-mapping thread (VS:1255-1373) without its publishing code: the host part VS:1296-1331 (the
+// buf_lba2loop poses, the window states with x.g while g_update == 1, x_curr) and VS:1366-1367 (g_update 1 -> 2) here, the map part
+// in ONE call.  pvec_buf == nullptr re-inserts the window from the outgoing map's own scan ring (device to device); otherwise
+// (*pvec_buf)[i] is the scan of frame i.
+inline void loop_update_states(const IMUST &dx, std::vector<ScanPose *> &buf_lba2loop, std::vector<IMUST> &x_buf, int win_count, IMUST &x_curr,
+                               int g_update) {
+  if (win_count < 1 || (size_t)win_count > x_buf.size()) throw std::invalid_argument("loop_update: win_count");
+  for (ScanPose *bl : buf_lba2loop) bl->update(dx);                         // VS:1286-1294
+  for (int i = 0; i < win_count; i++) {                                     // VS:1296-1311
+    apply_dx(x_buf[i], dx);
+    if (g_update == 1) { double g[3]; detail::mat3_vec(dx.R, x_buf[i].g, g); std::memcpy(x_buf[i].g, g, 24); }
+  }
+  double v[3];                                                              // VS:1327-1331
+  detail::mat3_vec(dx.R, x_curr.v, v);
+  std::memcpy(x_curr.R, x_buf[win_count - 1].R, 72); std::memcpy(x_curr.p, x_buf[win_count - 1].p, 24);
+  std::memcpy(x_curr.v, v, 24); std::memcpy(x_curr.g, x_buf[win_count - 1].g, 24);
+}
+inline void loop_update_finish(int &g_update) { if (g_update == 1) g_update = 2; }   // VS:1366-1367
+
+inline int VoxelMap::loop_update(LoopMap &map_loop, const IMUST &dx, std::vector<ScanPose *> &buf_lba2loop, std::vector<IMUST> &x_buf, int win_count,
+                                 IMUST &x_curr, int &g_update, const std::vector<const PVec *> *pvec_buf) {
+  loop_update_states(dx, buf_lba2loop, x_buf, win_count, x_curr, g_update);
+  const int k = (int)buf_lba2loop.size();
+  std::vector<int> off(k + 1, 0);
+  for (int i = 0; i < k; i++) off[i + 1] = off[i] + (int)buf_lba2loop[i]->pvec->size();
+  std::vector<double> pnt((size_t)off[k] * 3), var((size_t)off[k] * 9), poses_bl((size_t)k * 12);
+  for (int i = 0; i < k; i++) {
+    std::memcpy(&poses_bl[(size_t)i * 12], buf_lba2loop[i]->x.R, 72); std::memcpy(&poses_bl[(size_t)i * 12 + 9], buf_lba2loop[i]->x.p, 24);
+    size_t r = (size_t)off[i];
+    for (const pointVar &pv : *buf_lba2loop[i]->pvec) { std::memcpy(&pnt[3 * r], pv.pnt, 24); std::memcpy(&var[9 * r], pv.var, 72); r++; }
+  }
+  std::vector<IMUST> xw(x_buf.begin(), x_buf.begin() + win_count);
+  const std::vector<double> poses_win = LidarFactor::poses_of(xw);
+  std::vector<int> woff;
+  std::vector<double> wp, wv;
+  if (pvec_buf) {
+    woff.assign(win_count + 1, 0);
+    for (int i = 0; i < win_count; i++) woff[i + 1] = woff[i] + (int)(*pvec_buf)[i]->size();
+    wp.resize((size_t)woff[win_count] * 3 + 1); wv.resize((size_t)woff[win_count] * 9 + 1);
+    size_t r = 0;
+    for (int i = 0; i < win_count; i++)
+      for (const pointVar &pv : *(*pvec_buf)[i]) { std::memcpy(&wp[3 * r], pv.pnt, 24); std::memcpy(&wv[9 * r], pv.var, 72); r++; }
+  }
+  double dx12[12];
+  std::memcpy(dx12, dx.R, 72); std::memcpy(dx12 + 9, dx.p, 24);
+  int nf = 0;
+  check(c_, vba_loop_update(c_, map_loop.get(), dx12, k, off.data(), pnt.data(), var.data(), poses_bl.data(), win_count,
+                            pvec_buf ? wp.data() : nullptr, pvec_buf ? wv.data() : nullptr, pvec_buf ? woff.data() : nullptr, poses_win.data(), &nf));
+  loop_update_finish(g_update);
+  return nf;
+}
 
 #ifdef VBA_ADAPTER_HAVE_EIGEN
 // Eigen-typed conveniences so reference call sites keep their argument types (Eigen is column-major: converted here).

@@ -42,6 +42,8 @@ EXPORTS = [
     "vba_kf_create", "vba_kf_destroy", "vba_kf_reserve", "vba_kf_allocations", "vba_kf_size", "vba_kf_build", "vba_kf_last_counts",
     "vba_kf_generate_stds", "vba_kf_set_poses", "vba_kf_get", "vba_kf_set_history", "vba_kf_history_size", "vba_kf_load",
     "vba_kf_load_nearby", "vba_kf_read", "vba_kf_clouds",
+    "vba_loop_map_create", "vba_loop_map_destroy", "vba_loop_map_reserve", "vba_loop_map_allocations", "vba_loop_map_build",
+    "vba_loop_map_num_roots", "vba_loop_map_dump_leaves", "vba_loop_map_dump_plane_var", "vba_loop_update",
 ]
 
 
@@ -363,6 +365,58 @@ class KeyframeStore:
         self.ctx._chk(self.lib.vba_kf_clouds(self.h, C.byref(d), C.byref(o), C.byref(n)))
         off = np.array([o[i] for i in range(n.value + 1)], dtype=np.int32)
         return (d.value or 0), off, n.value
+
+
+class LoopMap:
+    """One vba_loop_map: ``map_loop`` of the loop-closure thread, a second voxel map resident in HBM."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx._chk(self.lib.vba_loop_map_create(ctx.h, C.byref(h)))
+        self.h = h
+        ctx._kf.append(self)         # destroyed with its context, as the stores are
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.vba_loop_map_destroy(self.h)
+            self.h = None
+        kf = getattr(self.ctx, "_kf", None)
+        if kf is not None and self in kf:
+            kf.remove(self)
+
+    def reserve(self, fix_points=0, nodes=0):
+        self.ctx._chk(self.lib.vba_loop_map_reserve(self.h, C.c_int64(fix_points), C.c_int64(nodes)))
+
+    def allocations(self):
+        n = C.c_int(); b = C.c_int64()
+        self.ctx._chk(self.lib.vba_loop_map_allocations(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def build(self, store, init_num=5, cumulative=True):
+        """VS:2601-2625 from the last ``init_num`` keyframes of ``store`` at their current x0 -> points inserted.
+        cumulative=True is the reference (pvec_tem is never cleared), False inserts every keyframe once."""
+        n = C.c_int()
+        self.ctx._chk(self.lib.vba_loop_map_build(self.h, store.h, C.c_int(init_num), C.c_int(int(cumulative)), C.byref(n)))
+        return n.value
+
+    def num_roots(self):
+        return self.lib.vba_loop_map_num_roots(self.h)
+
+    def dump_leaves(self):
+        n = self.lib.vba_loop_map_dump_leaves(self.h, None, C.c_int(0))
+        out = np.zeros((max(n, 0), 39))
+        if n > 0:
+            self.lib.vba_loop_map_dump_leaves(self.h, _p(out), C.c_int(n))
+        return out
+
+    def dump_plane_var(self):
+        n = self.lib.vba_loop_map_dump_plane_var(self.h, None, C.c_int(0))
+        out = np.zeros((max(n, 0), 86))
+        if n > 0:
+            self.lib.vba_loop_map_dump_plane_var(self.h, _p(out), C.c_int(n))
+        return out
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -702,6 +756,35 @@ class Context:
 
     def kf_store(self) -> "KeyframeStore":
         return KeyframeStore(self)
+
+    def loop_map(self) -> "LoopMap":
+        return LoopMap(self)
+
+    def loop_update(self, lm, poses_win, bl_scans=(), bl_poses=None, bl_vars=None, win_scans=None, win_vars=None, dx12=None):
+        """loop_update() (VS:1255-1373) on this context's map: adopt ``lm``, insert the buf_lba2loop scans ``bl_scans`` (list of
+        [n_i][3] body points, ``bl_vars`` the matching [n_i][9] or None) at ``bl_poses`` [k][12] as fixed points with covariances,
+        re-insert the window's scans at ``poses_win`` [win_count][12] (``win_scans`` None: from the outgoing map's own scan ring,
+        device to device) and recut.  Every pose is already moved by dx.  Returns the factor count."""
+        poses_win = _c(poses_win).reshape(-1, 12)
+        k = len(bl_scans)
+        off = pnt = var = bp = None
+        if k:
+            off, pnt = Context._ragged(bl_scans)
+            var = np.ascontiguousarray(np.concatenate([np.reshape(v, (-1, 9)) for v in bl_vars]), dtype=np.float64) if bl_vars is not None else None
+            bp = _c(bl_poses).reshape(k, 12)
+        woff = wp = wv = None
+        if win_scans is not None:
+            if len(win_scans) != len(poses_win):
+                raise ValueError("one pose per window scan")
+            woff, wp = Context._ragged(win_scans)
+            wv = np.ascontiguousarray(np.concatenate([np.reshape(v, (-1, 9)) for v in win_vars]), dtype=np.float64) if win_vars is not None else None
+        ip = C.POINTER(C.c_int)
+        nf = C.c_int()
+        self._chk(self.lib.vba_loop_update(self.h, lm.h, _p(_c(dx12)) if dx12 is not None else None, C.c_int(k),
+                                           off.ctypes.data_as(ip) if off is not None else None, _p(pnt), _p(var), _p(bp),
+                                           C.c_int(len(poses_win)), _p(wp), _p(wv), woff.ctypes.data_as(ip) if woff is not None else None,
+                                           _p(poses_win), C.byref(nf)))
+        return nf.value
 
     def btc_search_loop_sessions(self, dbs, rows, bits, cur_db, cur_frame=-1):
         """SearchLoop of one query against every database (VS:2417-2421): one upload, one synchronisation."""

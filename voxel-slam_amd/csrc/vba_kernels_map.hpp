@@ -756,9 +756,18 @@ __device__ __forceinline__ void fix_chain_append(const MapView &m, int leaf, int
   if (tail < 0) m.nfb_head[leaf] = blk; else m.fb_next[tail] = blk;
   m.nfb_tail[leaf] = blk;
 }
-// one wave per leaf group: push_fix_novar VM:1168-1178 for the group's points in call order; pts = the caller's [n][3] array
-__global__ __launch_bounds__(64) void k_fix_accum_ord(MapView m, MapParams P, int base, int n, const double *__restrict__ pts) {
+// one wave per leaf group: push_fix_novar VM:1168-1178 for the group's points in call order; pts = the caller's [n][3] array.
+// COV: where the covariance of a pool entry comes from (push_fix_novar stores pv WITH its covariance in point_fix; push_fix adds
+// Bf_var(pv) to cov_add when the leaf is first subdivided, VM:1149-1162).  FIXCOV_KEEP: the rows were zeroed by k_fix_to_soa
+// (vba_map_cut_voxel_fix: no covariance argument).  Otherwise the entry's row is written here, in pool (= group) order, from row
+// srcrow[p] of `cov`: float [.][3] diagonals widened to double, double [.][9] rows as they are, or zeros.  The 72-byte rows go out
+// through LDS so that consecutive lanes store consecutive doubles.
+enum { FIXCOV_KEEP = 0, FIXCOV_DIAG_F32 = 1, FIXCOV_FULL_F64 = 2, FIXCOV_ZERO = 3 };
+template <int COV>
+__global__ __launch_bounds__(64) void k_fix_accum_ord(MapView m, MapParams P, int base, int n, const double *__restrict__ pts, const int *__restrict__ srcrow,
+                                                      const void *__restrict__ cov) {
   __shared__ double T[64 * 9];
+  __shared__ double V[COV != FIXCOV_KEEP ? 64 * 9 : 1];
   const int lane = threadIdx.x;
   const int nseg = m.cnt[CNT_WL];
   const size_t cp = (size_t)m.cap, cf = (size_t)m.cap_fix;
@@ -787,9 +796,26 @@ __global__ __launch_bounds__(64) void k_fix_accum_ord(MapView m, MapParams P, in
         m.fnode[q] = store ? leaf : -1;
         double *t = T + lane * 9;
         t[0] = x * x; t[1] = x * y; t[2] = x * z; t[3] = y * y; t[4] = y * z; t[5] = z * z; t[6] = x; t[7] = y; t[8] = z;
+        if (COV != FIXCOV_KEEP) {
+          double *v = V + lane * 9;                  // rows of 9 doubles: conflict-free for the owning lane
+#pragma unroll
+          for (int k = 0; k < 9; k++) v[k] = 0.0;
+          if (COV == FIXCOV_DIAG_F32) {
+            const float *d = (const float *)cov + 3 * (size_t)srcrow[p];
+            v[0] = (double)d[0]; v[4] = (double)d[1]; v[8] = (double)d[2];
+          } else if (COV == FIXCOV_FULL_F64) {
+            const double *d = (const double *)cov + 9 * (size_t)srcrow[p];
+#pragma unroll
+            for (int k = 0; k < 9; k++) v[k] = d[k];
+          }
+        }
       }
       __syncthreads();
       const int cnt = end - c0 < 64 ? end - c0 : 64;
+      if (COV != FIXCOV_KEEP) {
+        double *ov = m.fvar + ((size_t)base + (size_t)c0) * 9;
+        for (int j = lane; j < cnt * 9; j += 64) ov[j] = V[j];
+      }
       if (lane < 18) {
         const int k = lane < 9 ? lane : lane - 9;    // pcr_fix.push(pnt) and pcr_add.push(pnt): the same terms, two chains
         for (int j = 0; j < cnt; j++) acc += T[j * 9 + k];
@@ -2377,7 +2403,7 @@ inline int map_cut_voxel_fix(MapStore &s, hipStream_t st, int n, const double *p
     MAPCHK(sort_pairs_u32(s.d_sort_tmp, tb, s.v.skey_a, s.v.skey_b, s.v.sval_a, s.v.sval_b, (size_t)n, map_key_bits(s), st));
   }
   hipLaunchKernelGGL(k_fix_heads, dim3(nb), dim3(256), 0, st, s.v, n);
-  hipLaunchKernelGGL(k_fix_accum_ord, dim3(n < 4096 ? n : 4096), dim3(64), 0, st, s.v, P, base, n, d_pts);
+  hipLaunchKernelGGL((k_fix_accum_ord<FIXCOV_KEEP>), dim3(n < 4096 ? n : 4096), dim3(64), 0, st, s.v, P, base, n, d_pts, (const int *)nullptr, (const void *)nullptr);
   MAPCHK(hipGetLastError());
   r = map_read_counters(s, st, err);
   if (r) return r;

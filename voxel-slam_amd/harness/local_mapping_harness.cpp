@@ -31,6 +31,15 @@
 //           then [n_loop] rows [m1, m2, id1, id2, rot(9), tra(3)] (noise v6_init = 1e-4), then [n_gba] rows [m1, m2, id1, id2, rot(9),
 //           tra(3), v6(6)] (gba_edges1 + gba_edges2 with scan ids); output: the states of every session after set_state, then the
 //           stats [n_updates][3]
+//   mode 7 (a loop closure carried back into local mapping, VS:2582-2625 + loop_update() VS:1255-1373, through vba::KeyframeStore,
+//           vba::LoopMap and vba::VoxelMap::loop_update): the lidar-only session of mode 0 with [n_loop, kf_every, dx(12)] after the
+//           header.  Every marginalised scan joins buf_lba2loop with its refined pose; every kf_every of them become a keyframe
+//           (KeyframeStore::build at voxel_size / 10).  Before scan n_loop is read: set_poses with the keyframes' x0 moved by dx,
+//           LoopMap::build, loop_update (window from the outgoing map's scan ring), and every later x_curr of the input is moved by
+//           dx.  (The device formed the scans' world covariances when it inserted them; buf_lba2loop keeps the covariances of the
+//           input, which is what both sides of the test use for the marginalised scans.)  The record written at that point:
+//           [-3, points inserted by the build, factor count, n_kf, per keyframe {n, x0(12), xyz[n][3], diag[n][3]},
+//            k, per buf_lba2loop scan {scan index, state(25)}, win_count, per frame {state(25)}]
 //   output: per optimised window [scan index, W x 25 states, v6[6]] ... then [-1, n_leaves] leaf dump [n][39] plane_var dump [n][86]
 #include "../../include/voxelba_adapter.hpp"
 #include <cmath>
@@ -221,6 +230,14 @@ int main(int argc, char **argv) {
   for (int i = 0; i < 4; i++) opt.min_point[i] = next();
   opt.imu_coef = next(); opt.thread_num = (int)next();
   opt.deterministic = det ? 1 : 0;
+  const bool lidar_only = mode == 0 || mode == 7;
+  int n_loop = -1, kf_every = 1;
+  IMUST dx;
+  if (mode == 7) {
+    n_loop = (int)next(); kf_every = (int)next();
+    for (int i = 0; i < 9; i++) dx.R[i] = next();
+    for (int i = 0; i < 3; i++) dx.p[i] = next();
+  }
 
   std::vector<double> out;
   try {
@@ -237,10 +254,19 @@ int main(int argc, char **argv) {
     // the noise globals of preintegration.hpp:8-9 travel at the end of the file
     const double *noise = &in[in.size() - 12];
     double scale_gravity = 1.0;                  // imupre_scale_gravity (PI:9)
+    // mode 7: keyframes, map_loop and the scans marginalised since the last keyframe (buf_lba2loop) with their scan indices
+    std::unique_ptr<KeyframeStore> keyframes;
+    std::unique_ptr<LoopMap> map_loop;
+    std::vector<std::unique_ptr<ScanPose>> buf_lba2loop;
+    std::vector<int> bl_index;
+    std::vector<IMUST> kf_x0;
+    std::vector<int> scan_of_frame;              // scan index of every frame of the window
+    bool moved = false;
+    if (mode == 7) { keyframes.reset(new KeyframeStore(ctx)); map_loop.reset(new LoopMap(ctx)); }
 
     // VS:1951-2043: optimise the full window, then marginalise and slide
     auto window_step = [&](int k) {
-        if (mode == 0) {                                         // lidar-only windows (what HBA_add_edge runs, VS:2895-2899)
+        if (lidar_only) {                                        // lidar-only windows (what HBA_add_edge runs, VS:2895-2899)
           Lidar_BA_Optimizer opt_lsv;
           std::vector<double> resis;
           opt_lsv.damping_iter(x_buf, voxhess, &hess, resis, 3);
@@ -254,8 +280,8 @@ int main(int argc, char **argv) {
           opt_lsv.damping_iter(x_buf, voxhess, imu_pre_buf, &hess);
         }
         // VS:1973-1977: v6 = 1 / |diag(hess.block<6,6>(0, DIM))|
-        const int nh = (mode == 0) ? 6 * win_size : DIM * win_size + ((int)hess.size() == (DIM * win_size + 3) * (DIM * win_size + 3) ? 3 : 0);
-        const int col0 = (mode == 0) ? 6 : DIM;
+        const int nh = lidar_only ? 6 * win_size : DIM * win_size + ((int)hess.size() == (DIM * win_size + 3) * (DIM * win_size + 3) ? 3 : 0);
+        const int col0 = lidar_only ? 6 : DIM;
         double v6[6];
         for (int i = 0; i < 6; i++) v6[i] = 1.0 / std::fabs(hess[(size_t)i * nh + col0 + i]);
         out.push_back((double)k);
@@ -265,6 +291,19 @@ int main(int argc, char **argv) {
         surf_map.multi_margi(jour, win_count, x_buf);            // VS:1991
         jour += 0.1;
         surf_map.slide(mgsize);                                  // mp[] rotation VS:2014-2019
+        if (mode == 7) {                                         // VS:2001-2010: the marginalised scan goes to the loop-closure thread
+          buf_lba2loop.emplace_back(new ScanPose(x_buf[0], pvec_buf[0]));
+          bl_index.push_back(scan_of_frame[0]);
+          scan_of_frame.erase(scan_of_frame.begin());
+          if ((int)buf_lba2loop.size() >= kf_every) {            // VS:2354-2397
+            std::vector<ScanPoseRef> bl_local;
+            for (int i = 0; i < kf_every; i++) bl_local.push_back(ScanPoseRef{&buf_lba2loop[i]->x, buf_lba2loop[i]->pvec.get()});
+            keyframes->build(bl_local, opt.voxel_size / 10, keyframes->size(), jour);
+            kf_x0.push_back(buf_lba2loop[kf_every - 1]->x);
+            buf_lba2loop.erase(buf_lba2loop.begin(), buf_lba2loop.begin() + kf_every);
+            bl_index.erase(bl_index.begin(), bl_index.begin() + kf_every);
+          }
+        }
         for (int i = mgsize; i < win_count; i++) {               // VS:2022-2028
           x_buf[i - mgsize] = x_buf[i];
           std::swap(pvec_buf[i - mgsize], pvec_buf[i]);
@@ -322,9 +361,37 @@ int main(int argc, char **argv) {
     }
 
     for (int k = k_first; k < n_scans; k++) {
+      if (mode == 7 && k == n_loop) {                            // loop_detect == 1 (VS:1768-1773)
+        if (keyframes->size() < 2 || win_count < 1) throw std::runtime_error("mode 7: the session built fewer than two keyframes");
+        for (IMUST &x0 : kf_x0) apply_dx(x0, dx);                // VS:2582-2587 with a synthetic correction
+        keyframes->set_poses(0, kf_x0);
+        const int n_ins = map_loop->build(*keyframes);           // VS:2601-2625
+        std::vector<ScanPose *> bl;
+        for (auto &b : buf_lba2loop) bl.push_back(b.get());
+        IMUST x_now = x_buf[win_count - 1];
+        int g_upd = 0;
+        const int nf = surf_map.loop_update(*map_loop, dx, bl, x_buf, win_count, x_now, g_upd);
+        out.push_back(-3.0); out.push_back(n_ins); out.push_back(nf); out.push_back(keyframes->size());
+        for (int i = 0; i < keyframes->size(); i++) {
+          std::vector<XYZ> xyz, nrm;
+          keyframes->read(i, xyz, &nrm);
+          out.push_back((double)xyz.size());
+          out.insert(out.end(), kf_x0[i].R, kf_x0[i].R + 9); out.insert(out.end(), kf_x0[i].p, kf_x0[i].p + 3);
+          for (const XYZ &a : xyz) { out.push_back(a.x); out.push_back(a.y); out.push_back(a.z); }
+          for (const XYZ &a : nrm) { out.push_back(a.x); out.push_back(a.y); out.push_back(a.z); }
+        }
+        out.push_back((double)bl.size());
+        for (size_t i = 0; i < bl.size(); i++) { out.push_back(bl_index[i]); out.insert(out.end(), &bl[i]->x.t, &bl[i]->x.t + 25); }
+        out.push_back(win_count);
+        for (int i = 0; i < win_count; i++) out.insert(out.end(), &x_buf[i].t, &x_buf[i].t + 25);
+        buf_lba2loop.clear(); bl_index.clear();
+        moved = true;
+      }
       const int n = (int)next();
       IMUST x_curr;
       std::memcpy(&x_curr.t, &in.at(q), 25 * sizeof(double)); q += 25;
+      if (moved) apply_dx(x_curr, dx);
+      scan_of_frame.push_back(k);
       std::memcpy(x_curr.cov, &in.at(q), 225 * sizeof(double)); q += 225;
       const int n_imu = (int)next();
       std::shared_ptr<PVec> pptr(new PVec((size_t)n));
