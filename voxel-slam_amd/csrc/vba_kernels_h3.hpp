@@ -27,7 +27,11 @@ __host__ __device__ constexpr bool h3_fits(int nv, int p) {
 // Tile table of the store [0, n): classes = runs of equal popcount (the extraction's order; a store pushed by the host in any order is
 // one class); inside a class one wave walks the masks 64 at a time with a running union and cuts a tile where the budget breaks
 // (the budget is monotone in both the union and the count, so the first violating lane is the cut).  tiles[0] = count; entry t =
-// (first voxel, voxels, union of the masks, 0) at tiles[4 + 4 t].
+// (first voxel, voxels, union of the masks, 0) at tiles[4 + 4 t].  A tile whose voxels see no frame at all (a fixed cluster only: they
+// still add coe * lambda_0 to the residual, VM:275) is given frame 0: k_hessian3 has one thread per slot of the union, and the thread
+// of a voxel's first union frame is the one that adds its residual; with an empty union nobody did (h3_tile_union).
+__device__ __forceinline__ int h3_tile_union(unsigned int U) { return (int)(U ? U : 1u); }
+
 __global__ __launch_bounds__(1024) void k_factor_tiles(FactorView f, int n) {
   __shared__ int bnd[18];
   __shared__ int nbnd;
@@ -70,11 +74,11 @@ __global__ __launch_bounds__(1024) void k_factor_tiles(FactorView f, int n) {
         if (i + take >= v1) { nv += take; U = Ut; i = v1; break; }         // the class ends inside this step
         // cut: the tile is [start, i + take)
         nv += take;
-        if (pass && lane == 0) { out[4 * ntile] = start; out[4 * ntile + 1] = nv; out[4 * ntile + 2] = (int)Ut; out[4 * ntile + 3] = 0; }
+        if (pass && lane == 0) { out[4 * ntile] = start; out[4 * ntile + 1] = nv; out[4 * ntile + 2] = h3_tile_union(Ut); out[4 * ntile + 3] = 0; }
         ntile++;
         start = i + take; i = start; nv = 0; U = 0;
       }
-      if (nv > 0) { if (pass && lane == 0) { out[4 * ntile] = start; out[4 * ntile + 1] = nv; out[4 * ntile + 2] = (int)U; out[4 * ntile + 3] = 0; } ntile++; }
+      if (nv > 0) { if (pass && lane == 0) { out[4 * ntile] = start; out[4 * ntile + 1] = nv; out[4 * ntile + 2] = h3_tile_union(U); out[4 * ntile + 3] = 0; } ntile++; }
       if (!pass && lane == 0) cnt[wave] = ntile;
     }
     __syncthreads();
