@@ -672,6 +672,49 @@ int vba_kf_read(vba_kf_store *s, int k, int cap, double *xyz, float *vardiag, in
  * offsets[f].  The pointers are valid until the next call that may grow the store (see "Growth and locking"). */
 int vba_kf_clouds(vba_kf_store *s, const double **d_pnt, const int **offsets, int *n_kf);
 
+/* ---- ResultOutput::pub_globalmap (VS:110-154): the global map of one or more sessions, from the stores.
+ *
+ * vba_kf_export_plan is HOST ONLY (no context, no device, like vba_io_*): which points are exported and where the messages are cut.
+ *   sizes[k]      point count of keyframe k of the sequence "all keyframes of all exported sessions in publication order" (the loop
+ *                 over ids at VS:126): the differences of the offsets vba_kf_clouds returns, store after store.
+ *   jump == 0     the reference's rule (VS:116-124): psize = sum of sizes, jump = psize / (10 * interval_size) + 1 in integer
+ *                 division; interval_size is 5e6 there.  The reference holds psize in a 32-bit unsigned, which wraps; here the sum is
+ *                 formed in 64 bits and a sum of 2^32 or more is VBA_ERR_BAD_ARG.  jump >= 1 is used as given (no limit on the sum).
+ *   *jump_out     the jump in force.
+ *   kf_begin      [n_kf + 1]: keyframe k contributes its points j = 0, jump, 2 jump, ... < sizes[k] (VS:133; the stride restarts
+ *                 at every keyframe), that is ceil(sizes[k] / jump) points; kf_begin[k] = exported points before keyframe k,
+ *                 kf_begin[n_kf] = the total.
+ *   messages      VS:145-153: after each keyframe a message ends when the points accumulated since the last cut are STRICTLY MORE than
+ *                 interval_size; one final message always follows and may be empty (pl is published unconditionally at VS:153).
+ *                 msg_end_kf[m] = one past the last keyframe of message m: message m is exactly the exported points
+ *                 [kf_begin[msg_end_kf[m-1]], kf_begin[msg_end_kf[m]]) (msg_end_kf[-1] = 0).  *n_msgs = the number of messages,
+ *                 always; at most cap_msgs entries are written (n_kf + 1 always suffices).
+ * The empty publish that clears the display (VS:113) stays with the node.
+ * VBA_ERR_BAD_ARG, with nothing written: n_kf < 0, a negative size, interval_size < 1, jump < 0, a NULL output (msg_end_kf may be
+ * NULL when cap_msgs == 0). */
+int vba_kf_export_plan(int n_kf, const int *sizes, int64_t interval_size, int jump, int *jump_out, int64_t *kf_begin /* [n_kf + 1] */,
+                       int cap_msgs, int *msg_end_kf /* [cap_msgs] */, int *n_msgs);
+/* Exported points [begin, begin + count) of the sequence the plan defines for the keyframes of stores[0], then stores[1], ... (the
+ * loop over ids, VS:126-151), as records x y z intensity of four floats; intensity[s] takes the place of pp.intensity = id (VS:128).
+ * world = x0.R p + x0.p with the store's CURRENT x0 (what vba_kf_set_poses last wrote) in the operation order stated above for the
+ * merge and used by vba_kf_load: q[r] = ((R[r][0]*x + R[r][1]*y) + R[r][2]*z) + p[r], every product and sum rounded on its own,
+ * nothing contracted; each coordinate is then narrowed to float once (pp.x = vv[0], VS:139-141).  This order is part of the interface.
+ * xyzi [count][4] is HOST or DEVICE memory (a device buffer 16-byte aligned).  The work runs on ctx's stream; the stores may hang
+ * off other contexts on the same device (another device: VBA_ERR_BAD_ARG).  Host memory: the records pass through a staging buffer
+ * of the context in passes of at most 2^22 records and the call synchronises once, at its end.  Device memory: stream-ordered, no
+ * synchronisation, the buffer may be consumed by later work on that stream.  (The per-keyframe table goes up through a ring of four
+ * pinned images; a call waits for the upload of the fourth call before it only if that is still pending.)  The table and the
+ * staging buffer belong to the context, grow by doubling when an export needs more and are never allocated per call.
+ * The stores are read and nothing in them changes: no exist flag, no pose, no point.  The caller excludes vba_kf_build /
+ * vba_kf_reserve / vba_kf_load* on these stores for the duration of the call ("Growth and locking").  With a DEVICE xyzi the call
+ * returns while the gather is still queued: the exclusion then lasts until that work on ctx's stream has completed (vba_synchronize
+ * (ctx), or an event the caller recorded behind the call), because a build or reserve that grows a store waits only for the store's
+ * own context before it frees the old arrays.
+ * VBA_ERR_BAD_ARG before any device work, xyzi untouched: n_stores < 1, a NULL store or intensity, jump < 1, begin < 0, count < 0,
+ * begin + count beyond the plan's total, count > 0 with a NULL xyzi.  count == 0 is a success that does nothing. */
+int vba_kf_export_world(vba_ctx *ctx, int n_stores, vba_kf_store *const *stores, const float *intensity /* [n_stores] */, int jump,
+                        int64_t begin, int64_t count, float *xyzi /* [count][4], HOST or DEVICE */);
+
 /* ------------------------------------------------------------------------------------------------
  * Loop-closure map: the counterpart of `map_loop` (VS:2601-2625) and loop_update() (VS:1255-1373), the step that
  * carries a loop closure back into local mapping.  A vba_loop_map owns one second voxel map, created from its context's options

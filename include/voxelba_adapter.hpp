@@ -11,6 +11,7 @@
 //   multi_recut / multi_margi    VS:1682 / VS:1590                  vba::VoxelMap::multi_recut / multi_margi
 //   Initialization::motion_init  VS:617-819                         vba::Initialization::motion_init
 //   build_graph + gtsam::ISAM2   VS:2078-2156, VS:2550-2561          vba::PoseGraph (add_edge LR:147-161, set_state LR:36-43)
+//   ResultOutput::pub_globalmap  VS:110-154                         vba::pub_globalmap
 //
 // The reference's types are Eigen-based (tools.hpp:4).  This header compiles without Eigen (plain-array structs that
 // mirror PointCluster / IMUST / IMU_PRE field for field); when <Eigen/Core> is available the Eigen-typed overloads
@@ -661,6 +662,14 @@ class KeyframeStore {
   }
   // the (offsets, pnt_local) arguments of vba_hba_add_edge / vba_hba_global / vba_gba_build, zero copy: pnt_local is DEVICE memory
   void clouds(const double *&d_pnt, const int *&offsets, int &n_kf) const { check(ctx_, vba_kf_clouds(s_, &d_pnt, &offsets, &n_kf)); }
+  // smps[i]->plptr->size() for every keyframe: the `sizes` of vba_kf_export_plan
+  std::vector<int> sizes() const {
+    const double *d_pnt; const int *off; int n = 0;
+    clouds(d_pnt, off, n);
+    std::vector<int> out((size_t)n);
+    for (int i = 0; i < n; i++) out[i] = off[i + 1] - off[i];
+    return out;
+  }
   // keyframe k's plptr on the host (save_pcd, tests): x y z and normal_x/y/z
   void read(int k, std::vector<XYZ> &xyz, std::vector<XYZ> *normal = nullptr) const {
     int n = 0;
@@ -679,6 +688,40 @@ class KeyframeStore {
   vba_ctx *ctx_ = nullptr;
   vba_kf_store *s_ = nullptr;
 };
+
+// ResultOutput::pub_globalmap (VS:110-154) from the stores: relc_submaps[id] is session id's store, `ids` the sessions to publish in
+// order, publish(const float *xyzi, int64_t n) receives one message of n records x y z intensity (intensity = id), the final one
+// included even when it is empty (VS:153).  The empty publish that clears the display first (VS:113) stays with the caller.  The
+// work runs on ctx's stream; the caller holds mtx_keyframe as for any reader of the stores.  Returns the jump in force.
+template <class Publish>
+inline int pub_globalmap(Context &ctx, const std::vector<KeyframeStore *> &relc_submaps, const std::vector<int> &ids, Publish &&publish,
+                         int64_t interval_size = 5000000, int jump = 0) {
+  std::vector<vba_kf_store *> stores;
+  std::vector<float> intensity;
+  std::vector<int> sizes;
+  for (int id : ids) {
+    KeyframeStore &smps = *relc_submaps.at((size_t)id);
+    stores.push_back(smps.get());
+    intensity.push_back((float)id);                                             // pp.intensity = id, VS:128
+    const std::vector<int> sz = smps.sizes();
+    sizes.insert(sizes.end(), sz.begin(), sz.end());
+  }
+  const int n_kf = (int)sizes.size();
+  std::vector<int64_t> kf_begin((size_t)n_kf + 1);
+  std::vector<int> msg_end((size_t)n_kf + 1);
+  int n_msgs = 0;
+  check(ctx.get(), vba_kf_export_plan(n_kf, sizes.data(), interval_size, jump, &jump, kf_begin.data(), n_kf + 1, msg_end.data(), &n_msgs));
+  std::vector<float> pl;
+  int k0 = 0;
+  for (int m = 0; m < n_msgs; m++) {
+    const int64_t begin = kf_begin[(size_t)k0], n = kf_begin[(size_t)msg_end[(size_t)m]] - begin;
+    pl.resize((size_t)n * 4);
+    if (n > 0) check(ctx.get(), vba_kf_export_world(ctx.get(), (int)stores.size(), stores.data(), intensity.data(), jump, begin, n, pl.data()));
+    publish((const float *)pl.data(), n);
+    k0 = msg_end[(size_t)m];
+  }
+  return jump;
+}
 
 // ---- loop closure -> local mapping (voxelba.h "Loop-closure map").  The pose algebra runs here, on the host, one
 // separately rounded product and sum after the other in the order  s = a0*b0; s += a1*b1; s += a2*b2  (compile without contraction

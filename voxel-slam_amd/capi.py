@@ -41,7 +41,7 @@ EXPORTS = [
     "vba_pgo_optimize",
     "vba_kf_create", "vba_kf_destroy", "vba_kf_reserve", "vba_kf_allocations", "vba_kf_size", "vba_kf_build", "vba_kf_last_counts",
     "vba_kf_generate_stds", "vba_kf_set_poses", "vba_kf_get", "vba_kf_set_history", "vba_kf_history_size", "vba_kf_load",
-    "vba_kf_load_nearby", "vba_kf_read", "vba_kf_clouds",
+    "vba_kf_load_nearby", "vba_kf_read", "vba_kf_clouds", "vba_kf_export_plan", "vba_kf_export_world",
     "vba_loop_map_create", "vba_loop_map_destroy", "vba_loop_map_reserve", "vba_loop_map_allocations", "vba_loop_map_build",
     "vba_loop_map_num_roots", "vba_loop_map_dump_leaves", "vba_loop_map_dump_plane_var", "vba_loop_update",
 ]
@@ -366,6 +366,10 @@ class KeyframeStore:
         off = np.array([o[i] for i in range(n.value + 1)], dtype=np.int32)
         return (d.value or 0), off, n.value
 
+    def sizes(self):
+        """point count of every keyframe (int32 [n_kf]): the ``sizes`` of kf_export_plan"""
+        return np.diff(self.clouds()[1]).astype(np.int32)
+
 
 class LoopMap:
     """One vba_loop_map: ``map_loop`` of the loop-closure thread, a second voxel map resident in HBM."""
@@ -557,6 +561,20 @@ def save_pose(path, states, v6):
     """FileReaderWriter::save_pose (voxelslam.cpp:181-204); writes nothing for fewer than 100 scans."""
     states = _c(states).reshape(-1, 25); v6 = _c(v6).reshape(-1, 6)
     _io_chk(load().vba_io_save_pose(os.fsencode(path), C.c_int(len(states)), _p(states), _p(v6)))
+
+
+def kf_export_plan(sizes, interval_size=5_000_000, jump=0):
+    """vba_kf_export_plan (pub_globalmap, voxelslam.cpp:110-154; host only): ``sizes`` = the point counts of all keyframes of all
+    exported sessions in publication order, jump 0 = the reference's rule.  Returns (jump in force, kf_begin int64 [n_kf + 1],
+    msg_end_kf int32 [n_msgs]): message m is the exported points kf_begin[msg_end_kf[m - 1]] .. kf_begin[msg_end_kf[m]]."""
+    sizes = np.ascontiguousarray(sizes, dtype=np.int32).ravel()
+    n = len(sizes)
+    ip = C.POINTER(C.c_int)
+    j = C.c_int(); nm = C.c_int()
+    kb = np.zeros(n + 1, dtype=np.int64); me = np.zeros(n + 1, dtype=np.int32)
+    _io_chk(load().vba_kf_export_plan(C.c_int(n), sizes.ctypes.data_as(ip), C.c_int64(int(interval_size)), C.c_int(int(jump)), C.byref(j),
+                                      kb.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(n + 1), me.ctypes.data_as(ip), C.byref(nm)))
+    return j.value, kb, me[:nm.value].copy()
 
 
 def read_lidarstate(path):
@@ -759,6 +777,27 @@ class Context:
 
     def loop_map(self) -> "LoopMap":
         return LoopMap(self)
+
+    def kf_export_world(self, stores, intensity, jump, begin=0, count=None, out=None):
+        """vba_kf_export_world on this context's stream: exported points [begin, begin + count) of ``stores`` (KeyframeStore objects of
+        this device, in publication order) at their current poses, ``intensity`` one float per store, ``jump`` >= 1 as kf_export_plan
+        returned it.  count None = up to the end.  Returns float32 [count][4] records x y z intensity; with ``out`` (the address of a
+        16-byte aligned DEVICE buffer of count records) the call is stream-ordered, does not synchronise and returns None."""
+        inten = np.ascontiguousarray(intensity, dtype=np.float32).ravel()
+        if len(inten) != len(stores):
+            raise ValueError("one intensity per store")
+        if count is None:
+            j = max(int(jump), 1)
+            count = sum(int(((s.sizes().astype(np.int64) + j - 1) // j).sum()) for s in stores) - int(begin)
+        hs = (C.c_void_p * max(len(stores), 1))(*[(s.h.value if s is not None else None) for s in stores])
+        args = (self.h, C.c_int(len(stores)), hs, inten.ctypes.data_as(C.POINTER(C.c_float)), C.c_int(int(jump)), C.c_int64(int(begin)),
+                C.c_int64(int(count)))
+        if out is not None:
+            self._chk(self.lib.vba_kf_export_world(*args, out if isinstance(out, C.c_void_p) else C.c_void_p(int(out))))
+            return None
+        res = np.zeros((max(int(count), 0), 4), dtype=np.float32)
+        self._chk(self.lib.vba_kf_export_world(*args, res.ctypes.data_as(C.c_void_p)))
+        return res
 
     def loop_update(self, lm, poses_win, bl_scans=(), bl_poses=None, bl_vars=None, win_scans=None, win_vars=None, dx12=None):
         """loop_update() (VS:1255-1373) on this context's map: adopt ``lm``, insert the buf_lba2loop scans ``bl_scans`` (list of

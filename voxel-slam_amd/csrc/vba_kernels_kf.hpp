@@ -75,4 +75,50 @@ __global__ __launch_bounds__(256) void k_kf_emit(int n, const DsSlot *__restrict
   count[pos] = s.cnt;
 }
 
+// pub_globalmap (VS:110-154): the strided gather of the stores' keyframes into 16-byte x y z intensity records.
+// One table row per keyframe, in publication order: the exported points before it (`first`, counted over the whole export), the
+// store row of its first point, its current x0.  Keyframe k contributes rows row, row + jump, ... (the stride restarts at every
+// keyframe, VS:133), so exported point i of keyframe k is store row  row + (i - first) * jump.
+struct ExpKf { long long first; long long row; double T[12]; };   // 112 bytes
+
+// One output record per lane, lanes on consecutive records; the grid is capped and strides over the rest.  Outputs i0 .. i0 + n - 1
+// of the export, out = the record of i0; tab[0 .. nkf) = the keyframes of ONE store that these outputs can touch (tab[0].first <= i0),
+// pnt = that store's point array.  A workgroup's 256 consecutive outputs touch the keyframes between the one of its first and the
+// one of its last output: two lanes find those two in the table, every lane then searches only between them (as k_kf_merge does
+// over its whole table; empty keyframes are skipped by the <=).  world = x0.R p + x0.p in kf_apply's order, each coordinate narrowed
+// to float once (pp.x = vv[0], VS:139-141); one 16-byte store per record.  Every index into pnt and out is formed in 64 bits.
+__global__ __launch_bounds__(256) void k_kf_export(long long i0, long long n, int nkf, const ExpKf *__restrict__ tab, const double *__restrict__ pnt,
+                                                   int jump, float intensity, float4 *__restrict__ out) {
+  __shared__ int s_k[2];
+  const long long step = (long long)gridDim.x * 256;
+  for (long long base = (long long)blockIdx.x * 256; base < n; base += step) {        // (uniform per workgroup: the barriers below are safe)
+    const long long rem = n - base, cnt = rem < 256 ? rem : 256;
+    if (threadIdx.x < 2) {
+      const long long t = i0 + base + (threadIdx.x ? cnt - 1 : 0);
+      int lo = 0, hi = nkf - 1;                               // last j with tab[j].first <= t
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab[mid].first <= t) lo = mid; else hi = mid - 1;
+      }
+      s_k[threadIdx.x] = lo;
+    }
+    __syncthreads();
+    int lo = s_k[0], hi = s_k[1];
+    __syncthreads();                                          // s_k is rewritten by the next round
+    if ((long long)threadIdx.x < cnt) {
+      const long long o = base + threadIdx.x, i = i0 + o;
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab[mid].first <= i) lo = mid; else hi = mid - 1;
+      }
+      const ExpKf *__restrict__ e = tab + lo;
+      const long long row = e->row + (i - e->first) * (long long)jump;
+      const size_t b = 3 * (size_t)row;
+      double x, y, z;
+      kf_apply(e->T, pnt[b], pnt[b + 1], pnt[b + 2], x, y, z);
+      out[o] = make_float4((float)x, (float)y, (float)z, intensity);
+    }
+  }
+}
+
 }  // namespace vba

@@ -182,6 +182,13 @@ struct vba_ctx {
   // pose-graph optimisation (vba_pgo_optimize): graph structure and per-update work areas, and the dense skeleton system; grow-only
   char *d_pgo = nullptr; size_t pgo_bytes = 0;
   double *d_pgoAb = nullptr; size_t pgoAb_bytes = 0;
+  // vba_kf_export_world: the per-keyframe table (pinned upload ring, so that a call need not drain the stream before
+  // it writes the next image, and the device copy) and the staging of host output; grow-only
+  static const int kExpRing = 4;
+  char *h_exp[kExpRing] = {nullptr}; hipEvent_t exp_ev[kExpRing] = {nullptr}; int exp_next = 0;
+  char *d_exp = nullptr; size_t exp_cap = 0;            // keyframes
+  char *d_expout = nullptr; size_t expout_cap = 0;      // records
+  std::vector<long long> exp_first; std::vector<int> exp_kbase;   // host scratch: exported points before every keyframe, keyframes before every store
 
   void set_error(const std::string &s) { err = s; }
 };
@@ -661,6 +668,9 @@ void vba_destroy(vba_ctx *c) {
   if (c->d_icppart) hipFree(c->d_icppart);
   if (c->d_pgo) hipFree(c->d_pgo);
   if (c->d_pgoAb) hipFree(c->d_pgoAb);
+  for (int i = 0; i < vba_ctx::kExpRing; i++) { if (c->h_exp[i]) hipHostFree(c->h_exp[i]); if (c->exp_ev[i]) hipEventDestroy(c->exp_ev[i]); }
+  if (c->d_exp) hipFree(c->d_exp);
+  if (c->d_expout) hipFree(c->d_expout);
   if (c->d_lipack) hipFree(c->d_lipack);
   if (c->d_liscr) hipFree(c->d_liscr);
   for (int i = 0; i < 2; i++) if (c->d_kdtree[i]) hipFree(c->d_kdtree[i]);
@@ -4238,6 +4248,146 @@ int vba_kf_read(vba_kf_store *s, int k, int cap, double *xyz, float *vardiag, in
 int vba_kf_clouds(vba_kf_store *s, const double **d_pnt, const int **offsets, int *n_kf) {
   if (!s || !d_pnt || !offsets || !n_kf) return VBA_ERR_BAD_ARG;
   *d_pnt = s->d_pnt; *offsets = s->off.data(); *n_kf = (int)s->kf.size();
+  return VBA_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ global map export (vba_kf_export_*)
+namespace {
+
+const long long kExpChunk = 1ll << 22;       // records per pass through the staging buffer of a host export (64 MiB)
+const int kExpMaxBlocks = 2048;              // grid cap of the streaming kernel: 256 CUs x 8 workgroups, the rest is grid-strided
+
+inline long long exp_count(long long size, long long jump) { return (size + jump - 1) / jump; }   // j = 0, jump, ... < size
+
+// the table of `entries` keyframes: every image of the pinned ring and the device copy
+int exp_ensure_tab(vba_ctx *c, size_t entries) {
+  for (int i = 0; i < vba_ctx::kExpRing; i++)
+    if (!c->exp_ev[i]) HIPCHK(c, hipEventCreateWithFlags(&c->exp_ev[i], hipEventDisableTiming));
+  if (entries <= c->exp_cap) return VBA_OK;
+  size_t m = c->exp_cap ? c->exp_cap : 1024;
+  while (m < entries) m *= 2;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < vba_ctx::kExpRing; i++) { if (c->h_exp[i]) hipHostFree(c->h_exp[i]); c->h_exp[i] = nullptr; }
+  if (c->d_exp) hipFree(c->d_exp);
+  c->d_exp = nullptr; c->exp_cap = 0;
+  for (int i = 0; i < vba_ctx::kExpRing; i++) HIPCHK(c, hipHostMalloc((void **)&c->h_exp[i], m * sizeof(ExpKf), hipHostMallocDefault));
+  HIPCHK(c, hipMalloc((void **)&c->d_exp, m * sizeof(ExpKf)));
+  c->exp_cap = m;
+  return VBA_OK;
+}
+
+int exp_ensure_out(vba_ctx *c, size_t recs) {
+  if (recs <= c->expout_cap) return VBA_OK;
+  size_t m = c->expout_cap ? c->expout_cap : 65536;
+  while (m < recs) m *= 2;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->d_expout) hipFree(c->d_expout);
+  c->d_expout = nullptr; c->expout_cap = 0;
+  HIPCHK(c, hipMalloc((void **)&c->d_expout, m * sizeof(float4)));
+  c->expout_cap = m;
+  return VBA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vba_kf_export_plan(int n_kf, const int *sizes, int64_t interval_size, int jump, int *jump_out, int64_t *kf_begin, int cap_msgs, int *msg_end_kf,
+                       int *n_msgs) {
+  if (n_kf < 0 || (n_kf > 0 && !sizes) || interval_size < 1 || jump < 0 || !jump_out || !kf_begin || !n_msgs || cap_msgs < 0 ||
+      (cap_msgs > 0 && !msg_end_kf))
+    return VBA_ERR_BAD_ARG;
+  uint64_t psize = 0;                                          // VS:117-123 in 64 bits: the reference's `uint psize` wraps at 2^32
+  for (int k = 0; k < n_kf; k++) {
+    if (sizes[k] < 0) return VBA_ERR_BAD_ARG;
+    psize += (uint64_t)sizes[k];
+  }
+  if (jump == 0) {
+    if (psize >= ((uint64_t)1 << 32)) return VBA_ERR_BAD_ARG;
+    const uint64_t ten = interval_size > INT64_MAX / 10 ? (uint64_t)INT64_MAX : 10 * (uint64_t)interval_size;
+    jump = (int)(psize / ten) + 1;                             // VS:124
+  }
+  *jump_out = jump;
+  int64_t total = 0, pl = 0;
+  int nm = 0;
+  for (int k = 0; k < n_kf; k++) {
+    kf_begin[k] = total;
+    const int64_t cnt = exp_count(sizes[k], jump);             // VS:133
+    total += cnt; pl += cnt;
+    if (pl > interval_size) {                                  // VS:145-150
+      if (nm < cap_msgs) msg_end_kf[nm] = k + 1;
+      nm++; pl = 0;
+    }
+  }
+  kf_begin[n_kf] = total;
+  if (nm < cap_msgs) msg_end_kf[nm] = n_kf;                    // VS:153: published whatever it holds
+  nm++;
+  *n_msgs = nm;
+  return VBA_OK;
+}
+
+int vba_kf_export_world(vba_ctx *c, int n_stores, vba_kf_store *const *stores, const float *intensity, int jump, int64_t begin, int64_t count,
+                        float *xyzi) {
+  if (!c || n_stores < 1 || !stores || !intensity || jump < 1 || begin < 0 || count < 0 || (count > 0 && !xyzi)) return VBA_ERR_BAD_ARG;
+  for (int s = 0; s < n_stores; s++) if (!stores[s] || stores[s]->ctx->device != c->device) return VBA_ERR_BAD_ARG;
+  // exported points before every keyframe of the whole sequence (the plan's kf_begin), keyframes before every store
+  std::vector<long long> &first = c->exp_first;
+  std::vector<int> &kbase = c->exp_kbase;
+  first.clear(); kbase.clear();
+  long long total = 0;
+  for (int s = 0; s < n_stores; s++) {
+    const std::vector<int> &off = stores[s]->off;
+    if (first.size() + stores[s]->kf.size() > (size_t)(1 << 30)) return VBA_ERR_CAPACITY;
+    kbase.push_back((int)first.size());
+    for (size_t k = 0; k + 1 < off.size(); k++) { first.push_back(total); total += exp_count((long long)off[k + 1] - off[k], jump); }
+  }
+  kbase.push_back((int)first.size());
+  first.push_back(total);
+  if (begin > total || count > total - begin) return VBA_ERR_BAD_ARG;
+  if (count == 0) return VBA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool dev_out = is_device_ptr(xyzi);
+  if (dev_out && ((uintptr_t)xyzi & 15)) { c->set_error("vba_kf_export_world: a device xyzi must be 16-byte aligned"); return VBA_ERR_BAD_ARG; }
+  const long long end = begin + count;
+  // the keyframes of the first and of the last exported point: the last k with first[k] <= i (never an empty keyframe)
+  auto kf_of = [&](long long i) { return (int)(std::upper_bound(first.begin(), first.end() - 1, i) - first.begin()) - 1; };
+  const int ka = kf_of(begin), kb = kf_of(end - 1), nk = kb - ka + 1;
+  int st;
+  if ((st = exp_ensure_tab(c, (size_t)nk))) return st;
+  if (!dev_out && (st = exp_ensure_out(c, (size_t)(count < kExpChunk ? count : kExpChunk)))) return st;
+  const int slot = c->exp_next;
+  c->exp_next = (slot + 1) % vba_ctx::kExpRing;
+  HIPCHK(c, hipEventSynchronize(c->exp_ev[slot]));             // the upload that last read this image (kExpRing calls ago): long done
+  ExpKf *h = (ExpKf *)c->h_exp[slot];
+  for (int s = 0; s < n_stores; s++) {
+    const vba_kf_store *S = stores[s];
+    for (int g = std::max(ka, kbase[s]); g <= kb && g < kbase[s + 1]; g++) {
+      const int k = g - kbase[s];
+      ExpKf &e = h[g - ka];
+      e.first = first[g]; e.row = S->off[k];
+      std::memcpy(e.T, S->kf[k].x0, 12 * sizeof(double));
+    }
+  }
+  HIPCHK(c, hipMemcpyAsync(c->d_exp, h, (size_t)nk * sizeof(ExpKf), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->exp_ev[slot], c->stream));
+  const ExpKf *d_tab = (const ExpKf *)c->d_exp;
+  for (long long cb = begin; cb < end; cb += dev_out ? count : kExpChunk) {
+    const long long ce = dev_out ? end : std::min(end, cb + kExpChunk);
+    float4 *out = dev_out ? (float4 *)xyzi : (float4 *)c->d_expout;                     // the record of cb
+    for (int s = 0; s < n_stores; s++) {                       // one launch per store: its point array, its intensity, its rows of the table
+      const long long a = std::max(cb, first[kbase[s]]), b = std::min(ce, first[kbase[s + 1]]);
+      if (a >= b) continue;
+      const int g0 = std::max(ka, kbase[s]), g1 = std::min(kb, kbase[s + 1] - 1);
+      const long long nb = (b - a + 255) / 256;
+      hipLaunchKernelGGL(k_kf_export, dim3((unsigned)std::min<long long>(nb, kExpMaxBlocks)), dim3(256), 0, c->stream, a, b - a, g1 - g0 + 1,
+                         d_tab + (g0 - ka), (const double *)stores[s]->d_pnt, jump, intensity[s], out + (a - cb));
+    }
+    HIPCHK(c, hipGetLastError());
+    if (!dev_out) HIPCHK(c, hipMemcpyAsync(xyzi + 4 * (size_t)(cb - begin), c->d_expout, (size_t)(ce - cb) * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (!dev_out) HIPCHK(c, hipStreamSynchronize(c->stream));
   return VBA_OK;
 }
 
