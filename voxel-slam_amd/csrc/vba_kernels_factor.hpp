@@ -285,6 +285,20 @@ __device__ __forceinline__ double wave_sum_to_lane63(double x) {
   return x;
 }
 
+// Initial LM state of a call (vba_lm_begin), handed BY VALUE to the first kernel the call launches instead of being copied into the
+// LmDev image up front: with `on` set every workgroup takes the poses from x (kernarg segment, nothing is read from the image) and
+// workgroup 0 writes the complete image to dst (lm_init_store, vba_kernels_lm.hpp).  on == 0: the kernel reads and behaves as
+// without the argument.
+struct LmDev;
+template <int W>
+struct LmInit {
+  double x[12 * W];                  // begin poses
+  LmDev *dst;
+  int on, dbg;                       // dbg: LmDev::pad (diagnostic mask)
+};
+template <int W>
+__device__ __forceinline__ void lm_init_store(const LmInit<W> &a, int tid, int nt);
+
 template <int W, int TV>
 struct ResCfg {
   static constexpr int NT = ((TV * W + 63) / 64) * 64;      // threads per workgroup
@@ -297,7 +311,7 @@ struct ResCfg {
 template <int W, int TV, bool STAMPS>
 __global__ __launch_bounds__((ResCfg<W, TV>::NT)) void k_residual_s(FactorView f, const double *__restrict__ poses, int head, int end,
                                                                   double *__restrict__ partial, const int *__restrict__ gate,
-                                                                  long long *__restrict__ stamps) {
+                                                                  long long *__restrict__ stamps, LmInit<W> init) {
   using C = ResCfg<W, TV>;
   __shared__ double T[10][W][TV];                               // world-frame cluster of every slot (zeros for empty slots)
   __shared__ double S[10][TV];                                  // pcr_add of every voxel
@@ -314,7 +328,7 @@ __global__ __launch_bounds__((ResCfg<W, TV>::NT)) void k_residual_s(FactorView f
   if (STAMPS) st0 = clock64();
   // ---- trip 1: the voxel's occupancy mask, this thread's scalars of the fixed cluster, coe (row 0), the poses
   const unsigned int occm = f.occ[vc];
-  const double pose_s = poses[tid < W * 12 ? tid : 0];
+  const double pose_s = init.on ? init.x[tid < W * 12 ? tid : 0] : poses[tid < W * 12 ? tid : 0];
   double acc[C::KPT];
 #pragma unroll
   for (int j = 0; j < C::KPT; j++) { const int k = fi + j * C::NF; acc[j] = f.fix[(size_t)(k < 10 ? k : 9) * vs + vc]; }
@@ -322,6 +336,7 @@ __global__ __launch_bounds__((ResCfg<W, TV>::NT)) void k_residual_s(FactorView f
   unsigned int occv = occm;
   asm volatile("" : "+v"(occv), "+v"(coe), "+v"(acc[0]));       // keep the loads above the exit (they would be sunk below it)
   if (gate_v == 0) return;
+  if (init.on && blockIdx.x == 0) lm_init_store(init, tid, C::NT);
   if (tid < W * 12) sp[tid] = pose_s;
   // ---- trip 2: the 10 scalars of an occupied slot (an empty slot costs nothing beyond its mask bit)
   const bool occ = fi < W && v < end && ((occv >> fic) & 1u);
@@ -394,9 +409,13 @@ __global__ __launch_bounds__((ResCfg<W, TV>::NT)) void k_residual_s(FactorView f
 // for the slot-parallel form (and 194-208 us before the store was ordered); V = 2.8e5: 28.5 us = 0.72 against 42.7 us; at the bench
 // window (V = 1.8e4: 288 waves, one per CU, the frames of a voxel serial in its lane) 7.8 us against 5.5 us — stores below
 // ~45k voxels keep the slot-parallel form.
-template <int W, bool STAMPS>
+// INIT: the instance vba_lm_refresh_eigen launches as the first LM kernel of a call (init.on is then set): the poses come from the
+// init argument.  A compile-time switch here, not only the flag: with both pose sources in one instance the kernel held 34 VGPRs more
+// (W = 10: 240 -> 256 + 18 AGPRs, one wave per SIMD instead of two); the INIT = false instance ignores the argument.
+template <int W, bool STAMPS, bool INIT = false>
 __global__ __launch_bounds__(64) void k_residual_v(FactorView f, const double *__restrict__ poses, int head, int end,
-                                                   double *__restrict__ partial, const int *__restrict__ gate, long long *__restrict__ stamps) {
+                                                   double *__restrict__ partial, const int *__restrict__ gate, long long *__restrict__ stamps,
+                                                   LmInit<W> init) {
   const int gate_v = gate ? *gate : 1;
   const int lane = threadIdx.x;
   const int v = head + blockIdx.x * 64 + lane;
@@ -411,6 +430,7 @@ __global__ __launch_bounds__(64) void k_residual_v(FactorView f, const double *_
   double coe = f.coe[vc];
   asm volatile("" : "+v"(occm), "+v"(coe), "+v"(acc[0]));       // keep the loads above the exit
   if (gate_v == 0) return;
+  if (INIT && blockIdx.x == 0) lm_init_store(init, lane, 64);
   if (v >= end) occm = 0;
   // trip 2: all frames the wave sees
   double c[W][10];
@@ -430,7 +450,7 @@ __global__ __launch_bounds__(64) void k_residual_v(FactorView f, const double *_
     const bool on = (occm >> i) & 1u;
     if (__ballot(on) != 0ull) {
       if (on) {
-        const Cl10 w = cluster_transform_exact(c[i][0], c[i][1], c[i][2], c[i][3], c[i][4], c[i][5], c[i][6], c[i][7], c[i][8], c[i][9], poses + 12 * i);
+        const Cl10 w = cluster_transform_exact(c[i][0], c[i][1], c[i][2], c[i][3], c[i][4], c[i][5], c[i][6], c[i][7], c[i][8], c[i][9], (INIT ? init.x : poses) + 12 * i);
         acc[0] += w.p00; acc[1] += w.p10; acc[2] += w.p20; acc[3] += w.p11; acc[4] += w.p21; acc[5] += w.p22;
         acc[6] += w.v0; acc[7] += w.v1; acc[8] += w.v2; acc[9] += w.n;
       }
@@ -469,7 +489,9 @@ __global__ __launch_bounds__(64) void k_residual_v(FactorView f, const double *_
 __global__ __launch_bounds__(256) void k_reduce_partials(const double *__restrict__ partial, int nb, int nout, double *__restrict__ out,
                                                         const int *__restrict__ gate) {
   __shared__ double s[256];
-  const int gate_v = gate ? *gate : 1;            // requested together with the first 16 partials (one memory trip, see k_residual_s)
+  // the gate first, with a wait of its own: a gated launch (after a rejected step) requests nothing of the (nb x nout) slab, whose
+  // loads a wave would have to see return before it retires; an ungated launch pays one more dependent trip (measured: DESIGN.md 5)
+  if (gate && *gate == 0) return;
   const int j = threadIdx.x & 15, q = threadIdx.x >> 4;
   const int o = blockIdx.x * 16 + j, oc = o < nout ? o : nout - 1;
   double pv[16];
@@ -477,7 +499,6 @@ __global__ __launch_bounds__(256) void k_reduce_partials(const double *__restric
   for (int k = 0; k < 16; k++) { const int b = q + 16 * k; pv[k] = partial[(size_t)(b < nb ? b : 0) * nout + oc]; }
 #pragma unroll
   for (int k = 0; k < 16; k++) asm volatile("" : "+v"(pv[k]));
-  if (gate_v == 0) return;
   double acc = 0.0;
   if (o < nout) {
 #pragma unroll
@@ -711,7 +732,7 @@ template <int W>
 __global__ __launch_bounds__(HessCfg2<W>::NT) void k_hessian2(FactorView f, const double *__restrict__ poses, int head, int end,
                                                              int ntiles, double *__restrict__ partial, const int *__restrict__ gate,
                                                              long long *__restrict__ stamps, LmDev *lm, const double *__restrict__ k4_partial, int k4_nb,
-                                                             int nwg, LiJob li) {
+                                                             int nwg, LiJob li, LmInit<W> init) {
   using C = HessCfg2<W>;
   extern __shared__ __attribute__((aligned(16))) double lds[];
   // (every wave of this kernel holds ~300 registers, so a CU takes ONE workgroup: the IMU workgroup is block 0 — dispatched first —
@@ -730,8 +751,8 @@ __global__ __launch_bounds__(HessCfg2<W>::NT) void k_hessian2(FactorView f, cons
   unsigned int occ_nx = 0;
   if (my_fi < W && tile0 < tile1) { const int v0 = head + tile0 * HessCfg2<W>::TV + my_vl; occ_nx = f.occ[v0 < end ? v0 : end - 1]; }
   __shared__ int lm_dec[2];
-  int gate_v = (gate && !lm) ? *gate : 1;     // consumed after the first tile's loads have been requested (one trip, not two)
-  double lm_r2 = 0.0;
+  int gate_v = (gate && !lm && !init.on) ? *gate : 1;     // consumed after the first tile's loads have been requested (one trip, not two)
+  double lm_r2 = 0.0;                         // (init.on: the first pass of a call, run_hess = 1 is part of the image this launch writes)
   if (lm) {
     if (threadIdx.x < 64) {
       lm_r2 = lm_sum_partials(k4_partial, k4_nb, threadIdx.x);
@@ -754,7 +775,12 @@ __global__ __launch_bounds__(HessCfg2<W>::NT) void k_hessian2(FactorView f, cons
   double *sp = cK + C::NK;                    // [W][12]
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 
-  for (int t = tid; t < W * 12; t += C::NT) sp[t] = poses[t];
+  if (init.on) {
+    for (int t = tid; t < W * 12; t += C::NT) sp[t] = init.x[t];
+    if (bid == 0) lm_init_store(init, tid, C::NT);
+  } else {
+    for (int t = tid; t < W * 12; t += C::NT) sp[t] = poses[t];
+  }
   constexpr int PADC = C::GS - C::NC;                               // padded columns (none at W = 8) stay zero for the whole kernel
   if constexpr (PADC > 0)
     for (int t = tid; t < C::NK * PADC; t += C::NT) { G[(size_t)(t / PADC) * C::GS + C::NC + t % PADC] = 0.0; if (C::PRESCALE) GA[(size_t)(t / PADC) * C::GS + C::NC + t % PADC] = 0.0; }

@@ -24,6 +24,35 @@ struct LmDev {
   double xt_spec[LM_SPEC][VBA_MAX_WIN_DEV * 12];
 };
 
+// The image vba_lm_begin defines (x = xt = begin poses, u = 0.01, v = 2 (VM:427), is_calc_hess = all_accepted = run_hess = run_res = 1,
+// max_trace = 64, pad = the diagnostic mask, every other byte zero), written by the nt threads of ONE workgroup of the first kernel
+// of the call (LmInit, vba_kernels_factor.hpp) or by k_lm_init.  Every 8-byte word of the image is stored exactly once.
+template <int W>
+__device__ __forceinline__ void lm_init_store(const LmInit<W> &a, int tid, int nt) {
+  constexpr int NW = sizeof(LmDev) / 8, XT = offsetof(LmDev, xt) / 8, U = offsetof(LmDev, u) / 8, V = offsetof(LmDev, v) / 8,
+                I = offsetof(LmDev, is_calc_hess) / 8;
+  static_assert(sizeof(LmDev) % 8 == 0 && offsetof(LmDev, x) == 0 && offsetof(LmDev, u) == 2 * offsetof(LmDev, xt) && 12 * W <= XT, "x and xt lead the image");
+  static_assert(offsetof(LmDev, is_calc_hess) % 8 == 0 && offsetof(LmDev, pad) == offsetof(LmDev, is_calc_hess) + 36, "the ten flags are five words");
+  auto two = [](int lo, int hi) { return (unsigned long long)(unsigned int)lo | ((unsigned long long)(unsigned int)hi << 32); };
+  unsigned long long *o = reinterpret_cast<unsigned long long *>(a.dst);
+  for (int w = tid; w < NW; w += nt) {
+    unsigned long long val = 0ull;
+    if (w < 2 * XT) { const int k = w < XT ? w : w - XT; if (k < 12 * W) val = (unsigned long long)__double_as_longlong(a.x[k]); }
+    else if (w == U) val = (unsigned long long)__double_as_longlong(0.01);
+    else if (w == V) val = (unsigned long long)__double_as_longlong(2.0);
+    else if (w == I) val = two(1, 0);               // is_calc_hess, stop
+    else if (w == I + 2) val = two(1, 0);           // all_accepted, last_accepted
+    else if (w == I + 3) val = two(64, 1);          // max_trace, run_hess
+    else if (w == I + 4) val = two(1, a.dbg);       // run_res, pad
+    o[w] = val;
+  }
+}
+
+// Stand-alone form: callers whose first kernel is not one of the fused sites (multi-rank flow, the occupancy-compact Hessian pass,
+// LI-BA, an empty store, vba_lm_end right after vba_lm_begin, vba_timing_launch_hessian).
+template <int W>
+__global__ __launch_bounds__(256) void k_lm_init(LmInit<W> a) { lm_init_store(a, threadIdx.x, 256); }
+
 __device__ __forceinline__ void so3_exp_dev(const double *w, double *R) {   // tools.hpp:51-66
   const double n = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
   if (n >= 1e-11) {
@@ -327,6 +356,31 @@ __global__ __launch_bounds__(64) void k_lm_update(LmDev *s, const double *__rest
   const double r2 = (nb > 0) ? lm_sum_partials(r2_dev, nb, threadIdx.x) : r2_dev[0];
   if (stop) return;
   lm_update_apply(s, r2, W);
+}
+
+// The fetching vba_lm_end in ONE launch.  Workgroup 0: wave 0 applies the pending accept/reject (upd != 0: the same lm_sum_partials /
+// lm_update_apply as k_lm_update, so the same sums), then the workgroup stores the LmDev image through the host mapping.  The image
+// is RE-READ for that with device-scope loads behind a device-scope fence and the workgroup barrier: the copy then does not depend
+// on this CU's L1 holding what wave 0 has just stored (lm_update_apply reads the lines it then writes).  Workgroups 1 .. : *hess,
+// tile layout -> row-major (6W)^2 (tl_fetch, as k_tiles_to_full) straight into the pinned buffer (h_hess == nullptr: not launched).
+template <int W>
+__global__ __launch_bounds__(256) void k_lm_finish(LmDev *s, const double *__restrict__ r2_dev, int nb, int upd, LmDev *h_lm,
+                                                   const double *__restrict__ red, double *__restrict__ h_hess) {
+  if (blockIdx.x == 0) {
+    if (upd && threadIdx.x < 64) {
+      const int stop = s->stop;
+      const double r2 = lm_sum_partials(r2_dev, nb, threadIdx.x);
+      if (!stop) lm_update_apply(s, r2, W);
+      __threadfence();
+    }
+    __syncthreads();
+    const unsigned long long *src = reinterpret_cast<const unsigned long long *>(s);
+    unsigned long long *dst = reinterpret_cast<unsigned long long *>(h_lm);
+    for (int w = threadIdx.x; w < (int)(sizeof(LmDev) / 8); w += 256) dst[w] = __hip_atomic_load(src + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    constexpr int n = 6 * W;
+    for (int t = (blockIdx.x - 1) * 256 + threadIdx.x; t < n * n; t += (gridDim.x - 1) * 256) h_hess[t] = tl_fetch<W>(red, t / n, t % n);
+  }
 }
 
 }  // namespace vba

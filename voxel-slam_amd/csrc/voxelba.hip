@@ -147,10 +147,9 @@ struct vba_ctx {
   // device-resident LM state (lm_begin / lm_iterate / lm_end)
   LmDev *d_lm = nullptr;
   LmDev *h_lm = nullptr;          // pinned mirror (download side)
-  static const int kLmRing = 8;
-  LmDev *h_lm_up[kLmRing] = {nullptr};   // pinned upload ring: lm_begin never has to drain the stream
-  hipEvent_t lm_up_ev[kLmRing] = {nullptr};
-  int lm_up_next = 0;
+  // vba_lm_begin copies nothing: it leaves the begin poses here and the first LM kernel of the call writes the image (LmInit), or
+  // lm_init_flush does for callers whose first kernel is not a fused site
+  struct { bool pending = false; int dbg = 0; double x[VBA_MAX_WIN_DEV * 12]; } lm_init;
   double *d_raw = nullptr;        // last valid all-reduced [H|g|r] (multi-rank only; single rank reads d_out in place)
   struct { bool active = false; int thd_num = 2; bool have_hess = false; bool pending_update = false; int k4_nb = 0; } lm;   // pending_update: the accept/reject step of the last iteration rides in the next Hessian pass
   int k4part_cap = 0;
@@ -291,9 +290,35 @@ int upload_poses(vba_ctx *c, const double *poses) {
   return VBA_OK;
 }
 
+// The by-value init argument of the LM kernels.  take: consume the context's pending init (the launch that receives the argument
+// writes the LmDev image); otherwise the argument is off.
+template <int W>
+LmInit<W> lm_init_arg(vba_ctx *c, bool take) {
+  LmInit<W> a{};
+  if (take && c->lm_init.pending) {
+    std::memcpy(a.x, c->lm_init.x, sizeof(a.x));
+    a.dst = c->d_lm; a.on = 1; a.dbg = c->lm_init.dbg;
+    c->lm_init.pending = false;
+  }
+  return a;
+}
+// Everything that reads d_lm and is not a fused site calls this first: a pending init becomes a launch of its own.
+int lm_init_flush(vba_ctx *c) {
+  if (!c->lm_init.pending) return VBA_OK;
+  switch (c->opt.win_size) {
+#define VBA_LI_CASE(WW) case WW: hipLaunchKernelGGL(k_lm_init<WW>, dim3(1), dim3(256), 0, c->stream, lm_init_arg<WW>(c, true)); break;
+    VBA_LI_CASE(2) VBA_LI_CASE(3) VBA_LI_CASE(4) VBA_LI_CASE(5) VBA_LI_CASE(6) VBA_LI_CASE(7) VBA_LI_CASE(8) VBA_LI_CASE(9) VBA_LI_CASE(10)
+    VBA_LI_CASE(11) VBA_LI_CASE(12) VBA_LI_CASE(13) VBA_LI_CASE(14) VBA_LI_CASE(15) VBA_LI_CASE(16)
+#undef VBA_LI_CASE
+    default: return VBA_ERR_UNSUPPORTED_WINDOW;
+  }
+  HIPCHK(c, hipGetLastError());
+  return VBA_OK;
+}
+
 template <int W>
 int launch_hessian2_t(vba_ctx *c, const double *poses_dev, const int *gate, int head, int end, int *nblocks_out, LmDev *lm, const double *k4p, int k4nb,
-                      const LiJob &li, size_t li_lds) {
+                      const LiJob &li, size_t li_lds, bool init) {
   using C = HessCfg2<W>;
   const int ntiles = (end - head + C::TV - 1) / C::TV;
   const int maxb = li.dev ? c->max_blocks_hess - 1 : c->max_blocks_hess;      // (the IMU workgroup of LI-BA takes a CU of its own)
@@ -316,7 +341,7 @@ int launch_hessian2_t(vba_ctx *c, const double *poses_dev, const int *gate, int 
   }
   const size_t lds = (li.dev && li_lds > C::LDS_BYTES) ? li_lds : C::LDS_BYTES;
   hipLaunchKernelGGL(k_hessian2<W>, dim3(nb + (li.dev ? 1 : 0)), dim3(C::NT), lds, c->stream, c->fv, poses_dev, head, end, ntiles, c->d_partial, gate, stamps, lm, k4p, k4nb,
-                     nb, li);
+                     nb, li, lm_init_arg<W>(c, init));
   if (want_stamps) {
     std::vector<long long> h((size_t)nb * 16);
     hipStreamSynchronize(c->stream);
@@ -375,10 +400,13 @@ int launch_hessian3_t(vba_ctx *c, const double *poses_dev, const int *gate, int 
   return VBA_OK;
 }
 
+// init: the launch may carry the call's pending LM init (k_hessian2 only: the opt-in occupancy-compact pass takes the stand-alone
+// init kernel in front of it)
 int launch_hessian(vba_ctx *c, const double *pd, const int *gate, int head, int end, int *nb, LmDev *lm = nullptr, const double *k4p = nullptr, int k4nb = 0,
-                   const LiJob &li = LiJob{}, size_t li_lds = 0) {
+                   const LiJob &li = LiJob{}, size_t li_lds = 0, bool init = false) {
   // whole store, W <= 10: the occupancy-compact pass (vba_kernels_h3.hpp); sub-ranges and wider windows: the dense-tile pass
   if (head == 0 && end == c->nvox && c->opt.win_size <= 10 && c->use_h3) {
+    if (init) { const int st = lm_init_flush(c); if (st) return st; }
     switch (c->opt.win_size) {
 #define VBA_H3_CASE(WW) case WW: return launch_hessian3_t<WW>(c, pd, gate, nb, lm, k4p, k4nb, li, li_lds);
       VBA_H3_CASE(2) VBA_H3_CASE(3) VBA_H3_CASE(4) VBA_H3_CASE(5) VBA_H3_CASE(6) VBA_H3_CASE(7) VBA_H3_CASE(8) VBA_H3_CASE(9) VBA_H3_CASE(10)
@@ -386,7 +414,7 @@ int launch_hessian(vba_ctx *c, const double *pd, const int *gate, int head, int 
     }
   }
   switch (c->opt.win_size) {
-#define VBA_H_CASE(WW) case WW: return launch_hessian2_t<WW>(c, pd, gate, head, end, nb, lm, k4p, k4nb, li, li_lds);
+#define VBA_H_CASE(WW) case WW: return launch_hessian2_t<WW>(c, pd, gate, head, end, nb, lm, k4p, k4nb, li, li_lds, init);
     VBA_H_CASE(2) VBA_H_CASE(3) VBA_H_CASE(4) VBA_H_CASE(5) VBA_H_CASE(6) VBA_H_CASE(7) VBA_H_CASE(8) VBA_H_CASE(9) VBA_H_CASE(10)
     VBA_H_CASE(11) VBA_H_CASE(12) VBA_H_CASE(13) VBA_H_CASE(14) VBA_H_CASE(15) VBA_H_CASE(16)
 #undef VBA_H_CASE
@@ -418,7 +446,8 @@ void k4_stamps_dump(vba_ctx *c, int nb, long long *d_st) {
 }
 
 // residual pass over voxels [head, end) (end > head); partials (one per workgroup) go to dst or d_partial; returns their number
-int launch_residual(vba_ctx *c, const double *pd, const int *gate, int head, int end, double *dst = nullptr) {
+// (negative: the stand-alone init of a diagnostic run failed, the context holds the error)
+int launch_residual(vba_ctx *c, const double *pd, const int *gate, int head, int end, double *dst = nullptr, bool init = false) {
   double *part = dst ? dst : c->d_partial;
   const int nb = residual_nb(c, end - head);
   static const bool want_stamps = diag_env("VBA_K4_STAMPS") != nullptr;
@@ -427,10 +456,15 @@ int launch_residual(vba_ctx *c, const double *pd, const int *gate, int head, int
     if (!d_st) hipMalloc((void **)&d_st, 2048 * 4 * 8);
     hipMemsetAsync(d_st, 0, 2048 * 4 * 8, c->stream);
   }
+  if (want_stamps && init) {                // (the diagnostic STAMPS instances carry no init: it becomes a launch of its own)
+    if (lm_init_flush(c)) return -1;
+    init = false;
+  }
   if (residual_vpl(c, end - head)) {
 #define VBA_RESV_CASE(WW) case WW: \
-    if (want_stamps) hipLaunchKernelGGL((k_residual_v<WW, true>), dim3(nb), dim3(64), 0, c->stream, c->fv, pd, head, end, part, gate, d_st); \
-    else hipLaunchKernelGGL((k_residual_v<WW, false>), dim3(nb), dim3(64), 0, c->stream, c->fv, pd, head, end, part, gate, (long long *)nullptr); break;
+    if (want_stamps) hipLaunchKernelGGL((k_residual_v<WW, true>), dim3(nb), dim3(64), 0, c->stream, c->fv, pd, head, end, part, gate, d_st, lm_init_arg<WW>(c, false)); \
+    else if (init && c->lm_init.pending) hipLaunchKernelGGL((k_residual_v<WW, false, true>), dim3(nb), dim3(64), 0, c->stream, c->fv, pd, head, end, part, gate, (long long *)nullptr, lm_init_arg<WW>(c, true)); \
+    else hipLaunchKernelGGL((k_residual_v<WW, false>), dim3(nb), dim3(64), 0, c->stream, c->fv, pd, head, end, part, gate, (long long *)nullptr, lm_init_arg<WW>(c, false)); break;
     switch (c->opt.win_size) {
       VBA_RESV_CASE(2) VBA_RESV_CASE(3) VBA_RESV_CASE(4) VBA_RESV_CASE(5) VBA_RESV_CASE(6) VBA_RESV_CASE(7) VBA_RESV_CASE(8) VBA_RESV_CASE(9) VBA_RESV_CASE(10)
       VBA_RESV_CASE(11) VBA_RESV_CASE(12) VBA_RESV_CASE(13) VBA_RESV_CASE(14) VBA_RESV_CASE(15) VBA_RESV_CASE(16)
@@ -438,8 +472,8 @@ int launch_residual(vba_ctx *c, const double *pd, const int *gate, int head, int
 #undef VBA_RESV_CASE
   } else {
 #define VBA_RES_CASE(WW) case WW: { using RC = ResCfg<WW, VBA_K4_TV>; \
-    if (want_stamps) hipLaunchKernelGGL((k_residual_s<WW, VBA_K4_TV, true>), dim3(nb), dim3(RC::NT), 0, c->stream, c->fv, pd, head, end, part, gate, d_st); \
-    else hipLaunchKernelGGL((k_residual_s<WW, VBA_K4_TV, false>), dim3(nb), dim3(RC::NT), 0, c->stream, c->fv, pd, head, end, part, gate, (long long *)nullptr); break; }
+    if (want_stamps) hipLaunchKernelGGL((k_residual_s<WW, VBA_K4_TV, true>), dim3(nb), dim3(RC::NT), 0, c->stream, c->fv, pd, head, end, part, gate, d_st, lm_init_arg<WW>(c, init)); \
+    else hipLaunchKernelGGL((k_residual_s<WW, VBA_K4_TV, false>), dim3(nb), dim3(RC::NT), 0, c->stream, c->fv, pd, head, end, part, gate, (long long *)nullptr, lm_init_arg<WW>(c, init)); break; }
     switch (c->opt.win_size) {
       VBA_RES_CASE(2) VBA_RES_CASE(3) VBA_RES_CASE(4) VBA_RES_CASE(5) VBA_RES_CASE(6) VBA_RES_CASE(7) VBA_RES_CASE(8) VBA_RES_CASE(9) VBA_RES_CASE(10)
       VBA_RES_CASE(11) VBA_RES_CASE(12) VBA_RES_CASE(13) VBA_RES_CASE(14) VBA_RES_CASE(15) VBA_RES_CASE(16)
@@ -480,15 +514,16 @@ int ctx_allgather(vba_ctx *c, double *buf, size_t chunk) {
 
 // device passes on device-resident poses (gate == nullptr: unconditional)
 int hessian_pass(vba_ctx *c, const double *poses_dev, const int *gate, int head, int end, LmDev *lm = nullptr, const double *k4p = nullptr, int k4nb = 0,
-                 const LiJob &li = LiJob{}, size_t li_lds = 0) {
+                 const LiJob &li = LiJob{}, size_t li_lds = 0, bool init = false) {
   const int W = c->opt.win_size, nout = nout_tl(W);
   if (end <= head) {
+    if (init) { const int st = lm_init_flush(c); if (st) return st; }     // (no kernel to carry it)
     HIPCHK(c, hipMemsetAsync(c->d_out, 0, (size_t)nout * sizeof(double), c->stream));
   } else {
     int nb = 0;
     TimedSpan s1{}, s2{};
     span_begin(c, "hessian", s1);
-    int st = launch_hessian(c, poses_dev, gate, head, end, &nb, lm, k4p, k4nb, li, li_lds);
+    int st = launch_hessian(c, poses_dev, gate, head, end, &nb, lm, k4p, k4nb, li, li_lds, init);
     if (st) return st;
     span_end(c, "hessian", s1);
     span_begin(c, "reduce", s2);
@@ -689,7 +724,6 @@ void vba_destroy(vba_ctx *c) {
   if (c->d_lm) hipFree(c->d_lm);
   if (c->d_raw) hipFree(c->d_raw);
   if (c->h_lm) hipHostFree(c->h_lm);
-  for (int i = 0; i < vba_ctx::kLmRing; i++) { if (c->h_lm_up[i]) hipHostFree(c->h_lm_up[i]); if (c->lm_up_ev[i]) hipEventDestroy(c->lm_up_ev[i]); }
   for (auto &kv : c->spans) for (auto &s : kv.second) { hipEventDestroy(s.a); hipEventDestroy(s.b); }
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
   delete c;
@@ -801,24 +835,11 @@ int vba_factor_occupied_slots(vba_ctx *c, long long *slots) {
 // ---------------------------------------------------------------- Lidar_BA_Optimizer (VM:342-498), device-resident loop
 int vba_lm_begin(vba_ctx *c, const double *poses, int thd_num) {
   const int W = c->opt.win_size;
-  const int slot = c->lm_up_next;
-  c->lm_up_next = (slot + 1) % vba_ctx::kLmRing;
-  if (!c->h_lm_up[slot]) {
-    HIPCHK(c, hipHostMalloc((void **)&c->h_lm_up[slot], sizeof(LmDev), hipHostMallocDefault));
-    HIPCHK(c, hipEventCreateWithFlags(&c->lm_up_ev[slot], hipEventDisableTiming));
-  } else {
-    HIPCHK(c, hipEventSynchronize(c->lm_up_ev[slot]));      // the copy that last used this slot has long completed
-  }
-  LmDev *h = c->h_lm_up[slot];
-  std::memset(h, 0, sizeof(LmDev));
-  std::memcpy(h->x, poses, (size_t)W * 12 * sizeof(double));
-  std::memcpy(h->xt, poses, (size_t)W * 12 * sizeof(double));   // vector<IMUST> x_stats_temp = x_stats  VM:435
-  h->u = 0.01; h->v = 2;                                        // VM:427
-  h->is_calc_hess = 1; h->stop = 0; h->iter = 0; h->n_trace = 0; h->all_accepted = 1; h->last_accepted = 0; h->max_trace = 64;
-  h->run_hess = 1; h->run_res = 1;
-  { const char *e = diag_env("VBA_DEBUG_SOLVE"); h->pad = e ? atoi(e) : 0; }   // ablation / stamp mask of -DVBA_DIAG builds (0 otherwise)
-  HIPCHK(c, hipMemcpyAsync(c->d_lm, h, sizeof(LmDev), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->lm_up_ev[slot], c->stream));
+  // No copy, no host wait: the LmDev image (lm_init_store: x = xt = poses (VM:435), u = 0.01, v = 2 (VM:427), the flags) is written by the
+  // first LM kernel of the call from a by-value argument; a second vba_lm_begin simply replaces a pending init.
+  std::memcpy(c->lm_init.x, poses, (size_t)W * 12 * sizeof(double));
+  { const char *e = diag_env("VBA_DEBUG_SOLVE"); c->lm_init.dbg = e ? atoi(e) : 0; }   // ablation / stamp mask of -DVBA_DIAG builds (0 otherwise)
+  c->lm_init.pending = true;
   c->lm.active = true; c->lm.thd_num = thd_num; c->lm.have_hess = false; c->lm.pending_update = false;
   c->trace.clear();
   // "Too Less Voxel" (VM:399-403) is a statement about the whole window: a sharded rank decides it from the voxel count summed over
@@ -850,7 +871,10 @@ int vba_lm_refresh_eigen(vba_ctx *c) {
   if ((size_t)residual_nb(c, c->nvox) > c->partial_doubles) { c->set_error("partial buffer too small"); return VBA_ERR_CAPACITY; }
   TimedSpan s1{};
   span_begin(c, "residual", s1);
-  launch_residual(c, x_dev, nullptr, 0, c->nvox);
+  // single-rank: the pass carries the call's init when it is the first LM kernel; the multi-rank flow takes the stand-alone init
+  const bool fuse_init = !c->collective();
+  if (!fuse_init) { const int st = lm_init_flush(c); if (st) return st; }
+  if (launch_residual(c, x_dev, nullptr, 0, c->nvox, nullptr, fuse_init) < 0) return VBA_ERR_HIP;
   span_end(c, "residual", s1);
   HIPCHK(c, hipGetLastError());
   return VBA_OK;
@@ -860,7 +884,9 @@ int vba_timing_launch_hessian(vba_ctx *c) {
   if (!c->lm.active || c->nvox <= 0) return VBA_ERR_BAD_ARG;
   const double *x_dev = reinterpret_cast<const double *>(reinterpret_cast<char *>(c->d_lm) + offsetof(LmDev, x));
   int nb = 0;
-  const int st = launch_hessian(c, x_dev, nullptr, 0, c->nvox, &nb);
+  int st = lm_init_flush(c);
+  if (st) return st;
+  st = launch_hessian(c, x_dev, nullptr, 0, c->nvox, &nb);
   if (st) return st;
   HIPCHK(c, hipGetLastError());
   return VBA_OK;
@@ -870,7 +896,7 @@ int vba_timing_launch_hessian(vba_ctx *c) {
 int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
   if (!c->lm.active) return VBA_ERR_BAD_ARG;
   const int W = c->opt.win_size, nout = nout_of(W), V = c->nvox;
-  if (c->nvox_global < c->lm.thd_num) return VBA_ERR_TOO_FEW_VOXELS;   // VM:399-403 (and g_size checks of VM:367); the same on every rank
+  if (c->nvox_global < c->lm.thd_num) { c->lm_init.pending = false; return VBA_ERR_TOO_FEW_VOXELS; }   // VM:399-403 (and g_size checks of VM:367); the same on every rank
   char *base = reinterpret_cast<char *>(c->d_lm);
   const double *x_dev = reinterpret_cast<const double *>(base + offsetof(LmDev, x));
   const double *xt_dev = reinterpret_cast<const double *>(base + offsetof(LmDev, xt));
@@ -883,12 +909,13 @@ int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
   const int copy_raw = c->collective() ? 1 : 0;
   int st = VBA_OK;
   static const bool no_fuse = diag_env("VBA_NO_FUSED_UPDATE") != nullptr;   // diagnostic: accept/reject always as its own kernel
+  if (copy_raw) { st = lm_init_flush(c); if (st) return st; }               // the multi-rank flow takes the stand-alone init
   if (!(copy_raw && c->lm.have_hess)) {
     if (c->lm.pending_update) {               // the previous iteration's accept/reject rides in this pass (runs on xt after an accepted step)
       st = hessian_pass(c, x_dev, run_hess, 0, V, c->d_lm, c->d_k4part, c->lm.k4_nb);
       c->lm.pending_update = false;
     } else {
-      st = hessian_pass(c, x_dev, run_hess, 0, V);   // divide_thread  VM:445 (skipped on device after a reject)
+      st = hessian_pass(c, x_dev, run_hess, 0, V, nullptr, nullptr, 0, LiJob{}, 0, true);   // divide_thread  VM:445 (skipped on device after a reject); the first pass of a call carries its init
     }
   }
   if (st) return st;
@@ -941,22 +968,35 @@ int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
 int vba_lm_end(vba_ctx *c, double *poses, double *hess, double *resis2) {
   if (!c->lm.active) return VBA_ERR_BAD_ARG;
   const int W = c->opt.win_size, n = 6 * W;
-  if (c->lm.pending_update) {                 // the last iteration's accept/reject has no Hessian pass to ride in
+  const bool want = poses || hess || resis2;
+  if (!want && !c->lm.pending_update) { c->lm_init.pending = false; c->lm.active = false; return VBA_OK; }   // (an init nothing consumed is dropped with the call)
+  int st = lm_init_flush(c);                  // vba_lm_end right after vba_lm_begin
+  if (st) return st;
+  if (!want) {                                // nothing requested: no synchronisation; the last iteration's accept/reject has no Hessian pass to ride in
     hipLaunchKernelGGL(k_lm_update, dim3(1), dim3(64), 0, c->stream, c->d_lm, c->d_k4part, c->lm.k4_nb, W);
     c->lm.pending_update = false;
+    c->lm.active = false;
+    return VBA_OK;
   }
-  if (!poses && !hess && !resis2) { c->lm.active = false; return VBA_OK; }    // nothing requested: no synchronisation
-  // One host round trip: the LM state (and *hess) reach the pinned mirrors through kernels that store via the host mapping — a D2H
-  // copy queued behind in-flight kernels completes much later (see li_ba_device), and draining the stream first is a second trip.
-  hipLaunchKernelGGL(k_words_to_host, dim3(4), dim3(256), 0, c->stream, (const int *)c->d_lm, (int *)c->h_lm, (int)(sizeof(LmDev) / 4));
+  // One host round trip and ONE launch (k_lm_finish): the pending accept/reject, then the LM state and *hess reach the pinned mirrors
+  // through stores via the host mapping — a D2H copy queued behind in-flight kernels completes much later (see li_ba_device), and
+  // draining the stream first is a second trip.
+  double *h_hess = nullptr;
   if (hess) {
-    int st = ensure_pin(c, 65536 + (size_t)n * n + 1024);
+    st = ensure_pin(c, 65536 + (size_t)n * n + 1024);
     if (st) return st;
-    const double *src = c->collective() ? c->d_raw : c->d_out;    // *hess = Hess before gauge fixing (VM:446)
-    st = tiles_to_full(c, src);
-    if (st) return st;
-    hipLaunchKernelGGL(k_words_to_host, dim3(16), dim3(256), 0, c->stream, (const int *)c->d_full, (int *)(c->h_pin + 32768), n * n * 2);
+    h_hess = c->h_pin + 32768;
   }
+  const double *src = c->collective() ? c->d_raw : c->d_out;      // *hess = Hess before gauge fixing (VM:446)
+  const int upd = c->lm.pending_update ? 1 : 0;
+  switch (W) {
+#define VBA_FIN_CASE(WW) case WW: hipLaunchKernelGGL(k_lm_finish<WW>, dim3(hess ? 17 : 1), dim3(256), 0, c->stream, c->d_lm, c->d_k4part, upd ? c->lm.k4_nb : 0, upd, c->h_lm, src, h_hess); break;
+    VBA_FIN_CASE(2) VBA_FIN_CASE(3) VBA_FIN_CASE(4) VBA_FIN_CASE(5) VBA_FIN_CASE(6) VBA_FIN_CASE(7) VBA_FIN_CASE(8) VBA_FIN_CASE(9) VBA_FIN_CASE(10)
+    VBA_FIN_CASE(11) VBA_FIN_CASE(12) VBA_FIN_CASE(13) VBA_FIN_CASE(14) VBA_FIN_CASE(15) VBA_FIN_CASE(16)
+#undef VBA_FIN_CASE
+    default: return VBA_ERR_UNSUPPORTED_WINDOW;
+  }
+  c->lm.pending_update = false;
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const LmDev *h = c->h_lm;
@@ -1041,6 +1081,8 @@ static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, i
   std::vector<double> poses((size_t)W * 12);
   states_to_poses(states, W, poses.data());
   int st = vba_lm_begin(c, poses.data(), 0);
+  if (st) return st;
+  st = lm_init_flush(c);                      // the LI-BA kernels read the LM state from their first launch on
   if (st) return st;
   LiDev h{};
   h.W = W; h.n = n; h.nb = nb; h.gravity = gravity ? 1 : 0; h.gauge = gravity ? 6 : DIM; h.F = F; h.imu_coef = c->opt.imu_coef;   // VM:653-656 / 906-909
