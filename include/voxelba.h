@@ -424,7 +424,9 @@ int vba_lm_end(vba_ctx *ctx, double *poses, double *hess, double *resis2);
  *   VBA_SOLVE_DENSE  big_damping_iter's solve (host pivot order, k_bigl_* on the device), n = 6W (W = 2..1024), gauge rows 0..5,
  *                    one candidate.
  * VBA_SOLVE_COPY_RAW launches the multi-rank form of the lidar / LI kernel (system read from the reduced buffer and saved), with
- * VBA_SOLVE_FROM_RAW the form that reads the saved copy after a rejected step.  Non-finite input, a W out of range or an
+ * VBA_SOLVE_FROM_RAW the form that reads the saved copy after a rejected step.  The lidar and LI kernels end the factorisation
+ * with the panel of the last live pivot (behind it lie only decoupled gauge rows, the right-hand-side row and padding; the solution
+ * there is written as 0); VBA_SOLVE_ALL_PANELS runs every panel instead, the two must agree by value.  Non-finite input, a W out of range or an
  * asymmetric H: VBA_ERR_BAD_ARG with nothing launched.  The context's LM state is not touched. */
 #define VBA_SOLVE_LIDAR 0
 #define VBA_SOLVE_LI 1
@@ -434,6 +436,7 @@ int vba_lm_end(vba_ctx *ctx, double *poses, double *hess, double *resis2);
 #define VBA_SOLVE_FROM_RAW 4
 #define VBA_SOLVE_GRAVITY 8
 #define VBA_SOLVE_DENSE_MASK 16
+#define VBA_SOLVE_ALL_PANELS 32
 int vba_debug_solve(vba_ctx *ctx, int kind, int W, int flags, const double *H, const double *g, double u, double v, double *dx, double *q1);
 
 /* ------------------------------------------------------------------------------------------------

@@ -695,7 +695,7 @@ class Context:
         return dict(states=states, imus=imus, hess=H, resis=resis, trace=self.last_trace())
 
     SOLVE_KINDS = {"lidar": 0, "li": 1, "dense": 2}
-    SOLVE_FLAGS = {"e_packed": 1, "copy_raw": 2, "from_raw": 4, "gravity": 8, "dense_mask": 16}
+    SOLVE_FLAGS = {"e_packed": 1, "copy_raw": 2, "from_raw": 4, "gravity": 8, "dense_mask": 16, "all_panels": 32}
 
     def debug_solve(self, kind, W, H, g, u, v=2.0, **flags):
         """vba_debug_solve: one linear solve of the LM loop through the production kernel on the system (H, g) (before the gauge).

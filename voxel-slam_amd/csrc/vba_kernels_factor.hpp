@@ -284,6 +284,17 @@ __device__ __forceinline__ double wave_sum_to_lane63(double x) {
   x += dpp_mov_f64(x, 0.0, 0x143, 0xC);   // row_bcast31 into rows 2 and 3
   return x;
 }
+// Maximum of a non-negative int over the 64 lanes of a wave, result valid in LANE 63 only (the same moves as wave_sum_to_lane63)
+__device__ __forceinline__ int wave_max_to_lane63(int x) {
+  auto mx = [](int a, int b) { return a > b ? a : b; };
+  x = mx(x, __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false));     // quad_perm [1,0,3,2]
+  x = mx(x, __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false));     // quad_perm [2,3,0,1]
+  x = mx(x, __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false));    // row_half_mirror
+  x = mx(x, __builtin_amdgcn_update_dpp(x, x, 0x140, 0xF, 0xF, false));    // row_mirror: every lane of a 16-lane row holds the row's maximum
+  x = mx(x, __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false));    // row_bcast15 into rows 1 and 3 (the others see 0)
+  x = mx(x, __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false));    // row_bcast31 into rows 2 and 3
+  return x;
+}
 
 // Initial LM state of a call (vba_lm_begin), handed BY VALUE to the first kernel the call launches instead of being copied into the
 // LmDev image up front: with `on` set every workgroup takes the poses from x (kernarg segment, nothing is read from the image) and

@@ -259,7 +259,7 @@ __global__ __launch_bounds__(NT) void k_li_solve(LmDev *s, LiDev *li, const doub
     gimu_v = gimu[tid];
     if (!copy_raw && tid < 15 * W) { const int a = tid / 15, lr = tid - 15 * a; glid_v = (lr < 6) ? red[C2::GB + 6 * a + lr] : 0.0; }
   }
-  const int stop = s->stop, calc = s->is_calc_hess, iter0 = s->iter, dbg = sb == 0 ? s->pad : 0, use_spec = s->use_spec;
+  const int stop = s->stop, calc = s->is_calc_hess, iter0 = s->iter, dmask = s->pad, dbg = sb == 0 ? dmask : 0, use_spec = s->use_spec;
   const double u0 = s->u, v0 = s->v, rimu0 = li->rimu[0], rlid0 = copy_raw ? 0.0 : red[C2::RB];
   if (stop || use_spec) return;
   double u = u0;
@@ -339,9 +339,12 @@ __global__ __launch_bounds__(NT) void k_li_solve(LmDev *s, LiDev *li, const doub
   long long *stamps = ((dbg & 16) != 0) ? s->stamps : nullptr;
   if (stamps && tid == 0) stamps[1] = clock64();
   auto live = [&](int kb) -> unsigned { return li_live(kb, W, n, NP); };
-  if constexpr (DENSE_MASK) ldlt_mfma<NP, NT>(Lst, Tp, P, n, elem, stamps, LdltDense());
-  else ldlt_mfma<NP, NT>(Lst, Tp, P, n, elem, stamps, live);
-  if (stamps && tid == 0) stamps[3] = clock64();
+  // the panels from column n on hold only the right-hand-side row and the identity padding: they are not run
+  // (VBA_SOLVE_ALL_PANELS, bit 128 of the diagnostic mask: every panel; vba_debug_solve only)
+  const int ncols = (dmask & 128) ? NP : n;
+  if constexpr (DENSE_MASK) ldlt_mfma<NP, NT>(Lst, Tp, P, n, elem, stamps, LdltDense(), ncols);
+  else ldlt_mfma<NP, NT>(Lst, Tp, P, n, elem, stamps, live, ncols);
+  if (stamps && tid == 0) { stamps[3] = clock64(); stamps[6] = (ncols + 7) / 8 < LC::NBLK ? (ncols + 7) / 8 : LC::NBLK; }
   if (tid < n) xs[tid] = Lst[LC::lat(n, tid)];                                  // z = D^-1 L^-1 P (-g)
   __syncthreads();
   const double x = ldlt_backsub<NP>(Lst, xs, n);

@@ -193,6 +193,20 @@ __global__ __launch_bounds__(256) void k_lm_solve_m(LmDev *s, const double *__re
 #pragma unroll
     for (int h = 0; h < NH; h++) rk[h] += (o > dk[h] || (o == dk[h] && j < lane + 64 * h)) ? 1 : 0;
   }
+  // The last live pivot.  rmax = the largest rank of a row k >= 6: every rank above it belongs to a gauge row (an identity row with a
+  // zero right-hand side, decoupled from every other row: its solution component is exactly 0), and behind those come only the
+  // right-hand-side row and the padding.  The factorisation ends with the panel that holds rmax (ldlt_mfma's ncols), the back
+  // substitution finds zeros in the rows beyond, the components beyond are written as 0.  A zero row is live (a frame without data at
+  // u = 0 ranks behind the gauge rows), so nothing is skipped past it.  Every wave ranks all rows, so every wave holds the same rmax;
+  // integer maximum over the wave by DPP moves (fixed tree, no LDS), read from lane 63.
+  int rmax = 0;
+#pragma unroll
+  for (int h = 0; h < NH; h++) {
+    const int k = lane + 64 * h;
+    rmax = (k >= 6 && k < n && rk[h] > rmax) ? rk[h] : rmax;
+  }
+  rmax = wave_max_to_lane63(rmax);
+  const int npan = __builtin_amdgcn_readlane(rmax, 63) / 8 + 1;
   // scatter the (gauged, damped) system to its permuted position
   int prow[T16], pcol[T16];
 #pragma unroll
@@ -240,9 +254,18 @@ __global__ __launch_bounds__(256) void k_lm_solve_m(LmDev *s, const double *__re
     return img[i >= j ? i * (i + 1) / 2 + j : ZERO];
   };
   if (stamps) stamps[1] = clock64();
-  ldlt_mfma<NP, NT>(Lst, Tp, P, n, elem, ((dbg & 16) && sb == 0) ? s->stamps : nullptr);
-  if (stamps) stamps[3] = clock64();
-  if (tid < n) xs[tid] = Lst[LC::lat(n, tid)];
+  // (VBA_SOLVE_ALL_PANELS, bit 128 of the diagnostic mask: every panel, as before the limit existed; vba_debug_solve only)
+  const int ncols = (dbg & 128) ? NP : 8 * npan, nsol = ncols < n ? ncols : n;
+  ldlt_mfma<NP, NT>(Lst, Tp, P, n, elem, ((dbg & 16) && sb == 0) ? s->stamps : nullptr, LdltDense(), ncols);
+  if (stamps) { stamps[3] = clock64(); stamps[6] = (ncols + 7) / 8 < LC::NBLK ? (ncols + 7) / 8 : LC::NBLK; }
+  // The L blocks of the panels that were not run hold stale image words.  z is not loaded from them (0 beyond nsol), and the words
+  // the back substitution reads there, L[j][i] for nsol <= i < j < n, are set to 0: the rows from nsol on then contribute 0 x 0, as
+  // they do when their panels are run.  (At most six gauge rows lie beyond rmax, so this is one store on a few dozen threads; bounding
+  // the substitution's loops by nsol instead, or masking its loads, cost 1.1-1.9k cycles at n = 60: with n a constant its loops are
+  // unrolled and every load has an immediate offset.)
+  if (tid < n) xs[tid] = tid < nsol ? Lst[LC::lat(n, tid)] : 0.0;
+  for (int kb = (nsol + 7) >> 3; 8 * kb < n; kb++)
+    for (int e = tid; e < (n - 8 * kb) * LC::LS; e += NT) Lst[LC::lst_off(kb) + e] = 0.0;
   __syncthreads();
   const double x = ldlt_backsub<NP>(Lst, xs, n);
   if (stamps) stamps[4] = clock64();

@@ -26,6 +26,11 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
 //     -T = -L D; two MFMAs per live tile apply the rank-8 update C += L (-T)^T;
 //   * two barriers per panel instead of one or two per column.
 // A right-hand side carried as an extra ROW (rhs_row) leaves D^-1 L^-1 b in that row of L.
+// `ncols` (wave-uniform, the same in every wave; default NP) ends the factorisation early: only the panels with 8 kb < ncols are run,
+// and the last of them is followed by neither a trailing update nor the publication of the next panel.  For a caller whose rows of
+// rank >= ncols are decoupled from the rest (identity rows with a zero right-hand side, the right-hand-side row itself, padding) no
+// operation on another row is touched.  The L blocks of the panels that are not run are NOT written: a caller that goes on to
+// ldlt_backsub defines the words it reads there (k_lm_solve_m zeroes them).
 // Zero pivots follow Eigen (ldlt_inplace: a column with |d| == 0 is left unscaled; solve(): |d| <= DBL_MIN gives 0).
 template <int NP>
 struct LdltCfg {
@@ -41,8 +46,9 @@ struct LdltCfg {
 // system passes LdltDense.
 struct LdltDense { __device__ __forceinline__ unsigned operator()(int) const { return ~0u; } };
 template <int NP, int NT, typename F, typename LV = LdltDense>
-__device__ __forceinline__ void ldlt_mfma(double *__restrict__ Lst, double *__restrict__ Tp, double *__restrict__ P, int rhs_row, F elem, long long *stamps = nullptr, LV live = LV()) {
+__device__ __forceinline__ void ldlt_mfma(double *__restrict__ Lst, double *__restrict__ Tp, double *__restrict__ P, int rhs_row, F elem, long long *stamps = nullptr, LV live = LV(), int ncols = NP) {
   using C = LdltCfg<NP>;
+  const int nc = __builtin_amdgcn_readfirstlane(ncols < NP ? ncols : NP);      // every wave takes the same trip count: the loop holds barriers
   constexpr int NW = NT / 64, TPW = (C::NTILES + NW - 1) / NW, LS = C::LS;
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, lr = l >> 4, lc = l & 15;
   // tile t (ordered by tile column descending, then tile row) -> (ti, tj); wave w owns t = w, w + NW, ...
@@ -63,7 +69,7 @@ __device__ __forceinline__ void ldlt_mfma(double *__restrict__ Lst, double *__re
     }
   }
   if (stamps && tid == 0) stamps[2] = clock64();
-  for (int kb = 0; kb < C::NBLK; kb++) {
+  for (int kb = 0; 8 * kb < nc; kb++) {
     const int k0 = 8 * kb;
     double *Lk = Lst + C::lst_off(kb);
     __syncthreads();
@@ -90,6 +96,9 @@ __device__ __forceinline__ void ldlt_mfma(double *__restrict__ Lst, double *__re
       for (int c = 0; c < 8; c++) {
         // pivot c of the diagonal block.  f64 dependent-issue latency is ~40 cycles here, so the recurrence is arranged to keep
         // the chain pivot -> next pivot short: 1/d by v_rcp_f64 and two Newton steps in three levels (e^2 is formed beside y1)
+        // (Forming the next pivot ahead of the lrc broadcasts — in lane c + 1 readlane(lrc, c + 1) is the lane's own lrc — and taking
+        //  the zero-pivot select off the chain were measured: 2972 and 3188 cycles per panel against 2896.  The panel is bound by the
+        //  instructions it issues, not by this chain: an extra fma per pivot costs more than the broadcast it overtakes.)
         const double d = readlane_f64(Dr[c], c);
         const bool ok = fabs(d) > 0.0;
         const double y0 = __builtin_amdgcn_rcp(d);
@@ -115,7 +124,7 @@ __device__ __forceinline__ void ldlt_mfma(double *__restrict__ Lst, double *__re
     __syncthreads();
     if (stamps && tid == 0 && kb < 20) stamps[9 + 2 * kb] = clock64();
     const int kn = k0 + 8;
-    if (kn >= NP) break;
+    if (kn >= nc) break;
     const int tjn = kn >> 4, cb0 = kn & 15;
     const unsigned lm = (unsigned)__builtin_amdgcn_readfirstlane((int)live(kb));
     // operands of every live tile first (unconditional loads on clamped rows: they overlap), then the MFMAs

@@ -1007,8 +1007,9 @@ int vba_lm_end(vba_ctx *c, double *poses, double *hess, double *resis2) {
   if (h->pad & 16) {
     fprintf(stderr, "[k_lm_solve_m cycles] prologue %lld | tile load %lld | factorisation %lld | backsub %lld | epilogue %lld | panels:", h->stamps[1] - h->stamps[0],
             h->stamps[2] - h->stamps[1], h->stamps[3] - h->stamps[2], h->stamps[4] - h->stamps[3], h->stamps[5] - h->stamps[4]);
-    for (int kb = 0; kb < 8; kb++) fprintf(stderr, " %lld+%lld", h->stamps[9 + 2 * kb] - h->stamps[8 + 2 * kb], kb < 7 ? h->stamps[10 + 2 * kb] - h->stamps[9 + 2 * kb] : 0LL);
-    fprintf(stderr, "\n");
+    const int npr = (int)h->stamps[6];             // panels run: the factorisation ends with the panel of the last live pivot
+    for (int kb = 0; kb < npr && kb < 8; kb++) fprintf(stderr, " %lld+%lld", h->stamps[9 + 2 * kb] - h->stamps[8 + 2 * kb], kb < npr - 1 ? h->stamps[10 + 2 * kb] - h->stamps[9 + 2 * kb] : 0LL);
+    fprintf(stderr, " | %d panels run\n", npr);
   }
   c->lm.active = false;
   return VBA_OK;
@@ -1255,8 +1256,9 @@ static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, i
     fprintf(stderr, "[k_li_solve prologue] stage imu %lld | stage lidar %lld | diag+g %lld | rank %lld\n", hl->stamps[50] - hl->stamps[0], hl->stamps[51] - hl->stamps[50], hl->stamps[52] - hl->stamps[51], hl->stamps[1] - hl->stamps[52]);
     fprintf(stderr, "[k_li_solve cycles] prologue %lld | tile load %lld | factorisation %lld | backsub %lld | epilogue %lld | panels:", hl->stamps[1] - hl->stamps[0],
             hl->stamps[2] - hl->stamps[1], hl->stamps[3] - hl->stamps[2], hl->stamps[4] - hl->stamps[3], hl->stamps[5] - hl->stamps[4]);
-    for (int kb = 0; kb < 20; kb++) fprintf(stderr, " %lld+%lld", hl->stamps[9 + 2 * kb] - hl->stamps[8 + 2 * kb], kb < 19 ? hl->stamps[10 + 2 * kb] - hl->stamps[9 + 2 * kb] : 0LL);
-    fprintf(stderr, "\n");
+    const int npr = (int)hl->stamps[6];            // panels run: those from column n on are skipped
+    for (int kb = 0; kb < npr && kb < 20; kb++) fprintf(stderr, " %lld+%lld", hl->stamps[9 + 2 * kb] - hl->stamps[8 + 2 * kb], kb < npr - 1 ? hl->stamps[10 + 2 * kb] - hl->stamps[9 + 2 * kb] : 0LL);
+    fprintf(stderr, " | %d panels run\n", npr);
   }
   if (want_times && (hl->pad & 64)) fprintf(stderr, "[k_li_imu cycles] factor algebra (one lane per factor) %lld | cov^-1 joc %lld | contractions %lld\n", hl->stamps[41] - hl->stamps[40], hl->stamps[42] - hl->stamps[41], hl->stamps[43] - hl->stamps[42]);
   if (want_times && (hl->pad & 32)) { double v[6]; std::memcpy(v, &hl->stamps[58], sizeof(v)); fprintf(stderr, "[li r1 parts] rank %d: rimu %.10g lidar %.10g | %.10g %.10g | %.10g %.10g\n", c->rank, v[0], v[1], v[2], v[3], v[4], v[5]); }
@@ -3857,6 +3859,7 @@ int vba_debug_solve(vba_ctx *c, int kind, int W, int flags, const double *H, con
   std::memset(h, 0, sizeof(LmDev));
   for (int f = 0; f < W; f++) { h->x[12 * f] = h->x[12 * f + 4] = h->x[12 * f + 8] = 1.0; }
   h->u = u; h->v = v;
+  if (flags & VBA_SOLVE_ALL_PANELS) h->pad = 128;   // bit of the diagnostic mask the solve kernels load: run every panel
   double *d_dx = nullptr;
   HIPCHK(c, B.alloc(&d_dx, (size_t)ncand * n));
   int st = VBA_ERR_BAD_ARG;
