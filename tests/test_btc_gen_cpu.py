@@ -25,8 +25,8 @@ def test_float_config_quirks():
 
 
 def test_header_defaults_match_restatement():
-    """vba_btc_default_gen_config in voxelba.hip states the same values as read_parameters here"""
-    src = open(os.path.join(ROOT, "voxel-slam_amd", "csrc", "voxelba.hip")).read()
+    """vba_btc_default_gen_config in vba_btc.hip states the same values as read_parameters here"""
+    src = open(os.path.join(ROOT, "voxel-slam_amd", "csrc", "vba_btc.hip")).read()
     body = src[src.index("int vba_btc_default_gen_config"):]
     body = body[:body.index("return VBA_OK;")]
     for h in (0, 1):

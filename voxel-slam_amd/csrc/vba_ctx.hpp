@@ -1,0 +1,230 @@
+// Private header of libvoxelba.so's translation units ("source layout"): the context, the handle structs that more than one
+// unit reads, and the declarations of the host functions and kernels that one unit defines and another calls.  It defines no kernel.
+#pragma once
+#include "../../include/voxelba.h"
+#include "vba_types.hpp"
+#include "vba_common.hpp"
+#include "vba_btcgen.hpp"
+
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>     // TYPES only: the entry points are resolved at run time (rccl_api in voxelba.hip), the library does not link librccl
+#include <array>
+#include <map>
+#include <string>
+#include <vector>
+
+using namespace vba;
+
+#define HIPCHK(ctx, expr)                                                                        \
+  do {                                                                                           \
+    hipError_t _e = (expr);                                                                      \
+    if (_e != hipSuccess) {                                                                      \
+      (ctx)->set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                       \
+      return VBA_ERR_HIP;                                                                        \
+    }                                                                                            \
+  } while (0)
+
+namespace vba {
+struct TimedSpan { hipEvent_t a, b; };
+}
+
+struct vba_ctx {
+  vba_options opt;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  std::string err;
+
+  // factor store (HBM, SoA)
+  FactorView fv{};
+  int nvox = 0;   // voxels stored
+  int nvox_global = 0;   // the same summed over the ranks (set by vba_lm_begin when the factor store is sharded)
+  int cap = 0;    // capacity = stride
+  double *d_poses = nullptr;     // [W][12]
+  double *d_partial = nullptr;   // workgroup partials
+  size_t partial_doubles = 0;
+  double *d_out = nullptr;       // reduced Hessian pass, tile layout (vba_kernels_factor.hpp)
+  double *d_full = nullptr;      // the same in full layout [H | g | r] for host consumers
+  double *d_scal = nullptr;      // reduced residual scalar
+  double *h_pin = nullptr;       // pinned host staging
+  size_t pin_doubles = 0;
+  void *d_stage = nullptr;       // AoS upload staging
+  size_t stage_bytes = 0;
+
+  // multi-GPU
+  vba_allreduce_fn allreduce = nullptr;
+  void *allreduce_user = nullptr;
+  int rank = 0, n_ranks = 1;
+  bool force_collective = false;  // vba_options::force_collective (rehearsal: run the exchange step with one rank)
+  int max_blocks_hess = 256;      // vba_options::hessian_workgroups
+  int residual_vpl_from = 45000;  // vba_options::residual_vpl_from
+  bool use_h3 = false;            // vba_options::hessian_compact_tiles != 0
+  ncclComm_t comm = nullptr;      // RCCL communicator: the exchange step is issued by the library on the context's stream
+  bool own_comm = false;
+  bool collective_off = false;    // replica phases (bottom-layer HBA windows) run their LM loops without the exchange step
+  bool collective() const { return !collective_off && (allreduce || comm) && (n_ranks > 1 || force_collective); }
+
+  // timing
+  bool timing = false;
+  std::string timing_only;        // when non-empty only this kernel family is bracketed by events
+  int timing_every = 1; unsigned timing_ctr = 0;   // bracket every n-th launch of the selected family
+  int lm_spec = LM_SPEC;          // damping candidates per solve launch
+  std::vector<std::array<double, 450>> covinv_cache; size_t covinv_next = 0;   // li_ba_device: (cov, cov^-1) of recently seen IMU factors
+  std::map<std::string, std::vector<TimedSpan>> spans;
+
+  // device-resident LM state (lm_begin / lm_iterate / lm_end)
+  LmDev *d_lm = nullptr;
+  LmDev *h_lm = nullptr;          // pinned mirror (download side)
+  // vba_lm_begin copies nothing: it leaves the begin poses here and the first LM kernel of the call writes the image (LmInit), or
+  // lm_init_flush does for callers whose first kernel is not a fused site
+  struct { bool pending = false; int dbg = 0; double x[VBA_MAX_WIN_DEV * 12]; } lm_init;
+  double *d_raw = nullptr;        // last valid all-reduced [H|g|r] (multi-rank only; single rank reads d_out in place)
+  struct { bool active = false; int thd_num = 2; bool have_hess = false; bool pending_update = false; int k4_nb = 0; } lm;   // pending_update: the accept/reject step of the last iteration rides in the next Hessian pass
+  int k4part_cap = 0;
+  double *d_k4part = nullptr;     // residual-pass partials of the LM loop (the Hessian pass reuses d_partial while they are still read)   // have_hess: [H|g|r] of the next solve is already reduced (multi-rank)
+  std::vector<double> trace;
+
+  // device-resident LI-BA (vba_kernels_li.hpp)
+  LiDev *d_li = nullptr;
+  double *d_imu = nullptr, *d_himu = nullptr, *d_gimu = nullptr;
+
+  MapStore map;
+  GbaStore gba;
+  BigStore big;                   // arbitrary-window path (top-level global BA)
+  double *d_kdtree[2] = {nullptr, nullptr};   // pl_tree of the initialisation odometry (float-valued xyz), ping-pong for the re-sampling
+  size_t kd_cap = 0; int kd_n = 0, kd_cur = 0;
+  double *d_refpts = nullptr;     // submap cloud staging (HBA_add_edge)
+  size_t refpts_doubles = 0;
+  double *d_lipack = nullptr; size_t lipack_doubles = 0;       // li_ba_device: results gathered for one D2H copy
+  double *d_liscr = nullptr; size_t liscr_doubles = 0;         // k_li_solve at W > 10: staged matrix / L outside the LDS
+  double *d_hba_all = nullptr; size_t hba_all_doubles = 0;   // vba_hba_global: keyframe clouds + submap clouds, kept across calls
+  std::vector<vba_ctx *> hba_workers;                         // vba_hba_global: extra contexts (own stream, own octree) that optimise bottom-layer windows side by side
+  void *d_init = nullptr; size_t init_bytes = 0;            // vba_motion_init: raw clouds (uploaded once per call), blurred rows, pose tables
+  // loop retrieval (vba_btc_*): the query upload, the per-(query, cell) counts and the ICP state are shared by the context's databases
+  char *d_btcq = nullptr, *h_btcq = nullptr; size_t btcq_bytes = 0;
+  int *d_btccnt = nullptr; size_t btccnt_cap = 0;
+  BtcIcpDev *d_icp = nullptr, *h_icp = nullptr;
+  unsigned long long *d_icpkey = nullptr; size_t icpkey_cap = 0;
+  double *d_icppart = nullptr; size_t icppart_cap = 0;
+  // pose-graph optimisation (vba_pgo_optimize): graph structure and per-update work areas, and the dense skeleton system; grow-only
+  char *d_pgo = nullptr; size_t pgo_bytes = 0;
+  double *d_pgoAb = nullptr; size_t pgoAb_bytes = 0;
+  // vba_kf_export_world: the per-keyframe table (pinned upload ring, so that a call need not drain the stream before
+  // it writes the next image, and the device copy) and the staging of host output; grow-only
+  static const int kExpRing = 4;
+  char *h_exp[kExpRing] = {nullptr}; hipEvent_t exp_ev[kExpRing] = {nullptr}; int exp_next = 0;
+  char *d_exp = nullptr; size_t exp_cap = 0;            // keyframes
+  char *d_expout = nullptr; size_t expout_cap = 0;      // records
+  std::vector<long long> exp_first; std::vector<int> exp_kbase;   // host scratch: exported points before every keyframe, keyframes before every store
+
+  void set_error(const std::string &s) { err = s; }
+};
+
+// loop retrieval (vba_btc.hip); the keyframe store writes the generator's point buffer (db->gen->xyz)
+struct vba_btc_db {
+  vba_ctx *ctx = nullptr;
+  vba_btc_config cfg{};
+  int nstd = 0, cap = 0;                     // descriptors stored / capacity (rows)
+  BtcStds d{};
+  std::vector<int> tab;                      // host mirror of the cell table, 8 ints per slot (vba_kernels_btc.hpp)
+  int tab_mask = 0, ncell = 0;
+  int *d_tab = nullptr;
+  int nchunk = 0, chunk_cap = 0;
+  int *d_ent = nullptr, *d_next = nullptr;
+  std::vector<int> off{0}, seq;              // plane clouds: point offsets, header.seq
+  float *d_pc = nullptr; size_t pc_cap = 0;
+  int *d_off = nullptr; int off_cap = 0;
+  int mcap = 0; int *d_m = nullptr;          // match list and per-candidate pair lists: mq | md | mf | pq | pd, mcap each
+  int vcap = 0; int *d_votes = nullptr;
+  int *d_cand = nullptr, *d_total = nullptr; double *d_cres = nullptr, *d_res = nullptr, *h_res = nullptr;
+  bool have_search = false;                  // the last search ran the kernels (n > 0)
+  // descriptor generation (vba_btc_generate_stds): its configuration, device buffers, the AddSTDescs count (current_frame_id_)
+  // and the corners of the last call
+  vba_btc_gen_config gcfg{};
+  BtcGen *gen = nullptr;
+  int n_add = 0;
+  std::vector<double> last_loc; std::vector<uint64_t> last_bits;
+  BtcCfgDev dev_cfg() const {
+    BtcCfgDev f;
+    f.skip_near = cfg.skip_near_num; f.cand_num = cfg.candidate_num; f.rough = cfg.rough_dis_threshold; f.sim = cfg.similarity_threshold;
+    f.icp = cfg.icp_threshold; f.normal = cfg.normal_threshold; f.dis = cfg.dis_threshold;
+    return f;
+  }
+  BtcIndex index() const { BtcIndex ix; ix.tab = d_tab; ix.mask = tab_mask; ix.ent = d_ent; ix.next = d_next; return ix; }
+};
+
+// keyframe store (vba_kf.hip); the loop map reads its clouds and poses
+struct vba_kf_store {
+  vba_ctx *ctx = nullptr;
+  // the keyframes: points (their own frame, float values in doubles) and covariance diagonals, ragged by off
+  double *d_pnt = nullptr; float *d_var = nullptr; size_t cap = 0;
+  std::vector<int> off{0};
+  struct Meta { double x0[12]; int id; double jour; int exist; };
+  std::vector<Meta> kf;
+  // scratch of one merge of up to mcap points: staged host input, merged cloud (also the world points of a load), gathered covariance
+  // diagonals, per-voxel counts, the down-sampler's work area; pinned: gathered diagonals of a host covariance array
+  size_t mcap = 0;
+  double *d_src = nullptr, *d_merge = nullptr, *d_mdiag = nullptr, *h_diag = nullptr;
+  int *d_cnt = nullptr; char *d_ws = nullptr; size_t ws_bytes = 0;
+  // per-scan transforms [tcap][12] and offsets [tcap + 1]: pinned image and device copy; the voxel count of a build (pinned)
+  int tcap = 0; char *h_tab = nullptr, *d_tab = nullptr; int *h_n = nullptr;
+  hipEvent_t ev = nullptr;
+  int allocs = 0; int64_t bytes = 0;
+  int hist = 0; std::vector<float> hist_pos;   // history_kfsize, pl_kdmap
+  int last_m = 0;                              // voxels of the last build (their counts stay in d_cnt)
+};
+
+namespace vba {
+
+// ---------------------------------------------------------------- voxelba.hip
+void span_begin(vba_ctx *c, const char *name, TimedSpan &s);
+void span_end(vba_ctx *c, const char *name, TimedSpan &s);
+int ensure_pin(vba_ctx *c, size_t n);
+int ensure_stage(vba_ctx *c, size_t bytes);
+// the reduction of workgroup partials (vba_kernels_factor.hpp), also behind the odometry's k_odom_match in vba_map.hip
+__global__ __launch_bounds__(256) void k_reduce_partials(const double *__restrict__ partial, int nb, int nout, double *__restrict__ out,
+                                                         const int *__restrict__ gate);
+// the dense LDL^T of vba_kernels_big.hpp, also the skeleton solve of vba_pgo.hip
+__global__ __launch_bounds__(256) void k_bigl_panel(double *__restrict__ Ab, double *__restrict__ Tb, int NP, int ld, int k0);
+__global__ __launch_bounds__(256) void k_bigl_update(double *__restrict__ Ab, const double *__restrict__ Tb, int NP, int ld, int k0);
+__global__ __launch_bounds__(64) void k_bigl_bs_tri(double *__restrict__ Ab, int NP, int ld, int n, int lo);
+__global__ __launch_bounds__(256) void k_bigl_bs_gemv(double *__restrict__ Ab, int NP, int ld, int n, int lo);
+
+// ---------------------------------------------------------------- vba_btc.hip
+int btc_gen_ensure(vba_btc_db *db, int64_t points, int64_t cells, size_t corners);
+int btc_generate_check(vba_btc_db *db, int n, int cap, double *rows, uint64_t *bits, int *n_stds);
+int btc_generate_impl(vba_btc_db *db, int n, const float *xyz, int id, int cap, double *rows, uint64_t *bits, int *n_stds);
+
+// ---------------------------------------------------------------- vba_map.hip (vba_kernels_map.hpp, vba_kernels_loop.hpp)
+void map_init(MapStore &s, const vba_options &o);
+std::vector<DevArr> node_arrays(MapView &v, int W);
+std::vector<DevArr> scan_arrays(MapView &v, int W);
+std::vector<DevArr> fix_arrays(MapView &v);
+int map_read_counters(MapStore &s, hipStream_t st, std::string &err);
+int map_hash_alloc(MapStore &s, unsigned int cap, hipStream_t st, std::string &err);
+int map_base(MapStore &s, hipStream_t st, std::string &err);
+void map_free(MapStore &s);
+bool is_device_ptr(const void *p);
+int map_cut_voxel(MapStore &s, hipStream_t st, int win_count, int n, const double *pnt_body, const double *var, const double *pose,
+                  bool multi, std::string &err, const double *cov6 = nullptr);
+int map_cut_voxel_fix(MapStore &s, hipStream_t st, int n, const double *pnt_world, double jour, std::string &err);
+int map_recut(MapStore &s, hipStream_t st, int win_count, const double *poses, bool multi, std::string &err, int *n_factors);
+int map_extract_factors(MapStore &s, hipStream_t st, FactorView f, std::string &err, int *n_factors);
+int map_margi(MapStore &s, hipStream_t st, int win_count, const double *poses, double jour, FactorView f, int nfac, std::string &err);
+int map_slide(MapStore &s, int mgsize);
+int map_reset(MapStore &s, hipStream_t st, std::string &err);
+int map_num_roots(MapStore &s, hipStream_t st, bool slide);
+int map_stats(MapStore &s, hipStream_t st, long long *out8, std::string &err);
+int map_dump_leaves(MapStore &s, hipStream_t st, double *out, int max_leaves, std::string &err);
+int map_dump_plane_var(MapStore &s, hipStream_t st, double *out, int max_leaves, std::string &err);
+int map_prune(MapStore &s, hipStream_t st, double jour, int dist, std::string &err);
+int map_odom_accumulate(MapStore &s, hipStream_t st, const OdomState &X, int n, const double *d_pts, const double *d_var,
+                        double *d_partial, double *d_out34, double *out34, std::string &err);
+int map_fix_source_ensure(MapStore &s, hipStream_t st, size_t nodes, size_t fix, size_t n, std::string &err);
+int map_cut_voxel_fix_source(MapStore &s, hipStream_t st, int n, const FixSource &src, double jour, std::string &err);
+// fills the map's root table with the empty key, also the hash tables of vba_kernels_big.hpp in voxelba.hip
+__global__ void k_fill_u64(unsigned long long *p, unsigned long long v, size_t n);
+// the one-workgroup exclusive scan of the map's stable compactions, also the match-list offsets of vba_btc.hip
+__global__ __launch_bounds__(1024) void k_det_scan(int *a, int n_max, int *cnt, int which_n, int cap_n, int which_out);
+
+}  // namespace vba

@@ -16,21 +16,10 @@
 #include <cmath>
 #include <string>
 #include <vector>
+#include "vba_types.hpp"
+#include "vba_common.hpp"
 
 namespace vba {
-
-struct BigView {
-  int W, V, E, capV, capE;
-  int *vptr;        // [V + 1]
-  int *efr, *evox;  // [E] frame / voxel of an entry
-  double *ecl;      // [10][capE] body clusters
-  double *gv;       // [18][capE] g1, g2, h of an entry (Hessian pass scratch)
-  double *eval, *evec, *pcr;   // [3][capV], [9][capV], [10][capV]
-  double *poses;    // [W][12]
-  double *H, *g, *r;   // dense (6W)^2, 6W, 1
-  int *eidx;           // [V][W] entry of (voxel, frame) or -1 (k_big_syrk operand staging)
-  double *es;          // [27][capE] diagonal-block remainder E (21 upper) + gradient (6) of an entry, summed per frame by k_big_diag
-};
 
 __device__ __forceinline__ void big_cluster_tf(const double *c, const double *R, double *o) { cluster_transform_dev(c, R, o); }
 
@@ -236,24 +225,6 @@ __global__ __launch_bounds__(256) void k_big_syrk(BigView b, int nt, int nslice)
 }
 
 // ---------------------------------------------------------------- octree build with (node, frame) hashed body clusters
-struct GbaBigView {
-  // roots
-  unsigned long long *hkeys; int *hvals; unsigned int hmask;
-  // nodes
-  int cap, W, npts;
-  double *nadd, *ncenter, *neval, *nevec;
-  float *nql;
-  int *nchild, *nfac, *nexi;
-  signed char *nlayer;
-  // (node, frame) entries
-  unsigned long long *ekeys; unsigned int emask; double *ecl;   // [10][emask + 1]
-  // points
-  double *pw; const double *pl; int *pframe, *pnode;
-  int *perm;                   // points ordered by root voxel (the accumulation pass walks them in this order: see k_gbab_accum)
-  unsigned int *skey; int *sval;   // sort input: root id (all ones = no root) / point index
-  int *cnt; double *poses; int *offsets;
-};
-
 __device__ __forceinline__ int big_frame_of(const int *offsets, int W, int p) {   // largest f with offsets[f] <= p
   int lo = 0, hi = W;
   while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (offsets[mid] <= p) lo = mid; else hi = mid; }
@@ -587,34 +558,6 @@ __global__ void k_bigl_bs_out(const double *__restrict__ Ab, int NP, int ld, int
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dxi[ord[i]] = Ab[(size_t)NP * ld + i];
 }
-
-struct BigStore {
-  int last_cap = 1 << 17;
-  BigView b{};
-  GbaBigView g{};
-  // Device memory comes from an arena of large chunks that survives across builds (reset() rewinds it): hipMalloc / hipFree
-  // of ~40 buffers per build, some of them 10^8 bytes, cost more than the kernels of a top-level window.
-  struct Chunk { char *base; size_t size, used; };
-  std::vector<Chunk> chunks;
-  hipError_t arena(void **p, size_t bytes) {
-    bytes = (bytes ? bytes : 8) + 255 & ~(size_t)255;
-    for (Chunk &ck : chunks)
-      if (ck.size - ck.used >= bytes) { *p = ck.base + ck.used; ck.used += bytes; return hipSuccess; }
-    Chunk ck{nullptr, bytes > ((size_t)256 << 20) ? bytes : ((size_t)256 << 20), 0};
-    hipError_t e = hipMalloc((void **)&ck.base, ck.size);
-    if (e != hipSuccess) return e;
-    ck.used = bytes; *p = ck.base;
-    chunks.push_back(ck);
-    return hipSuccess;
-  }
-  void reset() { for (Chunk &ck : chunks) ck.used = 0; b = BigView(); g = GbaBigView(); }
-  int *h_cnt = nullptr;
-  int *d_vcnt = nullptr, *d_fill = nullptr;
-  double *d_Ab = nullptr, *d_Tb = nullptr; int *d_ord = nullptr;   // dense solver (allocated by big_build)
-  double *d_vec = nullptr;                                          // [3 n + 6 W W]: diag(H) | g copy | dxi | cross-block diagonals
-  int NP = 0, ld = 0;
-  void release() { for (Chunk &ck : chunks) hipFree(ck.base); chunks.clear(); if (h_cnt) hipHostFree(h_cnt); h_cnt = nullptr; b = BigView(); g = GbaBigView(); }
-};
 
 #define BIGCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return VBA_ERR_HIP; } } while (0)
 

@@ -17,7 +17,8 @@
 #include <hip/hip_runtime.h>
 #include "vba_hostmath.hpp"
 #include "vba_ldlt6.hpp"
-#include "vba_eig3.hpp"
+#include "vba_types.hpp"
+#include "vba_common.hpp"
 #include "vba_btc_svd.hpp"
 
 namespace vba {
@@ -26,21 +27,6 @@ constexpr int BTC_CHUNK = 64;        // cell entries per chunk
 constexpr int BTC_MAX_CAND = 256;    // upper bound of candidate_num_
 constexpr int BTC_SAMPLES = 50;      // use_size <= 50 (skip_len = size / 50 + 1)
 constexpr int BTC_RES = 16;          // per-search result doubles: id, score, t[3], R[9], ncand, total matches
-
-struct BtcStds {                     // descriptor rows, SoA (a database, or the uploaded query)
-  double *tri, *cen, *loc;           // [cap][3], [cap][3], [cap][9] (locations of A, B, C)
-  unsigned long long *bits;          // [cap][3]  occupy_array_ of A, B, C as bit masks
-  int *summ;                         // [cap][3]  summary_ of A, B, C
-  int *frame;                        // [cap]     frame_number_
-};
-
-struct BtcIndex {                    // the cell index of a database
-  const int *tab; int mask;          // [mask + 1][8]
-  const int *ent;                    // [chunks][64] descriptor indices
-  const int *next;                   // [chunks]     next chunk of the same cell, -1 = last
-};
-
-struct BtcCfgDev { int skip_near, cand_num; double rough, sim, icp, normal, dis; };
 
 __host__ __device__ inline unsigned btc_hash(int x, int y, int z) {
   return ((unsigned)x * 73856093u) ^ ((unsigned)y * 19349663u) ^ ((unsigned)z * 83492791u);
@@ -331,12 +317,6 @@ __global__ void k_btc_scatter(int n, const int *pairs, int *dst) {
 }
 
 // ------------------------------------------------------------------------------------------------ icp_normal (loop_refine.hpp:47-139)
-struct BtcIcpDev {
-  double R[9], t[3], paras[4];
-  int is_conv, done, iters, pad;
-  double mat[6];            // mat_norm of the last iteration (xx xy xz yy yz zz)
-  double eig[3];
-};
 constexpr int BTC_ICP_PART = 35;   // Hess (21, upper) | JacT (6) | resi | match_num | mat_norm (6)
 
 // 1-NN of every transformed source point within one slice of the target (gridDim.y slices); key per (slice, point)

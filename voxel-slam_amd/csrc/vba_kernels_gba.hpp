@@ -13,30 +13,12 @@
 #include <hip/hip_runtime.h>
 #include <string>
 #include <vector>
+#include "vba_types.hpp"
+#include "vba_common.hpp"
 
 namespace vba {
 
 enum { GCNT_NODES = 0, GCNT_FACTORS, GCNT_OVERFLOW, GCNT_ROOTS, GCNT_N };
-
-struct GbaView {
-  unsigned long long *hkeys; int *hvals; unsigned int hmask;
-  int cap, W, npts;
-  double *nadd;     // [10][cap]     world cluster (pcr_add)
-  double *nlc;      // [10][W][cap]  body clusters per keyframe
-  double *ncenter;  // [3][cap]
-  float *nql;       // [cap]
-  int *nchild, *nfac;
-  signed char *nlayer;
-  double *neval, *nevec;   // [3][cap], [9][cap]
-  double *pw;       // [3][npts] world points
-  const double *pl; // [npts][3] local points (caller's layout)
-  int *pframe, *pnode;
-  int *cnt;
-  double *poses;    // [W][12]
-  int *offsets;     // [W+1]
-};
-
-struct GbaParams { double voxel_size, min_eigen_value, eig_array[4]; int max_layer; };
 
 __global__ void k_gba_keys(GbaView g, GbaParams P) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -266,22 +248,6 @@ __global__ void k_gba_to_ref(int n, int W, const int *__restrict__ offsets, cons
 }
 
 // ---------------------------------------------------------------- host side
-struct GbaStore {
-  GbaView v{};
-  int cap_pts = 0, cap_hash = 0;
-  double *d_pl = nullptr;      // device copy of the local points [n][3]
-  int *h_cnt = nullptr;        // pinned
-  std::vector<void *> node_bufs;
-
-  void free_nodes() { for (void *p : node_bufs) hipFree(p); node_bufs.clear(); v.cap = 0; }
-  void free_all() {
-    free_nodes();
-    hipFree(v.hkeys); hipFree(v.hvals); hipFree(v.pw); hipFree(v.pframe); hipFree(v.pnode); hipFree(d_pl); hipFree(v.cnt); hipFree(v.poses); hipFree(v.offsets);
-    if (h_cnt) hipHostFree(h_cnt);
-    *this = GbaStore();
-  }
-};
-
 #define GBACHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return VBA_ERR_HIP; } } while (0)
 
 inline int gba_alloc_nodes(GbaStore &s, int cap, int W, std::string &err) {

@@ -5,17 +5,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "vba_common.hpp"
 #include "vba_kernels_scan.hpp"
 
 namespace vba {
-
-// q = ((T[0] x + T[1] y) + T[2] z) + T[9], ... with T = [dR row-major (9), dp (3)]
-__device__ __forceinline__ void kf_apply(const double *__restrict__ T, double x, double y, double z, double &qx, double &qy, double &qz) {
-#pragma clang fp contract(off)
-  qx = ((T[0] * x + T[1] * y) + T[2] * z) + T[9];
-  qy = ((T[3] * x + T[4] * y) + T[5] * z) + T[10];
-  qz = ((T[6] * x + T[7] * y) + T[8] * z) + T[11];
-}
 
 // Merge: point i of the concatenated input belongs to scan j with off[j] <= i < off[j + 1] and moves by xf[j] ([k][12]).
 //   out   double [n][3]  the merged cloud (down-sampler input), may be nullptr

@@ -5,11 +5,11 @@
 // kernels test on entry.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "vba_types.hpp"
 #include "vba_ldlt.hpp"
 
 namespace vba {
 
-constexpr int LM_SPEC = 4;           // damping candidates solved per launch of the solve kernel (one workgroup each)
 
 struct LmDev {
   double x[VBA_MAX_WIN_DEV * 12];    // x_stats       (accepted poses)

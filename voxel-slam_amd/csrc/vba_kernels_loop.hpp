@@ -11,7 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "vba_kernels_kf.hpp"
+#include "vba_common.hpp"
 #include "vba_kernels_map.hpp"
 
 namespace vba {
@@ -40,16 +40,6 @@ __global__ __launch_bounds__(256) void k_loop_gather(MapView m, int base, int n,
   srcrow[i] = row;
 }
 
-// a fixed insertion whose points and covariances are in HBM already
-struct FixSource {
-  int nseg = 0;
-  const int4 *d_seg = nullptr;        // [nseg] device
-  const double *d_poses = nullptr;    // [.][12] device
-  const double *d_pnt = nullptr;      // source rows [.][3]
-  int cov_kind = FIXCOV_ZERO;          // FIXCOV_* of vba_kernels_map.hpp (not FIXCOV_KEEP: the pool tail is not zeroed here)
-  const void *d_cov = nullptr;        // float [.][3] diagonals (VS:2614-2621) or double [.][9] rows, taken over unrotated (VS:1341-1344)
-};
-
 // bytes of the map's staging buffer one insertion of n points needs: world points, source rows and the seven per-point temporaries
 // of the insert kernels.  The temporaries live here, not in the map's [max_pts] arrays: those are sized for ONE scan and come in
 // [W] rows, and an expanded keyframe sequence is 10-40 scans long.
@@ -69,7 +59,7 @@ inline int map_sort_reserve_n(MapStore &s, hipStream_t st, size_t n, std::string
 }
 
 // room for an insertion of n fixed points on top of what the map holds (counters current): nodes, pool, root table, staging, sort
-inline int map_fix_source_ensure(MapStore &s, hipStream_t st, size_t nodes, size_t fix, size_t n, std::string &err) {
+int map_fix_source_ensure(MapStore &s, hipStream_t st, size_t nodes, size_t fix, size_t n, std::string &err) {
   int r = map_ensure(s, st, nodes, 0, fix, err);
   if (r) return r;
   if (2 * ((size_t)s.ub_used + n) > (size_t)s.hcap) {       // as map_ensure keeps the table under ~50 % load, for n possible new roots
@@ -86,7 +76,7 @@ inline int map_fix_source_ensure(MapStore &s, hipStream_t st, size_t nodes, size
 
 // map_cut_voxel_fix for a FixSource: n = points of the expanded sequence.  Same kernels after the staging, same single counter
 // read-back at the end; k_fix_to_soa does not run (k_loop_gather writes the pool tail itself).
-inline int map_cut_voxel_fix_source(MapStore &s, hipStream_t st, int n, const FixSource &src, double jour, std::string &err) {
+int map_cut_voxel_fix_source(MapStore &s, hipStream_t st, int n, const FixSource &src, double jour, std::string &err) {
   if (n < 0 || (n > 0 && (!src.d_pnt || !src.d_seg || !src.d_poses || src.nseg < 1)) || src.cov_kind == FIXCOV_KEEP || (src.cov_kind != FIXCOV_ZERO && !src.d_cov)) return VBA_ERR_BAD_ARG;
   if (n == 0) return VBA_OK;
   int r = map_base(s, st, err);

@@ -16,39 +16,10 @@
 #include <vector>
 #include <functional>
 #include "../../include/voxelba.h"
-#include "vba_kernels_factor.hpp"
+#include "vba_types.hpp"
+#include "vba_common.hpp"
 
 namespace vba {
-
-// vba_sort.hip (rocPRIM): stable radix sort of (key, value) pairs on key bits [0, end_bit); tmp == nullptr queries tmp_bytes
-hipError_t sort_pairs_u32(void *tmp, size_t &tmp_bytes, const unsigned int *keys_in, unsigned int *keys_out, const int *vals_in, int *vals_out,
-                          size_t n, unsigned int end_bit, hipStream_t stream);
-
-// 16-bit bucket of a root voxel key; ranks own contiguous bucket ranges
-__host__ __device__ inline uint64_t shard_bucket(int64_t kx, int64_t ky, int64_t kz) {
-  uint64_t h = (uint64_t)kx * 0x9E3779B97F4A7C15ull;
-  h ^= (uint64_t)ky * 0xC2B2AE3D27D4EB4Full + (h << 6) + (h >> 2);
-  h ^= (uint64_t)kz * 0x165667B19E3779F9ull + (h << 6) + (h >> 2);
-  h ^= h >> 29; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 32;
-  return h & 0xFFFFull;
-}
-
-static constexpr unsigned long long KEY_EMPTY = ~0ull;
-static constexpr unsigned long long KEY_TOMB = ~0ull - 1;   // erased root (map pruning): probes walk past it
-static constexpr int KEY_BITS = 21, KEY_OFF = 1 << 20;
-
-__host__ __device__ inline unsigned long long pack_key(long long kx, long long ky, long long kz) {
-  return ((unsigned long long)(kx + KEY_OFF) << 42) | ((unsigned long long)(ky + KEY_OFF) << 21) | (unsigned long long)(kz + KEY_OFF);
-}
-__host__ __device__ inline void unpack_key(unsigned long long k, long long &kx, long long &ky, long long &kz) {
-  kx = (long long)((k >> 42) & 0x1FFFFF) - KEY_OFF; ky = (long long)((k >> 21) & 0x1FFFFF) - KEY_OFF; kz = (long long)(k & 0x1FFFFF) - KEY_OFF;
-}
-// The reference's key quirk VM:1907-1918: float narrowing, -1 if negative, truncation toward zero.
-__host__ __device__ inline long long key_axis(double pw, double voxel_size) {
-  float loc = (float)(pw / voxel_size);
-  if (loc < 0) loc -= 1.0f;
-  return (long long)loc;
-}
 
 // CNT_USED = hash slots that are not EMPTY (live roots + tombstones); CNT_FREE_ROOTS / CNT_FREE_BLOCKS = depth of the two
 // free-node stacks that map pruning fills and node creation drains
@@ -60,60 +31,6 @@ enum { CNT_NODES = 0, CNT_FIX, CNT_SLIDE, CNT_OVERFLOW, CNT_TOUCH, CNT_ROOTS, CN
        CNT_DBG0, CNT_DBG1, CNT_DBG2, CNT_DBG3, // diagnostics build only (-DVBA_DIAG)
        CNT_SLIDE_G, CNT_TOUCH_G,   // the two counts the reference's 'fewer voxels than threads' quirks test, summed over the ranks when the map is sharded
        CNT_N };
-
-struct MapParams {
-  int W, max_layer, max_points, thread_num;
-  double voxel_size, min_eigen_value;
-  double plane_thre[4], min_point[4];
-  int mp[VBA_MAX_WIN];
-  int rank, n_ranks;
-};
-
-struct MapView {
-  // hash table of roots
-  unsigned long long *hkeys; int *hvals; unsigned int hmask;
-  // nodes
-  int cap;
-  unsigned long long *nkey; int *nroot; int *nparent; int *nchild; int *npath; int *nopt; int *nflist /* factor index -> leaf (tras_opt order) */; int *nfl2 /* the same before the occupancy sort */; unsigned int *nfkey; int *fhist /* [EXTRACT_NB_MAX] */; int *nlast; int *nstamp; int *nsplit; int *ntake; int *nclear; int *ndead;
-  int *nfree_root, *nfree_blk;   // stacks of recycled node ids: single root nodes / bases of 8-node child blocks (map_prune)
-  int *ndet, *dblk;              // deterministic mode: [cap] split flags of a recut level / [cap] per-workgroup counts of a compaction
-  unsigned int *hfirst;          // deterministic mode: [hash cap] smallest index of an input point of a root created by the current insert
-  int *nseg_a, *nseg_b;          // [W][cap]: the points a scan slot gave to a leaf AT INSERTION = perm[slot][nseg_a .. nseg_b) (scan order)
-  int *ncnt;                     // [cap] points of the scan being inserted per leaf, then the scatter cursor; zero between inserts
-  int *nsl;                      // [cap] leaves split by the current recut level (margi: leaves whose oldest frame joins the fixed points)
-  int *nfb_head, *nfb_tail;      // [cap] a leaf's fixed points (point_fix) arrive in BLOCKS of consecutive pool entries; the blocks are chained in arrival order
-  signed char *nlayer; signed char *nstate;
-  unsigned char *f_exist, *f_sw, *f_plane, *f_touched; int *f_slide;
-  float *nql; double *ncenter; double *njour;
-  double *nadd, *nfix, *ncov, *neval, *nevec, *nplane, *nlc;
-  // scan ring
-  int max_pts;
-  double *px;   // [W][max_pts][3]  (AoS: the per-leaf kernels gather whole points by index)
-  double *pvar; // [W][max_pts][9]
-  int *pnode;   // [W][max_pts]
-  int *phash;   // [max_pts] temp
-  int *newslots;  // [max_pts] temp
-  int *perm;    // [W][max_pts] point indices of a slot grouped by insertion leaf, scan order inside a group
-  // the slot's points IN THAT ORDER (what sw->points[mord] of the leaves hold in the reference): the passes that walk a leaf's points again
-  // (subdivide, the move of the oldest frame to point_fix) stream them instead of chasing perm -> point
-  double *sx;   // [3][W][max_pts]
-  double *svar; // [9][W][max_pts]
-  int *pleaf;   // [W][max_pts] the leaf that holds the point NOW (-1: none / released)
-  unsigned int *skey_a, *skey_b;   // [max_pts] sort keys (leaf id) in / out
-  int *sval_a;  // [max_pts] sort values in (the point index)
-  int *wl;      // [max_pts] leaves that received points of the scan being inserted
-  int *wlb;     // [max_pts] those with more than 64 points
-  int4 *wl4;    // [max_pts] work list entries (leaf, segment start, points, -) for the per-leaf kernels: one 16-byte load
-  // fixed-point pool
-  int cap_fix;
-  double *fx;   // [cap_fix][3]  (AoS, as the window points: a leaf's block is one contiguous run)
-  double *fvar; // [cap_fix][9]
-  int *fnode;
-  int *fb_base, *fb_len, *fb_next;   // [cap_fix] block table of the pool (a block has >= 1 point)
-  int *sval_b;  // [max_pts] sort values out where the destination is not a slot's perm (fixed-point insertion)
-  int *cnt;     // counters [CNT_N]
-  double *poses;  // [W][12]
-};
 
 // ------------------------------------------------------------------------------------------------ helpers
 // ------------------------------------------------------------------------------------------------ order-preserving accumulation
@@ -212,18 +129,6 @@ __device__ __forceinline__ int alloc_nodes(const MapView &m, int which_cnt, cons
 // popcount in lane order, wave totals in LDS).  Owners are ranked by the index they are launched over (point index, node id).
 constexpr unsigned int DET_NONE = 0x7F7F7F7Fu;   // hfirst of a slot that no insert is creating a root in (a byte fill)
 
-// rank of a flagged thread among the flagged threads of its 256-thread workgroup (lane order) and the workgroup's count.  Every
-// thread of the workgroup must call it (it synchronises).
-__device__ __forceinline__ int det_wg_rank(bool f, int *wsum, int &tot) {
-  const unsigned long long mask = __ballot(f);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) wsum[wave] = __popcll(mask);
-  __syncthreads();
-  int before = 0;
-  tot = 0;
-  for (int w = 0; w < 4; w++) { const int c = wsum[w]; before += w < wave ? c : 0; tot += c; }
-  return before + __popcll(mask & ((1ull << lane) - 1ull));
-}
 __device__ __forceinline__ void det_count(bool f, int *wsum, int *blk) {
   int tot;
   det_wg_rank(f, wsum, tot);
@@ -762,7 +667,6 @@ __device__ __forceinline__ void fix_chain_append(const MapView &m, int leaf, int
 // (vba_map_cut_voxel_fix: no covariance argument).  Otherwise the entry's row is written here, in pool (= group) order, from row
 // srcrow[p] of `cov`: float [.][3] diagonals widened to double, double [.][9] rows as they are, or zeros.  The 72-byte rows go out
 // through LDS so that consecutive lanes store consecutive doubles.
-enum { FIXCOV_KEEP = 0, FIXCOV_DIAG_F32 = 1, FIXCOV_FULL_F64 = 2, FIXCOV_ZERO = 3 };
 template <int COV>
 __global__ __launch_bounds__(64) void k_fix_accum_ord(MapView m, MapParams P, int base, int n, const double *__restrict__ pts, const int *__restrict__ srcrow,
                                                       const void *__restrict__ cov) {
@@ -1329,10 +1233,6 @@ __global__ __launch_bounds__(256) void k_extract_write(MapView m, MapParams P, F
 }
 
 // ------------------------------------------------------------------------------------------------ K5: marginalise
-__device__ __forceinline__ void cluster_transform_dev(const double *c /*10*/, const double *R /*12*/, double *o /*10*/) {
-  const Cl10 w = cluster_transform_exact(c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], R);   // the reference's operation order
-  o[0] = w.p00; o[1] = w.p10; o[2] = w.p20; o[3] = w.p11; o[4] = w.p21; o[5] = w.p22; o[6] = w.v0; o[7] = w.v1; o[8] = w.v2; o[9] = w.n;
-}
 
 // plane_update VM:1344-1388.  nplane layout: center(3) normal(3) radius(1) plane_var(36 row-major)
 // Everything is unrolled onto registers (the caller is launched with 256-thread bounds): the first version indexed its local
@@ -1712,8 +1612,6 @@ __global__ void k_prune_fix(MapView m) {
 // (read-only probe), octant descent, the two 3-sigma gates, then the weighted normal equations
 //   HTH (6x6 sym, 21) | HTz (6) | nnt (3x3 sym, 6) | match_num   = 34 sums per workgroup.
 // The reference's per-point cache octos[i] (voxelslam.cpp:1020) only short-cuts the lookup; the full lookup is done here.
-struct OdomState { double R[9], t[3], rot_var[9], tsl_var[9]; };
-
 __global__ __launch_bounds__(256) void k_odom_match(MapView m, MapParams P, OdomState X, int n, const double *__restrict__ pts,
                                                     const double *__restrict__ var, double *__restrict__ partial) {
   __shared__ double red[4][34];
@@ -1885,52 +1783,6 @@ __global__ void k_rehash(const unsigned long long *okeys, const int *ovals, unsi
     h = (h + 1) & nmask;
   }
 }
-// var_init (voxelslam.hpp:210-234) = calcBodyVar (voxelslam.hpp:180-200) + extrinsic: one thread per point.
-// DEG2RAD is PCL's macro ((x) * 0.017453293), see oracle/map_oracle.hpp.
-__global__ void k_var_init(int n, const double *__restrict__ pin, double *__restrict__ pout, double *__restrict__ var, const double *__restrict__ ext,
-                           float range_inc, float degree_inc) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n) return;
-  double x = pin[3 * (size_t)p], y = pin[3 * (size_t)p + 1], z = pin[3 * (size_t)p + 2];
-  if (z == 0) z = 0.0001;
-  const float range = (float)sqrt(x * x + y * y + z * z);
-  const float range_var = range_inc * range_inc;
-  const double sn = sin((degree_inc) * 0.017453293), dv = sn * sn;
-  const double nrm = sqrt(x * x + y * y + z * z);
-  const double d0 = x / nrm, d1 = y / nrm, d2 = z / nrm;
-  double b1x = 1, b1y = 1, b1z = -(d0 + d1) / d2;
-  const double n1 = sqrt(b1x * b1x + b1y * b1y + b1z * b1z);
-  b1x /= n1; b1y /= n1; b1z /= n1;
-  double b2x = b1y * d2 - b1z * d1, b2y = b1z * d0 - b1x * d2, b2z = b1x * d1 - b1y * d0;   // b1 x direction
-  const double n2 = sqrt(b2x * b2x + b2y * b2y + b2z * b2z);
-  b2x /= n2; b2y /= n2; b2z /= n2;
-  // A = range * hat(direction) * [b1 b2]
-  const double r = (double)range;
-  const double a1x = r * (d1 * b1z - d2 * b1y), a1y = r * (d2 * b1x - d0 * b1z), a1z = r * (d0 * b1y - d1 * b1x);
-  const double a2x = r * (d1 * b2z - d2 * b2y), a2y = r * (d2 * b2x - d0 * b2z), a2z = r * (d0 * b2y - d1 * b2x);
-  const double rv = (double)range_var;
-  const double d[3] = {d0, d1, d2}, a1[3] = {a1x, a1y, a1z}, a2[3] = {a2x, a2y, a2z};
-  double vb[9];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) vb[3 * i + j] = d[i] * rv * d[j] + (a1[i] * dv * a1[j] + a2[i] * dv * a2[j]);
-  // extrinsic: pnt = R p + t ; var = R var R^T
-  const double *R = ext;
-  pout[3 * (size_t)p] = R[0] * x + R[1] * y + R[2] * z + R[9];
-  pout[3 * (size_t)p + 1] = R[3] * x + R[4] * y + R[5] * z + R[10];
-  pout[3 * (size_t)p + 2] = R[6] * x + R[7] * y + R[8] * z + R[11];
-  double RV[9];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) RV[3 * i + j] = R[3 * i] * vb[j] + R[3 * i + 1] * vb[3 + j] + R[3 * i + 2] * vb[6 + j];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) var[9 * (size_t)p + 3 * i + j] = RV[3 * i] * R[3 * j] + RV[3 * i + 1] * R[3 * j + 1] + RV[3 * i + 2] * R[3 * j + 2];
-}
-
 // pvec_update (voxelslam.hpp:242-265) fused into the staging of a scan: var_world = R var R^T + phat rot_var phat^T + tsl_var
 // (pw = R p + t is recomputed by the insert kernels).  cov6 = [rot_var(9) | tsl_var(9)].
 __global__ __launch_bounds__(256) void k_scan_to_soa_pvec_update(MapView m, int W, int slot, int n, const double *pts, const double *var, const double *pose, const double *cov6) {
@@ -2002,40 +1854,8 @@ __global__ void k_recut_prep(int *cnt, int first, int last) {
   if (last) cnt[CNT_FACTORS] = 0;
 }
 __global__ void k_copy_counter(int *cnt, int from, int to) { cnt[to] = cnt[from]; }
-struct DevArr {  // a [rows][cap] device array that can grow its cap keeping [rows][used]
-  void **slot; size_t elem, rows;
-};
 
-struct MapStore {
-  vba_options opt;
-  int rank = 0, n_ranks = 1;
-  MapView v{};
-  bool allocated = false;
-  bool have_var = false;
-  int mp[VBA_MAX_WIN];
-  int npts[VBA_MAX_WIN];
-  int epoch = 1, stamp = 1;
-  unsigned int hcap = 0;
-  int *h_cnt = nullptr;    // pinned
-  // Inserts are enqueued without reading the counters back: the host keeps pessimistic upper bounds (every point may
-  // create a root) and re-reads the true counters only when a bound would exceed a capacity.
-  long long ub_nodes = 0, ub_roots = 0, ub_used = 0;   // ub_used: hash slots that are not EMPTY (live roots + tombstones)
-  bool cnt_stale = false;
-  double *h_pose_ring = nullptr; hipEvent_t pose_ev[8] = {nullptr}; int pose_next = 0;
-  void *d_stage = nullptr; size_t stage_bytes = 0;
-  void *d_sort_tmp = nullptr; size_t sort_tmp_bytes = 0; int sort_tmp_for = 0;   // rocPRIM scratch, sized for max_pts pairs
-  // sharded map: SUM all-reduce of n doubles in HBM over the ranks, stream-ordered (set by the context); d_gc = its 2-double scratch
-  std::function<int(double *, size_t)> allreduce;
-  double *d_gc = nullptr;
-  // per-call plane thresholds (vba_motion_init's relaxed values, VS:624-630): when set they replace opt's in every MapParams
-  bool thr_override = false;
-  double ovr_min_eigen_value = 0.0, ovr_plane_thre[4] = {0.0, 0.0, 0.0, 0.0};
-  // deterministic mode (vba_options::deterministic); d_whist = the per-workgroup bucket histograms of the stable sort
-  bool det = false;
-  int *d_whist = nullptr; size_t whist_cap = 0;
-};
-
-inline void map_init(MapStore &s, const vba_options &o) {
+void map_init(MapStore &s, const vba_options &o) {
   s.opt = o;
   s.det = o.deterministic != 0;
   for (int i = 0; i < VBA_MAX_WIN; i++) { s.mp[i] = i; s.npts[i] = 0; }   // VS:3158-3160
@@ -2061,7 +1881,7 @@ inline MapParams map_params(const MapStore &s) {
   return P;
 }
 
-inline std::vector<DevArr> node_arrays(MapView &v, int W) {
+std::vector<DevArr> node_arrays(MapView &v, int W) {
   return {
       {(void **)&v.nkey, 8, 1}, {(void **)&v.nroot, 4, 1}, {(void **)&v.nparent, 4, 1}, {(void **)&v.nchild, 4, 1}, {(void **)&v.npath, 4, 1},
       {(void **)&v.nopt, 4, 1}, {(void **)&v.nflist, 4, 1}, {(void **)&v.nfl2, 4, 1}, {(void **)&v.nfkey, 4, 1}, {(void **)&v.nlast, 4, 1}, {(void **)&v.nstamp, 4, 1}, {(void **)&v.nsplit, 4, 1}, {(void **)&v.ntake, 4, 1},
@@ -2072,11 +1892,11 @@ inline std::vector<DevArr> node_arrays(MapView &v, int W) {
       {(void **)&v.neval, 24, 1}, {(void **)&v.nevec, 72, 1}, {(void **)&v.nplane, 8, 43}, {(void **)&v.nlc, (size_t)80 * W, 1},
   };
 }
-inline std::vector<DevArr> scan_arrays(MapView &v, int W) {
+std::vector<DevArr> scan_arrays(MapView &v, int W) {
   return {{(void **)&v.px, 24, (size_t)W}, {(void **)&v.pvar, 72, (size_t)W}, {(void **)&v.pnode, 4, (size_t)W}, {(void **)&v.phash, 4, 1}, {(void **)&v.newslots, 4, 1},
           {(void **)&v.perm, 4, (size_t)W}, {(void **)&v.sx, 24, (size_t)W}, {(void **)&v.svar, 72, (size_t)W}, {(void **)&v.pleaf, 4, (size_t)W}, {(void **)&v.skey_a, 4, 1}, {(void **)&v.skey_b, 4, 1}, {(void **)&v.sval_a, 4, 1}, {(void **)&v.sval_b, 4, 1}, {(void **)&v.wl, 4, 1}, {(void **)&v.wlb, 4, 1}, {(void **)&v.wl4, 16, 1}};
 }
-inline std::vector<DevArr> fix_arrays(MapView &v) {
+std::vector<DevArr> fix_arrays(MapView &v) {
   return {{(void **)&v.fx, 24, 1}, {(void **)&v.fvar, 72, 1}, {(void **)&v.fnode, 4, 1}, {(void **)&v.fb_base, 4, 1}, {(void **)&v.fb_len, 4, 1}, {(void **)&v.fb_next, 4, 1}};
 }
 
@@ -2100,7 +1920,7 @@ inline int grow_arrays(std::vector<DevArr> arrs, size_t oldcap, size_t newcap, s
 __global__ void k_words_to_host(const int *__restrict__ src, int *__restrict__ dst, int n) {
   for (int i = threadIdx.x + blockIdx.x * blockDim.x; i < n; i += blockDim.x * gridDim.x) dst[i] = src[i];
 }
-inline int map_read_counters(MapStore &s, hipStream_t st, std::string &err) {
+int map_read_counters(MapStore &s, hipStream_t st, std::string &err) {
   hipLaunchKernelGGL(k_words_to_host, dim3(1), dim3(64), 0, st, s.v.cnt, s.h_cnt, (int)CNT_N);
   MAPCHK(hipGetLastError());
   MAPCHK(hipStreamSynchronize(st));
@@ -2108,7 +1928,7 @@ inline int map_read_counters(MapStore &s, hipStream_t st, std::string &err) {
   return VBA_OK;
 }
 
-inline int map_hash_alloc(MapStore &s, unsigned int cap, hipStream_t st, std::string &err) {
+int map_hash_alloc(MapStore &s, unsigned int cap, hipStream_t st, std::string &err) {
   unsigned long long *nk = nullptr; int *nv = nullptr;
   MAPCHK(hipMalloc((void **)&nk, (size_t)cap * 8));
   MAPCHK(hipMalloc((void **)&nv, (size_t)cap * 4));
@@ -2132,7 +1952,7 @@ inline int map_hash_alloc(MapStore &s, unsigned int cap, hipStream_t st, std::st
   return VBA_OK;
 }
 
-inline int map_base(MapStore &s, hipStream_t st, std::string &err) {
+int map_base(MapStore &s, hipStream_t st, std::string &err) {
   if (s.allocated) return VBA_OK;
   MAPCHK(hipMalloc((void **)&s.v.cnt, CNT_N * sizeof(int)));
   MAPCHK(hipMalloc((void **)&s.v.fhist, (size_t)EXTRACT_NB_MAX * sizeof(int)));
@@ -2199,7 +2019,7 @@ inline int map_ensure(MapStore &s, hipStream_t st, size_t need_nodes, size_t nee
   return VBA_OK;
 }
 
-inline void map_free(MapStore &s) {
+void map_free(MapStore &s) {
   if (!s.allocated) return;
   const int W = s.opt.win_size;
   for (auto &a : node_arrays(s.v, W)) if (*a.slot) hipFree(*a.slot);
@@ -2222,7 +2042,7 @@ inline void map_free(MapStore &s) {
   s.allocated = false;
 }
 
-inline bool is_device_ptr(const void *p) {
+bool is_device_ptr(const void *p) {
   hipPointerAttribute_t a;
   if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
   return a.type == hipMemoryTypeDevice;
@@ -2290,8 +2110,8 @@ inline void map_ins_roots(MapStore &s, hipStream_t st, const MapParams &P, int s
 }
 
 // cut_voxel / cut_voxel_multi for one scan
-inline int map_cut_voxel(MapStore &s, hipStream_t st, int win_count, int n, const double *pnt_body, const double *var, const double *pose,
-                         bool multi, std::string &err, const double *cov6 = nullptr) {
+int map_cut_voxel(MapStore &s, hipStream_t st, int win_count, int n, const double *pnt_body, const double *var, const double *pose,
+                  bool multi, std::string &err, const double *cov6) {
   const int W = s.opt.win_size;
   if (win_count < 0 || win_count >= W || n < 0 || !pose || (n > 0 && !pnt_body)) return VBA_ERR_BAD_ARG;
   int r = map_base(s, st, err);
@@ -2373,7 +2193,7 @@ inline int map_cut_voxel(MapStore &s, hipStream_t st, int win_count, int n, cons
   return VBA_OK;
 }
 
-inline int map_cut_voxel_fix(MapStore &s, hipStream_t st, int n, const double *pnt_world, double jour, std::string &err) {
+int map_cut_voxel_fix(MapStore &s, hipStream_t st, int n, const double *pnt_world, double jour, std::string &err) {
   if (n < 0 || (n > 0 && !pnt_world)) return VBA_ERR_BAD_ARG;
   if (n == 0) return VBA_OK;
   int r = map_base(s, st, err);
@@ -2412,7 +2232,7 @@ inline int map_cut_voxel_fix(MapStore &s, hipStream_t st, int n, const double *p
 }
 
 // recut over the scope + factor index assignment; *n_factors = number of planar leaves selected by tras_opt
-inline int map_recut(MapStore &s, hipStream_t st, int win_count, const double *poses, bool multi, std::string &err, int *n_factors) {
+int map_recut(MapStore &s, hipStream_t st, int win_count, const double *poses, bool multi, std::string &err, int *n_factors) {
   const int W = s.opt.win_size;
   *n_factors = 0;
   if (win_count < 0 || win_count > W || !poses) return VBA_ERR_BAD_ARG;
@@ -2484,7 +2304,7 @@ inline int map_recut(MapStore &s, hipStream_t st, int win_count, const double *p
   return VBA_OK;
 }
 
-inline int map_extract_factors(MapStore &s, hipStream_t st, FactorView f, std::string &err, int *n_factors) {
+int map_extract_factors(MapStore &s, hipStream_t st, FactorView f, std::string &err, int *n_factors) {
   *n_factors = 0;
   if (!s.allocated) return VBA_OK;
   const MapParams P = map_params(s);
@@ -2517,7 +2337,7 @@ inline int map_extract_factors(MapStore &s, hipStream_t st, FactorView f, std::s
   return VBA_OK;
 }
 
-inline int map_margi(MapStore &s, hipStream_t st, int win_count, const double *poses, double jour, FactorView f, int nfac, std::string &err) {
+int map_margi(MapStore &s, hipStream_t st, int win_count, const double *poses, double jour, FactorView f, int nfac, std::string &err) {
   const int W = s.opt.win_size;
   if (win_count < 1 || win_count > W || !poses) return VBA_ERR_BAD_ARG;
   if (!s.allocated) return VBA_OK;
@@ -2556,14 +2376,14 @@ inline int map_margi(MapStore &s, hipStream_t st, int win_count, const double *p
   return VBA_OK;
 }
 
-inline int map_slide(MapStore &s, int mgsize) {   // VS:2014-2019
+int map_slide(MapStore &s, int mgsize) {   // VS:2014-2019
   const int W = s.opt.win_size;
   if (mgsize < 0 || mgsize > W) return VBA_ERR_BAD_ARG;
   for (int i = 0; i < W; i++) { s.mp[i] += mgsize; if (s.mp[i] >= W) s.mp[i] -= W; }
   return VBA_OK;
 }
 
-inline int map_reset(MapStore &s, hipStream_t st, std::string &err) {
+int map_reset(MapStore &s, hipStream_t st, std::string &err) {
   if (!s.allocated) return VBA_OK;
   const int W = s.opt.win_size;
   hipStreamSynchronize(st);
@@ -2582,7 +2402,7 @@ inline int map_reset(MapStore &s, hipStream_t st, std::string &err) {
   return VBA_OK;
 }
 
-inline int map_num_roots(MapStore &s, hipStream_t st, bool slide) {
+int map_num_roots(MapStore &s, hipStream_t st, bool slide) {
   if (!s.allocated) return 0;
   std::string err;
   if (map_read_counters(s, st, err)) return -1;
@@ -2591,7 +2411,7 @@ inline int map_num_roots(MapStore &s, hipStream_t st, bool slide) {
 
 // storage statistics: [node high-water mark, free root nodes, free child blocks, hash capacity, hash slots in use (roots +
 // tombstones), roots, sliding-map roots, fixed points]
-inline int map_stats(MapStore &s, hipStream_t st, long long *out8, std::string &err) {
+int map_stats(MapStore &s, hipStream_t st, long long *out8, std::string &err) {
   for (int k = 0; k < 8; k++) out8[k] = 0;
   if (!s.allocated) return VBA_OK;
   int r = map_read_counters(s, st, err);
@@ -2601,7 +2421,7 @@ inline int map_stats(MapStore &s, hipStream_t st, long long *out8, std::string &
   return VBA_OK;
 }
 
-inline int map_dump_leaves(MapStore &s, hipStream_t st, double *out, int max_leaves, std::string &err) {
+int map_dump_leaves(MapStore &s, hipStream_t st, double *out, int max_leaves, std::string &err) {
   if (!s.allocated) return 0;
   if (map_read_counters(s, st, err)) return -1;
   const int nn = s.h_cnt[CNT_NODES] < s.v.cap ? s.h_cnt[CNT_NODES] : s.v.cap;
@@ -2626,7 +2446,7 @@ inline int map_dump_leaves(MapStore &s, hipStream_t st, double *out, int max_lea
   return n;
 }
 
-inline int map_dump_plane_var(MapStore &s, hipStream_t st, double *out, int max_leaves, std::string &err) {
+int map_dump_plane_var(MapStore &s, hipStream_t st, double *out, int max_leaves, std::string &err) {
   if (!s.allocated) return 0;
   if (map_read_counters(s, st, err)) return -1;
   const int nn = s.h_cnt[CNT_NODES] < s.v.cap ? s.h_cnt[CNT_NODES] : s.v.cap;
@@ -2651,7 +2471,7 @@ inline int map_dump_plane_var(MapStore &s, hipStream_t st, double *out, int max_
   return n;
 }
 
-inline int map_prune(MapStore &s, hipStream_t st, double jour, int dist, std::string &err) {
+int map_prune(MapStore &s, hipStream_t st, double jour, int dist, std::string &err) {
   if (!s.allocated) return VBA_OK;
   int r = map_read_counters(s, st, err);
   if (r) return r;
@@ -2678,8 +2498,8 @@ inline int map_prune(MapStore &s, hipStream_t st, double jour, int dist, std::st
 }
 
 // One scan-to-map accumulation: out34 (host) = [HTH upper (21) | HTz (6) | nnt upper (6) | match_num]
-inline int map_odom_accumulate(MapStore &s, hipStream_t st, const OdomState &X, int n, const double *d_pts, const double *d_var,
-                               double *d_partial, double *d_out34, double *out34, std::string &err) {
+int map_odom_accumulate(MapStore &s, hipStream_t st, const OdomState &X, int n, const double *d_pts, const double *d_var,
+                        double *d_partial, double *d_out34, double *out34, std::string &err) {
   if (!s.allocated) { for (int k = 0; k < 34; k++) out34[k] = 0.0; return VBA_OK; }
   const MapParams P = map_params(s);
   const int nb = (n + 255) / 256;

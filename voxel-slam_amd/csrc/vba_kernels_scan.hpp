@@ -5,16 +5,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "vba_types.hpp"
 
 namespace vba {
 
-struct DsSlot {
-  unsigned long long key;      // packed voxel index, DS_EMPTY when free
-  double sx, sy, sz;
-  double vx, vy, vz;           // down_sampling_pvec: sums of the covariance diagonals
-  unsigned long long mind;     // down_sampling_close: smallest squared distance to the centroid (bits of a non-negative double)
-  int cnt, first, best, pad;
-};
 static constexpr unsigned long long DS_EMPTY = ~0ull;
 
 // TL:210-217 on PCL float coordinates; dbl != 0: the pointVar form of VM:45-51 (double coordinates)
@@ -202,6 +196,52 @@ __device__ __forceinline__ void undist_one(const double *__restrict__ q, const d
   x = (double)(float)(Rx[0] * g[0] + Rx[3] * g[1] + Rx[6] * g[2]);                                            // Lid_rot_to_IMU^T * (...)
   y = (double)(float)(Rx[1] * g[0] + Rx[4] * g[1] + Rx[7] * g[2]);
   z = (double)(float)(Rx[2] * g[0] + Rx[5] * g[1] + Rx[8] * g[2]);
+}
+
+// var_init (voxelslam.hpp:210-234) = calcBodyVar (voxelslam.hpp:180-200) + extrinsic: one thread per point.
+// DEG2RAD is PCL's macro ((x) * 0.017453293), see oracle/map_oracle.hpp.
+__global__ void k_var_init(int n, const double *__restrict__ pin, double *__restrict__ pout, double *__restrict__ var, const double *__restrict__ ext,
+                           float range_inc, float degree_inc) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  double x = pin[3 * (size_t)p], y = pin[3 * (size_t)p + 1], z = pin[3 * (size_t)p + 2];
+  if (z == 0) z = 0.0001;
+  const float range = (float)sqrt(x * x + y * y + z * z);
+  const float range_var = range_inc * range_inc;
+  const double sn = sin((degree_inc) * 0.017453293), dv = sn * sn;
+  const double nrm = sqrt(x * x + y * y + z * z);
+  const double d0 = x / nrm, d1 = y / nrm, d2 = z / nrm;
+  double b1x = 1, b1y = 1, b1z = -(d0 + d1) / d2;
+  const double n1 = sqrt(b1x * b1x + b1y * b1y + b1z * b1z);
+  b1x /= n1; b1y /= n1; b1z /= n1;
+  double b2x = b1y * d2 - b1z * d1, b2y = b1z * d0 - b1x * d2, b2z = b1x * d1 - b1y * d0;   // b1 x direction
+  const double n2 = sqrt(b2x * b2x + b2y * b2y + b2z * b2z);
+  b2x /= n2; b2y /= n2; b2z /= n2;
+  // A = range * hat(direction) * [b1 b2]
+  const double r = (double)range;
+  const double a1x = r * (d1 * b1z - d2 * b1y), a1y = r * (d2 * b1x - d0 * b1z), a1z = r * (d0 * b1y - d1 * b1x);
+  const double a2x = r * (d1 * b2z - d2 * b2y), a2y = r * (d2 * b2x - d0 * b2z), a2z = r * (d0 * b2y - d1 * b2x);
+  const double rv = (double)range_var;
+  const double d[3] = {d0, d1, d2}, a1[3] = {a1x, a1y, a1z}, a2[3] = {a2x, a2y, a2z};
+  double vb[9];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) vb[3 * i + j] = d[i] * rv * d[j] + (a1[i] * dv * a1[j] + a2[i] * dv * a2[j]);
+  // extrinsic: pnt = R p + t ; var = R var R^T
+  const double *R = ext;
+  pout[3 * (size_t)p] = R[0] * x + R[1] * y + R[2] * z + R[9];
+  pout[3 * (size_t)p + 1] = R[3] * x + R[4] * y + R[5] * z + R[10];
+  pout[3 * (size_t)p + 2] = R[6] * x + R[7] * y + R[8] * z + R[11];
+  double RV[9];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) RV[3 * i + j] = R[3 * i] * vb[j] + R[3 * i + 1] * vb[3 + j] + R[3 * i + 2] * vb[6 + j];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) var[9 * (size_t)p + 3 * i + j] = RV[3 * i] * R[3 * j] + RV[3 * i + 1] * R[3 * j + 1] + RV[3 * i + 2] * R[3 * j + 2];
 }
 
 // Points are time-sorted (voxelslam.hpp:92-95), so the backwards walk of EK:138-163 assigns point i to the last pose with

@@ -1,23 +1,16 @@
-// libvoxelba.so — implementation of include/voxelba.h for MI355X (gfx950).
+// libvoxelba.so — implementation of include/voxelba.h for MI355X (gfx950): the BA core.  The map, the scan pre-processing and keyframe
+// store, the loop map, loop retrieval, pose-graph optimisation and the session formats are units of their own ("source layout").
 // Host side: context / HBM store management, the three LM drivers (voxel_map.hpp:342-976) and the IMU factor;
-// device side: the kernels in vba_kernels_factor.hpp / vba_kernels_map.hpp.  No CPU compute fallback exists.
-#include "../../include/voxelba.h"
-
-#define VBA_MAX_WIN_DEV VBA_MAX_WIN
+// device side: the kernels in vba_kernels_factor.hpp and the headers included below.  No CPU compute fallback exists.
+#include "vba_ctx.hpp"
 #include "vba_kernels_factor.hpp"
 #include "vba_kernels_h3.hpp"
-#include "vba_kernels_map.hpp"
 #include "vba_kernels_lm.hpp"
 #include "vba_kernels_li.hpp"
-#include "vba_kernels_scan.hpp"
 #include "vba_kernels_gba.hpp"
 #include "vba_kernels_big.hpp"
-#include "vba_kernels_pgo.hpp"
 #include "vba_kernels_kd.hpp"
 #include "vba_kernels_init.hpp"
-#include "vba_kernels_btc.hpp"
-#include "vba_btcgen.hpp"
-#include "vba_io.hpp"
 #include <cstddef>
 #include "vba_hostmath.hpp"
 
@@ -40,17 +33,7 @@
 
 using namespace vba;
 
-#define HIPCHK(ctx, expr)                                                                        \
-  do {                                                                                           \
-    hipError_t _e = (expr);                                                                      \
-    if (_e != hipSuccess) {                                                                      \
-      (ctx)->set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                       \
-      return VBA_ERR_HIP;                                                                        \
-    }                                                                                            \
-  } while (0)
-
 namespace {
-struct TimedSpan { hipEvent_t a, b; };
 
 // RCCL entry points, resolved on first use: the copy the process has ALREADY loaded wins (a host program that imported torch carries
 // torch/lib/librccl.so; binding to a second build would split the communicator state), then the system librccl.so.1.  A process
@@ -100,98 +83,6 @@ inline const char *diag_env(const char *name) {
 }
 }
 
-struct vba_ctx {
-  vba_options opt;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  std::string err;
-
-  // factor store (HBM, SoA)
-  FactorView fv{};
-  int nvox = 0;   // voxels stored
-  int nvox_global = 0;   // the same summed over the ranks (set by vba_lm_begin when the factor store is sharded)
-  int cap = 0;    // capacity = stride
-  double *d_poses = nullptr;     // [W][12]
-  double *d_partial = nullptr;   // workgroup partials
-  size_t partial_doubles = 0;
-  double *d_out = nullptr;       // reduced Hessian pass, tile layout (vba_kernels_factor.hpp)
-  double *d_full = nullptr;      // the same in full layout [H | g | r] for host consumers
-  double *d_scal = nullptr;      // reduced residual scalar
-  double *h_pin = nullptr;       // pinned host staging
-  size_t pin_doubles = 0;
-  void *d_stage = nullptr;       // AoS upload staging
-  size_t stage_bytes = 0;
-
-  // multi-GPU
-  vba_allreduce_fn allreduce = nullptr;
-  void *allreduce_user = nullptr;
-  int rank = 0, n_ranks = 1;
-  bool force_collective = false;  // vba_options::force_collective (rehearsal: run the exchange step with one rank)
-  int max_blocks_hess = 256;      // vba_options::hessian_workgroups
-  int residual_vpl_from = 45000;  // vba_options::residual_vpl_from
-  bool use_h3 = false;            // vba_options::hessian_compact_tiles != 0
-  ncclComm_t comm = nullptr;      // RCCL communicator: the exchange step is issued by the library on the context's stream
-  bool own_comm = false;
-  bool collective_off = false;    // replica phases (bottom-layer HBA windows) run their LM loops without the exchange step
-  bool collective() const { return !collective_off && (allreduce || comm) && (n_ranks > 1 || force_collective); }
-
-  // timing
-  bool timing = false;
-  std::string timing_only;        // when non-empty only this kernel family is bracketed by events
-  int timing_every = 1; unsigned timing_ctr = 0;   // bracket every n-th launch of the selected family
-  int lm_spec = LM_SPEC;          // damping candidates per solve launch
-  std::vector<std::array<double, 450>> covinv_cache; size_t covinv_next = 0;   // li_ba_device: (cov, cov^-1) of recently seen IMU factors
-  std::map<std::string, std::vector<TimedSpan>> spans;
-
-  // device-resident LM state (lm_begin / lm_iterate / lm_end)
-  LmDev *d_lm = nullptr;
-  LmDev *h_lm = nullptr;          // pinned mirror (download side)
-  // vba_lm_begin copies nothing: it leaves the begin poses here and the first LM kernel of the call writes the image (LmInit), or
-  // lm_init_flush does for callers whose first kernel is not a fused site
-  struct { bool pending = false; int dbg = 0; double x[VBA_MAX_WIN_DEV * 12]; } lm_init;
-  double *d_raw = nullptr;        // last valid all-reduced [H|g|r] (multi-rank only; single rank reads d_out in place)
-  struct { bool active = false; int thd_num = 2; bool have_hess = false; bool pending_update = false; int k4_nb = 0; } lm;   // pending_update: the accept/reject step of the last iteration rides in the next Hessian pass
-  int k4part_cap = 0;
-  double *d_k4part = nullptr;     // residual-pass partials of the LM loop (the Hessian pass reuses d_partial while they are still read)   // have_hess: [H|g|r] of the next solve is already reduced (multi-rank)
-  std::vector<double> trace;
-
-  // device-resident LI-BA (vba_kernels_li.hpp)
-  LiDev *d_li = nullptr;
-  double *d_imu = nullptr, *d_himu = nullptr, *d_gimu = nullptr;
-
-  MapStore map;
-  GbaStore gba;
-  BigStore big;                   // arbitrary-window path (top-level global BA)
-  double *d_kdtree[2] = {nullptr, nullptr};   // pl_tree of the initialisation odometry (float-valued xyz), ping-pong for the re-sampling
-  size_t kd_cap = 0; int kd_n = 0, kd_cur = 0;
-  double *d_refpts = nullptr;     // submap cloud staging (HBA_add_edge)
-  size_t refpts_doubles = 0;
-  double *d_lipack = nullptr; size_t lipack_doubles = 0;       // li_ba_device: results gathered for one D2H copy
-  double *d_liscr = nullptr; size_t liscr_doubles = 0;         // k_li_solve at W > 10: staged matrix / L outside the LDS
-  double *d_hba_all = nullptr; size_t hba_all_doubles = 0;   // vba_hba_global: keyframe clouds + submap clouds, kept across calls
-  std::vector<vba_ctx *> hba_workers;                         // vba_hba_global: extra contexts (own stream, own octree) that optimise bottom-layer windows side by side
-  void *d_init = nullptr; size_t init_bytes = 0;            // vba_motion_init: raw clouds (uploaded once per call), blurred rows, pose tables
-  // loop retrieval (vba_btc_*): the query upload, the per-(query, cell) counts and the ICP state are shared by the context's databases
-  char *d_btcq = nullptr, *h_btcq = nullptr; size_t btcq_bytes = 0;
-  int *d_btccnt = nullptr; size_t btccnt_cap = 0;
-  BtcIcpDev *d_icp = nullptr, *h_icp = nullptr;
-  unsigned long long *d_icpkey = nullptr; size_t icpkey_cap = 0;
-  double *d_icppart = nullptr; size_t icppart_cap = 0;
-  // pose-graph optimisation (vba_pgo_optimize): graph structure and per-update work areas, and the dense skeleton system; grow-only
-  char *d_pgo = nullptr; size_t pgo_bytes = 0;
-  double *d_pgoAb = nullptr; size_t pgoAb_bytes = 0;
-  // vba_kf_export_world: the per-keyframe table (pinned upload ring, so that a call need not drain the stream before
-  // it writes the next image, and the device copy) and the staging of host output; grow-only
-  static const int kExpRing = 4;
-  char *h_exp[kExpRing] = {nullptr}; hipEvent_t exp_ev[kExpRing] = {nullptr}; int exp_next = 0;
-  char *d_exp = nullptr; size_t exp_cap = 0;            // keyframes
-  char *d_expout = nullptr; size_t expout_cap = 0;      // records
-  std::vector<long long> exp_first; std::vector<int> exp_kbase;   // host scratch: exported points before every keyframe, keyframes before every store
-
-  void set_error(const std::string &s) { err = s; }
-};
-
 namespace {
 
 // damping candidates per solve launch (vba_kernels_lm.hpp, "Speculative damping"); 1 = the plain sequential solve.  Read when a
@@ -206,6 +97,9 @@ int nout_tl(int W) {                                      // tile layout produce
 }
 
 static inline bool span_on(vba_ctx *c, const char *name) { return c->timing && (c->timing_only.empty() || c->timing_only == name); }
+}  // namespace
+
+namespace vba {
 void span_begin(vba_ctx *c, const char *name, TimedSpan &s) {
   s.a = s.b = nullptr;
   if (!span_on(c, name)) return;
@@ -235,6 +129,9 @@ int ensure_stage(vba_ctx *c, size_t bytes) {
   c->stage_bytes = bytes;
   return VBA_OK;
 }
+}  // namespace vba
+
+namespace {
 
 // (re)allocate the SoA factor store with stride newcap, preserving the first nvox voxels
 int factor_reserve(vba_ctx *c, int need) {
@@ -1987,160 +1884,6 @@ int vba_map_pvec_update_cut_voxel(vba_ctx *c, int win_count, int n, const double
   span_end(c, "insert", s);
   return st;
 }
-int vba_scan_var_init(vba_ctx *c, int n, const double *pnt_in, const double *ext_pose, double dept_err, double beam_err, double *pnt_out,
-                      double *var_out) {
-  if (n < 0 || (n > 0 && (!pnt_in || !pnt_out || !var_out)) || !ext_pose) return VBA_ERR_BAD_ARG;
-  if (n == 0) return VBA_OK;
-  int st = ensure_stage(c, ((size_t)n * 15 + 16) * sizeof(double));
-  if (st) return st;
-  double *d_in = (double *)c->d_stage, *d_out = d_in + (size_t)n * 3, *d_var = d_out + (size_t)n * 3, *d_ext = d_var + (size_t)n * 9;
-  HIPCHK(c, hipMemcpyAsync(d_in, pnt_in, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_ext, ext_pose, 12 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_var_init, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, d_in, d_out, d_var, d_ext, (float)dept_err, (float)beam_err);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(pnt_out, d_out, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
-  HIPCHK(c, hipMemcpyAsync(var_out, d_var, (size_t)n * 9 * sizeof(double), hipMemcpyDefault, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return VBA_OK;
-}
-// The device half of the down-samplers: everything between the input and the emit, on buffers the caller owns.
-//   tab [cap] slots (cap a power of two >= 2n), slot [n], blk [(n + 255) / 256], n_out [1]; dist [n] for mode 2;
-//   deterministic mode: skey / idx / sidx [n] and rocPRIM scratch tmp (sort_pairs_u32 over n keys of key_bits bits).
-// After it the table holds every voxel's sums, count and first point, blk the exclusive scan of the per-block voxel counts and
-// *n_out the number of voxels: what k_ds_emit (and the keyframe store's k_kf_emit) compact in first-occurrence order.
-struct DsWork {
-  DsSlot *tab = nullptr; int cap = 0; unsigned int key_bits = 0;
-  int *slot = nullptr, *blk = nullptr, *n_out = nullptr; double *dist = nullptr;
-  unsigned int *skey = nullptr; int *idx = nullptr, *sidx = nullptr; void *tmp = nullptr; size_t tmp_bytes = 0;
-};
-static int ds_core(vba_ctx *c, hipStream_t stream, int mode, int n, const double *d_in, const double *d_var, int vrow, int vstep, double voxel_size,
-                   bool det, const DsWork &w) {
-  const int nb = (n + 255) / 256;
-  hipLaunchKernelGGL(k_ds_clear, dim3((w.cap + 255) / 256), dim3(256), 0, stream, w.tab, w.cap);
-  if (det) {
-    hipLaunchKernelGGL(k_ds_insert<true>, dim3(nb), dim3(256), 0, stream, n, d_in, d_var, voxel_size, w.tab, w.cap - 1, w.slot, vrow, vstep);
-    hipLaunchKernelGGL(k_iota, dim3(nb), dim3(256), 0, stream, w.idx, n);
-    size_t tmp = w.tmp_bytes;
-    HIPCHK(c, sort_pairs_u32(w.tmp, tmp, (const unsigned int *)w.slot, w.skey, w.idx, w.sidx, (size_t)n, w.key_bits, stream));
-    hipLaunchKernelGGL(k_ds_segstart, dim3(nb), dim3(256), 0, stream, n, w.skey, w.tab);
-    hipLaunchKernelGGL(k_ds_sum_det, dim3(nb), dim3(256), 0, stream, n, d_in, d_var, w.sidx, w.tab, w.slot, vrow, vstep);
-  } else {
-    hipLaunchKernelGGL(k_ds_insert<false>, dim3(nb), dim3(256), 0, stream, n, d_in, d_var, voxel_size, w.tab, w.cap - 1, w.slot, vrow, vstep);
-  }
-  if (mode == 2) {
-    hipLaunchKernelGGL(k_ds_close_min, dim3(nb), dim3(256), 0, stream, n, d_in, w.tab, w.slot, w.dist);
-    hipLaunchKernelGGL(k_ds_close_arg, dim3(nb), dim3(256), 0, stream, n, w.tab, w.slot, w.dist);
-  }
-  hipLaunchKernelGGL(k_ds_count, dim3(nb), dim3(256), 0, stream, n, w.tab, w.slot, w.blk);
-  hipLaunchKernelGGL(k_ds_scan, dim3(1), dim3(256), 0, stream, nb, w.blk, w.n_out);
-  return VBA_OK;
-}
-// mode 0 down_sampling_voxel, 1 down_sampling_pvec (var in, vout out), 2 down_sampling_close (first_out = chosen indices)
-static int ds_common(vba_ctx *c, int mode, int n, const double *pnt, const double *var, double voxel_size, double *pnt_out, double *vout, int *count_out,
-                     int *first_out, int *n_out) {
-  if (n < 0 || !n_out || (n > 0 && (!pnt || !first_out)) || (mode != 2 && n > 0 && (!pnt_out || !count_out)) || (mode == 1 && n > 0 && (!var || !vout)))
-    return VBA_ERR_BAD_ARG;
-  *n_out = 0;
-  if (n == 0) return VBA_OK;
-  if (voxel_size < 0.001 && mode != 1) {                                // TL:203 / TL:242: the cloud is left untouched
-    if (pnt_out) HIPCHK(c, hipMemcpyAsync(pnt_out, pnt, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
-    std::vector<int> z(n, 0), id(n);
-    for (int i = 0; i < n; i++) id[i] = i;
-    if (count_out) HIPCHK(c, hipMemcpyAsync(count_out, z.data(), (size_t)n * sizeof(int), hipMemcpyDefault, c->stream));
-    HIPCHK(c, hipMemcpyAsync(first_out, id.data(), (size_t)n * sizeof(int), hipMemcpyDefault, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *n_out = n;
-    return VBA_OK;
-  }
-  int cap = 1024;
-  while (cap < 2 * n) cap <<= 1;
-  const int nb = (n + 255) / 256;
-  const bool det = c->opt.deterministic != 0;
-  unsigned int key_bits = 1;
-  while ((1u << key_bits) < (unsigned)cap) key_bits++;
-  size_t b_sort = 0;   // deterministic mode: sorted slot keys, index values in / out, rocPRIM scratch
-  if (det) {
-    size_t tmp = 0;
-    HIPCHK(c, sort_pairs_u32(nullptr, tmp, nullptr, nullptr, nullptr, nullptr, (size_t)n, key_bits, c->stream));
-    b_sort = 3 * ((((size_t)n * sizeof(int)) + 15) & ~(size_t)15) + ((tmp + 255) & ~(size_t)255);
-  }
-  const size_t b_tab = (size_t)cap * sizeof(DsSlot), b_pnt = (size_t)n * 3 * sizeof(double), b_i = (((size_t)n * sizeof(int)) + 15) & ~(size_t)15,
-               b_blk = (((size_t)nb + 1) * sizeof(int) + 15) & ~(size_t)15, b_var = mode == 1 ? (size_t)n * 9 * sizeof(double) : 0,
-               b_dist = mode == 2 ? (size_t)n * sizeof(double) : 0;
-  int st = ensure_stage(c, b_tab + 3 * b_pnt + b_var + b_dist + 3 * b_i + b_blk + 64 + b_sort + 256);
-  if (st) return st;
-  char *base = (char *)c->d_stage;
-  DsSlot *tab = (DsSlot *)base;
-  double *d_in = (double *)(base + b_tab), *d_out = (double *)(base + b_tab + b_pnt), *d_vout = (double *)(base + b_tab + 2 * b_pnt),
-         *d_var = (double *)(base + b_tab + 3 * b_pnt), *d_dist = (double *)(base + b_tab + 3 * b_pnt + b_var);
-  int *d_slot = (int *)(base + b_tab + 3 * b_pnt + b_var + b_dist), *d_cnt = (int *)((char *)d_slot + b_i), *d_first = (int *)((char *)d_cnt + b_i),
-      *d_blk = (int *)((char *)d_first + b_i), *d_n = d_blk + nb;
-  HIPCHK(c, hipMemcpyAsync(d_in, pnt, b_pnt, hipMemcpyDefault, c->stream));
-  if (mode == 1) HIPCHK(c, hipMemcpyAsync(d_var, var, b_var, hipMemcpyDefault, c->stream));
-  TimedSpan sp{};
-  span_begin(c, "downsample", sp);
-  DsWork w{};
-  w.tab = tab; w.cap = cap; w.key_bits = key_bits; w.slot = d_slot; w.blk = d_blk; w.n_out = d_n; w.dist = d_dist;
-  if (det) {
-    char *sb = (char *)(((uintptr_t)((char *)d_n + 64) + 255) & ~(uintptr_t)255);
-    w.skey = (unsigned int *)sb; w.idx = (int *)(sb + b_i); w.sidx = (int *)(sb + 2 * b_i);
-    w.tmp = sb + 3 * b_i; w.tmp_bytes = b_sort - 3 * b_i;
-  }
-  st = ds_core(c, c->stream, mode, n, d_in, mode == 1 ? d_var : nullptr, 9, 4, voxel_size, det, w);
-  if (st) return st;
-  hipLaunchKernelGGL(k_ds_emit, dim3(nb), dim3(256), 0, c->stream, n, tab, d_slot, d_blk, d_out, d_cnt, d_first, d_vout, mode);
-  span_end(c, "downsample", sp);
-  HIPCHK(c, hipGetLastError());
-  int m = 0;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpyAsync(&m, d_n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (m > 0) {
-    if (pnt_out) HIPCHK(c, hipMemcpyAsync(pnt_out, d_out, (size_t)m * 3 * sizeof(double), hipMemcpyDefault, c->stream));
-    if (count_out) HIPCHK(c, hipMemcpyAsync(count_out, d_cnt, (size_t)m * sizeof(int), hipMemcpyDefault, c->stream));
-    HIPCHK(c, hipMemcpyAsync(first_out, d_first, (size_t)m * sizeof(int), hipMemcpyDefault, c->stream));
-    if (mode == 1) HIPCHK(c, hipMemcpyAsync(vout, d_vout, (size_t)m * 3 * sizeof(double), hipMemcpyDefault, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  *n_out = m;
-  return VBA_OK;
-}
-int vba_scan_down_sampling_voxel(vba_ctx *c, int n, const double *pnt, double voxel_size, double *pnt_out, int *count_out, int *first_out,
-                                 int *n_out) {
-  return ds_common(c, 0, n, pnt, nullptr, voxel_size, pnt_out, nullptr, count_out, first_out, n_out);
-}
-int vba_scan_down_sampling_pvec(vba_ctx *c, int n, const double *pnt, const double *var, double voxel_size, double *pnt_out, double *vardiag_out,
-                                int *count_out, int *n_out) {
-  std::vector<int> first(n > 0 ? n : 1);
-  return ds_common(c, 1, n, pnt, var, voxel_size, pnt_out, vardiag_out, count_out, first.data(), n_out);
-}
-int vba_scan_down_sampling_close(vba_ctx *c, int n, const double *pnt, double voxel_size, int *index_out, int *n_out) {
-  return ds_common(c, 2, n, pnt, nullptr, voxel_size, nullptr, nullptr, nullptr, index_out, n_out);
-}
-int vba_scan_undistort(vba_ctx *c, int n, double *pnt, const double *curv, int m, const double *imu_poses, const double *end_pose,
-                       const double *ext_pose) {
-  if (n < 0 || m < 0 || (n > 0 && (!pnt || !curv)) || (m > 0 && !imu_poses) || !end_pose || !ext_pose) return VBA_ERR_BAD_ARG;
-  if (n == 0 || m == 0) return VBA_OK;
-  const size_t nprm = (size_t)22 * m + 24;
-  int st = ensure_stage(c, ((size_t)n * 4 + nprm) * sizeof(double));
-  if (st) return st;
-  double *d_p = (double *)c->d_stage, *d_c = d_p + (size_t)n * 3, *d_prm = d_c + n;
-  std::vector<double> prm(nprm);
-  std::memcpy(prm.data(), imu_poses, (size_t)22 * m * sizeof(double));
-  std::memcpy(prm.data() + (size_t)22 * m, end_pose, 12 * sizeof(double));
-  std::memcpy(prm.data() + (size_t)22 * m + 12, ext_pose, 12 * sizeof(double));
-  HIPCHK(c, hipMemcpyAsync(d_p, pnt, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_c, curv, (size_t)n * sizeof(double), hipMemcpyDefault, c->stream));
-  HIPCHK(c, hipMemcpyAsync(d_prm, prm.data(), nprm * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  TimedSpan sp{};
-  span_begin(c, "undistort", sp);
-  hipLaunchKernelGGL(k_undistort, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, d_p, d_c, m, d_prm);
-  span_end(c, "undistort", sp);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(pnt, d_p, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));      // prm is a host temporary
-  return VBA_OK;
-}
 int vba_map_cut_voxel_fix(vba_ctx *c, int n, const double *pnt_world, double jour) {
   return map_cut_voxel_fix(c->map, c->stream, n, pnt_world, jour, c->err);
 }
@@ -2506,1198 +2249,8 @@ int vba_odom_lio_state_estimation(vba_ctx *c, int n, const double *pnt_body, con
 int vba_map_dump_leaves(vba_ctx *c, double *out, int max_leaves) { return map_dump_leaves(c->map, c->stream, out, max_leaves, c->err); }
 int vba_map_dump_plane_var(vba_ctx *c, double *out, int max_leaves) { return map_dump_plane_var(c->map, c->stream, out, max_leaves, c->err); }
 
-// ---------------------------------------------------------------- session-store formats (vba_io.hpp), host only
-int vba_io_save_pcd(const char *path, int n, const double *xyz) {
-  if (!path || n < 0 || (n > 0 && !xyz)) return VBA_ERR_BAD_ARG;
-  FILE *f = std::fopen(path, "wb");
-  if (!f) return VBA_ERR_IO;
-  std::fprintf(f, "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z intensity\nSIZE 4 4 4 4\nTYPE F F F F\nCOUNT 1 1 1 1\n"
-                  "WIDTH %d\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %d\nDATA binary\n", n, n);
-  std::vector<float> rec((size_t)n * 4);
-  for (int i = 0; i < n; i++) {                                // save_pcd sets x, y, z only: intensity keeps PointXYZI's default 0 (VS:170-176)
-    rec[4 * (size_t)i] = (float)xyz[3 * (size_t)i]; rec[4 * (size_t)i + 1] = (float)xyz[3 * (size_t)i + 1];
-    rec[4 * (size_t)i + 2] = (float)xyz[3 * (size_t)i + 2]; rec[4 * (size_t)i + 3] = 0.f;
-  }
-  const size_t w = n > 0 ? std::fwrite(rec.data(), 16, (size_t)n, f) : 0;
-  const int bad = std::fclose(f);
-  return (w == (size_t)n && !bad) ? VBA_OK : VBA_ERR_IO;
-}
-
-int vba_io_load_pcd(const char *path, int cap, double *xyz, double *intensity, int *n_out) {
-  if (!path || !n_out || cap < 0 || (cap > 0 && !xyz)) return VBA_ERR_BAD_ARG;
-  *n_out = 0;
-  FILE *f = std::fopen(path, "rb");
-  if (!f) return VBA_ERR_IO;
-  struct Close { FILE *f; ~Close() { std::fclose(f); } } closer{f};
-  vba_io::PcdHeader h;
-  char line[1024];
-  while (h.data.empty()) {
-    if (!std::fgets(line, sizeof(line), f)) return VBA_ERR_IO;
-    std::istringstream ss(line);
-    std::string key, tok;
-    if (!(ss >> key) || key[0] == '#') continue;
-    if (key == "FIELDS" || key == "COLUMNS") while (ss >> tok) h.fields.push_back(tok);
-    else if (key == "SIZE") while (ss >> tok) h.size.push_back(std::atoi(tok.c_str()));
-    else if (key == "TYPE") while (ss >> tok) h.type.push_back(tok);
-    else if (key == "COUNT") while (ss >> tok) h.count.push_back(std::atoi(tok.c_str()));
-    else if (key == "WIDTH") ss >> h.width;
-    else if (key == "HEIGHT") ss >> h.height;
-    else if (key == "POINTS") ss >> h.points;
-    else if (key == "DATA") ss >> h.data;
-  }
-  const size_t nf = h.fields.size();
-  if (nf == 0 || h.size.size() != nf || h.type.size() != nf) return VBA_ERR_IO;
-  if (h.count.empty()) h.count.assign(nf, 1);
-  if (h.count.size() != nf) return VBA_ERR_IO;
-  if (h.points < 0) h.points = h.width * h.height;
-  if (h.points < 0) return VBA_ERR_IO;
-  int fx = -1, fy = -1, fz = -1, fi = -1;
-  std::vector<size_t> off(nf);
-  size_t stride = 0;
-  for (size_t k = 0; k < nf; k++) {
-    off[k] = stride; stride += (size_t)h.size[k] * (size_t)h.count[k];
-    if (h.fields[k] == "x") fx = (int)k; else if (h.fields[k] == "y") fy = (int)k; else if (h.fields[k] == "z") fz = (int)k;
-    else if (h.fields[k] == "intensity") fi = (int)k;
-  }
-  if (fx < 0 || fy < 0 || fz < 0) return VBA_ERR_IO;
-  *n_out = (int)h.points;
-  if (h.points > cap) return VBA_ERR_CAPACITY;                 // *n_out tells the caller what to allocate
-  auto scalar = [&](const unsigned char *p, size_t k) -> double {
-    const char t = h.type[k][0]; const int sz = h.size[k];
-    if (t == 'F') { if (sz == 4) { float v; std::memcpy(&v, p, 4); return v; } if (sz == 8) { double v; std::memcpy(&v, p, 8); return v; } }
-    if (t == 'U') { uint64_t v = 0; std::memcpy(&v, p, (size_t)sz); return (double)v; }              // little endian
-    if (t == 'I') { int64_t v = 0; std::memcpy(&v, p, (size_t)sz); const int sh = 64 - 8 * sz; return (double)((v << sh) >> sh); }
-    return 0.0;
-  };
-  if (h.data == "binary") {
-    std::vector<unsigned char> buf((size_t)h.points * stride);
-    if (h.points > 0 && std::fread(buf.data(), stride, (size_t)h.points, f) != (size_t)h.points) return VBA_ERR_IO;
-    for (long i = 0; i < h.points; i++) {
-      const unsigned char *r = buf.data() + (size_t)i * stride;
-      xyz[3 * i] = scalar(r + off[fx], fx); xyz[3 * i + 1] = scalar(r + off[fy], fy); xyz[3 * i + 2] = scalar(r + off[fz], fz);
-      if (intensity) intensity[i] = fi >= 0 ? scalar(r + off[fi], fi) : 0.0;
-    }
-  } else if (h.data == "ascii") {
-    for (long i = 0; i < h.points; i++) {
-      if (!std::fgets(line, sizeof(line), f)) return VBA_ERR_IO;
-      std::istringstream ss(line);
-      if (intensity) intensity[i] = 0.0;
-      for (size_t k = 0; k < nf; k++)
-        for (int cidx = 0; cidx < h.count[k]; cidx++) {
-          double v;
-          if (!(ss >> v)) return VBA_ERR_IO;
-          if (cidx) continue;
-          if ((int)k == fx) xyz[3 * i] = v; else if ((int)k == fy) xyz[3 * i + 1] = v; else if ((int)k == fz) xyz[3 * i + 2] = v;
-          else if ((int)k == fi && intensity) intensity[i] = v;
-        }
-    }
-  } else {
-    return VBA_ERR_IO;                                          // binary_compressed: never written by the reference (VS:178)
-  }
-  return VBA_OK;
-}
-
-int vba_io_save_pose(const char *path, int n, const double *states, const double *v6) {
-  if (!path || n < 0 || (n > 0 && (!states || !v6))) return VBA_ERR_BAD_ARG;
-  if (n < 100) return VBA_OK;                                   // VS:183-184: short sessions are not saved
-  FILE *f = std::fopen(path, "w");
-  if (!f) return VBA_ERR_IO;
-  for (int i = 0; i < n; i++) {
-    vbh::State x;
-    std::memcpy(&x, states + (size_t)i * 25, sizeof(x));
-    double q[4];
-    vba_io::quat_from_rot(x.R, q);
-    std::fprintf(f, "%.6f ", x.t);                              // fixed, precision 6; then precision 7 for the rest (VS:192-193)
-    std::fprintf(f, "%.7f %.7f %.7f ", x.p[0], x.p[1], x.p[2]);
-    std::fprintf(f, "%.7f %.7f %.7f %.7f", q[0], q[1], q[2], q[3]);
-    const double *grp[4] = {x.v, x.bg, x.ba, x.g};
-    for (int g = 0; g < 4; g++) std::fprintf(f, " %.7f %.7f %.7f", grp[g][0], grp[g][1], grp[g][2]);
-    for (int j = 0; j < 6; j++) std::fprintf(f, " %.7f", v6[(size_t)i * 6 + j]);
-    std::fprintf(f, "\n");
-  }
-  return std::fclose(f) ? VBA_ERR_IO : VBA_OK;
-}
-
-int vba_io_read_lidarstate(const char *path, int cap, double *states, double *v6, int *n_out) {
-  if (!path || !n_out || cap < 0 || (cap > 0 && !states)) return VBA_ERR_BAD_ARG;
-  *n_out = 0;
-  FILE *f = std::fopen(path, "r");
-  if (!f) return VBA_ERR_IO;                                    // the reference prints "not found" and exits (VH:271-275)
-  struct Close { FILE *f; ~Close() { std::fclose(f); } } closer{f};
-  std::vector<char> line(1 << 16);
-  int n = 0;
-  while (std::fgets(line.data(), (int)line.size(), f)) {
-    std::vector<double> nums;
-    char *p = line.data();
-    for (;;) {
-      char *e = nullptr;
-      const double v = std::strtod(p, &e);
-      if (e == p) break;
-      nums.push_back(v); p = e;
-    }
-    if (nums.size() < 8) { if (nums.empty()) continue; return VBA_ERR_IO; }
-    if (n < cap) {
-      vbh::State x;
-      std::memset(&x, 0, sizeof(x));
-      x.g[2] = -9.8;                                            // lines without g: the reference leaves IMUST::g unset (TL:188-197); gravity here
-      x.t = nums[0];
-      for (int k = 0; k < 3; k++) x.p[k] = nums[1 + k];
-      const double q[4] = {nums[4], nums[5], nums[6], nums[7]};
-      vba_io::rot_from_quat(q, x.R);
-      if (nums.size() >= 20)
-        for (int k = 0; k < 3; k++) { x.v[k] = nums[8 + k]; x.bg[k] = nums[11 + k]; x.ba[k] = nums[14 + k]; x.g[k] = nums[17 + k]; }
-      std::memcpy(states + (size_t)n * 25, &x, sizeof(x));
-      if (v6) for (int k = 0; k < 6; k++) v6[(size_t)n * 6 + k] = nums.size() >= 26 ? nums[20 + k] : 0.0;
-    }
-    n++;
-  }
-  *n_out = n;
-  return n > cap ? VBA_ERR_CAPACITY : VBA_OK;
-}
-
 }  // extern "C"
-
-// ------------------------------------------------------------------------------------------------ loop retrieval (vba_btc_*)
-struct vba_btc_db {
-  vba_ctx *ctx = nullptr;
-  vba_btc_config cfg{};
-  int nstd = 0, cap = 0;                     // descriptors stored / capacity (rows)
-  BtcStds d{};
-  std::vector<int> tab;                      // host mirror of the cell table, 8 ints per slot (vba_kernels_btc.hpp)
-  int tab_mask = 0, ncell = 0;
-  int *d_tab = nullptr;
-  int nchunk = 0, chunk_cap = 0;
-  int *d_ent = nullptr, *d_next = nullptr;
-  std::vector<int> off{0}, seq;              // plane clouds: point offsets, header.seq
-  float *d_pc = nullptr; size_t pc_cap = 0;
-  int *d_off = nullptr; int off_cap = 0;
-  int mcap = 0; int *d_m = nullptr;          // match list and per-candidate pair lists: mq | md | mf | pq | pd, mcap each
-  int vcap = 0; int *d_votes = nullptr;
-  int *d_cand = nullptr, *d_total = nullptr; double *d_cres = nullptr, *d_res = nullptr, *h_res = nullptr;
-  bool have_search = false;                  // the last search ran the kernels (n > 0)
-  // descriptor generation (vba_btc_generate_stds): its configuration, device buffers, the AddSTDescs count (current_frame_id_)
-  // and the corners of the last call
-  vba_btc_gen_config gcfg{};
-  BtcGen *gen = nullptr;
-  int n_add = 0;
-  std::vector<double> last_loc; std::vector<uint64_t> last_bits;
-  BtcCfgDev dev_cfg() const {
-    BtcCfgDev f;
-    f.skip_near = cfg.skip_near_num; f.cand_num = cfg.candidate_num; f.rough = cfg.rough_dis_threshold; f.sim = cfg.similarity_threshold;
-    f.icp = cfg.icp_threshold; f.normal = cfg.normal_threshold; f.dis = cfg.dis_threshold;
-    return f;
-  }
-  BtcIndex index() const { BtcIndex ix; ix.tab = d_tab; ix.mask = tab_mask; ix.ent = d_ent; ix.next = d_next; return ix; }
-};
-
-namespace {
-
-// the "loop" timing span of one call, closed on every return path
-struct BtcSpan {
-  vba_ctx *c; TimedSpan s{}; bool open = true;
-  explicit BtcSpan(vba_ctx *cc) : c(cc) { span_begin(c, "loop", s); }
-  void end() { if (open) span_end(c, "loop", s); open = false; }
-  ~BtcSpan() { end(); }
-};
-
-// grow a device array to new_n elements, keeping the first keep elements (stream-ordered copy; the old block is freed after it)
-template <class T>
-int btc_grow(vba_ctx *c, T **p, size_t keep, size_t new_n) {
-  T *q = nullptr;
-  HIPCHK(c, hipMalloc((void **)&q, new_n * sizeof(T)));
-  if (*p && keep) HIPCHK(c, hipMemcpyAsync(q, *p, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
-  if (*p) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(*p); }
-  *p = q;
-  return VBA_OK;
-}
-
-int btc_reserve_rows(vba_btc_db *db, int need) {
-  if (need <= db->cap) return VBA_OK;
-  vba_ctx *c = db->ctx;
-  int nc = db->cap ? db->cap : 1024;
-  while (nc < need) nc *= 2;
-  const size_t k = (size_t)db->nstd;
-  int st;
-  if ((st = btc_grow(c, &db->d.tri, 3 * k, 3 * (size_t)nc)) || (st = btc_grow(c, &db->d.cen, 3 * k, 3 * (size_t)nc)) ||
-      (st = btc_grow(c, &db->d.loc, 9 * k, 9 * (size_t)nc)) || (st = btc_grow(c, &db->d.bits, 3 * k, 3 * (size_t)nc)) ||
-      (st = btc_grow(c, &db->d.summ, 3 * k, 3 * (size_t)nc)) || (st = btc_grow(c, &db->d.frame, k, (size_t)nc)))
-    return st;
-  db->cap = nc;
-  return VBA_OK;
-}
-
-// row checks shared by add_stds and the query: summaries are unsigned chars, masks fit occupy_len
-int btc_check_rows(int n, const double *rows, const uint64_t *bits, int occupy_len) {
-  const uint64_t mask = occupy_len >= 64 ? ~0ull : ((1ull << occupy_len) - 1ull);
-  for (int i = 0; i < n; i++) {
-    const double *r = rows + (size_t)i * VBA_BTC_ROW_LEN;
-    if (!(r[6] == std::floor(r[6]) && std::fabs(r[6]) < 2147483647.0)) return VBA_ERR_BAD_ARG;
-    for (int k = 16; k < 19; k++) if (!(r[k] >= 0 && r[k] <= 255 && r[k] == std::floor(r[k]))) return VBA_ERR_BAD_ARG;
-    for (int k = 0; k < 3; k++) if (bits[3 * (size_t)i + k] & ~mask) return VBA_ERR_BAD_ARG;
-    for (int k = 0; k < 3; k++) if (!(std::fabs(r[k]) < 1e9)) return VBA_ERR_BAD_ARG;    // (int) of the cell key must be defined
-  }
-  return VBA_OK;
-}
-
-// rows -> SoA block [tri 3n | cen 3n | loc 9n | bits 3n | summ 3n | frame n] (host), and the views of the same block on the device
-size_t btc_pack_bytes(int n) { return (size_t)n * (15 * sizeof(double) + 3 * sizeof(unsigned long long) + 4 * sizeof(int)); }
-void btc_pack(int n, const double *rows, const uint64_t *bits, char *h) {
-  double *tri = (double *)h, *cen = tri + 3 * (size_t)n, *loc = cen + 3 * (size_t)n;
-  unsigned long long *bb = (unsigned long long *)(loc + 9 * (size_t)n);
-  int *summ = (int *)(bb + 3 * (size_t)n), *frame = summ + 3 * (size_t)n;
-  for (int i = 0; i < n; i++) {
-    const double *r = rows + (size_t)i * VBA_BTC_ROW_LEN;
-    for (int k = 0; k < 3; k++) { tri[3 * i + k] = r[k]; cen[3 * i + k] = r[3 + k]; summ[3 * i + k] = (int)r[16 + k]; bb[3 * i + k] = bits[3 * (size_t)i + k]; }
-    for (int k = 0; k < 9; k++) loc[9 * i + k] = r[7 + k];
-    frame[i] = (int)r[6];
-  }
-}
-BtcStds btc_view(int n, char *dev) {
-  BtcStds v;
-  v.tri = (double *)dev; v.cen = v.tri + 3 * (size_t)n; v.loc = v.cen + 3 * (size_t)n;
-  v.bits = (unsigned long long *)(v.loc + 9 * (size_t)n);
-  v.summ = (int *)(v.bits + 3 * (size_t)n); v.frame = v.summ + 3 * (size_t)n;
-  return v;
-}
-
-int btc_table_upload(vba_btc_db *db) {
-  vba_ctx *c = db->ctx;
-  if (db->d_tab) hipFree(db->d_tab);
-  db->d_tab = nullptr;
-  HIPCHK(c, hipMalloc((void **)&db->d_tab, db->tab.size() * sizeof(int)));
-  HIPCHK(c, hipMemcpyAsync(db->d_tab, db->tab.data(), db->tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  return VBA_OK;
-}
-int btc_table_find(const std::vector<int> &tab, int mask, int x, int y, int z, bool &fresh) {
-  unsigned s = btc_hash(x, y, z) & (unsigned)mask;
-  for (;;) {
-    const int *e = tab.data() + 8 * (size_t)s;
-    if (e[3] < 0) { fresh = true; return (int)s; }
-    if (e[0] == x && e[1] == y && e[2] == z) { fresh = false; return (int)s; }
-    s = (s + 1) & (unsigned)mask;
-  }
-}
-void btc_table_init(std::vector<int> &tab, int slots) {
-  tab.assign((size_t)slots * 8, 0);
-  for (int s = 0; s < slots; s++) { tab[8 * (size_t)s + 3] = -1; tab[8 * (size_t)s + 5] = -1; }
-}
-
-// the host table into `slots` slots (a power of two), entries re-probed in slot order; the caller uploads it
-void btc_rehash(vba_btc_db *db, int slots) {
-  std::vector<int> nt;
-  btc_table_init(nt, slots);
-  for (int u = 0; u <= db->tab_mask; u++) {
-    const int *e = db->tab.data() + 8 * (size_t)u;
-    if (e[3] < 0) continue;
-    bool f2;
-    const int t = btc_table_find(nt, slots - 1, e[0], e[1], e[2], f2);
-    std::memcpy(nt.data() + 8 * (size_t)t, e, 8 * sizeof(int));
-  }
-  db->tab.swap(nt);
-  db->tab_mask = slots - 1;
-}
-
-// one search of db, enqueued: counts, scan, ranked match list + votes, candidate list, verification, choice, result -> h_res
-int btc_enqueue(vba_btc_db *db, const BtcStds &q, int n, const float *pl, int npl) {
-  vba_ctx *c = db->ctx;
-  const int nf = (int)db->off.size() - 1, G = 27 * n, nb = (G + 3) / 4;
-  const BtcCfgDev cf = db->dev_cfg();
-  const BtcIndex ix = db->index();
-  int *mq = db->d_m, *md = mq + db->mcap, *mf = md + db->mcap, *pq = mf + db->mcap, *pd = pq + db->mcap;
-  if (nf > 0) HIPCHK(c, hipMemsetAsync(db->d_votes, 0, (size_t)nf * sizeof(int), c->stream));
-  k_btc_match<true><<<nb, 256, 0, c->stream>>>(n, q, db->d, ix, cf, c->d_btccnt, db->d_total, db->mcap, mq, md, mf, db->d_votes);
-  k_det_scan<<<1, 1024, 0, c->stream>>>(c->d_btccnt, G, db->d_total, -1, 0, 0);
-  k_btc_match<false><<<nb, 256, 0, c->stream>>>(n, q, db->d, ix, cf, c->d_btccnt, db->d_total, db->mcap, mq, md, mf, db->d_votes);
-  k_btc_select<<<1, 256, 0, c->stream>>>(nf, db->cfg.candidate_num, db->mcap, db->d_total, db->d_votes, db->d_cand, db->d_res);
-  k_btc_verify<<<db->cfg.candidate_num, 256, 0, c->stream>>>(q, db->d, cf, db->d_total, db->mcap, mq, md, mf, pq, pd, db->d_cand, db->d_res,
-                                                             db->d_cres, pl, npl, db->d_pc, db->d_off);
-  k_btc_final<<<1, 64, 0, c->stream>>>(cf, db->d_cand, db->d_cres, db->d_res);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(db->h_res, db->d_res, BTC_RES * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  return VBA_OK;
-}
-
-void btc_result(const vba_btc_db *db, vba_btc_result *r) {
-  const double *h = db->h_res;
-  r->loop_id = (int)h[0]; r->score = h[1];
-  for (int k = 0; k < 3; k++) r->t[k] = h[2 + k];
-  for (int k = 0; k < 9; k++) r->R[k] = h[5 + k];
-}
-
-int btc_search_run(int n_db, vba_btc_db *const *dbs, int n, const double *rows, const uint64_t *bits, const vba_btc_db *cur, int cur_frame,
-                   vba_btc_result *results);
-int btc_search(int n_db, vba_btc_db *const *dbs, int n, const double *rows, const uint64_t *bits, const vba_btc_db *cur, int cur_frame,
-               vba_btc_result *results) {
-  if (n_db < 0 || (n_db > 0 && (!dbs || !results)) || n < 0 || (n > 0 && (!rows || !bits)) || !cur) return VBA_ERR_BAD_ARG;
-  if (n_db == 0) return VBA_OK;
-  vba_ctx *c = dbs[0]->ctx;
-  for (int k = 0; k < n_db; k++) if (!dbs[k] || dbs[k]->ctx != c) return VBA_ERR_BAD_ARG;
-  if (cur->ctx != c || cur_frame < 0 || cur_frame >= (int)cur->off.size() - 1) return VBA_ERR_BAD_ARG;
-  for (int k = 0; k < n_db; k++) { const int st = btc_check_rows(n, rows, bits, dbs[k]->cfg.occupy_len); if (st) return st; }
-  if (n == 0) {                                                   // BTC.cpp:210-214
-    for (int k = 0; k < n_db; k++) { results[k] = vba_btc_result{}; results[k].loop_id = -1; dbs[k]->have_search = false; }
-    return VBA_OK;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  BtcSpan sp(c);
-  return btc_search_run(n_db, dbs, n, rows, bits, cur, cur_frame, results);
-}
-
-int btc_search_run(int n_db, vba_btc_db *const *dbs, int n, const double *rows, const uint64_t *bits, const vba_btc_db *cur, int cur_frame,
-                   vba_btc_result *results) {
-  vba_ctx *c = dbs[0]->ctx;
-  // query upload (once) and the shared count scratch
-  const size_t qb = btc_pack_bytes(n);
-  if (qb > c->btcq_bytes) {
-    if (c->d_btcq) hipFree(c->d_btcq);
-    if (c->h_btcq) hipHostFree(c->h_btcq);
-    c->d_btcq = c->h_btcq = nullptr; c->btcq_bytes = 0;
-    size_t nbytes = 1 << 16;
-    while (nbytes < qb) nbytes *= 2;
-    HIPCHK(c, hipMalloc((void **)&c->d_btcq, nbytes));
-    HIPCHK(c, hipHostMalloc((void **)&c->h_btcq, nbytes, hipHostMallocDefault));
-    c->btcq_bytes = nbytes;
-  }
-  if ((size_t)27 * n > c->btccnt_cap) {
-    if (c->d_btccnt) hipFree(c->d_btccnt);
-    c->d_btccnt = nullptr;
-    size_t m = 8192;
-    while (m < (size_t)27 * n) m *= 2;
-    HIPCHK(c, hipMalloc((void **)&c->d_btccnt, m * sizeof(int)));
-    c->btccnt_cap = m;
-  }
-  for (int k = 0; k < n_db; k++) {                                // votes sized by the frames pushed so far
-    vba_btc_db *db = dbs[k];
-    const int nf = (int)db->off.size() - 1;
-    if (nf > db->vcap) {
-      int m = db->vcap ? db->vcap : 1024;
-      while (m < nf) m *= 2;
-      const int st = btc_grow(c, &db->d_votes, 0, (size_t)m);
-      if (st) return st;
-      db->vcap = m;
-    }
-  }
-  btc_pack(n, rows, bits, c->h_btcq);
-  HIPCHK(c, hipMemcpyAsync(c->d_btcq, c->h_btcq, qb, hipMemcpyHostToDevice, c->stream));
-  const BtcStds q = btc_view(n, c->d_btcq);
-  const int plo = cur->off[cur_frame], npl = cur->off[cur_frame + 1] - plo;
-  const float *pl = cur->d_pc ? cur->d_pc + 6 * (size_t)plo : nullptr;
-  for (int k = 0; k < n_db; k++) { const int st = btc_enqueue(dbs[k], q, n, pl, npl); if (st) return st; }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  // a match list that did not fit: grow it and search that database again (amortised: the list only grows)
-  for (int k = 0; k < n_db; k++) {
-    vba_btc_db *db = dbs[k];
-    const double total = db->h_res[15];
-    if (total > db->mcap) {
-      int m = db->mcap;
-      while (m < total) m *= 2;
-      int st = btc_grow(c, &db->d_m, 0, 5 * (size_t)m);
-      if (st) return st;
-      db->mcap = m;
-      if ((st = btc_enqueue(db, q, n, pl, npl))) return st;
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    db->have_search = true;
-    btc_result(db, &results[k]);
-  }
-  return VBA_OK;
-}
-
-}  // namespace
-
 extern "C" {
-
-int vba_btc_default_config(int is_high_fly, vba_btc_config *f) {   // BTC.cpp:3-68
-  if (!f) return VBA_ERR_BAD_ARG;
-  std::memset(f, 0, sizeof(*f));
-  f->skip_near_num = 30;
-  f->candidate_num = is_high_fly ? 100 : 20;
-  f->rough_dis_threshold = 0.01f;
-  f->similarity_threshold = is_high_fly ? 0.5f : 0.7f;
-  f->icp_threshold = 0.15f;
-  f->normal_threshold = 0.2f;
-  f->dis_threshold = 0.5f;
-  f->occupy_len = 50;   // (proj_dis_max_ - proj_dis_min_) / proj_image_high_inc_: 5 / 0.1 and 10 / 0.2
-  return VBA_OK;
-}
-
-int vba_btc_create(vba_ctx *c, const vba_btc_config *cfg, vba_btc_db **out) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VBA_ERR_NO_DEVICE;
-  if (!c || !cfg || !out) return VBA_ERR_BAD_ARG;
-  *out = nullptr;
-  if (cfg->occupy_len < 0 || cfg->occupy_len > 64 || cfg->candidate_num < 1 || cfg->candidate_num > BTC_MAX_CAND) return VBA_ERR_BAD_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  vba_btc_db *db = new vba_btc_db();
-  db->ctx = c; db->cfg = *cfg;
-  vba_btc_default_gen_config(0, &db->gcfg);
-  btc_table_init(db->tab, 1024);
-  db->tab_mask = 1023;
-  int st = btc_table_upload(db);
-  if (!st) st = btc_reserve_rows(db, 1024);
-  if (!st) st = btc_grow(c, &db->d_off, 0, 1024);
-  if (!st) st = btc_grow(c, &db->d_ent, 0, (size_t)256 * BTC_CHUNK);
-  if (!st) st = btc_grow(c, &db->d_next, 0, 256);
-  if (!st) st = btc_grow(c, &db->d_m, 0, 5 * (size_t)65536);
-  if (!st) st = btc_grow(c, &db->d_votes, 0, 1024);
-  if (!st) st = btc_grow(c, &db->d_cand, 0, 5 * (size_t)BTC_MAX_CAND);
-  if (!st) st = btc_grow(c, &db->d_total, 0, 4);
-  if (!st) st = btc_grow(c, &db->d_cres, 0, 13 * (size_t)BTC_MAX_CAND);
-  if (!st) st = btc_grow(c, &db->d_res, 0, BTC_RES);
-  if (!st && hipHostMalloc((void **)&db->h_res, BTC_RES * sizeof(double), hipHostMallocDefault) != hipSuccess) st = VBA_ERR_HIP;
-  if (st) { vba_btc_destroy(db); return st; }
-  db->off_cap = 1024; db->chunk_cap = 256; db->mcap = 65536; db->vcap = 1024;
-  const int zero = 0;
-  hipMemcpyAsync(db->d_off, &zero, sizeof(int), hipMemcpyHostToDevice, c->stream);
-  if (hipStreamSynchronize(c->stream) != hipSuccess) { vba_btc_destroy(db); return VBA_ERR_HIP; }
-  *out = db;
-  return VBA_OK;
-}
-
-void vba_btc_destroy(vba_btc_db *db) {
-  if (!db) return;
-  vba_ctx *c = db->ctx;
-  hipSetDevice(c->device);
-  hipStreamSynchronize(c->stream);
-  void *p[] = {db->d.tri, db->d.cen, db->d.loc, db->d.bits, db->d.summ, db->d.frame, db->d_tab, db->d_ent, db->d_next, db->d_pc, db->d_off,
-               db->d_m, db->d_votes, db->d_cand, db->d_total, db->d_cres, db->d_res};
-  for (void *q : p) if (q) hipFree(q);
-  if (db->h_res) hipHostFree(db->h_res);
-  if (db->gen) { btcgen_free(*db->gen); delete db->gen; }
-  delete db;
-}
-
-int vba_btc_reserve(vba_btc_db *db, int stds, int frames, int64_t cloud_points, int matches) {
-  if (!db || stds < 0 || frames < 0 || cloud_points < 0 || matches < 0 || stds > (1 << 29) || frames > (1 << 29) || matches > (1 << 28))
-    return VBA_ERR_BAD_ARG;
-  vba_ctx *c = db->ctx;
-  HIPCHK(c, hipSetDevice(c->device));
-  int st;
-  if ((st = btc_reserve_rows(db, stds))) return st;
-  int slots = db->tab_mask + 1;                               // cells <= descriptors, load factor <= 1/2
-  while (slots < 2 * stds) slots *= 2;
-  if (slots > db->tab_mask + 1) { btc_rehash(db, slots); if ((st = btc_table_upload(db))) return st; }
-  if (stds > db->chunk_cap) {                                 // chunks <= descriptors
-    int m = db->chunk_cap;
-    while (m < stds) m *= 2;
-    if ((st = btc_grow(c, &db->d_ent, (size_t)db->nchunk * BTC_CHUNK, (size_t)m * BTC_CHUNK)) || (st = btc_grow(c, &db->d_next, (size_t)db->nchunk, (size_t)m)))
-      return st;
-    db->chunk_cap = m;
-  }
-  if (frames + 1 > db->off_cap) {
-    int m = db->off_cap;
-    while (m < frames + 1) m *= 2;
-    if ((st = btc_grow(c, &db->d_off, db->off.size(), (size_t)m))) return st;
-    db->off_cap = m;
-  }
-  if (frames > db->vcap) {
-    int m = db->vcap;
-    while (m < frames) m *= 2;
-    if ((st = btc_grow(c, &db->d_votes, 0, (size_t)m))) return st;
-    db->vcap = m;
-  }
-  if ((size_t)cloud_points > db->pc_cap) {
-    size_t m = db->pc_cap ? db->pc_cap : 65536;
-    while (m < (size_t)cloud_points) m *= 2;
-    if ((st = btc_grow(c, &db->d_pc, 6 * (size_t)db->off.back(), 6 * m))) return st;
-    db->pc_cap = m;
-  }
-  if (matches > db->mcap) {
-    int m = db->mcap;
-    while (m < matches) m *= 2;
-    if ((st = btc_grow(c, &db->d_m, 0, 5 * (size_t)m))) return st;
-    db->mcap = m;
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return VBA_OK;
-}
-
-int vba_btc_set_skip_near_num(vba_btc_db *db, int v) { if (!db) return VBA_ERR_BAD_ARG; db->cfg.skip_near_num = v; return VBA_OK; }
-int vba_btc_num_frames(vba_btc_db *db) { return db ? (int)db->off.size() - 1 : -1; }
-int vba_btc_frame_seq(vba_btc_db *db, int frame, int *seq) {
-  if (!db || !seq || frame < 0 || frame >= (int)db->seq.size()) return VBA_ERR_BAD_ARG;
-  *seq = db->seq[frame];
-  return VBA_OK;
-}
-
-int vba_btc_push_plane_cloud(vba_btc_db *db, int n, const float *xyz_normal, int seq) {
-  if (!db || n < 0 || (n > 0 && !xyz_normal)) return VBA_ERR_BAD_ARG;
-  vba_ctx *c = db->ctx;
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t have = (size_t)db->off.back(), need = have + (size_t)n;
-  if (need > db->pc_cap) {
-    size_t m = db->pc_cap ? db->pc_cap : 65536;
-    while (m < need) m *= 2;
-    const int st = btc_grow(c, &db->d_pc, 6 * have, 6 * m);
-    if (st) return st;
-    db->pc_cap = m;
-  }
-  const int nf = (int)db->off.size();        // frames after this push + 1 offsets
-  if (nf + 1 > db->off_cap) {
-    int m = db->off_cap * 2;
-    while (m < nf + 1) m *= 2;
-    const int st = btc_grow(c, &db->d_off, (size_t)nf, (size_t)m);
-    if (st) return st;
-    db->off_cap = m;
-  }
-  if (need > (size_t)INT32_MAX) return VBA_ERR_CAPACITY;
-  db->off.push_back((int)need);
-  db->seq.push_back(seq);
-  if (n) HIPCHK(c, hipMemcpyAsync(db->d_pc + 6 * have, xyz_normal, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(db->d_off + nf, &db->off.back(), sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return VBA_OK;
-}
-
-int vba_btc_add_stds(vba_btc_db *db, int n, const double *rows, const uint64_t *bits) {   // BTC.cpp:258-277
-  if (!db || n < 0 || (n > 0 && (!rows || !bits))) return VBA_ERR_BAD_ARG;
-  if (n == 0) { db->n_add++; return VBA_OK; }
-  vba_ctx *c = db->ctx;
-  int st = btc_check_rows(n, rows, bits, db->cfg.occupy_len);
-  if (st) return st;
-  const int nf = (int)db->off.size() - 1;
-  for (int i = 0; i < n; i++) { const double f = rows[(size_t)i * VBA_BTC_ROW_LEN + 6]; if (f < 0 || f >= nf) return VBA_ERR_BAD_ARG; }
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((st = btc_reserve_rows(db, db->nstd + n))) return st;
-  // rows -> SoA at [nstd, nstd + n)
-  std::vector<char> h(btc_pack_bytes(n));
-  btc_pack(n, rows, bits, h.data());
-  const BtcStds v = btc_view(n, h.data());
-  const size_t k = (size_t)db->nstd;
-  HIPCHK(c, hipMemcpyAsync(db->d.tri + 3 * k, v.tri, 3 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(db->d.cen + 3 * k, v.cen, 3 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(db->d.loc + 9 * k, v.loc, 9 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(db->d.bits + 3 * k, v.bits, 3 * (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(db->d.summ + 3 * k, v.summ, 3 * (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(db->d.frame + k, v.frame, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  // cell index: STD_LOC = (int)(triangle_ + 0.5) (BTC.cpp:263-266); each cell's chunks list its descriptors in insertion order
-  std::vector<int> ent, nxt, slots;          // (position, value) pairs and the touched table slots
-  bool rehash = false;
-  for (int i = 0; i < n; i++) {
-    const double *r = rows + (size_t)i * VBA_BTC_ROW_LEN;
-    const int x = (int)(r[0] + 0.5), y = (int)(r[1] + 0.5), z = (int)(r[2] + 0.5);
-    bool fresh;
-    int s = btc_table_find(db->tab, db->tab_mask, x, y, z, fresh);
-    if (fresh && 2 * (db->ncell + 1) > db->tab_mask + 1) {     // keep the load factor <= 1/2: rehash into twice the slots
-      btc_rehash(db, 2 * (db->tab_mask + 1));
-      rehash = true;
-      slots.clear();
-      s = btc_table_find(db->tab, db->tab_mask, x, y, z, fresh);
-    }
-    int *e = db->tab.data() + 8 * (size_t)s;
-    if (fresh) { e[0] = x; e[1] = y; e[2] = z; e[3] = -1; e[4] = 0; e[5] = -1; db->ncell++; }
-    if (e[4] % BTC_CHUNK == 0) {                                // a new chunk for this cell
-      if (db->nchunk + 1 > db->chunk_cap) {
-        const int m = db->chunk_cap * 2;
-        if ((st = btc_grow(c, &db->d_ent, (size_t)db->nchunk * BTC_CHUNK, (size_t)m * BTC_CHUNK)) || (st = btc_grow(c, &db->d_next, (size_t)db->nchunk, (size_t)m)))
-          return st;
-        db->chunk_cap = m;
-      }
-      const int ch = db->nchunk++;
-      if (e[5] >= 0) { nxt.push_back(e[5]); nxt.push_back(ch); }
-      else e[3] = ch;
-      nxt.push_back(ch); nxt.push_back(-1);
-      e[5] = ch;
-    }
-    ent.push_back(e[5] * BTC_CHUNK + e[4] % BTC_CHUNK); ent.push_back(db->nstd + i);
-    e[4]++;
-    if (!rehash) slots.push_back(s);
-  }
-  db->nstd += n;
-  // a chunk opened and then linked in the same batch appears twice in nxt ((ch, -1), later (ch, ch2)): keep the LAST value per
-  // position, so every position is written once by the scatter (two writes to one address in one launch have no order)
-  {
-    std::map<int, int> last;
-    for (size_t u = 0; u < nxt.size(); u += 2) last[nxt[u]] = nxt[u + 1];
-    nxt.clear();
-    for (const auto &kv : last) { nxt.push_back(kv.first); nxt.push_back(kv.second); }
-  }
-  // one upload of the (position, value) pairs, three scatters; the table goes whole after a rehash
-  std::vector<int> tp;
-  if (!rehash) {
-    std::sort(slots.begin(), slots.end());
-    slots.erase(std::unique(slots.begin(), slots.end()), slots.end());
-    for (int s : slots) for (int u = 0; u < 8; u++) { tp.push_back(8 * s + u); tp.push_back(db->tab[8 * (size_t)s + u]); }
-  } else if ((st = btc_table_upload(db))) return st;
-  std::vector<int> all;
-  all.insert(all.end(), ent.begin(), ent.end());
-  all.insert(all.end(), nxt.begin(), nxt.end());
-  all.insert(all.end(), tp.begin(), tp.end());
-  if ((st = ensure_stage(c, all.size() * sizeof(int)))) return st;
-  int *ds = (int *)c->d_stage;
-  HIPCHK(c, hipMemcpyAsync(ds, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  const int ne = (int)ent.size() / 2, nn = (int)nxt.size() / 2, nt = (int)tp.size() / 2;
-  if (ne) k_btc_scatter<<<(ne + 255) / 256, 256, 0, c->stream>>>(ne, ds, db->d_ent);
-  if (nn) k_btc_scatter<<<(nn + 255) / 256, 256, 0, c->stream>>>(nn, ds + 2 * ne, db->d_next);
-  if (nt) k_btc_scatter<<<(nt + 255) / 256, 256, 0, c->stream>>>(nt, ds + 2 * (ne + nn), db->d_tab);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  db->n_add++;
-  return VBA_OK;
-}
-
-int vba_btc_search_loop(vba_btc_db *db, int n, const double *rows, const uint64_t *bits, const vba_btc_db *cur_db, int cur_frame,
-                        vba_btc_result *result) {
-  if (!db || !result) return VBA_ERR_BAD_ARG;
-  vba_btc_db *dbs[1] = {db};
-  return btc_search(1, dbs, n, rows, bits, cur_db, cur_frame, result);
-}
-
-int vba_btc_search_loop_sessions(int n_db, vba_btc_db *const *dbs, int n, const double *rows, const uint64_t *bits,
-                                 const vba_btc_db *cur_db, int cur_frame, vba_btc_result *results) {
-  return btc_search(n_db, dbs, n, rows, bits, cur_db, cur_frame, results);
-}
-
-int vba_btc_last_candidates(vba_btc_db *db, int cap, vba_btc_candidate *out, int *n) {
-  if (!db || !n || cap < 0 || (cap > 0 && !out)) return VBA_ERR_BAD_ARG;
-  *n = 0;
-  if (!db->have_search) return VBA_OK;
-  vba_ctx *c = db->ctx;
-  HIPCHK(c, hipSetDevice(c->device));
-  const int nc = (int)db->h_res[14];
-  *n = nc;
-  const int m = nc < cap ? nc : cap;
-  if (m == 0) return VBA_OK;
-  std::vector<int> ci(5 * (size_t)m);
-  std::vector<double> cr(13 * (size_t)m);
-  HIPCHK(c, hipMemcpyAsync(ci.data(), db->d_cand, ci.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(cr.data(), db->d_cres, cr.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int k = 0; k < m; k++) {
-    out[k].frame = ci[5 * k]; out[k].votes = ci[5 * k + 1]; out[k].match_len = ci[5 * k + 1];
-    out[k].max_vote_index = ci[5 * k + 3]; out[k].max_vote = ci[5 * k + 4]; out[k].score = cr[13 * k];
-  }
-  return VBA_OK;
-}
-
-int vba_btc_icp_normal(vba_btc_db *src_db, int src_frame, vba_btc_db *tar_db, int tar_frame, double *t, double *R, double icp_eigval,
-                       int *ok, double *eig, int *iters) {   // loop_refine.hpp:47-139
-  if (!src_db || !tar_db || !t || !R || src_db->ctx != tar_db->ctx) return VBA_ERR_BAD_ARG;
-  if (src_frame < 0 || src_frame >= (int)src_db->off.size() - 1 || tar_frame < 0 || tar_frame >= (int)tar_db->off.size() - 1) return VBA_ERR_BAD_ARG;
-  vba_ctx *c = src_db->ctx;
-  HIPCHK(c, hipSetDevice(c->device));
-  const int ns = src_db->off[src_frame + 1] - src_db->off[src_frame], nt = tar_db->off[tar_frame + 1] - tar_db->off[tar_frame];
-  const float *src = src_db->d_pc ? src_db->d_pc + 6 * (size_t)src_db->off[src_frame] : nullptr;
-  const float *tar = tar_db->d_pc ? tar_db->d_pc + 6 * (size_t)tar_db->off[tar_frame] : nullptr;
-  const int nb = ns > 0 ? (ns + 255) / 256 : 1, ntile = (nt + 255) / 256;
-  int slices = 1;
-  while (slices < ntile && nb * slices * 2 <= 1024) slices *= 2;          // ~1024 workgroups on the 1-NN pass
-  if (slices > ntile && ntile > 0) slices = ntile;
-  if (!c->d_icp) {
-    HIPCHK(c, hipMalloc((void **)&c->d_icp, sizeof(BtcIcpDev)));
-    HIPCHK(c, hipHostMalloc((void **)&c->h_icp, sizeof(BtcIcpDev), hipHostMallocDefault));
-  }
-  if ((size_t)slices * ns > c->icpkey_cap) {
-    size_t m = 65536;
-    while (m < (size_t)slices * ns) m *= 2;
-    const int st = btc_grow(c, &c->d_icpkey, 0, m);
-    if (st) return st;
-    c->icpkey_cap = m;
-  }
-  if ((size_t)nb * BTC_ICP_PART > c->icppart_cap) {
-    size_t m = 4096;
-    while (m < (size_t)nb * BTC_ICP_PART) m *= 2;
-    const int st = btc_grow(c, &c->d_icppart, 0, m);
-    if (st) return st;
-    c->icppart_cap = m;
-  }
-  BtcSpan sp(c);
-  HIPCHK(c, hipStreamSynchronize(c->stream));       // (the pinned state block may still be in flight from an earlier call)
-  BtcIcpDev *h = c->h_icp;
-  std::memset(h, 0, sizeof(*h));
-  for (int k = 0; k < 9; k++) h->R[k] = R[k];
-  for (int k = 0; k < 3; k++) h->t[k] = t[k];
-  h->paras[0] = 0.2; h->paras[1] = 0.2; h->paras[2] = 0.5; h->paras[3] = 3;
-  HIPCHK(c, hipMemcpyAsync(c->d_icp, h, sizeof(*h), hipMemcpyHostToDevice, c->stream));
-  for (int it = 0; it < 20; it++) {                  // launches after convergence return at once (BtcIcpDev::done)
-    k_btc_icp_nn<<<dim3(nb, slices), 256, 0, c->stream>>>(ns, src, nt, tar, c->d_icp, c->d_icpkey);
-    k_btc_icp_accum<<<nb, 256, 0, c->stream>>>(ns, src, tar, slices, c->d_icpkey, c->d_icp, c->d_icppart);
-    k_btc_icp_step<<<1, 64, 0, c->stream>>>(nb, c->d_icppart, c->d_icp);
-  }
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(h, c->d_icp, sizeof(*h), hipMemcpyDeviceToHost, c->stream));
-  sp.end();
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int k = 0; k < 9; k++) R[k] = h->R[k];
-  for (int k = 0; k < 3; k++) t[k] = h->t[k];
-  if (eig) for (int k = 0; k < 3; k++) eig[k] = h->eig[k];
-  if (iters) *iters = h->iters;
-  if (ok) *ok = (h->eig[0] > icp_eigval && h->is_conv == 1) ? 1 : 0;
-  return VBA_OK;
-}
-
-
-// ------------------------------------------------------------------------------------------------ descriptor generation
-int vba_btc_default_gen_config(int is_high_fly, vba_btc_gen_config *f) {   // BTC.cpp:3-68
-  if (!f) return VBA_ERR_BAD_ARG;
-  std::memset(f, 0, sizeof(*f));
-  f->useful_corner_num = is_high_fly ? 200 : 100;
-  f->plane_merge_normal_thre = is_high_fly ? 0.3f : 0.1f;
-  f->plane_merge_dis_thre = is_high_fly ? 0.6f : 0.3f;
-  f->plane_detection_thre = is_high_fly ? 0.05f : 0.01f;
-  f->voxel_size = is_high_fly ? 2.0f : 1.0f;
-  f->voxel_init_num = 10;
-  f->proj_plane_num = is_high_fly ? 1 : 2;
-  f->proj_image_resolution = 0.5f;
-  f->proj_image_high_inc = is_high_fly ? 0.2f : 0.1f;
-  f->proj_dis_min = 0.0f;
-  f->proj_dis_max = is_high_fly ? 10.0f : 5.0f;
-  f->summary_min_thre = is_high_fly ? 6.0f : 10.0f;
-  f->line_filter_enable = is_high_fly ? 0 : 1;
-  f->touch_filter_enable = 0;
-  f->descriptor_near_num = 15.0f;
-  f->descriptor_min_len = is_high_fly ? 3.0f : 2.0f;
-  f->descriptor_max_len = 50.0f;
-  f->non_max_suppression_radius = is_high_fly ? 3.0f : 2.0f;
-  f->std_side_resolution = 0.2f;
-  return VBA_OK;
-}
-
-namespace {
-// cut_num of extract_binary: (int)((proj_dis_max_ - proj_dis_min_) / proj_image_high_inc_), the float fields promoted to double
-int btc_cut_num(const vba_btc_gen_config &g) {
-  return (int)(((double)g.proj_dis_max - (double)g.proj_dis_min) / (double)g.proj_image_high_inc);
-}
-size_t btc_max_stds(const vba_btc_gen_config &g) {      // useful_corner_num * C(K - 1, 2)
-  const size_t K1 = (size_t)((int)g.descriptor_near_num - 1);
-  return (size_t)g.useful_corner_num * (K1 * (K1 - 1) / 2);
-}
-BgCfg btc_bg_cfg(const vba_btc_gen_config &g) {
-  BgCfg f;
-  f.useful = g.useful_corner_num; f.vinit = g.voxel_init_num; f.proj_num = g.proj_plane_num; f.line_filter = g.line_filter_enable;
-  f.touch_filter = g.touch_filter_enable; f.K = (int)g.descriptor_near_num; f.cut_num = btc_cut_num(g);
-  f.merge_n = g.plane_merge_normal_thre; f.merge_d = g.plane_merge_dis_thre; f.detect = g.plane_detection_thre; f.vsize = g.voxel_size;
-  f.res = g.proj_image_resolution; f.high_inc = g.proj_image_high_inc; f.dmin = g.proj_dis_min; f.dmax = g.proj_dis_max;
-  f.summ_min = g.summary_min_thre; f.min_len = g.descriptor_min_len; f.max_len = g.descriptor_max_len;
-  f.scale = 1.0 / (double)g.std_side_resolution;
-  const double r = g.non_max_suppression_radius;
-  f.nms_r2 = (float)(r * r);
-  return f;
-}
-int btc_gen_check(const vba_btc_gen_config &g) {
-  const int K = (int)g.descriptor_near_num;
-  if (!(g.useful_corner_num >= 1 && g.voxel_size > 0 && g.voxel_init_num >= 0 && g.proj_plane_num >= 1 && g.proj_plane_num <= BG_MAX_PROJ &&
-        g.proj_image_resolution > 0 && g.proj_image_high_inc > 0 && g.descriptor_near_num >= 3 && K <= BG_MAX_K &&
-        g.descriptor_min_len >= 0 && g.descriptor_max_len <= 2000 && g.std_side_resolution > 0 && g.proj_dis_max >= g.proj_dis_min &&
-        btc_cut_num(g) >= 0 && btc_cut_num(g) <= 64 && btc_max_stds(g) < (size_t)(1 << 26)))
-    return VBA_ERR_BAD_ARG;
-  return VBA_OK;
-}
-int btc_gen_ensure(vba_btc_db *db, int64_t points, int64_t cells, size_t corners) {
-  vba_ctx *c = db->ctx;
-  if (!db->gen) db->gen = new BtcGen();
-  const BtcGen &g = *db->gen;
-  const size_t stds = btc_max_stds(db->gcfg);
-  if ((size_t)points <= g.pts_cap && (size_t)cells <= g.cell_cap && corners <= g.corn_cap && stds <= g.cand_cap &&
-      g.pts_cap / (size_t)(db->gcfg.voxel_init_num + 1) + 1 <= g.plane_cap && g.cnt)
-    return VBA_OK;
-  HIPCHK(c, btcgen_reserve(*db->gen, (size_t)points, (size_t)cells, corners, stds, db->gcfg.voxel_init_num, c->stream));
-  return VBA_OK;
-}
-}  // namespace
-
-int vba_btc_set_gen_config(vba_btc_db *db, const vba_btc_gen_config *cfg) {
-  if (!db || !cfg || btc_gen_check(*cfg)) return VBA_ERR_BAD_ARG;
-  db->gcfg = *cfg;
-  return VBA_OK;
-}
-
-int vba_btc_get_gen_config(const vba_btc_db *db, vba_btc_gen_config *cfg) {
-  if (!db || !cfg) return VBA_ERR_BAD_ARG;
-  *cfg = db->gcfg;
-  return VBA_OK;
-}
-
-int vba_btc_gen_reserve(vba_btc_db *db, int64_t points, int64_t cells, int frames) {
-  if (!db || points < 0 || cells < 0 || frames < 0 || points > (1 << 28) || cells > BG_MAX_CELLS || frames > (1 << 20)) return VBA_ERR_BAD_ARG;
-  vba_ctx *c = db->ctx;
-  HIPCHK(c, hipSetDevice(c->device));
-  int st;
-  if ((st = btc_gen_ensure(db, points, cells, 0))) return st;
-  // plane-cloud room for `frames` more calls at the bound a call reserves (points / (voxel_init_num + 1) + 1 planes each)
-  const int64_t planes = (int64_t)(points / (db->gcfg.voxel_init_num + 1) + 1) * frames;
-  if ((st = vba_btc_reserve(db, 0, (int)db->off.size() - 1 + frames + 1, (int64_t)db->off.back() + planes, 0))) return st;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return VBA_OK;
-}
-
-int vba_btc_gen_allocations(vba_btc_db *db, int *count, int64_t *bytes) {
-  if (!db || !count || !bytes) return VBA_ERR_BAD_ARG;
-  *count = db->gen ? db->gen->allocs : 0;
-  *bytes = db->gen ? (int64_t)db->gen->dev_bytes : 0;
-  return VBA_OK;
-}
-
-// the argument checks of vba_btc_generate_stds that do not concern the cloud itself (no side effect)
-static int btc_generate_check(vba_btc_db *db, int n, int cap, double *rows, uint64_t *bits, int *n_stds) {
-  if (!db || n < 0 || n > (1 << 28) || !n_stds || cap < 0 || (cap > 0 && (!rows || !bits))) return VBA_ERR_BAD_ARG;
-  const vba_btc_gen_config &g = db->gcfg;
-  if ((size_t)cap < btc_max_stds(g) || btc_cut_num(g) > db->cfg.occupy_len) return VBA_ERR_BAD_ARG;
-  return VBA_OK;
-}
-// GenerateSTDescs on a cloud from host memory (xyz) or from the device: with xyz == nullptr and n > 0 the caller has sized the
-// generator for n points (btc_gen_ensure) and enqueued, ahead of the database's stream, the writes of float [n][3] into its point
-// buffer db->gen->xyz; the generator only reads that buffer, so a second attempt after a buffer grew finds it intact
-static int btc_generate_impl(vba_btc_db *db, int n, const float *xyz, int id, int cap, double *rows, uint64_t *bits, int *n_stds) {
-  int chk = btc_generate_check(db, n, cap, rows, bits, n_stds);
-  if (chk) return chk;
-  const vba_btc_gen_config &g = db->gcfg;
-  vba_ctx *c = db->ctx;
-  HIPCHK(c, hipSetDevice(c->device));
-  *n_stds = 0;
-  if (n == 0) {                                 // empty cloud: an empty plane cloud, no corners, no descriptors
-    db->last_loc.clear(); db->last_bits.clear();
-    return vba_btc_push_plane_cloud(db, 0, nullptr, id);
-  }
-  BtcSpan sp(c);
-  int st;
-  const size_t planes = (size_t)n / (size_t)(g.voxel_init_num + 1) + 1;
-  const size_t have = (size_t)db->off.back();
-  if (have + planes > (size_t)INT32_MAX) return VBA_ERR_CAPACITY;
-  if ((st = btc_gen_ensure(db, n, 0, 0))) return st;
-  // room for this frame's plane cloud and offset (the same growth as vba_btc_push_plane_cloud), counted with the generator's own
-  if (have + planes > db->pc_cap) {
-    size_t m = db->pc_cap ? db->pc_cap : 65536;
-    while (m < have + planes) m *= 2;
-    if ((st = btc_grow(c, &db->d_pc, 6 * have, 6 * m))) return st;
-    db->pc_cap = m;
-    db->gen->allocs++;
-  }
-  const int nf = (int)db->off.size();
-  if (nf + 1 > db->off_cap) {
-    int m = db->off_cap * 2;
-    while (m < nf + 1) m *= 2;
-    if ((st = btc_grow(c, &db->d_off, (size_t)nf, (size_t)m))) return st;
-    db->off_cap = m;
-    db->gen->allocs++;
-  }
-  const BgCfg cf = btc_bg_cfg(g);
-  // the image and the corner list grow on overflow and the call runs again (nothing is committed before it succeeds)
-  for (int attempt = 0;; attempt++) {
-    BtcGen &G = *db->gen;
-    HIPCHK(c, btcgen_enqueue(G, cf, n, xyz, db->d_pc + 6 * have, db->d_off + nf, (int)have, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const int *h = G.h_cnt;
-    if (h[BGC_ERR] & 1) return VBA_ERR_BAD_ARG;
-    if (h[BGC_ERR] & 4) return VBA_ERR_CAPACITY;           // a projection image above BG_MAX_CELLS: refused before allocating
-    const bool cells_over = (h[BGC_ERR] & 2) != 0, corn_over = (size_t)h[BGC_NTEMP] > G.corn_cap;
-    if (!cells_over && !corn_over) break;
-    if (attempt >= 2) return VBA_ERR_CAPACITY;
-    if ((st = btc_gen_ensure(db, n, cells_over ? (int64_t)h[BGC_CELLS] : 0, corn_over ? (size_t)h[BGC_NTEMP] : 0))) return st;
-  }
-  const BtcGen &G = *db->gen;
-  const int np = G.h_cnt[BGC_NPL], ns = G.h_cnt[BGC_NSTD], nc = G.h_cnt[BGC_NCORN];
-  db->off.push_back((int)(have + (size_t)np));
-  db->seq.push_back(id);
-  db->last_loc.resize(4 * (size_t)nc); db->last_bits.resize(nc);
-  for (int i = 0; i < nc; i++) {
-    const BgCorner &k = G.h_corn[i];
-    for (int j = 0; j < 3; j++) db->last_loc[4 * (size_t)i + j] = k.loc[j];
-    db->last_loc[4 * (size_t)i + 3] = (double)k.summ;
-    db->last_bits[i] = k.bits;
-  }
-  // rows: [triangle center frame A.loc B.loc C.loc A.summ B.summ C.summ], masks of A, B, C
-  for (int i = 0; i < ns; i++) {
-    const BgStd &t = G.h_stds[i];
-    double *r = rows + (size_t)i * VBA_BTC_ROW_LEN;
-    const int v[3] = {t.a, t.b, t.c};
-    for (int j = 0; j < 3; j++) { r[j] = t.tri[j]; r[3 + j] = t.cen[j]; }
-    r[6] = (double)db->n_add;
-    for (int u = 0; u < 3; u++) {
-      const BgCorner &k = G.h_corn[v[u]];
-      for (int j = 0; j < 3; j++) r[7 + 3 * u + j] = k.loc[j];
-      r[16 + u] = (double)k.summ;
-      bits[3 * (size_t)i + u] = k.bits;
-    }
-  }
-  *n_stds = ns;
-  return VBA_OK;
-}
-
-int vba_btc_generate_stds(vba_btc_db *db, int n, const float *xyz, int id, int cap, double *rows, uint64_t *bits, int *n_stds) {
-  if (n > 0 && !xyz) return VBA_ERR_BAD_ARG;
-  return btc_generate_impl(db, n, xyz, id, cap, rows, bits, n_stds);
-}
-
-int vba_btc_plane_cloud(vba_btc_db *db, int frame, int cap, float *xyz_normal, int *n) {
-  if (!db || !n || frame < 0 || frame >= (int)db->off.size() - 1 || cap < 0 || (cap > 0 && !xyz_normal)) return VBA_ERR_BAD_ARG;
-  vba_ctx *c = db->ctx;
-  HIPCHK(c, hipSetDevice(c->device));
-  const int b = db->off[frame], e = db->off[frame + 1];
-  *n = e - b;
-  const int w = (e - b) < cap ? (e - b) : cap;
-  if (w > 0) HIPCHK(c, hipMemcpyAsync(xyz_normal, db->d_pc + 6 * (size_t)b, (size_t)w * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return VBA_OK;
-}
-
-int vba_btc_last_corners(vba_btc_db *db, int cap, double *loc_summary, uint64_t *bits, int *n) {
-  if (!db || !n || cap < 0 || (cap > 0 && (!loc_summary || !bits))) return VBA_ERR_BAD_ARG;
-  const int k = (int)db->last_bits.size();
-  *n = k;
-  const int w = k < cap ? k : cap;
-  for (int i = 0; i < w; i++) {
-    for (int j = 0; j < 4; j++) loc_summary[4 * (size_t)i + j] = db->last_loc[4 * (size_t)i + j];
-    bits[i] = db->last_bits[i];
-  }
-  return VBA_OK;
-}
-
-// ---------------------------------------------------------------- pose-graph optimisation (vba_kernels_pgo.hpp)
-int vba_pgo_optimize(vba_ctx *c, int n, double *poses, int m, const double *edges, int n_prior, const double *priors, int n_updates,
-                     double relin_threshold, double *stats) {
-  if (!c || n < 1 || !poses || m < 0 || n_prior < 0 || (m > 0 && !edges) || (n_prior > 0 && !priors) || n_updates < 1 ||
-      !(relin_threshold >= 0.0) || !std::isfinite(relin_threshold))
-    return VBA_ERR_BAD_ARG;
-  const int F = m + n_prior;
-  // ---- validation and factor table (edges first, then priors)
-  std::vector<int> fi(F), fj(F);
-  std::vector<double> fz((size_t)F * 18);
-  auto index_of = [n](double x, int &k) { if (!(x >= 0.0 && x < (double)n) || x != std::floor(x)) return false; k = (int)x; return true; };
-  for (size_t q = 0; q < (size_t)n * 12; q++) if (!std::isfinite(poses[q])) return VBA_ERR_BAD_ARG;
-  for (int f = 0; f < F; f++) {
-    const bool pr = f >= m;
-    const double *row = pr ? priors + (size_t)(f - m) * 19 : edges + (size_t)f * 20;
-    const double *z = pr ? row + 1 : row + 2;
-    int i, j = -1;
-    if (!index_of(row[0], i) || (!pr && (!index_of(row[1], j) || i == j))) return VBA_ERR_BAD_ARG;
-    for (int q = 0; q < 18; q++) {
-      if (!std::isfinite(z[q]) || (q >= 12 && !(z[q] > 0.0))) return VBA_ERR_BAD_ARG;
-      fz[(size_t)f * 18 + q] = q < 12 ? z[q] : 1.0 / z[q];
-    }
-    fi[f] = i; fj[f] = j;
-  }
-  // ---- distinct neighbour pairs, components, skeleton
-  std::vector<long long> pk;
-  pk.reserve(m);
-  for (int f = 0; f < m; f++) pk.push_back((long long)std::min(fi[f], fj[f]) * n + std::max(fi[f], fj[f]));
-  std::sort(pk.begin(), pk.end());
-  pk.erase(std::unique(pk.begin(), pk.end()), pk.end());
-  const int NPAIR = (int)pk.size(), NB = n + NPAIR;
-  auto pair_block = [&](int a, int b) {   // block code of H(a, b): blk * 2 + transposed
-    if (a == b) return 2 * a;
-    const long long key = (long long)std::min(a, b) * n + std::max(a, b);
-    const int p = (int)(std::lower_bound(pk.begin(), pk.end(), key) - pk.begin());
-    return 2 * (n + p) + (a > b ? 1 : 0);
-  };
-  std::vector<int> nb_off(n + 1, 0), nb(2 * (size_t)NPAIR);
-  for (long long key : pk) { nb_off[key / n + 1]++; nb_off[key % n + 1]++; }
-  for (int k = 0; k < n; k++) nb_off[k + 1] += nb_off[k];
-  {
-    std::vector<int> fill(nb_off.begin(), nb_off.end() - 1);
-    for (long long key : pk) { const int a = (int)(key / n), b = (int)(key % n); nb[fill[a]++] = b; nb[fill[b]++] = a; }
-  }
-  std::vector<int> uf(n);
-  for (int k = 0; k < n; k++) uf[k] = k;
-  std::function<int(int)> root = [&](int k) { while (uf[k] != k) { uf[k] = uf[uf[k]]; k = uf[k]; } return k; };
-  for (long long key : pk) { const int a = root((int)(key / n)), b = root((int)(key % n)); if (a != b) uf[std::max(a, b)] = std::min(a, b); }
-  std::vector<char> has_prior(n, 0), comp_prior(n, 0);
-  for (int f = m; f < F; f++) has_prior[fi[f]] = 1;
-  for (int k = 0; k < n; k++) if (has_prior[k]) comp_prior[root(k)] = 1;
-  for (int k = 0; k < n; k++)
-    if (!comp_prior[root(k)]) { c->set_error("vba_pgo_optimize: a connected component holds no prior"); return VBA_ERR_SINGULAR; }
-  std::vector<int> node_skel(n, -1), skel_node;
-  auto is_path = [&](int k) { return !has_prior[k] && nb_off[k + 1] - nb_off[k] <= 2; };
-  for (int k = 0; k < n; k++) if (!is_path(k)) { node_skel[k] = (int)skel_node.size(); skel_node.push_back(k); }
-  const int K = (int)skel_node.size();
-  // ---- segments: maximal runs of path nodes, oriented so that a single attachment is B (eliminated towards it: no fill)
-  std::vector<int> seg_off(1, 0), seg_nodes, seg_att, seg_ecode, seg_ccode;
-  std::vector<char> seen(n, 0);
-  for (int v0 = 0; v0 < n; v0++) {
-    if (!is_path(v0) || seen[v0]) continue;
-    int end = v0, prev = -1;                      // walk to one end of the run
-    for (;;) {
-      int nxt = -1;
-      for (int e = nb_off[end]; e < nb_off[end + 1]; e++) if (nb[e] != prev && is_path(nb[e])) { nxt = nb[e]; break; }
-      if (nxt < 0 || nxt == v0) break;            // (nxt == v0: a cycle of path nodes, impossible once every component has a prior)
-      prev = end; end = nxt;
-    }
-    std::vector<int> run;
-    prev = -1;
-    for (int cur = end; cur >= 0;) {
-      run.push_back(cur); seen[cur] = 1;
-      int nxt = -1;
-      for (int e = nb_off[cur]; e < nb_off[cur + 1]; e++) if (nb[e] != prev && is_path(nb[e]) && !seen[nb[e]]) { nxt = nb[e]; break; }
-      prev = cur; cur = nxt;
-    }
-    const int L = (int)run.size();
-    auto skel_nb = [&](int node, int other_path) {     // the skeleton neighbours of an end node (other than its run neighbour)
-      std::vector<int> r;
-      for (int e = nb_off[node]; e < nb_off[node + 1]; e++) if (nb[e] != other_path && !is_path(nb[e])) r.push_back(nb[e]);
-      return r;
-    };
-    int A = -1, B = -1;
-    if (L == 1) {
-      std::vector<int> sn = skel_nb(run[0], -1);
-      if (sn.size() == 2) { A = sn[0]; B = sn[1]; } else if (sn.size() == 1) B = sn[0];
-    } else {
-      std::vector<int> s0 = skel_nb(run[0], run[1]), s1 = skel_nb(run[L - 1], run[L - 2]);
-      A = s0.empty() ? -1 : s0[0]; B = s1.empty() ? -1 : s1[0];
-      if (B < 0) { std::reverse(run.begin(), run.end()); std::swap(A, B); }
-    }
-    if (B < 0) { c->set_error("vba_pgo_optimize: a chain without a skeleton node"); return VBA_ERR_SINGULAR; }
-    for (int k = 0; k < L; k++) {
-      seg_nodes.push_back(run[k]);
-      seg_ccode.push_back(k + 1 < L ? pair_block(run[k], run[k + 1]) : pair_block(run[k], B));
-    }
-    seg_att.push_back(A >= 0 ? node_skel[A] : -1); seg_att.push_back(node_skel[B]);
-    seg_ecode.push_back(A >= 0 ? pair_block(run[0], A) : -1);
-    seg_off.push_back((int)seg_nodes.size());
-  }
-  const int S = (int)seg_off.size() - 1, LS = (int)seg_nodes.size();
-  // ---- block CSR in factor order
-  std::vector<int> blk_off(NB + 1, 0), blk_ent;
-  auto pair_index = [&](int a, int b) { return pair_block(a, b) >> 1; };
-  for (int f = 0; f < F; f++) { blk_off[fi[f] + 1]++; if (fj[f] >= 0) { blk_off[fj[f] + 1]++; blk_off[pair_index(fi[f], fj[f]) + 1]++; } }
-  for (int b = 0; b < NB; b++) blk_off[b + 1] += blk_off[b];
-  blk_ent.resize(blk_off[NB] > 0 ? blk_off[NB] : 1);
-  {
-    std::vector<int> fill(blk_off.begin(), blk_off.end() - 1);
-    for (int f = 0; f < F; f++) {
-      blk_ent[fill[fi[f]]++] = 4 * f + 0;
-      if (fj[f] >= 0) {
-        blk_ent[fill[fj[f]]++] = 4 * f + 1;
-        blk_ent[fill[pair_index(fi[f], fj[f])]++] = 4 * f + (fi[f] < fj[f] ? 2 : 3);
-      }
-    }
-  }
-  // ---- skeleton blocks: diagonal, direct skeleton pairs, segment A-B pairs; CSR of segment contributions in segment order
-  std::map<std::pair<int, int>, int> sbm;
-  for (int p = 0; p < K; p++) sbm[{p, p}] = 0;
-  for (long long key : pk) {
-    const int a = node_skel[key / n], b = node_skel[key % n];
-    if (a >= 0 && b >= 0) sbm[{std::max(a, b), std::min(a, b)}] = 0;
-  }
-  for (int s = 0; s < S; s++) { const int a = seg_att[2 * s], b = seg_att[2 * s + 1]; if (a >= 0 && a != b) sbm[{std::max(a, b), std::min(a, b)}] = 0; }
-  const int NSB = (int)sbm.size();
-  std::vector<int> sb_pq, sb_base;
-  { int b = 0; for (auto &kv : sbm) { kv.second = b++; sb_pq.push_back(kv.first.first); sb_pq.push_back(kv.first.second);
-      const int na = skel_node[kv.first.first], nbb = skel_node[kv.first.second];
-      const long long key = (long long)std::min(na, nbb) * n + std::max(na, nbb);
-      sb_base.push_back(na == nbb || std::binary_search(pk.begin(), pk.end(), key) ? pair_block(na, nbb) : -1); } }
-  std::vector<std::vector<int>> sbl(NSB);
-  for (int s = 0; s < S; s++) {
-    const int a = seg_att[2 * s], b = seg_att[2 * s + 1];
-    if (a >= 0) sbl[sbm[{a, a}]].push_back(4 * s + 0);
-    sbl[sbm[{b, b}]].push_back(4 * s + 1);
-    if (a >= 0) {
-      if (a == b) { sbl[sbm[{a, a}]].push_back(4 * s + 2); sbl[sbm[{a, a}]].push_back(4 * s + 3); }
-      else if (b > a) sbl[sbm[{b, a}]].push_back(4 * s + 2);    // rows B, columns A: S_BA
-      else sbl[sbm[{a, b}]].push_back(4 * s + 3);               // rows A, columns B: S_BA^T
-    }
-  }
-  std::vector<int> sb_off(1, 0), sb_ent;
-  for (auto &l : sbl) { sb_ent.insert(sb_ent.end(), l.begin(), l.end()); sb_off.push_back((int)sb_ent.size()); }
-  // ---- device memory: one grow-only arena for the structure and work areas, one for the dense skeleton system
-  const int n6 = 6 * K, NP = (n6 + 7) / 8 * 8, ld = (NP + 63) / 64 * 64;
-  size_t bytes = 0;
-  auto take = [&](size_t b) { const size_t o = bytes; bytes += (b + 255) & ~(size_t)255; return o; };
-  const int U = n_updates;
-  const size_t o_theta = take((size_t)n * 96), o_fz = take((size_t)F * 144), o_fi = take((size_t)F * 4), o_fj = take((size_t)F * 4),
-      o_slot = take((size_t)F * PGO_SLOT * 8), o_blk = take((size_t)NB * 288), o_g = take((size_t)n * 48),
-      o_blkoff = take((size_t)(NB + 1) * 4), o_blkent = take(blk_ent.size() * 4), o_segoff = take(seg_off.size() * 4),
-      o_segnodes = take((size_t)LS * 4), o_segatt = take((size_t)S * 8), o_sege = take((size_t)S * 4), o_segc = take((size_t)LS * 4),
-      o_segY = take((size_t)LS * PGO_Y * 8), o_segout = take((size_t)S * PGO_SEGOUT * 8), o_skel = take((size_t)K * 4),
-      o_sbpq = take((size_t)NSB * 8), o_sbbase = take((size_t)NSB * 4), o_sboff = take(sb_off.size() * 4), o_sbent = take(sb_ent.size() * 4),
-      o_dx = take((size_t)n * 48), o_res = take((size_t)U * 24 + 8);   // cost[U] | mx[U] | cnt[U] | status
-  HIPCHK(c, hipSetDevice(c->device));
-  // grow-only buffers owned by the context; a size the device cannot hold is VBA_ERR_CAPACITY (the old buffer is released first)
-  auto grow = [&](void **buf, size_t &have, size_t want, const char *what) -> int {
-    if (want <= have) return VBA_OK;
-    if (*buf) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(*buf)); *buf = nullptr; have = 0; }
-    size_t fr = 0, tot = 0;
-    HIPCHK(c, hipMemGetInfo(&fr, &tot));
-    const hipError_t e = want > fr ? hipErrorOutOfMemory : hipMalloc(buf, want);
-    if (e == hipErrorOutOfMemory) {
-      (void)hipGetLastError();                      // a refused allocation must not surface in a later call's error check
-      *buf = nullptr;
-      c->set_error(std::string("vba_pgo_optimize: the ") + what + " needs " + std::to_string(want) + " bytes, " + std::to_string(fr) + " free");
-      return VBA_ERR_CAPACITY;
-    }
-    HIPCHK(c, e);
-    have = want;
-    return VBA_OK;
-  };
-  const size_t abytes = ((size_t)(NP + 1) * ld + (size_t)(NP + 1) * 8) * 8;
-  if (int r = grow((void **)&c->d_pgo, c->pgo_bytes, bytes, "graph structure")) return r;
-  if (int r = grow((void **)&c->d_pgoAb, c->pgoAb_bytes, abytes, "dense skeleton system (8 (6K)^2 bytes)")) return r;
-  char *d = c->d_pgo;
-  PgoView v{};
-  v.n = n; v.F = F; v.NB = NB; v.S = S; v.K = K; v.NSB = NSB; v.U = U; v.NP = NP; v.ld = ld; v.thr = relin_threshold;
-  v.theta = (double *)(d + o_theta); v.fz = (const double *)(d + o_fz); v.fi = (const int *)(d + o_fi); v.fj = (const int *)(d + o_fj);
-  v.slot = (double *)(d + o_slot); v.blk = (double *)(d + o_blk); v.g = (double *)(d + o_g);
-  v.blk_off = (const int *)(d + o_blkoff); v.blk_ent = (const int *)(d + o_blkent);
-  v.seg_off = (const int *)(d + o_segoff); v.seg_nodes = (const int *)(d + o_segnodes); v.seg_att = (const int *)(d + o_segatt);
-  v.seg_ecode = (const int *)(d + o_sege); v.seg_ccode = (const int *)(d + o_segc); v.segY = (double *)(d + o_segY);
-  v.segout = (double *)(d + o_segout); v.skel_node = (const int *)(d + o_skel); v.sb_pq = (const int *)(d + o_sbpq);
-  v.sb_base = (const int *)(d + o_sbbase); v.sb_off = (const int *)(d + o_sboff); v.sb_ent = (const int *)(d + o_sbent);
-  v.Ab = c->d_pgoAb; v.Tb = c->d_pgoAb + (size_t)(NP + 1) * ld; v.dx = (double *)(d + o_dx);
-  v.cost = (double *)(d + o_res); v.mx = (unsigned long long *)(d + o_res + (size_t)U * 8); v.cnt = (int *)(d + o_res + (size_t)U * 16);
-  v.status = (int *)(d + o_res + (size_t)U * 20);
-  hipStream_t st = c->stream;
-  // the sources are pageable locals of this call: on a failed copy the stream is drained before they go out of scope
-  hipError_t ue = hipSuccess;
-  auto up = [&](size_t off, const void *src, size_t b) { if (ue == hipSuccess && b) ue = hipMemcpyAsync(d + off, src, b, hipMemcpyHostToDevice, st); };
-  up(o_theta, poses, (size_t)n * 96);
-  up(o_fz, fz.data(), fz.size() * 8); up(o_fi, fi.data(), (size_t)F * 4); up(o_fj, fj.data(), (size_t)F * 4);
-  up(o_blkoff, blk_off.data(), blk_off.size() * 4); up(o_blkent, blk_ent.data(), blk_ent.size() * 4);
-  up(o_segoff, seg_off.data(), seg_off.size() * 4); up(o_segnodes, seg_nodes.data(), (size_t)LS * 4);
-  up(o_segatt, seg_att.data(), (size_t)S * 8); up(o_sege, seg_ecode.data(), (size_t)S * 4);
-  up(o_segc, seg_ccode.data(), (size_t)LS * 4); up(o_skel, skel_node.data(), (size_t)K * 4);
-  up(o_sbpq, sb_pq.data(), (size_t)NSB * 8); up(o_sbbase, sb_base.data(), (size_t)NSB * 4);
-  up(o_sboff, sb_off.data(), sb_off.size() * 4); up(o_sbent, sb_ent.data(), sb_ent.size() * 4);
-  if (ue != hipSuccess) { hipStreamSynchronize(st); HIPCHK(c, ue); }
-  HIPCHK(c, hipMemsetAsync(d + o_res, 0, (size_t)U * 24 + 8, st));
-  auto grid = [](long long cnt, int bs) { return dim3((unsigned)((cnt + bs - 1) / bs)); };
-  TimedSpan sp;
-  span_begin(c, "pgo", sp);
-  for (int u = 0; u < U; u++) {
-    if (F > 0) {
-      hipLaunchKernelGGL(k_pgo_linearize, grid(F, 256), dim3(256), 0, st, v);
-      hipLaunchKernelGGL(k_pgo_cost, dim3(1), dim3(256), 0, st, v, u);
-    }
-    hipLaunchKernelGGL(k_pgo_assemble, grid(NB, 256), dim3(256), 0, st, v);
-    if (S > 0) hipLaunchKernelGGL(k_pgo_seg_elim, grid(S, 64), dim3(64), 0, st, v);
-    hipLaunchKernelGGL(k_pgo_skel_fill, grid((long long)(NP + 1) * NP, 256), dim3(256), 0, st, v);
-    hipLaunchKernelGGL(k_pgo_skel_scatter, grid(NSB, 256), dim3(256), 0, st, v);
-    for (int k0 = 0; k0 < NP; k0 += 8) {
-      hipLaunchKernelGGL(k_bigl_panel, dim3(1), dim3(256), 0, st, v.Ab, v.Tb, NP, ld, k0);
-      const int kn = k0 + 8;
-      const int nt = (NP + 1 - kn + 63) / 64;
-      if (nt > 0) hipLaunchKernelGGL(k_bigl_update, dim3(nt * (nt + 1) / 2), dim3(256), 0, st, v.Ab, v.Tb, NP, ld, k0);
-    }
-    hipLaunchKernelGGL(k_pgo_pivots, grid(n6, 256), dim3(256), 0, st, v);
-    for (int lo = ((n6 - 1) / 64) * 64; lo >= 0; lo -= 64) {
-      hipLaunchKernelGGL(k_bigl_bs_tri, dim3(1), dim3(64), 0, st, v.Ab, NP, ld, n6, lo);
-      if (lo > 0) hipLaunchKernelGGL(k_bigl_bs_gemv, grid(lo, 256), dim3(256), 0, st, v.Ab, NP, ld, n6, lo);
-    }
-    hipLaunchKernelGGL(k_pgo_skel_dx, grid(K, 256), dim3(256), 0, st, v);
-    if (S > 0) hipLaunchKernelGGL(k_pgo_seg_back, grid(S, 64), dim3(64), 0, st, v);
-    hipLaunchKernelGGL(k_pgo_relin, grid(n, 256), dim3(256), 0, st, v, u);
-  }
-  span_end(c, "pgo", sp);
-  HIPCHK(c, hipGetLastError());
-  std::vector<double> out((size_t)n * 12);
-  std::vector<char> res((size_t)U * 24 + 8);
-  hipError_t de = hipMemcpyAsync(out.data(), v.theta, out.size() * 8, hipMemcpyDeviceToHost, st);
-  if (de == hipSuccess) de = hipMemcpyAsync(res.data(), d + o_res, res.size(), hipMemcpyDeviceToHost, st);
-  const hipError_t se = hipStreamSynchronize(st);   // always drained before out / res go out of scope
-  HIPCHK(c, de);
-  HIPCHK(c, se);
-  int status;
-  std::memcpy(&status, res.data() + (size_t)U * 20, 4);
-  if (status == PGO_SINGULAR) { c->set_error("vba_pgo_optimize: non-positive or non-finite pivot"); return VBA_ERR_SINGULAR; }
-  std::memcpy(poses, out.data(), out.size() * 8);
-  if (stats)
-    for (int u = 0; u < U; u++) {
-      double cost, mx; int cnt;
-      std::memcpy(&cost, res.data() + (size_t)u * 8, 8);
-      std::memcpy(&mx, res.data() + (size_t)U * 8 + (size_t)u * 8, 8);
-      std::memcpy(&cnt, res.data() + (size_t)U * 16 + (size_t)u * 4, 4);
-      stats[3 * u] = cnt; stats[3 * u + 1] = cost; stats[3 * u + 2] = mx;
-    }
-  return VBA_OK;
-}
 
 // ---------------------------------------------------------------- diagnostic: one LM linear solve through the production kernels
 // The caller's system is written into the buffers the solve kernel reads, in their production layout, and the kernel is launched
@@ -3873,854 +2426,6 @@ int vba_debug_solve(vba_ctx *c, int kind, int W, int flags, const double *H, con
   HIPCHK(c, hipMemcpyAsync(dx, d_dx, (size_t)ncand * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int b = 0; b < ncand; b++) q1[b] = h->q1_spec[b];
-  return VBA_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------ keyframe store (vba_kf_*)
-#include "vba_kernels_kf.hpp"
-
-struct vba_kf_store {
-  vba_ctx *ctx = nullptr;
-  // the keyframes: points (their own frame, float values in doubles) and covariance diagonals, ragged by off
-  double *d_pnt = nullptr; float *d_var = nullptr; size_t cap = 0;
-  std::vector<int> off{0};
-  struct Meta { double x0[12]; int id; double jour; int exist; };
-  std::vector<Meta> kf;
-  // scratch of one merge of up to mcap points: staged host input, merged cloud (also the world points of a load), gathered covariance
-  // diagonals, per-voxel counts, the down-sampler's work area; pinned: gathered diagonals of a host covariance array
-  size_t mcap = 0;
-  double *d_src = nullptr, *d_merge = nullptr, *d_mdiag = nullptr, *h_diag = nullptr;
-  int *d_cnt = nullptr; char *d_ws = nullptr; size_t ws_bytes = 0;
-  // per-scan transforms [tcap][12] and offsets [tcap + 1]: pinned image and device copy; the voxel count of a build (pinned)
-  int tcap = 0; char *h_tab = nullptr, *d_tab = nullptr; int *h_n = nullptr;
-  hipEvent_t ev = nullptr;
-  int allocs = 0; int64_t bytes = 0;
-  int hist = 0; std::vector<float> hist_pos;   // history_kfsize, pl_kdmap
-  int last_m = 0;                              // voxels of the last build (their counts stay in d_cnt)
-};
-
-namespace {
-
-size_t kf_tab_bytes(int t) { return (size_t)t * 12 * sizeof(double) + (((size_t)t + 1) * sizeof(int) + 15 & ~(size_t)15); }
-
-template <class T>
-int kf_alloc(vba_kf_store *s, T **p, size_t n) {
-  vba_ctx *c = s->ctx;
-  if (*p) hipFree(*p);
-  *p = nullptr;
-  HIPCHK(c, hipMalloc((void **)p, (n ? n : 1) * sizeof(T)));
-  s->allocs++; s->bytes += (int64_t)(n * sizeof(T));
-  return VBA_OK;
-}
-
-// layout of the down-sampler's work area for n points
-size_t kf_ws_layout(vba_ctx *c, int n, bool det, char *base, DsWork *w, int *status) {
-  int cap = 1024;
-  while (cap < 2 * n) cap <<= 1;
-  unsigned int key_bits = 1;
-  while ((1u << key_bits) < (unsigned)cap) key_bits++;
-  const int nb = (n + 255) / 256;
-  const size_t b_i = (((size_t)n * sizeof(int)) + 255) & ~(size_t)255, b_tab = (size_t)cap * sizeof(DsSlot),
-               b_blk = (((size_t)nb + 2) * sizeof(int) + 255) & ~(size_t)255;
-  size_t tmp = 0;
-  if (det && sort_pairs_u32(nullptr, tmp, nullptr, nullptr, nullptr, nullptr, (size_t)n, key_bits, c->stream) != hipSuccess) { *status = VBA_ERR_HIP; return 0; }
-  tmp = (tmp + 255) & ~(size_t)255;
-  if (w) {
-    w->tab = (DsSlot *)base; w->cap = cap; w->key_bits = key_bits;
-    w->slot = (int *)(base + b_tab); w->blk = (int *)(base + b_tab + b_i); w->n_out = w->blk + nb;
-    if (det) {
-      char *sb = base + b_tab + b_i + b_blk;
-      w->skey = (unsigned int *)sb; w->idx = (int *)(sb + b_i); w->sidx = (int *)(sb + 2 * b_i); w->tmp = sb + 3 * b_i; w->tmp_bytes = tmp;
-    }
-  }
-  *status = VBA_OK;
-  return b_tab + b_i + b_blk + (det ? 3 * b_i + tmp : 0);
-}
-
-// grow-only: the keyframe arrays move (device-to-device copy, the old blocks are freed after a synchronise)
-int kf_ensure_rows(vba_kf_store *s, size_t need) {
-  if (need <= s->cap) return VBA_OK;
-  vba_ctx *c = s->ctx;
-  size_t m = s->cap ? s->cap : 65536;
-  while (m < need) m *= 2;
-  double *np = nullptr; float *nv = nullptr;
-  HIPCHK(c, hipMalloc((void **)&np, m * 3 * sizeof(double)));
-  if (hipMalloc((void **)&nv, m * 3 * sizeof(float)) != hipSuccess) { hipFree(np); c->set_error("keyframe store: out of device memory"); return VBA_ERR_HIP; }
-  const size_t have = (size_t)s->off.back();
-  if (have) {
-    HIPCHK(c, hipMemcpyAsync(np, s->d_pnt, have * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(nv, s->d_var, have * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (s->d_pnt) hipFree(s->d_pnt);
-  if (s->d_var) hipFree(s->d_var);
-  s->d_pnt = np; s->d_var = nv; s->cap = m;
-  s->allocs += 2; s->bytes += (int64_t)(m * 3 * (sizeof(double) + sizeof(float)));
-  return VBA_OK;
-}
-
-int kf_ensure_merge(vba_kf_store *s, size_t need) {
-  if (need <= s->mcap) return VBA_OK;
-  vba_ctx *c = s->ctx;
-  size_t m = s->mcap ? s->mcap : 65536;
-  while (m < need) m *= 2;
-  if (m > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  int st = VBA_OK;
-  const size_t ws = kf_ws_layout(c, (int)m, true, nullptr, nullptr, &st);
-  if (st) return st;
-  if ((st = kf_alloc(s, &s->d_src, 3 * m)) || (st = kf_alloc(s, &s->d_merge, 3 * m)) || (st = kf_alloc(s, &s->d_mdiag, 3 * m)) ||
-      (st = kf_alloc(s, &s->d_cnt, m)) || (st = kf_alloc(s, &s->d_ws, ws)))
-    return st;
-  if (s->h_diag) hipHostFree(s->h_diag);
-  s->h_diag = nullptr;
-  HIPCHK(c, hipHostMalloc((void **)&s->h_diag, 3 * m * sizeof(double), hipHostMallocDefault));
-  s->allocs++;
-  s->ws_bytes = ws; s->mcap = m;
-  return VBA_OK;
-}
-
-int kf_ensure_tab(vba_kf_store *s, int k) {
-  if (k <= s->tcap) return VBA_OK;
-  vba_ctx *c = s->ctx;
-  int t = s->tcap ? s->tcap : 64;
-  while (t < k) t *= 2;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (s->h_tab) hipHostFree(s->h_tab);
-  s->h_tab = nullptr;
-  HIPCHK(c, hipHostMalloc((void **)&s->h_tab, kf_tab_bytes(t), hipHostMallocDefault));
-  s->allocs++;
-  int st = kf_alloc(s, &s->d_tab, kf_tab_bytes(t));
-  if (st) return st;
-  s->tcap = t;
-  return VBA_OK;
-}
-
-// Host half of the merge (include/voxelba.h, "order of operations"): T = [dR, dp] of a cloud at pose x into the frame of pose xc
-void kf_delta(const double *xc, const double *x, double *T) {
-  volatile double a, b, e;     // every product and sum rounded on its own, whatever the host compiler would contract
-  for (int r = 0; r < 3; r++)
-    for (int cc = 0; cc < 3; cc++) {
-      a = xc[0 * 3 + r] * x[0 * 3 + cc]; b = xc[1 * 3 + r] * x[1 * 3 + cc]; a = a + b; e = xc[2 * 3 + r] * x[2 * 3 + cc];
-      T[3 * r + cc] = a + e;
-    }
-  const double d0 = x[9] - xc[9], d1 = x[10] - xc[10], d2 = x[11] - xc[11];
-  for (int r = 0; r < 3; r++) {
-    a = xc[0 * 3 + r] * d0; b = xc[1 * 3 + r] * d1; a = a + b; e = xc[2 * 3 + r] * d2;
-    T[9 + r] = a + e;
-  }
-}
-
-// the transform table of k clouds with poses [k][12] (xc = the last) and row offsets rel [k + 1] -> pinned image -> device, on st
-int kf_upload_tab(vba_kf_store *s, int k, const double *const *poses, const int *rel, hipStream_t st) {
-  vba_ctx *c = s->ctx;
-  double *T = (double *)s->h_tab;
-  int *o = (int *)(s->h_tab + (size_t)s->tcap * 12 * sizeof(double));
-  for (int i = 0; i < k; i++) kf_delta(poses[k - 1], poses[i], T + 12 * i);
-  for (int i = 0; i <= k; i++) o[i] = rel[i];
-  HIPCHK(c, hipMemcpyAsync(s->d_tab, s->h_tab, kf_tab_bytes(s->tcap), hipMemcpyHostToDevice, st));
-  return VBA_OK;
-}
-const double *kf_dev_xf(const vba_kf_store *s) { return (const double *)s->d_tab; }
-const int *kf_dev_off(const vba_kf_store *s) { return (const int *)(s->d_tab + (size_t)s->tcap * 12 * sizeof(double)); }
-
-bool kf_pose_ok(const double *p) { for (int i = 0; i < 12; i++) if (!std::isfinite(p[i])) return false; return true; }
-
-}  // namespace
-
-extern "C" {
-
-int vba_kf_create(vba_ctx *c, vba_kf_store **out) {
-  if (!c || !out) return VBA_ERR_BAD_ARG;
-  *out = nullptr;
-  HIPCHK(c, hipSetDevice(c->device));
-  vba_kf_store *s = new vba_kf_store();
-  s->ctx = c;
-  int st = kf_ensure_tab(s, 64);
-  if (!st && hipHostMalloc((void **)&s->h_n, 64, hipHostMallocDefault) != hipSuccess) st = VBA_ERR_HIP;
-  if (!st && hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) st = VBA_ERR_HIP;
-  if (st) { vba_kf_destroy(s); return st; }
-  s->allocs++;
-  *out = s;
-  return VBA_OK;
-}
-
-void vba_kf_destroy(vba_kf_store *s) {
-  if (!s) return;
-  hipSetDevice(s->ctx->device);
-  hipStreamSynchronize(s->ctx->stream);
-  void *d[] = {s->d_pnt, s->d_var, s->d_src, s->d_merge, s->d_mdiag, s->d_cnt, s->d_ws, s->d_tab};
-  for (void *p : d) if (p) hipFree(p);
-  if (s->h_diag) hipHostFree(s->h_diag);
-  if (s->h_tab) hipHostFree(s->h_tab);
-  if (s->h_n) hipHostFree(s->h_n);
-  if (s->ev) hipEventDestroy(s->ev);
-  delete s;
-}
-
-int vba_kf_reserve(vba_kf_store *s, int64_t points, int keyframes, int64_t merge_points) {
-  if (!s || points < 0 || keyframes < 0 || merge_points < 0 || points > ((int64_t)1 << 30) || merge_points > ((int64_t)1 << 28) || keyframes > (1 << 24))
-    return VBA_ERR_BAD_ARG;
-  vba_ctx *c = s->ctx;
-  HIPCHK(c, hipSetDevice(c->device));
-  int st;
-  if (merge_points > 0 && (st = kf_ensure_merge(s, (size_t)merge_points))) return st;
-  // a build writes its kept cloud straight behind the last keyframe, and that cloud is bounded only by the merged one
-  if (points + merge_points > 0 && (st = kf_ensure_rows(s, (size_t)(points + merge_points)))) return st;
-  s->off.reserve((size_t)keyframes + 1); s->kf.reserve((size_t)keyframes); s->hist_pos.reserve(3 * (size_t)keyframes);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return VBA_OK;
-}
-
-int vba_kf_allocations(vba_kf_store *s, int *count, int64_t *bytes) {
-  if (!s || !count || !bytes) return VBA_ERR_BAD_ARG;
-  *count = s->allocs; *bytes = s->bytes;
-  return VBA_OK;
-}
-
-int vba_kf_size(vba_kf_store *s) { return s ? (int)s->kf.size() : 0; }
-
-int vba_kf_build(vba_kf_store *s, int k, const int *offsets, const double *pnt, const double *var, const double *poses, double voxel_size, int id,
-                 double jour, vba_btc_db *db, int cap, double *rows, uint64_t *bits, int *n_stds, int *n_points) {
-  if (!s || k < 1 || !offsets || !poses || !n_points || !(voxel_size > 0) || (!var && voxel_size < 0.001)) return VBA_ERR_BAD_ARG;
-  for (int i = 0; i < k; i++) if (offsets[i] < 0 || offsets[i + 1] < offsets[i]) return VBA_ERR_BAD_ARG;
-  const int off0 = offsets[0], n = offsets[k] - off0;
-  if (n > (1 << 28) || (n > 0 && !pnt)) return VBA_ERR_BAD_ARG;
-  for (int i = 0; i < k; i++) if (!kf_pose_ok(poses + 12 * i)) return VBA_ERR_BAD_ARG;
-  vba_ctx *c = s->ctx;
-  const size_t N = (size_t)s->off.back();
-  if (N + (size_t)n > (size_t)INT32_MAX) return VBA_ERR_CAPACITY;
-  int st;
-  if (db) {
-    if (db->ctx->device != c->device) return VBA_ERR_BAD_ARG;
-    if ((st = btc_generate_check(db, n, cap, rows, bits, n_stds))) return st;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((st = kf_ensure_tab(s, k)) || (st = kf_ensure_merge(s, (size_t)n)) || (st = kf_ensure_rows(s, N + (size_t)n))) return st;
-  if (db && n > 0 && (st = btc_gen_ensure(db, n, 0, 0))) return st;
-  int m = 0;
-  if (n > 0) {
-    std::vector<const double *> pp(k);
-    std::vector<int> rel(k + 1);
-    for (int i = 0; i < k; i++) pp[i] = poses + 12 * i;
-    for (int i = 0; i <= k; i++) rel[i] = offsets[i] - off0;
-    if ((st = kf_upload_tab(s, k, pp.data(), rel.data(), c->stream))) return st;
-    const double *src = pnt + 3 * (size_t)off0, *dvar = nullptr;
-    if (!is_device_ptr(pnt)) {
-      HIPCHK(c, hipMemcpyAsync(s->d_src, src, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      src = s->d_src;
-    }
-    if (var) {
-      if (is_device_ptr(var)) dvar = var + 9 * (size_t)off0;      // gathered by the merge kernel, 72 bytes apart
-      else {                                                       // host array: only the three diagonal doubles per point cross
-        const double *v = var + 9 * (size_t)off0;
-        for (size_t i = 0; i < (size_t)n; i++) { s->h_diag[3 * i] = v[9 * i]; s->h_diag[3 * i + 1] = v[9 * i + 4]; s->h_diag[3 * i + 2] = v[9 * i + 8]; }
-        HIPCHK(c, hipMemcpyAsync(s->d_mdiag, s->h_diag, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      }
-    }
-    const int nb = (n + 255) / 256;
-    hipLaunchKernelGGL(k_kf_merge, dim3(nb), dim3(256), 0, c->stream, n, k, kf_dev_off(s), kf_dev_xf(s), src, dvar, 9, 4, s->d_merge,
-                       db ? db->gen->xyz : (float *)nullptr, dvar ? s->d_mdiag : (double *)nullptr);
-    if (db && db->ctx->stream != c->stream) {                      // the generator runs on its database's stream, behind the merge
-      HIPCHK(c, hipEventRecord(s->ev, c->stream));
-      HIPCHK(c, hipStreamWaitEvent(db->ctx->stream, s->ev, 0));
-    }
-    const bool det = c->opt.deterministic != 0;
-    DsWork w{};
-    kf_ws_layout(c, n, det, s->d_ws, &w, &st);
-    if (st) return st;
-    TimedSpan sp{};
-    span_begin(c, "downsample", sp);
-    if ((st = ds_core(c, c->stream, var ? 1 : 0, n, s->d_merge, var ? s->d_mdiag : nullptr, 3, 1, voxel_size, det, w))) return st;
-    hipLaunchKernelGGL(k_kf_emit, dim3(nb), dim3(256), 0, c->stream, n, w.tab, w.slot, w.blk, s->d_pnt + 3 * N, s->d_var + 3 * N, s->d_cnt, var ? 1 : 0);
-    span_end(c, "downsample", sp);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(s->h_n, w.n_out, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  }
-  if (db) {
-    st = btc_generate_impl(db, n, nullptr, id, cap, rows, bits, n_stds);
-    if (st) { hipStreamSynchronize(c->stream); return st; }
-  }
-  if (n > 0) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    m = s->h_n[0];
-  }
-  // commit
-  vba_kf_store::Meta me{};
-  std::memcpy(me.x0, poses + 12 * (size_t)(k - 1), 12 * sizeof(double));
-  me.id = id; me.jour = jour; me.exist = 0;
-  s->kf.push_back(me);
-  s->off.push_back((int)(N + (size_t)m));
-  s->last_m = m;
-  *n_points = m;
-  return VBA_OK;
-}
-
-int vba_kf_last_counts(vba_kf_store *s, int cap, int *counts, int *n) {
-  if (!s || !n || cap < 0 || (cap > 0 && !counts)) return VBA_ERR_BAD_ARG;
-  vba_ctx *c = s->ctx;
-  *n = s->last_m;
-  const int w = s->last_m < cap ? s->last_m : cap;
-  if (w > 0) {
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(counts, s->d_cnt, (size_t)w * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return VBA_OK;
-}
-
-int vba_kf_generate_stds(vba_kf_store *s, int first, int count, vba_btc_db *db, int cap, double *rows, uint64_t *bits, int *n_stds) {
-  if (!s || !db || first < 0 || count < 1 || (size_t)first + (size_t)count > s->kf.size()) return VBA_ERR_BAD_ARG;
-  vba_ctx *c = s->ctx;
-  if (db->ctx->device != c->device) return VBA_ERR_BAD_ARG;
-  const int b = s->off[first], n = s->off[first + count] - b;
-  int st;
-  if ((st = btc_generate_check(db, n, cap, rows, bits, n_stds))) return st;
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((st = kf_ensure_tab(s, count))) return st;
-  const int id = s->kf[first + count - 1].id;
-  if (n > 0) {
-    if ((st = btc_gen_ensure(db, n, 0, 0))) return st;
-    std::vector<const double *> pp(count);
-    std::vector<int> rel(count + 1);
-    for (int i = 0; i < count; i++) pp[i] = s->kf[first + i].x0;
-    for (int i = 0; i <= count; i++) rel[i] = s->off[first + i] - b;
-    hipStream_t q = db->ctx->stream;                               // the store is quiescent between calls: everything on the database's stream
-    if ((st = kf_upload_tab(s, count, pp.data(), rel.data(), q))) return st;
-    hipLaunchKernelGGL(k_kf_merge, dim3((n + 255) / 256), dim3(256), 0, q, n, count, kf_dev_off(s), kf_dev_xf(s), s->d_pnt + 3 * (size_t)b,
-                       (const double *)nullptr, 9, 4, (double *)nullptr, db->gen->xyz, (double *)nullptr);
-    HIPCHK(c, hipGetLastError());
-  }
-  st = btc_generate_impl(db, n, nullptr, id, cap, rows, bits, n_stds);
-  if (st) hipStreamSynchronize(db->ctx->stream);
-  return st;
-}
-
-int vba_kf_set_poses(vba_kf_store *s, int first, int n, const double *poses) {
-  if (!s || first < 0 || n < 0 || (size_t)first + (size_t)n > s->kf.size() || (n > 0 && !poses)) return VBA_ERR_BAD_ARG;
-  for (int i = 0; i < n; i++) if (!kf_pose_ok(poses + 12 * i)) return VBA_ERR_BAD_ARG;
-  for (int i = 0; i < n; i++) std::memcpy(s->kf[first + i].x0, poses + 12 * (size_t)i, 12 * sizeof(double));
-  return VBA_OK;
-}
-
-int vba_kf_get(vba_kf_store *s, int k, double *pose12, int *id, double *jour, int *exist, int *n_points) {
-  if (!s || k < 0 || (size_t)k >= s->kf.size()) return VBA_ERR_BAD_ARG;
-  const vba_kf_store::Meta &m = s->kf[k];
-  if (pose12) std::memcpy(pose12, m.x0, 12 * sizeof(double));
-  if (id) *id = m.id;
-  if (jour) *jour = m.jour;
-  if (exist) *exist = m.exist;
-  if (n_points) *n_points = s->off[k + 1] - s->off[k];
-  return VBA_OK;
-}
-
-int vba_kf_set_history(vba_kf_store *s, int n_hist) {
-  if (!s || n_hist < 0 || (size_t)n_hist > s->kf.size()) return VBA_ERR_BAD_ARG;
-  s->hist_pos.resize(3 * (size_t)n_hist);
-  for (size_t i = 0; i < s->kf.size(); i++) {
-    s->kf[i].exist = (int)i < n_hist ? 1 : 0;
-    if ((int)i < n_hist) for (int j = 0; j < 3; j++) s->hist_pos[3 * i + j] = (float)s->kf[i].x0[9 + j];
-  }
-  s->hist = n_hist;
-  return VBA_OK;
-}
-
-int vba_kf_history_size(vba_kf_store *s) { return s ? s->hist : 0; }
-
-int vba_kf_load(vba_kf_store *s, int k, vba_ctx *mc, double jour) {
-  if (!s || !mc || k < 0 || (size_t)k >= s->kf.size()) return VBA_ERR_BAD_ARG;
-  vba_ctx *c = s->ctx;
-  if (mc->device != c->device) return VBA_ERR_BAD_ARG;
-  const int b = s->off[k], n = s->off[k + 1] - b;
-  if (n > 0) {
-    HIPCHK(c, hipSetDevice(c->device));
-    int st;
-    if ((st = kf_ensure_merge(s, (size_t)n))) return st;
-    // the keyframe's x0 goes through the pinned table; the world points into the merge scratch, on the map context's stream
-    std::memcpy(s->h_tab, s->kf[k].x0, 12 * sizeof(double));
-    HIPCHK(mc, hipMemcpyAsync(s->d_tab, s->h_tab, 12 * sizeof(double), hipMemcpyHostToDevice, mc->stream));
-    hipLaunchKernelGGL(k_kf_world, dim3((n + 255) / 256), dim3(256), 0, mc->stream, n, (const double *)s->d_tab, s->d_pnt + 3 * (size_t)b, s->d_merge);
-    HIPCHK(mc, hipGetLastError());
-    st = map_cut_voxel_fix(mc->map, mc->stream, n, s->d_merge, jour, mc->err);   // ends with the map's counter read-back: one synchronise
-    if (st) { hipStreamSynchronize(mc->stream); return st; }
-  }
-  s->kf[k].exist = 0;
-  return VBA_OK;
-}
-
-int vba_kf_load_nearby(vba_kf_store *s, vba_ctx *mc, const double *p3, double radius, double jour, int *loaded) {
-  if (!s || !mc || !p3 || !loaded || !(radius >= 0)) return VBA_ERR_BAD_ARG;
-  *loaded = -1;
-  if (s->hist <= 0) return VBA_OK;                                   // VS:1382
-  const float q[3] = {(float)p3[0], (float)p3[1], (float)p3[2]};
-  const float r2 = (float)(radius * radius);
-  std::vector<std::pair<float, int>> hit;
-  const int nh = (int)(s->hist_pos.size() / 3);
-  for (int i = 0; i < nh; i++) {
-    volatile float d2 = 0.0f, t;                                     // x, then y, then z, each product and sum rounded to float
-    for (int j = 0; j < 3; j++) { t = s->hist_pos[3 * (size_t)i + j] - q[j]; t = t * t; d2 = d2 + t; }
-    if (d2 < r2) hit.emplace_back((float)d2, i);
-  }
-  std::sort(hit.begin(), hit.end());                                 // ascending distance, the lower index on a tie
-  for (const auto &h : hit) {
-    if (!s->kf[h.second].exist) continue;
-    const int st = vba_kf_load(s, h.second, mc, jour);
-    if (st) return st;
-    s->hist--;
-    *loaded = h.second;
-    break;
-  }
-  return VBA_OK;
-}
-
-int vba_kf_read(vba_kf_store *s, int k, int cap, double *xyz, float *vardiag, int *n) {
-  if (!s || !n || k < 0 || (size_t)k >= s->kf.size() || cap < 0) return VBA_ERR_BAD_ARG;
-  vba_ctx *c = s->ctx;
-  const int b = s->off[k], m = s->off[k + 1] - b;
-  *n = m;
-  const int w = m < cap ? m : cap;
-  if (w > 0 && (xyz || vardiag)) {
-    HIPCHK(c, hipSetDevice(c->device));
-    if (xyz) HIPCHK(c, hipMemcpyAsync(xyz, s->d_pnt + 3 * (size_t)b, (size_t)w * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (vardiag) HIPCHK(c, hipMemcpyAsync(vardiag, s->d_var + 3 * (size_t)b, (size_t)w * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return VBA_OK;
-}
-
-int vba_kf_clouds(vba_kf_store *s, const double **d_pnt, const int **offsets, int *n_kf) {
-  if (!s || !d_pnt || !offsets || !n_kf) return VBA_ERR_BAD_ARG;
-  *d_pnt = s->d_pnt; *offsets = s->off.data(); *n_kf = (int)s->kf.size();
-  return VBA_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------ global map export (vba_kf_export_*)
-namespace {
-
-const long long kExpChunk = 1ll << 22;       // records per pass through the staging buffer of a host export (64 MiB)
-const int kExpMaxBlocks = 2048;              // grid cap of the streaming kernel: 256 CUs x 8 workgroups, the rest is grid-strided
-
-inline long long exp_count(long long size, long long jump) { return (size + jump - 1) / jump; }   // j = 0, jump, ... < size
-
-// the table of `entries` keyframes: every image of the pinned ring and the device copy
-int exp_ensure_tab(vba_ctx *c, size_t entries) {
-  for (int i = 0; i < vba_ctx::kExpRing; i++)
-    if (!c->exp_ev[i]) HIPCHK(c, hipEventCreateWithFlags(&c->exp_ev[i], hipEventDisableTiming));
-  if (entries <= c->exp_cap) return VBA_OK;
-  size_t m = c->exp_cap ? c->exp_cap : 1024;
-  while (m < entries) m *= 2;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int i = 0; i < vba_ctx::kExpRing; i++) { if (c->h_exp[i]) hipHostFree(c->h_exp[i]); c->h_exp[i] = nullptr; }
-  if (c->d_exp) hipFree(c->d_exp);
-  c->d_exp = nullptr; c->exp_cap = 0;
-  for (int i = 0; i < vba_ctx::kExpRing; i++) HIPCHK(c, hipHostMalloc((void **)&c->h_exp[i], m * sizeof(ExpKf), hipHostMallocDefault));
-  HIPCHK(c, hipMalloc((void **)&c->d_exp, m * sizeof(ExpKf)));
-  c->exp_cap = m;
-  return VBA_OK;
-}
-
-int exp_ensure_out(vba_ctx *c, size_t recs) {
-  if (recs <= c->expout_cap) return VBA_OK;
-  size_t m = c->expout_cap ? c->expout_cap : 65536;
-  while (m < recs) m *= 2;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->d_expout) hipFree(c->d_expout);
-  c->d_expout = nullptr; c->expout_cap = 0;
-  HIPCHK(c, hipMalloc((void **)&c->d_expout, m * sizeof(float4)));
-  c->expout_cap = m;
-  return VBA_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int vba_kf_export_plan(int n_kf, const int *sizes, int64_t interval_size, int jump, int *jump_out, int64_t *kf_begin, int cap_msgs, int *msg_end_kf,
-                       int *n_msgs) {
-  if (n_kf < 0 || (n_kf > 0 && !sizes) || interval_size < 1 || jump < 0 || !jump_out || !kf_begin || !n_msgs || cap_msgs < 0 ||
-      (cap_msgs > 0 && !msg_end_kf))
-    return VBA_ERR_BAD_ARG;
-  uint64_t psize = 0;                                          // VS:117-123 in 64 bits: the reference's `uint psize` wraps at 2^32
-  for (int k = 0; k < n_kf; k++) {
-    if (sizes[k] < 0) return VBA_ERR_BAD_ARG;
-    psize += (uint64_t)sizes[k];
-  }
-  if (jump == 0) {
-    if (psize >= ((uint64_t)1 << 32)) return VBA_ERR_BAD_ARG;
-    const uint64_t ten = interval_size > INT64_MAX / 10 ? (uint64_t)INT64_MAX : 10 * (uint64_t)interval_size;
-    jump = (int)(psize / ten) + 1;                             // VS:124
-  }
-  *jump_out = jump;
-  int64_t total = 0, pl = 0;
-  int nm = 0;
-  for (int k = 0; k < n_kf; k++) {
-    kf_begin[k] = total;
-    const int64_t cnt = exp_count(sizes[k], jump);             // VS:133
-    total += cnt; pl += cnt;
-    if (pl > interval_size) {                                  // VS:145-150
-      if (nm < cap_msgs) msg_end_kf[nm] = k + 1;
-      nm++; pl = 0;
-    }
-  }
-  kf_begin[n_kf] = total;
-  if (nm < cap_msgs) msg_end_kf[nm] = n_kf;                    // VS:153: published whatever it holds
-  nm++;
-  *n_msgs = nm;
-  return VBA_OK;
-}
-
-int vba_kf_export_world(vba_ctx *c, int n_stores, vba_kf_store *const *stores, const float *intensity, int jump, int64_t begin, int64_t count,
-                        float *xyzi) {
-  if (!c || n_stores < 1 || !stores || !intensity || jump < 1 || begin < 0 || count < 0 || (count > 0 && !xyzi)) return VBA_ERR_BAD_ARG;
-  for (int s = 0; s < n_stores; s++) if (!stores[s] || stores[s]->ctx->device != c->device) return VBA_ERR_BAD_ARG;
-  // exported points before every keyframe of the whole sequence (the plan's kf_begin), keyframes before every store
-  std::vector<long long> &first = c->exp_first;
-  std::vector<int> &kbase = c->exp_kbase;
-  first.clear(); kbase.clear();
-  long long total = 0;
-  for (int s = 0; s < n_stores; s++) {
-    const std::vector<int> &off = stores[s]->off;
-    if (first.size() + stores[s]->kf.size() > (size_t)(1 << 30)) return VBA_ERR_CAPACITY;
-    kbase.push_back((int)first.size());
-    for (size_t k = 0; k + 1 < off.size(); k++) { first.push_back(total); total += exp_count((long long)off[k + 1] - off[k], jump); }
-  }
-  kbase.push_back((int)first.size());
-  first.push_back(total);
-  if (begin > total || count > total - begin) return VBA_ERR_BAD_ARG;
-  if (count == 0) return VBA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  const bool dev_out = is_device_ptr(xyzi);
-  if (dev_out && ((uintptr_t)xyzi & 15)) { c->set_error("vba_kf_export_world: a device xyzi must be 16-byte aligned"); return VBA_ERR_BAD_ARG; }
-  const long long end = begin + count;
-  // the keyframes of the first and of the last exported point: the last k with first[k] <= i (never an empty keyframe)
-  auto kf_of = [&](long long i) { return (int)(std::upper_bound(first.begin(), first.end() - 1, i) - first.begin()) - 1; };
-  const int ka = kf_of(begin), kb = kf_of(end - 1), nk = kb - ka + 1;
-  int st;
-  if ((st = exp_ensure_tab(c, (size_t)nk))) return st;
-  if (!dev_out && (st = exp_ensure_out(c, (size_t)(count < kExpChunk ? count : kExpChunk)))) return st;
-  const int slot = c->exp_next;
-  c->exp_next = (slot + 1) % vba_ctx::kExpRing;
-  HIPCHK(c, hipEventSynchronize(c->exp_ev[slot]));             // the upload that last read this image (kExpRing calls ago): long done
-  ExpKf *h = (ExpKf *)c->h_exp[slot];
-  for (int s = 0; s < n_stores; s++) {
-    const vba_kf_store *S = stores[s];
-    for (int g = std::max(ka, kbase[s]); g <= kb && g < kbase[s + 1]; g++) {
-      const int k = g - kbase[s];
-      ExpKf &e = h[g - ka];
-      e.first = first[g]; e.row = S->off[k];
-      std::memcpy(e.T, S->kf[k].x0, 12 * sizeof(double));
-    }
-  }
-  HIPCHK(c, hipMemcpyAsync(c->d_exp, h, (size_t)nk * sizeof(ExpKf), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->exp_ev[slot], c->stream));
-  const ExpKf *d_tab = (const ExpKf *)c->d_exp;
-  for (long long cb = begin; cb < end; cb += dev_out ? count : kExpChunk) {
-    const long long ce = dev_out ? end : std::min(end, cb + kExpChunk);
-    float4 *out = dev_out ? (float4 *)xyzi : (float4 *)c->d_expout;                     // the record of cb
-    for (int s = 0; s < n_stores; s++) {                       // one launch per store: its point array, its intensity, its rows of the table
-      const long long a = std::max(cb, first[kbase[s]]), b = std::min(ce, first[kbase[s + 1]]);
-      if (a >= b) continue;
-      const int g0 = std::max(ka, kbase[s]), g1 = std::min(kb, kbase[s + 1] - 1);
-      const long long nb = (b - a + 255) / 256;
-      hipLaunchKernelGGL(k_kf_export, dim3((unsigned)std::min<long long>(nb, kExpMaxBlocks)), dim3(256), 0, c->stream, a, b - a, g1 - g0 + 1,
-                         d_tab + (g0 - ka), (const double *)stores[s]->d_pnt, jump, intensity[s], out + (a - cb));
-    }
-    HIPCHK(c, hipGetLastError());
-    if (!dev_out) HIPCHK(c, hipMemcpyAsync(xyzi + 4 * (size_t)(cb - begin), c->d_expout, (size_t)(ce - cb) * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-  }
-  if (!dev_out) HIPCHK(c, hipStreamSynchronize(c->stream));
-  return VBA_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------ loop-closure map (vba_loop_map_*, vba_loop_update)
-#include "vba_kernels_loop.hpp"
-
-struct vba_loop_map {
-  vba_ctx *ctx = nullptr;
-  MapStore map;                                  // map_loop; after vba_loop_update the map the context gave up (ping-pong)
-  size_t res_fix = 0, res_nodes = 0;             // vba_loop_map_reserve: applied to whichever store the object owns
-  // segment table int4 [tcap] + poses double [tcap][12]: pinned image and device copy
-  int tcap = 0; char *h_tab = nullptr, *d_tab = nullptr;
-  char *d_in = nullptr; size_t in_bytes = 0;     // host-memory scans of vba_loop_update on their way to the device
-  int allocs = 0; int64_t bytes = 0;
-};
-
-namespace {
-
-size_t lm_tab_bytes(int t) { return (size_t)t * (sizeof(int4) + 12 * sizeof(double)); }
-
-// device bytes behind a MapStore, from its capacities (what grows when a call allocates)
-int64_t lm_store_bytes(MapStore &s) {
-  if (!s.allocated) return 0;
-  const int W = s.opt.win_size;
-  size_t b = 0;
-  for (auto &a : node_arrays(s.v, W)) b += a.elem * a.rows * (size_t)s.v.cap;
-  for (auto &a : scan_arrays(s.v, W)) b += a.elem * a.rows * (size_t)s.v.max_pts;
-  for (auto &a : fix_arrays(s.v)) b += a.elem * a.rows * (size_t)s.v.cap_fix;
-  b += (size_t)s.hcap * (s.det ? 16 : 12) + s.stage_bytes + s.sort_tmp_bytes + s.whist_cap * sizeof(int);
-  return (int64_t)b;
-}
-
-// allocations made by the calls on this object: every store the call may have grown is measured around it
-struct LmAccount {
-  vba_loop_map *lm; MapStore *a, *b; int64_t before;
-  LmAccount(vba_loop_map *l, MapStore *x, MapStore *y = nullptr) : lm(l), a(x), b(y), before(lm_store_bytes(*x) + (y ? lm_store_bytes(*y) : 0)) {}
-  ~LmAccount() {
-    const int64_t after = lm_store_bytes(*a) + (b ? lm_store_bytes(*b) : 0);
-    if (after != before) { lm->allocs++; lm->bytes += after - before; }
-  }
-};
-
-int lm_ensure_tab(vba_loop_map *lm, int t) {
-  if (t <= lm->tcap) return VBA_OK;
-  vba_ctx *c = lm->ctx;
-  int m = lm->tcap ? lm->tcap : 64;
-  while (m < t) m *= 2;
-  HIPCHK(c, hipDeviceSynchronize());
-  if (lm->h_tab) hipHostFree(lm->h_tab);
-  if (lm->d_tab) hipFree(lm->d_tab);
-  lm->h_tab = nullptr; lm->d_tab = nullptr; lm->tcap = 0;
-  HIPCHK(c, hipHostMalloc((void **)&lm->h_tab, lm_tab_bytes(m), hipHostMallocDefault));
-  HIPCHK(c, hipMalloc((void **)&lm->d_tab, lm_tab_bytes(m)));
-  lm->allocs += 2; lm->bytes += (int64_t)lm_tab_bytes(m);
-  lm->tcap = m;
-  return VBA_OK;
-}
-int lm_ensure_in(vba_loop_map *lm, size_t bytes) {
-  if (bytes <= lm->in_bytes) return VBA_OK;
-  vba_ctx *c = lm->ctx;
-  HIPCHK(c, hipDeviceSynchronize());
-  if (lm->d_in) hipFree(lm->d_in);
-  lm->d_in = nullptr; lm->in_bytes = 0;
-  HIPCHK(c, hipMalloc((void **)&lm->d_in, bytes));
-  lm->allocs++; lm->bytes += (int64_t)bytes;
-  lm->in_bytes = bytes;
-  return VBA_OK;
-}
-int4 *lm_h_seg(vba_loop_map *lm) { return (int4 *)lm->h_tab; }
-double *lm_h_pose(vba_loop_map *lm) { return (double *)(lm->h_tab + (size_t)lm->tcap * sizeof(int4)); }
-const int4 *lm_d_seg(vba_loop_map *lm) { return (const int4 *)lm->d_tab; }
-const double *lm_d_pose(vba_loop_map *lm) { return (const double *)(lm->d_tab + (size_t)lm->tcap * sizeof(int4)); }
-
-// the reservation on the store the object owns now
-int lm_apply_reserve(vba_loop_map *lm, hipStream_t st, std::string &err) {
-  if (!lm->res_fix && !lm->res_nodes) return VBA_OK;
-  MapStore &s = lm->map;
-  int r = map_base(s, st, err);
-  if (r) return r;
-  if (s.cnt_stale) { r = map_read_counters(s, st, err); if (r) return r; }
-  return map_fix_source_ensure(s, st, lm->res_nodes, lm->res_fix, lm->res_fix, err);
-}
-
-bool lm_same_map_options(const vba_options &a, const vba_options &b) {
-  if (a.win_size != b.win_size || a.voxel_size != b.voxel_size || a.max_layer != b.max_layer || a.max_points != b.max_points ||
-      a.min_eigen_value != b.min_eigen_value || a.thread_num != b.thread_num || (a.deterministic != 0) != (b.deterministic != 0))
-    return false;
-  for (int i = 0; i < 4; i++) if (a.plane_eigen_value_thre[i] != b.plane_eigen_value_thre[i] || a.min_point[i] != b.min_point[i]) return false;
-  return true;
-}
-
-// The two maps trade places.  What belongs to a context stays with it: its options, its shard and its all-reduce closure; buffers
-// (arrays, staging, pose ring, pinned counters, sort scratch) travel with the store: they are memory of the device, not of a stream.
-void lm_swap_stores(MapStore &a, MapStore &b) {
-  std::swap(a, b);
-  std::swap(a.opt, b.opt); std::swap(a.rank, b.rank); std::swap(a.n_ranks, b.n_ranks); std::swap(a.allreduce, b.allreduce);
-}
-
-bool lm_finite(const double *p, size_t n) { for (size_t i = 0; i < n; i++) if (!std::isfinite(p[i])) return false; return true; }
-
-}  // namespace
-
-extern "C" {
-
-int vba_loop_map_create(vba_ctx *c, vba_loop_map **out) {
-  if (!c || !out) return VBA_ERR_BAD_ARG;
-  *out = nullptr;
-  HIPCHK(c, hipSetDevice(c->device));
-  vba_loop_map *lm = new vba_loop_map();
-  lm->ctx = c;
-  map_init(lm->map, c->opt);
-  const int st = lm_ensure_tab(lm, 64);
-  if (st) { vba_loop_map_destroy(lm); return st; }
-  *out = lm;
-  return VBA_OK;
-}
-
-void vba_loop_map_destroy(vba_loop_map *lm) {
-  if (!lm) return;
-  hipSetDevice(lm->ctx->device);
-  hipStreamSynchronize(lm->ctx->stream);
-  map_free(lm->map);
-  if (lm->h_tab) hipHostFree(lm->h_tab);
-  if (lm->d_tab) hipFree(lm->d_tab);
-  if (lm->d_in) hipFree(lm->d_in);
-  delete lm;
-}
-
-int vba_loop_map_reserve(vba_loop_map *lm, int64_t fix_points, int64_t nodes) {
-  if (!lm || fix_points < 0 || nodes < 0 || fix_points > ((int64_t)1 << 27) || nodes > ((int64_t)1 << 28)) return VBA_ERR_BAD_ARG;
-  vba_ctx *c = lm->ctx;
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((size_t)fix_points > lm->res_fix) lm->res_fix = (size_t)fix_points;
-  if ((size_t)nodes > lm->res_nodes) lm->res_nodes = (size_t)nodes;
-  int st;
-  {
-    LmAccount acc(lm, &lm->map);
-    st = lm_apply_reserve(lm, c->stream, c->err);
-  }
-  if (!st) st = lm_ensure_in(lm, lm->res_fix * 96);
-  if (st) return st;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return VBA_OK;
-}
-
-int vba_loop_map_allocations(vba_loop_map *lm, int *count, int64_t *bytes) {
-  if (!lm || !count || !bytes) return VBA_ERR_BAD_ARG;
-  *count = lm->allocs; *bytes = lm->bytes;
-  return VBA_OK;
-}
-
-int vba_loop_map_build(vba_loop_map *lm, vba_kf_store *s, int init_num, int cumulative, int *n_inserted) {
-  if (!lm || !s || !n_inserted || init_num < 1 || init_num > 64) return VBA_ERR_BAD_ARG;
-  *n_inserted = 0;
-  vba_ctx *c = lm->ctx;
-  if (s->ctx->device != c->device) return VBA_ERR_BAD_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  const int size = (int)s->kf.size();
-  const int first = size - init_num > 0 ? size - init_num : 0, m = size - first;       // indices below zero are skipped (VS:2607-2608)
-  const int nseg = cumulative ? m * (m + 1) / 2 : m;
-  int st;
-  if ((st = lm_ensure_tab(lm, nseg > m ? nseg : (m > 0 ? m : 1)))) return st;
-  // pvec_tem is never cleared (VS:2602): call j inserts keyframes first .. first + j again
-  int4 *seg = lm_h_seg(lm);
-  double *hp = lm_h_pose(lm);
-  long long n = 0;
-  int ns = 0;
-  for (int j = 0; j < m; j++)                               // insertion j of the reference: keyframes 0 .. j (corrected form: j alone)
-    for (int i = cumulative ? 0 : j; i <= j; i++) {
-      seg[ns++] = make_int4((int)n, s->off[first + i], i, 0);
-      n += s->off[first + i + 1] - s->off[first + i];
-    }
-  for (int i = 0; i < m; i++) std::memcpy(hp + 12 * i, s->kf[first + i].x0, 12 * sizeof(double));
-  if (n > ((long long)1 << 27)) return VBA_ERR_CAPACITY;
-  LmAccount acc(lm, &lm->map);
-  if ((st = map_reset(lm->map, c->stream, c->err))) return st;
-  if (n > 0) {
-    HIPCHK(c, hipMemcpyAsync(lm->d_tab, lm->h_tab, lm_tab_bytes(lm->tcap), hipMemcpyHostToDevice, c->stream));
-    FixSource src;
-    src.nseg = ns; src.d_seg = lm_d_seg(lm); src.d_poses = lm_d_pose(lm); src.d_pnt = s->d_pnt; src.cov_kind = FIXCOV_DIAG_F32; src.d_cov = s->d_var;
-    st = map_cut_voxel_fix_source(lm->map, c->stream, (int)n, src, 0.0, c->err);       // ends with the counter read-back: the map is complete
-    if (st) { hipStreamSynchronize(c->stream); map_reset(lm->map, c->stream, c->err); return st; }
-  }
-  for (int i = 0; i < m; i++) s->kf[first + i].exist = 0;                               // VS:2612
-  *n_inserted = (int)n;
-  return VBA_OK;
-}
-
-int vba_loop_map_num_roots(vba_loop_map *lm) { return lm ? map_num_roots(lm->map, lm->ctx->stream, false) : -1; }
-int vba_loop_map_dump_leaves(vba_loop_map *lm, double *out, int max_leaves) { return lm ? map_dump_leaves(lm->map, lm->ctx->stream, out, max_leaves, lm->ctx->err) : -1; }
-int vba_loop_map_dump_plane_var(vba_loop_map *lm, double *out, int max_leaves) { return lm ? map_dump_plane_var(lm->map, lm->ctx->stream, out, max_leaves, lm->ctx->err) : -1; }
-
-int vba_loop_update(vba_ctx *c, vba_loop_map *lm, const double *dx12, int k, const int *offsets, const double *pnt, const double *var, const double *poses_bl,
-                    int win_count, const double *win_pnt, const double *win_var, const int *win_offsets, const double *poses_win, int *n_factors) {
-  // ---- 1. arguments, before any device work
-  if (!c || !lm || !n_factors || !poses_win || k < 0) return VBA_ERR_BAD_ARG;
-  *n_factors = 0;
-  const int W = c->opt.win_size;
-  if (win_count < 1 || win_count > W) { c->set_error("vba_loop_update: win_count outside 1..win_size"); return VBA_ERR_BAD_ARG; }
-  if (lm->ctx->device != c->device) { c->set_error("vba_loop_update: the loop map is on another device"); return VBA_ERR_BAD_ARG; }
-  if (!lm_same_map_options(lm->map.opt, c->opt)) { c->set_error("vba_loop_update: the loop map was created with other map options"); return VBA_ERR_BAD_ARG; }
-  if (c->n_ranks > 1 || c->map.n_ranks > 1 || lm->map.n_ranks > 1 || c->rank != 0) { c->set_error("vba_loop_update: sharded maps are not supported"); return VBA_ERR_UNSUPPORTED; }
-  if (dx12 && !lm_finite(dx12, 12)) return VBA_ERR_BAD_ARG;
-  if (!lm_finite(poses_win, 12 * (size_t)win_count)) return VBA_ERR_BAD_ARG;
-  long long n_bl = 0;
-  if (k > 0) {
-    if (!offsets || !poses_bl || !lm_finite(poses_bl, 12 * (size_t)k)) return VBA_ERR_BAD_ARG;
-    for (int i = 0; i < k; i++) if (offsets[i] < 0 || offsets[i + 1] < offsets[i]) return VBA_ERR_BAD_ARG;
-    n_bl = (long long)offsets[k] - offsets[0];
-    if (n_bl > ((long long)1 << 27)) return VBA_ERR_CAPACITY;
-    if (n_bl > 0 && !pnt) return VBA_ERR_BAD_ARG;
-  }
-  if (win_pnt) {
-    if (!win_offsets) return VBA_ERR_BAD_ARG;
-    for (int i = 0; i < win_count; i++) if (win_offsets[i] < 0 || win_offsets[i + 1] < win_offsets[i]) return VBA_ERR_BAD_ARG;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  int r;
-  if ((r = lm_ensure_tab(lm, k > 0 ? k : 1))) { c->set_error(lm->ctx->err); return r; }
-  const bool bl_host = n_bl > 0 && !is_device_ptr(pnt);
-  if (bl_host && (r = lm_ensure_in(lm, (size_t)n_bl * (var ? 96 : 24)))) { c->set_error(lm->ctx->err); return r; }
-  HIPCHK(c, hipStreamSynchronize(lm->ctx->stream));          // (the build ended with a synchronise; a dump on that stream may not have)
-  LmAccount acc(lm, &lm->map, &c->map);
-  // ---- 2. the context adopts map_loop (surf_map = map_loop, VS:1275-1276); the outgoing map stays readable until the end
-  lm_swap_stores(c->map, lm->map);
-  MapStore &old = lm->map;
-  for (int i = 0; i < VBA_MAX_WIN; i++) c->map.mp[i] = i;    // VS:1334-1335
-  auto fail = [&](int code) {                                // the context gets its map back untouched; the loop map has to be built again
-    hipStreamSynchronize(st);
-    const std::string why = c->err;
-    lm_swap_stores(c->map, lm->map);
-    std::string e2;
-    map_reset(lm->map, st, e2);
-    c->set_error(why + " (vba_loop_update: the context's map is unchanged, the loop map was reset)");
-    return code;
-  };
-  // ---- 3. the buf_lba2loop scans: one fixed insertion with their covariances at jour = 0 (VS:1338-1347)
-  if (n_bl > 0) {
-    const int off0 = offsets[0];
-    int4 *seg = lm_h_seg(lm);
-    for (int i = 0; i < k; i++) seg[i] = make_int4(offsets[i] - off0, offsets[i] - off0, i, 0);
-    std::memcpy(lm_h_pose(lm), poses_bl, 12 * sizeof(double) * (size_t)k);
-    if (hipMemcpyAsync(lm->d_tab, lm->h_tab, lm_tab_bytes(lm->tcap), hipMemcpyHostToDevice, st) != hipSuccess) { c->set_error("vba_loop_update: table upload failed"); return fail(VBA_ERR_HIP); }
-    const double *d_p = pnt + 3 * (size_t)off0, *d_v = var ? var + 9 * (size_t)off0 : nullptr;
-    if (bl_host) {
-      hipError_t e = hipMemcpyAsync(lm->d_in, d_p, (size_t)n_bl * 24, hipMemcpyHostToDevice, st);
-      if (e == hipSuccess && var) e = hipMemcpyAsync(lm->d_in + (size_t)n_bl * 24, d_v, (size_t)n_bl * 72, hipMemcpyHostToDevice, st);
-      if (e != hipSuccess) { c->set_error("vba_loop_update: scan upload failed"); return fail(VBA_ERR_HIP); }
-      d_p = (const double *)lm->d_in; d_v = var ? (const double *)(lm->d_in + (size_t)n_bl * 24) : nullptr;
-    }
-    FixSource src;
-    src.nseg = k; src.d_seg = lm_d_seg(lm); src.d_poses = lm_d_pose(lm); src.d_pnt = d_p;
-    src.cov_kind = d_v ? FIXCOV_FULL_F64 : FIXCOV_ZERO; src.d_cov = d_v;
-    if ((r = map_cut_voxel_fix_source(c->map, st, (int)n_bl, src, 0.0, c->err))) return fail(r);
-  }
-  // ---- 4. the window's scans again: cut_voxel at frame i with the moved pose (VS:1350-1359)
-  for (int i = 0; i < win_count; i++) {
-    const double *p, *v; int n;
-    if (win_pnt) {
-      n = win_offsets[i + 1] - win_offsets[i];
-      p = win_pnt + 3 * (size_t)win_offsets[i]; v = win_var ? win_var + 9 * (size_t)win_offsets[i] : nullptr;
-    } else {                                                  // the outgoing map's scan ring: raw body points and covariances as inserted
-      const int slot = old.mp[i];
-      n = old.npts[slot];
-      p = n > 0 ? old.v.px + (size_t)slot * old.v.max_pts * 3 : nullptr;
-      v = n > 0 && old.have_var ? old.v.pvar + (size_t)slot * old.v.max_pts * 9 : nullptr;
-    }
-    if ((r = map_cut_voxel(c->map, st, i, n, p, v, poses_win + 12 * (size_t)i, false, c->err))) return fail(r);
-  }
-  // ---- 5. recut over all roots (VS:1362-1363), with vba_map_recut's factor extraction
-  if ((r = vba_map_recut(c, win_count, poses_win, 0))) return fail(r);
-  *n_factors = c->nvox;
-  // ---- 6. the outgoing map is emptied and keeps its allocations for the next loop closure
-  std::string e2;
-  r = map_reset(old, st, e2);
-  if (!r) r = lm_apply_reserve(lm, st, e2);
-  if (!r && old.hcap != c->map.hcap) {                         // both tables at the larger size: the capacities stop moving after one cycle
-    MapStore &small = old.hcap < c->map.hcap ? old : c->map;
-    const unsigned int big = old.hcap < c->map.hcap ? c->map.hcap : old.hcap;
-    if (small.allocated) {
-      if (small.cnt_stale) r = map_read_counters(small, st, e2);
-      if (!r) r = map_hash_alloc(small, big, st, e2);
-    }
-  }
-  if (r) { c->set_error("vba_loop_update: the context holds the new map; resetting the outgoing map failed: " + e2); return r; }
   return VBA_OK;
 }
 
