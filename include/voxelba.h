@@ -782,6 +782,95 @@ int vba_loop_update(vba_ctx *ctx, vba_loop_map *lm, const double *dx12, int k, c
                     const double *poses_bl, int win_count, const double *win_pnt, const double *win_var, const int *win_offsets,
                     const double *poses_win, int *n_factors);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scan front end: the node's per-scan path from the raw sensor message to the points and covariances that the
+ * odometry and the map read, resident in HBM.  A frame owns the device buffers of one scan.
+ *   decode:  Features::process + pcl_handler (FP:103-366, VH:77-103): raw message bytes -> decoded, filtered, time-sorted, cut cloud.
+ *   prepare: motion_blur's point loop + down_sampling_voxel + the retry + var_init (EK:135-163, VS:1877-1888), stream-ordered; returns
+ *            DEVICE pointers that vba_odom_lio_state_estimation and vba_map_pvec_update_cut_voxel consume in place.
+ * Between the two the node runs sync_packages (it needs the last curvature, VH:129) and the host IMU propagation (EK:55-123) that
+ * produces imu_poses.
+ *
+ * A record of the message is point_step bytes; the fields are read at byte offsets that need not be aligned:
+ *   x, y, z     float32.
+ *   intensity   by intensity_type; NONE gives 0 (velodyne FP:185, tartanair).
+ *   curvature   by time_type.  U32_DIV1E9: the u32 converted to float (round to nearest), then ONE float division by float(1e9).
+ *               F64_REL_FIRST: t[i] - t[0] in double, t[0] read from raw record 0 whether or not it is kept, narrowed once.
+ * filter == 1: record i is kept iff i % point_filter_num == 0 and (double)((x*x + y*y) + z*z) > blind2, products and sums in float in
+ * that order, not contracted (a point exactly on the blind sphere is dropped).  filter == 0: every record is kept.
+ * Kept points keep message order.  No kept point (or n_raw == 0): two points at the origin, intensity 0, curvatures 0 and 0.09f
+ * (VH:82-90).  Then the sort on the float curvature, ascending (VH:92-95), and the cut of trailing points with
+ * (double)curvature > 0.11 (VH:96-97).
+ *
+ * TIES: the sort is STABLE, points of equal curvature keep message order (-0.0f and +0.0f are equal).  The reference's std::sort
+ * leaves their order undefined.
+ * Deviations from the reference: (1) a message whose points are ALL beyond 0.11 ends with n = 0, *last_curvature = 0 and VBA_OK
+ * (the reference pops from an empty vector), and prepare on such a frame returns n = 0; (2) NaN times are unsupported input
+ * (undefined behaviour in the reference; here their position after the sort is unspecified); (3) time_type F32 (velodyne): when the
+ * last raw record's time is not inside (0.01, 0.12) the reference takes its yaw-angle branch (FP:200-252), which is not built:
+ * VBA_ERR_UNSUPPORTED, read on the host from `raw`.
+ *
+ * Stored form: coordinates and curvature as PCL floats carried in doubles ([n][3], [n]), the convention of the vba_scan_* calls
+ * above; intensity as float. */
+typedef struct vba_scan_frame vba_scan_frame;
+
+enum { VBA_SCAN_TIME_NONE = 0,         /* curvature = 0                                          tartanair FP:356 */
+       VBA_SCAN_TIME_F32 = 1,          /* curvature = the float field as it is                   velodyne  FP:188 */
+       VBA_SCAN_TIME_U32_DIV1E9 = 2,   /* (float)u32 / float(1e9), one float division            livox FP:155, ouster FP:271 */
+       VBA_SCAN_TIME_F64_REL_FIRST = 3 /* (float)(t[i] - t[0]), the subtraction in double        hesai FP:304, robosense FP:335 */ };
+enum { VBA_SCAN_INTENSITY_NONE = 0, VBA_SCAN_INTENSITY_F32 = 1, VBA_SCAN_INTENSITY_U8 = 2 /* livox reflectivity FP:153 */ };
+
+typedef struct vba_scan_layout {
+  int point_step;                  /* bytes from one record to the next (any value >= 1; 26 for the Hesai driver) */
+  int off_x, off_y, off_z;         /* float32 fields */
+  int off_intensity, intensity_type;
+  int off_time, time_type;
+  int filter;                      /* 1: decimation + blind test apply; 0: every point is kept (tartanair FP:350-366) */
+} vba_scan_layout;
+
+/* livox_ros_driver::CustomPoint as it lies in memory: step 20, time u32 @0, xyz @4/8/12, reflectivity u8 @16 */
+int vba_scan_layout_livox(vba_scan_layout *l);
+/* Host only (no device needed): VBA_OK when point_step >= 1, the type codes are known, filter is 0 or 1 and every field that its type
+ * code selects lies inside [0, point_step); VBA_ERR_BAD_ARG otherwise. */
+int vba_scan_layout_check(const vba_scan_layout *l);
+
+/* A frame belongs to the device of ctx; decode runs on ctx's stream.  The buffers are grow-only, by doubling after a synchronise;
+ * after vba_scan_frame_reserve no call allocates while n_raw <= max_raw_points, n_raw * point_step <= max_raw_points * max_point_step
+ * and m <= 64 IMU poses (vba_scan_frame_allocations counts allocations and bytes, as vba_kf_allocations does).  Growing discards the
+ * frame's contents.  A frame is not synchronised internally; destroy it before its context. */
+int vba_scan_frame_create(vba_ctx *ctx, vba_scan_frame **out);
+void vba_scan_frame_destroy(vba_scan_frame *f);
+int vba_scan_frame_reserve(vba_scan_frame *f, int max_raw_points, int max_point_step);
+int vba_scan_frame_allocations(vba_scan_frame *f, int *n_allocs, int64_t *bytes);
+
+/* raw: n_raw records in HOST memory, uploaded once.  blind2 = blind * blind (VS:906).  *n_out = points of the frame's cloud,
+ * *last_curvature = pl_ptr->back().curvature (VH:129; 0 when n = 0).  Complete when it returns (one synchronise).
+ * VBA_ERR_BAD_ARG: a layout that fails vba_scan_layout_check, n_raw < 0, point_filter_num < 1. */
+int vba_scan_decode(vba_scan_frame *f, const vba_scan_layout *l, const void *raw, int n_raw, int point_filter_num, double blind2,
+                    int *n_out, double *last_curvature);
+
+/* On ctx's stream (ctx may be another context of the frame's device), from the frame's decoded cloud:
+ *  1. undistortion as vba_scan_undistort (imu_poses [m][22], end_pose [12], ext_pose [12]), skipped when point_notime != 0 (EK:135);
+ *  2. down_sampling_voxel at down_size; if min_points > 0 and fewer than min_points voxels result, once more at down_size / 2 from
+ *     the UNDISTORTED cloud, that result kept whatever its count (VS:1880-1884; the node passes 500, and 0 with
+ *     down_size = max(down_size, 0.5) for VS:1470-1474).  A size < 0.001 leaves the cloud as it is (TL:203).
+ *     vba_options::deterministic of ctx selects the deterministic summation;
+ *  3. var_init with ext_pose, dept_err, beam_err into *d_pnt_body [n][3] and *d_var_body [n][9].
+ * The two pointers are DEVICE pointers owned by the frame, valid until the frame's next decode, prepare, reserve or destroy; the
+ * call may return before var_init has finished, consumers on ctx's stream are ordered behind it.  One synchronise per call, two when
+ * the retry runs.  Preparing a frame again repeats the work from the decoded cloud.
+ * VBA_ERR_BAD_ARG when the frame has not been decoded (or lost its contents by growing), or lives on another device. */
+int vba_scan_prepare(vba_ctx *ctx, vba_scan_frame *f, int m, const double *imu_poses, const double *end_pose, const double *ext_pose,
+                     int point_notime, double down_size, int min_points, double dept_err, double beam_err, int *n_out,
+                     const double **d_pnt_body, const double **d_var_body);
+
+/* Inspection (synchronises).  stage 0 = decoded + sorted: pnt [n][3], intensity [n], curvature [n]; 1 = undistorted: the same with the
+ * moved points; 2 = down-sampled: pnt [m][3], count [m], first [m] as vba_scan_down_sampling_voxel; 3 = var_init: pnt [m][3],
+ * var [m][9].  n and m are the counts that decode and prepare returned.  NULL outputs, and outputs that a stage does not have, are
+ * skipped.  Stages 1-3 need a prepared frame (VBA_ERR_BAD_ARG). */
+int vba_scan_frame_read(vba_scan_frame *f, int stage, double *pnt, float *intensity, double *curvature, int *count, int *first,
+                        double *var);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@
 //   Initialization::motion_init  VS:617-819                         vba::Initialization::motion_init
 //   build_graph + gtsam::ISAM2   VS:2078-2156, VS:2550-2561          vba::PoseGraph (add_edge LR:147-161, set_state LR:36-43)
 //   ResultOutput::pub_globalmap  VS:110-154                         vba::pub_globalmap
+//   pcl_handler VH:77-103; motion_blur's loop + VS:1877-1888        vba::ScanFrame::decode / prepare (ScanView feeds the odometry and the map)
 //
 // The reference's types are Eigen-based (tools.hpp:4).  This header compiles without Eigen (plain-array structs that
 // mirror PointCluster / IMUST / IMU_PRE field for field); when <Eigen/Core> is available the Eigen-typed overloads
@@ -181,6 +182,39 @@ class LI_BA_OptimizerGravity {
 struct pointVar { double pnt[3]; double var[9]; };   // VM:18-34
 typedef std::vector<pointVar> PVec;
 
+// ---- scan front end: pcl_handler VH:77-103, then odom_ekf.process's point loop + VS:1877-1888, resident in HBM
+struct ScanView { int n = 0; const double *pnt = nullptr; const double *var = nullptr; };   // DEVICE arrays [n][3], [n][9] owned by a ScanFrame
+class ScanFrame {
+ public:
+  explicit ScanFrame(Context &ctx) : ctx_(ctx.get()) { check(ctx_, vba_scan_frame_create(ctx_, &f_)); }
+  ~ScanFrame() { vba_scan_frame_destroy(f_); }
+  ScanFrame(const ScanFrame &) = delete;
+  ScanFrame &operator=(const ScanFrame &) = delete;
+  void reserve(int max_raw_points, int max_point_step) { check(ctx_, vba_scan_frame_reserve(f_, max_raw_points, max_point_step)); }
+  // feat.process(msg, *pl_ptr) + the rest of pcl_handler: data = &msg->data[0] (PointCloud2) or &msg->points[0] (livox CustomMsg).
+  // Returns pl_ptr->back().curvature, the end-time offset that sync_packages adds to the message stamp (VH:129); size() = pl_ptr->size()
+  double decode(const void *data, int n_raw, const vba_scan_layout &layout, int point_filter_num, double blind) {
+    double last = 0;
+    check(ctx_, vba_scan_decode(f_, &layout, data, n_raw, point_filter_num, blind * blind, &n_, &last));
+    return last;
+  }
+  int size() const { return n_; }
+  // imu_poses [m][22], end = xc after the propagation (EK:121-123), ext = extrin_para; min_points 500 (VS:1880), 0 while initialising
+  ScanView prepare(Context &ctx, int m, const double *imu_poses, const IMUST &end, const IMUST &ext, bool point_notime, double down_size,
+                   double dept_err, double beam_err, int min_points = 500) {
+    double e[12], x[12];
+    std::memcpy(e, end.R, 72); std::memcpy(e + 9, end.p, 24); std::memcpy(x, ext.R, 72); std::memcpy(x + 9, ext.p, 24);
+    ScanView v;
+    check(ctx.get(), vba_scan_prepare(ctx.get(), f_, m, imu_poses, e, x, point_notime ? 1 : 0, down_size, min_points, dept_err, beam_err, &v.n, &v.pnt, &v.var));
+    return v;
+  }
+  vba_scan_frame *get() const { return f_; }
+ private:
+  vba_ctx *ctx_;
+  vba_scan_frame *f_ = nullptr;
+  int n_ = 0;
+};
+
 class LoopMap;
 struct ScanPose;
 class VoxelMap {
@@ -199,6 +233,12 @@ class VoxelMap {
     double pose[12];
     std::memcpy(pose, x.R, 72); std::memcpy(pose + 9, x.p, 24);
     check(c_, vba_map_pvec_update_cut_voxel(c_, win_count, (int)n, p.data(), v.data(), pose, x.cov, 1));
+  }
+  // the same on a prepared scan frame: the device arrays are consumed in place, on the context that prepared them
+  void pvec_update_cut_voxel_multi(const ScanView &scan, int win_count, const IMUST &x) {
+    double pose[12];
+    std::memcpy(pose, x.R, 72); std::memcpy(pose + 9, x.p, 24);
+    check(c_, vba_map_pvec_update_cut_voxel(c_, win_count, scan.n, scan.pnt, scan.var, pose, x.cov, 1));
   }
   // cut_voxel(feat_map, PVec&, wdsize, jour) VM:2108
   void cut_voxel_fix(const PVec &pvec, double jour) {
@@ -425,6 +465,13 @@ inline void set_state(IMUST &x, const double *pose12) {
   std::memcpy(x.R, pose12, 72); std::memcpy(x.p, pose12 + 9, 24);
   for (int i = 0; i < 3; i++) v[i] = rot[3 * i] * x.v[0] + rot[3 * i + 1] * x.v[1] + rot[3 * i + 2] * x.v[2];
   std::memcpy(x.v, v, 24);
+}
+
+// VOXEL_SLAM::lio_state_estimation(pptr) VS:962-1098 on a prepared scan frame (device arrays, consumed in place): x_curr in/out
+inline bool lio_state_estimation(Context &ctx, const ScanView &scan, IMUST &x_curr) {
+  int ok = 0;
+  check(ctx.get(), vba_odom_lio_state_estimation(ctx.get(), scan.n, scan.pnt, scan.var, &x_curr.t, x_curr.cov, &ok));
+  return ok != 0;
 }
 
 // VOXEL_SLAM::lio_state_estimation_kdtree(pptr) VS:1102-1252: x_curr (state + cov) in/out, the point-cloud map (pl_tree) lives in

@@ -44,6 +44,8 @@ EXPORTS = [
     "vba_kf_load_nearby", "vba_kf_read", "vba_kf_clouds", "vba_kf_export_plan", "vba_kf_export_world",
     "vba_loop_map_create", "vba_loop_map_destroy", "vba_loop_map_reserve", "vba_loop_map_allocations", "vba_loop_map_build",
     "vba_loop_map_num_roots", "vba_loop_map_dump_leaves", "vba_loop_map_dump_plane_var", "vba_loop_update",
+    "vba_scan_layout_livox", "vba_scan_layout_check", "vba_scan_frame_create", "vba_scan_frame_destroy", "vba_scan_frame_reserve",
+    "vba_scan_frame_allocations", "vba_scan_decode", "vba_scan_prepare", "vba_scan_frame_read",
 ]
 
 
@@ -420,6 +422,112 @@ class LoopMap:
         out = np.zeros((max(n, 0), 86))
         if n > 0:
             self.lib.vba_loop_map_dump_plane_var(self.h, _p(out), C.c_int(n))
+        return out
+
+
+SCAN_TIME_NONE, SCAN_TIME_F32, SCAN_TIME_U32_DIV1E9, SCAN_TIME_F64_REL_FIRST = range(4)
+SCAN_INTENSITY_NONE, SCAN_INTENSITY_F32, SCAN_INTENSITY_U8 = range(3)
+
+
+class ScanLayout(C.Structure):
+    """vba_scan_layout: where the fields of one record of a raw sensor message lie (byte offsets, not necessarily aligned)."""
+    _fields_ = [("point_step", C.c_int), ("off_x", C.c_int), ("off_y", C.c_int), ("off_z", C.c_int),
+                ("off_intensity", C.c_int), ("intensity_type", C.c_int), ("off_time", C.c_int), ("time_type", C.c_int), ("filter", C.c_int)]
+
+
+def scan_layout(name) -> ScanLayout:
+    """Layouts of the reference's sensors as their drivers usually publish them; a node fills the struct from msg->fields instead
+    (INTEGRATION.md).  livox: CustomPoint; velodyne: x y z intensity time ring, padded to 32; ouster: ouster_ros::Point (48);
+    hesai: the 26-byte packed record of the XT32 driver (f64 timestamp at 16); tartanair: PointXYZ, no filter."""
+    if name == "livox":
+        l = ScanLayout()
+        st = load().vba_scan_layout_livox(C.byref(l))
+        if st != OK:
+            raise VbaError(st, "vba_scan_layout_livox")
+        return l
+    table = {
+        "velodyne": (32, 0, 4, 8, 0, SCAN_INTENSITY_NONE, 20, SCAN_TIME_F32, 1),
+        "ouster": (48, 0, 4, 8, 16, SCAN_INTENSITY_F32, 20, SCAN_TIME_U32_DIV1E9, 1),
+        "hesai": (26, 0, 4, 8, 12, SCAN_INTENSITY_F32, 16, SCAN_TIME_F64_REL_FIRST, 1),
+        "tartanair": (16, 0, 4, 8, 0, SCAN_INTENSITY_NONE, 0, SCAN_TIME_NONE, 0),
+    }
+    return ScanLayout(*table[name])
+
+
+def scan_layout_check(layout) -> int:
+    """vba_scan_layout_check (host only): the status, OK or ERR_BAD_ARG."""
+    return load().vba_scan_layout_check(C.byref(layout))
+
+
+class ScanFrame:
+    """One vba_scan_frame: the device buffers of one scan from the raw message to var_init's output."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx._chk(self.lib.vba_scan_frame_create(ctx.h, C.byref(h)))
+        self.h = h
+        self.n = 0
+        self.n_ds = 0
+        ctx._kf.append(self)         # destroyed with its context, as the stores are
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.vba_scan_frame_destroy(self.h)
+            self.h = None
+        kf = getattr(self.ctx, "_kf", None)
+        if kf is not None and self in kf:
+            kf.remove(self)
+
+    def reserve(self, max_raw_points, max_point_step):
+        self.ctx._chk(self.lib.vba_scan_frame_reserve(self.h, C.c_int(max_raw_points), C.c_int(max_point_step)))
+
+    def allocations(self):
+        n = C.c_int(); b = C.c_int64()
+        self.ctx._chk(self.lib.vba_scan_frame_allocations(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def decode(self, layout, raw, point_filter_num=1, blind2=0.0, n_raw=None):
+        """raw: the message's bytes (bytes or a uint8 array).  Returns (n, last_curvature)."""
+        buf = np.ascontiguousarray(np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray, memoryview)) else raw, dtype=np.uint8).ravel()
+        if n_raw is None:
+            n_raw = len(buf) // layout.point_step
+        if len(buf) < n_raw * layout.point_step:
+            raise ValueError("raw holds fewer than n_raw records")
+        n = C.c_int(0); last = C.c_double(0.0)
+        self.ctx._chk(self.lib.vba_scan_decode(self.h, C.byref(layout), buf.ctypes.data_as(C.c_void_p), C.c_int(n_raw), C.c_int(point_filter_num),
+                                               C.c_double(blind2), C.byref(n), C.byref(last)))
+        self.n = n.value; self.n_ds = 0
+        return n.value, last.value
+
+    def prepare(self, imu_poses22, end_pose12, ext_pose12, down_size, dept_err, beam_err, min_points=500, point_notime=False, ctx=None):
+        """Returns (n, d_pnt_body, d_var_body): the count and two DEVICE addresses (integers) owned by the frame."""
+        ctx = ctx or self.ctx
+        ip = _c(imu_poses22) if imu_poses22 is not None else np.zeros((0, 22))
+        end = _c(end_pose12) if end_pose12 is not None else None
+        n = C.c_int(0); dp = C.c_void_p(); dv = C.c_void_p()
+        ctx._chk(self.lib.vba_scan_prepare(ctx.h, self.h, C.c_int(len(ip)), _p(ip), _p(end), _p(_c(ext_pose12)), C.c_int(int(point_notime)),
+                                           C.c_double(down_size), C.c_int(min_points), C.c_double(dept_err), C.c_double(beam_err),
+                                           C.byref(n), C.byref(dp), C.byref(dv)))
+        self.n_ds = n.value
+        return n.value, dp.value or 0, dv.value or 0
+
+    def read(self, stage):
+        """stage 0 / 1: dict(pnt, intensity, curvature); 2: dict(pnt, count, first); 3: dict(pnt, var)."""
+        n = self.n if stage < 2 else self.n_ds
+        ip = C.POINTER(C.c_int)
+        pnt = np.zeros((n, 3)); out = dict(pnt=pnt)
+        inten = curv = cnt = first = var = None
+        if stage < 2:
+            inten = np.zeros(n, dtype=np.float32); curv = np.zeros(n); out.update(intensity=inten, curvature=curv)
+        elif stage == 2:
+            cnt = np.zeros(n, dtype=np.int32); first = np.zeros(n, dtype=np.int32); out.update(count=cnt, first=first)
+        else:
+            var = np.zeros((n, 9)); out.update(var=var)
+        self.ctx._chk(self.lib.vba_scan_frame_read(self.h, C.c_int(stage), _p(pnt), inten.ctypes.data_as(C.POINTER(C.c_float)) if inten is not None else None,
+                                                   _p(curv), cnt.ctypes.data_as(ip) if cnt is not None else None,
+                                                   first.ctypes.data_as(ip) if first is not None else None, _p(var)))
         return out
 
 
@@ -848,6 +956,15 @@ class Context:
         self._chk(self.lib.vba_map_pvec_update_cut_voxel(self.h, C.c_int(win_count), C.c_int(len(pnt_body)), _p(pnt_body), _p(var_body),
                                                          _p(pose12), _p(cov), C.c_int(int(multi))))
 
+    def pvec_update_cut_voxel_dev(self, win_count, n, d_pnt_body, d_var_body, pose12, cov225, multi=False):
+        """The same on DEVICE arrays (addresses as integers, e.g. what ScanFrame.prepare returns): consumed in place."""
+        pose12 = _c(pose12); cov = _c(cov225)
+        self._chk(self.lib.vba_map_pvec_update_cut_voxel(self.h, C.c_int(win_count), C.c_int(n), C.c_void_p(d_pnt_body), C.c_void_p(d_var_body),
+                                                         _p(pose12), _p(cov), C.c_int(int(multi))))
+
+    def scan_frame(self) -> "ScanFrame":
+        return ScanFrame(self)
+
     def var_init(self, pnt, ext_pose12, dept_err, beam_err):
         """var_init (voxelslam.hpp:210-234): returns (pnt_out, var_out)."""
         pnt = _c(pnt); ext = _c(ext_pose12)
@@ -936,6 +1053,12 @@ class Context:
         pnt_body = _c(pnt_body); var_body = _c(var_body)
         state = _c(state25).copy(); cov = _c(cov225).copy(); ok = C.c_int(0)
         self._chk(self.lib.vba_odom_lio_state_estimation(self.h, C.c_int(len(pnt_body)), _p(pnt_body), _p(var_body), _p(state), _p(cov), C.byref(ok)))
+        return bool(ok.value), state, cov
+
+    def lio_state_estimation_dev(self, n, d_pnt_body, d_var_body, state25, cov225):
+        """lio_state_estimation on DEVICE arrays (addresses as integers, e.g. what ScanFrame.prepare returns)."""
+        state = _c(state25).copy(); cov = _c(cov225).copy(); ok = C.c_int(0)
+        self._chk(self.lib.vba_odom_lio_state_estimation(self.h, C.c_int(n), C.c_void_p(d_pnt_body), C.c_void_p(d_var_body), _p(state), _p(cov), C.byref(ok)))
         return bool(ok.value), state, cov
 
     # ---- multi-GPU / timing

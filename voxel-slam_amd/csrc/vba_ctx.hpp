@@ -195,6 +195,19 @@ int btc_gen_ensure(vba_btc_db *db, int64_t points, int64_t cells, size_t corners
 int btc_generate_check(vba_btc_db *db, int n, int cap, double *rows, uint64_t *bits, int *n_stds);
 int btc_generate_impl(vba_btc_db *db, int n, const float *xyz, int id, int cap, double *rows, uint64_t *bits, int *n_stds);
 
+// ---------------------------------------------------------------- vba_kf.hip (vba_kernels_scan.hpp): the scan passes that the scan
+// frame of vba_scan.hip chains on its own buffers
+int ds_core(vba_ctx *c, hipStream_t stream, int mode, int n, const double *d_in, const double *d_var, int vrow, int vstep, double voxel_size,
+            bool det, const DsWork &w);
+size_t kf_ws_layout(vba_ctx *c, int n, bool det, char *base, DsWork *w, int *status);
+__global__ void k_iota(int *__restrict__ a, int n);
+__global__ __launch_bounds__(256) void k_ds_scan(int nb, int *__restrict__ blk, int *__restrict__ n_out);
+__global__ __launch_bounds__(256) void k_ds_emit(int n, const DsSlot *__restrict__ tab, const int *__restrict__ slot_of, const int *__restrict__ blk,
+                                                 double *__restrict__ out, int *__restrict__ count, int *__restrict__ first, double *__restrict__ vout, int mode);
+__global__ void k_undistort(int n, double *__restrict__ pnt, const double *__restrict__ curv, int m, const double *__restrict__ prm);
+__global__ void k_var_init(int n, const double *__restrict__ pin, double *__restrict__ pout, double *__restrict__ var, const double *__restrict__ ext,
+                           float range_inc, float degree_inc);
+
 // ---------------------------------------------------------------- vba_map.hip (vba_kernels_map.hpp, vba_kernels_loop.hpp)
 void map_init(MapStore &s, const vba_options &o);
 std::vector<DevArr> node_arrays(MapView &v, int W);

@@ -35,8 +35,11 @@ int vba_scan_var_init(vba_ctx *c, int n, const double *pnt_in, const double *ext
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return VBA_OK;
 }
-static int ds_core(vba_ctx *c, hipStream_t stream, int mode, int n, const double *d_in, const double *d_var, int vrow, int vstep, double voxel_size,
-                   bool det, const DsWork &w) {
+}  // extern "C"
+namespace vba {
+// also the down-sampling pass of vba_scan_prepare (vba_scan.hip)
+int ds_core(vba_ctx *c, hipStream_t stream, int mode, int n, const double *d_in, const double *d_var, int vrow, int vstep, double voxel_size,
+            bool det, const DsWork &w) {
   const int nb = (n + 255) / 256;
   hipLaunchKernelGGL(k_ds_clear, dim3((w.cap + 255) / 256), dim3(256), 0, stream, w.tab, w.cap);
   if (det) {
@@ -57,6 +60,8 @@ static int ds_core(vba_ctx *c, hipStream_t stream, int mode, int n, const double
   hipLaunchKernelGGL(k_ds_scan, dim3(1), dim3(256), 0, stream, nb, w.blk, w.n_out);
   return VBA_OK;
 }
+}  // namespace vba
+extern "C" {
 // mode 0 down_sampling_voxel, 1 down_sampling_pvec (var in, vout out), 2 down_sampling_close (first_out = chosen indices)
 static int ds_common(vba_ctx *c, int mode, int n, const double *pnt, const double *var, double voxel_size, double *pnt_out, double *vout, int *count_out,
                      int *first_out, int *n_out) {
@@ -182,7 +187,9 @@ int kf_alloc(vba_kf_store *s, T **p, size_t n) {
   return VBA_OK;
 }
 
-// layout of the down-sampler's work area for n points
+}  // namespace
+namespace vba {
+// layout of the down-sampler's work area for n points (also the scan frame's, vba_scan.hip)
 size_t kf_ws_layout(vba_ctx *c, int n, bool det, char *base, DsWork *w, int *status) {
   int cap = 1024;
   while (cap < 2 * n) cap <<= 1;
@@ -205,6 +212,8 @@ size_t kf_ws_layout(vba_ctx *c, int n, bool det, char *base, DsWork *w, int *sta
   *status = VBA_OK;
   return b_tab + b_i + b_blk + (det ? 3 * b_i + tmp : 0);
 }
+}  // namespace vba
+namespace {
 
 // grow-only: the keyframe arrays move (device-to-device copy, the old blocks are freed after a synchronise)
 int kf_ensure_rows(vba_kf_store *s, size_t need) {
