@@ -245,6 +245,29 @@ int vba_map_dump_plane_var(vba_ctx *ctx, double *out, int max_leaves);
 int vba_odom_lio_state_estimation(vba_ctx *ctx, int n, const double *pnt_body, const double *var_body, double *state,
                                   double *cov, int *ok);
 
+/* The same update with its 2-4 iterations resident on the device: no host round trip between them.
+ * d_pnt_body [n][3] and d_var_body [n][9] are DEVICE arrays (what vba_scan_prepare hands out), read in place and never copied;
+ * state [25] and cov [225] are host arrays, in/out, in the layout of vba_odom_lio_state_estimation; *ok (may be NULL) as there.
+ * Call shape: cov^-1 is computed on the host (the bits of the call above); ONE host-to-device copy of one parameter block; for each
+ * of the four possible iterations a point-loop launch and an update launch (one workgroup: fixed-order sum of the workgroup
+ * partials, the 15x15 EKF step, the stop rule rematch_num >= 2 || iter == 3 of VS:1073-1086, and at the stop cov <- (I - G) cov);
+ * after the stop the remaining launches find a flag in device memory and return at once; ONE device-to-host copy of one result
+ * block and ONE stream synchronise.  No atomics: the call is bit-reproducible with and without vba_options::deterministic.
+ * Scratch (device state, pinned image, partials) belongs to the context and only grows: a steady-state call allocates nothing.
+ * report (may be NULL) receives what the loop saw; entries of iterations that did not run are zero.
+ * n == 0 or a map that was never allocated: no point loop runs, all sums are zero, which the algebra takes as it is: the solution
+ * is exactly zero, iterations == 2, state and cov come back bit-identical, *ok = 0.
+ * VBA_ERR_BAD_ARG: NULL state / cov, n < 0, n > 0 with a NULL array.  VBA_ERR_UNSUPPORTED: a sharded context (n_ranks > 1) - the
+ * all-reduce hook cannot run between iterations that the host never sees. */
+typedef struct vba_odom_report {
+  int iterations;                  /* EKF iterations run, 2..4 (VS:990-1087) */
+  int match_num[4];                /* per iteration, VS:1048 */
+  double rot_add[4], tra_add[4];   /* |solution(0:3)|, |solution(3:6)| per iteration, VS:1061-1062 */
+  double nnt_eig_min;              /* evalue[0] of the last iteration's nnt, VS:1090-1094 */
+} vba_odom_report;
+int vba_odom_lio_state_estimation_resident(vba_ctx *ctx, int n, const double *d_pnt_body, const double *d_var_body,
+                                           double *state, double *cov, int *ok, vba_odom_report *report /* may be NULL */);
+
 /* void VOXEL_SLAM::lio_state_estimation_kdtree(PVecPtr pptr) (VS:1102-1252), the odometry used while the system initialises:
  * scan points against a point-cloud map (pl_tree, kept by the context) through an exact 5-nearest-neighbour plane fit.
  * While the map holds fewer than 100 points the scan only seeds it (VS:1105-1118, *iterations = 0); otherwise state / cov

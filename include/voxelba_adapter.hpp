@@ -474,6 +474,14 @@ inline bool lio_state_estimation(Context &ctx, const ScanView &scan, IMUST &x_cu
   return ok != 0;
 }
 
+// The same with the EKF iterations resident on the device: one upload, one download, one wait.  report, when
+// given, receives the iteration count, the matches and step norms per iteration and the smallest eigenvalue of nnt.
+inline bool lio_state_estimation_resident(Context &ctx, const ScanView &scan, IMUST &x_curr, vba_odom_report *report = nullptr) {
+  int ok = 0;
+  check(ctx.get(), vba_odom_lio_state_estimation_resident(ctx.get(), scan.n, scan.pnt, scan.var, &x_curr.t, x_curr.cov, &ok, report));
+  return ok != 0;
+}
+
 // VOXEL_SLAM::lio_state_estimation_kdtree(pptr) VS:1102-1252: x_curr (state + cov) in/out, the point-cloud map (pl_tree) lives in
 // the context.  Returns the number of EKF iterations (0 while the map is only being seeded).
 inline int lio_state_estimation_kdtree(Context &ctx, const std::vector<pointVar> &pvec, IMUST &x_curr) {

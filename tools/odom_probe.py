@@ -1,27 +1,97 @@
-"""Timing of the odometry scan-to-map update (vba_odom_lio_state_estimation) on the bench-size map: 200k-point scan."""
-import sys, os, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+"""Measurement of the scan-to-map EKF update for DESIGN.md section 17 (run on an MI355X): one 200k-point scan against the full
+hesai200k_w10 window map (the set-up of bench.py's odometry_update), the same state and covariance for every call.
+    python tools/odom_probe.py [out.json=profiles/odom_probe.json] [reps=5]
+  (a) resident   vba_odom_lio_state_estimation_resident on device pointers (one upload, 8 launches, one download, one wait)
+  (b) existing   vba_odom_lio_state_estimation on the SAME device pointers (device-to-device staging, a host round trip pair per iteration)
+  (c) host       vba_odom_lio_state_estimation on host arrays (points + covariances uploaded per call: the number of the bench)
+The three alternate in one process; median of `reps` after a warm-up round; host clocks around calls that end in a device
+synchronise.  Every record holds the EKF iteration count: (a) reports its own, and (b), (c) run the same iterations on the same
+input (their results are checked against (a) at the bars of tests/test_gpu_odom.py).  Acceptance: median (a) <= median (b)."""
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
-import voxel_slam_amd
+import torch
+import voxel_slam_amd  # noqa: F401
 from voxel_slam_amd import capi, synth
-wl = synth.CONFIGS["hesai200k_w10"]
-s = synth.make_scans(wl)
-W = wl.win_size
-poses = synth.poses_flat(s["R_gt"], s["p_gt"])
-ctx = capi.Context(capi.options_from_workload(wl))
-rng = np.random.default_rng(1)
-def rand_var(n, scale=0.01):
-    A = rng.normal(0, scale, (n, 3, 3))
-    return np.ascontiguousarray((A @ A.transpose(0, 2, 1) + 1e-6 * np.eye(3)).reshape(n, 9))
-for i in range(W):
-    ctx.cut_voxel(i, s["points"][i], poses[i], var=rand_var(len(s["points"][i])), multi=True)
-ctx.recut(W, poses, multi=True)
-ctx.margi(W, poses, jour=0.0)          # refreshes the planes (plane_update)
-k = W - 1
-state = np.zeros(25); state[1:10] = s["R_gt"][k].ravel(); state[10:13] = s["p_gt"][k] + 0.01; state[22:25] = [0, 0, -9.8]
-cov = np.eye(15) * 1e-4
-pts = s["points"][k]; var_b = rand_var(len(pts), 0.005)
-ok, st, cv = ctx.lio_state_estimation(pts, var_b, state, cov)
-t0 = time.perf_counter()
-for _ in range(10): ok, st, cv = ctx.lio_state_estimation(pts, var_b, state, cov)
-print("lio_state_estimation: %.2f ms per call (%d points, ok=%s)" % (1e2 * (time.perf_counter() - t0), len(pts), ok))
+from prof_summary import source_hash  # noqa: E402
+
+
+def main():
+    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "odom_probe.json")
+    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    wl = synth.CONFIGS["hesai200k_w10"]
+    W = wl.win_size
+    t0 = time.time()
+    torch.cuda.set_device(0)
+    torch.zeros(1, device="cuda:0")                # torch's HIP runtime comes up before the library's context, as in bench.py
+    scans = synth.make_scans(wl)
+    poses = synth.poses_flat(scans["R_gt"], scans["p_gt"])
+    ctx = capi.Context(capi.options_from_workload(wl))
+    rng = np.random.default_rng(1)
+
+    def rand_var(n, scale):
+        A = rng.normal(0, scale, (n, 3, 3))
+        return np.ascontiguousarray((A @ A.transpose(0, 2, 1) + 1e-6 * np.eye(3)).reshape(n, 9))
+    for i in range(W):
+        ctx.cut_voxel(i, scans["points"][i], poses[i], var=rand_var(len(scans["points"][i]), 0.01), multi=True)
+    ctx.recut(W, poses, multi=True)
+    ctx.margi(W, poses, jour=0.0)                  # plane_update runs inside margi
+    k = W - 1
+    state = np.zeros(25); state[1:10] = scans["R_gt"][k].ravel(); state[10:13] = scans["p_gt"][k] + 0.01; state[22:25] = [0, 0, -9.8]
+    cov = np.eye(15) * 1e-4
+    pts = np.ascontiguousarray(scans["points"][k], dtype=np.float64); var_b = rand_var(len(pts), 0.005)
+    n = len(pts)
+    d_p = torch.from_numpy(pts).to("cuda:0"); d_v = torch.from_numpy(var_b).to("cuda:0")
+    torch.cuda.synchronize()
+    ctx.synchronize()
+    print("%d points, W = %d (%.1f s to set up)" % (n, W, time.time() - t0), flush=True)
+
+    def resident():
+        ok, st, cv, rep = ctx.lio_state_estimation_resident(n, d_p.data_ptr(), d_v.data_ptr(), state, cov)
+        return ok, st, cv, rep["iterations"]
+
+    def existing():
+        return ctx.lio_state_estimation_dev(n, d_p.data_ptr(), d_v.data_ptr(), state, cov) + (None,)
+
+    def host():
+        return ctx.lio_state_estimation(pts, var_b, state, cov) + (None,)
+
+    legs = (("resident_dev", resident), ("existing_dev", existing), ("existing_host", host))
+    recs = {name: [] for name, _ in legs}
+    out = {}
+    for r in range(reps + 1):                      # round 0 is the warm-up
+        for name, f in legs:
+            t1 = time.perf_counter(); res = f(); dt = time.perf_counter() - t1
+            out[name] = res
+            if r:
+                recs[name].append(dt * 1e3)
+    ok_a, st_a, cv_a, iters = out["resident_dev"]
+    for name in ("existing_dev", "existing_host"):
+        ok_b, st_b, cv_b, _ = out[name]
+        assert ok_a == ok_b, name
+        assert np.abs(st_a - st_b).max() < 1e-7, (name, np.abs(st_a - st_b).max())
+        assert np.abs(cv_a - cv_b).max() < 1e-9 * np.abs(cv_b).max(), name
+    rep = ctx.lio_state_estimation_resident(n, d_p.data_ptr(), d_v.data_ptr(), state, cov)[3]
+    res = dict(source_hash=source_hash(), workload=wl.name, points=n, reps=reps, converged=bool(ok_a), iterations=int(iters),
+               match_num=[int(x) for x in rep["match_num"]], nnt_eig_min=float(rep["nnt_eig_min"]),
+               state_vs_existing=float(np.abs(st_a - out["existing_dev"][1]).max()))
+    for name, _ in legs:
+        t = np.array(recs[name])
+        res[name] = dict(median_ms=float(np.median(t)), min_ms=float(t.min()), max_ms=float(t.max()), iterations=int(iters), runs_ms=[float(x) for x in t])
+        print("%-14s median %.3f ms (min %.3f, max %.3f), %d EKF iterations" % (name, np.median(t), t.min(), t.max(), iters), flush=True)
+    res["resident_over_existing_dev"] = res["resident_dev"]["median_ms"] / res["existing_dev"]["median_ms"]
+    res["acceptance_met"] = bool(res["resident_dev"]["median_ms"] <= res["existing_dev"]["median_ms"])
+    print("resident / existing on device pointers: %.3f -> acceptance %s" % (res["resident_over_existing_dev"], "met" if res["acceptance_met"] else "NOT met"))
+    ctx.close()
+    json.dump(res, open(out_path, "w"), indent=1)
+    print("OK")
+
+
+if __name__ == "__main__":
+    main()

@@ -27,7 +27,7 @@ EXPORTS = [
     "vba_lidar_ba_damping_iter", "vba_li_ba_damping_iter", "vba_last_lm_trace",
     "vba_imu_preintegrate", "vba_imu_give_evaluate",
     "vba_map_cut_voxel", "vba_map_pvec_update_cut_voxel", "vba_scan_var_init", "vba_scan_down_sampling_voxel", "vba_scan_down_sampling_pvec", "vba_scan_down_sampling_close", "vba_scan_undistort", "vba_odom_lio_state_estimation_kdtree", "vba_odom_kdtree_reset", "vba_odom_kdtree_size", "vba_odom_kdtree_points", "vba_gba_build", "vba_hba_add_edge", "vba_hba_global", "vba_map_cut_voxel_fix", "vba_map_recut", "vba_map_margi", "vba_map_slide", "vba_map_prune", "vba_map_reset",
-    "vba_map_num_roots", "vba_map_num_slide_roots", "vba_map_stats", "vba_map_dump_leaves", "vba_map_dump_plane_var", "vba_odom_lio_state_estimation",
+    "vba_map_num_roots", "vba_map_num_slide_roots", "vba_map_stats", "vba_map_dump_leaves", "vba_map_dump_plane_var", "vba_odom_lio_state_estimation", "vba_odom_lio_state_estimation_resident",
     "vba_set_allreduce", "vba_rccl_get_unique_id", "vba_rccl_init", "vba_set_rccl_comm", "vba_shard_owner", "vba_set_shard",
     "vba_timing_enable", "vba_timing_calibration_read", "vba_timing_select", "vba_timing_sample_every", "vba_timing_launch_hessian", "vba_timing_null_span", "vba_timing_reset", "vba_timing_get",
     "vba_lm_begin", "vba_lm_refresh_eigen", "vba_lm_iterate", "vba_lm_end", "vba_debug_solve",
@@ -529,6 +529,12 @@ class ScanFrame:
                                                    _p(curv), cnt.ctypes.data_as(ip) if cnt is not None else None,
                                                    first.ctypes.data_as(ip) if first is not None else None, _p(var)))
         return out
+
+
+class OdomReport(C.Structure):
+    """vba_odom_report (include/voxelba.h)."""
+    _fields_ = [("iterations", C.c_int), ("match_num", C.c_int * 4), ("rot_add", C.c_double * 4), ("tra_add", C.c_double * 4),
+                ("nnt_eig_min", C.c_double)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -1060,6 +1066,17 @@ class Context:
         state = _c(state25).copy(); cov = _c(cov225).copy(); ok = C.c_int(0)
         self._chk(self.lib.vba_odom_lio_state_estimation(self.h, C.c_int(n), C.c_void_p(d_pnt_body), C.c_void_p(d_var_body), _p(state), _p(cov), C.byref(ok)))
         return bool(ok.value), state, cov
+
+    def lio_state_estimation_resident(self, n, d_pnt_body, d_var_body, state25, cov225):
+        """The same update with its iterations resident on the device on DEVICE arrays (addresses as integers),
+        read in place.  Returns (ok, state, cov, report) with report a dict: iterations, match_num[4], rot_add[4], tra_add[4] (entries
+        of iterations that did not run are zero) and nnt_eig_min."""
+        state = _c(state25).copy(); cov = _c(cov225).copy(); ok = C.c_int(0); rep = OdomReport()
+        self._chk(self.lib.vba_odom_lio_state_estimation_resident(self.h, C.c_int(n), C.c_void_p(d_pnt_body), C.c_void_p(d_var_body), _p(state), _p(cov),
+                                                                  C.byref(ok), C.byref(rep)))
+        report = dict(iterations=rep.iterations, match_num=np.array(rep.match_num[:], dtype=np.int64), rot_add=np.array(rep.rot_add[:]),
+                      tra_add=np.array(rep.tra_add[:]), nnt_eig_min=rep.nnt_eig_min)
+        return bool(ok.value), state, cov, report
 
     # ---- multi-GPU / timing
     def lio_state_estimation_kdtree(self, pnt_body, state25, cov225):

@@ -27,6 +27,7 @@ using namespace vba;
 namespace vba {
 struct TimedSpan { hipEvent_t a, b; };
 }
+namespace vbh { struct OdomEkf; }   // vba_odom_ekf.hpp
 
 struct vba_ctx {
   vba_options opt;
@@ -116,6 +117,10 @@ struct vba_ctx {
   char *d_exp = nullptr; size_t exp_cap = 0;            // keyframes
   char *d_expout = nullptr; size_t expout_cap = 0;      // records
   std::vector<long long> exp_first; std::vector<int> exp_kbase;   // host scratch: exported points before every keyframe, keyframes before every store
+  // vba_odom_lio_state_estimation_resident: the loop's device state, its pinned image (parameter block up, result
+  // block down) and the point loop's workgroup partials; grow-only
+  vbh::OdomEkf *d_odom = nullptr, *h_odom = nullptr;
+  double *d_odom_part = nullptr; size_t odom_part_doubles = 0;
 
   void set_error(const std::string &s) { err = s; }
 };
@@ -233,6 +238,8 @@ int map_dump_plane_var(MapStore &s, hipStream_t st, double *out, int max_leaves,
 int map_prune(MapStore &s, hipStream_t st, double jour, int dist, std::string &err);
 int map_odom_accumulate(MapStore &s, hipStream_t st, const OdomState &X, int n, const double *d_pts, const double *d_var,
                         double *d_partial, double *d_out34, double *out34, std::string &err);
+int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomEkf *h_img, int n, const double *d_pts,
+                      const double *d_var, double *d_partial, std::string &err);
 int map_fix_source_ensure(MapStore &s, hipStream_t st, size_t nodes, size_t fix, size_t n, std::string &err);
 int map_cut_voxel_fix_source(MapStore &s, hipStream_t st, int n, const FixSource &src, double jour, std::string &err);
 // fills the map's root table with the empty key, also the hash tables of vba_kernels_big.hpp in voxelba.hip

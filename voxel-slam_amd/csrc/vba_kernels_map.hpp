@@ -1612,8 +1612,10 @@ __global__ void k_prune_fix(MapView m) {
 // (read-only probe), octant descent, the two 3-sigma gates, then the weighted normal equations
 //   HTH (6x6 sym, 21) | HTz (6) | nnt (3x3 sym, 6) | match_num   = 34 sums per workgroup.
 // The reference's per-point cache octos[i] (voxelslam.cpp:1020) only short-cuts the lookup; the full lookup is done here.
-__global__ __launch_bounds__(256) void k_odom_match(MapView m, MapParams P, OdomState X, int n, const double *__restrict__ pts,
-                                                    const double *__restrict__ var, double *__restrict__ partial) {
+// The body is shared by the two kernels that run it: k_odom_match takes the pose and the covariance blocks by value, k_odom_match_dev
+// (vba_kernels_odom.hpp) reads them from the device state of the resident EKF loop.
+__device__ __forceinline__ void odom_match_body(const MapView &m, const MapParams &P, const OdomState &X, int n, const double *__restrict__ pts,
+                                                const double *__restrict__ var, double *__restrict__ partial) {
   __shared__ double red[4][34];
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   const size_t cp = (size_t)m.cap;
@@ -1712,6 +1714,10 @@ __global__ __launch_bounds__(256) void k_odom_match(MapView m, MapParams P, Odom
     for (int k = 0; k < 34; k++) red[threadIdx.x >> 6][k] = acc[k];
   __syncthreads();
   if (threadIdx.x < 34) partial[(size_t)blockIdx.x * 34 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+__global__ __launch_bounds__(256) void k_odom_match(MapView m, MapParams P, OdomState X, int n, const double *__restrict__ pts,
+                                                    const double *__restrict__ var, double *__restrict__ partial) {
+  odom_match_body(m, P, X, n, pts, var, partial);
 }
 
 // ------------------------------------------------------------------------------------------------ dumps

@@ -1,0 +1,82 @@
+// The device-resident iterated EKF of the odometry scan-to-map update (VOXEL_SLAM::lio_state_estimation,
+// voxelslam.cpp:962-1098):
+//   k_odom_match_dev   the point loop of k_odom_match (vba_kernels_map.hpp) with the pose and the covariance blocks read from the
+//                      device state of the loop instead of the kernel arguments
+//   k_odom_update      ONE workgroup: sums the workgroup partials in a fixed order and runs one iteration of vba_odom_ekf.hpp on them
+// Both read the state's `done` flag first and return at once when the stop rule has fired, so the host queues all four iterations
+// without waiting for any of them (the pattern of LmDev::stop in vba_kernels_lm.hpp).  No atomics.  Included after vba_kernels_map.hpp.
+#pragma once
+#include "vba_odom_ekf.hpp"
+
+namespace vba {
+
+typedef __attribute__((address_space(3))) double odom_lds_f64;
+
+// a double every lane loaded from the same address, made wave-uniform for the compiler too
+__device__ __forceinline__ double odom_uniform(double x) {
+  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(x)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(x));
+  return __hiloint2double(hi, lo);
+}
+
+__global__ __launch_bounds__(256) void k_odom_match_dev(MapView m, MapParams P, const vbh::OdomEkf *__restrict__ S, int n,
+                                                        const double *__restrict__ pts, const double *__restrict__ var,
+                                                        double *__restrict__ partial) {
+  if (__builtin_amdgcn_readfirstlane(S->done)) return;
+  OdomState X;
+#pragma unroll
+  for (int k = 0; k < 9; k++) { X.R[k] = odom_uniform(S->R[k]); X.rot_var[k] = odom_uniform(S->rot_var[k]); X.tsl_var[k] = odom_uniform(S->tsl_var[k]); }
+#pragma unroll
+  for (int k = 0; k < 3; k++) X.t[k] = odom_uniform(S->t[k]);
+  odom_match_body(m, P, X, n, pts, var, partial);
+}
+
+struct OdomWgSync { __device__ __forceinline__ void operator()() const { __syncthreads(); } };
+
+// Column c of the nb x 34 partials is summed by the seven lanes c, c + 34, ..., c + 204: lane t adds the elements t, t + 238,
+// t + 476, ... of the flat array (rows t / 34, t / 34 + 7, ... of its column: consecutive lanes read consecutive doubles) in that
+// order, then lane c adds the seven group sums in group order.  The order depends on nb alone.
+static constexpr int ODOM_RED_LANES = 7 * 34;
+__global__ __launch_bounds__(256) void k_odom_update(vbh::OdomEkf *S, const double *__restrict__ partial, int nb, int iter) {
+#pragma clang fp contract(off)
+  __shared__ double wsm[vbh::OE_WORK];
+  __shared__ double red[ODOM_RED_LANES];
+  if (__builtin_amdgcn_readfirstlane(S->done)) return;
+  odom_lds_f64 *w = (odom_lds_f64 *)wsm;
+  odom_lds_f64 *rd = (odom_lds_f64 *)red;
+  const int t = threadIdx.x;
+  if (t < ODOM_RED_LANES) {
+    const size_t tot = (size_t)nb * 34;
+    double s = 0.0;
+    for (size_t i = t; i < tot; i += ODOM_RED_LANES) s += partial[i];
+    rd[t] = s;
+  }
+  __syncthreads();
+  if (t < 34) {
+    double s = rd[t];
+    for (int g = 1; g < 7; g++) s += rd[t + 34 * g];
+    w[vbh::OE_S34 + t] = s;
+  }
+  __syncthreads();
+  vbh::odom_ekf_iterate(w, S, iter, t, 256, OdomWgSync());
+}
+
+// The whole call on the stream: one upload of the image, (match, update) x 4, one download of the result block, one wait.  h_img
+// is pinned and holds the image on entry and the result block on return.
+int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomEkf *h_img, int n, const double *d_pts,
+                      const double *d_var, double *d_partial, std::string &err) {
+  MAPCHK(hipMemcpyAsync(d_S, h_img, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, st));
+  const bool match = n > 0 && s.allocated;               // otherwise every sum is zero: the update runs on no partials
+  const int nb = match ? (n + 255) / 256 : 0;
+  const MapParams P = map_params(s);
+  for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
+    if (match) hipLaunchKernelGGL(k_odom_match_dev, dim3(nb), dim3(256), 0, st, s.v, P, (const vbh::OdomEkf *)d_S, n, d_pts, d_var, d_partial);
+    hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, st, d_S, (const double *)d_partial, nb, iter);
+  }
+  MAPCHK(hipGetLastError());
+  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
+  MAPCHK(hipMemcpyAsync((char *)h_img + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, st));
+  MAPCHK(hipStreamSynchronize(st));
+  return VBA_OK;
+}
+
+}  // namespace vba

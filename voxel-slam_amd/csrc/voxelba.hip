@@ -13,6 +13,7 @@
 #include "vba_kernels_init.hpp"
 #include <cstddef>
 #include "vba_hostmath.hpp"
+#include "vba_odom_ekf.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>     // TYPES only: the entry points are resolved at run time (rccl_api below), the library does not link librccl
@@ -603,6 +604,9 @@ void vba_destroy(vba_ctx *c) {
   for (int i = 0; i < vba_ctx::kExpRing; i++) { if (c->h_exp[i]) hipHostFree(c->h_exp[i]); if (c->exp_ev[i]) hipEventDestroy(c->exp_ev[i]); }
   if (c->d_exp) hipFree(c->d_exp);
   if (c->d_expout) hipFree(c->d_expout);
+  if (c->d_odom) hipFree(c->d_odom);
+  if (c->h_odom) hipHostFree(c->h_odom);
+  if (c->d_odom_part) hipFree(c->d_odom_part);
   if (c->d_lipack) hipFree(c->d_lipack);
   if (c->d_liscr) hipFree(c->d_liscr);
   for (int i = 0; i < 2; i++) if (c->d_kdtree[i]) hipFree(c->d_kdtree[i]);
@@ -2218,30 +2222,44 @@ int vba_odom_lio_state_estimation(vba_ctx *c, int n, const double *pnt_body, con
   }
   std::memcpy(state, &x_curr, sizeof(x_curr));
   std::memcpy(cov, P.data(), 225 * sizeof(double));
-  if (ok) {
-    // SelfAdjointEigenSolver(nnt).eigenvalues()[0] < 14 -> false  (VS:1090-1097); closed form is not needed here: Jacobi on host
-    double a[3][3] = {{nnt[0], nnt[1], nnt[2]}, {nnt[3], nnt[4], nnt[5]}, {nnt[6], nnt[7], nnt[8]}};
-    for (int sweep = 0; sweep < 60; sweep++) {
-      const double off = std::fabs(a[0][1]) + std::fabs(a[0][2]) + std::fabs(a[1][2]);
-      if (off == 0.0) break;
-      for (int p = 0; p < 2; p++)
-        for (int q = p + 1; q < 3; q++) {
-          if (a[p][q] == 0.0) continue;
-          const double theta = 0.5 * (a[q][q] - a[p][p]) / a[p][q];
-          double t = 1.0 / (std::fabs(theta) + std::sqrt(1.0 + theta * theta));
-          if (theta < 0) t = -t;
-          const double cth = 1.0 / std::sqrt(1 + t * t), sth = t * cth, apq = a[p][q];
-          const int r = 3 - p - q;
-          const double arp = a[r][p], arq = a[r][q];
-          a[p][p] -= t * apq; a[q][q] += t * apq; a[p][q] = a[q][p] = 0.0;
-          a[r][p] = a[p][r] = cth * arp - sth * arq; a[r][q] = a[q][r] = sth * arp + cth * arq;
-          if (std::fabs(a[r][p]) < 1e-300) a[r][p] = a[p][r] = 0.0;
-          if (std::fabs(a[r][q]) < 1e-300) a[r][q] = a[q][r] = 0.0;
-        }
-      if (off < 1e-14 * (std::fabs(a[0][0]) + std::fabs(a[1][1]) + std::fabs(a[2][2]))) break;
-    }
-    const double emin = std::min(a[0][0], std::min(a[1][1], a[2][2]));
-    *ok = (emin < 14) ? 0 : 1;
+  // SelfAdjointEigenSolver(nnt).eigenvalues()[0] < 14 -> false  (VS:1090-1097); closed form is not needed here: Jacobi on host
+  if (ok) *ok = (vbh::odom_nnt_eig_min(nnt) < 14) ? 0 : 1;
+  return VBA_OK;
+}
+
+// The same update with the iterations resident on the device: the host inverts P once, writes one image, queues the
+// four (point loop, update) pairs and waits once; which of them do any work is decided by the `done` flag in the device state.
+int vba_odom_lio_state_estimation_resident(vba_ctx *c, int n, const double *d_pnt_body, const double *d_var_body, double *state, double *cov,
+                                           int *ok, vba_odom_report *report) {
+  if (n < 0 || (n > 0 && (!d_pnt_body || !d_var_body)) || !state || !cov) return VBA_ERR_BAD_ARG;
+  if (c->n_ranks > 1) { c->set_error("the resident odometry loop has no all-reduce step between its iterations: unsharded contexts only"); return VBA_ERR_UNSUPPORTED; }
+  if (!c->d_odom) {
+    HIPCHK(c, hipMalloc((void **)&c->d_odom, sizeof(vbh::OdomEkf)));
+    HIPCHK(c, hipHostMalloc((void **)&c->h_odom, sizeof(vbh::OdomEkf), hipHostMallocDefault));
+  }
+  const size_t need = (size_t)((n + 255) / 256) * 34;
+  if (need > c->odom_part_doubles) {
+    if (c->d_odom_part) hipFree(c->d_odom_part);       // idle: the call that used it ended in a synchronise
+    c->d_odom_part = nullptr; c->odom_part_doubles = 0;
+    size_t cap = 256 * 34;
+    while (cap < need) cap *= 2;
+    HIPCHK(c, hipMalloc((void **)&c->d_odom_part, cap * sizeof(double)));
+    c->odom_part_doubles = cap;
+  }
+  double cov_inv[225];
+  vbh::inverse_pplu(cov, cov_inv, VBA_DIM);                                // VS:987
+  vbh::OdomEkf &S = *c->h_odom;
+  vbh::odom_ekf_begin(S, state, cov, cov_inv);
+  const int st = map_odom_resident(c->map, c->stream, c->d_odom, c->h_odom, n, d_pnt_body, d_var_body, c->d_odom_part, c->err);
+  if (st) return st;
+  std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
+  std::memcpy(cov, S.P_out, sizeof(S.P_out));
+  const double emin = vbh::odom_nnt_eig_min(S.nnt);
+  if (ok) *ok = (emin < 14) ? 0 : 1;
+  if (report) {
+    report->iterations = S.iterations;
+    for (int k = 0; k < 4; k++) { report->match_num[k] = S.match_num[k]; report->rot_add[k] = S.rot_add[k]; report->tra_add[k] = S.tra_add[k]; }
+    report->nnt_eig_min = emin;
   }
   return VBA_OK;
 }
