@@ -278,6 +278,43 @@ int vba_odom_kdtree_reset(vba_ctx *ctx);   /* pl_tree->clear() */
 int vba_odom_kdtree_size(vba_ctx *ctx);    /* pl_tree->size() */
 int vba_odom_kdtree_points(vba_ctx *ctx, double *xyz_out /* [size][3] */);
 
+/* lio_state_estimation_kdtree (VS:1102-1252) on DEVICE points, read in place; iterations, map append and 0.5 m re-sampling stay on
+ * the device.  d_pnt_body [n][3] is a DEVICE array of doubles (what vba_scan_prepare hands out), used as the
+ * doubles it holds: only the 5-NN query and the appended map point are rounded to float (VS:1155-1157, VH:223-229).  state [25] and
+ * cov [225] are host arrays, in/out; *iterations (may be NULL) as in the call above.  The map is the one the call above keeps: the two
+ * calls may alternate on one context.
+ * Call shape, map below 100 points (seeding, VS:1105-1118): ONE append launch with the pose passed by value; *iterations = 0, state
+ * and cov untouched; no copy and no wait - the call is stream-ordered (vba_odom_kdtree_points and every later call follow it on the
+ * context's stream).
+ * Call shape, estimation: cov^-1 / 1000 is computed on the host (the bits of the call above); ONE host-to-device copy of one parameter
+ * block; for each of the four possible iterations four launches - 5-NN candidates per map slice, slice merge + plane fit, the 28 sums
+ * per workgroup, and the one-workgroup update of vba_odom_lio_state_estimation_resident under the kd stop rule (only a converged
+ * iteration counts as a rematch; refind = converged || (iter == 2 && none converged yet)), 16 launches in all; one append launch
+ * that reads its pose from the device state; the 0.5 m re-sampling of map + scan into the other half of the map's ping-pong; ONE
+ * device-to-host copy of one result block, which carries the new map size; ONE stream synchronise.  Every launch of the loop reads a
+ * `done` flag in device memory first and returns at once when the stop rule has fired; the search and fit launches also return when
+ * the device-side refind flag is clear, so the planes of the last search stay in place for the sums.  The re-sampling's count and
+ * first-index arrays are not downloaded.
+ * n == 0 on a map of 100 points or more: no search, fit, sum or append launch; the update runs on zero sums (the solution is exactly
+ * zero, *iterations = 2, state and cov come back bit-identical) and the map is still re-sampled, as the call above does.
+ * No atomics except the ones of the re-sampling's non-deterministic mode: with vba_options::deterministic = 1 two contexts given the
+ * same call sequence return identical bits for state, cov, report and map.
+ * report (may be NULL): iterations, match_num[i] = points with an accepted plane, rot_add, tra_add; nnt_eig_min = 0 (this variant has
+ * no nnt); all zero after a seeding call.
+ * Scratch belongs to the context and grows by doubling after a synchronise.  After vba_odom_kdtree_reserve(max_map_points,
+ * max_scan_points) no call allocates while size + n <= max_map_points and n <= max_scan_points: the reservation covers both halves of
+ * the map, the candidates at the largest slice count, planes, partial sums, the re-sampler's work area and the pinned block.
+ * vba_odom_kdtree_allocations counts the allocations of all of these and the bytes they asked for, cumulatively, as
+ * vba_scan_frame_allocations does: a block that grows is counted again at its new size and the freed one is not subtracted, so a
+ * counter that does not move means that nothing was allocated.  The map's halves are counted whichever of the two kd-tree calls grew
+ * them; the loop state and its pinned block are shared with vba_odom_lio_state_estimation_resident and counted here whichever call
+ * allocated them first.
+ * VBA_ERR_BAD_ARG: NULL state / cov, n < 0, n > 0 with a NULL array, a negative reservation. */
+int vba_odom_lio_state_estimation_kdtree_resident(vba_ctx *ctx, int n, const double *d_pnt_body, double *state, double *cov,
+                                                  int *iterations, vba_odom_report *report /* may be NULL */);
+int vba_odom_kdtree_reserve(vba_ctx *ctx, int max_map_points, int max_scan_points);
+int vba_odom_kdtree_allocations(vba_ctx *ctx, int *n_allocs, int64_t *bytes);
+
 /* ------------------------------------------------------------------------------------------------
  * LiDAR-inertial initialisation: int Initialization::motion_init(pl_origs, vec_imus, beg_times, hess, voxhess, x_buf, surf_map,
  * surf_map_slide, pvec_buf, win_size, sws, x_curr, imu_pre_buf, extrin_para) (VS:617-819, called from initialization at VS:1524).

@@ -493,6 +493,16 @@ inline int lio_state_estimation_kdtree(Context &ctx, const std::vector<pointVar>
   return iters;
 }
 
+// The same on a prepared scan frame: the frame's device points are read in place, as the doubles they are
+// (pv.pnt is a Vector3d, VS:1155-1157; the overload above rounds them to float first), and the iterations, the map append and the
+// re-sampling stay on the device: one upload, one download, one wait.  report, when given, receives the iteration count and the
+// valid points and step norms per iteration.
+inline int lio_state_estimation_kdtree(Context &ctx, const ScanView &scan, IMUST &x_curr, vba_odom_report *report = nullptr) {
+  int iters = 0;
+  check(ctx.get(), vba_odom_lio_state_estimation_kdtree_resident(ctx.get(), scan.n, scan.pnt, &x_curr.t, x_curr.cov, &iters, report));
+  return iters;
+}
+
 // FileReaderWriter::save_pcd / save_pose (VS:166-204), pcl::io::loadPCDFile (VS:340), read_lidarstate (VH:268-307)
 inline void save_pcd(const std::vector<pointVar> &pvec, int count, const std::string &savename) {
   std::vector<double> p(pvec.size() * 3);

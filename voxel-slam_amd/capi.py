@@ -26,7 +26,7 @@ EXPORTS = [
     "vba_factor_evaluate_only_residual", "vba_factor_read_back", "vba_factor_occupied_slots", "vba_factor_occupancy_masks",
     "vba_lidar_ba_damping_iter", "vba_li_ba_damping_iter", "vba_last_lm_trace",
     "vba_imu_preintegrate", "vba_imu_give_evaluate",
-    "vba_map_cut_voxel", "vba_map_pvec_update_cut_voxel", "vba_scan_var_init", "vba_scan_down_sampling_voxel", "vba_scan_down_sampling_pvec", "vba_scan_down_sampling_close", "vba_scan_undistort", "vba_odom_lio_state_estimation_kdtree", "vba_odom_kdtree_reset", "vba_odom_kdtree_size", "vba_odom_kdtree_points", "vba_gba_build", "vba_hba_add_edge", "vba_hba_global", "vba_map_cut_voxel_fix", "vba_map_recut", "vba_map_margi", "vba_map_slide", "vba_map_prune", "vba_map_reset",
+    "vba_map_cut_voxel", "vba_map_pvec_update_cut_voxel", "vba_scan_var_init", "vba_scan_down_sampling_voxel", "vba_scan_down_sampling_pvec", "vba_scan_down_sampling_close", "vba_scan_undistort", "vba_odom_lio_state_estimation_kdtree", "vba_odom_kdtree_reset", "vba_odom_kdtree_size", "vba_odom_kdtree_points", "vba_odom_lio_state_estimation_kdtree_resident", "vba_odom_kdtree_reserve", "vba_odom_kdtree_allocations", "vba_gba_build", "vba_hba_add_edge", "vba_hba_global", "vba_map_cut_voxel_fix", "vba_map_recut", "vba_map_margi", "vba_map_slide", "vba_map_prune", "vba_map_reset",
     "vba_map_num_roots", "vba_map_num_slide_roots", "vba_map_stats", "vba_map_dump_leaves", "vba_map_dump_plane_var", "vba_odom_lio_state_estimation", "vba_odom_lio_state_estimation_resident",
     "vba_set_allreduce", "vba_rccl_get_unique_id", "vba_rccl_init", "vba_set_rccl_comm", "vba_shard_owner", "vba_set_shard",
     "vba_timing_enable", "vba_timing_calibration_read", "vba_timing_select", "vba_timing_sample_every", "vba_timing_launch_hessian", "vba_timing_null_span", "vba_timing_reset", "vba_timing_get",
@@ -1083,6 +1083,25 @@ class Context:
         pnt = _c(pnt_body); st = _c(state25).copy(); cov = _c(cov225).copy(); it = C.c_int(0)
         self._chk(self.lib.vba_odom_lio_state_estimation_kdtree(self.h, C.c_int(len(pnt)), _p(pnt), _p(st), _p(cov), C.byref(it)))
         return it.value, st, cov
+
+    def lio_state_estimation_kdtree_resident(self, n, d_pnt_body, state25, cov225):
+        """The same odometry on a DEVICE array of n points (its address as an integer), read in place, with the iterations, the map
+        append and the re-sampling resident on the device.  Returns (iterations, state, cov, report), report as
+        in lio_state_estimation_resident (nnt_eig_min is 0: this variant has no nnt)."""
+        st = _c(state25).copy(); cov = _c(cov225).copy(); it = C.c_int(0); rep = OdomReport()
+        self._chk(self.lib.vba_odom_lio_state_estimation_kdtree_resident(self.h, C.c_int(n), C.c_void_p(d_pnt_body), _p(st), _p(cov), C.byref(it),
+                                                                         C.byref(rep)))
+        report = dict(iterations=rep.iterations, match_num=np.array(rep.match_num[:], dtype=np.int64), rot_add=np.array(rep.rot_add[:]),
+                      tra_add=np.array(rep.tra_add[:]), nnt_eig_min=rep.nnt_eig_min)
+        return it.value, st, cov, report
+
+    def kdtree_reserve(self, max_map_points, max_scan_points):
+        self._chk(self.lib.vba_odom_kdtree_reserve(self.h, C.c_int(max_map_points), C.c_int(max_scan_points)))
+
+    def kdtree_allocations(self):
+        n = C.c_int(); b = C.c_int64()
+        self._chk(self.lib.vba_odom_kdtree_allocations(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
 
     def kdtree_size(self):
         return self.lib.vba_odom_kdtree_size(self.h)

@@ -179,6 +179,12 @@ __device__ __forceinline__ double wave_sum(double x) {
   return x;
 }
 
+// a double every lane loaded from the same address, made wave-uniform for the compiler too
+__device__ __forceinline__ double odom_uniform(double x) {
+  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(x)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(x));
+  return __hiloint2double(hi, lo);
+}
+
 // rank of a flagged thread among the flagged threads of its 256-thread workgroup (lane order) and the workgroup's count.  Every
 // thread of the workgroup must call it (it synchronises).
 __device__ __forceinline__ int det_wg_rank(bool f, int *wsum, int &tot) {

@@ -94,6 +94,12 @@ struct vba_ctx {
   BigStore big;                   // arbitrary-window path (top-level global BA)
   double *d_kdtree[2] = {nullptr, nullptr};   // pl_tree of the initialisation odometry (float-valued xyz), ping-pong for the re-sampling
   size_t kd_cap = 0; int kd_n = 0, kd_cur = 0;
+  // vba_odom_lio_state_estimation_kdtree_resident: scratch sized by the scan (planes, partials, candidates), scratch
+  // sized by map + scan (the re-sampler's count / first arrays and work area); the loop's state and pinned image are d_odom / h_odom
+  // below.  kd_allocs / kd_bytes count these and the map's two halves, cumulatively (a freed block is not subtracted).
+  char *d_kdscan = nullptr; size_t kdscan_pts = 0;
+  char *d_kdws = nullptr; size_t kdws_pts = 0, kdws_bytes = 0;
+  int kd_allocs = 0; int64_t kd_bytes = 0;
   double *d_refpts = nullptr;     // submap cloud staging (HBA_add_edge)
   size_t refpts_doubles = 0;
   double *d_lipack = nullptr; size_t lipack_doubles = 0;       // li_ba_device: results gathered for one D2H copy
@@ -118,7 +124,7 @@ struct vba_ctx {
   char *d_expout = nullptr; size_t expout_cap = 0;      // records
   std::vector<long long> exp_first; std::vector<int> exp_kbase;   // host scratch: exported points before every keyframe, keyframes before every store
   // vba_odom_lio_state_estimation_resident: the loop's device state, its pinned image (parameter block up, result
-  // block down) and the point loop's workgroup partials; grow-only
+  // block down; also those of the kd-tree variant, §18) and the point loop's workgroup partials; grow-only
   vbh::OdomEkf *d_odom = nullptr, *h_odom = nullptr;
   double *d_odom_part = nullptr; size_t odom_part_doubles = 0;
 
@@ -240,6 +246,8 @@ int map_odom_accumulate(MapStore &s, hipStream_t st, const OdomState &X, int n, 
                         double *d_partial, double *d_out34, double *out34, std::string &err);
 int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomEkf *h_img, int n, const double *d_pts,
                       const double *d_var, double *d_partial, std::string &err);
+// the update launch of the resident EKF loops (vba_kernels_odom.hpp), also the kd-tree variant's in voxelba.hip
+__global__ __launch_bounds__(256) void k_odom_update(vbh::OdomEkf *S, const double *__restrict__ partial, int nb, int iter, int kd);
 int map_fix_source_ensure(MapStore &s, hipStream_t st, size_t nodes, size_t fix, size_t n, std::string &err);
 int map_cut_voxel_fix_source(MapStore &s, hipStream_t st, int n, const FixSource &src, double jour, std::string &err);
 // fills the map's root table with the empty key, also the hash tables of vba_kernels_big.hpp in voxelba.hip

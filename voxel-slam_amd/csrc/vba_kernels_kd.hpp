@@ -4,8 +4,15 @@
 // odometry.  The map here holds at most a few 10^4 points (it is re-sampled on a 0.5 m grid after every scan), so the
 // exact 5-NN is a tiled brute-force scan: one thread per (scan point, map slice), the slice streamed through LDS 256 points at
 // a time, the five best kept sorted in registers, the slices merged by a second kernel — no tree, no traversal divergence.
+//
+// Every kernel is a thin wrapper over a __device__ body.  k_kd_match / fit / accum / append take the pose by value and are launched by
+// the host-driven loop (vba_odom_lio_state_estimation_kdtree); the k_kd_*_dev wrappers belong to the device-resident loop (DESIGN.md
+// §18): they read the pose from the loop's device state, and first of all its `done` flag (and, the search and the fit, its
+// `refind` flag), returning at once when there is nothing to do.  No atomics.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "vba_common.hpp"
+#include "vba_odom_ekf.hpp"
 
 namespace vba {
 
@@ -65,8 +72,8 @@ __device__ __forceinline__ void kd_lstsq_5x3(double A[5][3], double b[5], double
 // (gridDim.y slices: one thread per scan point alone leaves three quarters of the chip idle at 20k-point scans).  A candidate
 // is the 64-bit word (float distance bits << 32 | index): positive floats order like their bit patterns, so comparing the
 // words orders by distance and, at equal distance, by index — the order a sequential scan with strict `<` produces.
-__global__ __launch_bounds__(256) void k_kd_match(int n, const double *__restrict__ pts, KdPose X, int m, const double *__restrict__ tree,
-                                                  unsigned long long *__restrict__ cand /*[slices][n][5]*/) {
+__device__ __forceinline__ void kd_match_body(int n, const double *__restrict__ pts, const KdPose &X, int m, const double *__restrict__ tree,
+                                              unsigned long long *__restrict__ cand /*[slices][n][5]*/) {
   __shared__ float tx[256], ty[256], tz[256];
   const int i = blockIdx.x * 256 + threadIdx.x;
   float qx = 0, qy = 0, qz = 0;
@@ -109,10 +116,14 @@ __global__ __launch_bounds__(256) void k_kd_match(int n, const double *__restric
   o[3] = ((unsigned long long)__float_as_uint(bd3) << 32) | (unsigned int)bi3;
   o[4] = ((unsigned long long)__float_as_uint(bd4) << 32) | (unsigned int)bi4;
 }
+__global__ __launch_bounds__(256) void k_kd_match(int n, const double *__restrict__ pts, KdPose X, int m, const double *__restrict__ tree,
+                                                  unsigned long long *__restrict__ cand) {
+  kd_match_body(n, pts, X, m, tree, cand);
+}
 
 // stage 2: merge the slices' candidates, fit the plane (VS:1166-1190): (unit normal, distance) per scan point, distance < 0 = rejected
-__global__ __launch_bounds__(256) void k_kd_fit(int n, int slices, const unsigned long long *__restrict__ cand, const double *__restrict__ tree,
-                                                double *__restrict__ planes /*[n][4]*/) {
+__device__ __forceinline__ void kd_fit_body(int n, int slices, const unsigned long long *__restrict__ cand, const double *__restrict__ tree,
+                                            double *__restrict__ planes /*[n][4]*/) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   unsigned long long b0 = ~0ull, b1 = ~0ull, b2 = ~0ull, b3 = ~0ull, b4 = ~0ull;
@@ -149,9 +160,15 @@ __global__ __launch_bounds__(256) void k_kd_fit(int n, int slices, const unsigne
   const double d = 1.0 / sqrt(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
   o[0] = dir[0] * d; o[1] = dir[1] * d; o[2] = dir[2] * d; o[3] = d;
 }
+__global__ __launch_bounds__(256) void k_kd_fit(int n, int slices, const unsigned long long *__restrict__ cand, const double *__restrict__ tree,
+                                                double *__restrict__ planes) {
+  kd_fit_body(n, slices, cand, tree, planes);
+}
 
-// HTH (21 unique), HTz (6), valid count: per-block partials [nb][28]  (VS:1198-1209)
-__global__ __launch_bounds__(256) void k_kd_accum(int n, const double *__restrict__ pts, KdPose X, const double *__restrict__ planes, double *__restrict__ part) {
+// HTH (21 unique), HTz (6), valid count: per-block partials [nb][28]  (VS:1198-1209).  NCOL == 34: the same 28 sums as rows of the
+// 34-column layout that k_odom_update reduces (vba_odom_ekf.hpp): HTH 0-20, HTz 21-26, zeros 27-32 (no nnt here), valid 33.
+template <int NCOL>
+__device__ __forceinline__ void kd_accum_body(int n, const double *__restrict__ pts, const KdPose &X, const double *__restrict__ planes, double *__restrict__ part) {
   __shared__ double red[4][28];
   const int i = blockIdx.x * 256 + threadIdx.x;
   double s[28];
@@ -182,17 +199,57 @@ __global__ __launch_bounds__(256) void k_kd_accum(int n, const double *__restric
 #pragma unroll
     for (int k = 0; k < 28; k++) red[threadIdx.x >> 6][k] = s[k];
   __syncthreads();
-  if (threadIdx.x < 28) part[(size_t)blockIdx.x * 28 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  if (NCOL == 28) {
+    if (threadIdx.x < 28) part[(size_t)blockIdx.x * 28 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  } else if (threadIdx.x < 34) {
+    const int k = threadIdx.x < 27 ? threadIdx.x : 27;
+    const double v = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+    part[(size_t)blockIdx.x * 34 + threadIdx.x] = (threadIdx.x >= 27 && threadIdx.x < 33) ? 0.0 : v;
+  }
+}
+__global__ __launch_bounds__(256) void k_kd_accum(int n, const double *__restrict__ pts, KdPose X, const double *__restrict__ planes, double *__restrict__ part) {
+  kd_accum_body<28>(n, pts, X, planes, part);
 }
 
 // world points of the scan appended to the map, as PCL floats (VS:1107-1114, 1238-1246)
-__global__ void k_kd_append(int n, const double *__restrict__ pts, KdPose X, double *__restrict__ tree_out) {
+__device__ __forceinline__ void kd_append_body(int n, const double *__restrict__ pts, const KdPose &X, double *__restrict__ tree_out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const double x = pts[3 * (size_t)i], y = pts[3 * (size_t)i + 1], z = pts[3 * (size_t)i + 2];
   tree_out[3 * (size_t)i] = (double)(float)(X.R[0] * x + X.R[1] * y + X.R[2] * z + X.t[0]);
   tree_out[3 * (size_t)i + 1] = (double)(float)(X.R[3] * x + X.R[4] * y + X.R[5] * z + X.t[1]);
   tree_out[3 * (size_t)i + 2] = (double)(float)(X.R[6] * x + X.R[7] * y + X.R[8] * z + X.t[2]);
+}
+__global__ void k_kd_append(int n, const double *__restrict__ pts, KdPose X, double *__restrict__ tree_out) { kd_append_body(n, pts, X, tree_out); }
+
+// ---------------------------------------------------------------- the device-resident loop's wrappers
+// the pose of x_curr as the last update launch left it in the loop's state, wave-uniform
+__device__ __forceinline__ KdPose kd_pose_of(const vbh::OdomEkf *__restrict__ S) {
+  KdPose X;
+#pragma unroll
+  for (int k = 0; k < 9; k++) X.R[k] = odom_uniform(S->R[k]);
+#pragma unroll
+  for (int k = 0; k < 3; k++) X.t[k] = odom_uniform(S->t[k]);
+  return X;
+}
+__global__ __launch_bounds__(256) void k_kd_match_dev(const vbh::OdomEkf *__restrict__ S, int n, const double *__restrict__ pts, int m,
+                                                      const double *__restrict__ tree, unsigned long long *__restrict__ cand) {
+  if (__builtin_amdgcn_readfirstlane(S->done) || !__builtin_amdgcn_readfirstlane(S->refind)) return;
+  kd_match_body(n, pts, kd_pose_of(S), m, tree, cand);
+}
+__global__ __launch_bounds__(256) void k_kd_fit_dev(const vbh::OdomEkf *__restrict__ S, int n, int slices, const unsigned long long *__restrict__ cand,
+                                                    const double *__restrict__ tree, double *__restrict__ planes) {
+  if (__builtin_amdgcn_readfirstlane(S->done) || !__builtin_amdgcn_readfirstlane(S->refind)) return;
+  kd_fit_body(n, slices, cand, tree, planes);
+}
+__global__ __launch_bounds__(256) void k_kd_accum_dev(const vbh::OdomEkf *__restrict__ S, int n, const double *__restrict__ pts,
+                                                      const double *__restrict__ planes, double *__restrict__ part /*[nb][34]*/) {
+  if (__builtin_amdgcn_readfirstlane(S->done)) return;
+  kd_accum_body<34>(n, pts, kd_pose_of(S), planes, part);
+}
+// after the loop: x_curr is final whether or not `done` is set
+__global__ void k_kd_append_dev(const vbh::OdomEkf *__restrict__ S, int n, const double *__restrict__ pts, double *__restrict__ tree_out) {
+  kd_append_body(n, pts, kd_pose_of(S), tree_out);
 }
 
 }  // namespace vba

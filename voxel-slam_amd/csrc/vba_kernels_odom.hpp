@@ -12,12 +12,6 @@ namespace vba {
 
 typedef __attribute__((address_space(3))) double odom_lds_f64;
 
-// a double every lane loaded from the same address, made wave-uniform for the compiler too
-__device__ __forceinline__ double odom_uniform(double x) {
-  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(x)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(x));
-  return __hiloint2double(hi, lo);
-}
-
 __global__ __launch_bounds__(256) void k_odom_match_dev(MapView m, MapParams P, const vbh::OdomEkf *__restrict__ S, int n,
                                                         const double *__restrict__ pts, const double *__restrict__ var,
                                                         double *__restrict__ partial) {
@@ -36,7 +30,8 @@ struct OdomWgSync { __device__ __forceinline__ void operator()() const { __synct
 // t + 476, ... of the flat array (rows t / 34, t / 34 + 7, ... of its column: consecutive lanes read consecutive doubles) in that
 // order, then lane c adds the seven group sums in group order.  The order depends on nb alone.
 static constexpr int ODOM_RED_LANES = 7 * 34;
-__global__ __launch_bounds__(256) void k_odom_update(vbh::OdomEkf *S, const double *__restrict__ partial, int nb, int iter) {
+// kd: the stop rule of the kd-tree variant (vba_odom_ekf.hpp), whose loop in voxelba.hip launches this kernel too.
+__global__ __launch_bounds__(256) void k_odom_update(vbh::OdomEkf *S, const double *__restrict__ partial, int nb, int iter, int kd) {
 #pragma clang fp contract(off)
   __shared__ double wsm[vbh::OE_WORK];
   __shared__ double red[ODOM_RED_LANES];
@@ -57,7 +52,7 @@ __global__ __launch_bounds__(256) void k_odom_update(vbh::OdomEkf *S, const doub
     w[vbh::OE_S34 + t] = s;
   }
   __syncthreads();
-  vbh::odom_ekf_iterate(w, S, iter, t, 256, OdomWgSync());
+  vbh::odom_ekf_iterate(w, S, iter, t, 256, OdomWgSync(), kd);
 }
 
 // The whole call on the stream: one upload of the image, (match, update) x 4, one download of the result block, one wait.  h_img
@@ -70,7 +65,7 @@ int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomE
   const MapParams P = map_params(s);
   for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
     if (match) hipLaunchKernelGGL(k_odom_match_dev, dim3(nb), dim3(256), 0, st, s.v, P, (const vbh::OdomEkf *)d_S, n, d_pts, d_var, d_partial);
-    hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, st, d_S, (const double *)d_partial, nb, iter);
+    hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, st, d_S, (const double *)d_partial, nb, iter, 0);
   }
   MAPCHK(hipGetLastError());
   const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);

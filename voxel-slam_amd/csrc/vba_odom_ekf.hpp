@@ -40,9 +40,12 @@ struct OdomEkf {
   int iterations;               // iterations run so far
   int rematch_num;
   int done;                     // the stop rule has fired: later launches return at once
-  int pad_;
+  int n_map;                    // kd mode: points of the re-sampled map, written by the down-sampler's scan after the loop
   // ---- what the next point loop reads: pose of x_curr, rotation and translation blocks of P
   double R[9], t[3], rot_var[9], tsl_var[9];
+  // ---- kd mode only (lio_state_estimation_kdtree, VS:1159, VS:1216-1227): whether the next iteration searches its neighbours again
+  // (the caller sets it to 1 after odom_ekf_begin), whether an iteration has converged yet
+  int refind, converged_once;
 };
 static const int ODOM_EKF_MAX_ITER = 4;
 
@@ -138,8 +141,12 @@ VBH_HD inline void odom_ekf_solve(WP w, const double *cov_inv, const State &x_pr
 
 // One whole iteration `iter` on the sums in w[OE_S34..]: the step, the trace row, the stop rule, on a stop the covariance, and the
 // pose and covariance blocks of the next point loop.  The caller has already found S->done clear.
+// kd != 0 is the stop rule of lio_state_estimation_kdtree (VS:1216-1233) on the same step: only a converged iteration counts as a
+// rematch, the refind that iteration MAX - 2 forces when none has converged does not (VS:1224-1227), and S->refind tells the next
+// iteration's neighbour search whether to run.  The stop iteration is the same expression in both modes.  (In kd mode the caller has
+// divided cov_inv by 1000, VS:1213, and columns 27-32 of the sums are zero: there is no nnt.)
 template <class WP, class Sync>
-VBH_HD inline void odom_ekf_iterate(WP w, OdomEkf *S, int iter, int lane, int nl, Sync sync) {
+VBH_HD inline void odom_ekf_iterate(WP w, OdomEkf *S, int iter, int lane, int nl, Sync sync, int kd = 0) {
   VBE_NO_CONTRACT
   odom_ekf_solve(w, S->cov_inv, S->x_prop, S->x_curr, lane, nl, sync);
   if (lane == 0) {
@@ -159,7 +166,10 @@ VBH_HD inline void odom_ekf_iterate(WP w, OdomEkf *S, int iter, int lane, int nl
     S->iterations = iter + 1;
     const bool converged = (rot_add * 57.3 < 0.01) && (tra_add * 100 < 0.015);     // VS:1072
     int rematch = S->rematch_num;
-    if (converged || (rematch == 0 && iter == ODOM_EKF_MAX_ITER - 2)) rematch++;   // VS:1076-1079
+    if (kd) {
+      if (converged) { rematch++; S->converged_once = 1; }                         // VS:1218-1223
+      S->refind = (converged || (iter == ODOM_EKF_MAX_ITER - 2 && !S->converged_once)) ? 1 : 0;
+    } else if (converged || (rematch == 0 && iter == ODOM_EKF_MAX_ITER - 2)) rematch++;   // VS:1076-1079
     S->rematch_num = rematch;
     const bool stop = rematch >= 2 || iter == ODOM_EKF_MAX_ITER - 1;               // VS:1082
     if (stop) S->done = 1;

@@ -610,6 +610,8 @@ void vba_destroy(vba_ctx *c) {
   if (c->d_lipack) hipFree(c->d_lipack);
   if (c->d_liscr) hipFree(c->d_liscr);
   for (int i = 0; i < 2; i++) if (c->d_kdtree[i]) hipFree(c->d_kdtree[i]);
+  if (c->d_kdscan) hipFree(c->d_kdscan);
+  if (c->d_kdws) hipFree(c->d_kdws);
   if (c->d_refpts) hipFree(c->d_refpts);
   if (c->d_li) hipFree(c->d_li);
   if (c->d_k4part) hipFree(c->d_k4part);
@@ -1190,8 +1192,11 @@ static int kd_reserve(vba_ctx *c, size_t pts) {
     c->d_kdtree[i] = nw;
   }
   c->kd_cap = cap;
+  c->kd_allocs += 2; c->kd_bytes += (int64_t)(2 * cap * 3 * sizeof(double));
   return VBA_OK;
 }
+// map slices of the 5-NN search for nb workgroups of scan points: enough workgroups to cover the chip
+static int kd_slices_of(int nb) { return nb >= 512 ? 1 : (nb >= 128 ? 4 : 8); }
 int vba_odom_kdtree_reset(vba_ctx *c) { c->kd_n = 0; return VBA_OK; }
 int vba_odom_kdtree_size(vba_ctx *c) { return c->kd_n; }
 int vba_odom_kdtree_points(vba_ctx *c, double *out) {
@@ -1207,7 +1212,7 @@ int vba_odom_lio_state_estimation_kdtree(vba_ctx *c, int n, const double *pnt_bo
   if (n < 0 || (n > 0 && !pnt_body) || !state || !cov) return VBA_ERR_BAD_ARG;
   if (iterations) *iterations = 0;
   const int DIM = VBA_DIM, nb = (n + 255) / 256;
-  const int kd_slices = nb >= 512 ? 1 : (nb >= 128 ? 4 : 8);               // enough workgroups to cover the chip
+  const int kd_slices = kd_slices_of(nb);
   int st = ensure_stage(c, ((size_t)n * 7 + (size_t)nb * 28 + (size_t)kd_slices * n * 5 + 64) * sizeof(double));
   if (st) return st;
   double *d_pts = (double *)c->d_stage, *d_pl = d_pts + (size_t)n * 3, *d_part = d_pl + (size_t)n * 4;
@@ -1302,6 +1307,144 @@ int vba_odom_lio_state_estimation_kdtree(vba_ctx *c, int n, const double *pnt_bo
   std::memcpy(state, &x_curr, sizeof(x_curr));
   std::memcpy(cov, P.data(), 225 * sizeof(double));
   if (iterations) *iterations = iters;
+  return VBA_OK;
+}
+
+// ---------------------------------------------------------------- the same odometry resident on the device
+// device state and pinned image of the resident EKF loops (this one and vba_odom_lio_state_estimation_resident)
+static int odom_image_ensure(vba_ctx *c) {
+  if (c->d_odom) return VBA_OK;
+  HIPCHK(c, hipMalloc((void **)&c->d_odom, sizeof(vbh::OdomEkf)));
+  HIPCHK(c, hipHostMalloc((void **)&c->h_odom, sizeof(vbh::OdomEkf), hipHostMallocDefault));
+  c->kd_allocs += 2; c->kd_bytes += (int64_t)(2 * sizeof(vbh::OdomEkf));
+  return VBA_OK;
+}
+static size_t kd_up(size_t b) { return (b + 255) & ~(size_t)255; }
+// scratch sized by a scan of up to p points: planes [p][4] | partials [ceil(p / 256)][34] | candidates at the slice count that
+// needs the most of them among the scans of up to p points
+struct KdScanLayout { size_t o_part, o_cand, bytes; };
+static KdScanLayout kd_scan_layout(size_t p) {
+  const size_t a = 8 * std::min<size_t>(p, 127 * 256), b = 4 * std::min<size_t>(p, 511 * 256);
+  KdScanLayout L;
+  L.o_part = kd_up(p * 4 * sizeof(double));
+  L.o_cand = L.o_part + kd_up(((p + 255) / 256) * 34 * sizeof(double));
+  L.bytes = L.o_cand + kd_up(std::max(std::max(a, b), p) * 5 * sizeof(unsigned long long));
+  return L;
+}
+static int kd_scan_ensure(vba_ctx *c, size_t pts) {
+  if (pts <= c->kdscan_pts) return VBA_OK;
+  size_t cap = c->kdscan_pts ? c->kdscan_pts : 16384;
+  while (cap < pts) cap *= 2;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->d_kdscan) hipFree(c->d_kdscan);
+  c->d_kdscan = nullptr; c->kdscan_pts = 0;
+  const size_t b = kd_scan_layout(cap).bytes;
+  HIPCHK(c, hipMalloc((void **)&c->d_kdscan, b));
+  c->kdscan_pts = cap; c->kd_allocs++; c->kd_bytes += (int64_t)b;
+  return VBA_OK;
+}
+// scratch sized by map + scan of up to p points: the re-sampler's count [p] | first [p] | work area (the deterministic layout, the larger)
+static int kd_ws_ensure(vba_ctx *c, size_t pts) {
+  if (pts <= c->kdws_pts) return VBA_OK;
+  if (pts > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
+  size_t cap = c->kdws_pts ? c->kdws_pts : 65536;
+  while (cap < pts) cap *= 2;
+  int st = VBA_OK;
+  const size_t ws = kf_ws_layout(c, (int)cap, true, nullptr, nullptr, &st);
+  if (st) return st;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->d_kdws) hipFree(c->d_kdws);
+  c->d_kdws = nullptr; c->kdws_pts = 0; c->kdws_bytes = 0;
+  const size_t b = 2 * kd_up(cap * sizeof(int)) + ws;
+  HIPCHK(c, hipMalloc((void **)&c->d_kdws, b));
+  c->kdws_pts = cap; c->kdws_bytes = b; c->kd_allocs++; c->kd_bytes += (int64_t)b;
+  return VBA_OK;
+}
+
+int vba_odom_kdtree_reserve(vba_ctx *c, int max_map_points, int max_scan_points) {
+  if (!c || max_map_points < 0 || max_scan_points < 0 || max_map_points > (1 << 28) || max_scan_points > (1 << 28)) return VBA_ERR_BAD_ARG;
+  int st = odom_image_ensure(c);
+  if (st || (st = kd_reserve(c, (size_t)max_map_points + 16)) || (st = kd_scan_ensure(c, (size_t)max_scan_points)) ||
+      (st = kd_ws_ensure(c, (size_t)max_map_points)))
+    return st;
+  return VBA_OK;
+}
+int vba_odom_kdtree_allocations(vba_ctx *c, int *n_allocs, int64_t *bytes) {
+  if (!c || !n_allocs || !bytes) return VBA_ERR_BAD_ARG;
+  *n_allocs = c->kd_allocs; *bytes = c->kd_bytes;
+  return VBA_OK;
+}
+
+int vba_odom_lio_state_estimation_kdtree_resident(vba_ctx *c, int n, const double *d_pnt_body, double *state, double *cov, int *iterations,
+                                                  vba_odom_report *report) {
+  if (!c || n < 0 || (n > 0 && !d_pnt_body) || !state || !cov) return VBA_ERR_BAD_ARG;
+  if (iterations) *iterations = 0;
+  if (report) std::memset(report, 0, sizeof(*report));
+  const int nb = (n + 255) / 256, kd_slices = kd_slices_of(nb);
+  const size_t tot = (size_t)c->kd_n + (size_t)n;
+  if (tot > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
+  int st = kd_reserve(c, tot + 16);
+  if (st) return st;
+  if (c->kd_n < 100) {                                                       // VS:1105-1118: the map is only seeded; stream-ordered
+    if (n > 0) {
+      KdPose X;
+      std::memcpy(X.R, state + 1, sizeof(X.R)); std::memcpy(X.t, state + 10, sizeof(X.t));
+      hipLaunchKernelGGL(k_kd_append, dim3(nb), dim3(256), 0, c->stream, n, d_pnt_body, X, c->d_kdtree[c->kd_cur] + (size_t)c->kd_n * 3);
+      HIPCHK(c, hipGetLastError());
+    }
+    c->kd_n += n;
+    return VBA_OK;
+  }
+  if ((st = odom_image_ensure(c)) || (st = kd_scan_ensure(c, (size_t)n)) || (st = kd_ws_ensure(c, tot))) return st;
+  const bool det = c->opt.deterministic != 0;
+  int *d_cnt = (int *)c->d_kdws, *d_first = (int *)(c->d_kdws + kd_up(c->kdws_pts * sizeof(int)));
+  char *ws = c->d_kdws + 2 * kd_up(c->kdws_pts * sizeof(int));
+  DsWork w{};
+  if (2 * kd_up(c->kdws_pts * sizeof(int)) + kf_ws_layout(c, (int)tot, det, ws, &w, &st) > c->kdws_bytes || st) return st ? st : VBA_ERR_CAPACITY;
+  const KdScanLayout L = kd_scan_layout(c->kdscan_pts);
+  double *d_pl = (double *)c->d_kdscan, *d_part = (double *)(c->d_kdscan + L.o_part);
+  unsigned long long *d_cand = (unsigned long long *)(c->d_kdscan + L.o_cand);
+  // the image: cov_inv = P^-1 / 1000 entry by entry (VS:1134, VS:1213), the first iteration searches
+  double cov_inv[225];
+  vbh::inverse_pplu(cov, cov_inv, VBA_DIM);
+  for (int k = 0; k < 225; k++) cov_inv[k] = cov_inv[k] / 1000;
+  vbh::OdomEkf &S = *c->h_odom;
+  vbh::odom_ekf_begin(S, state, cov, cov_inv);
+  S.refind = 1;
+  vbh::OdomEkf *d_S = c->d_odom;
+  hipStream_t s = c->stream;
+  double *tree = c->d_kdtree[c->kd_cur], *tree_out = c->d_kdtree[c->kd_cur ^ 1];
+  HIPCHK(c, hipMemcpyAsync(d_S, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
+  for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
+    if (n > 0) {
+      hipLaunchKernelGGL(k_kd_match_dev, dim3(nb, kd_slices), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pnt_body, c->kd_n, (const double *)tree, d_cand);
+      hipLaunchKernelGGL(k_kd_fit_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, kd_slices, (const unsigned long long *)d_cand, (const double *)tree, d_pl);
+      hipLaunchKernelGGL(k_kd_accum_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pnt_body, (const double *)d_pl, d_part);
+    }
+    // n == 0: nb == 0 and d_part may be NULL (no scan scratch was ever needed); the reduction reads nb * 34 doubles, that is none
+    hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, s, d_S, (const double *)d_part, nb, iter, 1);
+  }
+  // map update VS:1238-1250: the scan appended in the refined pose, map + scan re-sampled on a 0.5 m grid into the other half; the
+  // voxel count lands in the result block
+  if (n > 0) hipLaunchKernelGGL(k_kd_append_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pnt_body, tree + (size_t)c->kd_n * 3);
+  w.n_out = &d_S->n_map;
+  if ((st = ds_core(c, s, 0, (int)tot, tree, nullptr, 9, 4, 0.5, det, w))) return st;
+  hipLaunchKernelGGL(k_ds_emit, dim3(((int)tot + 255) / 256), dim3(256), 0, s, (int)tot, (const DsSlot *)w.tab, (const int *)w.slot, (const int *)w.blk, tree_out, d_cnt,
+                     d_first, (double *)nullptr, 0);
+  HIPCHK(c, hipGetLastError());
+  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
+  HIPCHK(c, hipMemcpyAsync((char *)&S + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (S.n_map < 1 || (size_t)S.n_map > tot) { c->set_error("kd-tree odometry: voxel count of the re-sampled map out of range"); return VBA_ERR_HIP; }
+  c->kd_cur ^= 1; c->kd_n = S.n_map;
+  std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
+  std::memcpy(cov, S.P_out, sizeof(S.P_out));
+  if (iterations) *iterations = S.iterations;
+  if (report) {
+    report->iterations = S.iterations;
+    for (int k = 0; k < 4; k++) { report->match_num[k] = S.match_num[k]; report->rot_add[k] = S.rot_add[k]; report->tra_add[k] = S.tra_add[k]; }
+    report->nnt_eig_min = 0.0;
+  }
   return VBA_OK;
 }
 
@@ -2233,9 +2376,9 @@ int vba_odom_lio_state_estimation_resident(vba_ctx *c, int n, const double *d_pn
                                            int *ok, vba_odom_report *report) {
   if (n < 0 || (n > 0 && (!d_pnt_body || !d_var_body)) || !state || !cov) return VBA_ERR_BAD_ARG;
   if (c->n_ranks > 1) { c->set_error("the resident odometry loop has no all-reduce step between its iterations: unsharded contexts only"); return VBA_ERR_UNSUPPORTED; }
-  if (!c->d_odom) {
-    HIPCHK(c, hipMalloc((void **)&c->d_odom, sizeof(vbh::OdomEkf)));
-    HIPCHK(c, hipHostMalloc((void **)&c->h_odom, sizeof(vbh::OdomEkf), hipHostMallocDefault));
+  {
+    const int st = odom_image_ensure(c);
+    if (st) return st;
   }
   const size_t need = (size_t)((n + 255) / 256) * 34;
   if (need > c->odom_part_doubles) {
