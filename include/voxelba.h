@@ -241,14 +241,17 @@ int vba_map_dump_plane_var(vba_ctx *ctx, double *out, int max_leaves);
  * with match() (VM:2167-2205) / OctoTree::match (VM:1649-1721).  pnt_body [n][3] and var_body [n][9] are the scan's
  * body-frame points and covariances (pointVar as produced by var_init, VH:210-234); state [25] and cov [225] = x_curr
  * (IMUST incl. its 15x15 covariance) in/out; *ok receives the bool result (false = degenerate, VS:1090-1097).
- * The per-point loop runs on the device, the 15x15 EKF algebra on the host. */
+ * pnt_body / var_body may be host or device arrays.  The call is a staging front end of vba_odom_lio_state_estimation_resident
+ * below: it copies the scan into the context's staging buffer (device to device when handed device arrays), runs that call's loop on
+ * the copy and returns its bits; the call has completed when it returns.  n == 0 or a map that was never allocated: state and cov
+ * come back bit-identical, *ok = 0.  Unlike the call below it accepts a sharded context and runs on the local map. */
 int vba_odom_lio_state_estimation(vba_ctx *ctx, int n, const double *pnt_body, const double *var_body, double *state,
                                   double *cov, int *ok);
 
 /* The same update with its 2-4 iterations resident on the device: no host round trip between them.
  * d_pnt_body [n][3] and d_var_body [n][9] are DEVICE arrays (what vba_scan_prepare hands out), read in place and never copied;
  * state [25] and cov [225] are host arrays, in/out, in the layout of vba_odom_lio_state_estimation; *ok (may be NULL) as there.
- * Call shape: cov^-1 is computed on the host (the bits of the call above); ONE host-to-device copy of one parameter block; for each
+ * Call shape: cov^-1 is computed on the host; ONE host-to-device copy of one parameter block; for each
  * of the four possible iterations a point-loop launch and an update launch (one workgroup: fixed-order sum of the workgroup
  * partials, the 15x15 EKF step, the stop rule rematch_num >= 2 || iter == 3 of VS:1073-1086, and at the stop cov <- (I - G) cov);
  * after the stop the remaining launches find a flag in device memory and return at once; ONE device-to-host copy of one result
@@ -271,7 +274,12 @@ int vba_odom_lio_state_estimation_resident(vba_ctx *ctx, int n, const double *d_
 /* void VOXEL_SLAM::lio_state_estimation_kdtree(PVecPtr pptr) (VS:1102-1252), the odometry used while the system initialises:
  * scan points against a point-cloud map (pl_tree, kept by the context) through an exact 5-nearest-neighbour plane fit.
  * While the map holds fewer than 100 points the scan only seeds it (VS:1105-1118, *iterations = 0); otherwise state / cov
- * are updated in place, the scan is appended in the refined pose and the map re-sampled on a 0.5 m grid (VS:1238-1250). */
+ * are updated in place, the scan is appended in the refined pose and the map re-sampled on a 0.5 m grid (VS:1238-1250).
+ * pnt_body may be a host or a device array.  The call is a staging front end of vba_odom_lio_state_estimation_kdtree_resident
+ * below: it copies the points into the context's staging buffer, runs that call on the copy and returns its bits (state, cov,
+ * iterations, map); unlike that call it has completed when it returns, after a seeding call too.  It shares that call's scratch,
+ * allocated on first use and counted by vba_odom_kdtree_allocations, and its limit: VBA_ERR_CAPACITY when map + scan exceed 2^28
+ * points. */
 int vba_odom_lio_state_estimation_kdtree(vba_ctx *ctx, int n, const double *pnt_body, double *state, double *cov,
                                          int *iterations);
 int vba_odom_kdtree_reset(vba_ctx *ctx);   /* pl_tree->clear() */
@@ -286,7 +294,7 @@ int vba_odom_kdtree_points(vba_ctx *ctx, double *xyz_out /* [size][3] */);
  * Call shape, map below 100 points (seeding, VS:1105-1118): ONE append launch with the pose passed by value; *iterations = 0, state
  * and cov untouched; no copy and no wait - the call is stream-ordered (vba_odom_kdtree_points and every later call follow it on the
  * context's stream).
- * Call shape, estimation: cov^-1 / 1000 is computed on the host (the bits of the call above); ONE host-to-device copy of one parameter
+ * Call shape, estimation: cov^-1 / 1000 is computed on the host; ONE host-to-device copy of one parameter
  * block; for each of the four possible iterations four launches - 5-NN candidates per map slice, slice merge + plane fit, the 28 sums
  * per workgroup, and the one-workgroup update of vba_odom_lio_state_estimation_resident under the kd stop rule (only a converged
  * iteration counts as a rematch; refind = converged || (iter == 2 && none converged yet)), 16 launches in all; one append launch
@@ -309,7 +317,8 @@ int vba_odom_kdtree_points(vba_ctx *ctx, double *xyz_out /* [size][3] */);
  * counter that does not move means that nothing was allocated.  The map's halves are counted whichever of the two kd-tree calls grew
  * them; the loop state and its pinned block are shared with vba_odom_lio_state_estimation_resident and counted here whichever call
  * allocated them first.
- * VBA_ERR_BAD_ARG: NULL state / cov, n < 0, n > 0 with a NULL array, a negative reservation. */
+ * VBA_ERR_BAD_ARG: NULL state / cov, n < 0, n > 0 with a NULL array, a negative reservation.  VBA_ERR_CAPACITY: map + scan exceed
+ * 2^28 points. */
 int vba_odom_lio_state_estimation_kdtree_resident(vba_ctx *ctx, int n, const double *d_pnt_body, double *state, double *cov,
                                                   int *iterations, vba_odom_report *report /* may be NULL */);
 int vba_odom_kdtree_reserve(vba_ctx *ctx, int max_map_points, int max_scan_points);

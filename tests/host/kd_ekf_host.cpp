@@ -6,7 +6,7 @@
 
 namespace {
 struct NoSync { void operator()() const {} };
-// the 28 sums of k_kd_accum in the 34-column layout: HTH 0-20, HTz 21-26, zeros 27-32, valid 33
+// the 28 sums of k_kd_accum_dev in the 34-column layout: HTH 0-20, HTz 21-26, zeros 27-32, valid 33
 void widen(const double *s28, double *s34) {
   for (int k = 0; k < 27; k++) s34[k] = s28[k];
   for (int k = 27; k < 33; k++) s34[k] = 0.0;

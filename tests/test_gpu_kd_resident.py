@@ -3,7 +3,8 @@ CPU oracle of VOXEL_SLAM::lio_state_estimation_kdtree (voxelslam.cpp:1102-1252) 
 pointer in a second context.  The scene, the predictions (rng seed 17) and the bars are those of
 test_gpu_odom.test_lio_state_estimation_kdtree_parity: state 1e-5, covariance 1e-4 of its largest entry, map size within
 max(2, len / 500) and 1e-4 on the points when the sizes agree.  match_num is printed, not compared: a point on the 0.1 gate may fall
-either way."""
+either way.  The existing call is a staging front end of the same loop: in deterministic contexts it returns the resident call's bits
+(without the mode the re-sampler's atomic insert promises no bits for the map, and the bars are the only assertion)."""
 import ctypes as C
 import dataclasses
 
@@ -264,6 +265,57 @@ def test_repeatable_and_read_only(env):
     assert all(d.unchanged() for d in env["keep"][first:])
 
 
+def _assert_same_bits(tag, a, b, ca, cb):
+    """(iterations, state, cov) of two calls and the maps of their contexts, bit for bit."""
+    assert a[0] == b[0], tag
+    np.testing.assert_array_equal(a[1], b[1], err_msg=tag); np.testing.assert_array_equal(a[2], b[2], err_msg=tag)
+    assert ca.kdtree_size() == cb.kdtree_size(), tag
+    np.testing.assert_array_equal(ca.kdtree_points(), cb.kdtree_points(), err_msg=tag)
+
+
+def test_existing_call_on_host_arrays_gives_the_same_bits(env):
+    """The existing call is a staging front end of the resident loop: over the sequence of case 2 (a seed, then an empty scan after
+    every estimation) in two deterministic contexts, the existing call on host arrays and the resident call on device pointers return
+    the same iterations, state, covariance, map size and map points after every call."""
+    ch, cd = _ctx(env, deterministic=1), _ctx(env, deterministic=1)
+    cov_h, cov_d = _cov0(), _cov0()
+    iters = []
+    for k, (p, state) in enumerate(_every20(env)):
+        dev = _dev(env, p)
+        h = ch.lio_state_estimation_kdtree(p, state, cov_h)
+        d = cd.lio_state_estimation_kdtree_resident(*dev.args, state, cov_d)[:3]
+        _assert_same_bits("scan %d" % k, h, d, ch, cd)
+        iters.append(h[0])
+        if h[0]:
+            cov_h, cov_d = h[2], d[2]
+            h0 = ch.lio_state_estimation_kdtree(np.zeros((0, 3)), h[1], cov_h)
+            d0 = cd.lio_state_estimation_kdtree_resident(0, 0, d[1], cov_d)[:3]
+            _assert_same_bits("empty scan after %d" % k, h0, d0, ch, cd)
+            iters.append(h0[0])
+    assert iters[0] == 0 and len(iters) == 9 and all(i >= 2 for i in iters[1:])     # the first scan seeded, every other call estimated
+
+
+def test_existing_call_keeps_its_stage_in_stream_order(env):
+    """The existing call stages the scan in the context's staging buffer.  Other calls that stage there (a down-sampling, whose voxel
+    table lands on the staged points, and a cut_voxel) between two existing calls change nothing: every result equals that of a
+    context that made the kd calls alone."""
+    ca, cb = _ctx(env, deterministic=1), _ctx(env, deterministic=1)
+    scans = _every20(env)[:3]
+    small = env["pts"][3][::100]
+    pose = np.concatenate([np.eye(3).ravel(), np.zeros(3)])
+    cov_a, cov_b = _cov0(), _cov0()
+    for k, (p, state) in enumerate(scans):
+        a = ca.lio_state_estimation_kdtree(p, state, cov_a)
+        b = cb.lio_state_estimation_kdtree(p, state, cov_b)
+        _assert_same_bits("scan %d" % k, a, b, ca, cb)
+        assert a[0] == 0 if k == 0 else a[0] >= 2
+        if a[0]:
+            cov_a, cov_b = a[2], b[2]
+        out, _, _ = ca.down_sampling_voxel(small, 0.5)
+        assert 0 < len(out) <= len(small)
+        ca.cut_voxel(0, small, pose)
+
+
 def test_reservation(env):
     """Case 6: after the reservation the sequence of case 2 allocates nothing; a scan past it does, and is still right."""
     cn, ce = _ctx(env), _ctx(env)
@@ -295,6 +347,11 @@ def test_errors(env):
     assert f(ctx.h, C.c_int(64), None, capi._p(state), capi._p(cov), C.byref(it), None) == capi.ERR_BAD_ARG
     assert ctx.kdtree_size() == 0
     assert f(ctx.h, C.c_int(64), C.c_void_p(dev.args[1]), capi._p(state), capi._p(cov), None, None) == capi.OK      # iterations may be NULL
+    assert ctx.kdtree_size() == 64
+    g = ctx.lib.vba_odom_lio_state_estimation_kdtree
+    big = C.c_int((1 << 28) - 63)                     # map + scan past 2^28 points: refused by both calls before anything is read
+    assert f(ctx.h, big, C.c_void_p(dev.args[1]), capi._p(state), capi._p(cov), C.byref(it), None) == capi.ERR_CAPACITY
+    assert g(ctx.h, big, C.c_void_p(dev.args[1]), capi._p(state), capi._p(cov), C.byref(it)) == capi.ERR_CAPACITY
     assert ctx.kdtree_size() == 64
     assert ctx.lib.vba_odom_kdtree_reserve(ctx.h, C.c_int(-1), C.c_int(0)) == capi.ERR_BAD_ARG
     assert ctx.lib.vba_odom_kdtree_allocations(ctx.h, None, None) == capi.ERR_BAD_ARG

@@ -1,5 +1,7 @@
 """GPU tests of the device-resident scan-to-map EKF update (vba_odom_lio_state_estimation_resident) against the
 CPU oracle of VOXEL_SLAM::lio_state_estimation (voxelslam.cpp:962-1098) and against the existing call on the same device pointers.
+The existing call (vba_odom_lio_state_estimation) is a staging front end of the same loop: besides the bars, its ok, state and
+covariance equal the resident call's bit for bit, from device pointers and from host arrays, and a sharded context accepts it.
 The scene is that of test_gpu_odom.test_lio_state_estimation_parity and the bars are its bars (state 1e-7, covariance 1e-9 of its
 largest entry); the step norms of the report are held to the oracle's trace at 1e-7.  match_num is printed, not compared: a point on
 a float gate may fall either way."""
@@ -74,7 +76,8 @@ def scene(oracle):
 
 
 def _parity(sc, pts, var, state, cov, dev=None):
-    """New call vs oracle and vs the existing call on the same device pointers, at the bars; returns the three results."""
+    """New call vs oracle and vs the existing call on the same device pointers, at the bars, and bit for bit vs the existing call;
+    returns the three results."""
     ctx, om = sc["ctx"], sc["om"]
     dev = dev or Dev(pts, var)
     ok_n, st_n, cov_n, rep = ctx.lio_state_estimation_resident(*dev.args, state, cov)
@@ -96,6 +99,7 @@ def _parity(sc, pts, var, state, cov, dev=None):
     assert np.abs(rep["tra_add"][:it] - tr[:, 2]).max() < STEP_BAR
     assert np.all(rep["rot_add"][it:] == 0) and np.all(rep["tra_add"][it:] == 0) and np.all(rep["match_num"][it:] == 0)
     assert ok_n == (rep["nnt_eig_min"] >= 14)
+    assert np.array_equal(st_e, st_n) and np.array_equal(cov_e, cov_n)   # the existing call runs the resident loop on a staged copy
     return (ok_n, st_n, cov_n, rep), (ok_e, st_e, cov_e), (ok_o, st_o, cov_o, tr)
 
 
@@ -148,6 +152,15 @@ def test_sizes(scene, n):
         assert not new[0]                              # too few normals: the degenerate branch
 
 
+def test_existing_call_on_host_arrays(scene):
+    """The existing call on host arrays gives the resident call's bits."""
+    sc = scene
+    ok_n, st_n, cov_n, _ = sc["ctx"].lio_state_estimation_resident(*sc["dev"].args, sc["state"], sc["cov"])
+    ok_h, st_h, cov_h = sc["ctx"].lio_state_estimation(sc["pts"], sc["var"], sc["state"], sc["cov"])
+    assert (st_n != sc["state"]).any()
+    assert ok_h == ok_n and np.array_equal(st_h, st_n) and np.array_equal(cov_h, cov_n)
+
+
 def _assert_untouched(res, state, cov):
     ok, st, cv, rep = res
     assert np.array_equal(st, state) and np.array_equal(cv, cov)
@@ -155,6 +168,12 @@ def _assert_untouched(res, state, cov):
     assert not ok
     assert np.all(rep["match_num"] == 0) and np.all(rep["rot_add"] == 0) and np.all(rep["tra_add"] == 0)
     assert rep["nnt_eig_min"] == 0.0
+
+
+def _assert_existing_untouched(res, state, cov):
+    ok, st, cv = res
+    assert np.array_equal(st, state) and np.array_equal(cv, cov)
+    assert ok == 0
 
 
 def test_no_point_matches(scene):
@@ -165,15 +184,20 @@ def test_no_point_matches(scene):
 
 
 def test_empty_scan_and_empty_map(scene):
-    """Case 5: n == 0, and a context whose map was never allocated."""
+    """Case 5: n == 0, and a context whose map was never allocated; the existing call too returns its input and ok == 0."""
     sc = scene
     _assert_untouched(sc["ctx"].lio_state_estimation_resident(0, 0, 0, sc["state"], sc["cov"]), sc["state"], sc["cov"])
     fresh = sc["capi"].Context(sc["capi"].options_from_workload(sc["wl"]))
     try:
         _assert_untouched(fresh.lio_state_estimation_resident(*sc["dev"].args, sc["state"], sc["cov"]), sc["state"], sc["cov"])
         _assert_untouched(fresh.lio_state_estimation_resident(0, 0, 0, sc["state"], sc["cov"]), sc["state"], sc["cov"])
+        _assert_existing_untouched(fresh.lio_state_estimation(sc["pts"], sc["var"], sc["state"], sc["cov"]), sc["state"], sc["cov"])
+        _assert_existing_untouched(fresh.lio_state_estimation_dev(*sc["dev"].args, sc["state"], sc["cov"]), sc["state"], sc["cov"])
     finally:
         fresh.close()
+    empty = np.zeros((0, 3)), np.zeros((0, 9))
+    _assert_existing_untouched(sc["ctx"].lio_state_estimation(*empty, sc["state"], sc["cov"]), sc["state"], sc["cov"])
+    _assert_existing_untouched(sc["ctx"].lio_state_estimation_dev(0, 0, 0, sc["state"], sc["cov"]), sc["state"], sc["cov"])
 
 
 def _same(a, b):
@@ -195,7 +219,8 @@ def test_repeatable_and_reads_only(scene):
 
 
 def test_errors(scene):
-    """Case 7: a sharded context is refused; null arrays with n > 0, null state, n < 0 are bad arguments."""
+    """Case 7: a sharded context is refused by the resident call (the existing call runs on the local map); null arrays with n > 0,
+    null state, n < 0 are bad arguments."""
     sc = scene
     capi = sc["capi"]
     ctx = sc["ctx"]
@@ -217,6 +242,9 @@ def test_errors(scene):
         with pytest.raises(capi.VbaError) as e:
             sharded.lio_state_estimation_resident(*sc["dev"].args, sc["state"], sc["cov"])
         assert e.value.status == capi.ERR_UNSUPPORTED
+        n, dp, dv = sc["dev"].args
+        st, cv, ok = sc["state"].copy(), sc["cov"].copy(), C.c_int(-1)
+        assert sharded.lib.vba_odom_lio_state_estimation(sharded.h, C.c_int(n), C.c_void_p(dp), C.c_void_p(dv), capi._p(st), capi._p(cv), C.byref(ok)) == capi.OK
     finally:
         sharded.close()
 

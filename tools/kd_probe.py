@@ -3,14 +3,15 @@ hesai200k_w10 scene against the point-cloud map that four such scans leave, the 
     python tools/kd_probe.py [out.json=profiles/kd_probe.json] [reps=5]
   (a) resident   vba_odom_lio_state_estimation_kdtree_resident on a device pointer (one upload, 17 launches + the re-sampling, one
                  download, one wait)
-  (b) existing   vba_odom_lio_state_estimation_kdtree on the SAME device pointer (device-to-device staging, a wait pair per
-                 iteration, the re-sampling through the public call)
-  (c) host       vba_odom_lio_state_estimation_kdtree on a host array
+  (b) existing   vba_odom_lio_state_estimation_kdtree, the staging front end of (a), on the SAME device pointer (a device-to-device
+                 copy of the points, then the loop of (a))
+  (c) host       vba_odom_lio_state_estimation_kdtree on a host array (the points uploaded per call)
 The three alternate in one process.  Before every call the map is put back, untimed: pl_tree->clear() and one seeding call at the
 identity pose on the saved map points (which are float values, so the append reproduces them bit for bit), then a synchronise.
 Median of `reps` after a warm-up round; host clocks around calls that end in a device synchronise.  Every record holds n, the map
 size and the EKF iteration count; (b) and (c) are checked against (a) at the bars of tests/test_gpu_odom.py.
-Acceptance: median (a) <= median (b).  No per-kernel trace is taken: nothing is claimed about how the time divides."""
+Acceptance: median (a) <= median (b).  No per-kernel trace is taken: nothing is claimed about how the time divides.
+VBA_LIB=<another build's libvoxelba.so> times that build instead (an A/B run against a parent commit)."""
 import json
 import os
 import sys

@@ -1,12 +1,17 @@
 """Measurement of the scan-to-map EKF update for DESIGN.md section 17 (run on an MI355X): one 200k-point scan against the full
 hesai200k_w10 window map (the set-up of bench.py's odometry_update), the same state and covariance for every call.
-    python tools/odom_probe.py [out.json=profiles/odom_probe.json] [reps=5]
+    python tools/odom_probe.py [out.json=profiles/odom_probe.json] [reps=5] [alone]
   (a) resident   vba_odom_lio_state_estimation_resident on device pointers (one upload, 8 launches, one download, one wait)
-  (b) existing   vba_odom_lio_state_estimation on the SAME device pointers (device-to-device staging, a host round trip pair per iteration)
+  (b) existing   vba_odom_lio_state_estimation, the staging front end of (a), on the SAME device pointers (a device-to-device copy of
+                 points + covariances, then the loop of (a))
   (c) host       vba_odom_lio_state_estimation on host arrays (points + covariances uploaded per call: the number of the bench)
 The three alternate in one process; median of `reps` after a warm-up round; host clocks around calls that end in a device
-synchronise.  Every record holds the EKF iteration count: (a) reports its own, and (b), (c) run the same iterations on the same
-input (their results are checked against (a) at the bars of tests/test_gpu_odom.py).  Acceptance: median (a) <= median (b)."""
+synchronise.  Every record holds the EKF iteration count: (a) reports its own, and (b), (c) run the same loop on a copy of the same
+input (their results are checked against (a) at the bars of tests/test_gpu_odom.py).  Acceptance: median (a) <= median (b).
+VBA_LIB=<another build's libvoxelba.so> times that build instead (an A/B run against a parent commit).
+With `alone` every leg is timed by itself instead, back to back: 3 untimed calls, then 3 * reps timed ones, the three legs in turn,
+twice; the record holds [median, min, max] per leg and block under "alone" (what a leg costs when its neighbours are calls of its
+own kind, where the alternation gives what it costs after a call of another kind)."""
 import json
 import os
 import sys
@@ -63,6 +68,21 @@ def main():
         return ctx.lio_state_estimation(pts, var_b, state, cov) + (None,)
 
     legs = (("resident_dev", resident), ("existing_dev", existing), ("existing_host", host))
+    if len(sys.argv) > 3 and sys.argv[3] == "alone":
+        res = dict(source_hash=source_hash(), workload=wl.name, points=n, reps=3 * reps, alone={})
+        for block in range(2):
+            for name, f in legs:
+                for _ in range(3):
+                    f()
+                t = []
+                for _ in range(3 * reps):
+                    t1 = time.perf_counter(); f(); t.append((time.perf_counter() - t1) * 1e3)
+                res["alone"]["%s_%d" % (name, block)] = [float(np.median(t)), float(min(t)), float(max(t))]
+                print("%-14s alone, block %d: median %.4f ms (min %.4f, max %.4f)" % (name, block, np.median(t), min(t), max(t)), flush=True)
+        ctx.close()
+        json.dump(res, open(out_path, "w"), indent=1)
+        print("OK")
+        return
     recs = {name: [] for name, _ in legs}
     out = {}
     for r in range(reps + 1):                      # round 0 is the warm-up

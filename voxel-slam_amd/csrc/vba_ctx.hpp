@@ -192,9 +192,6 @@ void span_begin(vba_ctx *c, const char *name, TimedSpan &s);
 void span_end(vba_ctx *c, const char *name, TimedSpan &s);
 int ensure_pin(vba_ctx *c, size_t n);
 int ensure_stage(vba_ctx *c, size_t bytes);
-// the reduction of workgroup partials (vba_kernels_factor.hpp), also behind the odometry's k_odom_match in vba_map.hip
-__global__ __launch_bounds__(256) void k_reduce_partials(const double *__restrict__ partial, int nb, int nout, double *__restrict__ out,
-                                                         const int *__restrict__ gate);
 // the dense LDL^T of vba_kernels_big.hpp, also the skeleton solve of vba_pgo.hip
 __global__ __launch_bounds__(256) void k_bigl_panel(double *__restrict__ Ab, double *__restrict__ Tb, int NP, int ld, int k0);
 __global__ __launch_bounds__(256) void k_bigl_update(double *__restrict__ Ab, const double *__restrict__ Tb, int NP, int ld, int k0);
@@ -242,8 +239,6 @@ int map_stats(MapStore &s, hipStream_t st, long long *out8, std::string &err);
 int map_dump_leaves(MapStore &s, hipStream_t st, double *out, int max_leaves, std::string &err);
 int map_dump_plane_var(MapStore &s, hipStream_t st, double *out, int max_leaves, std::string &err);
 int map_prune(MapStore &s, hipStream_t st, double jour, int dist, std::string &err);
-int map_odom_accumulate(MapStore &s, hipStream_t st, const OdomState &X, int n, const double *d_pts, const double *d_var,
-                        double *d_partial, double *d_out34, double *out34, std::string &err);
 int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomEkf *h_img, int n, const double *d_pts,
                       const double *d_var, double *d_partial, std::string &err);
 // the update launch of the resident EKF loops (vba_kernels_odom.hpp), also the kd-tree variant's in voxelba.hip

@@ -167,7 +167,7 @@ __device__ inline void btc_triangle_solver(const BtcStds &q, int a, const BtcStd
   for (int r = 0; r < 3; r++) t[r] = -((R[3 * r] * c1[0] + R[3 * r + 1] * c1[1]) + R[3 * r + 2] * c1[2]) + c2[r];
 }
 
-// exact 1-NN of one query point over a cloud streamed through LDS (k_kd_match's conventions: squared L2 in float, x then y then
+// exact 1-NN of one query point over a cloud streamed through LDS (kd_match_body's conventions: squared L2 in float, x then y then
 // z; the key (distance bits << 32 | index) orders by distance, then index).  Every thread of the workgroup must call it.
 __device__ __forceinline__ unsigned long long btc_nn_tile(float qx, float qy, float qz, const float *cl, int lo, int hi, float *tx, float *ty, float *tz) {
   BTC_NOCONTRACT

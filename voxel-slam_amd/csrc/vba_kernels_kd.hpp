@@ -5,10 +5,10 @@
 // exact 5-NN is a tiled brute-force scan: one thread per (scan point, map slice), the slice streamed through LDS 256 points at
 // a time, the five best kept sorted in registers, the slices merged by a second kernel — no tree, no traversal divergence.
 //
-// Every kernel is a thin wrapper over a __device__ body.  k_kd_match / fit / accum / append take the pose by value and are launched by
-// the host-driven loop (vba_odom_lio_state_estimation_kdtree); the k_kd_*_dev wrappers belong to the device-resident loop (DESIGN.md
-// §18): they read the pose from the loop's device state, and first of all its `done` flag (and, the search and the fit, its
-// `refind` flag), returning at once when there is nothing to do.  No atomics.
+// Every kernel is a thin wrapper over a __device__ body.  The k_kd_*_dev wrappers belong to the device-resident loop:
+// they read the pose from the loop's device state, and first of all its `done` flag (and, the search and the fit, its `refind` flag),
+// returning at once when there is nothing to do.  k_kd_append takes the pose by value: it seeds the map before any loop has run.  No
+// atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vba_common.hpp"
@@ -116,10 +116,6 @@ __device__ __forceinline__ void kd_match_body(int n, const double *__restrict__ 
   o[3] = ((unsigned long long)__float_as_uint(bd3) << 32) | (unsigned int)bi3;
   o[4] = ((unsigned long long)__float_as_uint(bd4) << 32) | (unsigned int)bi4;
 }
-__global__ __launch_bounds__(256) void k_kd_match(int n, const double *__restrict__ pts, KdPose X, int m, const double *__restrict__ tree,
-                                                  unsigned long long *__restrict__ cand) {
-  kd_match_body(n, pts, X, m, tree, cand);
-}
 
 // stage 2: merge the slices' candidates, fit the plane (VS:1166-1190): (unit normal, distance) per scan point, distance < 0 = rejected
 __device__ __forceinline__ void kd_fit_body(int n, int slices, const unsigned long long *__restrict__ cand, const double *__restrict__ tree,
@@ -160,14 +156,9 @@ __device__ __forceinline__ void kd_fit_body(int n, int slices, const unsigned lo
   const double d = 1.0 / sqrt(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
   o[0] = dir[0] * d; o[1] = dir[1] * d; o[2] = dir[2] * d; o[3] = d;
 }
-__global__ __launch_bounds__(256) void k_kd_fit(int n, int slices, const unsigned long long *__restrict__ cand, const double *__restrict__ tree,
-                                                double *__restrict__ planes) {
-  kd_fit_body(n, slices, cand, tree, planes);
-}
 
-// HTH (21 unique), HTz (6), valid count: per-block partials [nb][28]  (VS:1198-1209).  NCOL == 34: the same 28 sums as rows of the
-// 34-column layout that k_odom_update reduces (vba_odom_ekf.hpp): HTH 0-20, HTz 21-26, zeros 27-32 (no nnt here), valid 33.
-template <int NCOL>
+// HTH (21 unique), HTz (6), valid count (VS:1198-1209): per-block partials [nb][34], the 28 sums as rows of the layout that
+// k_odom_update reduces (vba_odom_ekf.hpp): HTH 0-20, HTz 21-26, zeros 27-32 (no nnt here), valid 33.
 __device__ __forceinline__ void kd_accum_body(int n, const double *__restrict__ pts, const KdPose &X, const double *__restrict__ planes, double *__restrict__ part) {
   __shared__ double red[4][28];
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -199,16 +190,11 @@ __device__ __forceinline__ void kd_accum_body(int n, const double *__restrict__ 
 #pragma unroll
     for (int k = 0; k < 28; k++) red[threadIdx.x >> 6][k] = s[k];
   __syncthreads();
-  if (NCOL == 28) {
-    if (threadIdx.x < 28) part[(size_t)blockIdx.x * 28 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-  } else if (threadIdx.x < 34) {
+  if (threadIdx.x < 34) {
     const int k = threadIdx.x < 27 ? threadIdx.x : 27;
     const double v = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
     part[(size_t)blockIdx.x * 34 + threadIdx.x] = (threadIdx.x >= 27 && threadIdx.x < 33) ? 0.0 : v;
   }
-}
-__global__ __launch_bounds__(256) void k_kd_accum(int n, const double *__restrict__ pts, KdPose X, const double *__restrict__ planes, double *__restrict__ part) {
-  kd_accum_body<28>(n, pts, X, planes, part);
 }
 
 // world points of the scan appended to the map, as PCL floats (VS:1107-1114, 1238-1246)
@@ -245,7 +231,7 @@ __global__ __launch_bounds__(256) void k_kd_fit_dev(const vbh::OdomEkf *__restri
 __global__ __launch_bounds__(256) void k_kd_accum_dev(const vbh::OdomEkf *__restrict__ S, int n, const double *__restrict__ pts,
                                                       const double *__restrict__ planes, double *__restrict__ part /*[nb][34]*/) {
   if (__builtin_amdgcn_readfirstlane(S->done)) return;
-  kd_accum_body<34>(n, pts, kd_pose_of(S), planes, part);
+  kd_accum_body(n, pts, kd_pose_of(S), planes, part);
 }
 // after the loop: x_curr is final whether or not `done` is set
 __global__ void k_kd_append_dev(const vbh::OdomEkf *__restrict__ S, int n, const double *__restrict__ pts, double *__restrict__ tree_out) {

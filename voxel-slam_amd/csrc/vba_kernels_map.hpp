@@ -1612,8 +1612,8 @@ __global__ void k_prune_fix(MapView m) {
 // (read-only probe), octant descent, the two 3-sigma gates, then the weighted normal equations
 //   HTH (6x6 sym, 21) | HTz (6) | nnt (3x3 sym, 6) | match_num   = 34 sums per workgroup.
 // The reference's per-point cache octos[i] (voxelslam.cpp:1020) only short-cuts the lookup; the full lookup is done here.
-// The body is shared by the two kernels that run it: k_odom_match takes the pose and the covariance blocks by value, k_odom_match_dev
-// (vba_kernels_odom.hpp) reads them from the device state of the resident EKF loop.
+// Run by k_odom_match_dev (vba_kernels_odom.hpp), which reads the pose and the covariance blocks from the device state of the
+// resident EKF loop.
 __device__ __forceinline__ void odom_match_body(const MapView &m, const MapParams &P, const OdomState &X, int n, const double *__restrict__ pts,
                                                 const double *__restrict__ var, double *__restrict__ partial) {
   __shared__ double red[4][34];
@@ -1714,10 +1714,6 @@ __device__ __forceinline__ void odom_match_body(const MapView &m, const MapParam
     for (int k = 0; k < 34; k++) red[threadIdx.x >> 6][k] = acc[k];
   __syncthreads();
   if (threadIdx.x < 34) partial[(size_t)blockIdx.x * 34 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-}
-__global__ __launch_bounds__(256) void k_odom_match(MapView m, MapParams P, OdomState X, int n, const double *__restrict__ pts,
-                                                    const double *__restrict__ var, double *__restrict__ partial) {
-  odom_match_body(m, P, X, n, pts, var, partial);
 }
 
 // ------------------------------------------------------------------------------------------------ dumps
@@ -2501,21 +2497,6 @@ int map_prune(MapStore &s, hipStream_t st, double jour, int dist, std::string &e
   if (s.h_cnt[CNT_FIX] > 0) hipLaunchKernelGGL(k_prune_fix, dim3((s.h_cnt[CNT_FIX] + 255) / 256), dim3(256), 0, st, s.v);
   MAPCHK(hipGetLastError());
   return map_read_counters(s, st, err);
-}
-
-// One scan-to-map accumulation: out34 (host) = [HTH upper (21) | HTz (6) | nnt upper (6) | match_num]
-int map_odom_accumulate(MapStore &s, hipStream_t st, const OdomState &X, int n, const double *d_pts, const double *d_var,
-                        double *d_partial, double *d_out34, double *out34, std::string &err) {
-  if (!s.allocated) { for (int k = 0; k < 34; k++) out34[k] = 0.0; return VBA_OK; }
-  const MapParams P = map_params(s);
-  const int nb = (n + 255) / 256;
-  hipLaunchKernelGGL(k_odom_match, dim3(nb), dim3(256), 0, st, s.v, P, X, n, d_pts, d_var, d_partial);
-  hipLaunchKernelGGL(k_reduce_partials, dim3(3), dim3(256), 0, st, d_partial, nb, 34, d_out34, (const int *)nullptr);
-  MAPCHK(hipGetLastError());
-  MAPCHK(hipStreamSynchronize(st));
-  MAPCHK(hipMemcpyAsync(out34, d_out34, 34 * sizeof(double), hipMemcpyDeviceToHost, st));
-  MAPCHK(hipStreamSynchronize(st));
-  return VBA_OK;
 }
 
 }  // namespace vba

@@ -1,7 +1,7 @@
 // The device-resident iterated EKF of the odometry scan-to-map update (VOXEL_SLAM::lio_state_estimation,
 // voxelslam.cpp:962-1098):
-//   k_odom_match_dev   the point loop of k_odom_match (vba_kernels_map.hpp) with the pose and the covariance blocks read from the
-//                      device state of the loop instead of the kernel arguments
+//   k_odom_match_dev   the point loop (odom_match_body, vba_kernels_map.hpp) with the pose and the covariance blocks read from the
+//                      device state of the loop
 //   k_odom_update      ONE workgroup: sums the workgroup partials in a fixed order and runs one iteration of vba_odom_ekf.hpp on them
 // Both read the state's `done` flag first and return at once when the stop rule has fired, so the host queues all four iterations
 // without waiting for any of them (the pattern of LmDev::stop in vba_kernels_lm.hpp).  No atomics.  Included after vba_kernels_map.hpp.

@@ -1208,110 +1208,8 @@ int vba_odom_kdtree_points(vba_ctx *c, double *out) {
   return VBA_OK;
 }
 
-int vba_odom_lio_state_estimation_kdtree(vba_ctx *c, int n, const double *pnt_body, double *state, double *cov, int *iterations) {
-  if (n < 0 || (n > 0 && !pnt_body) || !state || !cov) return VBA_ERR_BAD_ARG;
-  if (iterations) *iterations = 0;
-  const int DIM = VBA_DIM, nb = (n + 255) / 256;
-  const int kd_slices = kd_slices_of(nb);
-  int st = ensure_stage(c, ((size_t)n * 7 + (size_t)nb * 28 + (size_t)kd_slices * n * 5 + 64) * sizeof(double));
-  if (st) return st;
-  double *d_pts = (double *)c->d_stage, *d_pl = d_pts + (size_t)n * 3, *d_part = d_pl + (size_t)n * 4;
-  unsigned long long *d_cand = (unsigned long long *)(d_part + (size_t)nb * 28);
-  if (n > 0) HIPCHK(c, hipMemcpyAsync(d_pts, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
-  vbh::State x_curr, x_prop;
-  std::memcpy(&x_curr, state, sizeof(x_curr));
-  auto pose_of = [](const vbh::State &x) { KdPose X; std::memcpy(X.R, x.R, sizeof(X.R)); std::memcpy(X.t, x.p, sizeof(X.t)); return X; };
-  st = kd_reserve(c, (size_t)c->kd_n + (size_t)n + 16);
-  if (st) return st;
-  if (c->kd_n < 100) {                                                       // VS:1105-1118: the map is only seeded
-    if (n > 0) hipLaunchKernelGGL(k_kd_append, dim3(nb), dim3(256), 0, c->stream, n, d_pts, pose_of(x_curr), c->d_kdtree[c->kd_cur] + (size_t)c->kd_n * 3);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->kd_n += n;
-    return VBA_OK;
-  }
-  x_prop = x_curr;
-  std::vector<double> P(cov, cov + 225), cov_inv(225), part((size_t)nb * 28);
-  vbh::inverse_pplu(P.data(), cov_inv.data(), DIM);                          // VS:1134
-  const int num_max_iter = 4;
-  int rematch_num = 0, iters = 0;
-  bool refind = true, converged_once = false;
-  double G[225];
-  std::memset(G, 0, sizeof(G));
-  for (int iter = 0; iter < num_max_iter; iter++) {
-    iters++;
-    const KdPose X = pose_of(x_curr);
-    double s28[28];
-    std::memset(s28, 0, sizeof(s28));
-    if (n > 0) {
-      if (refind) {
-        hipLaunchKernelGGL(k_kd_match, dim3(nb, kd_slices), dim3(256), 0, c->stream, n, d_pts, X, c->kd_n, c->d_kdtree[c->kd_cur], d_cand);
-        hipLaunchKernelGGL(k_kd_fit, dim3(nb), dim3(256), 0, c->stream, n, kd_slices, d_cand, c->d_kdtree[c->kd_cur], d_pl);
-      }
-      hipLaunchKernelGGL(k_kd_accum, dim3(nb), dim3(256), 0, c->stream, n, d_pts, X, d_pl, d_part);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipMemcpyAsync(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      for (int b = 0; b < nb; b++) for (int k = 0; k < 28; k++) s28[k] += part[(size_t)b * 28 + k];
-    }
-    double HTH[36], HTz[6];
-    { int idx = 0; for (int r = 0; r < 6; r++) for (int k = r; k < 6; k++) { HTH[r * 6 + k] = s28[idx]; HTH[k * 6 + r] = s28[idx]; idx++; } }
-    for (int r = 0; r < 6; r++) HTz[r] = s28[21 + r];
-    // K_1 = (H_T_H + cov_inv / 1000)^-1 ; G(:,0:6) = K_1(:,0:6) HTH ; solution = K_1(:,0:6) HTz + vec - G(:,0:6) vec(0:6)   VS:1213-1217
-    std::vector<double> A(225), K1(225);
-    for (int k = 0; k < 225; k++) A[k] = cov_inv[k] / 1000;
-    for (int r = 0; r < 6; r++) for (int k = 0; k < 6; k++) A[r * DIM + k] += HTH[r * 6 + k];
-    vbh::inverse_pplu(A.data(), K1.data(), DIM);
-    for (int r = 0; r < DIM; r++)
-      for (int k = 0; k < 6; k++) { double sacc = 0; for (int j = 0; j < 6; j++) sacc += K1[r * DIM + j] * HTH[j * 6 + k]; G[r * DIM + k] = sacc; }
-    double vec[15], RtR[9], lg[3];
-    vbh::m3_Tmul(x_curr.R, x_prop.R, RtR);
-    vbh::so3_log(RtR, lg);
-    for (int k = 0; k < 3; k++) { vec[k] = lg[k]; vec[3 + k] = x_prop.p[k] - x_curr.p[k]; vec[6 + k] = x_prop.v[k] - x_curr.v[k]; vec[9 + k] = x_prop.bg[k] - x_curr.bg[k]; vec[12 + k] = x_prop.ba[k] - x_curr.ba[k]; }
-    double sol[15];
-    for (int r = 0; r < DIM; r++) {
-      double a = 0, b = 0;
-      for (int j = 0; j < 6; j++) { a += K1[r * DIM + j] * HTz[j]; b += G[r * DIM + j] * vec[j]; }
-      sol[r] = a + vec[r] - b;
-    }
-    double E[9], Rn[9];
-    vbh::so3_exp(sol, E);
-    vbh::m3_mul(x_curr.R, E, Rn);
-    std::memcpy(x_curr.R, Rn, sizeof(Rn));
-    for (int k = 0; k < 3; k++) { x_curr.p[k] += sol[3 + k]; x_curr.v[k] += sol[6 + k]; x_curr.bg[k] += sol[9 + k]; x_curr.ba[k] += sol[12 + k]; }
-    const double rot_add = vbh::norm3(sol), tra_add = vbh::norm3(sol + 3);
-    refind = false;                                                          // VS:1223-1234
-    if ((rot_add * 57.3 < 0.01) && (tra_add * 100 < 0.015)) { refind = true; converged_once = true; rematch_num++; }
-    if (iter == num_max_iter - 2 && !converged_once) refind = true;
-    if (rematch_num >= 2 || (iter == num_max_iter - 1)) {
-      std::vector<double> IG(225), Pn(225);
-      for (int r = 0; r < DIM; r++) for (int k = 0; k < DIM; k++) IG[r * DIM + k] = (r == k ? 1.0 : 0.0) - G[r * DIM + k];
-      vbh::mat_mul(IG.data(), P.data(), Pn.data(), DIM, DIM, DIM);
-      P = Pn;
-      break;
-    }
-  }
-  // map update VS:1238-1250: append the scan in the refined pose, re-sample on a 0.5 m grid
-  if (n > 0) hipLaunchKernelGGL(k_kd_append, dim3(nb), dim3(256), 0, c->stream, n, d_pts, pose_of(x_curr), c->d_kdtree[c->kd_cur] + (size_t)c->kd_n * 3);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const int tot = c->kd_n + n;
-  {
-    std::vector<int> cnt(tot), first(tot);
-    int m = 0;
-    st = vba_scan_down_sampling_voxel(c, tot, c->d_kdtree[c->kd_cur], 0.5, c->d_kdtree[c->kd_cur ^ 1], cnt.data(), first.data(), &m);
-    if (st) return st;
-    c->kd_cur ^= 1; c->kd_n = m;
-  }
-  std::memcpy(state, &x_curr, sizeof(x_curr));
-  std::memcpy(cov, P.data(), 225 * sizeof(double));
-  if (iterations) *iterations = iters;
-  return VBA_OK;
-}
-
-// ---------------------------------------------------------------- the same odometry resident on the device
-// device state and pinned image of the resident EKF loops (this one and vba_odom_lio_state_estimation_resident)
+// ---------------------------------------------------------------- its EKF loop, resident on the device
+// device state and pinned image of the resident EKF loops (this one and the voxel map's)
 static int odom_image_ensure(vba_ctx *c) {
   if (c->d_odom) return VBA_OK;
   HIPCHK(c, hipMalloc((void **)&c->d_odom, sizeof(vbh::OdomEkf)));
@@ -1375,21 +1273,20 @@ int vba_odom_kdtree_allocations(vba_ctx *c, int *n_allocs, int64_t *bytes) {
   return VBA_OK;
 }
 
-int vba_odom_lio_state_estimation_kdtree_resident(vba_ctx *c, int n, const double *d_pnt_body, double *state, double *cov, int *iterations,
-                                                  vba_odom_report *report) {
-  if (!c || n < 0 || (n > 0 && !d_pnt_body) || !state || !cov) return VBA_ERR_BAD_ARG;
-  if (iterations) *iterations = 0;
-  if (report) std::memset(report, 0, sizeof(*report));
+// One update on a scan in device memory, c->kd_n + n <= 2^28.  With fewer than 100 map points the scan only seeds the map (VS:1105-1118):
+// the append is enqueued, *ran stays false and nothing is waited for.  Otherwise state and cov are updated, the call has completed on
+// return and c->h_odom holds the loop's result block.  Nothing here touches c->d_stage: a caller may keep the scan there.
+static int kd_odom_core(vba_ctx *c, int n, const double *d_pts, double *state, double *cov, bool *ran) {
+  *ran = false;
   const int nb = (n + 255) / 256, kd_slices = kd_slices_of(nb);
   const size_t tot = (size_t)c->kd_n + (size_t)n;
-  if (tot > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
   int st = kd_reserve(c, tot + 16);
   if (st) return st;
-  if (c->kd_n < 100) {                                                       // VS:1105-1118: the map is only seeded; stream-ordered
+  if (c->kd_n < 100) {
     if (n > 0) {
       KdPose X;
       std::memcpy(X.R, state + 1, sizeof(X.R)); std::memcpy(X.t, state + 10, sizeof(X.t));
-      hipLaunchKernelGGL(k_kd_append, dim3(nb), dim3(256), 0, c->stream, n, d_pnt_body, X, c->d_kdtree[c->kd_cur] + (size_t)c->kd_n * 3);
+      hipLaunchKernelGGL(k_kd_append, dim3(nb), dim3(256), 0, c->stream, n, d_pts, X, c->d_kdtree[c->kd_cur] + (size_t)c->kd_n * 3);
       HIPCHK(c, hipGetLastError());
     }
     c->kd_n += n;
@@ -1417,16 +1314,16 @@ int vba_odom_lio_state_estimation_kdtree_resident(vba_ctx *c, int n, const doubl
   HIPCHK(c, hipMemcpyAsync(d_S, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
   for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
     if (n > 0) {
-      hipLaunchKernelGGL(k_kd_match_dev, dim3(nb, kd_slices), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pnt_body, c->kd_n, (const double *)tree, d_cand);
+      hipLaunchKernelGGL(k_kd_match_dev, dim3(nb, kd_slices), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, c->kd_n, (const double *)tree, d_cand);
       hipLaunchKernelGGL(k_kd_fit_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, kd_slices, (const unsigned long long *)d_cand, (const double *)tree, d_pl);
-      hipLaunchKernelGGL(k_kd_accum_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pnt_body, (const double *)d_pl, d_part);
+      hipLaunchKernelGGL(k_kd_accum_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, (const double *)d_pl, d_part);
     }
     // n == 0: nb == 0 and d_part may be NULL (no scan scratch was ever needed); the reduction reads nb * 34 doubles, that is none
     hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, s, d_S, (const double *)d_part, nb, iter, 1);
   }
   // map update VS:1238-1250: the scan appended in the refined pose, map + scan re-sampled on a 0.5 m grid into the other half; the
   // voxel count lands in the result block
-  if (n > 0) hipLaunchKernelGGL(k_kd_append_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pnt_body, tree + (size_t)c->kd_n * 3);
+  if (n > 0) hipLaunchKernelGGL(k_kd_append_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, tree + (size_t)c->kd_n * 3);
   w.n_out = &d_S->n_map;
   if ((st = ds_core(c, s, 0, (int)tot, tree, nullptr, 9, 4, 0.5, det, w))) return st;
   hipLaunchKernelGGL(k_ds_emit, dim3(((int)tot + 255) / 256), dim3(256), 0, s, (int)tot, (const DsSlot *)w.tab, (const int *)w.slot, (const int *)w.blk, tree_out, d_cnt,
@@ -1439,12 +1336,41 @@ int vba_odom_lio_state_estimation_kdtree_resident(vba_ctx *c, int n, const doubl
   c->kd_cur ^= 1; c->kd_n = S.n_map;
   std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
   std::memcpy(cov, S.P_out, sizeof(S.P_out));
+  *ran = true;
+  return VBA_OK;
+}
+
+int vba_odom_lio_state_estimation_kdtree_resident(vba_ctx *c, int n, const double *d_pnt_body, double *state, double *cov, int *iterations,
+                                                  vba_odom_report *report) {
+  if (!c || n < 0 || (n > 0 && !d_pnt_body) || !state || !cov) return VBA_ERR_BAD_ARG;
+  if (iterations) *iterations = 0;
+  if (report) std::memset(report, 0, sizeof(*report));
+  if ((size_t)c->kd_n + (size_t)n > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
+  bool ran;
+  const int st = kd_odom_core(c, n, d_pnt_body, state, cov, &ran);
+  if (st || !ran) return st;
+  const vbh::OdomEkf &S = *c->h_odom;
   if (iterations) *iterations = S.iterations;
   if (report) {
     report->iterations = S.iterations;
     for (int k = 0; k < 4; k++) { report->match_num[k] = S.match_num[k]; report->rot_add[k] = S.rot_add[k]; report->tra_add[k] = S.tra_add[k]; }
     report->nnt_eig_min = 0.0;
   }
+  return VBA_OK;
+}
+
+// The staging front end of the same update: the scan may be in host or device memory and the call has completed when it returns.
+int vba_odom_lio_state_estimation_kdtree(vba_ctx *c, int n, const double *pnt_body, double *state, double *cov, int *iterations) {
+  if (n < 0 || (n > 0 && !pnt_body) || !state || !cov) return VBA_ERR_BAD_ARG;
+  if (iterations) *iterations = 0;
+  if ((size_t)c->kd_n + (size_t)n > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
+  int st = ensure_stage(c, (size_t)n * 3 * sizeof(double));
+  if (st) return st;
+  if (n > 0) HIPCHK(c, hipMemcpyAsync(c->d_stage, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
+  bool ran;
+  if ((st = kd_odom_core(c, n, (const double *)c->d_stage, state, cov, &ran))) return st;
+  if (!ran) HIPCHK(c, hipStreamSynchronize(c->stream));                    // seeded: the core only enqueued the append
+  else if (iterations) *iterations = c->h_odom->iterations;
   return VBA_OK;
 }
 
@@ -2297,89 +2223,13 @@ int vba_motion_init(vba_ctx *c, int W, const int *pt_offsets, const double *pnt,
 }
 
 // ---------------------------------------------------------------- odometry scan-to-map (VS:962-1098)
-int vba_odom_lio_state_estimation(vba_ctx *c, int n, const double *pnt_body, const double *var_body, double *state, double *cov, int *ok) {
-  if (n < 0 || (n > 0 && (!pnt_body || !var_body)) || !state || !cov) return VBA_ERR_BAD_ARG;
-  const int DIM = VBA_DIM;
-  // stage the scan once: [pts n*3 | var n*9 | partial nb*34 | out 34]
-  const int nb = (n + 255) / 256;
-  const size_t bytes = ((size_t)n * 12 + (size_t)nb * 34 + 64) * sizeof(double);
-  int st = ensure_stage(c, bytes);
+// One update on a scan in device memory with the iterations resident on the device: the host inverts P once, writes
+// one image, queues the four (point loop, update) pairs and waits once; which of them do any work is decided by the `done` flag in the
+// device state.  state and cov are updated, c->h_odom holds the loop's result block.  Nothing here touches c->d_stage: a caller may keep
+// the scan there.  Runs on this rank's map, whatever n_ranks is.
+static int odom_core(vba_ctx *c, int n, const double *d_pts, const double *d_var, double *state, double *cov) {
+  int st = odom_image_ensure(c);
   if (st) return st;
-  double *d_pts = (double *)c->d_stage, *d_var = d_pts + (size_t)n * 3, *d_part = d_var + (size_t)n * 9, *d_o34 = d_part + (size_t)nb * 34;
-  if (n > 0) {
-    HIPCHK(c, hipMemcpyAsync(d_pts, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_var, var_body, (size_t)n * 9 * sizeof(double), hipMemcpyDefault, c->stream));
-  }
-  vbh::State x_curr, x_prop;
-  std::memcpy(&x_curr, state, sizeof(x_curr));
-  x_prop = x_curr;                                                         // VS:965
-  std::vector<double> P(cov, cov + 225), cov_inv(225);
-  vbh::inverse_pplu(P.data(), cov_inv.data(), DIM);                        // VS:987
-  const int num_max_iter = 4;
-  int rematch_num = 0;
-  double nnt[9] = {0};
-  double G[225];
-  for (int iter = 0; iter < num_max_iter; iter++) {
-    OdomState X;
-    std::memcpy(X.R, x_curr.R, sizeof(X.R)); std::memcpy(X.t, x_curr.p, sizeof(X.t));
-    for (int r = 0; r < 3; r++) for (int k = 0; k < 3; k++) { X.rot_var[3 * r + k] = P[r * DIM + k]; X.tsl_var[3 * r + k] = P[(3 + r) * DIM + 3 + k]; }   // VS:1000-1001
-    double s34[34];
-    if (n > 0) { st = map_odom_accumulate(c->map, c->stream, X, n, d_pts, d_var, d_part, d_o34, s34, c->err); if (st) return st; }
-    else std::memset(s34, 0, sizeof(s34));
-    double HTH[36], HTz[6];
-    { int idx = 0; for (int r = 0; r < 6; r++) for (int k = r; k < 6; k++) { HTH[r * 6 + k] = s34[idx]; HTH[k * 6 + r] = s34[idx]; idx++; } }
-    for (int r = 0; r < 6; r++) HTz[r] = s34[21 + r];
-    nnt[0] = s34[27]; nnt[1] = nnt[3] = s34[28]; nnt[2] = nnt[6] = s34[29]; nnt[4] = s34[30]; nnt[5] = nnt[7] = s34[31]; nnt[8] = s34[32];
-    // K_1 = (H_T_H + cov_inv)^-1 ; G(:,0:6) = K_1(:,0:6) HTH ; solution = K_1(:,0:6) HTz + vec - G(:,0:6) vec(0:6)      VS:1056-1060
-    std::vector<double> A(cov_inv), K1(225);
-    for (int r = 0; r < 6; r++) for (int k = 0; k < 6; k++) A[r * DIM + k] += HTH[r * 6 + k];
-    vbh::inverse_pplu(A.data(), K1.data(), DIM);
-    std::memset(G, 0, sizeof(G));
-    for (int r = 0; r < DIM; r++)
-      for (int k = 0; k < 6; k++) { double sacc = 0; for (int j = 0; j < 6; j++) sacc += K1[r * DIM + j] * HTH[j * 6 + k]; G[r * DIM + k] = sacc; }
-    double vec[15], RtR[9], lg[3];
-    vbh::m3_Tmul(x_curr.R, x_prop.R, RtR);                                 // x_prop - x_curr: Log(b.R^T this.R)  TL:164-173
-    vbh::so3_log(RtR, lg);
-    for (int k = 0; k < 3; k++) { vec[k] = lg[k]; vec[3 + k] = x_prop.p[k] - x_curr.p[k]; vec[6 + k] = x_prop.v[k] - x_curr.v[k]; vec[9 + k] = x_prop.bg[k] - x_curr.bg[k]; vec[12 + k] = x_prop.ba[k] - x_curr.ba[k]; }
-    double sol[15];
-    for (int r = 0; r < DIM; r++) {
-      double a = 0, b = 0;
-      for (int j = 0; j < 6; j++) { a += K1[r * DIM + j] * HTz[j]; b += G[r * DIM + j] * vec[j]; }
-      sol[r] = a + vec[r] - b;
-    }
-    double E[9], Rn[9];                                                    // x_curr += solution  TL:154-162
-    vbh::so3_exp(sol, E);
-    vbh::m3_mul(x_curr.R, E, Rn);
-    std::memcpy(x_curr.R, Rn, sizeof(Rn));
-    for (int k = 0; k < 3; k++) { x_curr.p[k] += sol[3 + k]; x_curr.v[k] += sol[6 + k]; x_curr.bg[k] += sol[9 + k]; x_curr.ba[k] += sol[12 + k]; }
-    const double rot_add = vbh::norm3(sol), tra_add = vbh::norm3(sol + 3);
-    const bool converged = (rot_add * 57.3 < 0.01) && (tra_add * 100 < 0.015);     // VS:1072
-    if (converged || ((rematch_num == 0) && (iter == num_max_iter - 2))) rematch_num++;   // VS:1076-1079
-    if (rematch_num >= 2 || (iter == num_max_iter - 1)) {                  // x_curr.cov = (I - G) cov   VS:1082-1086
-      std::vector<double> IG(225), Pn(225);
-      for (int r = 0; r < DIM; r++) for (int k = 0; k < DIM; k++) IG[r * DIM + k] = (r == k ? 1.0 : 0.0) - G[r * DIM + k];
-      vbh::mat_mul(IG.data(), P.data(), Pn.data(), DIM, DIM, DIM);
-      P = Pn;
-      break;
-    }
-  }
-  std::memcpy(state, &x_curr, sizeof(x_curr));
-  std::memcpy(cov, P.data(), 225 * sizeof(double));
-  // SelfAdjointEigenSolver(nnt).eigenvalues()[0] < 14 -> false  (VS:1090-1097); closed form is not needed here: Jacobi on host
-  if (ok) *ok = (vbh::odom_nnt_eig_min(nnt) < 14) ? 0 : 1;
-  return VBA_OK;
-}
-
-// The same update with the iterations resident on the device: the host inverts P once, writes one image, queues the
-// four (point loop, update) pairs and waits once; which of them do any work is decided by the `done` flag in the device state.
-int vba_odom_lio_state_estimation_resident(vba_ctx *c, int n, const double *d_pnt_body, const double *d_var_body, double *state, double *cov,
-                                           int *ok, vba_odom_report *report) {
-  if (n < 0 || (n > 0 && (!d_pnt_body || !d_var_body)) || !state || !cov) return VBA_ERR_BAD_ARG;
-  if (c->n_ranks > 1) { c->set_error("the resident odometry loop has no all-reduce step between its iterations: unsharded contexts only"); return VBA_ERR_UNSUPPORTED; }
-  {
-    const int st = odom_image_ensure(c);
-    if (st) return st;
-  }
   const size_t need = (size_t)((n + 255) / 256) * 34;
   if (need > c->odom_part_doubles) {
     if (c->d_odom_part) hipFree(c->d_odom_part);       // idle: the call that used it ended in a synchronise
@@ -2393,10 +2243,20 @@ int vba_odom_lio_state_estimation_resident(vba_ctx *c, int n, const double *d_pn
   vbh::inverse_pplu(cov, cov_inv, VBA_DIM);                                // VS:987
   vbh::OdomEkf &S = *c->h_odom;
   vbh::odom_ekf_begin(S, state, cov, cov_inv);
-  const int st = map_odom_resident(c->map, c->stream, c->d_odom, c->h_odom, n, d_pnt_body, d_var_body, c->d_odom_part, c->err);
-  if (st) return st;
+  if ((st = map_odom_resident(c->map, c->stream, c->d_odom, c->h_odom, n, d_pts, d_var, c->d_odom_part, c->err))) return st;
   std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
   std::memcpy(cov, S.P_out, sizeof(S.P_out));
+  return VBA_OK;
+}
+
+int vba_odom_lio_state_estimation_resident(vba_ctx *c, int n, const double *d_pnt_body, const double *d_var_body, double *state, double *cov,
+                                           int *ok, vba_odom_report *report) {
+  if (n < 0 || (n > 0 && (!d_pnt_body || !d_var_body)) || !state || !cov) return VBA_ERR_BAD_ARG;
+  if (c->n_ranks > 1) { c->set_error("the resident odometry loop has no all-reduce step between its iterations: unsharded contexts only"); return VBA_ERR_UNSUPPORTED; }
+  const int st = odom_core(c, n, d_pnt_body, d_var_body, state, cov);
+  if (st) return st;
+  const vbh::OdomEkf &S = *c->h_odom;
+  // SelfAdjointEigenSolver(nnt).eigenvalues()[0] < 14 -> false  (VS:1090-1097)
   const double emin = vbh::odom_nnt_eig_min(S.nnt);
   if (ok) *ok = (emin < 14) ? 0 : 1;
   if (report) {
@@ -2404,6 +2264,21 @@ int vba_odom_lio_state_estimation_resident(vba_ctx *c, int n, const double *d_pn
     for (int k = 0; k < 4; k++) { report->match_num[k] = S.match_num[k]; report->rot_add[k] = S.rot_add[k]; report->tra_add[k] = S.tra_add[k]; }
     report->nnt_eig_min = emin;
   }
+  return VBA_OK;
+}
+
+// The staging front end of the same update: the scan may be in host or device memory, and a sharded context is accepted.
+int vba_odom_lio_state_estimation(vba_ctx *c, int n, const double *pnt_body, const double *var_body, double *state, double *cov, int *ok) {
+  if (n < 0 || (n > 0 && (!pnt_body || !var_body)) || !state || !cov) return VBA_ERR_BAD_ARG;
+  int st = ensure_stage(c, (size_t)n * 12 * sizeof(double));             // [pts n*3 | var n*9]
+  if (st) return st;
+  double *d_pts = (double *)c->d_stage, *d_var = d_pts + (size_t)n * 3;
+  if (n > 0) {
+    HIPCHK(c, hipMemcpyAsync(d_pts, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_var, var_body, (size_t)n * 9 * sizeof(double), hipMemcpyDefault, c->stream));
+  }
+  if ((st = odom_core(c, n, d_pts, d_var, state, cov))) return st;
+  if (ok) *ok = (vbh::odom_nnt_eig_min(c->h_odom->nnt) < 14) ? 0 : 1;
   return VBA_OK;
 }
 
