@@ -179,6 +179,34 @@ __device__ __forceinline__ double wave_sum(double x) {
   return x;
 }
 
+// Sum over the 64 lanes of a wave, result valid in LANE 63 only.  Data-parallel-primitive moves instead of ds_bpermute
+// (__shfl_xor goes through the LDS crossbar: ~100+ cycles per step, six dependent steps): quad swaps, row mirrors, then the
+// two row broadcasts of gfx9.  Fixed summation tree, so the result does not depend on the launch.
+__device__ __forceinline__ double dpp_mov_f64(double x, double old, const int ctrl, const int row_mask) {
+  const long long xi = __double_as_longlong(x), oi = __double_as_longlong(old);
+  int lo = (int)xi, hi = (int)(xi >> 32);
+  const int olo = (int)oi, ohi = (int)(oi >> 32);
+  switch (ctrl) {   // (the control word is an immediate operand)
+    case 0xB1: lo = __builtin_amdgcn_update_dpp(olo, lo, 0xB1, 0xF, 0xF, false); hi = __builtin_amdgcn_update_dpp(ohi, hi, 0xB1, 0xF, 0xF, false); break;
+    case 0x4E: lo = __builtin_amdgcn_update_dpp(olo, lo, 0x4E, 0xF, 0xF, false); hi = __builtin_amdgcn_update_dpp(ohi, hi, 0x4E, 0xF, 0xF, false); break;
+    case 0x141: lo = __builtin_amdgcn_update_dpp(olo, lo, 0x141, 0xF, 0xF, false); hi = __builtin_amdgcn_update_dpp(ohi, hi, 0x141, 0xF, 0xF, false); break;
+    case 0x140: lo = __builtin_amdgcn_update_dpp(olo, lo, 0x140, 0xF, 0xF, false); hi = __builtin_amdgcn_update_dpp(ohi, hi, 0x140, 0xF, 0xF, false); break;
+    case 0x142: lo = __builtin_amdgcn_update_dpp(olo, lo, 0x142, 0xA, 0xF, false); hi = __builtin_amdgcn_update_dpp(ohi, hi, 0x142, 0xA, 0xF, false); break;
+    default: lo = __builtin_amdgcn_update_dpp(olo, lo, 0x143, 0xC, 0xF, false); hi = __builtin_amdgcn_update_dpp(ohi, hi, 0x143, 0xC, 0xF, false); break;
+  }
+  (void)row_mask;
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+__device__ __forceinline__ double wave_sum_to_lane63(double x) {
+  x += dpp_mov_f64(x, x, 0xB1, 0xF);      // quad_perm [1,0,3,2]
+  x += dpp_mov_f64(x, x, 0x4E, 0xF);      // quad_perm [2,3,0,1]
+  x += dpp_mov_f64(x, x, 0x141, 0xF);     // row_half_mirror
+  x += dpp_mov_f64(x, x, 0x140, 0xF);     // row_mirror: every lane of a 16-lane row holds the row's sum
+  x += dpp_mov_f64(x, 0.0, 0x142, 0xA);   // row_bcast15 into rows 1 and 3 (the others add 0)
+  x += dpp_mov_f64(x, 0.0, 0x143, 0xC);   // row_bcast31 into rows 2 and 3
+  return x;
+}
+
 // a double every lane loaded from the same address, made wave-uniform for the compiler too
 __device__ __forceinline__ double odom_uniform(double x) {
   const int lo = __builtin_amdgcn_readfirstlane(__double2loint(x)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(x));

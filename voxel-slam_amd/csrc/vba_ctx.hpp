@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>     // TYPES only: the entry points are resolved at run time (rccl_api in voxelba.hip), the library does not link librccl
 #include <array>
+#include <cstdlib>
 #include <map>
 #include <string>
 #include <vector>
@@ -26,6 +27,20 @@ using namespace vba;
 
 namespace vba {
 struct TimedSpan { hipEvent_t a, b; };
+
+constexpr int kMaxDevices = 64;            // per-device "kernel attribute set" flags
+
+// Diagnostic switches (in-kernel stamps, host-side phase timers, ablation forms) exist only in a -DVBA_DIAG build (make diag ->
+// libvoxelba_diag.so, tools/README.md); the shipped library reads no environment variable.  Internal linkage: the diagnostic library links
+// -DVBA_DIAG objects of the units that call this (csrc/Makefile, DIAG_UNITS) with plain objects of the others.
+static inline const char *diag_env(const char *name) {
+#ifdef VBA_DIAG
+  return std::getenv(name);
+#else
+  (void)name;
+  return nullptr;
+#endif
+}
 }
 namespace vbh { struct OdomEkf; }   // vba_odom_ekf.hpp
 
@@ -192,7 +207,17 @@ void span_begin(vba_ctx *c, const char *name, TimedSpan &s);
 void span_end(vba_ctx *c, const char *name, TimedSpan &s);
 int ensure_pin(vba_ctx *c, size_t n);
 int ensure_stage(vba_ctx *c, size_t bytes);
-// the dense LDL^T of vba_kernels_big.hpp, also the skeleton solve of vba_pgo.hip
+int factor_reserve(vba_ctx *c, int need);
+void factor_update_mask(vba_ctx *c, int base, int n);
+int ctx_allgather(vba_ctx *c, double *buf, size_t chunk);
+bool li_device_supported(int W);
+
+// ---------------------------------------------------------------- vba_hba.hip (vba_kernels_big.hpp)
+// the damped solve of the any-window path, also VBA_SOLVE_DENSE of vba_debug_solve in voxelba.hip
+void big_pivot_order(const double *hd, double u, int n, int *ord);
+double big_q1(const double *dxi, const double *hd, const double *g, double u, int n);
+int big_solve(BigStore &s, hipStream_t st, const int *ord, double u, double *dxi, std::string &err);
+// its dense LDL^T, also the skeleton solve of vba_pgo.hip
 __global__ __launch_bounds__(256) void k_bigl_panel(double *__restrict__ Ab, double *__restrict__ Tb, int NP, int ld, int k0);
 __global__ __launch_bounds__(256) void k_bigl_update(double *__restrict__ Ab, const double *__restrict__ Tb, int NP, int ld, int k0);
 __global__ __launch_bounds__(64) void k_bigl_bs_tri(double *__restrict__ Ab, int NP, int ld, int n, int lo);
@@ -216,7 +241,7 @@ __global__ void k_undistort(int n, double *__restrict__ pnt, const double *__res
 __global__ void k_var_init(int n, const double *__restrict__ pin, double *__restrict__ pout, double *__restrict__ var, const double *__restrict__ ext,
                            float range_inc, float degree_inc);
 
-// ---------------------------------------------------------------- vba_map.hip (vba_kernels_map.hpp, vba_kernels_loop.hpp)
+// ---------------------------------------------------------------- vba_map.hip
 void map_init(MapStore &s, const vba_options &o);
 std::vector<DevArr> node_arrays(MapView &v, int W);
 std::vector<DevArr> scan_arrays(MapView &v, int W);
@@ -241,11 +266,11 @@ int map_dump_plane_var(MapStore &s, hipStream_t st, double *out, int max_leaves,
 int map_prune(MapStore &s, hipStream_t st, double jour, int dist, std::string &err);
 int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomEkf *h_img, int n, const double *d_pts,
                       const double *d_var, double *d_partial, std::string &err);
-// the update launch of the resident EKF loops (vba_kernels_odom.hpp), also the kd-tree variant's in voxelba.hip
+// the update launch of the resident EKF loops (vba_kernels_odom.hpp), also the kd-tree variant's in vba_odom.hip
 __global__ __launch_bounds__(256) void k_odom_update(vbh::OdomEkf *S, const double *__restrict__ partial, int nb, int iter, int kd);
 int map_fix_source_ensure(MapStore &s, hipStream_t st, size_t nodes, size_t fix, size_t n, std::string &err);
 int map_cut_voxel_fix_source(MapStore &s, hipStream_t st, int n, const FixSource &src, double jour, std::string &err);
-// fills the map's root table with the empty key, also the hash tables of vba_kernels_big.hpp in voxelba.hip
+// fills the map's root table with the empty key, also the hash tables of vba_kernels_big.hpp in vba_hba.hip
 __global__ void k_fill_u64(unsigned long long *p, unsigned long long v, size_t n);
 // the one-workgroup exclusive scan of the map's stable compactions, also the match-list offsets of vba_btc.hip
 __global__ __launch_bounds__(1024) void k_det_scan(int *a, int n_max, int *cnt, int which_n, int cap_n, int which_out);

@@ -1,0 +1,760 @@
+// libvoxelba.so: hierarchical global BA (vba_gba_build, vba_hba_add_edge, vba_hba_global).  The octree build and extraction of
+// vba_kernels_gba.hpp, the any-window sparse path of vba_kernels_big.hpp (compiled here and nowhere else) and their host drivers; the
+// fixed-window LM loop, the factor store and the exchange step are the BA core's (voxelba.hip), reached through the C ABI and vba_ctx.hpp.
+#include "vba_ctx.hpp"
+#include "vba_kernels_gba.hpp"
+#include "vba_kernels_big.hpp"
+#include "vba_hostmath.hpp"
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <thread>
+#include <vector>
+
+namespace vba {
+
+// ---------------------------------------------------------------- host side of vba_kernels_gba.hpp: the octree of one window
+#define GBACHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return VBA_ERR_HIP; } } while (0)
+
+inline int gba_alloc_nodes(GbaStore &s, int cap, int W, std::string &err) {
+  s.free_nodes();
+  const size_t cp = (size_t)cap;
+  auto al = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes); if (e == hipSuccess) s.node_bufs.push_back(*p); return e; };
+  GBACHK(al((void **)&s.v.nadd, 10 * cp * 8)); GBACHK(al((void **)&s.v.nlc, 10 * cp * W * 8)); GBACHK(al((void **)&s.v.ncenter, 3 * cp * 8));
+  GBACHK(al((void **)&s.v.nql, cp * 4)); GBACHK(al((void **)&s.v.nchild, cp * 4)); GBACHK(al((void **)&s.v.nfac, cp * 4)); GBACHK(al((void **)&s.v.nlayer, cp));
+  GBACHK(al((void **)&s.v.neval, 3 * cp * 8)); GBACHK(al((void **)&s.v.nevec, 9 * cp * 8));
+  s.v.cap = cap; s.v.W = W;
+  return VBA_OK;
+}
+
+// Builds the octree of one keyframe window and leaves the planar voxels in device node storage; *n_factors = their count.
+// pl may be a host or device pointer ([n][3] local points, keyframe i = rows offsets[i]..offsets[i+1]).
+inline int gba_build(GbaStore &s, hipStream_t st, int W, const int *offsets, const double *pl, const double *poses, const GbaParams &P, int *n_factors,
+                     std::string &err) {
+  const int n = offsets[W];
+  *n_factors = 0;
+  if (!s.h_cnt) {
+    GBACHK(hipHostMalloc((void **)&s.h_cnt, GCNT_N * sizeof(int), hipHostMallocDefault));
+    GBACHK(hipMalloc((void **)&s.v.cnt, GCNT_N * sizeof(int)));
+    GBACHK(hipMalloc((void **)&s.v.poses, VBA_MAX_WIN * 12 * sizeof(double)));
+    GBACHK(hipMalloc((void **)&s.v.offsets, (VBA_MAX_WIN + 1) * sizeof(int)));
+  }
+  if (n > s.cap_pts) {
+    hipFree(s.v.pw); hipFree(s.v.pframe); hipFree(s.v.pnode); hipFree(s.d_pl);
+    const size_t c = (size_t)n + n / 4 + 1024;
+    GBACHK(hipMalloc((void **)&s.v.pw, 3 * c * 8)); GBACHK(hipMalloc((void **)&s.v.pframe, c * 4)); GBACHK(hipMalloc((void **)&s.v.pnode, c * 4));
+    GBACHK(hipMalloc((void **)&s.d_pl, 3 * c * 8));
+    s.cap_pts = (int)c;
+  }
+  int hcap = 1 << 16;
+  while (hcap < 2 * n && hcap < (1 << 28)) hcap <<= 1;
+  if (hcap > s.cap_hash) {
+    hipFree(s.v.hkeys); hipFree(s.v.hvals);
+    GBACHK(hipMalloc((void **)&s.v.hkeys, (size_t)hcap * 8)); GBACHK(hipMalloc((void **)&s.v.hvals, (size_t)hcap * 4));
+    s.cap_hash = hcap;
+  }
+  s.v.hmask = (unsigned int)(s.cap_hash - 1);
+  s.v.npts = n;
+  GBACHK(hipMemcpyAsync(s.d_pl, pl, (size_t)n * 3 * 8, hipMemcpyDefault, st));
+  s.v.pl = s.d_pl;
+  GBACHK(hipMemcpyAsync(s.v.poses, poses, (size_t)W * 12 * 8, hipMemcpyHostToDevice, st));
+  GBACHK(hipMemcpyAsync(s.v.offsets, offsets, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, st));
+  if (s.v.cap == 0 || s.v.W != W) { int r = gba_alloc_nodes(s, 1 << 17, W, err); if (r) return r; }
+  const dim3 b(256), gp((n + 255) / 256);
+  for (int attempt = 0; attempt < 8; attempt++) {
+    const size_t cp = (size_t)s.v.cap;
+    GBACHK(hipMemsetAsync(s.v.cnt, 0, GCNT_N * sizeof(int), st));
+    GBACHK(hipMemsetAsync(s.v.hkeys, 0xFF, (size_t)s.cap_hash * 8, st));
+    GBACHK(hipMemsetAsync(s.v.nadd, 0, 10 * cp * 8, st));
+    GBACHK(hipMemsetAsync(s.v.nlc, 0, 10 * cp * W * 8, st));
+    if (n > 0) {
+      hipLaunchKernelGGL(k_gba_keys, gp, b, 0, st, s.v, P);
+      hipLaunchKernelGGL(k_gba_roots, dim3((s.cap_hash + 4095) / 4096), b, 0, st, s.v, P);
+      hipLaunchKernelGGL(k_gba_rootid, gp, b, 0, st, s.v);
+      for (int L = 0; L <= P.max_layer; L++) {
+        hipLaunchKernelGGL(k_gba_accum, gp, b, 0, st, s.v);
+        hipLaunchKernelGGL(k_gba_decide, dim3((s.v.cap + 255) / 256), b, 0, st, s.v, P, L);
+        if (L < P.max_layer) hipLaunchKernelGGL(k_gba_descend, gp, b, 0, st, s.v);
+      }
+    }
+    GBACHK(hipGetLastError());
+    GBACHK(hipStreamSynchronize(st));   // drain first (see map_read_counters)
+    GBACHK(hipMemcpyAsync(s.h_cnt, s.v.cnt, GCNT_N * sizeof(int), hipMemcpyDeviceToHost, st));
+    GBACHK(hipStreamSynchronize(st));
+    if (s.h_cnt[GCNT_OVERFLOW] == 2) { err = "keyframe point outside the 21-bit voxel index range"; return VBA_ERR_CAPACITY; }
+    if (!s.h_cnt[GCNT_OVERFLOW]) { *n_factors = s.h_cnt[GCNT_FACTORS]; return VBA_OK; }
+    int want = s.v.cap * 2;
+    while (want < s.h_cnt[GCNT_NODES] + 64) want *= 2;
+    int r = gba_alloc_nodes(s, want, W, err);
+    if (r) return r;
+  }
+  err = "octree node capacity";
+  return VBA_ERR_CAPACITY;
+}
+
+// ---------------------------------------------------------------- host side of vba_kernels_big.hpp: the any-window sparse path
+#define BIGCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return VBA_ERR_HIP; } } while (0)
+
+// Builds the octree of `W` keyframes and the sparse factor store (everything is re-allocated per call: the top-level BA
+// runs once per loop closure).  pl: device pointer to the local points [n][3].
+inline int big_build(BigStore &s, hipStream_t st, int W, const int *offsets, const double *d_pl, const double *poses, const GbaParams &P, std::string &err) {
+  s.reset();
+  const int n = offsets[W];
+  auto al = [&](void **p, size_t bytes) { return s.arena(p, bytes); };
+  if (!s.h_cnt) BIGCHK(hipHostMalloc((void **)&s.h_cnt, GCNT_N * sizeof(int), hipHostMallocDefault));
+  GbaBigView &g = s.g;
+  g.W = W; g.npts = n; g.pl = d_pl;
+  unsigned int hcap = 1u << 16; while (hcap < 2u * (unsigned)n && hcap < (1u << 28)) hcap <<= 1;
+  unsigned int ecap = 1u << 16;                         // (node, frame) pairs of ALL levels share the table: <= points per level
+  while ((unsigned long long)ecap < 2ull * (unsigned long long)n * (unsigned)(P.max_layer + 1) && ecap < (1u << 30)) ecap <<= 1;
+  g.hmask = hcap - 1; g.emask = ecap - 1;
+  BIGCHK(al((void **)&g.hkeys, (size_t)hcap * 8)); BIGCHK(al((void **)&g.hvals, (size_t)hcap * 4));
+  BIGCHK(al((void **)&g.ekeys, (size_t)ecap * 8)); BIGCHK(al((void **)&g.ecl, (size_t)ecap * 10 * 8));
+  BIGCHK(al((void **)&g.pw, (size_t)n * 3 * 8)); BIGCHK(al((void **)&g.pframe, (size_t)n * 4)); BIGCHK(al((void **)&g.pnode, (size_t)n * 4));
+  unsigned int *skey_b = nullptr; void *sort_tmp = nullptr; size_t sort_bytes = 0;
+  BIGCHK(al((void **)&g.skey, (size_t)n * 4)); BIGCHK(al((void **)&skey_b, (size_t)n * 4)); BIGCHK(al((void **)&g.sval, (size_t)n * 4)); BIGCHK(al((void **)&g.perm, (size_t)n * 4));
+  if (n > 0) {
+    BIGCHK(sort_pairs_u32(nullptr, sort_bytes, g.skey, skey_b, g.sval, g.perm, (size_t)n, 32u, st));
+    BIGCHK(al(&sort_tmp, sort_bytes + 256));
+  }
+  BIGCHK(al((void **)&g.cnt, GCNT_N * sizeof(int))); BIGCHK(al((void **)&g.poses, (size_t)W * 12 * 8)); BIGCHK(al((void **)&g.offsets, (size_t)(W + 1) * 4));
+  BIGCHK(hipMemcpyAsync(g.poses, poses, (size_t)W * 12 * 8, hipMemcpyHostToDevice, st));
+  BIGCHK(hipMemcpyAsync(g.offsets, offsets, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, st));
+  int cap = s.last_cap;                          // (the node capacity the previous build ended with: no doubling attempts, each of which re-clears the tables)
+  const dim3 bk(256), gp((n + 255) / 256);
+  for (int attempt = 0; attempt < 10; attempt++) {
+    const size_t cp = (size_t)cap;
+    g.cap = cap;
+    void *tmp[9];
+    size_t sz[9] = {10 * cp * 8, 3 * cp * 8, 3 * cp * 8, 9 * cp * 8, cp * 4, cp * 4, cp * 4, cp * 4, cp};
+    for (int k = 0; k < 9; k++) { if (s.arena(&tmp[k], sz[k]) != hipSuccess) { err = "octree node storage"; return VBA_ERR_HIP; } }
+    g.nadd = (double *)tmp[0]; g.ncenter = (double *)tmp[1]; g.neval = (double *)tmp[2]; g.nevec = (double *)tmp[3]; g.nql = (float *)tmp[4];
+    g.nchild = (int *)tmp[5]; g.nfac = (int *)tmp[6]; g.nexi = (int *)tmp[7]; g.nlayer = (signed char *)tmp[8];
+    BIGCHK(hipMemsetAsync(g.cnt, 0, GCNT_N * sizeof(int), st));
+    BIGCHK(hipMemsetAsync(g.hkeys, 0xFF, (size_t)hcap * 8, st));
+    BIGCHK(hipMemsetAsync(g.nadd, 0, 10 * cp * 8, st));
+    BIGCHK(hipMemsetAsync(g.nexi, 0, cp * 4, st));
+    if (n > 0) {
+      hipLaunchKernelGGL(k_gbab_keys, gp, bk, 0, st, g, P);
+      hipLaunchKernelGGL(k_gbab_roots, dim3((hcap + 4095) / 4096), bk, 0, st, g, P);
+      hipLaunchKernelGGL(k_gbab_rootid, gp, bk, 0, st, g);
+      {
+        unsigned int bits = 1; while (bits < 32 && (1ull << bits) <= (unsigned long long)cap) bits++;     // keys are <= cap
+        size_t tb = sort_bytes + 256;
+        BIGCHK(sort_pairs_u32(sort_tmp, tb, g.skey, skey_b, g.sval, g.perm, (size_t)n, bits, st));
+      }
+      for (int L = 0; L <= P.max_layer; L++) {
+        // entries of the previous level are dead: a planar node keeps its own entries (it stopped descending), so the
+        // table is only cleared of nothing here — finished nodes never receive points again and their keys stay valid
+        if (L == 0) {   // (a fill kernel: the runtime's memset moved the 5.4 GB of an 8 M-point window at 750 GB/s, 7.2 ms a time)
+          hipLaunchKernelGGL(k_fill_u64, dim3(4096), dim3(256), 0, st, g.ekeys, ~0ull, (size_t)ecap);
+          hipLaunchKernelGGL(k_fill_u64, dim3(4096), dim3(256), 0, st, (unsigned long long *)g.ecl, 0ull, (size_t)ecap * 10);
+        }
+        hipLaunchKernelGGL(k_gbab_accum, gp, bk, 0, st, g);
+        hipLaunchKernelGGL(k_gbab_decide, dim3((cap + 255) / 256), bk, 0, st, g, P, L);
+        if (L < P.max_layer) hipLaunchKernelGGL(k_gbab_descend, gp, bk, 0, st, g);
+      }
+    }
+    BIGCHK(hipGetLastError());
+    BIGCHK(hipStreamSynchronize(st));
+    BIGCHK(hipMemcpyAsync(s.h_cnt, g.cnt, GCNT_N * sizeof(int), hipMemcpyDeviceToHost, st));
+    BIGCHK(hipStreamSynchronize(st));
+    if (s.h_cnt[GCNT_OVERFLOW] == 2) { err = "keyframe point outside the 21-bit voxel index range"; return VBA_ERR_CAPACITY; }
+    if (!s.h_cnt[GCNT_OVERFLOW]) { s.last_cap = cap; break; }
+    // (the undersized node arrays stay in the arena until the next build rewinds it)
+    cap *= 2;
+    if (attempt == 9) { err = "octree node capacity"; return VBA_ERR_CAPACITY; }
+  }
+  // sparse factor store
+  BigView &b = s.b;
+  const int V = s.h_cnt[GCNT_FACTORS];
+  b.W = W; b.V = V; b.capV = V > 0 ? V : 1;
+  BIGCHK(al((void **)&b.vptr, (size_t)(V + 1) * 4)); BIGCHK(al((void **)&s.d_vcnt, (size_t)b.capV * 4)); BIGCHK(al((void **)&s.d_fill, (size_t)b.capV * 4));
+  BIGCHK(al((void **)&b.eval, (size_t)b.capV * 3 * 8)); BIGCHK(al((void **)&b.evec, (size_t)b.capV * 9 * 8)); BIGCHK(al((void **)&b.pcr, (size_t)b.capV * 10 * 8));
+  BIGCHK(al((void **)&b.poses, (size_t)W * 12 * 8));
+  const size_t n6 = (size_t)6 * W;
+  BIGCHK(al((void **)&b.H, n6 * n6 * 8)); BIGCHK(al((void **)&b.g, n6 * 8)); BIGCHK(al((void **)&b.r, 8));
+
+  s.NP = (int)((n6 + 7) / 8 * 8); s.ld = (int)((s.NP + 63) / 64 * 64);
+  BIGCHK(al((void **)&s.d_Ab, (size_t)(s.NP + 1) * s.ld * 8)); BIGCHK(al((void **)&s.d_Tb, (size_t)(s.NP + 1) * 8 * 8)); BIGCHK(al((void **)&s.d_ord, n6 * 4)); BIGCHK(al((void **)&s.d_vec, ((size_t)3 * n6 + (size_t)6 * W * W) * 8));
+  BIGCHK(hipMemsetAsync(s.d_fill, 0, (size_t)b.capV * 4, st));
+  BIGCHK(hipMemsetAsync(b.vptr, 0, (size_t)(V + 1) * 4, st));
+  int E = 0;
+  if (V > 0) {
+    const int nn = s.h_cnt[GCNT_NODES] < g.cap ? s.h_cnt[GCNT_NODES] : g.cap;
+    hipLaunchKernelGGL(k_gbab_vcount, dim3((nn + 255) / 256), bk, 0, st, g, s.d_vcnt);
+    hipLaunchKernelGGL(k_big_scan, dim3(1), bk, 0, st, V, s.d_vcnt, b.vptr);
+    BIGCHK(hipStreamSynchronize(st));
+    BIGCHK(hipMemcpyAsync(&E, b.vptr + V, 4, hipMemcpyDeviceToHost, st));
+    BIGCHK(hipStreamSynchronize(st));
+  }
+  b.E = E; b.capE = E > 0 ? E : 1;
+  BIGCHK(al((void **)&b.efr, (size_t)b.capE * 4)); BIGCHK(al((void **)&b.evox, (size_t)b.capE * 4));
+  BIGCHK(al((void **)&b.ecl, (size_t)b.capE * 10 * 8)); BIGCHK(al((void **)&b.gv, (size_t)b.capE * 18 * 8)); BIGCHK(al((void **)&b.es, (size_t)b.capE * 27 * 8));
+  if (V > 0) {
+    const int nn = s.h_cnt[GCNT_NODES] < g.cap ? s.h_cnt[GCNT_NODES] : g.cap;
+    hipLaunchKernelGGL(k_gbab_fill, dim3((ecap + 255) / 256), bk, 0, st, g, b, s.d_fill);
+    hipLaunchKernelGGL(k_gbab_voxels, dim3((nn + 255) / 256), bk, 0, st, g, b);
+    BIGCHK(hipGetLastError());
+  }
+  BIGCHK(al((void **)&b.eidx, (size_t)b.capV * W * 4));
+  BIGCHK(hipMemsetAsync(b.eidx, 0xFF, (size_t)b.capV * W * 4, st));
+  if (V > 0 && E > 0) {
+    hipLaunchKernelGGL(k_big_eidx, dim3((E + 255) / 256), bk, 0, st, b);
+    BIGCHK(hipGetLastError());
+  }
+  return VBA_OK;
+}
+
+// divide_thread (VM:347-389): H, g, r at `poses` on the host side buffers (full layout)
+// Hessian pass on the sparse store: H (n x n) and g stay in HBM (the solver reads them there); the host gets diag(H), g and r.
+inline int big_hessian(BigStore &s, hipStream_t st, const double *poses, double *hdiag, double *gvec, double *r, std::string &err) {
+  BigView &b = s.b;
+  const size_t n6 = (size_t)6 * b.W;
+  BIGCHK(hipMemcpyAsync(b.poses, poses, (size_t)b.W * 12 * 8, hipMemcpyHostToDevice, st));
+  BIGCHK(hipMemsetAsync(b.H, 0, n6 * n6 * 8, st)); BIGCHK(hipMemsetAsync(b.g, 0, n6 * 8, st)); BIGCHK(hipMemsetAsync(b.r, 0, 8, st));
+  if (b.E > 0) {
+    hipLaunchKernelGGL(k_big_slot, dim3((b.E + 127) / 128), dim3(128), 0, st, b);
+    const int nt = (b.W + BIG_TF - 1) / BIG_TF, npair = nt * (nt + 1) / 2, nchunk = (b.V + BIG_VC - 1) / BIG_VC;
+    int nslice = (2048 + npair - 1) / npair;
+    if (nslice > nchunk) nslice = nchunk;
+    if (nslice < 1) nslice = 1;
+    hipLaunchKernelGGL(k_big_syrk, dim3(npair, nslice), dim3(256), 0, st, b, nt, nslice);
+    hipLaunchKernelGGL(k_big_diag, dim3(b.W), dim3(256), 0, st, b);   // after the SYRK atomics on H (stream order)
+  }
+  hipLaunchKernelGGL(k_big_getdiag, dim3((unsigned)((n6 + 255) / 256)), dim3(256), 0, st, b.H, (int)n6, s.d_vec);
+  BIGCHK(hipGetLastError());
+  BIGCHK(hipStreamSynchronize(st));
+  BIGCHK(hipMemcpyAsync(hdiag, s.d_vec, n6 * 8, hipMemcpyDeviceToHost, st));
+  BIGCHK(hipMemcpyAsync(gvec, b.g, n6 * 8, hipMemcpyDeviceToHost, st));
+  BIGCHK(hipMemcpyAsync(r, b.r, 8, hipMemcpyDeviceToHost, st));
+  BIGCHK(hipStreamSynchronize(st));
+  return VBA_OK;
+}
+// the six diagonal entries of every 6x6 cross block of the Hessian of the last big_hessian (before the gauge): [W][W][6]
+inline int big_block_diagonals(BigStore &s, hipStream_t st, double *out, std::string &err) {
+  const int W = s.b.W;
+  const size_t n6 = (size_t)6 * W, cnt = (size_t)6 * W * W;
+  hipLaunchKernelGGL(k_big_blockdiag, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, s.b.H, W, s.d_vec + 3 * n6);
+  BIGCHK(hipGetLastError());
+  BIGCHK(hipStreamSynchronize(st));
+  BIGCHK(hipMemcpyAsync(out, s.d_vec + 3 * n6, cnt * 8, hipMemcpyDeviceToHost, st));
+  BIGCHK(hipStreamSynchronize(st));
+  return VBA_OK;
+}
+// only_residual (VM:391-420): also refreshes the per-voxel eigen state
+inline int big_residual(BigStore &s, hipStream_t st, const double *poses, double *r, std::string &err) {
+  BigView &b = s.b;
+  BIGCHK(hipMemcpyAsync(b.poses, poses, (size_t)b.W * 12 * 8, hipMemcpyHostToDevice, st));
+  BIGCHK(hipMemsetAsync(b.r, 0, 8, st));
+  if (b.V > 0) hipLaunchKernelGGL(k_big_residual, dim3((b.V + 255) / 256), dim3(256), 0, st, b);
+  BIGCHK(hipGetLastError());
+  BIGCHK(hipStreamSynchronize(st));
+  BIGCHK(hipMemcpyAsync(r, b.r, 8, hipMemcpyDeviceToHost, st));
+  BIGCHK(hipStreamSynchronize(st));
+  return VBA_OK;
+}
+
+// Eigen's LDLT pivot order for (H + u D): largest |stored diagonal| first, first index wins ties.  hd = diag(H) after the gauge.
+void big_pivot_order(const double *hd, double u, int n, int *ord) {
+  std::vector<double> dabs(n);
+  for (int r = 0; r < n; r++) { ord[r] = r; dabs[r] = std::fabs(hd[r] + u * hd[r]); }
+  std::stable_sort(ord, ord + n, [&](int a, int b) { return dabs[a] > dabs[b]; });
+}
+// the model decrease q1 = 0.5 dx^T (u D dx - g) of VM:465 (hd, g after the gauge), summed in row order
+double big_q1(const double *dxi, const double *hd, const double *g, double u, int n) {
+  double q1 = 0;
+  for (int r = 0; r < n; r++) q1 += dxi[r] * (u * hd[r] * dxi[r] - g[r]);
+  return 0.5 * q1;
+}
+
+// (H + u D) dxi = -g with the gauge of VM:452-455, H / g = the device buffers of the last big_hessian (before the gauge).
+// ord = Eigen's pivot order (host).  Factorisation and back substitution run on the device; the host gets dxi (n doubles).
+int big_solve(BigStore &s, hipStream_t st, const int *ord, double u, double *dxi, std::string &err) {
+  const int n = 6 * s.b.W, NP = s.NP, ld = s.ld;
+  BIGCHK(hipMemcpyAsync(s.d_ord, ord, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  const long long tot = (long long)(NP + 1) * NP;
+  hipLaunchKernelGGL(k_bigl_setup, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, s.b.H, s.b.g, s.d_ord, n, NP, ld, u, s.d_Ab);
+  for (int k0 = 0; k0 < NP; k0 += 8) {
+    hipLaunchKernelGGL(k_bigl_panel, dim3(1), dim3(256), 0, st, s.d_Ab, s.d_Tb, NP, ld, k0);
+    const int kn = k0 + 8;
+    if (kn <= NP) {
+      const int nt = (NP + 1 - kn + 63) / 64;
+      if (nt > 0) hipLaunchKernelGGL(k_bigl_update, dim3(nt * (nt + 1) / 2), dim3(256), 0, st, s.d_Ab, s.d_Tb, NP, ld, k0);
+    }
+  }
+  // back substitution on the device, 64 unknowns per step from the bottom
+  for (int lo = ((n - 1) / 64) * 64; lo >= 0; lo -= 64) {
+    hipLaunchKernelGGL(k_bigl_bs_tri, dim3(1), dim3(64), 0, st, s.d_Ab, NP, ld, n, lo);
+    if (lo > 0) hipLaunchKernelGGL(k_bigl_bs_gemv, dim3((lo + 255) / 256), dim3(256), 0, st, s.d_Ab, NP, ld, n, lo);
+  }
+  double *d_dxi = s.d_vec + 2 * (size_t)n;
+  hipLaunchKernelGGL(k_bigl_bs_out, dim3((n + 255) / 256), dim3(256), 0, st, s.d_Ab, NP, ld, n, s.d_ord, d_dxi);
+  BIGCHK(hipGetLastError());
+  BIGCHK(hipStreamSynchronize(st));
+  BIGCHK(hipMemcpyAsync(dxi, d_dxi, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  BIGCHK(hipStreamSynchronize(st));
+  return VBA_OK;
+}
+
+}  // namespace vba
+
+extern "C" {
+
+// ---------------------------------------------------------------- the entry points
+static GbaParams gba_params(vba_ctx *c, double voxel_size, double min_eig, const double *eig_array) {
+  GbaParams P;
+  P.voxel_size = voxel_size; P.min_eigen_value = min_eig; P.max_layer = c->opt.max_layer;
+  for (int k = 0; k < 4; k++) P.eig_array[k] = eig_array[k];
+  return P;
+}
+static int gba_build_into_store(vba_ctx *c, int wdsize, const int *offsets, const double *pl, const double *poses, const GbaParams &P) {
+  int nf = 0;
+  TimedSpan sp{};
+  span_begin(c, "gba_build", sp);
+  int st = gba_build(c->gba, c->stream, wdsize, offsets, pl, poses, P, &nf, c->err);
+  if (st) return st;
+  c->nvox = 0;
+  st = factor_reserve(c, nf > 0 ? nf : 1);
+  if (st) return st;
+  if (nf > 0) {
+    const int nn = c->gba.h_cnt[GCNT_NODES] < c->gba.v.cap ? c->gba.h_cnt[GCNT_NODES] : c->gba.v.cap;
+    hipLaunchKernelGGL(k_gba_extract, dim3((nn + 255) / 256, 10 * wdsize + 33), dim3(256), 0, c->stream, c->gba.v, c->fv);
+    factor_update_mask(c, 0, nf);
+    HIPCHK(c, hipGetLastError());
+  }
+  span_end(c, "gba_build", sp);
+  c->nvox = nf;
+  return VBA_OK;
+}
+static int gba_check(vba_ctx *c, int wdsize, const int *offsets, const double *pl, const double *poses) {
+  if (wdsize != c->opt.win_size) return VBA_ERR_UNSUPPORTED_WINDOW;
+  if (!offsets || !poses || offsets[0] != 0) return VBA_ERR_BAD_ARG;
+  for (int i = 0; i < wdsize; i++) if (offsets[i + 1] < offsets[i]) return VBA_ERR_BAD_ARG;
+  if (offsets[wdsize] > 0 && !pl) return VBA_ERR_BAD_ARG;
+  return VBA_OK;
+}
+int vba_gba_build(vba_ctx *c, int wdsize, const int *offsets, const double *pnt_local, const double *poses, double gba_voxel_size,
+                  double gba_min_eigen_value, const double *gba_eigen_value_array) {
+  int st = gba_check(c, wdsize, offsets, pnt_local, poses);
+  if (st) return st;
+  if (!gba_eigen_value_array) return VBA_ERR_BAD_ARG;
+  return gba_build_into_store(c, wdsize, offsets, pnt_local, poses, gba_params(c, gba_voxel_size, gba_min_eigen_value, gba_eigen_value_array));
+}
+
+// Lidar_BA_Optimizer::damping_iter (VM:422-497) for an arbitrary window: device Hessian / residual passes on the sparse
+// store, gauge + (H + uD) LDL^T + retraction on the host.
+// hdiag6_out: [W][W][6] = the six diagonal entries of every 6x6 block of *hess (all that HBA_add_edge reads of it, VS:2926-2951);
+// the n x n Hessian itself stays in HBM.
+static int big_damping_iter(vba_ctx *c, int W, double *poses, std::vector<double> &hdiag6_out, double *resis2, int max_iter, int thd_num, int *is_converge) {
+  BigStore &S = c->big;
+  const int n = 6 * W;
+  if (S.b.V < thd_num) return VBA_ERR_TOO_FEW_VOXELS;                 // VM:399-403
+  std::vector<double> x(poses, poses + (size_t)W * 12), xt(x), hd(n), JacT(n), dxi(n);
+  double u = 0.01, v = 2, residual1 = 0, residual2 = 0;
+  bool is_calc_hess = true, conv = true;
+  c->trace.clear();
+  for (int it = 0; it < max_iter; it++) {
+    if (is_calc_hess) {
+      int st = big_hessian(S, c->stream, x.data(), hd.data(), JacT.data(), &residual1, c->err);   // *hess = Hess (VM:446) stays on the device
+      if (st) return st;
+      for (int r = 0; r < 6; r++) { hd[r] = 1.0; JacT[r] = 0.0; }     // gauge VM:452-455 (k_bigl_setup applies it to the matrix)
+    }
+    if (it == 0) resis2[0] = residual1;
+    {
+      // pivot order of Eigen's LDLT (largest |stored diagonal| first, first index wins ties), then the device factorisation
+      std::vector<int> ord(n);
+      big_pivot_order(hd.data(), u, n, ord.data());
+      int st2 = big_solve(S, c->stream, ord.data(), u, dxi.data(), c->err);
+      if (st2) return st2;
+    }
+    for (int j = 0; j < W; j++) {
+      double E[9];
+      vbh::so3_exp(&dxi[6 * j], E);
+      vbh::m3_mul(&x[12 * j], E, &xt[12 * j]);
+      for (int k = 0; k < 3; k++) xt[12 * j + 9 + k] = x[12 * j + 9 + k] + dxi[6 * j + 3 + k];
+    }
+    const double q1 = big_q1(dxi.data(), hd.data(), JacT.data(), u, n);
+    int st = big_residual(S, c->stream, xt.data(), &residual2, c->err);
+    if (st) return st;
+    double q = residual1 - residual2;
+    const double tr[5] = {residual1, residual2, u, v, q1};
+    c->trace.insert(c->trace.end(), tr, tr + 5);
+    if (q > 0) {
+      x = xt;
+      q = q / q1;
+      v = 2;
+      q = 1 - std::pow(2 * q - 1, 3);
+      u *= (q < 1.0 / 3 ? 1.0 / 3 : q);
+      is_calc_hess = true;
+    } else {
+      u = u * v; v = 2 * v;
+      is_calc_hess = false; conv = false;
+    }
+    if (std::fabs((residual1 - residual2) / residual1) < 1e-6) break;
+  }
+  resis2[1] = residual2;
+  std::memcpy(poses, x.data(), x.size() * sizeof(double));
+  if (is_converge) *is_converge = conv ? 1 : 0;
+  hdiag6_out.resize((size_t)6 * W * W);
+  return big_block_diagonals(S, c->stream, hdiag6_out.data(), c->err);   // b.H still holds the last evaluated Hessian (a rejected step does not recompute it)
+}
+
+int vba_hba_add_edge(vba_ctx *c, int wdsize, const int *offsets, const double *pnt_local, double *poses, double gba_voxel_size,
+                     double gba_min_eigen_value, const double *gba_eigen_value_array, int max_iter, int thread_num, double *edges_out, int *n_edges,
+                     double *cloud_out, int *cloud_count, int *n_cloud, double *resis_log, int *n_log) {
+  const bool big = (wdsize != c->opt.win_size);      // any other window size (the top-level BA over all submaps): sparse path
+  if (big && wdsize < 2) return VBA_ERR_BAD_ARG;
+  int st = VBA_OK;
+  if (!big) st = gba_check(c, wdsize, offsets, pnt_local, poses);
+  else {
+    if (!offsets || !poses || offsets[0] != 0) return VBA_ERR_BAD_ARG;
+    for (int i = 0; i < wdsize; i++) if (offsets[i + 1] < offsets[i]) return VBA_ERR_BAD_ARG;
+    if (offsets[wdsize] > 0 && !pnt_local) return VBA_ERR_BAD_ARG;
+  }
+  if (st) return st;
+  if (!gba_eigen_value_array || !edges_out || !n_edges || (cloud_out && (!cloud_count || !n_cloud))) return VBA_ERR_BAD_ARG;
+  const int W = wdsize, n6 = 6 * W, n = offsets[W];
+  *n_edges = 0;
+  if (n_log) *n_log = 0;
+  static const bool want_times = diag_env("VBA_HBA_TIMES") != nullptr;      // diagnostic: wall-clock split of the call on stderr
+  double t_ph[5] = {0, 0, 0, 0, 0};
+  auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  double t_mark = want_times ? now() : 0.0;
+  auto lap = [&](int k) { if (want_times) { hipStreamSynchronize(c->stream); const double t = now(); t_ph[k] += t - t_mark; t_mark = t; } };
+  // the keyframe clouds stay in HBM for the whole call (every outer iteration re-cuts them with the current poses)
+  if ((size_t)n * 3 > c->refpts_doubles) {
+    if (c->d_refpts) hipFree(c->d_refpts);
+    c->refpts_doubles = (size_t)n * 3 + 3072;
+    HIPCHK(c, hipMalloc((void **)&c->d_refpts, 2 * c->refpts_doubles * sizeof(double)));
+  }
+  double *d_pl = c->d_refpts, *d_ref = c->d_refpts + c->refpts_doubles;
+  if (n > 0) HIPCHK(c, hipMemcpyAsync(d_pl, pnt_local, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
+  GbaParams P = gba_params(c, gba_voxel_size, gba_min_eigen_value, gba_eigen_value_array);
+  std::vector<double> hess(big ? 0 : (size_t)n6 * n6, 0.0), hd6;      // the any-window path keeps *hess in HBM and returns its block diagonals
+  lap(0);
+  const int up = 4;                                                       // VS:2866
+  int converge_flag = 0;
+  double converge_thre = 0.05;
+  for (int iterCnt = 0; iterCnt < max_iter; iterCnt++) {
+    if (converge_flag == 1 || iterCnt == max_iter - 1)                    // VS:2871-2881: last pass with the local-map parameters
+      P = gba_params(c, c->opt.voxel_size, c->opt.min_eigen_value, c->opt.plane_eigen_value_thre);
+    double resis[2] = {0, 0};
+    int is_converge = 0;
+    if (!big) {
+      st = gba_build_into_store(c, W, offsets, d_pl, poses, P);
+      if (st) return st;
+      lap(1);
+      st = vba_lidar_ba_damping_iter(c, poses, hess.data(), resis, up, thread_num, &is_converge);
+    } else {
+      st = big_build(c->big, c->stream, W, offsets, d_pl, poses, P, c->err);
+      if (st) return st;
+      lap(1);
+      st = big_damping_iter(c, W, poses, hd6, resis, up, thread_num, &is_converge);
+    }
+    if (st) return st;
+    lap(2);
+    if (resis_log && n_log) { resis_log[2 * *n_log] = resis[0]; resis_log[2 * *n_log + 1] = resis[1]; (*n_log)++; }
+    if ((std::fabs(resis[0] - resis[1]) / resis[0] < converge_thre && is_converge) || (iterCnt == max_iter - 2 && converge_flag == 0)) {
+      converge_thre = 0.01;                                               // VS:2903-2915
+      if (converge_flag == 0) converge_flag = 1;
+      else if (converge_flag == 1) break;
+    }
+  }
+  int ne = 0;
+  for (int i = 0; i < W - 1; i++)
+    for (int j = i + 1; j < W; j++) {                                     // VS:2926-2951
+      bool isAdd = true;
+      double v6[6];
+      for (int k = 0; k < 6; k++) {
+        const double hc = std::fabs(big ? hd6[((size_t)i * W + j) * 6 + k] : hess[(size_t)(6 * i + k) * n6 + 6 * j + k]);
+        if (hc < 1e-6) { isAdd = false; break; }
+        v6[k] = 1.0 / hc;
+      }
+      if (!isAdd) continue;
+      double *o = edges_out + 20 * (size_t)ne++;
+      const double *Ri = poses + 12 * i, *Rj = poses + 12 * j;
+      o[0] = i; o[1] = j;
+      vbh::m3_Tmul(Ri, Rj, o + 2);
+      const double d[3] = {Rj[9] - Ri[9], Rj[10] - Ri[10], Rj[11] - Ri[11]};
+      vbh::m3_Tvec(Ri, d, o + 11);
+      for (int k = 0; k < 6; k++) o[14 + k] = v6[k];
+    }
+  *n_edges = ne;
+  lap(3);
+  if (cloud_out) {                                                        // VS:2954-2989
+    *n_cloud = 0;
+    if (n > 0) {
+      std::vector<double> rel((size_t)W * 12);
+      for (int i = 0; i < W; i++) {
+        const double *R0 = poses, *Ri = poses + 12 * i;
+        vbh::m3_Tmul(R0, Ri, rel.data() + 12 * i);
+        const double d[3] = {Ri[9] - R0[9], Ri[10] - R0[10], Ri[11] - R0[11]};
+        vbh::m3_Tvec(R0, d, rel.data() + 12 * i + 9);
+      }
+      double *d_rel = big ? c->big.g.poses : c->gba.v.poses;
+      const int *d_off = big ? c->big.g.offsets : c->gba.v.offsets;
+      HIPCHK(c, hipMemcpyAsync(d_rel, rel.data(), rel.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+      hipLaunchKernelGGL(k_gba_to_ref, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, W, d_off, d_pl, d_rel, d_ref);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipStreamSynchronize(c->stream));      // rel is a host temporary
+      std::vector<int> first(n);
+      st = vba_scan_down_sampling_voxel(c, n, d_ref, c->opt.voxel_size / 8, cloud_out, cloud_count, first.data(), n_cloud);
+      if (st) return st;
+    }
+  }
+  lap(4);
+  if (want_times)
+    std::fprintf(stderr, "[hba_add_edge W=%d n=%d] upload %.0f  build %.0f  LM %.0f  edges %.0f  cloud %.0f us\n", W, n, t_ph[0], t_ph[1], t_ph[2], t_ph[3], t_ph[4]);
+  return VBA_OK;
+}
+
+// thd_globalmapping (VS:3018-3141), the optimisation work of the hierarchical global BA over one map:
+//   bottom layer  windows of `wdsize` keyframes, stride `mgsize` (VS:3033-3034, 3064-3066, 3136-3137): HBA_add_edge(xs = x0 of the
+//                 window, max_iter 1, thread_num 2) -> edges1 + one submap (pose x0 of the window's first keyframe, cloud
+//                 = the window's down-sampled points in that frame, VS:3084-3089);
+//   top layer     HBA_add_edge over all submaps with their CURRENT poses (VS:3096-3110): edges2.
+// Edge rows carry GLOBAL keyframe indices.  (Queue handling, map switching and the GTSAM pose graph stay with the caller.)
+int vba_hba_global(vba_ctx *c, int n_kf, const int *offsets, const double *pnt_local, const double *poses_x0, const double *poses_now,
+                   double gba_voxel_size, double gba_min_eigen_value, const double *gba_eigen_value_array, int total_max_iter, int wdsize, int mgsize,
+                   double *edges1_out, int cap1, int *n_edges1, double *edges2_out, int cap2, int *n_edges2) {
+  if (n_kf < 0 || wdsize < 2 || mgsize < 1 || !offsets || !poses_x0 || !poses_now || !gba_eigen_value_array || !n_edges1 || !n_edges2 ||
+      (offsets[n_kf] > 0 && !pnt_local))
+    return VBA_ERR_BAD_ARG;
+  *n_edges1 = 0; *n_edges2 = 0;
+  std::vector<int> sub_first, sub_n;                // global id of every submap's first keyframe, points of its cloud
+  std::vector<double> edges((size_t)(wdsize * (wdsize - 1) / 2 + 1) * 20);
+  // the keyframe clouds go to HBM once (the stride-5 windows overlap: every keyframe is used twice) and the submap clouds
+  // never leave it: every window's down-sampled cloud is written behind the previous one and the top-level BA reads them there
+  const size_t n_all = (size_t)offsets[n_kf];
+  size_t n_sub_cap = 0, n_win_max = 0;
+  for (int start = 0; start + wdsize <= n_kf; start += mgsize) {
+    const size_t nw = (size_t)(offsets[start + wdsize] - offsets[start]);
+    n_sub_cap += nw; if (nw > n_win_max) n_win_max = nw;
+  }
+  // More than one rank ("windows are independent problems => replicas across GPUs for the bottom layer"): window
+  // wi is optimised by rank wi % n_ranks with the exchange step switched off; every rank packs its windows' clouds and its
+  // [points, edges, status | edge rows] records into ITS chunk of two buffers, and one ALL-GATHER of each hands every rank all of
+  // them (a rank receives each foreign byte once).  A window that fails on one rank travels as its status word: every rank
+  // enters both collectives and all of them return the same error afterwards — no rank is left waiting in a collective.
+  // The top-level window then runs replicated (identical inputs on every rank).
+  const bool replicas = c->collective() && c->n_ranks > 1;
+  int n_win = 0;
+  for (int start = 0; start + wdsize <= n_kf; start += mgsize) n_win++;
+  // ONE rank: the windows are independent problems too, and one window is a chain of small kernels and host round trips that leaves
+  // most of the chip idle — KL worker contexts (own stream, own octree and LM state; host threads drive them) optimise windows
+  // side by side, with the bookkeeping of the replicas: worker t takes windows t, t + KL, ... and writes their clouds into its chunk.
+  const int kl_opt = c->opt.hba_workers > 0 ? (c->opt.hba_workers < 8 ? c->opt.hba_workers : 8) : 4;
+  const int KL = (!replicas && n_win >= 2 * kl_opt) ? kl_opt : 1;
+  const bool local_rep = KL > 1, chunked = replicas || local_rep;
+  const int NR = replicas ? c->n_ranks : KL;
+  const size_t meta_per = 3 + (size_t)(wdsize * (wdsize - 1) / 2) * 20;
+  const size_t win_per_rank = chunked ? (size_t)(n_win + NR - 1) / NR : 0, meta_chunk = meta_per * win_per_rank;
+  std::vector<size_t> rank_cap(NR, 0), win_roff(n_win > 0 ? n_win : 1, 0);      // points capacity per rank chunk, window offset inside it
+  if (chunked) {
+    int w = 0;
+    for (int start = 0; start + wdsize <= n_kf; start += mgsize, w++) {
+      win_roff[w] = rank_cap[w % NR];
+      rank_cap[w % NR] += (size_t)(offsets[start + wdsize] - offsets[start]);
+    }
+  }
+  size_t chunk_pts = 0;
+  for (int r = 0; r < NR; r++) if (rank_cap[r] > chunk_pts) chunk_pts = rank_cap[r];
+  if (!chunked) chunk_pts = 0;
+  const size_t need = (n_all + n_sub_cap + (size_t)NR * chunk_pts) * 3 + (size_t)NR * meta_chunk + 64;
+  if (need > c->hba_all_doubles) {
+    if (c->d_hba_all) hipFree(c->d_hba_all);
+    c->d_hba_all = nullptr; c->hba_all_doubles = 0;
+    HIPCHK(c, hipMalloc((void **)&c->d_hba_all, need * sizeof(double)));
+    c->hba_all_doubles = need;
+  }
+  double *d_all = c->d_hba_all, *d_sub = c->d_hba_all + n_all * 3;
+  if (n_all > 0 && !local_rep) HIPCHK(c, hipMemcpyAsync(d_all, pnt_local, n_all * 3 * sizeof(double), hipMemcpyDefault, c->stream));   // (the worker path uploads in chunks, under the first windows)
+  std::vector<int> ccnt(n_win_max > 0 ? n_win_max : 1);
+  size_t sub_off = 0;
+  double *d_rep = d_sub + n_sub_cap * 3, *d_meta = d_rep + (size_t)NR * chunk_pts * 3;      // replica mode only
+  std::vector<double> meta((size_t)NR * meta_chunk, 0.0);
+  struct Restore { vba_ctx *c; bool was; ~Restore() { c->collective_off = was; } } restore{c, c->collective_off};
+  if (replicas) c->collective_off = true;                                       // the windows' own LM loops must not enter a collective
+  int wi = -1;
+  static const bool want_times = diag_env("VBA_HBA_TIMES") != nullptr;
+  auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  const double t_g0 = want_times ? (hipStreamSynchronize(c->stream), now()) : 0.0;
+  double t_g1 = 0;
+  if (local_rep) {
+    while ((int)c->hba_workers.size() < KL - 1) {
+      vba_options o = c->opt; o.stream = nullptr; o.device = c->device;
+      vba_ctx *w = nullptr;
+      const int stc = vba_create(&o, &w);
+      if (stc) { c->set_error("vba_hba_global: could not create a worker context"); return stc; }
+      c->hba_workers.push_back(w);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int w = 0; w < n_win; w++) meta[(size_t)(w % KL) * meta_chunk + meta_per * (size_t)(w / KL) + 2] = -1.0;   // "not run"
+    std::vector<std::string> werr(KL);
+    // the keyframe clouds travel to HBM in chunks on a stream of their own while the first windows are already being optimised
+    // (2.4 GB at full length: as long as the windows themselves); a window starts when its keyframes have arrived
+    std::atomic<int> kf_ready{0}, give_up{0};
+    auto work = [&](int tw) {
+      vba_ctx *cx = tw == 0 ? c : c->hba_workers[tw - 1];
+      hipSetDevice(c->device);
+      std::vector<double> ed(edges.size());
+      std::vector<int> cc(ccnt.size()), off(wdsize + 1);
+      for (int w = tw; w < n_win; w += KL) {
+        const int start = w * mgsize;
+        while (kf_ready.load(std::memory_order_acquire) < start + wdsize && !give_up.load()) std::this_thread::sleep_for(std::chrono::microseconds(20));
+        if (give_up.load()) return;
+        for (int i = 0; i <= wdsize; i++) off[i] = offsets[start + i] - offsets[start];
+        std::vector<double> xs(poses_x0 + (size_t)start * 12, poses_x0 + (size_t)(start + wdsize) * 12);
+        int ne = 0, nc = 0;
+        double *mrec = &meta[(size_t)tw * meta_chunk + meta_per * (size_t)(w / KL)];
+        const int st = vba_hba_add_edge(cx, wdsize, off.data(), d_all + (size_t)offsets[start] * 3, xs.data(), gba_voxel_size, gba_min_eigen_value,
+                                        gba_eigen_value_array, 1, 2, ed.data(), &ne, d_rep + ((size_t)tw * chunk_pts + win_roff[w]) * 3,
+                                        cc.data(), &nc, nullptr, nullptr);
+        mrec[2] = st;
+        if (st != VBA_OK) { werr[tw] = cx->err; return; }
+        mrec[0] = nc; mrec[1] = ne;
+        std::memcpy(mrec + 3, ed.data(), (size_t)ne * 20 * sizeof(double));
+      }
+    };
+    int up_status = VBA_OK;
+    {
+      std::vector<std::thread> th;
+      for (int tw = 0; tw < KL; tw++) th.emplace_back(work, tw);
+      // (one uploader: three threads staging chunks in turn moved the pageable copy no faster — 4-5 GB/s either way; at full
+      //  length the call is bound by this copy once the windows overlap it)
+      hipStream_t up = nullptr;
+      if (hipStreamCreateWithFlags(&up, hipStreamNonBlocking) != hipSuccess) { up_status = VBA_ERR_HIP; give_up.store(1); }
+      const int CH = 16;                                                           // keyframes per chunk
+      for (int k0 = 0; k0 < n_kf && up_status == VBA_OK; k0 += CH) {
+        const int k1 = k0 + CH < n_kf ? k0 + CH : n_kf;
+        const size_t o0 = (size_t)offsets[k0] * 3, nb = (size_t)(offsets[k1] - offsets[k0]) * 3 * sizeof(double);
+        if (nb > 0 && (hipMemcpyAsync(d_all + o0, pnt_local + o0, nb, hipMemcpyDefault, up) != hipSuccess || hipStreamSynchronize(up) != hipSuccess)) {
+          up_status = VBA_ERR_HIP; give_up.store(1); break;
+        }
+        kf_ready.store(k1, std::memory_order_release);
+      }
+      if (up) hipStreamDestroy(up);
+      for (auto &x : th) x.join();
+    }
+    hipSetDevice(c->device);
+    if (up_status != VBA_OK) { c->set_error("vba_hba_global: uploading the keyframe clouds failed"); return up_status; }
+    for (int w = 0; w < n_win; w++) {                                            // the first failing window in window order decides
+      const int stw = (int)meta[(size_t)(w % KL) * meta_chunk + meta_per * (size_t)(w / KL) + 2];
+      if (stw > 0) { if (!werr[w % KL].empty()) c->set_error(werr[w % KL]); return stw; }
+    }
+    for (int w = 0; w < n_win; w++) {
+      const double *mrec = &meta[(size_t)(w % KL) * meta_chunk + meta_per * (size_t)(w / KL)];
+      if ((int)mrec[2] != VBA_OK) { c->set_error("vba_hba_global: a bottom-layer window was not run"); return VBA_ERR_HIP; }
+      const int nc = (int)mrec[0], ne = (int)mrec[1], start = w * mgsize;
+      for (int e = 0; e < ne; e++) {
+        if (*n_edges1 >= cap1) return VBA_ERR_CAPACITY;
+        double *o = edges1_out + (size_t)(*n_edges1) * 20;
+        std::memcpy(o, mrec + 3 + (size_t)e * 20, 20 * sizeof(double));
+        o[0] += start; o[1] += start;
+        (*n_edges1)++;
+      }
+      if (nc > 0) HIPCHK(c, hipMemcpyAsync(d_sub + sub_off * 3, d_rep + ((size_t)(w % KL) * chunk_pts + win_roff[w]) * 3, (size_t)nc * 3 * sizeof(double),
+                                           hipMemcpyDeviceToDevice, c->stream));
+      sub_first.push_back(start);
+      sub_n.push_back(nc);
+      sub_off += (size_t)nc;
+    }
+  }
+  for (int start = 0; !local_rep && start + wdsize <= n_kf; start += mgsize) {
+    std::vector<int> off(wdsize + 1);
+    for (int i = 0; i <= wdsize; i++) off[i] = offsets[start + i] - offsets[start];
+    std::vector<double> xs(poses_x0 + (size_t)start * 12, poses_x0 + (size_t)(start + wdsize) * 12);
+    int ne = 0, nc = 0;
+    wi++;
+    if (replicas) {
+      sub_first.push_back(start);
+      if (wi % NR != c->rank) continue;
+      double *mrec = &meta[(size_t)c->rank * meta_chunk + meta_per * (size_t)(wi / NR)];
+      const int st = vba_hba_add_edge(c, wdsize, off.data(), d_all + (size_t)offsets[start] * 3, xs.data(), gba_voxel_size, gba_min_eigen_value,
+                                      gba_eigen_value_array, 1, 2, edges.data(), &ne, d_rep + ((size_t)c->rank * chunk_pts + win_roff[wi]) * 3,
+                                      ccnt.data(), &nc, nullptr, nullptr);
+      mrec[2] = st;                            // travels with the gather: every rank learns it
+      if (st == VBA_OK) {
+        mrec[0] = nc; mrec[1] = ne;
+        std::memcpy(mrec + 3, edges.data(), (size_t)ne * 20 * sizeof(double));
+      }
+      continue;
+    }
+    int st = vba_hba_add_edge(c, wdsize, off.data(), d_all + (size_t)offsets[start] * 3, xs.data(), gba_voxel_size, gba_min_eigen_value,
+                              gba_eigen_value_array, 1, 2, edges.data(), &ne, d_sub + sub_off * 3, ccnt.data(), &nc, nullptr, nullptr);
+    if (st) return st;
+    for (int e = 0; e < ne; e++) {
+      if (*n_edges1 >= cap1) return VBA_ERR_CAPACITY;
+      double *o = edges1_out + (size_t)(*n_edges1) * 20;
+      std::memcpy(o, &edges[(size_t)e * 20], 20 * sizeof(double));
+      o[0] += start; o[1] += start;
+      (*n_edges1)++;
+    }
+    sub_first.push_back(start);
+    sub_n.push_back(nc);
+    sub_off += (size_t)nc;
+  }
+  if (replicas) {
+    c->collective_off = restore.was;
+    if (meta_chunk > 0)
+      HIPCHK(c, hipMemcpyAsync(d_meta + (size_t)c->rank * meta_chunk, meta.data() + (size_t)c->rank * meta_chunk, meta_chunk * sizeof(double),
+                               hipMemcpyHostToDevice, c->stream));
+    int rc = ctx_allgather(c, d_rep, chunk_pts * 3);
+    if (rc) return rc;
+    rc = ctx_allgather(c, d_meta, meta_chunk);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(meta.data(), d_meta, meta.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int worst = VBA_OK;
+    for (int w = 0; w < n_win; w++) {
+      const int stw = (int)meta[(size_t)(w % NR) * meta_chunk + meta_per * (size_t)(w / NR) + 2];
+      if (stw != VBA_OK && worst == VBA_OK) worst = stw;
+    }
+    if (worst != VBA_OK) { c->set_error("a bottom-layer window failed on one of the ranks"); return worst; }   // the same on every rank
+    for (int w = 0; w < n_win; w++) {
+      const double *mrec = &meta[(size_t)(w % NR) * meta_chunk + meta_per * (size_t)(w / NR)];
+      const int nc = (int)mrec[0], ne = (int)mrec[1], start = sub_first[w];
+      for (int e = 0; e < ne; e++) {
+        if (*n_edges1 >= cap1) return VBA_ERR_CAPACITY;
+        double *o = edges1_out + (size_t)(*n_edges1) * 20;
+        std::memcpy(o, mrec + 3 + (size_t)e * 20, 20 * sizeof(double));
+        o[0] += start; o[1] += start;
+        (*n_edges1)++;
+      }
+      if (nc > 0) HIPCHK(c, hipMemcpyAsync(d_sub + sub_off * 3, d_rep + ((size_t)(w % NR) * chunk_pts + win_roff[w]) * 3, (size_t)nc * 3 * sizeof(double),
+                                           hipMemcpyDeviceToDevice, c->stream));
+      sub_n.push_back(nc);
+      sub_off += (size_t)nc;
+    }
+  }
+  const int ns = (int)sub_first.size();
+  if (want_times) t_g1 = now();
+  struct Report { bool on; double t0, *t1; decltype(now) *clk; ~Report() { if (on) std::fprintf(stderr, "[hba_global] windows %.0f us, top %.0f us (after the upload)\n", *t1 - t0, (*clk)() - *t1); } } report{want_times, t_g0, &t_g1, &now};
+  if (ns >= 2) {
+    std::vector<int> off(ns + 1, 0);
+    for (int i = 0; i < ns; i++) off[i + 1] = off[i] + sub_n[i];
+    std::vector<double> xs((size_t)ns * 12), e2((size_t)(ns * (ns - 1) / 2 + 1) * 20);
+    for (int i = 0; i < ns; i++) std::memcpy(&xs[(size_t)i * 12], poses_now + (size_t)sub_first[i] * 12, 12 * sizeof(double));
+    int ne = 0;
+    int st = vba_hba_add_edge(c, ns, off.data(), d_sub, xs.data(), gba_voxel_size, gba_min_eigen_value, gba_eigen_value_array, total_max_iter, 5,
+                              e2.data(), &ne, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (st) return st;
+    for (int e = 0; e < ne; e++) {
+      if (*n_edges2 >= cap2) return VBA_ERR_CAPACITY;
+      double *o = edges2_out + (size_t)(*n_edges2) * 20;
+      std::memcpy(o, &e2[(size_t)e * 20], 20 * sizeof(double));
+      o[0] = sub_first[(int)e2[(size_t)e * 20]]; o[1] = sub_first[(int)e2[(size_t)e * 20 + 1]];
+      (*n_edges2)++;
+    }
+  }
+  return VBA_OK;
+}
+
+}  // extern "C"

@@ -18,6 +18,7 @@
 #include <vector>
 #include "vba_types.hpp"
 #include "vba_common.hpp"
+#include "vba_ldlt.hpp"     // readlane_f64, v4f64_l
 
 namespace vba {
 
@@ -557,210 +558,6 @@ __global__ __launch_bounds__(256) void k_bigl_bs_gemv(double *__restrict__ Ab, i
 __global__ void k_bigl_bs_out(const double *__restrict__ Ab, int NP, int ld, int n, const int *__restrict__ ord, double *__restrict__ dxi) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dxi[ord[i]] = Ab[(size_t)NP * ld + i];
-}
-
-#define BIGCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return VBA_ERR_HIP; } } while (0)
-
-// Builds the octree of `W` keyframes and the sparse factor store (everything is re-allocated per call: the top-level BA
-// runs once per loop closure).  pl: device pointer to the local points [n][3].
-inline int big_build(BigStore &s, hipStream_t st, int W, const int *offsets, const double *d_pl, const double *poses, const GbaParams &P, std::string &err) {
-  s.reset();
-  const int n = offsets[W];
-  auto al = [&](void **p, size_t bytes) { return s.arena(p, bytes); };
-  if (!s.h_cnt) BIGCHK(hipHostMalloc((void **)&s.h_cnt, GCNT_N * sizeof(int), hipHostMallocDefault));
-  GbaBigView &g = s.g;
-  g.W = W; g.npts = n; g.pl = d_pl;
-  unsigned int hcap = 1u << 16; while (hcap < 2u * (unsigned)n && hcap < (1u << 28)) hcap <<= 1;
-  unsigned int ecap = 1u << 16;                         // (node, frame) pairs of ALL levels share the table: <= points per level
-  while ((unsigned long long)ecap < 2ull * (unsigned long long)n * (unsigned)(P.max_layer + 1) && ecap < (1u << 30)) ecap <<= 1;
-  g.hmask = hcap - 1; g.emask = ecap - 1;
-  BIGCHK(al((void **)&g.hkeys, (size_t)hcap * 8)); BIGCHK(al((void **)&g.hvals, (size_t)hcap * 4));
-  BIGCHK(al((void **)&g.ekeys, (size_t)ecap * 8)); BIGCHK(al((void **)&g.ecl, (size_t)ecap * 10 * 8));
-  BIGCHK(al((void **)&g.pw, (size_t)n * 3 * 8)); BIGCHK(al((void **)&g.pframe, (size_t)n * 4)); BIGCHK(al((void **)&g.pnode, (size_t)n * 4));
-  unsigned int *skey_b = nullptr; void *sort_tmp = nullptr; size_t sort_bytes = 0;
-  BIGCHK(al((void **)&g.skey, (size_t)n * 4)); BIGCHK(al((void **)&skey_b, (size_t)n * 4)); BIGCHK(al((void **)&g.sval, (size_t)n * 4)); BIGCHK(al((void **)&g.perm, (size_t)n * 4));
-  if (n > 0) {
-    BIGCHK(sort_pairs_u32(nullptr, sort_bytes, g.skey, skey_b, g.sval, g.perm, (size_t)n, 32u, st));
-    BIGCHK(al(&sort_tmp, sort_bytes + 256));
-  }
-  BIGCHK(al((void **)&g.cnt, GCNT_N * sizeof(int))); BIGCHK(al((void **)&g.poses, (size_t)W * 12 * 8)); BIGCHK(al((void **)&g.offsets, (size_t)(W + 1) * 4));
-  BIGCHK(hipMemcpyAsync(g.poses, poses, (size_t)W * 12 * 8, hipMemcpyHostToDevice, st));
-  BIGCHK(hipMemcpyAsync(g.offsets, offsets, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, st));
-  int cap = s.last_cap;                          // (the node capacity the previous build ended with: no doubling attempts, each of which re-clears the tables)
-  const dim3 bk(256), gp((n + 255) / 256);
-  for (int attempt = 0; attempt < 10; attempt++) {
-    const size_t cp = (size_t)cap;
-    g.cap = cap;
-    void *tmp[9];
-    size_t sz[9] = {10 * cp * 8, 3 * cp * 8, 3 * cp * 8, 9 * cp * 8, cp * 4, cp * 4, cp * 4, cp * 4, cp};
-    for (int k = 0; k < 9; k++) { if (s.arena(&tmp[k], sz[k]) != hipSuccess) { err = "octree node storage"; return VBA_ERR_HIP; } }
-    g.nadd = (double *)tmp[0]; g.ncenter = (double *)tmp[1]; g.neval = (double *)tmp[2]; g.nevec = (double *)tmp[3]; g.nql = (float *)tmp[4];
-    g.nchild = (int *)tmp[5]; g.nfac = (int *)tmp[6]; g.nexi = (int *)tmp[7]; g.nlayer = (signed char *)tmp[8];
-    BIGCHK(hipMemsetAsync(g.cnt, 0, GCNT_N * sizeof(int), st));
-    BIGCHK(hipMemsetAsync(g.hkeys, 0xFF, (size_t)hcap * 8, st));
-    BIGCHK(hipMemsetAsync(g.nadd, 0, 10 * cp * 8, st));
-    BIGCHK(hipMemsetAsync(g.nexi, 0, cp * 4, st));
-    if (n > 0) {
-      hipLaunchKernelGGL(k_gbab_keys, gp, bk, 0, st, g, P);
-      hipLaunchKernelGGL(k_gbab_roots, dim3((hcap + 4095) / 4096), bk, 0, st, g, P);
-      hipLaunchKernelGGL(k_gbab_rootid, gp, bk, 0, st, g);
-      {
-        unsigned int bits = 1; while (bits < 32 && (1ull << bits) <= (unsigned long long)cap) bits++;     // keys are <= cap
-        size_t tb = sort_bytes + 256;
-        BIGCHK(sort_pairs_u32(sort_tmp, tb, g.skey, skey_b, g.sval, g.perm, (size_t)n, bits, st));
-      }
-      for (int L = 0; L <= P.max_layer; L++) {
-        // entries of the previous level are dead: a planar node keeps its own entries (it stopped descending), so the
-        // table is only cleared of nothing here — finished nodes never receive points again and their keys stay valid
-        if (L == 0) {   // (a fill kernel: the runtime's memset moved the 5.4 GB of an 8 M-point window at 750 GB/s, 7.2 ms a time)
-          hipLaunchKernelGGL(k_fill_u64, dim3(4096), dim3(256), 0, st, g.ekeys, ~0ull, (size_t)ecap);
-          hipLaunchKernelGGL(k_fill_u64, dim3(4096), dim3(256), 0, st, (unsigned long long *)g.ecl, 0ull, (size_t)ecap * 10);
-        }
-        hipLaunchKernelGGL(k_gbab_accum, gp, bk, 0, st, g);
-        hipLaunchKernelGGL(k_gbab_decide, dim3((cap + 255) / 256), bk, 0, st, g, P, L);
-        if (L < P.max_layer) hipLaunchKernelGGL(k_gbab_descend, gp, bk, 0, st, g);
-      }
-    }
-    BIGCHK(hipGetLastError());
-    BIGCHK(hipStreamSynchronize(st));
-    BIGCHK(hipMemcpyAsync(s.h_cnt, g.cnt, GCNT_N * sizeof(int), hipMemcpyDeviceToHost, st));
-    BIGCHK(hipStreamSynchronize(st));
-    if (s.h_cnt[GCNT_OVERFLOW] == 2) { err = "keyframe point outside the 21-bit voxel index range"; return VBA_ERR_CAPACITY; }
-    if (!s.h_cnt[GCNT_OVERFLOW]) { s.last_cap = cap; break; }
-    // (the undersized node arrays stay in the arena until the next build rewinds it)
-    cap *= 2;
-    if (attempt == 9) { err = "octree node capacity"; return VBA_ERR_CAPACITY; }
-  }
-  // sparse factor store
-  BigView &b = s.b;
-  const int V = s.h_cnt[GCNT_FACTORS];
-  b.W = W; b.V = V; b.capV = V > 0 ? V : 1;
-  BIGCHK(al((void **)&b.vptr, (size_t)(V + 1) * 4)); BIGCHK(al((void **)&s.d_vcnt, (size_t)b.capV * 4)); BIGCHK(al((void **)&s.d_fill, (size_t)b.capV * 4));
-  BIGCHK(al((void **)&b.eval, (size_t)b.capV * 3 * 8)); BIGCHK(al((void **)&b.evec, (size_t)b.capV * 9 * 8)); BIGCHK(al((void **)&b.pcr, (size_t)b.capV * 10 * 8));
-  BIGCHK(al((void **)&b.poses, (size_t)W * 12 * 8));
-  const size_t n6 = (size_t)6 * W;
-  BIGCHK(al((void **)&b.H, n6 * n6 * 8)); BIGCHK(al((void **)&b.g, n6 * 8)); BIGCHK(al((void **)&b.r, 8));
-
-  s.NP = (int)((n6 + 7) / 8 * 8); s.ld = (int)((s.NP + 63) / 64 * 64);
-  BIGCHK(al((void **)&s.d_Ab, (size_t)(s.NP + 1) * s.ld * 8)); BIGCHK(al((void **)&s.d_Tb, (size_t)(s.NP + 1) * 8 * 8)); BIGCHK(al((void **)&s.d_ord, n6 * 4)); BIGCHK(al((void **)&s.d_vec, ((size_t)3 * n6 + (size_t)6 * W * W) * 8));
-  BIGCHK(hipMemsetAsync(s.d_fill, 0, (size_t)b.capV * 4, st));
-  BIGCHK(hipMemsetAsync(b.vptr, 0, (size_t)(V + 1) * 4, st));
-  int E = 0;
-  if (V > 0) {
-    const int nn = s.h_cnt[GCNT_NODES] < g.cap ? s.h_cnt[GCNT_NODES] : g.cap;
-    hipLaunchKernelGGL(k_gbab_vcount, dim3((nn + 255) / 256), bk, 0, st, g, s.d_vcnt);
-    hipLaunchKernelGGL(k_big_scan, dim3(1), bk, 0, st, V, s.d_vcnt, b.vptr);
-    BIGCHK(hipStreamSynchronize(st));
-    BIGCHK(hipMemcpyAsync(&E, b.vptr + V, 4, hipMemcpyDeviceToHost, st));
-    BIGCHK(hipStreamSynchronize(st));
-  }
-  b.E = E; b.capE = E > 0 ? E : 1;
-  BIGCHK(al((void **)&b.efr, (size_t)b.capE * 4)); BIGCHK(al((void **)&b.evox, (size_t)b.capE * 4));
-  BIGCHK(al((void **)&b.ecl, (size_t)b.capE * 10 * 8)); BIGCHK(al((void **)&b.gv, (size_t)b.capE * 18 * 8)); BIGCHK(al((void **)&b.es, (size_t)b.capE * 27 * 8));
-  if (V > 0) {
-    const int nn = s.h_cnt[GCNT_NODES] < g.cap ? s.h_cnt[GCNT_NODES] : g.cap;
-    hipLaunchKernelGGL(k_gbab_fill, dim3((ecap + 255) / 256), bk, 0, st, g, b, s.d_fill);
-    hipLaunchKernelGGL(k_gbab_voxels, dim3((nn + 255) / 256), bk, 0, st, g, b);
-    BIGCHK(hipGetLastError());
-  }
-  BIGCHK(al((void **)&b.eidx, (size_t)b.capV * W * 4));
-  BIGCHK(hipMemsetAsync(b.eidx, 0xFF, (size_t)b.capV * W * 4, st));
-  if (V > 0 && E > 0) {
-    hipLaunchKernelGGL(k_big_eidx, dim3((E + 255) / 256), bk, 0, st, b);
-    BIGCHK(hipGetLastError());
-  }
-  return VBA_OK;
-}
-
-// divide_thread (VM:347-389): H, g, r at `poses` on the host side buffers (full layout)
-// Hessian pass on the sparse store: H (n x n) and g stay in HBM (the solver reads them there); the host gets diag(H), g and r.
-inline int big_hessian(BigStore &s, hipStream_t st, const double *poses, double *hdiag, double *gvec, double *r, std::string &err) {
-  BigView &b = s.b;
-  const size_t n6 = (size_t)6 * b.W;
-  BIGCHK(hipMemcpyAsync(b.poses, poses, (size_t)b.W * 12 * 8, hipMemcpyHostToDevice, st));
-  BIGCHK(hipMemsetAsync(b.H, 0, n6 * n6 * 8, st)); BIGCHK(hipMemsetAsync(b.g, 0, n6 * 8, st)); BIGCHK(hipMemsetAsync(b.r, 0, 8, st));
-  if (b.E > 0) {
-    hipLaunchKernelGGL(k_big_slot, dim3((b.E + 127) / 128), dim3(128), 0, st, b);
-    const int nt = (b.W + BIG_TF - 1) / BIG_TF, npair = nt * (nt + 1) / 2, nchunk = (b.V + BIG_VC - 1) / BIG_VC;
-    int nslice = (2048 + npair - 1) / npair;
-    if (nslice > nchunk) nslice = nchunk;
-    if (nslice < 1) nslice = 1;
-    hipLaunchKernelGGL(k_big_syrk, dim3(npair, nslice), dim3(256), 0, st, b, nt, nslice);
-    hipLaunchKernelGGL(k_big_diag, dim3(b.W), dim3(256), 0, st, b);   // after the SYRK atomics on H (stream order)
-  }
-  hipLaunchKernelGGL(k_big_getdiag, dim3((unsigned)((n6 + 255) / 256)), dim3(256), 0, st, b.H, (int)n6, s.d_vec);
-  BIGCHK(hipGetLastError());
-  BIGCHK(hipStreamSynchronize(st));
-  BIGCHK(hipMemcpyAsync(hdiag, s.d_vec, n6 * 8, hipMemcpyDeviceToHost, st));
-  BIGCHK(hipMemcpyAsync(gvec, b.g, n6 * 8, hipMemcpyDeviceToHost, st));
-  BIGCHK(hipMemcpyAsync(r, b.r, 8, hipMemcpyDeviceToHost, st));
-  BIGCHK(hipStreamSynchronize(st));
-  return VBA_OK;
-}
-// the six diagonal entries of every 6x6 cross block of the Hessian of the last big_hessian (before the gauge): [W][W][6]
-inline int big_block_diagonals(BigStore &s, hipStream_t st, double *out, std::string &err) {
-  const int W = s.b.W;
-  const size_t n6 = (size_t)6 * W, cnt = (size_t)6 * W * W;
-  hipLaunchKernelGGL(k_big_blockdiag, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, s.b.H, W, s.d_vec + 3 * n6);
-  BIGCHK(hipGetLastError());
-  BIGCHK(hipStreamSynchronize(st));
-  BIGCHK(hipMemcpyAsync(out, s.d_vec + 3 * n6, cnt * 8, hipMemcpyDeviceToHost, st));
-  BIGCHK(hipStreamSynchronize(st));
-  return VBA_OK;
-}
-// only_residual (VM:391-420): also refreshes the per-voxel eigen state
-inline int big_residual(BigStore &s, hipStream_t st, const double *poses, double *r, std::string &err) {
-  BigView &b = s.b;
-  BIGCHK(hipMemcpyAsync(b.poses, poses, (size_t)b.W * 12 * 8, hipMemcpyHostToDevice, st));
-  BIGCHK(hipMemsetAsync(b.r, 0, 8, st));
-  if (b.V > 0) hipLaunchKernelGGL(k_big_residual, dim3((b.V + 255) / 256), dim3(256), 0, st, b);
-  BIGCHK(hipGetLastError());
-  BIGCHK(hipStreamSynchronize(st));
-  BIGCHK(hipMemcpyAsync(r, b.r, 8, hipMemcpyDeviceToHost, st));
-  BIGCHK(hipStreamSynchronize(st));
-  return VBA_OK;
-}
-
-// Eigen's LDLT pivot order for (H + u D): largest |stored diagonal| first, first index wins ties.  hd = diag(H) after the gauge.
-inline void big_pivot_order(const double *hd, double u, int n, int *ord) {
-  std::vector<double> dabs(n);
-  for (int r = 0; r < n; r++) { ord[r] = r; dabs[r] = std::fabs(hd[r] + u * hd[r]); }
-  std::stable_sort(ord, ord + n, [&](int a, int b) { return dabs[a] > dabs[b]; });
-}
-// the model decrease q1 = 0.5 dx^T (u D dx - g) of VM:465 (hd, g after the gauge), summed in row order
-inline double big_q1(const double *dxi, const double *hd, const double *g, double u, int n) {
-  double q1 = 0;
-  for (int r = 0; r < n; r++) q1 += dxi[r] * (u * hd[r] * dxi[r] - g[r]);
-  return 0.5 * q1;
-}
-
-// (H + u D) dxi = -g with the gauge of VM:452-455, H / g = the device buffers of the last big_hessian (before the gauge).
-// ord = Eigen's pivot order (host).  Factorisation and back substitution run on the device; the host gets dxi (n doubles).
-inline int big_solve(BigStore &s, hipStream_t st, const int *ord, double u, double *dxi, std::string &err) {
-  const int n = 6 * s.b.W, NP = s.NP, ld = s.ld;
-  BIGCHK(hipMemcpyAsync(s.d_ord, ord, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  const long long tot = (long long)(NP + 1) * NP;
-  hipLaunchKernelGGL(k_bigl_setup, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, s.b.H, s.b.g, s.d_ord, n, NP, ld, u, s.d_Ab);
-  for (int k0 = 0; k0 < NP; k0 += 8) {
-    hipLaunchKernelGGL(k_bigl_panel, dim3(1), dim3(256), 0, st, s.d_Ab, s.d_Tb, NP, ld, k0);
-    const int kn = k0 + 8;
-    if (kn <= NP) {
-      const int nt = (NP + 1 - kn + 63) / 64;
-      if (nt > 0) hipLaunchKernelGGL(k_bigl_update, dim3(nt * (nt + 1) / 2), dim3(256), 0, st, s.d_Ab, s.d_Tb, NP, ld, k0);
-    }
-  }
-  // back substitution on the device, 64 unknowns per step from the bottom
-  for (int lo = ((n - 1) / 64) * 64; lo >= 0; lo -= 64) {
-    hipLaunchKernelGGL(k_bigl_bs_tri, dim3(1), dim3(64), 0, st, s.d_Ab, NP, ld, n, lo);
-    if (lo > 0) hipLaunchKernelGGL(k_bigl_bs_gemv, dim3((lo + 255) / 256), dim3(256), 0, st, s.d_Ab, NP, ld, n, lo);
-  }
-  double *d_dxi = s.d_vec + 2 * (size_t)n;
-  hipLaunchKernelGGL(k_bigl_bs_out, dim3((n + 255) / 256), dim3(256), 0, st, s.d_Ab, NP, ld, n, s.d_ord, d_dxi);
-  BIGCHK(hipGetLastError());
-  BIGCHK(hipStreamSynchronize(st));
-  BIGCHK(hipMemcpyAsync(dxi, d_dxi, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-  BIGCHK(hipStreamSynchronize(st));
-  return VBA_OK;
 }
 
 }  // namespace vba

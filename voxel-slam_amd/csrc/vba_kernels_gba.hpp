@@ -247,83 +247,4 @@ __global__ void k_gba_to_ref(int n, int W, const int *__restrict__ offsets, cons
   out[3 * (size_t)p + 2] = (double)(float)((R[6] * x + R[7] * y + R[8] * z) + R[11]);
 }
 
-// ---------------------------------------------------------------- host side
-#define GBACHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return VBA_ERR_HIP; } } while (0)
-
-inline int gba_alloc_nodes(GbaStore &s, int cap, int W, std::string &err) {
-  s.free_nodes();
-  const size_t cp = (size_t)cap;
-  auto al = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes); if (e == hipSuccess) s.node_bufs.push_back(*p); return e; };
-  GBACHK(al((void **)&s.v.nadd, 10 * cp * 8)); GBACHK(al((void **)&s.v.nlc, 10 * cp * W * 8)); GBACHK(al((void **)&s.v.ncenter, 3 * cp * 8));
-  GBACHK(al((void **)&s.v.nql, cp * 4)); GBACHK(al((void **)&s.v.nchild, cp * 4)); GBACHK(al((void **)&s.v.nfac, cp * 4)); GBACHK(al((void **)&s.v.nlayer, cp));
-  GBACHK(al((void **)&s.v.neval, 3 * cp * 8)); GBACHK(al((void **)&s.v.nevec, 9 * cp * 8));
-  s.v.cap = cap; s.v.W = W;
-  return VBA_OK;
-}
-
-// Builds the octree of one keyframe window and leaves the planar voxels in device node storage; *n_factors = their count.
-// pl may be a host or device pointer ([n][3] local points, keyframe i = rows offsets[i]..offsets[i+1]).
-inline int gba_build(GbaStore &s, hipStream_t st, int W, const int *offsets, const double *pl, const double *poses, const GbaParams &P, int *n_factors,
-                     std::string &err) {
-  const int n = offsets[W];
-  *n_factors = 0;
-  if (!s.h_cnt) {
-    GBACHK(hipHostMalloc((void **)&s.h_cnt, GCNT_N * sizeof(int), hipHostMallocDefault));
-    GBACHK(hipMalloc((void **)&s.v.cnt, GCNT_N * sizeof(int)));
-    GBACHK(hipMalloc((void **)&s.v.poses, VBA_MAX_WIN * 12 * sizeof(double)));
-    GBACHK(hipMalloc((void **)&s.v.offsets, (VBA_MAX_WIN + 1) * sizeof(int)));
-  }
-  if (n > s.cap_pts) {
-    hipFree(s.v.pw); hipFree(s.v.pframe); hipFree(s.v.pnode); hipFree(s.d_pl);
-    const size_t c = (size_t)n + n / 4 + 1024;
-    GBACHK(hipMalloc((void **)&s.v.pw, 3 * c * 8)); GBACHK(hipMalloc((void **)&s.v.pframe, c * 4)); GBACHK(hipMalloc((void **)&s.v.pnode, c * 4));
-    GBACHK(hipMalloc((void **)&s.d_pl, 3 * c * 8));
-    s.cap_pts = (int)c;
-  }
-  int hcap = 1 << 16;
-  while (hcap < 2 * n && hcap < (1 << 28)) hcap <<= 1;
-  if (hcap > s.cap_hash) {
-    hipFree(s.v.hkeys); hipFree(s.v.hvals);
-    GBACHK(hipMalloc((void **)&s.v.hkeys, (size_t)hcap * 8)); GBACHK(hipMalloc((void **)&s.v.hvals, (size_t)hcap * 4));
-    s.cap_hash = hcap;
-  }
-  s.v.hmask = (unsigned int)(s.cap_hash - 1);
-  s.v.npts = n;
-  GBACHK(hipMemcpyAsync(s.d_pl, pl, (size_t)n * 3 * 8, hipMemcpyDefault, st));
-  s.v.pl = s.d_pl;
-  GBACHK(hipMemcpyAsync(s.v.poses, poses, (size_t)W * 12 * 8, hipMemcpyHostToDevice, st));
-  GBACHK(hipMemcpyAsync(s.v.offsets, offsets, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, st));
-  if (s.v.cap == 0 || s.v.W != W) { int r = gba_alloc_nodes(s, 1 << 17, W, err); if (r) return r; }
-  const dim3 b(256), gp((n + 255) / 256);
-  for (int attempt = 0; attempt < 8; attempt++) {
-    const size_t cp = (size_t)s.v.cap;
-    GBACHK(hipMemsetAsync(s.v.cnt, 0, GCNT_N * sizeof(int), st));
-    GBACHK(hipMemsetAsync(s.v.hkeys, 0xFF, (size_t)s.cap_hash * 8, st));
-    GBACHK(hipMemsetAsync(s.v.nadd, 0, 10 * cp * 8, st));
-    GBACHK(hipMemsetAsync(s.v.nlc, 0, 10 * cp * W * 8, st));
-    if (n > 0) {
-      hipLaunchKernelGGL(k_gba_keys, gp, b, 0, st, s.v, P);
-      hipLaunchKernelGGL(k_gba_roots, dim3((s.cap_hash + 4095) / 4096), b, 0, st, s.v, P);
-      hipLaunchKernelGGL(k_gba_rootid, gp, b, 0, st, s.v);
-      for (int L = 0; L <= P.max_layer; L++) {
-        hipLaunchKernelGGL(k_gba_accum, gp, b, 0, st, s.v);
-        hipLaunchKernelGGL(k_gba_decide, dim3((s.v.cap + 255) / 256), b, 0, st, s.v, P, L);
-        if (L < P.max_layer) hipLaunchKernelGGL(k_gba_descend, gp, b, 0, st, s.v);
-      }
-    }
-    GBACHK(hipGetLastError());
-    GBACHK(hipStreamSynchronize(st));   // drain first (see map_read_counters)
-    GBACHK(hipMemcpyAsync(s.h_cnt, s.v.cnt, GCNT_N * sizeof(int), hipMemcpyDeviceToHost, st));
-    GBACHK(hipStreamSynchronize(st));
-    if (s.h_cnt[GCNT_OVERFLOW] == 2) { err = "keyframe point outside the 21-bit voxel index range"; return VBA_ERR_CAPACITY; }
-    if (!s.h_cnt[GCNT_OVERFLOW]) { *n_factors = s.h_cnt[GCNT_FACTORS]; return VBA_OK; }
-    int want = s.v.cap * 2;
-    while (want < s.h_cnt[GCNT_NODES] + 64) want *= 2;
-    int r = gba_alloc_nodes(s, want, W, err);
-    if (r) return r;
-  }
-  err = "octree node capacity";
-  return VBA_ERR_CAPACITY;
-}
-
 }  // namespace vba

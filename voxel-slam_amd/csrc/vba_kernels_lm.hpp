@@ -287,7 +287,7 @@ __global__ __launch_bounds__(256) void k_lm_solve_m(LmDev *s, const double *__re
     if (lane == 63) red8[3] = 0.0;                 // (the wave sum of no rows)
   } else {
     double q = tid < n ? dxs[tid] * (u * hd[tid] * dxs[tid] - gs[tid]) : 0.0;                          // VM:465
-    q = wave_sum_to_lane63(q);                                  // DPP adds (vba_kernels_factor.hpp), no LDS round trips
+    q = wave_sum_to_lane63(q);                                  // DPP adds (vba_common.hpp), no LDS round trips
     if (lane == 63) red8[wv] = q;
   }
   __syncthreads();

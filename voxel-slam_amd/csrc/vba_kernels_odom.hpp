@@ -30,7 +30,7 @@ struct OdomWgSync { __device__ __forceinline__ void operator()() const { __synct
 // t + 476, ... of the flat array (rows t / 34, t / 34 + 7, ... of its column: consecutive lanes read consecutive doubles) in that
 // order, then lane c adds the seven group sums in group order.  The order depends on nb alone.
 static constexpr int ODOM_RED_LANES = 7 * 34;
-// kd: the stop rule of the kd-tree variant (vba_odom_ekf.hpp), whose loop in voxelba.hip launches this kernel too.
+// kd: the stop rule of the kd-tree variant (vba_odom_ekf.hpp), whose loop in vba_odom.hip launches this kernel too.
 __global__ __launch_bounds__(256) void k_odom_update(vbh::OdomEkf *S, const double *__restrict__ partial, int nb, int iter, int kd) {
 #pragma clang fp contract(off)
   __shared__ double wsm[vbh::OE_WORK];
@@ -53,25 +53,6 @@ __global__ __launch_bounds__(256) void k_odom_update(vbh::OdomEkf *S, const doub
   }
   __syncthreads();
   vbh::odom_ekf_iterate(w, S, iter, t, 256, OdomWgSync(), kd);
-}
-
-// The whole call on the stream: one upload of the image, (match, update) x 4, one download of the result block, one wait.  h_img
-// is pinned and holds the image on entry and the result block on return.
-int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomEkf *h_img, int n, const double *d_pts,
-                      const double *d_var, double *d_partial, std::string &err) {
-  MAPCHK(hipMemcpyAsync(d_S, h_img, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, st));
-  const bool match = n > 0 && s.allocated;               // otherwise every sum is zero: the update runs on no partials
-  const int nb = match ? (n + 255) / 256 : 0;
-  const MapParams P = map_params(s);
-  for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
-    if (match) hipLaunchKernelGGL(k_odom_match_dev, dim3(nb), dim3(256), 0, st, s.v, P, (const vbh::OdomEkf *)d_S, n, d_pts, d_var, d_partial);
-    hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, st, d_S, (const double *)d_partial, nb, iter, 0);
-  }
-  MAPCHK(hipGetLastError());
-  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
-  MAPCHK(hipMemcpyAsync((char *)h_img + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, st));
-  MAPCHK(hipStreamSynchronize(st));
-  return VBA_OK;
 }
 
 }  // namespace vba

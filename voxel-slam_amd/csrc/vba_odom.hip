@@ -1,0 +1,272 @@
+// libvoxelba.so: the odometry EKF updates, both variants.  The initialisation odometry on a point-cloud map (vba_odom_kdtree_*,
+// vba_odom_lio_state_estimation_kdtree*) with the kernels of vba_kernels_kd.hpp, compiled here and nowhere else, and
+// the scan-to-map update on the voxel map (vba_odom_lio_state_estimation*, §17), whose kernels the map unit compiles
+// (vba_kernels_odom.hpp) and whose loop it queues (map_odom_resident).
+#include "vba_ctx.hpp"
+#include "vba_kernels_kd.hpp"
+#include "vba_hostmath.hpp"
+#include "vba_odom_ekf.hpp"
+
+#include <algorithm>
+#include <cstddef>
+#include <cstring>
+
+extern "C" {
+
+// ---------------------------------------------------------------- initialisation odometry on a point-cloud map (vba_kernels_kd.hpp)
+static int kd_reserve(vba_ctx *c, size_t pts) {
+  if (pts <= c->kd_cap) return VBA_OK;
+  size_t cap = c->kd_cap ? c->kd_cap : 65536;
+  while (cap < pts) cap *= 2;
+  for (int i = 0; i < 2; i++) {
+    double *nw = nullptr;
+    HIPCHK(c, hipMalloc((void **)&nw, cap * 3 * sizeof(double)));
+    if (c->d_kdtree[i]) {
+      if (i == c->kd_cur && c->kd_n > 0) HIPCHK(c, hipMemcpyAsync(nw, c->d_kdtree[i], (size_t)c->kd_n * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      hipFree(c->d_kdtree[i]);
+    }
+    c->d_kdtree[i] = nw;
+  }
+  c->kd_cap = cap;
+  c->kd_allocs += 2; c->kd_bytes += (int64_t)(2 * cap * 3 * sizeof(double));
+  return VBA_OK;
+}
+// map slices of the 5-NN search for nb workgroups of scan points: enough workgroups to cover the chip
+static int kd_slices_of(int nb) { return nb >= 512 ? 1 : (nb >= 128 ? 4 : 8); }
+int vba_odom_kdtree_reset(vba_ctx *c) { c->kd_n = 0; return VBA_OK; }
+int vba_odom_kdtree_size(vba_ctx *c) { return c->kd_n; }
+int vba_odom_kdtree_points(vba_ctx *c, double *out) {
+  if (!out && c->kd_n > 0) return VBA_ERR_BAD_ARG;
+  if (c->kd_n == 0) return VBA_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(out, c->d_kdtree[c->kd_cur], (size_t)c->kd_n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VBA_OK;
+}
+
+// ---------------------------------------------------------------- its EKF loop, resident on the device
+// device state and pinned image of the resident EKF loops (this one and the voxel map's)
+static int odom_image_ensure(vba_ctx *c) {
+  if (c->d_odom) return VBA_OK;
+  HIPCHK(c, hipMalloc((void **)&c->d_odom, sizeof(vbh::OdomEkf)));
+  HIPCHK(c, hipHostMalloc((void **)&c->h_odom, sizeof(vbh::OdomEkf), hipHostMallocDefault));
+  c->kd_allocs += 2; c->kd_bytes += (int64_t)(2 * sizeof(vbh::OdomEkf));
+  return VBA_OK;
+}
+// what a resident entry point reports of the loop's result block
+static void odom_report_fill(vba_odom_report *report, const vbh::OdomEkf &S, double nnt_eig_min) {
+  report->iterations = S.iterations;
+  for (int k = 0; k < 4; k++) { report->match_num[k] = S.match_num[k]; report->rot_add[k] = S.rot_add[k]; report->tra_add[k] = S.tra_add[k]; }
+  report->nnt_eig_min = nnt_eig_min;
+}
+static size_t kd_up(size_t b) { return (b + 255) & ~(size_t)255; }
+// scratch sized by a scan of up to p points: planes [p][4] | partials [ceil(p / 256)][34] | candidates at the slice count that
+// needs the most of them among the scans of up to p points
+struct KdScanLayout { size_t o_part, o_cand, bytes; };
+static KdScanLayout kd_scan_layout(size_t p) {
+  const size_t a = 8 * std::min<size_t>(p, 127 * 256), b = 4 * std::min<size_t>(p, 511 * 256);
+  KdScanLayout L;
+  L.o_part = kd_up(p * 4 * sizeof(double));
+  L.o_cand = L.o_part + kd_up(((p + 255) / 256) * 34 * sizeof(double));
+  L.bytes = L.o_cand + kd_up(std::max(std::max(a, b), p) * 5 * sizeof(unsigned long long));
+  return L;
+}
+static int kd_scan_ensure(vba_ctx *c, size_t pts) {
+  if (pts <= c->kdscan_pts) return VBA_OK;
+  size_t cap = c->kdscan_pts ? c->kdscan_pts : 16384;
+  while (cap < pts) cap *= 2;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->d_kdscan) hipFree(c->d_kdscan);
+  c->d_kdscan = nullptr; c->kdscan_pts = 0;
+  const size_t b = kd_scan_layout(cap).bytes;
+  HIPCHK(c, hipMalloc((void **)&c->d_kdscan, b));
+  c->kdscan_pts = cap; c->kd_allocs++; c->kd_bytes += (int64_t)b;
+  return VBA_OK;
+}
+// scratch sized by map + scan of up to p points: the re-sampler's count [p] | first [p] | work area (the deterministic layout, the larger)
+static int kd_ws_ensure(vba_ctx *c, size_t pts) {
+  if (pts <= c->kdws_pts) return VBA_OK;
+  if (pts > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
+  size_t cap = c->kdws_pts ? c->kdws_pts : 65536;
+  while (cap < pts) cap *= 2;
+  int st = VBA_OK;
+  const size_t ws = kf_ws_layout(c, (int)cap, true, nullptr, nullptr, &st);
+  if (st) return st;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->d_kdws) hipFree(c->d_kdws);
+  c->d_kdws = nullptr; c->kdws_pts = 0; c->kdws_bytes = 0;
+  const size_t b = 2 * kd_up(cap * sizeof(int)) + ws;
+  HIPCHK(c, hipMalloc((void **)&c->d_kdws, b));
+  c->kdws_pts = cap; c->kdws_bytes = b; c->kd_allocs++; c->kd_bytes += (int64_t)b;
+  return VBA_OK;
+}
+
+int vba_odom_kdtree_reserve(vba_ctx *c, int max_map_points, int max_scan_points) {
+  if (!c || max_map_points < 0 || max_scan_points < 0 || max_map_points > (1 << 28) || max_scan_points > (1 << 28)) return VBA_ERR_BAD_ARG;
+  int st = odom_image_ensure(c);
+  if (st || (st = kd_reserve(c, (size_t)max_map_points + 16)) || (st = kd_scan_ensure(c, (size_t)max_scan_points)) ||
+      (st = kd_ws_ensure(c, (size_t)max_map_points)))
+    return st;
+  return VBA_OK;
+}
+int vba_odom_kdtree_allocations(vba_ctx *c, int *n_allocs, int64_t *bytes) {
+  if (!c || !n_allocs || !bytes) return VBA_ERR_BAD_ARG;
+  *n_allocs = c->kd_allocs; *bytes = c->kd_bytes;
+  return VBA_OK;
+}
+
+// One update on a scan in device memory, c->kd_n + n <= 2^28.  With fewer than 100 map points the scan only seeds the map (VS:1105-1118):
+// the append is enqueued, *ran stays false and nothing is waited for.  Otherwise state and cov are updated, the call has completed on
+// return and c->h_odom holds the loop's result block.  Nothing here touches c->d_stage: a caller may keep the scan there.
+static int kd_odom_core(vba_ctx *c, int n, const double *d_pts, double *state, double *cov, bool *ran) {
+  *ran = false;
+  const int nb = (n + 255) / 256, kd_slices = kd_slices_of(nb);
+  const size_t tot = (size_t)c->kd_n + (size_t)n;
+  int st = kd_reserve(c, tot + 16);
+  if (st) return st;
+  if (c->kd_n < 100) {
+    if (n > 0) {
+      KdPose X;
+      std::memcpy(X.R, state + 1, sizeof(X.R)); std::memcpy(X.t, state + 10, sizeof(X.t));
+      hipLaunchKernelGGL(k_kd_append, dim3(nb), dim3(256), 0, c->stream, n, d_pts, X, c->d_kdtree[c->kd_cur] + (size_t)c->kd_n * 3);
+      HIPCHK(c, hipGetLastError());
+    }
+    c->kd_n += n;
+    return VBA_OK;
+  }
+  if ((st = odom_image_ensure(c)) || (st = kd_scan_ensure(c, (size_t)n)) || (st = kd_ws_ensure(c, tot))) return st;
+  const bool det = c->opt.deterministic != 0;
+  int *d_cnt = (int *)c->d_kdws, *d_first = (int *)(c->d_kdws + kd_up(c->kdws_pts * sizeof(int)));
+  char *ws = c->d_kdws + 2 * kd_up(c->kdws_pts * sizeof(int));
+  DsWork w{};
+  if (2 * kd_up(c->kdws_pts * sizeof(int)) + kf_ws_layout(c, (int)tot, det, ws, &w, &st) > c->kdws_bytes || st) return st ? st : VBA_ERR_CAPACITY;
+  const KdScanLayout L = kd_scan_layout(c->kdscan_pts);
+  double *d_pl = (double *)c->d_kdscan, *d_part = (double *)(c->d_kdscan + L.o_part);
+  unsigned long long *d_cand = (unsigned long long *)(c->d_kdscan + L.o_cand);
+  // the image: cov_inv = P^-1 / 1000 entry by entry (VS:1134, VS:1213), the first iteration searches
+  double cov_inv[225];
+  vbh::inverse_pplu(cov, cov_inv, VBA_DIM);
+  for (int k = 0; k < 225; k++) cov_inv[k] = cov_inv[k] / 1000;
+  vbh::OdomEkf &S = *c->h_odom;
+  vbh::odom_ekf_begin(S, state, cov, cov_inv);
+  S.refind = 1;
+  vbh::OdomEkf *d_S = c->d_odom;
+  hipStream_t s = c->stream;
+  double *tree = c->d_kdtree[c->kd_cur], *tree_out = c->d_kdtree[c->kd_cur ^ 1];
+  HIPCHK(c, hipMemcpyAsync(d_S, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
+  for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
+    if (n > 0) {
+      hipLaunchKernelGGL(k_kd_match_dev, dim3(nb, kd_slices), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, c->kd_n, (const double *)tree, d_cand);
+      hipLaunchKernelGGL(k_kd_fit_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, kd_slices, (const unsigned long long *)d_cand, (const double *)tree, d_pl);
+      hipLaunchKernelGGL(k_kd_accum_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, (const double *)d_pl, d_part);
+    }
+    // n == 0: nb == 0 and d_part may be NULL (no scan scratch was ever needed); the reduction reads nb * 34 doubles, that is none
+    hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, s, d_S, (const double *)d_part, nb, iter, 1);
+  }
+  // map update VS:1238-1250: the scan appended in the refined pose, map + scan re-sampled on a 0.5 m grid into the other half; the
+  // voxel count lands in the result block
+  if (n > 0) hipLaunchKernelGGL(k_kd_append_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, tree + (size_t)c->kd_n * 3);
+  w.n_out = &d_S->n_map;
+  if ((st = ds_core(c, s, 0, (int)tot, tree, nullptr, 9, 4, 0.5, det, w))) return st;
+  hipLaunchKernelGGL(k_ds_emit, dim3(((int)tot + 255) / 256), dim3(256), 0, s, (int)tot, (const DsSlot *)w.tab, (const int *)w.slot, (const int *)w.blk, tree_out, d_cnt,
+                     d_first, (double *)nullptr, 0);
+  HIPCHK(c, hipGetLastError());
+  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
+  HIPCHK(c, hipMemcpyAsync((char *)&S + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (S.n_map < 1 || (size_t)S.n_map > tot) { c->set_error("kd-tree odometry: voxel count of the re-sampled map out of range"); return VBA_ERR_HIP; }
+  c->kd_cur ^= 1; c->kd_n = S.n_map;
+  std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
+  std::memcpy(cov, S.P_out, sizeof(S.P_out));
+  *ran = true;
+  return VBA_OK;
+}
+
+int vba_odom_lio_state_estimation_kdtree_resident(vba_ctx *c, int n, const double *d_pnt_body, double *state, double *cov, int *iterations,
+                                                  vba_odom_report *report) {
+  if (!c || n < 0 || (n > 0 && !d_pnt_body) || !state || !cov) return VBA_ERR_BAD_ARG;
+  if (iterations) *iterations = 0;
+  if (report) std::memset(report, 0, sizeof(*report));
+  if ((size_t)c->kd_n + (size_t)n > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
+  bool ran;
+  const int st = kd_odom_core(c, n, d_pnt_body, state, cov, &ran);
+  if (st || !ran) return st;
+  const vbh::OdomEkf &S = *c->h_odom;
+  if (iterations) *iterations = S.iterations;
+  if (report) odom_report_fill(report, S, 0.0);
+  return VBA_OK;
+}
+
+// The staging front end of the same update: the scan may be in host or device memory and the call has completed when it returns.
+int vba_odom_lio_state_estimation_kdtree(vba_ctx *c, int n, const double *pnt_body, double *state, double *cov, int *iterations) {
+  if (n < 0 || (n > 0 && !pnt_body) || !state || !cov) return VBA_ERR_BAD_ARG;
+  if (iterations) *iterations = 0;
+  if ((size_t)c->kd_n + (size_t)n > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
+  int st = ensure_stage(c, (size_t)n * 3 * sizeof(double));
+  if (st) return st;
+  if (n > 0) HIPCHK(c, hipMemcpyAsync(c->d_stage, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
+  bool ran;
+  if ((st = kd_odom_core(c, n, (const double *)c->d_stage, state, cov, &ran))) return st;
+  if (!ran) HIPCHK(c, hipStreamSynchronize(c->stream));                    // seeded: the core only enqueued the append
+  else if (iterations) *iterations = c->h_odom->iterations;
+  return VBA_OK;
+}
+
+// ---------------------------------------------------------------- odometry scan-to-map (VS:962-1098)
+// One update on a scan in device memory with the iterations resident on the device: the host inverts P once, writes
+// one image, queues the four (point loop, update) pairs and waits once; which of them do any work is decided by the `done` flag in the
+// device state.  state and cov are updated, c->h_odom holds the loop's result block.  Nothing here touches c->d_stage: a caller may keep
+// the scan there.  Runs on this rank's map, whatever n_ranks is.
+static int odom_core(vba_ctx *c, int n, const double *d_pts, const double *d_var, double *state, double *cov) {
+  int st = odom_image_ensure(c);
+  if (st) return st;
+  const size_t need = (size_t)((n + 255) / 256) * 34;
+  if (need > c->odom_part_doubles) {
+    if (c->d_odom_part) hipFree(c->d_odom_part);       // idle: the call that used it ended in a synchronise
+    c->d_odom_part = nullptr; c->odom_part_doubles = 0;
+    size_t cap = 256 * 34;
+    while (cap < need) cap *= 2;
+    HIPCHK(c, hipMalloc((void **)&c->d_odom_part, cap * sizeof(double)));
+    c->odom_part_doubles = cap;
+  }
+  double cov_inv[225];
+  vbh::inverse_pplu(cov, cov_inv, VBA_DIM);                                // VS:987
+  vbh::OdomEkf &S = *c->h_odom;
+  vbh::odom_ekf_begin(S, state, cov, cov_inv);
+  if ((st = map_odom_resident(c->map, c->stream, c->d_odom, c->h_odom, n, d_pts, d_var, c->d_odom_part, c->err))) return st;
+  std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
+  std::memcpy(cov, S.P_out, sizeof(S.P_out));
+  return VBA_OK;
+}
+
+int vba_odom_lio_state_estimation_resident(vba_ctx *c, int n, const double *d_pnt_body, const double *d_var_body, double *state, double *cov,
+                                           int *ok, vba_odom_report *report) {
+  if (n < 0 || (n > 0 && (!d_pnt_body || !d_var_body)) || !state || !cov) return VBA_ERR_BAD_ARG;
+  if (c->n_ranks > 1) { c->set_error("the resident odometry loop has no all-reduce step between its iterations: unsharded contexts only"); return VBA_ERR_UNSUPPORTED; }
+  const int st = odom_core(c, n, d_pnt_body, d_var_body, state, cov);
+  if (st) return st;
+  const vbh::OdomEkf &S = *c->h_odom;
+  // SelfAdjointEigenSolver(nnt).eigenvalues()[0] < 14 -> false  (VS:1090-1097)
+  const double emin = vbh::odom_nnt_eig_min(S.nnt);
+  if (ok) *ok = (emin < 14) ? 0 : 1;
+  if (report) odom_report_fill(report, S, emin);
+  return VBA_OK;
+}
+
+// The staging front end of the same update: the scan may be in host or device memory, and a sharded context is accepted.
+int vba_odom_lio_state_estimation(vba_ctx *c, int n, const double *pnt_body, const double *var_body, double *state, double *cov, int *ok) {
+  if (n < 0 || (n > 0 && (!pnt_body || !var_body)) || !state || !cov) return VBA_ERR_BAD_ARG;
+  int st = ensure_stage(c, (size_t)n * 12 * sizeof(double));             // [pts n*3 | var n*9]
+  if (st) return st;
+  double *d_pts = (double *)c->d_stage, *d_var = d_pts + (size_t)n * 3;
+  if (n > 0) {
+    HIPCHK(c, hipMemcpyAsync(d_pts, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_var, var_body, (size_t)n * 9 * sizeof(double), hipMemcpyDefault, c->stream));
+  }
+  if ((st = odom_core(c, n, d_pts, d_var, state, cov))) return st;
+  if (ok) *ok = (vbh::odom_nnt_eig_min(c->h_odom->nnt) < 14) ? 0 : 1;
+  return VBA_OK;
+}
+
+}  // extern "C"

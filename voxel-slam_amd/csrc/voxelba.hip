@@ -1,5 +1,6 @@
-// libvoxelba.so — implementation of include/voxelba.h for MI355X (gfx950): the BA core.  The map, the scan pre-processing and keyframe
-// store, the loop map, loop retrieval, pose-graph optimisation and the session formats are units of their own ("source layout").
+// libvoxelba.so — implementation of include/voxelba.h for MI355X (gfx950): the BA core.  The map, the odometry, hierarchical global BA,
+// the initialisation, the scan pre-processing and keyframe store, the loop map, loop retrieval, pose-graph optimisation and the session
+// formats are units of their own ("source layout").
 // Host side: context / HBM store management, the three LM drivers (voxel_map.hpp:342-976) and the IMU factor;
 // device side: the kernels in vba_kernels_factor.hpp and the headers included below.  No CPU compute fallback exists.
 #include "vba_ctx.hpp"
@@ -7,13 +8,8 @@
 #include "vba_kernels_h3.hpp"
 #include "vba_kernels_lm.hpp"
 #include "vba_kernels_li.hpp"
-#include "vba_kernels_gba.hpp"
-#include "vba_kernels_big.hpp"
-#include "vba_kernels_kd.hpp"
-#include "vba_kernels_init.hpp"
 #include <cstddef>
 #include "vba_hostmath.hpp"
-#include "vba_odom_ekf.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>     // TYPES only: the entry points are resolved at run time (rccl_api below), the library does not link librccl
@@ -21,15 +17,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <atomic>
 #include <string>
-#include <thread>
 #include <vector>
 #include <array>
 #include <map>
 #include <chrono>
-#include <deque>
-#include <functional>
 #include <algorithm>
 
 using namespace vba;
@@ -71,24 +63,12 @@ const RcclApi &rccl_api() {
   }();
   return api;
 }
-
-// Diagnostic switches (in-kernel stamps, host-side phase timers, ablation forms) exist only in a -DVBA_DIAG build (make diag ->
-// libvoxelba_diag.so, tools/README.md); the shipped library reads no environment variable.
-inline const char *diag_env(const char *name) {
-#ifdef VBA_DIAG
-  return std::getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
 }
 
 namespace {
 
 // damping candidates per solve launch (vba_kernels_lm.hpp, "Speculative damping"); 1 = the plain sequential solve.  Read when a
 // context is created (vba_options::lm_spec; tests compare the two forms bit for bit).
-static const int kMaxDevices = 64;         // per-device "kernel attribute set" flags
 static const int kMaxBlocksHess = 256;     // upper bound of vba_options::hessian_workgroups (sizes the partial slab): one workgroup per CU
 
 int nout_of(int W) { return 36 * W * W + 6 * W + 1; }   // full layout [H | g | r]
@@ -130,9 +110,6 @@ int ensure_stage(vba_ctx *c, size_t bytes) {
   c->stage_bytes = bytes;
   return VBA_OK;
 }
-}  // namespace vba
-
-namespace {
 
 // (re)allocate the SoA factor store with stride newcap, preserving the first nvox voxels
 int factor_reserve(vba_ctx *c, int need) {
@@ -178,6 +155,9 @@ void factor_update_mask(vba_ctx *c, int base, int n) {
   // the Hessian pass' tile table of the whole store [0, base + n) (vba_kernels_h3.hpp)
   if (base + n > 0 && c->use_h3) hipLaunchKernelGGL(k_factor_tiles, dim3(1), dim3(1024), 0, c->stream, c->fv, base + n);
 }
+}  // namespace vba
+
+namespace {
 
 int upload_poses(vba_ctx *c, const double *poses) {
   const int W = c->opt.win_size;
@@ -395,6 +375,9 @@ int ctx_allreduce(vba_ctx *c, double *buf, size_t n) {
   if (c->allreduce(c->allreduce_user, buf, n, c->stream)) { c->set_error("allreduce hook failed"); return VBA_ERR_HIP; }
   return VBA_OK;
 }
+}  // namespace
+
+namespace vba {
 // All-gather in place: buf holds n_ranks chunks of `chunk` doubles, rank r has filled chunk r.  RCCL moves every chunk once;
 // the hook (SUM only) emulates it by zeroing the foreign chunks first.
 int ctx_allgather(vba_ctx *c, double *buf, size_t chunk) {
@@ -409,6 +392,9 @@ int ctx_allgather(vba_ctx *c, double *buf, size_t chunk) {
     if (r != c->rank) HIPCHK(c, hipMemsetAsync(buf + (size_t)r * chunk, 0, chunk * sizeof(double), c->stream));
   return ctx_allreduce(c, buf, chunk * (size_t)c->n_ranks);
 }
+}  // namespace vba
+
+namespace {
 
 // device passes on device-resident poses (gate == nullptr: unconditional)
 int hessian_pass(vba_ctx *c, const double *poses_dev, const int *gate, int head, int end, LmDev *lm = nullptr, const double *k4p = nullptr, int k4nb = 0,
@@ -964,9 +950,10 @@ static int launch_li_solve(vba_ctx *c, int copy_raw, int n, int gauge, int grav)
                      c->opt.imu_coef, c->d_liscr, nullptr);
   return VBA_OK;
 }
+namespace vba {
+bool li_device_supported(int W) { return W >= 2 && W <= LI_MAX_W; }
+}
 }  // extern "C++"
-
-static bool li_device_supported(int W) { return W >= 2 && W <= LI_MAX_W; }
 
 static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, int max_iter, double *hess, double *resis2) {
   static const bool want_times = diag_env("VBA_LI_TIMES") != nullptr;   // diagnostic: host-side phases of one call
@@ -1176,655 +1163,6 @@ int vba_li_ba_damping_iter(vba_ctx *c, double *states, double *imus, int gravity
   return li_ba_device(c, states, imus, gravity, max_iter, hess, resis2);
 }
 
-// ---------------------------------------------------------------- initialisation odometry on a point-cloud map (vba_kernels_kd.hpp)
-static int kd_reserve(vba_ctx *c, size_t pts) {
-  if (pts <= c->kd_cap) return VBA_OK;
-  size_t cap = c->kd_cap ? c->kd_cap : 65536;
-  while (cap < pts) cap *= 2;
-  for (int i = 0; i < 2; i++) {
-    double *nw = nullptr;
-    HIPCHK(c, hipMalloc((void **)&nw, cap * 3 * sizeof(double)));
-    if (c->d_kdtree[i]) {
-      if (i == c->kd_cur && c->kd_n > 0) HIPCHK(c, hipMemcpyAsync(nw, c->d_kdtree[i], (size_t)c->kd_n * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      hipFree(c->d_kdtree[i]);
-    }
-    c->d_kdtree[i] = nw;
-  }
-  c->kd_cap = cap;
-  c->kd_allocs += 2; c->kd_bytes += (int64_t)(2 * cap * 3 * sizeof(double));
-  return VBA_OK;
-}
-// map slices of the 5-NN search for nb workgroups of scan points: enough workgroups to cover the chip
-static int kd_slices_of(int nb) { return nb >= 512 ? 1 : (nb >= 128 ? 4 : 8); }
-int vba_odom_kdtree_reset(vba_ctx *c) { c->kd_n = 0; return VBA_OK; }
-int vba_odom_kdtree_size(vba_ctx *c) { return c->kd_n; }
-int vba_odom_kdtree_points(vba_ctx *c, double *out) {
-  if (!out && c->kd_n > 0) return VBA_ERR_BAD_ARG;
-  if (c->kd_n == 0) return VBA_OK;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpyAsync(out, c->d_kdtree[c->kd_cur], (size_t)c->kd_n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return VBA_OK;
-}
-
-// ---------------------------------------------------------------- its EKF loop, resident on the device
-// device state and pinned image of the resident EKF loops (this one and the voxel map's)
-static int odom_image_ensure(vba_ctx *c) {
-  if (c->d_odom) return VBA_OK;
-  HIPCHK(c, hipMalloc((void **)&c->d_odom, sizeof(vbh::OdomEkf)));
-  HIPCHK(c, hipHostMalloc((void **)&c->h_odom, sizeof(vbh::OdomEkf), hipHostMallocDefault));
-  c->kd_allocs += 2; c->kd_bytes += (int64_t)(2 * sizeof(vbh::OdomEkf));
-  return VBA_OK;
-}
-static size_t kd_up(size_t b) { return (b + 255) & ~(size_t)255; }
-// scratch sized by a scan of up to p points: planes [p][4] | partials [ceil(p / 256)][34] | candidates at the slice count that
-// needs the most of them among the scans of up to p points
-struct KdScanLayout { size_t o_part, o_cand, bytes; };
-static KdScanLayout kd_scan_layout(size_t p) {
-  const size_t a = 8 * std::min<size_t>(p, 127 * 256), b = 4 * std::min<size_t>(p, 511 * 256);
-  KdScanLayout L;
-  L.o_part = kd_up(p * 4 * sizeof(double));
-  L.o_cand = L.o_part + kd_up(((p + 255) / 256) * 34 * sizeof(double));
-  L.bytes = L.o_cand + kd_up(std::max(std::max(a, b), p) * 5 * sizeof(unsigned long long));
-  return L;
-}
-static int kd_scan_ensure(vba_ctx *c, size_t pts) {
-  if (pts <= c->kdscan_pts) return VBA_OK;
-  size_t cap = c->kdscan_pts ? c->kdscan_pts : 16384;
-  while (cap < pts) cap *= 2;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->d_kdscan) hipFree(c->d_kdscan);
-  c->d_kdscan = nullptr; c->kdscan_pts = 0;
-  const size_t b = kd_scan_layout(cap).bytes;
-  HIPCHK(c, hipMalloc((void **)&c->d_kdscan, b));
-  c->kdscan_pts = cap; c->kd_allocs++; c->kd_bytes += (int64_t)b;
-  return VBA_OK;
-}
-// scratch sized by map + scan of up to p points: the re-sampler's count [p] | first [p] | work area (the deterministic layout, the larger)
-static int kd_ws_ensure(vba_ctx *c, size_t pts) {
-  if (pts <= c->kdws_pts) return VBA_OK;
-  if (pts > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
-  size_t cap = c->kdws_pts ? c->kdws_pts : 65536;
-  while (cap < pts) cap *= 2;
-  int st = VBA_OK;
-  const size_t ws = kf_ws_layout(c, (int)cap, true, nullptr, nullptr, &st);
-  if (st) return st;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->d_kdws) hipFree(c->d_kdws);
-  c->d_kdws = nullptr; c->kdws_pts = 0; c->kdws_bytes = 0;
-  const size_t b = 2 * kd_up(cap * sizeof(int)) + ws;
-  HIPCHK(c, hipMalloc((void **)&c->d_kdws, b));
-  c->kdws_pts = cap; c->kdws_bytes = b; c->kd_allocs++; c->kd_bytes += (int64_t)b;
-  return VBA_OK;
-}
-
-int vba_odom_kdtree_reserve(vba_ctx *c, int max_map_points, int max_scan_points) {
-  if (!c || max_map_points < 0 || max_scan_points < 0 || max_map_points > (1 << 28) || max_scan_points > (1 << 28)) return VBA_ERR_BAD_ARG;
-  int st = odom_image_ensure(c);
-  if (st || (st = kd_reserve(c, (size_t)max_map_points + 16)) || (st = kd_scan_ensure(c, (size_t)max_scan_points)) ||
-      (st = kd_ws_ensure(c, (size_t)max_map_points)))
-    return st;
-  return VBA_OK;
-}
-int vba_odom_kdtree_allocations(vba_ctx *c, int *n_allocs, int64_t *bytes) {
-  if (!c || !n_allocs || !bytes) return VBA_ERR_BAD_ARG;
-  *n_allocs = c->kd_allocs; *bytes = c->kd_bytes;
-  return VBA_OK;
-}
-
-// One update on a scan in device memory, c->kd_n + n <= 2^28.  With fewer than 100 map points the scan only seeds the map (VS:1105-1118):
-// the append is enqueued, *ran stays false and nothing is waited for.  Otherwise state and cov are updated, the call has completed on
-// return and c->h_odom holds the loop's result block.  Nothing here touches c->d_stage: a caller may keep the scan there.
-static int kd_odom_core(vba_ctx *c, int n, const double *d_pts, double *state, double *cov, bool *ran) {
-  *ran = false;
-  const int nb = (n + 255) / 256, kd_slices = kd_slices_of(nb);
-  const size_t tot = (size_t)c->kd_n + (size_t)n;
-  int st = kd_reserve(c, tot + 16);
-  if (st) return st;
-  if (c->kd_n < 100) {
-    if (n > 0) {
-      KdPose X;
-      std::memcpy(X.R, state + 1, sizeof(X.R)); std::memcpy(X.t, state + 10, sizeof(X.t));
-      hipLaunchKernelGGL(k_kd_append, dim3(nb), dim3(256), 0, c->stream, n, d_pts, X, c->d_kdtree[c->kd_cur] + (size_t)c->kd_n * 3);
-      HIPCHK(c, hipGetLastError());
-    }
-    c->kd_n += n;
-    return VBA_OK;
-  }
-  if ((st = odom_image_ensure(c)) || (st = kd_scan_ensure(c, (size_t)n)) || (st = kd_ws_ensure(c, tot))) return st;
-  const bool det = c->opt.deterministic != 0;
-  int *d_cnt = (int *)c->d_kdws, *d_first = (int *)(c->d_kdws + kd_up(c->kdws_pts * sizeof(int)));
-  char *ws = c->d_kdws + 2 * kd_up(c->kdws_pts * sizeof(int));
-  DsWork w{};
-  if (2 * kd_up(c->kdws_pts * sizeof(int)) + kf_ws_layout(c, (int)tot, det, ws, &w, &st) > c->kdws_bytes || st) return st ? st : VBA_ERR_CAPACITY;
-  const KdScanLayout L = kd_scan_layout(c->kdscan_pts);
-  double *d_pl = (double *)c->d_kdscan, *d_part = (double *)(c->d_kdscan + L.o_part);
-  unsigned long long *d_cand = (unsigned long long *)(c->d_kdscan + L.o_cand);
-  // the image: cov_inv = P^-1 / 1000 entry by entry (VS:1134, VS:1213), the first iteration searches
-  double cov_inv[225];
-  vbh::inverse_pplu(cov, cov_inv, VBA_DIM);
-  for (int k = 0; k < 225; k++) cov_inv[k] = cov_inv[k] / 1000;
-  vbh::OdomEkf &S = *c->h_odom;
-  vbh::odom_ekf_begin(S, state, cov, cov_inv);
-  S.refind = 1;
-  vbh::OdomEkf *d_S = c->d_odom;
-  hipStream_t s = c->stream;
-  double *tree = c->d_kdtree[c->kd_cur], *tree_out = c->d_kdtree[c->kd_cur ^ 1];
-  HIPCHK(c, hipMemcpyAsync(d_S, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
-  for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
-    if (n > 0) {
-      hipLaunchKernelGGL(k_kd_match_dev, dim3(nb, kd_slices), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, c->kd_n, (const double *)tree, d_cand);
-      hipLaunchKernelGGL(k_kd_fit_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, kd_slices, (const unsigned long long *)d_cand, (const double *)tree, d_pl);
-      hipLaunchKernelGGL(k_kd_accum_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, (const double *)d_pl, d_part);
-    }
-    // n == 0: nb == 0 and d_part may be NULL (no scan scratch was ever needed); the reduction reads nb * 34 doubles, that is none
-    hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, s, d_S, (const double *)d_part, nb, iter, 1);
-  }
-  // map update VS:1238-1250: the scan appended in the refined pose, map + scan re-sampled on a 0.5 m grid into the other half; the
-  // voxel count lands in the result block
-  if (n > 0) hipLaunchKernelGGL(k_kd_append_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, tree + (size_t)c->kd_n * 3);
-  w.n_out = &d_S->n_map;
-  if ((st = ds_core(c, s, 0, (int)tot, tree, nullptr, 9, 4, 0.5, det, w))) return st;
-  hipLaunchKernelGGL(k_ds_emit, dim3(((int)tot + 255) / 256), dim3(256), 0, s, (int)tot, (const DsSlot *)w.tab, (const int *)w.slot, (const int *)w.blk, tree_out, d_cnt,
-                     d_first, (double *)nullptr, 0);
-  HIPCHK(c, hipGetLastError());
-  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
-  HIPCHK(c, hipMemcpyAsync((char *)&S + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  if (S.n_map < 1 || (size_t)S.n_map > tot) { c->set_error("kd-tree odometry: voxel count of the re-sampled map out of range"); return VBA_ERR_HIP; }
-  c->kd_cur ^= 1; c->kd_n = S.n_map;
-  std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
-  std::memcpy(cov, S.P_out, sizeof(S.P_out));
-  *ran = true;
-  return VBA_OK;
-}
-
-int vba_odom_lio_state_estimation_kdtree_resident(vba_ctx *c, int n, const double *d_pnt_body, double *state, double *cov, int *iterations,
-                                                  vba_odom_report *report) {
-  if (!c || n < 0 || (n > 0 && !d_pnt_body) || !state || !cov) return VBA_ERR_BAD_ARG;
-  if (iterations) *iterations = 0;
-  if (report) std::memset(report, 0, sizeof(*report));
-  if ((size_t)c->kd_n + (size_t)n > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
-  bool ran;
-  const int st = kd_odom_core(c, n, d_pnt_body, state, cov, &ran);
-  if (st || !ran) return st;
-  const vbh::OdomEkf &S = *c->h_odom;
-  if (iterations) *iterations = S.iterations;
-  if (report) {
-    report->iterations = S.iterations;
-    for (int k = 0; k < 4; k++) { report->match_num[k] = S.match_num[k]; report->rot_add[k] = S.rot_add[k]; report->tra_add[k] = S.tra_add[k]; }
-    report->nnt_eig_min = 0.0;
-  }
-  return VBA_OK;
-}
-
-// The staging front end of the same update: the scan may be in host or device memory and the call has completed when it returns.
-int vba_odom_lio_state_estimation_kdtree(vba_ctx *c, int n, const double *pnt_body, double *state, double *cov, int *iterations) {
-  if (n < 0 || (n > 0 && !pnt_body) || !state || !cov) return VBA_ERR_BAD_ARG;
-  if (iterations) *iterations = 0;
-  if ((size_t)c->kd_n + (size_t)n > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
-  int st = ensure_stage(c, (size_t)n * 3 * sizeof(double));
-  if (st) return st;
-  if (n > 0) HIPCHK(c, hipMemcpyAsync(c->d_stage, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
-  bool ran;
-  if ((st = kd_odom_core(c, n, (const double *)c->d_stage, state, cov, &ran))) return st;
-  if (!ran) HIPCHK(c, hipStreamSynchronize(c->stream));                    // seeded: the core only enqueued the append
-  else if (iterations) *iterations = c->h_odom->iterations;
-  return VBA_OK;
-}
-
-// ---------------------------------------------------------------- hierarchical global BA (vba_kernels_gba.hpp)
-static GbaParams gba_params(vba_ctx *c, double voxel_size, double min_eig, const double *eig_array) {
-  GbaParams P;
-  P.voxel_size = voxel_size; P.min_eigen_value = min_eig; P.max_layer = c->opt.max_layer;
-  for (int k = 0; k < 4; k++) P.eig_array[k] = eig_array[k];
-  return P;
-}
-static int gba_build_into_store(vba_ctx *c, int wdsize, const int *offsets, const double *pl, const double *poses, const GbaParams &P) {
-  int nf = 0;
-  TimedSpan sp{};
-  span_begin(c, "gba_build", sp);
-  int st = gba_build(c->gba, c->stream, wdsize, offsets, pl, poses, P, &nf, c->err);
-  if (st) return st;
-  c->nvox = 0;
-  st = factor_reserve(c, nf > 0 ? nf : 1);
-  if (st) return st;
-  if (nf > 0) {
-    const int nn = c->gba.h_cnt[GCNT_NODES] < c->gba.v.cap ? c->gba.h_cnt[GCNT_NODES] : c->gba.v.cap;
-    hipLaunchKernelGGL(k_gba_extract, dim3((nn + 255) / 256, 10 * wdsize + 33), dim3(256), 0, c->stream, c->gba.v, c->fv);
-    factor_update_mask(c, 0, nf);
-    HIPCHK(c, hipGetLastError());
-  }
-  span_end(c, "gba_build", sp);
-  c->nvox = nf;
-  return VBA_OK;
-}
-static int gba_check(vba_ctx *c, int wdsize, const int *offsets, const double *pl, const double *poses) {
-  if (wdsize != c->opt.win_size) return VBA_ERR_UNSUPPORTED_WINDOW;
-  if (!offsets || !poses || offsets[0] != 0) return VBA_ERR_BAD_ARG;
-  for (int i = 0; i < wdsize; i++) if (offsets[i + 1] < offsets[i]) return VBA_ERR_BAD_ARG;
-  if (offsets[wdsize] > 0 && !pl) return VBA_ERR_BAD_ARG;
-  return VBA_OK;
-}
-int vba_gba_build(vba_ctx *c, int wdsize, const int *offsets, const double *pnt_local, const double *poses, double gba_voxel_size,
-                  double gba_min_eigen_value, const double *gba_eigen_value_array) {
-  int st = gba_check(c, wdsize, offsets, pnt_local, poses);
-  if (st) return st;
-  if (!gba_eigen_value_array) return VBA_ERR_BAD_ARG;
-  return gba_build_into_store(c, wdsize, offsets, pnt_local, poses, gba_params(c, gba_voxel_size, gba_min_eigen_value, gba_eigen_value_array));
-}
-
-// Lidar_BA_Optimizer::damping_iter (VM:422-497) for an arbitrary window: device Hessian / residual passes on the sparse
-// store, gauge + (H + uD) LDL^T + retraction on the host.
-// hdiag6_out: [W][W][6] = the six diagonal entries of every 6x6 block of *hess (all that HBA_add_edge reads of it, VS:2926-2951);
-// the n x n Hessian itself stays in HBM.
-static int big_damping_iter(vba_ctx *c, int W, double *poses, std::vector<double> &hdiag6_out, double *resis2, int max_iter, int thd_num, int *is_converge) {
-  BigStore &S = c->big;
-  const int n = 6 * W;
-  if (S.b.V < thd_num) return VBA_ERR_TOO_FEW_VOXELS;                 // VM:399-403
-  std::vector<double> x(poses, poses + (size_t)W * 12), xt(x), hd(n), JacT(n), dxi(n);
-  double u = 0.01, v = 2, residual1 = 0, residual2 = 0;
-  bool is_calc_hess = true, conv = true;
-  c->trace.clear();
-  for (int it = 0; it < max_iter; it++) {
-    if (is_calc_hess) {
-      int st = big_hessian(S, c->stream, x.data(), hd.data(), JacT.data(), &residual1, c->err);   // *hess = Hess (VM:446) stays on the device
-      if (st) return st;
-      for (int r = 0; r < 6; r++) { hd[r] = 1.0; JacT[r] = 0.0; }     // gauge VM:452-455 (k_bigl_setup applies it to the matrix)
-    }
-    if (it == 0) resis2[0] = residual1;
-    {
-      // pivot order of Eigen's LDLT (largest |stored diagonal| first, first index wins ties), then the device factorisation
-      std::vector<int> ord(n);
-      big_pivot_order(hd.data(), u, n, ord.data());
-      int st2 = big_solve(S, c->stream, ord.data(), u, dxi.data(), c->err);
-      if (st2) return st2;
-    }
-    for (int j = 0; j < W; j++) {
-      double E[9];
-      vbh::so3_exp(&dxi[6 * j], E);
-      vbh::m3_mul(&x[12 * j], E, &xt[12 * j]);
-      for (int k = 0; k < 3; k++) xt[12 * j + 9 + k] = x[12 * j + 9 + k] + dxi[6 * j + 3 + k];
-    }
-    const double q1 = big_q1(dxi.data(), hd.data(), JacT.data(), u, n);
-    int st = big_residual(S, c->stream, xt.data(), &residual2, c->err);
-    if (st) return st;
-    double q = residual1 - residual2;
-    const double tr[5] = {residual1, residual2, u, v, q1};
-    c->trace.insert(c->trace.end(), tr, tr + 5);
-    if (q > 0) {
-      x = xt;
-      q = q / q1;
-      v = 2;
-      q = 1 - std::pow(2 * q - 1, 3);
-      u *= (q < 1.0 / 3 ? 1.0 / 3 : q);
-      is_calc_hess = true;
-    } else {
-      u = u * v; v = 2 * v;
-      is_calc_hess = false; conv = false;
-    }
-    if (std::fabs((residual1 - residual2) / residual1) < 1e-6) break;
-  }
-  resis2[1] = residual2;
-  std::memcpy(poses, x.data(), x.size() * sizeof(double));
-  if (is_converge) *is_converge = conv ? 1 : 0;
-  hdiag6_out.resize((size_t)6 * W * W);
-  return big_block_diagonals(S, c->stream, hdiag6_out.data(), c->err);   // b.H still holds the last evaluated Hessian (a rejected step does not recompute it)
-}
-
-int vba_hba_add_edge(vba_ctx *c, int wdsize, const int *offsets, const double *pnt_local, double *poses, double gba_voxel_size,
-                     double gba_min_eigen_value, const double *gba_eigen_value_array, int max_iter, int thread_num, double *edges_out, int *n_edges,
-                     double *cloud_out, int *cloud_count, int *n_cloud, double *resis_log, int *n_log) {
-  const bool big = (wdsize != c->opt.win_size);      // any other window size (the top-level BA over all submaps): sparse path
-  if (big && wdsize < 2) return VBA_ERR_BAD_ARG;
-  int st = VBA_OK;
-  if (!big) st = gba_check(c, wdsize, offsets, pnt_local, poses);
-  else {
-    if (!offsets || !poses || offsets[0] != 0) return VBA_ERR_BAD_ARG;
-    for (int i = 0; i < wdsize; i++) if (offsets[i + 1] < offsets[i]) return VBA_ERR_BAD_ARG;
-    if (offsets[wdsize] > 0 && !pnt_local) return VBA_ERR_BAD_ARG;
-  }
-  if (st) return st;
-  if (!gba_eigen_value_array || !edges_out || !n_edges || (cloud_out && (!cloud_count || !n_cloud))) return VBA_ERR_BAD_ARG;
-  const int W = wdsize, n6 = 6 * W, n = offsets[W];
-  *n_edges = 0;
-  if (n_log) *n_log = 0;
-  static const bool want_times = diag_env("VBA_HBA_TIMES") != nullptr;      // diagnostic: wall-clock split of the call on stderr
-  double t_ph[5] = {0, 0, 0, 0, 0};
-  auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_mark = want_times ? now() : 0.0;
-  auto lap = [&](int k) { if (want_times) { hipStreamSynchronize(c->stream); const double t = now(); t_ph[k] += t - t_mark; t_mark = t; } };
-  // the keyframe clouds stay in HBM for the whole call (every outer iteration re-cuts them with the current poses)
-  if ((size_t)n * 3 > c->refpts_doubles) {
-    if (c->d_refpts) hipFree(c->d_refpts);
-    c->refpts_doubles = (size_t)n * 3 + 3072;
-    HIPCHK(c, hipMalloc((void **)&c->d_refpts, 2 * c->refpts_doubles * sizeof(double)));
-  }
-  double *d_pl = c->d_refpts, *d_ref = c->d_refpts + c->refpts_doubles;
-  if (n > 0) HIPCHK(c, hipMemcpyAsync(d_pl, pnt_local, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
-  GbaParams P = gba_params(c, gba_voxel_size, gba_min_eigen_value, gba_eigen_value_array);
-  std::vector<double> hess(big ? 0 : (size_t)n6 * n6, 0.0), hd6;      // the any-window path keeps *hess in HBM and returns its block diagonals
-  lap(0);
-  const int up = 4;                                                       // VS:2866
-  int converge_flag = 0;
-  double converge_thre = 0.05;
-  for (int iterCnt = 0; iterCnt < max_iter; iterCnt++) {
-    if (converge_flag == 1 || iterCnt == max_iter - 1)                    // VS:2871-2881: last pass with the local-map parameters
-      P = gba_params(c, c->opt.voxel_size, c->opt.min_eigen_value, c->opt.plane_eigen_value_thre);
-    double resis[2] = {0, 0};
-    int is_converge = 0;
-    if (!big) {
-      st = gba_build_into_store(c, W, offsets, d_pl, poses, P);
-      if (st) return st;
-      lap(1);
-      st = vba_lidar_ba_damping_iter(c, poses, hess.data(), resis, up, thread_num, &is_converge);
-    } else {
-      st = big_build(c->big, c->stream, W, offsets, d_pl, poses, P, c->err);
-      if (st) return st;
-      lap(1);
-      st = big_damping_iter(c, W, poses, hd6, resis, up, thread_num, &is_converge);
-    }
-    if (st) return st;
-    lap(2);
-    if (resis_log && n_log) { resis_log[2 * *n_log] = resis[0]; resis_log[2 * *n_log + 1] = resis[1]; (*n_log)++; }
-    if ((std::fabs(resis[0] - resis[1]) / resis[0] < converge_thre && is_converge) || (iterCnt == max_iter - 2 && converge_flag == 0)) {
-      converge_thre = 0.01;                                               // VS:2903-2915
-      if (converge_flag == 0) converge_flag = 1;
-      else if (converge_flag == 1) break;
-    }
-  }
-  int ne = 0;
-  for (int i = 0; i < W - 1; i++)
-    for (int j = i + 1; j < W; j++) {                                     // VS:2926-2951
-      bool isAdd = true;
-      double v6[6];
-      for (int k = 0; k < 6; k++) {
-        const double hc = std::fabs(big ? hd6[((size_t)i * W + j) * 6 + k] : hess[(size_t)(6 * i + k) * n6 + 6 * j + k]);
-        if (hc < 1e-6) { isAdd = false; break; }
-        v6[k] = 1.0 / hc;
-      }
-      if (!isAdd) continue;
-      double *o = edges_out + 20 * (size_t)ne++;
-      const double *Ri = poses + 12 * i, *Rj = poses + 12 * j;
-      o[0] = i; o[1] = j;
-      vbh::m3_Tmul(Ri, Rj, o + 2);
-      const double d[3] = {Rj[9] - Ri[9], Rj[10] - Ri[10], Rj[11] - Ri[11]};
-      vbh::m3_Tvec(Ri, d, o + 11);
-      for (int k = 0; k < 6; k++) o[14 + k] = v6[k];
-    }
-  *n_edges = ne;
-  lap(3);
-  if (cloud_out) {                                                        // VS:2954-2989
-    *n_cloud = 0;
-    if (n > 0) {
-      std::vector<double> rel((size_t)W * 12);
-      for (int i = 0; i < W; i++) {
-        const double *R0 = poses, *Ri = poses + 12 * i;
-        vbh::m3_Tmul(R0, Ri, rel.data() + 12 * i);
-        const double d[3] = {Ri[9] - R0[9], Ri[10] - R0[10], Ri[11] - R0[11]};
-        vbh::m3_Tvec(R0, d, rel.data() + 12 * i + 9);
-      }
-      double *d_rel = big ? c->big.g.poses : c->gba.v.poses;
-      const int *d_off = big ? c->big.g.offsets : c->gba.v.offsets;
-      HIPCHK(c, hipMemcpyAsync(d_rel, rel.data(), rel.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      hipLaunchKernelGGL(k_gba_to_ref, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, W, d_off, d_pl, d_rel, d_ref);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipStreamSynchronize(c->stream));      // rel is a host temporary
-      std::vector<int> first(n);
-      st = vba_scan_down_sampling_voxel(c, n, d_ref, c->opt.voxel_size / 8, cloud_out, cloud_count, first.data(), n_cloud);
-      if (st) return st;
-    }
-  }
-  lap(4);
-  if (want_times)
-    std::fprintf(stderr, "[hba_add_edge W=%d n=%d] upload %.0f  build %.0f  LM %.0f  edges %.0f  cloud %.0f us\n", W, n, t_ph[0], t_ph[1], t_ph[2], t_ph[3], t_ph[4]);
-  return VBA_OK;
-}
-
-// thd_globalmapping (VS:3018-3141), the optimisation work of the hierarchical global BA over one map:
-//   bottom layer  windows of `wdsize` keyframes, stride `mgsize` (VS:3033-3034, 3064-3066, 3136-3137): HBA_add_edge(xs = x0 of the
-//                 window, max_iter 1, thread_num 2) -> edges1 + one submap (pose x0 of the window's first keyframe, cloud
-//                 = the window's down-sampled points in that frame, VS:3084-3089);
-//   top layer     HBA_add_edge over all submaps with their CURRENT poses (VS:3096-3110): edges2.
-// Edge rows carry GLOBAL keyframe indices.  (Queue handling, map switching and the GTSAM pose graph stay with the caller.)
-int vba_hba_global(vba_ctx *c, int n_kf, const int *offsets, const double *pnt_local, const double *poses_x0, const double *poses_now,
-                   double gba_voxel_size, double gba_min_eigen_value, const double *gba_eigen_value_array, int total_max_iter, int wdsize, int mgsize,
-                   double *edges1_out, int cap1, int *n_edges1, double *edges2_out, int cap2, int *n_edges2) {
-  if (n_kf < 0 || wdsize < 2 || mgsize < 1 || !offsets || !poses_x0 || !poses_now || !gba_eigen_value_array || !n_edges1 || !n_edges2 ||
-      (offsets[n_kf] > 0 && !pnt_local))
-    return VBA_ERR_BAD_ARG;
-  *n_edges1 = 0; *n_edges2 = 0;
-  std::vector<int> sub_first, sub_n;                // global id of every submap's first keyframe, points of its cloud
-  std::vector<double> edges((size_t)(wdsize * (wdsize - 1) / 2 + 1) * 20);
-  // the keyframe clouds go to HBM once (the stride-5 windows overlap: every keyframe is used twice) and the submap clouds
-  // never leave it: every window's down-sampled cloud is written behind the previous one and the top-level BA reads them there
-  const size_t n_all = (size_t)offsets[n_kf];
-  size_t n_sub_cap = 0, n_win_max = 0;
-  for (int start = 0; start + wdsize <= n_kf; start += mgsize) {
-    const size_t nw = (size_t)(offsets[start + wdsize] - offsets[start]);
-    n_sub_cap += nw; if (nw > n_win_max) n_win_max = nw;
-  }
-  // More than one rank ("windows are independent problems => replicas across GPUs for the bottom layer"): window
-  // wi is optimised by rank wi % n_ranks with the exchange step switched off; every rank packs its windows' clouds and its
-  // [points, edges, status | edge rows] records into ITS chunk of two buffers, and one ALL-GATHER of each hands every rank all of
-  // them (a rank receives each foreign byte once).  A window that fails on one rank travels as its status word: every rank
-  // enters both collectives and all of them return the same error afterwards — no rank is left waiting in a collective.
-  // The top-level window then runs replicated (identical inputs on every rank).
-  const bool replicas = c->collective() && c->n_ranks > 1;
-  int n_win = 0;
-  for (int start = 0; start + wdsize <= n_kf; start += mgsize) n_win++;
-  // ONE rank: the windows are independent problems too, and one window is a chain of small kernels and host round trips that leaves
-  // most of the chip idle — KL worker contexts (own stream, own octree and LM state; host threads drive them) optimise windows
-  // side by side, with the bookkeeping of the replicas: worker t takes windows t, t + KL, ... and writes their clouds into its chunk.
-  const int kl_opt = c->opt.hba_workers > 0 ? (c->opt.hba_workers < 8 ? c->opt.hba_workers : 8) : 4;
-  const int KL = (!replicas && n_win >= 2 * kl_opt) ? kl_opt : 1;
-  const bool local_rep = KL > 1, chunked = replicas || local_rep;
-  const int NR = replicas ? c->n_ranks : KL;
-  const size_t meta_per = 3 + (size_t)(wdsize * (wdsize - 1) / 2) * 20;
-  const size_t win_per_rank = chunked ? (size_t)(n_win + NR - 1) / NR : 0, meta_chunk = meta_per * win_per_rank;
-  std::vector<size_t> rank_cap(NR, 0), win_roff(n_win > 0 ? n_win : 1, 0);      // points capacity per rank chunk, window offset inside it
-  if (chunked) {
-    int w = 0;
-    for (int start = 0; start + wdsize <= n_kf; start += mgsize, w++) {
-      win_roff[w] = rank_cap[w % NR];
-      rank_cap[w % NR] += (size_t)(offsets[start + wdsize] - offsets[start]);
-    }
-  }
-  size_t chunk_pts = 0;
-  for (int r = 0; r < NR; r++) if (rank_cap[r] > chunk_pts) chunk_pts = rank_cap[r];
-  if (!chunked) chunk_pts = 0;
-  const size_t need = (n_all + n_sub_cap + (size_t)NR * chunk_pts) * 3 + (size_t)NR * meta_chunk + 64;
-  if (need > c->hba_all_doubles) {
-    if (c->d_hba_all) hipFree(c->d_hba_all);
-    c->d_hba_all = nullptr; c->hba_all_doubles = 0;
-    HIPCHK(c, hipMalloc((void **)&c->d_hba_all, need * sizeof(double)));
-    c->hba_all_doubles = need;
-  }
-  double *d_all = c->d_hba_all, *d_sub = c->d_hba_all + n_all * 3;
-  if (n_all > 0 && !local_rep) HIPCHK(c, hipMemcpyAsync(d_all, pnt_local, n_all * 3 * sizeof(double), hipMemcpyDefault, c->stream));   // (the worker path uploads in chunks, under the first windows)
-  std::vector<int> ccnt(n_win_max > 0 ? n_win_max : 1);
-  size_t sub_off = 0;
-  double *d_rep = d_sub + n_sub_cap * 3, *d_meta = d_rep + (size_t)NR * chunk_pts * 3;      // replica mode only
-  std::vector<double> meta((size_t)NR * meta_chunk, 0.0);
-  struct Restore { vba_ctx *c; bool was; ~Restore() { c->collective_off = was; } } restore{c, c->collective_off};
-  if (replicas) c->collective_off = true;                                       // the windows' own LM loops must not enter a collective
-  int wi = -1;
-  static const bool want_times = diag_env("VBA_HBA_TIMES") != nullptr;
-  auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t_g0 = want_times ? (hipStreamSynchronize(c->stream), now()) : 0.0;
-  double t_g1 = 0;
-  if (local_rep) {
-    while ((int)c->hba_workers.size() < KL - 1) {
-      vba_options o = c->opt; o.stream = nullptr; o.device = c->device;
-      vba_ctx *w = nullptr;
-      const int stc = vba_create(&o, &w);
-      if (stc) { c->set_error("vba_hba_global: could not create a worker context"); return stc; }
-      c->hba_workers.push_back(w);
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int w = 0; w < n_win; w++) meta[(size_t)(w % KL) * meta_chunk + meta_per * (size_t)(w / KL) + 2] = -1.0;   // "not run"
-    std::vector<std::string> werr(KL);
-    // the keyframe clouds travel to HBM in chunks on a stream of their own while the first windows are already being optimised
-    // (2.4 GB at full length: as long as the windows themselves); a window starts when its keyframes have arrived
-    std::atomic<int> kf_ready{0}, give_up{0};
-    auto work = [&](int tw) {
-      vba_ctx *cx = tw == 0 ? c : c->hba_workers[tw - 1];
-      hipSetDevice(c->device);
-      std::vector<double> ed(edges.size());
-      std::vector<int> cc(ccnt.size()), off(wdsize + 1);
-      for (int w = tw; w < n_win; w += KL) {
-        const int start = w * mgsize;
-        while (kf_ready.load(std::memory_order_acquire) < start + wdsize && !give_up.load()) std::this_thread::sleep_for(std::chrono::microseconds(20));
-        if (give_up.load()) return;
-        for (int i = 0; i <= wdsize; i++) off[i] = offsets[start + i] - offsets[start];
-        std::vector<double> xs(poses_x0 + (size_t)start * 12, poses_x0 + (size_t)(start + wdsize) * 12);
-        int ne = 0, nc = 0;
-        double *mrec = &meta[(size_t)tw * meta_chunk + meta_per * (size_t)(w / KL)];
-        const int st = vba_hba_add_edge(cx, wdsize, off.data(), d_all + (size_t)offsets[start] * 3, xs.data(), gba_voxel_size, gba_min_eigen_value,
-                                        gba_eigen_value_array, 1, 2, ed.data(), &ne, d_rep + ((size_t)tw * chunk_pts + win_roff[w]) * 3,
-                                        cc.data(), &nc, nullptr, nullptr);
-        mrec[2] = st;
-        if (st != VBA_OK) { werr[tw] = cx->err; return; }
-        mrec[0] = nc; mrec[1] = ne;
-        std::memcpy(mrec + 3, ed.data(), (size_t)ne * 20 * sizeof(double));
-      }
-    };
-    int up_status = VBA_OK;
-    {
-      std::vector<std::thread> th;
-      for (int tw = 0; tw < KL; tw++) th.emplace_back(work, tw);
-      // (one uploader: three threads staging chunks in turn moved the pageable copy no faster — 4-5 GB/s either way; at full
-      //  length the call is bound by this copy once the windows overlap it)
-      hipStream_t up = nullptr;
-      if (hipStreamCreateWithFlags(&up, hipStreamNonBlocking) != hipSuccess) { up_status = VBA_ERR_HIP; give_up.store(1); }
-      const int CH = 16;                                                           // keyframes per chunk
-      for (int k0 = 0; k0 < n_kf && up_status == VBA_OK; k0 += CH) {
-        const int k1 = k0 + CH < n_kf ? k0 + CH : n_kf;
-        const size_t o0 = (size_t)offsets[k0] * 3, nb = (size_t)(offsets[k1] - offsets[k0]) * 3 * sizeof(double);
-        if (nb > 0 && (hipMemcpyAsync(d_all + o0, pnt_local + o0, nb, hipMemcpyDefault, up) != hipSuccess || hipStreamSynchronize(up) != hipSuccess)) {
-          up_status = VBA_ERR_HIP; give_up.store(1); break;
-        }
-        kf_ready.store(k1, std::memory_order_release);
-      }
-      if (up) hipStreamDestroy(up);
-      for (auto &x : th) x.join();
-    }
-    hipSetDevice(c->device);
-    if (up_status != VBA_OK) { c->set_error("vba_hba_global: uploading the keyframe clouds failed"); return up_status; }
-    for (int w = 0; w < n_win; w++) {                                            // the first failing window in window order decides
-      const int stw = (int)meta[(size_t)(w % KL) * meta_chunk + meta_per * (size_t)(w / KL) + 2];
-      if (stw > 0) { if (!werr[w % KL].empty()) c->set_error(werr[w % KL]); return stw; }
-    }
-    for (int w = 0; w < n_win; w++) {
-      const double *mrec = &meta[(size_t)(w % KL) * meta_chunk + meta_per * (size_t)(w / KL)];
-      if ((int)mrec[2] != VBA_OK) { c->set_error("vba_hba_global: a bottom-layer window was not run"); return VBA_ERR_HIP; }
-      const int nc = (int)mrec[0], ne = (int)mrec[1], start = w * mgsize;
-      for (int e = 0; e < ne; e++) {
-        if (*n_edges1 >= cap1) return VBA_ERR_CAPACITY;
-        double *o = edges1_out + (size_t)(*n_edges1) * 20;
-        std::memcpy(o, mrec + 3 + (size_t)e * 20, 20 * sizeof(double));
-        o[0] += start; o[1] += start;
-        (*n_edges1)++;
-      }
-      if (nc > 0) HIPCHK(c, hipMemcpyAsync(d_sub + sub_off * 3, d_rep + ((size_t)(w % KL) * chunk_pts + win_roff[w]) * 3, (size_t)nc * 3 * sizeof(double),
-                                           hipMemcpyDeviceToDevice, c->stream));
-      sub_first.push_back(start);
-      sub_n.push_back(nc);
-      sub_off += (size_t)nc;
-    }
-  }
-  for (int start = 0; !local_rep && start + wdsize <= n_kf; start += mgsize) {
-    std::vector<int> off(wdsize + 1);
-    for (int i = 0; i <= wdsize; i++) off[i] = offsets[start + i] - offsets[start];
-    std::vector<double> xs(poses_x0 + (size_t)start * 12, poses_x0 + (size_t)(start + wdsize) * 12);
-    int ne = 0, nc = 0;
-    wi++;
-    if (replicas) {
-      sub_first.push_back(start);
-      if (wi % NR != c->rank) continue;
-      double *mrec = &meta[(size_t)c->rank * meta_chunk + meta_per * (size_t)(wi / NR)];
-      const int st = vba_hba_add_edge(c, wdsize, off.data(), d_all + (size_t)offsets[start] * 3, xs.data(), gba_voxel_size, gba_min_eigen_value,
-                                      gba_eigen_value_array, 1, 2, edges.data(), &ne, d_rep + ((size_t)c->rank * chunk_pts + win_roff[wi]) * 3,
-                                      ccnt.data(), &nc, nullptr, nullptr);
-      mrec[2] = st;                            // travels with the gather: every rank learns it
-      if (st == VBA_OK) {
-        mrec[0] = nc; mrec[1] = ne;
-        std::memcpy(mrec + 3, edges.data(), (size_t)ne * 20 * sizeof(double));
-      }
-      continue;
-    }
-    int st = vba_hba_add_edge(c, wdsize, off.data(), d_all + (size_t)offsets[start] * 3, xs.data(), gba_voxel_size, gba_min_eigen_value,
-                              gba_eigen_value_array, 1, 2, edges.data(), &ne, d_sub + sub_off * 3, ccnt.data(), &nc, nullptr, nullptr);
-    if (st) return st;
-    for (int e = 0; e < ne; e++) {
-      if (*n_edges1 >= cap1) return VBA_ERR_CAPACITY;
-      double *o = edges1_out + (size_t)(*n_edges1) * 20;
-      std::memcpy(o, &edges[(size_t)e * 20], 20 * sizeof(double));
-      o[0] += start; o[1] += start;
-      (*n_edges1)++;
-    }
-    sub_first.push_back(start);
-    sub_n.push_back(nc);
-    sub_off += (size_t)nc;
-  }
-  if (replicas) {
-    c->collective_off = restore.was;
-    if (meta_chunk > 0)
-      HIPCHK(c, hipMemcpyAsync(d_meta + (size_t)c->rank * meta_chunk, meta.data() + (size_t)c->rank * meta_chunk, meta_chunk * sizeof(double),
-                               hipMemcpyHostToDevice, c->stream));
-    int rc = ctx_allgather(c, d_rep, chunk_pts * 3);
-    if (rc) return rc;
-    rc = ctx_allgather(c, d_meta, meta_chunk);
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpyAsync(meta.data(), d_meta, meta.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int worst = VBA_OK;
-    for (int w = 0; w < n_win; w++) {
-      const int stw = (int)meta[(size_t)(w % NR) * meta_chunk + meta_per * (size_t)(w / NR) + 2];
-      if (stw != VBA_OK && worst == VBA_OK) worst = stw;
-    }
-    if (worst != VBA_OK) { c->set_error("a bottom-layer window failed on one of the ranks"); return worst; }   // the same on every rank
-    for (int w = 0; w < n_win; w++) {
-      const double *mrec = &meta[(size_t)(w % NR) * meta_chunk + meta_per * (size_t)(w / NR)];
-      const int nc = (int)mrec[0], ne = (int)mrec[1], start = sub_first[w];
-      for (int e = 0; e < ne; e++) {
-        if (*n_edges1 >= cap1) return VBA_ERR_CAPACITY;
-        double *o = edges1_out + (size_t)(*n_edges1) * 20;
-        std::memcpy(o, mrec + 3 + (size_t)e * 20, 20 * sizeof(double));
-        o[0] += start; o[1] += start;
-        (*n_edges1)++;
-      }
-      if (nc > 0) HIPCHK(c, hipMemcpyAsync(d_sub + sub_off * 3, d_rep + ((size_t)(w % NR) * chunk_pts + win_roff[w]) * 3, (size_t)nc * 3 * sizeof(double),
-                                           hipMemcpyDeviceToDevice, c->stream));
-      sub_n.push_back(nc);
-      sub_off += (size_t)nc;
-    }
-  }
-  const int ns = (int)sub_first.size();
-  if (want_times) t_g1 = now();
-  struct Report { bool on; double t0, *t1; decltype(now) *clk; ~Report() { if (on) std::fprintf(stderr, "[hba_global] windows %.0f us, top %.0f us (after the upload)\n", *t1 - t0, (*clk)() - *t1); } } report{want_times, t_g0, &t_g1, &now};
-  if (ns >= 2) {
-    std::vector<int> off(ns + 1, 0);
-    for (int i = 0; i < ns; i++) off[i + 1] = off[i] + sub_n[i];
-    std::vector<double> xs((size_t)ns * 12), e2((size_t)(ns * (ns - 1) / 2 + 1) * 20);
-    for (int i = 0; i < ns; i++) std::memcpy(&xs[(size_t)i * 12], poses_now + (size_t)sub_first[i] * 12, 12 * sizeof(double));
-    int ne = 0;
-    int st = vba_hba_add_edge(c, ns, off.data(), d_sub, xs.data(), gba_voxel_size, gba_min_eigen_value, gba_eigen_value_array, total_max_iter, 5,
-                              e2.data(), &ne, nullptr, nullptr, nullptr, nullptr, nullptr);
-    if (st) return st;
-    for (int e = 0; e < ne; e++) {
-      if (*n_edges2 >= cap2) return VBA_ERR_CAPACITY;
-      double *o = edges2_out + (size_t)(*n_edges2) * 20;
-      std::memcpy(o, &e2[(size_t)e * 20], 20 * sizeof(double));
-      o[0] = sub_first[(int)e2[(size_t)e * 20]]; o[1] = sub_first[(int)e2[(size_t)e * 20 + 1]];
-      (*n_edges2)++;
-    }
-  }
-  return VBA_OK;
-}
-
 // ---------------------------------------------------------------- IMU factor (host)
 int vba_imu_preintegrate(int n, const double *t, const double *gyr, const double *acc, const double *bg, const double *ba,
                          const double *nm6, const double *nw6, double scale_gravity, double *out) {
@@ -1990,298 +1328,6 @@ int vba_map_reset(vba_ctx *c) { return map_reset(c->map, c->stream, c->err); }
 int vba_map_num_roots(vba_ctx *c) { return map_num_roots(c->map, c->stream, false); }
 int vba_map_num_slide_roots(vba_ctx *c) { return map_num_roots(c->map, c->stream, true); }
 int vba_map_stats(vba_ctx *c, long long *out8) { return out8 ? map_stats(c->map, c->stream, out8, c->err) : VBA_ERR_BAD_ARG; }
-// ---------------------------------------------------------------- LiDAR-inertial initialisation (VS:617-819)
-int vba_init_imu_poses(int m, const double *imu, const double *state_c, const double *state_l, double beg_time, double scale_gravity,
-                       double *out) {
-  if (m < 0 || (m > 0 && !imu) || !state_c || !state_l || (m > 1 && !out)) return VBA_ERR_BAD_ARG;
-  init_imu_poses(m, imu, state_c, state_l, beg_time, scale_gravity, out);
-  return VBA_OK;
-}
-int vba_init_align_gravity(int n, double *states) {
-  if (n < 1 || !states) return VBA_ERR_BAD_ARG;
-  init_align_gravity(n, states);
-  return VBA_OK;
-}
-
-namespace {
-// Restores the map's own thresholds however vba_motion_init returns (the context's options are never written).
-struct ThrOverride {
-  MapStore &s;
-  explicit ThrOverride(MapStore &m) : s(m) {}
-  void set(bool on) {
-    s.thr_override = on;
-    s.ovr_min_eigen_value = 0.02;                              // VS:624-627
-    for (int k = 0; k < 4; k++) s.ovr_plane_thre[k] = 1.0 / 4; // VS:628-630 (stored inverted)
-  }
-  ~ThrOverride() { s.thr_override = false; }
-};
-}
-
-static int motion_init_impl(vba_ctx *c, int W, const int *pt_offsets, const double *pnt, const double *curv, const int *imu_offsets, const double *imu,
-                    const double *beg_times, const double *ext_pose, double dept_err, double beam_err, double scale_gravity, int point_notime,
-                    const double *nm6, const double *nw6, double *states, const double *covs, double *imus, double *hess, int *converged,
-                    double *eigvalue3, int *iterations, int *thresholds_left_relaxed, double *round_log, int max_rounds, double *pnt_out,
-                    double *var_out, int *pvec_offsets, int pvec_cap, bool &started) {
-  if (!c || W != c->opt.win_size || W < 2 || !pt_offsets || !imu_offsets || !beg_times || !ext_pose || !nm6 || !nw6 || !states || !covs || !imus ||
-      !converged || !eigvalue3 || !iterations || !thresholds_left_relaxed || (round_log && max_rounds < 0) || (pnt_out && (!var_out || !pvec_offsets)))
-    return VBA_ERR_BAD_ARG;
-  if (!li_device_supported(W)) return VBA_ERR_UNSUPPORTED_WINDOW;
-  const int np = pt_offsets[W];
-  if (pt_offsets[0] != 0 || np < 0 || (np > 0 && (!pnt || !curv)) || imu_offsets[0] != 0 || imu_offsets[W] < 0 || (imu_offsets[W] > 0 && !imu))
-    return VBA_ERR_BAD_ARG;
-  for (int i = 0; i < W; i++)
-    if (pt_offsets[i + 1] < pt_offsets[i] || imu_offsets[i + 1] < imu_offsets[i]) return VBA_ERR_BAD_ARG;
-  for (int i = 0; i < W; i++) {                   // each deque's times ascend (the blur's binary search needs descending pose times)
-    for (int k = imu_offsets[i] + 1; k < imu_offsets[i + 1]; k++)
-      if (imu[7 * (size_t)k] < imu[7 * (size_t)(k - 1)]) return VBA_ERR_BAD_ARG;
-    if (i > 0 && imu_offsets[i + 1] == imu_offsets[i]) return VBA_ERR_BAD_ARG;   // IMU_PRE::push_imu needs samples (VS:729)
-  }
-
-  // The walk's shape depends on the curvatures and the IMU / scan times only, not on the states: rows per scan are fixed for the call.
-  std::vector<InitScan> scans(W);
-  int n_out = 0, n_pose = 0;
-  for (int i = 0; i < W; i++) {
-    InitScan &S = scans[i];
-    std::memset(&S, 0, sizeof(S));
-    S.pt_off = pt_offsets[i]; S.n_pts = pt_offsets[i + 1] - pt_offsets[i];
-    const int m = imu_offsets[i + 1] - imu_offsets[i];
-    S.pose_off = n_pose; S.n_pose = m > 1 ? m - 1 : 0;
-    S.notime = point_notime != 0;
-    S.k0 = -1;
-    if (S.notime) { S.j_min = 0; S.n_out = S.n_pts; }
-    else if (S.n_pose == 0 || S.n_pts == 0) { S.j_min = S.n_pts; S.n_out = 0; }
-    else {
-      const double *im = imu + 7 * (size_t)imu_offsets[i];
-      const double *cv = curv + S.pt_off;
-      const double t_last = im[0] - beg_times[i];                                 // oldest pose: head = the deque's first sample
-      int j = S.n_pts;
-      while (j > 0 && cv[j - 1] > t_last) j--;                                      // the walk stops at the first point at or before it
-      S.j_min = j;
-      int dups = 0;
-      if (j == 0) {
-        int k = 0;                                                                  // pose that pushes point 0: first with t < curvature
-        while (k < S.n_pose && !((im[7 * (size_t)(m - 2 - k)] - beg_times[i]) < cv[0])) k++;
-        S.k0 = k;
-        dups = S.n_pose - 1 - k;
-      }
-      S.n_out = S.n_pts - j + dups;
-    }
-    S.out_off = n_out;
-    n_out += S.n_out;
-    n_pose += S.n_pose;
-    S.range_inc = (float)dept_err; S.degree_inc = (float)beam_err;
-    for (int k = 0; k < 9; k++) S.Rx[k] = ext_pose[k];
-    for (int k = 0; k < 3; k++) S.tx[k] = ext_pose[9 + k];
-  }
-  if (pvec_offsets) for (int i = 0; i <= W; i++) pvec_offsets[i] = i < W ? scans[i].out_off : n_out;
-  if (pnt_out && n_out > pvec_cap) return VBA_ERR_CAPACITY;
-
-  // the IMU deques split once for the re-preintegration (VS:724-730)
-  std::vector<std::vector<double>> it(W), ig(W), ia(W);
-  for (int i = 0; i < W; i++) {
-    const int m = imu_offsets[i + 1] - imu_offsets[i];
-    const double *im = imu + 7 * (size_t)imu_offsets[i];
-    it[i].resize(m); ig[i].resize(3 * (size_t)m); ia[i].resize(3 * (size_t)m);
-    for (int k = 0; k < m; k++) {
-      it[i][k] = im[7 * k];
-      for (int q = 0; q < 3; q++) { ig[i][3 * k + q] = im[7 * k + 1 + q]; ia[i][3 * k + q] = im[7 * k + 4 + q]; }
-    }
-  }
-  // device buffer: raw cloud + curvatures (uploaded once), blurred rows + their var, pose tables, scan table, Σ n nᵀ partials and result
-  const size_t b_pnt = (size_t)np * 24, b_cv = (size_t)np * 8, b_pb = (size_t)n_out * 24, b_var = (size_t)n_out * 72,
-               b_pose = (size_t)n_pose * INIT_POSE_LEN * 8, b_sc = (size_t)W * sizeof(InitScan), b_nnt = (size_t)(INIT_NNT_WG * 6 + 16) * 8;
-  const size_t need = b_pnt + b_cv + b_pb + b_var + b_pose + b_sc + b_nnt + 64;
-  if (need > c->init_bytes) {
-    if (c->d_init) hipFree(c->d_init);
-    c->d_init = nullptr; c->init_bytes = 0;
-    HIPCHK(c, hipMalloc(&c->d_init, need));
-    c->init_bytes = need;
-  }
-  char *base = (char *)c->d_init;
-  double *d_pnt = (double *)base, *d_cv = (double *)(base + b_pnt), *d_pb = (double *)(base + b_pnt + b_cv), *d_var = (double *)(base + b_pnt + b_cv + b_pb),
-         *d_pose = (double *)(base + b_pnt + b_cv + b_pb + b_var);
-  InitScan *d_sc = (InitScan *)(base + b_pnt + b_cv + b_pb + b_var + b_pose);
-  double *d_part = (double *)(base + b_pnt + b_cv + b_pb + b_var + b_pose + b_sc), *d_nnt = d_part + INIT_NNT_WG * 6;
-  if (np > 0) {
-    HIPCHK(c, hipMemcpyAsync(d_pnt, pnt, b_pnt, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_cv, curv, b_cv, hipMemcpyHostToDevice, c->stream));
-  }
-
-  ThrOverride thr(c->map);
-  thr.set(true);
-  started = true;                                 // from here on a failure leaves device state behind
-  bool relaxed = true;
-  std::vector<double> ptab((size_t)n_pose * INIT_POSE_LEN + 1);
-  std::vector<double> poses((size_t)W * 12);
-  double last_nnt[9] = {0};
-  int converge_flag = 0, rounds = 0, st = VBA_OK;
-  double converge_thre = 0.05;
-  bool is_degrade = true;
-  double eig[3] = {0, 0, 0};
-  for (int iterCnt = 0; iterCnt < 10; iterCnt++) {
-    rounds = iterCnt + 1;
-    if (converge_flag == 1 && relaxed) { thr.set(false); relaxed = false; }    // VS:643-647
-    st = map_reset(c->map, c->stream, c->err); if (st) return st;              // VS:650-661
-    for (int i = 0; i < W; i++) {
-      InitScan &S = scans[i];
-      const double *xc = states + (size_t)VBA_STATE_LEN * i, *xl = states + (size_t)VBA_STATE_LEN * (i == 0 ? 0 : i - 1);
-      if (!S.notime && S.n_pose > 0)
-        init_imu_poses(S.n_pose + 1, imu + 7 * (size_t)imu_offsets[i], xc, xl, beg_times[i], scale_gravity, ptab.data() + (size_t)INIT_POSE_LEN * S.pose_off);
-      for (int k = 0; k < 9; k++) S.R[k] = xc[1 + k];
-      for (int k = 0; k < 3; k++) S.p[k] = xc[10 + k];
-      const double *cv = covs + (size_t)VBA_DIM * VBA_DIM * i;
-      for (int r = 0; r < 3; r++)
-        for (int k = 0; k < 3; k++) { S.cov6[3 * r + k] = cv[r * VBA_DIM + k]; S.cov6[9 + 3 * r + k] = cv[(3 + r) * VBA_DIM + 3 + k]; }
-      S.conv = converge_flag;
-      for (int k = 0; k < 9; k++) poses[12 * i + k] = xc[1 + k];
-      for (int k = 0; k < 3; k++) poses[12 * i + 9 + k] = xc[10 + k];
-    }
-    if (n_pose > 0) HIPCHK(c, hipMemcpyAsync(d_pose, ptab.data(), b_pose, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_sc, scans.data(), b_sc, hipMemcpyHostToDevice, c->stream));
-    if (n_out > 0) {
-      TimedSpan sp{};
-      span_begin(c, "init", sp);
-      hipLaunchKernelGGL(k_init_blur, dim3((n_out + 255) / 256), dim3(256), 0, c->stream, W, n_out, d_sc, d_pose, d_pnt, d_cv, d_pb, d_var);
-      span_end(c, "init", sp);
-      HIPCHK(c, hipGetLastError());
-    }
-    // cut_voxel (VM:1896) per scan with win_count = i, straight from the blurred rows in HBM
-    for (int i = 0; i < W; i++) {
-      TimedSpan sp{};
-      span_begin(c, "insert", sp);
-      st = map_cut_voxel(c->map, c->stream, i, scans[i].n_out, d_pb + 3 * (size_t)scans[i].out_off, d_var + 9 * (size_t)scans[i].out_off,
-                         poses.data() + 12 * i, false, c->err);
-      span_end(c, "insert", sp);
-      if (st) return st;
-    }
-    st = vba_map_recut(c, W, poses.data(), 0); if (st) return st;               // recut + tras_opt over surf_map (VS:695-703)
-    const int nf = c->nvox;
-    double resis[2] = {0, 0};
-    double *log = (round_log && iterCnt < max_rounds) ? round_log + 5 * iterCnt : nullptr;
-    if (log) { log[0] = nf; log[1] = log[2] = 0.0; log[3] = vbh::norm3(states + 22); log[4] = converge_flag; }
-    if (nf < 10) break;                                                         // VS:706-707
-    st = vba_li_ba_damping_iter(c, states, imus, 1, 3, hess, resis); if (st) return st;   // LI_BA_OptimizerGravity::damping_iter(.., 3)
-    for (int i = 1; i < W; i++) {                                               // VS:719-730
-      const double *xp = states + (size_t)VBA_STATE_LEN * (i - 1);
-      st = vba_imu_preintegrate((int)it[i].size(), it[i].data(), ig[i].data(), ia[i].data(), xp + 16, xp + 19, nm6, nw6, scale_gravity,
-                                imus + (size_t)VBA_IMU_PRE_LEN * (i - 1));
-      if (st) return st;
-    }
-    bool stop = false;
-    if (std::fabs(resis[0] - resis[1]) / resis[0] < converge_thre && iterCnt >= 2) {   // VS:733-758
-      TimedSpan sp{};
-      span_begin(c, "init", sp);
-      const int nb = std::min(INIT_NNT_WG, (nf + 255) / 256);
-      hipLaunchKernelGGL(k_init_nnt_part, dim3(nb), dim3(256), 0, c->stream, c->fv, nf, d_part);
-      hipLaunchKernelGGL(k_init_nnt_fin, dim3(1), dim3(64), 0, c->stream, nb, d_part, d_nnt);
-      span_end(c, "init", sp);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipMemcpyAsync(last_nnt, d_nnt, 9 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      for (int k = 0; k < 3; k++) eig[k] = last_nnt[k];
-      is_degrade = eig[0] < 15;
-      converge_thre = 0.01;
-      if (converge_flag == 0) { init_align_gravity(W, states); converge_flag = 1; }
-      else stop = true;
-    }
-    if (log) { log[1] = resis[0]; log[2] = resis[1]; log[3] = vbh::norm3(states + 22); log[4] = converge_flag; }
-    if (stop) break;
-  }
-  const double gnm = vbh::norm3(states + (size_t)VBA_STATE_LEN * (W - 1) + 22);  // x_curr = x_buf[win_size - 1] (VS:761-762)
-  if (is_degrade || gnm < 9.6 || gnm > 10.0) converge_flag = 0;
-  if (converge_flag == 0) { st = map_reset(c->map, c->stream, c->err); if (st) return st; }   // VS:771-786
-  if (pnt_out && n_out > 0) {
-    HIPCHK(c, hipMemcpyAsync(pnt_out, d_pb, b_pb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(var_out, d_var, b_var, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *converged = converge_flag;
-  for (int k = 0; k < 3; k++) eigvalue3[k] = eig[k];
-  *iterations = rounds;
-  *thresholds_left_relaxed = relaxed ? 1 : 0;
-  return VBA_OK;
-}
-
-// A failing device step leaves no half-built window behind: the map is torn down and the factor store emptied (states / imus
-// are undefined then, as the header says).
-int vba_motion_init(vba_ctx *c, int W, const int *pt_offsets, const double *pnt, const double *curv, const int *imu_offsets, const double *imu,
-                    const double *beg_times, const double *ext_pose, double dept_err, double beam_err, double scale_gravity, int point_notime,
-                    const double *nm6, const double *nw6, double *states, const double *covs, double *imus, double *hess, int *converged,
-                    double *eigvalue3, int *iterations, int *thresholds_left_relaxed, double *round_log, int max_rounds, double *pnt_out,
-                    double *var_out, int *pvec_offsets, int pvec_cap) {
-  bool started = false;
-  const int st = motion_init_impl(c, W, pt_offsets, pnt, curv, imu_offsets, imu, beg_times, ext_pose, dept_err, beam_err, scale_gravity, point_notime,
-                                  nm6, nw6, states, covs, imus, hess, converged, eigvalue3, iterations, thresholds_left_relaxed, round_log, max_rounds,
-                                  pnt_out, var_out, pvec_offsets, pvec_cap, started);
-  if (st != VBA_OK && started) {
-    const std::string why = c->err;
-    map_reset(c->map, c->stream, c->err);
-    c->nvox = 0;
-    c->err = why;
-  }
-  return st;
-}
-
-// ---------------------------------------------------------------- odometry scan-to-map (VS:962-1098)
-// One update on a scan in device memory with the iterations resident on the device: the host inverts P once, writes
-// one image, queues the four (point loop, update) pairs and waits once; which of them do any work is decided by the `done` flag in the
-// device state.  state and cov are updated, c->h_odom holds the loop's result block.  Nothing here touches c->d_stage: a caller may keep
-// the scan there.  Runs on this rank's map, whatever n_ranks is.
-static int odom_core(vba_ctx *c, int n, const double *d_pts, const double *d_var, double *state, double *cov) {
-  int st = odom_image_ensure(c);
-  if (st) return st;
-  const size_t need = (size_t)((n + 255) / 256) * 34;
-  if (need > c->odom_part_doubles) {
-    if (c->d_odom_part) hipFree(c->d_odom_part);       // idle: the call that used it ended in a synchronise
-    c->d_odom_part = nullptr; c->odom_part_doubles = 0;
-    size_t cap = 256 * 34;
-    while (cap < need) cap *= 2;
-    HIPCHK(c, hipMalloc((void **)&c->d_odom_part, cap * sizeof(double)));
-    c->odom_part_doubles = cap;
-  }
-  double cov_inv[225];
-  vbh::inverse_pplu(cov, cov_inv, VBA_DIM);                                // VS:987
-  vbh::OdomEkf &S = *c->h_odom;
-  vbh::odom_ekf_begin(S, state, cov, cov_inv);
-  if ((st = map_odom_resident(c->map, c->stream, c->d_odom, c->h_odom, n, d_pts, d_var, c->d_odom_part, c->err))) return st;
-  std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
-  std::memcpy(cov, S.P_out, sizeof(S.P_out));
-  return VBA_OK;
-}
-
-int vba_odom_lio_state_estimation_resident(vba_ctx *c, int n, const double *d_pnt_body, const double *d_var_body, double *state, double *cov,
-                                           int *ok, vba_odom_report *report) {
-  if (n < 0 || (n > 0 && (!d_pnt_body || !d_var_body)) || !state || !cov) return VBA_ERR_BAD_ARG;
-  if (c->n_ranks > 1) { c->set_error("the resident odometry loop has no all-reduce step between its iterations: unsharded contexts only"); return VBA_ERR_UNSUPPORTED; }
-  const int st = odom_core(c, n, d_pnt_body, d_var_body, state, cov);
-  if (st) return st;
-  const vbh::OdomEkf &S = *c->h_odom;
-  // SelfAdjointEigenSolver(nnt).eigenvalues()[0] < 14 -> false  (VS:1090-1097)
-  const double emin = vbh::odom_nnt_eig_min(S.nnt);
-  if (ok) *ok = (emin < 14) ? 0 : 1;
-  if (report) {
-    report->iterations = S.iterations;
-    for (int k = 0; k < 4; k++) { report->match_num[k] = S.match_num[k]; report->rot_add[k] = S.rot_add[k]; report->tra_add[k] = S.tra_add[k]; }
-    report->nnt_eig_min = emin;
-  }
-  return VBA_OK;
-}
-
-// The staging front end of the same update: the scan may be in host or device memory, and a sharded context is accepted.
-int vba_odom_lio_state_estimation(vba_ctx *c, int n, const double *pnt_body, const double *var_body, double *state, double *cov, int *ok) {
-  if (n < 0 || (n > 0 && (!pnt_body || !var_body)) || !state || !cov) return VBA_ERR_BAD_ARG;
-  int st = ensure_stage(c, (size_t)n * 12 * sizeof(double));             // [pts n*3 | var n*9]
-  if (st) return st;
-  double *d_pts = (double *)c->d_stage, *d_var = d_pts + (size_t)n * 3;
-  if (n > 0) {
-    HIPCHK(c, hipMemcpyAsync(d_pts, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_var, var_body, (size_t)n * 9 * sizeof(double), hipMemcpyDefault, c->stream));
-  }
-  if ((st = odom_core(c, n, d_pts, d_var, state, cov))) return st;
-  if (ok) *ok = (vbh::odom_nnt_eig_min(c->h_odom->nnt) < 14) ? 0 : 1;
-  return VBA_OK;
-}
-
 int vba_map_dump_leaves(vba_ctx *c, double *out, int max_leaves) { return map_dump_leaves(c->map, c->stream, out, max_leaves, c->err); }
 int vba_map_dump_plane_var(vba_ctx *c, double *out, int max_leaves) { return map_dump_plane_var(c->map, c->stream, out, max_leaves, c->err); }
 
