@@ -507,6 +507,26 @@ int vba_lm_end(vba_ctx *ctx, double *poses, double *hess, double *resis2);
 #define VBA_SOLVE_DENSE_MASK 16
 #define VBA_SOLVE_ALL_PANELS 32
 int vba_debug_solve(vba_ctx *ctx, int kind, int W, int flags, const double *H, const double *g, double u, double v, double *dx, double *q1);
+/* Diagnostic: the IMU factor pass of the LI-BA loop (li_imu_body; with VBA_IMU_TRIAL also the trial-state residual of k_li_update)
+ * once, on the caller's window (tests/test_gpu_imu.py).  states[W][25] and imus[W-1][304] are those of vba_li_ba_damping_iter; the
+ * set-up (LM state, LiDev, the factor image with the host-inverted cov) is the code that call runs.  W must be the context's
+ * win_size (2..16), gravity 0 or 1, n = 15W + 3 gravity.  The pass is launched in the form flags selects:
+ *   0                 alone, as k_li_imu;
+ *   VBA_IMU_RIDE_H2   as the extra workgroup of k_hessian2 over the context's factor store;
+ *   VBA_IMU_RIDE_H3   as the extra workgroup of k_hessian3 (contexts with hessian_compact_tiles, W <= 10).
+ * A riding form needs a pushed store and must be the lidar kernel the context selects for this window (k_hessian3 where it exists
+ * for the context, else k_hessian2); otherwise VBA_ERR_BAD_ARG, so the caller knows which form ran.  Outputs, after the stream is
+ * drained: h_dense[n * n] = the compact IMU image read through li_hb_get (no imu_coef, no lidar part, no gauge), g[n], rimu[0] =
+ * sum_f r^T cov^-1 r at the states.  VBA_IMU_TRIAL launches k_li_update afterwards with the states in the trial slots, a zero lidar
+ * residual and the fresh LM bookkeeping, and returns its sum in rimu[1] (0 without the flag).  covinv_out (may be NULL):
+ * [W-1][225], the cov^-1 blocks the kernels read.  VBA_ERR_BAD_ARG with nothing launched: a NULL pointer other than covinv_out,
+ * W not the context's, gravity not 0 / 1, an unknown flag, both riding flags, a non-finite input.  VBA_ERR_UNSUPPORTED: a sharded
+ * context.  A pending LM call of the context is dropped. */
+#define VBA_IMU_RIDE_H2 1
+#define VBA_IMU_RIDE_H3 2
+#define VBA_IMU_TRIAL 4
+int vba_debug_li_imu(vba_ctx *ctx, int W, int gravity, int flags, const double *states, const double *imus, double *h_dense, double *g,
+                     double *rimu, double *covinv_out);
 
 /* ------------------------------------------------------------------------------------------------
  * Session-store formats either side of the path.  Host only, no context.

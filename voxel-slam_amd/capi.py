@@ -30,7 +30,7 @@ EXPORTS = [
     "vba_map_num_roots", "vba_map_num_slide_roots", "vba_map_stats", "vba_map_dump_leaves", "vba_map_dump_plane_var", "vba_odom_lio_state_estimation", "vba_odom_lio_state_estimation_resident",
     "vba_set_allreduce", "vba_rccl_get_unique_id", "vba_rccl_init", "vba_set_rccl_comm", "vba_shard_owner", "vba_set_shard",
     "vba_timing_enable", "vba_timing_calibration_read", "vba_timing_select", "vba_timing_sample_every", "vba_timing_launch_hessian", "vba_timing_null_span", "vba_timing_reset", "vba_timing_get",
-    "vba_lm_begin", "vba_lm_refresh_eigen", "vba_lm_iterate", "vba_lm_end", "vba_debug_solve",
+    "vba_lm_begin", "vba_lm_refresh_eigen", "vba_lm_iterate", "vba_lm_end", "vba_debug_solve", "vba_debug_li_imu",
     "vba_io_save_pcd", "vba_io_load_pcd", "vba_io_save_pose", "vba_io_read_lidarstate",
     "vba_motion_init", "vba_init_imu_poses", "vba_init_align_gravity",
     "vba_btc_default_config", "vba_btc_create", "vba_btc_destroy", "vba_btc_set_skip_near_num", "vba_btc_push_plane_cloud",
@@ -823,6 +823,20 @@ class Context:
         self._chk(self.lib.vba_debug_solve(self.h, C.c_int(self.SOLVE_KINDS[kind]), C.c_int(W), C.c_int(f), _p(H), _p(g),
                                            C.c_double(u), C.c_double(v), _p(dx), _p(q1)))
         return dx, q1
+
+    IMU_FORMS = {"alone": 0, "h2": 1, "h3": 2}
+
+    def debug_li_imu(self, states, imus, gravity=False, form="alone", trial=False, raw_flags=None):
+        """vba_debug_li_imu: the IMU factor pass of LI-BA once, through the production kernels, on states [W][25] and imus [W-1][304].
+        form in IMU_FORMS (alone / riding k_hessian2 / riding k_hessian3); trial=True also runs k_li_update on the same states.
+        Returns dict(H [n][n] dense, no imu_coef), g [n], rimu [2], covinv [W-1][15][15] (what the kernels read))."""
+        states = _c(states); imus = _c(imus)
+        W = self.W; n = 15 * W + (3 if gravity else 0)
+        f = (self.IMU_FORMS[form] | (4 if trial else 0)) if raw_flags is None else raw_flags
+        H = np.zeros((n, n)); g = np.zeros(n); rimu = np.zeros(2); ci = np.zeros((max(W - 1, 1), 15, 15))
+        self._chk(self.lib.vba_debug_li_imu(self.h, C.c_int(W), C.c_int(int(gravity)), C.c_int(f), _p(states), _p(imus), _p(H), _p(g),
+                                            _p(rimu), _p(ci)))
+        return dict(H=H, g=g, rimu=rimu, covinv=ci)
 
     def lm_begin(self, poses, thd_num=2):
         poses = _c(poses)

@@ -36,18 +36,7 @@ __device__ __forceinline__ void li_state(const double *pose12, const double *ex1
   for (int k = 0; k < 3; k++) { s.p[k] = pose12[9 + k]; s.v[k] = ex12[k]; s.bg[k] = ex12[3 + k]; s.ba[k] = ex12[6 + k]; s.g[k] = ex12[9 + k]; }
 }
 
-// compact IMU Hessian layout: [pair (a, b), |a - b| <= 1][15][15] | (R, g col k) [15W][3] | (g row k, C) [3][15W] | corner [3][3]
-__host__ __device__ inline int li_hb_pair(int a, int b) { return (3 * a + (b - a)) * 225; }
-__host__ __device__ inline int li_hb_ne1(int W) { return (3 * W - 2) * 225; }
-__host__ __device__ inline int li_hb_size(int W, int grav) { return li_hb_ne1(W) + (grav ? 90 * W + 9 : 0); }
-__host__ __device__ inline double li_hb_get(const double *hb, int W, int n, int R, int C) {   // dense (R, C) from the compact image
-  const int nw = 15 * W;
-  if (R < nw && C < nw) { const int a = R / 15, b = C / 15; if (a - b > 1 || b - a > 1) return 0.0; return hb[li_hb_pair(a, b) + (R - 15 * a) * 15 + (C - 15 * b)]; }
-  const int ne1 = li_hb_ne1(W);
-  if (R < nw) return hb[ne1 + R * 3 + (C - nw)];
-  if (C < nw) return hb[ne1 + 45 * W + (R - nw) * nw + C];
-  return hb[ne1 + 90 * W + (R - nw) * 3 + (C - nw)];
-}
+// (the compact IMU Hessian layout li_hb_* lives in vba_li_order.hpp: host-compilable, the CPU tests read images through it)
 
 // IMU part of divide_thread (VM:551-567 / 783-801).  imu[f] = the ImuPre image of factor f with `cov` REPLACED by cov^-1
 // (cov is constant inside damping_iter; the host inverts it once per call, preintegration.hpp:166 does it per evaluation).

@@ -40,6 +40,19 @@ LIO_HD unsigned li_live(int kb, int W, int n, int NP) {
   return m;
 }
 
+// compact IMU Hessian layout: [pair (a, b), |a - b| <= 1][15][15] | (R, g col k) [15W][3] | (g row k, C) [3][15W] | corner [3][3]
+LIO_HD int li_hb_pair(int a, int b) { return (3 * a + (b - a)) * 225; }
+LIO_HD int li_hb_ne1(int W) { return (3 * W - 2) * 225; }
+LIO_HD int li_hb_size(int W, int grav) { return li_hb_ne1(W) + (grav ? 90 * W + 9 : 0); }
+LIO_HD double li_hb_get(const double *hb, int W, int n, int R, int C) {   // dense (R, C) from the compact image
+  const int nw = 15 * W;
+  if (R < nw && C < nw) { const int a = R / 15, b = C / 15; if (a - b > 1 || b - a > 1) return 0.0; return hb[li_hb_pair(a, b) + (R - 15 * a) * 15 + (C - 15 * b)]; }
+  const int ne1 = li_hb_ne1(W);
+  if (R < nw) return hb[ne1 + R * 3 + (C - nw)];
+  if (C < nw) return hb[ne1 + 45 * W + (R - nw) * nw + C];
+  return hb[ne1 + 90 * W + (R - nw) * 3 + (C - nw)];
+}
+
 }  // namespace vba
 
 #undef LIO_HD

@@ -955,13 +955,11 @@ bool li_device_supported(int W) { return W >= 2 && W <= LI_MAX_W; }
 }
 }  // extern "C++"
 
-static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, int max_iter, double *hess, double *resis2) {
-  static const bool want_times = diag_env("VBA_LI_TIMES") != nullptr;   // diagnostic: host-side phases of one call
-  const auto t_0 = std::chrono::steady_clock::now();
-  auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count(); };
-  const int W = c->opt.win_size, V = c->nvox, DIM = VBA_DIM, F = W - 1;
-  const int n = W * DIM + (gravity ? 3 : 0), nb = gravity ? 33 : 30, n6 = 6 * W;
-  if (!gravity) max_iter = 3;                                         // VM:643
+// Set-up shared by li_ba_device and vba_debug_li_imu: device buffers, the LM state (poses view of `states`, flushed), LiDev `h`, the
+// factor image `fimg` (= imus with cov^-1 in place of cov) uploaded, himu / gimu cleared, the LDS ceiling of k_li_imu.
+static int li_setup(vba_ctx *c, const double *states, const double *imus, int gravity, LiDev &h, std::vector<double> &fimg) {
+  const int W = c->opt.win_size, DIM = VBA_DIM, F = W - 1;
+  const int n = W * DIM + (gravity ? 3 : 0), nb = gravity ? 33 : 30;
   if (!c->d_li) {
     HIPCHK(c, hipMalloc((void **)&c->d_li, sizeof(LiDev)));
     HIPCHK(c, hipMalloc((void **)&c->d_imu, (size_t)LI_MAX_W * 304 * sizeof(double)));
@@ -975,14 +973,14 @@ static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, i
   if (st) return st;
   st = lm_init_flush(c);                      // the LI-BA kernels read the LM state from their first launch on
   if (st) return st;
-  LiDev h{};
+  h = LiDev{};
   h.W = W; h.n = n; h.nb = nb; h.gravity = gravity ? 1 : 0; h.gauge = gravity ? 6 : DIM; h.F = F; h.imu_coef = c->opt.imu_coef;   // VM:653-656 / 906-909
   for (int i = 0; i < W; i++) {
     const double *sx = states + 25 * i;
     h.tstamp[i] = sx[0];
     for (int k = 0; k < 12; k++) h.ex[12 * i + k] = h.ext[12 * i + k] = sx[13 + k];
   }
-  std::vector<double> fimg((size_t)F * 304);
+  fimg.resize((size_t)F * 304);
   std::memcpy(fimg.data(), imus, fimg.size() * sizeof(double));
   // cov^-1 (PI:166 / 244) is a property of the factor, and a sliding window hands the same factors in again scan after scan: a small
   // content-addressed cache (exact comparison of the 225 doubles) saves the host inversions (~4 us each)
@@ -1007,24 +1005,42 @@ static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, i
   }
   HIPCHK(c, hipMemsetAsync(c->d_himu, 0, (size_t)li_hb_size(W, 1) * sizeof(double), c->stream));
   HIPCHK(c, hipMemsetAsync(c->d_gimu, 0, (size_t)n * sizeof(double), c->stream));
+  {
+    static bool attr_set[kMaxDevices] = {false};      // W = 10 with gravity: 88 KB
+    constexpr int FM = LI_MAX_W - 1;
+    if (!attr_set[c->device % kMaxDevices]) { hipFuncSetAttribute((const void *)k_li_imu, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)2 * FM * 15 * 33 + 2 * FM * 15 + FM + 16) * sizeof(double))); attr_set[c->device % kMaxDevices] = true; }
+  }
+  return VBA_OK;
+}
+// dynamic LDS of li_imu_body (joc, cov^-1 joc, rr, cov^-1 rr, the per-factor scalars)
+static size_t li_imu_lds(int F, int nb) { return ((size_t)2 * F * 15 * nb + 2 * F * 15 + F + 16) * sizeof(double); }
+// the IMU pass rides the lidar Hessian launch when there is one on this rank and its LDS fits beside it
+static bool li_imu_rides(const vba_ctx *c, int copy_raw, int V, size_t lds_imu) { return !(copy_raw && c->lm.have_hess) && V > 0 && lds_imu <= 150 * 1024; }
+
+static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, int max_iter, double *hess, double *resis2) {
+  static const bool want_times = diag_env("VBA_LI_TIMES") != nullptr;   // diagnostic: host-side phases of one call
+  const auto t_0 = std::chrono::steady_clock::now();
+  auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count(); };
+  const int W = c->opt.win_size, V = c->nvox, DIM = VBA_DIM, F = W - 1;
+  const int n = W * DIM + (gravity ? 3 : 0), nb = gravity ? 33 : 30, n6 = 6 * W;
+  if (!gravity) max_iter = 3;                                         // VM:643
+  LiDev h{};
+  std::vector<double> fimg;
+  int st = li_setup(c, states, imus, gravity, h, fimg);
+  if (st) return st;
   char *base = reinterpret_cast<char *>(c->d_lm);
   const double *x_dev = reinterpret_cast<const double *>(base + offsetof(LmDev, x));
   const double *xt_dev = reinterpret_cast<const double *>(base + offsetof(LmDev, xt));
   const int *run_hess = reinterpret_cast<const int *>(base + offsetof(LmDev, run_hess));
   const int *run_res = reinterpret_cast<const int *>(base + offsetof(LmDev, run_res));
   const int copy_raw = c->collective() ? 1 : 0;
-  const size_t lds_imu = ((size_t)2 * F * 15 * nb + 2 * F * 15 + F + 16) * sizeof(double);
-  {
-    static bool attr_set[kMaxDevices] = {false};      // W = 10 with gravity: 88 KB
-    constexpr int FM = LI_MAX_W - 1;
-    if (!attr_set[c->device % kMaxDevices]) { hipFuncSetAttribute((const void *)k_li_imu, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)2 * FM * 15 * 33 + 2 * FM * 15 + FM + 16) * sizeof(double))); attr_set[c->device % kMaxDevices] = true; }
-  }
+  const size_t lds_imu = li_imu_lds(F, nb);
   const double t_up = since(t_0);
   for (int it = 0; it < max_iter; it++) {
     // The IMU factors' workgroup rides in the lidar Hessian launch as block 0 on a CU of its own (k_hessian2).  As a kernel of its own
     // in front of the lidar pass it cost its 28 us + a kernel boundary; on a side stream (fork / join events around it) the two
     // cross-stream dependencies cost more than they hid (209 vs 196 us per iteration).
-    const bool lidar_now = !(copy_raw && c->lm.have_hess) && V > 0 && lds_imu <= 150 * 1024;
+    const bool lidar_now = li_imu_rides(c, copy_raw, V, lds_imu);
     if (lidar_now) {          // the IMU workgroup rides in the lidar Hessian launch
       const LiJob job{c->d_lm, c->d_li, c->d_imu, c->d_himu, c->d_gimu};
       st = hessian_pass(c, x_dev, run_hess, 0, V, nullptr, nullptr, 0, job, lds_imu);   // lidar part of divide_thread (+ all-reduce)
@@ -1161,6 +1177,70 @@ int vba_li_ba_damping_iter(vba_ctx *c, double *states, double *imus, int gravity
   // the whole optimiser runs on the device (k_li_imu / k_li_solve / k_li_update) for every window the context accepts (2..16)
   if (!li_device_supported(c->opt.win_size)) return VBA_ERR_UNSUPPORTED_WINDOW;
   return li_ba_device(c, states, imus, gravity, max_iter, hess, resis2);
+}
+
+// ---------------------------------------------------------------- diagnostic: the IMU factor pass through the production kernels
+static int debug_li_imu_run(vba_ctx *c, int gravity, int flags, const double *states, const double *imus, double *h_dense, double *g, double *rimu,
+                            double *covinv_out) {
+  const int W = c->opt.win_size, V = c->nvox, F = W - 1, n = 15 * W + (gravity ? 3 : 0), nb = gravity ? 33 : 30;
+  LiDev h{};
+  std::vector<double> fimg;
+  int st = li_setup(c, states, imus, gravity, h, fimg);
+  if (st) return st;
+  char *base = reinterpret_cast<char *>(c->d_lm);
+  const double *x_dev = reinterpret_cast<const double *>(base + offsetof(LmDev, x));
+  const int *run_hess = reinterpret_cast<const int *>(base + offsetof(LmDev, run_hess));
+  const size_t lds_imu = li_imu_lds(F, nb);
+  if (flags & (VBA_IMU_RIDE_H2 | VBA_IMU_RIDE_H3)) {
+    const LiJob job{c->d_lm, c->d_li, c->d_imu, c->d_himu, c->d_gimu};
+    st = hessian_pass(c, x_dev, run_hess, 0, V, nullptr, nullptr, 0, job, lds_imu);
+    if (st) return st;
+  } else {
+    hipLaunchKernelGGL(k_li_imu, dim3(1), dim3(LI_IMU_NT), lds_imu, c->stream, c->d_lm, c->d_li, c->d_imu, c->d_himu, c->d_gimu);
+  }
+  HIPCHK(c, hipGetLastError());
+  if (flags & VBA_IMU_TRIAL) {      // xt = x and ext = ex hold the caller's states (li_setup); r2 = 0, r1 = q1 = 0: the bookkeeping has nothing to decide
+    HIPCHK(c, hipMemsetAsync(c->d_scal, 0, sizeof(double), c->stream));
+    hipLaunchKernelGGL(k_li_update, dim3(1), dim3(LI_UPD_NT), 0, c->stream, c->d_lm, c->d_li, c->d_imu, c->d_scal, 0);
+    HIPCHK(c, hipGetLastError());
+  }
+  std::vector<double> hb((size_t)li_hb_size(W, gravity));
+  hipError_t e = hipMemcpyAsync(hb.data(), c->d_himu, hb.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(g, c->d_gimu, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&h, c->d_li, sizeof(LiDev), hipMemcpyDeviceToHost, c->stream);
+  const hipError_t es = hipStreamSynchronize(c->stream);      // (always drained: the destinations are locals of this call)
+  HIPCHK(c, e);
+  HIPCHK(c, es);
+  for (int r = 0; r < n; r++)
+    for (int k = 0; k < n; k++) h_dense[(size_t)r * n + k] = li_hb_get(hb.data(), W, n, r, k);
+  rimu[0] = h.rimu[0];
+  rimu[1] = (flags & VBA_IMU_TRIAL) ? h.rimu[1] : 0.0;
+  if (covinv_out)
+    for (int f = 0; f < F; f++) std::memcpy(covinv_out + 225 * (size_t)f, fimg.data() + 304 * (size_t)f + 79, 225 * sizeof(double));
+  return VBA_OK;
+}
+int vba_debug_li_imu(vba_ctx *c, int W, int gravity, int flags, const double *states, const double *imus, double *h_dense, double *g, double *rimu,
+                     double *covinv_out) {
+  if (!c || !states || !imus || !h_dense || !g || !rimu) return VBA_ERR_BAD_ARG;
+  if (W != c->opt.win_size || !li_device_supported(W) || (gravity != 0 && gravity != 1)) return VBA_ERR_BAD_ARG;
+  if (flags & ~(VBA_IMU_RIDE_H2 | VBA_IMU_RIDE_H3 | VBA_IMU_TRIAL)) return VBA_ERR_BAD_ARG;
+  const bool h2 = (flags & VBA_IMU_RIDE_H2) != 0, h3 = (flags & VBA_IMU_RIDE_H3) != 0;
+  if (h2 && h3) return VBA_ERR_BAD_ARG;
+  if (c->collective()) return VBA_ERR_UNSUPPORTED;
+  if (h2 || h3) {
+    // the riding forms need a pushed store, and the lidar kernel is the one the context selects for it (launch_hessian)
+    const bool ctx_h3 = c->use_h3 && W <= 10;
+    if (c->nvox <= 0 || h3 != ctx_h3) return VBA_ERR_BAD_ARG;
+    if (!li_imu_rides(c, 0, c->nvox, li_imu_lds(W - 1, gravity ? 33 : 30))) return VBA_ERR_BAD_ARG;
+  }
+  for (size_t i = 0; i < (size_t)25 * W; i++) if (!std::isfinite(states[i])) return VBA_ERR_BAD_ARG;
+  for (size_t i = 0; i < (size_t)304 * (W - 1); i++) if (!std::isfinite(imus[i])) return VBA_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int st = debug_li_imu_run(c, gravity, flags, states, imus, h_dense, g, rimu, covinv_out);
+  if (st) hipStreamSynchronize(c->stream);       // (nothing of this call is left in flight behind a status)
+  c->lm_init.pending = false;
+  c->lm.active = false;
+  return st;
 }
 
 // ---------------------------------------------------------------- IMU factor (host)
