@@ -1,6 +1,7 @@
 """The source layout of libvoxelba.so as DESIGN.md states it ("Source layout"): one object per csrc/*.hip unit, every kernel header
 compiled by exactly one unit, host launch code in the units and not in the kernel headers.  A text check over include lines, function
-heads and file names; nothing is compiled."""
+heads and file names; nothing is compiled.  Also its ownership rule: device and pinned buffers are members of the owning types of
+vba_mem.hpp and free themselves, so the runtime's free calls appear only there and in the few stores with a lifetime of their own."""
 import glob
 import os
 import re
@@ -58,3 +59,70 @@ def test_makefile_units_are_the_hip_files():
     listed = m.group(1).split()
     assert len(listed) == len(set(listed))
     assert sorted(listed) == units()
+
+
+# ---------------------------------------------------------------- buffer ownership ("Source layout": vba_mem.hpp)
+FREE_CALL = re.compile(r"\bhip(?:Host)?Free\s*\(")
+# a definition that starts in column 0: `struct Name`, or a function head `... name(`
+TOP_LEVEL = re.compile(r"^(?:struct\s+(\w+)|[A-Za-z_][^\n;(]*?(~?\w+)\s*\()", re.M)
+# the owners that keep their own free lists: the voxel map (DevArr growth, hash tables, staging, sort scratch and the histogram of
+# the factor extraction, map_free), the global-BA stores (GbaStore and its growth in gba_build, BigStore's chunk arena), the
+# descriptor generator (BtcGen: bg_grow, btcgen_reserve, btcgen_free) and the debug entry points' scoped DbgBufs
+FREE_ALLOWED = {
+    "vba_map.hip": {"grow_arrays", "map_hash_alloc", "map_free", "map_stage", "map_sort_reserve", "map_sort_reserve_n", "map_extract_factors"},
+    "vba_hba.hip": {"gba_build"},
+    "vba_btcgen.hip": {"bg_grow", "btcgen_reserve", "btcgen_free"},
+    "vba_types.hpp": {"GbaStore", "BigStore"},
+    "voxelba.hip": {"DbgBufs"},
+}
+
+
+def free_sites(name):
+    """{enclosing top-level definition: number of free calls} of one file"""
+    text = read(name)
+    heads = [(m.start(), m.group(1) or m.group(2)) for m in TOP_LEVEL.finditer(text)]
+    out = {}
+    for m in FREE_CALL.finditer(text):
+        owner = [h for pos, h in heads if pos < m.start()][-1]
+        out[owner] = out.get(owner, 0) + 1
+    return out
+
+
+def function_body(text, head):
+    """the text between the braces of the definition whose head `head` matches"""
+    i = text.index("{", re.search(head, text, re.M).end() - 1)
+    depth, j = 0, i
+    while True:
+        depth += {"{": 1, "}": -1}.get(text[j], 0)
+        if depth == 0:
+            return text[i:j + 1]
+        j += 1
+
+
+def test_free_calls_only_in_the_owning_types_and_the_listed_stores():
+    assert FREE_CALL.search("if (p) hipHostFree (p);") and FREE_CALL.search("hipFree(q)") and not FREE_CALL.search("map_free(s)")
+    assert free_sites("vba_mem.hpp") == {"Mem": 2}
+    files = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*.hip"))) + ["vba_ctx.hpp", "vba_types.hpp"]
+    found = {f: set(free_sites(f)) for f in files if free_sites(f)}
+    assert found == FREE_ALLOWED
+
+
+def test_vba_destroy_lists_no_buffers():
+    body = function_body(read("voxelba.hip"), r"^void vba_destroy\(vba_ctx \*c\) \{")
+    assert "delete c;" in body and "hipStreamDestroy" in body
+    assert not FREE_CALL.search(body)
+    for handle, unit in (("vba_kf_destroy", "vba_kf.hip"), ("vba_btc_destroy", "vba_btc.hip"), ("vba_scan_frame_destroy", "vba_scan.hip"),
+                         ("vba_loop_map_destroy", "vba_loop.hip")):
+        assert not FREE_CALL.search(function_body(read(unit), r"^void %s\(\w+ \*\w+\) \{" % handle)), handle
+
+
+def test_vba_mem_is_a_shared_header_without_kernels():
+    assert "__global__" not in read("vba_mem.hpp")
+    assert INCLUDE.findall(read("vba_mem.hpp")) == []          # the runtime's header only
+    for u in units():
+        direct = INCLUDE.findall(read(u + ".hip"))
+        if "vba_mem.hpp" in reached(u + ".hip"):
+            assert "vba_ctx.hpp" in direct or "vba_mem.hpp" in direct, u
+    assert "vba_mem.hpp" in INCLUDE.findall(read("vba_ctx.hpp"))
+    # no unit reaches it through a kernel header
+    assert [h for h in kernel_headers() if "vba_mem.hpp" in reached(h)] == []

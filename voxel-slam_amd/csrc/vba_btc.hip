@@ -26,28 +26,19 @@ struct BtcSpan {
   ~BtcSpan() { end(); }
 };
 
-// grow a device array to new_n elements, keeping the first keep elements (stream-ordered copy; the old block is freed after it)
-template <class T>
-int btc_grow(vba_ctx *c, T **p, size_t keep, size_t new_n) {
-  T *q = nullptr;
-  HIPCHK(c, hipMalloc((void **)&q, new_n * sizeof(T)));
-  if (*p && keep) HIPCHK(c, hipMemcpyAsync(q, *p, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
-  if (*p) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(*p); }
-  *p = q;
-  return VBA_OK;
-}
-
 int btc_reserve_rows(vba_btc_db *db, int need) {
   if (need <= db->cap) return VBA_OK;
   vba_ctx *c = db->ctx;
   int nc = db->cap ? db->cap : 1024;
   while (nc < need) nc *= 2;
   const size_t k = (size_t)db->nstd;
-  int st;
-  if ((st = btc_grow(c, &db->d.tri, 3 * k, 3 * (size_t)nc)) || (st = btc_grow(c, &db->d.cen, 3 * k, 3 * (size_t)nc)) ||
-      (st = btc_grow(c, &db->d.loc, 9 * k, 9 * (size_t)nc)) || (st = btc_grow(c, &db->d.bits, 3 * k, 3 * (size_t)nc)) ||
-      (st = btc_grow(c, &db->d.summ, 3 * k, 3 * (size_t)nc)) || (st = btc_grow(c, &db->d.frame, k, (size_t)nc)))
-    return st;
+  hipStream_t s = c->stream;
+  hipError_t e;
+  (e = db->tri.grow_keep(3 * (size_t)nc, 3 * k, s)) || (e = db->cen.grow_keep(3 * (size_t)nc, 3 * k, s)) ||
+      (e = db->loc.grow_keep(9 * (size_t)nc, 9 * k, s)) || (e = db->bits.grow_keep(3 * (size_t)nc, 3 * k, s)) ||
+      (e = db->summ.grow_keep(3 * (size_t)nc, 3 * k, s)) || (e = db->frame.grow_keep((size_t)nc, k, s));
+  db->d = BtcStds{db->tri, db->cen, db->loc, db->bits, db->summ, db->frame};      // the view follows whatever did grow
+  HIPCHK(c, e);
   db->cap = nc;
   return VBA_OK;
 }
@@ -88,9 +79,8 @@ BtcStds btc_view(int n, char *dev) {
 
 int btc_table_upload(vba_btc_db *db) {
   vba_ctx *c = db->ctx;
-  if (db->d_tab) hipFree(db->d_tab);
-  db->d_tab = nullptr;
-  HIPCHK(c, hipMalloc((void **)&db->d_tab, db->tab.size() * sizeof(int)));
+  db->d_tab.reset();
+  HIPCHK(c, db->d_tab.ensure(db->tab.size()));
   HIPCHK(c, hipMemcpyAsync(db->d_tab, db->tab.data(), db->tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
   return VBA_OK;
 }
@@ -174,23 +164,17 @@ int btc_search_run(int n_db, vba_btc_db *const *dbs, int n, const double *rows, 
   vba_ctx *c = dbs[0]->ctx;
   // query upload (once) and the shared count scratch
   const size_t qb = btc_pack_bytes(n);
-  if (qb > c->btcq_bytes) {
-    if (c->d_btcq) hipFree(c->d_btcq);
-    if (c->h_btcq) hipHostFree(c->h_btcq);
-    c->d_btcq = c->h_btcq = nullptr; c->btcq_bytes = 0;
+  if (qb > c->h_btcq.n) {                                          // (the pinned half is made last)
+    c->d_btcq.reset(); c->h_btcq.reset();
     size_t nbytes = 1 << 16;
     while (nbytes < qb) nbytes *= 2;
-    HIPCHK(c, hipMalloc((void **)&c->d_btcq, nbytes));
-    HIPCHK(c, hipHostMalloc((void **)&c->h_btcq, nbytes, hipHostMallocDefault));
-    c->btcq_bytes = nbytes;
+    HIPCHK(c, c->d_btcq.ensure(nbytes));
+    HIPCHK(c, c->h_btcq.ensure(nbytes));
   }
-  if ((size_t)27 * n > c->btccnt_cap) {
-    if (c->d_btccnt) hipFree(c->d_btccnt);
-    c->d_btccnt = nullptr;
+  if ((size_t)27 * n > c->d_btccnt.n) {
     size_t m = 8192;
     while (m < (size_t)27 * n) m *= 2;
-    HIPCHK(c, hipMalloc((void **)&c->d_btccnt, m * sizeof(int)));
-    c->btccnt_cap = m;
+    HIPCHK(c, c->d_btccnt.ensure(m));
   }
   for (int k = 0; k < n_db; k++) {                                // votes sized by the frames pushed so far
     vba_btc_db *db = dbs[k];
@@ -198,8 +182,7 @@ int btc_search_run(int n_db, vba_btc_db *const *dbs, int n, const double *rows, 
     if (nf > db->vcap) {
       int m = db->vcap ? db->vcap : 1024;
       while (m < nf) m *= 2;
-      const int st = btc_grow(c, &db->d_votes, 0, (size_t)m);
-      if (st) return st;
+      HIPCHK(c, db->d_votes.grow_keep((size_t)m, 0, c->stream));
       db->vcap = m;
     }
   }
@@ -217,9 +200,9 @@ int btc_search_run(int n_db, vba_btc_db *const *dbs, int n, const double *rows, 
     if (total > db->mcap) {
       int m = db->mcap;
       while (m < total) m *= 2;
-      int st = btc_grow(c, &db->d_m, 0, 5 * (size_t)m);
-      if (st) return st;
+      HIPCHK(c, db->d_m.grow_keep(5 * (size_t)m, 0, c->stream));
       db->mcap = m;
+      int st;
       if ((st = btc_enqueue(db, q, n, pl, npl))) return st;
       HIPCHK(c, hipStreamSynchronize(c->stream));
     }
@@ -259,18 +242,19 @@ int vba_btc_create(vba_ctx *c, const vba_btc_config *cfg, vba_btc_db **out) {
   vba_btc_default_gen_config(0, &db->gcfg);
   btc_table_init(db->tab, 1024);
   db->tab_mask = 1023;
+  auto make = [c](auto &m, size_t n) -> int { HIPCHK(c, m.ensure(n)); return VBA_OK; };
   int st = btc_table_upload(db);
   if (!st) st = btc_reserve_rows(db, 1024);
-  if (!st) st = btc_grow(c, &db->d_off, 0, 1024);
-  if (!st) st = btc_grow(c, &db->d_ent, 0, (size_t)256 * BTC_CHUNK);
-  if (!st) st = btc_grow(c, &db->d_next, 0, 256);
-  if (!st) st = btc_grow(c, &db->d_m, 0, 5 * (size_t)65536);
-  if (!st) st = btc_grow(c, &db->d_votes, 0, 1024);
-  if (!st) st = btc_grow(c, &db->d_cand, 0, 5 * (size_t)BTC_MAX_CAND);
-  if (!st) st = btc_grow(c, &db->d_total, 0, 4);
-  if (!st) st = btc_grow(c, &db->d_cres, 0, 13 * (size_t)BTC_MAX_CAND);
-  if (!st) st = btc_grow(c, &db->d_res, 0, BTC_RES);
-  if (!st && hipHostMalloc((void **)&db->h_res, BTC_RES * sizeof(double), hipHostMallocDefault) != hipSuccess) st = VBA_ERR_HIP;
+  if (!st) st = make(db->d_off, 1024);
+  if (!st) st = make(db->d_ent, (size_t)256 * BTC_CHUNK);
+  if (!st) st = make(db->d_next, 256);
+  if (!st) st = make(db->d_m, 5 * (size_t)65536);
+  if (!st) st = make(db->d_votes, 1024);
+  if (!st) st = make(db->d_cand, 5 * (size_t)BTC_MAX_CAND);
+  if (!st) st = make(db->d_total, 4);
+  if (!st) st = make(db->d_cres, 13 * (size_t)BTC_MAX_CAND);
+  if (!st) st = make(db->d_res, BTC_RES);
+  if (!st && db->h_res.ensure(BTC_RES) != hipSuccess) st = VBA_ERR_HIP;
   if (st) { vba_btc_destroy(db); return st; }
   db->off_cap = 1024; db->chunk_cap = 256; db->mcap = 65536; db->vcap = 1024;
   const int zero = 0;
@@ -285,10 +269,6 @@ void vba_btc_destroy(vba_btc_db *db) {
   vba_ctx *c = db->ctx;
   hipSetDevice(c->device);
   hipStreamSynchronize(c->stream);
-  void *p[] = {db->d.tri, db->d.cen, db->d.loc, db->d.bits, db->d.summ, db->d.frame, db->d_tab, db->d_ent, db->d_next, db->d_pc, db->d_off,
-               db->d_m, db->d_votes, db->d_cand, db->d_total, db->d_cres, db->d_res};
-  for (void *q : p) if (q) hipFree(q);
-  if (db->h_res) hipHostFree(db->h_res);
   if (db->gen) { btcgen_free(*db->gen); delete db->gen; }
   delete db;
 }
@@ -306,32 +286,32 @@ int vba_btc_reserve(vba_btc_db *db, int stds, int frames, int64_t cloud_points, 
   if (stds > db->chunk_cap) {                                 // chunks <= descriptors
     int m = db->chunk_cap;
     while (m < stds) m *= 2;
-    if ((st = btc_grow(c, &db->d_ent, (size_t)db->nchunk * BTC_CHUNK, (size_t)m * BTC_CHUNK)) || (st = btc_grow(c, &db->d_next, (size_t)db->nchunk, (size_t)m)))
-      return st;
+    HIPCHK(c, db->d_ent.grow_keep((size_t)m * BTC_CHUNK, (size_t)db->nchunk * BTC_CHUNK, c->stream));
+    HIPCHK(c, db->d_next.grow_keep((size_t)m, (size_t)db->nchunk, c->stream));
     db->chunk_cap = m;
   }
   if (frames + 1 > db->off_cap) {
     int m = db->off_cap;
     while (m < frames + 1) m *= 2;
-    if ((st = btc_grow(c, &db->d_off, db->off.size(), (size_t)m))) return st;
+    HIPCHK(c, db->d_off.grow_keep((size_t)m, db->off.size(), c->stream));
     db->off_cap = m;
   }
   if (frames > db->vcap) {
     int m = db->vcap;
     while (m < frames) m *= 2;
-    if ((st = btc_grow(c, &db->d_votes, 0, (size_t)m))) return st;
+    HIPCHK(c, db->d_votes.grow_keep((size_t)m, 0, c->stream));
     db->vcap = m;
   }
   if ((size_t)cloud_points > db->pc_cap) {
     size_t m = db->pc_cap ? db->pc_cap : 65536;
     while (m < (size_t)cloud_points) m *= 2;
-    if ((st = btc_grow(c, &db->d_pc, 6 * (size_t)db->off.back(), 6 * m))) return st;
+    HIPCHK(c, db->d_pc.grow_keep(6 * m, 6 * (size_t)db->off.back(), c->stream));
     db->pc_cap = m;
   }
   if (matches > db->mcap) {
     int m = db->mcap;
     while (m < matches) m *= 2;
-    if ((st = btc_grow(c, &db->d_m, 0, 5 * (size_t)m))) return st;
+    HIPCHK(c, db->d_m.grow_keep(5 * (size_t)m, 0, c->stream));
     db->mcap = m;
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -354,16 +334,14 @@ int vba_btc_push_plane_cloud(vba_btc_db *db, int n, const float *xyz_normal, int
   if (need > db->pc_cap) {
     size_t m = db->pc_cap ? db->pc_cap : 65536;
     while (m < need) m *= 2;
-    const int st = btc_grow(c, &db->d_pc, 6 * have, 6 * m);
-    if (st) return st;
+    HIPCHK(c, db->d_pc.grow_keep(6 * m, 6 * have, c->stream));
     db->pc_cap = m;
   }
   const int nf = (int)db->off.size();        // frames after this push + 1 offsets
   if (nf + 1 > db->off_cap) {
     int m = db->off_cap * 2;
     while (m < nf + 1) m *= 2;
-    const int st = btc_grow(c, &db->d_off, (size_t)nf, (size_t)m);
-    if (st) return st;
+    HIPCHK(c, db->d_off.grow_keep((size_t)m, (size_t)nf, c->stream));
     db->off_cap = m;
   }
   if (need > (size_t)INT32_MAX) return VBA_ERR_CAPACITY;
@@ -415,8 +393,8 @@ int vba_btc_add_stds(vba_btc_db *db, int n, const double *rows, const uint64_t *
     if (e[4] % BTC_CHUNK == 0) {                                // a new chunk for this cell
       if (db->nchunk + 1 > db->chunk_cap) {
         const int m = db->chunk_cap * 2;
-        if ((st = btc_grow(c, &db->d_ent, (size_t)db->nchunk * BTC_CHUNK, (size_t)m * BTC_CHUNK)) || (st = btc_grow(c, &db->d_next, (size_t)db->nchunk, (size_t)m)))
-          return st;
+        HIPCHK(c, db->d_ent.grow_keep((size_t)m * BTC_CHUNK, (size_t)db->nchunk * BTC_CHUNK, c->stream));
+        HIPCHK(c, db->d_next.grow_keep((size_t)m, (size_t)db->nchunk, c->stream));
         db->chunk_cap = m;
       }
       const int ch = db->nchunk++;
@@ -450,7 +428,7 @@ int vba_btc_add_stds(vba_btc_db *db, int n, const double *rows, const uint64_t *
   all.insert(all.end(), nxt.begin(), nxt.end());
   all.insert(all.end(), tp.begin(), tp.end());
   if ((st = ensure_stage(c, all.size() * sizeof(int)))) return st;
-  int *ds = (int *)c->d_stage;
+  int *ds = (int *)c->d_stage.p;
   HIPCHK(c, hipMemcpyAsync(ds, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
   const int ne = (int)ent.size() / 2, nn = (int)nxt.size() / 2, nt = (int)tp.size() / 2;
   if (ne) k_btc_scatter<<<(ne + 255) / 256, 256, 0, c->stream>>>(ne, ds, db->d_ent);
@@ -509,23 +487,17 @@ int vba_btc_icp_normal(vba_btc_db *src_db, int src_frame, vba_btc_db *tar_db, in
   int slices = 1;
   while (slices < ntile && nb * slices * 2 <= 1024) slices *= 2;          // ~1024 workgroups on the 1-NN pass
   if (slices > ntile && ntile > 0) slices = ntile;
-  if (!c->d_icp) {
-    HIPCHK(c, hipMalloc((void **)&c->d_icp, sizeof(BtcIcpDev)));
-    HIPCHK(c, hipHostMalloc((void **)&c->h_icp, sizeof(BtcIcpDev), hipHostMallocDefault));
-  }
-  if ((size_t)slices * ns > c->icpkey_cap) {
+  HIPCHK(c, c->d_icp.ensure(1));
+  HIPCHK(c, c->h_icp.ensure(1));
+  if ((size_t)slices * ns > c->d_icpkey.n) {
     size_t m = 65536;
     while (m < (size_t)slices * ns) m *= 2;
-    const int st = btc_grow(c, &c->d_icpkey, 0, m);
-    if (st) return st;
-    c->icpkey_cap = m;
+    HIPCHK(c, c->d_icpkey.grow_keep(m, 0, c->stream));
   }
-  if ((size_t)nb * BTC_ICP_PART > c->icppart_cap) {
+  if ((size_t)nb * BTC_ICP_PART > c->d_icppart.n) {
     size_t m = 4096;
     while (m < (size_t)nb * BTC_ICP_PART) m *= 2;
-    const int st = btc_grow(c, &c->d_icppart, 0, m);
-    if (st) return st;
-    c->icppart_cap = m;
+    HIPCHK(c, c->d_icppart.grow_keep(m, 0, c->stream));
   }
   BtcSpan sp(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));       // (the pinned state block may still be in flight from an earlier call)
@@ -691,7 +663,7 @@ int btc_generate_impl(vba_btc_db *db, int n, const float *xyz, int id, int cap, 
   if (have + planes > db->pc_cap) {
     size_t m = db->pc_cap ? db->pc_cap : 65536;
     while (m < have + planes) m *= 2;
-    if ((st = btc_grow(c, &db->d_pc, 6 * have, 6 * m))) return st;
+    HIPCHK(c, db->d_pc.grow_keep(6 * m, 6 * have, c->stream));
     db->pc_cap = m;
     db->gen->allocs++;
   }
@@ -699,7 +671,7 @@ int btc_generate_impl(vba_btc_db *db, int n, const float *xyz, int id, int cap, 
   if (nf + 1 > db->off_cap) {
     int m = db->off_cap * 2;
     while (m < nf + 1) m *= 2;
-    if ((st = btc_grow(c, &db->d_off, (size_t)nf, (size_t)m))) return st;
+    HIPCHK(c, db->d_off.grow_keep((size_t)m, (size_t)nf, c->stream));
     db->off_cap = m;
     db->gen->allocs++;
   }

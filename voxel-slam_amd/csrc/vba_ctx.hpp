@@ -4,6 +4,7 @@
 #include "../../include/voxelba.h"
 #include "vba_types.hpp"
 #include "vba_common.hpp"
+#include "vba_mem.hpp"
 #include "vba_btcgen.hpp"
 
 #include <hip/hip_runtime.h>
@@ -51,21 +52,21 @@ struct vba_ctx {
   bool own_stream = false;
   std::string err;
 
-  // factor store (HBM, SoA)
+  // factor store (HBM, SoA): fv is the view the kernels take, refreshed from its owners by factor_reserve
   FactorView fv{};
+  DevMem<double> fv_rows[6];      // cl, fix, coe, eigval, eigvec, pcr
+  DevMem<unsigned int> fv_occ;
+  DevMem<int> fv_tiles;
   int nvox = 0;   // voxels stored
   int nvox_global = 0;   // the same summed over the ranks (set by vba_lm_begin when the factor store is sharded)
   int cap = 0;    // capacity = stride
-  double *d_poses = nullptr;     // [W][12]
-  double *d_partial = nullptr;   // workgroup partials
-  size_t partial_doubles = 0;
-  double *d_out = nullptr;       // reduced Hessian pass, tile layout (vba_kernels_factor.hpp)
-  double *d_full = nullptr;      // the same in full layout [H | g | r] for host consumers
-  double *d_scal = nullptr;      // reduced residual scalar
-  double *h_pin = nullptr;       // pinned host staging
-  size_t pin_doubles = 0;
-  void *d_stage = nullptr;       // AoS upload staging
-  size_t stage_bytes = 0;
+  DevMem<double> d_poses;        // [W][12]
+  DevMem<double> d_partial;      // workgroup partials
+  DevMem<double> d_out;          // reduced Hessian pass, tile layout (vba_kernels_factor.hpp)
+  DevMem<double> d_full;         // the same in full layout [H | g | r] for host consumers
+  DevMem<double> d_scal;         // reduced residual scalar
+  PinMem<double> h_pin;          // pinned host staging
+  DevMem<char> d_stage;          // AoS upload staging
 
   // multi-GPU
   vba_allreduce_fn allreduce = nullptr;
@@ -89,59 +90,57 @@ struct vba_ctx {
   std::map<std::string, std::vector<TimedSpan>> spans;
 
   // device-resident LM state (lm_begin / lm_iterate / lm_end)
-  LmDev *d_lm = nullptr;
-  LmDev *h_lm = nullptr;          // pinned mirror (download side)
+  DevMem<LmDev> d_lm;
+  PinMem<LmDev> h_lm;             // pinned mirror (download side)
   // vba_lm_begin copies nothing: it leaves the begin poses here and the first LM kernel of the call writes the image (LmInit), or
   // lm_init_flush does for callers whose first kernel is not a fused site
   struct { bool pending = false; int dbg = 0; double x[VBA_MAX_WIN_DEV * 12]; } lm_init;
-  double *d_raw = nullptr;        // last valid all-reduced [H|g|r] (multi-rank only; single rank reads d_out in place)
+  DevMem<double> d_raw;           // last valid all-reduced [H|g|r] (multi-rank only; single rank reads d_out in place)
   struct { bool active = false; int thd_num = 2; bool have_hess = false; bool pending_update = false; int k4_nb = 0; } lm;   // pending_update: the accept/reject step of the last iteration rides in the next Hessian pass
-  int k4part_cap = 0;
-  double *d_k4part = nullptr;     // residual-pass partials of the LM loop (the Hessian pass reuses d_partial while they are still read)   // have_hess: [H|g|r] of the next solve is already reduced (multi-rank)
+  DevMem<double> d_k4part;        // residual-pass partials of the LM loop (the Hessian pass reuses d_partial while they are still read)   // have_hess: [H|g|r] of the next solve is already reduced (multi-rank)
   std::vector<double> trace;
 
   // device-resident LI-BA (vba_kernels_li.hpp)
-  LiDev *d_li = nullptr;
-  double *d_imu = nullptr, *d_himu = nullptr, *d_gimu = nullptr;
+  DevMem<LiDev> d_li;
+  DevMem<double> d_imu, d_himu, d_gimu;
 
   MapStore map;
   GbaStore gba;
   BigStore big;                   // arbitrary-window path (top-level global BA)
-  double *d_kdtree[2] = {nullptr, nullptr};   // pl_tree of the initialisation odometry (float-valued xyz), ping-pong for the re-sampling
-  size_t kd_cap = 0; int kd_n = 0, kd_cur = 0;
+  DevMem<double> d_kdtree[2];     // pl_tree of the initialisation odometry (float-valued xyz), ping-pong for the re-sampling
+  int kd_n = 0, kd_cur = 0;
   // vba_odom_lio_state_estimation_kdtree_resident: scratch sized by the scan (planes, partials, candidates), scratch
   // sized by map + scan (the re-sampler's count / first arrays and work area); the loop's state and pinned image are d_odom / h_odom
   // below.  kd_allocs / kd_bytes count these and the map's two halves, cumulatively (a freed block is not subtracted).
-  char *d_kdscan = nullptr; size_t kdscan_pts = 0;
-  char *d_kdws = nullptr; size_t kdws_pts = 0, kdws_bytes = 0;
+  DevMem<char> d_kdscan; size_t kdscan_pts = 0;
+  DevMem<char> d_kdws; size_t kdws_pts = 0;
   int kd_allocs = 0; int64_t kd_bytes = 0;
-  double *d_refpts = nullptr;     // submap cloud staging (HBA_add_edge)
-  size_t refpts_doubles = 0;
-  double *d_lipack = nullptr; size_t lipack_doubles = 0;       // li_ba_device: results gathered for one D2H copy
-  double *d_liscr = nullptr; size_t liscr_doubles = 0;         // k_li_solve at W > 10: staged matrix / L outside the LDS
-  double *d_hba_all = nullptr; size_t hba_all_doubles = 0;   // vba_hba_global: keyframe clouds + submap clouds, kept across calls
+  DevMem<double> d_refpts;        // submap cloud staging (HBA_add_edge)
+  DevMem<double> d_lipack;        // li_ba_device: results gathered for one D2H copy
+  DevMem<double> d_liscr;         // k_li_solve at W > 10: staged matrix / L outside the LDS
+  DevMem<double> d_hba_all;       // vba_hba_global: keyframe clouds + submap clouds, kept across calls
   std::vector<vba_ctx *> hba_workers;                         // vba_hba_global: extra contexts (own stream, own octree) that optimise bottom-layer windows side by side
-  void *d_init = nullptr; size_t init_bytes = 0;            // vba_motion_init: raw clouds (uploaded once per call), blurred rows, pose tables
+  DevMem<char> d_init;            // vba_motion_init: raw clouds (uploaded once per call), blurred rows, pose tables
   // loop retrieval (vba_btc_*): the query upload, the per-(query, cell) counts and the ICP state are shared by the context's databases
-  char *d_btcq = nullptr, *h_btcq = nullptr; size_t btcq_bytes = 0;
-  int *d_btccnt = nullptr; size_t btccnt_cap = 0;
-  BtcIcpDev *d_icp = nullptr, *h_icp = nullptr;
-  unsigned long long *d_icpkey = nullptr; size_t icpkey_cap = 0;
-  double *d_icppart = nullptr; size_t icppart_cap = 0;
+  DevMem<char> d_btcq; PinMem<char> h_btcq;
+  DevMem<int> d_btccnt;
+  DevMem<BtcIcpDev> d_icp; PinMem<BtcIcpDev> h_icp;
+  DevMem<unsigned long long> d_icpkey;
+  DevMem<double> d_icppart;
   // pose-graph optimisation (vba_pgo_optimize): graph structure and per-update work areas, and the dense skeleton system; grow-only
-  char *d_pgo = nullptr; size_t pgo_bytes = 0;
-  double *d_pgoAb = nullptr; size_t pgoAb_bytes = 0;
+  DevMem<char> d_pgo;
+  DevMem<double> d_pgoAb;
   // vba_kf_export_world: the per-keyframe table (pinned upload ring, so that a call need not drain the stream before
   // it writes the next image, and the device copy) and the staging of host output; grow-only
   static const int kExpRing = 4;
-  char *h_exp[kExpRing] = {nullptr}; hipEvent_t exp_ev[kExpRing] = {nullptr}; int exp_next = 0;
-  char *d_exp = nullptr; size_t exp_cap = 0;            // keyframes
-  char *d_expout = nullptr; size_t expout_cap = 0;      // records
+  PinMem<char> h_exp[kExpRing]; hipEvent_t exp_ev[kExpRing] = {nullptr}; int exp_next = 0;
+  DevMem<char> d_exp;                                   // keyframes
+  DevMem<float4> d_expout;                              // records
   std::vector<long long> exp_first; std::vector<int> exp_kbase;   // host scratch: exported points before every keyframe, keyframes before every store
   // vba_odom_lio_state_estimation_resident: the loop's device state, its pinned image (parameter block up, result
   // block down; also those of the kd-tree variant, §18) and the point loop's workgroup partials; grow-only
-  vbh::OdomEkf *d_odom = nullptr, *h_odom = nullptr;
-  double *d_odom_part = nullptr; size_t odom_part_doubles = 0;
+  DevMem<vbh::OdomEkf> d_odom; PinMem<vbh::OdomEkf> h_odom;
+  DevMem<double> d_odom_part;
 
   void set_error(const std::string &s) { err = s; }
 };
@@ -151,18 +150,19 @@ struct vba_btc_db {
   vba_ctx *ctx = nullptr;
   vba_btc_config cfg{};
   int nstd = 0, cap = 0;                     // descriptors stored / capacity (rows)
-  BtcStds d{};
+  BtcStds d{};                               // the view the kernels take of the six arrays below (btc_reserve_rows)
+  DevMem<double> tri, cen, loc; DevMem<unsigned long long> bits; DevMem<int> summ, frame;
   std::vector<int> tab;                      // host mirror of the cell table, 8 ints per slot (vba_kernels_btc.hpp)
   int tab_mask = 0, ncell = 0;
-  int *d_tab = nullptr;
+  DevMem<int> d_tab;
   int nchunk = 0, chunk_cap = 0;
-  int *d_ent = nullptr, *d_next = nullptr;
+  DevMem<int> d_ent, d_next;
   std::vector<int> off{0}, seq;              // plane clouds: point offsets, header.seq
-  float *d_pc = nullptr; size_t pc_cap = 0;
-  int *d_off = nullptr; int off_cap = 0;
-  int mcap = 0; int *d_m = nullptr;          // match list and per-candidate pair lists: mq | md | mf | pq | pd, mcap each
-  int vcap = 0; int *d_votes = nullptr;
-  int *d_cand = nullptr, *d_total = nullptr; double *d_cres = nullptr, *d_res = nullptr, *h_res = nullptr;
+  DevMem<float> d_pc; size_t pc_cap = 0;
+  DevMem<int> d_off; int off_cap = 0;
+  int mcap = 0; DevMem<int> d_m;             // match list and per-candidate pair lists: mq | md | mf | pq | pd, mcap each
+  int vcap = 0; DevMem<int> d_votes;
+  DevMem<int> d_cand, d_total; DevMem<double> d_cres, d_res; PinMem<double> h_res;
   bool have_search = false;                  // the last search ran the kernels (n > 0)
   // descriptor generation (vba_btc_generate_stds): its configuration, device buffers, the AddSTDescs count (current_frame_id_)
   // and the corners of the last call
@@ -183,17 +183,17 @@ struct vba_btc_db {
 struct vba_kf_store {
   vba_ctx *ctx = nullptr;
   // the keyframes: points (their own frame, float values in doubles) and covariance diagonals, ragged by off
-  double *d_pnt = nullptr; float *d_var = nullptr; size_t cap = 0;
+  DevMem<double> d_pnt; DevMem<float> d_var; size_t cap = 0;
   std::vector<int> off{0};
   struct Meta { double x0[12]; int id; double jour; int exist; };
   std::vector<Meta> kf;
   // scratch of one merge of up to mcap points: staged host input, merged cloud (also the world points of a load), gathered covariance
   // diagonals, per-voxel counts, the down-sampler's work area; pinned: gathered diagonals of a host covariance array
   size_t mcap = 0;
-  double *d_src = nullptr, *d_merge = nullptr, *d_mdiag = nullptr, *h_diag = nullptr;
-  int *d_cnt = nullptr; char *d_ws = nullptr; size_t ws_bytes = 0;
+  DevMem<double> d_src, d_merge, d_mdiag; PinMem<double> h_diag;
+  DevMem<int> d_cnt; DevMem<char> d_ws;
   // per-scan transforms [tcap][12] and offsets [tcap + 1]: pinned image and device copy; the voxel count of a build (pinned)
-  int tcap = 0; char *h_tab = nullptr, *d_tab = nullptr; int *h_n = nullptr;
+  int tcap = 0; PinMem<char> h_tab; DevMem<char> d_tab; PinMem<int> h_n;
   hipEvent_t ev = nullptr;
   int allocs = 0; int64_t bytes = 0;
   int hist = 0; std::vector<float> hist_pos;   // history_kfsize, pl_kdmap

@@ -428,12 +428,8 @@ int vba_hba_add_edge(vba_ctx *c, int wdsize, const int *offsets, const double *p
   double t_mark = want_times ? now() : 0.0;
   auto lap = [&](int k) { if (want_times) { hipStreamSynchronize(c->stream); const double t = now(); t_ph[k] += t - t_mark; t_mark = t; } };
   // the keyframe clouds stay in HBM for the whole call (every outer iteration re-cuts them with the current poses)
-  if ((size_t)n * 3 > c->refpts_doubles) {
-    if (c->d_refpts) hipFree(c->d_refpts);
-    c->refpts_doubles = (size_t)n * 3 + 3072;
-    HIPCHK(c, hipMalloc((void **)&c->d_refpts, 2 * c->refpts_doubles * sizeof(double)));
-  }
-  double *d_pl = c->d_refpts, *d_ref = c->d_refpts + c->refpts_doubles;
+  if ((size_t)n * 3 > c->d_refpts.n / 2) HIPCHK(c, c->d_refpts.ensure(2 * ((size_t)n * 3 + 3072)));      // two halves: the cloud, its reference
+  double *d_pl = c->d_refpts, *d_ref = c->d_refpts + c->d_refpts.n / 2;
   if (n > 0) HIPCHK(c, hipMemcpyAsync(d_pl, pnt_local, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
   GbaParams P = gba_params(c, gba_voxel_size, gba_min_eigen_value, gba_eigen_value_array);
   std::vector<double> hess(big ? 0 : (size_t)n6 * n6, 0.0), hd6;      // the any-window path keeps *hess in HBM and returns its block diagonals
@@ -567,12 +563,7 @@ int vba_hba_global(vba_ctx *c, int n_kf, const int *offsets, const double *pnt_l
   for (int r = 0; r < NR; r++) if (rank_cap[r] > chunk_pts) chunk_pts = rank_cap[r];
   if (!chunked) chunk_pts = 0;
   const size_t need = (n_all + n_sub_cap + (size_t)NR * chunk_pts) * 3 + (size_t)NR * meta_chunk + 64;
-  if (need > c->hba_all_doubles) {
-    if (c->d_hba_all) hipFree(c->d_hba_all);
-    c->d_hba_all = nullptr; c->hba_all_doubles = 0;
-    HIPCHK(c, hipMalloc((void **)&c->d_hba_all, need * sizeof(double)));
-    c->hba_all_doubles = need;
-  }
+  HIPCHK(c, c->d_hba_all.ensure(need));
   double *d_all = c->d_hba_all, *d_sub = c->d_hba_all + n_all * 3;
   if (n_all > 0 && !local_rep) HIPCHK(c, hipMemcpyAsync(d_all, pnt_local, n_all * 3 * sizeof(double), hipMemcpyDefault, c->stream));   // (the worker path uploads in chunks, under the first windows)
   std::vector<int> ccnt(n_win_max > 0 ? n_win_max : 1);

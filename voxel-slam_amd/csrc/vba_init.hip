@@ -114,13 +114,8 @@ static int motion_init_impl(vba_ctx *c, int W, const int *pt_offsets, const doub
   const size_t b_pnt = (size_t)np * 24, b_cv = (size_t)np * 8, b_pb = (size_t)n_out * 24, b_var = (size_t)n_out * 72,
                b_pose = (size_t)n_pose * INIT_POSE_LEN * 8, b_sc = (size_t)W * sizeof(InitScan), b_nnt = (size_t)(INIT_NNT_WG * 6 + 16) * 8;
   const size_t need = b_pnt + b_cv + b_pb + b_var + b_pose + b_sc + b_nnt + 64;
-  if (need > c->init_bytes) {
-    if (c->d_init) hipFree(c->d_init);
-    c->d_init = nullptr; c->init_bytes = 0;
-    HIPCHK(c, hipMalloc(&c->d_init, need));
-    c->init_bytes = need;
-  }
-  char *base = (char *)c->d_init;
+  HIPCHK(c, c->d_init.ensure(need));
+  char *base = c->d_init;
   double *d_pnt = (double *)base, *d_cv = (double *)(base + b_pnt), *d_pb = (double *)(base + b_pnt + b_cv), *d_var = (double *)(base + b_pnt + b_cv + b_pb),
          *d_pose = (double *)(base + b_pnt + b_cv + b_pb + b_var);
   InitScan *d_sc = (InitScan *)(base + b_pnt + b_cv + b_pb + b_var + b_pose);

@@ -25,7 +25,7 @@ int vba_scan_var_init(vba_ctx *c, int n, const double *pnt_in, const double *ext
   if (n == 0) return VBA_OK;
   int st = ensure_stage(c, ((size_t)n * 15 + 16) * sizeof(double));
   if (st) return st;
-  double *d_in = (double *)c->d_stage, *d_out = d_in + (size_t)n * 3, *d_var = d_out + (size_t)n * 3, *d_ext = d_var + (size_t)n * 9;
+  double *d_in = (double *)c->d_stage.p, *d_out = d_in + (size_t)n * 3, *d_var = d_out + (size_t)n * 3, *d_ext = d_var + (size_t)n * 9;
   HIPCHK(c, hipMemcpyAsync(d_in, pnt_in, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_ext, ext_pose, 12 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_var_init, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, d_in, d_out, d_var, d_ext, (float)dept_err, (float)beam_err);
@@ -96,7 +96,7 @@ static int ds_common(vba_ctx *c, int mode, int n, const double *pnt, const doubl
                b_dist = mode == 2 ? (size_t)n * sizeof(double) : 0;
   int st = ensure_stage(c, b_tab + 3 * b_pnt + b_var + b_dist + 3 * b_i + b_blk + 64 + b_sort + 256);
   if (st) return st;
-  char *base = (char *)c->d_stage;
+  char *base = (char *)c->d_stage.p;
   DsSlot *tab = (DsSlot *)base;
   double *d_in = (double *)(base + b_tab), *d_out = (double *)(base + b_tab + b_pnt), *d_vout = (double *)(base + b_tab + 2 * b_pnt),
          *d_var = (double *)(base + b_tab + 3 * b_pnt), *d_dist = (double *)(base + b_tab + 3 * b_pnt + b_var);
@@ -151,7 +151,7 @@ int vba_scan_undistort(vba_ctx *c, int n, double *pnt, const double *curv, int m
   const size_t nprm = (size_t)22 * m + 24;
   int st = ensure_stage(c, ((size_t)n * 4 + nprm) * sizeof(double));
   if (st) return st;
-  double *d_p = (double *)c->d_stage, *d_c = d_p + (size_t)n * 3, *d_prm = d_c + n;
+  double *d_p = (double *)c->d_stage.p, *d_c = d_p + (size_t)n * 3, *d_prm = d_c + n;
   std::vector<double> prm(nprm);
   std::memcpy(prm.data(), imu_poses, (size_t)22 * m * sizeof(double));
   std::memcpy(prm.data() + (size_t)22 * m, end_pose, 12 * sizeof(double));
@@ -177,12 +177,11 @@ namespace {
 
 size_t kf_tab_bytes(int t) { return (size_t)t * 12 * sizeof(double) + (((size_t)t + 1) * sizeof(int) + 15 & ~(size_t)15); }
 
+// a fresh device block of n elements, counted (vba_kf_allocations)
 template <class T>
-int kf_alloc(vba_kf_store *s, T **p, size_t n) {
-  vba_ctx *c = s->ctx;
-  if (*p) hipFree(*p);
-  *p = nullptr;
-  HIPCHK(c, hipMalloc((void **)p, (n ? n : 1) * sizeof(T)));
+int kf_alloc(vba_kf_store *s, DevMem<T> &m, size_t n) {
+  m.reset();
+  HIPCHK(s->ctx, m.ensure(n ? n : 1));
   s->allocs++; s->bytes += (int64_t)(n * sizeof(T));
   return VBA_OK;
 }
@@ -221,18 +220,10 @@ int kf_ensure_rows(vba_kf_store *s, size_t need) {
   vba_ctx *c = s->ctx;
   size_t m = s->cap ? s->cap : 65536;
   while (m < need) m *= 2;
-  double *np = nullptr; float *nv = nullptr;
-  HIPCHK(c, hipMalloc((void **)&np, m * 3 * sizeof(double)));
-  if (hipMalloc((void **)&nv, m * 3 * sizeof(float)) != hipSuccess) { hipFree(np); c->set_error("keyframe store: out of device memory"); return VBA_ERR_HIP; }
   const size_t have = (size_t)s->off.back();
-  if (have) {
-    HIPCHK(c, hipMemcpyAsync(np, s->d_pnt, have * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(nv, s->d_var, have * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (s->d_pnt) hipFree(s->d_pnt);
-  if (s->d_var) hipFree(s->d_var);
-  s->d_pnt = np; s->d_var = nv; s->cap = m;
+  HIPCHK(c, s->d_pnt.grow_keep(m * 3, have * 3, c->stream));
+  HIPCHK(c, s->d_var.grow_keep(m * 3, have * 3, c->stream));
+  s->cap = m;
   s->allocs += 2; s->bytes += (int64_t)(m * 3 * (sizeof(double) + sizeof(float)));
   return VBA_OK;
 }
@@ -247,14 +238,12 @@ int kf_ensure_merge(vba_kf_store *s, size_t need) {
   int st = VBA_OK;
   const size_t ws = kf_ws_layout(c, (int)m, true, nullptr, nullptr, &st);
   if (st) return st;
-  if ((st = kf_alloc(s, &s->d_src, 3 * m)) || (st = kf_alloc(s, &s->d_merge, 3 * m)) || (st = kf_alloc(s, &s->d_mdiag, 3 * m)) ||
-      (st = kf_alloc(s, &s->d_cnt, m)) || (st = kf_alloc(s, &s->d_ws, ws)))
+  if ((st = kf_alloc(s, s->d_src, 3 * m)) || (st = kf_alloc(s, s->d_merge, 3 * m)) || (st = kf_alloc(s, s->d_mdiag, 3 * m)) ||
+      (st = kf_alloc(s, s->d_cnt, m)) || (st = kf_alloc(s, s->d_ws, ws)))
     return st;
-  if (s->h_diag) hipHostFree(s->h_diag);
-  s->h_diag = nullptr;
-  HIPCHK(c, hipHostMalloc((void **)&s->h_diag, 3 * m * sizeof(double), hipHostMallocDefault));
+  HIPCHK(c, s->h_diag.ensure(3 * m));
   s->allocs++;
-  s->ws_bytes = ws; s->mcap = m;
+  s->mcap = m;
   return VBA_OK;
 }
 
@@ -264,11 +253,9 @@ int kf_ensure_tab(vba_kf_store *s, int k) {
   int t = s->tcap ? s->tcap : 64;
   while (t < k) t *= 2;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (s->h_tab) hipHostFree(s->h_tab);
-  s->h_tab = nullptr;
-  HIPCHK(c, hipHostMalloc((void **)&s->h_tab, kf_tab_bytes(t), hipHostMallocDefault));
+  HIPCHK(c, s->h_tab.ensure(kf_tab_bytes(t)));
   s->allocs++;
-  int st = kf_alloc(s, &s->d_tab, kf_tab_bytes(t));
+  int st = kf_alloc(s, s->d_tab, kf_tab_bytes(t));
   if (st) return st;
   s->tcap = t;
   return VBA_OK;
@@ -292,14 +279,14 @@ void kf_delta(const double *xc, const double *x, double *T) {
 // the transform table of k clouds with poses [k][12] (xc = the last) and row offsets rel [k + 1] -> pinned image -> device, on st
 int kf_upload_tab(vba_kf_store *s, int k, const double *const *poses, const int *rel, hipStream_t st) {
   vba_ctx *c = s->ctx;
-  double *T = (double *)s->h_tab;
+  double *T = (double *)s->h_tab.p;
   int *o = (int *)(s->h_tab + (size_t)s->tcap * 12 * sizeof(double));
   for (int i = 0; i < k; i++) kf_delta(poses[k - 1], poses[i], T + 12 * i);
   for (int i = 0; i <= k; i++) o[i] = rel[i];
   HIPCHK(c, hipMemcpyAsync(s->d_tab, s->h_tab, kf_tab_bytes(s->tcap), hipMemcpyHostToDevice, st));
   return VBA_OK;
 }
-const double *kf_dev_xf(const vba_kf_store *s) { return (const double *)s->d_tab; }
+const double *kf_dev_xf(const vba_kf_store *s) { return (const double *)s->d_tab.p; }
 const int *kf_dev_off(const vba_kf_store *s) { return (const int *)(s->d_tab + (size_t)s->tcap * 12 * sizeof(double)); }
 
 bool kf_pose_ok(const double *p) { for (int i = 0; i < 12; i++) if (!std::isfinite(p[i])) return false; return true; }
@@ -315,7 +302,7 @@ int vba_kf_create(vba_ctx *c, vba_kf_store **out) {
   vba_kf_store *s = new vba_kf_store();
   s->ctx = c;
   int st = kf_ensure_tab(s, 64);
-  if (!st && hipHostMalloc((void **)&s->h_n, 64, hipHostMallocDefault) != hipSuccess) st = VBA_ERR_HIP;
+  if (!st && s->h_n.ensure(16) != hipSuccess) st = VBA_ERR_HIP;
   if (!st && hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) st = VBA_ERR_HIP;
   if (st) { vba_kf_destroy(s); return st; }
   s->allocs++;
@@ -327,11 +314,6 @@ void vba_kf_destroy(vba_kf_store *s) {
   if (!s) return;
   hipSetDevice(s->ctx->device);
   hipStreamSynchronize(s->ctx->stream);
-  void *d[] = {s->d_pnt, s->d_var, s->d_src, s->d_merge, s->d_mdiag, s->d_cnt, s->d_ws, s->d_tab};
-  for (void *p : d) if (p) hipFree(p);
-  if (s->h_diag) hipHostFree(s->h_diag);
-  if (s->h_tab) hipHostFree(s->h_tab);
-  if (s->h_n) hipHostFree(s->h_n);
   if (s->ev) hipEventDestroy(s->ev);
   delete s;
 }
@@ -517,7 +499,7 @@ int vba_kf_load(vba_kf_store *s, int k, vba_ctx *mc, double jour) {
     // the keyframe's x0 goes through the pinned table; the world points into the merge scratch, on the map context's stream
     std::memcpy(s->h_tab, s->kf[k].x0, 12 * sizeof(double));
     HIPCHK(mc, hipMemcpyAsync(s->d_tab, s->h_tab, 12 * sizeof(double), hipMemcpyHostToDevice, mc->stream));
-    hipLaunchKernelGGL(k_kf_world, dim3((n + 255) / 256), dim3(256), 0, mc->stream, n, (const double *)s->d_tab, s->d_pnt + 3 * (size_t)b, s->d_merge);
+    hipLaunchKernelGGL(k_kf_world, dim3((n + 255) / 256), dim3(256), 0, mc->stream, n, (const double *)s->d_tab.p, s->d_pnt + 3 * (size_t)b, s->d_merge);
     HIPCHK(mc, hipGetLastError());
     st = map_cut_voxel_fix(mc->map, mc->stream, n, s->d_merge, jour, mc->err);   // ends with the map's counter read-back: one synchronise
     if (st) { hipStreamSynchronize(mc->stream); return st; }
@@ -586,28 +568,24 @@ inline long long exp_count(long long size, long long jump) { return (size + jump
 int exp_ensure_tab(vba_ctx *c, size_t entries) {
   for (int i = 0; i < vba_ctx::kExpRing; i++)
     if (!c->exp_ev[i]) HIPCHK(c, hipEventCreateWithFlags(&c->exp_ev[i], hipEventDisableTiming));
-  if (entries <= c->exp_cap) return VBA_OK;
-  size_t m = c->exp_cap ? c->exp_cap : 1024;
+  const size_t have = c->d_exp.n / sizeof(ExpKf);        // the device copy is made last
+  if (entries <= have) return VBA_OK;
+  size_t m = have ? have : 1024;
   while (m < entries) m *= 2;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int i = 0; i < vba_ctx::kExpRing; i++) { if (c->h_exp[i]) hipHostFree(c->h_exp[i]); c->h_exp[i] = nullptr; }
-  if (c->d_exp) hipFree(c->d_exp);
-  c->d_exp = nullptr; c->exp_cap = 0;
-  for (int i = 0; i < vba_ctx::kExpRing; i++) HIPCHK(c, hipHostMalloc((void **)&c->h_exp[i], m * sizeof(ExpKf), hipHostMallocDefault));
-  HIPCHK(c, hipMalloc((void **)&c->d_exp, m * sizeof(ExpKf)));
-  c->exp_cap = m;
+  c->d_exp.reset();
+  for (auto &h : c->h_exp) h.reset();
+  for (auto &h : c->h_exp) HIPCHK(c, h.ensure(m * sizeof(ExpKf)));
+  HIPCHK(c, c->d_exp.ensure(m * sizeof(ExpKf)));
   return VBA_OK;
 }
 
 int exp_ensure_out(vba_ctx *c, size_t recs) {
-  if (recs <= c->expout_cap) return VBA_OK;
-  size_t m = c->expout_cap ? c->expout_cap : 65536;
+  if (recs <= c->d_expout.n) return VBA_OK;
+  size_t m = c->d_expout.n ? c->d_expout.n : 65536;
   while (m < recs) m *= 2;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->d_expout) hipFree(c->d_expout);
-  c->d_expout = nullptr; c->expout_cap = 0;
-  HIPCHK(c, hipMalloc((void **)&c->d_expout, m * sizeof(float4)));
-  c->expout_cap = m;
+  HIPCHK(c, c->d_expout.ensure(m));
   return VBA_OK;
 }
 
@@ -681,7 +659,7 @@ int vba_kf_export_world(vba_ctx *c, int n_stores, vba_kf_store *const *stores, c
   const int slot = c->exp_next;
   c->exp_next = (slot + 1) % vba_ctx::kExpRing;
   HIPCHK(c, hipEventSynchronize(c->exp_ev[slot]));             // the upload that last read this image (kExpRing calls ago): long done
-  ExpKf *h = (ExpKf *)c->h_exp[slot];
+  ExpKf *h = (ExpKf *)c->h_exp[slot].p;
   for (int s = 0; s < n_stores; s++) {
     const vba_kf_store *S = stores[s];
     for (int g = std::max(ka, kbase[s]); g <= kb && g < kbase[s + 1]; g++) {
@@ -693,10 +671,10 @@ int vba_kf_export_world(vba_ctx *c, int n_stores, vba_kf_store *const *stores, c
   }
   HIPCHK(c, hipMemcpyAsync(c->d_exp, h, (size_t)nk * sizeof(ExpKf), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipEventRecord(c->exp_ev[slot], c->stream));
-  const ExpKf *d_tab = (const ExpKf *)c->d_exp;
+  const ExpKf *d_tab = (const ExpKf *)c->d_exp.p;
   for (long long cb = begin; cb < end; cb += dev_out ? count : kExpChunk) {
     const long long ce = dev_out ? end : std::min(end, cb + kExpChunk);
-    float4 *out = dev_out ? (float4 *)xyzi : (float4 *)c->d_expout;                     // the record of cb
+    float4 *out = dev_out ? (float4 *)xyzi : c->d_expout.p;                     // the record of cb
     for (int s = 0; s < n_stores; s++) {                       // one launch per store: its point array, its intensity, its rows of the table
       const long long a = std::max(cb, first[kbase[s]]), b = std::min(ce, first[kbase[s + 1]]);
       if (a >= b) continue;

@@ -22,8 +22,8 @@ struct vba_loop_map {
   MapStore map;                                  // map_loop; after vba_loop_update the map the context gave up (ping-pong)
   size_t res_fix = 0, res_nodes = 0;             // vba_loop_map_reserve: applied to whichever store the object owns
   // segment table int4 [tcap] + poses double [tcap][12]: pinned image and device copy
-  int tcap = 0; char *h_tab = nullptr, *d_tab = nullptr;
-  char *d_in = nullptr; size_t in_bytes = 0;     // host-memory scans of vba_loop_update on their way to the device
+  int tcap = 0; PinMem<char> h_tab; DevMem<char> d_tab;
+  DevMem<char> d_in;                             // host-memory scans of vba_loop_update on their way to the device
   int allocs = 0; int64_t bytes = 0;
 };
 
@@ -59,29 +59,24 @@ int lm_ensure_tab(vba_loop_map *lm, int t) {
   int m = lm->tcap ? lm->tcap : 64;
   while (m < t) m *= 2;
   HIPCHK(c, hipDeviceSynchronize());
-  if (lm->h_tab) hipHostFree(lm->h_tab);
-  if (lm->d_tab) hipFree(lm->d_tab);
-  lm->h_tab = nullptr; lm->d_tab = nullptr; lm->tcap = 0;
-  HIPCHK(c, hipHostMalloc((void **)&lm->h_tab, lm_tab_bytes(m), hipHostMallocDefault));
-  HIPCHK(c, hipMalloc((void **)&lm->d_tab, lm_tab_bytes(m)));
+  lm->tcap = 0;
+  HIPCHK(c, lm->h_tab.ensure(lm_tab_bytes(m)));
+  HIPCHK(c, lm->d_tab.ensure(lm_tab_bytes(m)));
   lm->allocs += 2; lm->bytes += (int64_t)lm_tab_bytes(m);
   lm->tcap = m;
   return VBA_OK;
 }
 int lm_ensure_in(vba_loop_map *lm, size_t bytes) {
-  if (bytes <= lm->in_bytes) return VBA_OK;
+  if (bytes <= lm->d_in.n) return VBA_OK;
   vba_ctx *c = lm->ctx;
   HIPCHK(c, hipDeviceSynchronize());
-  if (lm->d_in) hipFree(lm->d_in);
-  lm->d_in = nullptr; lm->in_bytes = 0;
-  HIPCHK(c, hipMalloc((void **)&lm->d_in, bytes));
+  HIPCHK(c, lm->d_in.ensure(bytes));
   lm->allocs++; lm->bytes += (int64_t)bytes;
-  lm->in_bytes = bytes;
   return VBA_OK;
 }
-int4 *lm_h_seg(vba_loop_map *lm) { return (int4 *)lm->h_tab; }
+int4 *lm_h_seg(vba_loop_map *lm) { return (int4 *)lm->h_tab.p; }
 double *lm_h_pose(vba_loop_map *lm) { return (double *)(lm->h_tab + (size_t)lm->tcap * sizeof(int4)); }
-const int4 *lm_d_seg(vba_loop_map *lm) { return (const int4 *)lm->d_tab; }
+const int4 *lm_d_seg(vba_loop_map *lm) { return (const int4 *)lm->d_tab.p; }
 const double *lm_d_pose(vba_loop_map *lm) { return (const double *)(lm->d_tab + (size_t)lm->tcap * sizeof(int4)); }
 
 // the reservation on the store the object owns now
@@ -133,9 +128,6 @@ void vba_loop_map_destroy(vba_loop_map *lm) {
   hipSetDevice(lm->ctx->device);
   hipStreamSynchronize(lm->ctx->stream);
   map_free(lm->map);
-  if (lm->h_tab) hipHostFree(lm->h_tab);
-  if (lm->d_tab) hipFree(lm->d_tab);
-  if (lm->d_in) hipFree(lm->d_in);
   delete lm;
 }
 
@@ -260,7 +252,7 @@ int vba_loop_update(vba_ctx *c, vba_loop_map *lm, const double *dx12, int k, con
       hipError_t e = hipMemcpyAsync(lm->d_in, d_p, (size_t)n_bl * 24, hipMemcpyHostToDevice, st);
       if (e == hipSuccess && var) e = hipMemcpyAsync(lm->d_in + (size_t)n_bl * 24, d_v, (size_t)n_bl * 72, hipMemcpyHostToDevice, st);
       if (e != hipSuccess) { c->set_error("vba_loop_update: scan upload failed"); return fail(VBA_ERR_HIP); }
-      d_p = (const double *)lm->d_in; d_v = var ? (const double *)(lm->d_in + (size_t)n_bl * 24) : nullptr;
+      d_p = (const double *)lm->d_in.p; d_v = var ? (const double *)(lm->d_in + (size_t)n_bl * 24) : nullptr;
     }
     FixSource src;
     src.nseg = k; src.d_seg = lm_d_seg(lm); src.d_poses = lm_d_pose(lm); src.d_pnt = d_p;

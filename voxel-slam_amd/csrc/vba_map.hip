@@ -577,8 +577,8 @@ int map_dump_leaves(MapStore &s, hipStream_t st, double *out, int max_leaves, st
   const int nn = s.h_cnt[CNT_NODES] < s.v.cap ? s.h_cnt[CNT_NODES] : s.v.cap;
   if (nn == 0) return 0;
   const int cap_out = out ? max_leaves : 0;
-  double *d_out = nullptr;
-  if (cap_out > 0 && hipMalloc((void **)&d_out, (size_t)cap_out * 39 * 8) != hipSuccess) return -1;
+  DevMem<double> d_out;                         // a temporary of this call
+  if (cap_out > 0 && d_out.ensure((size_t)cap_out * 39) != hipSuccess) return -1;
   if (map_set_counter(s, st, CNT_LEAVES, 0, err)) return -1;
   if (s.det) {   // rows in ascending node id
     hipLaunchKernelGGL(k_dump_leaves<1>, dim3((nn + 255) / 256), dim3(256), 0, st, s.v, d_out, cap_out);
@@ -589,10 +589,7 @@ int map_dump_leaves(MapStore &s, hipStream_t st, double *out, int max_leaves, st
   }
   if (map_read_counters(s, st, err)) return -1;
   const int n = s.h_cnt[CNT_LEAVES];
-  if (cap_out > 0) {
-    hipMemcpy(out, d_out, (size_t)(n < cap_out ? n : cap_out) * 39 * 8, hipMemcpyDeviceToHost);
-    hipFree(d_out);
-  }
+  if (cap_out > 0) hipMemcpy(out, d_out, (size_t)(n < cap_out ? n : cap_out) * 39 * 8, hipMemcpyDeviceToHost);
   return n;
 }
 
@@ -602,8 +599,8 @@ int map_dump_plane_var(MapStore &s, hipStream_t st, double *out, int max_leaves,
   const int nn = s.h_cnt[CNT_NODES] < s.v.cap ? s.h_cnt[CNT_NODES] : s.v.cap;
   if (nn == 0) return 0;
   const int cap_out = out ? max_leaves : 0;
-  double *d_out = nullptr;
-  if (cap_out > 0 && hipMalloc((void **)&d_out, (size_t)cap_out * 86 * 8) != hipSuccess) return -1;
+  DevMem<double> d_out;                         // a temporary of this call
+  if (cap_out > 0 && d_out.ensure((size_t)cap_out * 86) != hipSuccess) return -1;
   if (map_set_counter(s, st, CNT_LEAVES, 0, err)) return -1;
   if (s.det) {   // rows in ascending node id
     hipLaunchKernelGGL(k_dump_plane_var<1>, dim3((nn + 255) / 256), dim3(256), 0, st, s.v, d_out, cap_out);
@@ -614,10 +611,7 @@ int map_dump_plane_var(MapStore &s, hipStream_t st, double *out, int max_leaves,
   }
   if (map_read_counters(s, st, err)) return -1;
   const int n = s.h_cnt[CNT_LEAVES];
-  if (cap_out > 0) {
-    hipMemcpy(out, d_out, (size_t)(n < cap_out ? n : cap_out) * 86 * 8, hipMemcpyDeviceToHost);
-    hipFree(d_out);
-  }
+  if (cap_out > 0) hipMemcpy(out, d_out, (size_t)(n < cap_out ? n : cap_out) * 86 * 8, hipMemcpyDeviceToHost);
   return n;
 }
 

@@ -15,20 +15,11 @@ extern "C" {
 
 // ---------------------------------------------------------------- initialisation odometry on a point-cloud map (vba_kernels_kd.hpp)
 static int kd_reserve(vba_ctx *c, size_t pts) {
-  if (pts <= c->kd_cap) return VBA_OK;
-  size_t cap = c->kd_cap ? c->kd_cap : 65536;
+  const size_t have = c->d_kdtree[1].n / 3;             // points; the second half grows last
+  if (pts <= have) return VBA_OK;
+  size_t cap = have ? have : 65536;
   while (cap < pts) cap *= 2;
-  for (int i = 0; i < 2; i++) {
-    double *nw = nullptr;
-    HIPCHK(c, hipMalloc((void **)&nw, cap * 3 * sizeof(double)));
-    if (c->d_kdtree[i]) {
-      if (i == c->kd_cur && c->kd_n > 0) HIPCHK(c, hipMemcpyAsync(nw, c->d_kdtree[i], (size_t)c->kd_n * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      hipFree(c->d_kdtree[i]);
-    }
-    c->d_kdtree[i] = nw;
-  }
-  c->kd_cap = cap;
+  for (int i = 0; i < 2; i++) HIPCHK(c, c->d_kdtree[i].grow_keep(cap * 3, i == c->kd_cur ? (size_t)c->kd_n * 3 : 0, c->stream));
   c->kd_allocs += 2; c->kd_bytes += (int64_t)(2 * cap * 3 * sizeof(double));
   return VBA_OK;
 }
@@ -48,9 +39,11 @@ int vba_odom_kdtree_points(vba_ctx *c, double *out) {
 // ---------------------------------------------------------------- its EKF loop, resident on the device
 // device state and pinned image of the resident EKF loops (this one and the voxel map's)
 static int odom_image_ensure(vba_ctx *c) {
-  if (c->d_odom) return VBA_OK;
-  HIPCHK(c, hipMalloc((void **)&c->d_odom, sizeof(vbh::OdomEkf)));
-  HIPCHK(c, hipHostMalloc((void **)&c->h_odom, sizeof(vbh::OdomEkf), hipHostMallocDefault));
+  if (c->h_odom) return VBA_OK;                         // the pinned image is made last: complete or empty
+  HIPCHK(c, c->d_odom.ensure(1));
+  const hipError_t e = c->h_odom.ensure(1);
+  if (e != hipSuccess) c->d_odom.reset();
+  HIPCHK(c, e);
   c->kd_allocs += 2; c->kd_bytes += (int64_t)(2 * sizeof(vbh::OdomEkf));
   return VBA_OK;
 }
@@ -77,10 +70,9 @@ static int kd_scan_ensure(vba_ctx *c, size_t pts) {
   size_t cap = c->kdscan_pts ? c->kdscan_pts : 16384;
   while (cap < pts) cap *= 2;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->d_kdscan) hipFree(c->d_kdscan);
-  c->d_kdscan = nullptr; c->kdscan_pts = 0;
+  c->d_kdscan.reset(); c->kdscan_pts = 0;
   const size_t b = kd_scan_layout(cap).bytes;
-  HIPCHK(c, hipMalloc((void **)&c->d_kdscan, b));
+  HIPCHK(c, c->d_kdscan.ensure(b));
   c->kdscan_pts = cap; c->kd_allocs++; c->kd_bytes += (int64_t)b;
   return VBA_OK;
 }
@@ -94,11 +86,10 @@ static int kd_ws_ensure(vba_ctx *c, size_t pts) {
   const size_t ws = kf_ws_layout(c, (int)cap, true, nullptr, nullptr, &st);
   if (st) return st;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->d_kdws) hipFree(c->d_kdws);
-  c->d_kdws = nullptr; c->kdws_pts = 0; c->kdws_bytes = 0;
+  c->d_kdws.reset(); c->kdws_pts = 0;
   const size_t b = 2 * kd_up(cap * sizeof(int)) + ws;
-  HIPCHK(c, hipMalloc((void **)&c->d_kdws, b));
-  c->kdws_pts = cap; c->kdws_bytes = b; c->kd_allocs++; c->kd_bytes += (int64_t)b;
+  HIPCHK(c, c->d_kdws.ensure(b));
+  c->kdws_pts = cap; c->kd_allocs++; c->kd_bytes += (int64_t)b;
   return VBA_OK;
 }
 
@@ -137,12 +128,12 @@ static int kd_odom_core(vba_ctx *c, int n, const double *d_pts, double *state, d
   }
   if ((st = odom_image_ensure(c)) || (st = kd_scan_ensure(c, (size_t)n)) || (st = kd_ws_ensure(c, tot))) return st;
   const bool det = c->opt.deterministic != 0;
-  int *d_cnt = (int *)c->d_kdws, *d_first = (int *)(c->d_kdws + kd_up(c->kdws_pts * sizeof(int)));
+  int *d_cnt = (int *)c->d_kdws.p, *d_first = (int *)(c->d_kdws + kd_up(c->kdws_pts * sizeof(int)));
   char *ws = c->d_kdws + 2 * kd_up(c->kdws_pts * sizeof(int));
   DsWork w{};
-  if (2 * kd_up(c->kdws_pts * sizeof(int)) + kf_ws_layout(c, (int)tot, det, ws, &w, &st) > c->kdws_bytes || st) return st ? st : VBA_ERR_CAPACITY;
+  if (2 * kd_up(c->kdws_pts * sizeof(int)) + kf_ws_layout(c, (int)tot, det, ws, &w, &st) > c->d_kdws.n || st) return st ? st : VBA_ERR_CAPACITY;
   const KdScanLayout L = kd_scan_layout(c->kdscan_pts);
-  double *d_pl = (double *)c->d_kdscan, *d_part = (double *)(c->d_kdscan + L.o_part);
+  double *d_pl = (double *)c->d_kdscan.p, *d_part = (double *)(c->d_kdscan + L.o_part);
   unsigned long long *d_cand = (unsigned long long *)(c->d_kdscan + L.o_cand);
   // the image: cov_inv = P^-1 / 1000 entry by entry (VS:1134, VS:1213), the first iteration searches
   double cov_inv[225];
@@ -207,7 +198,7 @@ int vba_odom_lio_state_estimation_kdtree(vba_ctx *c, int n, const double *pnt_bo
   if (st) return st;
   if (n > 0) HIPCHK(c, hipMemcpyAsync(c->d_stage, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
   bool ran;
-  if ((st = kd_odom_core(c, n, (const double *)c->d_stage, state, cov, &ran))) return st;
+  if ((st = kd_odom_core(c, n, (const double *)c->d_stage.p, state, cov, &ran))) return st;
   if (!ran) HIPCHK(c, hipStreamSynchronize(c->stream));                    // seeded: the core only enqueued the append
   else if (iterations) *iterations = c->h_odom->iterations;
   return VBA_OK;
@@ -222,13 +213,10 @@ static int odom_core(vba_ctx *c, int n, const double *d_pts, const double *d_var
   int st = odom_image_ensure(c);
   if (st) return st;
   const size_t need = (size_t)((n + 255) / 256) * 34;
-  if (need > c->odom_part_doubles) {
-    if (c->d_odom_part) hipFree(c->d_odom_part);       // idle: the call that used it ended in a synchronise
-    c->d_odom_part = nullptr; c->odom_part_doubles = 0;
+  if (need > c->d_odom_part.n) {
     size_t cap = 256 * 34;
     while (cap < need) cap *= 2;
-    HIPCHK(c, hipMalloc((void **)&c->d_odom_part, cap * sizeof(double)));
-    c->odom_part_doubles = cap;
+    HIPCHK(c, c->d_odom_part.ensure(cap));               // idle: the call that used it ended in a synchronise
   }
   double cov_inv[225];
   vbh::inverse_pplu(cov, cov_inv, VBA_DIM);                                // VS:987
@@ -259,7 +247,7 @@ int vba_odom_lio_state_estimation(vba_ctx *c, int n, const double *pnt_body, con
   if (n < 0 || (n > 0 && (!pnt_body || !var_body)) || !state || !cov) return VBA_ERR_BAD_ARG;
   int st = ensure_stage(c, (size_t)n * 12 * sizeof(double));             // [pts n*3 | var n*9]
   if (st) return st;
-  double *d_pts = (double *)c->d_stage, *d_var = d_pts + (size_t)n * 3;
+  double *d_pts = (double *)c->d_stage.p, *d_var = d_pts + (size_t)n * 3;
   if (n > 0) {
     HIPCHK(c, hipMemcpyAsync(d_pts, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_var, var_body, (size_t)n * 9 * sizeof(double), hipMemcpyDefault, c->stream));

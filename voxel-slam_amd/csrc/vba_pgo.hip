@@ -177,25 +177,23 @@ int vba_pgo_optimize(vba_ctx *c, int n, double *poses, int m, const double *edge
       o_dx = take((size_t)n * 48), o_res = take((size_t)U * 24 + 8);   // cost[U] | mx[U] | cnt[U] | status
   HIPCHK(c, hipSetDevice(c->device));
   // grow-only buffers owned by the context; a size the device cannot hold is VBA_ERR_CAPACITY (the old buffer is released first)
-  auto grow = [&](void **buf, size_t &have, size_t want, const char *what) -> int {
-    if (want <= have) return VBA_OK;
-    if (*buf) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(*buf)); *buf = nullptr; have = 0; }
+  auto grow = [&](auto &buf, size_t want, const char *what) -> int {            // want: bytes
+    if (want <= buf.n * sizeof(*buf.p)) return VBA_OK;
+    if (buf) { HIPCHK(c, hipStreamSynchronize(c->stream)); buf.reset(); }
     size_t fr = 0, tot = 0;
     HIPCHK(c, hipMemGetInfo(&fr, &tot));
-    const hipError_t e = want > fr ? hipErrorOutOfMemory : hipMalloc(buf, want);
+    const hipError_t e = want > fr ? hipErrorOutOfMemory : buf.ensure(want / sizeof(*buf.p));
     if (e == hipErrorOutOfMemory) {
       (void)hipGetLastError();                      // a refused allocation must not surface in a later call's error check
-      *buf = nullptr;
       c->set_error(std::string("vba_pgo_optimize: the ") + what + " needs " + std::to_string(want) + " bytes, " + std::to_string(fr) + " free");
       return VBA_ERR_CAPACITY;
     }
     HIPCHK(c, e);
-    have = want;
     return VBA_OK;
   };
   const size_t abytes = ((size_t)(NP + 1) * ld + (size_t)(NP + 1) * 8) * 8;
-  if (int r = grow((void **)&c->d_pgo, c->pgo_bytes, bytes, "graph structure")) return r;
-  if (int r = grow((void **)&c->d_pgoAb, c->pgoAb_bytes, abytes, "dense skeleton system (8 (6K)^2 bytes)")) return r;
+  if (int r = grow(c->d_pgo, bytes, "graph structure")) return r;
+  if (int r = grow(c->d_pgoAb, abytes, "dense skeleton system (8 (6K)^2 bytes)")) return r;
   char *d = c->d_pgo;
   PgoView v{};
   v.n = n; v.F = F; v.NB = NB; v.S = S; v.K = K; v.NSB = NSB; v.U = U; v.NP = NP; v.ld = ld; v.thr = relin_threshold;

@@ -15,18 +15,18 @@ using namespace vba;
 struct vba_scan_frame {
   vba_ctx *ctx = nullptr;
   // raw message bytes (16-byte aligned, padded to a multiple of 16)
-  unsigned char *d_raw = nullptr; size_t raw_cap = 0;
+  DevMem<unsigned char> d_raw;
   // everything sized by the number of raw points: one block, carved by frame_carve
-  char *d_pts = nullptr; int pcap = 0;
+  DevMem<char> d_pts; int pcap = 0;
   float *d_rec = nullptr; unsigned int *d_key = nullptr, *d_kin = nullptr, *d_kout = nullptr; int *d_vin = nullptr, *d_vout = nullptr, *d_blk = nullptr, *d_res = nullptr;
   double *d_pnt0 = nullptr, *d_curv = nullptr; float *d_int = nullptr;                     // stage 0: decoded, sorted, cut
   double *d_pnt1 = nullptr;                                                               // stage 1: undistorted
   double *d_dsp = nullptr; int *d_dscnt = nullptr, *d_dsfirst = nullptr;                  // stage 2: down-sampled
   double *d_pb = nullptr, *d_vb = nullptr;                                                // stage 3: var_init
-  char *d_sort = nullptr; size_t sort_bytes = 0;                                          // rocPRIM scratch of the time sort
-  char *d_ws = nullptr; size_t ws_bytes = 0;                                              // the down-sampler's work area
-  double *d_prm = nullptr, *h_prm = nullptr; int prm_cap = 0;                             // undistortion parameters: pinned image, device copy
-  int *h_res = nullptr;                                                                   // pinned: {n, bits of the last curvature, kept, -, voxels}
+  DevMem<char> d_sort;                                                                    // rocPRIM scratch of the time sort
+  DevMem<char> d_ws;                                                                      // the down-sampler's work area
+  DevMem<double> d_prm; PinMem<double> h_prm; int prm_cap = 0;                            // undistortion parameters: pinned image, device copy
+  PinMem<int> h_res;                                                                      // pinned: {n, bits of the last curvature, kept, -, voxels}
   int allocs = 0; int64_t bytes = 0;
   bool decoded = false, prepared = false;
   int n = 0, n_ds = 0;
@@ -64,17 +64,16 @@ int frame_drain(vba_scan_frame *f) {
 
 // grow-only, by doubling from `first` bytes (first == 0: exactly `need`, the caller doubles), after a synchronise; the contents do not
 // survive (a decode rewrites all of them)
-int frame_grow(vba_scan_frame *f, char **p, size_t *cap, size_t need, size_t first) {
-  if (need <= *cap) return VBA_OK;
+template <class Byte>
+int frame_grow(vba_scan_frame *f, DevMem<Byte> &p, size_t need, size_t first) {
+  if (need <= p.n) return VBA_OK;
   vba_ctx *c = f->ctx;
-  size_t m = first ? (*cap ? *cap : first) : need;
+  size_t m = first ? (p.n ? p.n : first) : need;
   while (m < need) m *= 2;
   int st = frame_drain(f);
   if (st) return st;
-  if (*p) hipFree(*p);
-  *p = nullptr; *cap = 0;
-  HIPCHK(c, hipMalloc((void **)p, m));
-  *cap = m; f->allocs++; f->bytes += (int64_t)m;
+  HIPCHK(c, p.ensure(m));
+  f->allocs++; f->bytes += (int64_t)m;
   f->decoded = f->prepared = false;
   return VBA_OK;
 }
@@ -84,8 +83,7 @@ int frame_ensure_points(vba_scan_frame *f, int need) {
   if (need > f->pcap) {
     int m = f->pcap ? f->pcap : 65536;
     while (m < need) m *= 2;
-    size_t have = 0;
-    int st = frame_grow(f, &f->d_pts, &have, frame_carve(f, nullptr, m), 0);
+    int st = frame_grow(f, f->d_pts, frame_carve(f, nullptr, m), 0);
     if (st) { f->pcap = 0; return st; }
     frame_carve(f, f->d_pts, m);
     f->pcap = m;
@@ -94,11 +92,11 @@ int frame_ensure_points(vba_scan_frame *f, int need) {
   // scratch of the sort over pcap pairs and of the down-sampler over pcap + 2 points (deterministic mode is the larger layout)
   size_t tmp = 0;
   HIPCHK(c, sort_pairs_u32(nullptr, tmp, nullptr, nullptr, nullptr, nullptr, (size_t)f->pcap, 32u, c->stream));
-  int st = frame_grow(f, &f->d_sort, &f->sort_bytes, up(tmp), 1 << 16);
+  int st = frame_grow(f, f->d_sort, up(tmp), 1 << 16);
   if (st) return st;
   const size_t ws = kf_ws_layout(c, f->pcap + 2, true, nullptr, nullptr, &st);
   if (st) return st;
-  if ((st = frame_grow(f, &f->d_ws, &f->ws_bytes, ws, 1 << 16))) return st;
+  if ((st = frame_grow(f, f->d_ws, ws, 1 << 16))) return st;
   f->scratch_for = f->pcap;
   return VBA_OK;
 }
@@ -110,12 +108,10 @@ int frame_ensure_prm(vba_scan_frame *f, int m) {
   while (k < m) k *= 2;
   int st = frame_drain(f);
   if (st) return st;
-  if (f->d_prm) hipFree(f->d_prm);
-  if (f->h_prm) hipHostFree(f->h_prm);
-  f->d_prm = f->h_prm = nullptr; f->prm_cap = 0;
+  f->prm_cap = 0;
   const size_t b = ((size_t)22 * k + 24) * sizeof(double);
-  HIPCHK(c, hipMalloc((void **)&f->d_prm, b));
-  HIPCHK(c, hipHostMalloc((void **)&f->h_prm, b, hipHostMallocDefault));
+  HIPCHK(c, f->d_prm.ensure((size_t)22 * k + 24));
+  HIPCHK(c, f->h_prm.ensure((size_t)22 * k + 24));
   f->prm_cap = k; f->allocs += 2; f->bytes += (int64_t)b;
   return VBA_OK;
 }
@@ -160,7 +156,7 @@ int vba_scan_frame_create(vba_ctx *c, vba_scan_frame **out) {
   vba_scan_frame *f = new vba_scan_frame();
   f->ctx = c;
   int st = frame_ensure_prm(f, 64);
-  if (!st && hipHostMalloc((void **)&f->h_res, 64, hipHostMallocDefault) != hipSuccess) st = VBA_ERR_HIP;
+  if (!st && f->h_res.ensure(16) != hipSuccess) st = VBA_ERR_HIP;
   if (st) { vba_scan_frame_destroy(f); return st; }
   f->allocs++;
   *out = f;
@@ -172,10 +168,6 @@ void vba_scan_frame_destroy(vba_scan_frame *f) {
   hipSetDevice(f->ctx->device);
   hipStreamSynchronize(f->ctx->stream);
   if (f->last && f->last != f->ctx->stream) hipDeviceSynchronize();
-  void *d[] = {f->d_raw, f->d_pts, f->d_sort, f->d_ws, f->d_prm};
-  for (void *p : d) if (p) hipFree(p);
-  if (f->h_prm) hipHostFree(f->h_prm);
-  if (f->h_res) hipHostFree(f->h_res);
   delete f;
 }
 
@@ -183,7 +175,7 @@ int vba_scan_frame_reserve(vba_scan_frame *f, int max_raw_points, int max_point_
   if (!f || max_raw_points < 0 || max_point_step < 1 || max_raw_points > (1 << 28) || max_point_step > (1 << 16)) return VBA_ERR_BAD_ARG;
   vba_ctx *c = f->ctx;
   HIPCHK(c, hipSetDevice(c->device));
-  int st = frame_grow(f, (char **)&f->d_raw, &f->raw_cap, ((size_t)max_raw_points * (size_t)max_point_step + 15) & ~(size_t)15, 1 << 20);
+  int st = frame_grow(f, f->d_raw, ((size_t)max_raw_points * (size_t)max_point_step + 15) & ~(size_t)15, 1 << 20);
   if (st) return st;
   return frame_ensure_points(f, max_raw_points > 0 ? max_raw_points : 1);
 }
@@ -208,7 +200,7 @@ int vba_scan_decode(vba_scan_frame *f, const vba_scan_layout *l, const void *raw
   HIPCHK(c, hipSetDevice(c->device));
   f->decoded = f->prepared = false;
   const size_t nbytes = (size_t)n_raw * (size_t)l->point_step, padded = (nbytes + 15) & ~(size_t)15;
-  int st = frame_grow(f, (char **)&f->d_raw, &f->raw_cap, padded, 1 << 20);
+  int st = frame_grow(f, f->d_raw, padded, 1 << 20);
   if (st || (st = frame_ensure_points(f, n_raw > 0 ? n_raw : 1))) return st;
   hipStream_t s = c->stream;
   f->last = s;
@@ -226,7 +218,7 @@ int vba_scan_decode(vba_scan_frame *f, const vba_scan_layout *l, const void *raw
   hipLaunchKernelGGL(k_ds_scan, dim3(1), dim3(256), 0, s, nb, f->d_blk, d_total);
   if (n_raw > 0) {
     hipLaunchKernelGGL(k_scan_pairs, dim3(nb), dim3(256), 0, s, n_raw, l->filter, point_filter_num, n_sort, f->d_key, f->d_blk, d_total, f->d_kin, f->d_vin);
-    size_t tmp = f->sort_bytes;
+    size_t tmp = f->d_sort.n;
     HIPCHK(c, sort_pairs_u32(f->d_sort, tmp, f->d_kin, f->d_kout, f->d_vin, f->d_vout, (size_t)n_sort, 32u, s));
   }
   float fcut = (float)0.11;                                        // the largest float that is <= 0.11 as a double
@@ -272,7 +264,7 @@ int vba_scan_prepare(vba_ctx *c, vba_scan_frame *f, int m, const double *imu_pos
   int nd = n;
   const bool det = c->opt.deterministic != 0;
   DsWork w{};
-  if (kf_ws_layout(c, n, det, f->d_ws, &w, &st) > f->ws_bytes || st) return st ? st : VBA_ERR_CAPACITY;
+  if (kf_ws_layout(c, n, det, f->d_ws, &w, &st) > f->d_ws.n || st) return st ? st : VBA_ERR_CAPACITY;
   auto down_sample = [&](double vs) -> int {
     if (vs < 0.001) {                                              // TL:203: the cloud as it is, counts 0
       HIPCHK(c, hipMemcpyAsync(f->d_dsp, f->d_pnt1, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));

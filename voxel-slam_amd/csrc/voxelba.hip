@@ -95,19 +95,11 @@ void span_end(vba_ctx *c, const char *name, TimedSpan &s) {
 }
 
 int ensure_pin(vba_ctx *c, size_t n) {
-  if (n <= c->pin_doubles) return VBA_OK;
-  if (c->h_pin) hipHostFree(c->h_pin);
-  c->h_pin = nullptr; c->pin_doubles = 0;
-  HIPCHK(c, hipHostMalloc((void **)&c->h_pin, n * sizeof(double), hipHostMallocDefault));
-  c->pin_doubles = n;
+  HIPCHK(c, c->h_pin.ensure(n));
   return VBA_OK;
 }
 int ensure_stage(vba_ctx *c, size_t bytes) {
-  if (bytes <= c->stage_bytes) return VBA_OK;
-  if (c->d_stage) hipFree(c->d_stage);
-  c->d_stage = nullptr; c->stage_bytes = 0;
-  HIPCHK(c, hipMalloc(&c->d_stage, bytes));
-  c->stage_bytes = bytes;
+  HIPCHK(c, c->d_stage.ensure(bytes));
   return VBA_OK;
 }
 
@@ -123,26 +115,25 @@ int factor_reserve(vba_ctx *c, int need) {
   FactorView n = c->fv;
   n.vs = newcap; n.W = W;
   const size_t rows[6] = {(size_t)10 * W, 10, 1, 3, 9, 10};
-  double **np[6] = {&n.cl, &n.fix, &n.coe, &n.eigval, &n.eigvec, &n.pcr};
-  double *op[6] = {c->fv.cl, c->fv.fix, c->fv.coe, c->fv.eigval, c->fv.eigvec, c->fv.pcr};
+  // the new set is built in locals and swapped in after the synchronise: an early return frees it, the old set dies at scope exit
+  DevMem<double> nr[6]; DevMem<unsigned int> nocc; DevMem<int> ntiles;
   for (int k = 0; k < 6; k++) {
-    HIPCHK(c, hipMalloc((void **)np[k], rows[k] * newcap * sizeof(double)));
-    HIPCHK(c, hipMemsetAsync(*np[k], 0, rows[k] * newcap * sizeof(double), c->stream));
-    if (c->nvox > 0 && op[k])
-      HIPCHK(c, hipMemcpy2DAsync(*np[k], (size_t)newcap * sizeof(double), op[k], (size_t)c->cap * sizeof(double),
+    HIPCHK(c, nr[k].ensure(rows[k] * newcap));
+    HIPCHK(c, hipMemsetAsync(nr[k], 0, rows[k] * newcap * sizeof(double), c->stream));
+    if (c->nvox > 0 && c->fv_rows[k])
+      HIPCHK(c, hipMemcpy2DAsync(nr[k], (size_t)newcap * sizeof(double), c->fv_rows[k], (size_t)c->cap * sizeof(double),
                                  (size_t)c->nvox * sizeof(double), rows[k], hipMemcpyDeviceToDevice, c->stream));
   }
-  unsigned int *oocc = c->fv.occ;
-  int *otiles = c->fv.tiles;
-  HIPCHK(c, hipMalloc((void **)&n.tiles, ((size_t)4 * newcap + 16) * sizeof(int)));
-  HIPCHK(c, hipMemsetAsync(n.tiles, 0, ((size_t)4 * newcap + 16) * sizeof(int), c->stream));
-  HIPCHK(c, hipMalloc((void **)&n.occ, (size_t)newcap * sizeof(unsigned int)));
-  HIPCHK(c, hipMemsetAsync(n.occ, 0, (size_t)newcap * sizeof(unsigned int), c->stream));
-  if (c->nvox > 0 && oocc) HIPCHK(c, hipMemcpyAsync(n.occ, oocc, (size_t)c->nvox * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, ntiles.ensure((size_t)4 * newcap + 16));
+  HIPCHK(c, hipMemsetAsync(ntiles, 0, ((size_t)4 * newcap + 16) * sizeof(int), c->stream));
+  HIPCHK(c, nocc.ensure((size_t)newcap));
+  HIPCHK(c, hipMemsetAsync(nocc, 0, (size_t)newcap * sizeof(unsigned int), c->stream));
+  if (c->nvox > 0 && c->fv_occ) HIPCHK(c, hipMemcpyAsync(nocc, c->fv_occ, (size_t)c->nvox * sizeof(unsigned int), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int k = 0; k < 6; k++) if (op[k]) hipFree(op[k]);
-  if (oocc) hipFree(oocc);
-  if (otiles) hipFree(otiles);
+  for (int k = 0; k < 6; k++) std::swap(c->fv_rows[k], nr[k]);
+  std::swap(c->fv_occ, nocc); std::swap(c->fv_tiles, ntiles);
+  n.cl = c->fv_rows[0]; n.fix = c->fv_rows[1]; n.coe = c->fv_rows[2]; n.eigval = c->fv_rows[3]; n.eigvec = c->fv_rows[4]; n.pcr = c->fv_rows[5];
+  n.occ = c->fv_occ; n.tiles = c->fv_tiles;
   c->fv = n;
   if (c->nvox > 0 && c->use_h3) hipLaunchKernelGGL(k_factor_tiles, dim3(1), dim3(1024), 0, c->stream, c->fv, c->nvox);   // (the table lives in the new allocation)
   c->cap = newcap;
@@ -427,7 +418,7 @@ int residual_pass(vba_ctx *c, const double *poses_dev, const int *gate, int head
     HIPCHK(c, hipMemsetAsync(d_scalar_out, 0, sizeof(double), c->stream));
   } else {
     const int nb = residual_nb(c, end - head);
-    if ((size_t)nb > c->partial_doubles) { c->set_error("partial buffer too small"); return VBA_ERR_CAPACITY; }
+    if ((size_t)nb > c->d_partial.n) { c->set_error("partial buffer too small"); return VBA_ERR_CAPACITY; }
     TimedSpan s1{}, s2{};
     span_begin(c, "residual", s1);
     launch_residual(c, poses_dev, gate, head, end);
@@ -473,11 +464,7 @@ int eval_residual_dev(vba_ctx *c, const double *poses, int head, int end, double
 }
 
 int ensure_partial(vba_ctx *c, size_t doubles) {
-  if (doubles <= c->partial_doubles) return VBA_OK;
-  if (c->d_partial) hipFree(c->d_partial);
-  c->d_partial = nullptr; c->partial_doubles = 0;
-  HIPCHK(c, hipMalloc((void **)&c->d_partial, doubles * sizeof(double)));
-  c->partial_doubles = doubles;
+  HIPCHK(c, c->d_partial.ensure(doubles));
   return VBA_OK;
 }
 
@@ -553,13 +540,10 @@ int vba_create(const vba_options *opt, vba_ctx **out) {
   }
   const int W = opt->win_size, nout = nout_of(W);
   c->fv.W = W;
-  if (hipMalloc((void **)&c->d_poses, (size_t)VBA_MAX_WIN * 12 * sizeof(double)) != hipSuccess ||
-      hipMalloc((void **)&c->d_out, ((size_t)nout_tl(W) + 64) * sizeof(double)) != hipSuccess ||
-      hipMalloc((void **)&c->d_full, ((size_t)nout + 64) * sizeof(double)) != hipSuccess ||
-      hipMalloc((void **)&c->d_scal, 64 * sizeof(double)) != hipSuccess) { vba_destroy(c); return VBA_ERR_HIP; }
+  if (c->d_poses.ensure((size_t)VBA_MAX_WIN * 12) != hipSuccess || c->d_out.ensure((size_t)nout_tl(W) + 64) != hipSuccess ||
+      c->d_full.ensure((size_t)nout + 64) != hipSuccess || c->d_scal.ensure(64) != hipSuccess) { vba_destroy(c); return VBA_ERR_HIP; }
   if (ensure_partial(c, (size_t)kMaxBlocksHess * (nout_tl(W) > nout ? nout_tl(W) : nout)) != VBA_OK || ensure_pin(c, 65536 + (size_t)nout + 1024) != VBA_OK) { vba_destroy(c); return VBA_ERR_HIP; }
-  if (hipMalloc((void **)&c->d_lm, sizeof(LmDev)) != hipSuccess || hipMalloc((void **)&c->d_raw, ((size_t)nout_tl(W) + 64) * 8) != hipSuccess ||
-      hipHostMalloc((void **)&c->h_lm, sizeof(LmDev), hipHostMallocDefault) != hipSuccess) { vba_destroy(c); return VBA_ERR_HIP; }
+  if (c->d_lm.ensure(1) != hipSuccess || c->d_raw.ensure((size_t)nout_tl(W) + 64) != hipSuccess || c->h_lm.ensure(1) != hipSuccess) { vba_destroy(c); return VBA_ERR_HIP; }
   if (opt->max_voxels && factor_reserve(c, (int)opt->max_voxels) != VBA_OK) { vba_destroy(c); return VBA_ERR_HIP; }
   map_init(c->map, c->opt);
   *out = c;
@@ -576,46 +560,10 @@ void vba_destroy(vba_ctx *c) {
   c->big.release();
   for (vba_ctx *w : c->hba_workers) vba_destroy(w);
   c->hba_workers.clear();
-  if (c->d_hba_all) hipFree(c->d_hba_all);
-  if (c->d_init) hipFree(c->d_init);
-  if (c->d_btcq) hipFree(c->d_btcq);
-  if (c->h_btcq) hipHostFree(c->h_btcq);
-  if (c->d_btccnt) hipFree(c->d_btccnt);
-  if (c->d_icp) hipFree(c->d_icp);
-  if (c->h_icp) hipHostFree(c->h_icp);
-  if (c->d_icpkey) hipFree(c->d_icpkey);
-  if (c->d_icppart) hipFree(c->d_icppart);
-  if (c->d_pgo) hipFree(c->d_pgo);
-  if (c->d_pgoAb) hipFree(c->d_pgoAb);
-  for (int i = 0; i < vba_ctx::kExpRing; i++) { if (c->h_exp[i]) hipHostFree(c->h_exp[i]); if (c->exp_ev[i]) hipEventDestroy(c->exp_ev[i]); }
-  if (c->d_exp) hipFree(c->d_exp);
-  if (c->d_expout) hipFree(c->d_expout);
-  if (c->d_odom) hipFree(c->d_odom);
-  if (c->h_odom) hipHostFree(c->h_odom);
-  if (c->d_odom_part) hipFree(c->d_odom_part);
-  if (c->d_lipack) hipFree(c->d_lipack);
-  if (c->d_liscr) hipFree(c->d_liscr);
-  for (int i = 0; i < 2; i++) if (c->d_kdtree[i]) hipFree(c->d_kdtree[i]);
-  if (c->d_kdscan) hipFree(c->d_kdscan);
-  if (c->d_kdws) hipFree(c->d_kdws);
-  if (c->d_refpts) hipFree(c->d_refpts);
-  if (c->d_li) hipFree(c->d_li);
-  if (c->d_k4part) hipFree(c->d_k4part);
-  if (c->d_imu) hipFree(c->d_imu);
-  if (c->d_himu) hipFree(c->d_himu);
-  if (c->d_gimu) hipFree(c->d_gimu);
-  double *p[] = {c->fv.cl, c->fv.fix, c->fv.coe, c->fv.eigval, c->fv.eigvec, c->fv.pcr, c->d_poses, c->d_partial, c->d_out, c->d_full, c->d_scal};
-  for (double *q : p) if (q) hipFree(q);
-  if (c->fv.occ) hipFree(c->fv.occ);
-  if (c->fv.tiles) hipFree(c->fv.tiles);
-  if (c->d_stage) hipFree(c->d_stage);
-  if (c->h_pin) hipHostFree(c->h_pin);
-  if (c->d_lm) hipFree(c->d_lm);
-  if (c->d_raw) hipFree(c->d_raw);
-  if (c->h_lm) hipHostFree(c->h_lm);
+  for (hipEvent_t e : c->exp_ev) if (e) hipEventDestroy(e);
   for (auto &kv : c->spans) for (auto &s : kv.second) { hipEventDestroy(s.a); hipEventDestroy(s.b); }
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
-  delete c;
+  delete c;      // the buffers free themselves here (vba_mem.hpp), after the stream has been drained
 }
 
 const char *vba_last_error(vba_ctx *c) { return c ? c->err.c_str() : ""; }
@@ -635,7 +583,7 @@ int vba_factor_push_voxels(vba_ctx *c, int n, const double *clusters, const doub
   const size_t per = (size_t)10 * W + 33;
   st = ensure_stage(c, per * n * sizeof(double));
   if (st) return st;
-  double *d = (double *)c->d_stage;
+  double *d = (double *)c->d_stage.p;
   double *d_cl = d, *d_fix = d_cl + (size_t)n * W * 10, *d_coe = d_fix + (size_t)n * 10, *d_ev = d_coe + n, *d_evec = d_ev + (size_t)n * 3,
          *d_pcr = d_evec + (size_t)n * 9;
   HIPCHK(c, hipMemcpyAsync(d_cl, clusters, (size_t)n * W * 10 * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -686,7 +634,7 @@ int vba_factor_read_back(vba_ctx *c, double *eig_val, double *eig_vec, double *p
   if (n == 0) return VBA_OK;
   int st = ensure_stage(c, (size_t)n * 22 * sizeof(double));
   if (st) return st;
-  double *d = (double *)c->d_stage;
+  double *d = (double *)c->d_stage.p;
   double *d_ev = d, *d_evec = d + (size_t)n * 3, *d_pcr = d_evec + (size_t)n * 9;
   int nb = (int)(((long long)n * 22 + 255) / 256);
   if (nb > 4096) nb = 4096;
@@ -713,7 +661,7 @@ int vba_factor_occupied_slots(vba_ctx *c, long long *slots) {
   int st = ensure_stage(c, 64);
   if (st) return st;
   HIPCHK(c, hipMemsetAsync(c->d_stage, 0, 8, c->stream));
-  hipLaunchKernelGGL(k_count_slots, dim3(512), dim3(256), 0, c->stream, c->fv, c->nvox, (unsigned long long *)c->d_stage);
+  hipLaunchKernelGGL(k_count_slots, dim3(512), dim3(256), 0, c->stream, c->fv, c->nvox, (unsigned long long *)c->d_stage.p);
   unsigned long long h = 0;
   HIPCHK(c, hipMemcpyAsync(&h, c->d_stage, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -754,10 +702,10 @@ int vba_lm_begin(vba_ctx *c, const double *poses, int thd_num) {
 // damping_iter (VM:1628); a caller that restarts the optimiser on an unchanged factor store uses this instead.
 int vba_lm_refresh_eigen(vba_ctx *c) {
   if (!c->lm.active) return VBA_ERR_BAD_ARG;
-  const double *x_dev = reinterpret_cast<const double *>(reinterpret_cast<char *>(c->d_lm) + offsetof(LmDev, x));
+  const double *x_dev = reinterpret_cast<const double *>(reinterpret_cast<char *>(c->d_lm.p) + offsetof(LmDev, x));
   if (c->nvox <= 0) return VBA_OK;
   // only the pass' side effect is wanted (eig_values / eig_vectors / pcr_adds at the begin poses): its partials are not summed
-  if ((size_t)residual_nb(c, c->nvox) > c->partial_doubles) { c->set_error("partial buffer too small"); return VBA_ERR_CAPACITY; }
+  if ((size_t)residual_nb(c, c->nvox) > c->d_partial.n) { c->set_error("partial buffer too small"); return VBA_ERR_CAPACITY; }
   TimedSpan s1{};
   span_begin(c, "residual", s1);
   // single-rank: the pass carries the call's init when it is the first LM kernel; the multi-rank flow takes the stand-alone init
@@ -771,7 +719,7 @@ int vba_lm_refresh_eigen(vba_ctx *c) {
 
 int vba_timing_launch_hessian(vba_ctx *c) {
   if (!c->lm.active || c->nvox <= 0) return VBA_ERR_BAD_ARG;
-  const double *x_dev = reinterpret_cast<const double *>(reinterpret_cast<char *>(c->d_lm) + offsetof(LmDev, x));
+  const double *x_dev = reinterpret_cast<const double *>(reinterpret_cast<char *>(c->d_lm.p) + offsetof(LmDev, x));
   int nb = 0;
   int st = lm_init_flush(c);
   if (st) return st;
@@ -786,7 +734,7 @@ int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
   if (!c->lm.active) return VBA_ERR_BAD_ARG;
   const int W = c->opt.win_size, nout = nout_of(W), V = c->nvox;
   if (c->nvox_global < c->lm.thd_num) { c->lm_init.pending = false; return VBA_ERR_TOO_FEW_VOXELS; }   // VM:399-403 (and g_size checks of VM:367); the same on every rank
-  char *base = reinterpret_cast<char *>(c->d_lm);
+  char *base = reinterpret_cast<char *>(c->d_lm.p);
   const double *x_dev = reinterpret_cast<const double *>(base + offsetof(LmDev, x));
   const double *xt_dev = reinterpret_cast<const double *>(base + offsetof(LmDev, xt));
   const int *run_hess = reinterpret_cast<const int *>(base + offsetof(LmDev, run_hess));
@@ -830,11 +778,9 @@ int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
     hipLaunchKernelGGL(k_lm_update, dim3(1), dim3(64), 0, c->stream, c->d_lm, c->d_out + (nout_tl(W) - 1), 0, W);
   } else {
     const int nb = residual_nb(c, V);
-    if (nb > c->k4part_cap) {
-      if (c->d_k4part) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(c->d_k4part); c->d_k4part = nullptr; }
-      const int cap = nb > 65536 ? 2 * nb : 65536;
-      HIPCHK(c, hipMalloc((void **)&c->d_k4part, (size_t)cap * sizeof(double)));
-      c->k4part_cap = cap;
+    if ((size_t)nb > c->d_k4part.n) {
+      if (c->d_k4part) HIPCHK(c, hipStreamSynchronize(c->stream));
+      HIPCHK(c, c->d_k4part.ensure(nb > 65536 ? 2 * (size_t)nb : 65536));
     }
     const bool fuse = !no_fuse && !(accepted || stop);
     TimedSpan s1{};
@@ -939,12 +885,9 @@ static int launch_li_solve(vba_ctx *c, int copy_raw, int n, int gauge, int grav)
   constexpr size_t l_doubles = LiSolveCfg<W>::l_doubles, lds = LiSolveCfg<W>::lds;
   static bool attr_set[kMaxDevices] = {false};
   if (!attr_set[c->device % kMaxDevices]) { hipFuncSetAttribute((const void *)k_li_solve<W, NT, GL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set[c->device % kMaxDevices] = true; }
-  if (GL && c->liscr_doubles < l_doubles * LM_SPEC) {           // one region per damping candidate; W is fixed per context, so this runs once
+  if (GL && c->d_liscr.n < l_doubles * LM_SPEC) {           // one region per damping candidate; W is fixed per context, so this runs once
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->d_liscr) hipFree(c->d_liscr);
-    c->d_liscr = nullptr; c->liscr_doubles = 0;
-    HIPCHK(c, hipMalloc((void **)&c->d_liscr, l_doubles * LM_SPEC * sizeof(double)));
-    c->liscr_doubles = l_doubles * LM_SPEC;
+    HIPCHK(c, c->d_liscr.ensure(l_doubles * LM_SPEC));
   }
   hipLaunchKernelGGL((k_li_solve<W, NT, GL>), dim3(c->lm_spec), dim3(NT), lds, c->stream, c->d_lm, c->d_li, c->d_out, c->d_raw, copy_raw, c->d_himu, c->d_gimu, c->d_imu, n, gauge, grav,
                      c->opt.imu_coef, c->d_liscr, nullptr);
@@ -961,10 +904,10 @@ static int li_setup(vba_ctx *c, const double *states, const double *imus, int gr
   const int W = c->opt.win_size, DIM = VBA_DIM, F = W - 1;
   const int n = W * DIM + (gravity ? 3 : 0), nb = gravity ? 33 : 30;
   if (!c->d_li) {
-    HIPCHK(c, hipMalloc((void **)&c->d_li, sizeof(LiDev)));
-    HIPCHK(c, hipMalloc((void **)&c->d_imu, (size_t)LI_MAX_W * 304 * sizeof(double)));
-    HIPCHK(c, hipMalloc((void **)&c->d_himu, (size_t)LI_MAX_N * LI_MAX_N * sizeof(double)));
-    HIPCHK(c, hipMalloc((void **)&c->d_gimu, (size_t)LI_MAX_N * sizeof(double)));
+    HIPCHK(c, c->d_li.ensure(1));
+    HIPCHK(c, c->d_imu.ensure((size_t)LI_MAX_W * 304));
+    HIPCHK(c, c->d_himu.ensure((size_t)LI_MAX_N * LI_MAX_N));
+    HIPCHK(c, c->d_gimu.ensure((size_t)LI_MAX_N));
   }
   // upload: LM state (poses view), the IMU extras, the factors with cov^-1 in place of cov
   std::vector<double> poses((size_t)W * 12);
@@ -1028,7 +971,7 @@ static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, i
   std::vector<double> fimg;
   int st = li_setup(c, states, imus, gravity, h, fimg);
   if (st) return st;
-  char *base = reinterpret_cast<char *>(c->d_lm);
+  char *base = reinterpret_cast<char *>(c->d_lm.p);
   const double *x_dev = reinterpret_cast<const double *>(base + offsetof(LmDev, x));
   const double *xt_dev = reinterpret_cast<const double *>(base + offsetof(LmDev, xt));
   const int *run_hess = reinterpret_cast<const int *>(base + offsetof(LmDev, run_hess));
@@ -1107,17 +1050,12 @@ static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, i
                o_lm = o_lid + (size_t)n6 * n6, o_end = o_lm + sizeof(LmDev) / 8;
   st = ensure_pin(c, o_end + 64);
   if (st) return st;
-  if (o_end + 64 > c->lipack_doubles) {
-    if (c->d_lipack) hipFree(c->d_lipack);
-    c->d_lipack = nullptr; c->lipack_doubles = 0;
-    HIPCHK(c, hipMalloc((void **)&c->d_lipack, (o_end + 64) * sizeof(double)));
-    c->lipack_doubles = o_end + 64;
-  }
+  HIPCHK(c, c->d_lipack.ensure(o_end + 64));
   PackSegs segs{};
   segs.n = 3;
-  segs.src[0] = (const double *)c->d_li; segs.off[0] = o_li; segs.len[0] = sizeof(LiDev) / 8;
+  segs.src[0] = (const double *)c->d_li.p; segs.off[0] = o_li; segs.len[0] = sizeof(LiDev) / 8;
   segs.src[1] = c->d_imu; segs.off[1] = o_img; segs.len[1] = fimg.size();
-  segs.src[2] = (const double *)c->d_lm; segs.off[2] = o_lm; segs.len[2] = sizeof(LmDev) / 8;
+  segs.src[2] = (const double *)c->d_lm.p; segs.off[2] = o_lm; segs.len[2] = sizeof(LmDev) / 8;
   if (hess) {
     st = tiles_to_full(c, copy_raw ? c->d_raw : c->d_out);
     if (st) return st;
@@ -1187,7 +1125,7 @@ static int debug_li_imu_run(vba_ctx *c, int gravity, int flags, const double *st
   std::vector<double> fimg;
   int st = li_setup(c, states, imus, gravity, h, fimg);
   if (st) return st;
-  char *base = reinterpret_cast<char *>(c->d_lm);
+  char *base = reinterpret_cast<char *>(c->d_lm.p);
   const double *x_dev = reinterpret_cast<const double *>(base + offsetof(LmDev, x));
   const int *run_hess = reinterpret_cast<const int *>(base + offsetof(LmDev, run_hess));
   const size_t lds_imu = li_imu_lds(F, nb);
@@ -1317,13 +1255,13 @@ int vba_set_shard(vba_ctx *c, int rank, int n_ranks) {
 int vba_timing_calibration_read(vba_ctx *c, size_t n_bytes) {
   const size_t nblk = n_bytes / (256 * 128);
   if (nblk == 0 || nblk > 0x7fffffffu) return VBA_ERR_BAD_ARG;
-  double *buf = nullptr;
-  HIPCHK(c, hipMalloc((void **)&buf, nblk * 256 * 128 + 64));
+  DevMem<char> mem;                             // freed at scope exit, after the synchronise
+  HIPCHK(c, mem.ensure(nblk * 256 * 128 + 64));
+  double *buf = (double *)mem.p;
   HIPCHK(c, hipMemsetAsync(buf, 0, nblk * 256 * 128 + 64, c->stream));
   hipLaunchKernelGGL(k_calib_read8, dim3((unsigned)nblk), dim3(256), 0, c->stream, buf, buf + nblk * 256 * 16);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  hipFree(buf);
   return VBA_OK;
 }
 int vba_timing_enable(vba_ctx *c, int on) { c->timing = on != 0; return VBA_OK; }
