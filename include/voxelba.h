@@ -960,6 +960,58 @@ int vba_scan_prepare(vba_ctx *ctx, vba_scan_frame *f, int m, const double *imu_p
 int vba_scan_frame_read(vba_scan_frame *f, int stage, double *pnt, float *intensity, double *curvature, int *count, int *first,
                         double *var);
 
+/* ------------------------------------------------------------------------------------------------
+ * Initialisation window: pl_origs of initialization() (VS:1499-1516) resident in HBM.  Per scan of the window the
+ * node does  pl_down = orig; down_sampling_close(pl_down, down_size); if (size < 1000) { pl_down = orig; down_sampling_close(pl_down,
+ * down_size / 2) }; sort(curvature <); pl_origs.push_back(pl_down)  with orig the copy of pcl_curr taken before odom_ekf.process
+ * (VS:1458): the frame's stage 0, which vba_scan_prepare leaves alone.  The window holds the ragged clouds in the form
+ * vba_motion_init reads (pnt [n][3], curv [n], PCL floats carried in doubles); the offsets stay on the host.
+ *
+ * Stage 0 is sorted by curvature with a STABLE sort and down_sampling_close keeps a subset of it, so the reference's sort, with ties
+ * resolved as the scan front end resolves them (message order), is that subset in ascending stage-0 index: push runs no sort, it
+ * compacts in index order.
+ *
+ * A window belongs to the device of ctx and works on ctx's stream.  Its buffers grow by doubling and keep their contents; after
+ * vba_init_window_reserve(w, max_scans, max_points_per_scan) no call allocates while the window holds at most max_scans scans and
+ * every pushed frame's decoded cloud (or pushed array) has at most max_points_per_scan points; vba_init_window_allocations counts
+ * allocations and bytes as vba_scan_frame_allocations does.  Destroy it before its context. */
+typedef struct vba_init_window vba_init_window;
+int vba_init_window_create(vba_ctx *ctx, vba_init_window **out);
+void vba_init_window_destroy(vba_init_window *w);
+int vba_init_window_reserve(vba_init_window *w, int max_scans, int max_points_per_scan);
+int vba_init_window_allocations(vba_init_window *w, int *n_allocs, int64_t *bytes);
+int vba_init_window_clear(vba_init_window *w);   /* pl_origs.clear() (VS:795); the storage is kept */
+/* *n_scans = pl_origs.size(); offsets [n_scans + 1] (may be NULL): rows before every scan, and their total */
+int vba_init_window_size(vba_init_window *w, int *n_scans, int64_t *offsets);
+/* Appends one scan from the frame's stage 0, read in place on the window's stream (the frame may have been decoded or prepared on
+ * another context of the same device; the read is ordered behind the decode).  The selection is vba_scan_down_sampling_close at
+ * down_size (float centroid, first point in input order among equal distances, only distances < 100 compete; vba_options::deterministic
+ * of the window's context selects the summation).  If min_points > 0 and fewer than min_points points are kept (strict, VS:1503; the
+ * node passes 1000), once more from the full decoded cloud at down_size / 2, that result kept whatever its count, *retried = 1.  A
+ * size < 0.001 leaves the cloud as it is (TL:242), on either pass.  The kept rows are written in ascending stage-0 index, xyz and
+ * curvature bit for bit.  A frame with n = 0 appends an empty scan.  Complete when it returns: one synchronise, two when the retry
+ * runs.  VBA_ERR_BAD_ARG, window unchanged: an undecoded frame, a frame on another device, a NULL output pointer. */
+int vba_init_window_push(vba_init_window *w, vba_scan_frame *frame, double down_size, int min_points, int *n_kept, int *retried);
+/* Appends pnt [n][3], curv [n] as they are (HOST or DEVICE arrays; one synchronise).  The curvatures must ascend: HOST arrays are
+ * checked (VBA_ERR_BAD_ARG), DEVICE arrays are NOT, the caller answers for them. */
+int vba_init_window_push_points(vba_init_window *w, int n, const double *pnt, const double *curv);
+/* Inspection (synchronises): the rows of one scan; NULL outputs are skipped. */
+int vba_init_window_read(vba_init_window *w, int scan, double *pnt, double *curv);
+
+/* vba_motion_init with pl_origs taken from a window: the arguments of vba_motion_init with pt_offsets, pnt, curv replaced by w.  The
+ * clouds are read in place, no copy of them is made on the host or the device.  What the host walk of vba_motion_init reads from the
+ * curvatures (per scan the number of leading points at or before the oldest pose, and the curvature of point 0) is found by one small
+ * kernel (binary search; curvature ascends) and crosses in one W-row download with one synchronise; everything after that is the code
+ * of vba_motion_init, and the results are the same bit for bit.  The window must hold exactly win_size scans and live on ctx's device
+ * (it may belong to another context of it): VBA_ERR_BAD_ARG before any device work otherwise.  The window is not cleared.  Errors and
+ * what they leave behind: as vba_motion_init. */
+int vba_motion_init_resident(vba_ctx *ctx, int win_size, vba_init_window *w, const int *imu_offsets, const double *imu,
+                             const double *beg_times, const double *ext_pose, double dept_err, double beam_err, double scale_gravity,
+                             int point_notime, const double *noise_meas_diag6, const double *noise_walk_diag6, double *states,
+                             const double *covs, double *imus, double *hess, int *converged, double *eigvalue3, int *iterations,
+                             int *thresholds_left_relaxed, double *round_log, int max_rounds, double *pnt_out, double *var_out,
+                             int *pvec_offsets, int pvec_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@
 //   cut_voxel / cut_voxel_multi / cut_voxel(fix)  VM:1896/1964/2108 vba::VoxelMap::cut_voxel[_multi|_fix]
 //   multi_recut / multi_margi    VS:1682 / VS:1590                  vba::VoxelMap::multi_recut / multi_margi
 //   Initialization::motion_init  VS:617-819                         vba::Initialization::motion_init
+//   initialization(), pl_origs   VS:1499-1516                       vba::InitWindow::push + the InitWindow overload of motion_init
 //   build_graph + gtsam::ISAM2   VS:2078-2156, VS:2550-2561          vba::PoseGraph (add_edge LR:147-161, set_state LR:36-43)
 //   ResultOutput::pub_globalmap  VS:110-154                         vba::pub_globalmap
 //   pcl_handler VH:77-103; motion_blur's loop + VS:1877-1888        vba::ScanFrame::decode / prepare (ScanView feeds the odometry and the map)
@@ -275,6 +276,38 @@ class VoxelMap {
   vba_ctx *c_;
 };
 
+// ---- the initialisation window: pl_origs of initialization() (VS:1499-1516), resident in HBM
+class InitWindow {
+ public:
+  explicit InitWindow(Context &ctx) : ctx_(ctx.get()) { check(ctx_, vba_init_window_create(ctx_, &w_)); }
+  ~InitWindow() { vba_init_window_destroy(w_); }
+  InitWindow(const InitWindow &) = delete;
+  InitWindow &operator=(const InitWindow &) = delete;
+  void reserve(int max_scans, int max_points_per_scan) { check(ctx_, vba_init_window_reserve(w_, max_scans, max_points_per_scan)); }
+  // pl_down = orig; down_sampling_close(pl_down, down_size); the `< 1000` retry at down_size / 2; sort(curvature <);
+  // pl_origs.push_back(pl_down)  (VS:1499-1512) on the frame's decoded cloud (`orig`, VS:1458).  Returns the points kept.
+  int push(ScanFrame &orig, double down_size, int min_points = 1000, bool *retried = nullptr) {
+    int n = 0, r = 0;
+    check(ctx_, vba_init_window_push(w_, orig.get(), down_size, min_points, &n, &r));
+    if (retried) *retried = r != 0;
+    return n;
+  }
+  // a cloud the caller holds (host or device arrays [n][3], [n]; curvature ascending), appended as it is
+  void push_points(int n, const double *pnt, const double *curv) { check(ctx_, vba_init_window_push_points(w_, n, pnt, curv)); }
+  int size() const { int n = 0; vba_init_window_size(w_, &n, nullptr); return n; }                  // pl_origs.size()
+  long long points() const {                                                                       // points of all scans
+    std::vector<int64_t> off((size_t)size() + 1);
+    int n = 0;
+    vba_init_window_size(w_, &n, off.data());
+    return (long long)off.back();
+  }
+  void clear() { check(ctx_, vba_init_window_clear(w_)); }                                          // pl_origs.clear() (VS:795)
+  vba_init_window *get() const { return w_; }
+ private:
+  vba_ctx *ctx_;
+  vba_init_window *w_ = nullptr;
+};
+
 // ---- LiDAR-inertial initialisation: class Initialization (voxelslam.cpp:460-820)
 struct PointXYZC { float x, y, z, curvature; };   // the fields of a PointType (pcl::PointXYZINormal) that motion_init reads
 struct ImuSample { double t, gyr[3], acc[3]; };   // one sensor_msgs::Imu of a deque: stamp, angular_velocity, linear_acceleration
@@ -302,17 +335,57 @@ class Initialization {
     if ((int)pl_origs.size() < W || (int)vec_imus.size() < W || (int)beg_times.size() < W || (int)x_buf.size() < W ||
         (int)imu_pre_buf.size() < W - 1)
       throw std::runtime_error("libvoxelba: motion_init: fewer than win_size scans / states / IMU factors");
-    std::vector<int> pto(W + 1, 0), imo(W + 1, 0);
-    for (int i = 0; i < W; i++) { pto[i + 1] = pto[i] + (int)pl_origs[i].size(); imo[i + 1] = imo[i] + (int)vec_imus[i].size(); }
-    std::vector<double> pnt((size_t)pto[W] * 3 + 3), curv((size_t)pto[W] + 1), imu((size_t)imo[W] * 7 + 7);
-    for (int i = 0; i < W; i++) {
+    std::vector<int> pto(W + 1, 0);
+    for (int i = 0; i < W; i++) pto[i + 1] = pto[i] + (int)pl_origs[i].size();
+    std::vector<double> pnt((size_t)pto[W] * 3 + 3), curv((size_t)pto[W] + 1);
+    for (int i = 0; i < W; i++)
       for (size_t k = 0; k < pl_origs[i].size(); k++) {
         const PointXYZC &a = pl_origs[i][k];
         const size_t r = (size_t)pto[i] + k;
         pnt[3 * r] = a.x; pnt[3 * r + 1] = a.y; pnt[3 * r + 2] = a.z; curv[r] = a.curvature;
       }
+    const int converged = run(pto[W], vec_imus, beg_times, hess, voxhess, x_buf, pvec_buf, W, x_curr, imu_pre_buf, extrin_para, [&](const Call &a) {
+      return vba_motion_init(voxhess.ctx(), W, pto.data(), pnt.data(), curv.data(), a.imo, a.imu, beg_times.data(), a.ext, dept_err, beam_err, scale_gravity,
+                             point_notime, noise_meas, noise_walk, a.st, a.cov, a.im, a.hess, a.converged, eigvalue, &iterations, &thresholds_left_relaxed,
+                             nullptr, 0, a.po, a.vo, a.pvo, a.cap);
+    });
+    (void)surf_map;   // the map (and voxhess) stay on the context, as surf_map / voxhess in the reference
+    pl_origs.clear(); vec_imus.clear(); beg_times.clear();         // VS:795-797
+    return converged;
+  }
+
+  // The same with pl_origs resident in HBM: the window the node filled with InitWindow::push, one scan at a time, in
+  // place of VS:1499-1512.  The clouds are read where they are; the window is cleared on return, as the vectors are.
+  int motion_init(InitWindow &pl_origs, std::vector<std::vector<ImuSample>> &vec_imus, std::vector<double> &beg_times, std::vector<double> *hess,
+                  LidarFactor &voxhess, std::vector<IMUST> &x_buf, VoxelMap &surf_map, std::vector<std::shared_ptr<PVec>> &pvec_buf, int win_size,
+                  IMUST &x_curr, std::deque<IMU_PRE *> &imu_pre_buf, const IMUST &extrin_para) {
+    const int W = win_size;
+    if (pl_origs.size() != W || (int)vec_imus.size() < W || (int)beg_times.size() < W || (int)x_buf.size() < W || (int)imu_pre_buf.size() < W - 1)
+      throw std::runtime_error("libvoxelba: motion_init: the window does not hold win_size scans, or fewer than win_size states / IMU factors");
+    const int converged = run((int)pl_origs.points(), vec_imus, beg_times, hess, voxhess, x_buf, pvec_buf, W, x_curr, imu_pre_buf, extrin_para, [&](const Call &a) {
+      return vba_motion_init_resident(voxhess.ctx(), W, pl_origs.get(), a.imo, a.imu, beg_times.data(), a.ext, dept_err, beam_err, scale_gravity,
+                                      point_notime, noise_meas, noise_walk, a.st, a.cov, a.im, a.hess, a.converged, eigvalue, &iterations,
+                                      &thresholds_left_relaxed, nullptr, 0, a.po, a.vo, a.pvo, a.cap);
+    });
+    (void)surf_map;
+    pl_origs.clear(); vec_imus.clear(); beg_times.clear();         // VS:795-797
+    return converged;
+  }
+
+ private:
+  // what both overloads hand to the library besides the clouds
+  struct Call { const int *imo; const double *imu, *ext; double *st; const double *cov; double *im, *hess; int *converged; double *po, *vo; int *pvo, cap; };
+  // packs the deques, states and factors, calls `call`, and unpacks states, factors and pvec_buf; n_pts = points of the whole window
+  template <class F>
+  int run(int n_pts, std::vector<std::vector<ImuSample>> &vec_imus, std::vector<double> &beg_times, std::vector<double> *hess, LidarFactor &voxhess,
+          std::vector<IMUST> &x_buf, std::vector<std::shared_ptr<PVec>> &pvec_buf, int W, IMUST &x_curr, std::deque<IMU_PRE *> &imu_pre_buf,
+          const IMUST &extrin_para, F &&call) {
+    (void)beg_times;
+    std::vector<int> imo(W + 1, 0);
+    for (int i = 0; i < W; i++) imo[i + 1] = imo[i] + (int)vec_imus[i].size();
+    std::vector<double> imu((size_t)imo[W] * 7 + 7);
+    for (int i = 0; i < W; i++)
       for (size_t k = 0; k < vec_imus[i].size(); k++) std::memcpy(&imu[((size_t)imo[i] + k) * 7], &vec_imus[i][k], 7 * sizeof(double));
-    }
     std::vector<double> st((size_t)W * 25), cov((size_t)W * 225), im((size_t)(W - 1) * VBA_IMU_PRE_LEN);
     for (int i = 0; i < W; i++) { std::memcpy(&st[(size_t)i * 25], &x_buf[i].t, 25 * sizeof(double)); std::memcpy(&cov[(size_t)i * 225], x_buf[i].cov, 225 * sizeof(double)); }
     for (int i = 0; i < W - 1; i++) std::memcpy(&im[(size_t)i * VBA_IMU_PRE_LEN], imu_pre_buf[i]->f, sizeof(imu_pre_buf[i]->f));
@@ -320,15 +393,12 @@ class Initialization {
     std::memcpy(ext, extrin_para.R, 72); std::memcpy(ext + 9, extrin_para.p, 24);
     const int nh = 15 * W + 3;
     if (hess) hess->assign((size_t)nh * nh, 0.0);
-    const int cap = pto[W] + imo[W];
+    const int cap = n_pts + imo[W];
     std::vector<double> po((size_t)cap * 3 + 3), vo((size_t)cap * 9 + 9);
     std::vector<int> pvo(W + 1);
     int converged = 0;
-    check(voxhess.ctx(), vba_motion_init(voxhess.ctx(), W, pto.data(), pnt.data(), curv.data(), imo.data(), imu.data(), beg_times.data(), ext, dept_err,
-                                         beam_err, scale_gravity, point_notime, noise_meas, noise_walk, st.data(), cov.data(), im.data(),
-                                         hess ? hess->data() : nullptr, &converged, eigvalue, &iterations, &thresholds_left_relaxed, nullptr, 0,
-                                         po.data(), vo.data(), pvo.data(), cap));
-    (void)surf_map;   // the map (and voxhess) stay on the context, as surf_map / voxhess in the reference
+    const Call a{imo.data(), imu.data(), ext, st.data(), cov.data(), im.data(), hess ? hess->data() : nullptr, &converged, po.data(), vo.data(), pvo.data(), cap};
+    check(voxhess.ctx(), call(a));
     for (int i = 0; i < W; i++) std::memcpy(&x_buf[i].t, &st[(size_t)i * 25], 25 * sizeof(double));
     for (int i = 1; i < W; i++) {                                  // IMU_PRE(x_buf[i-1].bg, x_buf[i-1].ba) + push_imu (VS:724-730)
       IMU_PRE *f = imu_pre_buf[i - 1];
@@ -346,7 +416,6 @@ class Initialization {
       }
     }
     x_curr = x_buf[W - 1];                                         // VS:761
-    pl_origs.clear(); vec_imus.clear(); beg_times.clear();         // VS:795-797
     return converged;
   }
 };

@@ -46,6 +46,8 @@ EXPORTS = [
     "vba_loop_map_num_roots", "vba_loop_map_dump_leaves", "vba_loop_map_dump_plane_var", "vba_loop_update",
     "vba_scan_layout_livox", "vba_scan_layout_check", "vba_scan_frame_create", "vba_scan_frame_destroy", "vba_scan_frame_reserve",
     "vba_scan_frame_allocations", "vba_scan_decode", "vba_scan_prepare", "vba_scan_frame_read",
+    "vba_init_window_create", "vba_init_window_destroy", "vba_init_window_reserve", "vba_init_window_allocations", "vba_init_window_clear",
+    "vba_init_window_size", "vba_init_window_push", "vba_init_window_push_points", "vba_init_window_read", "vba_motion_init_resident",
 ]
 
 
@@ -531,6 +533,71 @@ class ScanFrame:
         return out
 
 
+class InitWindow:
+    """One vba_init_window: pl_origs of the LiDAR-inertial initialisation, resident in HBM."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx._chk(self.lib.vba_init_window_create(ctx.h, C.byref(h)))
+        self.h = h
+        ctx._kf.append(self)         # destroyed with its context, as the stores are
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.vba_init_window_destroy(self.h)
+            self.h = None
+        kf = getattr(self.ctx, "_kf", None)
+        if kf is not None and self in kf:
+            kf.remove(self)
+
+    def reserve(self, max_scans, max_points_per_scan):
+        self.ctx._chk(self.lib.vba_init_window_reserve(self.h, C.c_int(max_scans), C.c_int(max_points_per_scan)))
+
+    def allocations(self):
+        n = C.c_int(); b = C.c_int64()
+        self.ctx._chk(self.lib.vba_init_window_allocations(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def clear(self):
+        self.ctx._chk(self.lib.vba_init_window_clear(self.h))
+
+    def size(self):
+        n = C.c_int()
+        self.ctx._chk(self.lib.vba_init_window_size(self.h, C.byref(n), None))
+        return n.value
+
+    def offsets(self):
+        off = np.zeros(self.size() + 1, dtype=np.int64)
+        n = C.c_int()
+        self.ctx._chk(self.lib.vba_init_window_size(self.h, C.byref(n), off.ctypes.data_as(C.POINTER(C.c_int64))))
+        return off
+
+    def push(self, frame, down_size, min_points=1000):
+        """down_sampling_close + retry + sort of VS:1499-1511 from the frame's stage 0.  Returns (n_kept, retried)."""
+        n = C.c_int(0); r = C.c_int(0)
+        self.ctx._chk(self.lib.vba_init_window_push(self.h, frame.h, C.c_double(down_size), C.c_int(min_points), C.byref(n), C.byref(r)))
+        return n.value, r.value
+
+    def push_points(self, pnt, curv):
+        """Appends host arrays pnt [n][3], curv [n] (ascending) as they are."""
+        pnt = _c(np.reshape(pnt, (-1, 3))); curv = _c(np.ravel(curv))
+        if len(pnt) != len(curv):
+            raise ValueError("pnt and curv differ in length")
+        self.ctx._chk(self.lib.vba_init_window_push_points(self.h, C.c_int(len(curv)), _p(pnt), _p(curv)))
+
+    def read(self, scan):
+        """(pnt [n][3], curv [n]) of one scan."""
+        off = self.offsets()
+        if not 0 <= scan < len(off) - 1:
+            raise IndexError(scan)
+        n = int(off[scan + 1] - off[scan])
+        pnt = np.zeros((n, 3)); curv = np.zeros(n)
+        self.ctx._chk(self.lib.vba_init_window_read(self.h, C.c_int(scan), _p(pnt), _p(curv)))
+        return pnt, curv
+
+
 class OdomReport(C.Structure):
     """vba_odom_report (include/voxelba.h)."""
     _fields_ = [("iterations", C.c_int), ("match_num", C.c_int * 4), ("rot_add", C.c_double * 4), ("tra_add", C.c_double * 4),
@@ -887,6 +954,38 @@ class Context:
         vo = np.zeros((cap, 9)) if want_pvec else None
         self._chk(self.lib.vba_motion_init(
             self.h, C.c_int(W), pto.ctypes.data_as(ip_), _p(pnt), _p(cv), imo.ctypes.data_as(ip_), _p(imu), _p(bt), _p(ext),
+            C.c_double(dept_err), C.c_double(beam_err), C.c_double(scale_gravity), C.c_int(int(point_notime)), _p(nm), _p(nw),
+            _p(xs), _p(cov), _p(ip), _p(H), C.byref(conv), _p(eig), C.byref(iters), C.byref(relax), _p(log), C.c_int(10),
+            _p(po), _p(vo), pvo.ctypes.data_as(ip_), C.c_int(cap)))
+        out = dict(converged=conv.value, eigvalue3=eig, iterations=iters.value, thresholds_left_relaxed=relax.value,
+                   round_log=log[:iters.value].copy(), states=xs, imu_pre=ip, hess=H, pvec_offsets=pvo)
+        if want_pvec:
+            out["pvec"] = [(po[pvo[i]:pvo[i + 1]].copy(), vo[pvo[i]:pvo[i + 1]].reshape(-1, 3, 3).copy()) for i in range(W)]
+        return out
+
+    def init_window(self) -> "InitWindow":
+        return InitWindow(self)
+
+    def motion_init_resident(self, window, imus_raw, beg_times, ext_pose12, dept_err, beam_err, scale_gravity, noise_meas, noise_walk,
+                             states, covs, imu_pre, point_notime=False, want_hess=False, want_pvec=True):
+        """motion_init with pl_origs read in place from an InitWindow (which is not cleared).  Returns the dict of motion_init."""
+        W = len(imus_raw)
+        off = window.offsets()
+        imo = np.zeros(W + 1, dtype=np.int32)
+        imo[1:] = np.cumsum([len(x) for x in imus_raw])
+        imu = _c(np.concatenate([np.reshape(x, (-1, 7)) for x in imus_raw])) if imo[-1] else np.zeros((1, 7))
+        bt, ext, nm, nw = _c(beg_times), _c(ext_pose12), _c(noise_meas), _c(noise_walk)
+        xs = _c(states).copy(); cov = _c(covs); ip = _c(imu_pre).copy()
+        n = 15 * W + 3
+        H = np.zeros((n, n)) if want_hess else None
+        conv = C.c_int(0); iters = C.c_int(0); relax = C.c_int(0); eig = np.zeros(3); log = np.zeros((10, 5))
+        ip_ = C.POINTER(C.c_int)
+        pvo = np.zeros(W + 1, dtype=np.int32)
+        cap = int(off[-1] + imo[-1]) + 1 if want_pvec else 0
+        po = np.zeros((cap, 3)) if want_pvec else None
+        vo = np.zeros((cap, 9)) if want_pvec else None
+        self._chk(self.lib.vba_motion_init_resident(
+            self.h, C.c_int(W), window.h, imo.ctypes.data_as(ip_), _p(imu), _p(bt), _p(ext),
             C.c_double(dept_err), C.c_double(beam_err), C.c_double(scale_gravity), C.c_int(int(point_notime)), _p(nm), _p(nw),
             _p(xs), _p(cov), _p(ip), _p(H), C.byref(conv), _p(eig), C.byref(iters), C.byref(relax), _p(log), C.c_int(10),
             _p(po), _p(vo), pvo.ctypes.data_as(ip_), C.c_int(cap)))

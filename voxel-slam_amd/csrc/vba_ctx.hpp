@@ -241,6 +241,12 @@ __global__ void k_undistort(int n, double *__restrict__ pnt, const double *__res
 __global__ void k_var_init(int n, const double *__restrict__ pin, double *__restrict__ pout, double *__restrict__ var, const double *__restrict__ ext,
                            float range_inc, float degree_inc);
 
+// ---------------------------------------------------------------- vba_scan.hip
+// Stage 0 of a decoded frame (decoded, sorted, cut; vba_scan_prepare leaves it alone) for a reader on `stream`, which is ordered
+// behind the decode.  false: the frame holds no decoded cloud.  stream == nullptr: the fields only, nothing is queued.
+struct ScanStage0 { vba_ctx *ctx; int n; const double *pnt, *curv; };
+bool scan_frame_stage0(vba_scan_frame *f, hipStream_t stream, ScanStage0 *out);
+
 // ---------------------------------------------------------------- vba_map.hip
 void map_init(MapStore &s, const vba_options &o);
 std::vector<DevArr> node_arrays(MapView &v, int W);

@@ -2,11 +2,15 @@
 //   k_init_blur           the initialisation variant of motion blur (VS:506-601) over all W scans of the window in one launch:
 //                         backward-propagated pose table, points pushed from last to first, drops and the repeated point 0
 //   k_init_nnt_part/_fin  Σ v0 v0ᵀ over the factor store's plane normals (VS:737-741) and its eigenvalues (VS:744-745)
+//   k_initw_count/_gather the initialisation window (vba_init_window_push, VS:1499-1511): order-preserving compaction of the points
+//                         that down_sampling_close keeps, from the frame's stage 0 into the window at its append offset
+//   k_init_walk           per scan of a resident window, what the host walk of vba_motion_init reads from the curvatures
 // plus the host side of the same call: the pose-table propagation (VS:508-544) and align_gravity (VS:470-497).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vba_eig3.hpp"
 #include "vba_hostmath.hpp"
+#include "vba_types.hpp"
 
 namespace vba {
 
@@ -25,6 +29,12 @@ struct InitScan {
   double Rx[9], tx[3];     // extrin_para
   double cov6[18];         // x_buf[i].cov rot block (0,0), translation block (3,3)
 };
+
+// What the walk of motion_blur (VS:562-599) needs from one scan's curvatures: the number of leading points at or before the oldest
+// pose (the walk drops them) and the curvature of point 0 (which pose pushes it).  Host-fed clouds: read on the host; resident ones:
+// k_init_walk from InitWalkIn.
+struct InitWalk { int j_min, pad; double cv0; };
+struct InitWalkIn { long long off; int n, pad; double t_last; };   // the scan's rows in the window (n = 0: no walk), oldest pose time
 
 // ---------------------------------------------------------------- host side
 // Backward IMU propagation of motion_blur (VS:508-544) from xc = state_c (biases of state_l), m samples rows [t, gyr(3), acc(3)]:
@@ -180,6 +190,56 @@ __global__ __launch_bounds__(256) void k_init_blur(int W, int n_out, const InitS
                            ((PR[3 * rr] * ph[3 * cc] + PR[3 * rr + 1] * ph[3 * cc + 1]) + PR[3 * rr + 2] * ph[3 * cc + 2])) + cv6[9 + 3 * rr + cc];
   }
   pb[3 * (size_t)o] = x; pb[3 * (size_t)o + 1] = y; pb[3 * (size_t)o + 2] = z;
+}
+
+// ---------------------------------------------------------------- initialisation window
+// The point that down_sampling_close keeps of a voxel, from the table ds_core leaves in mode 2: `best`, or `first` when no distance
+// competed (TL:281-295; what k_ds_emit writes to first[] in mode 2).  Point i is kept iff it is that point of its own voxel, so the
+// mark is a predicate of the table and no pass writes it.
+__device__ __forceinline__ int initw_kept(const DsSlot *__restrict__ tab, const int *__restrict__ slot_of, int i) {
+  const DsSlot *s = tab + slot_of[i];
+  const int b = s->best;
+  return ((b != 0x7fffffff) ? b : s->first) == i;
+}
+// kept points per 256-point block; k_ds_scan turns blk into the exclusive scan and the total
+__global__ __launch_bounds__(256) void k_initw_count(int n, const DsSlot *__restrict__ tab, const int *__restrict__ slot_of, int *__restrict__ blk) {
+  __shared__ int wsum[4];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int f = (i < n) ? initw_kept(tab, slot_of, i) : 0;
+  const unsigned long long m = __ballot(f);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) blk[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+// Kept point i goes to row row0 + (kept points below i): ascending stage-0 index, i.e. ascending curvature with ties in message
+// order.  The row is copied as it is (xyz and curvature, bit for bit).  No atomics.
+__global__ __launch_bounds__(256) void k_initw_gather(int n, const DsSlot *__restrict__ tab, const int *__restrict__ slot_of, const int *__restrict__ blk,
+                                                      const double *__restrict__ pnt, const double *__restrict__ curv, double *__restrict__ wpnt,
+                                                      double *__restrict__ wcurv, long long row0) {
+  __shared__ int wsum[4];
+  const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int f = (i < n) ? initw_kept(tab, slot_of, i) : 0;
+  const unsigned long long m = __ballot(f);
+  if (lane == 0) wsum[w] = __popcll(m);
+  __syncthreads();
+  if (!f) return;
+  int pos = blk[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+  for (int k = 0; k < w; k++) pos += wsum[k];
+  const long long r = row0 + (long long)pos;
+  wpnt[3 * r] = pnt[3 * (size_t)i]; wpnt[3 * r + 1] = pnt[3 * (size_t)i + 1]; wpnt[3 * r + 2] = pnt[3 * (size_t)i + 2];
+  wcurv[r] = curv[i];
+}
+// One thread per scan: curvature ascends, so the points the walk drops are a prefix, found by binary search (first row with
+// curv > t_last).
+__global__ __launch_bounds__(64) void k_init_walk(int W, const InitWalkIn *__restrict__ in, const double *__restrict__ curv, InitWalk *__restrict__ out) {
+  const int i = threadIdx.x;
+  if (i >= W) return;
+  const int n = in[i].n;
+  const double *cv = curv + in[i].off, t = in[i].t_last;
+  int lo = 0, hi = n;
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (cv[mid] <= t) lo = mid + 1; else hi = mid; }
+  InitWalk o; o.j_min = lo; o.pad = 0; o.cv0 = n > 0 ? cv[0] : 0.0;
+  out[i] = o;
 }
 
 // Σ v0 v0ᵀ (VS:737-741), first level: workgroup b sums voxels b*256 + t, (b + nb)*256 + t, ... per lane, then the wave sums (DPP, fixed

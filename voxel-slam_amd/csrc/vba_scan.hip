@@ -32,6 +32,7 @@ struct vba_scan_frame {
   int n = 0, n_ds = 0;
   int scratch_for = 0;                                                                    // the point capacity that d_sort and d_ws were sized for
   hipStream_t last = nullptr;                                                             // the stream of the last call that queued work on the buffers
+  hipEvent_t ev0 = nullptr;                                                               // recorded behind the decode: readers of stage 0 on other streams wait for it
 };
 
 namespace {
@@ -120,6 +121,16 @@ bool field_ok(int off, int size, int step) { return off >= 0 && off <= step - si
 
 }  // namespace
 
+namespace vba {
+// the initialisation window (vba_init.hip) reads stage 0 in place on its own context's stream
+bool scan_frame_stage0(vba_scan_frame *f, hipStream_t stream, ScanStage0 *out) {
+  if (!f || !f->decoded) return false;
+  out->ctx = f->ctx; out->n = f->n; out->pnt = f->d_pnt0; out->curv = f->d_curv;
+  if (stream && stream != f->ctx->stream && hipStreamWaitEvent(stream, f->ev0, 0) != hipSuccess) return false;
+  return true;
+}
+}  // namespace vba
+
 extern "C" {
 
 int vba_scan_layout_livox(vba_scan_layout *l) {
@@ -157,6 +168,7 @@ int vba_scan_frame_create(vba_ctx *c, vba_scan_frame **out) {
   f->ctx = c;
   int st = frame_ensure_prm(f, 64);
   if (!st && f->h_res.ensure(16) != hipSuccess) st = VBA_ERR_HIP;
+  if (!st && hipEventCreateWithFlags(&f->ev0, hipEventDisableTiming) != hipSuccess) st = VBA_ERR_HIP;
   if (st) { vba_scan_frame_destroy(f); return st; }
   f->allocs++;
   *out = f;
@@ -168,6 +180,7 @@ void vba_scan_frame_destroy(vba_scan_frame *f) {
   hipSetDevice(f->ctx->device);
   hipStreamSynchronize(f->ctx->stream);
   if (f->last && f->last != f->ctx->stream) hipDeviceSynchronize();
+  if (f->ev0) hipEventDestroy(f->ev0);
   delete f;
 }
 
@@ -228,6 +241,7 @@ int vba_scan_decode(vba_scan_frame *f, const vba_scan_layout *l, const void *raw
                      f->d_int, f->d_res);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(f->h_res, f->d_res, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipEventRecord(f->ev0, s));
   HIPCHK(c, hipStreamSynchronize(s));
   f->n = f->h_res[0];
   float lc;

@@ -40,6 +40,12 @@
 //           input, which is what both sides of the test use for the marginalised scans.)  The record written at that point:
 //           [-3, points inserted by the build, factor count, n_kf, per keyframe {n, x0(12), xyz[n][3], diag[n][3]},
 //            k, per buf_lba2loop scan {scan index, state(25)}, win_count, per frame {state(25)}]
+//   mode 8 (the initialisation window resident in HBM, VS:1450-1534 through vba::ScanFrame::decode, vba::InitWindow::push and the
+//           InitWindow overload of motion_init): the header and the initialisation block of mode 3 with n_scans = win_size,
+//           then [down_size, min_points, point_filter_num, blind, layout (point_step, off_x, off_y, off_z, off_intensity, intensity_type,
+//           off_time, time_type, filter)], per scan [n_raw, n_words, n_imu, beg_time, x_buf state (25), cov (225)] then the raw message in
+//           n_words doubles (its bytes, padded) and imu[n_imu][7]; output: the initialisation record of mode 3, then per scan
+//           [points kept, retried], then the final map as below
 //   output: per optimised window [scan index, W x 25 states, v6[6]] ... then [-1, n_leaves] leaf dump [n][39] plane_var dump [n][86]
 #include "../../include/voxelba_adapter.hpp"
 #include <cmath>
@@ -358,6 +364,59 @@ int main(int argc, char **argv) {
       win_count = win_size;
       window_step(win_size - 1);                                 // VS:1951 with the initialised window
       k_first = win_size;
+    }
+
+    if (mode == 8) {                                             // the same window, collected on the device (VS:1458, VS:1499-1516)
+      Initialization init;
+      init.point_notime = (int)next(); init.dept_err = next(); init.beam_err = next(); init.scale_gravity = scale_gravity = next();
+      std::memcpy(init.noise_meas, noise, 48); std::memcpy(init.noise_walk, noise + 6, 48);
+      IMUST extrin_para;
+      for (int i = 0; i < 9; i++) extrin_para.R[i] = next();
+      for (int i = 0; i < 3; i++) extrin_para.p[i] = next();
+      const double down_size = next();
+      const int min_points = (int)next(), point_filter_num = (int)next();
+      const double blind = next();
+      vba_scan_layout layout;
+      layout.point_step = (int)next(); layout.off_x = (int)next(); layout.off_y = (int)next(); layout.off_z = (int)next();
+      layout.off_intensity = (int)next(); layout.intensity_type = (int)next(); layout.off_time = (int)next(); layout.time_type = (int)next();
+      layout.filter = (int)next();
+      ScanFrame frame(ctx);
+      InitWindow pl_origs(ctx);
+      std::vector<std::vector<ImuSample>> vec_imus(win_size);
+      std::vector<double> beg_times(win_size), kept;
+      for (int i = 0; i < win_size; i++) {
+        const int n_raw = (int)next();
+        const size_t n_words = (size_t)next();
+        const int n_imu = (int)next();
+        beg_times[i] = next();
+        IMUST x;
+        std::memcpy(&x.t, &in.at(q), 25 * sizeof(double)); q += 25;
+        std::memcpy(x.cov, &in.at(q), 225 * sizeof(double)); q += 225;
+        x_buf.push_back(x);
+        if (n_raw < 0 || (size_t)n_raw * (size_t)layout.point_step > n_words * 8 || q + n_words > in.size())
+          throw std::runtime_error("mode 8: the raw message does not fit its words");
+        frame.decode(n_words ? &in[q] : nullptr, n_raw, layout, point_filter_num, blind);     // pcl_handler; `orig` = its cloud (VS:1458)
+        q += n_words;
+        bool retried = false;
+        kept.push_back(pl_origs.push(frame, down_size, min_points, &retried));                // VS:1499-1512
+        kept.push_back(retried ? 1.0 : 0.0);
+        vec_imus[i].resize((size_t)n_imu);
+        for (int j = 0; j < n_imu; j++) { std::memcpy(&vec_imus[i][j], &in.at(q), 7 * sizeof(double)); q += 7; }
+      }
+      for (int i = 1; i < win_size; i++) {
+        std::vector<double> t, g, a;
+        for (const ImuSample &m : vec_imus[i]) { t.push_back(m.t); g.insert(g.end(), m.gyr, m.gyr + 3); a.insert(a.end(), m.acc, m.acc + 3); }
+        imu_pre_buf.push_back(new IMU_PRE(x_buf[i - 1].bg, x_buf[i - 1].ba));
+        imu_pre_buf.back()->push_imu((int)t.size(), t.data(), g.data(), a.data(), noise, noise + 6, scale_gravity);
+      }
+      IMUST x_curr;
+      const int ok = init.motion_init(pl_origs, vec_imus, beg_times, &hess, voxhess, x_buf, surf_map, pvec_buf, win_size, x_curr, imu_pre_buf,
+                                      extrin_para);
+      out.push_back(-2.0); out.push_back(ok); out.push_back(init.iterations); out.push_back(init.thresholds_left_relaxed);
+      out.insert(out.end(), init.eigvalue, init.eigvalue + 3);
+      for (int i = 0; i < win_size; i++) out.insert(out.end(), &x_buf[i].t, &x_buf[i].t + 25);
+      out.insert(out.end(), kept.begin(), kept.end());
+      k_first = n_scans;                                         // the steady-state continuation is mode 3's
     }
 
     for (int k = k_first; k < n_scans; k++) {
