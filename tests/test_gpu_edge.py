@@ -143,3 +143,31 @@ def test_maximum_window_size_through_the_map_path(oracle):
     assert set(g) == set(o)
     assert all(g[k][5] == o[k][5] and g[k][6] == o[k][6] and g[k][7] == o[k][7] and g[k][8] == o[k][8] for k in o)
     ctx.close()
+
+
+def test_window_sizes_outside_the_supported_range_are_statuses():
+    """One status from every entry: vba_create refuses a window outside 2..16 before it builds anything, the debug solve checks its
+    own W against the kind's range before the window dispatch."""
+    import ctypes as C
+    capi, synth, wl, ctx = _ctx()
+    for w in (1, 17):
+        opt = capi.options_from_workload(wl)
+        opt.win_size = w
+        h = C.c_void_p(0xdead)
+        assert ctx.lib.vba_create(C.byref(opt), C.byref(h)) == 3 and h.value is None      # VBA_ERR_UNSUPPORTED_WINDOW, handle null
+    for kind, w, n in (("lidar", 17, 6 * 17), ("li", 17, 15 * 17)):                       # (LI_MAX_W = 16)
+        with pytest.raises(capi.VbaError) as e:
+            ctx.debug_solve(kind, w, np.eye(n), np.zeros(n), 0.01)
+        assert e.value.status == 2                                                        # VBA_ERR_BAD_ARG
+    ctx.close()
+
+
+def test_concurrent_first_use_of_the_lm_kernels():
+    """Four threads with a context each make a fresh process's first launches of the LM kernels side by side (their first use opts
+    the kernels in to more LDS, vba_launch.hpp), as vba_hba_global's workers do; a fifth context alone gives the same bits."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "first_use_child.py")], capture_output=True, text=True, timeout=180, cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["ok"] and out["differ"] == [] and out["lm_rows"] > 0 and out["li_rows"] > 0

@@ -126,3 +126,25 @@ def test_vba_mem_is_a_shared_header_without_kernels():
     assert "vba_mem.hpp" in INCLUDE.findall(read("vba_ctx.hpp"))
     # no unit reaches it through a kernel header
     assert [h for h in kernel_headers() if "vba_mem.hpp" in reached(h)] == []
+
+
+# ---------------------------------------------------------------- launch plumbing ("Source layout": vba_launch.hpp)
+def sources():
+    return sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
+
+
+def test_window_dispatch_and_lds_opt_in_live_in_vba_launch():
+    case_macro = re.compile(r"#\s*define\s+VBA_\w+_CASE\b")
+    assert case_macro.search("#define VBA_LI_CASE(WW) case WW:") and not case_macro.search("#define VBA_K4_TV 32")
+    assert [f for f in sources() if case_macro.search(read(f))] == []
+    assert [f for f in sources() if "hipFuncSetAttribute" in read(f)] == ["vba_launch.hpp"]
+    assert [f for f in sources() if "attr_set" in read(f)] == []
+
+
+def test_vba_launch_is_a_shared_header_without_kernels():
+    assert "__global__" not in read("vba_launch.hpp")
+    assert INCLUDE.findall(read("vba_launch.hpp")) == []       # the runtime's and the standard library's headers only
+    assert "vba_launch.hpp" in INCLUDE.findall(read("vba_ctx.hpp"))
+    # the units reach it through vba_ctx.hpp and nothing else, no kernel header reaches it
+    assert [f for f in sources() if f != "vba_ctx.hpp" and "vba_launch.hpp" in INCLUDE.findall(read(f))] == []
+    assert [h for h in kernel_headers() if "vba_launch.hpp" in reached(h)] == []

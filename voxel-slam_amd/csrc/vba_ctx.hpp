@@ -5,6 +5,7 @@
 #include "vba_types.hpp"
 #include "vba_common.hpp"
 #include "vba_mem.hpp"
+#include "vba_launch.hpp"
 #include "vba_btcgen.hpp"
 
 #include <hip/hip_runtime.h>
@@ -28,8 +29,6 @@ using namespace vba;
 
 namespace vba {
 struct TimedSpan { hipEvent_t a, b; };
-
-constexpr int kMaxDevices = 64;            // per-device "kernel attribute set" flags
 
 // Diagnostic switches (in-kernel stamps, host-side phase timers, ablation forms) exist only in a -DVBA_DIAG build (make diag ->
 // libvoxelba_diag.so, tools/README.md); the shipped library reads no environment variable.  Internal linkage: the diagnostic library links

@@ -321,13 +321,10 @@ int map_cut_voxel(MapStore &s, hipStream_t st, int win_count, int n, const doubl
     int win = 128; while (win < n && win < (1 << 19)) win *= 2;         // bitmap window of the big-leaf kernel (<= 96 KB of LDS)
     size_t lds_big = (size_t)(win / 64) * 12 + 16;
     if (lds_big < (size_t)4 * 64 * 33 * 8) lds_big = (size_t)4 * 64 * 33 * 8;             // bitmap + prefix, then the four term images in the same space
-    static bool attr_set[64] = {false};
+    static LdsOptIn opt_in_var, opt_in_novar;
     int dev = 0; hipGetDevice(&dev);
-    if (!attr_set[dev & 63]) {
-      hipFuncSetAttribute((const void *)k_ins_accum_big<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-      hipFuncSetAttribute((const void *)k_ins_accum_big<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-      attr_set[dev & 63] = true;
-    }
+    MAPCHK(opt_in_var(dev, (const void *)k_ins_accum_big<true>, 160 * 1024 - 64));
+    MAPCHK(opt_in_novar(dev, (const void *)k_ins_accum_big<false>, 160 * 1024 - 64));
     if (var) {
       hipLaunchKernelGGL((k_ins_accum_ord<true>), dim3(nwg), dim3(64), 0, st, s.v, P, slot);
       hipLaunchKernelGGL((k_ins_accum_big<true>), dim3(256), dim3(256), lds_big, st, s.v, P, slot, n, win);

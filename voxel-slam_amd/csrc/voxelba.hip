@@ -159,6 +159,14 @@ int upload_poses(vba_ctx *c, const double *poses) {
   return VBA_OK;
 }
 
+// device addresses of the LmDev fields the passes take as arguments: accepted and trial poses, the gates of the two passes
+struct LmPtrs { const double *x, *xt; const int *run_hess, *run_res; };
+LmPtrs lm_ptrs(vba_ctx *c) {
+  const char *base = reinterpret_cast<const char *>(c->d_lm.p);
+  return {reinterpret_cast<const double *>(base + offsetof(LmDev, x)), reinterpret_cast<const double *>(base + offsetof(LmDev, xt)),
+          reinterpret_cast<const int *>(base + offsetof(LmDev, run_hess)), reinterpret_cast<const int *>(base + offsetof(LmDev, run_res))};
+}
+
 // The by-value init argument of the LM kernels.  take: consume the context's pending init (the launch that receives the argument
 // writes the LmDev image); otherwise the argument is off.
 template <int W>
@@ -174,15 +182,42 @@ LmInit<W> lm_init_arg(vba_ctx *c, bool take) {
 // Everything that reads d_lm and is not a fused site calls this first: a pending init becomes a launch of its own.
 int lm_init_flush(vba_ctx *c) {
   if (!c->lm_init.pending) return VBA_OK;
-  switch (c->opt.win_size) {
-#define VBA_LI_CASE(WW) case WW: hipLaunchKernelGGL(k_lm_init<WW>, dim3(1), dim3(256), 0, c->stream, lm_init_arg<WW>(c, true)); break;
-    VBA_LI_CASE(2) VBA_LI_CASE(3) VBA_LI_CASE(4) VBA_LI_CASE(5) VBA_LI_CASE(6) VBA_LI_CASE(7) VBA_LI_CASE(8) VBA_LI_CASE(9) VBA_LI_CASE(10)
-    VBA_LI_CASE(11) VBA_LI_CASE(12) VBA_LI_CASE(13) VBA_LI_CASE(14) VBA_LI_CASE(15) VBA_LI_CASE(16)
-#undef VBA_LI_CASE
-    default: return VBA_ERR_UNSUPPORTED_WINDOW;
+  return for_window<2, 16>(c->opt.win_size, [&](auto wc) {
+    constexpr int W = decltype(wc)::value;
+    hipLaunchKernelGGL(k_lm_init<W>, dim3(1), dim3(256), 0, c->stream, lm_init_arg<W>(c, true));
+    HIPCHK(c, hipGetLastError());
+    return VBA_OK;
+  });
+}
+
+// the IMU workgroup of LI-BA rides a lidar Hessian launch when its LDS fits this ceiling (150 KB hold it up to W = 16)
+constexpr size_t kLiRideLds = 150 * 1024;
+
+// diagnostic (VBA_K3_STAMPS=1): 16 in-kernel clock stamps per workgroup of the Hessian pass.  k3_stamps_buffer: the cleared device
+// buffer in front of the launch, nullptr unless asked for; k3_stamps_dump: the first nst of four workgroups, relative to the earliest.
+long long *k3_stamps_buffer(vba_ctx *c) {
+  static const bool want_stamps = diag_env("VBA_K3_STAMPS") != nullptr;     // -DVBA_DIAG builds only
+  if (!want_stamps) return nullptr;
+  static long long *d_st = nullptr;
+  if (!d_st) hipMalloc((void **)&d_st, (size_t)kMaxBlocksHess * 16 * 8);
+  hipMemsetAsync(d_st, 0, (size_t)kMaxBlocksHess * 16 * 8, c->stream);
+  return d_st;
+}
+void k3_stamps_dump(vba_ctx *c, const long long *d_st, int nb, int nst, const char *legend) {
+  if (!d_st) return;
+  std::vector<long long> h((size_t)nb * 16);
+  hipStreamSynchronize(c->stream);
+  hipMemcpy(h.data(), d_st, h.size() * 8, hipMemcpyDeviceToHost);
+  long long t0 = h[0];
+  for (int b = 0; b < nb; b++) if (h[(size_t)b * 16] && h[(size_t)b * 16] < t0) t0 = h[(size_t)b * 16];
+  for (int b : {0, 1, nb / 2, nb - 1}) {
+    fprintf(stderr, "[k3 stamps] wg %d:", b);
+    for (int i = 0; i < nst; i++) fprintf(stderr, " %lld", h[(size_t)b * 16 + i] ? h[(size_t)b * 16 + i] - t0 : -1);
+    fprintf(stderr, "\n");
   }
-  HIPCHK(c, hipGetLastError());
-  return VBA_OK;
+  long long tmax = 0;
+  for (int b = 0; b < nb; b++) if (h[(size_t)b * 16 + nst - 1] - t0 > tmax) tmax = h[(size_t)b * 16 + nst - 1] - t0;
+  fprintf(stderr, "[k3 stamps] last workgroup ends at %lld ticks (100 MHz wall clock: 1 tick = 10 ns)%s\n", tmax, legend);
 }
 
 template <int W>
@@ -193,39 +228,13 @@ int launch_hessian2_t(vba_ctx *c, const double *poses_dev, const int *gate, int 
   const int maxb = li.dev ? c->max_blocks_hess - 1 : c->max_blocks_hess;      // (the IMU workgroup of LI-BA takes a CU of its own)
   int nb = ntiles < maxb ? ntiles : maxb;
   if (nb < 1) nb = 1;
-  static bool attr_set[kMaxDevices] = {false};      // the attribute is per DEVICE (a process may hold contexts on several)
-  if (!attr_set[c->device % kMaxDevices]) {
-    // (the IMU workgroup of LI-BA needs up to 150 KB at W = 16; a lidar-only launch asks for C::LDS_BYTES)
-    const size_t li_max = 150 * 1024;
-    hipFuncSetAttribute((const void *)k_hessian2<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(C::LDS_BYTES > li_max ? C::LDS_BYTES : li_max));
-    attr_set[c->device % kMaxDevices] = true;
-  }
-  long long *stamps = nullptr;
-  static const bool want_stamps = diag_env("VBA_K3_STAMPS") != nullptr;     // -DVBA_DIAG builds only
-  if (want_stamps) {
-    static long long *d_st = nullptr;
-    if (!d_st) hipMalloc((void **)&d_st, (size_t)kMaxBlocksHess * 16 * 8);
-    hipMemsetAsync(d_st, 0, (size_t)kMaxBlocksHess * 16 * 8, c->stream);
-    stamps = d_st;
-  }
+  static LdsOptIn opt_in;      // (a lidar-only launch asks for C::LDS_BYTES, one that carries the IMU workgroup for up to kLiRideLds)
+  HIPCHK(c, opt_in(c->device, (const void *)k_hessian2<W>, C::LDS_BYTES > kLiRideLds ? C::LDS_BYTES : kLiRideLds));
+  long long *stamps = k3_stamps_buffer(c);
   const size_t lds = (li.dev && li_lds > C::LDS_BYTES) ? li_lds : C::LDS_BYTES;
   hipLaunchKernelGGL(k_hessian2<W>, dim3(nb + (li.dev ? 1 : 0)), dim3(C::NT), lds, c->stream, c->fv, poses_dev, head, end, ntiles, c->d_partial, gate, stamps, lm, k4p, k4nb,
                      nb, li, lm_init_arg<W>(c, init));
-  if (want_stamps) {
-    std::vector<long long> h((size_t)nb * 16);
-    hipStreamSynchronize(c->stream);
-    hipMemcpy(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost);
-    long long t0 = h[0];
-    for (int b = 0; b < nb; b++) if (h[(size_t)b * 16] && h[(size_t)b * 16] < t0) t0 = h[(size_t)b * 16];
-    for (int b : {0, 1, nb / 2, nb - 1}) {
-      fprintf(stderr, "[k3 stamps] wg %d:", b);
-      for (int i = 0; i < 15; i++) fprintf(stderr, " %lld", h[(size_t)b * 16 + i] ? h[(size_t)b * 16 + i] - t0 : -1);
-      fprintf(stderr, "\n");
-    }
-    long long tmax = 0;
-    for (int b = 0; b < nb; b++) if (h[(size_t)b * 16 + 14] - t0 > tmax) tmax = h[(size_t)b * 16 + 14] - t0;
-    fprintf(stderr, "[k3 stamps] last workgroup ends at %lld ticks (100 MHz wall clock: 1 tick = 10 ns)\n", tmax);
-  }
+  k3_stamps_dump(c, stamps, nb, 15, "");
   *nblocks_out = nb;
   return VBA_OK;
 }
@@ -234,37 +243,12 @@ template <int W>
 int launch_hessian3_t(vba_ctx *c, const double *poses_dev, const int *gate, int *nblocks_out, LmDev *lm, const double *k4p, int k4nb, const LiJob &li, size_t li_lds) {
   using C = HessCfg3<W>;
   const int nb = li.dev ? c->max_blocks_hess - 1 : c->max_blocks_hess;      // (the IMU workgroup of LI-BA takes a CU of its own)
-  static bool attr_set[kMaxDevices] = {false};
-  if (!attr_set[c->device % kMaxDevices]) {
-    const size_t li_max = 150 * 1024;
-    hipFuncSetAttribute((const void *)k_hessian3<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(C::LDS_BYTES > li_max ? C::LDS_BYTES : li_max));
-    attr_set[c->device % kMaxDevices] = true;
-  }
+  static LdsOptIn opt_in;
+  HIPCHK(c, opt_in(c->device, (const void *)k_hessian3<W>, C::LDS_BYTES > kLiRideLds ? C::LDS_BYTES : kLiRideLds));
   const size_t lds = (li.dev && li_lds > C::LDS_BYTES) ? li_lds : C::LDS_BYTES;
-  long long *stamps = nullptr;
-  static const bool want_stamps = diag_env("VBA_K3_STAMPS") != nullptr;     // -DVBA_DIAG builds only
-  if (want_stamps) {
-    static long long *d_st = nullptr;
-    if (!d_st) hipMalloc((void **)&d_st, (size_t)kMaxBlocksHess * 16 * 8);
-    hipMemsetAsync(d_st, 0, (size_t)kMaxBlocksHess * 16 * 8, c->stream);
-    stamps = d_st;
-  }
+  long long *stamps = k3_stamps_buffer(c);
   hipLaunchKernelGGL(k_hessian3<W>, dim3(nb + (li.dev ? 1 : 0)), dim3(C::NT), lds, c->stream, c->fv, poses_dev, c->nvox, c->d_partial, gate, lm, k4p, k4nb, nb, li, stamps);
-  if (want_stamps) {
-    std::vector<long long> h((size_t)nb * 16);
-    hipStreamSynchronize(c->stream);
-    hipMemcpy(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost);
-    long long t0 = h[0];
-    for (int b = 0; b < nb; b++) if (h[(size_t)b * 16] && h[(size_t)b * 16] < t0) t0 = h[(size_t)b * 16];
-    for (int b : {0, 1, nb / 2, nb - 1}) {
-      fprintf(stderr, "[k3 stamps] wg %d:", b);
-      for (int i = 0; i < 16; i++) fprintf(stderr, " %lld", h[(size_t)b * 16 + i] ? h[(size_t)b * 16 + i] - t0 : -1);
-      fprintf(stderr, "\n");
-    }
-    long long tmax = 0;
-    for (int b = 0; b < nb; b++) if (h[(size_t)b * 16 + 15] - t0 > tmax) tmax = h[(size_t)b * 16 + 15] - t0;
-    fprintf(stderr, "[k3 stamps] last workgroup ends at %lld ticks (100 MHz wall clock: 1 tick = 10 ns); per workgroup: start, prologue, then per tile [A, B, combine, E]\n", tmax);
-  }
+  k3_stamps_dump(c, stamps, nb, 16, "; per workgroup: start, prologue, then per tile [A, B, combine, E]");
   *nblocks_out = nb;
   return VBA_OK;
 }
@@ -276,19 +260,9 @@ int launch_hessian(vba_ctx *c, const double *pd, const int *gate, int head, int 
   // whole store, W <= 10: the occupancy-compact pass (vba_kernels_h3.hpp); sub-ranges and wider windows: the dense-tile pass
   if (head == 0 && end == c->nvox && c->opt.win_size <= 10 && c->use_h3) {
     if (init) { const int st = lm_init_flush(c); if (st) return st; }
-    switch (c->opt.win_size) {
-#define VBA_H3_CASE(WW) case WW: return launch_hessian3_t<WW>(c, pd, gate, nb, lm, k4p, k4nb, li, li_lds);
-      VBA_H3_CASE(2) VBA_H3_CASE(3) VBA_H3_CASE(4) VBA_H3_CASE(5) VBA_H3_CASE(6) VBA_H3_CASE(7) VBA_H3_CASE(8) VBA_H3_CASE(9) VBA_H3_CASE(10)
-#undef VBA_H3_CASE
-    }
+    return for_window<2, 10>(c->opt.win_size, [&](auto wc) { return launch_hessian3_t<decltype(wc)::value>(c, pd, gate, nb, lm, k4p, k4nb, li, li_lds); });
   }
-  switch (c->opt.win_size) {
-#define VBA_H_CASE(WW) case WW: return launch_hessian2_t<WW>(c, pd, gate, head, end, nb, lm, k4p, k4nb, li, li_lds, init);
-    VBA_H_CASE(2) VBA_H_CASE(3) VBA_H_CASE(4) VBA_H_CASE(5) VBA_H_CASE(6) VBA_H_CASE(7) VBA_H_CASE(8) VBA_H_CASE(9) VBA_H_CASE(10)
-    VBA_H_CASE(11) VBA_H_CASE(12) VBA_H_CASE(13) VBA_H_CASE(14) VBA_H_CASE(15) VBA_H_CASE(16)
-#undef VBA_H_CASE
-    default: return VBA_ERR_UNSUPPORTED_WINDOW;
-  }
+  return for_window<2, 16>(c->opt.win_size, [&](auto wc) { return launch_hessian2_t<decltype(wc)::value>(c, pd, gate, head, end, nb, lm, k4p, k4nb, li, li_lds, init); });
 }
 
 #ifndef VBA_K4_TV
@@ -314,8 +288,7 @@ void k4_stamps_dump(vba_ctx *c, int nb, long long *d_st) {
   fprintf(stderr, "[k4 stamps] %d workgroups: loads+transforms %.0f, frame sum + eigen %.0f, stores+reduce %.0f cycles (mean per workgroup); last one ends at %.0f cycles\n", n, a / n, e / n, w / n, last);
 }
 
-// residual pass over voxels [head, end) (end > head); partials (one per workgroup) go to dst or d_partial; returns their number
-// (negative: the stand-alone init of a diagnostic run failed, the context holds the error)
+// residual pass over voxels [head, end) (end > head); its residual_nb partials (one per workgroup) go to dst or d_partial
 int launch_residual(vba_ctx *c, const double *pd, const int *gate, int head, int end, double *dst = nullptr, bool init = false) {
   double *part = dst ? dst : c->d_partial;
   const int nb = residual_nb(c, end - head);
@@ -326,31 +299,25 @@ int launch_residual(vba_ctx *c, const double *pd, const int *gate, int head, int
     hipMemsetAsync(d_st, 0, 2048 * 4 * 8, c->stream);
   }
   if (want_stamps && init) {                // (the diagnostic STAMPS instances carry no init: it becomes a launch of its own)
-    if (lm_init_flush(c)) return -1;
+    const int st = lm_init_flush(c);
+    if (st) return st;
     init = false;
   }
-  if (residual_vpl(c, end - head)) {
-#define VBA_RESV_CASE(WW) case WW: \
-    if (want_stamps) hipLaunchKernelGGL((k_residual_v<WW, true>), dim3(nb), dim3(64), 0, c->stream, c->fv, pd, head, end, part, gate, d_st, lm_init_arg<WW>(c, false)); \
-    else if (init && c->lm_init.pending) hipLaunchKernelGGL((k_residual_v<WW, false, true>), dim3(nb), dim3(64), 0, c->stream, c->fv, pd, head, end, part, gate, (long long *)nullptr, lm_init_arg<WW>(c, true)); \
-    else hipLaunchKernelGGL((k_residual_v<WW, false>), dim3(nb), dim3(64), 0, c->stream, c->fv, pd, head, end, part, gate, (long long *)nullptr, lm_init_arg<WW>(c, false)); break;
-    switch (c->opt.win_size) {
-      VBA_RESV_CASE(2) VBA_RESV_CASE(3) VBA_RESV_CASE(4) VBA_RESV_CASE(5) VBA_RESV_CASE(6) VBA_RESV_CASE(7) VBA_RESV_CASE(8) VBA_RESV_CASE(9) VBA_RESV_CASE(10)
-      VBA_RESV_CASE(11) VBA_RESV_CASE(12) VBA_RESV_CASE(13) VBA_RESV_CASE(14) VBA_RESV_CASE(15) VBA_RESV_CASE(16)
-    }
-#undef VBA_RESV_CASE
-  } else {
-#define VBA_RES_CASE(WW) case WW: { using RC = ResCfg<WW, VBA_K4_TV>; \
-    if (want_stamps) hipLaunchKernelGGL((k_residual_s<WW, VBA_K4_TV, true>), dim3(nb), dim3(RC::NT), 0, c->stream, c->fv, pd, head, end, part, gate, d_st, lm_init_arg<WW>(c, init)); \
-    else hipLaunchKernelGGL((k_residual_s<WW, VBA_K4_TV, false>), dim3(nb), dim3(RC::NT), 0, c->stream, c->fv, pd, head, end, part, gate, (long long *)nullptr, lm_init_arg<WW>(c, init)); break; }
-    switch (c->opt.win_size) {
-      VBA_RES_CASE(2) VBA_RES_CASE(3) VBA_RES_CASE(4) VBA_RES_CASE(5) VBA_RES_CASE(6) VBA_RES_CASE(7) VBA_RES_CASE(8) VBA_RES_CASE(9) VBA_RES_CASE(10)
-      VBA_RES_CASE(11) VBA_RES_CASE(12) VBA_RES_CASE(13) VBA_RES_CASE(14) VBA_RES_CASE(15) VBA_RES_CASE(16)
-    }
-#undef VBA_RES_CASE
-  }
-  if (want_stamps) k4_stamps_dump(c, nb, d_st);
-  return nb;
+  const int st = residual_vpl(c, end - head) ? for_window<2, 16>(c->opt.win_size, [&](auto wc) {
+    constexpr int W = decltype(wc)::value;
+    if (want_stamps) hipLaunchKernelGGL((k_residual_v<W, true>), dim3(nb), dim3(64), 0, c->stream, c->fv, pd, head, end, part, gate, d_st, lm_init_arg<W>(c, false));
+    else if (init && c->lm_init.pending) hipLaunchKernelGGL((k_residual_v<W, false, true>), dim3(nb), dim3(64), 0, c->stream, c->fv, pd, head, end, part, gate, (long long *)nullptr, lm_init_arg<W>(c, true));
+    else hipLaunchKernelGGL((k_residual_v<W, false>), dim3(nb), dim3(64), 0, c->stream, c->fv, pd, head, end, part, gate, (long long *)nullptr, lm_init_arg<W>(c, false));
+    return VBA_OK;
+  }) : for_window<2, 16>(c->opt.win_size, [&](auto wc) {
+    constexpr int W = decltype(wc)::value;
+    using RC = ResCfg<W, VBA_K4_TV>;
+    if (want_stamps) hipLaunchKernelGGL((k_residual_s<W, VBA_K4_TV, true>), dim3(nb), dim3(RC::NT), 0, c->stream, c->fv, pd, head, end, part, gate, d_st, lm_init_arg<W>(c, init));
+    else hipLaunchKernelGGL((k_residual_s<W, VBA_K4_TV, false>), dim3(nb), dim3(RC::NT), 0, c->stream, c->fv, pd, head, end, part, gate, (long long *)nullptr, lm_init_arg<W>(c, init));
+    return VBA_OK;
+  });
+  if (st == VBA_OK && want_stamps) k4_stamps_dump(c, nb, d_st);
+  return st;
 }
 
 // SUM all-reduce of n doubles in HBM across the ranks, ordered on the context's stream: RCCL when the context holds a
@@ -421,7 +388,8 @@ int residual_pass(vba_ctx *c, const double *poses_dev, const int *gate, int head
     if ((size_t)nb > c->d_partial.n) { c->set_error("partial buffer too small"); return VBA_ERR_CAPACITY; }
     TimedSpan s1{}, s2{};
     span_begin(c, "residual", s1);
-    launch_residual(c, poses_dev, gate, head, end);
+    const int st = launch_residual(c, poses_dev, gate, head, end);
+    if (st) return st;
     span_end(c, "residual", s1);
     span_begin(c, "reduce", s2);
     hipLaunchKernelGGL(k_sum_scalar, dim3(1), dim3(256), 0, c->stream, c->d_partial, nb, d_scalar_out, gate);
@@ -437,15 +405,11 @@ int residual_pass(vba_ctx *c, const double *poses_dev, const int *gate, int head
 
 // tile layout -> full layout [H | g | r] in d_full (host consumers only; the device LM reads the tile layout directly)
 int tiles_to_full(vba_ctx *c, const double *src) {
-#define VBA_TF_CASE(WW) case WW: hipLaunchKernelGGL(k_tiles_to_full<WW>, dim3(16), dim3(256), 0, c->stream, src, c->d_full); break;
-  switch (c->opt.win_size) {
-    VBA_TF_CASE(2) VBA_TF_CASE(3) VBA_TF_CASE(4) VBA_TF_CASE(5) VBA_TF_CASE(6) VBA_TF_CASE(7) VBA_TF_CASE(8) VBA_TF_CASE(9) VBA_TF_CASE(10)
-    VBA_TF_CASE(11) VBA_TF_CASE(12) VBA_TF_CASE(13) VBA_TF_CASE(14) VBA_TF_CASE(15) VBA_TF_CASE(16)
-    default: return VBA_ERR_UNSUPPORTED_WINDOW;
-  }
-#undef VBA_TF_CASE
-  HIPCHK(c, hipGetLastError());
-  return VBA_OK;
+  return for_window<2, 16>(c->opt.win_size, [&](auto wc) {
+    hipLaunchKernelGGL(k_tiles_to_full<decltype(wc)::value>, dim3(16), dim3(256), 0, c->stream, src, c->d_full);
+    HIPCHK(c, hipGetLastError());
+    return VBA_OK;
+  });
 }
 
 // device: d_full = [H | g | r] over voxels [head,end) for host poses (+ all-reduce across ranks when configured)
@@ -702,7 +666,6 @@ int vba_lm_begin(vba_ctx *c, const double *poses, int thd_num) {
 // damping_iter (VM:1628); a caller that restarts the optimiser on an unchanged factor store uses this instead.
 int vba_lm_refresh_eigen(vba_ctx *c) {
   if (!c->lm.active) return VBA_ERR_BAD_ARG;
-  const double *x_dev = reinterpret_cast<const double *>(reinterpret_cast<char *>(c->d_lm.p) + offsetof(LmDev, x));
   if (c->nvox <= 0) return VBA_OK;
   // only the pass' side effect is wanted (eig_values / eig_vectors / pcr_adds at the begin poses): its partials are not summed
   if ((size_t)residual_nb(c, c->nvox) > c->d_partial.n) { c->set_error("partial buffer too small"); return VBA_ERR_CAPACITY; }
@@ -711,7 +674,8 @@ int vba_lm_refresh_eigen(vba_ctx *c) {
   // single-rank: the pass carries the call's init when it is the first LM kernel; the multi-rank flow takes the stand-alone init
   const bool fuse_init = !c->collective();
   if (!fuse_init) { const int st = lm_init_flush(c); if (st) return st; }
-  if (launch_residual(c, x_dev, nullptr, 0, c->nvox, nullptr, fuse_init) < 0) return VBA_ERR_HIP;
+  const int st = launch_residual(c, lm_ptrs(c).x, nullptr, 0, c->nvox, nullptr, fuse_init);
+  if (st) return st;
   span_end(c, "residual", s1);
   HIPCHK(c, hipGetLastError());
   return VBA_OK;
@@ -719,11 +683,10 @@ int vba_lm_refresh_eigen(vba_ctx *c) {
 
 int vba_timing_launch_hessian(vba_ctx *c) {
   if (!c->lm.active || c->nvox <= 0) return VBA_ERR_BAD_ARG;
-  const double *x_dev = reinterpret_cast<const double *>(reinterpret_cast<char *>(c->d_lm.p) + offsetof(LmDev, x));
   int nb = 0;
   int st = lm_init_flush(c);
   if (st) return st;
-  st = launch_hessian(c, x_dev, nullptr, 0, c->nvox, &nb);
+  st = launch_hessian(c, lm_ptrs(c).x, nullptr, 0, c->nvox, &nb);
   if (st) return st;
   HIPCHK(c, hipGetLastError());
   return VBA_OK;
@@ -734,11 +697,7 @@ int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
   if (!c->lm.active) return VBA_ERR_BAD_ARG;
   const int W = c->opt.win_size, nout = nout_of(W), V = c->nvox;
   if (c->nvox_global < c->lm.thd_num) { c->lm_init.pending = false; return VBA_ERR_TOO_FEW_VOXELS; }   // VM:399-403 (and g_size checks of VM:367); the same on every rank
-  char *base = reinterpret_cast<char *>(c->d_lm.p);
-  const double *x_dev = reinterpret_cast<const double *>(base + offsetof(LmDev, x));
-  const double *xt_dev = reinterpret_cast<const double *>(base + offsetof(LmDev, xt));
-  const int *run_hess = reinterpret_cast<const int *>(base + offsetof(LmDev, run_hess));
-  const int *run_res = reinterpret_cast<const int *>(base + offsetof(LmDev, run_res));
+  const LmPtrs p = lm_ptrs(c);
   // Multi-rank: ONE collective per iteration.  After the residual pass at the trial poses the Hessian pass is run there
   // too (speculating that the step is accepted) and [H | g | r] is all-reduced once: its r (the sum of the eigenvalues the
   // residual pass just stored) is the trial residual the accept test needs, and on acceptance H is already the next
@@ -749,30 +708,26 @@ int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
   if (copy_raw) { st = lm_init_flush(c); if (st) return st; }               // the multi-rank flow takes the stand-alone init
   if (!(copy_raw && c->lm.have_hess)) {
     if (c->lm.pending_update) {               // the previous iteration's accept/reject rides in this pass (runs on xt after an accepted step)
-      st = hessian_pass(c, x_dev, run_hess, 0, V, c->d_lm, c->d_k4part, c->lm.k4_nb);
+      st = hessian_pass(c, p.x, p.run_hess, 0, V, c->d_lm, c->d_k4part, c->lm.k4_nb);
       c->lm.pending_update = false;
     } else {
-      st = hessian_pass(c, x_dev, run_hess, 0, V, nullptr, nullptr, 0, LiJob{}, 0, true);   // divide_thread  VM:445 (skipped on device after a reject); the first pass of a call carries its init
+      st = hessian_pass(c, p.x, p.run_hess, 0, V, nullptr, nullptr, 0, LiJob{}, 0, true);   // divide_thread  VM:445 (skipped on device after a reject); the first pass of a call carries its init
     }
   }
   if (st) return st;
   TimedSpan sp{};
   span_begin(c, "solve", sp);
-  switch (W) {
-#define VBA_SM_CASE(WW) case WW: \
-    if (copy_raw) hipLaunchKernelGGL((k_lm_solve_m<WW, true>), dim3(c->lm_spec), dim3(256), 0, c->stream, c->d_lm, c->d_out, c->d_raw, nullptr); \
-    else hipLaunchKernelGGL((k_lm_solve_m<WW, false>), dim3(c->lm_spec), dim3(256), 0, c->stream, c->d_lm, c->d_out, c->d_raw, nullptr); \
-    break;
-    VBA_SM_CASE(2) VBA_SM_CASE(3) VBA_SM_CASE(4) VBA_SM_CASE(5) VBA_SM_CASE(6) VBA_SM_CASE(7) VBA_SM_CASE(8) VBA_SM_CASE(9) VBA_SM_CASE(10)
-    VBA_SM_CASE(11) VBA_SM_CASE(12) VBA_SM_CASE(13) VBA_SM_CASE(14) VBA_SM_CASE(15) VBA_SM_CASE(16)
-#undef VBA_SM_CASE
-    default: return VBA_ERR_UNSUPPORTED_WINDOW;
-  }
+  st = for_window<2, 16>(W, [&](auto wc) {
+    constexpr int WW = decltype(wc)::value;
+    if (copy_raw) hipLaunchKernelGGL((k_lm_solve_m<WW, true>), dim3(c->lm_spec), dim3(256), 0, c->stream, c->d_lm, c->d_out, c->d_raw, nullptr);
+    else hipLaunchKernelGGL((k_lm_solve_m<WW, false>), dim3(c->lm_spec), dim3(256), 0, c->stream, c->d_lm, c->d_out, c->d_raw, nullptr);
+    return VBA_OK;
+  });
+  if (st) return st;
   span_end(c, "solve", sp);
-  double *d_r = c->d_scal;
   if (copy_raw) {
-    if (V > 0) launch_residual(c, xt_dev, run_res, 0, V);   // only_residual VM:467: refreshes the eigen state at the trial poses
-    st = hessian_pass(c, xt_dev, run_res, 0, V);                      // speculative divide_thread there + the one all-reduce
+    if (V > 0) st = launch_residual(c, p.xt, p.run_res, 0, V);   // only_residual VM:467: refreshes the eigen state at the trial poses
+    if (!st) st = hessian_pass(c, p.xt, p.run_res, 0, V);             // speculative divide_thread there + the one all-reduce
     if (st) return st;
     c->lm.have_hess = true;
     hipLaunchKernelGGL(k_lm_update, dim3(1), dim3(64), 0, c->stream, c->d_lm, c->d_out + (nout_tl(W) - 1), 0, W);
@@ -785,7 +740,8 @@ int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
     const bool fuse = !no_fuse && !(accepted || stop);
     TimedSpan s1{};
     span_begin(c, "residual", s1);
-    launch_residual(c, xt_dev, run_res, 0, V, c->d_k4part);
+    st = launch_residual(c, p.xt, p.run_res, 0, V, c->d_k4part);
+    if (st) return st;
     span_end(c, "residual", s1);
     if (fuse) { c->lm.pending_update = true; c->lm.k4_nb = nb; }
     else hipLaunchKernelGGL(k_lm_update, dim3(1), dim3(64), 0, c->stream, c->d_lm, c->d_k4part, nb, W);   // sums the partials itself
@@ -824,13 +780,11 @@ int vba_lm_end(vba_ctx *c, double *poses, double *hess, double *resis2) {
   }
   const double *src = c->collective() ? c->d_raw : c->d_out;      // *hess = Hess before gauge fixing (VM:446)
   const int upd = c->lm.pending_update ? 1 : 0;
-  switch (W) {
-#define VBA_FIN_CASE(WW) case WW: hipLaunchKernelGGL(k_lm_finish<WW>, dim3(hess ? 17 : 1), dim3(256), 0, c->stream, c->d_lm, c->d_k4part, upd ? c->lm.k4_nb : 0, upd, c->h_lm, src, h_hess); break;
-    VBA_FIN_CASE(2) VBA_FIN_CASE(3) VBA_FIN_CASE(4) VBA_FIN_CASE(5) VBA_FIN_CASE(6) VBA_FIN_CASE(7) VBA_FIN_CASE(8) VBA_FIN_CASE(9) VBA_FIN_CASE(10)
-    VBA_FIN_CASE(11) VBA_FIN_CASE(12) VBA_FIN_CASE(13) VBA_FIN_CASE(14) VBA_FIN_CASE(15) VBA_FIN_CASE(16)
-#undef VBA_FIN_CASE
-    default: return VBA_ERR_UNSUPPORTED_WINDOW;
-  }
+  st = for_window<2, 16>(W, [&](auto wc) {
+    hipLaunchKernelGGL(k_lm_finish<decltype(wc)::value>, dim3(hess ? 17 : 1), dim3(256), 0, c->stream, c->d_lm, c->d_k4part, upd ? c->lm.k4_nb : 0, upd, c->h_lm, src, h_hess);
+    return VBA_OK;
+  });
+  if (st) return st;
   c->lm.pending_update = false;
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -883,8 +837,8 @@ template <int W, int NT = (W > 10 ? 1024 : 512)>
 static int launch_li_solve(vba_ctx *c, int copy_raw, int n, int gauge, int grav) {
   constexpr bool GL = LiSolveCfg<W>::GL;
   constexpr size_t l_doubles = LiSolveCfg<W>::l_doubles, lds = LiSolveCfg<W>::lds;
-  static bool attr_set[kMaxDevices] = {false};
-  if (!attr_set[c->device % kMaxDevices]) { hipFuncSetAttribute((const void *)k_li_solve<W, NT, GL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set[c->device % kMaxDevices] = true; }
+  static LdsOptIn opt_in;
+  HIPCHK(c, opt_in(c->device, (const void *)k_li_solve<W, NT, GL>, lds));
   if (GL && c->d_liscr.n < l_doubles * LM_SPEC) {           // one region per damping candidate; W is fixed per context, so this runs once
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, c->d_liscr.ensure(l_doubles * LM_SPEC));
@@ -898,6 +852,8 @@ bool li_device_supported(int W) { return W >= 2 && W <= LI_MAX_W; }
 }
 }  // extern "C++"
 
+// dynamic LDS of li_imu_body (joc, cov^-1 joc, rr, cov^-1 rr, the per-factor scalars)
+static size_t li_imu_lds(int F, int nb) { return ((size_t)2 * F * 15 * nb + 2 * F * 15 + F + 16) * sizeof(double); }
 // Set-up shared by li_ba_device and vba_debug_li_imu: device buffers, the LM state (poses view of `states`, flushed), LiDev `h`, the
 // factor image `fimg` (= imus with cov^-1 in place of cov) uploaded, himu / gimu cleared, the LDS ceiling of k_li_imu.
 static int li_setup(vba_ctx *c, const double *states, const double *imus, int gravity, LiDev &h, std::vector<double> &fimg) {
@@ -948,17 +904,12 @@ static int li_setup(vba_ctx *c, const double *states, const double *imus, int gr
   }
   HIPCHK(c, hipMemsetAsync(c->d_himu, 0, (size_t)li_hb_size(W, 1) * sizeof(double), c->stream));
   HIPCHK(c, hipMemsetAsync(c->d_gimu, 0, (size_t)n * sizeof(double), c->stream));
-  {
-    static bool attr_set[kMaxDevices] = {false};      // W = 10 with gravity: 88 KB
-    constexpr int FM = LI_MAX_W - 1;
-    if (!attr_set[c->device % kMaxDevices]) { hipFuncSetAttribute((const void *)k_li_imu, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)2 * FM * 15 * 33 + 2 * FM * 15 + FM + 16) * sizeof(double))); attr_set[c->device % kMaxDevices] = true; }
-  }
+  static LdsOptIn opt_in;      // W = 10 with gravity: 88 KB
+  HIPCHK(c, opt_in(c->device, (const void *)k_li_imu, li_imu_lds(LI_MAX_W - 1, 33)));
   return VBA_OK;
 }
-// dynamic LDS of li_imu_body (joc, cov^-1 joc, rr, cov^-1 rr, the per-factor scalars)
-static size_t li_imu_lds(int F, int nb) { return ((size_t)2 * F * 15 * nb + 2 * F * 15 + F + 16) * sizeof(double); }
 // the IMU pass rides the lidar Hessian launch when there is one on this rank and its LDS fits beside it
-static bool li_imu_rides(const vba_ctx *c, int copy_raw, int V, size_t lds_imu) { return !(copy_raw && c->lm.have_hess) && V > 0 && lds_imu <= 150 * 1024; }
+static bool li_imu_rides(const vba_ctx *c, int copy_raw, int V, size_t lds_imu) { return !(copy_raw && c->lm.have_hess) && V > 0 && lds_imu <= kLiRideLds; }
 
 static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, int max_iter, double *hess, double *resis2) {
   static const bool want_times = diag_env("VBA_LI_TIMES") != nullptr;   // diagnostic: host-side phases of one call
@@ -971,11 +922,7 @@ static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, i
   std::vector<double> fimg;
   int st = li_setup(c, states, imus, gravity, h, fimg);
   if (st) return st;
-  char *base = reinterpret_cast<char *>(c->d_lm.p);
-  const double *x_dev = reinterpret_cast<const double *>(base + offsetof(LmDev, x));
-  const double *xt_dev = reinterpret_cast<const double *>(base + offsetof(LmDev, xt));
-  const int *run_hess = reinterpret_cast<const int *>(base + offsetof(LmDev, run_hess));
-  const int *run_res = reinterpret_cast<const int *>(base + offsetof(LmDev, run_res));
+  const LmPtrs p = lm_ptrs(c);
   const int copy_raw = c->collective() ? 1 : 0;
   const size_t lds_imu = li_imu_lds(F, nb);
   const double t_up = since(t_0);
@@ -986,53 +933,41 @@ static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, i
     const bool lidar_now = li_imu_rides(c, copy_raw, V, lds_imu);
     if (lidar_now) {          // the IMU workgroup rides in the lidar Hessian launch
       const LiJob job{c->d_lm, c->d_li, c->d_imu, c->d_himu, c->d_gimu};
-      st = hessian_pass(c, x_dev, run_hess, 0, V, nullptr, nullptr, 0, job, lds_imu);   // lidar part of divide_thread (+ all-reduce)
+      st = hessian_pass(c, p.x, p.run_hess, 0, V, nullptr, nullptr, 0, job, lds_imu);   // lidar part of divide_thread (+ all-reduce)
     } else {
       hipLaunchKernelGGL(k_li_imu, dim3(1), dim3(LI_IMU_NT), lds_imu, c->stream, c->d_lm, c->d_li, c->d_imu, c->d_himu, c->d_gimu);
-      if (!(copy_raw && c->lm.have_hess)) st = hessian_pass(c, x_dev, run_hess, 0, V);
+      if (!(copy_raw && c->lm.have_hess)) st = hessian_pass(c, p.x, p.run_hess, 0, V);
     }
-    if (st) { c->lm.active = false; return st; }
+    if (st) return st;
     TimedSpan s1{};
     span_begin(c, "solve", s1);
-    switch (W) {
-      case 2: st = launch_li_solve<2>(c, copy_raw, n, h.gauge, h.gravity); break;
-      case 3: st = launch_li_solve<3>(c, copy_raw, n, h.gauge, h.gravity); break;
-      case 4: st = launch_li_solve<4>(c, copy_raw, n, h.gauge, h.gravity); break;
-      case 5: st = launch_li_solve<5>(c, copy_raw, n, h.gauge, h.gravity); break;
-      case 6: st = launch_li_solve<6>(c, copy_raw, n, h.gauge, h.gravity); break;
-      case 7: st = launch_li_solve<7>(c, copy_raw, n, h.gauge, h.gravity); break;
-      case 9: st = launch_li_solve<9>(c, copy_raw, n, h.gauge, h.gravity); break;
-      case 8: st = launch_li_solve<8>(c, copy_raw, n, h.gauge, h.gravity); break;
-      case 10: {
+    st = for_window<2, 16>(W, [&](auto wc) {
+      constexpr int WW = decltype(wc)::value;
+      if constexpr (WW == 10) {
         static const int nt = diag_env("VBA_LI_NT") ? atoi(diag_env("VBA_LI_NT")) : 512;      // -DVBA_DIAG builds only
-        if (nt == 256) st = launch_li_solve<10, 256>(c, copy_raw, n, h.gauge, h.gravity); else if (nt == 1024) st = launch_li_solve<10, 1024>(c, copy_raw, n, h.gauge, h.gravity); else st = launch_li_solve<10, 512>(c, copy_raw, n, h.gauge, h.gravity);
-        break;
+        if (nt == 256) return launch_li_solve<10, 256>(c, copy_raw, n, h.gauge, h.gravity);
+        if (nt == 1024) return launch_li_solve<10, 1024>(c, copy_raw, n, h.gauge, h.gravity);
       }
-      case 11: st = launch_li_solve<11>(c, copy_raw, n, h.gauge, h.gravity); break;
-      case 12: st = launch_li_solve<12>(c, copy_raw, n, h.gauge, h.gravity); break;
-      case 13: st = launch_li_solve<13>(c, copy_raw, n, h.gauge, h.gravity); break;
-      case 14: st = launch_li_solve<14>(c, copy_raw, n, h.gauge, h.gravity); break;
-      case 15: st = launch_li_solve<15>(c, copy_raw, n, h.gauge, h.gravity); break;
-      case 16: st = launch_li_solve<16>(c, copy_raw, n, h.gauge, h.gravity); break;
-      default: c->lm.active = false; return VBA_ERR_UNSUPPORTED_WINDOW;
-    }
+      return launch_li_solve<WW>(c, copy_raw, n, h.gauge, h.gravity);
+    });
     span_end(c, "solve", s1);
-    if (st) { c->lm.active = false; return st; }                     // (scratch allocation of the W > 10 solve failed: nothing was launched)
+    if (st) return st;                                                // (the opt-in or the scratch allocation of the W > 10 solve failed: nothing was launched)
     if (copy_raw) {                                                   // one collective per iteration (see vba_lm_iterate)
-      if (V > 0) launch_residual(c, xt_dev, run_res, 0, V);
-      st = hessian_pass(c, xt_dev, run_res, 0, V);
-      if (st) { c->lm.active = false; return st; }
+      if (V > 0) st = launch_residual(c, p.xt, p.run_res, 0, V);
+      if (!st) st = hessian_pass(c, p.xt, p.run_res, 0, V);
+      if (st) return st;
       c->lm.have_hess = true;
       hipLaunchKernelGGL(k_li_update, dim3(1), dim3(LI_UPD_NT), 0, c->stream, c->d_lm, c->d_li, c->d_imu, c->d_out + (nout_tl(W) - 1), 0);
     } else if (V == 0) {
-      st = residual_pass(c, xt_dev, run_res, 0, V, c->d_scal);
-      if (st) { c->lm.active = false; return st; }
+      st = residual_pass(c, p.xt, p.run_res, 0, V, c->d_scal);
+      if (st) return st;
       hipLaunchKernelGGL(k_li_update, dim3(1), dim3(LI_UPD_NT), 0, c->stream, c->d_lm, c->d_li, c->d_imu, c->d_scal, 0);
     } else {
       const int nbk = residual_nb(c, V);
       TimedSpan s2{};
       span_begin(c, "residual", s2);
-      launch_residual(c, xt_dev, run_res, 0, V);
+      st = launch_residual(c, p.xt, p.run_res, 0, V);
+      if (st) return st;
       span_end(c, "residual", s2);
       hipLaunchKernelGGL(k_li_update, dim3(1), dim3(LI_UPD_NT), 0, c->stream, c->d_lm, c->d_li, c->d_imu, c->d_partial, nbk);
     }
@@ -1114,7 +1049,9 @@ static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, i
 int vba_li_ba_damping_iter(vba_ctx *c, double *states, double *imus, int gravity, int max_iter, double *hess, double *resis2) {
   // the whole optimiser runs on the device (k_li_imu / k_li_solve / k_li_update) for every window the context accepts (2..16)
   if (!li_device_supported(c->opt.win_size)) return VBA_ERR_UNSUPPORTED_WINDOW;
-  return li_ba_device(c, states, imus, gravity, max_iter, hess, resis2);
+  const int st = li_ba_device(c, states, imus, gravity, max_iter, hess, resis2);
+  if (st) c->lm.active = false;                 // (li_setup began an LM call; a success has ended it)
+  return st;
 }
 
 // ---------------------------------------------------------------- diagnostic: the IMU factor pass through the production kernels
@@ -1125,13 +1062,11 @@ static int debug_li_imu_run(vba_ctx *c, int gravity, int flags, const double *st
   std::vector<double> fimg;
   int st = li_setup(c, states, imus, gravity, h, fimg);
   if (st) return st;
-  char *base = reinterpret_cast<char *>(c->d_lm.p);
-  const double *x_dev = reinterpret_cast<const double *>(base + offsetof(LmDev, x));
-  const int *run_hess = reinterpret_cast<const int *>(base + offsetof(LmDev, run_hess));
+  const LmPtrs p = lm_ptrs(c);
   const size_t lds_imu = li_imu_lds(F, nb);
   if (flags & (VBA_IMU_RIDE_H2 | VBA_IMU_RIDE_H3)) {
     const LiJob job{c->d_lm, c->d_li, c->d_imu, c->d_himu, c->d_gimu};
-    st = hessian_pass(c, x_dev, run_hess, 0, V, nullptr, nullptr, 0, job, lds_imu);
+    st = hessian_pass(c, p.x, p.run_hess, 0, V, nullptr, nullptr, 0, job, lds_imu);
     if (st) return st;
   } else {
     hipLaunchKernelGGL(k_li_imu, dim3(1), dim3(LI_IMU_NT), lds_imu, c->stream, c->d_lm, c->d_li, c->d_imu, c->d_himu, c->d_gimu);
@@ -1451,11 +1386,13 @@ int dbg_li(vba_ctx *c, DbgBufs &B, const double *H, const double *g, int flags, 
   HIPCHK(c, hipMemcpyAsync(s, &h, sizeof(LmDev), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_li, &li, sizeof(LiDev), hipMemcpyHostToDevice, c->stream));
   if (flags & VBA_SOLVE_DENSE_MASK) {
-    HIPCHK(c, hipFuncSetAttribute((const void *)k_li_solve<W, NT, LC::GL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LC::lds));
+    static LdsOptIn opt_in;
+    HIPCHK(c, opt_in(c->device, (const void *)k_li_solve<W, NT, LC::GL, true>, LC::lds));
     hipLaunchKernelGGL((k_li_solve<W, NT, LC::GL, true>), dim3(c->lm_spec), dim3(NT), LC::lds, c->stream, s, d_li, red, raw, copy_raw, himu, gimu, imu, n, gauge, grav,
                        1.0, scr, d_dx);
   } else {
-    HIPCHK(c, hipFuncSetAttribute((const void *)k_li_solve<W, NT, LC::GL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LC::lds));
+    static LdsOptIn opt_in;
+    HIPCHK(c, opt_in(c->device, (const void *)k_li_solve<W, NT, LC::GL>, LC::lds));
     hipLaunchKernelGGL((k_li_solve<W, NT, LC::GL>), dim3(c->lm_spec), dim3(NT), LC::lds, c->stream, s, d_li, red, raw, copy_raw, himu, gimu, imu, n, gauge, grav,
                        1.0, scr, d_dx);
   }
@@ -1515,13 +1452,10 @@ int vba_debug_solve(vba_ctx *c, int kind, int W, int flags, const double *H, con
   if (flags & VBA_SOLVE_ALL_PANELS) h->pad = 128;   // bit of the diagnostic mask the solve kernels load: run every panel
   double *d_dx = nullptr;
   HIPCHK(c, B.alloc(&d_dx, (size_t)ncand * n));
-  int st = VBA_ERR_BAD_ARG;
-  switch (W) {
-#define VBA_DS_CASE(WW) case WW: st = kind == VBA_SOLVE_LIDAR ? dbg_lidar<WW>(c, B, H, g, flags, *h, d_dx) : dbg_li<WW>(c, B, H, g, flags, *h, d_dx); break;
-    VBA_DS_CASE(2) VBA_DS_CASE(3) VBA_DS_CASE(4) VBA_DS_CASE(5) VBA_DS_CASE(6) VBA_DS_CASE(7) VBA_DS_CASE(8) VBA_DS_CASE(9) VBA_DS_CASE(10)
-    VBA_DS_CASE(11) VBA_DS_CASE(12) VBA_DS_CASE(13) VBA_DS_CASE(14) VBA_DS_CASE(15) VBA_DS_CASE(16)
-#undef VBA_DS_CASE
-  }
+  const int st = for_window<2, 16>(W, [&](auto wc) {
+    constexpr int WW = decltype(wc)::value;
+    return kind == VBA_SOLVE_LIDAR ? dbg_lidar<WW>(c, B, H, g, flags, *h, d_dx) : dbg_li<WW>(c, B, H, g, flags, *h, d_dx);
+  });
   if (st) return st;
   HIPCHK(c, hipMemcpyAsync(dx, d_dx, (size_t)ncand * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
