@@ -136,6 +136,8 @@ struct LmInit {
 };
 template <int W>
 __device__ __forceinline__ void lm_init_store(const LmInit<W> &a, int tid, int nt);
+template <int W, int NT>
+__device__ __forceinline__ void lm_init_store_lds(const double *sp, LmDev *dst, int dbg, int tid);   // from poses the workgroup holds in LDS
 
 template <int W, int TV>
 struct ResCfg {
@@ -174,7 +176,6 @@ __global__ __launch_bounds__((ResCfg<W, TV>::NT)) void k_residual_s(FactorView f
   unsigned int occv = occm;
   asm volatile("" : "+v"(occv), "+v"(coe), "+v"(acc[0]));       // keep the loads above the exit (they would be sunk below it)
   if (gate_v == 0) return;
-  if (init.on && blockIdx.x == 0) lm_init_store(init, tid, C::NT);
   if (tid < W * 12) sp[tid] = pose_s;
   // ---- trip 2: the 10 scalars of an occupied slot (an empty slot costs nothing beyond its mask bit)
   const bool occ = fi < W && v < end && ((occv >> fic) & 1u);
@@ -183,6 +184,7 @@ __global__ __launch_bounds__((ResCfg<W, TV>::NT)) void k_residual_s(FactorView f
   for (int k = 0; k < 9; k++) c[k] = occ ? f.cl[(size_t)k * fs + (size_t)fi * vs + v] : 0.0;
   if (occ) n = f.cl[9 * fs + (size_t)fi * vs + v];
   __syncthreads();
+  if (init.on && blockIdx.x == 0) lm_init_store_lds<W, C::NT>(sp, init.dst, init.dbg, tid);   // the image from sp: stores only, beside trip 2
   if (occ) {
     const Cl10 w = cluster_transform_exact(c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], n, sp + 12 * fi);   // tools.hpp:357-363
     T[0][fi][vl] = w.p00; T[1][fi][vl] = w.p10; T[2][fi][vl] = w.p20; T[3][fi][vl] = w.p11; T[4][fi][vl] = w.p21; T[5][fi][vl] = w.p22;
@@ -546,7 +548,8 @@ struct LmDev;
 __device__ int lm_prev_stop(const LmDev *s);
 __device__ double lm_r1(const LmDev *s);
 __device__ const double *lm_xt(const LmDev *s);
-__device__ void lm_update_apply(LmDev *s, double r2, int W);
+__device__ void lm_spec_state(const LmDev *s, int &spec_i, int &spec_n);   // which damping candidate a rejection would install
+__device__ void lm_update_apply(LmDev *s, double r2, int W, int spec_i, int spec_n);
 __device__ __forceinline__ double lm_sum_partials(const double *__restrict__ r2_dev, int nb, int lane) {   // one wave; every lane gets the sum
   double pv[8];
 #pragma unroll
@@ -591,8 +594,10 @@ __global__ __launch_bounds__(HessCfg2<W>::NT) void k_hessian2(FactorView f, cons
   __shared__ int lm_dec[2];
   int gate_v = (gate && !lm && !init.on) ? *gate : 1;     // consumed after the first tile's loads have been requested (one trip, not two)
   double lm_r2 = 0.0;                         // (init.on: the first pass of a call, run_hess = 1 is part of the image this launch writes)
+  int lm_si = 0, lm_sn = 0;                   // spec_i, spec_n: they name the candidate row the bookkeeping reads behind the barrier
   if (lm) {
     if (threadIdx.x < 64) {
+      lm_spec_state(lm, lm_si, lm_sn);
       lm_r2 = lm_sum_partials(k4_partial, k4_nb, threadIdx.x);
       if (threadIdx.x == 0) {
         const double r1 = lm_r1(lm);
@@ -615,7 +620,6 @@ __global__ __launch_bounds__(HessCfg2<W>::NT) void k_hessian2(FactorView f, cons
 
   if (init.on) {
     for (int t = tid; t < W * 12; t += C::NT) sp[t] = init.x[t];
-    if (bid == 0) lm_init_store(init, tid, C::NT);
   } else {
     for (int t = tid; t < W * 12; t += C::NT) sp[t] = poses[t];
   }
@@ -639,9 +643,10 @@ __global__ __launch_bounds__(HessCfg2<W>::NT) void k_hessian2(FactorView f, cons
   asm volatile("" : "+v"(nx.n));
   if (gate_v == 0) return;                    // uniform
   __syncthreads();
+  if (init.on && bid == 0) lm_init_store_lds<W, C::NT>(sp, init.dst, init.dbg, tid);   // the image from sp, which the barrier above has published
   if (lm) {
     const int run = lm_dec[0], was_stopped = lm_dec[1];
-    if (bid == 0 && threadIdx.x < 64 && !was_stopped) lm_update_apply(lm, lm_r2, W);
+    if (bid == 0 && threadIdx.x < 64 && !was_stopped) lm_update_apply(lm, lm_r2, W, lm_si, lm_sn);
     if (!run) return;                         // uniform: rejected step or converged -> no Hessian pass (VM:443)
   }
   VBA_STAMP(1);

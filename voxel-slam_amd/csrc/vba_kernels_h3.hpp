@@ -192,8 +192,10 @@ __global__ __launch_bounds__(256, 1) void k_hessian3(FactorView f, const double 
   if (t_nx2 < ntiles) e_nx2 = tab[t_nx2];
   int gate_v = (gate && !lm) ? *gate : 1;
   double lm_r2 = 0.0;
+  int lm_si = 0, lm_sn = 0;
   if (lm) {
     if (tid < 64) {
+      lm_spec_state(lm, lm_si, lm_sn);
       lm_r2 = lm_sum_partials(k4_partial, k4_nb, tid);
       if (tid == 0) {
         const double r1 = lm_r1(lm);
@@ -231,7 +233,7 @@ __global__ __launch_bounds__(256, 1) void k_hessian3(FactorView f, const double 
   __syncthreads();
   if (lm) {
     const int run = lm_dec[0], was_stopped = lm_dec[1];
-    if (bid == 0 && tid < 64 && !was_stopped) lm_update_apply(lm, lm_r2, W);
+    if (bid == 0 && tid < 64 && !was_stopped) lm_update_apply(lm, lm_r2, W, lm_si, lm_sn);
     if (!run) return;                         // uniform: rejected step or converged -> no Hessian pass (VM:443)
   }
   double rres = 0.0;

@@ -48,6 +48,40 @@ __device__ __forceinline__ void lm_init_store(const LmInit<W> &a, int tid, int n
   }
 }
 
+// The same image from poses the workgroup already holds in LDS (sp, 12 W doubles, published by a barrier the caller has passed):
+// the fused sites keep the begin poses there for their own work, so workgroup 0 needs no second read of the argument.  NT = the
+// workgroup's thread count; the word loop is unrolled by the compile-time word count, the (at most ceil(2 XT / NT)) LDS reads come
+// first, and what follows is stores only: nothing in it waits for memory, and every word is still stored exactly once.
+template <int W, int NT>
+__device__ __forceinline__ void lm_init_store_lds(const double *sp, LmDev *dst, int dbg, int tid) {
+  constexpr int NW = sizeof(LmDev) / 8, XT = offsetof(LmDev, xt) / 8, U = offsetof(LmDev, u) / 8, V = offsetof(LmDev, v) / 8,
+                I = offsetof(LmDev, is_calc_hess) / 8;
+  constexpr int NI = (NW + NT - 1) / NT, NP = (2 * XT + NT - 1) / NT;     // rounds in all, rounds that reach a pose word
+  static_assert(sizeof(LmDev) % 8 == 0 && offsetof(LmDev, x) == 0 && offsetof(LmDev, u) == 2 * offsetof(LmDev, xt) && 12 * W <= XT, "x and xt lead the image");
+  static_assert(offsetof(LmDev, is_calc_hess) % 8 == 0 && offsetof(LmDev, pad) == offsetof(LmDev, is_calc_hess) + 36, "the ten flags are five words");
+  auto two = [](int lo, int hi) { return (unsigned long long)(unsigned int)lo | ((unsigned long long)(unsigned int)hi << 32); };
+  unsigned long long *o = reinterpret_cast<unsigned long long *>(dst);
+  double pv[NP];
+#pragma unroll
+  for (int j = 0; j < NP; j++) {
+    const int w = tid + j * NT, k = w < XT ? w : w - XT;
+    pv[j] = sp[(w < 2 * XT && k < 12 * W) ? k : 0];
+  }
+#pragma unroll
+  for (int j = 0; j < NI; j++) {
+    const int w = tid + j * NT;
+    unsigned long long val = 0ull;
+    if (j < NP && w < 2 * XT) { const int k = w < XT ? w : w - XT; if (k < 12 * W) val = (unsigned long long)__double_as_longlong(pv[j < NP ? j : 0]); }
+    else if (w == U) val = (unsigned long long)__double_as_longlong(0.01);
+    else if (w == V) val = (unsigned long long)__double_as_longlong(2.0);
+    else if (w == I) val = two(1, 0);               // is_calc_hess, stop
+    else if (w == I + 2) val = two(1, 0);           // all_accepted, last_accepted
+    else if (w == I + 3) val = two(64, 1);          // max_trace, run_hess
+    else if (w == I + 4) val = two(1, dbg);         // run_res, pad
+    if (w < NW) o[w] = val;
+  }
+}
+
 // Stand-alone form: callers whose first kernel is not one of the fused sites (multi-rank flow, the occupancy-compact Hessian pass,
 // LI-BA, an empty store, vba_lm_end right after vba_lm_begin, vba_timing_launch_hessian).
 template <int W>
@@ -314,24 +348,51 @@ __device__ int lm_prev_stop(const LmDev *s) { return s->stop; }
 __device__ double lm_r1(const LmDev *s) { return s->r1; }
 __device__ const double *lm_xt(const LmDev *s) { return s->xt; }
 
-// One wave (all 64 lanes call it with the same r2).  Reads of the state come first, in one batch.
-__device__ void lm_update_apply(LmDev *s, double r2, int W) {
-  const int ntr = s->n_trace, mtr = s->max_trace, it = s->iter, spec_n = s->spec_n, spec_nx = s->spec_i + 1;
-  const double r1 = s->r1, q1 = s->q1, u0 = s->u, v0 = s->v;
+// Everything a decision can need, requested in ONE batch: no address depends on a value of that batch.  The candidate a rejection
+// installs is xt_spec[spec_i + 1], and spec_i is itself part of the state.  A caller that knows spec_i from an earlier trip (the Hessian
+// passes read it with r1 and stop in front of their barrier) names the row; the stand-alone kernels request the lane's words of ALL
+// LM_SPEC - 1 candidates (and their q1) and select when spec_i has arrived.  A lane owns the pose words lane, lane + 64, lane + 128
+// of a 12 VBA_MAX_WIN_DEV-word row: all three lie inside the row for every W, so the loads carry no condition; the stores keep theirs.
+struct LmCand { double q1, p0, p1, p2; };                    // a candidate's q1 and this lane's three pose words
+struct LmUpdIn {                                            // (named scalars, no arrays: every field lives in a register from the start)
+  int stop, ntr, mtr, it, spec_n, spec_i;
+  double r1, q1, u0, v0, xt0, xt1, xt2;
+  LmCand c;                                                 // the candidate behind spec_i (any row when there is none: unused then)
+};
+static_assert(VBA_MAX_WIN_DEV * 12 == 192 && LM_SPEC == 4, "three pose words per lane; candidates 1, 2, 3");
+__device__ __forceinline__ LmCand lm_cand_load(const LmDev *s, int b, int lane) {
+  return {s->q1_spec[b], s->xt_spec[b][lane], s->xt_spec[b][lane + 64], s->xt_spec[b][lane + 128]};
+}
+__device__ __forceinline__ void lm_update_load(const LmDev *s, int lane, LmUpdIn &in) {
+  in.stop = s->stop; in.ntr = s->n_trace; in.mtr = s->max_trace; in.it = s->iter; in.spec_n = s->spec_n; in.spec_i = s->spec_i;
+  in.r1 = s->r1; in.q1 = s->q1; in.u0 = s->u; in.v0 = s->v;
+  in.xt0 = s->xt[lane]; in.xt1 = s->xt[lane + 64]; in.xt2 = s->xt[lane + 128];
+}
+// The pose words are used only inside the branches of the decision, and the compiler sinks their loads into those branches (measured:
+// the rejected step's Hessian launch then lasted 0.4 us longer than the parent's).  Naming them as operands of an empty statement
+// keeps the loads where they were issued; the caller puts this behind the last request of its first batch.
+__device__ __forceinline__ void lm_pin(LmCand &c) { asm volatile("" : "+v"(c.p0), "+v"(c.p1), "+v"(c.p2)); }
+__device__ __forceinline__ void lm_pin(LmUpdIn &in) { asm volatile("" : "+v"(in.xt0), "+v"(in.xt1), "+v"(in.xt2)); }
+// Stand-alone kernels: the state and all candidates in one batch; `wait` runs between the requests and their use (the partial sum).
+template <class F>
+__device__ __forceinline__ void lm_update_load_all(const LmDev *s, int lane, LmUpdIn &in, F wait) {
+  lm_update_load(s, lane, in);
+  LmCand c1 = lm_cand_load(s, 1, lane), c2 = lm_cand_load(s, 2, lane), c3 = lm_cand_load(s, 3, lane);
+  wait();
+  lm_pin(in); lm_pin(c1); lm_pin(c2); lm_pin(c3);
+  const int nx = in.spec_i + 1;                             // >= 1
+  auto pick = [nx](double a1, double a2, double a3) { return nx == 2 ? a2 : nx == 3 ? a3 : a1; };
+  in.c = {pick(c1.q1, c2.q1, c3.q1), pick(c1.p0, c2.p0, c3.p0), pick(c1.p1, c2.p1, c3.p1), pick(c1.p2, c2.p2, c3.p2)};
+}
+
+// One wave (all 64 lanes call it with the same r2 and their own `in`).  `in.stop` is the caller's to test.
+__device__ __forceinline__ void lm_update_commit(LmDev *s, const LmUpdIn &in, double r2, int W) {
+  const int ntr = in.ntr, mtr = in.mtr, it = in.it, spec_n = in.spec_n, spec_nx = in.spec_i + 1;
+  const double r1 = in.r1, q1 = in.q1, u0 = in.u0, v0 = in.v0;
   const int lane = threadIdx.x & 63;
   const bool have_spec = spec_nx < spec_n;                  // a candidate for the damping a rejection leads to (k_lm_solve_m)
-  const double *xs_ = s->xt_spec[have_spec ? spec_nx : 0];
-  double sp0 = 0.0, sp1 = 0.0, sp2 = 0.0;
-  if (have_spec) {
-    if (lane < 12 * W) sp0 = xs_[lane];
-    if (lane + 64 < 12 * W) sp1 = xs_[lane + 64];
-    if (lane + 128 < 12 * W) sp2 = xs_[lane + 128];
-  }
-  const double q1_nx = s->q1_spec[have_spec ? spec_nx : 0];
-  double xt0 = 0.0, xt1 = 0.0, xt2 = 0.0;                 // up to 192 pose scalars = 3 per lane
-  if (lane < 12 * W) xt0 = s->xt[lane];
-  if (lane + 64 < 12 * W) xt1 = s->xt[lane + 64];
-  if (lane + 128 < 12 * W) xt2 = s->xt[lane + 128];
+  const double sp0 = in.c.p0, sp1 = in.c.p1, sp2 = in.c.p2, q1_nx = in.c.q1;   // used only with have_spec
+  const double xt0 = in.xt0, xt1 = in.xt1, xt2 = in.xt2;      // up to 192 pose scalars = 3 per lane
   double q = r1 - r2, u = u0, v = v0;
   const bool accept = q > 0;
   if (accept) {                                             // VM:473-483
@@ -373,16 +434,30 @@ __device__ void lm_update_apply(LmDev *s, double r2, int W) {
   s->run_hess = (accept && !nstop) ? 1 : 0;
 }
 
+// The form the Hessian passes call behind their prologue's barrier (the caller has tested stop, and read spec_i / spec_n in front of
+// the barrier: lm_spec_state): the state, the trial poses and the ONE candidate in one trip, then the stores.
+__device__ void lm_spec_state(const LmDev *s, int &spec_i, int &spec_n) { spec_i = s->spec_i; spec_n = s->spec_n; }
+__device__ void lm_update_apply(LmDev *s, double r2, int W, int spec_i, int spec_n) {
+  const int lane = threadIdx.x & 63, nx = spec_i + 1;
+  LmUpdIn in;
+  lm_update_load(s, lane, in);
+  in.c = lm_cand_load(s, (nx >= 1 && nx < spec_n && nx < LM_SPEC) ? nx : 1, lane);
+  lm_pin(in); lm_pin(in.c);
+  lm_update_commit(s, in, r2, W);
+}
+
 // Stand-alone form (multi-rank flow, the last iteration of a call, callers that want the flags after every iteration).
+// The state batch, stop among it, is requested in front of the partials: one trip before the stores.
 __global__ __launch_bounds__(64) void k_lm_update(LmDev *s, const double *__restrict__ r2_dev, int nb, int W) {
-  const int stop = s->stop;
-  const double r2 = (nb > 0) ? lm_sum_partials(r2_dev, nb, threadIdx.x) : r2_dev[0];
-  if (stop) return;
-  lm_update_apply(s, r2, W);
+  LmUpdIn in;
+  double r2;
+  lm_update_load_all(s, threadIdx.x, in, [&] { r2 = (nb > 0) ? lm_sum_partials(r2_dev, nb, threadIdx.x) : r2_dev[0]; });
+  if (in.stop) return;
+  lm_update_commit(s, in, r2, W);
 }
 
 // The fetching vba_lm_end in ONE launch.  Workgroup 0: wave 0 applies the pending accept/reject (upd != 0: the same lm_sum_partials /
-// lm_update_apply as k_lm_update, so the same sums), then the workgroup stores the LmDev image through the host mapping.  The image
+// lm_update_commit as k_lm_update, so the same sums), then the workgroup stores the LmDev image through the host mapping.  The image
 // is RE-READ for that with device-scope loads behind a device-scope fence and the workgroup barrier: the copy then does not depend
 // on this CU's L1 holding what wave 0 has just stored (lm_update_apply reads the lines it then writes).  Workgroups 1 .. : *hess,
 // tile layout -> row-major (6W)^2 (tl_fetch, as k_tiles_to_full) straight into the pinned buffer (h_hess == nullptr: not launched).
@@ -391,9 +466,10 @@ __global__ __launch_bounds__(256) void k_lm_finish(LmDev *s, const double *__res
                                                    const double *__restrict__ red, double *__restrict__ h_hess) {
   if (blockIdx.x == 0) {
     if (upd && threadIdx.x < 64) {
-      const int stop = s->stop;
-      const double r2 = lm_sum_partials(r2_dev, nb, threadIdx.x);
-      if (!stop) lm_update_apply(s, r2, W);
+      LmUpdIn in;
+      double r2;
+      lm_update_load_all(s, threadIdx.x, in, [&] { r2 = lm_sum_partials(r2_dev, nb, threadIdx.x); });
+      if (!in.stop) lm_update_commit(s, in, r2, W);
       __threadfence();
     }
     __syncthreads();
