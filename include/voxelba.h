@@ -527,6 +527,28 @@ int vba_debug_solve(vba_ctx *ctx, int kind, int W, int flags, const double *H, c
 #define VBA_IMU_TRIAL 4
 int vba_debug_li_imu(vba_ctx *ctx, int W, int gravity, int flags, const double *states, const double *imus, double *h_dense, double *g,
                      double *rimu, double *covinv_out);
+/* Diagnostic: ONE point loop of a resident odometry update, and what it left in device memory (tests/test_gpu_odom_sums.py).  The
+ * image is built by the code the real calls run (odom_ekf_begin on state [25] and cov [225], host arrays; done = 0, refind = 1), the
+ * launches are those one iteration of the loop queues, the stream is drained, nothing of the context's state, covariance or map changes.
+ *   VBA_ODOM_SUMS_VOXEL  the scan-to-map loop of vba_odom_lio_state_estimation_resident on the context's voxel map: pnt_body [n][3]
+ *                        and var_body [n][9], host or device arrays; slices must be 0, cand and planes are not touched.
+ *   VBA_ODOM_SUMS_KD     the loop of vba_odom_lio_state_estimation_kdtree_resident on the context's current point-cloud map, which is
+ *                        not appended to: pnt_body [n][3]; var_body is not read.  slices = 0: the slice count the loop takes for a scan
+ *                        of n points; 1..8: that many.  cand [slices][n][5]: the raw 64-bit candidates of the sliced search (float
+ *                        distance bits << 32 | map index; index 0xFFFFFFFF = unfilled slot), so 8 * n * 5 words cover every choice;
+ *                        planes [n][4]: (unit normal, distance) of the fit, (0, 0, 0, -1) = rejected.
+ * Outputs of both, host arrays: partial [ceil(n / 256)][34], the per-workgroup sums [HTH upper (21) | HTz (6) | nnt upper (6) |
+ * match_num] (kd: columns 27-32 zero), and sums [34], the reduction of k_odom_update over them stored by a one-workgroup launch of
+ * the same code: column c by the seven lanes c + 34 g, lane t adding the elements t, t + 238, ... of the flat partials in that order,
+ * then the seven group sums in group order.  On a voxel map never allocated the loop matches nothing: partial and sums are zero.
+ * *slices_used (may be NULL): the slice count that ran (0 for VOXEL).  VBA_ERR_BAD_ARG with nothing launched: a NULL pointer that the
+ * kind reads or writes, n < 1, a non-finite state, cov or host-array input, an unknown kind or slice count, KD on a map of fewer than
+ * 100 points (the loop never searches one).  VBA_ERR_UNSUPPORTED: a sharded context. */
+#define VBA_ODOM_SUMS_VOXEL 0
+#define VBA_ODOM_SUMS_KD 1
+int vba_debug_odom_sums(vba_ctx *ctx, int kind, int n, const double *pnt_body, const double *var_body, const double *state,
+                        const double *cov, int slices, double *partial, double *sums, unsigned long long *cand, double *planes,
+                        int *slices_used);
 
 /* ------------------------------------------------------------------------------------------------
  * Session-store formats either side of the path.  Host only, no context.

@@ -30,7 +30,7 @@ EXPORTS = [
     "vba_map_num_roots", "vba_map_num_slide_roots", "vba_map_stats", "vba_map_dump_leaves", "vba_map_dump_plane_var", "vba_odom_lio_state_estimation", "vba_odom_lio_state_estimation_resident",
     "vba_set_allreduce", "vba_rccl_get_unique_id", "vba_rccl_init", "vba_set_rccl_comm", "vba_shard_owner", "vba_set_shard",
     "vba_timing_enable", "vba_timing_calibration_read", "vba_timing_select", "vba_timing_sample_every", "vba_timing_launch_hessian", "vba_timing_null_span", "vba_timing_reset", "vba_timing_get",
-    "vba_lm_begin", "vba_lm_refresh_eigen", "vba_lm_iterate", "vba_lm_end", "vba_debug_solve", "vba_debug_li_imu",
+    "vba_lm_begin", "vba_lm_refresh_eigen", "vba_lm_iterate", "vba_lm_end", "vba_debug_solve", "vba_debug_li_imu", "vba_debug_odom_sums",
     "vba_io_save_pcd", "vba_io_load_pcd", "vba_io_save_pose", "vba_io_read_lidarstate",
     "vba_motion_init", "vba_init_imu_poses", "vba_init_align_gravity",
     "vba_btc_default_config", "vba_btc_create", "vba_btc_destroy", "vba_btc_set_skip_near_num", "vba_btc_push_plane_cloud",
@@ -1207,6 +1207,27 @@ class Context:
         report = dict(iterations=rep.iterations, match_num=np.array(rep.match_num[:], dtype=np.int64), rot_add=np.array(rep.rot_add[:]),
                       tra_add=np.array(rep.tra_add[:]), nnt_eig_min=rep.nnt_eig_min)
         return it.value, st, cov, report
+
+    ODOM_SUMS_KINDS = {"voxel": 0, "kd": 1}
+
+    def debug_odom_sums(self, kind, pnt_body, var_body, state25, cov225, slices=0):
+        """vba_debug_odom_sums: ONE point loop of a resident odometry update on host arrays.  kind in ODOM_SUMS_KINDS.  Returns
+        dict(partial [nb][34], sums [34]) and, for "kd", cand [slices][n][5] (uint64), planes [n][4] and slices (the count that ran)."""
+        pnt = _c(pnt_body).reshape(-1, 3); n = len(pnt); nb = (n + 255) // 256
+        kd = self.ODOM_SUMS_KINDS[kind] == 1
+        var = None if var_body is None else _c(var_body)
+        st = _c(state25); cov = _c(cov225)
+        partial = np.full((nb, 34), np.nan); sums = np.full(34, np.nan); used = C.c_int(-1)
+        cand = np.zeros((8, max(n, 1), 5), dtype=np.uint64) if kd else None
+        planes = np.full((max(n, 1), 4), np.nan) if kd else None
+        self._chk(self.lib.vba_debug_odom_sums(self.h, C.c_int(self.ODOM_SUMS_KINDS[kind]), C.c_int(n), _p(pnt), None if var is None else _p(var),
+                                               _p(st), _p(cov), C.c_int(slices), _p(partial), _p(sums),
+                                               cand.ctypes.data_as(C.c_void_p) if kd else None, _p(planes) if kd else None, C.byref(used)))
+        out = dict(partial=partial, sums=sums)
+        if kd:
+            ns = used.value
+            out.update(cand=cand.reshape(-1)[:ns * n * 5].reshape(ns, n, 5).copy(), planes=planes[:n], slices=ns)
+        return out
 
     def kdtree_reserve(self, max_map_points, max_scan_points):
         self._chk(self.lib.vba_odom_kdtree_reserve(self.h, C.c_int(max_map_points), C.c_int(max_scan_points)))

@@ -271,8 +271,12 @@ int map_dump_plane_var(MapStore &s, hipStream_t st, double *out, int max_leaves,
 int map_prune(MapStore &s, hipStream_t st, double jour, int dist, std::string &err);
 int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomEkf *h_img, int n, const double *d_pts,
                       const double *d_var, double *d_partial, std::string &err);
-// the update launch of the resident EKF loops (vba_kernels_odom.hpp), also the kd-tree variant's in vba_odom.hip
+int map_odom_debug_sums(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, const vbh::OdomEkf *h_img, int n, const double *d_pts,
+                        const double *d_var, double *d_partial, double *d_sums, int *nb_out, std::string &err);
+// the update launch of the resident EKF loops (vba_kernels_odom.hpp), also the kd-tree variant's in vba_odom.hip, and the launch that
+// stores its sums alone (vba_debug_odom_sums)
 __global__ __launch_bounds__(256) void k_odom_update(vbh::OdomEkf *S, const double *__restrict__ partial, int nb, int iter, int kd);
+__global__ __launch_bounds__(256) void k_odom_sums(const double *__restrict__ partial, int nb, double *__restrict__ sums);
 int map_fix_source_ensure(MapStore &s, hipStream_t st, size_t nodes, size_t fix, size_t n, std::string &err);
 int map_cut_voxel_fix_source(MapStore &s, hipStream_t st, int n, const FixSource &src, double jour, std::string &err);
 // fills the map's root table with the empty key, also the hash tables of vba_kernels_big.hpp in vba_hba.hip

@@ -74,6 +74,9 @@ __device__ __forceinline__ void kd_lstsq_5x3(double A[5][3], double b[5], double
 // words orders by distance and, at equal distance, by index — the order a sequential scan with strict `<` produces.
 __device__ __forceinline__ void kd_match_body(int n, const double *__restrict__ pts, const KdPose &X, int m, const double *__restrict__ tree,
                                               unsigned long long *__restrict__ cand /*[slices][n][5]*/) {
+  // every product and sum below is rounded on its own, as FLANN's are: a fused multiply-add changes the low bits of a float distance,
+  // and with them the order of near-equidistant neighbours (tests/test_gpu_odom_sums.py holds the words to the unfused restatement)
+#pragma clang fp contract(off)
   __shared__ float tx[256], ty[256], tz[256];
   const int i = blockIdx.x * 256 + threadIdx.x;
   float qx = 0, qy = 0, qz = 0;

@@ -724,22 +724,42 @@ int map_cut_voxel_fix_source(MapStore &s, hipStream_t st, int n, const FixSource
 }
 
 // ================================================================================================ resident odometry loop (vba_kernels_odom.hpp)
+// One point loop of the resident update, as queued: the match launch over nb workgroups when there is anything to match, else nothing
+// (every sum is zero: the reduction then runs on no partials).  Returns nb, the rows of d_partial the reduction is to read.
+static int map_odom_point_loop(MapStore &s, hipStream_t st, const MapParams &P, const vbh::OdomEkf *d_S, int n, const double *d_pts,
+                               const double *d_var, double *d_partial) {
+  if (!(n > 0 && s.allocated)) return 0;
+  const int nb = (n + 255) / 256;
+  hipLaunchKernelGGL(k_odom_match_dev, dim3(nb), dim3(256), 0, st, s.v, P, d_S, n, d_pts, d_var, d_partial);
+  return nb;
+}
 // The whole call on the stream: one upload of the image, (match, update) x 4, one download of the result block, one wait.  h_img
 // is pinned and holds the image on entry and the result block on return.
 int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomEkf *h_img, int n, const double *d_pts,
                       const double *d_var, double *d_partial, std::string &err) {
   MAPCHK(hipMemcpyAsync(d_S, h_img, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, st));
-  const bool match = n > 0 && s.allocated;               // otherwise every sum is zero: the update runs on no partials
-  const int nb = match ? (n + 255) / 256 : 0;
   const MapParams P = map_params(s);
   for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
-    if (match) hipLaunchKernelGGL(k_odom_match_dev, dim3(nb), dim3(256), 0, st, s.v, P, (const vbh::OdomEkf *)d_S, n, d_pts, d_var, d_partial);
+    const int nb = map_odom_point_loop(s, st, P, d_S, n, d_pts, d_var, d_partial);
     hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, st, d_S, (const double *)d_partial, nb, iter, 0);
   }
   MAPCHK(hipGetLastError());
   const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
   MAPCHK(hipMemcpyAsync((char *)h_img + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, st));
   MAPCHK(hipStreamSynchronize(st));
+  return VBA_OK;
+}
+// vba_debug_odom_sums on the voxel map: the image uploaded, ONE point loop as the call above queues it, the reduction of
+// k_odom_update stored by k_odom_sums, the stream drained.  *nb_out = the rows of d_partial that the loop wrote (0 on a map never
+// allocated).  d_sums: 34 doubles of device memory.
+int map_odom_debug_sums(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, const vbh::OdomEkf *h_img, int n, const double *d_pts,
+                        const double *d_var, double *d_partial, double *d_sums, int *nb_out, std::string &err) {
+  MAPCHK(hipMemcpyAsync(d_S, h_img, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, st));
+  const int nb = map_odom_point_loop(s, st, map_params(s), d_S, n, d_pts, d_var, d_partial);
+  hipLaunchKernelGGL(k_odom_sums, dim3(1), dim3(256), 0, st, (const double *)d_partial, nb, d_sums);
+  MAPCHK(hipGetLastError());
+  MAPCHK(hipStreamSynchronize(st));
+  *nb_out = nb;
   return VBA_OK;
 }
 

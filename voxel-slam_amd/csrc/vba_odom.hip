@@ -8,6 +8,7 @@
 #include "vba_odom_ekf.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstring>
 
@@ -107,6 +108,24 @@ int vba_odom_kdtree_allocations(vba_ctx *c, int *n_allocs, int64_t *bytes) {
   return VBA_OK;
 }
 
+// The image of a call: odom_ekf_begin on (state, cov) with cov_inv = P^-1 (VS:987), or in kd mode P^-1 / 1000 entry by entry (VS:1134,
+// VS:1213) and the first iteration searching
+static void odom_image_begin(vbh::OdomEkf &S, const double *state, const double *cov, bool kd) {
+  double cov_inv[225];
+  vbh::inverse_pplu(cov, cov_inv, VBA_DIM);
+  if (kd) for (int k = 0; k < 225; k++) cov_inv[k] = cov_inv[k] / 1000;
+  vbh::odom_ekf_begin(S, state, cov, cov_inv);
+  if (kd) S.refind = 1;
+}
+// One point loop of the kd-tree update, as queued: search per slice, merge + fit, the 28 sums per workgroup.  n > 0.
+static void kd_point_loop(hipStream_t s, const vbh::OdomEkf *d_S, int n, int kd_slices, const double *d_pts, int m, const double *tree,
+                          unsigned long long *d_cand, double *d_pl, double *d_part) {
+  const int nb = (n + 255) / 256;
+  hipLaunchKernelGGL(k_kd_match_dev, dim3(nb, kd_slices), dim3(256), 0, s, d_S, n, d_pts, m, tree, d_cand);
+  hipLaunchKernelGGL(k_kd_fit_dev, dim3(nb), dim3(256), 0, s, d_S, n, kd_slices, (const unsigned long long *)d_cand, tree, d_pl);
+  hipLaunchKernelGGL(k_kd_accum_dev, dim3(nb), dim3(256), 0, s, d_S, n, d_pts, (const double *)d_pl, d_part);
+}
+
 // One update on a scan in device memory, c->kd_n + n <= 2^28.  With fewer than 100 map points the scan only seeds the map (VS:1105-1118):
 // the append is enqueued, *ran stays false and nothing is waited for.  Otherwise state and cov are updated, the call has completed on
 // return and c->h_odom holds the loop's result block.  Nothing here touches c->d_stage: a caller may keep the scan there.
@@ -135,23 +154,14 @@ static int kd_odom_core(vba_ctx *c, int n, const double *d_pts, double *state, d
   const KdScanLayout L = kd_scan_layout(c->kdscan_pts);
   double *d_pl = (double *)c->d_kdscan.p, *d_part = (double *)(c->d_kdscan + L.o_part);
   unsigned long long *d_cand = (unsigned long long *)(c->d_kdscan + L.o_cand);
-  // the image: cov_inv = P^-1 / 1000 entry by entry (VS:1134, VS:1213), the first iteration searches
-  double cov_inv[225];
-  vbh::inverse_pplu(cov, cov_inv, VBA_DIM);
-  for (int k = 0; k < 225; k++) cov_inv[k] = cov_inv[k] / 1000;
   vbh::OdomEkf &S = *c->h_odom;
-  vbh::odom_ekf_begin(S, state, cov, cov_inv);
-  S.refind = 1;
+  odom_image_begin(S, state, cov, true);
   vbh::OdomEkf *d_S = c->d_odom;
   hipStream_t s = c->stream;
   double *tree = c->d_kdtree[c->kd_cur], *tree_out = c->d_kdtree[c->kd_cur ^ 1];
   HIPCHK(c, hipMemcpyAsync(d_S, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
   for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
-    if (n > 0) {
-      hipLaunchKernelGGL(k_kd_match_dev, dim3(nb, kd_slices), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, c->kd_n, (const double *)tree, d_cand);
-      hipLaunchKernelGGL(k_kd_fit_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, kd_slices, (const unsigned long long *)d_cand, (const double *)tree, d_pl);
-      hipLaunchKernelGGL(k_kd_accum_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, (const double *)d_pl, d_part);
-    }
+    if (n > 0) kd_point_loop(s, d_S, n, kd_slices, d_pts, c->kd_n, tree, d_cand, d_pl, d_part);
     // n == 0: nb == 0 and d_part may be NULL (no scan scratch was ever needed); the reduction reads nb * 34 doubles, that is none
     hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, s, d_S, (const double *)d_part, nb, iter, 1);
   }
@@ -209,19 +219,20 @@ int vba_odom_lio_state_estimation_kdtree(vba_ctx *c, int n, const double *pnt_bo
 // one image, queues the four (point loop, update) pairs and waits once; which of them do any work is decided by the `done` flag in the
 // device state.  state and cov are updated, c->h_odom holds the loop's result block.  Nothing here touches c->d_stage: a caller may keep
 // the scan there.  Runs on this rank's map, whatever n_ranks is.
-static int odom_core(vba_ctx *c, int n, const double *d_pts, const double *d_var, double *state, double *cov) {
-  int st = odom_image_ensure(c);
-  if (st) return st;
+static int odom_part_ensure(vba_ctx *c, int n) {
   const size_t need = (size_t)((n + 255) / 256) * 34;
   if (need > c->d_odom_part.n) {
     size_t cap = 256 * 34;
     while (cap < need) cap *= 2;
     HIPCHK(c, c->d_odom_part.ensure(cap));               // idle: the call that used it ended in a synchronise
   }
-  double cov_inv[225];
-  vbh::inverse_pplu(cov, cov_inv, VBA_DIM);                                // VS:987
+  return VBA_OK;
+}
+static int odom_core(vba_ctx *c, int n, const double *d_pts, const double *d_var, double *state, double *cov) {
+  int st = odom_image_ensure(c);
+  if (st || (st = odom_part_ensure(c, n))) return st;
   vbh::OdomEkf &S = *c->h_odom;
-  vbh::odom_ekf_begin(S, state, cov, cov_inv);
+  odom_image_begin(S, state, cov, false);
   if ((st = map_odom_resident(c->map, c->stream, c->d_odom, c->h_odom, n, d_pts, d_var, c->d_odom_part, c->err))) return st;
   std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
   std::memcpy(cov, S.P_out, sizeof(S.P_out));
@@ -254,6 +265,58 @@ int vba_odom_lio_state_estimation(vba_ctx *c, int n, const double *pnt_body, con
   }
   if ((st = odom_core(c, n, d_pts, d_var, state, cov))) return st;
   if (ok) *ok = (vbh::odom_nnt_eig_min(c->h_odom->nnt) < 14) ? 0 : 1;
+  return VBA_OK;
+}
+
+// ---------------------------------------------------------------- diagnostic: one point loop of either variant (include/voxelba.h)
+static bool all_finite(const double *a, size_t n) {
+  for (size_t i = 0; i < n; i++) if (!std::isfinite(a[i])) return false;
+  return true;
+}
+int vba_debug_odom_sums(vba_ctx *c, int kind, int n, const double *pnt_body, const double *var_body, const double *state, const double *cov,
+                        int slices, double *partial, double *sums, unsigned long long *cand, double *planes, int *slices_used) {
+  if (!c || !pnt_body || !state || !cov || !partial || !sums || n < 1 || n > (1 << 28)) return VBA_ERR_BAD_ARG;
+  if (kind != VBA_ODOM_SUMS_VOXEL && kind != VBA_ODOM_SUMS_KD) return VBA_ERR_BAD_ARG;
+  const bool kd = kind == VBA_ODOM_SUMS_KD;
+  if (kd ? (!cand || !planes || slices < 0 || slices > 8 || c->kd_n < 100) : (!var_body || slices != 0)) return VBA_ERR_BAD_ARG;
+  if (!all_finite(state, 25) || !all_finite(cov, 225)) return VBA_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!is_device_ptr(pnt_body) && !all_finite(pnt_body, (size_t)n * 3)) return VBA_ERR_BAD_ARG;
+  if (!kd && !is_device_ptr(var_body) && !all_finite(var_body, (size_t)n * 9)) return VBA_ERR_BAD_ARG;
+  if (c->n_ranks > 1) { c->set_error("vba_debug_odom_sums runs the resident odometry loops: unsharded contexts only"); return VBA_ERR_UNSUPPORTED; }
+  const int nb = (n + 255) / 256, ns = kd ? (slices ? slices : kd_slices_of(nb)) : 0;
+  if (slices_used) *slices_used = ns;
+  // the scan staged as the host-fed calls stage it; the outputs of the loop in buffers of this call: [sums 34 | partial nb * 34 |
+  // planes n * 4], candidates [ns][n][5]
+  int st = ensure_stage(c, (size_t)n * 12 * sizeof(double));
+  if (st || (st = odom_image_ensure(c))) return st;
+  double *d_pts = (double *)c->d_stage.p, *d_var = d_pts + (size_t)n * 3;
+  DevMem<double> d_out;
+  DevMem<unsigned long long> d_cand;
+  HIPCHK(c, d_out.ensure(34 + (size_t)nb * 34 + (size_t)n * 4));
+  if (kd) HIPCHK(c, d_cand.ensure((size_t)ns * n * 5));
+  double *d_sums = d_out.p, *d_part = d_sums + 34, *d_pl = d_part + (size_t)nb * 34;
+  hipStream_t s = c->stream;
+  HIPCHK(c, hipMemsetAsync(d_out.p, 0, d_out.n * sizeof(double), s));
+  HIPCHK(c, hipMemcpyAsync(d_pts, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, s));
+  if (!kd) HIPCHK(c, hipMemcpyAsync(d_var, var_body, (size_t)n * 9 * sizeof(double), hipMemcpyDefault, s));
+  vbh::OdomEkf &S = *c->h_odom;
+  odom_image_begin(S, state, cov, kd);
+  if (kd) {
+    HIPCHK(c, hipMemcpyAsync(c->d_odom.p, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
+    kd_point_loop(s, c->d_odom, n, ns, d_pts, c->kd_n, c->d_kdtree[c->kd_cur], d_cand, d_pl, d_part);
+    hipLaunchKernelGGL(k_odom_sums, dim3(1), dim3(256), 0, s, (const double *)d_part, nb, d_sums);
+    st = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess ? VBA_OK : VBA_ERR_HIP;
+  } else {
+    int nb_run = 0;
+    st = map_odom_debug_sums(c->map, s, c->d_odom, c->h_odom, n, d_pts, d_var, d_part, d_sums, &nb_run, c->err);
+  }
+  if (st) { hipStreamSynchronize(s); return st; }                           // (nothing of this call is left in flight behind a status)
+  hipError_t e = hipMemcpy(sums, d_sums, 34 * sizeof(double), hipMemcpyDefault);
+  if (e == hipSuccess) e = hipMemcpy(partial, d_part, (size_t)nb * 34 * sizeof(double), hipMemcpyDefault);
+  if (e == hipSuccess && kd) e = hipMemcpy(planes, d_pl, (size_t)n * 4 * sizeof(double), hipMemcpyDefault);
+  if (e == hipSuccess && kd) e = hipMemcpy(cand, d_cand.p, (size_t)ns * n * 5 * sizeof(unsigned long long), hipMemcpyDefault);
+  HIPCHK(c, e);
   return VBA_OK;
 }
 
