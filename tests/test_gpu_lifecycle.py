@@ -8,7 +8,15 @@ after each cycle's destroy does not drift.
 The sizes are the smallest that cross each buffer's first capacity: the factor store starts at 4096 voxels (6208 after the stride
 skew), the keyframe arrays, the kd-tree map and the plane clouds at 65536 points, the descriptor rows, offsets and votes at 1024,
 the match list at 65536, a scan frame's message at 1 MiB and its point block at 65536 points.  The tables that only grow past 64
-scans or segments (keyframe transforms, undistortion parameters, loop-map segments) are allocated, not grown, here."""
+scans or segments (keyframe transforms, undistortion parameters, loop-map segments) are allocated, not grown, here.
+
+A second test does the same for the stores whose blocks are owning members beside a view ("Buffer ownership": the voxel
+map, the global-BA stores, the descriptor generator): each through its first allocation and the smallest growth that exists.  The
+node family of the map starts at 2^18 and the first recut asks for nodes + 8 * 65536, so it grows to 2^20 with the first scan's
+leaves kept; the scan family starts at 65536 points a slot and a 70 000-point scan grows it with slot 0 kept; the fixed pool is
+allocated (2^20 points, its growth runs the same code as the other two families); the point group of the global BA starts at
+n + n / 4 + 1024; the generator's point group goes 65536 -> 131072.  That a grown map holds what a map sized in advance holds is
+checked in deterministic mode, where the leaf dump has a canonical order: bit for bit."""
 import ctypes as C
 import dataclasses
 
@@ -24,6 +32,13 @@ GRANULE = 2 << 20
 # identical in either run (the parent's series does not scatter, so the bound is asserted)
 PARENT_DRIFT = 0
 CHILD_DRIFT = 0
+# the same for test_store_cycles_leave_no_device_memory_behind, parent = the commit before the stores' blocks became owning members
+# (hand-kept free lists in map_free, GbaStore::free_all, BigStore::release, btcgen_free), same MI355X, same visit: the six readings
+# after each cycle's destroy and their drift; neither series scatters
+STORE_PARENT_FREE = [308092600320] * 6              # (this test alone in its process)
+STORE_CHILD_FREE = [307979354112] * 6               # (after the test above in the same process)
+STORE_PARENT_DRIFT = 0
+STORE_CHILD_DRIFT = 0
 
 
 def _hip():
@@ -118,3 +133,93 @@ def test_cycles_leave_no_device_memory_behind(inputs):
     drift = free[0] - free[-1]
     print("free bytes after each cycle's destroy: %s; drift %d (parent %d, child %d as measured)" % (free, drift, PARENT_DRIFT, CHILD_DRIFT))
     assert drift <= PARENT_DRIFT + GRANULE
+
+
+# ---------------------------------------------------------------- the stores with a view beside their owners
+GBA = dict(gba_voxel_size=2.0, gba_min_eigen_value=0.1, gba_eig=[0.25, 0.25, 0.25, 0.25])
+
+
+@pytest.fixture(scope="module")
+def store_inputs():
+    import voxel_slam_amd  # noqa: F401
+    from voxel_slam_amd import capi, synth
+    wl = dataclasses.replace(synth.CONFIGS["room20k_w4"], win_size=W, n_pts=90000)
+    s = synth.make_scans(wl)
+    assert min(len(p) for p in s["points"]) >= 70000
+    rng = np.random.default_rng(5)
+    A = rng.normal(0, 0.01, (70000, 3, 3))
+    var = np.ascontiguousarray((A @ A.transpose(0, 2, 1) + 1e-6 * np.eye(3)).reshape(-1, 9))
+    poses = synth.poses_flat(s["R0"], s["p0"])
+    fixed = np.ascontiguousarray((s["points"][2] @ s["R0"][2].T + s["p0"][2])[:500])
+    wl4 = dataclasses.replace(synth.CONFIGS["room20k_w4"], win_size=4, n_pts=4000)
+    s4 = synth.make_scans(wl4)
+    f32 = lambda a: np.ascontiguousarray(a).astype(np.float32).astype(np.float64)
+    cloud = synth.make_btc_keyframe_sessions(n_sessions=1, n_kf=1, n_points=100000, seed=11)[0]["cloud"][0]
+    assert len(cloud) >= 70000
+    return dict(capi=capi, wl=wl, pts=[np.ascontiguousarray(s["points"][0][:2000]), np.ascontiguousarray(s["points"][1][:70000])], var=var, poses=poses,
+                fixed=fixed, gba_small=[f32(p[:300]) for p in s["points"]], gba_big=[f32(p[:2000]) for p in s["points"]],
+                clouds4=[f32(p) for p in s4["points"]], poses4=synth.poses_flat(s4["R0"], s4["p0"]), cloud=np.ascontiguousarray(cloud[:70000], dtype=np.float32))
+
+
+def _map_sequence(inp, ctx):
+    """first allocation of the node, scan and fixed families and the root table, growth of the node and scan families with contents
+    kept; returns the leaf dump after recut(2)"""
+    pts, var, poses = inp["pts"], inp["var"], inp["poses"]
+    ctx.cut_voxel(0, pts[0], poses[0], var=var[:2000])
+    ctx.recut(1, poses)
+    ctx.cut_voxel(1, pts[1], poses[1], var=var)
+    ctx.recut(2, poses)
+    dump = ctx.dump_leaves()
+    assert len(dump) > 100
+    ctx.margi(2, poses, jour=1.0)
+    ctx.cut_voxel_fix(inp["fixed"], jour=2.0)
+    ctx.prune(2.0)
+    ctx.map_reset()
+    assert ctx.num_roots() == 0
+    return dump
+
+
+def _store_cycle(inp):
+    capi = inp["capi"]
+
+    def context(**kw):
+        opt = capi.options_from_workload(inp["wl"])
+        opt.device = 0
+        for k, v in kw.items():
+            setattr(opt, k, v)
+        return capi.Context(opt)
+
+    ctx = context()
+    _map_sequence(inp, ctx)
+    # global BA: the octree of a window (point group allocated, then grown), then a window of another size: the sparse path's arena
+    assert ctx.gba_build(inp["gba_small"], inp["poses"], GBA["gba_voxel_size"], GBA["gba_min_eigen_value"], GBA["gba_eig"]) >= 0
+    assert ctx.gba_build(inp["gba_big"], inp["poses"], GBA["gba_voxel_size"], GBA["gba_min_eigen_value"], GBA["gba_eig"]) > 0
+    got = ctx.hba_add_edge(inp["clouds4"], inp["poses4"], GBA["gba_voxel_size"], GBA["gba_min_eigen_value"], GBA["gba_eig"], 1, 2, want_cloud=False)
+    assert np.isfinite(got["poses"]).all()
+    # descriptor generator: every group allocated, then the point group (and the planes sized by it) grown
+    db = ctx.btc_db(capi.btc_default_config(0))
+    db.set_gen_config(capi.btc_default_gen_config(0))
+    db.generate_stds(inp["cloud"][:2000], 0)
+    n0, _ = db.gen_allocations()
+    assert n0 > 0
+    db.generate_stds(inp["cloud"], 1)
+    assert db.gen_allocations()[0] > n0
+    db.close()
+    ctx.close()
+    # deterministic mode (hfirst, the stable sort's histograms): the grown map against one sized in advance
+    grown, sized = context(deterministic=1), context(deterministic=1, max_points_per_scan=131072, max_map_nodes=1 << 20)
+    a, b = _map_sequence(inp, grown), _map_sequence(inp, sized)
+    assert a.shape == b.shape and np.array_equal(a, b)
+    grown.close(); sized.close()
+
+
+def test_store_cycles_leave_no_device_memory_behind(store_inputs):
+    _store_cycle(store_inputs)                       # warm-up
+    hip = _hip()
+    free = []
+    for _ in range(6):
+        _store_cycle(store_inputs)
+        free.append(_free_bytes(hip))
+    drift = free[0] - free[-1]
+    print("free bytes after each cycle's destroy: %s; drift %d (parent %d, child %d as measured)" % (free, drift, STORE_PARENT_DRIFT, STORE_CHILD_DRIFT))
+    assert drift <= STORE_PARENT_DRIFT + GRANULE

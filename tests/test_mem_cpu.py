@@ -1,5 +1,5 @@
 """The owning buffer types of csrc/vba_mem.hpp on the CPU: tests/host/mem_host.cpp is built by g++ with the address and
-undefined-behaviour sanitizers against the runtime's headers only (its own stubs stand in for the six runtime calls, nothing of the
+undefined-behaviour sanitizers against the runtime's headers only (its own stubs stand in for the eight runtime calls, nothing of the
 HIP runtime is linked) and run as a child process, one case per run.  Every case also fails when a block is still live at its end."""
 import os
 import subprocess
@@ -19,7 +19,8 @@ def mem_host():
     return out
 
 
-@pytest.mark.parametrize("case", ["ensure", "failed_ensure", "move", "reset", "grow_keep", "grow_keep_alloc_fails", "grow_keep_copy_fails"])
+@pytest.mark.parametrize("case", ["ensure", "failed_ensure", "move", "reset", "grow_keep", "grow_keep_alloc_fails", "grow_keep_copy_fails",
+                                  "family_grow", "family_alloc_fails", "family_copy_fails"])
 def test_mem(mem_host, case):
     r = subprocess.run([mem_host, case], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stderr[-4000:]

@@ -1,7 +1,7 @@
 """The source layout of libvoxelba.so as DESIGN.md states it ("Source layout"): one object per csrc/*.hip unit, every kernel header
 compiled by exactly one unit, host launch code in the units and not in the kernel headers.  A text check over include lines, function
 heads and file names; nothing is compiled.  Also its ownership rule: device and pinned buffers are members of the owning types of
-vba_mem.hpp and free themselves, so the runtime's free calls appear only there and in the few stores with a lifetime of their own."""
+vba_mem.hpp and free themselves, so the runtime's allocation and free calls appear only there."""
 import glob
 import os
 import re
@@ -65,24 +65,20 @@ def test_makefile_units_are_the_hip_files():
 FREE_CALL = re.compile(r"\bhip(?:Host)?Free\s*\(")
 # a definition that starts in column 0: `struct Name`, or a function head `... name(`
 TOP_LEVEL = re.compile(r"^(?:struct\s+(\w+)|[A-Za-z_][^\n;(]*?(~?\w+)\s*\()", re.M)
-# the owners that keep their own free lists: the voxel map (DevArr growth, hash tables, staging, sort scratch and the histogram of
-# the factor extraction, map_free), the global-BA stores (GbaStore and its growth in gba_build, BigStore's chunk arena), the
-# descriptor generator (BtcGen: bg_grow, btcgen_reserve, btcgen_free) and the debug entry points' scoped DbgBufs
-FREE_ALLOWED = {
-    "vba_map.hip": {"grow_arrays", "map_hash_alloc", "map_free", "map_stage", "map_sort_reserve", "map_sort_reserve_n", "map_extract_factors"},
-    "vba_hba.hip": {"gba_build"},
-    "vba_btcgen.hip": {"bg_grow", "btcgen_reserve", "btcgen_free"},
-    "vba_types.hpp": {"GbaStore", "BigStore"},
-    "voxelba.hip": {"DbgBufs"},
-}
+ALLOC_CALL = re.compile(r"\bhip(?:Host)?Malloc\s*\(")
+# no owner keeps a free list of its own: the voxel map, the global-BA stores, the descriptor generator and the debug entry points'
+# scoped DbgBufs hold owning members like everything else
+FREE_ALLOWED = {}
+# the two stamp buffers of the -DVBA_DIAG build: statics that live as long as the process and are never freed
+ALLOC_ALLOWED = {"voxelba.hip": {"k3_stamps_buffer", "launch_residual"}}
 
 
-def free_sites(name):
-    """{enclosing top-level definition: number of free calls} of one file"""
+def call_sites(name, call):
+    """{enclosing top-level definition: number of calls matching `call`} of one file"""
     text = read(name)
     heads = [(m.start(), m.group(1) or m.group(2)) for m in TOP_LEVEL.finditer(text)]
     out = {}
-    for m in FREE_CALL.finditer(text):
+    for m in call.finditer(text):
         owner = [h for pos, h in heads if pos < m.start()][-1]
         out[owner] = out.get(owner, 0) + 1
     return out
@@ -99,12 +95,14 @@ def function_body(text, head):
         j += 1
 
 
-def test_free_calls_only_in_the_owning_types_and_the_listed_stores():
+def test_free_and_allocation_calls_only_in_the_owning_types():
     assert FREE_CALL.search("if (p) hipHostFree (p);") and FREE_CALL.search("hipFree(q)") and not FREE_CALL.search("map_free(s)")
-    assert free_sites("vba_mem.hpp") == {"Mem": 2}
-    files = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*.hip"))) + ["vba_ctx.hpp", "vba_types.hpp"]
-    found = {f: set(free_sites(f)) for f in files if free_sites(f)}
-    assert found == FREE_ALLOWED
+    assert ALLOC_CALL.search("e = hipHostMalloc ((void **)&p, n, 0);") and ALLOC_CALL.search("hipMalloc(&q, n)") and not ALLOC_CALL.search("hipMallocAsync(")
+    assert call_sites("vba_mem.hpp", FREE_CALL) == {"Mem": 2} and call_sites("vba_mem.hpp", ALLOC_CALL) == {"Mem": 2}
+    files = [f for f in sources() if f != "vba_mem.hpp"]
+    assert "vba_stores.hpp" in files and "vba_btcgen.hpp" in files and len(files) > 40
+    assert {f: set(call_sites(f, FREE_CALL)) for f in files if call_sites(f, FREE_CALL)} == FREE_ALLOWED
+    assert {f: set(call_sites(f, ALLOC_CALL)) for f in files if call_sites(f, ALLOC_CALL)} == ALLOC_ALLOWED
 
 
 def test_vba_destroy_lists_no_buffers():
@@ -114,6 +112,11 @@ def test_vba_destroy_lists_no_buffers():
     for handle, unit in (("vba_kf_destroy", "vba_kf.hip"), ("vba_btc_destroy", "vba_btc.hip"), ("vba_scan_frame_destroy", "vba_scan.hip"),
                          ("vba_loop_map_destroy", "vba_loop.hip")):
         assert not FREE_CALL.search(function_body(read(unit), r"^void %s\(\w+ \*\w+\) \{" % handle)), handle
+    # the map's memory goes as a whole: map_free names the events it destroys and no buffer
+    body = function_body(read("vba_map.hip"), r"^void map_free\(MapStore &s\) \{")
+    assert "hipEventDestroy" in body and "MapMem()" in body
+    assert not FREE_CALL.search(body) and not re.search(r"\.reset\(\)|\bs\.(?:v\.)?\w+\s*=\s*nullptr", body)
+    assert "free_all" not in read("voxelba.hip") and "btcgen_free" not in read("vba_btc.hip")
 
 
 def test_vba_mem_is_a_shared_header_without_kernels():
@@ -124,8 +127,10 @@ def test_vba_mem_is_a_shared_header_without_kernels():
         if "vba_mem.hpp" in reached(u + ".hip"):
             assert "vba_ctx.hpp" in direct or "vba_mem.hpp" in direct, u
     assert "vba_mem.hpp" in INCLUDE.findall(read("vba_ctx.hpp"))
-    # no unit reaches it through a kernel header
+    # no unit reaches it through a kernel header: the stores that hold owning members are host code of their own header
     assert [h for h in kernel_headers() if "vba_mem.hpp" in reached(h)] == []
+    assert "vba_mem.hpp" in INCLUDE.findall(read("vba_stores.hpp")) and "vba_mem.hpp" not in reached("vba_types.hpp")
+    assert [f for f in sources() if f != "vba_ctx.hpp" and "vba_stores.hpp" in INCLUDE.findall(read(f))] == []
 
 
 # ---------------------------------------------------------------- launch plumbing ("Source layout": vba_launch.hpp)

@@ -269,7 +269,7 @@ void vba_btc_destroy(vba_btc_db *db) {
   vba_ctx *c = db->ctx;
   hipSetDevice(c->device);
   hipStreamSynchronize(c->stream);
-  if (db->gen) { btcgen_free(*db->gen); delete db->gen; }
+  delete db->gen;      // its buffers free themselves (vba_mem.hpp)
   delete db;
 }
 
@@ -590,7 +590,7 @@ int btc_gen_ensure(vba_btc_db *db, int64_t points, int64_t cells, size_t corners
   const BtcGen &g = *db->gen;
   const size_t stds = btc_max_stds(db->gcfg);
   if ((size_t)points <= g.pts_cap && (size_t)cells <= g.cell_cap && corners <= g.corn_cap && stds <= g.cand_cap &&
-      g.pts_cap / (size_t)(db->gcfg.voxel_init_num + 1) + 1 <= g.plane_cap && g.cnt)
+      g.pts_cap / (size_t)(db->gcfg.voxel_init_num + 1) + 1 <= g.plane_cap && g.h_cnt)
     return VBA_OK;
   HIPCHK(c, btcgen_reserve(*db->gen, (size_t)points, (size_t)cells, corners, stds, db->gcfg.voxel_init_num, c->stream));
   return VBA_OK;
@@ -641,7 +641,7 @@ int btc_generate_check(vba_btc_db *db, int n, int cap, double *rows, uint64_t *b
 }
 // GenerateSTDescs on a cloud from host memory (xyz) or from the device: with xyz == nullptr and n > 0 the caller has sized the
 // generator for n points (btc_gen_ensure) and enqueued, ahead of the database's stream, the writes of float [n][3] into its point
-// buffer db->gen->xyz; the generator only reads that buffer, so a second attempt after a buffer grew finds it intact
+// buffer db->gen->pts.xyz; the generator only reads that buffer, so a second attempt after a buffer grew finds it intact
 int btc_generate_impl(vba_btc_db *db, int n, const float *xyz, int id, int cap, double *rows, uint64_t *bits, int *n_stds) {
   int chk = btc_generate_check(db, n, cap, rows, bits, n_stds);
   if (chk) return chk;
@@ -695,20 +695,20 @@ int btc_generate_impl(vba_btc_db *db, int n, const float *xyz, int id, int cap, 
   db->seq.push_back(id);
   db->last_loc.resize(4 * (size_t)nc); db->last_bits.resize(nc);
   for (int i = 0; i < nc; i++) {
-    const BgCorner &k = G.h_corn[i];
+    const BgCorner &k = G.cor.h_corn[i];
     for (int j = 0; j < 3; j++) db->last_loc[4 * (size_t)i + j] = k.loc[j];
     db->last_loc[4 * (size_t)i + 3] = (double)k.summ;
     db->last_bits[i] = k.bits;
   }
   // rows: [triangle center frame A.loc B.loc C.loc A.summ B.summ C.summ], masks of A, B, C
   for (int i = 0; i < ns; i++) {
-    const BgStd &t = G.h_stds[i];
+    const BgStd &t = G.tri.h_stds[i];
     double *r = rows + (size_t)i * VBA_BTC_ROW_LEN;
     const int v[3] = {t.a, t.b, t.c};
     for (int j = 0; j < 3; j++) { r[j] = t.tri[j]; r[3 + j] = t.cen[j]; }
     r[6] = (double)db->n_add;
     for (int u = 0; u < 3; u++) {
-      const BgCorner &k = G.h_corn[v[u]];
+      const BgCorner &k = G.cor.h_corn[v[u]];
       for (int j = 0; j < 3; j++) r[7 + 3 * u + j] = k.loc[j];
       r[16 + u] = (double)k.summ;
       bits[3 * (size_t)i + u] = k.bits;

@@ -14,6 +14,7 @@
 //  - neighbours exact in float (squared L2, x then y then z, ties to the earlier index), radius test d^2 < (float)(r r);
 //  - triangle dedupe: the first in (i, m, n) order wins (atomicMin of the emission index per key), output in emission order.
 #include "vba_btcgen.hpp"
+#include "vba_mem.hpp"
 #include "vba_btcgen_fit.hpp"
 
 #include <climits>
@@ -609,16 +610,25 @@ __global__ __launch_bounds__(1024) void k_bg_std(const BgCfg cf, int *cnt, const
   if (tid == 0) cnt[BGC_NSTD] = base;
 }
 
+// one array of a group: counted whether or not the allocation succeeds
 template <class T>
-hipError_t bg_grow(BtcGen &g, T **p, size_t n) {
-  if (*p) { hipError_t e = hipFree(*p); if (e != hipSuccess) return e; }
-  *p = nullptr;
+hipError_t bg_grow(BtcGen &g, DevMem<T> &m, size_t n) {
   g.allocs++;
   g.dev_bytes += n * sizeof(T);
-  return hipMalloc((void **)p, n * sizeof(T) > 0 ? n * sizeof(T) : sizeof(T));
+  return m.ensure(n);
 }
 
 #define BGCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return _e; } while (0)
+
+// a capacity group goes from its old size to m: `cap` reads 0 while `grow` runs, and a failure empties the group (complete or empty)
+template <class G, class F>
+hipError_t bg_regroup(G &grp, size_t &cap, size_t m, F grow) {
+  cap = 0;
+  const hipError_t e = grow();
+  if (e != hipSuccess) grp = G();
+  else cap = m;
+  return e;
+}
 
 }  // namespace
 
@@ -627,66 +637,73 @@ hipError_t btcgen_reserve(BtcGen &g, size_t n, size_t cells, size_t corners, siz
     BGCHK(hipStreamSynchronize(st));
     size_t m = g.pts_cap ? g.pts_cap : 65536;
     while (m < n) m *= 2;
-    BGCHK(bg_grow(g, &g.xyz, 3 * m)); BGCHK(bg_grow(g, &g.sxyz, 3 * m));
-    BGCHK(bg_grow(g, &g.key, m)); BGCHK(bg_grow(g, &g.skey, m));
-    BGCHK(bg_grow(g, &g.idx, m)); BGCHK(bg_grow(g, &g.sidx, m)); BGCHK(bg_grow(g, &g.flag, m));
-    BGCHK(bg_grow(g, &g.ckey, m)); BGCHK(bg_grow(g, &g.sckey, m));
-    BGCHK(bg_grow(g, &g.px, m)); BGCHK(bg_grow(g, &g.py, m)); BGCHK(bg_grow(g, &g.pd, m));
-    BGCHK(bg_grow(g, &g.vstart, m)); BGCHK(bg_grow(g, &g.vlen, m)); BGCHK(bg_grow(g, &g.isc, m + 1));
-    size_t b1 = 0, b2 = 0;
-    BGCHK(sort_pairs_u64(nullptr, b1, nullptr, nullptr, nullptr, nullptr, m, 3 * BG_KEY_BITS, st));
-    BGCHK(sort_pairs_u32(nullptr, b2, nullptr, nullptr, nullptr, nullptr, m, 32u, st));
-    g.sort_bytes = b1 > b2 ? b1 : b2;
-    char *t = (char *)g.sort_tmp;
-    BGCHK(bg_grow(g, &t, g.sort_bytes));
-    g.sort_tmp = t;
-    g.pts_cap = m;
+    BtcGen::Pts &p = g.pts;
+    BGCHK(bg_regroup(p, g.pts_cap, m, [&]() -> hipError_t {
+      BGCHK(bg_grow(g, p.xyz, 3 * m)); BGCHK(bg_grow(g, p.sxyz, 3 * m));
+      BGCHK(bg_grow(g, p.key, m)); BGCHK(bg_grow(g, p.skey, m));
+      BGCHK(bg_grow(g, p.idx, m)); BGCHK(bg_grow(g, p.sidx, m)); BGCHK(bg_grow(g, p.flag, m));
+      BGCHK(bg_grow(g, p.ckey, m)); BGCHK(bg_grow(g, p.sckey, m));
+      BGCHK(bg_grow(g, p.px, m)); BGCHK(bg_grow(g, p.py, m)); BGCHK(bg_grow(g, p.pd, m));
+      BGCHK(bg_grow(g, p.vstart, m)); BGCHK(bg_grow(g, p.vlen, m)); BGCHK(bg_grow(g, p.isc, m + 1));
+      size_t b1 = 0, b2 = 0;
+      BGCHK(sort_pairs_u64(nullptr, b1, nullptr, nullptr, nullptr, nullptr, m, 3 * BG_KEY_BITS, st));
+      BGCHK(sort_pairs_u32(nullptr, b2, nullptr, nullptr, nullptr, nullptr, m, 32u, st));
+      g.sort_bytes = b1 > b2 ? b1 : b2;
+      return bg_grow(g, p.sort_tmp, g.sort_bytes);
+    }));
   }
   const size_t pc = g.pts_cap / (size_t)(vinit + 1) + 1;
   if (pc > g.plane_cap) {
     BGCHK(hipStreamSynchronize(st));
-    BGCHK(bg_grow(g, &g.planes, 5 * pc * sizeof(BgPlane)));
-    BGCHK(bg_grow(g, &g.isp, pc + 1)); BGCHK(bg_grow(g, &g.ids, pc)); BGCHK(bg_grow(g, &g.ids2, pc + 1)); BGCHK(bg_grow(g, &g.first, pc + 1));
-    g.plane_cap = pc;
+    BtcGen::Planes &p = g.pln;
+    BGCHK(bg_regroup(p, g.plane_cap, pc, [&]() -> hipError_t {
+      BGCHK(bg_grow(g, p.planes, 5 * pc * sizeof(BgPlane)));
+      BGCHK(bg_grow(g, p.isp, pc + 1)); BGCHK(bg_grow(g, p.ids, pc)); BGCHK(bg_grow(g, p.ids2, pc + 1));
+      return bg_grow(g, p.first, pc + 1);
+    }));
   }
-  if (!g.cnt) {
-    BGCHK(bg_grow(g, &g.cnt, BGC_N));
-    BGCHK(bg_grow(g, &g.mm, 4 * BG_MAX_PROJ));
-    BGCHK(bg_grow(g, &g.sel, BG_MAX_PROJ * sizeof(BgSel)));
+  if (!g.h_cnt) {
+    BGCHK(bg_grow(g, g.cnt, BGC_N));
+    BGCHK(bg_grow(g, g.mm, 4 * BG_MAX_PROJ));
+    BGCHK(bg_grow(g, g.sel, BG_MAX_PROJ * sizeof(BgSel)));
     g.allocs++;
-    BGCHK(hipHostMalloc((void **)&g.h_cnt, BGC_N * sizeof(int), hipHostMallocDefault));
+    BGCHK(g.h_cnt.ensure(BGC_N));
   }
   if (cells < 65536) cells = 65536;
   if (cells > g.cell_cap) {
     BGCHK(hipStreamSynchronize(st));
     size_t m = g.cell_cap ? g.cell_cap : 65536;
     while (m < cells) m *= 2;
-    BGCHK(bg_grow(g, &g.ccnt, m)); BGCHK(bg_grow(g, &g.cdis, m)); BGCHK(bg_grow(g, &g.csx, m)); BGCHK(bg_grow(g, &g.csy, m));
-    BGCHK(bg_grow(g, &g.cbits, m));
-    g.cell_cap = m;
+    BtcGen::Cells &p = g.cel;
+    BGCHK(bg_regroup(p, g.cell_cap, m, [&]() -> hipError_t {
+      BGCHK(bg_grow(g, p.ccnt, m)); BGCHK(bg_grow(g, p.cdis, m)); BGCHK(bg_grow(g, p.csx, m)); BGCHK(bg_grow(g, p.csy, m));
+      return bg_grow(g, p.cbits, m);
+    }));
   }
   if (corners < 1024) corners = 1024;
   if (corners > g.corn_cap) {
     BGCHK(hipStreamSynchronize(st));
     size_t m = g.corn_cap ? g.corn_cap : 1024;
     while (m < corners) m *= 2;
-    BGCHK(bg_grow(g, &g.corn, m)); BGCHK(bg_grow(g, &g.corn2, m)); BGCHK(bg_grow(g, &g.corn3, m));
-    if (g.h_corn) BGCHK(hipHostFree(g.h_corn));
-    g.allocs++;
-    BGCHK(hipHostMalloc((void **)&g.h_corn, m * sizeof(BgCorner), hipHostMallocDefault));
-    g.corn_cap = m;
+    BtcGen::Corners &p = g.cor;
+    BGCHK(bg_regroup(p, g.corn_cap, m, [&]() -> hipError_t {
+      BGCHK(bg_grow(g, p.corn, m)); BGCHK(bg_grow(g, p.corn2, m)); BGCHK(bg_grow(g, p.corn3, m));
+      g.allocs++;
+      return p.h_corn.ensure(m);
+    }));
   }
   if (stds < 1024) stds = 1024;
   if (stds > g.cand_cap) {
     BGCHK(hipStreamSynchronize(st));
     size_t m = g.cand_cap ? g.cand_cap : 1024;
     while (m < stds) m *= 2;
-    BGCHK(bg_grow(g, &g.cand, m)); BGCHK(bg_grow(g, &g.stds, m)); BGCHK(bg_grow(g, &g.ckeys, m)); BGCHK(bg_grow(g, &g.cslot, m));
-    BGCHK(bg_grow(g, &g.htab, 2 * m)); BGCHK(bg_grow(g, &g.hmin, 2 * m));
-    if (g.h_stds) BGCHK(hipHostFree(g.h_stds));
-    g.allocs++;
-    BGCHK(hipHostMalloc((void **)&g.h_stds, m * sizeof(BgStd), hipHostMallocDefault));
-    g.cand_cap = m;
+    BtcGen::Cands &p = g.tri;
+    BGCHK(bg_regroup(p, g.cand_cap, m, [&]() -> hipError_t {
+      BGCHK(bg_grow(g, p.cand, m)); BGCHK(bg_grow(g, p.stds, m)); BGCHK(bg_grow(g, p.ckeys, m)); BGCHK(bg_grow(g, p.cslot, m));
+      BGCHK(bg_grow(g, p.htab, 2 * m)); BGCHK(bg_grow(g, p.hmin, 2 * m));
+      g.allocs++;
+      return p.h_stds.ensure(m);
+    }));
   }
   return hipSuccess;
 }
@@ -694,43 +711,43 @@ hipError_t btcgen_reserve(BtcGen &g, size_t n, size_t cells, size_t corners, siz
 hipError_t btcgen_enqueue(BtcGen &g, const BgCfg &cf, int n, const float *h_xyz, float *pc_dst, int *off_slot, int have, hipStream_t st) {
   const int nb = (n + 255) / 256;
   const size_t pc = g.plane_cap;
-  BgPlane *cpl = (BgPlane *)g.planes, *pl = cpl + pc, *grp = pl + pc, *srt = grp + pc, *mrg = srt + pc;
+  BgPlane *cpl = (BgPlane *)g.pln.planes.p, *pl = cpl + pc, *grp = pl + pc, *srt = grp + pc, *mrg = srt + pc;
   BgPlane *fin = cpl;                                     // the candidates are dead once the planes are compacted
   BGCHK(hipMemsetAsync(g.cnt, 0, BGC_N * sizeof(int), st));
-  if (h_xyz) BGCHK(hipMemcpyAsync(g.xyz, h_xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, st));   // nullptr: g.xyz was filled on the device
+  if (h_xyz) BGCHK(hipMemcpyAsync(g.pts.xyz, h_xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, st));   // nullptr: g.pts.xyz was filled on the device
   // voxels
-  k_bg_key<<<nb, 256, 0, st>>>(n, g.xyz, cf.vsize, g.key, g.idx, g.cnt);
+  k_bg_key<<<nb, 256, 0, st>>>(n, g.pts.xyz, cf.vsize, g.pts.key, g.pts.idx, g.cnt);
   size_t tb = g.sort_bytes;
-  BGCHK(sort_pairs_u64(g.sort_tmp, tb, g.key, g.skey, g.idx, g.sidx, (size_t)n, 3 * BG_KEY_BITS, st));
-  BGCHK(hipMemsetAsync(g.flag, 0, (size_t)n * sizeof(int), st));
-  k_bg_gather<<<nb, 256, 0, st>>>(n, g.xyz, g.skey, g.sidx, g.sxyz, g.flag);
-  k_bg_scan<<<1, 1024, 0, st>>>(g.flag, nullptr, n, g.cnt + BGC_NVOX);
-  k_bg_runs<<<nb, 256, 0, st>>>(n, g.skey, g.sidx, g.flag, cf.vinit, g.vstart, g.vlen, g.isc);
+  BGCHK(sort_pairs_u64(g.pts.sort_tmp, tb, g.pts.key, g.pts.skey, g.pts.idx, g.pts.sidx, (size_t)n, 3 * BG_KEY_BITS, st));
+  BGCHK(hipMemsetAsync(g.pts.flag, 0, (size_t)n * sizeof(int), st));
+  k_bg_gather<<<nb, 256, 0, st>>>(n, g.pts.xyz, g.pts.skey, g.pts.sidx, g.pts.sxyz, g.pts.flag);
+  k_bg_scan<<<1, 1024, 0, st>>>(g.pts.flag, nullptr, n, g.cnt + BGC_NVOX);
+  k_bg_runs<<<nb, 256, 0, st>>>(n, g.pts.skey, g.pts.sidx, g.pts.flag, cf.vinit, g.pts.vstart, g.pts.vlen, g.pts.isc);
   // candidate voxels (> voxel_init_num points) -> candidate index in voxel order; fits; planes -> plane index
-  BGCHK(hipMemcpyAsync(g.flag, g.isc, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, st));
-  k_bg_scan<<<1, 1024, 0, st>>>(g.flag, g.cnt + BGC_NVOX, n, g.cnt + BGC_NCAND);
-  k_bg_fit<<<nb, 256, 0, st>>>(g.cnt, g.sxyz, g.vstart, g.vlen, g.isc, g.flag, cf.detect, cpl, g.isp);
+  BGCHK(hipMemcpyAsync(g.pts.flag, g.pts.isc, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, st));
+  k_bg_scan<<<1, 1024, 0, st>>>(g.pts.flag, g.cnt + BGC_NVOX, n, g.cnt + BGC_NCAND);
+  k_bg_fit<<<nb, 256, 0, st>>>(g.cnt, g.pts.sxyz, g.pts.vstart, g.pts.vlen, g.pts.isc, g.pts.flag, cf.detect, cpl, g.pln.isp);
   const int npc = (int)pc;
-  BGCHK(hipMemcpyAsync(g.ids2, g.isp, pc * sizeof(int), hipMemcpyDeviceToDevice, st));
-  k_bg_scan<<<1, 1024, 0, st>>>(g.ids2, g.cnt + BGC_NCAND, npc, g.cnt + BGC_NPL);
-  k_bg_planes<<<(npc + 255) / 256, 256, 0, st>>>(g.cnt, cpl, g.isp, g.ids2, pl, pc_dst, off_slot, have);
+  BGCHK(hipMemcpyAsync(g.pln.ids2, g.pln.isp, pc * sizeof(int), hipMemcpyDeviceToDevice, st));
+  k_bg_scan<<<1, 1024, 0, st>>>(g.pln.ids2, g.cnt + BGC_NCAND, npc, g.cnt + BGC_NPL);
+  k_bg_planes<<<(npc + 255) / 256, 256, 0, st>>>(g.cnt, cpl, g.pln.isp, g.pln.ids2, pl, pc_dst, off_slot, have);
   // projection planes
-  BgSel *sel = (BgSel *)g.sel;
-  k_bg_select<<<1, 1024, 0, st>>>(cf, g.xyz, g.cnt, pl, grp, srt, mrg, fin, g.ids, g.first, sel, g.mm);
+  BgSel *sel = (BgSel *)g.sel.p;
+  k_bg_select<<<1, 1024, 0, st>>>(cf, g.pts.xyz, g.cnt, pl, grp, srt, mrg, fin, g.pln.ids, g.pln.first, sel, g.mm);
   // extract_binary for each selected plane (launches of planes beyond the selection return at once)
   const long long ccap = (long long)g.cell_cap;
   for (int s = 0; s < cf.proj_num; s++) {
-    k_bg_proj<<<nb, 256, 0, st>>>(n, g.xyz, cf, sel, s, g.cnt, g.mm, g.px, g.py, g.pd);
-    k_bg_cellkey<<<nb, 256, 0, st>>>(n, cf, s, g.cnt, g.mm, g.px, g.py, g.pd, ccap, g.ckey, g.idx);
+    k_bg_proj<<<nb, 256, 0, st>>>(n, g.pts.xyz, cf, sel, s, g.cnt, g.mm, g.pts.px, g.pts.py, g.pts.pd);
+    k_bg_cellkey<<<nb, 256, 0, st>>>(n, cf, s, g.cnt, g.mm, g.pts.px, g.pts.py, g.pts.pd, ccap, g.pts.ckey, g.pts.idx);
     tb = g.sort_bytes;
-    BGCHK(sort_pairs_u32(g.sort_tmp, tb, g.ckey, g.sckey, g.idx, g.sidx, (size_t)n, 32u, st));
-    k_bg_cellzero<<<1024, 256, 0, st>>>(cf, s, g.cnt, g.mm, ccap, g.ccnt, g.cdis);
-    k_bg_cells<<<nb, 256, 0, st>>>(n, cf, s, g.cnt, g.mm, ccap, g.sckey, g.sidx, g.px, g.py, g.pd, g.ccnt, g.cdis, g.csx, g.csy, g.cbits);
-    k_bg_segments<<<1, 1024, 0, st>>>(cf, s, g.cnt, g.mm, ccap, sel, g.ccnt, g.cdis, g.csx, g.csy, g.cbits, g.corn, (int)g.corn_cap);
+    BGCHK(sort_pairs_u32(g.pts.sort_tmp, tb, g.pts.ckey, g.pts.sckey, g.pts.idx, g.pts.sidx, (size_t)n, 32u, st));
+    k_bg_cellzero<<<1024, 256, 0, st>>>(cf, s, g.cnt, g.mm, ccap, g.cel.ccnt, g.cel.cdis);
+    k_bg_cells<<<nb, 256, 0, st>>>(n, cf, s, g.cnt, g.mm, ccap, g.pts.sckey, g.pts.sidx, g.pts.px, g.pts.py, g.pts.pd, g.cel.ccnt, g.cel.cdis, g.cel.csx, g.cel.csy, g.cel.cbits);
+    k_bg_segments<<<1, 1024, 0, st>>>(cf, s, g.cnt, g.mm, ccap, sel, g.cel.ccnt, g.cel.cdis, g.cel.csx, g.cel.csy, g.cel.cbits, g.cor.corn, (int)g.corn_cap);
   }
-  k_bg_corners<<<1, 1024, 0, st>>>(cf, g.cnt, g.corn, (int)g.corn_cap, g.corn2, g.corn3);
+  k_bg_corners<<<1, 1024, 0, st>>>(cf, g.cnt, g.cor.corn, (int)g.corn_cap, g.cor.corn2, g.cor.corn3);
   const int hs = (int)(2 * g.cand_cap);
-  k_bg_std<<<1, 1024, 0, st>>>(cf, g.cnt, g.corn3, g.cand, g.ckeys, g.cslot, g.htab, g.hmin, hs, g.stds);
+  k_bg_std<<<1, 1024, 0, st>>>(cf, g.cnt, g.cor.corn3, g.tri.cand, g.tri.ckeys, g.tri.cslot, g.tri.htab, g.tri.hmin, hs, g.tri.stds);
   BGCHK(hipGetLastError());
   // read-back: counters, every triangle slot the configuration allows, the final corners
   const size_t K1 = (size_t)(cf.K - 1);
@@ -738,20 +755,9 @@ hipError_t btcgen_enqueue(BtcGen &g, const BgCfg &cf, int n, const float *h_xyz,
   if (maxstd > g.cand_cap) maxstd = g.cand_cap;
   size_t maxc = (size_t)cf.useful < g.corn_cap ? (size_t)cf.useful : g.corn_cap;
   BGCHK(hipMemcpyAsync(g.h_cnt, g.cnt, BGC_N * sizeof(int), hipMemcpyDeviceToHost, st));
-  if (maxstd) BGCHK(hipMemcpyAsync(g.h_stds, g.stds, maxstd * sizeof(BgStd), hipMemcpyDeviceToHost, st));
-  if (maxc) BGCHK(hipMemcpyAsync(g.h_corn, g.corn3, maxc * sizeof(BgCorner), hipMemcpyDeviceToHost, st));
+  if (maxstd) BGCHK(hipMemcpyAsync(g.tri.h_stds, g.tri.stds, maxstd * sizeof(BgStd), hipMemcpyDeviceToHost, st));
+  if (maxc) BGCHK(hipMemcpyAsync(g.cor.h_corn, g.cor.corn3, maxc * sizeof(BgCorner), hipMemcpyDeviceToHost, st));
   return hipSuccess;
-}
-
-void btcgen_free(BtcGen &g) {
-  void *p[] = {g.xyz, g.sxyz, g.key, g.skey, g.idx, g.sidx, g.flag, g.ckey, g.sckey, g.px, g.py, g.pd, g.sort_tmp, g.vstart, g.vlen, g.isc,
-               g.isp, g.ids, g.ids2, g.first, g.planes, g.ccnt, g.cdis, g.csx, g.csy, g.cbits, g.sel, g.mm, g.corn, g.corn2, g.corn3, g.cand,
-               g.stds, g.ckeys, g.htab, g.hmin, g.cslot, g.cnt};
-  for (void *q : p) if (q) hipFree(q);
-  if (g.h_cnt) hipHostFree(g.h_cnt);
-  if (g.h_stds) hipHostFree(g.h_stds);
-  if (g.h_corn) hipHostFree(g.h_corn);
-  g = BtcGen{};
 }
 
 }  // namespace vba

@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <hip/hip_runtime.h>
+#include "vba_mem.hpp"
 
 namespace vba {
 
@@ -26,39 +27,43 @@ enum { BGC_NVOX = 0, BGC_NCAND, BGC_NPL, BGC_NG, BGC_NM, BGC_NSEL, BGC_NTEMP, BG
 struct BgStd { double tri[3], cen[3]; int a, b, c, pad; };      // corner indices of A, B, C into the final corner list
 struct BgCorner { double loc[3]; unsigned long long bits; int summ, pad; };
 
+// Five capacity groups and a fixed one, each array an owning member (vba_mem.hpp).  A group grows as a whole, contents not kept, and
+// is complete or empty: a failed growth leaves it empty with its capacity at 0, so the next reserve allocates it again.
 struct BtcGen {
-  size_t pts_cap = 0, cell_cap = 0, corn_cap = 0, cand_cap = 0, sort_bytes = 0;
+  size_t pts_cap = 0, plane_cap = 0, cell_cap = 0, corn_cap = 0, cand_cap = 0, sort_bytes = 0;
   int allocs = 0;                    // device and pinned-host allocations made so far (plane-cloud growth of the database included)
   size_t dev_bytes = 0;
-  // point-indexed
-  float *xyz = nullptr, *sxyz = nullptr;
-  unsigned long long *key = nullptr, *skey = nullptr;
-  int *idx = nullptr, *sidx = nullptr, *flag = nullptr;
-  unsigned *ckey = nullptr, *sckey = nullptr;
-  double *px = nullptr, *py = nullptr, *pd = nullptr;
-  void *sort_tmp = nullptr;
-  // voxel / plane scratch (bounded by the point count)
-  int *vstart = nullptr, *vlen = nullptr, *isc = nullptr, *isp = nullptr, *ids = nullptr, *ids2 = nullptr, *first = nullptr;
-  char *planes = nullptr;            // BgPlane [5][pts_cap / (voxel_init_num + 1) + 1]: candidates, planes, groups, sorted, merged
-  size_t plane_cap = 0;
-  // projection images
-  int *ccnt = nullptr, *cdis = nullptr; double *csx = nullptr, *csy = nullptr; unsigned long long *cbits = nullptr;
-  char *sel = nullptr; unsigned long long *mm = nullptr;
-  BgCorner *corn = nullptr, *corn2 = nullptr, *corn3 = nullptr;
-  // triangles
-  BgStd *cand = nullptr, *stds = nullptr; unsigned long long *ckeys = nullptr, *htab = nullptr; int *hmin = nullptr, *cslot = nullptr;
-  int *cnt = nullptr;
-  // pinned read-back
-  int *h_cnt = nullptr; BgStd *h_stds = nullptr; BgCorner *h_corn = nullptr; size_t h_std_cap = 0, h_corn_cap = 0;
+  struct Pts {                       // [pts_cap]: point-indexed, the voxel scratch bounded by the point count, the sort scratch
+    DevMem<float> xyz, sxyz;
+    DevMem<unsigned long long> key, skey;
+    DevMem<int> idx, sidx, flag;
+    DevMem<unsigned> ckey, sckey;
+    DevMem<double> px, py, pd;
+    DevMem<int> vstart, vlen, isc;
+    DevMem<char> sort_tmp;
+  } pts;
+  struct Planes {                    // [plane_cap = pts_cap / (voxel_init_num + 1) + 1]
+    DevMem<char> planes;             // BgPlane [5][plane_cap]: candidates, planes, groups, sorted, merged
+    DevMem<int> isp, ids, ids2, first;
+  } pln;
+  struct Cells { DevMem<int> ccnt, cdis; DevMem<double> csx, csy; DevMem<unsigned long long> cbits; } cel;   // [cell_cap] projection images
+  struct Corners { DevMem<BgCorner> corn, corn2, corn3; PinMem<BgCorner> h_corn; } cor;                        // [corn_cap]
+  struct Cands {                     // [cand_cap] triangles
+    DevMem<BgStd> cand, stds; DevMem<unsigned long long> ckeys; DevMem<int> cslot;
+    DevMem<unsigned long long> htab; DevMem<int> hmin;   // [2 cand_cap]
+    PinMem<BgStd> h_stds;
+  } tri;
+  // fixed size: counters, per-projection min/max and selection, the counters' pinned read-back (allocated last: it marks the four as there)
+  DevMem<int> cnt; DevMem<unsigned long long> mm; DevMem<char> sel;
+  PinMem<int> h_cnt;
 };
 
 // grow the buffers for n points, `cells` image cells, `corners` temporary corners and `stds` triangle candidates (0 keeps a size)
 hipError_t btcgen_reserve(BtcGen &g, size_t n, size_t cells, size_t corners, size_t stds, int vinit, hipStream_t st);
 // enqueue one GenerateSTDescs over n >= 1 host points (h_xyz == nullptr: the caller has already enqueued the writes of the
-// points into g.xyz on st); the plane cloud goes to pc_dst (room for n / (vinit + 1) + 1 points) and
-// its end offset (have + planes) to *off_slot; the counters, triangles and corners land in g.h_cnt / h_stds / h_corn after the
+// points into g.pts.xyz on st); the plane cloud goes to pc_dst (room for n / (vinit + 1) + 1 points) and
+// its end offset (have + planes) to *off_slot; the counters, triangles and corners land in g.h_cnt / tri.h_stds / cor.h_corn after the
 // caller synchronises the stream
 hipError_t btcgen_enqueue(BtcGen &g, const BgCfg &cfg, int n, const float *h_xyz, float *pc_dst, int *off_slot, int have, hipStream_t st);
-void btcgen_free(BtcGen &g);
 
 }  // namespace vba

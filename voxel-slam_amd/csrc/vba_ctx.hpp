@@ -5,6 +5,7 @@
 #include "vba_types.hpp"
 #include "vba_common.hpp"
 #include "vba_mem.hpp"
+#include "vba_stores.hpp"
 #include "vba_launch.hpp"
 #include "vba_btcgen.hpp"
 

@@ -21,13 +21,28 @@ namespace vba {
 // ---------------------------------------------------------------- host side of vba_kernels_gba.hpp: the octree of one window
 #define GBACHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return VBA_ERR_HIP; } } while (0)
 
+// the view's pointers from the owners (null where a group is empty)
+inline void gba_refresh(GbaStore &s) {
+  GbaView &v = s.v;
+  v.nadd = s.nodes.nadd; v.nlc = s.nodes.nlc; v.ncenter = s.nodes.ncenter; v.nql = s.nodes.nql; v.nchild = s.nodes.nchild; v.nfac = s.nodes.nfac;
+  v.nlayer = s.nodes.nlayer; v.neval = s.nodes.neval; v.nevec = s.nodes.nevec;
+  v.hkeys = s.hash.keys; v.hvals = s.hash.vals;
+  v.pw = s.pts.pw; v.pl = s.pts.pl; v.pframe = s.pts.pframe; v.pnode = s.pts.pnode;
+  v.cnt = s.cnt; v.poses = s.poses; v.offsets = s.offsets;
+}
+
+// The groups of GbaStore are re-allocated as a whole: the old group is freed first (its contents are not kept), and a group that
+// could not be allocated completely is left empty with its capacity at 0, so that the next call allocates it again.
 inline int gba_alloc_nodes(GbaStore &s, int cap, int W, std::string &err) {
-  s.free_nodes();
+  GbaStore::Nodes &m = s.nodes;
+  m = GbaStore::Nodes(); s.v.cap = 0;
   const size_t cp = (size_t)cap;
-  auto al = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes); if (e == hipSuccess) s.node_bufs.push_back(*p); return e; };
-  GBACHK(al((void **)&s.v.nadd, 10 * cp * 8)); GBACHK(al((void **)&s.v.nlc, 10 * cp * W * 8)); GBACHK(al((void **)&s.v.ncenter, 3 * cp * 8));
-  GBACHK(al((void **)&s.v.nql, cp * 4)); GBACHK(al((void **)&s.v.nchild, cp * 4)); GBACHK(al((void **)&s.v.nfac, cp * 4)); GBACHK(al((void **)&s.v.nlayer, cp));
-  GBACHK(al((void **)&s.v.neval, 3 * cp * 8)); GBACHK(al((void **)&s.v.nevec, 9 * cp * 8));
+  hipError_t alloc;
+  if ((alloc = m.nadd.ensure(10 * cp)) || (alloc = m.nlc.ensure(10 * cp * W)) || (alloc = m.ncenter.ensure(3 * cp)) || (alloc = m.nql.ensure(cp)) || (alloc = m.nchild.ensure(cp)) ||
+      (alloc = m.nfac.ensure(cp)) || (alloc = m.nlayer.ensure(cp)) || (alloc = m.neval.ensure(3 * cp)) || (alloc = m.nevec.ensure(9 * cp)))
+    m = GbaStore::Nodes();
+  gba_refresh(s);
+  GBACHK(alloc);
   s.v.cap = cap; s.v.W = W;
   return VBA_OK;
 }
@@ -38,30 +53,32 @@ inline int gba_build(GbaStore &s, hipStream_t st, int W, const int *offsets, con
                      std::string &err) {
   const int n = offsets[W];
   *n_factors = 0;
-  if (!s.h_cnt) {
-    GBACHK(hipHostMalloc((void **)&s.h_cnt, GCNT_N * sizeof(int), hipHostMallocDefault));
-    GBACHK(hipMalloc((void **)&s.v.cnt, GCNT_N * sizeof(int)));
-    GBACHK(hipMalloc((void **)&s.v.poses, VBA_MAX_WIN * 12 * sizeof(double)));
-    GBACHK(hipMalloc((void **)&s.v.offsets, (VBA_MAX_WIN + 1) * sizeof(int)));
-  }
+  hipError_t alloc;
+  GBACHK(s.h_cnt.ensure(GCNT_N));
+  GBACHK(s.cnt.ensure(GCNT_N));
+  GBACHK(s.poses.ensure(VBA_MAX_WIN * 12));
+  GBACHK(s.offsets.ensure(VBA_MAX_WIN + 1));
   if (n > s.cap_pts) {
-    hipFree(s.v.pw); hipFree(s.v.pframe); hipFree(s.v.pnode); hipFree(s.d_pl);
+    GbaStore::Pts &m = s.pts;
+    m = GbaStore::Pts(); s.cap_pts = 0;
     const size_t c = (size_t)n + n / 4 + 1024;
-    GBACHK(hipMalloc((void **)&s.v.pw, 3 * c * 8)); GBACHK(hipMalloc((void **)&s.v.pframe, c * 4)); GBACHK(hipMalloc((void **)&s.v.pnode, c * 4));
-    GBACHK(hipMalloc((void **)&s.d_pl, 3 * c * 8));
+    if ((alloc = m.pw.ensure(3 * c)) || (alloc = m.pframe.ensure(c)) || (alloc = m.pnode.ensure(c)) || (alloc = m.pl.ensure(3 * c))) { m = GbaStore::Pts(); gba_refresh(s); }
+    GBACHK(alloc);
     s.cap_pts = (int)c;
   }
   int hcap = 1 << 16;
   while (hcap < 2 * n && hcap < (1 << 28)) hcap <<= 1;
   if (hcap > s.cap_hash) {
-    hipFree(s.v.hkeys); hipFree(s.v.hvals);
-    GBACHK(hipMalloc((void **)&s.v.hkeys, (size_t)hcap * 8)); GBACHK(hipMalloc((void **)&s.v.hvals, (size_t)hcap * 4));
+    GbaStore::Hash &m = s.hash;
+    m = GbaStore::Hash(); s.cap_hash = 0;
+    if ((alloc = m.keys.ensure(hcap)) || (alloc = m.vals.ensure(hcap))) { m = GbaStore::Hash(); gba_refresh(s); }
+    GBACHK(alloc);
     s.cap_hash = hcap;
   }
+  gba_refresh(s);
   s.v.hmask = (unsigned int)(s.cap_hash - 1);
   s.v.npts = n;
-  GBACHK(hipMemcpyAsync(s.d_pl, pl, (size_t)n * 3 * 8, hipMemcpyDefault, st));
-  s.v.pl = s.d_pl;
+  GBACHK(hipMemcpyAsync(s.pts.pl, pl, (size_t)n * 3 * 8, hipMemcpyDefault, st));
   GBACHK(hipMemcpyAsync(s.v.poses, poses, (size_t)W * 12 * 8, hipMemcpyHostToDevice, st));
   GBACHK(hipMemcpyAsync(s.v.offsets, offsets, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, st));
   if (s.v.cap == 0 || s.v.W != W) { int r = gba_alloc_nodes(s, 1 << 17, W, err); if (r) return r; }
@@ -106,7 +123,7 @@ inline int big_build(BigStore &s, hipStream_t st, int W, const int *offsets, con
   s.reset();
   const int n = offsets[W];
   auto al = [&](void **p, size_t bytes) { return s.arena(p, bytes); };
-  if (!s.h_cnt) BIGCHK(hipHostMalloc((void **)&s.h_cnt, GCNT_N * sizeof(int), hipHostMallocDefault));
+  BIGCHK(s.h_cnt.ensure(GCNT_N));
   GbaBigView &g = s.g;
   g.W = W; g.npts = n; g.pl = d_pl;
   unsigned int hcap = 1u << 16; while (hcap < 2u * (unsigned)n && hcap < (1u << 28)) hcap <<= 1;

@@ -380,7 +380,7 @@ int vba_kf_build(vba_kf_store *s, int k, const int *offsets, const double *pnt, 
     }
     const int nb = (n + 255) / 256;
     hipLaunchKernelGGL(k_kf_merge, dim3(nb), dim3(256), 0, c->stream, n, k, kf_dev_off(s), kf_dev_xf(s), src, dvar, 9, 4, s->d_merge,
-                       db ? db->gen->xyz : (float *)nullptr, dvar ? s->d_mdiag : (double *)nullptr);
+                       db ? db->gen->pts.xyz.p : (float *)nullptr, dvar ? s->d_mdiag : (double *)nullptr);
     if (db && db->ctx->stream != c->stream) {                      // the generator runs on its database's stream, behind the merge
       HIPCHK(c, hipEventRecord(s->ev, c->stream));
       HIPCHK(c, hipStreamWaitEvent(db->ctx->stream, s->ev, 0));
@@ -448,7 +448,7 @@ int vba_kf_generate_stds(vba_kf_store *s, int first, int count, vba_btc_db *db, 
     hipStream_t q = db->ctx->stream;                               // the store is quiescent between calls: everything on the database's stream
     if ((st = kf_upload_tab(s, count, pp.data(), rel.data(), q))) return st;
     hipLaunchKernelGGL(k_kf_merge, dim3((n + 255) / 256), dim3(256), 0, q, n, count, kf_dev_off(s), kf_dev_xf(s), s->d_pnt + 3 * (size_t)b,
-                       (const double *)nullptr, 9, 4, (double *)nullptr, db->gen->xyz, (double *)nullptr);
+                       (const double *)nullptr, 9, 4, (double *)nullptr, db->gen->pts.xyz.p, (double *)nullptr);
     HIPCHK(c, hipGetLastError());
   }
   st = btc_generate_impl(db, n, nullptr, id, cap, rows, bits, n_stds);

@@ -39,7 +39,7 @@ int64_t lm_store_bytes(MapStore &s) {
   for (auto &a : node_arrays(s.v, W)) b += a.elem * a.rows * (size_t)s.v.cap;
   for (auto &a : scan_arrays(s.v, W)) b += a.elem * a.rows * (size_t)s.v.max_pts;
   for (auto &a : fix_arrays(s.v)) b += a.elem * a.rows * (size_t)s.v.cap_fix;
-  b += (size_t)s.hcap * (s.det ? 16 : 12) + s.stage_bytes + s.sort_tmp_bytes + s.whist_cap * sizeof(int);
+  b += (size_t)s.hcap * (s.det ? 16 : 12) + s.d_stage.n + s.d_sort_tmp.n + s.d_whist.n * sizeof(int);
   return (int64_t)b;
 }
 

@@ -55,23 +55,16 @@ std::vector<DevArr> fix_arrays(MapView &v) {
   return {{(void **)&v.fx, 24, 1}, {(void **)&v.fvar, 72, 1}, {(void **)&v.fnode, 4, 1}, {(void **)&v.fb_base, 4, 1}, {(void **)&v.fb_len, 4, 1}, {(void **)&v.fb_next, 4, 1}};
 }
 
-// grow a family of [rows][cap] arrays from oldcap to newcap, keeping the first `used` columns; new space zero-filled
-inline int grow_arrays(std::vector<DevArr> arrs, size_t oldcap, size_t newcap, size_t used, hipStream_t st, std::string &err) {
-  for (auto &a : arrs) {
-    void *np = nullptr;
-    MAPCHK(hipMalloc(&np, a.elem * a.rows * newcap));
-    MAPCHK(hipMemsetAsync(np, 0, a.elem * a.rows * newcap, st));
-    if (*a.slot && used > 0)
-      MAPCHK(hipMemcpy2DAsync(np, newcap * a.elem, *a.slot, oldcap * a.elem, used * a.elem, a.rows, hipMemcpyDeviceToDevice, st));
-    MAPCHK(hipStreamSynchronize(st));
-    if (*a.slot) hipFree(*a.slot);
-    *a.slot = np;
-  }
+// grow a family of [rows][cap] arrays from oldcap to newcap, keeping the first `used` columns; new space zero-filled.  All or nothing
+// (grow_family, vba_mem.hpp): after a failure the owners and the view slots are as they were, under the capacity the caller still records
+inline int grow_arrays(std::vector<DevMem<char>> &own, const std::vector<DevArr> &arrs, size_t oldcap, size_t newcap, size_t used, hipStream_t st, std::string &err) {
+  MAPCHK(grow_family(own, arrs, oldcap, newcap, used, st));
+  for (size_t i = 0; i < arrs.size(); i++) *arrs[i].slot = own[i].p;
   return VBA_OK;
 }
 
 int map_read_counters(MapStore &s, hipStream_t st, std::string &err) {
-  hipLaunchKernelGGL(k_words_to_host, dim3(1), dim3(64), 0, st, s.v.cnt, s.h_cnt, (int)CNT_N);
+  hipLaunchKernelGGL(k_words_to_host, dim3(1), dim3(64), 0, st, s.v.cnt, s.h_cnt.p, (int)CNT_N);
   MAPCHK(hipGetLastError());
   MAPCHK(hipStreamSynchronize(st));
   s.ub_nodes = s.h_cnt[CNT_NODES]; s.ub_roots = s.h_cnt[CNT_ROOTS]; s.ub_used = s.h_cnt[CNT_USED]; s.cnt_stale = false;
@@ -79,37 +72,36 @@ int map_read_counters(MapStore &s, hipStream_t st, std::string &err) {
 }
 
 int map_hash_alloc(MapStore &s, unsigned int cap, hipStream_t st, std::string &err) {
-  unsigned long long *nk = nullptr; int *nv = nullptr;
-  MAPCHK(hipMalloc((void **)&nk, (size_t)cap * 8));
-  MAPCHK(hipMalloc((void **)&nv, (size_t)cap * 4));
+  // the new table is built in locals and adopted at the end: an early return frees it and leaves the map on its old one
+  DevMem<unsigned long long> nk; DevMem<int> nv; DevMem<unsigned int> nf;
+  MAPCHK(nk.ensure(cap));
+  MAPCHK(nv.ensure(cap));
   if (s.det) {   // (no insert is in flight between calls: every slot reads DET_NONE)
-    unsigned int *nf = nullptr;
-    MAPCHK(hipMalloc((void **)&nf, (size_t)cap * 4));
-    MAPCHK(hipMemsetAsync(nf, 0x7F, (size_t)cap * 4, st));
-    if (s.v.hfirst) { MAPCHK(hipStreamSynchronize(st)); hipFree(s.v.hfirst); }
-    s.v.hfirst = nf;
+    MAPCHK(nf.ensure(cap));
+    MAPCHK(hipMemsetAsync(nf.p, 0x7F, (size_t)cap * 4, st));
   }
-  hipLaunchKernelGGL(k_fill_u64, dim3(1024), dim3(256), 0, st, nk, KEY_EMPTY, (size_t)cap);
-  MAPCHK(hipMemsetAsync(nv, 0xFF, (size_t)cap * 4, st));
-  if (s.v.hkeys) {
-    hipLaunchKernelGGL(k_rehash, dim3((s.hcap + 255) / 256), dim3(256), 0, st, s.v.hkeys, s.v.hvals, s.v.hmask, nk, nv, cap - 1);
+  hipLaunchKernelGGL(k_fill_u64, dim3(1024), dim3(256), 0, st, nk.p, KEY_EMPTY, (size_t)cap);
+  MAPCHK(hipMemsetAsync(nv.p, 0xFF, (size_t)cap * 4, st));
+  if (s.hkeys) {
+    hipLaunchKernelGGL(k_rehash, dim3((s.hcap + 255) / 256), dim3(256), 0, st, s.v.hkeys, s.v.hvals, s.v.hmask, nk.p, nv.p, cap - 1);
     hipLaunchKernelGGL(k_copy_counter, dim3(1), dim3(1), 0, st, s.v.cnt, (int)CNT_ROOTS, (int)CNT_USED);   // the tombstones are gone
-    MAPCHK(hipStreamSynchronize(st));
-    hipFree(s.v.hkeys); hipFree(s.v.hvals);
+    MAPCHK(hipStreamSynchronize(st));   // (before the moves below free the old table)
     s.ub_used = s.ub_roots;
   }
-  s.v.hkeys = nk; s.v.hvals = nv; s.v.hmask = cap - 1; s.hcap = cap;
+  s.hkeys = std::move(nk); s.hvals = std::move(nv); s.hfirst = std::move(nf);
+  s.v.hkeys = s.hkeys; s.v.hvals = s.hvals; s.v.hfirst = s.hfirst; s.v.hmask = cap - 1; s.hcap = cap;
   return VBA_OK;
 }
 
 int map_base(MapStore &s, hipStream_t st, std::string &err) {
   if (s.allocated) return VBA_OK;
-  MAPCHK(hipMalloc((void **)&s.v.cnt, CNT_N * sizeof(int)));
-  MAPCHK(hipMalloc((void **)&s.v.fhist, (size_t)EXTRACT_NB_MAX * sizeof(int)));
-  MAPCHK(hipMemsetAsync(s.v.cnt, 0, CNT_N * sizeof(int), st));
-  MAPCHK(hipMalloc((void **)&s.v.poses, VBA_MAX_WIN * 12 * sizeof(double)));
-  MAPCHK(hipHostMalloc((void **)&s.h_cnt, CNT_N * sizeof(int) + 64, hipHostMallocDefault));
-  std::memset(s.h_cnt, 0, CNT_N * sizeof(int) + 64);
+  MAPCHK(s.cnt.ensure(CNT_N));
+  MAPCHK(s.fhist.ensure(EXTRACT_NB_MAX));
+  MAPCHK(hipMemsetAsync(s.cnt.p, 0, CNT_N * sizeof(int), st));
+  MAPCHK(s.poses.ensure(VBA_MAX_WIN * 12));
+  MAPCHK(s.h_cnt.ensure(CNT_N + 16));
+  std::memset(s.h_cnt.p, 0, CNT_N * sizeof(int) + 64);
+  s.v.cnt = s.cnt; s.v.fhist = s.fhist; s.v.poses = s.poses;
   // initial root table: 2^20 slots, or (with the max_points_per_scan capacity hint) the power of two above 4x the hint
   unsigned int hc = 1u << 20;
   if (s.opt.max_points_per_scan) { hc = 1u << 10; while ((size_t)hc < 4 * s.opt.max_points_per_scan && hc < (1u << 30)) hc *= 2; }
@@ -130,14 +122,14 @@ inline int map_ensure(MapStore &s, hipStream_t st, size_t need_nodes, size_t nee
   if (need_nodes > (size_t)s.v.cap) {
     size_t nc = s.v.cap ? (size_t)s.v.cap : (size_t)1 << 18;
     while (nc < need_nodes) nc *= 2;
-    int r = grow_arrays(node_arrays(s.v, W), (size_t)s.v.cap, nc, (size_t)s.v.cap, st, err);
+    int r = grow_arrays(s.node_mem, node_arrays(s.v, W), (size_t)s.v.cap, nc, (size_t)s.v.cap, st, err);
     if (r) return r;
     s.v.cap = (int)nc;
   }
   if (need_pts > (size_t)s.v.max_pts) {
     size_t nc = s.v.max_pts ? (size_t)s.v.max_pts : (size_t)1 << 16;
     while (nc < need_pts) nc *= 2;
-    int r = grow_arrays(scan_arrays(s.v, W), (size_t)s.v.max_pts, nc, (size_t)s.v.max_pts, st, err);
+    int r = grow_arrays(s.scan_mem, scan_arrays(s.v, W), (size_t)s.v.max_pts, nc, (size_t)s.v.max_pts, st, err);
     if (r) return r;
     if (s.v.max_pts == 0) { MAPCHK(hipMemsetAsync(s.v.pnode, 0xFF, (size_t)W * nc * 4, st)); MAPCHK(hipMemsetAsync(s.v.pleaf, 0xFF, (size_t)W * nc * 4, st)); }
     else {  // new tail of every slot must read "no node"
@@ -151,7 +143,7 @@ inline int map_ensure(MapStore &s, hipStream_t st, size_t need_nodes, size_t nee
   if (need_fix > (size_t)s.v.cap_fix) {
     size_t nc = s.v.cap_fix ? (size_t)s.v.cap_fix : (size_t)1 << 20;
     while (nc < need_fix) nc *= 2;
-    int r = grow_arrays(fix_arrays(s.v), (size_t)s.v.cap_fix, nc, (size_t)s.v.cap_fix, st, err);
+    int r = grow_arrays(s.fix_mem, fix_arrays(s.v), (size_t)s.v.cap_fix, nc, (size_t)s.v.cap_fix, st, err);
     if (r) return r;
     s.v.cap_fix = (int)nc;
   }
@@ -169,26 +161,12 @@ inline int map_ensure(MapStore &s, hipStream_t st, size_t need_nodes, size_t nee
   return VBA_OK;
 }
 
+// what is not memory (the pose ring's events), then the memory as a whole: the owners of MapMem free themselves
 void map_free(MapStore &s) {
-  if (!s.allocated) return;
-  const int W = s.opt.win_size;
-  for (auto &a : node_arrays(s.v, W)) if (*a.slot) hipFree(*a.slot);
-  for (auto &a : scan_arrays(s.v, W)) if (*a.slot) hipFree(*a.slot);
-  for (auto &a : fix_arrays(s.v)) if (*a.slot) hipFree(*a.slot);
-  if (s.v.hkeys) hipFree(s.v.hkeys);
-  if (s.v.hvals) hipFree(s.v.hvals);
-  if (s.v.hfirst) hipFree(s.v.hfirst);
-  if (s.d_whist) { hipFree(s.d_whist); s.d_whist = nullptr; s.whist_cap = 0; }
-  if (s.v.cnt) hipFree(s.v.cnt);
-  if (s.v.fhist) hipFree(s.v.fhist);
-  if (s.v.poses) hipFree(s.v.poses);
-  if (s.h_cnt) hipHostFree(s.h_cnt);
-  if (s.h_pose_ring) hipHostFree(s.h_pose_ring);
-  for (int i = 0; i < 8; i++) if (s.pose_ev[i]) hipEventDestroy(s.pose_ev[i]);
-  if (s.d_stage) hipFree(s.d_stage);
-  if (s.d_sort_tmp) { hipFree(s.d_sort_tmp); s.d_sort_tmp = nullptr; s.sort_tmp_bytes = 0; s.sort_tmp_for = 0; }
-  if (s.d_gc) { hipFree(s.d_gc); s.d_gc = nullptr; }
+  for (hipEvent_t &e : s.pose_ev) { if (e) hipEventDestroy(e); e = nullptr; }
+  static_cast<MapMem &>(s) = MapMem();
   s.v = MapView{};
+  s.sort_tmp_for = 0;
   s.allocated = false;
 }
 
@@ -198,11 +176,7 @@ bool is_device_ptr(const void *p) {
   return a.type == hipMemoryTypeDevice;
 }
 inline int map_stage(MapStore &s, size_t bytes, std::string &err) {
-  if (bytes <= s.stage_bytes) return VBA_OK;
-  if (s.d_stage) hipFree(s.d_stage);
-  s.d_stage = nullptr; s.stage_bytes = 0;
-  MAPCHK(hipMalloc(&s.d_stage, bytes));
-  s.stage_bytes = bytes;
+  MAPCHK(s.d_stage.ensure(bytes));
   return VBA_OK;
 }
 inline int map_set_counter(MapStore &s, hipStream_t st, int which, int val, std::string &err) {   // stream-ordered, no host sync
@@ -214,10 +188,10 @@ inline int map_set_counter(MapStore &s, hipStream_t st, int which, int val, std:
 // cnt[to] = sum over the ranks of cnt[from]  (no-op for an unsharded map)
 inline int map_global_count(MapStore &s, hipStream_t st, int from, int to, std::string &err) {
   if (s.n_ranks <= 1 || !s.allreduce) return VBA_OK;
-  if (!s.d_gc) MAPCHK(hipMalloc((void **)&s.d_gc, 2 * sizeof(double)));
-  hipLaunchKernelGGL(k_cnt_to_f64, dim3(1), dim3(1), 0, st, s.v.cnt, from, s.d_gc);
+  MAPCHK(s.d_gc.ensure(2));
+  hipLaunchKernelGGL(k_cnt_to_f64, dim3(1), dim3(1), 0, st, s.v.cnt, from, s.d_gc.p);
   if (s.allreduce(s.d_gc, 1)) { err = "collective failed while summing a map counter over the ranks"; return VBA_ERR_HIP; }
-  hipLaunchKernelGGL(k_f64_to_cnt, dim3(1), dim3(1), 0, st, s.d_gc, s.v.cnt, to);
+  hipLaunchKernelGGL(k_f64_to_cnt, dim3(1), dim3(1), 0, st, s.d_gc.p, s.v.cnt, to);
   MAPCHK(hipGetLastError());
   return VBA_OK;
 }
@@ -227,12 +201,9 @@ inline int map_sort_reserve(MapStore &s, hipStream_t st, std::string &err) {
   if (s.sort_tmp_for >= s.v.max_pts) return VBA_OK;
   size_t need = 0;
   MAPCHK(sort_pairs_u32(nullptr, need, s.v.skey_a, s.v.skey_b, s.v.sval_a, s.v.sval_b, (size_t)s.v.max_pts, 32u, st));
-  if (need > s.sort_tmp_bytes) {
+  if (need > s.d_sort_tmp.n) {
     MAPCHK(hipStreamSynchronize(st));
-    if (s.d_sort_tmp) hipFree(s.d_sort_tmp);
-    s.d_sort_tmp = nullptr; s.sort_tmp_bytes = 0;
-    MAPCHK(hipMalloc(&s.d_sort_tmp, need + 256));
-    s.sort_tmp_bytes = need + 256;
+    MAPCHK(s.d_sort_tmp.ensure(need + 256));
   }
   s.sort_tmp_for = s.v.max_pts;
   return VBA_OK;
@@ -282,15 +253,15 @@ int map_cut_voxel(MapStore &s, hipStream_t st, int win_count, int n, const doubl
     r = map_stage(s, bytes, err);
     if (r) return r;
     MAPCHK(hipMemcpyAsync(s.d_stage, pnt_body, (size_t)n * 3 * 8, hipMemcpyHostToDevice, st));
-    d_pts = (const double *)s.d_stage;
+    d_pts = (const double *)s.d_stage.p;
     if (var) {
-      MAPCHK(hipMemcpyAsync((char *)s.d_stage + (size_t)n * 3 * 8, var, (size_t)n * 9 * 8, hipMemcpyHostToDevice, st));
-      d_var = (const double *)((char *)s.d_stage + (size_t)n * 3 * 8);
+      MAPCHK(hipMemcpyAsync(s.d_stage + (size_t)n * 3 * 8, var, (size_t)n * 9 * 8, hipMemcpyHostToDevice, st));
+      d_var = (const double *)(s.d_stage + (size_t)n * 3 * 8);
     }
   }
   if (var) s.have_var = true;
   {  // pose upload through a pinned ring: no implicit synchronisation of a pageable copy
-    if (!s.h_pose_ring) MAPCHK(hipHostMalloc((void **)&s.h_pose_ring, 8 * 40 * sizeof(double), hipHostMallocDefault));
+    MAPCHK(s.h_pose_ring.ensure(8 * 40));
     const int k = s.pose_next; s.pose_next = (k + 1) & 7;
     if (!s.pose_ev[k]) MAPCHK(hipEventCreateWithFlags(&s.pose_ev[k], hipEventDisableTiming));
     else MAPCHK(hipEventSynchronize(s.pose_ev[k]));
@@ -353,7 +324,7 @@ int map_cut_voxel_fix(MapStore &s, hipStream_t st, int n, const double *pnt_worl
     r = map_stage(s, (size_t)n * 3 * 8, err);
     if (r) return r;
     MAPCHK(hipMemcpyAsync(s.d_stage, pnt_world, (size_t)n * 3 * 8, hipMemcpyHostToDevice, st));
-    d_pts = (const double *)s.d_stage;
+    d_pts = (const double *)s.d_stage.p;
   }
   const MapParams P = map_params(s);
   const int base = s.h_cnt[CNT_FIX];
@@ -366,8 +337,8 @@ int map_cut_voxel_fix(MapStore &s, hipStream_t st, int n, const double *pnt_worl
   r = map_set_counter(s, st, CNT_WL, 0, err); if (r) return r;
   hipLaunchKernelGGL(k_fix_leaf, dim3(nb), dim3(256), 0, st, s.v, P, base, n);
   {
-    size_t tb = s.sort_tmp_bytes;
-    MAPCHK(sort_pairs_u32(s.d_sort_tmp, tb, s.v.skey_a, s.v.skey_b, s.v.sval_a, s.v.sval_b, (size_t)n, map_key_bits(s), st));
+    size_t tb = s.d_sort_tmp.n;
+    MAPCHK(sort_pairs_u32(s.d_sort_tmp.p, tb, s.v.skey_a, s.v.skey_b, s.v.sval_a, s.v.sval_b, (size_t)n, map_key_bits(s), st));
   }
   hipLaunchKernelGGL(k_fix_heads, dim3(nb), dim3(256), 0, st, s.v, n);
   hipLaunchKernelGGL((k_fix_accum_ord<FIXCOV_KEEP>), dim3(n < 4096 ? n : 4096), dim3(64), 0, st, s.v, P, base, n, d_pts, (const int *)nullptr, (const void *)nullptr);
@@ -461,16 +432,13 @@ int map_extract_factors(MapStore &s, hipStream_t st, FactorView f, std::string &
     const int nwg = (nfac + 255) / 256;
     if (s.det) {   // stable: (bucket, node id)
       const size_t need = (size_t)nbuckets * nwg;
-      if (need > s.whist_cap) {
+      if (need > s.d_whist.n) {
         MAPCHK(hipStreamSynchronize(st));
-        if (s.d_whist) hipFree(s.d_whist);
-        s.d_whist = nullptr; s.whist_cap = 0;
-        MAPCHK(hipMalloc((void **)&s.d_whist, need * sizeof(int)));
-        s.whist_cap = need;
+        MAPCHK(s.d_whist.ensure(need));
       }
-      hipLaunchKernelGGL(k_extract_key<true>, dim3(nwg), dim3(256), 0, st, s.v, P, nfac, nbuckets, s.d_whist);
-      hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(1024), 0, st, s.d_whist, (int)need, s.v.cnt, -1, 0, -1);
-      hipLaunchKernelGGL(k_extract_scatter_det, dim3(nwg), dim3(256), 0, st, s.v, (const int *)s.d_whist, nfac, nbuckets);
+      hipLaunchKernelGGL(k_extract_key<true>, dim3(nwg), dim3(256), 0, st, s.v, P, nfac, nbuckets, s.d_whist.p);
+      hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(1024), 0, st, s.d_whist.p, (int)need, s.v.cnt, -1, 0, -1);
+      hipLaunchKernelGGL(k_extract_scatter_det, dim3(nwg), dim3(256), 0, st, s.v, (const int *)s.d_whist.p, nfac, nbuckets);
     } else {
       MAPCHK(hipMemsetAsync(s.v.fhist, 0, (size_t)nbuckets * sizeof(int), st));
       hipLaunchKernelGGL(k_extract_key<false>, dim3(nwg), dim3(256), 0, st, s.v, P, nfac, nbuckets, (int *)nullptr);
@@ -648,12 +616,9 @@ inline size_t fix_source_stage_bytes(size_t n) { return ((n * 24 + 255) & ~(size
 inline int map_sort_reserve_n(MapStore &s, hipStream_t st, size_t n, std::string &err) {
   size_t need = 0;
   MAPCHK(sort_pairs_u32(nullptr, need, nullptr, nullptr, nullptr, nullptr, n, 32u, st));
-  if (need + 256 > s.sort_tmp_bytes) {
+  if (need + 256 > s.d_sort_tmp.n) {
     MAPCHK(hipStreamSynchronize(st));
-    if (s.d_sort_tmp) hipFree(s.d_sort_tmp);
-    s.d_sort_tmp = nullptr; s.sort_tmp_bytes = 0;
-    MAPCHK(hipMalloc(&s.d_sort_tmp, need + 256));
-    s.sort_tmp_bytes = need + 256;
+    MAPCHK(s.d_sort_tmp.ensure(need + 256));
   }
   return VBA_OK;
 }
@@ -668,7 +633,7 @@ int map_fix_source_ensure(MapStore &s, hipStream_t st, size_t nodes, size_t fix,
     r = map_hash_alloc(s, nc, st, err);
     if (r) return r;
   }
-  if (fix_source_stage_bytes(n) > s.stage_bytes) MAPCHK(hipStreamSynchronize(st));
+  if (fix_source_stage_bytes(n) > s.d_stage.n) MAPCHK(hipStreamSynchronize(st));
   r = map_stage(s, fix_source_stage_bytes(n), err);
   if (r) return r;
   return map_sort_reserve_n(s, st, n, err);
@@ -686,7 +651,7 @@ int map_cut_voxel_fix_source(MapStore &s, hipStream_t st, int n, const FixSource
   r = map_fix_source_ensure(s, st, (size_t)s.h_cnt[CNT_NODES] + (size_t)n + 64, (size_t)s.h_cnt[CNT_FIX] + (size_t)n, (size_t)n, err);
   if (r) return r;
   const size_t bi = ((size_t)n * 4 + 255) & ~(size_t)255;
-  char *stg = (char *)s.d_stage;
+  char *stg = s.d_stage;
   double *world = (double *)stg; stg += ((size_t)n * 24 + 255) & ~(size_t)255;
   int *srcrow = (int *)stg; stg += bi;
   // the insert kernels take their per-point temporaries from the view: for this call they point into the staging buffer
@@ -707,8 +672,8 @@ int map_cut_voxel_fix_source(MapStore &s, hipStream_t st, int n, const FixSource
   r = map_set_counter(s, st, CNT_WL, 0, err); if (r) return r;
   hipLaunchKernelGGL(k_fix_leaf, dim3(nb), dim3(256), 0, st, s.v, P, base, n);
   {
-    size_t tb = s.sort_tmp_bytes;
-    MAPCHK(sort_pairs_u32(s.d_sort_tmp, tb, s.v.skey_a, s.v.skey_b, s.v.sval_a, s.v.sval_b, (size_t)n, map_key_bits(s), st));
+    size_t tb = s.d_sort_tmp.n;
+    MAPCHK(sort_pairs_u32(s.d_sort_tmp.p, tb, s.v.skey_a, s.v.skey_b, s.v.sval_a, s.v.sval_b, (size_t)n, map_key_bits(s), st));
   }
   hipLaunchKernelGGL(k_fix_heads, dim3(nb), dim3(256), 0, st, s.v, n);
   const dim3 ga(n < 4096 ? n : 4096), ba(64);

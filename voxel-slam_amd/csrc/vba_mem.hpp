@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
+#include <vector>
 
 namespace vba {
 
@@ -51,5 +52,25 @@ struct Mem {
 };
 template <class T> using DevMem = Mem<T, false>;
 template <class T> using PinMem = Mem<T, true>;
+
+// A family of [rows][cap] device arrays that share one capacity (array i: arrs[i].rows rows of arrs[i].elem-byte elements) grows
+// from oldcap to newcap columns as a whole: every new block is allocated and zero-filled and takes the first `used` columns of its
+// old block at the new stride, the stream is synchronised once, then `own` holds the new blocks and the old ones are freed.  After a
+// failure `own` is untouched (the stride its arrays were written with stays the one the caller records) and the new blocks are gone.
+template <class Arr>
+hipError_t grow_family(std::vector<DevMem<char>> &own, const std::vector<Arr> &arrs, size_t oldcap, size_t newcap, size_t used, hipStream_t stream) {
+  std::vector<DevMem<char>> nw(arrs.size());
+  hipError_t e = hipSuccess;
+  for (size_t i = 0; e == hipSuccess && i < arrs.size(); i++) {
+    const size_t elem = arrs[i].elem, bytes = elem * arrs[i].rows * newcap;
+    e = nw[i].ensure(bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(nw[i].p, 0, bytes, stream);
+    if (e == hipSuccess && i < own.size() && own[i].p && used > 0)
+      e = hipMemcpy2DAsync(nw[i].p, newcap * elem, own[i].p, oldcap * elem, used * elem, arrs[i].rows, hipMemcpyDeviceToDevice, stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e == hipSuccess) own.swap(nw);
+  return e;
+}
 
 }  // namespace vba

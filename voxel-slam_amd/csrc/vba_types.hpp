@@ -1,11 +1,10 @@
 // Plain structs that a host-side struct holds by value or that cross a translation-unit boundary: views of device arrays passed to
-// kernels by value, the stores that own them, and the small records kernels and host code share.  No kernel and no device function
-// is defined here, so every unit may include it ("source layout").
+// kernels by value and the small records kernels and host code share (the stores that own the arrays are host code: vba_stores.hpp).
+// No kernel and no device function is defined here, so every unit may include it ("source layout").
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
-#include <functional>
 #include <string>
 #include <vector>
 #include "../../include/voxelba.h"
@@ -93,49 +92,6 @@ enum { FIXCOV_KEEP = 0, FIXCOV_DIAG_F32 = 1, FIXCOV_FULL_F64 = 2, FIXCOV_ZERO = 
 
 struct OdomState { double R[9], t[3], rot_var[9], tsl_var[9]; };
 
-struct DevArr {  // a [rows][cap] device array that can grow its cap keeping [rows][used]
-  void **slot; size_t elem, rows;
-};
-
-struct MapStore {
-  vba_options opt;
-  int rank = 0, n_ranks = 1;
-  MapView v{};
-  bool allocated = false;
-  bool have_var = false;
-  int mp[VBA_MAX_WIN];
-  int npts[VBA_MAX_WIN];
-  int epoch = 1, stamp = 1;
-  unsigned int hcap = 0;
-  int *h_cnt = nullptr;    // pinned
-  // Inserts are enqueued without reading the counters back: the host keeps pessimistic upper bounds (every point may
-  // create a root) and re-reads the true counters only when a bound would exceed a capacity.
-  long long ub_nodes = 0, ub_roots = 0, ub_used = 0;   // ub_used: hash slots that are not EMPTY (live roots + tombstones)
-  bool cnt_stale = false;
-  double *h_pose_ring = nullptr; hipEvent_t pose_ev[8] = {nullptr}; int pose_next = 0;
-  void *d_stage = nullptr; size_t stage_bytes = 0;
-  void *d_sort_tmp = nullptr; size_t sort_tmp_bytes = 0; int sort_tmp_for = 0;   // rocPRIM scratch, sized for max_pts pairs
-  // sharded map: SUM all-reduce of n doubles in HBM over the ranks, stream-ordered (set by the context); d_gc = its 2-double scratch
-  std::function<int(double *, size_t)> allreduce;
-  double *d_gc = nullptr;
-  // per-call plane thresholds (vba_motion_init's relaxed values, VS:624-630): when set they replace opt's in every MapParams
-  bool thr_override = false;
-  double ovr_min_eigen_value = 0.0, ovr_plane_thre[4] = {0.0, 0.0, 0.0, 0.0};
-  // deterministic mode (vba_options::deterministic); d_whist = the per-workgroup bucket histograms of the stable sort
-  bool det = false;
-  int *d_whist = nullptr; size_t whist_cap = 0;
-};
-
-// a fixed insertion whose points and covariances are in HBM already
-struct FixSource {
-  int nseg = 0;
-  const int4 *d_seg = nullptr;        // [nseg] device
-  const double *d_poses = nullptr;    // [.][12] device
-  const double *d_pnt = nullptr;      // source rows [.][3]
-  int cov_kind = FIXCOV_ZERO;          // FIXCOV_* of vba_kernels_map.hpp (not FIXCOV_KEEP: the pool tail is not zeroed here)
-  const void *d_cov = nullptr;        // float [.][3] diagonals (VS:2614-2621) or double [.][9] rows, taken over unrotated (VS:1341-1344)
-};
-
 // ---------------------------------------------------------------- global BA (vba_kernels_gba.hpp, vba_kernels_big.hpp)
 struct GbaView {
   unsigned long long *hkeys; int *hvals; unsigned int hmask;
@@ -156,22 +112,6 @@ struct GbaView {
 };
 
 struct GbaParams { double voxel_size, min_eigen_value, eig_array[4]; int max_layer; };
-
-struct GbaStore {
-  GbaView v{};
-  int cap_pts = 0, cap_hash = 0;
-  double *d_pl = nullptr;      // device copy of the local points [n][3]
-  int *h_cnt = nullptr;        // pinned
-  std::vector<void *> node_bufs;
-
-  void free_nodes() { for (void *p : node_bufs) hipFree(p); node_bufs.clear(); v.cap = 0; }
-  void free_all() {
-    free_nodes();
-    hipFree(v.hkeys); hipFree(v.hvals); hipFree(v.pw); hipFree(v.pframe); hipFree(v.pnode); hipFree(d_pl); hipFree(v.cnt); hipFree(v.poses); hipFree(v.offsets);
-    if (h_cnt) hipHostFree(h_cnt);
-    *this = GbaStore();
-  }
-};
 
 struct BigView {
   int W, V, E, capV, capE;
@@ -202,34 +142,6 @@ struct GbaBigView {
   int *perm;                   // points ordered by root voxel (the accumulation pass walks them in this order: see k_gbab_accum)
   unsigned int *skey; int *sval;   // sort input: root id (all ones = no root) / point index
   int *cnt; double *poses; int *offsets;
-};
-
-struct BigStore {
-  int last_cap = 1 << 17;
-  BigView b{};
-  GbaBigView g{};
-  // Device memory comes from an arena of large chunks that survives across builds (reset() rewinds it): hipMalloc / hipFree
-  // of ~40 buffers per build, some of them 10^8 bytes, cost more than the kernels of a top-level window.
-  struct Chunk { char *base; size_t size, used; };
-  std::vector<Chunk> chunks;
-  hipError_t arena(void **p, size_t bytes) {
-    bytes = (bytes ? bytes : 8) + 255 & ~(size_t)255;
-    for (Chunk &ck : chunks)
-      if (ck.size - ck.used >= bytes) { *p = ck.base + ck.used; ck.used += bytes; return hipSuccess; }
-    Chunk ck{nullptr, bytes > ((size_t)256 << 20) ? bytes : ((size_t)256 << 20), 0};
-    hipError_t e = hipMalloc((void **)&ck.base, ck.size);
-    if (e != hipSuccess) return e;
-    ck.used = bytes; *p = ck.base;
-    chunks.push_back(ck);
-    return hipSuccess;
-  }
-  void reset() { for (Chunk &ck : chunks) ck.used = 0; b = BigView(); g = GbaBigView(); }
-  int *h_cnt = nullptr;
-  int *d_vcnt = nullptr, *d_fill = nullptr;
-  double *d_Ab = nullptr, *d_Tb = nullptr; int *d_ord = nullptr;   // dense solver (allocated by big_build)
-  double *d_vec = nullptr;                                          // [3 n + 6 W W]: diag(H) | g copy | dxi | cross-block diagonals
-  int NP = 0, ld = 0;
-  void release() { for (Chunk &ck : chunks) hipFree(ck.base); chunks.clear(); if (h_cnt) hipHostFree(h_cnt); h_cnt = nullptr; b = BigView(); g = GbaBigView(); }
 };
 
 // ---------------------------------------------------------------- scan pre-processing (vba_kernels_scan.hpp)

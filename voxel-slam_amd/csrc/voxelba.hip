@@ -520,8 +520,6 @@ void vba_destroy(vba_ctx *c) {
   if (c->stream) hipStreamSynchronize(c->stream);
   if (c->comm && c->own_comm) rccl_api().CommDestroy(c->comm);      // (a communicator exists only if the API resolved)
   map_free(c->map);
-  c->gba.free_all();
-  c->big.release();
   for (vba_ctx *w : c->hba_workers) vba_destroy(w);
   c->hba_workers.clear();
   for (hipEvent_t e : c->exp_ev) if (e) hipEventDestroy(e);
@@ -1294,13 +1292,13 @@ extern "C++" {
 namespace {
 struct DbgBufs {                      // device buffers of one call; drained and freed on every exit path
   hipStream_t st;
-  std::vector<void *> p;
+  std::vector<DevMem<char>> p;
   explicit DbgBufs(hipStream_t s) : st(s) {}
-  ~DbgBufs() { if (!p.empty()) hipStreamSynchronize(st); for (void *q : p) hipFree(q); }
+  ~DbgBufs() { if (!p.empty()) hipStreamSynchronize(st); }      // the blocks free themselves after the drain
   template <typename T> hipError_t alloc(T **out, size_t count) {
-    void *q = nullptr;
-    const hipError_t e = hipMalloc(&q, (count ? count : 1) * sizeof(T));
-    if (e == hipSuccess) { p.push_back(q); *out = (T *)q; }
+    DevMem<char> q;
+    const hipError_t e = q.ensure((count ? count : 1) * sizeof(T));
+    if (e == hipSuccess) { *out = (T *)q.p; p.push_back(std::move(q)); }
     return e;
   }
 };
