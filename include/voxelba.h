@@ -549,6 +549,39 @@ int vba_debug_li_imu(vba_ctx *ctx, int W, int gravity, int flags, const double *
 int vba_debug_odom_sums(vba_ctx *ctx, int kind, int n, const double *pnt_body, const double *var_body, const double *state,
                         const double *cov, int slices, double *partial, double *sums, unsigned long long *cand, double *planes,
                         int *slices_used);
+/* Diagnostic: the passes of the any-window path (csrc/vba_kernels_big.hpp) one at a time on the context's sparse store, the store that
+ * vba_hba_add_edge builds and optimises whenever wdsize != win_size (tests/test_gpu_big.py).  The store is CSR over voxels, one entry
+ * per occupied (voxel, frame).  Every call drains the stream; none touches the context's LM state, its dense factor store or its map.
+ *   vba_debug_big_load      replaces the store by the caller's: W frames (2..1024, the range of VBA_SOLVE_DENSE), V voxels, vptr[V + 1],
+ *                           efr[E] (frame of every entry), ecl[E][10] (body cluster sums Pxx Pxy Pxz Pyy Pyz Pzz vx vy vz N), and per voxel
+ *                           eig_val[V][3], eig_vec[V][9] (row-major, columns = eigenvectors), pcr_add[V][10].  Sizing and allocation are
+ *                           the code big_build ends with; evox is the CSR row of each entry, eidx comes from k_big_eidx.  V = 0 is an
+ *                           empty store (only vptr is read).  VBA_ERR_BAD_ARG with nothing launched and the previous store intact: a NULL
+ *                           pointer, W out of range, V < 0, vptr not starting at 0 or not increasing (a voxel without an entry would make
+ *                           the residual pass divide by N = 0; the build cannot produce one), efr not strictly increasing within a voxel
+ *                           or outside [0, W), a non-finite input.
+ *   vba_debug_big_build     big_build on the caller's clouds with the arguments of vba_hba_add_edge (points staged as that call stages
+ *                           them); *V, *E = the size of the store it left.
+ *   vba_debug_big_size      W, V, E of the current store (zeros when there is none).
+ *   vba_debug_big_read      the store as it stands: vptr[V + 1], efr[E], evox[E], eidx[V][W] (entry of (voxel, frame) or -1), ecl[E][10],
+ *                           eig_val, eig_vec, pcr_add as above.  Any pointer may be NULL.  After a residual pass the last three are what
+ *                           that pass stored.
+ *   vba_debug_big_hessian   big_hessian at poses[W][12] (R row-major | p): H[(6W)^2], g[6W], *r, and blockdiag[W][W][6], the output of
+ *                           big_block_diagonals (the six diagonal entries of every 6 x 6 block; all vba_hba_add_edge reads of H).  slices:
+ *                           voxel slices of k_big_syrk, 0 = the pass's own choice (what vba_hba_add_edge runs), k >= 1 = k; at most one
+ *                           per chunk of 16 voxels either way.
+ *   vba_debug_big_residual  big_residual at poses: *r; the eigen-data and sums it stored are read through vba_debug_big_read.
+ * Read and the two passes return VBA_ERR_BAD_ARG without a store (no load or build yet); the passes also for a NULL pointer, a negative
+ * slice count or non-finite poses.  All: VBA_ERR_UNSUPPORTED on a sharded context. */
+int vba_debug_big_load(vba_ctx *ctx, int W, int V, const int *vptr, const int *efr, const double *ecl, const double *eig_val,
+                       const double *eig_vec, const double *pcr_add);
+int vba_debug_big_build(vba_ctx *ctx, int W, const int *offsets, const double *pnt_local, const double *poses, double gba_voxel_size,
+                        double gba_min_eigen_value, const double *gba_eigen_value_array, int *V, int *E);
+int vba_debug_big_size(vba_ctx *ctx, int *W, int *V, int *E);
+int vba_debug_big_read(vba_ctx *ctx, int *vptr, int *efr, int *evox, int *eidx, double *ecl, double *eig_val, double *eig_vec,
+                       double *pcr_add);
+int vba_debug_big_hessian(vba_ctx *ctx, const double *poses, int slices, double *H, double *g, double *r, double *blockdiag);
+int vba_debug_big_residual(vba_ctx *ctx, const double *poses, double *r);
 
 /* ------------------------------------------------------------------------------------------------
  * Session-store formats either side of the path.  Host only, no context.

@@ -5,6 +5,9 @@
   * the map's leaf fit (k_recut_leaf) and its refit in margi, on designed clouds (grid and disc patches, arcs, poles, blobs, tilted
     planes) 10-100 m from the origin;
   * the GBA build (k_gba_decide) on the same clouds split over the keyframes.
+Two further sites, those of the any-window path, are covered in tests/test_gpu_big.py with the same corpus, clouds and bars: the residual
+pass k_big_residual (test_eig3_corpus_through_the_residual_pass, and the eigen-data of every test_residual_pass case) and the hashed
+build's k_gbab_decide (test_eig3_designed_clouds_through_the_build).
 Where the device forms cov from sums in f64 the bars are scaled by the cancellation scale m2 = max|P/N| instead of |A|_2."""
 import numpy as np
 import pytest

@@ -31,6 +31,7 @@ EXPORTS = [
     "vba_set_allreduce", "vba_rccl_get_unique_id", "vba_rccl_init", "vba_set_rccl_comm", "vba_shard_owner", "vba_set_shard",
     "vba_timing_enable", "vba_timing_calibration_read", "vba_timing_select", "vba_timing_sample_every", "vba_timing_launch_hessian", "vba_timing_null_span", "vba_timing_reset", "vba_timing_get",
     "vba_lm_begin", "vba_lm_refresh_eigen", "vba_lm_iterate", "vba_lm_end", "vba_debug_solve", "vba_debug_li_imu", "vba_debug_odom_sums",
+    "vba_debug_big_load", "vba_debug_big_build", "vba_debug_big_size", "vba_debug_big_read", "vba_debug_big_hessian", "vba_debug_big_residual",
     "vba_io_save_pcd", "vba_io_load_pcd", "vba_io_save_pose", "vba_io_read_lidarstate",
     "vba_motion_init", "vba_init_imu_poses", "vba_init_align_gravity",
     "vba_btc_default_config", "vba_btc_create", "vba_btc_destroy", "vba_btc_set_skip_near_num", "vba_btc_push_plane_cloud",
@@ -1287,6 +1288,62 @@ class Context:
                                           C.c_double(gba_voxel_size), C.c_double(gba_min_eigen_value), _p(_c(gba_eig)), C.c_int(total_max_iter),
                                           C.c_int(wdsize), C.c_int(mgsize), _p(e1), C.c_int(cap1), C.byref(n1), _p(e2), C.c_int(cap2), C.byref(n2)))
         return e1[:n1.value].copy(), e2[:n2.value].copy()
+
+    # ---- diagnostic entries of the any-window path (vba_debug_big_*; tests/test_gpu_big.py)
+    @staticmethod
+    def _i32(a):
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    @staticmethod
+    def _pi(a):
+        return a.ctypes.data_as(C.POINTER(C.c_int)) if a is not None else None
+
+    def debug_big_load(self, W, vptr, efr, ecl, eig_val, eig_vec, pcr_add, raw=False):
+        """vba_debug_big_load: the caller's sparse store (CSR vptr [V+1], efr [E], ecl [E][10]; eig_val [V][3], eig_vec [V][9],
+        pcr_add [V][10]) becomes the context's.  raw=True returns the status instead of raising."""
+        vptr = self._i32(vptr); efr = self._i32(efr)
+        a = [_c(x) for x in (ecl, eig_val, eig_vec, pcr_add)]
+        st = self.lib.vba_debug_big_load(self.h, C.c_int(W), C.c_int(len(vptr) - 1), self._pi(vptr), self._pi(efr), *[_p(x) for x in a])
+        if raw:
+            return st
+        self._chk(st)
+
+    def debug_big_build(self, clouds, poses, gba_voxel_size, gba_min_eigen_value, gba_eig):
+        """vba_debug_big_build: big_build on the clouds, as vba_hba_add_edge runs it for a window of another size -> (V, E)"""
+        off, pnt = self._ragged(clouds)
+        V = C.c_int(0); E = C.c_int(0)
+        self._chk(self.lib.vba_debug_big_build(self.h, C.c_int(len(clouds)), self._pi(off), _p(pnt), _p(_c(poses)), C.c_double(gba_voxel_size),
+                                               C.c_double(gba_min_eigen_value), _p(_c(gba_eig)), C.byref(V), C.byref(E)))
+        return V.value, E.value
+
+    def debug_big_size(self):
+        W = C.c_int(0); V = C.c_int(0); E = C.c_int(0)
+        self._chk(self.lib.vba_debug_big_size(self.h, C.byref(W), C.byref(V), C.byref(E)))
+        return W.value, V.value, E.value
+
+    def debug_big_read(self):
+        """vba_debug_big_read -> dict(W, vptr, efr, evox, eidx [V][W], ecl [E][10], eig_val, eig_vec, pcr_add) of the current store"""
+        W, V, E = self.debug_big_size()
+        vptr = np.zeros(V + 1, dtype=np.int32); efr = np.zeros(E, dtype=np.int32); evox = np.zeros(E, dtype=np.int32)
+        eidx = np.zeros((V, W), dtype=np.int32); ecl = np.zeros((E, 10)); ev = np.zeros((V, 3)); evec = np.zeros((V, 9)); pa = np.zeros((V, 10))
+        self._chk(self.lib.vba_debug_big_read(self.h, self._pi(vptr), self._pi(efr), self._pi(evox), self._pi(eidx), _p(ecl), _p(ev), _p(evec), _p(pa)))
+        return dict(W=W, vptr=vptr, efr=efr, evox=evox, eidx=eidx, ecl=ecl, eig_val=ev, eig_vec=evec, pcr_add=pa)
+
+    def debug_big_hessian(self, poses, slices=0):
+        """vba_debug_big_hessian: the Hessian pass of the any-window path at poses -> (H [6W][6W], g [6W], r, blockdiag [W][W][6])"""
+        W = self.debug_big_size()[0]
+        poses = _c(poses); n = 6 * W
+        assert poses.size == 12 * W
+        H = np.full((n, n), np.nan); g = np.full(n, np.nan); r = C.c_double(np.nan); bd = np.full((W, W, 6), np.nan)
+        self._chk(self.lib.vba_debug_big_hessian(self.h, _p(poses), C.c_int(slices), _p(H), _p(g), C.byref(r), _p(bd)))
+        return H, g, r.value, bd
+
+    def debug_big_residual(self, poses):
+        """vba_debug_big_residual: the residual pass at poses (it rewrites the store's eigen-data and sums) -> r"""
+        poses = _c(poses); r = C.c_double(np.nan)
+        assert poses.size == 12 * self.debug_big_size()[0]
+        self._chk(self.lib.vba_debug_big_residual(self.h, _p(poses), C.byref(r)))
+        return r.value
 
     def pgo_optimize(self, poses, edges, priors, n_updates=6, relin_threshold=0.01):
         """build_graph + ISAM2 update() x n_updates + calculateEstimate() (VS:2078-2156, VS:2550-2561, VS:2769-2777):

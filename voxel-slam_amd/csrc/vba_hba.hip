@@ -117,6 +117,44 @@ inline int gba_build(GbaStore &s, hipStream_t st, int W, const int *offsets, con
 // ---------------------------------------------------------------- host side of vba_kernels_big.hpp: the any-window sparse path
 #define BIGCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return VBA_ERR_HIP; } } while (0)
 
+// The sparse factor store of W frames in the arena, in three steps with the producer's launches between them (big_build: the octree
+// kernels; vba_debug_big_load: the caller's arrays).  1: the per-voxel arrays, H / g / r, the dense solver's buffers and NP / ld; vptr and
+// d_fill are cleared.  2: the per-entry arrays, once E is known.  3: the (voxel, frame) -> entry map from evox / efr (k_big_eidx).
+inline int big_store_voxels(BigStore &s, hipStream_t st, int W, int V, std::string &err) {
+  auto al = [&](void **p, size_t bytes) { return s.arena(p, bytes); };
+  BigView &b = s.b;
+  b.W = W; b.V = V; b.capV = V > 0 ? V : 1;
+  BIGCHK(al((void **)&b.vptr, (size_t)(V + 1) * 4)); BIGCHK(al((void **)&s.d_vcnt, (size_t)b.capV * 4)); BIGCHK(al((void **)&s.d_fill, (size_t)b.capV * 4));
+  BIGCHK(al((void **)&b.eval, (size_t)b.capV * 3 * 8)); BIGCHK(al((void **)&b.evec, (size_t)b.capV * 9 * 8)); BIGCHK(al((void **)&b.pcr, (size_t)b.capV * 10 * 8));
+  BIGCHK(al((void **)&b.poses, (size_t)W * 12 * 8));
+  const size_t n6 = (size_t)6 * W;
+  BIGCHK(al((void **)&b.H, n6 * n6 * 8)); BIGCHK(al((void **)&b.g, n6 * 8)); BIGCHK(al((void **)&b.r, 8));
+
+  s.NP = (int)((n6 + 7) / 8 * 8); s.ld = (int)((s.NP + 63) / 64 * 64);
+  BIGCHK(al((void **)&s.d_Ab, (size_t)(s.NP + 1) * s.ld * 8)); BIGCHK(al((void **)&s.d_Tb, (size_t)(s.NP + 1) * 8 * 8)); BIGCHK(al((void **)&s.d_ord, n6 * 4)); BIGCHK(al((void **)&s.d_vec, ((size_t)3 * n6 + (size_t)6 * W * W) * 8));
+  BIGCHK(hipMemsetAsync(s.d_fill, 0, (size_t)b.capV * 4, st));
+  BIGCHK(hipMemsetAsync(b.vptr, 0, (size_t)(V + 1) * 4, st));
+  return VBA_OK;
+}
+inline int big_store_entries(BigStore &s, int E, std::string &err) {
+  auto al = [&](void **p, size_t bytes) { return s.arena(p, bytes); };
+  BigView &b = s.b;
+  b.E = E; b.capE = E > 0 ? E : 1;
+  BIGCHK(al((void **)&b.efr, (size_t)b.capE * 4)); BIGCHK(al((void **)&b.evox, (size_t)b.capE * 4));
+  BIGCHK(al((void **)&b.ecl, (size_t)b.capE * 10 * 8)); BIGCHK(al((void **)&b.gv, (size_t)b.capE * 18 * 8)); BIGCHK(al((void **)&b.es, (size_t)b.capE * 27 * 8));
+  return VBA_OK;
+}
+inline int big_store_eidx(BigStore &s, hipStream_t st, std::string &err) {
+  BigView &b = s.b;
+  BIGCHK(s.arena((void **)&b.eidx, (size_t)b.capV * b.W * 4));
+  BIGCHK(hipMemsetAsync(b.eidx, 0xFF, (size_t)b.capV * b.W * 4, st));
+  if (b.V > 0 && b.E > 0) {
+    hipLaunchKernelGGL(k_big_eidx, dim3((b.E + 255) / 256), dim3(256), 0, st, b);
+    BIGCHK(hipGetLastError());
+  }
+  return VBA_OK;
+}
+
 // Builds the octree of `W` keyframes and the sparse factor store (everything is re-allocated per call: the top-level BA
 // runs once per loop closure).  pl: device pointer to the local points [n][3].
 inline int big_build(BigStore &s, hipStream_t st, int W, const int *offsets, const double *d_pl, const double *poses, const GbaParams &P, std::string &err) {
@@ -190,17 +228,7 @@ inline int big_build(BigStore &s, hipStream_t st, int W, const int *offsets, con
   // sparse factor store
   BigView &b = s.b;
   const int V = s.h_cnt[GCNT_FACTORS];
-  b.W = W; b.V = V; b.capV = V > 0 ? V : 1;
-  BIGCHK(al((void **)&b.vptr, (size_t)(V + 1) * 4)); BIGCHK(al((void **)&s.d_vcnt, (size_t)b.capV * 4)); BIGCHK(al((void **)&s.d_fill, (size_t)b.capV * 4));
-  BIGCHK(al((void **)&b.eval, (size_t)b.capV * 3 * 8)); BIGCHK(al((void **)&b.evec, (size_t)b.capV * 9 * 8)); BIGCHK(al((void **)&b.pcr, (size_t)b.capV * 10 * 8));
-  BIGCHK(al((void **)&b.poses, (size_t)W * 12 * 8));
-  const size_t n6 = (size_t)6 * W;
-  BIGCHK(al((void **)&b.H, n6 * n6 * 8)); BIGCHK(al((void **)&b.g, n6 * 8)); BIGCHK(al((void **)&b.r, 8));
-
-  s.NP = (int)((n6 + 7) / 8 * 8); s.ld = (int)((s.NP + 63) / 64 * 64);
-  BIGCHK(al((void **)&s.d_Ab, (size_t)(s.NP + 1) * s.ld * 8)); BIGCHK(al((void **)&s.d_Tb, (size_t)(s.NP + 1) * 8 * 8)); BIGCHK(al((void **)&s.d_ord, n6 * 4)); BIGCHK(al((void **)&s.d_vec, ((size_t)3 * n6 + (size_t)6 * W * W) * 8));
-  BIGCHK(hipMemsetAsync(s.d_fill, 0, (size_t)b.capV * 4, st));
-  BIGCHK(hipMemsetAsync(b.vptr, 0, (size_t)(V + 1) * 4, st));
+  { int r = big_store_voxels(s, st, W, V, err); if (r) return r; }
   int E = 0;
   if (V > 0) {
     const int nn = s.h_cnt[GCNT_NODES] < g.cap ? s.h_cnt[GCNT_NODES] : g.cap;
@@ -210,27 +238,23 @@ inline int big_build(BigStore &s, hipStream_t st, int W, const int *offsets, con
     BIGCHK(hipMemcpyAsync(&E, b.vptr + V, 4, hipMemcpyDeviceToHost, st));
     BIGCHK(hipStreamSynchronize(st));
   }
-  b.E = E; b.capE = E > 0 ? E : 1;
-  BIGCHK(al((void **)&b.efr, (size_t)b.capE * 4)); BIGCHK(al((void **)&b.evox, (size_t)b.capE * 4));
-  BIGCHK(al((void **)&b.ecl, (size_t)b.capE * 10 * 8)); BIGCHK(al((void **)&b.gv, (size_t)b.capE * 18 * 8)); BIGCHK(al((void **)&b.es, (size_t)b.capE * 27 * 8));
+  { int r = big_store_entries(s, E, err); if (r) return r; }
   if (V > 0) {
     const int nn = s.h_cnt[GCNT_NODES] < g.cap ? s.h_cnt[GCNT_NODES] : g.cap;
-    hipLaunchKernelGGL(k_gbab_fill, dim3((ecap + 255) / 256), bk, 0, st, g, b, s.d_fill);
+    BigView bt = b;                                  // table order into scratch (es: 27 rows of capE doubles), frame order into the store
+    bt.ecl = b.es; bt.efr = (int *)(b.es + (size_t)10 * b.capE);
+    hipLaunchKernelGGL(k_gbab_fill, dim3((ecap + 255) / 256), bk, 0, st, g, bt, s.d_fill);
+    if (E > 0) hipLaunchKernelGGL(k_gbab_order, dim3((E + 255) / 256), bk, 0, st, b, (const int *)bt.efr, (const double *)bt.ecl);
     hipLaunchKernelGGL(k_gbab_voxels, dim3((nn + 255) / 256), bk, 0, st, g, b);
     BIGCHK(hipGetLastError());
   }
-  BIGCHK(al((void **)&b.eidx, (size_t)b.capV * W * 4));
-  BIGCHK(hipMemsetAsync(b.eidx, 0xFF, (size_t)b.capV * W * 4, st));
-  if (V > 0 && E > 0) {
-    hipLaunchKernelGGL(k_big_eidx, dim3((E + 255) / 256), bk, 0, st, b);
-    BIGCHK(hipGetLastError());
-  }
-  return VBA_OK;
+  return big_store_eidx(s, st, err);
 }
 
 // divide_thread (VM:347-389): H, g, r at `poses` on the host side buffers (full layout)
 // Hessian pass on the sparse store: H (n x n) and g stay in HBM (the solver reads them there); the host gets diag(H), g and r.
-inline int big_hessian(BigStore &s, hipStream_t st, const double *poses, double *hdiag, double *gvec, double *r, std::string &err) {
+// slices: voxel slices of the SYRK, 0 = chosen here (about 2048 workgroups), k >= 1 = k; either way at most one per chunk.
+inline int big_hessian(BigStore &s, hipStream_t st, const double *poses, double *hdiag, double *gvec, double *r, std::string &err, int slices) {
   BigView &b = s.b;
   const size_t n6 = (size_t)6 * b.W;
   BIGCHK(hipMemcpyAsync(b.poses, poses, (size_t)b.W * 12 * 8, hipMemcpyHostToDevice, st));
@@ -238,7 +262,7 @@ inline int big_hessian(BigStore &s, hipStream_t st, const double *poses, double 
   if (b.E > 0) {
     hipLaunchKernelGGL(k_big_slot, dim3((b.E + 127) / 128), dim3(128), 0, st, b);
     const int nt = (b.W + BIG_TF - 1) / BIG_TF, npair = nt * (nt + 1) / 2, nchunk = (b.V + BIG_VC - 1) / BIG_VC;
-    int nslice = (2048 + npair - 1) / npair;
+    int nslice = slices >= 1 ? slices : (2048 + npair - 1) / npair;
     if (nslice > nchunk) nslice = nchunk;
     if (nslice < 1) nslice = 1;
     hipLaunchKernelGGL(k_big_syrk, dim3(npair, nslice), dim3(256), 0, st, b, nt, nslice);
@@ -378,7 +402,7 @@ static int big_damping_iter(vba_ctx *c, int W, double *poses, std::vector<double
   c->trace.clear();
   for (int it = 0; it < max_iter; it++) {
     if (is_calc_hess) {
-      int st = big_hessian(S, c->stream, x.data(), hd.data(), JacT.data(), &residual1, c->err);   // *hess = Hess (VM:446) stays on the device
+      int st = big_hessian(S, c->stream, x.data(), hd.data(), JacT.data(), &residual1, c->err, 0);   // *hess = Hess (VM:446) stays on the device
       if (st) return st;
       for (int r = 0; r < 6; r++) { hd[r] = 1.0; JacT[r] = 0.0; }     // gauge VM:452-455 (k_bigl_setup applies it to the matrix)
     }
@@ -422,6 +446,14 @@ static int big_damping_iter(vba_ctx *c, int W, double *poses, std::vector<double
   return big_block_diagonals(S, c->stream, hdiag6_out.data(), c->err);   // b.H still holds the last evaluated Hessian (a rejected step does not recompute it)
 }
 
+// the keyframe clouds of an HBA_add_edge call in HBM: the two halves of d_refpts, the cloud (*d_pl) and its reference (*d_ref)
+static int hba_stage_points(vba_ctx *c, int n, const double *pnt_local, double **d_pl, double **d_ref) {
+  if ((size_t)n * 3 > c->d_refpts.n / 2) HIPCHK(c, c->d_refpts.ensure(2 * ((size_t)n * 3 + 3072)));
+  *d_pl = c->d_refpts; *d_ref = c->d_refpts + c->d_refpts.n / 2;
+  if (n > 0) HIPCHK(c, hipMemcpyAsync(*d_pl, pnt_local, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
+  return VBA_OK;
+}
+
 int vba_hba_add_edge(vba_ctx *c, int wdsize, const int *offsets, const double *pnt_local, double *poses, double gba_voxel_size,
                      double gba_min_eigen_value, const double *gba_eigen_value_array, int max_iter, int thread_num, double *edges_out, int *n_edges,
                      double *cloud_out, int *cloud_count, int *n_cloud, double *resis_log, int *n_log) {
@@ -445,9 +477,9 @@ int vba_hba_add_edge(vba_ctx *c, int wdsize, const int *offsets, const double *p
   double t_mark = want_times ? now() : 0.0;
   auto lap = [&](int k) { if (want_times) { hipStreamSynchronize(c->stream); const double t = now(); t_ph[k] += t - t_mark; t_mark = t; } };
   // the keyframe clouds stay in HBM for the whole call (every outer iteration re-cuts them with the current poses)
-  if ((size_t)n * 3 > c->d_refpts.n / 2) HIPCHK(c, c->d_refpts.ensure(2 * ((size_t)n * 3 + 3072)));      // two halves: the cloud, its reference
-  double *d_pl = c->d_refpts, *d_ref = c->d_refpts + c->d_refpts.n / 2;
-  if (n > 0) HIPCHK(c, hipMemcpyAsync(d_pl, pnt_local, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
+  double *d_pl = nullptr, *d_ref = nullptr;
+  st = hba_stage_points(c, n, pnt_local, &d_pl, &d_ref);
+  if (st) return st;
   GbaParams P = gba_params(c, gba_voxel_size, gba_min_eigen_value, gba_eigen_value_array);
   std::vector<double> hess(big ? 0 : (size_t)n6 * n6, 0.0), hd6;      // the any-window path keeps *hess in HBM and returns its block diagonals
   lap(0);
@@ -525,6 +557,156 @@ int vba_hba_add_edge(vba_ctx *c, int wdsize, const int *offsets, const double *p
   if (want_times)
     std::fprintf(stderr, "[hba_add_edge W=%d n=%d] upload %.0f  build %.0f  LM %.0f  edges %.0f  cloud %.0f us\n", W, n, t_ph[0], t_ph[1], t_ph[2], t_ph[3], t_ph[4]);
   return VBA_OK;
+}
+
+// ---------------------------------------------------------------- diagnostic entries of the any-window path (tests/test_gpu_big.py)
+static bool big_finite(const double *a, size_t n) {
+  for (size_t i = 0; i < n; i++) if (!std::isfinite(a[i])) return false;
+  return true;
+}
+static int big_dbg_ctx(vba_ctx *c, const char *who) {
+  if (!c) return VBA_ERR_BAD_ARG;
+  if (c->n_ranks > 1) { c->set_error(std::string(who) + " runs the any-window path of one device: unsharded contexts only"); return VBA_ERR_UNSUPPORTED; }
+  return VBA_OK;
+}
+static bool big_has_store(const vba_ctx *c) { return c->big.b.W >= 2 && c->big.b.H != nullptr && c->big.b.eidx != nullptr; }
+
+int vba_debug_big_load(vba_ctx *c, int W, int V, const int *vptr, const int *efr, const double *ecl, const double *eig_val, const double *eig_vec,
+                       const double *pcr_add) {
+  int st = big_dbg_ctx(c, "vba_debug_big_load");
+  if (st) return st;
+  if (W < 2 || W > 1024 || V < 0 || !vptr || vptr[0] != 0) return VBA_ERR_BAD_ARG;
+  for (int v = 0; v < V; v++) if (vptr[v + 1] <= vptr[v]) return VBA_ERR_BAD_ARG;        // non-decreasing, and no voxel without an entry (N = 0)
+  const int E = vptr[V];
+  if (V > 0 && (!efr || !ecl || !eig_val || !eig_vec || !pcr_add)) return VBA_ERR_BAD_ARG;
+  for (int v = 0; v < V; v++)
+    for (int e = vptr[v]; e < vptr[v + 1]; e++)
+      if (efr[e] < 0 || efr[e] >= W || (e > vptr[v] && efr[e] <= efr[e - 1])) return VBA_ERR_BAD_ARG;
+  if (V > 0 && (!big_finite(ecl, (size_t)E * 10) || !big_finite(eig_val, (size_t)V * 3) || !big_finite(eig_vec, (size_t)V * 9) || !big_finite(pcr_add, (size_t)V * 10)))
+    return VBA_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  BigStore &s = c->big;
+  HIPCHK(c, hipStreamSynchronize(c->stream));        // nothing of the previous store is in flight when the arena is rewound
+  s.reset();
+  st = big_store_voxels(s, c->stream, W, V, c->err);
+  if (st) return st;
+  st = big_store_entries(s, E, c->err);
+  if (st) return st;
+  BigView &b = s.b;
+  if (V > 0) {
+    // the arrays of the view are SoA with strides capV / capE; evox is the CSR row of every entry
+    const size_t cv = (size_t)b.capV, ce = (size_t)b.capE;
+    std::vector<double> hv(22 * cv), he(10 * ce);
+    std::vector<int> hx(ce);
+    for (int v = 0; v < V; v++) {
+      for (int k = 0; k < 3; k++) hv[(size_t)k * cv + v] = eig_val[3 * (size_t)v + k];
+      for (int k = 0; k < 9; k++) hv[(size_t)(3 + k) * cv + v] = eig_vec[9 * (size_t)v + k];
+      for (int k = 0; k < 10; k++) hv[(size_t)(12 + k) * cv + v] = pcr_add[10 * (size_t)v + k];
+      for (int e = vptr[v]; e < vptr[v + 1]; e++) hx[e] = v;
+    }
+    for (int e = 0; e < E; e++)
+      for (int k = 0; k < 10; k++) he[(size_t)k * ce + e] = ecl[10 * (size_t)e + k];
+    HIPCHK(c, hipMemcpyAsync(b.vptr, vptr, (size_t)(V + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.eval, hv.data(), 3 * cv * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.evec, hv.data() + 3 * cv, 9 * cv * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.pcr, hv.data() + 12 * cv, 10 * cv * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.efr, efr, (size_t)E * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.evox, hx.data(), (size_t)E * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.ecl, he.data(), 10 * ce * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // the staging vectors are host temporaries
+  }
+  st = big_store_eidx(s, c->stream, c->err);
+  if (st) return st;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VBA_OK;
+}
+
+int vba_debug_big_build(vba_ctx *c, int W, const int *offsets, const double *pnt_local, const double *poses, double gba_voxel_size,
+                        double gba_min_eigen_value, const double *gba_eigen_value_array, int *V, int *E) {
+  int st = big_dbg_ctx(c, "vba_debug_big_build");
+  if (st) return st;
+  if (W < 2 || W > 1024 || !offsets || !poses || !gba_eigen_value_array || !V || !E || offsets[0] != 0) return VBA_ERR_BAD_ARG;
+  for (int i = 0; i < W; i++) if (offsets[i + 1] < offsets[i]) return VBA_ERR_BAD_ARG;
+  const int n = offsets[W];
+  if (n > 0 && !pnt_local) return VBA_ERR_BAD_ARG;
+  if (!big_finite(poses, (size_t)W * 12) || !big_finite(gba_eigen_value_array, 4) || !std::isfinite(gba_voxel_size) || !(gba_voxel_size > 0.0) ||
+      !std::isfinite(gba_min_eigen_value))
+    return VBA_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  double *d_pl = nullptr, *d_ref = nullptr;
+  st = hba_stage_points(c, n, pnt_local, &d_pl, &d_ref);
+  if (st) return st;
+  st = big_build(c->big, c->stream, W, offsets, d_pl, poses, gba_params(c, gba_voxel_size, gba_min_eigen_value, gba_eigen_value_array), c->err);
+  if (st) return st;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *V = c->big.b.V; *E = c->big.b.E;
+  return VBA_OK;
+}
+
+int vba_debug_big_size(vba_ctx *c, int *W, int *V, int *E) {
+  int st = big_dbg_ctx(c, "vba_debug_big_size");
+  if (st) return st;
+  if (!W || !V || !E) return VBA_ERR_BAD_ARG;
+  const bool has = big_has_store(c);
+  *W = has ? c->big.b.W : 0; *V = has ? c->big.b.V : 0; *E = has ? c->big.b.E : 0;
+  return VBA_OK;
+}
+
+int vba_debug_big_read(vba_ctx *c, int *vptr, int *efr, int *evox, int *eidx, double *ecl, double *eig_val, double *eig_vec, double *pcr_add) {
+  int st = big_dbg_ctx(c, "vba_debug_big_read");
+  if (st) return st;
+  if (!big_has_store(c)) return VBA_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  const BigView &b = c->big.b;
+  const int V = b.V, E = b.E, W = b.W;
+  const size_t cv = (size_t)b.capV, ce = (size_t)b.capE;
+  std::vector<double> hv(22 * cv), he(10 * ce);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (vptr) HIPCHK(c, hipMemcpy(vptr, b.vptr, (size_t)(V + 1) * 4, hipMemcpyDeviceToHost));
+  if (efr && E > 0) HIPCHK(c, hipMemcpy(efr, b.efr, (size_t)E * 4, hipMemcpyDeviceToHost));
+  if (evox && E > 0) HIPCHK(c, hipMemcpy(evox, b.evox, (size_t)E * 4, hipMemcpyDeviceToHost));
+  if (eidx && V > 0) HIPCHK(c, hipMemcpy(eidx, b.eidx, (size_t)V * W * 4, hipMemcpyDeviceToHost));
+  if (ecl && E > 0) {
+    HIPCHK(c, hipMemcpy(he.data(), b.ecl, 10 * ce * 8, hipMemcpyDeviceToHost));
+    for (int e = 0; e < E; e++)
+      for (int k = 0; k < 10; k++) ecl[10 * (size_t)e + k] = he[(size_t)k * ce + e];
+  }
+  if (V > 0 && (eig_val || eig_vec || pcr_add)) {
+    HIPCHK(c, hipMemcpy(hv.data(), b.eval, 3 * cv * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hv.data() + 3 * cv, b.evec, 9 * cv * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hv.data() + 12 * cv, b.pcr, 10 * cv * 8, hipMemcpyDeviceToHost));
+    for (int v = 0; v < V; v++) {
+      if (eig_val) for (int k = 0; k < 3; k++) eig_val[3 * (size_t)v + k] = hv[(size_t)k * cv + v];
+      if (eig_vec) for (int k = 0; k < 9; k++) eig_vec[9 * (size_t)v + k] = hv[(size_t)(3 + k) * cv + v];
+      if (pcr_add) for (int k = 0; k < 10; k++) pcr_add[10 * (size_t)v + k] = hv[(size_t)(12 + k) * cv + v];
+    }
+  }
+  return VBA_OK;
+}
+
+int vba_debug_big_hessian(vba_ctx *c, const double *poses, int slices, double *H, double *g, double *r, double *blockdiag) {
+  int st = big_dbg_ctx(c, "vba_debug_big_hessian");
+  if (st) return st;
+  if (!poses || !H || !g || !r || !blockdiag || slices < 0 || !big_has_store(c)) return VBA_ERR_BAD_ARG;
+  BigStore &S = c->big;
+  const size_t n6 = (size_t)6 * S.b.W;
+  if (!big_finite(poses, (size_t)S.b.W * 12)) return VBA_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<double> hd(n6);
+  st = big_hessian(S, c->stream, poses, hd.data(), g, r, c->err, slices);
+  if (st) return st;
+  HIPCHK(c, hipMemcpyAsync(H, S.b.H, n6 * n6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return big_block_diagonals(S, c->stream, blockdiag, c->err);
+}
+
+int vba_debug_big_residual(vba_ctx *c, const double *poses, double *r) {
+  int st = big_dbg_ctx(c, "vba_debug_big_residual");
+  if (st) return st;
+  if (!poses || !r || !big_has_store(c)) return VBA_ERR_BAD_ARG;
+  if (!big_finite(poses, (size_t)c->big.b.W * 12)) return VBA_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  return big_residual(c->big, c->stream, poses, r, c->err);
 }
 
 // thd_globalmapping (VS:3018-3141), the optimisation work of the hierarchical global BA over one map:

@@ -391,6 +391,23 @@ __global__ void k_gbab_fill(GbaBigView g, BigView b, int *fill) {
   b.efr[pos] = fr; b.evox[pos] = a;
   for (int k = 0; k < 10; k++) b.ecl[(size_t)k * ce + pos] = g.ecl[(size_t)k * ct + s];
 }
+// k_gbab_fill leaves a voxel's entries in table order (hash slot and atomic order: different run to run).  The build therefore fills
+// into scratch (tfr / tcl: the es rows of the view, which no kernel reads before k_big_slot has written them) and this kernel, one
+// thread per entry, moves each entry to its place in frame order: its rank is the number of entries of its voxel with a smaller frame
+// (a voxel's frames are distinct).  The store is then the CSR that vba_debug_big_load takes, does not depend on the table layout, and
+// the residual pass adds a voxel's frames in the order the reference does.
+__global__ void k_gbab_order(BigView b, const int *__restrict__ tfr, const double *__restrict__ tcl) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= b.E) return;
+  const size_t ce = (size_t)b.capE;
+  const int v = b.evox[e], f = tfr[e];
+  const int e0 = b.vptr[v], e1 = b.vptr[v + 1];
+  int rank = 0;
+  for (int q = e0; q < e1; q++) rank += tfr[q] < f ? 1 : 0;
+  const int dst = e0 + rank;
+  b.efr[dst] = f;
+  for (int k = 0; k < 10; k++) b.ecl[(size_t)k * ce + dst] = tcl[(size_t)k * ce + e];
+}
 __global__ void k_gbab_voxels(GbaBigView g, BigView b) {
   const int id = blockIdx.x * blockDim.x + threadIdx.x;
   const int nn = g.cnt[GCNT_NODES] < g.cap ? g.cnt[GCNT_NODES] : g.cap;
