@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include "vba_types.hpp"
 #include "vba_common.hpp"
+#include "vba_hess_units.hpp"
 
 namespace vba {
 
@@ -104,13 +105,6 @@ __global__ __launch_bounds__(256) void k_calib_read8(const double *__restrict__ 
 // issues the transform once per wave, and ~3 waves per SIMD (instead of 0.3) overlap each other's memory trips.
 
 // (dpp_mov_f64 and wave_sum_to_lane63: vba_common.hpp)
-// sum over each aligned group of 8 lanes, result in all 8 lanes (fixed tree)
-__device__ __forceinline__ double group8_sum(double x) {
-  x += dpp_mov_f64(x, x, 0xB1, 0xF);      // quad_perm [1,0,3,2]
-  x += dpp_mov_f64(x, x, 0x4E, 0xF);      // quad_perm [2,3,0,1]
-  x += dpp_mov_f64(x, x, 0x141, 0xF);     // row_half_mirror
-  return x;
-}
 // Maximum of a non-negative int over the 64 lanes of a wave, result valid in LANE 63 only (the same moves as wave_sum_to_lane63)
 __device__ __forceinline__ int wave_max_to_lane63(int x) {
   auto mx = [](int a, int b) { return a > b ? a : b; };
@@ -385,19 +379,17 @@ __global__ __launch_bounds__(256) void k_sum_scalar(const double *__restrict__ p
 // the epilogue: 34.5 us per pass at V = 1.8e4, in-kernel stamps in profiles/r01_k3_stamps.txt):
 //   * phase A issues ALL of a slot's loads in one batch (no dependent second round trip on N != 0) and the loads of the
 //     NEXT tile are issued before the current tile's contraction, so they fly under phase B;
-//   * phase B is the dense contraction H += G^T C G on the matrix cores: v_mfma_f64_16x16x4_f64, each wave owns
-//     ceil(NU / waves) of the NU upper-triangle 16x16 tiles of the (6W)^2 output (W = 10: 10 tiles over 5 waves);
-//     LDS image G[k][GS] with GS = 16 (mod 32) doubles, so the 4 rows x 16 columns a wave reads per operand are
-//     bank-conflict free (rows k, k+1 land in opposite halves of the 64 banks);
-//   * the epilogue writes the accumulator tiles straight into the LDS H image (no zero fill).
+//   * phase B is the dense contraction H += G^T C G on the matrix cores: v_mfma_f64_16x16x4_f64 over (16x16 upper-triangle tile,
+//     k-split) units, UPW to each of the four waves by the table HessCfg2<W>::unit (vba_hess_units.hpp; W = 10: 10 tiles x 2 k-splits,
+//     5 units per wave).  The wave index is a scalar (readfirstlane) and the wave's row of the table is selected once, in front of the
+//     tile loop: between the barrier that opens phase B and the first operand read there is no loop and no data-dependent branch, only
+//     the scalar unpacking of the unit bytes (the diagnostic stamp's skip aside).  LDS images G / c_k G [k][GS], GS odd (HessCfg2);
+//   * the epilogue stores the accumulator tiles in register order (k-splits combined through LDS) and sums the slot threads' E /
+//     gradient / residual terms out of an LDS staging area, one column per thread, in the fixed tree group8_tree — no cross-lane
+//     moves; the cK scales are stored only where the unscaled form reads them (W = 3).
 // f64 MFMA fragment layout (cdna_hip_programming.md, "f64 MFMA does NOT use these maps"):
 //   A[i = l & 15][k = l >> 4], B[k = l >> 4][j = l & 15], D[row = (l >> 4) + 4 r][col = l & 15], r = 0..3.
 typedef double v4f64 __attribute__((ext_vector_type(4)));
-
-constexpr int hess2_tv(int W) {   // voxels per tile: ~256 / W slot threads = exactly 4 waves, multiple of 8, K-split divisible
-  return W == 2 ? 128 : W == 3 ? 80 : W == 4 ? 64 : W == 5 ? 48 : W == 6 ? 40 : (W == 7 || W == 8) ? 32 : (W == 9 || W == 10) ? 24 : 16;
-}
-constexpr int gcd_i(int a, int b) { return b == 0 ? a : gcd_i(b, a % b); }
 
 __device__ __forceinline__ double rcp_f64(double x) {
   double y = __builtin_amdgcn_rcp(x);
@@ -405,38 +397,6 @@ __device__ __forceinline__ double rcp_f64(double x) {
   y = y * (2.0 - x * y);
   return y;
 }
-
-template <int W>
-struct HessCfg2 {
-  static constexpr int TV = hess2_tv(W);
-  static constexpr int NT = 256;                         // 4 waves: one per SIMD (5 waves measured 2x slower per tile)
-  static constexpr int NC = 6 * W;
-  static constexpr int NT16 = (NC + 15) / 16;
-  static constexpr int NCP = 16 * NT16;
-  // row stride of the LDS images in doubles.  ODD: the slot threads of one frame write rows 3 vl, 3 vl + 1, 3 vl + 2 — with the earlier
-  // stride = 16 (mod 32) their stores all fell on two bank groups (12-way conflicts); an odd stride spreads them, and the MFMA operand
-  // reads (4 rows x 16 consecutive doubles per wave) stay at 2-3 passes, far from binding
-  static constexpr int GS = ((NCP % 32 == 16) ? NCP : NCP + 16) + 1;
-  static constexpr int NK = 3 * TV;
-  static constexpr int NWV = NT / 64;
-  static constexpr int NU = NT16 * (NT16 + 1) / 2;       // upper-triangle 16x16 tiles
-  static constexpr int KS = NWV / gcd_i(NU, NWV);        // K-splits so that NU*KS units divide evenly over the waves
-  static constexpr int UPW = NU * KS / NWV;              // (tile, k-split) units per wave
-  static constexpr int KSTEPS = NK / 4 / KS;             // MFMAs per unit
-  static constexpr int NOUT = NC * NC + NC + 1;           // full layout [H | g | r]
-  static constexpr int EB = NU * 256;                     // tile layout: offset of the per-frame E blocks
-  static constexpr int GB = EB + 21 * W;                  //              offset of the gradient
-  static constexpr int RB = GB + 6 * W;                   //              offset of the residual
-  static constexpr int NOUT2 = RB + 1;
-  static constexpr int NG8 = NT / 8;
-  static_assert(TV * W <= NT && TV % 8 == 0 && (NK / 4) % KS == 0 && (NU * KS) % NWV == 0, "tile shape");
-  // PRESCALE: a second LDS image holds c_k * G, so the MFMA loop carries no f64 VALU multiply (f64 VALU and f64 MFMA share the issue on
-  // gfx950: one multiply per MFMA cost 21 of 95 cycles, tools/micro/mfma_lds.hip); every window except W = 3 has the LDS for it
-  static constexpr bool PRESCALE = ((size_t)2 * NK * GS + NK + W * 12 + 8) * sizeof(double) <= (size_t)150 * 1024;
-  static constexpr size_t LDS_MAIN = (size_t)NK * GS * (PRESCALE ? 2 : 1) + NK + W * 12 + 8;
-  static constexpr size_t LDS_EPI = (size_t)(KS > 1 ? NU * 256 : 0) + (size_t)28 * NG8 + 8;
-  static constexpr size_t LDS_BYTES = (LDS_MAIN > LDS_EPI ? LDS_MAIN : LDS_EPI) * sizeof(double);
-};
 
 struct SlotLoad {   // everything one (voxel, frame) slot thread reads from HBM
   double n, c[9], coe, l0, l1, l2, NN, vs0, vs1, vs2, U[9];
@@ -616,7 +576,29 @@ __global__ __launch_bounds__(HessCfg2<W>::NT) void k_hessian2(FactorView f, cons
   double *GA = C::PRESCALE ? G + (size_t)C::NK * C::GS : G;   // [NK][GS] rows scaled by c_k (the A operand)
   double *cK = GA + (size_t)C::NK * C::GS;    // [NK]
   double *sp = cK + C::NK;                    // [W][12]
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
+  // The wave index as a SCALAR: which MFMA units a wave owns (HessCfg2::unit) is a function of it and of compile-time constants only.
+  // The wave's row of the table is picked here, once, by scalar selects: its k-split (a wave's units are consecutive tiles of ONE
+  // k-split) and a byte [ta | tb << 3] per unit, four units to a register.  Left as `tid >> 6` the index is a vector
+  // register, the compiler takes it for divergent, and the decode ran as exec-masked loops in front of every tile's first operand read.
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  static_assert(C::NT16 <= 8 && C::wave_units_are_a_run(), "a unit packs into a byte; one k-split per wave");
+  constexpr int NUP = (C::UPW + 3) / 4;
+  unsigned int upk[NUP];
+  int ks_w = 0;
+#pragma unroll
+  for (int w = 0; w < C::NWV; w++) {
+    if (wv == w) ks_w = C::unit(w, 0).ks;
+#pragma unroll
+    for (int i = 0; i < NUP; i++) {
+      unsigned int word = 0;
+      for (int t = 4 * i; t < 4 * i + 4 && t < C::UPW; t++) { const HessUnit un = C::unit(w, t); word |= (unsigned int)(un.ta | un.tb << 3) << (8 * (t - 4 * i)); }
+      if (wv == w) upk[i] = word;
+    }
+  }
+  auto unit_ta = [&](int t) { return (int)(upk[t / 4] >> (8 * (t % 4)) & 7u); };
+  auto unit_tb = [&](int t) { return (int)(upk[t / 4] >> (8 * (t % 4) + 3) & 7u); };
+  auto unit_u = [&](int t) { const int ta = unit_ta(t); return ta * C::NT16 - ta * (ta - 1) / 2 + (unit_tb(t) - ta); };   // (as tl_fetch numbers the tiles)
 
   if (init.on) {
     for (int t = tid; t < W * 12; t += C::NT) sp[t] = init.x[t];
@@ -667,7 +649,7 @@ __global__ __launch_bounds__(HessCfg2<W>::NT) void k_hessian2(FactorView f, cons
 #pragma unroll
         for (int d = 0; d < 6; d++) { ga[d] = g1[d] * ck1; ga[C::GS + d] = g2[d] * ck2; ga[2 * C::GS + d] = hh[d] * ck3; }
       }
-      if (fi == 0) { cK[3 * vl] = ck1; cK[3 * vl + 1] = ck2; cK[3 * vl + 2] = ck3; }
+      if (!C::PRESCALE && fi == 0) { cK[3 * vl] = ck1; cK[3 * vl + 1] = ck2; cK[3 * vl + 2] = ck3; }   // (read by the unscaled form only)
       // the next tile's loads fly under this tile's contraction
       const int nt = tile + 1;
       nx.valid = false;
@@ -686,17 +668,16 @@ __global__ __launch_bounds__(HessCfg2<W>::NT) void k_hessian2(FactorView f, cons
     {
       const int kr = lane >> 4, cl = lane & 15;
       const double *gap[C::UPW], *gbp[C::UPW], *ckp[C::UPW];
+      // lane part + the wave's scalar unit part: no loop and no branch between the barrier above and the first operand read.  (The
+      // packed words pass through an empty asm so that the few scalar shifts stay HERE: hoisted out of the tile loop, the 2 UPW offsets
+      // would sit in registers through phase A, which has none to spare.)
+#pragma unroll
+      for (int i = 0; i < NUP; i++) asm volatile("" : "+s"(upk[i]));
+      const int kb = ks_w * (C::KSTEPS * 4);
+      const double *ga0 = GA + (kb + kr) * C::GS + cl, *gb0 = G + (kb + kr) * C::GS + cl, *ck0 = cK + kb + kr;
 #pragma unroll
       for (int t = 0; t < C::UPW; t++) {
-        const int unit = wv * C::UPW + t;
-        const int u = unit % C::NU, ksp = unit / C::NU;
-        int p = u, ta = 0;
-        while (p >= C::NT16 - ta) { p -= C::NT16 - ta; ta++; }
-        const int tb = ta + p;
-        const int kb = ksp * C::KSTEPS * 4;
-        gap[t] = GA + (size_t)(kb + kr) * C::GS + 16 * ta + cl;
-        gbp[t] = G + (size_t)(kb + kr) * C::GS + 16 * tb + cl;
-        ckp[t] = cK + kb + kr;
+        gap[t] = ga0 + 16 * unit_ta(t); gbp[t] = gb0 + 16 * unit_tb(t); ckp[t] = ck0;
       }
       double ar[C::UPW], cr[C::UPW], br[C::UPW];
 #pragma unroll
@@ -725,67 +706,54 @@ __global__ __launch_bounds__(HessCfg2<W>::NT) void k_hessian2(FactorView f, cons
   // ---------------- epilogue: accumulator tiles go to HBM in register order (coalesced 512 B per wave store)
   double *out = partial + (size_t)bid * C::NOUT2;
   double *Tb = lds;                                   // [NU][256] staging to combine k-splits
-  double *Eb = Tb + (C::KS > 1 ? C::NU * 256 : 0);    // [28][NG8]
+  double *Sb = Tb + (C::KS > 1 ? C::NU * 256 : 0);    // [28][SS] the threads' E / gradient / residual terms
   if (C::KS > 1) {
+    if (ks_w == 1) {
 #pragma unroll
-    for (int t = 0; t < C::UPW; t++) {
-      const int unit = wv * C::UPW + t;
-      if (unit / C::NU != 0) {
-        const int u = unit % C::NU;
+      for (int t = 0; t < C::UPW; t++)
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
-          if (unit / C::NU == 1) Tb[u * 256 + r * 64 + lane] = acc[t][r];
-        }
-      }
+        for (int r = 0; r < 4; r++) Tb[unit_u(t) * 256 + r * 64 + lane] = acc[t][r];
     }
     for (int ksp = 2; ksp < C::KS; ksp++) {
       __syncthreads();
+      if (ks_w == ksp) {
 #pragma unroll
-      for (int t = 0; t < C::UPW; t++) {
-        const int unit = wv * C::UPW + t;
-        if (unit / C::NU == ksp) {
-          const int u = unit % C::NU;
+        for (int t = 0; t < C::UPW; t++)
 #pragma unroll
-          for (int r = 0; r < 4; r++) Tb[u * 256 + r * 64 + lane] += acc[t][r];
-        }
+          for (int r = 0; r < 4; r++) Tb[unit_u(t) * 256 + r * 64 + lane] += acc[t][r];
       }
     }
   }
-  // E / gradient / residual: 8-lane groups never straddle a frame (TV % 8 == 0).  Data-parallel-primitive adds: the same 28 x 3
-  // steps through __shfl_xor (ds_bpermute, ~100 cycles of LDS round trip per dependent step) took most of the 7.7 us epilogue.
+  // E / gradient / residual: every thread parks its 28 terms in LDS, one column per thread (a wave stores 64 consecutive doubles per
+  // row; threads that are no slot, or whose slots were all invalid, hold +0.0).  Behind the barrier that also publishes Tb, thread
+  // (k, frame) adds the frame's TV / 8 aligned groups of 8 columns, each in the tree of group8_tree and the groups in ascending order:
+  // bit for bit the sums that three data-parallel-primitive steps per term and a [28][NT / 8] stage gave before, at a fraction of
+  // their ~640 VALU instructions.  8-column groups never straddle a frame (TV % 8 == 0).
 #pragma unroll
-  for (int k = 0; k < 6; k++) { Err[k] = group8_sum(Err[k]); Ett[k] = group8_sum(Ett[k]); gj[k] = group8_sum(gj[k]); }
+  for (int k = 0; k < 6; k++) { Sb[k * C::SS + tid] = Err[k]; Sb[(15 + k) * C::SS + tid] = Ett[k]; Sb[(21 + k) * C::SS + tid] = gj[k]; }
 #pragma unroll
-  for (int k = 0; k < 9; k++) Ert[k] = group8_sum(Ert[k]);
-  rres = group8_sum(rres);
-  if ((tid & 7) == 0) {
-    const int g8 = tid >> 3;
-#pragma unroll
-    for (int k = 0; k < 6; k++) { Eb[(size_t)k * C::NG8 + g8] = Err[k]; Eb[(size_t)(15 + k) * C::NG8 + g8] = Ett[k]; Eb[(size_t)(21 + k) * C::NG8 + g8] = gj[k]; }
-#pragma unroll
-    for (int k = 0; k < 9; k++) Eb[(size_t)(6 + k) * C::NG8 + g8] = Ert[k];
-    Eb[(size_t)27 * C::NG8 + g8] = rres;
-  }
+  for (int k = 0; k < 9; k++) Sb[(6 + k) * C::SS + tid] = Ert[k];
+  Sb[27 * C::SS + tid] = rres;
   __syncthreads();
   VBA_STAMP(13);
+  if (ks_w == 0) {
 #pragma unroll
-  for (int t = 0; t < C::UPW; t++) {
-    const int unit = wv * C::UPW + t;
-    if (unit / C::NU == 0) {
-      const int u = unit % C::NU;
+    for (int t = 0; t < C::UPW; t++) {
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         double val = acc[t][r];
-        if (C::KS > 1) val += Tb[u * 256 + r * 64 + lane];
-        out[u * 256 + r * 64 + lane] = val;
+        if (C::KS > 1) val += Tb[unit_u(t) * 256 + r * 64 + lane];
+        out[unit_u(t) * 256 + r * 64 + lane] = val;
       }
     }
   }
-  for (int t = tid; t < 28 * W; t += C::NT) {
+  // (dealt from the last thread down: where 28 W > NT the second trip falls to the last wave, which has no tiles to store when KS > 1)
+  for (int t = C::NT - 1 - tid; t < 28 * W; t += C::NT) {
     const int k = t % 28, fr = t / 28;
+    const double *sk = Sb + k * C::SS + fr * C::TV;
     double sum = 0.0;
 #pragma unroll
-    for (int g = 0; g < C::TV / 8; g++) sum += Eb[(size_t)k * C::NG8 + fr * (C::TV / 8) + g];
+    for (int g = 0; g < C::TV / 8; g++) sum += group8_tree(sk + 8 * g);
     if (k < 21) out[C::EB + 21 * fr + k] = sum;
     else if (k < 27) out[C::GB + 6 * fr + (k - 21)] = sum;
     else if (fr == 0) out[C::RB] = sum;
