@@ -549,6 +549,14 @@ int vba_debug_li_imu(vba_ctx *ctx, int W, int gravity, int flags, const double *
 int vba_debug_odom_sums(vba_ctx *ctx, int kind, int n, const double *pnt_body, const double *var_body, const double *state,
                         const double *cov, int slices, double *partial, double *sums, unsigned long long *cand, double *planes,
                         int *slices_used);
+/* Diagnostic: plane_update (the centre, normal, radius and 6x6 covariance of a leaf's plane) alone, on caller-supplied leaves
+ * (tests/test_gpu_plane.py).  The device function that the marginalisation runs is launched with one lane per leaf on scratch
+ * buffers of this call; the context's map is neither read nor written.  Host arrays:
+ *   in  [n][67]  pcr_add (Pxx Pxy Pxz Pyy Pyz Pzz vx vy vz N) | eig_value (3) | eig_vector (9, row-major, columns = eigenvectors) |
+ *                cov_add (45: the upper triangle of the symmetric 9x9, row by row)
+ *   out [n][43]  centre (3) | normal (3) | radius | plane_var (36, row-major)
+ * The stream is drained.  VBA_ERR_BAD_ARG with nothing launched: a NULL pointer, n < 1 or n > 2^20. */
+int vba_debug_plane_update(vba_ctx *ctx, int n, const double *in, double *out);
 /* Diagnostic: the passes of the any-window path (csrc/vba_kernels_big.hpp) one at a time on the context's sparse store, the store that
  * vba_hba_add_edge builds and optimises whenever wdsize != win_size (tests/test_gpu_big.py).  The store is CSR over voxels, one entry
  * per occupied (voxel, frame).  Every call drains the stream; none touches the context's LM state, its dense factor store or its map.

@@ -90,3 +90,11 @@ def test_host_imu_give_evaluate_matches_oracle(capi, oracle):
         assert ra == pytest.approx(rb, rel=1e-10)
         assert np.allclose(Ja, Jb, rtol=1e-9, atol=1e-9 * np.abs(Jb).max())
         assert np.allclose(ga, gb, rtol=1e-9, atol=1e-9 * np.abs(gb).max())
+
+
+def test_debug_plane_update_refuses_without_a_context(capi):
+    """the diagnostic entry of tests/test_gpu_plane.py checks its arguments before it touches a device"""
+    lib = capi.load()
+    rows = np.zeros((1, 67)); out = np.full((1, 43), np.nan)
+    st = lib.vba_debug_plane_update(None, C.c_int(1), rows.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+    assert st == capi.ERR_BAD_ARG and np.isnan(out).all()

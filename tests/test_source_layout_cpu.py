@@ -153,3 +153,15 @@ def test_vba_launch_is_a_shared_header_without_kernels():
     # the units reach it through vba_ctx.hpp and nothing else, no kernel header reaches it
     assert [f for f in sources() if f != "vba_ctx.hpp" and "vba_launch.hpp" in INCLUDE.findall(read(f))] == []
     assert [h for h in kernel_headers() if "vba_launch.hpp" in reached(h)] == []
+
+
+# ---------------------------------------------------------------- diagnostics run the production code
+def test_debug_plane_update_runs_the_production_device_function():
+    """vba_debug_plane_update pins plane_update_dev itself: one definition, called by the marginalisation and by the diagnostic
+    kernel, whose host launch lives in the unit"""
+    text = read("vba_kernels_map.hpp")
+    assert len(re.findall(r"void plane_update_dev\(", text)) == 1
+    body = function_body(text, r"^__global__ __launch_bounds__\(256\) void k_debug_plane_update\(")
+    assert "plane_update_dev(m, id, add, ev, U);" in body
+    assert "plane_update_dev(m, id, add, ev, U);" in function_body(text, r"^__device__ __forceinline__ int margi_leaf_body\([^;]*\) \{")
+    assert [f for f in sources() if "k_debug_plane_update" in read(f)] == ["vba_kernels_map.hpp", "vba_map.hip"]

@@ -30,7 +30,7 @@ EXPORTS = [
     "vba_map_num_roots", "vba_map_num_slide_roots", "vba_map_stats", "vba_map_dump_leaves", "vba_map_dump_plane_var", "vba_odom_lio_state_estimation", "vba_odom_lio_state_estimation_resident",
     "vba_set_allreduce", "vba_rccl_get_unique_id", "vba_rccl_init", "vba_set_rccl_comm", "vba_shard_owner", "vba_set_shard",
     "vba_timing_enable", "vba_timing_calibration_read", "vba_timing_select", "vba_timing_sample_every", "vba_timing_launch_hessian", "vba_timing_null_span", "vba_timing_reset", "vba_timing_get",
-    "vba_lm_begin", "vba_lm_refresh_eigen", "vba_lm_iterate", "vba_lm_end", "vba_debug_solve", "vba_debug_li_imu", "vba_debug_odom_sums",
+    "vba_lm_begin", "vba_lm_refresh_eigen", "vba_lm_iterate", "vba_lm_end", "vba_debug_solve", "vba_debug_li_imu", "vba_debug_odom_sums", "vba_debug_plane_update",
     "vba_debug_big_load", "vba_debug_big_build", "vba_debug_big_size", "vba_debug_big_read", "vba_debug_big_hessian", "vba_debug_big_residual",
     "vba_io_save_pcd", "vba_io_load_pcd", "vba_io_save_pose", "vba_io_read_lidarstate",
     "vba_motion_init", "vba_init_imu_poses", "vba_init_align_gravity",
@@ -1228,6 +1228,14 @@ class Context:
         if kd:
             ns = used.value
             out.update(cand=cand.reshape(-1)[:ns * n * 5].reshape(ns, n, 5).copy(), planes=planes[:n], slices=ns)
+        return out
+
+    def debug_plane_update(self, rows67):
+        """vba_debug_plane_update: plane_update alone on leaves [n][67] = add10 | ev3 | U9 | cov45 (host array, left as given).
+        Returns [n][43] = centre3 | normal3 | radius | plane_var36."""
+        rows = _c(rows67).reshape(-1, 67); n = len(rows)
+        out = np.full((n, 43), np.nan)
+        self._chk(self.lib.vba_debug_plane_update(self.h, C.c_int(n), _p(rows), _p(out)))
         return out
 
     def kdtree_reserve(self, max_map_points, max_scan_points):

@@ -274,6 +274,7 @@ int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomE
                       const double *d_var, double *d_partial, std::string &err);
 int map_odom_debug_sums(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, const vbh::OdomEkf *h_img, int n, const double *d_pts,
                         const double *d_var, double *d_partial, double *d_sums, int *nb_out, std::string &err);
+int map_debug_plane_update(hipStream_t st, int n, const double *in, double *out, std::string &err);
 // the update launch of the resident EKF loops (vba_kernels_odom.hpp), also the kd-tree variant's in vba_odom.hip, and the launch that
 // stores its sums alone (vba_debug_odom_sums)
 __global__ __launch_bounds__(256) void k_odom_update(vbh::OdomEkf *S, const double *__restrict__ partial, int nb, int iter, int kd);

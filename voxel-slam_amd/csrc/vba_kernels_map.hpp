@@ -1302,6 +1302,21 @@ __device__ __forceinline__ void plane_update_dev(const MapView &m, int id, const
   for (int k = 0; k < 36; k++) pl[(size_t)(7 + k) * cp + id] = pv[k];
 }
 
+// plane_update_dev alone, for vba_debug_plane_update: one lane per leaf on a scratch view (cap = n; only ncov and nplane are set).
+// in [n][67] = add(10) | ev(3) | U(9) | cov_add upper triangle (45);  out [n][43] = the leaf's nplane column, in the layout above.
+__global__ __launch_bounds__(256) void k_debug_plane_update(MapView m, int n, const double *__restrict__ in, double *__restrict__ out) {
+  const int id = blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= n) return;
+  const double *r = in + (size_t)id * 67;
+  double add[10], ev[3], U[9];
+  for (int k = 0; k < 10; k++) add[k] = r[k];
+  for (int k = 0; k < 3; k++) ev[k] = r[10 + k];
+  for (int k = 0; k < 9; k++) U[k] = r[13 + k];
+  for (int k = 0; k < 45; k++) ncov_at(m, k, id) = r[22 + k];
+  plane_update_dev(m, id, add, ev, U);
+  for (int k = 0; k < 43; k++) out[(size_t)id * 43 + k] = m.nplane[(size_t)k * m.cap + id];
+}
+
 // One thread per leaf: OctoTree::margi leaf branch VM:1468-1584 with mgsize = 1.
 __device__ __forceinline__ int margi_leaf_body(const MapView &m, const MapParams &P, const FactorView &f, int nfac, int win_count, int epoch, int id, const int *smp);
 __global__ __launch_bounds__(256) void k_margi_leaf(MapView m, MapParams P, FactorView f, int nfac, int win_count, int epoch) {

@@ -728,4 +728,22 @@ int map_odom_debug_sums(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, const vb
   return VBA_OK;
 }
 
+// vba_debug_plane_update: plane_update_dev on n caller-supplied leaves, one lane each, on a scratch view of this call (cap = n, ncov
+// and nplane in a buffer the call owns): no array of the map is read or written.  in [n][67], out [n][43], host arrays.
+int map_debug_plane_update(hipStream_t st, int n, const double *in, double *out, std::string &err) {
+  const size_t N = (size_t)n;
+  DevMem<double> buf;                           // [in 67 n | ncov 45 n | nplane 43 n | out 43 n]
+  MAPCHK(buf.ensure(N * (67 + 45 + 43 + 43)));
+  double *d_in = buf.p, *d_cov = d_in + N * 67, *d_plane = d_cov + N * 45, *d_out = d_plane + N * 43;
+  MAPCHK(hipMemcpyAsync(d_in, in, N * 67 * sizeof(double), hipMemcpyHostToDevice, st));
+  MAPCHK(hipMemsetAsync(d_cov, 0, N * (45 + 43 + 43) * sizeof(double), st));
+  MapView v{};
+  v.cap = n; v.ncov = d_cov; v.nplane = d_plane;
+  hipLaunchKernelGGL(k_debug_plane_update, dim3((n + 255) / 256), dim3(256), 0, st, v, n, (const double *)d_in, d_out);
+  MAPCHK(hipGetLastError());
+  MAPCHK(hipMemcpyAsync(out, d_out, N * 43 * sizeof(double), hipMemcpyDeviceToHost, st));
+  MAPCHK(hipStreamSynchronize(st));
+  return VBA_OK;
+}
+
 }  // namespace vba

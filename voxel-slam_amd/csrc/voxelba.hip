@@ -1281,6 +1281,12 @@ int vba_map_num_slide_roots(vba_ctx *c) { return map_num_roots(c->map, c->stream
 int vba_map_stats(vba_ctx *c, long long *out8) { return out8 ? map_stats(c->map, c->stream, out8, c->err) : VBA_ERR_BAD_ARG; }
 int vba_map_dump_leaves(vba_ctx *c, double *out, int max_leaves) { return map_dump_leaves(c->map, c->stream, out, max_leaves, c->err); }
 int vba_map_dump_plane_var(vba_ctx *c, double *out, int max_leaves) { return map_dump_plane_var(c->map, c->stream, out, max_leaves, c->err); }
+// diagnostic: plane_update_dev on caller-supplied leaves (include/voxelba.h); the context's map is not touched
+int vba_debug_plane_update(vba_ctx *c, int n, const double *in, double *out) {
+  if (!c || !in || !out || n < 1 || n > (1 << 20)) return VBA_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  return map_debug_plane_update(c->stream, n, in, out, c->err);
+}
 
 }  // extern "C"
 extern "C" {
