@@ -8,7 +8,9 @@ vba_li_ba_damping_iter against imu_coef * H_imu* + H_lidar*.
     the stand-alone form, and within the bars;
   * the reference is computed once for the whole corpus, on the cov^-1 blocks the hook hands back, and shared by the forms;
   * the production call on the `offset` window at W = 3, 10, 16 with gravity (max_iter = 1) and W = 3, 10 without: see
-    test_production_hess for which state its hess belongs to, and how the three forced iterations of the second mode are ended.
+    test_production_hess for which state its hess belongs to, and how the three forced iterations of the second mode are ended;
+  * the same call through its sharded flow with one rank (force_collective, W = 2 and 11, both gravity modes): hess under the same
+    bar, states, increments and trace against the CPU oracle (test_collective_flow_one_rank).
 The printed ratios are reports; nothing depends on them."""
 import numpy as np
 import pytest
@@ -219,3 +221,80 @@ def test_production_hess(capi, W, gravity):
     ratio = float((err[~z] / bar[~z]).max())
     print("production W=%d gravity=%d hess worst ratio to imu_coef * bar_imu + bar_lidar: %.3g" % (W, gravity, ratio))
     assert ratio <= 1.0
+
+
+# ------------------------------------------------------------------------------------------------ the LI call's sharded flow, one rank
+COLL_V = 70        # voxels of the store: three workgroups of the residual pass, pushed in one fixed order
+
+
+def _oracle_li(W, store, st, im, gravity, coef, max_iter):
+    import oracle_api
+    f = oracle_api.Factor(W)
+    f.push_dict(store)
+    return f.li_ba_damping_iter(st, im, gravity=bool(gravity), imu_coef=coef, max_iter=max_iter)
+
+
+@pytest.mark.parametrize("gravity", [0, 1])
+@pytest.mark.parametrize("W", [2, 11])
+def test_collective_flow_one_rank(capi, W, gravity):
+    """vba_li_ba_damping_iter with force_collective = 1 and an all-reduce hook that returns its input: the sharded branch of the LI call
+    (stand-alone init, the trial step with its speculative Hessian pass and the one all-reduce, *hess from the saved copy `raw`) with
+    one rank, which otherwise runs only under the two-process shard tests.  W = 2, and W = 11, the smallest window whose k_li_solve
+    keeps L outside the LDS; gravity off and on.  Two calls per case on a context of its own:
+      * *hess, in the setting of test_production_hess (max_iter = 1 with gravity, the ballast voxel without), against the same
+        double-double sum and under the same bar, worst ratio <= 1;
+      * states, the IMU increments and the trace of a three-iteration call on the plain store (an iteration after an accepted step
+        starts from the all-reduced Hessian of the trial step) against the CPU oracle.  This file held no bar for them; they are the bars of the
+        single-rank LI cases of test_gpu_factor.py (test_li_ba_damping_iter_parity), unchanged: trace rtol 1e-6 / atol 1e-10, states
+        and increments 1e-7."""
+    st, im = I.inputs("offset", W)
+    plain = _ctx(capi, W)
+    try:
+        covinv = plain.debug_li_imu(st, im, gravity=bool(gravity))["covinv"]      # (the hook is not available on a collective context)
+        coef = float(plain.opt.imu_coef)
+    finally:
+        plain.close()
+    Ht, _, rt = I.Ref([(st, im, covinv)]).window(0, gravity)
+    store = _store_at(_poses(st), 177 + W, V=COLL_V)
+    pinned = store
+    if not gravity:
+        whole = 0.5 * coef * float(rt.v.f64()) + float((store["coe"] * store["eig_val"][:, 0]).sum())
+        pinned = _store_at(_poses(st), 177 + W, V=COLL_V, ballast=1e8 * whole)
+    outs = []
+    for fac, max_iter in ((pinned, 1), (store, 3)):
+        ctx = _ctx(capi, W, force_collective=1)
+        try:
+            ctx.set_allreduce(lambda ptr, n, stream: 0)     # one rank: the sum over the ranks is the buffer itself
+            ctx.push_voxels(fac["clusters"], fac["fix"], fac["coe"], fac["eig_val"], fac["eig_vec"], fac["pcr_add"])
+            outs.append(ctx.li_ba_damping_iter(st, im, gravity=bool(gravity), max_iter=max_iter))
+        finally:
+            ctx.close()
+    one, three = outs
+    assert len(one["trace"]) == 1, one["trace"]
+    # *hess of the pinned call
+    lid = R.Ref(pinned["clusters"], pinned["coe"], pinned["eig_val"], pinned["eig_vec"], pinned["pcr_add"], _poses(st))
+    (Hl, _, _), (barL, _, _) = lid.sums(np.arange(len(pinned["coe"])))
+    n = 15 * W + 3 * gravity
+    pose = np.array([15 * (k // 6) + k % 6 for k in range(6 * W)])
+    Hs = R.DD(Ht.v.hi.copy(), Ht.v.lo.copy()) * R.DD(np.full((n, n), coef))
+    L = R.DD(np.zeros((n, n)))
+    L.hi[np.ix_(pose, pose)] = Hl.hi; L.lo[np.ix_(pose, pose)] = Hl.lo
+    Hs = Hs + L
+    bar = coef * Ht.bar()
+    bar[np.ix_(pose, pose)] += barL
+    H = one["hess"]
+    assert np.isfinite(H).all()
+    err = Hs.err_to(H)
+    z = bar == 0.0
+    assert not H[z].any()
+    ratio = float((err[~z] / bar[~z]).max())
+    print("\ncollective W=%d gravity=%d hess worst ratio to imu_coef * bar_imu + bar_lidar: %.3g" % (W, gravity, ratio))
+    # states, increments and trace of the three-iteration call against the oracle (the pinned call is built for *hess alone: beside its
+    # ballast the accept test of the gravity-free mode compares two sums that agree to 1e-8 of themselves)
+    b = _oracle_li(W, store, st, im, gravity, coef, 3)
+    tr_ok = three["trace"].shape == b["trace"].shape and np.allclose(three["trace"], b["trace"], rtol=1e-6, atol=1e-10)
+    ds = float(np.abs(three["states"] - b["states"]).max()); di = float(np.abs(three["imus"] - b["imus"]).max())
+    print("collective W=%d gravity=%d max_iter=3: %d trace rows (oracle %d), close %s; states %.3g, increments %.3g (bar 1e-7)"
+          % (W, gravity, len(three["trace"]), len(b["trace"]), tr_ok, ds, di))
+    assert ratio <= 1.0
+    assert tr_ok and ds < 1e-7 and di < 1e-7

@@ -70,7 +70,7 @@ ALLOC_CALL = re.compile(r"\bhip(?:Host)?Malloc\s*\(")
 # scoped DbgBufs hold owning members like everything else
 FREE_ALLOWED = {}
 # the two stamp buffers of the -DVBA_DIAG build: statics that live as long as the process and are never freed
-ALLOC_ALLOWED = {"voxelba.hip": {"k3_stamps_buffer", "launch_residual"}}
+ALLOC_ALLOWED = {"voxelba.hip": {"k3_stamps_buffer", "k4_stamps_buffer"}}
 
 
 def call_sites(name, call):
@@ -165,3 +165,57 @@ def test_debug_plane_update_runs_the_production_device_function():
     assert "plane_update_dev(m, id, add, ev, U);" in body
     assert "plane_update_dev(m, id, add, ev, U);" in function_body(text, r"^__device__ __forceinline__ int margi_leaf_body\([^;]*\) \{")
     assert [f for f in sources() if "k_debug_plane_update" in read(f)] == ["vba_kernels_map.hpp", "vba_map.hip"]
+
+
+# ---------------------------------------------------------------- the BA core's host side ("Source layout": voxelba.hip)
+# a macro definition with its continuation lines: (name, body)
+MACRO = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(\w+)((?:[^\n]*\\\n)*[^\n]*)", re.M)
+
+
+def macros(name):
+    return {m.group(1): m.group(2) for m in MACRO.finditer(read(name))}
+
+
+def test_one_hip_check_macro():
+    assert MACRO.search("#define A(x) do { \\\n  f(x); \\\n} while (0)\nint y;").group(2).endswith("while (0)")
+    builders, users = [], []
+    for f in sources():
+        for name, body in macros(f).items():
+            if "hipGetErrorString" in body and "VBA_ERR_HIP" in body:
+                builders.append((f, name))
+            elif "VBA_HIPCHK" in body:
+                users.append((f, name, body.strip()))
+    assert builders == [("vba_ctx.hpp", "VBA_HIPCHK")]
+    assert users == [("vba_ctx.hpp", "HIPCHK", "VBA_HIPCHK")]
+    # no unit keeps a check macro of its own; BGCHK hands the runtime's status on and builds no message
+    own = sorted((f, n) for f in sources() for n in macros(f) if n.endswith("CHK"))
+    assert own == [("vba_btcgen.hip", "BGCHK"), ("vba_ctx.hpp", "HIPCHK"), ("vba_ctx.hpp", "VBA_HIPCHK")]
+    assert "hipGetErrorString" not in macros("vba_btcgen.hip")["BGCHK"]
+    for f in ("vba_map.hip", "vba_hba.hip"):
+        assert len(re.findall(r"\bVBA_HIPCHK\(err, ", read(f))) > 50, f
+
+
+def test_core_call_paths_hold_no_printing():
+    text = read("voxelba.hip")
+    for head in (r"^int launch_residual\(", r"^int vba_lm_end\(", r"^static int li_ba_device\("):
+        body = function_body(text, head)
+        assert len(body) > 500 and "printf" not in body and "stderr" not in body, head
+    assert "fprintf" in function_body(text, r"^void k4_stamps_dump\(")       # (the search does see a printer)
+
+
+def test_sharded_trial_step_is_written_once():
+    text = read("voxelba.hip")
+    trial = re.compile(r"d_out\s*\+\s*\(\s*nout_tl\(")
+    assert trial.search("c->d_out + (nout_tl(W) - 1)")
+    step = function_body(text, r"^int sharded_trial_step\(")
+    assert len(trial.findall(text)) == 1 and len(trial.findall(step)) == 1
+    assert "k_lm_update" not in step and "k_li_update" not in step and "launch_update(" in step
+    for head, kernel in ((r"^int vba_lm_iterate\(", "k_lm_update"), (r"^static int li_ba_device\(", "k_li_update")):
+        body = function_body(text, head)
+        m = re.search(r"sharded_trial_step\(c, p, V, \[&\]\(const double \*r\) \{ hipLaunchKernelGGL\((\w+),", body)
+        assert m and m.group(1) == kernel, head
+        assert "have_hess = true" not in body
+    # "this rank still needs a Hessian pass" is one predicate
+    assert len(re.findall(r"lm\.have_hess\)", text)) == 1 and "lm.have_hess)" in function_body(text, r"^bool needs_hessian_pass\(")
+    for head in (r"^int vba_lm_iterate\(", r"^static bool li_imu_rides\(", r"^static int li_ba_device\("):
+        assert "needs_hessian_pass(c)" in function_body(text, head), head

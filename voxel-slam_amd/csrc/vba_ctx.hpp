@@ -19,17 +19,30 @@
 
 using namespace vba;
 
-#define HIPCHK(ctx, expr)                                                                        \
+// The one check of a runtime call: a failure leaves "<the call as written>: <the runtime's text>" in `err`, the error string itself or the
+// context that holds it (hipchk_err), and returns VBA_ERR_HIP.  HIPCHK(ctx, expr) is an alias, not a wrapper: an argument handed on through
+// a second macro is expanded before it is stringified, and the message would spell hipEventDisableTiming as 0x2.
+#define VBA_HIPCHK(err, expr)                                                                    \
   do {                                                                                           \
     hipError_t _e = (expr);                                                                      \
     if (_e != hipSuccess) {                                                                      \
-      (ctx)->set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                       \
+      hipchk_err(err) = std::string(#expr) + ": " + hipGetErrorString(_e);                       \
       return VBA_ERR_HIP;                                                                        \
     }                                                                                            \
   } while (0)
+#define HIPCHK VBA_HIPCHK
 
 namespace vba {
 struct TimedSpan { hipEvent_t a, b; };
+
+// Layout of vba_ctx::h_pin in doubles: poses [W][12] (upload_poses), the download stage (fetch: n doubles, reserving n + kPinFixed; *hess of
+// vba_lm_end: (6W)^2), this rank's voxel count on its way through the all-reduce of vba_lm_begin (device partner: d_scal + kScalCount), the end
+// of the fixed part; vba_create reserves kPinCreate + nout_of(W), vba_lm_end kPinCreate + (6W)^2
+constexpr size_t kPinPoses = 0, kPinStage = 32768, kPinCount = 60000, kPinFixed = 65536, kPinCreate = kPinFixed + 1024;
+constexpr int kScalCount = 8;
+static_assert(kPinPoses + (size_t)VBA_MAX_WIN_DEV * 12 <= kPinStage, "the pose region ends before the stage");
+static_assert(kPinStage + (size_t)36 * VBA_MAX_WIN_DEV * VBA_MAX_WIN_DEV <= kPinCount, "the *hess stage of vba_lm_end ends before the count slot");
+static_assert(kPinCount < kPinFixed && kPinFixed <= kPinCreate, "the fixed part fits inside what vba_create reserves");
 
 // Diagnostic switches (in-kernel stamps, host-side phase timers, ablation forms) exist only in a -DVBA_DIAG build (make diag ->
 // libvoxelba_diag.so, tools/README.md); the shipped library reads no environment variable.  Internal linkage: the diagnostic library links
@@ -144,6 +157,8 @@ struct vba_ctx {
 
   void set_error(const std::string &s) { err = s; }
 };
+inline std::string &hipchk_err(std::string &err) { return err; }      // where VBA_HIPCHK / HIPCHK leave their message
+inline std::string &hipchk_err(vba_ctx *c) { return c->err; }
 
 // loop retrieval (vba_btc.hip); the keyframe store writes the generator's point buffer (db->gen->xyz)
 struct vba_btc_db {

@@ -19,7 +19,6 @@
 namespace vba {
 
 // ---------------------------------------------------------------- host side of vba_kernels_gba.hpp: the octree of one window
-#define GBACHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return VBA_ERR_HIP; } } while (0)
 
 // the view's pointers from the owners (null where a group is empty)
 inline void gba_refresh(GbaStore &s) {
@@ -42,7 +41,7 @@ inline int gba_alloc_nodes(GbaStore &s, int cap, int W, std::string &err) {
       (alloc = m.nfac.ensure(cp)) || (alloc = m.nlayer.ensure(cp)) || (alloc = m.neval.ensure(3 * cp)) || (alloc = m.nevec.ensure(9 * cp)))
     m = GbaStore::Nodes();
   gba_refresh(s);
-  GBACHK(alloc);
+  VBA_HIPCHK(err, alloc);
   s.v.cap = cap; s.v.W = W;
   return VBA_OK;
 }
@@ -54,16 +53,16 @@ inline int gba_build(GbaStore &s, hipStream_t st, int W, const int *offsets, con
   const int n = offsets[W];
   *n_factors = 0;
   hipError_t alloc;
-  GBACHK(s.h_cnt.ensure(GCNT_N));
-  GBACHK(s.cnt.ensure(GCNT_N));
-  GBACHK(s.poses.ensure(VBA_MAX_WIN * 12));
-  GBACHK(s.offsets.ensure(VBA_MAX_WIN + 1));
+  VBA_HIPCHK(err, s.h_cnt.ensure(GCNT_N));
+  VBA_HIPCHK(err, s.cnt.ensure(GCNT_N));
+  VBA_HIPCHK(err, s.poses.ensure(VBA_MAX_WIN * 12));
+  VBA_HIPCHK(err, s.offsets.ensure(VBA_MAX_WIN + 1));
   if (n > s.cap_pts) {
     GbaStore::Pts &m = s.pts;
     m = GbaStore::Pts(); s.cap_pts = 0;
     const size_t c = (size_t)n + n / 4 + 1024;
     if ((alloc = m.pw.ensure(3 * c)) || (alloc = m.pframe.ensure(c)) || (alloc = m.pnode.ensure(c)) || (alloc = m.pl.ensure(3 * c))) { m = GbaStore::Pts(); gba_refresh(s); }
-    GBACHK(alloc);
+    VBA_HIPCHK(err, alloc);
     s.cap_pts = (int)c;
   }
   int hcap = 1 << 16;
@@ -72,23 +71,23 @@ inline int gba_build(GbaStore &s, hipStream_t st, int W, const int *offsets, con
     GbaStore::Hash &m = s.hash;
     m = GbaStore::Hash(); s.cap_hash = 0;
     if ((alloc = m.keys.ensure(hcap)) || (alloc = m.vals.ensure(hcap))) { m = GbaStore::Hash(); gba_refresh(s); }
-    GBACHK(alloc);
+    VBA_HIPCHK(err, alloc);
     s.cap_hash = hcap;
   }
   gba_refresh(s);
   s.v.hmask = (unsigned int)(s.cap_hash - 1);
   s.v.npts = n;
-  GBACHK(hipMemcpyAsync(s.pts.pl, pl, (size_t)n * 3 * 8, hipMemcpyDefault, st));
-  GBACHK(hipMemcpyAsync(s.v.poses, poses, (size_t)W * 12 * 8, hipMemcpyHostToDevice, st));
-  GBACHK(hipMemcpyAsync(s.v.offsets, offsets, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, st));
+  VBA_HIPCHK(err, hipMemcpyAsync(s.pts.pl, pl, (size_t)n * 3 * 8, hipMemcpyDefault, st));
+  VBA_HIPCHK(err, hipMemcpyAsync(s.v.poses, poses, (size_t)W * 12 * 8, hipMemcpyHostToDevice, st));
+  VBA_HIPCHK(err, hipMemcpyAsync(s.v.offsets, offsets, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, st));
   if (s.v.cap == 0 || s.v.W != W) { int r = gba_alloc_nodes(s, 1 << 17, W, err); if (r) return r; }
   const dim3 b(256), gp((n + 255) / 256);
   for (int attempt = 0; attempt < 8; attempt++) {
     const size_t cp = (size_t)s.v.cap;
-    GBACHK(hipMemsetAsync(s.v.cnt, 0, GCNT_N * sizeof(int), st));
-    GBACHK(hipMemsetAsync(s.v.hkeys, 0xFF, (size_t)s.cap_hash * 8, st));
-    GBACHK(hipMemsetAsync(s.v.nadd, 0, 10 * cp * 8, st));
-    GBACHK(hipMemsetAsync(s.v.nlc, 0, 10 * cp * W * 8, st));
+    VBA_HIPCHK(err, hipMemsetAsync(s.v.cnt, 0, GCNT_N * sizeof(int), st));
+    VBA_HIPCHK(err, hipMemsetAsync(s.v.hkeys, 0xFF, (size_t)s.cap_hash * 8, st));
+    VBA_HIPCHK(err, hipMemsetAsync(s.v.nadd, 0, 10 * cp * 8, st));
+    VBA_HIPCHK(err, hipMemsetAsync(s.v.nlc, 0, 10 * cp * W * 8, st));
     if (n > 0) {
       hipLaunchKernelGGL(k_gba_keys, gp, b, 0, st, s.v, P);
       hipLaunchKernelGGL(k_gba_roots, dim3((s.cap_hash + 4095) / 4096), b, 0, st, s.v, P);
@@ -99,10 +98,10 @@ inline int gba_build(GbaStore &s, hipStream_t st, int W, const int *offsets, con
         if (L < P.max_layer) hipLaunchKernelGGL(k_gba_descend, gp, b, 0, st, s.v);
       }
     }
-    GBACHK(hipGetLastError());
-    GBACHK(hipStreamSynchronize(st));   // drain first (see map_read_counters)
-    GBACHK(hipMemcpyAsync(s.h_cnt, s.v.cnt, GCNT_N * sizeof(int), hipMemcpyDeviceToHost, st));
-    GBACHK(hipStreamSynchronize(st));
+    VBA_HIPCHK(err, hipGetLastError());
+    VBA_HIPCHK(err, hipStreamSynchronize(st));   // drain first (see map_read_counters)
+    VBA_HIPCHK(err, hipMemcpyAsync(s.h_cnt, s.v.cnt, GCNT_N * sizeof(int), hipMemcpyDeviceToHost, st));
+    VBA_HIPCHK(err, hipStreamSynchronize(st));
     if (s.h_cnt[GCNT_OVERFLOW] == 2) { err = "keyframe point outside the 21-bit voxel index range"; return VBA_ERR_CAPACITY; }
     if (!s.h_cnt[GCNT_OVERFLOW]) { *n_factors = s.h_cnt[GCNT_FACTORS]; return VBA_OK; }
     int want = s.v.cap * 2;
@@ -115,7 +114,6 @@ inline int gba_build(GbaStore &s, hipStream_t st, int W, const int *offsets, con
 }
 
 // ---------------------------------------------------------------- host side of vba_kernels_big.hpp: the any-window sparse path
-#define BIGCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return VBA_ERR_HIP; } } while (0)
 
 // The sparse factor store of W frames in the arena, in three steps with the producer's launches between them (big_build: the octree
 // kernels; vba_debug_big_load: the caller's arrays).  1: the per-voxel arrays, H / g / r, the dense solver's buffers and NP / ld; vptr and
@@ -124,33 +122,33 @@ inline int big_store_voxels(BigStore &s, hipStream_t st, int W, int V, std::stri
   auto al = [&](void **p, size_t bytes) { return s.arena(p, bytes); };
   BigView &b = s.b;
   b.W = W; b.V = V; b.capV = V > 0 ? V : 1;
-  BIGCHK(al((void **)&b.vptr, (size_t)(V + 1) * 4)); BIGCHK(al((void **)&s.d_vcnt, (size_t)b.capV * 4)); BIGCHK(al((void **)&s.d_fill, (size_t)b.capV * 4));
-  BIGCHK(al((void **)&b.eval, (size_t)b.capV * 3 * 8)); BIGCHK(al((void **)&b.evec, (size_t)b.capV * 9 * 8)); BIGCHK(al((void **)&b.pcr, (size_t)b.capV * 10 * 8));
-  BIGCHK(al((void **)&b.poses, (size_t)W * 12 * 8));
+  VBA_HIPCHK(err, al((void **)&b.vptr, (size_t)(V + 1) * 4)); VBA_HIPCHK(err, al((void **)&s.d_vcnt, (size_t)b.capV * 4)); VBA_HIPCHK(err, al((void **)&s.d_fill, (size_t)b.capV * 4));
+  VBA_HIPCHK(err, al((void **)&b.eval, (size_t)b.capV * 3 * 8)); VBA_HIPCHK(err, al((void **)&b.evec, (size_t)b.capV * 9 * 8)); VBA_HIPCHK(err, al((void **)&b.pcr, (size_t)b.capV * 10 * 8));
+  VBA_HIPCHK(err, al((void **)&b.poses, (size_t)W * 12 * 8));
   const size_t n6 = (size_t)6 * W;
-  BIGCHK(al((void **)&b.H, n6 * n6 * 8)); BIGCHK(al((void **)&b.g, n6 * 8)); BIGCHK(al((void **)&b.r, 8));
+  VBA_HIPCHK(err, al((void **)&b.H, n6 * n6 * 8)); VBA_HIPCHK(err, al((void **)&b.g, n6 * 8)); VBA_HIPCHK(err, al((void **)&b.r, 8));
 
   s.NP = (int)((n6 + 7) / 8 * 8); s.ld = (int)((s.NP + 63) / 64 * 64);
-  BIGCHK(al((void **)&s.d_Ab, (size_t)(s.NP + 1) * s.ld * 8)); BIGCHK(al((void **)&s.d_Tb, (size_t)(s.NP + 1) * 8 * 8)); BIGCHK(al((void **)&s.d_ord, n6 * 4)); BIGCHK(al((void **)&s.d_vec, ((size_t)3 * n6 + (size_t)6 * W * W) * 8));
-  BIGCHK(hipMemsetAsync(s.d_fill, 0, (size_t)b.capV * 4, st));
-  BIGCHK(hipMemsetAsync(b.vptr, 0, (size_t)(V + 1) * 4, st));
+  VBA_HIPCHK(err, al((void **)&s.d_Ab, (size_t)(s.NP + 1) * s.ld * 8)); VBA_HIPCHK(err, al((void **)&s.d_Tb, (size_t)(s.NP + 1) * 8 * 8)); VBA_HIPCHK(err, al((void **)&s.d_ord, n6 * 4)); VBA_HIPCHK(err, al((void **)&s.d_vec, ((size_t)3 * n6 + (size_t)6 * W * W) * 8));
+  VBA_HIPCHK(err, hipMemsetAsync(s.d_fill, 0, (size_t)b.capV * 4, st));
+  VBA_HIPCHK(err, hipMemsetAsync(b.vptr, 0, (size_t)(V + 1) * 4, st));
   return VBA_OK;
 }
 inline int big_store_entries(BigStore &s, int E, std::string &err) {
   auto al = [&](void **p, size_t bytes) { return s.arena(p, bytes); };
   BigView &b = s.b;
   b.E = E; b.capE = E > 0 ? E : 1;
-  BIGCHK(al((void **)&b.efr, (size_t)b.capE * 4)); BIGCHK(al((void **)&b.evox, (size_t)b.capE * 4));
-  BIGCHK(al((void **)&b.ecl, (size_t)b.capE * 10 * 8)); BIGCHK(al((void **)&b.gv, (size_t)b.capE * 18 * 8)); BIGCHK(al((void **)&b.es, (size_t)b.capE * 27 * 8));
+  VBA_HIPCHK(err, al((void **)&b.efr, (size_t)b.capE * 4)); VBA_HIPCHK(err, al((void **)&b.evox, (size_t)b.capE * 4));
+  VBA_HIPCHK(err, al((void **)&b.ecl, (size_t)b.capE * 10 * 8)); VBA_HIPCHK(err, al((void **)&b.gv, (size_t)b.capE * 18 * 8)); VBA_HIPCHK(err, al((void **)&b.es, (size_t)b.capE * 27 * 8));
   return VBA_OK;
 }
 inline int big_store_eidx(BigStore &s, hipStream_t st, std::string &err) {
   BigView &b = s.b;
-  BIGCHK(s.arena((void **)&b.eidx, (size_t)b.capV * b.W * 4));
-  BIGCHK(hipMemsetAsync(b.eidx, 0xFF, (size_t)b.capV * b.W * 4, st));
+  VBA_HIPCHK(err, s.arena((void **)&b.eidx, (size_t)b.capV * b.W * 4));
+  VBA_HIPCHK(err, hipMemsetAsync(b.eidx, 0xFF, (size_t)b.capV * b.W * 4, st));
   if (b.V > 0 && b.E > 0) {
     hipLaunchKernelGGL(k_big_eidx, dim3((b.E + 255) / 256), dim3(256), 0, st, b);
-    BIGCHK(hipGetLastError());
+    VBA_HIPCHK(err, hipGetLastError());
   }
   return VBA_OK;
 }
@@ -161,25 +159,25 @@ inline int big_build(BigStore &s, hipStream_t st, int W, const int *offsets, con
   s.reset();
   const int n = offsets[W];
   auto al = [&](void **p, size_t bytes) { return s.arena(p, bytes); };
-  BIGCHK(s.h_cnt.ensure(GCNT_N));
+  VBA_HIPCHK(err, s.h_cnt.ensure(GCNT_N));
   GbaBigView &g = s.g;
   g.W = W; g.npts = n; g.pl = d_pl;
   unsigned int hcap = 1u << 16; while (hcap < 2u * (unsigned)n && hcap < (1u << 28)) hcap <<= 1;
   unsigned int ecap = 1u << 16;                         // (node, frame) pairs of ALL levels share the table: <= points per level
   while ((unsigned long long)ecap < 2ull * (unsigned long long)n * (unsigned)(P.max_layer + 1) && ecap < (1u << 30)) ecap <<= 1;
   g.hmask = hcap - 1; g.emask = ecap - 1;
-  BIGCHK(al((void **)&g.hkeys, (size_t)hcap * 8)); BIGCHK(al((void **)&g.hvals, (size_t)hcap * 4));
-  BIGCHK(al((void **)&g.ekeys, (size_t)ecap * 8)); BIGCHK(al((void **)&g.ecl, (size_t)ecap * 10 * 8));
-  BIGCHK(al((void **)&g.pw, (size_t)n * 3 * 8)); BIGCHK(al((void **)&g.pframe, (size_t)n * 4)); BIGCHK(al((void **)&g.pnode, (size_t)n * 4));
+  VBA_HIPCHK(err, al((void **)&g.hkeys, (size_t)hcap * 8)); VBA_HIPCHK(err, al((void **)&g.hvals, (size_t)hcap * 4));
+  VBA_HIPCHK(err, al((void **)&g.ekeys, (size_t)ecap * 8)); VBA_HIPCHK(err, al((void **)&g.ecl, (size_t)ecap * 10 * 8));
+  VBA_HIPCHK(err, al((void **)&g.pw, (size_t)n * 3 * 8)); VBA_HIPCHK(err, al((void **)&g.pframe, (size_t)n * 4)); VBA_HIPCHK(err, al((void **)&g.pnode, (size_t)n * 4));
   unsigned int *skey_b = nullptr; void *sort_tmp = nullptr; size_t sort_bytes = 0;
-  BIGCHK(al((void **)&g.skey, (size_t)n * 4)); BIGCHK(al((void **)&skey_b, (size_t)n * 4)); BIGCHK(al((void **)&g.sval, (size_t)n * 4)); BIGCHK(al((void **)&g.perm, (size_t)n * 4));
+  VBA_HIPCHK(err, al((void **)&g.skey, (size_t)n * 4)); VBA_HIPCHK(err, al((void **)&skey_b, (size_t)n * 4)); VBA_HIPCHK(err, al((void **)&g.sval, (size_t)n * 4)); VBA_HIPCHK(err, al((void **)&g.perm, (size_t)n * 4));
   if (n > 0) {
-    BIGCHK(sort_pairs_u32(nullptr, sort_bytes, g.skey, skey_b, g.sval, g.perm, (size_t)n, 32u, st));
-    BIGCHK(al(&sort_tmp, sort_bytes + 256));
+    VBA_HIPCHK(err, sort_pairs_u32(nullptr, sort_bytes, g.skey, skey_b, g.sval, g.perm, (size_t)n, 32u, st));
+    VBA_HIPCHK(err, al(&sort_tmp, sort_bytes + 256));
   }
-  BIGCHK(al((void **)&g.cnt, GCNT_N * sizeof(int))); BIGCHK(al((void **)&g.poses, (size_t)W * 12 * 8)); BIGCHK(al((void **)&g.offsets, (size_t)(W + 1) * 4));
-  BIGCHK(hipMemcpyAsync(g.poses, poses, (size_t)W * 12 * 8, hipMemcpyHostToDevice, st));
-  BIGCHK(hipMemcpyAsync(g.offsets, offsets, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, st));
+  VBA_HIPCHK(err, al((void **)&g.cnt, GCNT_N * sizeof(int))); VBA_HIPCHK(err, al((void **)&g.poses, (size_t)W * 12 * 8)); VBA_HIPCHK(err, al((void **)&g.offsets, (size_t)(W + 1) * 4));
+  VBA_HIPCHK(err, hipMemcpyAsync(g.poses, poses, (size_t)W * 12 * 8, hipMemcpyHostToDevice, st));
+  VBA_HIPCHK(err, hipMemcpyAsync(g.offsets, offsets, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, st));
   int cap = s.last_cap;                          // (the node capacity the previous build ended with: no doubling attempts, each of which re-clears the tables)
   const dim3 bk(256), gp((n + 255) / 256);
   for (int attempt = 0; attempt < 10; attempt++) {
@@ -190,10 +188,10 @@ inline int big_build(BigStore &s, hipStream_t st, int W, const int *offsets, con
     for (int k = 0; k < 9; k++) { if (s.arena(&tmp[k], sz[k]) != hipSuccess) { err = "octree node storage"; return VBA_ERR_HIP; } }
     g.nadd = (double *)tmp[0]; g.ncenter = (double *)tmp[1]; g.neval = (double *)tmp[2]; g.nevec = (double *)tmp[3]; g.nql = (float *)tmp[4];
     g.nchild = (int *)tmp[5]; g.nfac = (int *)tmp[6]; g.nexi = (int *)tmp[7]; g.nlayer = (signed char *)tmp[8];
-    BIGCHK(hipMemsetAsync(g.cnt, 0, GCNT_N * sizeof(int), st));
-    BIGCHK(hipMemsetAsync(g.hkeys, 0xFF, (size_t)hcap * 8, st));
-    BIGCHK(hipMemsetAsync(g.nadd, 0, 10 * cp * 8, st));
-    BIGCHK(hipMemsetAsync(g.nexi, 0, cp * 4, st));
+    VBA_HIPCHK(err, hipMemsetAsync(g.cnt, 0, GCNT_N * sizeof(int), st));
+    VBA_HIPCHK(err, hipMemsetAsync(g.hkeys, 0xFF, (size_t)hcap * 8, st));
+    VBA_HIPCHK(err, hipMemsetAsync(g.nadd, 0, 10 * cp * 8, st));
+    VBA_HIPCHK(err, hipMemsetAsync(g.nexi, 0, cp * 4, st));
     if (n > 0) {
       hipLaunchKernelGGL(k_gbab_keys, gp, bk, 0, st, g, P);
       hipLaunchKernelGGL(k_gbab_roots, dim3((hcap + 4095) / 4096), bk, 0, st, g, P);
@@ -201,7 +199,7 @@ inline int big_build(BigStore &s, hipStream_t st, int W, const int *offsets, con
       {
         unsigned int bits = 1; while (bits < 32 && (1ull << bits) <= (unsigned long long)cap) bits++;     // keys are <= cap
         size_t tb = sort_bytes + 256;
-        BIGCHK(sort_pairs_u32(sort_tmp, tb, g.skey, skey_b, g.sval, g.perm, (size_t)n, bits, st));
+        VBA_HIPCHK(err, sort_pairs_u32(sort_tmp, tb, g.skey, skey_b, g.sval, g.perm, (size_t)n, bits, st));
       }
       for (int L = 0; L <= P.max_layer; L++) {
         // entries of the previous level are dead: a planar node keeps its own entries (it stopped descending), so the
@@ -215,10 +213,10 @@ inline int big_build(BigStore &s, hipStream_t st, int W, const int *offsets, con
         if (L < P.max_layer) hipLaunchKernelGGL(k_gbab_descend, gp, bk, 0, st, g);
       }
     }
-    BIGCHK(hipGetLastError());
-    BIGCHK(hipStreamSynchronize(st));
-    BIGCHK(hipMemcpyAsync(s.h_cnt, g.cnt, GCNT_N * sizeof(int), hipMemcpyDeviceToHost, st));
-    BIGCHK(hipStreamSynchronize(st));
+    VBA_HIPCHK(err, hipGetLastError());
+    VBA_HIPCHK(err, hipStreamSynchronize(st));
+    VBA_HIPCHK(err, hipMemcpyAsync(s.h_cnt, g.cnt, GCNT_N * sizeof(int), hipMemcpyDeviceToHost, st));
+    VBA_HIPCHK(err, hipStreamSynchronize(st));
     if (s.h_cnt[GCNT_OVERFLOW] == 2) { err = "keyframe point outside the 21-bit voxel index range"; return VBA_ERR_CAPACITY; }
     if (!s.h_cnt[GCNT_OVERFLOW]) { s.last_cap = cap; break; }
     // (the undersized node arrays stay in the arena until the next build rewinds it)
@@ -234,9 +232,9 @@ inline int big_build(BigStore &s, hipStream_t st, int W, const int *offsets, con
     const int nn = s.h_cnt[GCNT_NODES] < g.cap ? s.h_cnt[GCNT_NODES] : g.cap;
     hipLaunchKernelGGL(k_gbab_vcount, dim3((nn + 255) / 256), bk, 0, st, g, s.d_vcnt);
     hipLaunchKernelGGL(k_big_scan, dim3(1), bk, 0, st, V, s.d_vcnt, b.vptr);
-    BIGCHK(hipStreamSynchronize(st));
-    BIGCHK(hipMemcpyAsync(&E, b.vptr + V, 4, hipMemcpyDeviceToHost, st));
-    BIGCHK(hipStreamSynchronize(st));
+    VBA_HIPCHK(err, hipStreamSynchronize(st));
+    VBA_HIPCHK(err, hipMemcpyAsync(&E, b.vptr + V, 4, hipMemcpyDeviceToHost, st));
+    VBA_HIPCHK(err, hipStreamSynchronize(st));
   }
   { int r = big_store_entries(s, E, err); if (r) return r; }
   if (V > 0) {
@@ -246,7 +244,7 @@ inline int big_build(BigStore &s, hipStream_t st, int W, const int *offsets, con
     hipLaunchKernelGGL(k_gbab_fill, dim3((ecap + 255) / 256), bk, 0, st, g, bt, s.d_fill);
     if (E > 0) hipLaunchKernelGGL(k_gbab_order, dim3((E + 255) / 256), bk, 0, st, b, (const int *)bt.efr, (const double *)bt.ecl);
     hipLaunchKernelGGL(k_gbab_voxels, dim3((nn + 255) / 256), bk, 0, st, g, b);
-    BIGCHK(hipGetLastError());
+    VBA_HIPCHK(err, hipGetLastError());
   }
   return big_store_eidx(s, st, err);
 }
@@ -257,8 +255,8 @@ inline int big_build(BigStore &s, hipStream_t st, int W, const int *offsets, con
 inline int big_hessian(BigStore &s, hipStream_t st, const double *poses, double *hdiag, double *gvec, double *r, std::string &err, int slices) {
   BigView &b = s.b;
   const size_t n6 = (size_t)6 * b.W;
-  BIGCHK(hipMemcpyAsync(b.poses, poses, (size_t)b.W * 12 * 8, hipMemcpyHostToDevice, st));
-  BIGCHK(hipMemsetAsync(b.H, 0, n6 * n6 * 8, st)); BIGCHK(hipMemsetAsync(b.g, 0, n6 * 8, st)); BIGCHK(hipMemsetAsync(b.r, 0, 8, st));
+  VBA_HIPCHK(err, hipMemcpyAsync(b.poses, poses, (size_t)b.W * 12 * 8, hipMemcpyHostToDevice, st));
+  VBA_HIPCHK(err, hipMemsetAsync(b.H, 0, n6 * n6 * 8, st)); VBA_HIPCHK(err, hipMemsetAsync(b.g, 0, n6 * 8, st)); VBA_HIPCHK(err, hipMemsetAsync(b.r, 0, 8, st));
   if (b.E > 0) {
     hipLaunchKernelGGL(k_big_slot, dim3((b.E + 127) / 128), dim3(128), 0, st, b);
     const int nt = (b.W + BIG_TF - 1) / BIG_TF, npair = nt * (nt + 1) / 2, nchunk = (b.V + BIG_VC - 1) / BIG_VC;
@@ -269,12 +267,12 @@ inline int big_hessian(BigStore &s, hipStream_t st, const double *poses, double 
     hipLaunchKernelGGL(k_big_diag, dim3(b.W), dim3(256), 0, st, b);   // after the SYRK atomics on H (stream order)
   }
   hipLaunchKernelGGL(k_big_getdiag, dim3((unsigned)((n6 + 255) / 256)), dim3(256), 0, st, b.H, (int)n6, s.d_vec);
-  BIGCHK(hipGetLastError());
-  BIGCHK(hipStreamSynchronize(st));
-  BIGCHK(hipMemcpyAsync(hdiag, s.d_vec, n6 * 8, hipMemcpyDeviceToHost, st));
-  BIGCHK(hipMemcpyAsync(gvec, b.g, n6 * 8, hipMemcpyDeviceToHost, st));
-  BIGCHK(hipMemcpyAsync(r, b.r, 8, hipMemcpyDeviceToHost, st));
-  BIGCHK(hipStreamSynchronize(st));
+  VBA_HIPCHK(err, hipGetLastError());
+  VBA_HIPCHK(err, hipStreamSynchronize(st));
+  VBA_HIPCHK(err, hipMemcpyAsync(hdiag, s.d_vec, n6 * 8, hipMemcpyDeviceToHost, st));
+  VBA_HIPCHK(err, hipMemcpyAsync(gvec, b.g, n6 * 8, hipMemcpyDeviceToHost, st));
+  VBA_HIPCHK(err, hipMemcpyAsync(r, b.r, 8, hipMemcpyDeviceToHost, st));
+  VBA_HIPCHK(err, hipStreamSynchronize(st));
   return VBA_OK;
 }
 // the six diagonal entries of every 6x6 cross block of the Hessian of the last big_hessian (before the gauge): [W][W][6]
@@ -282,22 +280,22 @@ inline int big_block_diagonals(BigStore &s, hipStream_t st, double *out, std::st
   const int W = s.b.W;
   const size_t n6 = (size_t)6 * W, cnt = (size_t)6 * W * W;
   hipLaunchKernelGGL(k_big_blockdiag, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, s.b.H, W, s.d_vec + 3 * n6);
-  BIGCHK(hipGetLastError());
-  BIGCHK(hipStreamSynchronize(st));
-  BIGCHK(hipMemcpyAsync(out, s.d_vec + 3 * n6, cnt * 8, hipMemcpyDeviceToHost, st));
-  BIGCHK(hipStreamSynchronize(st));
+  VBA_HIPCHK(err, hipGetLastError());
+  VBA_HIPCHK(err, hipStreamSynchronize(st));
+  VBA_HIPCHK(err, hipMemcpyAsync(out, s.d_vec + 3 * n6, cnt * 8, hipMemcpyDeviceToHost, st));
+  VBA_HIPCHK(err, hipStreamSynchronize(st));
   return VBA_OK;
 }
 // only_residual (VM:391-420): also refreshes the per-voxel eigen state
 inline int big_residual(BigStore &s, hipStream_t st, const double *poses, double *r, std::string &err) {
   BigView &b = s.b;
-  BIGCHK(hipMemcpyAsync(b.poses, poses, (size_t)b.W * 12 * 8, hipMemcpyHostToDevice, st));
-  BIGCHK(hipMemsetAsync(b.r, 0, 8, st));
+  VBA_HIPCHK(err, hipMemcpyAsync(b.poses, poses, (size_t)b.W * 12 * 8, hipMemcpyHostToDevice, st));
+  VBA_HIPCHK(err, hipMemsetAsync(b.r, 0, 8, st));
   if (b.V > 0) hipLaunchKernelGGL(k_big_residual, dim3((b.V + 255) / 256), dim3(256), 0, st, b);
-  BIGCHK(hipGetLastError());
-  BIGCHK(hipStreamSynchronize(st));
-  BIGCHK(hipMemcpyAsync(r, b.r, 8, hipMemcpyDeviceToHost, st));
-  BIGCHK(hipStreamSynchronize(st));
+  VBA_HIPCHK(err, hipGetLastError());
+  VBA_HIPCHK(err, hipStreamSynchronize(st));
+  VBA_HIPCHK(err, hipMemcpyAsync(r, b.r, 8, hipMemcpyDeviceToHost, st));
+  VBA_HIPCHK(err, hipStreamSynchronize(st));
   return VBA_OK;
 }
 
@@ -318,7 +316,7 @@ double big_q1(const double *dxi, const double *hd, const double *g, double u, in
 // ord = Eigen's pivot order (host).  Factorisation and back substitution run on the device; the host gets dxi (n doubles).
 int big_solve(BigStore &s, hipStream_t st, const int *ord, double u, double *dxi, std::string &err) {
   const int n = 6 * s.b.W, NP = s.NP, ld = s.ld;
-  BIGCHK(hipMemcpyAsync(s.d_ord, ord, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  VBA_HIPCHK(err, hipMemcpyAsync(s.d_ord, ord, (size_t)n * 4, hipMemcpyHostToDevice, st));
   const long long tot = (long long)(NP + 1) * NP;
   hipLaunchKernelGGL(k_bigl_setup, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, s.b.H, s.b.g, s.d_ord, n, NP, ld, u, s.d_Ab);
   for (int k0 = 0; k0 < NP; k0 += 8) {
@@ -336,10 +334,10 @@ int big_solve(BigStore &s, hipStream_t st, const int *ord, double u, double *dxi
   }
   double *d_dxi = s.d_vec + 2 * (size_t)n;
   hipLaunchKernelGGL(k_bigl_bs_out, dim3((n + 255) / 256), dim3(256), 0, st, s.d_Ab, NP, ld, n, s.d_ord, d_dxi);
-  BIGCHK(hipGetLastError());
-  BIGCHK(hipStreamSynchronize(st));
-  BIGCHK(hipMemcpyAsync(dxi, d_dxi, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-  BIGCHK(hipStreamSynchronize(st));
+  VBA_HIPCHK(err, hipGetLastError());
+  VBA_HIPCHK(err, hipStreamSynchronize(st));
+  VBA_HIPCHK(err, hipMemcpyAsync(dxi, d_dxi, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  VBA_HIPCHK(err, hipStreamSynchronize(st));
   return VBA_OK;
 }
 

@@ -16,12 +16,6 @@ void map_init(MapStore &s, const vba_options &o) {
   for (int i = 0; i < VBA_MAX_WIN; i++) { s.mp[i] = i; s.npts[i] = 0; }   // VS:3158-3160
 }
 
-#define MAPCHK(expr)                                                                 \
-  do {                                                                               \
-    hipError_t _e = (expr);                                                          \
-    if (_e != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(_e); return VBA_ERR_HIP; } \
-  } while (0)
-
 inline MapParams map_params(const MapStore &s) {
   MapParams P;
   P.W = s.opt.win_size; P.max_layer = s.opt.max_layer; P.max_points = s.opt.max_points; P.thread_num = s.opt.thread_num;
@@ -58,15 +52,15 @@ std::vector<DevArr> fix_arrays(MapView &v) {
 // grow a family of [rows][cap] arrays from oldcap to newcap, keeping the first `used` columns; new space zero-filled.  All or nothing
 // (grow_family, vba_mem.hpp): after a failure the owners and the view slots are as they were, under the capacity the caller still records
 inline int grow_arrays(std::vector<DevMem<char>> &own, const std::vector<DevArr> &arrs, size_t oldcap, size_t newcap, size_t used, hipStream_t st, std::string &err) {
-  MAPCHK(grow_family(own, arrs, oldcap, newcap, used, st));
+  VBA_HIPCHK(err, grow_family(own, arrs, oldcap, newcap, used, st));
   for (size_t i = 0; i < arrs.size(); i++) *arrs[i].slot = own[i].p;
   return VBA_OK;
 }
 
 int map_read_counters(MapStore &s, hipStream_t st, std::string &err) {
   hipLaunchKernelGGL(k_words_to_host, dim3(1), dim3(64), 0, st, s.v.cnt, s.h_cnt.p, (int)CNT_N);
-  MAPCHK(hipGetLastError());
-  MAPCHK(hipStreamSynchronize(st));
+  VBA_HIPCHK(err, hipGetLastError());
+  VBA_HIPCHK(err, hipStreamSynchronize(st));
   s.ub_nodes = s.h_cnt[CNT_NODES]; s.ub_roots = s.h_cnt[CNT_ROOTS]; s.ub_used = s.h_cnt[CNT_USED]; s.cnt_stale = false;
   return VBA_OK;
 }
@@ -74,18 +68,18 @@ int map_read_counters(MapStore &s, hipStream_t st, std::string &err) {
 int map_hash_alloc(MapStore &s, unsigned int cap, hipStream_t st, std::string &err) {
   // the new table is built in locals and adopted at the end: an early return frees it and leaves the map on its old one
   DevMem<unsigned long long> nk; DevMem<int> nv; DevMem<unsigned int> nf;
-  MAPCHK(nk.ensure(cap));
-  MAPCHK(nv.ensure(cap));
+  VBA_HIPCHK(err, nk.ensure(cap));
+  VBA_HIPCHK(err, nv.ensure(cap));
   if (s.det) {   // (no insert is in flight between calls: every slot reads DET_NONE)
-    MAPCHK(nf.ensure(cap));
-    MAPCHK(hipMemsetAsync(nf.p, 0x7F, (size_t)cap * 4, st));
+    VBA_HIPCHK(err, nf.ensure(cap));
+    VBA_HIPCHK(err, hipMemsetAsync(nf.p, 0x7F, (size_t)cap * 4, st));
   }
   hipLaunchKernelGGL(k_fill_u64, dim3(1024), dim3(256), 0, st, nk.p, KEY_EMPTY, (size_t)cap);
-  MAPCHK(hipMemsetAsync(nv.p, 0xFF, (size_t)cap * 4, st));
+  VBA_HIPCHK(err, hipMemsetAsync(nv.p, 0xFF, (size_t)cap * 4, st));
   if (s.hkeys) {
     hipLaunchKernelGGL(k_rehash, dim3((s.hcap + 255) / 256), dim3(256), 0, st, s.v.hkeys, s.v.hvals, s.v.hmask, nk.p, nv.p, cap - 1);
     hipLaunchKernelGGL(k_copy_counter, dim3(1), dim3(1), 0, st, s.v.cnt, (int)CNT_ROOTS, (int)CNT_USED);   // the tombstones are gone
-    MAPCHK(hipStreamSynchronize(st));   // (before the moves below free the old table)
+    VBA_HIPCHK(err, hipStreamSynchronize(st));   // (before the moves below free the old table)
     s.ub_used = s.ub_roots;
   }
   s.hkeys = std::move(nk); s.hvals = std::move(nv); s.hfirst = std::move(nf);
@@ -95,11 +89,11 @@ int map_hash_alloc(MapStore &s, unsigned int cap, hipStream_t st, std::string &e
 
 int map_base(MapStore &s, hipStream_t st, std::string &err) {
   if (s.allocated) return VBA_OK;
-  MAPCHK(s.cnt.ensure(CNT_N));
-  MAPCHK(s.fhist.ensure(EXTRACT_NB_MAX));
-  MAPCHK(hipMemsetAsync(s.cnt.p, 0, CNT_N * sizeof(int), st));
-  MAPCHK(s.poses.ensure(VBA_MAX_WIN * 12));
-  MAPCHK(s.h_cnt.ensure(CNT_N + 16));
+  VBA_HIPCHK(err, s.cnt.ensure(CNT_N));
+  VBA_HIPCHK(err, s.fhist.ensure(EXTRACT_NB_MAX));
+  VBA_HIPCHK(err, hipMemsetAsync(s.cnt.p, 0, CNT_N * sizeof(int), st));
+  VBA_HIPCHK(err, s.poses.ensure(VBA_MAX_WIN * 12));
+  VBA_HIPCHK(err, s.h_cnt.ensure(CNT_N + 16));
   std::memset(s.h_cnt.p, 0, CNT_N * sizeof(int) + 64);
   s.v.cnt = s.cnt; s.v.fhist = s.fhist; s.v.poses = s.poses;
   // initial root table: 2^20 slots, or (with the max_points_per_scan capacity hint) the power of two above 4x the hint
@@ -131,11 +125,11 @@ inline int map_ensure(MapStore &s, hipStream_t st, size_t need_nodes, size_t nee
     while (nc < need_pts) nc *= 2;
     int r = grow_arrays(s.scan_mem, scan_arrays(s.v, W), (size_t)s.v.max_pts, nc, (size_t)s.v.max_pts, st, err);
     if (r) return r;
-    if (s.v.max_pts == 0) { MAPCHK(hipMemsetAsync(s.v.pnode, 0xFF, (size_t)W * nc * 4, st)); MAPCHK(hipMemsetAsync(s.v.pleaf, 0xFF, (size_t)W * nc * 4, st)); }
+    if (s.v.max_pts == 0) { VBA_HIPCHK(err, hipMemsetAsync(s.v.pnode, 0xFF, (size_t)W * nc * 4, st)); VBA_HIPCHK(err, hipMemsetAsync(s.v.pleaf, 0xFF, (size_t)W * nc * 4, st)); }
     else {  // new tail of every slot must read "no node"
       for (int sl = 0; sl < W; sl++) {
-        MAPCHK(hipMemsetAsync(s.v.pnode + (size_t)sl * nc + s.v.max_pts, 0xFF, (nc - s.v.max_pts) * 4, st));
-        MAPCHK(hipMemsetAsync(s.v.pleaf + (size_t)sl * nc + s.v.max_pts, 0xFF, (nc - s.v.max_pts) * 4, st));
+        VBA_HIPCHK(err, hipMemsetAsync(s.v.pnode + (size_t)sl * nc + s.v.max_pts, 0xFF, (nc - s.v.max_pts) * 4, st));
+        VBA_HIPCHK(err, hipMemsetAsync(s.v.pleaf + (size_t)sl * nc + s.v.max_pts, 0xFF, (nc - s.v.max_pts) * 4, st));
       }
     }
     s.v.max_pts = (int)nc;
@@ -176,23 +170,23 @@ bool is_device_ptr(const void *p) {
   return a.type == hipMemoryTypeDevice;
 }
 inline int map_stage(MapStore &s, size_t bytes, std::string &err) {
-  MAPCHK(s.d_stage.ensure(bytes));
+  VBA_HIPCHK(err, s.d_stage.ensure(bytes));
   return VBA_OK;
 }
 inline int map_set_counter(MapStore &s, hipStream_t st, int which, int val, std::string &err) {   // stream-ordered, no host sync
   hipLaunchKernelGGL(k_set_counter, dim3(1), dim3(1), 0, st, s.v.cnt, which, val);
-  MAPCHK(hipGetLastError());
+  VBA_HIPCHK(err, hipGetLastError());
   return VBA_OK;
 }
 
 // cnt[to] = sum over the ranks of cnt[from]  (no-op for an unsharded map)
 inline int map_global_count(MapStore &s, hipStream_t st, int from, int to, std::string &err) {
   if (s.n_ranks <= 1 || !s.allreduce) return VBA_OK;
-  MAPCHK(s.d_gc.ensure(2));
+  VBA_HIPCHK(err, s.d_gc.ensure(2));
   hipLaunchKernelGGL(k_cnt_to_f64, dim3(1), dim3(1), 0, st, s.v.cnt, from, s.d_gc.p);
   if (s.allreduce(s.d_gc, 1)) { err = "collective failed while summing a map counter over the ranks"; return VBA_ERR_HIP; }
   hipLaunchKernelGGL(k_f64_to_cnt, dim3(1), dim3(1), 0, st, s.d_gc.p, s.v.cnt, to);
-  MAPCHK(hipGetLastError());
+  VBA_HIPCHK(err, hipGetLastError());
   return VBA_OK;
 }
 
@@ -200,10 +194,10 @@ inline int map_global_count(MapStore &s, hipStream_t st, int from, int to, std::
 inline int map_sort_reserve(MapStore &s, hipStream_t st, std::string &err) {
   if (s.sort_tmp_for >= s.v.max_pts) return VBA_OK;
   size_t need = 0;
-  MAPCHK(sort_pairs_u32(nullptr, need, s.v.skey_a, s.v.skey_b, s.v.sval_a, s.v.sval_b, (size_t)s.v.max_pts, 32u, st));
+  VBA_HIPCHK(err, sort_pairs_u32(nullptr, need, s.v.skey_a, s.v.skey_b, s.v.sval_a, s.v.sval_b, (size_t)s.v.max_pts, 32u, st));
   if (need > s.d_sort_tmp.n) {
-    MAPCHK(hipStreamSynchronize(st));
-    MAPCHK(s.d_sort_tmp.ensure(need + 256));
+    VBA_HIPCHK(err, hipStreamSynchronize(st));
+    VBA_HIPCHK(err, s.d_sort_tmp.ensure(need + 256));
   }
   s.sort_tmp_for = s.v.max_pts;
   return VBA_OK;
@@ -252,24 +246,24 @@ int map_cut_voxel(MapStore &s, hipStream_t st, int win_count, int n, const doubl
     const size_t bytes = (size_t)n * 3 * 8 + (var ? (size_t)n * 9 * 8 : 0);
     r = map_stage(s, bytes, err);
     if (r) return r;
-    MAPCHK(hipMemcpyAsync(s.d_stage, pnt_body, (size_t)n * 3 * 8, hipMemcpyHostToDevice, st));
+    VBA_HIPCHK(err, hipMemcpyAsync(s.d_stage, pnt_body, (size_t)n * 3 * 8, hipMemcpyHostToDevice, st));
     d_pts = (const double *)s.d_stage.p;
     if (var) {
-      MAPCHK(hipMemcpyAsync(s.d_stage + (size_t)n * 3 * 8, var, (size_t)n * 9 * 8, hipMemcpyHostToDevice, st));
+      VBA_HIPCHK(err, hipMemcpyAsync(s.d_stage + (size_t)n * 3 * 8, var, (size_t)n * 9 * 8, hipMemcpyHostToDevice, st));
       d_var = (const double *)(s.d_stage + (size_t)n * 3 * 8);
     }
   }
   if (var) s.have_var = true;
   {  // pose upload through a pinned ring: no implicit synchronisation of a pageable copy
-    MAPCHK(s.h_pose_ring.ensure(8 * 40));
+    VBA_HIPCHK(err, s.h_pose_ring.ensure(8 * 40));
     const int k = s.pose_next; s.pose_next = (k + 1) & 7;
-    if (!s.pose_ev[k]) MAPCHK(hipEventCreateWithFlags(&s.pose_ev[k], hipEventDisableTiming));
-    else MAPCHK(hipEventSynchronize(s.pose_ev[k]));
+    if (!s.pose_ev[k]) VBA_HIPCHK(err, hipEventCreateWithFlags(&s.pose_ev[k], hipEventDisableTiming));
+    else VBA_HIPCHK(err, hipEventSynchronize(s.pose_ev[k]));
     // entry = the device image poses[0 .. 34): pose (12) | 4 unused | rot_var, tsl_var (18) — one copy command
     std::memcpy(s.h_pose_ring + 40 * k, pose, 12 * sizeof(double));
     if (cov6) std::memcpy(s.h_pose_ring + 40 * k + 16, cov6, 18 * sizeof(double));
-    MAPCHK(hipMemcpyAsync(s.v.poses, s.h_pose_ring + 40 * k, (cov6 ? 34 : 12) * sizeof(double), hipMemcpyHostToDevice, st));
-    MAPCHK(hipEventRecord(s.pose_ev[k], st));
+    VBA_HIPCHK(err, hipMemcpyAsync(s.v.poses, s.h_pose_ring + 40 * k, (cov6 ? 34 : 12) * sizeof(double), hipMemcpyHostToDevice, st));
+    VBA_HIPCHK(err, hipEventRecord(s.pose_ev[k], st));
   }
   const MapParams P = map_params(s);
   const int nb = (n + 255) / 256;
@@ -294,8 +288,8 @@ int map_cut_voxel(MapStore &s, hipStream_t st, int win_count, int n, const doubl
     if (lds_big < (size_t)4 * 64 * 33 * 8) lds_big = (size_t)4 * 64 * 33 * 8;             // bitmap + prefix, then the four term images in the same space
     static LdsOptIn opt_in_var, opt_in_novar;
     int dev = 0; hipGetDevice(&dev);
-    MAPCHK(opt_in_var(dev, (const void *)k_ins_accum_big<true>, 160 * 1024 - 64));
-    MAPCHK(opt_in_novar(dev, (const void *)k_ins_accum_big<false>, 160 * 1024 - 64));
+    VBA_HIPCHK(err, opt_in_var(dev, (const void *)k_ins_accum_big<true>, 160 * 1024 - 64));
+    VBA_HIPCHK(err, opt_in_novar(dev, (const void *)k_ins_accum_big<false>, 160 * 1024 - 64));
     if (var) {
       hipLaunchKernelGGL((k_ins_accum_ord<true>), dim3(nwg), dim3(64), 0, st, s.v, P, slot);
       hipLaunchKernelGGL((k_ins_accum_big<true>), dim3(256), dim3(256), lds_big, st, s.v, P, slot, n, win);
@@ -304,10 +298,10 @@ int map_cut_voxel(MapStore &s, hipStream_t st, int win_count, int n, const doubl
       hipLaunchKernelGGL((k_ins_accum_big<false>), dim3(256), dim3(256), lds_big, st, s.v, P, slot, n, win);
     }
   }
-  MAPCHK(hipGetLastError());
+  VBA_HIPCHK(err, hipGetLastError());
   // no read-back: capacity was reserved for the worst case (n new roots), so this call cannot overflow
   s.ub_nodes += n; s.ub_roots += n; s.ub_used += n; s.cnt_stale = true;
-  if (!is_device_ptr(pnt_body)) MAPCHK(hipStreamSynchronize(st));   // the caller's host point buffers may go away (pose and covariance went through the pinned ring)
+  if (!is_device_ptr(pnt_body)) VBA_HIPCHK(err, hipStreamSynchronize(st));   // the caller's host point buffers may go away (pose and covariance went through the pinned ring)
   return VBA_OK;
 }
 
@@ -323,7 +317,7 @@ int map_cut_voxel_fix(MapStore &s, hipStream_t st, int n, const double *pnt_worl
   if (!is_device_ptr(pnt_world)) {
     r = map_stage(s, (size_t)n * 3 * 8, err);
     if (r) return r;
-    MAPCHK(hipMemcpyAsync(s.d_stage, pnt_world, (size_t)n * 3 * 8, hipMemcpyHostToDevice, st));
+    VBA_HIPCHK(err, hipMemcpyAsync(s.d_stage, pnt_world, (size_t)n * 3 * 8, hipMemcpyHostToDevice, st));
     d_pts = (const double *)s.d_stage.p;
   }
   const MapParams P = map_params(s);
@@ -338,11 +332,11 @@ int map_cut_voxel_fix(MapStore &s, hipStream_t st, int n, const double *pnt_worl
   hipLaunchKernelGGL(k_fix_leaf, dim3(nb), dim3(256), 0, st, s.v, P, base, n);
   {
     size_t tb = s.d_sort_tmp.n;
-    MAPCHK(sort_pairs_u32(s.d_sort_tmp.p, tb, s.v.skey_a, s.v.skey_b, s.v.sval_a, s.v.sval_b, (size_t)n, map_key_bits(s), st));
+    VBA_HIPCHK(err, sort_pairs_u32(s.d_sort_tmp.p, tb, s.v.skey_a, s.v.skey_b, s.v.sval_a, s.v.sval_b, (size_t)n, map_key_bits(s), st));
   }
   hipLaunchKernelGGL(k_fix_heads, dim3(nb), dim3(256), 0, st, s.v, n);
   hipLaunchKernelGGL((k_fix_accum_ord<FIXCOV_KEEP>), dim3(n < 4096 ? n : 4096), dim3(64), 0, st, s.v, P, base, n, d_pts, (const int *)nullptr, (const void *)nullptr);
-  MAPCHK(hipGetLastError());
+  VBA_HIPCHK(err, hipGetLastError());
   r = map_read_counters(s, st, err);
   if (r) return r;
   if (s.h_cnt[CNT_OVERFLOW]) { err = "voxel map capacity exceeded during fixed-point insert"; return VBA_ERR_CAPACITY; }
@@ -366,7 +360,7 @@ int map_recut(MapStore &s, hipStream_t st, int win_count, const double *poses, b
     // room for every current leaf to split once per level (checked again through the overflow flag)
     r = map_ensure(s, st, nodes_ub + 8 * (size_t)(attempt ? s.h_cnt[CNT_NODES] : 65536), 0, 0, err);
     if (r) return r;
-    MAPCHK(hipMemcpyAsync(s.v.poses, poses, (size_t)(win_count > 0 ? win_count : 1) * 12 * sizeof(double), hipMemcpyHostToDevice, st));
+    VBA_HIPCHK(err, hipMemcpyAsync(s.v.poses, poses, (size_t)(win_count > 0 ? win_count : 1) * 12 * sizeof(double), hipMemcpyHostToDevice, st));
     const MapParams P = map_params(s);
     int max_n = 0;
     for (int i = 0; i < win_count; i++) if (s.npts[s.mp[i]] > max_n) max_n = s.npts[s.mp[i]];
@@ -407,7 +401,7 @@ int map_recut(MapStore &s, hipStream_t st, int win_count, const double *poses, b
         hipLaunchKernelGGL(k_extract_count<0>, dim3(grid_nodes), dim3(256), 0, st, s.v, P, multi ? 1 : 0);
       }
     }
-    MAPCHK(hipGetLastError());
+    VBA_HIPCHK(err, hipGetLastError());
     r = map_read_counters(s, st, err);
     if (r) return r;
     if (s.h_cnt[CNT_OVERFLOW] == 4) { err = "root hash table full during scan insertion"; return VBA_ERR_CAPACITY; }
@@ -433,21 +427,21 @@ int map_extract_factors(MapStore &s, hipStream_t st, FactorView f, std::string &
     if (s.det) {   // stable: (bucket, node id)
       const size_t need = (size_t)nbuckets * nwg;
       if (need > s.d_whist.n) {
-        MAPCHK(hipStreamSynchronize(st));
-        MAPCHK(s.d_whist.ensure(need));
+        VBA_HIPCHK(err, hipStreamSynchronize(st));
+        VBA_HIPCHK(err, s.d_whist.ensure(need));
       }
       hipLaunchKernelGGL(k_extract_key<true>, dim3(nwg), dim3(256), 0, st, s.v, P, nfac, nbuckets, s.d_whist.p);
       hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(1024), 0, st, s.d_whist.p, (int)need, s.v.cnt, -1, 0, -1);
       hipLaunchKernelGGL(k_extract_scatter_det, dim3(nwg), dim3(256), 0, st, s.v, (const int *)s.d_whist.p, nfac, nbuckets);
     } else {
-      MAPCHK(hipMemsetAsync(s.v.fhist, 0, (size_t)nbuckets * sizeof(int), st));
+      VBA_HIPCHK(err, hipMemsetAsync(s.v.fhist, 0, (size_t)nbuckets * sizeof(int), st));
       hipLaunchKernelGGL(k_extract_key<false>, dim3(nwg), dim3(256), 0, st, s.v, P, nfac, nbuckets, (int *)nullptr);
       hipLaunchKernelGGL(k_extract_scan, dim3(1), dim3(1024), 0, st, s.v, nbuckets);
       hipLaunchKernelGGL(k_extract_scatter, dim3(nwg), dim3(256), 0, st, s.v, nfac, nbuckets);
     }
   }
   if (nfac > 0) hipLaunchKernelGGL(k_extract_write, dim3((nfac + XW_F - 1) / XW_F), dim3(256), (size_t)(10 * s.opt.win_size + 33) * (XW_F + 1) * 8, st, s.v, P, f, nfac);
-  MAPCHK(hipGetLastError());
+  VBA_HIPCHK(err, hipGetLastError());
   *n_factors = s.h_cnt[CNT_FACTORS];
   return VBA_OK;
 }
@@ -463,7 +457,7 @@ int map_margi(MapStore &s, hipStream_t st, int win_count, const double *poses, d
   r = map_ensure(s, st, 0, 0, (size_t)s.h_cnt[CNT_FIX] + (size_t)s.npts[slot0] + 1, err);
   if (r) return r;
   hipLaunchKernelGGL(k_set_counter2, dim3(1), dim3(1), 0, st, s.v.cnt, (int)CNT_OVERFLOW, 0, (int)CNT_TAKE, 0);
-  MAPCHK(hipMemcpyAsync(s.v.poses, poses, (size_t)win_count * 12 * sizeof(double), hipMemcpyHostToDevice, st));
+  VBA_HIPCHK(err, hipMemcpyAsync(s.v.poses, poses, (size_t)win_count * 12 * sizeof(double), hipMemcpyHostToDevice, st));
   const MapParams P = map_params(s);
   const int nn = s.h_cnt[CNT_NODES] < s.v.cap ? s.h_cnt[CNT_NODES] : s.v.cap;
   const int n_slide_before = s.n_ranks > 1 ? s.h_cnt[CNT_SLIDE_G] : s.h_cnt[CNT_SLIDE];
@@ -483,7 +477,7 @@ int map_margi(MapStore &s, hipStream_t st, int win_count, const double *poses, d
     hipLaunchKernelGGL(k_margi_clear_points, dim3((s.v.max_pts + 255) / 256, W), b, 0, st, s.v, P, s.epoch);
     s.npts[slot0] = 0;
   }
-  MAPCHK(hipGetLastError());
+  VBA_HIPCHK(err, hipGetLastError());
   r = map_read_counters(s, st, err);
   if (r) return r;
   if (s.h_cnt[CNT_OVERFLOW] == 2) { err = "Error: opt_state out of range"; return VBA_ERR_OPT_STATE; }
@@ -502,15 +496,15 @@ int map_reset(MapStore &s, hipStream_t st, std::string &err) {
   if (!s.allocated) return VBA_OK;
   const int W = s.opt.win_size;
   hipStreamSynchronize(st);
-  for (auto &a : node_arrays(s.v, W)) MAPCHK(hipMemsetAsync(*a.slot, 0, a.elem * a.rows * (size_t)s.v.cap, st));
-  if (s.v.pnode) MAPCHK(hipMemsetAsync(s.v.pnode, 0xFF, (size_t)W * s.v.max_pts * 4, st));
-  if (s.v.pleaf) MAPCHK(hipMemsetAsync(s.v.pleaf, 0xFF, (size_t)W * s.v.max_pts * 4, st));
-  if (s.v.fnode) MAPCHK(hipMemsetAsync(s.v.fnode, 0xFF, (size_t)s.v.cap_fix * 4, st));
+  for (auto &a : node_arrays(s.v, W)) VBA_HIPCHK(err, hipMemsetAsync(*a.slot, 0, a.elem * a.rows * (size_t)s.v.cap, st));
+  if (s.v.pnode) VBA_HIPCHK(err, hipMemsetAsync(s.v.pnode, 0xFF, (size_t)W * s.v.max_pts * 4, st));
+  if (s.v.pleaf) VBA_HIPCHK(err, hipMemsetAsync(s.v.pleaf, 0xFF, (size_t)W * s.v.max_pts * 4, st));
+  if (s.v.fnode) VBA_HIPCHK(err, hipMemsetAsync(s.v.fnode, 0xFF, (size_t)s.v.cap_fix * 4, st));
   hipLaunchKernelGGL(k_fill_u64, dim3(1024), dim3(256), 0, st, s.v.hkeys, KEY_EMPTY, (size_t)s.hcap);
-  MAPCHK(hipMemsetAsync(s.v.hvals, 0xFF, (size_t)s.hcap * 4, st));
-  if (s.v.hfirst) MAPCHK(hipMemsetAsync(s.v.hfirst, 0x7F, (size_t)s.hcap * 4, st));
-  MAPCHK(hipMemsetAsync(s.v.cnt, 0, CNT_N * sizeof(int), st));
-  MAPCHK(hipStreamSynchronize(st));
+  VBA_HIPCHK(err, hipMemsetAsync(s.v.hvals, 0xFF, (size_t)s.hcap * 4, st));
+  if (s.v.hfirst) VBA_HIPCHK(err, hipMemsetAsync(s.v.hfirst, 0x7F, (size_t)s.hcap * 4, st));
+  VBA_HIPCHK(err, hipMemsetAsync(s.v.cnt, 0, CNT_N * sizeof(int), st));
+  VBA_HIPCHK(err, hipStreamSynchronize(st));
   std::memset(s.h_cnt, 0, CNT_N * sizeof(int));
   for (int i = 0; i < VBA_MAX_WIN; i++) { s.mp[i] = i; s.npts[i] = 0; }
   s.have_var = false; s.ub_nodes = 0; s.ub_roots = 0; s.ub_used = 0; s.cnt_stale = false;
@@ -602,7 +596,7 @@ int map_prune(MapStore &s, hipStream_t st, double jour, int dist, std::string &e
   }
   hipLaunchKernelGGL(k_prune_zero, dim3((nn + 255) / 256, 130 + 10 * s.opt.win_size), dim3(256), 0, st, s.v, s.opt.win_size, s.epoch);
   if (s.h_cnt[CNT_FIX] > 0) hipLaunchKernelGGL(k_prune_fix, dim3((s.h_cnt[CNT_FIX] + 255) / 256), dim3(256), 0, st, s.v);
-  MAPCHK(hipGetLastError());
+  VBA_HIPCHK(err, hipGetLastError());
   return map_read_counters(s, st, err);
 }
 
@@ -615,10 +609,10 @@ inline size_t fix_source_stage_bytes(size_t n) { return ((n * 24 + 255) & ~(size
 
 inline int map_sort_reserve_n(MapStore &s, hipStream_t st, size_t n, std::string &err) {
   size_t need = 0;
-  MAPCHK(sort_pairs_u32(nullptr, need, nullptr, nullptr, nullptr, nullptr, n, 32u, st));
+  VBA_HIPCHK(err, sort_pairs_u32(nullptr, need, nullptr, nullptr, nullptr, nullptr, n, 32u, st));
   if (need + 256 > s.d_sort_tmp.n) {
-    MAPCHK(hipStreamSynchronize(st));
-    MAPCHK(s.d_sort_tmp.ensure(need + 256));
+    VBA_HIPCHK(err, hipStreamSynchronize(st));
+    VBA_HIPCHK(err, s.d_sort_tmp.ensure(need + 256));
   }
   return VBA_OK;
 }
@@ -633,7 +627,7 @@ int map_fix_source_ensure(MapStore &s, hipStream_t st, size_t nodes, size_t fix,
     r = map_hash_alloc(s, nc, st, err);
     if (r) return r;
   }
-  if (fix_source_stage_bytes(n) > s.d_stage.n) MAPCHK(hipStreamSynchronize(st));
+  if (fix_source_stage_bytes(n) > s.d_stage.n) VBA_HIPCHK(err, hipStreamSynchronize(st));
   r = map_stage(s, fix_source_stage_bytes(n), err);
   if (r) return r;
   return map_sort_reserve_n(s, st, n, err);
@@ -673,14 +667,14 @@ int map_cut_voxel_fix_source(MapStore &s, hipStream_t st, int n, const FixSource
   hipLaunchKernelGGL(k_fix_leaf, dim3(nb), dim3(256), 0, st, s.v, P, base, n);
   {
     size_t tb = s.d_sort_tmp.n;
-    MAPCHK(sort_pairs_u32(s.d_sort_tmp.p, tb, s.v.skey_a, s.v.skey_b, s.v.sval_a, s.v.sval_b, (size_t)n, map_key_bits(s), st));
+    VBA_HIPCHK(err, sort_pairs_u32(s.d_sort_tmp.p, tb, s.v.skey_a, s.v.skey_b, s.v.sval_a, s.v.sval_b, (size_t)n, map_key_bits(s), st));
   }
   hipLaunchKernelGGL(k_fix_heads, dim3(nb), dim3(256), 0, st, s.v, n);
   const dim3 ga(n < 4096 ? n : 4096), ba(64);
   if (src.cov_kind == FIXCOV_DIAG_F32) hipLaunchKernelGGL((k_fix_accum_ord<FIXCOV_DIAG_F32>), ga, ba, 0, st, s.v, P, base, n, (const double *)world, (const int *)srcrow, src.d_cov);
   else if (src.cov_kind == FIXCOV_FULL_F64) hipLaunchKernelGGL((k_fix_accum_ord<FIXCOV_FULL_F64>), ga, ba, 0, st, s.v, P, base, n, (const double *)world, (const int *)srcrow, src.d_cov);
   else hipLaunchKernelGGL((k_fix_accum_ord<FIXCOV_ZERO>), ga, ba, 0, st, s.v, P, base, n, (const double *)world, (const int *)srcrow, (const void *)nullptr);
-  MAPCHK(hipGetLastError());
+  VBA_HIPCHK(err, hipGetLastError());
   if (src.cov_kind != FIXCOV_ZERO) s.have_var = true;       // the recut reads fvar (k_recut_push<true>)
   r = map_read_counters(s, st, err);
   if (r) return r;
@@ -702,16 +696,16 @@ static int map_odom_point_loop(MapStore &s, hipStream_t st, const MapParams &P, 
 // is pinned and holds the image on entry and the result block on return.
 int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomEkf *h_img, int n, const double *d_pts,
                       const double *d_var, double *d_partial, std::string &err) {
-  MAPCHK(hipMemcpyAsync(d_S, h_img, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, st));
+  VBA_HIPCHK(err, hipMemcpyAsync(d_S, h_img, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, st));
   const MapParams P = map_params(s);
   for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
     const int nb = map_odom_point_loop(s, st, P, d_S, n, d_pts, d_var, d_partial);
     hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, st, d_S, (const double *)d_partial, nb, iter, 0);
   }
-  MAPCHK(hipGetLastError());
+  VBA_HIPCHK(err, hipGetLastError());
   const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
-  MAPCHK(hipMemcpyAsync((char *)h_img + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, st));
-  MAPCHK(hipStreamSynchronize(st));
+  VBA_HIPCHK(err, hipMemcpyAsync((char *)h_img + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, st));
+  VBA_HIPCHK(err, hipStreamSynchronize(st));
   return VBA_OK;
 }
 // vba_debug_odom_sums on the voxel map: the image uploaded, ONE point loop as the call above queues it, the reduction of
@@ -719,11 +713,11 @@ int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomE
 // allocated).  d_sums: 34 doubles of device memory.
 int map_odom_debug_sums(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, const vbh::OdomEkf *h_img, int n, const double *d_pts,
                         const double *d_var, double *d_partial, double *d_sums, int *nb_out, std::string &err) {
-  MAPCHK(hipMemcpyAsync(d_S, h_img, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, st));
+  VBA_HIPCHK(err, hipMemcpyAsync(d_S, h_img, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, st));
   const int nb = map_odom_point_loop(s, st, map_params(s), d_S, n, d_pts, d_var, d_partial);
   hipLaunchKernelGGL(k_odom_sums, dim3(1), dim3(256), 0, st, (const double *)d_partial, nb, d_sums);
-  MAPCHK(hipGetLastError());
-  MAPCHK(hipStreamSynchronize(st));
+  VBA_HIPCHK(err, hipGetLastError());
+  VBA_HIPCHK(err, hipStreamSynchronize(st));
   *nb_out = nb;
   return VBA_OK;
 }
@@ -733,16 +727,16 @@ int map_odom_debug_sums(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, const vb
 int map_debug_plane_update(hipStream_t st, int n, const double *in, double *out, std::string &err) {
   const size_t N = (size_t)n;
   DevMem<double> buf;                           // [in 67 n | ncov 45 n | nplane 43 n | out 43 n]
-  MAPCHK(buf.ensure(N * (67 + 45 + 43 + 43)));
+  VBA_HIPCHK(err, buf.ensure(N * (67 + 45 + 43 + 43)));
   double *d_in = buf.p, *d_cov = d_in + N * 67, *d_plane = d_cov + N * 45, *d_out = d_plane + N * 43;
-  MAPCHK(hipMemcpyAsync(d_in, in, N * 67 * sizeof(double), hipMemcpyHostToDevice, st));
-  MAPCHK(hipMemsetAsync(d_cov, 0, N * (45 + 43 + 43) * sizeof(double), st));
+  VBA_HIPCHK(err, hipMemcpyAsync(d_in, in, N * 67 * sizeof(double), hipMemcpyHostToDevice, st));
+  VBA_HIPCHK(err, hipMemsetAsync(d_cov, 0, N * (45 + 43 + 43) * sizeof(double), st));
   MapView v{};
   v.cap = n; v.ncov = d_cov; v.nplane = d_plane;
   hipLaunchKernelGGL(k_debug_plane_update, dim3((n + 255) / 256), dim3(256), 0, st, v, n, (const double *)d_in, d_out);
-  MAPCHK(hipGetLastError());
-  MAPCHK(hipMemcpyAsync(out, d_out, N * 43 * sizeof(double), hipMemcpyDeviceToHost, st));
-  MAPCHK(hipStreamSynchronize(st));
+  VBA_HIPCHK(err, hipGetLastError());
+  VBA_HIPCHK(err, hipMemcpyAsync(out, d_out, N * 43 * sizeof(double), hipMemcpyDeviceToHost, st));
+  VBA_HIPCHK(err, hipStreamSynchronize(st));
   return VBA_OK;
 }
 

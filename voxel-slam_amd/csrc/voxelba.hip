@@ -152,9 +152,9 @@ namespace {
 
 int upload_poses(vba_ctx *c, const double *poses) {
   const int W = c->opt.win_size;
-  int st = ensure_pin(c, 65536);
+  int st = ensure_pin(c, kPinFixed);
   if (st) return st;
-  std::memcpy(c->h_pin, poses, (size_t)W * 12 * sizeof(double));
+  std::memcpy(c->h_pin, poses, (size_t)W * 12 * sizeof(double));      // the pose region, kPinPoses = 0
   HIPCHK(c, hipMemcpyAsync(c->d_poses, c->h_pin, (size_t)W * 12 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   return VBA_OK;
 }
@@ -193,7 +193,9 @@ int lm_init_flush(vba_ctx *c) {
 // the IMU workgroup of LI-BA rides a lidar Hessian launch when its LDS fits this ceiling (150 KB hold it up to W = 16)
 constexpr size_t kLiRideLds = 150 * 1024;
 
-// diagnostic (VBA_K3_STAMPS=1): 16 in-kernel clock stamps per workgroup of the Hessian pass.  k3_stamps_buffer: the cleared device
+// ---------------------------------------------------------------- diagnostics of the BA core (-DVBA_DIAG builds, tools/README.md)
+// The call paths hold one call each; in the shipped build diag_env answers nullptr and LmDev::pad stays 0, so each returns at its first test.
+// VBA_K3_STAMPS=1: 16 in-kernel clock stamps per workgroup of the Hessian pass.  k3_stamps_buffer: the cleared device
 // buffer in front of the launch, nullptr unless asked for; k3_stamps_dump: the first nst of four workgroups, relative to the earliest.
 long long *k3_stamps_buffer(vba_ctx *c) {
   static const bool want_stamps = diag_env("VBA_K3_STAMPS") != nullptr;     // -DVBA_DIAG builds only
@@ -220,49 +222,107 @@ void k3_stamps_dump(vba_ctx *c, const long long *d_st, int nb, int nst, const ch
   fprintf(stderr, "[k3 stamps] last workgroup ends at %lld ticks (100 MHz wall clock: 1 tick = 10 ns)%s\n", tmax, legend);
 }
 
+// VBA_K4_STAMPS=1: the same for the residual pass, whose stamps are in a separate STAMPS instantiation; the production kernel holds none
+long long *k4_stamps_buffer(vba_ctx *c) {
+  static const bool want_stamps = diag_env("VBA_K4_STAMPS") != nullptr;
+  if (!want_stamps) return nullptr;
+  static long long *d_st = nullptr;
+  if (!d_st) hipMalloc((void **)&d_st, 2048 * 4 * 8);
+  hipMemsetAsync(d_st, 0, 2048 * 4 * 8, c->stream);
+  return d_st;
+}
+void k4_stamps_dump(vba_ctx *c, int nb, const long long *d_st) {
+  if (!d_st) return;
+  const int n = nb < 2048 ? nb : 2048;
+  std::vector<long long> h((size_t)n * 4);
+  hipStreamSynchronize(c->stream);
+  hipMemcpy(h.data(), d_st, h.size() * 8, hipMemcpyDeviceToHost);
+  long long t0 = h[0];
+  for (int b = 0; b < n; b++) if (h[b * 4] && h[b * 4] < t0) t0 = h[b * 4];
+  double a = 0, e = 0, w = 0, last = 0;
+  for (int b = 0; b < n; b++) { a += h[b * 4 + 1] - h[b * 4]; e += h[b * 4 + 2] - h[b * 4 + 1]; w += h[b * 4 + 3] - h[b * 4 + 2]; if (h[b * 4 + 3] - t0 > last) last = h[b * 4 + 3] - t0; }
+  fprintf(stderr, "[k4 stamps] %d workgroups: loads+transforms %.0f, frame sum + eigen %.0f, stores+reduce %.0f cycles (mean per workgroup); last one ends at %.0f cycles\n", n, a / n, e / n, w / n, last);
+}
+
+// the cycle table a solve kernel left in LmDev::stamps (bit 16 of the VBA_DEBUG_SOLVE mask): phases, then load+factor per panel
+void solve_cycles_dump(const char *kernel, const LmDev *h, int max_panels) {
+  if (!(h->pad & 16)) return;
+  fprintf(stderr, "[%s cycles] prologue %lld | tile load %lld | factorisation %lld | backsub %lld | epilogue %lld | panels:", kernel, h->stamps[1] - h->stamps[0],
+          h->stamps[2] - h->stamps[1], h->stamps[3] - h->stamps[2], h->stamps[4] - h->stamps[3], h->stamps[5] - h->stamps[4]);
+  const int npr = (int)h->stamps[6];             // panels run: k_lm_solve_m ends with the panel of the last live pivot, k_li_solve skips those from column n on
+  for (int kb = 0; kb < npr && kb < max_panels; kb++) fprintf(stderr, " %lld+%lld", h->stamps[9 + 2 * kb] - h->stamps[8 + 2 * kb], kb < npr - 1 ? h->stamps[10 + 2 * kb] - h->stamps[9 + 2 * kb] : 0LL);
+  fprintf(stderr, " | %d panels run\n", npr);
+}
+
+// VBA_LI_TIMES=1: host-side phases of one li_ba_device call, and the cycle tables of its kernels (VBA_DEBUG_SOLVE mask bits 16, 32, 64)
+struct LiPhases {
+  using Clock = std::chrono::steady_clock;
+  bool on; Clock::time_point t0; double at[3] = {0, 0, 0};      // at: us since t0 when uploaded, enqueued, drained
+  LiPhases() { static const bool want_times = diag_env("VBA_LI_TIMES") != nullptr; on = want_times; if (on) t0 = Clock::now(); }
+  double since() const { return std::chrono::duration<double, std::micro>(Clock::now() - t0).count(); }
+  void mark(int i) { if (on) at[i] = since(); }
+  void report(const vba_ctx *c, const LmDev *hl) const {
+    if (!on) return;
+    if (hl->pad & 16) fprintf(stderr, "[k_li_solve prologue] stage imu %lld | stage lidar %lld | diag+g %lld | rank %lld\n", hl->stamps[50] - hl->stamps[0], hl->stamps[51] - hl->stamps[50], hl->stamps[52] - hl->stamps[51], hl->stamps[1] - hl->stamps[52]);
+    solve_cycles_dump("k_li_solve", hl, 20);
+    if (hl->pad & 64) fprintf(stderr, "[k_li_imu cycles] factor algebra (one lane per factor) %lld | cov^-1 joc %lld | contractions %lld\n", hl->stamps[41] - hl->stamps[40], hl->stamps[42] - hl->stamps[41], hl->stamps[43] - hl->stamps[42]);
+    if (hl->pad & 32) { double v[6]; std::memcpy(v, &hl->stamps[58], sizeof(v)); fprintf(stderr, "[li r1 parts] rank %d: rimu %.10g lidar %.10g | %.10g %.10g | %.10g %.10g\n", c->rank, v[0], v[1], v[2], v[3], v[4], v[5]); }
+    fprintf(stderr, "[li_ba_device] upload %.1f us | enqueue %.1f | gpu drained at %.1f | total %.1f\n", at[0], at[1] - at[0], at[2], since());
+  }
+};
+
+// What a Hessian launch carries besides the lidar pass: up to three riders; an empty value carries nothing, the makers say which.
+struct PassCargo {
+  LmDev *lm = nullptr; const double *k4p = nullptr; int k4nb = 0;   // the previous iteration's accept/reject step and its K4 partials
+  LiJob li{}; size_t li_lds = 0;                                     // the IMU workgroup of LI-BA and its dynamic LDS
+  bool init = false;                                                 // the LM call's pending init (lm_init_arg)
+};
+PassCargo cargo_pending_update(vba_ctx *c) { PassCargo g; g.lm = c->d_lm; g.k4p = c->d_k4part; g.k4nb = c->lm.k4_nb; return g; }
+PassCargo cargo_call_init() { PassCargo g; g.init = true; return g; }
+PassCargo cargo_imu_job(vba_ctx *c, size_t lds_imu) { PassCargo g; g.li = LiJob{c->d_lm, c->d_li, c->d_imu, c->d_himu, c->d_gimu}; g.li_lds = lds_imu; return g; }
+
 template <int W>
-int launch_hessian2_t(vba_ctx *c, const double *poses_dev, const int *gate, int head, int end, int *nblocks_out, LmDev *lm, const double *k4p, int k4nb,
-                      const LiJob &li, size_t li_lds, bool init) {
+int launch_hessian2_t(vba_ctx *c, const double *poses_dev, const int *gate, int head, int end, int *nblocks_out, const PassCargo &g) {
   using C = HessCfg2<W>;
+  const bool imu = g.li.dev != nullptr;
   const int ntiles = (end - head + C::TV - 1) / C::TV;
-  const int maxb = li.dev ? c->max_blocks_hess - 1 : c->max_blocks_hess;      // (the IMU workgroup of LI-BA takes a CU of its own)
+  const int maxb = imu ? c->max_blocks_hess - 1 : c->max_blocks_hess;      // (the IMU workgroup of LI-BA takes a CU of its own)
   int nb = ntiles < maxb ? ntiles : maxb;
   if (nb < 1) nb = 1;
   static LdsOptIn opt_in;      // (a lidar-only launch asks for C::LDS_BYTES, one that carries the IMU workgroup for up to kLiRideLds)
   HIPCHK(c, opt_in(c->device, (const void *)k_hessian2<W>, C::LDS_BYTES > kLiRideLds ? C::LDS_BYTES : kLiRideLds));
   long long *stamps = k3_stamps_buffer(c);
-  const size_t lds = (li.dev && li_lds > C::LDS_BYTES) ? li_lds : C::LDS_BYTES;
-  hipLaunchKernelGGL(k_hessian2<W>, dim3(nb + (li.dev ? 1 : 0)), dim3(C::NT), lds, c->stream, c->fv, poses_dev, head, end, ntiles, c->d_partial, gate, stamps, lm, k4p, k4nb,
-                     nb, li, lm_init_arg<W>(c, init));
+  const size_t lds = (imu && g.li_lds > C::LDS_BYTES) ? g.li_lds : C::LDS_BYTES;
+  hipLaunchKernelGGL(k_hessian2<W>, dim3(nb + (imu ? 1 : 0)), dim3(C::NT), lds, c->stream, c->fv, poses_dev, head, end, ntiles, c->d_partial, gate, stamps, g.lm, g.k4p, g.k4nb,
+                     nb, g.li, lm_init_arg<W>(c, g.init));
   k3_stamps_dump(c, stamps, nb, 15, "");
   *nblocks_out = nb;
   return VBA_OK;
 }
 
 template <int W>
-int launch_hessian3_t(vba_ctx *c, const double *poses_dev, const int *gate, int *nblocks_out, LmDev *lm, const double *k4p, int k4nb, const LiJob &li, size_t li_lds) {
+int launch_hessian3_t(vba_ctx *c, const double *poses_dev, const int *gate, int *nblocks_out, const PassCargo &g) {
   using C = HessCfg3<W>;
-  const int nb = li.dev ? c->max_blocks_hess - 1 : c->max_blocks_hess;      // (the IMU workgroup of LI-BA takes a CU of its own)
+  const bool imu = g.li.dev != nullptr;
+  const int nb = imu ? c->max_blocks_hess - 1 : c->max_blocks_hess;      // (the IMU workgroup of LI-BA takes a CU of its own)
   static LdsOptIn opt_in;
   HIPCHK(c, opt_in(c->device, (const void *)k_hessian3<W>, C::LDS_BYTES > kLiRideLds ? C::LDS_BYTES : kLiRideLds));
-  const size_t lds = (li.dev && li_lds > C::LDS_BYTES) ? li_lds : C::LDS_BYTES;
+  const size_t lds = (imu && g.li_lds > C::LDS_BYTES) ? g.li_lds : C::LDS_BYTES;
   long long *stamps = k3_stamps_buffer(c);
-  hipLaunchKernelGGL(k_hessian3<W>, dim3(nb + (li.dev ? 1 : 0)), dim3(C::NT), lds, c->stream, c->fv, poses_dev, c->nvox, c->d_partial, gate, lm, k4p, k4nb, nb, li, stamps);
+  hipLaunchKernelGGL(k_hessian3<W>, dim3(nb + (imu ? 1 : 0)), dim3(C::NT), lds, c->stream, c->fv, poses_dev, c->nvox, c->d_partial, gate, g.lm, g.k4p, g.k4nb, nb, g.li, stamps);
   k3_stamps_dump(c, stamps, nb, 16, "; per workgroup: start, prologue, then per tile [A, B, combine, E]");
   *nblocks_out = nb;
   return VBA_OK;
 }
 
-// init: the launch may carry the call's pending LM init (k_hessian2 only: the opt-in occupancy-compact pass takes the stand-alone
-// init kernel in front of it)
-int launch_hessian(vba_ctx *c, const double *pd, const int *gate, int head, int end, int *nb, LmDev *lm = nullptr, const double *k4p = nullptr, int k4nb = 0,
-                   const LiJob &li = LiJob{}, size_t li_lds = 0, bool init = false) {
+// The init rider travels in k_hessian2 only: the opt-in occupancy-compact pass takes the stand-alone init kernel in front of it.
+int launch_hessian(vba_ctx *c, const double *pd, const int *gate, int head, int end, int *nb, const PassCargo &g) {
   // whole store, W <= 10: the occupancy-compact pass (vba_kernels_h3.hpp); sub-ranges and wider windows: the dense-tile pass
   if (head == 0 && end == c->nvox && c->opt.win_size <= 10 && c->use_h3) {
-    if (init) { const int st = lm_init_flush(c); if (st) return st; }
-    return for_window<2, 10>(c->opt.win_size, [&](auto wc) { return launch_hessian3_t<decltype(wc)::value>(c, pd, gate, nb, lm, k4p, k4nb, li, li_lds); });
+    if (g.init) { const int st = lm_init_flush(c); if (st) return st; }
+    return for_window<2, 10>(c->opt.win_size, [&](auto wc) { return launch_hessian3_t<decltype(wc)::value>(c, pd, gate, nb, g); });
   }
-  return for_window<2, 16>(c->opt.win_size, [&](auto wc) { return launch_hessian2_t<decltype(wc)::value>(c, pd, gate, head, end, nb, lm, k4p, k4nb, li, li_lds, init); });
+  return for_window<2, 16>(c->opt.win_size, [&](auto wc) { return launch_hessian2_t<decltype(wc)::value>(c, pd, gate, head, end, nb, g); });
 }
 
 #ifndef VBA_K4_TV
@@ -275,48 +335,35 @@ int launch_hessian(vba_ctx *c, const double *pd, const int *gate, int head, int 
 inline bool residual_vpl(const vba_ctx *c, int n) { return n > c->residual_vpl_from; }
 inline int residual_nb(const vba_ctx *c, int n) { return residual_vpl(c, n) ? (n + 63) / 64 : (n + VBA_K4_TV - 1) / VBA_K4_TV; }
 
-// diagnostic (VBA_K4_STAMPS=1): in-kernel clock stamps of a separate STAMPS instantiation; the production kernel holds none
-void k4_stamps_dump(vba_ctx *c, int nb, long long *d_st) {
-  const int n = nb < 2048 ? nb : 2048;
-  std::vector<long long> h((size_t)n * 4);
-  hipStreamSynchronize(c->stream);
-  hipMemcpy(h.data(), d_st, h.size() * 8, hipMemcpyDeviceToHost);
-  long long t0 = h[0];
-  for (int b = 0; b < n; b++) if (h[b * 4] && h[b * 4] < t0) t0 = h[b * 4];
-  double a = 0, e = 0, w = 0, last = 0;
-  for (int b = 0; b < n; b++) { a += h[b * 4 + 1] - h[b * 4]; e += h[b * 4 + 2] - h[b * 4 + 1]; w += h[b * 4 + 3] - h[b * 4 + 2]; if (h[b * 4 + 3] - t0 > last) last = h[b * 4 + 3] - t0; }
-  fprintf(stderr, "[k4 stamps] %d workgroups: loads+transforms %.0f, frame sum + eigen %.0f, stores+reduce %.0f cycles (mean per workgroup); last one ends at %.0f cycles\n", n, a / n, e / n, w / n, last);
-}
+// what launch_residual has decided, and the one launch line of each kernel (VPL: k_residual_v; FUSED: its instance that writes the LM init)
+struct ResidualLaunch {
+  vba_ctx *c; const double *pd; const int *gate; int head, end; double *part; int nb; long long *stamps; bool init;
+  template <int W, bool VPL, bool STAMPS, bool FUSED = false>
+  void go() const {
+    if constexpr (VPL) hipLaunchKernelGGL((k_residual_v<W, STAMPS, FUSED>), dim3(nb), dim3(64), 0, c->stream, c->fv, pd, head, end, part, gate, stamps, lm_init_arg<W>(c, FUSED));
+    else hipLaunchKernelGGL((k_residual_s<W, VBA_K4_TV, STAMPS>), dim3(nb), dim3(ResCfg<W, VBA_K4_TV>::NT), 0, c->stream, c->fv, pd, head, end, part, gate, stamps, lm_init_arg<W>(c, init));
+  }
+};
 
 // residual pass over voxels [head, end) (end > head); its residual_nb partials (one per workgroup) go to dst or d_partial
 int launch_residual(vba_ctx *c, const double *pd, const int *gate, int head, int end, double *dst = nullptr, bool init = false) {
-  double *part = dst ? dst : c->d_partial;
-  const int nb = residual_nb(c, end - head);
-  static const bool want_stamps = diag_env("VBA_K4_STAMPS") != nullptr;
-  static long long *d_st = nullptr;
-  if (want_stamps) {
-    if (!d_st) hipMalloc((void **)&d_st, 2048 * 4 * 8);
-    hipMemsetAsync(d_st, 0, 2048 * 4 * 8, c->stream);
-  }
-  if (want_stamps && init) {                // (the diagnostic STAMPS instances carry no init: it becomes a launch of its own)
+  long long *stamps = k4_stamps_buffer(c);
+  if (stamps && init) {                     // (the diagnostic STAMPS instances carry no init: it becomes a launch of its own)
     const int st = lm_init_flush(c);
     if (st) return st;
     init = false;
   }
-  const int st = residual_vpl(c, end - head) ? for_window<2, 16>(c->opt.win_size, [&](auto wc) {
+  const bool vpl = residual_vpl(c, end - head);
+  const ResidualLaunch r{c, pd, gate, head, end, dst ? dst : c->d_partial, residual_nb(c, end - head), stamps, init};
+  const int st = for_window<2, 16>(c->opt.win_size, [&](auto wc) {
     constexpr int W = decltype(wc)::value;
-    if (want_stamps) hipLaunchKernelGGL((k_residual_v<W, true>), dim3(nb), dim3(64), 0, c->stream, c->fv, pd, head, end, part, gate, d_st, lm_init_arg<W>(c, false));
-    else if (init && c->lm_init.pending) hipLaunchKernelGGL((k_residual_v<W, false, true>), dim3(nb), dim3(64), 0, c->stream, c->fv, pd, head, end, part, gate, (long long *)nullptr, lm_init_arg<W>(c, true));
-    else hipLaunchKernelGGL((k_residual_v<W, false>), dim3(nb), dim3(64), 0, c->stream, c->fv, pd, head, end, part, gate, (long long *)nullptr, lm_init_arg<W>(c, false));
-    return VBA_OK;
-  }) : for_window<2, 16>(c->opt.win_size, [&](auto wc) {
-    constexpr int W = decltype(wc)::value;
-    using RC = ResCfg<W, VBA_K4_TV>;
-    if (want_stamps) hipLaunchKernelGGL((k_residual_s<W, VBA_K4_TV, true>), dim3(nb), dim3(RC::NT), 0, c->stream, c->fv, pd, head, end, part, gate, d_st, lm_init_arg<W>(c, init));
-    else hipLaunchKernelGGL((k_residual_s<W, VBA_K4_TV, false>), dim3(nb), dim3(RC::NT), 0, c->stream, c->fv, pd, head, end, part, gate, (long long *)nullptr, lm_init_arg<W>(c, init));
+    if (!vpl) { if (stamps) r.go<W, false, true>(); else r.go<W, false, false>(); }    // the slot-parallel kernel takes the init by argument
+    else if (stamps) r.go<W, true, true>();
+    else if (init && c->lm_init.pending) r.go<W, true, false, true>();                 // the voxel-per-lane kernel has an instance for it
+    else r.go<W, true, false>();
     return VBA_OK;
   });
-  if (st == VBA_OK && want_stamps) k4_stamps_dump(c, nb, d_st);
+  if (st == VBA_OK) k4_stamps_dump(c, r.nb, stamps);
   return st;
 }
 
@@ -355,17 +402,16 @@ int ctx_allgather(vba_ctx *c, double *buf, size_t chunk) {
 namespace {
 
 // device passes on device-resident poses (gate == nullptr: unconditional)
-int hessian_pass(vba_ctx *c, const double *poses_dev, const int *gate, int head, int end, LmDev *lm = nullptr, const double *k4p = nullptr, int k4nb = 0,
-                 const LiJob &li = LiJob{}, size_t li_lds = 0, bool init = false) {
+int hessian_pass(vba_ctx *c, const double *poses_dev, const int *gate, int head, int end, const PassCargo &g) {
   const int W = c->opt.win_size, nout = nout_tl(W);
   if (end <= head) {
-    if (init) { const int st = lm_init_flush(c); if (st) return st; }     // (no kernel to carry it)
+    if (g.init) { const int st = lm_init_flush(c); if (st) return st; }     // (no kernel to carry it)
     HIPCHK(c, hipMemsetAsync(c->d_out, 0, (size_t)nout * sizeof(double), c->stream));
   } else {
     int nb = 0;
     TimedSpan s1{}, s2{};
     span_begin(c, "hessian", s1);
-    int st = launch_hessian(c, poses_dev, gate, head, end, &nb, lm, k4p, k4nb, li, li_lds, init);
+    int st = launch_hessian(c, poses_dev, gate, head, end, &nb, g);
     if (st) return st;
     span_end(c, "hessian", s1);
     span_begin(c, "reduce", s2);
@@ -403,6 +449,24 @@ int residual_pass(vba_ctx *c, const double *poses_dev, const int *gate, int head
   return VBA_OK;
 }
 
+// Sharded (multi-rank) LM calls, the lidar one and the LI one: ONE collective per iteration.  After the residual pass at the trial
+// poses the Hessian pass is run there too (speculating that the step is accepted) and [H | g | r] is all-reduced once: its r (the
+// sum of the eigenvalues the residual pass just stored) is the trial residual the accept test needs, and on acceptance H is already
+// the next iteration's Hessian; on a reject the solve keeps using its saved copy (`raw`), exactly as VM:443 skips divide_thread.
+// So such a call needs a Hessian pass at the head of an iteration only until its first trial step has run:
+bool needs_hessian_pass(const vba_ctx *c) { return !(c->collective() && c->lm.have_hess); }
+// the trial step; launch_update(r) enqueues the caller's accept/reject kernel on the all-reduced trial residual r (device address)
+template <class LaunchUpdate>
+int sharded_trial_step(vba_ctx *c, const LmPtrs &p, int V, LaunchUpdate launch_update) {
+  int st = VBA_OK;
+  if (V > 0) st = launch_residual(c, p.xt, p.run_res, 0, V);   // only_residual VM:467: refreshes the eigen state at the trial poses
+  if (!st) st = hessian_pass(c, p.xt, p.run_res, 0, V, PassCargo{});   // speculative divide_thread there + the one all-reduce
+  if (st) return st;
+  c->lm.have_hess = true;
+  launch_update(c->d_out + (nout_tl(c->opt.win_size) - 1));
+  return VBA_OK;
+}
+
 // tile layout -> full layout [H | g | r] in d_full (host consumers only; the device LM reads the tile layout directly)
 int tiles_to_full(vba_ctx *c, const double *src) {
   return for_window<2, 16>(c->opt.win_size, [&](auto wc) {
@@ -416,7 +480,7 @@ int tiles_to_full(vba_ctx *c, const double *src) {
 int eval_hessian_dev(vba_ctx *c, const double *poses, int head, int end) {
   int st = upload_poses(c, poses);
   if (st) return st;
-  st = hessian_pass(c, c->d_poses, nullptr, head, end);
+  st = hessian_pass(c, c->d_poses, nullptr, head, end, PassCargo{});
   if (st) return st;
   return tiles_to_full(c, c->d_out);
 }
@@ -434,9 +498,9 @@ int ensure_partial(vba_ctx *c, size_t doubles) {
 
 // host copies of the reduced device results
 int fetch(vba_ctx *c, const double *d_src, size_t n, double *dst) {
-  int st = ensure_pin(c, n + 65536);
+  int st = ensure_pin(c, n + kPinFixed);
   if (st) return st;
-  double *stage = c->h_pin + 32768;  // poses live in the first part
+  double *stage = c->h_pin + kPinStage;  // poses live in the first part
   HIPCHK(c, hipStreamSynchronize(c->stream));   // drain first: a D2H copy queued behind in-flight kernels completes much later (measured)
   HIPCHK(c, hipMemcpyAsync(stage, d_src, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -506,7 +570,7 @@ int vba_create(const vba_options *opt, vba_ctx **out) {
   c->fv.W = W;
   if (c->d_poses.ensure((size_t)VBA_MAX_WIN * 12) != hipSuccess || c->d_out.ensure((size_t)nout_tl(W) + 64) != hipSuccess ||
       c->d_full.ensure((size_t)nout + 64) != hipSuccess || c->d_scal.ensure(64) != hipSuccess) { vba_destroy(c); return VBA_ERR_HIP; }
-  if (ensure_partial(c, (size_t)kMaxBlocksHess * (nout_tl(W) > nout ? nout_tl(W) : nout)) != VBA_OK || ensure_pin(c, 65536 + (size_t)nout + 1024) != VBA_OK) { vba_destroy(c); return VBA_ERR_HIP; }
+  if (ensure_partial(c, (size_t)kMaxBlocksHess * (nout_tl(W) > nout ? nout_tl(W) : nout)) != VBA_OK || ensure_pin(c, kPinCreate + (size_t)nout) != VBA_OK) { vba_destroy(c); return VBA_ERR_HIP; }
   if (c->d_lm.ensure(1) != hipSuccess || c->d_raw.ensure((size_t)nout_tl(W) + 64) != hipSuccess || c->h_lm.ensure(1) != hipSuccess) { vba_destroy(c); return VBA_ERR_HIP; }
   if (opt->max_voxels && factor_reserve(c, (int)opt->max_voxels) != VBA_OK) { vba_destroy(c); return VBA_ERR_HIP; }
   map_init(c->map, c->opt);
@@ -645,16 +709,17 @@ int vba_lm_begin(vba_ctx *c, const double *poses, int thd_num) {
   // the ranks, so every rank takes the same branch and none is left waiting in the next collective
   c->nvox_global = c->nvox;
   if (c->collective()) {
-    int st = ensure_pin(c, 65536);
+    int st = ensure_pin(c, kPinFixed);
     if (st) return st;
-    c->h_pin[60000] = (double)c->nvox;
-    HIPCHK(c, hipMemcpyAsync(c->d_scal + 8, c->h_pin + 60000, sizeof(double), hipMemcpyHostToDevice, c->stream));
-    st = ctx_allreduce(c, c->d_scal + 8, 1);
+    double *h_count = c->h_pin + kPinCount, *d_count = c->d_scal + kScalCount;
+    *h_count = (double)c->nvox;
+    HIPCHK(c, hipMemcpyAsync(d_count, h_count, sizeof(double), hipMemcpyHostToDevice, c->stream));
+    st = ctx_allreduce(c, d_count, 1);
     if (st) return st;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_pin + 60000, c->d_scal + 8, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_count, d_count, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->nvox_global = (int)(c->h_pin[60000] + 0.5);
+    c->nvox_global = (int)(*h_count + 0.5);
   }
   return VBA_OK;
 }
@@ -684,7 +749,7 @@ int vba_timing_launch_hessian(vba_ctx *c) {
   int nb = 0;
   int st = lm_init_flush(c);
   if (st) return st;
-  st = launch_hessian(c, lm_ptrs(c).x, nullptr, 0, c->nvox, &nb);
+  st = launch_hessian(c, lm_ptrs(c).x, nullptr, 0, c->nvox, &nb, PassCargo{});
   if (st) return st;
   HIPCHK(c, hipGetLastError());
   return VBA_OK;
@@ -696,21 +761,14 @@ int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
   const int W = c->opt.win_size, nout = nout_of(W), V = c->nvox;
   if (c->nvox_global < c->lm.thd_num) { c->lm_init.pending = false; return VBA_ERR_TOO_FEW_VOXELS; }   // VM:399-403 (and g_size checks of VM:367); the same on every rank
   const LmPtrs p = lm_ptrs(c);
-  // Multi-rank: ONE collective per iteration.  After the residual pass at the trial poses the Hessian pass is run there
-  // too (speculating that the step is accepted) and [H | g | r] is all-reduced once: its r (the sum of the eigenvalues the
-  // residual pass just stored) is the trial residual the accept test needs, and on acceptance H is already the next
-  // iteration's Hessian; on a reject the solve keeps using its saved copy (`raw`), exactly as VM:443 skips divide_thread.
-  const int copy_raw = c->collective() ? 1 : 0;
+  const int copy_raw = c->collective() ? 1 : 0;      // multi-rank: one collective per iteration (sharded_trial_step)
   int st = VBA_OK;
   static const bool no_fuse = diag_env("VBA_NO_FUSED_UPDATE") != nullptr;   // diagnostic: accept/reject always as its own kernel
   if (copy_raw) { st = lm_init_flush(c); if (st) return st; }               // the multi-rank flow takes the stand-alone init
-  if (!(copy_raw && c->lm.have_hess)) {
-    if (c->lm.pending_update) {               // the previous iteration's accept/reject rides in this pass (runs on xt after an accepted step)
-      st = hessian_pass(c, p.x, p.run_hess, 0, V, c->d_lm, c->d_k4part, c->lm.k4_nb);
-      c->lm.pending_update = false;
-    } else {
-      st = hessian_pass(c, p.x, p.run_hess, 0, V, nullptr, nullptr, 0, LiJob{}, 0, true);   // divide_thread  VM:445 (skipped on device after a reject); the first pass of a call carries its init
-    }
+  if (needs_hessian_pass(c)) {
+    // divide_thread  VM:445 (skipped on device after a reject); carries the previous iteration's accept/reject (and then runs on xt after an accepted step), else the call's init
+    st = hessian_pass(c, p.x, p.run_hess, 0, V, c->lm.pending_update ? cargo_pending_update(c) : cargo_call_init());
+    c->lm.pending_update = false;
   }
   if (st) return st;
   TimedSpan sp{};
@@ -724,11 +782,8 @@ int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
   if (st) return st;
   span_end(c, "solve", sp);
   if (copy_raw) {
-    if (V > 0) st = launch_residual(c, p.xt, p.run_res, 0, V);   // only_residual VM:467: refreshes the eigen state at the trial poses
-    if (!st) st = hessian_pass(c, p.xt, p.run_res, 0, V);             // speculative divide_thread there + the one all-reduce
+    st = sharded_trial_step(c, p, V, [&](const double *r) { hipLaunchKernelGGL(k_lm_update, dim3(1), dim3(64), 0, c->stream, c->d_lm, r, 0, W); });
     if (st) return st;
-    c->lm.have_hess = true;
-    hipLaunchKernelGGL(k_lm_update, dim3(1), dim3(64), 0, c->stream, c->d_lm, c->d_out + (nout_tl(W) - 1), 0, W);
   } else {
     const int nb = residual_nb(c, V);
     if ((size_t)nb > c->d_k4part.n) {
@@ -772,9 +827,9 @@ int vba_lm_end(vba_ctx *c, double *poses, double *hess, double *resis2) {
   // draining the stream first is a second trip.
   double *h_hess = nullptr;
   if (hess) {
-    st = ensure_pin(c, 65536 + (size_t)n * n + 1024);
+    st = ensure_pin(c, kPinCreate + (size_t)n * n);
     if (st) return st;
-    h_hess = c->h_pin + 32768;
+    h_hess = c->h_pin + kPinStage;
   }
   const double *src = c->collective() ? c->d_raw : c->d_out;      // *hess = Hess before gauge fixing (VM:446)
   const int upd = c->lm.pending_update ? 1 : 0;
@@ -788,16 +843,10 @@ int vba_lm_end(vba_ctx *c, double *poses, double *hess, double *resis2) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const LmDev *h = c->h_lm;
   if (poses) std::memcpy(poses, h->x, (size_t)W * 12 * sizeof(double));
-  if (hess) std::memcpy(hess, c->h_pin + 32768, (size_t)n * n * sizeof(double));
+  if (hess) std::memcpy(hess, h_hess, (size_t)n * n * sizeof(double));
   if (resis2) { resis2[0] = h->resis_first; resis2[1] = h->r2; }
   c->trace.assign(h->trace, h->trace + 5 * h->n_trace);
-  if (h->pad & 16) {
-    fprintf(stderr, "[k_lm_solve_m cycles] prologue %lld | tile load %lld | factorisation %lld | backsub %lld | epilogue %lld | panels:", h->stamps[1] - h->stamps[0],
-            h->stamps[2] - h->stamps[1], h->stamps[3] - h->stamps[2], h->stamps[4] - h->stamps[3], h->stamps[5] - h->stamps[4]);
-    const int npr = (int)h->stamps[6];             // panels run: the factorisation ends with the panel of the last live pivot
-    for (int kb = 0; kb < npr && kb < 8; kb++) fprintf(stderr, " %lld+%lld", h->stamps[9 + 2 * kb] - h->stamps[8 + 2 * kb], kb < npr - 1 ? h->stamps[10 + 2 * kb] - h->stamps[9 + 2 * kb] : 0LL);
-    fprintf(stderr, " | %d panels run\n", npr);
-  }
+  solve_cycles_dump("k_lm_solve_m", h, 8);
   c->lm.active = false;
   return VBA_OK;
 }
@@ -907,12 +956,10 @@ static int li_setup(vba_ctx *c, const double *states, const double *imus, int gr
   return VBA_OK;
 }
 // the IMU pass rides the lidar Hessian launch when there is one on this rank and its LDS fits beside it
-static bool li_imu_rides(const vba_ctx *c, int copy_raw, int V, size_t lds_imu) { return !(copy_raw && c->lm.have_hess) && V > 0 && lds_imu <= kLiRideLds; }
+static bool li_imu_rides(const vba_ctx *c, int V, size_t lds_imu) { return needs_hessian_pass(c) && V > 0 && lds_imu <= kLiRideLds; }
 
 static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, int max_iter, double *hess, double *resis2) {
-  static const bool want_times = diag_env("VBA_LI_TIMES") != nullptr;   // diagnostic: host-side phases of one call
-  const auto t_0 = std::chrono::steady_clock::now();
-  auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count(); };
+  LiPhases phases;                                                     // diagnostic: host-side phases of one call
   const int W = c->opt.win_size, V = c->nvox, DIM = VBA_DIM, F = W - 1;
   const int n = W * DIM + (gravity ? 3 : 0), nb = gravity ? 33 : 30, n6 = 6 * W;
   if (!gravity) max_iter = 3;                                         // VM:643
@@ -923,18 +970,16 @@ static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, i
   const LmPtrs p = lm_ptrs(c);
   const int copy_raw = c->collective() ? 1 : 0;
   const size_t lds_imu = li_imu_lds(F, nb);
-  const double t_up = since(t_0);
+  phases.mark(0);
   for (int it = 0; it < max_iter; it++) {
     // The IMU factors' workgroup rides in the lidar Hessian launch as block 0 on a CU of its own (k_hessian2).  As a kernel of its own
     // in front of the lidar pass it cost its 28 us + a kernel boundary; on a side stream (fork / join events around it) the two
     // cross-stream dependencies cost more than they hid (209 vs 196 us per iteration).
-    const bool lidar_now = li_imu_rides(c, copy_raw, V, lds_imu);
-    if (lidar_now) {          // the IMU workgroup rides in the lidar Hessian launch
-      const LiJob job{c->d_lm, c->d_li, c->d_imu, c->d_himu, c->d_gimu};
-      st = hessian_pass(c, p.x, p.run_hess, 0, V, nullptr, nullptr, 0, job, lds_imu);   // lidar part of divide_thread (+ all-reduce)
+    if (li_imu_rides(c, V, lds_imu)) {
+      st = hessian_pass(c, p.x, p.run_hess, 0, V, cargo_imu_job(c, lds_imu));   // lidar part of divide_thread (+ all-reduce)
     } else {
       hipLaunchKernelGGL(k_li_imu, dim3(1), dim3(LI_IMU_NT), lds_imu, c->stream, c->d_lm, c->d_li, c->d_imu, c->d_himu, c->d_gimu);
-      if (!(copy_raw && c->lm.have_hess)) st = hessian_pass(c, p.x, p.run_hess, 0, V);
+      if (needs_hessian_pass(c)) st = hessian_pass(c, p.x, p.run_hess, 0, V, PassCargo{});
     }
     if (st) return st;
     TimedSpan s1{};
@@ -950,12 +995,9 @@ static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, i
     });
     span_end(c, "solve", s1);
     if (st) return st;                                                // (the opt-in or the scratch allocation of the W > 10 solve failed: nothing was launched)
-    if (copy_raw) {                                                   // one collective per iteration (see vba_lm_iterate)
-      if (V > 0) st = launch_residual(c, p.xt, p.run_res, 0, V);
-      if (!st) st = hessian_pass(c, p.xt, p.run_res, 0, V);
+    if (copy_raw) {                                                   // one collective per iteration
+      st = sharded_trial_step(c, p, V, [&](const double *r) { hipLaunchKernelGGL(k_li_update, dim3(1), dim3(LI_UPD_NT), 0, c->stream, c->d_lm, c->d_li, c->d_imu, r, 0); });
       if (st) return st;
-      c->lm.have_hess = true;
-      hipLaunchKernelGGL(k_li_update, dim3(1), dim3(LI_UPD_NT), 0, c->stream, c->d_lm, c->d_li, c->d_imu, c->d_out + (nout_tl(W) - 1), 0);
     } else if (V == 0) {
       st = residual_pass(c, p.xt, p.run_res, 0, V, c->d_scal);
       if (st) return st;
@@ -971,14 +1013,16 @@ static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, i
     }
     HIPCHK(c, hipGetLastError());
   }
-  const double t_enq = since(t_0);
+  phases.mark(1);
   // (no drain before the download: with everything packed into ONE copy, queueing it behind the kernels is as fast as draining
   //  first — 497 vs 503 us per call; with five separate copies draining first had been 2-3x faster)
-  const double t_gpu = since(t_0);
+  phases.mark(2);
   // download: accepted state, the factors' bias increments, trace, and (on request) *hess = Hess before gauge fixing —
   // everything lands in ONE pinned block (pageable destinations make every copy a blocking staged transfer)
   // — gathered on the device into one block first: five separate D2H copies cost ~20 us each (110 us per call, measured)
   static_assert(sizeof(LiDev) % 8 == 0 && sizeof(LmDev) % 8 == 0, "packed as doubles");
+  // The block is packed from offset 0 of h_pin and overlays the fixed regions (vba_ctx.hpp): nothing of them is in flight after li_setup (the
+  // count's round trip ends in a synchronise, every pose upload is followed by a fetch, which drains) and this call uses none of them.
   const size_t o_li = 0, o_img = o_li + sizeof(LiDev) / 8, o_hb = o_img + fimg.size(), o_lid = o_hb + (size_t)li_hb_size(W, 1),
                o_lm = o_lid + (size_t)n6 * n6, o_end = o_lm + sizeof(LmDev) / 8;
   st = ensure_pin(c, o_end + 64);
@@ -1029,17 +1073,7 @@ static int li_ba_device(vba_ctx *c, double *states, double *imus, int gravity, i
   }
   if (gravity && resis2) { resis2[0] = hl->resis_first; resis2[1] = hl->r2; }
   c->trace.assign(hl->trace, hl->trace + 5 * hl->n_trace);
-  if (want_times && (hl->pad & 16)) {
-    fprintf(stderr, "[k_li_solve prologue] stage imu %lld | stage lidar %lld | diag+g %lld | rank %lld\n", hl->stamps[50] - hl->stamps[0], hl->stamps[51] - hl->stamps[50], hl->stamps[52] - hl->stamps[51], hl->stamps[1] - hl->stamps[52]);
-    fprintf(stderr, "[k_li_solve cycles] prologue %lld | tile load %lld | factorisation %lld | backsub %lld | epilogue %lld | panels:", hl->stamps[1] - hl->stamps[0],
-            hl->stamps[2] - hl->stamps[1], hl->stamps[3] - hl->stamps[2], hl->stamps[4] - hl->stamps[3], hl->stamps[5] - hl->stamps[4]);
-    const int npr = (int)hl->stamps[6];            // panels run: those from column n on are skipped
-    for (int kb = 0; kb < npr && kb < 20; kb++) fprintf(stderr, " %lld+%lld", hl->stamps[9 + 2 * kb] - hl->stamps[8 + 2 * kb], kb < npr - 1 ? hl->stamps[10 + 2 * kb] - hl->stamps[9 + 2 * kb] : 0LL);
-    fprintf(stderr, " | %d panels run\n", npr);
-  }
-  if (want_times && (hl->pad & 64)) fprintf(stderr, "[k_li_imu cycles] factor algebra (one lane per factor) %lld | cov^-1 joc %lld | contractions %lld\n", hl->stamps[41] - hl->stamps[40], hl->stamps[42] - hl->stamps[41], hl->stamps[43] - hl->stamps[42]);
-  if (want_times && (hl->pad & 32)) { double v[6]; std::memcpy(v, &hl->stamps[58], sizeof(v)); fprintf(stderr, "[li r1 parts] rank %d: rimu %.10g lidar %.10g | %.10g %.10g | %.10g %.10g\n", c->rank, v[0], v[1], v[2], v[3], v[4], v[5]); }
-  if (want_times) fprintf(stderr, "[li_ba_device] upload %.1f us | enqueue %.1f | gpu drained at %.1f | total %.1f\n", t_up, t_enq - t_up, t_gpu, since(t_0));
+  phases.report(c, hl);
   return VBA_OK;
 }
 
@@ -1063,8 +1097,7 @@ static int debug_li_imu_run(vba_ctx *c, int gravity, int flags, const double *st
   const LmPtrs p = lm_ptrs(c);
   const size_t lds_imu = li_imu_lds(F, nb);
   if (flags & (VBA_IMU_RIDE_H2 | VBA_IMU_RIDE_H3)) {
-    const LiJob job{c->d_lm, c->d_li, c->d_imu, c->d_himu, c->d_gimu};
-    st = hessian_pass(c, p.x, p.run_hess, 0, V, nullptr, nullptr, 0, job, lds_imu);
+    st = hessian_pass(c, p.x, p.run_hess, 0, V, cargo_imu_job(c, lds_imu));
     if (st) return st;
   } else {
     hipLaunchKernelGGL(k_li_imu, dim3(1), dim3(LI_IMU_NT), lds_imu, c->stream, c->d_lm, c->d_li, c->d_imu, c->d_himu, c->d_gimu);
@@ -1102,7 +1135,7 @@ int vba_debug_li_imu(vba_ctx *c, int W, int gravity, int flags, const double *st
     // the riding forms need a pushed store, and the lidar kernel is the one the context selects for it (launch_hessian)
     const bool ctx_h3 = c->use_h3 && W <= 10;
     if (c->nvox <= 0 || h3 != ctx_h3) return VBA_ERR_BAD_ARG;
-    if (!li_imu_rides(c, 0, c->nvox, li_imu_lds(W - 1, gravity ? 33 : 30))) return VBA_ERR_BAD_ARG;
+    if (!li_imu_rides(c, c->nvox, li_imu_lds(W - 1, gravity ? 33 : 30))) return VBA_ERR_BAD_ARG;
   }
   for (size_t i = 0; i < (size_t)25 * W; i++) if (!std::isfinite(states[i])) return VBA_ERR_BAD_ARG;
   for (size_t i = 0; i < (size_t)304 * (W - 1); i++) if (!std::isfinite(imus[i])) return VBA_ERR_BAD_ARG;
