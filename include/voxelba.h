@@ -935,6 +935,83 @@ int vba_loop_update(vba_ctx *ctx, vba_loop_map *lm, const double *dx12, int k, c
                     const double *poses_win, int *n_factors);
 
 /* ------------------------------------------------------------------------------------------------
+ * Scan log: the counterpart of the live `ScanPose::pvec` pointers of one session (pvec_buf[0] -> ScanPose::pvec ->
+ * buf_lba2loop -> bl_local, VS:1974-1980 .. VS:2342), resident in HBM.  A scan enters the log from the map's scan ring by a
+ * device-to-device capture before it is marginalised, and the keyframe store, the loop update, pub_localmap and save_pcd read it
+ * in place: between leaving the window and becoming part of a keyframe no point crosses the host boundary.
+ *
+ * Layout: one arena double pnt [cap][3] (body points) and double var [cap][9] (the covariance rows as the map's ring held them: the
+ * world covariances of pvec_update, VH:259), used as a ring of WHOLE scans.  A scan never straddles the arena's end: when the tail
+ * is too short it is skipped, so consecutive scans need not be contiguous and every reader addresses a scan by its own start.
+ * Scans are numbered 0, 1, 2, ... in push order (64 bits); a session that pushes every marginalised scan has seq = win_base + i,
+ * the `count` of save_pcd's file name.  Release is first in, first out.
+ *
+ * Growth: the arena grows by doubling; growing allocates new blocks, copies the live scans device to device in order (packed from
+ * row 0), and frees the old blocks after a synchronise.  Numbers are kept.  After vba_scanlog_reserve(points, scans) no call on the
+ * log allocates device memory while, AT EVERY PUSH of n points,
+ *     live points + gap + n <= points   and   live scans + 1 <= scans,
+ * where gap = the rows at the arena's end that a wrap leaves unused: 0 while the scans lie in ascending order and the new one fits
+ * behind the newest; points - (end of the newest scan) when this push has to skip the tail; points - (end of the last scan before
+ * the skip) for as long as the oldest live scan still lies above the newest.  (A session of scans of at most m points that holds at
+ * most s of them live is safe with points = (s + 1) * m.)  This is exactly the test of the ring bookkeeping
+ * (csrc/vba_scanlog_ring.hpp, place), which is what decides when a push grows the arena.  vba_scanlog_allocations counts the
+ * calls that allocated and their bytes, as vba_kf_allocations does.
+ *
+ * Ordering and threads: the log works on its context's stream.  It is not locked internally beyond its bookkeeping: the producer
+ * thread (the push calls) and ONE consumer thread (release and the readers: range, read, export, the keyframe build, the loop
+ * update) may overlap as long as no push has to grow the arena; a push that grows must be excluded from every reader by the
+ * caller, because the arrays move.  A reader on another stream of the device is ordered behind the captures by an event, nothing
+ * waits on the host.  The one reader that returns with its device work still queued is the export into device memory: it leaves
+ * an event in the log, and the next push waits for that event on its own stream before it may write over released rows.
+ * Destroy the log before its context. */
+typedef struct vba_scanlog vba_scanlog;
+int vba_scanlog_create(vba_ctx *ctx, vba_scanlog **out);
+void vba_scanlog_destroy(vba_scanlog *l);
+int vba_scanlog_reserve(vba_scanlog *l, int64_t points, int scans);   /* points <= 2^30; also the float staging of vba_scanlog_read */
+int vba_scanlog_allocations(vba_scanlog *l, int *count, int64_t *bytes);
+/* Captures frame `frame` (0 .. win_size-1, slot mp[frame]) of the window of the log's context: the slot's body points and covariance
+ * rows exactly as they were inserted (zeros when the map holds no covariances), by one kernel on the context's stream.  No host
+ * synchronise: the count is the host's.  CALL IT WHERE THE REFERENCE CREATES THE ScanPose (VS:1974-1980): after the BA and BEFORE
+ * vba_map_margi, which clears the outgoing slot's count; after it the pushed scan is empty.  An empty frame is pushed as an empty
+ * scan and still gets a number.  *seq = the scan's number.  VBA_ERR_UNSUPPORTED: the context is sharded (its ring holds only the
+ * rank's share of a scan).  VBA_ERR_BAD_ARG: a frame outside the window. */
+int vba_scanlog_push_window(vba_scanlog *l, int frame, int64_t *seq);
+/* Pushes a scan the caller holds: pnt [n][3], var [n][9] (NULL: zeros), HOST or DEVICE memory as for vba_map_cut_voxel (host arrays
+ * are the caller's again on return).  For offline sessions and tests. */
+int vba_scanlog_push_points(vba_scanlog *l, int n, const double *pnt, const double *var, int64_t *seq);
+/* the live numbers [*first, *end) and the sizes of up to cap scans from *first */
+int vba_scanlog_range(vba_scanlog *l, int64_t *first, int64_t *end, int cap, int *sizes);
+/* drops every scan with seq < upto (pvec = nullptr, VS:2342 / VS:2375 / VS:2227-2228); their rows may be written by later pushes */
+int vba_scanlog_release(vba_scanlog *l, int64_t upto);
+/* Scan seq to the host (tests, save_pcd): pnt [cap][3], var [cap][9], xyz [cap][3] = the body point narrowed once to float ON THE
+ * DEVICE (pl_save, VS:172-174: 12 bytes per point cross); any output may be NULL.  *n = the scan's size, at most cap points are
+ * written.  Synchronises once.  VBA_ERR_BAD_ARG: seq is not live. */
+int vba_scanlog_read(vba_scanlog *l, int64_t seq, int cap, double *pnt, double *var, float *xyz, int *n);
+/* pub_localmap's point loop (VS:63-76) from the log: for scans first .. first+k-1 at poses [k][12] the points j = 0, stride,
+ * 2 stride, ... < size (the stride restarts at every scan: ceil(size / stride) points each) as records x y z intensity of four
+ * floats.  world = R p + t in the order stated for vba_kf_export_world, every product and sum rounded on its own, each coordinate
+ * narrowed to float once.  xyzi [cap][4] is HOST or DEVICE memory with that call's rules: host output passes through ctx's
+ * staging and the call synchronises once; device output (16-byte aligned) is stream-ordered on ctx's stream and the call returns
+ * with the gather queued (see "Ordering and threads").  ctx may be another context of the log's device.  *n_out = the record count,
+ * always; VBA_ERR_BAD_ARG with nothing queued and xyzi untouched when cap is smaller than it, when the range is not wholly live,
+ * for stride < 1, a non-finite pose or another device. */
+int vba_scanlog_export_world(vba_ctx *ctx, vba_scanlog *l, int64_t first, int k, const double *poses, int stride, float intensity,
+                             int64_t cap, float *xyzi, int64_t *n_out);
+/* vba_kf_build with var != NULL on scans first .. first+k-1 of the log: the merge reads scan j at its own arena start; everything
+ * after it (the transforms and their order of operations, the covariance diagonal taken unrotated, down_sampling_pvec, the
+ * descriptors, the commit rule, the errors) is vba_kf_build's own code.  The store may hang off another context of the log's
+ * device (another device: VBA_ERR_BAD_ARG): its stream waits for the captures through an event.  VBA_ERR_BAD_ARG, store and db
+ * untouched: a range that is not wholly live, or more than 2^28 points. */
+int vba_kf_build_from_log(vba_kf_store *s, vba_scanlog *l, int64_t first, int k, const double *poses, double voxel_size, int id,
+                          double jour, vba_btc_db *db, int cap, double *rows, uint64_t *bits, int *n_stds, int *n_points);
+/* vba_loop_update with steps 3 and 4 fed from the device: the buf_lba2loop scans are scans first .. first+k-1 of the log with their
+ * full covariance rows (each read at its own arena start), the window is the outgoing map's scan ring (the win_pnt == NULL form).
+ * Checks, the trade of the maps, the failure path and the synchronisation are that call's: one body serves both.  Additionally
+ * VBA_ERR_BAD_ARG for a range that is not wholly live or a log on another device. */
+int vba_scanlog_loop_update(vba_ctx *ctx, vba_loop_map *lm, const double *dx12, vba_scanlog *l, int64_t first, int k,
+                            const double *poses_bl, int win_count, const double *poses_win, int *n_factors);
+
+/* ------------------------------------------------------------------------------------------------
  * Scan front end: the node's per-scan path from the raw sensor message to the points and covariances that the
  * odometry and the map read, resident in HBM.  A frame owns the device buffers of one scan.
  *   decode:  Features::process + pcl_handler (FP:103-366, VH:77-103): raw message bytes -> decoded, filtered, time-sorted, cut cloud.

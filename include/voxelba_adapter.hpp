@@ -217,6 +217,7 @@ class ScanFrame {
 };
 
 class LoopMap;
+class ScanLog;
 struct ScanPose;
 class VoxelMap {
  public:
@@ -262,6 +263,11 @@ class VoxelMap {
   // loop_update() VS:1255-1373 (defined below, after LoopMap): returns the factor count of the closing recut
   inline int loop_update(LoopMap &map_loop, const IMUST &dx, std::vector<ScanPose *> &buf_lba2loop, std::vector<IMUST> &x_buf, int win_count,
                          IMUST &x_curr, int &g_update, const std::vector<const PVec *> *pvec_buf = nullptr);
+  // the same with the buf_lba2loop scans in a ScanLog (scans first .. first + bl_states.size() - 1; bl_states are their ScanPose::x,
+  // moved by dx here) and the window from the outgoing map's scan ring: no point crosses the host boundary
+  inline int loop_update(LoopMap &map_loop, const IMUST &dx, ScanLog &log, int64_t first, std::vector<IMUST> &bl_states, std::vector<IMUST> &x_buf,
+                         int win_count, IMUST &x_curr, int &g_update);
+  vba_ctx *get() const { return c_; }
   size_t size() const { return (size_t)vba_map_num_roots(c_); }
   size_t slide_size() const { return (size_t)vba_map_num_slide_roots(c_); }
  private:
@@ -772,6 +778,10 @@ class KeyframeStore {
     if (db && stds_vec) unpack_stds(rows, bits, n, *stds_vec);
     return kept;
   }
+  // the same from a ScanLog (defined below, after ScanLog): scans first .. first + bl_poses.size() - 1 at bl_poses (their bl.x),
+  // merged from the log's arena in place
+  inline int build(ScanLog &log, int64_t first, const std::vector<IMUST> &bl_poses, double voxel_size_10, int id, double jour,
+                   BtcDatabase *db = nullptr, std::vector<STD> *stds_vec = nullptr);
   // VS:384-409: descriptors of keyframes [first, first + count) merged into the last one's frame, from the store
   void GenerateSTDescs(int first, int count, BtcDatabase &db, std::vector<STD> &stds_vec) {
     const int cap = db.gen_cap();
@@ -964,6 +974,121 @@ inline int VoxelMap::loop_update(LoopMap &map_loop, const IMUST &dx, std::vector
                             pvec_buf ? wp.data() : nullptr, pvec_buf ? wv.data() : nullptr, pvec_buf ? woff.data() : nullptr, poses_win.data(), &nf));
   loop_update_finish(g_update);
   return nf;
+}
+
+// ---- the marginalised scans of a session, resident in HBM (voxelba.h "Scan log"): the counterpart of the live
+// ScanPose::pvec pointers.  push(map, frame) stands where the reference creates the ScanPose (VS:1974-1980), after the BA and BEFORE
+// multi_margi; the number it returns is win_base + frame for a session that pushes every marginalised scan.  The producer thread
+// (push) and one consumer thread (everything else) may overlap while no push has to grow the arena: reserve() first.  Destroy it
+// before its Context.
+class ScanLog {
+ public:
+  explicit ScanLog(Context &ctx) : ctx_(ctx.get()) { check(ctx_, vba_scanlog_create(ctx_, &l_)); }
+  ~ScanLog() { vba_scanlog_destroy(l_); }
+  ScanLog(const ScanLog &) = delete;
+  ScanLog &operator=(const ScanLog &) = delete;
+  vba_scanlog *get() const { return l_; }
+  void reserve(int64_t points, int scans) { check(ctx_, vba_scanlog_reserve(l_, points, scans)); }
+  // frame `frame` of the window, from the map's scan ring, device to device (the map must be the one of the log's Context)
+  int64_t push(VoxelMap &map, int frame) {
+    if (map.get() != ctx_) throw std::invalid_argument("ScanLog::push: the map belongs to another Context");
+    int64_t seq = -1;
+    check(ctx_, vba_scanlog_push_window(l_, frame, &seq));
+    return seq;
+  }
+  // a scan the caller holds (offline sessions)
+  int64_t push(const PVec &pvec) {
+    const size_t n = pvec.size();
+    std::vector<double> p(n * 3 + 1), v(n * 9 + 1);
+    for (size_t i = 0; i < n; i++) { std::memcpy(&p[i * 3], pvec[i].pnt, 24); std::memcpy(&v[i * 9], pvec[i].var, 72); }
+    int64_t seq = -1;
+    check(ctx_, vba_scanlog_push_points(l_, (int)n, p.data(), v.data(), &seq));
+    return seq;
+  }
+  void release(int64_t upto) { check(ctx_, vba_scanlog_release(l_, upto)); }     // pvec = nullptr for every scan below upto
+  int64_t first() const { int64_t a = 0, b = 0; check(ctx_, vba_scanlog_range(l_, &a, &b, 0, nullptr)); return a; }
+  int64_t end() const { int64_t a = 0, b = 0; check(ctx_, vba_scanlog_range(l_, &a, &b, 0, nullptr)); return b; }
+  int size(int64_t seq) const {
+    int n = 0;
+    check(ctx_, vba_scanlog_read(l_, seq, 0, nullptr, nullptr, nullptr, &n));
+    return n;
+  }
+  // scan seq on the host: the PVec as it was inserted, and / or its points narrowed to float on the device (pl_save, VS:172-174)
+  void read(int64_t seq, PVec *pvec, std::vector<XYZ> *xyz = nullptr) const {
+    const int n = size(seq);
+    std::vector<double> p(pvec ? (size_t)n * 3 + 1 : 0), v(pvec ? (size_t)n * 9 + 1 : 0);
+    std::vector<float> f(xyz ? (size_t)n * 3 + 1 : 0);
+    int m = 0;
+    check(ctx_, vba_scanlog_read(l_, seq, n, pvec ? p.data() : nullptr, pvec ? v.data() : nullptr, xyz ? f.data() : nullptr, &m));
+    if (m < n) throw std::runtime_error("ScanLog::read: the scan changed under the reader");
+    if (pvec) {
+      pvec->resize((size_t)n);
+      for (int i = 0; i < n; i++) { std::memcpy((*pvec)[i].pnt, &p[3 * (size_t)i], 24); std::memcpy((*pvec)[i].var, &v[9 * (size_t)i], 72); }
+    }
+    if (xyz) {
+      xyz->resize((size_t)n);
+      for (int i = 0; i < n; i++) (*xyz)[i] = XYZ{f[3 * (size_t)i], f[3 * (size_t)i + 1], f[3 * (size_t)i + 2]};
+    }
+  }
+ private:
+  vba_ctx *ctx_ = nullptr;
+  vba_scanlog *l_ = nullptr;
+};
+
+inline int KeyframeStore::build(ScanLog &log, int64_t first, const std::vector<IMUST> &bl_poses, double voxel_size_10, int id, double jour,
+                                BtcDatabase *db, std::vector<STD> *stds_vec) {
+  const std::vector<double> poses = LidarFactor::poses_of(bl_poses);
+  const int cap = db ? db->gen_cap() : 0;
+  std::vector<double> rows((size_t)(cap > 0 ? cap : 1) * VBA_BTC_ROW_LEN);
+  std::vector<uint64_t> bits((size_t)(cap > 0 ? cap : 1) * 3);
+  int n = 0, kept = 0;
+  check(ctx_, vba_kf_build_from_log(s_, log.get(), first, (int)bl_poses.size(), poses.data(), voxel_size_10, id, jour, db ? db->get() : nullptr, cap,
+                                    rows.data(), bits.data(), &n, &kept));
+  if (db && stds_vec) unpack_stds(rows, bits, n, *stds_vec);
+  return kept;
+}
+
+inline int VoxelMap::loop_update(LoopMap &map_loop, const IMUST &dx, ScanLog &log, int64_t first, std::vector<IMUST> &bl_states, std::vector<IMUST> &x_buf,
+                                 int win_count, IMUST &x_curr, int &g_update) {
+  std::vector<ScanPose *> none;
+  loop_update_states(dx, none, x_buf, win_count, x_curr, g_update);
+  for (IMUST &x : bl_states) apply_dx(x, dx);                                   // ScanPose::update, VS:1286-1294
+  const std::vector<double> poses_bl = LidarFactor::poses_of(bl_states);
+  std::vector<IMUST> xw(x_buf.begin(), x_buf.begin() + win_count);
+  const std::vector<double> poses_win = LidarFactor::poses_of(xw);
+  double dx12[12];
+  std::memcpy(dx12, dx.R, 72); std::memcpy(dx12 + 9, dx.p, 24);
+  int nf = 0;
+  check(c_, vba_scanlog_loop_update(c_, map_loop.get(), dx12, log.get(), first, (int)bl_states.size(), poses_bl.data(), win_count, poses_win.data(), &nf));
+  loop_update_finish(g_update);
+  return nf;
+}
+
+// ResultOutput::pub_localmap's point loop (VS:63-76) from the log: the mgsize scans first .. first + mgsize - 1 (the outgoing frames,
+// pushed before multi_margi) at x_buf[0 .. mgsize), every third point, intensity = cur_session; publish(const float *xyzi, int64_t n)
+// receives the records x y z intensity.  The path update VS:78-84 reads x_buf alone and stays with the caller.
+template <class Publish>
+inline int64_t pub_localmap(Context &ctx, ScanLog &log, int64_t first, int mgsize, const std::vector<IMUST> &x_buf, int cur_session, Publish &&publish,
+                            int stride = 3) {
+  if (mgsize < 0 || (size_t)mgsize > x_buf.size()) throw std::invalid_argument("pub_localmap: mgsize");
+  std::vector<IMUST> xs(x_buf.begin(), x_buf.begin() + mgsize);
+  const std::vector<double> poses = LidarFactor::poses_of(xs);
+  int64_t cap = 0, n = 0;
+  for (int i = 0; i < mgsize; i++) cap += (log.size(first + i) + stride - 1) / stride;
+  std::vector<float> pl((size_t)cap * 4 + 4);
+  check(ctx.get(), vba_scanlog_export_world(ctx.get(), log.get(), first, mgsize, poses.data(), stride, (float)cur_session, cap, pl.data(), &n));
+  publish((const float *)pl.data(), n);
+  return n;
+}
+
+// FileReaderWriter::save_pcd (VS:166-179) of scan seq: savename/seq.pcd from the float form read off the device
+inline void save_pcd(ScanLog &log, int64_t seq, const std::string &savename) {
+  std::vector<XYZ> xyz;
+  log.read(seq, nullptr, &xyz);
+  std::vector<double> p(xyz.size() * 3 + 1);
+  for (size_t i = 0; i < xyz.size(); i++) { p[3 * i] = xyz[i].x; p[3 * i + 1] = xyz[i].y; p[3 * i + 2] = xyz[i].z; }
+  const std::string path = savename + "/" + std::to_string(seq) + ".pcd";
+  if (vba_io_save_pcd(path.c_str(), (int)xyz.size(), p.data())) throw std::runtime_error("save_pcd: " + path);
 }
 
 #ifdef VBA_ADAPTER_HAVE_EIGEN

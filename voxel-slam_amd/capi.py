@@ -45,6 +45,9 @@ EXPORTS = [
     "vba_kf_load_nearby", "vba_kf_read", "vba_kf_clouds", "vba_kf_export_plan", "vba_kf_export_world",
     "vba_loop_map_create", "vba_loop_map_destroy", "vba_loop_map_reserve", "vba_loop_map_allocations", "vba_loop_map_build",
     "vba_loop_map_num_roots", "vba_loop_map_dump_leaves", "vba_loop_map_dump_plane_var", "vba_loop_update",
+    "vba_scanlog_create", "vba_scanlog_destroy", "vba_scanlog_reserve", "vba_scanlog_allocations", "vba_scanlog_push_window",
+    "vba_scanlog_push_points", "vba_scanlog_range", "vba_scanlog_release", "vba_scanlog_read", "vba_scanlog_export_world",
+    "vba_kf_build_from_log", "vba_scanlog_loop_update",
     "vba_scan_layout_livox", "vba_scan_layout_check", "vba_scan_frame_create", "vba_scan_frame_destroy", "vba_scan_frame_reserve",
     "vba_scan_frame_allocations", "vba_scan_decode", "vba_scan_prepare", "vba_scan_frame_read",
     "vba_init_window_create", "vba_init_window_destroy", "vba_init_window_reserve", "vba_init_window_allocations", "vba_init_window_clear",
@@ -298,6 +301,22 @@ class KeyframeStore:
             return npt.value, None, None
         return npt.value, rows[:ns.value].copy(), bits[:ns.value].copy()
 
+    def build_from_log(self, log, first, poses, voxel_size, id, jour=0.0, db=None, cap=None):
+        """``build`` with covariances from scans first .. first + len(poses) - 1 of the ScanLog ``log``, read in place."""
+        poses = _c(poses).reshape(-1, 12)
+        rows = bits = None; ns = C.c_int(); npt = C.c_int()
+        if db is not None:
+            if cap is None:
+                cap = btc_max_stds(getattr(db, "gcfg", None) or btc_default_gen_config(0))
+            rows = np.zeros((max(cap, 1), BTC_ROW_LEN)); bits = np.zeros((max(cap, 1), 3), dtype=np.uint64)
+        self.ctx._chk(self.lib.vba_kf_build_from_log(self.h, log.h, C.c_int64(first), C.c_int(len(poses)), _p(poses), C.c_double(voxel_size),
+                                                     C.c_int(int(id)), C.c_double(jour), db.h if db is not None else None,
+                                                     C.c_int(cap if db is not None else 0), _p(rows),
+                                                     bits.ctypes.data_as(C.POINTER(C.c_uint64)) if bits is not None else None, C.byref(ns), C.byref(npt)))
+        if db is None:
+            return npt.value, None, None
+        return npt.value, rows[:ns.value].copy(), bits[:ns.value].copy()
+
     def last_counts(self):
         n = C.c_int()
         self.ctx._chk(self.lib.vba_kf_last_counts(self.h, C.c_int(0), None, C.byref(n)))
@@ -426,6 +445,91 @@ class LoopMap:
         if n > 0:
             self.lib.vba_loop_map_dump_plane_var(self.h, _p(out), C.c_int(n))
         return out
+
+
+class ScanLog:
+    """One vba_scanlog: the marginalised scans of a session (the live ``ScanPose::pvec``) resident in HBM, between the map's scan
+    ring and the keyframes.  Scans are numbered 0, 1, 2, ... in push order and released first in, first out."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx._chk(self.lib.vba_scanlog_create(ctx.h, C.byref(h)))
+        self.h = h
+        ctx._kf.append(self)         # destroyed with its context, as the stores are
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.vba_scanlog_destroy(self.h)
+            self.h = None
+        kf = getattr(self.ctx, "_kf", None)
+        if kf is not None and self in kf:
+            kf.remove(self)
+
+    def reserve(self, points=0, scans=0):
+        self.ctx._chk(self.lib.vba_scanlog_reserve(self.h, C.c_int64(points), C.c_int(scans)))
+
+    def allocations(self):
+        n = C.c_int(); b = C.c_int64()
+        self.ctx._chk(self.lib.vba_scanlog_allocations(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def push_window(self, frame):
+        """capture frame ``frame`` of the context's window from the map's scan ring (before margi) -> the scan's number"""
+        seq = C.c_int64(-1)
+        self.ctx._chk(self.lib.vba_scanlog_push_window(self.h, C.c_int(frame), C.byref(seq)))
+        return seq.value
+
+    def push_points(self, pnt, var=None):
+        """push a host scan pnt [n][3] with var [n][9] (None: zeros) -> the scan's number"""
+        pnt = _c(pnt).reshape(-1, 3)
+        v = _c(var).reshape(-1, 9) if var is not None else None
+        seq = C.c_int64(-1)
+        self.ctx._chk(self.lib.vba_scanlog_push_points(self.h, C.c_int(len(pnt)), _p(pnt), _p(v), C.byref(seq)))
+        return seq.value
+
+    def range(self):
+        """(first, end, sizes int32 [end - first]) of the live scans"""
+        a = C.c_int64(); b = C.c_int64()
+        self.ctx._chk(self.lib.vba_scanlog_range(self.h, C.byref(a), C.byref(b), C.c_int(0), None))
+        sizes = np.zeros(max(b.value - a.value, 1), dtype=np.int32)
+        self.ctx._chk(self.lib.vba_scanlog_range(self.h, C.byref(a), C.byref(b), C.c_int(len(sizes)), sizes.ctypes.data_as(C.POINTER(C.c_int))))
+        return a.value, b.value, sizes[:max(b.value - a.value, 0)].copy()
+
+    def release(self, upto):
+        self.ctx._chk(self.lib.vba_scanlog_release(self.h, C.c_int64(upto)))
+
+    def read(self, seq, xyz=False):
+        """scan ``seq`` -> (pnt [n][3], var [n][9]); with xyz=True also the float32 [n][3] form narrowed on the device"""
+        n = C.c_int()
+        self.ctx._chk(self.lib.vba_scanlog_read(self.h, C.c_int64(seq), C.c_int(0), None, None, None, C.byref(n)))
+        m = max(n.value, 1)
+        pnt = np.zeros((m, 3)); var = np.zeros((m, 9)); f = np.zeros((m, 3), dtype=np.float32) if xyz else None
+        self.ctx._chk(self.lib.vba_scanlog_read(self.h, C.c_int64(seq), C.c_int(n.value), _p(pnt), _p(var),
+                                                f.ctypes.data_as(C.POINTER(C.c_float)) if xyz else None, C.byref(n)))
+        out = (pnt[:n.value].copy(), var[:n.value].copy())
+        return out + (f[:n.value].copy(),) if xyz else out
+
+    def export_world(self, first, poses, stride=1, intensity=0.0, ctx=None, out=None, cap=None):
+        """pub_localmap's point loop over scans first .. first + k - 1 at ``poses`` [k][12] on ``ctx``'s stream (default: the log's
+        context).  Returns float32 [n][4] records x y z intensity; with ``out`` (the address of a 16-byte aligned DEVICE buffer of
+        ``cap`` records) the call is stream-ordered, does not synchronise and returns the record count."""
+        ctx = ctx or self.ctx
+        poses = _c(poses).reshape(-1, 12)
+        k = len(poses)
+        n = C.c_int64()
+        head = (ctx.h, self.h, C.c_int64(first), C.c_int(k), _p(poses), C.c_int(int(stride)), C.c_float(intensity))
+        if out is not None:
+            ctx._chk(self.lib.vba_scanlog_export_world(*head, C.c_int64(int(cap)), out if isinstance(out, C.c_void_p) else C.c_void_p(int(out)), C.byref(n)))
+            return n.value
+        if cap is None:
+            a, b, sizes = self.range()
+            s = sizes[first - a:first - a + k].astype(np.int64)
+            cap = int(((s + stride - 1) // max(int(stride), 1)).sum())
+        res = np.zeros((max(int(cap), 1), 4), dtype=np.float32)
+        ctx._chk(self.lib.vba_scanlog_export_world(*head, C.c_int64(int(cap)), res.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return res[:n.value].copy()
 
 
 SCAN_TIME_NONE, SCAN_TIME_F32, SCAN_TIME_U32_DIV1E9, SCAN_TIME_F64_REL_FIRST = range(4)
@@ -1051,6 +1155,20 @@ class Context:
                                            off.ctypes.data_as(ip) if off is not None else None, _p(pnt), _p(var), _p(bp),
                                            C.c_int(len(poses_win)), _p(wp), _p(wv), woff.ctypes.data_as(ip) if woff is not None else None,
                                            _p(poses_win), C.byref(nf)))
+        return nf.value
+
+    def scan_log(self) -> "ScanLog":
+        return ScanLog(self)
+
+    def scanlog_loop_update(self, lm, poses_win, log, first, bl_poses, dx12=None):
+        """``loop_update`` with the buf_lba2loop scans taken from the ScanLog ``log`` (scans first .. first + len(bl_poses) - 1, with
+        their covariance rows) and the window from the outgoing map's scan ring.  Returns the factor count."""
+        poses_win = _c(poses_win).reshape(-1, 12)
+        bp = _c(bl_poses).reshape(-1, 12) if bl_poses is not None and len(bl_poses) else None
+        k = len(bp) if bp is not None else 0
+        nf = C.c_int()
+        self._chk(self.lib.vba_scanlog_loop_update(self.h, lm.h, _p(_c(dx12)) if dx12 is not None else None, log.h, C.c_int64(first), C.c_int(k),
+                                                   _p(bp), C.c_int(len(poses_win)), _p(poses_win), C.byref(nf)))
         return nf.value
 
     def btc_search_loop_sessions(self, dbs, rows, bits, cur_db, cur_frame=-1):

@@ -14,26 +14,45 @@ namespace vba {
 //   out   double [n][3]  the merged cloud (down-sampler input), may be nullptr
 //   outf  float  [n][3]  the same narrowed to float (the descriptor generator's point buffer), may be nullptr
 //   var / vout           covariance rows (vrow doubles apart, diagonal entries vstep apart) -> double [n][3] diagonals, unrotated
+// the scan of merged point i: the last j with off[j] <= i (empty scans are skipped by the <=)
+__device__ __forceinline__ int kf_merge_scan(int i, int k, const int *__restrict__ off) {
+  int lo = 0, hi = k - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+// merged point i from source row `row`, moved by T
+__device__ __forceinline__ void kf_merge_point(int i, size_t row, const double *__restrict__ T, const double *__restrict__ pnt, const double *__restrict__ var,
+                                               int vrow, int vstep, double *__restrict__ out, float *__restrict__ outf, double *__restrict__ vout) {
+  const size_t b = 3 * (size_t)i, sb = 3 * row;
+  double qx, qy, qz;
+  kf_apply(T, pnt[sb], pnt[sb + 1], pnt[sb + 2], qx, qy, qz);
+  if (out) { out[b] = qx; out[b + 1] = qy; out[b + 2] = qz; }
+  if (outf) { outf[b] = (float)qx; outf[b + 1] = (float)qy; outf[b + 2] = (float)qz; }
+  if (vout) {
+    const double *v = var + (size_t)vrow * row;
+    vout[b] = v[0]; vout[b + 1] = v[vstep]; vout[b + 2] = v[2 * vstep];
+  }
+}
 __global__ __launch_bounds__(256) void k_kf_merge(int n, int k, const int *__restrict__ off, const double *__restrict__ xf, const double *__restrict__ pnt,
                                                   const double *__restrict__ var, int vrow, int vstep, double *__restrict__ out, float *__restrict__ outf,
                                                   double *__restrict__ vout) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  int lo = 0, hi = k - 1;                                   // last j with off[j] <= i (empty scans are skipped by the <=)
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  const double *T = xf + 12 * lo;
-  const size_t b = 3 * (size_t)i;
-  double qx, qy, qz;
-  kf_apply(T, pnt[b], pnt[b + 1], pnt[b + 2], qx, qy, qz);
-  if (out) { out[b] = qx; out[b + 1] = qy; out[b + 2] = qz; }
-  if (outf) { outf[b] = (float)qx; outf[b + 1] = (float)qy; outf[b + 2] = (float)qz; }
-  if (vout) {
-    const double *v = var + (size_t)vrow * (size_t)i;
-    vout[b] = v[0]; vout[b + 1] = v[vstep]; vout[b + 2] = v[2 * vstep];
-  }
+  const int lo = kf_merge_scan(i, k, off);
+  kf_merge_point(i, (size_t)i, xf + 12 * lo, pnt, var, vrow, vstep, out, outf, vout);
+}
+// The merge from a scan log (vba_kf_build_from_log): the scans are whole but not contiguous, scan j starts at arena row start[j],
+// so merged point i is row start[j] + (i - off[j]) of pnt and of var.
+__global__ __launch_bounds__(256) void k_kf_merge_rows(int n, int k, const int *__restrict__ off, const int *__restrict__ start, const double *__restrict__ xf,
+                                                       const double *__restrict__ pnt, const double *__restrict__ var, int vrow, int vstep,
+                                                       double *__restrict__ out, float *__restrict__ outf, double *__restrict__ vout) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int lo = kf_merge_scan(i, k, off);
+  kf_merge_point(i, (size_t)start[lo] + (size_t)(i - off[lo]), xf + 12 * lo, pnt, var, vrow, vstep, out, outf, vout);
 }
 
 // keyframe_loading: world = x0.R p + x0.p in the same operation order, T = the keyframe's x0 ([12])

@@ -175,7 +175,9 @@ int vba_scan_undistort(vba_ctx *c, int n, double *pnt, const double *curv, int m
 
 namespace {
 
-size_t kf_tab_bytes(int t) { return (size_t)t * 12 * sizeof(double) + (((size_t)t + 1) * sizeof(int) + 15 & ~(size_t)15); }
+size_t kf_tab_off_bytes(int t) { return ((size_t)t + 1) * sizeof(int) + 15 & ~(size_t)15; }
+// transforms [t][12] | offsets [t + 1] | source starts [t] (a build from a scan log)
+size_t kf_tab_bytes(int t) { return (size_t)t * 12 * sizeof(double) + 2 * kf_tab_off_bytes(t); }
 
 // a fresh device block of n elements, counted (vba_kf_allocations)
 template <class T>
@@ -276,18 +278,22 @@ void kf_delta(const double *xc, const double *x, double *T) {
   }
 }
 
-// the transform table of k clouds with poses [k][12] (xc = the last) and row offsets rel [k + 1] -> pinned image -> device, on st
-int kf_upload_tab(vba_kf_store *s, int k, const double *const *poses, const int *rel, hipStream_t st) {
+// the transform table of k clouds with poses [k][12] (xc = the last), row offsets rel [k + 1] and, for clouds that lie apart in their
+// source array, the source row of each cloud's first point (starts [k], else nullptr) -> pinned image -> device, on st
+int kf_upload_tab(vba_kf_store *s, int k, const double *const *poses, const int *rel, hipStream_t st, const int *starts = nullptr) {
   vba_ctx *c = s->ctx;
   double *T = (double *)s->h_tab.p;
   int *o = (int *)(s->h_tab + (size_t)s->tcap * 12 * sizeof(double));
+  int *b = (int *)((char *)o + kf_tab_off_bytes(s->tcap));
   for (int i = 0; i < k; i++) kf_delta(poses[k - 1], poses[i], T + 12 * i);
   for (int i = 0; i <= k; i++) o[i] = rel[i];
+  if (starts) for (int i = 0; i < k; i++) b[i] = starts[i];
   HIPCHK(c, hipMemcpyAsync(s->d_tab, s->h_tab, kf_tab_bytes(s->tcap), hipMemcpyHostToDevice, st));
   return VBA_OK;
 }
 const double *kf_dev_xf(const vba_kf_store *s) { return (const double *)s->d_tab.p; }
 const int *kf_dev_off(const vba_kf_store *s) { return (const int *)(s->d_tab + (size_t)s->tcap * 12 * sizeof(double)); }
+const int *kf_dev_start(const vba_kf_store *s) { return (const int *)((const char *)kf_dev_off(s) + kf_tab_off_bytes(s->tcap)); }
 
 bool kf_pose_ok(const double *p) { for (int i = 0; i < 12; i++) if (!std::isfinite(p[i])) return false; return true; }
 
@@ -340,13 +346,18 @@ int vba_kf_allocations(vba_kf_store *s, int *count, int64_t *bytes) {
 
 int vba_kf_size(vba_kf_store *s) { return s ? (int)s->kf.size() : 0; }
 
-int vba_kf_build(vba_kf_store *s, int k, const int *offsets, const double *pnt, const double *var, const double *poses, double voxel_size, int id,
-                 double jour, vba_btc_db *db, int cap, double *rows, uint64_t *bits, int *n_stds, int *n_points) {
-  if (!s || k < 1 || !offsets || !poses || !n_points || !(voxel_size > 0) || (!var && voxel_size < 0.001)) return VBA_ERR_BAD_ARG;
-  for (int i = 0; i < k; i++) if (offsets[i] < 0 || offsets[i + 1] < offsets[i]) return VBA_ERR_BAD_ARG;
-  const int off0 = offsets[0], n = offsets[k] - off0;
-  if (n > (1 << 28) || (n > 0 && !pnt)) return VBA_ERR_BAD_ARG;
-  for (int i = 0; i < k; i++) if (!kf_pose_ok(poses + 12 * i)) return VBA_ERR_BAD_ARG;
+}  // extern "C"
+namespace {
+
+// The k scans of a build: rel [k + 1] = the points before each scan among the k.  Without starts they are rows rel[i] .. rel[i + 1]
+// of pnt / var (HOST or DEVICE); with starts [k] scan i begins at row starts[i] of the DEVICE arrays pnt / var (a scan log's arena).
+struct KfScans { const int *rel; const double *pnt, *var; const int *starts; };
+
+// vba_kf_build behind its argument checks: merge, down-sampling, descriptors, commit
+int kf_build_scans(vba_kf_store *s, int k, const KfScans &in, const double *poses, double voxel_size, int id, double jour, vba_btc_db *db, int cap,
+                   double *rows, uint64_t *bits, int *n_stds, int *n_points) {
+  const int n = in.rel[k];
+  const double *pnt = in.pnt, *var = in.var;
   vba_ctx *c = s->ctx;
   const size_t N = (size_t)s->off.back();
   if (N + (size_t)n > (size_t)INT32_MAX) return VBA_ERR_CAPACITY;
@@ -361,26 +372,28 @@ int vba_kf_build(vba_kf_store *s, int k, const int *offsets, const double *pnt, 
   int m = 0;
   if (n > 0) {
     std::vector<const double *> pp(k);
-    std::vector<int> rel(k + 1);
     for (int i = 0; i < k; i++) pp[i] = poses + 12 * i;
-    for (int i = 0; i <= k; i++) rel[i] = offsets[i] - off0;
-    if ((st = kf_upload_tab(s, k, pp.data(), rel.data(), c->stream))) return st;
-    const double *src = pnt + 3 * (size_t)off0, *dvar = nullptr;
-    if (!is_device_ptr(pnt)) {
+    if ((st = kf_upload_tab(s, k, pp.data(), in.rel, c->stream, in.starts))) return st;
+    const double *src = pnt, *dvar = nullptr;
+    if (!in.starts && !is_device_ptr(pnt)) {
       HIPCHK(c, hipMemcpyAsync(s->d_src, src, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
       src = s->d_src;
     }
     if (var) {
-      if (is_device_ptr(var)) dvar = var + 9 * (size_t)off0;      // gathered by the merge kernel, 72 bytes apart
+      if (in.starts || is_device_ptr(var)) dvar = var;            // gathered by the merge kernel, 72 bytes apart
       else {                                                       // host array: only the three diagonal doubles per point cross
-        const double *v = var + 9 * (size_t)off0;
+        const double *v = var;
         for (size_t i = 0; i < (size_t)n; i++) { s->h_diag[3 * i] = v[9 * i]; s->h_diag[3 * i + 1] = v[9 * i + 4]; s->h_diag[3 * i + 2] = v[9 * i + 8]; }
         HIPCHK(c, hipMemcpyAsync(s->d_mdiag, s->h_diag, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
       }
     }
     const int nb = (n + 255) / 256;
-    hipLaunchKernelGGL(k_kf_merge, dim3(nb), dim3(256), 0, c->stream, n, k, kf_dev_off(s), kf_dev_xf(s), src, dvar, 9, 4, s->d_merge,
-                       db ? db->gen->pts.xyz.p : (float *)nullptr, dvar ? s->d_mdiag : (double *)nullptr);
+    if (in.starts)
+      hipLaunchKernelGGL(k_kf_merge_rows, dim3(nb), dim3(256), 0, c->stream, n, k, kf_dev_off(s), kf_dev_start(s), kf_dev_xf(s), src, dvar, 9, 4,
+                         s->d_merge, db ? db->gen->pts.xyz.p : (float *)nullptr, dvar ? s->d_mdiag : (double *)nullptr);
+    else
+      hipLaunchKernelGGL(k_kf_merge, dim3(nb), dim3(256), 0, c->stream, n, k, kf_dev_off(s), kf_dev_xf(s), src, dvar, 9, 4, s->d_merge,
+                         db ? db->gen->pts.xyz.p : (float *)nullptr, dvar ? s->d_mdiag : (double *)nullptr);
     if (db && db->ctx->stream != c->stream) {                      // the generator runs on its database's stream, behind the merge
       HIPCHK(c, hipEventRecord(s->ev, c->stream));
       HIPCHK(c, hipStreamWaitEvent(db->ctx->stream, s->ev, 0));
@@ -414,6 +427,37 @@ int vba_kf_build(vba_kf_store *s, int k, const int *offsets, const double *pnt, 
   s->last_m = m;
   *n_points = m;
   return VBA_OK;
+}
+
+}  // namespace
+extern "C" {
+
+int vba_kf_build(vba_kf_store *s, int k, const int *offsets, const double *pnt, const double *var, const double *poses, double voxel_size, int id,
+                 double jour, vba_btc_db *db, int cap, double *rows, uint64_t *bits, int *n_stds, int *n_points) {
+  if (!s || k < 1 || !offsets || !poses || !n_points || !(voxel_size > 0) || (!var && voxel_size < 0.001)) return VBA_ERR_BAD_ARG;
+  for (int i = 0; i < k; i++) if (offsets[i] < 0 || offsets[i + 1] < offsets[i]) return VBA_ERR_BAD_ARG;
+  const int off0 = offsets[0], n = offsets[k] - off0;
+  if (n > (1 << 28) || (n > 0 && !pnt)) return VBA_ERR_BAD_ARG;
+  for (int i = 0; i < k; i++) if (!kf_pose_ok(poses + 12 * i)) return VBA_ERR_BAD_ARG;
+  std::vector<int> rel(k + 1);
+  for (int i = 0; i <= k; i++) rel[i] = offsets[i] - off0;
+  const KfScans in{rel.data(), pnt ? pnt + 3 * (size_t)off0 : nullptr, var ? var + 9 * (size_t)off0 : nullptr, nullptr};
+  return kf_build_scans(s, k, in, poses, voxel_size, id, jour, db, cap, rows, bits, n_stds, n_points);
+}
+
+// vba_kf_build (var != NULL) on scans first .. first + k - 1 of a scan log, read at their own arena starts
+int vba_kf_build_from_log(vba_kf_store *s, vba_scanlog *l, int64_t first, int k, const double *poses, double voxel_size, int id, double jour,
+                          vba_btc_db *db, int cap, double *rows, uint64_t *bits, int *n_stds, int *n_points) {
+  if (!s || !l || k < 1 || !poses || !n_points || !(voxel_size > 0)) return VBA_ERR_BAD_ARG;
+  for (int i = 0; i < k; i++) if (!kf_pose_ok(poses + 12 * i)) return VBA_ERR_BAD_ARG;
+  vba_ctx *c = s->ctx;
+  if (l->ctx->device != c->device) return VBA_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  ScanLogView v;
+  int st = scanlog_view(l, first, k, 1ll << 28, c->stream, &v);     // the store's stream waits for the captures through an event
+  if (st) return st;
+  const KfScans in{v.rel.data(), v.d_pnt, v.d_var, v.starts.data()};
+  return kf_build_scans(s, k, in, poses, voxel_size, id, jour, db, cap, rows, bits, n_stds, n_points);   // synchronises: nothing stays queued on the arena
 }
 
 int vba_kf_last_counts(vba_kf_store *s, int cap, int *counts, int *n) {
@@ -687,6 +731,57 @@ int vba_kf_export_world(vba_ctx *c, int n_stores, vba_kf_store *const *stores, c
     if (!dev_out) HIPCHK(c, hipMemcpyAsync(xyzi + 4 * (size_t)(cb - begin), c->d_expout, (size_t)(ce - cb) * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
   }
   if (!dev_out) HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VBA_OK;
+}
+
+// pub_localmap's point loop (VS:63-76) over scans of a scan log: the same gather with one table row per scan, whose `row` is the
+// scan's own arena start and whose T is the pose given for it
+int vba_scanlog_export_world(vba_ctx *c, vba_scanlog *l, int64_t first_seq, int k, const double *poses, int stride, float intensity, int64_t cap,
+                             float *xyzi, int64_t *n_out) {
+  if (!c || !l || !n_out || k < 0 || stride < 1 || cap < 0 || (k > 0 && !poses)) return VBA_ERR_BAD_ARG;
+  *n_out = 0;
+  if (l->ctx->device != c->device) return VBA_ERR_BAD_ARG;
+  for (int i = 0; i < k; i++) if (!kf_pose_ok(poses + 12 * i)) return VBA_ERR_BAD_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  ScanLogView v;
+  int st = scanlog_view(l, first_seq, k, INT32_MAX, nullptr, &v);   // the sizes first: cap is checked before any device work
+  if (st) return st;
+  std::vector<long long> &first = c->exp_first;
+  first.clear();
+  long long total = 0;
+  for (int i = 0; i < k; i++) { first.push_back(total); total += exp_count((long long)v.rel[i + 1] - v.rel[i], stride); }
+  *n_out = total;
+  if (total > cap || (total > 0 && !xyzi)) return VBA_ERR_BAD_ARG;
+  if (total == 0) return VBA_OK;
+  const bool dev_out = is_device_ptr(xyzi);
+  if (dev_out && ((uintptr_t)xyzi & 15)) { c->set_error("vba_scanlog_export_world: a device xyzi must be 16-byte aligned"); return VBA_ERR_BAD_ARG; }
+  if ((st = exp_ensure_tab(c, (size_t)k))) return st;
+  if (!dev_out && (st = exp_ensure_out(c, (size_t)(total < kExpChunk ? total : kExpChunk)))) return st;
+  if ((st = scanlog_view(l, first_seq, k, INT32_MAX, c->stream, &v))) return st;   // again, now ordering ctx's stream behind the captures
+  const int slot = c->exp_next;
+  c->exp_next = (slot + 1) % vba_ctx::kExpRing;
+  HIPCHK(c, hipEventSynchronize(c->exp_ev[slot]));
+  ExpKf *h = (ExpKf *)c->h_exp[slot].p;
+  for (int i = 0; i < k; i++) {
+    h[i].first = first[i]; h[i].row = v.starts[i];
+    std::memcpy(h[i].T, poses + 12 * (size_t)i, 12 * sizeof(double));
+  }
+  HIPCHK(c, hipMemcpyAsync(c->d_exp, h, (size_t)k * sizeof(ExpKf), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->exp_ev[slot], c->stream));
+  const ExpKf *d_tab = (const ExpKf *)c->d_exp.p;
+  for (long long cb = 0; cb < total; cb += dev_out ? total : kExpChunk) {
+    const long long ce = dev_out ? total : std::min(total, cb + kExpChunk);
+    float4 *out = dev_out ? (float4 *)xyzi : c->d_expout.p;
+    // the rows of the table that records cb .. ce - 1 can touch: from the last scan with first <= cb
+    const int g0 = (int)(std::upper_bound(first.begin(), first.end(), cb) - first.begin()) - 1;
+    const long long nb = (ce - cb + 255) / 256;
+    hipLaunchKernelGGL(k_kf_export, dim3((unsigned)std::min<long long>(nb, kExpMaxBlocks)), dim3(256), 0, c->stream, cb, ce - cb, k - g0, d_tab + g0, v.d_pnt,
+                       stride, intensity, out);
+    HIPCHK(c, hipGetLastError());
+    if (!dev_out) HIPCHK(c, hipMemcpyAsync(xyzi + 4 * (size_t)cb, c->d_expout, (size_t)(ce - cb) * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (!dev_out) HIPCHK(c, hipStreamSynchronize(c->stream));
+  else if ((st = scanlog_reader_queued(l, c->stream))) return st;   // the gather is still queued: the next push waits for it
   return VBA_OK;
 }
 

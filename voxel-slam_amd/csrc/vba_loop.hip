@@ -195,8 +195,14 @@ int vba_loop_map_num_roots(vba_loop_map *lm) { return lm ? map_num_roots(lm->map
 int vba_loop_map_dump_leaves(vba_loop_map *lm, double *out, int max_leaves) { return lm ? map_dump_leaves(lm->map, lm->ctx->stream, out, max_leaves, lm->ctx->err) : -1; }
 int vba_loop_map_dump_plane_var(vba_loop_map *lm, double *out, int max_leaves) { return lm ? map_dump_plane_var(lm->map, lm->ctx->stream, out, max_leaves, lm->ctx->err) : -1; }
 
-int vba_loop_update(vba_ctx *c, vba_loop_map *lm, const double *dx12, int k, const int *offsets, const double *pnt, const double *var, const double *poses_bl,
-                    int win_count, const double *win_pnt, const double *win_var, const int *win_offsets, const double *poses_win, int *n_factors) {
+}  // extern "C"
+namespace {
+
+// vba_loop_update.  log == nullptr: the buf_lba2loop scans are rows offsets[i] .. offsets[i + 1] of pnt / var.  Otherwise they are
+// scans first .. first + k - 1 of the scan log, each read at its own arena start (vba_scanlog_loop_update).
+int loop_update_scans(vba_ctx *c, vba_loop_map *lm, const double *dx12, int k, const int *offsets, const double *pnt, const double *var,
+                      vba_scanlog *log, int64_t first, const double *poses_bl, int win_count, const double *win_pnt, const double *win_var,
+                      const int *win_offsets, const double *poses_win, int *n_factors) {
   // ---- 1. arguments, before any device work
   if (!c || !lm || !n_factors || !poses_win || k < 0) return VBA_ERR_BAD_ARG;
   *n_factors = 0;
@@ -207,6 +213,12 @@ int vba_loop_update(vba_ctx *c, vba_loop_map *lm, const double *dx12, int k, con
   if (c->n_ranks > 1 || c->map.n_ranks > 1 || lm->map.n_ranks > 1 || c->rank != 0) { c->set_error("vba_loop_update: sharded maps are not supported"); return VBA_ERR_UNSUPPORTED; }
   if (dx12 && !lm_finite(dx12, 12)) return VBA_ERR_BAD_ARG;
   if (!lm_finite(poses_win, 12 * (size_t)win_count)) return VBA_ERR_BAD_ARG;
+  ScanLogView lv;
+  if (log) {
+    if (log->ctx->device != c->device) { c->set_error("vba_scanlog_loop_update: the scan log is on another device"); return VBA_ERR_BAD_ARG; }
+    if (scanlog_view(log, first, k, 1ll << 27, nullptr, &lv)) { c->set_error("vba_scanlog_loop_update: the scans are not all live, or hold more than 2^27 points"); return VBA_ERR_BAD_ARG; }
+    offsets = lv.rel.data(); pnt = lv.d_pnt; var = lv.d_var;
+  }
   long long n_bl = 0;
   if (k > 0) {
     if (!offsets || !poses_bl || !lm_finite(poses_bl, 12 * (size_t)k)) return VBA_ERR_BAD_ARG;
@@ -223,7 +235,8 @@ int vba_loop_update(vba_ctx *c, vba_loop_map *lm, const double *dx12, int k, con
   hipStream_t st = c->stream;
   int r;
   if ((r = lm_ensure_tab(lm, k > 0 ? k : 1))) { c->set_error(lm->ctx->err); return r; }
-  const bool bl_host = n_bl > 0 && !is_device_ptr(pnt);
+  const bool bl_host = n_bl > 0 && !log && !is_device_ptr(pnt);
+  if (log && n_bl > 0 && (r = scanlog_view(log, first, k, 1ll << 27, st, &lv))) return r;     // this stream behind the captures
   if (bl_host && (r = lm_ensure_in(lm, (size_t)n_bl * (var ? 96 : 24)))) { c->set_error(lm->ctx->err); return r; }
   HIPCHK(c, hipStreamSynchronize(lm->ctx->stream));          // (the build ended with a synchronise; a dump on that stream may not have)
   LmAccount acc(lm, &lm->map, &c->map);
@@ -244,7 +257,7 @@ int vba_loop_update(vba_ctx *c, vba_loop_map *lm, const double *dx12, int k, con
   if (n_bl > 0) {
     const int off0 = offsets[0];
     int4 *seg = lm_h_seg(lm);
-    for (int i = 0; i < k; i++) seg[i] = make_int4(offsets[i] - off0, offsets[i] - off0, i, 0);
+    for (int i = 0; i < k; i++) seg[i] = make_int4(offsets[i] - off0, log ? lv.starts[i] : offsets[i] - off0, i, 0);
     std::memcpy(lm_h_pose(lm), poses_bl, 12 * sizeof(double) * (size_t)k);
     if (hipMemcpyAsync(lm->d_tab, lm->h_tab, lm_tab_bytes(lm->tcap), hipMemcpyHostToDevice, st) != hipSuccess) { c->set_error("vba_loop_update: table upload failed"); return fail(VBA_ERR_HIP); }
     const double *d_p = pnt + 3 * (size_t)off0, *d_v = var ? var + 9 * (size_t)off0 : nullptr;
@@ -290,6 +303,20 @@ int vba_loop_update(vba_ctx *c, vba_loop_map *lm, const double *dx12, int k, con
   }
   if (r) { c->set_error("vba_loop_update: the context holds the new map; resetting the outgoing map failed: " + e2); return r; }
   return VBA_OK;
+}
+
+}  // namespace
+extern "C" {
+
+int vba_loop_update(vba_ctx *c, vba_loop_map *lm, const double *dx12, int k, const int *offsets, const double *pnt, const double *var, const double *poses_bl,
+                    int win_count, const double *win_pnt, const double *win_var, const int *win_offsets, const double *poses_win, int *n_factors) {
+  return loop_update_scans(c, lm, dx12, k, offsets, pnt, var, nullptr, 0, poses_bl, win_count, win_pnt, win_var, win_offsets, poses_win, n_factors);
+}
+
+int vba_scanlog_loop_update(vba_ctx *c, vba_loop_map *lm, const double *dx12, vba_scanlog *l, int64_t first, int k, const double *poses_bl,
+                            int win_count, const double *poses_win, int *n_factors) {
+  if (!l) return VBA_ERR_BAD_ARG;
+  return loop_update_scans(c, lm, dx12, k, nullptr, nullptr, nullptr, l, first, poses_bl, win_count, nullptr, nullptr, nullptr, poses_win, n_factors);
 }
 
 }  // extern "C"

@@ -40,6 +40,11 @@
 //           input, which is what both sides of the test use for the marginalised scans.)  The record written at that point:
 //           [-3, points inserted by the build, factor count, n_kf, per keyframe {n, x0(12), xyz[n][3], diag[n][3]},
 //            k, per buf_lba2loop scan {scan index, state(25)}, win_count, per frame {state(25)}]
+//   mode 9 (mode 7 with the marginalised scans resident in HBM, DESIGN.md §20, through vba::ScanLog): input and output layouts are
+//           mode 7's.  A vba::ScanLog takes the place of the host ScanPose::pvec: the outgoing frame is pushed from the map's scan
+//           ring before multi_margi, keyframes are built from the log (KeyframeStore::build(ScanLog&, ...)) and released after each
+//           build, loop_update takes the buf_lba2loop scans from the log.  (The log holds the map's world covariances, mode 7's host
+//           route the covariances of the input: the keyframes' diag rows and what derives from them differ between the two modes.)
 //   mode 8 (the initialisation window resident in HBM, VS:1450-1534 through vba::ScanFrame::decode, vba::InitWindow::push and the
 //           InitWindow overload of motion_init): the header and the initialisation block of mode 3 with n_scans = win_size,
 //           then [down_size, min_points, point_filter_num, blind, layout (point_step, off_x, off_y, off_z, off_intensity, intensity_type,
@@ -236,10 +241,11 @@ int main(int argc, char **argv) {
   for (int i = 0; i < 4; i++) opt.min_point[i] = next();
   opt.imu_coef = next(); opt.thread_num = (int)next();
   opt.deterministic = det ? 1 : 0;
-  const bool lidar_only = mode == 0 || mode == 7;
+  const bool loop_mode = mode == 7 || mode == 9, use_log = mode == 9;
+  const bool lidar_only = mode == 0 || loop_mode;
   int n_loop = -1, kf_every = 1;
   IMUST dx;
-  if (mode == 7) {
+  if (loop_mode) {
     n_loop = (int)next(); kf_every = (int)next();
     for (int i = 0; i < 9; i++) dx.R[i] = next();
     for (int i = 0; i < 3; i++) dx.p[i] = next();
@@ -268,7 +274,12 @@ int main(int argc, char **argv) {
     std::vector<IMUST> kf_x0;
     std::vector<int> scan_of_frame;              // scan index of every frame of the window
     bool moved = false;
-    if (mode == 7) { keyframes.reset(new KeyframeStore(ctx)); map_loop.reset(new LoopMap(ctx)); }
+    if (loop_mode) { keyframes.reset(new KeyframeStore(ctx)); map_loop.reset(new LoopMap(ctx)); }
+    // mode 9: the same scans in a ScanLog; bl_states are their ScanPose::x, scan bl_first of the log is the first of them
+    std::unique_ptr<ScanLog> scan_log;
+    std::vector<IMUST> bl_states;
+    int64_t bl_first = 0;
+    if (use_log) scan_log.reset(new ScanLog(ctx));
 
     // VS:1951-2043: optimise the full window, then marginalise and slide
     auto window_step = [&](int k) {
@@ -294,9 +305,25 @@ int main(int argc, char **argv) {
         for (int i = 0; i < win_size; i++) out.insert(out.end(), &x_buf[i].t, &x_buf[i].t + 25);
         out.insert(out.end(), v6, v6 + 6);
 
+        if (use_log && scan_log->push(surf_map, 0) != win_base)  // VS:1974-1980: where the ScanPose is created, before the margi
+          throw std::runtime_error("mode 9: the scan's number is not win_base");
         surf_map.multi_margi(jour, win_count, x_buf);            // VS:1991
         jour += 0.1;
         surf_map.slide(mgsize);                                  // mp[] rotation VS:2014-2019
+        if (use_log) {                                           // VS:2001-2010 and VS:2354-2397 with the scans in the log
+          bl_states.push_back(x_buf[0]);
+          bl_index.push_back(scan_of_frame[0]);
+          scan_of_frame.erase(scan_of_frame.begin());
+          if ((int)bl_states.size() >= kf_every) {
+            const std::vector<IMUST> bl_local(bl_states.begin(), bl_states.begin() + kf_every);
+            keyframes->build(*scan_log, bl_first, bl_local, opt.voxel_size / 10, keyframes->size(), jour);
+            kf_x0.push_back(bl_local.back());
+            bl_states.erase(bl_states.begin(), bl_states.begin() + kf_every);
+            bl_index.erase(bl_index.begin(), bl_index.begin() + kf_every);
+            bl_first += kf_every;
+            scan_log->release(bl_first);                           // pvec = nullptr, VS:2375
+          }
+        }
         if (mode == 7) {                                         // VS:2001-2010: the marginalised scan goes to the loop-closure thread
           buf_lba2loop.emplace_back(new ScanPose(x_buf[0], pvec_buf[0]));
           bl_index.push_back(scan_of_frame[0]);
@@ -420,8 +447,8 @@ int main(int argc, char **argv) {
     }
 
     for (int k = k_first; k < n_scans; k++) {
-      if (mode == 7 && k == n_loop) {                            // loop_detect == 1 (VS:1768-1773)
-        if (keyframes->size() < 2 || win_count < 1) throw std::runtime_error("mode 7: the session built fewer than two keyframes");
+      if (loop_mode && k == n_loop) {                            // loop_detect == 1 (VS:1768-1773)
+        if (keyframes->size() < 2 || win_count < 1) throw std::runtime_error("mode 7 / 9: the session built fewer than two keyframes");
         for (IMUST &x0 : kf_x0) apply_dx(x0, dx);                // VS:2582-2587 with a synthetic correction
         keyframes->set_poses(0, kf_x0);
         const int n_ins = map_loop->build(*keyframes);           // VS:2601-2625
@@ -429,7 +456,8 @@ int main(int argc, char **argv) {
         for (auto &b : buf_lba2loop) bl.push_back(b.get());
         IMUST x_now = x_buf[win_count - 1];
         int g_upd = 0;
-        const int nf = surf_map.loop_update(*map_loop, dx, bl, x_buf, win_count, x_now, g_upd);
+        const int nf = use_log ? surf_map.loop_update(*map_loop, dx, *scan_log, bl_first, bl_states, x_buf, win_count, x_now, g_upd)
+                               : surf_map.loop_update(*map_loop, dx, bl, x_buf, win_count, x_now, g_upd);
         out.push_back(-3.0); out.push_back(n_ins); out.push_back(nf); out.push_back(keyframes->size());
         for (int i = 0; i < keyframes->size(); i++) {
           std::vector<XYZ> xyz, nrm;
@@ -439,11 +467,13 @@ int main(int argc, char **argv) {
           for (const XYZ &a : xyz) { out.push_back(a.x); out.push_back(a.y); out.push_back(a.z); }
           for (const XYZ &a : nrm) { out.push_back(a.x); out.push_back(a.y); out.push_back(a.z); }
         }
-        out.push_back((double)bl.size());
+        out.push_back((double)(use_log ? bl_states.size() : bl.size()));
         for (size_t i = 0; i < bl.size(); i++) { out.push_back(bl_index[i]); out.insert(out.end(), &bl[i]->x.t, &bl[i]->x.t + 25); }
+        for (size_t i = 0; i < bl_states.size(); i++) { out.push_back(bl_index[i]); out.insert(out.end(), &bl_states[i].t, &bl_states[i].t + 25); }
         out.push_back(win_count);
         for (int i = 0; i < win_count; i++) out.insert(out.end(), &x_buf[i].t, &x_buf[i].t + 25);
         buf_lba2loop.clear(); bl_index.clear();
+        if (use_log) { bl_first += (int64_t)bl_states.size(); bl_states.clear(); scan_log->release(bl_first); }   // VS:2342
         moved = true;
       }
       const int n = (int)next();
