@@ -1152,6 +1152,61 @@ int vba_motion_init_resident(vba_ctx *ctx, int win_size, vba_init_window *w, con
                              int *thresholds_left_relaxed, double *round_log, int max_rounds, double *pnt_out, double *var_out,
                              int *pvec_offsets, int pvec_cap);
 
+/* ------------------------------------------------------------------------------------------------
+ * IMU forward propagation and the odometry state resident in HBM: IMUEKF::motion_blur's propagation of state and
+ * covariance (ekf_imu.hpp, "EK", EK:54-123) with the pose table the undistortion reads, and the per-scan chain
+ * odom_ekf.process -> vba_scan_prepare -> lio_state_estimation -> pvec_update + cut_voxel (VS:1873-1922) on a state that stays on the
+ * device from one scan to the next.
+ *
+ * imu [m][7] = [t, gyr(3), acc(3)]: the deque rows as they are after imus.push_front(last_imu) (EK:43).  noise [12] = cov_gyr, cov_acc,
+ * cov_bias_gyr, cov_bias_acc.  Intervals whose tail lies before last_pcl_end_time are skipped (EK:64), cur_time is clamped (EK:81-84),
+ * a pose row [offt, R(9), p(3), v(3), angvel_avr(3), acc_imu(3)] (the row of vba_scan_undistort) is pushed before the update (EK:87),
+ * cov <- F_x cov F_x^T + cov_w (EK:92-105, not symmetrised), position, velocity, rotation move in that order (EK:108-110), the tail is
+ * extrapolated with note = +-1 (EK:117-123), state.t = pcl_end_time; bg, ba, g are not written.  *n_poses = the rows written, at most
+ * m - 1: it depends on comparisons of the time stamps alone.  end_pose [12] = (xc.R, xc.p) after the propagation.
+ * VBA_ERR_BAD_ARG with state and covariance untouched: m < 2; no interval left after the EK:64 skip (the reference reads
+ * uninitialised values at EK:120); last_pcl_end_time - pcl_beg_time > 0.01 (the "LiDAR time regress" exit(0) of EK:45-49); a
+ * non-finite input; a NULL pointer. */
+
+/* Host only (no context, no device): state [25] and cov [225] in / out, imu_poses [m - 1][22] (rows beyond *n_poses are not written). */
+int vba_imu_ekf_propagate(int m, const double *imu, const double *noise, double scale_gravity, double last_pcl_end_time,
+                          double pcl_beg_time, double pcl_end_time, double *state, double *cov, double *imu_poses, double *end_pose,
+                          int *n_poses);
+
+/* A state object belongs to the device of ctx and is created with room for 64 IMU rows; its pose table grows by doubling after a
+ * synchronise, and after vba_odom_state_reserve(st, max_imu_rows) no call on it allocates while m <= max_imu_rows
+ * (vba_odom_state_allocations counts allocations and bytes as vba_scan_frame_allocations does).  Destroy it before its context. */
+typedef struct vba_odom_state vba_odom_state;
+int vba_odom_state_create(vba_ctx *ctx, vba_odom_state **out);
+void vba_odom_state_destroy(vba_odom_state *st);
+int vba_odom_state_reserve(vba_odom_state *st, int max_imu_rows);
+int vba_odom_state_allocations(vba_odom_state *st, int *n_allocs, int64_t *bytes);
+/* state [25], cov [225]: stream-ordered through a pinned block (the arrays may go away on return).  Non-finite values: VBA_ERR_BAD_ARG. */
+int vba_odom_state_set(vba_odom_state *st, const double *state, const double *cov);
+/* Synchronises.  NULL outputs are skipped. */
+int vba_odom_state_get(vba_odom_state *st, double *state, double *cov);
+/* Inspection (synchronises): the table of the last propagation, imu_poses [max_rows][22] (VBA_ERR_CAPACITY when it has more rows),
+ * and end_pose [12]; NULL outputs are skipped. */
+int vba_odom_state_poses(vba_odom_state *st, int max_rows, double *imu_poses, double *end_pose, int *n_poses);
+/* The propagation above on the device state (EK:54-123): one upload of the IMU rows and the parameters, one launch, no wait.  The
+ * table and end_pose stay on the device for vba_scan_prepare_on_state.  *n_poses is computed by the host from the same doubles. */
+int vba_odom_state_propagate(vba_odom_state *st, const double *noise, double scale_gravity, int m, const double *imu,
+                             double last_pcl_end_time, double pcl_beg_time, double pcl_end_time, int *n_poses);
+/* vba_scan_prepare with imu_poses and end_pose read in place from the table that the last propagation of st left (EK:135-163). */
+int vba_scan_prepare_on_state(vba_ctx *ctx, vba_scan_frame *f, vba_odom_state *st, const double *ext_pose, int point_notime,
+                              double down_size, int min_points, double dept_err, double beam_err, int *n_out, const double **d_pnt_body,
+                              const double **d_var_body);
+/* vba_odom_lio_state_estimation_resident (VS:962-1098) on the state of st: the image of the call is built on the device (P^-1 of VS:987
+ * by the device restatement of the host inverse, bit for bit), no host inverse and no image upload; one download of the result block
+ * and one synchronise.  st holds the updated state and covariance afterwards; state_out [25] (may be NULL) receives the state.
+ * VBA_ERR_UNSUPPORTED on a sharded context. */
+int vba_odom_lio_state_estimation_on_state(vba_ctx *ctx, vba_odom_state *st, int n, const double *d_pnt_body, const double *d_var_body,
+                                           int *ok, vba_odom_report *report, double *state_out);
+/* vba_map_pvec_update_cut_voxel (VS:1903-1920) with the pose and the two covariance blocks read from st on the device: nothing but
+ * the arguments comes from the host.  VBA_ERR_UNSUPPORTED on a sharded context. */
+int vba_map_pvec_update_cut_voxel_on_state(vba_ctx *ctx, vba_odom_state *st, int win_count, int n, const double *d_pnt_body,
+                                           const double *d_var_body, int multi);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@
 //   build_graph + gtsam::ISAM2   VS:2078-2156, VS:2550-2561          vba::PoseGraph (add_edge LR:147-161, set_state LR:36-43)
 //   ResultOutput::pub_globalmap  VS:110-154                         vba::pub_globalmap
 //   pcl_handler VH:77-103; motion_blur's loop + VS:1877-1888        vba::ScanFrame::decode / prepare (ScanView feeds the odometry and the map)
+//   class IMUEKF (IMU_init, process, motion_blur) EK:8-216          vba::ImuEkf, on the host or on a vba::OdomState resident in HBM
 //
 // The reference's types are Eigen-based (tools.hpp:4).  This header compiles without Eigen (plain-array structs that
 // mirror PointCluster / IMUST / IMU_PRE field for field); when <Eigen/Core> is available the Eigen-typed overloads
@@ -577,6 +578,144 @@ inline int lio_state_estimation_kdtree(Context &ctx, const ScanView &scan, IMUST
   check(ctx.get(), vba_odom_lio_state_estimation_kdtree_resident(ctx.get(), scan.n, scan.pnt, &x_curr.t, x_curr.cov, &iters, report));
   return iters;
 }
+
+// ---- the odometry state resident in HBM: x_curr and its covariance stay on the device from one scan to the next;
+// the per-scan chain odom_ekf.process -> prepare -> lio_state_estimation -> pvec_update + cut_voxel_multi (VS:1873-1922) reads and
+// writes them where they lie
+class OdomState {
+ public:
+  explicit OdomState(Context &ctx) : ctx_(ctx.get()) { check(ctx_, vba_odom_state_create(ctx_, &s_)); }
+  ~OdomState() { vba_odom_state_destroy(s_); }
+  OdomState(const OdomState &) = delete;
+  OdomState &operator=(const OdomState &) = delete;
+  void reserve(int max_imu_rows) { check(ctx_, vba_odom_state_reserve(s_, max_imu_rows)); }
+  void set(const IMUST &x) { check(ctx_, vba_odom_state_set(s_, &x.t, x.cov)); }
+  void get(IMUST &x) { check(ctx_, vba_odom_state_get(s_, &x.t, x.cov)); }
+  // the pose table [n][22] of the last propagation and, when asked for, end_pose [12]
+  std::vector<double> poses(double *end_pose12 = nullptr) {
+    int n = 0;
+    check(ctx_, vba_odom_state_poses(s_, 0, nullptr, nullptr, &n));
+    std::vector<double> rows((size_t)22 * n);
+    check(ctx_, vba_odom_state_poses(s_, n, rows.data(), end_pose12, &n));
+    return rows;
+  }
+  // imu [m][7] = [t, gyr, acc] after push_front(last_imu); noise12 = cov_gyr, cov_acc, cov_bias_gyr, cov_bias_acc.  Returns the rows of the table.
+  int propagate(const double *noise12, double scale_gravity, int m, const double *imu, double last_pcl_end_time, double pcl_beg_time, double pcl_end_time) {
+    int n = 0;
+    check(ctx_, vba_odom_state_propagate(s_, noise12, scale_gravity, m, imu, last_pcl_end_time, pcl_beg_time, pcl_end_time, &n));
+    return n;
+  }
+  // ScanFrame::prepare with the table and end_pose of the last propagation read in place
+  ScanView prepare(Context &ctx, ScanFrame &frame, const IMUST &ext, bool point_notime, double down_size, double dept_err, double beam_err,
+                   int min_points = 500) {
+    double x[12];
+    std::memcpy(x, ext.R, 72); std::memcpy(x + 9, ext.p, 24);
+    ScanView v;
+    check(ctx.get(), vba_scan_prepare_on_state(ctx.get(), frame.get(), s_, x, point_notime ? 1 : 0, down_size, min_points, dept_err, beam_err, &v.n, &v.pnt, &v.var));
+    return v;
+  }
+  // lio_state_estimation (VS:962-1098) on the resident state; x_out, when given, receives the updated state (not its covariance)
+  bool lio_state_estimation(Context &ctx, const ScanView &scan, vba_odom_report *report = nullptr, IMUST *x_out = nullptr) {
+    int ok = 0;
+    check(ctx.get(), vba_odom_lio_state_estimation_on_state(ctx.get(), s_, scan.n, scan.pnt, scan.var, &ok, report, x_out ? &x_out->t : nullptr));
+    return ok != 0;
+  }
+  // pvec_update + cut_voxel_multi (VS:1903-1920) with the pose and covariance blocks of the resident state
+  void pvec_update_cut_voxel_multi(Context &ctx, const ScanView &scan, int win_count) {
+    check(ctx.get(), vba_map_pvec_update_cut_voxel_on_state(ctx.get(), s_, win_count, scan.n, scan.pnt, scan.var, 1));
+  }
+  vba_odom_state *get() const { return s_; }
+ private:
+  vba_ctx *ctx_;
+  vba_odom_state *s_ = nullptr;
+};
+
+// class IMUEKF (ekf_imu.hpp, "EK"): its fields and call surface without the point loop of the undistortion (EK:135-163), which is
+// ScanFrame::prepare.  A deque holds ImuSample values where the reference holds sensor_msgs::Imu::Ptr.
+class ImuEkf {
+ public:
+  bool init_flag = false;
+  double pcl_beg_time = 0, pcl_end_time = 0, last_pcl_end_time = 0;
+  int init_num = 0;
+  double mean_acc[3] = {0, 0, 0}, mean_gyr[3] = {0, 0, 0};
+  ImuSample last_imu{};
+  int min_init_num = 30;
+  double cov_acc[3] = {0, 0, 0}, cov_gyr[3] = {0, 0, 0}, cov_bias_gyr[3] = {0, 0, 0}, cov_bias_acc[3] = {0, 0, 0};
+  double scale_gravity = 1.0;
+  std::vector<double> imu_poses;     // [n][22], the rows of vba_scan_undistort (host propagation only; on a state the table stays on the device)
+  int n_poses = 0;
+  double end_pose[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+  std::string imu_topic = "/livox/imu";
+  int point_notime = 0;
+
+  void IMU_init(std::deque<ImuSample> &imus) {                                                    // EK:167-195
+    for (const ImuSample &imu : imus) {
+      if (init_num != 0) {
+        for (int k = 0; k < 3; k++) { mean_acc[k] += (imu.acc[k] - mean_acc[k]) / init_num; mean_gyr[k] += (imu.gyr[k] - mean_gyr[k]) / init_num; }
+      } else {
+        for (int k = 0; k < 3; k++) { mean_acc[k] = imu.acc[k]; mean_gyr[k] = imu.gyr[k]; }
+        init_num = 1;
+      }
+      init_num++;
+    }
+    last_imu = imus.back();
+  }
+  // process(x_curr, pcl_in, imus) EK:197-214 with the propagation on the host: 0 while initialising, then 1
+  int process(IMUST &x_curr, std::deque<ImuSample> &imus) {
+    if (!init_flag) return init_step(x_curr, imus);
+    std::vector<double> rows = begin_blur(imus);
+    imu_poses.assign((size_t)22 * (imus.size() - 1), 0.0);
+    double noise[12];
+    noise12(noise);
+    const int st = vba_imu_ekf_propagate((int)imus.size(), rows.data(), noise, scale_gravity, last_pcl_end_time, pcl_beg_time, pcl_end_time, &x_curr.t,
+                                         x_curr.cov, imu_poses.data(), end_pose, &n_poses);
+    if (st != VBA_OK) { imus.pop_front(); check(nullptr, st); }
+    imu_poses.resize((size_t)22 * n_poses);
+    end_blur(imus);
+    return 1;
+  }
+  // the same on a resident state: x_curr is written only while initialising (the caller sets the state once that has ended); the
+  // table and end_pose stay on the device for OdomState::prepare
+  int process(OdomState &state, IMUST &x_curr, std::deque<ImuSample> &imus) {
+    if (!init_flag) return init_step(x_curr, imus);
+    std::vector<double> rows = begin_blur(imus);
+    double noise[12];
+    noise12(noise);
+    try { n_poses = state.propagate(noise, scale_gravity, (int)imus.size(), rows.data(), last_pcl_end_time, pcl_beg_time, pcl_end_time); }
+    catch (...) { imus.pop_front(); throw; }
+    end_blur(imus);
+    return 1;
+  }
+
+ private:
+  void noise12(double *n) const { std::memcpy(n, cov_gyr, 24); std::memcpy(n + 3, cov_acc, 24); std::memcpy(n + 6, cov_bias_gyr, 24); std::memcpy(n + 9, cov_bias_acc, 24); }
+  int init_step(IMUST &x_curr, std::deque<ImuSample> &imus) {                                     // EK:199-210
+    IMU_init(imus);
+    double norm = 0;
+    for (int k = 0; k < 3; k++) norm += mean_acc[k] * mean_acc[k];
+    if (norm < 4 && imu_topic == "/livox/imu") scale_gravity = 9.8;                               // G_m_s2, TL:15
+    for (int k = 0; k < 3; k++) x_curr.g[k] = -mean_acc[k] * scale_gravity;
+    if (init_num > min_init_num) init_flag = true;
+    last_pcl_end_time = pcl_end_time;
+    return 0;
+  }
+  // EK:43-49: push_front(last_imu), the "LiDAR time regress" exit as an exception; the deque as rows [m][7]
+  std::vector<double> begin_blur(std::deque<ImuSample> &imus) {
+    if (last_pcl_end_time - pcl_beg_time > 0.01) throw std::runtime_error("LiDAR time regress. Please check data");
+    imus.push_front(last_imu);
+    std::vector<double> rows(imus.size() * 7);
+    for (size_t i = 0; i < imus.size(); i++) { rows[7 * i] = imus[i].t; std::memcpy(&rows[7 * i + 1], imus[i].gyr, 24); std::memcpy(&rows[7 * i + 4], imus[i].acc, 24); }
+    return rows;
+  }
+  // EK:125-133: last_imu keeps the back as it came, front and back become copies re-stamped to the scan's ends (push_imu reads them, VS:1913)
+  void end_blur(std::deque<ImuSample> &imus) {
+    ImuSample imu1 = imus.front(), imu2 = imus.back();
+    imu1.t = last_pcl_end_time; imu2.t = pcl_end_time;
+    last_imu = imus.back();
+    last_pcl_end_time = pcl_end_time;
+    imus.front() = imu1; imus.back() = imu2;
+  }
+};
 
 // FileReaderWriter::save_pcd / save_pose (VS:166-204), pcl::io::loadPCDFile (VS:340), read_lidarstate (VH:268-307)
 inline void save_pcd(const std::vector<pointVar> &pvec, int count, const std::string &savename) {

@@ -52,6 +52,9 @@ EXPORTS = [
     "vba_scan_frame_allocations", "vba_scan_decode", "vba_scan_prepare", "vba_scan_frame_read",
     "vba_init_window_create", "vba_init_window_destroy", "vba_init_window_reserve", "vba_init_window_allocations", "vba_init_window_clear",
     "vba_init_window_size", "vba_init_window_push", "vba_init_window_push_points", "vba_init_window_read", "vba_motion_init_resident",
+    "vba_imu_ekf_propagate", "vba_odom_state_create", "vba_odom_state_destroy", "vba_odom_state_reserve", "vba_odom_state_allocations",
+    "vba_odom_state_set", "vba_odom_state_get", "vba_odom_state_poses", "vba_odom_state_propagate", "vba_scan_prepare_on_state",
+    "vba_odom_lio_state_estimation_on_state", "vba_map_pvec_update_cut_voxel_on_state",
 ]
 
 
@@ -709,6 +712,85 @@ class OdomReport(C.Structure):
                 ("nnt_eig_min", C.c_double)]
 
 
+class OdomState:
+    """One vba_odom_state: the odometry state and its covariance resident in HBM from one scan to the next, with the pose table of
+    the IMU propagation."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx._chk(self.lib.vba_odom_state_create(ctx.h, C.byref(h)))
+        self.h = h
+        ctx._kf.append(self)         # destroyed with its context, as the stores are
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.vba_odom_state_destroy(self.h)
+            self.h = None
+        kf = getattr(self.ctx, "_kf", None)
+        if kf is not None and self in kf:
+            kf.remove(self)
+
+    def reserve(self, max_imu_rows):
+        self.ctx._chk(self.lib.vba_odom_state_reserve(self.h, C.c_int(max_imu_rows)))
+
+    def allocations(self):
+        n = C.c_int(); b = C.c_int64()
+        self.ctx._chk(self.lib.vba_odom_state_allocations(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def set(self, state25, cov225):
+        self.ctx._chk(self.lib.vba_odom_state_set(self.h, _p(_c(state25)), _p(_c(cov225))))
+
+    def get(self):
+        """(state [25], cov [15][15]); synchronises"""
+        st = np.zeros(25); cov = np.zeros((15, 15))
+        self.ctx._chk(self.lib.vba_odom_state_get(self.h, _p(st), _p(cov)))
+        return st, cov
+
+    def poses(self):
+        """(imu_poses [n][22], end_pose [12]) of the last propagation; synchronises"""
+        n = C.c_int(0)
+        self.ctx._chk(self.lib.vba_odom_state_poses(self.h, C.c_int(0), None, None, C.byref(n)))
+        rows = np.zeros((n.value, 22)); end = np.zeros(12)
+        self.ctx._chk(self.lib.vba_odom_state_poses(self.h, C.c_int(n.value), _p(rows), _p(end), C.byref(n)))
+        return rows, end
+
+    def propagate(self, imu, noise12, last_pcl_end_time, pcl_beg_time, pcl_end_time, scale_gravity=1.0):
+        """IMUEKF::motion_blur's propagation (ekf_imu.hpp:54-123) on the device state; returns the rows of the pose table.  No wait."""
+        imu = _c(imu).reshape(-1, 7); n = C.c_int(0)
+        self.ctx._chk(self.lib.vba_odom_state_propagate(self.h, _p(_c(noise12)), C.c_double(scale_gravity), C.c_int(len(imu)), _p(imu),
+                                                        C.c_double(last_pcl_end_time), C.c_double(pcl_beg_time), C.c_double(pcl_end_time), C.byref(n)))
+        return n.value
+
+    def prepare(self, frame, ext_pose12, down_size, dept_err, beam_err, min_points=500, point_notime=False, ctx=None):
+        """ScanFrame.prepare with the table and end_pose of the last propagation read in place: (n, d_pnt_body, d_var_body)."""
+        ctx = ctx or self.ctx
+        n = C.c_int(0); dp = C.c_void_p(); dv = C.c_void_p()
+        ctx._chk(self.lib.vba_scan_prepare_on_state(ctx.h, frame.h, self.h, _p(_c(ext_pose12)), C.c_int(int(point_notime)), C.c_double(down_size),
+                                                    C.c_int(min_points), C.c_double(dept_err), C.c_double(beam_err), C.byref(n), C.byref(dp), C.byref(dv)))
+        frame.n_ds = n.value
+        return n.value, dp.value or 0, dv.value or 0
+
+    def lio_state_estimation(self, n, d_pnt_body, d_var_body, ctx=None):
+        """Context.lio_state_estimation_resident on the resident state: (ok, state, report); the state object holds state and
+        covariance afterwards."""
+        ctx = ctx or self.ctx
+        ok = C.c_int(0); rep = OdomReport(); st = np.zeros(25)
+        ctx._chk(self.lib.vba_odom_lio_state_estimation_on_state(ctx.h, self.h, C.c_int(n), C.c_void_p(d_pnt_body), C.c_void_p(d_var_body), C.byref(ok),
+                                                                 C.byref(rep), _p(st)))
+        report = dict(iterations=rep.iterations, match_num=np.array(rep.match_num[:], dtype=np.int64), rot_add=np.array(rep.rot_add[:]),
+                      tra_add=np.array(rep.tra_add[:]), nnt_eig_min=rep.nnt_eig_min)
+        return bool(ok.value), st, report
+
+    def pvec_update_cut_voxel(self, win_count, n, d_pnt_body, d_var_body, multi=False, ctx=None):
+        """Context.pvec_update_cut_voxel_dev with the pose and covariance blocks of the resident state."""
+        ctx = ctx or self.ctx
+        ctx._chk(self.lib.vba_map_pvec_update_cut_voxel_on_state(ctx.h, self.h, C.c_int(win_count), C.c_int(n), C.c_void_p(d_pnt_body),
+                                                                 C.c_void_p(d_var_body), C.c_int(int(multi))))
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 
@@ -799,6 +881,18 @@ def imu_give_evaluate(imu, st1, st2, with_g=False, jac=True):
     if st:
         raise VbaError(st)
     return r.value, jtj, gg
+
+
+def imu_ekf_propagate(imu, noise12, last_pcl_end_time, pcl_beg_time, pcl_end_time, state25, cov225, scale_gravity=1.0):
+    """IMUEKF::motion_blur's propagation (ekf_imu.hpp:54-123) on the host: imu [m][7] after push_front(last_imu).  Returns
+    (state, cov [15][15], imu_poses [n][22], end_pose [12])."""
+    imu = _c(imu).reshape(-1, 7); st = _c(state25).copy(); cov = _c(cov225).reshape(15, 15).copy()
+    rows = np.zeros((max(len(imu) - 1, 1), 22)); end = np.zeros(12); n = C.c_int(0)
+    r = load().vba_imu_ekf_propagate(C.c_int(len(imu)), _p(imu), _p(_c(noise12)), C.c_double(scale_gravity), C.c_double(last_pcl_end_time),
+                                     C.c_double(pcl_beg_time), C.c_double(pcl_end_time), _p(st), _p(cov), _p(rows), _p(end), C.byref(n))
+    if r:
+        raise VbaError(r)
+    return st, cov, rows[:n.value].copy(), end
 
 
 def init_imu_poses(imu, state_c, state_l, beg_time, scale_gravity=1.0):
@@ -1202,6 +1296,9 @@ class Context:
 
     def scan_frame(self) -> "ScanFrame":
         return ScanFrame(self)
+
+    def odom_state(self) -> "OdomState":
+        return OdomState(self)
 
     def var_init(self, pnt, ext_pose12, dept_err, beam_err):
         """var_init (voxelslam.hpp:210-234): returns (pnt_out, var_out)."""

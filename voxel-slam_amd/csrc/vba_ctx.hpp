@@ -233,7 +233,30 @@ struct vba_scanlog {
   int allocs = 0; int64_t bytes = 0;
 };
 
+// odometry state (vba_odom.hip); the scan frame reads its pose table in place
+struct vba_odom_state {
+  vba_ctx *ctx = nullptr;
+  DevMem<double> d_blk;            // [state 25 | P 225 | 6 unused]
+  // sized by cap IMU rows: the pose table [cap - 1][22] | end_pose 12 | extrinsic 12 (the parameter block of k_undistort), the upload
+  // [parameters 16 | imu cap x 7] with its pinned image
+  int cap = 0;
+  DevMem<double> d_tab, d_up; PinMem<double> h_up;
+  PinMem<double> h_blk;            // set / get / poses: one pinned block of max(256, table) doubles
+  hipEvent_t up_ev = nullptr;      // behind the newest copy out of h_up or h_blk
+  bool up_pending = false;
+  hipEvent_t res_ev = nullptr;     // behind the result download of the scan-to-map update, ahead of the copy back into the block
+  int n_poses = 0;                 // rows of the table that the last propagation wrote
+  hipStream_t last = nullptr;      // the stream of the last call that queued work on the block
+  int allocs = 0; int64_t bytes = 0;
+};
+
 namespace vba {
+
+// ---------------------------------------------------------------- vba_odom.hip (vba_kernels_imu_ekf.hpp)
+// Orders `stream` behind the work queued on the state's buffers by its last user.
+int odom_state_order(vba_odom_state *st, hipStream_t stream, std::string &err);
+// the map's pose image from the state block, launched by map_cut_voxel
+__global__ __launch_bounds__(64) void k_odom_state_pose(const double *blk, double *poses);
 
 // ---------------------------------------------------------------- vba_scanlog.hip
 // Scans first .. first + k - 1 for a reader on `stream`, which is ordered behind their captures: starts[i] = the first arena row of
@@ -300,7 +323,7 @@ int map_base(MapStore &s, hipStream_t st, std::string &err);
 void map_free(MapStore &s);
 bool is_device_ptr(const void *p);
 int map_cut_voxel(MapStore &s, hipStream_t st, int win_count, int n, const double *pnt_body, const double *var, const double *pose,
-                  bool multi, std::string &err, const double *cov6 = nullptr);
+                  bool multi, std::string &err, const double *cov6 = nullptr, const double *d_state_blk = nullptr);
 int map_cut_voxel_fix(MapStore &s, hipStream_t st, int n, const double *pnt_world, double jour, std::string &err);
 int map_recut(MapStore &s, hipStream_t st, int win_count, const double *poses, bool multi, std::string &err, int *n_factors);
 int map_extract_factors(MapStore &s, hipStream_t st, FactorView f, std::string &err, int *n_factors);
@@ -314,6 +337,9 @@ int map_dump_plane_var(MapStore &s, hipStream_t st, double *out, int max_leaves,
 int map_prune(MapStore &s, hipStream_t st, double jour, int dist, std::string &err);
 int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomEkf *h_img, int n, const double *d_pts,
                       const double *d_var, double *d_partial, std::string &err);
+// its four (point loop, update) pairs alone, on an image that is already in d_S
+int map_odom_queue(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, int n, const double *d_pts, const double *d_var, double *d_partial,
+                   std::string &err);
 int map_odom_debug_sums(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, const vbh::OdomEkf *h_img, int n, const double *d_pts,
                         const double *d_var, double *d_partial, double *d_sums, int *nb_out, std::string &err);
 int map_debug_plane_update(hipStream_t st, int n, const double *in, double *out, std::string &err);

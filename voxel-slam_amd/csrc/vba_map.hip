@@ -226,9 +226,9 @@ inline void map_ins_roots(MapStore &s, hipStream_t st, const MapParams &P, int s
 
 // cut_voxel / cut_voxel_multi for one scan
 int map_cut_voxel(MapStore &s, hipStream_t st, int win_count, int n, const double *pnt_body, const double *var, const double *pose,
-                  bool multi, std::string &err, const double *cov6) {
+                  bool multi, std::string &err, const double *cov6, const double *d_state_blk) {
   const int W = s.opt.win_size;
-  if (win_count < 0 || win_count >= W || n < 0 || !pose || (n > 0 && !pnt_body)) return VBA_ERR_BAD_ARG;
+  if (win_count < 0 || win_count >= W || n < 0 || (!pose && !d_state_blk) || (n > 0 && !pnt_body)) return VBA_ERR_BAD_ARG;
   int r = map_base(s, st, err);
   if (r) return r;
   if (s.cnt_stale && (s.ub_nodes + n + 64 > (long long)s.v.cap || 2 * (s.ub_used + n) > (long long)s.hcap)) {
@@ -254,7 +254,9 @@ int map_cut_voxel(MapStore &s, hipStream_t st, int win_count, int n, const doubl
     }
   }
   if (var) s.have_var = true;
-  {  // pose upload through a pinned ring: no implicit synchronisation of a pageable copy
+  // pose and covariance blocks of a resident odometry state: written where they lie, nothing comes from the host
+  if (d_state_blk) hipLaunchKernelGGL(k_odom_state_pose, dim3(1), dim3(64), 0, st, d_state_blk, s.v.poses);
+  else {  // pose upload through a pinned ring: no implicit synchronisation of a pageable copy
     VBA_HIPCHK(err, s.h_pose_ring.ensure(8 * 40));
     const int k = s.pose_next; s.pose_next = (k + 1) & 7;
     if (!s.pose_ev[k]) VBA_HIPCHK(err, hipEventCreateWithFlags(&s.pose_ev[k], hipEventDisableTiming));
@@ -267,7 +269,7 @@ int map_cut_voxel(MapStore &s, hipStream_t st, int win_count, int n, const doubl
   }
   const MapParams P = map_params(s);
   const int nb = (n + 255) / 256;
-  if (cov6 && var) hipLaunchKernelGGL(k_scan_to_soa_pvec_update, dim3(nb), dim3(256), 0, st, s.v, W, slot, n, d_pts, d_var, s.v.poses, s.v.poses + 16);
+  if ((cov6 || d_state_blk) && var) hipLaunchKernelGGL(k_scan_to_soa_pvec_update, dim3(nb), dim3(256), 0, st, s.v, W, slot, n, d_pts, d_var, s.v.poses, s.v.poses + 16);
   else hipLaunchKernelGGL(k_scan_to_soa, dim3(nb), dim3(256), 0, st, s.v, W, slot, n, d_pts, d_var);
   s.stamp++;
   map_ins_roots(s, st, P, slot, n, 0, 0.0, s.stamp);
@@ -692,17 +694,23 @@ static int map_odom_point_loop(MapStore &s, hipStream_t st, const MapParams &P, 
   hipLaunchKernelGGL(k_odom_match_dev, dim3(nb), dim3(256), 0, st, s.v, P, d_S, n, d_pts, d_var, d_partial);
   return nb;
 }
-// The whole call on the stream: one upload of the image, (match, update) x 4, one download of the result block, one wait.  h_img
-// is pinned and holds the image on entry and the result block on return.
-int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomEkf *h_img, int n, const double *d_pts,
-                      const double *d_var, double *d_partial, std::string &err) {
-  VBA_HIPCHK(err, hipMemcpyAsync(d_S, h_img, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, st));
+int map_odom_queue(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, int n, const double *d_pts, const double *d_var, double *d_partial,
+                   std::string &err) {
   const MapParams P = map_params(s);
   for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
     const int nb = map_odom_point_loop(s, st, P, d_S, n, d_pts, d_var, d_partial);
     hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, st, d_S, (const double *)d_partial, nb, iter, 0);
   }
   VBA_HIPCHK(err, hipGetLastError());
+  return VBA_OK;
+}
+// The whole call on the stream: one upload of the image, (match, update) x 4, one download of the result block, one wait.  h_img
+// is pinned and holds the image on entry and the result block on return.
+int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomEkf *h_img, int n, const double *d_pts,
+                      const double *d_var, double *d_partial, std::string &err) {
+  VBA_HIPCHK(err, hipMemcpyAsync(d_S, h_img, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, st));
+  const int r = map_odom_queue(s, st, d_S, n, d_pts, d_var, d_partial, err);
+  if (r) return r;
   const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
   VBA_HIPCHK(err, hipMemcpyAsync((char *)h_img + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, st));
   VBA_HIPCHK(err, hipStreamSynchronize(st));

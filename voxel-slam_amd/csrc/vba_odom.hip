@@ -1,9 +1,12 @@
 // libvoxelba.so: the odometry EKF updates, both variants.  The initialisation odometry on a point-cloud map (vba_odom_kdtree_*,
 // vba_odom_lio_state_estimation_kdtree*) with the kernels of vba_kernels_kd.hpp, compiled here and nowhere else, and
 // the scan-to-map update on the voxel map (vba_odom_lio_state_estimation*, §17), whose kernels the map unit compiles
-// (vba_kernels_odom.hpp) and whose loop it queues (map_odom_resident).
+// (vba_kernels_odom.hpp) and whose loop it queues (map_odom_resident).  And the odometry state resident in HBM (vba_odom_state_*, the
+// IMU propagation vba_imu_ekf_propagate / vba_odom_state_propagate, the update and the insertion on a state object) with
+// the kernels of vba_kernels_imu_ekf.hpp, compiled here and nowhere else.
 #include "vba_ctx.hpp"
 #include "vba_kernels_kd.hpp"
+#include "vba_kernels_imu_ekf.hpp"
 #include "vba_hostmath.hpp"
 #include "vba_odom_ekf.hpp"
 
@@ -318,6 +321,210 @@ int vba_debug_odom_sums(vba_ctx *c, int kind, int n, const double *pnt_body, con
   if (e == hipSuccess && kd) e = hipMemcpy(cand, d_cand.p, (size_t)ns * n * 5 * sizeof(unsigned long long), hipMemcpyDefault);
   HIPCHK(c, e);
   return VBA_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the odometry state resident in HBM (vba_kernels_imu_ekf.hpp)
+namespace vba {
+int odom_state_order(vba_odom_state *st, hipStream_t stream, std::string &err) {
+  if (st->last && st->last != stream) {
+    // up_ev serves: recorded again on the same stream it only moves later, and the host waits for it before it writes a pinned block
+    VBA_HIPCHK(err, hipEventRecord(st->up_ev, st->last));
+    VBA_HIPCHK(err, hipStreamWaitEvent(stream, st->up_ev, 0));
+    st->up_pending = true;
+  }
+  st->last = stream;
+  return VBA_OK;
+}
+}  // namespace vba
+static size_t ost_tab_doubles(int cap) { return (size_t)vbh::IE_ROW * (cap - 1) + 24; }
+static size_t ost_up_doubles(int cap) { return (size_t)vbh::IE_PRM + (size_t)7 * cap; }
+// the pinned blocks are free again once the copy (or the event of another stream's reader) recorded behind their last use has passed
+static int ost_pinned_free(vba_odom_state *st) {
+  if (st->up_pending) { HIPCHK(st->ctx, hipEventSynchronize(st->up_ev)); st->up_pending = false; }
+  return VBA_OK;
+}
+static int ost_drain(vba_odom_state *st) {
+  vba_ctx *c = st->ctx;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (st->last && st->last != c->stream) HIPCHK(c, hipDeviceSynchronize());
+  st->up_pending = false;
+  return VBA_OK;
+}
+// grow-only by doubling; the table's contents do not survive (a propagation rewrites all of them)
+static int ost_ensure(vba_odom_state *st, int rows) {
+  if (rows <= st->cap) return VBA_OK;
+  vba_ctx *c = st->ctx;
+  int cap = st->cap ? st->cap : 64;
+  while (cap < rows) cap *= 2;
+  int r = ost_drain(st);
+  if (r) return r;
+  st->cap = 0; st->n_poses = 0;
+  const size_t tab = ost_tab_doubles(cap), up = ost_up_doubles(cap), pin = std::max<size_t>(ODOM_STATE_BLOCK, tab);
+  HIPCHK(c, st->d_tab.ensure(tab)); HIPCHK(c, st->d_up.ensure(up));
+  HIPCHK(c, st->h_up.ensure(up)); HIPCHK(c, st->h_blk.ensure(pin));
+  st->cap = cap; st->allocs += 4; st->bytes += (int64_t)((tab + 2 * up + pin) * sizeof(double));
+  return VBA_OK;
+}
+
+extern "C" {
+
+int vba_imu_ekf_propagate(int m, const double *imu, const double *noise, double scale_gravity, double last_pcl_end_time, double pcl_beg_time,
+                          double pcl_end_time, double *state, double *cov, double *imu_poses, double *end_pose, int *n_poses) {
+  if (!imu || !noise || !state || !cov || !imu_poses || !end_pose || !n_poses || m < 2) return VBA_ERR_BAD_ARG;
+  double prm[vbh::IE_PRM] = {last_pcl_end_time, pcl_beg_time, pcl_end_time, scale_gravity};
+  std::memcpy(prm + vbh::IE_NOISE, noise, 12 * sizeof(double));
+  if (!vbh::imu_ekf_args_ok(m, imu, prm) || !all_finite(state, 25) || !all_finite(cov, 225)) return VBA_ERR_BAD_ARG;
+  std::vector<double> w(vbh::IE_WORK);
+  vbh::State x;
+  std::memcpy(&x, state, sizeof(x));
+  *n_poses = vbh::imu_ekf_propagate(w.data(), m, imu, prm, &x, cov, imu_poses, end_pose, 0, 1, [] {});
+  std::memcpy(state, &x, sizeof(x));
+  return VBA_OK;
+}
+
+int vba_odom_state_create(vba_ctx *c, vba_odom_state **out) {
+  if (!c || !out) return VBA_ERR_BAD_ARG;
+  *out = nullptr;
+  HIPCHK(c, hipSetDevice(c->device));
+  vba_odom_state *st = new vba_odom_state();
+  st->ctx = c;
+  int r = ost_ensure(st, 64);
+  if (!r && st->d_blk.ensure(ODOM_STATE_BLOCK) != hipSuccess) r = VBA_ERR_HIP;
+  if (!r && hipMemsetAsync(st->d_blk.p, 0, ODOM_STATE_BLOCK * sizeof(double), c->stream) != hipSuccess) r = VBA_ERR_HIP;
+  if (!r && hipEventCreateWithFlags(&st->up_ev, hipEventDisableTiming) != hipSuccess) r = VBA_ERR_HIP;
+  if (!r && hipEventCreateWithFlags(&st->res_ev, hipEventDisableTiming) != hipSuccess) r = VBA_ERR_HIP;
+  if (r) { vba_odom_state_destroy(st); return r; }
+  st->allocs++; st->bytes += (int64_t)(ODOM_STATE_BLOCK * sizeof(double));
+  st->last = c->stream;
+  *out = st;
+  return VBA_OK;
+}
+
+void vba_odom_state_destroy(vba_odom_state *st) {
+  if (!st) return;
+  hipSetDevice(st->ctx->device);
+  hipStreamSynchronize(st->ctx->stream);
+  if (st->last && st->last != st->ctx->stream) hipDeviceSynchronize();
+  if (st->up_ev) hipEventDestroy(st->up_ev);
+  if (st->res_ev) hipEventDestroy(st->res_ev);
+  delete st;
+}
+
+int vba_odom_state_reserve(vba_odom_state *st, int max_imu_rows) {
+  if (!st || max_imu_rows < 0 || max_imu_rows > (1 << 20)) return VBA_ERR_BAD_ARG;
+  HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+  return ost_ensure(st, max_imu_rows);
+}
+
+int vba_odom_state_allocations(vba_odom_state *st, int *n_allocs, int64_t *bytes) {
+  if (!st || !n_allocs || !bytes) return VBA_ERR_BAD_ARG;
+  *n_allocs = st->allocs; *bytes = st->bytes;
+  return VBA_OK;
+}
+
+int vba_odom_state_set(vba_odom_state *st, const double *state, const double *cov) {
+  if (!st || !state || !cov || !all_finite(state, 25) || !all_finite(cov, 225)) return VBA_ERR_BAD_ARG;
+  vba_ctx *c = st->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  int r = ost_pinned_free(st);
+  if (r || (r = odom_state_order(st, c->stream, c->err))) return r;
+  std::memcpy(st->h_blk.p, state, 25 * sizeof(double));
+  std::memcpy(st->h_blk.p + 25, cov, 225 * sizeof(double));
+  HIPCHK(c, hipMemcpyAsync(st->d_blk.p, st->h_blk.p, 250 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(st->up_ev, c->stream));
+  st->up_pending = true;
+  return VBA_OK;
+}
+
+int vba_odom_state_get(vba_odom_state *st, double *state, double *cov) {
+  if (!st) return VBA_ERR_BAD_ARG;
+  vba_ctx *c = st->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  int r = ost_pinned_free(st);
+  if (r || (r = odom_state_order(st, c->stream, c->err))) return r;
+  HIPCHK(c, hipMemcpyAsync(st->h_blk.p, st->d_blk.p, 250 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  st->up_pending = false;
+  if (state) std::memcpy(state, st->h_blk.p, 25 * sizeof(double));
+  if (cov) std::memcpy(cov, st->h_blk.p + 25, 225 * sizeof(double));
+  return VBA_OK;
+}
+
+int vba_odom_state_poses(vba_odom_state *st, int max_rows, double *imu_poses, double *end_pose, int *n_poses) {
+  if (!st || max_rows < 0) return VBA_ERR_BAD_ARG;
+  if (n_poses) *n_poses = st->n_poses;
+  if (imu_poses && st->n_poses > max_rows) return VBA_ERR_CAPACITY;
+  vba_ctx *c = st->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  int r = ost_pinned_free(st);
+  if (r || (r = odom_state_order(st, c->stream, c->err))) return r;
+  const size_t nd = (size_t)vbh::IE_ROW * st->n_poses + 12;
+  HIPCHK(c, hipMemcpyAsync(st->h_blk.p, st->d_tab.p, nd * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  st->up_pending = false;
+  if (imu_poses) std::memcpy(imu_poses, st->h_blk.p, (nd - 12) * sizeof(double));
+  if (end_pose) std::memcpy(end_pose, st->h_blk.p + nd - 12, 12 * sizeof(double));
+  return VBA_OK;
+}
+
+int vba_odom_state_propagate(vba_odom_state *st, const double *noise, double scale_gravity, int m, const double *imu, double last_pcl_end_time,
+                             double pcl_beg_time, double pcl_end_time, int *n_poses) {
+  if (!st || !noise || !imu || !n_poses || m < 2 || m > (1 << 20)) return VBA_ERR_BAD_ARG;
+  double prm[vbh::IE_PRM] = {last_pcl_end_time, pcl_beg_time, pcl_end_time, scale_gravity};
+  std::memcpy(prm + vbh::IE_NOISE, noise, 12 * sizeof(double));
+  if (!vbh::imu_ekf_args_ok(m, imu, prm)) return VBA_ERR_BAD_ARG;
+  vba_ctx *c = st->ctx;
+  HIPCHK(c, hipSetDevice(c->device));
+  int r = ost_ensure(st, m);
+  if (r || (r = ost_pinned_free(st)) || (r = odom_state_order(st, c->stream, c->err))) return r;
+  std::memcpy(st->h_up.p, prm, sizeof(prm));
+  std::memcpy(st->h_up.p + vbh::IE_PRM, imu, (size_t)7 * m * sizeof(double));
+  HIPCHK(c, hipMemcpyAsync(st->d_up.p, st->h_up.p, ost_up_doubles(m) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(st->up_ev, c->stream));
+  st->up_pending = true;
+  const int rows = vbh::imu_ekf_count(m, imu, last_pcl_end_time);
+  hipLaunchKernelGGL(k_imu_propagate, dim3(1), dim3(256), 0, c->stream, m, rows, (const double *)st->d_up.p, st->d_blk.p, st->d_tab.p);
+  HIPCHK(c, hipGetLastError());
+  *n_poses = st->n_poses = rows;
+  return VBA_OK;
+}
+
+int vba_odom_lio_state_estimation_on_state(vba_ctx *c, vba_odom_state *st, int n, const double *d_pnt_body, const double *d_var_body, int *ok,
+                                           vba_odom_report *report, double *state_out) {
+  if (!c || !st || n < 0 || (n > 0 && (!d_pnt_body || !d_var_body)) || c->device != st->ctx->device) return VBA_ERR_BAD_ARG;
+  if (c->n_ranks > 1) { c->set_error("the resident odometry loop has no all-reduce step between its iterations: unsharded contexts only"); return VBA_ERR_UNSUPPORTED; }
+  HIPCHK(c, hipSetDevice(c->device));
+  int r = odom_image_ensure(c);
+  if (r || (r = odom_part_ensure(c, n)) || (r = odom_state_order(st, c->stream, c->err))) return r;
+  hipStream_t s = c->stream;
+  vbh::OdomEkf *d_S = c->d_odom;
+  vbh::OdomEkf &S = *c->h_odom;
+  hipLaunchKernelGGL(k_odom_begin_dev, dim3(1), dim3(256), 0, s, d_S, (const double *)st->d_blk.p);
+  if ((r = map_odom_queue(c->map, s, d_S, n, d_pnt_body, d_var_body, c->d_odom_part, c->err))) return r;
+  // the wait is for the download alone: the copy back into the state block runs behind it, ordered before whatever reads the block next
+  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
+  HIPCHK(c, hipMemcpyAsync((char *)&S + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipEventRecord(st->res_ev, s));
+  hipLaunchKernelGGL(k_odom_commit_dev, dim3(1), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, st->d_blk.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventSynchronize(st->res_ev));
+  const double emin = vbh::odom_nnt_eig_min(S.nnt);      // VS:1090-1097
+  if (ok) *ok = (emin < 14) ? 0 : 1;
+  if (report) odom_report_fill(report, S, emin);
+  if (state_out) std::memcpy(state_out, &S.x_curr, sizeof(S.x_curr));
+  return VBA_OK;
+}
+
+int vba_map_pvec_update_cut_voxel_on_state(vba_ctx *c, vba_odom_state *st, int win_count, int n, const double *d_pnt_body, const double *d_var_body,
+                                           int multi) {
+  if (!c || !st || !d_var_body || c->device != st->ctx->device) return VBA_ERR_BAD_ARG;
+  if (c->n_ranks > 1) { c->set_error("the insertion on a resident odometry state runs on one rank's map: unsharded contexts only"); return VBA_ERR_UNSUPPORTED; }
+  HIPCHK(c, hipSetDevice(c->device));
+  const int r = odom_state_order(st, c->stream, c->err);
+  if (r) return r;
+  return map_cut_voxel(c->map, c->stream, win_count, n, d_pnt_body, d_var_body, nullptr, multi != 0, c->err, nullptr, st->d_blk.p);
 }
 
 }  // extern "C"

@@ -251,10 +251,13 @@ int vba_scan_decode(vba_scan_frame *f, const vba_scan_layout *l, const void *raw
   return VBA_OK;
 }
 
-int vba_scan_prepare(vba_ctx *c, vba_scan_frame *f, int m, const double *imu_poses, const double *end_pose, const double *ext_pose, int point_notime,
-                     double down_size, int min_points, double dept_err, double beam_err, int *n_out, const double **d_pnt_body, const double **d_var_body) {
+// vba_scan_prepare, and with `os` vba_scan_prepare_on_state: the table and end_pose are then the ones a propagation left in the state's
+// parameter block, read in place; only the extrinsic goes up, behind them
+static int scan_prepare_core(vba_ctx *c, vba_scan_frame *f, int m, const double *imu_poses, const double *end_pose, const double *ext_pose, int point_notime,
+                             double down_size, int min_points, double dept_err, double beam_err, int *n_out, const double **d_pnt_body,
+                             const double **d_var_body, vba_odom_state *os) {
   if (!c || !f || !n_out || !d_pnt_body || !d_var_body || m < 0 || !ext_pose || !(down_size == down_size)) return VBA_ERR_BAD_ARG;
-  if (!point_notime && (!end_pose || (m > 0 && !imu_poses))) return VBA_ERR_BAD_ARG;
+  if (!os && !point_notime && (!end_pose || (m > 0 && !imu_poses))) return VBA_ERR_BAD_ARG;
   if (!f->decoded || c->device != f->ctx->device) return VBA_ERR_BAD_ARG;
   *n_out = 0; *d_pnt_body = f->d_pb; *d_var_body = f->d_vb;
   f->prepared = false; f->n_ds = 0;
@@ -262,19 +265,27 @@ int vba_scan_prepare(vba_ctx *c, vba_scan_frame *f, int m, const double *imu_pos
   const int n = f->n;
   if (n == 0) { f->prepared = true; return VBA_OK; }
   const int mu = point_notime ? 0 : m;
-  int st = frame_ensure_prm(f, mu);
+  int st = frame_ensure_prm(f, os ? 0 : mu);
   if (st) return st;
   hipStream_t s = c->stream;
   f->last = s;
   // the parameter block of k_undistort; its last 12 doubles, the extrinsic, are also var_init's
-  double *prm = f->h_prm;
-  if (mu > 0) std::memcpy(prm, imu_poses, (size_t)22 * mu * sizeof(double));
-  if (end_pose) std::memcpy(prm + (size_t)22 * mu, end_pose, 12 * sizeof(double)); else std::memset(prm + (size_t)22 * mu, 0, 12 * sizeof(double));
-  std::memcpy(prm + (size_t)22 * mu + 12, ext_pose, 12 * sizeof(double));
-  HIPCHK(c, hipMemcpyAsync(f->d_prm, prm, ((size_t)22 * mu + 24) * sizeof(double), hipMemcpyHostToDevice, s));
+  double *prm = f->h_prm, *d_prm = f->d_prm;
+  const size_t ext_at = (size_t)22 * (os ? os->n_poses : mu) + 12;         // (the state's table keeps its rows when the scan has no time stamps)
+  if (os) {
+    if ((st = odom_state_order(os, s, c->err))) return st;
+    d_prm = os->d_tab;
+    std::memcpy(prm, ext_pose, 12 * sizeof(double));
+    HIPCHK(c, hipMemcpyAsync(d_prm + ext_at, prm, 12 * sizeof(double), hipMemcpyHostToDevice, s));
+  } else {
+    if (mu > 0) std::memcpy(prm, imu_poses, (size_t)22 * mu * sizeof(double));
+    if (end_pose) std::memcpy(prm + (size_t)22 * mu, end_pose, 12 * sizeof(double)); else std::memset(prm + (size_t)22 * mu, 0, 12 * sizeof(double));
+    std::memcpy(prm + (size_t)22 * mu + 12, ext_pose, 12 * sizeof(double));
+    HIPCHK(c, hipMemcpyAsync(d_prm, prm, ((size_t)22 * mu + 24) * sizeof(double), hipMemcpyHostToDevice, s));
+  }
   HIPCHK(c, hipMemcpyAsync(f->d_pnt1, f->d_pnt0, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
   const int nb = (n + 255) / 256;
-  if (mu > 0) hipLaunchKernelGGL(k_undistort, dim3(nb), dim3(256), 0, s, n, f->d_pnt1, f->d_curv, mu, f->d_prm);
+  if (mu > 0) hipLaunchKernelGGL(k_undistort, dim3(nb), dim3(256), 0, s, n, f->d_pnt1, f->d_curv, mu, (const double *)d_prm);
   int nd = n;
   const bool det = c->opt.deterministic != 0;
   DsWork w{};
@@ -300,12 +311,25 @@ int vba_scan_prepare(vba_ctx *c, vba_scan_frame *f, int m, const double *imu_pos
   if ((st = down_sample(down_size))) return st;
   if (min_points > 0 && nd < min_points && (st = down_sample(down_size / 2))) return st;   // VS:1880-1884: from the undistorted cloud, kept whatever its count
   if (nd < 1 || nd > n) { c->set_error("scan prepare: voxel count out of range"); return VBA_ERR_HIP; }
-  hipLaunchKernelGGL(k_var_init, dim3((nd + 255) / 256), dim3(256), 0, s, nd, f->d_dsp, f->d_pb, f->d_vb, f->d_prm + (size_t)22 * mu + 12, (float)dept_err,
-                     (float)beam_err);
+  hipLaunchKernelGGL(k_var_init, dim3((nd + 255) / 256), dim3(256), 0, s, nd, f->d_dsp, f->d_pb, f->d_vb, (const double *)d_prm + ext_at,
+                     (float)dept_err, (float)beam_err);
   HIPCHK(c, hipGetLastError());
   f->n_ds = nd; f->prepared = true;
   *n_out = nd;
   return VBA_OK;
+}
+
+int vba_scan_prepare(vba_ctx *c, vba_scan_frame *f, int m, const double *imu_poses, const double *end_pose, const double *ext_pose, int point_notime,
+                     double down_size, int min_points, double dept_err, double beam_err, int *n_out, const double **d_pnt_body, const double **d_var_body) {
+  return scan_prepare_core(c, f, m, imu_poses, end_pose, ext_pose, point_notime, down_size, min_points, dept_err, beam_err, n_out, d_pnt_body, d_var_body,
+                           nullptr);
+}
+
+int vba_scan_prepare_on_state(vba_ctx *c, vba_scan_frame *f, vba_odom_state *os, const double *ext_pose, int point_notime, double down_size,
+                              int min_points, double dept_err, double beam_err, int *n_out, const double **d_pnt_body, const double **d_var_body) {
+  if (!c || !os || c->device != os->ctx->device || os->n_poses < 1) return VBA_ERR_BAD_ARG;
+  return scan_prepare_core(c, f, os->n_poses, nullptr, nullptr, ext_pose, point_notime, down_size, min_points, dept_err, beam_err, n_out, d_pnt_body,
+                           d_var_body, os);
 }
 
 int vba_scan_frame_read(vba_scan_frame *f, int stage, double *pnt, float *intensity, double *curvature, int *count, int *first, double *var) {
