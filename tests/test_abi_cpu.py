@@ -1,5 +1,6 @@
 """CPU-side checks of the drop-in boundary: libvoxelba.so builds/loads, exports every symbol declared in
-include/voxelba.h, fails loudly without a GPU, and the host-side (non-device) entry points agree with the oracle."""
+include/voxelba.h, binds each with the header's prototype (voxel-slam_amd/abi.py, held to the header here), fails loudly without a
+GPU, and the host-side (non-device) entry points agree with the oracle."""
 import ctypes as C
 import os
 import re
@@ -19,14 +20,192 @@ def capi():
     return m
 
 
-def test_exports_match_header(capi):
+SCALAR_KINDS = {"int": "i", "int64_t": "q", "double": "d", "float": "f", "size_t": "z"}
+PROTOTYPE = re.compile(r"(?<![\w*])((?:const\s+)?[A-Za-z_]\w*[\s*]+)(vba_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
+
+
+def parse_prototypes(text):
+    """C declarations -> [(return type, name, [parameter types])], the types normalised ("const double *", "int64_t"), parameter
+    names dropped.  Comments and preprocessor lines are stripped first; a typedef of a function pointer is no prototype."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+
+    def norm(t, named):
+        toks = t.replace("*", " * ").split()
+        if named and toks[-1] != "*" and len(toks) > 1:      # the last word is the parameter's name
+            toks = toks[:-1]
+        return " ".join(toks)
+
+    out = []
+    for ret, name, params in PROTOTYPE.findall(text):
+        params = params.strip()
+        out.append((norm(ret, False), name, [] if params in ("", "void") else [norm(p, True) for p in params.split(",")]))
+    return out
+
+
+def kind_of(ctype, ret=False):
+    """the rule of voxel-slam_amd/abi.py: a C type -> its letter; anything outside the closed set is an error"""
+    if ctype == "const char *":
+        return "s"
+    if "*" in ctype or ctype == "vba_allreduce_fn":
+        return "p"
+    if ret and ctype == "void":
+        return "v"
+    return SCALAR_KINDS[ctype]
+
+
+def header_prototypes():
     hdr = open(os.path.join(ROOT, "include", "voxelba.h")).read()
+    return hdr, {name: kind_of(ret, True) + ":" + "".join(kind_of(p) for p in params) for ret, name, params in parse_prototypes(hdr)}
+
+
+def test_parser_has_teeth():
+    got = parse_prototypes("""
+        #define VBA_OK 0
+        typedef int (*vba_allreduce_fn)(void *user, void *dev, size_t n, void *stream);   /* no prototype */
+        /* vba_in_a_comment(int x); */
+        int vba_two_lines(vba_ctx *ctx, int n, const double *pnt,
+                          int64_t first, double *out);
+        int vba_inline(vba_ctx *ctx, vba_odom_report *report /* may be NULL */, float w);
+        int vba_sessions(int n_db, vba_btc_db *const *dbs, const double **rows, vba_allreduce_fn fn);
+        const char *vba_text(int status);     // a string back
+        void vba_read(vba_ctx *ctx, const char *name, size_t n_bytes, long long *slots);
+        int vba_none(void);
+    """)
+    assert got == [
+        ("int", "vba_two_lines", ["vba_ctx *", "int", "const double *", "int64_t", "double *"]),
+        ("int", "vba_inline", ["vba_ctx *", "vba_odom_report *", "float"]),
+        ("int", "vba_sessions", ["int", "vba_btc_db * const *", "const double * *", "vba_allreduce_fn"]),
+        ("const char *", "vba_text", ["int"]),
+        ("void", "vba_read", ["vba_ctx *", "const char *", "size_t", "long long *"]),
+        ("int", "vba_none", []),
+    ]
+    kinds = [kind_of(r, True) + ":" + "".join(kind_of(p) for p in ps) for r, _, ps in got]
+    assert kinds == ["i:pipqp", "i:ppf", "i:ippp", "s:i", "v:pszp", "i:"]
+    for outside in ("long long", "unsigned int", "void", "vba_options"):      # by value: not in the closed set
+        with pytest.raises(KeyError):
+            kind_of(outside)
+
+
+def test_exports_match_header(capi):
+    """abi.PROTOTYPES is the header: every function, its return kind and every parameter kind, in the header's order"""
+    from voxel_slam_amd import abi
+    hdr, parsed = header_prototypes()
     declared = set(re.findall(r"\b(vba_[a-z0-9_]+)\s*\(", hdr))
     declared -= {"vba_allreduce_fn"}
+    assert set(parsed) == declared and len(parsed) >= 176, set(parsed) ^ declared       # the parser skipped nothing
     lib = capi.load()
     missing = [s for s in sorted(declared) if not hasattr(lib, s)]
     assert not missing, missing
     assert declared == set(capi.EXPORTS), declared ^ set(capi.EXPORTS)
+    wrong = {s: (abi.PROTOTYPES.get(s), parsed[s]) for s in parsed if abi.PROTOTYPES.get(s) != parsed[s]}
+    assert not wrong, wrong
+    assert list(abi.PROTOTYPES) == list(parsed) == capi.EXPORTS                         # and in the same order
+    assert set("".join(abi.PROTOTYPES.values())) - {":"} <= set(abi.KINDS)
+
+
+def test_every_function_of_the_library_is_typed(capi):
+    from voxel_slam_amd import abi
+    _, parsed = header_prototypes()
+    lib = capi.load()
+    for name, proto in parsed.items():
+        fn = getattr(lib, name)
+        ret, params = proto.split(":")
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), name
+        assert list(fn.argtypes) == [abi.KINDS[k] for k in params] and fn.restype is abi.KINDS[ret], name
+    typed = [k for k, v in vars(lib).items() if k.startswith("vba_")]      # what attribute access has bound so far
+    assert set(typed) == set(parsed)
+
+
+def test_int64_argument_arrives_whole(capi):
+    """vba_kf_export_plan takes ``int64_t interval_size`` by value: cut to its low 32 bits, 2^33 + 2 is 2, every keyframe closes a
+    message and n_msgs is 4 (what an untyped call with a bare integer gave)"""
+    lib = capi.load()
+    interval = 2 ** 33 + 2
+    sizes = np.array([10, 10, 10], dtype=np.int32)
+    ip = C.POINTER(C.c_int)
+
+    def raw(iv):
+        j = C.c_int(-77); nm = C.c_int(-77)
+        kb = np.full(4, -77, dtype=np.int64); me = np.full(4, -77, dtype=np.int32)
+        st = lib.vba_kf_export_plan(3, sizes.ctypes.data_as(ip), iv, 1, C.byref(j), kb.ctypes.data_as(C.POINTER(C.c_int64)), 4,
+                                    me.ctypes.data_as(ip), C.byref(nm))
+        return st, j.value, kb.tolist(), me.tolist(), nm.value
+
+    bare = raw(interval)
+    assert bare[0] == 0 and bare[4] == 1 and bare[3][0] == 3, bare
+    assert bare == raw(C.c_int64(interval))
+    j, kb, me = capi.kf_export_plan(sizes, interval_size=interval, jump=1)
+    assert (j, kb.tolist(), me.tolist()) == (bare[1], bare[2], bare[3][:1])
+
+
+def test_double_argument_arrives_as_a_double(capi):
+    """vba_imu_ekf_propagate with its four by-value doubles as bare Python floats: the bits of the C.c_double call"""
+    import imu_ekf_ref
+    c = imu_ekf_ref.corpus()["m21"]
+    lib = capi.load()
+    dp = C.POINTER(C.c_double)
+    imu = np.ascontiguousarray(c["imu"], dtype=np.float64); noise = np.ascontiguousarray(c["noise"], dtype=np.float64)
+    scalars = [float(c[k]) for k in ("sg", "last_end", "beg", "end")]
+    assert all(type(x) is float for x in scalars) and any(x != int(x) for x in scalars)
+
+    def run(wrap):
+        st = np.array(c["state"], dtype=np.float64); cov = np.array(c["cov"], dtype=np.float64)
+        poses = np.zeros((len(imu), 22)); end = np.zeros(12); n = C.c_int(-7)
+        r = lib.vba_imu_ekf_propagate(len(imu), imu.ctypes.data_as(dp), noise.ctypes.data_as(dp), *[wrap(x) for x in scalars],
+                                      st.ctypes.data_as(dp), cov.ctypes.data_as(dp), poses.ctypes.data_as(dp), end.ctypes.data_as(dp), C.byref(n))
+        assert r == capi.OK and n.value > 0
+        return st, cov, poses, end, n.value
+
+    a, b = run(lambda x: x), run(C.c_double)
+    assert a[4] == b[4]
+    for x, y in zip(a[:4], b[:4]):
+        assert x.tobytes() == y.tobytes()
+    assert not np.array_equal(a[0], c["state"])          # the call did something
+
+
+def test_wrong_kinds_are_refused(capi):
+    lib = capi.load()
+    with pytest.raises(C.ArgumentError):
+        lib.vba_scanlog_release(None, C.c_int(0))        # the header says int64_t
+    with pytest.raises(C.ArgumentError):
+        lib.vba_scanlog_release(None, 0.5)
+    assert lib.vba_scanlog_release(None, C.c_int64(0)) == capi.ERR_BAD_ARG
+
+
+WRAPPED_BY_VALUE = re.compile(r"[(,]\s*C\.c_(int|int64|double|float|longlong|size_t)\(")
+SETS_A_PROTOTYPE = re.compile(r"\.argtypes\s*=|\.restype\s*=")
+
+
+def test_text_patterns_have_teeth():
+    assert WRAPPED_BY_VALUE.search("lib.vba_map_slide(self.h, C.c_int(mgsize))") and WRAPPED_BY_VALUE.search("f(C.c_int64(n),\n  C.c_double(x))")
+    assert WRAPPED_BY_VALUE.search("head = (ctx.h,\n        C.c_size_t(n))")
+    for ok in ("n = C.c_int(); b = C.c_int64(-1)", "lib.f(self.h, C.c_void_p(d), C.byref(n))", '("win_size", C.c_int), ("x", C.c_double * 4)',
+               "a.ctypes.data_as(C.POINTER(C.c_int))"):
+        assert not WRAPPED_BY_VALUE.search(ok), ok
+    assert SETS_A_PROTOTYPE.search("lib.vba_x.restype = C.c_char_p") and SETS_A_PROTOTYPE.search("fn.argtypes= [C.c_int]")
+    assert not SETS_A_PROTOTYPE.search("assert fn.argtypes is not None and len(fn.argtypes) == 3 and fn.restype is None")
+
+
+def test_binding_text(capi):
+    pkg = os.path.dirname(capi.__file__)
+    src = open(os.path.join(pkg, "capi.py")).read()
+    assert not WRAPPED_BY_VALUE.findall(src)
+    # prototypes are set in one place: the loop of capi.load() over the table
+    for f in sorted(os.listdir(pkg)):
+        if f.endswith(".py"):
+            text = open(os.path.join(pkg, f)).read()
+            hits = [m.start() for m in SETS_A_PROTOTYPE.finditer(text)]
+            if f != "capi.py":
+                assert not hits, f
+                continue
+            a = text.index("\ndef load():"); b = text.index("\ndef ", a + 1)
+            assert len(hits) == 2 and all(a < h < b for h in hits), hits
+    # one lifecycle: no create / destroy name is spelled out more than once
+    for prefix in ("vba_btc", "vba_kf", "vba_loop_map", "vba_scanlog", "vba_scan_frame", "vba_init_window", "vba_odom_state"):
+        for op in ("_create", "_destroy"):
+            assert len(re.findall(r"\b%s%s\b" % (prefix, op), src)) <= 1, prefix + op
 
 
 def test_no_device_is_a_loud_error(capi):

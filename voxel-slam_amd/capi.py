@@ -13,6 +13,8 @@ import subprocess
 
 import numpy as np
 
+from .abi import KINDS, PROTOTYPES
+
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VBA_LIB") or os.path.join(_PKG, "libvoxelba.so")   # VBA_LIB: an alternative build (tools/ A/B runs)
 _dp = C.POINTER(C.c_double)
@@ -20,42 +22,7 @@ _dp = C.POINTER(C.c_double)
 OK = 0
 ERR_NO_DEVICE, ERR_BAD_ARG, ERR_UNSUPPORTED_WINDOW, ERR_TOO_FEW_VOXELS, ERR_OPT_STATE, ERR_HIP, ERR_CAPACITY, ERR_IO, ERR_UNSUPPORTED, ERR_SINGULAR = range(1, 11)
 
-EXPORTS = [
-    "vba_default_options", "vba_create", "vba_destroy", "vba_status_string", "vba_last_error", "vba_synchronize",
-    "vba_factor_clear", "vba_factor_push_voxels", "vba_factor_size", "vba_factor_acc_evaluate2",
-    "vba_factor_evaluate_only_residual", "vba_factor_read_back", "vba_factor_occupied_slots", "vba_factor_occupancy_masks",
-    "vba_lidar_ba_damping_iter", "vba_li_ba_damping_iter", "vba_last_lm_trace",
-    "vba_imu_preintegrate", "vba_imu_give_evaluate",
-    "vba_map_cut_voxel", "vba_map_pvec_update_cut_voxel", "vba_scan_var_init", "vba_scan_down_sampling_voxel", "vba_scan_down_sampling_pvec", "vba_scan_down_sampling_close", "vba_scan_undistort", "vba_odom_lio_state_estimation_kdtree", "vba_odom_kdtree_reset", "vba_odom_kdtree_size", "vba_odom_kdtree_points", "vba_odom_lio_state_estimation_kdtree_resident", "vba_odom_kdtree_reserve", "vba_odom_kdtree_allocations", "vba_gba_build", "vba_hba_add_edge", "vba_hba_global", "vba_map_cut_voxel_fix", "vba_map_recut", "vba_map_margi", "vba_map_slide", "vba_map_prune", "vba_map_reset",
-    "vba_map_num_roots", "vba_map_num_slide_roots", "vba_map_stats", "vba_map_dump_leaves", "vba_map_dump_plane_var", "vba_odom_lio_state_estimation", "vba_odom_lio_state_estimation_resident",
-    "vba_set_allreduce", "vba_rccl_get_unique_id", "vba_rccl_init", "vba_set_rccl_comm", "vba_shard_owner", "vba_set_shard",
-    "vba_timing_enable", "vba_timing_calibration_read", "vba_timing_select", "vba_timing_sample_every", "vba_timing_launch_hessian", "vba_timing_null_span", "vba_timing_reset", "vba_timing_get",
-    "vba_lm_begin", "vba_lm_refresh_eigen", "vba_lm_iterate", "vba_lm_end", "vba_debug_solve", "vba_debug_li_imu", "vba_debug_odom_sums", "vba_debug_plane_update",
-    "vba_debug_big_load", "vba_debug_big_build", "vba_debug_big_size", "vba_debug_big_read", "vba_debug_big_hessian", "vba_debug_big_residual",
-    "vba_io_save_pcd", "vba_io_load_pcd", "vba_io_save_pose", "vba_io_read_lidarstate",
-    "vba_motion_init", "vba_init_imu_poses", "vba_init_align_gravity",
-    "vba_btc_default_config", "vba_btc_create", "vba_btc_destroy", "vba_btc_set_skip_near_num", "vba_btc_push_plane_cloud",
-    "vba_btc_num_frames", "vba_btc_frame_seq", "vba_btc_add_stds", "vba_btc_search_loop", "vba_btc_search_loop_sessions",
-    "vba_btc_icp_normal", "vba_btc_last_candidates", "vba_btc_reserve",
-    "vba_btc_default_gen_config", "vba_btc_set_gen_config", "vba_btc_generate_stds", "vba_btc_plane_cloud", "vba_btc_last_corners",
-    "vba_btc_gen_reserve", "vba_btc_gen_allocations", "vba_btc_get_gen_config",
-    "vba_pgo_optimize",
-    "vba_kf_create", "vba_kf_destroy", "vba_kf_reserve", "vba_kf_allocations", "vba_kf_size", "vba_kf_build", "vba_kf_last_counts",
-    "vba_kf_generate_stds", "vba_kf_set_poses", "vba_kf_get", "vba_kf_set_history", "vba_kf_history_size", "vba_kf_load",
-    "vba_kf_load_nearby", "vba_kf_read", "vba_kf_clouds", "vba_kf_export_plan", "vba_kf_export_world",
-    "vba_loop_map_create", "vba_loop_map_destroy", "vba_loop_map_reserve", "vba_loop_map_allocations", "vba_loop_map_build",
-    "vba_loop_map_num_roots", "vba_loop_map_dump_leaves", "vba_loop_map_dump_plane_var", "vba_loop_update",
-    "vba_scanlog_create", "vba_scanlog_destroy", "vba_scanlog_reserve", "vba_scanlog_allocations", "vba_scanlog_push_window",
-    "vba_scanlog_push_points", "vba_scanlog_range", "vba_scanlog_release", "vba_scanlog_read", "vba_scanlog_export_world",
-    "vba_kf_build_from_log", "vba_scanlog_loop_update",
-    "vba_scan_layout_livox", "vba_scan_layout_check", "vba_scan_frame_create", "vba_scan_frame_destroy", "vba_scan_frame_reserve",
-    "vba_scan_frame_allocations", "vba_scan_decode", "vba_scan_prepare", "vba_scan_frame_read",
-    "vba_init_window_create", "vba_init_window_destroy", "vba_init_window_reserve", "vba_init_window_allocations", "vba_init_window_clear",
-    "vba_init_window_size", "vba_init_window_push", "vba_init_window_push_points", "vba_init_window_read", "vba_motion_init_resident",
-    "vba_imu_ekf_propagate", "vba_odom_state_create", "vba_odom_state_destroy", "vba_odom_state_reserve", "vba_odom_state_allocations",
-    "vba_odom_state_set", "vba_odom_state_get", "vba_odom_state_poses", "vba_odom_state_propagate", "vba_scan_prepare_on_state",
-    "vba_odom_lio_state_estimation_on_state", "vba_map_pvec_update_cut_voxel_on_state",
-]
+EXPORTS = list(PROTOTYPES)     # every function of include/voxelba.h, in the header's order
 
 
 class Options(C.Structure):
@@ -106,7 +73,7 @@ class BtcGenConfig(C.Structure):
 def btc_default_gen_config(is_high_fly=0) -> BtcGenConfig:
     """read_parameters (BTC.cpp:3-68), generation fields."""
     f = BtcGenConfig()
-    st = load().vba_btc_default_gen_config(C.c_int(int(is_high_fly)), C.byref(f))
+    st = load().vba_btc_default_gen_config(int(is_high_fly), C.byref(f))
     if st:
         raise VbaError(st)
     return f
@@ -121,7 +88,7 @@ def btc_max_stds(gcfg) -> int:
 def btc_default_config(is_high_fly=0) -> BtcConfig:
     """read_parameters (BTC.cpp:3-68), retrieval fields only."""
     f = BtcConfig()
-    st = load().vba_btc_default_config(C.c_int(int(is_high_fly)), C.byref(f))
+    st = load().vba_btc_default_config(int(is_high_fly), C.byref(f))
     if st:
         raise VbaError(st)
     return f
@@ -160,26 +127,26 @@ class BtcDb:
 
     def reserve(self, stds=0, frames=0, cloud_points=0, matches=0):
         """capacity hint: a database sized for these never re-allocates (results do not depend on it)"""
-        self.ctx._chk(self.lib.vba_btc_reserve(self.h, C.c_int(stds), C.c_int(frames), C.c_int64(cloud_points), C.c_int(matches)))
+        self.ctx._chk(self.lib.vba_btc_reserve(self.h, stds, frames, cloud_points, matches))
 
     def set_skip_near_num(self, v):
-        self.ctx._chk(self.lib.vba_btc_set_skip_near_num(self.h, C.c_int(int(v))))
+        self.ctx._chk(self.lib.vba_btc_set_skip_near_num(self.h, int(v)))
 
     def push_plane_cloud(self, xyz_normal, seq):
         a = np.ascontiguousarray(np.reshape(xyz_normal, (-1, 6)), dtype=np.float32)
-        self.ctx._chk(self.lib.vba_btc_push_plane_cloud(self.h, C.c_int(len(a)), a.ctypes.data_as(C.POINTER(C.c_float)), C.c_int(int(seq))))
+        self.ctx._chk(self.lib.vba_btc_push_plane_cloud(self.h, len(a), a.ctypes.data_as(C.POINTER(C.c_float)), int(seq)))
 
     def num_frames(self):
         return self.lib.vba_btc_num_frames(self.h)
 
     def frame_seq(self, frame):
         s = C.c_int()
-        self.ctx._chk(self.lib.vba_btc_frame_seq(self.h, C.c_int(frame), C.byref(s)))
+        self.ctx._chk(self.lib.vba_btc_frame_seq(self.h, frame, C.byref(s)))
         return s.value
 
     def add_stds(self, rows, bits):
         rows, bits, bp = _btc_query(rows, bits)
-        self.ctx._chk(self.lib.vba_btc_add_stds(self.h, C.c_int(len(rows)), _p(rows), bp))
+        self.ctx._chk(self.lib.vba_btc_add_stds(self.h, len(rows), _p(rows), bp))
 
     def search_loop(self, rows, bits, cur_db, cur_frame=-1):
         """SearchLoop against this database; pl_cur = plane cloud cur_frame of cur_db (-1: its last)."""
@@ -187,14 +154,14 @@ class BtcDb:
         if cur_frame < 0:
             cur_frame = cur_db.num_frames() + cur_frame
         r = BtcResult()
-        self.ctx._chk(self.lib.vba_btc_search_loop(self.h, C.c_int(len(rows)), _p(rows), bp, cur_db.h, C.c_int(cur_frame), C.byref(r)))
+        self.ctx._chk(self.lib.vba_btc_search_loop(self.h, len(rows), _p(rows), bp, cur_db.h, cur_frame, C.byref(r)))
         return _btc_result(r)
 
     def last_candidates(self):
         """list of dicts (frame, votes, match_len, max_vote_index, max_vote, score) of the last search"""
         n = C.c_int()
         out = (BtcCandidate * 256)()
-        self.ctx._chk(self.lib.vba_btc_last_candidates(self.h, C.c_int(256), out, C.byref(n)))
+        self.ctx._chk(self.lib.vba_btc_last_candidates(self.h, 256, out, C.byref(n)))
         return [dict(frame=o.frame, votes=o.votes, match_len=o.match_len, max_vote_index=o.max_vote_index, max_vote=o.max_vote,
                      score=o.score) for o in out[:n.value]]
 
@@ -204,7 +171,7 @@ class BtcDb:
 
     def gen_reserve(self, points=0, cells=0, frames=1):
         """capacity hint for generate_stds: clouds of `points` points, projection images of `cells` cells, `frames` more calls"""
-        self.ctx._chk(self.lib.vba_btc_gen_reserve(self.h, C.c_int64(points), C.c_int64(cells), C.c_int(frames)))
+        self.ctx._chk(self.lib.vba_btc_gen_reserve(self.h, points, cells, frames))
 
     def gen_allocations(self):
         n = C.c_int(); b = C.c_int64()
@@ -218,23 +185,23 @@ class BtcDb:
             cap = btc_max_stds(getattr(self, "gcfg", None) or btc_default_gen_config(0))
         rows = np.zeros((max(cap, 1), BTC_ROW_LEN)); bits = np.zeros((max(cap, 1), 3), dtype=np.uint64)
         n = C.c_int()
-        self.ctx._chk(self.lib.vba_btc_generate_stds(self.h, C.c_int(len(a)), a.ctypes.data_as(C.POINTER(C.c_float)), C.c_int(int(id)),
-                                                     C.c_int(cap), _p(rows), bits.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)))
+        self.ctx._chk(self.lib.vba_btc_generate_stds(self.h, len(a), a.ctypes.data_as(C.POINTER(C.c_float)), int(id),
+                                                     cap, _p(rows), bits.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)))
         return rows[:n.value].copy(), bits[:n.value].copy()
 
     def plane_cloud(self, frame):
         n = C.c_int()
-        self.ctx._chk(self.lib.vba_btc_plane_cloud(self.h, C.c_int(frame), C.c_int(0), None, C.byref(n)))
+        self.ctx._chk(self.lib.vba_btc_plane_cloud(self.h, frame, 0, None, C.byref(n)))
         out = np.zeros((max(n.value, 1), 6), dtype=np.float32)
-        self.ctx._chk(self.lib.vba_btc_plane_cloud(self.h, C.c_int(frame), C.c_int(n.value), out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n)))
+        self.ctx._chk(self.lib.vba_btc_plane_cloud(self.h, frame, n.value, out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n)))
         return out[:n.value].copy()
 
     def last_corners(self):
         """binary_list of the last generate_stds: (locations [n][3], summaries [n], masks [n])"""
         n = C.c_int()
-        self.ctx._chk(self.lib.vba_btc_last_corners(self.h, C.c_int(0), None, None, C.byref(n)))
+        self.ctx._chk(self.lib.vba_btc_last_corners(self.h, 0, None, None, C.byref(n)))
         ls = np.zeros((max(n.value, 1), 4)); b = np.zeros(max(n.value, 1), dtype=np.uint64)
-        self.ctx._chk(self.lib.vba_btc_last_corners(self.h, C.c_int(n.value), _p(ls), b.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)))
+        self.ctx._chk(self.lib.vba_btc_last_corners(self.h, n.value, _p(ls), b.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)))
         k = n.value
         return ls[:k, :3].copy(), ls[:k, 3].astype(np.int64), b[:k].copy()
 
@@ -242,37 +209,54 @@ class BtcDb:
         """icp_normal(plane cloud src_frame of this db, plane cloud tar_frame of tar_db, (t, R), icp_eigval)"""
         tt = _c(t).copy(); RR = _c(R).reshape(3, 3).copy()
         ok = C.c_int(); it = C.c_int(); eig = np.zeros(3)
-        self.ctx._chk(self.lib.vba_btc_icp_normal(self.h, C.c_int(src_frame), tar_db.h, C.c_int(tar_frame), _p(tt), _p(RR),
-                                                  C.c_double(icp_eigval), C.byref(ok), _p(eig), C.byref(it)))
+        self.ctx._chk(self.lib.vba_btc_icp_normal(self.h, src_frame, tar_db.h, tar_frame, _p(tt), _p(RR),
+                                                  icp_eigval, C.byref(ok), _p(eig), C.byref(it)))
         return dict(ok=ok.value, t=tt, R=RR, eig=eig, iters=it.value)
 
 
-class KeyframeStore:
-    """One vba_kf_store: the session's keyframes (``vector<Keyframe*> *keyframes``) resident in HBM (DESIGN.md section 13)."""
+class _Handle:
+    """What the device-resident objects of a context share: PREFIX_create on the context, a place in the context's ``_kf`` list
+    (Context.close() destroys those first, then the databases, then itself), PREFIX_destroy and PREFIX_allocations.  (BtcDb is not
+    one of them: its create call takes a config and it has gen_allocations, not allocations.)"""
+    PREFIX = None
 
     def __init__(self, ctx):
         self.ctx = ctx
         self.lib = ctx.lib
         h = C.c_void_p()
-        ctx._chk(self.lib.vba_kf_create(ctx.h, C.byref(h)))
+        ctx._chk(getattr(self.lib, self.PREFIX + "_create")(ctx.h, C.byref(h)))
         self.h = h
         ctx._kf.append(self)
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.vba_kf_destroy(self.h)
+            getattr(self.lib, self.PREFIX + "_destroy")(self.h)
             self.h = None
         kf = getattr(self.ctx, "_kf", None)
         if kf is not None and self in kf:
             kf.remove(self)
 
-    def reserve(self, points=0, keyframes=0, merge_points=0):
-        self.ctx._chk(self.lib.vba_kf_reserve(self.h, C.c_int64(points), C.c_int(keyframes), C.c_int64(merge_points)))
-
     def allocations(self):
         n = C.c_int(); b = C.c_int64()
-        self.ctx._chk(self.lib.vba_kf_allocations(self.h, C.byref(n), C.byref(b)))
+        self.ctx._chk(getattr(self.lib, self.PREFIX + "_allocations")(self.h, C.byref(n), C.byref(b)))
         return n.value, b.value
+
+
+def _dump_rows(fn, h, width):
+    """The "ask for the size, then fill" leaf dumps: fn(h, NULL, 0) returns the leaf count, fn(h, out, n) fills out [n][width]."""
+    n = fn(h, None, 0)
+    out = np.zeros((max(n, 0), width))
+    if n > 0:
+        fn(h, _p(out), n)
+    return out
+
+
+class KeyframeStore(_Handle):
+    """One vba_kf_store: the session's keyframes (``vector<Keyframe*> *keyframes``) resident in HBM (DESIGN.md section 13)."""
+    PREFIX = "vba_kf"
+
+    def reserve(self, points=0, keyframes=0, merge_points=0):
+        self.ctx._chk(self.lib.vba_kf_reserve(self.h, points, keyframes, merge_points))
 
     def size(self):
         return self.lib.vba_kf_size(self.h)
@@ -296,9 +280,9 @@ class KeyframeStore:
             if cap is None:
                 cap = btc_max_stds(getattr(db, "gcfg", None) or btc_default_gen_config(0))
             rows = np.zeros((max(cap, 1), BTC_ROW_LEN)); bits = np.zeros((max(cap, 1), 3), dtype=np.uint64)
-        self.ctx._chk(self.lib.vba_kf_build(self.h, C.c_int(k), off.ctypes.data_as(C.POINTER(C.c_int)), _p(pnt), _p(var), _p(poses),
-                                            C.c_double(voxel_size), C.c_int(int(id)), C.c_double(jour), db.h if db is not None else None,
-                                            C.c_int(cap if db is not None else 0), _p(rows),
+        self.ctx._chk(self.lib.vba_kf_build(self.h, k, off.ctypes.data_as(C.POINTER(C.c_int)), _p(pnt), _p(var), _p(poses),
+                                            voxel_size, int(id), jour, db.h if db is not None else None,
+                                            cap if db is not None else 0, _p(rows),
                                             bits.ctypes.data_as(C.POINTER(C.c_uint64)) if bits is not None else None, C.byref(ns), C.byref(npt)))
         if db is None:
             return npt.value, None, None
@@ -312,9 +296,9 @@ class KeyframeStore:
             if cap is None:
                 cap = btc_max_stds(getattr(db, "gcfg", None) or btc_default_gen_config(0))
             rows = np.zeros((max(cap, 1), BTC_ROW_LEN)); bits = np.zeros((max(cap, 1), 3), dtype=np.uint64)
-        self.ctx._chk(self.lib.vba_kf_build_from_log(self.h, log.h, C.c_int64(first), C.c_int(len(poses)), _p(poses), C.c_double(voxel_size),
-                                                     C.c_int(int(id)), C.c_double(jour), db.h if db is not None else None,
-                                                     C.c_int(cap if db is not None else 0), _p(rows),
+        self.ctx._chk(self.lib.vba_kf_build_from_log(self.h, log.h, first, len(poses), _p(poses), voxel_size,
+                                                     int(id), jour, db.h if db is not None else None,
+                                                     cap if db is not None else 0, _p(rows),
                                                      bits.ctypes.data_as(C.POINTER(C.c_uint64)) if bits is not None else None, C.byref(ns), C.byref(npt)))
         if db is None:
             return npt.value, None, None
@@ -322,9 +306,9 @@ class KeyframeStore:
 
     def last_counts(self):
         n = C.c_int()
-        self.ctx._chk(self.lib.vba_kf_last_counts(self.h, C.c_int(0), None, C.byref(n)))
+        self.ctx._chk(self.lib.vba_kf_last_counts(self.h, 0, None, C.byref(n)))
         out = np.zeros(max(n.value, 1), dtype=np.int32)
-        self.ctx._chk(self.lib.vba_kf_last_counts(self.h, C.c_int(n.value), out.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n)))
+        self.ctx._chk(self.lib.vba_kf_last_counts(self.h, n.value, out.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n)))
         return out[:n.value].copy()
 
     def generate_stds(self, first, count, db, cap=None):
@@ -332,40 +316,40 @@ class KeyframeStore:
         if cap is None:
             cap = btc_max_stds(getattr(db, "gcfg", None) or btc_default_gen_config(0))
         rows = np.zeros((max(cap, 1), BTC_ROW_LEN)); bits = np.zeros((max(cap, 1), 3), dtype=np.uint64); n = C.c_int()
-        self.ctx._chk(self.lib.vba_kf_generate_stds(self.h, C.c_int(first), C.c_int(count), db.h, C.c_int(cap), _p(rows),
+        self.ctx._chk(self.lib.vba_kf_generate_stds(self.h, first, count, db.h, cap, _p(rows),
                                                     bits.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n)))
         return rows[:n.value].copy(), bits[:n.value].copy()
 
     def set_poses(self, first, poses):
         poses = _c(poses).reshape(-1, 12)
-        self.ctx._chk(self.lib.vba_kf_set_poses(self.h, C.c_int(first), C.c_int(len(poses)), _p(poses)))
+        self.ctx._chk(self.lib.vba_kf_set_poses(self.h, first, len(poses), _p(poses)))
 
     def get(self, k):
         pose = np.zeros(12); i = C.c_int(); j = C.c_double(); e = C.c_int(); n = C.c_int()
-        self.ctx._chk(self.lib.vba_kf_get(self.h, C.c_int(k), _p(pose), C.byref(i), C.byref(j), C.byref(e), C.byref(n)))
+        self.ctx._chk(self.lib.vba_kf_get(self.h, k, _p(pose), C.byref(i), C.byref(j), C.byref(e), C.byref(n)))
         return dict(x0=pose, id=i.value, jour=j.value, exist=e.value, n_points=n.value)
 
     def set_history(self, n_hist):
-        self.ctx._chk(self.lib.vba_kf_set_history(self.h, C.c_int(n_hist)))
+        self.ctx._chk(self.lib.vba_kf_set_history(self.h, n_hist))
 
     def history_size(self):
         return self.lib.vba_kf_history_size(self.h)
 
     def load(self, k, map_ctx, jour=0.0):
-        self.ctx._chk(self.lib.vba_kf_load(self.h, C.c_int(k), map_ctx.h, C.c_double(jour)))
+        self.ctx._chk(self.lib.vba_kf_load(self.h, k, map_ctx.h, jour))
 
     def load_nearby(self, map_ctx, p3, radius=10.0, jour=0.0):
         """keyframe_loading(jour) around p3 -> index of the loaded keyframe, -1 = none"""
         k = C.c_int(-1)
-        self.ctx._chk(self.lib.vba_kf_load_nearby(self.h, map_ctx.h, _p(_c(p3)), C.c_double(radius), C.c_double(jour), C.byref(k)))
+        self.ctx._chk(self.lib.vba_kf_load_nearby(self.h, map_ctx.h, _p(_c(p3)), radius, jour, C.byref(k)))
         return k.value
 
     def read(self, k):
         """keyframe k -> (xyz [n][3] float values in doubles, covariance diagonals float32 [n][3])"""
         n = C.c_int()
-        self.ctx._chk(self.lib.vba_kf_read(self.h, C.c_int(k), C.c_int(0), None, None, C.byref(n)))
+        self.ctx._chk(self.lib.vba_kf_read(self.h, k, 0, None, None, C.byref(n)))
         xyz = np.zeros((max(n.value, 1), 3)); vd = np.zeros((max(n.value, 1), 3), dtype=np.float32)
-        self.ctx._chk(self.lib.vba_kf_read(self.h, C.c_int(k), C.c_int(n.value), _p(xyz), vd.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n)))
+        self.ctx._chk(self.lib.vba_kf_read(self.h, k, n.value, _p(xyz), vd.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n)))
         return xyz[:n.value].copy(), vd[:n.value].copy()
 
     def hba_add_edge(self, ctx, first, count, poses, gba_voxel_size, gba_min_eigen_value, gba_eig, max_iter, thread_num):
@@ -379,9 +363,9 @@ class KeyframeStore:
         edges = np.zeros((count * (count - 1) // 2 + 1, 20)); ne = C.c_int(0)
         cloud = np.zeros((max(npt, 1), 3)); ccnt = np.zeros(max(npt, 1), dtype=np.int32); nc = C.c_int(0)
         rl = np.zeros((max_iter + 1, 2)); nl = C.c_int(0)
-        ctx._chk(self.lib.vba_hba_add_edge(ctx.h, C.c_int(count), rel.ctypes.data_as(C.POINTER(C.c_int)), base, _p(poses),
-                                           C.c_double(gba_voxel_size), C.c_double(gba_min_eigen_value), _p(_c(gba_eig)), C.c_int(max_iter),
-                                           C.c_int(thread_num), _p(edges), C.byref(ne), _p(cloud), ccnt.ctypes.data_as(C.POINTER(C.c_int)),
+        ctx._chk(self.lib.vba_hba_add_edge(ctx.h, count, rel.ctypes.data_as(C.POINTER(C.c_int)), base, _p(poses),
+                                           gba_voxel_size, gba_min_eigen_value, _p(_c(gba_eig)), max_iter,
+                                           thread_num, _p(edges), C.byref(ne), _p(cloud), ccnt.ctypes.data_as(C.POINTER(C.c_int)),
                                            C.byref(nc), _p(rl), C.byref(nl)))
         return dict(poses=poses, edges=edges[:ne.value].copy(), cloud=cloud[:nc.value].copy(), cloud_count=ccnt[:nc.value].copy(),
                     resis=rl[:nl.value].copy())
@@ -398,90 +382,42 @@ class KeyframeStore:
         return np.diff(self.clouds()[1]).astype(np.int32)
 
 
-class LoopMap:
+class LoopMap(_Handle):
     """One vba_loop_map: ``map_loop`` of the loop-closure thread, a second voxel map resident in HBM."""
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.lib = ctx.lib
-        h = C.c_void_p()
-        ctx._chk(self.lib.vba_loop_map_create(ctx.h, C.byref(h)))
-        self.h = h
-        ctx._kf.append(self)         # destroyed with its context, as the stores are
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.vba_loop_map_destroy(self.h)
-            self.h = None
-        kf = getattr(self.ctx, "_kf", None)
-        if kf is not None and self in kf:
-            kf.remove(self)
+    PREFIX = "vba_loop_map"
 
     def reserve(self, fix_points=0, nodes=0):
-        self.ctx._chk(self.lib.vba_loop_map_reserve(self.h, C.c_int64(fix_points), C.c_int64(nodes)))
-
-    def allocations(self):
-        n = C.c_int(); b = C.c_int64()
-        self.ctx._chk(self.lib.vba_loop_map_allocations(self.h, C.byref(n), C.byref(b)))
-        return n.value, b.value
+        self.ctx._chk(self.lib.vba_loop_map_reserve(self.h, fix_points, nodes))
 
     def build(self, store, init_num=5, cumulative=True):
         """VS:2601-2625 from the last ``init_num`` keyframes of ``store`` at their current x0 -> points inserted.
         cumulative=True is the reference (pvec_tem is never cleared), False inserts every keyframe once."""
         n = C.c_int()
-        self.ctx._chk(self.lib.vba_loop_map_build(self.h, store.h, C.c_int(init_num), C.c_int(int(cumulative)), C.byref(n)))
+        self.ctx._chk(self.lib.vba_loop_map_build(self.h, store.h, init_num, int(cumulative), C.byref(n)))
         return n.value
 
     def num_roots(self):
         return self.lib.vba_loop_map_num_roots(self.h)
 
     def dump_leaves(self):
-        n = self.lib.vba_loop_map_dump_leaves(self.h, None, C.c_int(0))
-        out = np.zeros((max(n, 0), 39))
-        if n > 0:
-            self.lib.vba_loop_map_dump_leaves(self.h, _p(out), C.c_int(n))
-        return out
+        return _dump_rows(self.lib.vba_loop_map_dump_leaves, self.h, 39)
 
     def dump_plane_var(self):
-        n = self.lib.vba_loop_map_dump_plane_var(self.h, None, C.c_int(0))
-        out = np.zeros((max(n, 0), 86))
-        if n > 0:
-            self.lib.vba_loop_map_dump_plane_var(self.h, _p(out), C.c_int(n))
-        return out
+        return _dump_rows(self.lib.vba_loop_map_dump_plane_var, self.h, 86)
 
 
-class ScanLog:
+class ScanLog(_Handle):
     """One vba_scanlog: the marginalised scans of a session (the live ``ScanPose::pvec``) resident in HBM, between the map's scan
     ring and the keyframes.  Scans are numbered 0, 1, 2, ... in push order and released first in, first out."""
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.lib = ctx.lib
-        h = C.c_void_p()
-        ctx._chk(self.lib.vba_scanlog_create(ctx.h, C.byref(h)))
-        self.h = h
-        ctx._kf.append(self)         # destroyed with its context, as the stores are
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.vba_scanlog_destroy(self.h)
-            self.h = None
-        kf = getattr(self.ctx, "_kf", None)
-        if kf is not None and self in kf:
-            kf.remove(self)
+    PREFIX = "vba_scanlog"
 
     def reserve(self, points=0, scans=0):
-        self.ctx._chk(self.lib.vba_scanlog_reserve(self.h, C.c_int64(points), C.c_int(scans)))
-
-    def allocations(self):
-        n = C.c_int(); b = C.c_int64()
-        self.ctx._chk(self.lib.vba_scanlog_allocations(self.h, C.byref(n), C.byref(b)))
-        return n.value, b.value
+        self.ctx._chk(self.lib.vba_scanlog_reserve(self.h, points, scans))
 
     def push_window(self, frame):
         """capture frame ``frame`` of the context's window from the map's scan ring (before margi) -> the scan's number"""
         seq = C.c_int64(-1)
-        self.ctx._chk(self.lib.vba_scanlog_push_window(self.h, C.c_int(frame), C.byref(seq)))
+        self.ctx._chk(self.lib.vba_scanlog_push_window(self.h, frame, C.byref(seq)))
         return seq.value
 
     def push_points(self, pnt, var=None):
@@ -489,27 +425,27 @@ class ScanLog:
         pnt = _c(pnt).reshape(-1, 3)
         v = _c(var).reshape(-1, 9) if var is not None else None
         seq = C.c_int64(-1)
-        self.ctx._chk(self.lib.vba_scanlog_push_points(self.h, C.c_int(len(pnt)), _p(pnt), _p(v), C.byref(seq)))
+        self.ctx._chk(self.lib.vba_scanlog_push_points(self.h, len(pnt), _p(pnt), _p(v), C.byref(seq)))
         return seq.value
 
     def range(self):
         """(first, end, sizes int32 [end - first]) of the live scans"""
         a = C.c_int64(); b = C.c_int64()
-        self.ctx._chk(self.lib.vba_scanlog_range(self.h, C.byref(a), C.byref(b), C.c_int(0), None))
+        self.ctx._chk(self.lib.vba_scanlog_range(self.h, C.byref(a), C.byref(b), 0, None))
         sizes = np.zeros(max(b.value - a.value, 1), dtype=np.int32)
-        self.ctx._chk(self.lib.vba_scanlog_range(self.h, C.byref(a), C.byref(b), C.c_int(len(sizes)), sizes.ctypes.data_as(C.POINTER(C.c_int))))
+        self.ctx._chk(self.lib.vba_scanlog_range(self.h, C.byref(a), C.byref(b), len(sizes), sizes.ctypes.data_as(C.POINTER(C.c_int))))
         return a.value, b.value, sizes[:max(b.value - a.value, 0)].copy()
 
     def release(self, upto):
-        self.ctx._chk(self.lib.vba_scanlog_release(self.h, C.c_int64(upto)))
+        self.ctx._chk(self.lib.vba_scanlog_release(self.h, upto))
 
     def read(self, seq, xyz=False):
         """scan ``seq`` -> (pnt [n][3], var [n][9]); with xyz=True also the float32 [n][3] form narrowed on the device"""
         n = C.c_int()
-        self.ctx._chk(self.lib.vba_scanlog_read(self.h, C.c_int64(seq), C.c_int(0), None, None, None, C.byref(n)))
+        self.ctx._chk(self.lib.vba_scanlog_read(self.h, seq, 0, None, None, None, C.byref(n)))
         m = max(n.value, 1)
         pnt = np.zeros((m, 3)); var = np.zeros((m, 9)); f = np.zeros((m, 3), dtype=np.float32) if xyz else None
-        self.ctx._chk(self.lib.vba_scanlog_read(self.h, C.c_int64(seq), C.c_int(n.value), _p(pnt), _p(var),
+        self.ctx._chk(self.lib.vba_scanlog_read(self.h, seq, n.value, _p(pnt), _p(var),
                                                 f.ctypes.data_as(C.POINTER(C.c_float)) if xyz else None, C.byref(n)))
         out = (pnt[:n.value].copy(), var[:n.value].copy())
         return out + (f[:n.value].copy(),) if xyz else out
@@ -522,16 +458,16 @@ class ScanLog:
         poses = _c(poses).reshape(-1, 12)
         k = len(poses)
         n = C.c_int64()
-        head = (ctx.h, self.h, C.c_int64(first), C.c_int(k), _p(poses), C.c_int(int(stride)), C.c_float(intensity))
+        head = (ctx.h, self.h, first, k, _p(poses), int(stride), intensity)
         if out is not None:
-            ctx._chk(self.lib.vba_scanlog_export_world(*head, C.c_int64(int(cap)), out if isinstance(out, C.c_void_p) else C.c_void_p(int(out)), C.byref(n)))
+            ctx._chk(self.lib.vba_scanlog_export_world(*head, int(cap), out if isinstance(out, C.c_void_p) else C.c_void_p(int(out)), C.byref(n)))
             return n.value
         if cap is None:
             a, b, sizes = self.range()
             s = sizes[first - a:first - a + k].astype(np.int64)
             cap = int(((s + stride - 1) // max(int(stride), 1)).sum())
         res = np.zeros((max(int(cap), 1), 4), dtype=np.float32)
-        ctx._chk(self.lib.vba_scanlog_export_world(*head, C.c_int64(int(cap)), res.ctypes.data_as(C.c_void_p), C.byref(n)))
+        ctx._chk(self.lib.vba_scanlog_export_world(*head, int(cap), res.ctypes.data_as(C.c_void_p), C.byref(n)))
         return res[:n.value].copy()
 
 
@@ -569,34 +505,17 @@ def scan_layout_check(layout) -> int:
     return load().vba_scan_layout_check(C.byref(layout))
 
 
-class ScanFrame:
+class ScanFrame(_Handle):
     """One vba_scan_frame: the device buffers of one scan from the raw message to var_init's output."""
+    PREFIX = "vba_scan_frame"
 
     def __init__(self, ctx):
-        self.ctx = ctx
-        self.lib = ctx.lib
-        h = C.c_void_p()
-        ctx._chk(self.lib.vba_scan_frame_create(ctx.h, C.byref(h)))
-        self.h = h
+        super().__init__(ctx)
         self.n = 0
         self.n_ds = 0
-        ctx._kf.append(self)         # destroyed with its context, as the stores are
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.vba_scan_frame_destroy(self.h)
-            self.h = None
-        kf = getattr(self.ctx, "_kf", None)
-        if kf is not None and self in kf:
-            kf.remove(self)
 
     def reserve(self, max_raw_points, max_point_step):
-        self.ctx._chk(self.lib.vba_scan_frame_reserve(self.h, C.c_int(max_raw_points), C.c_int(max_point_step)))
-
-    def allocations(self):
-        n = C.c_int(); b = C.c_int64()
-        self.ctx._chk(self.lib.vba_scan_frame_allocations(self.h, C.byref(n), C.byref(b)))
-        return n.value, b.value
+        self.ctx._chk(self.lib.vba_scan_frame_reserve(self.h, max_raw_points, max_point_step))
 
     def decode(self, layout, raw, point_filter_num=1, blind2=0.0, n_raw=None):
         """raw: the message's bytes (bytes or a uint8 array).  Returns (n, last_curvature)."""
@@ -606,8 +525,8 @@ class ScanFrame:
         if len(buf) < n_raw * layout.point_step:
             raise ValueError("raw holds fewer than n_raw records")
         n = C.c_int(0); last = C.c_double(0.0)
-        self.ctx._chk(self.lib.vba_scan_decode(self.h, C.byref(layout), buf.ctypes.data_as(C.c_void_p), C.c_int(n_raw), C.c_int(point_filter_num),
-                                               C.c_double(blind2), C.byref(n), C.byref(last)))
+        self.ctx._chk(self.lib.vba_scan_decode(self.h, C.byref(layout), buf.ctypes.data_as(C.c_void_p), n_raw, point_filter_num,
+                                               blind2, C.byref(n), C.byref(last)))
         self.n = n.value; self.n_ds = 0
         return n.value, last.value
 
@@ -617,8 +536,8 @@ class ScanFrame:
         ip = _c(imu_poses22) if imu_poses22 is not None else np.zeros((0, 22))
         end = _c(end_pose12) if end_pose12 is not None else None
         n = C.c_int(0); dp = C.c_void_p(); dv = C.c_void_p()
-        ctx._chk(self.lib.vba_scan_prepare(ctx.h, self.h, C.c_int(len(ip)), _p(ip), _p(end), _p(_c(ext_pose12)), C.c_int(int(point_notime)),
-                                           C.c_double(down_size), C.c_int(min_points), C.c_double(dept_err), C.c_double(beam_err),
+        ctx._chk(self.lib.vba_scan_prepare(ctx.h, self.h, len(ip), _p(ip), _p(end), _p(_c(ext_pose12)), int(point_notime),
+                                           down_size, min_points, dept_err, beam_err,
                                            C.byref(n), C.byref(dp), C.byref(dv)))
         self.n_ds = n.value
         return n.value, dp.value or 0, dv.value or 0
@@ -635,38 +554,18 @@ class ScanFrame:
             cnt = np.zeros(n, dtype=np.int32); first = np.zeros(n, dtype=np.int32); out.update(count=cnt, first=first)
         else:
             var = np.zeros((n, 9)); out.update(var=var)
-        self.ctx._chk(self.lib.vba_scan_frame_read(self.h, C.c_int(stage), _p(pnt), inten.ctypes.data_as(C.POINTER(C.c_float)) if inten is not None else None,
+        self.ctx._chk(self.lib.vba_scan_frame_read(self.h, stage, _p(pnt), inten.ctypes.data_as(C.POINTER(C.c_float)) if inten is not None else None,
                                                    _p(curv), cnt.ctypes.data_as(ip) if cnt is not None else None,
                                                    first.ctypes.data_as(ip) if first is not None else None, _p(var)))
         return out
 
 
-class InitWindow:
+class InitWindow(_Handle):
     """One vba_init_window: pl_origs of the LiDAR-inertial initialisation, resident in HBM."""
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.lib = ctx.lib
-        h = C.c_void_p()
-        ctx._chk(self.lib.vba_init_window_create(ctx.h, C.byref(h)))
-        self.h = h
-        ctx._kf.append(self)         # destroyed with its context, as the stores are
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.vba_init_window_destroy(self.h)
-            self.h = None
-        kf = getattr(self.ctx, "_kf", None)
-        if kf is not None and self in kf:
-            kf.remove(self)
+    PREFIX = "vba_init_window"
 
     def reserve(self, max_scans, max_points_per_scan):
-        self.ctx._chk(self.lib.vba_init_window_reserve(self.h, C.c_int(max_scans), C.c_int(max_points_per_scan)))
-
-    def allocations(self):
-        n = C.c_int(); b = C.c_int64()
-        self.ctx._chk(self.lib.vba_init_window_allocations(self.h, C.byref(n), C.byref(b)))
-        return n.value, b.value
+        self.ctx._chk(self.lib.vba_init_window_reserve(self.h, max_scans, max_points_per_scan))
 
     def clear(self):
         self.ctx._chk(self.lib.vba_init_window_clear(self.h))
@@ -685,7 +584,7 @@ class InitWindow:
     def push(self, frame, down_size, min_points=1000):
         """down_sampling_close + retry + sort of VS:1499-1511 from the frame's stage 0.  Returns (n_kept, retried)."""
         n = C.c_int(0); r = C.c_int(0)
-        self.ctx._chk(self.lib.vba_init_window_push(self.h, frame.h, C.c_double(down_size), C.c_int(min_points), C.byref(n), C.byref(r)))
+        self.ctx._chk(self.lib.vba_init_window_push(self.h, frame.h, down_size, min_points, C.byref(n), C.byref(r)))
         return n.value, r.value
 
     def push_points(self, pnt, curv):
@@ -693,7 +592,7 @@ class InitWindow:
         pnt = _c(np.reshape(pnt, (-1, 3))); curv = _c(np.ravel(curv))
         if len(pnt) != len(curv):
             raise ValueError("pnt and curv differ in length")
-        self.ctx._chk(self.lib.vba_init_window_push_points(self.h, C.c_int(len(curv)), _p(pnt), _p(curv)))
+        self.ctx._chk(self.lib.vba_init_window_push_points(self.h, len(curv), _p(pnt), _p(curv)))
 
     def read(self, scan):
         """(pnt [n][3], curv [n]) of one scan."""
@@ -702,7 +601,7 @@ class InitWindow:
             raise IndexError(scan)
         n = int(off[scan + 1] - off[scan])
         pnt = np.zeros((n, 3)); curv = np.zeros(n)
-        self.ctx._chk(self.lib.vba_init_window_read(self.h, C.c_int(scan), _p(pnt), _p(curv)))
+        self.ctx._chk(self.lib.vba_init_window_read(self.h, scan, _p(pnt), _p(curv)))
         return pnt, curv
 
 
@@ -712,33 +611,13 @@ class OdomReport(C.Structure):
                 ("nnt_eig_min", C.c_double)]
 
 
-class OdomState:
+class OdomState(_Handle):
     """One vba_odom_state: the odometry state and its covariance resident in HBM from one scan to the next, with the pose table of
     the IMU propagation."""
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.lib = ctx.lib
-        h = C.c_void_p()
-        ctx._chk(self.lib.vba_odom_state_create(ctx.h, C.byref(h)))
-        self.h = h
-        ctx._kf.append(self)         # destroyed with its context, as the stores are
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.vba_odom_state_destroy(self.h)
-            self.h = None
-        kf = getattr(self.ctx, "_kf", None)
-        if kf is not None and self in kf:
-            kf.remove(self)
+    PREFIX = "vba_odom_state"
 
     def reserve(self, max_imu_rows):
-        self.ctx._chk(self.lib.vba_odom_state_reserve(self.h, C.c_int(max_imu_rows)))
-
-    def allocations(self):
-        n = C.c_int(); b = C.c_int64()
-        self.ctx._chk(self.lib.vba_odom_state_allocations(self.h, C.byref(n), C.byref(b)))
-        return n.value, b.value
+        self.ctx._chk(self.lib.vba_odom_state_reserve(self.h, max_imu_rows))
 
     def set(self, state25, cov225):
         self.ctx._chk(self.lib.vba_odom_state_set(self.h, _p(_c(state25)), _p(_c(cov225))))
@@ -752,24 +631,24 @@ class OdomState:
     def poses(self):
         """(imu_poses [n][22], end_pose [12]) of the last propagation; synchronises"""
         n = C.c_int(0)
-        self.ctx._chk(self.lib.vba_odom_state_poses(self.h, C.c_int(0), None, None, C.byref(n)))
+        self.ctx._chk(self.lib.vba_odom_state_poses(self.h, 0, None, None, C.byref(n)))
         rows = np.zeros((n.value, 22)); end = np.zeros(12)
-        self.ctx._chk(self.lib.vba_odom_state_poses(self.h, C.c_int(n.value), _p(rows), _p(end), C.byref(n)))
+        self.ctx._chk(self.lib.vba_odom_state_poses(self.h, n.value, _p(rows), _p(end), C.byref(n)))
         return rows, end
 
     def propagate(self, imu, noise12, last_pcl_end_time, pcl_beg_time, pcl_end_time, scale_gravity=1.0):
         """IMUEKF::motion_blur's propagation (ekf_imu.hpp:54-123) on the device state; returns the rows of the pose table.  No wait."""
         imu = _c(imu).reshape(-1, 7); n = C.c_int(0)
-        self.ctx._chk(self.lib.vba_odom_state_propagate(self.h, _p(_c(noise12)), C.c_double(scale_gravity), C.c_int(len(imu)), _p(imu),
-                                                        C.c_double(last_pcl_end_time), C.c_double(pcl_beg_time), C.c_double(pcl_end_time), C.byref(n)))
+        self.ctx._chk(self.lib.vba_odom_state_propagate(self.h, _p(_c(noise12)), scale_gravity, len(imu), _p(imu),
+                                                        last_pcl_end_time, pcl_beg_time, pcl_end_time, C.byref(n)))
         return n.value
 
     def prepare(self, frame, ext_pose12, down_size, dept_err, beam_err, min_points=500, point_notime=False, ctx=None):
         """ScanFrame.prepare with the table and end_pose of the last propagation read in place: (n, d_pnt_body, d_var_body)."""
         ctx = ctx or self.ctx
         n = C.c_int(0); dp = C.c_void_p(); dv = C.c_void_p()
-        ctx._chk(self.lib.vba_scan_prepare_on_state(ctx.h, frame.h, self.h, _p(_c(ext_pose12)), C.c_int(int(point_notime)), C.c_double(down_size),
-                                                    C.c_int(min_points), C.c_double(dept_err), C.c_double(beam_err), C.byref(n), C.byref(dp), C.byref(dv)))
+        ctx._chk(self.lib.vba_scan_prepare_on_state(ctx.h, frame.h, self.h, _p(_c(ext_pose12)), int(point_notime), down_size,
+                                                    min_points, dept_err, beam_err, C.byref(n), C.byref(dp), C.byref(dv)))
         frame.n_ds = n.value
         return n.value, dp.value or 0, dv.value or 0
 
@@ -778,7 +657,7 @@ class OdomState:
         covariance afterwards."""
         ctx = ctx or self.ctx
         ok = C.c_int(0); rep = OdomReport(); st = np.zeros(25)
-        ctx._chk(self.lib.vba_odom_lio_state_estimation_on_state(ctx.h, self.h, C.c_int(n), C.c_void_p(d_pnt_body), C.c_void_p(d_var_body), C.byref(ok),
+        ctx._chk(self.lib.vba_odom_lio_state_estimation_on_state(ctx.h, self.h, n, C.c_void_p(d_pnt_body), C.c_void_p(d_var_body), C.byref(ok),
                                                                  C.byref(rep), _p(st)))
         report = dict(iterations=rep.iterations, match_num=np.array(rep.match_num[:], dtype=np.int64), rot_add=np.array(rep.rot_add[:]),
                       tra_add=np.array(rep.tra_add[:]), nnt_eig_min=rep.nnt_eig_min)
@@ -787,8 +666,8 @@ class OdomState:
     def pvec_update_cut_voxel(self, win_count, n, d_pnt_body, d_var_body, multi=False, ctx=None):
         """Context.pvec_update_cut_voxel_dev with the pose and covariance blocks of the resident state."""
         ctx = ctx or self.ctx
-        ctx._chk(self.lib.vba_map_pvec_update_cut_voxel_on_state(ctx.h, self.h, C.c_int(win_count), C.c_int(n), C.c_void_p(d_pnt_body),
-                                                                 C.c_void_p(d_var_body), C.c_int(int(multi))))
+        ctx._chk(self.lib.vba_map_pvec_update_cut_voxel_on_state(ctx.h, self.h, win_count, n, C.c_void_p(d_pnt_body),
+                                                                 C.c_void_p(d_var_body), int(multi)))
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -818,9 +697,11 @@ def load():
         if not os.path.exists(LIB_PATH):
             raise RuntimeError("libvoxelba.so is missing (run __graft_entry__.build()); there is no CPU fallback")
         lib = C.CDLL(LIB_PATH)
-        lib.vba_status_string.restype = C.c_char_p
-        lib.vba_last_error.restype = C.c_char_p
-        lib.vba_shard_owner.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int]
+        for name, proto in PROTOTYPES.items():     # (a symbol the library lacks raises AttributeError here)
+            fn = getattr(lib, name)
+            ret, params = proto.split(":")
+            fn.restype = KINDS[ret]
+            fn.argtypes = [KINDS[k] for k in params]
         _lib = lib
     return _lib
 
@@ -867,7 +748,7 @@ def shard_owner(key3, n_ranks: int) -> int:
 def imu_preintegrate(t, gyr, acc, bg, ba, noise_meas, noise_walk, scale_gravity=1.0):
     t, gyr, acc, bg, ba, nm, nw = map(_c, (t, gyr, acc, bg, ba, noise_meas, noise_walk))
     out = np.empty(304)
-    st = load().vba_imu_preintegrate(C.c_int(len(t)), _p(t), _p(gyr), _p(acc), _p(bg), _p(ba), _p(nm), _p(nw), C.c_double(scale_gravity), _p(out))
+    st = load().vba_imu_preintegrate(len(t), _p(t), _p(gyr), _p(acc), _p(bg), _p(ba), _p(nm), _p(nw), scale_gravity, _p(out))
     if st:
         raise VbaError(st)
     return out
@@ -877,7 +758,7 @@ def imu_give_evaluate(imu, st1, st2, with_g=False, jac=True):
     imu, st1, st2 = map(_c, (imu, st1, st2))
     nb = 33 if with_g else 30
     jtj = np.zeros((nb, nb)); gg = np.zeros(nb); r = C.c_double()
-    st = load().vba_imu_give_evaluate(_p(imu), _p(st1), _p(st2), C.c_int(int(with_g)), C.c_int(int(jac)), _p(jtj), _p(gg), C.byref(r))
+    st = load().vba_imu_give_evaluate(_p(imu), _p(st1), _p(st2), int(with_g), int(jac), _p(jtj), _p(gg), C.byref(r))
     if st:
         raise VbaError(st)
     return r.value, jtj, gg
@@ -888,8 +769,8 @@ def imu_ekf_propagate(imu, noise12, last_pcl_end_time, pcl_beg_time, pcl_end_tim
     (state, cov [15][15], imu_poses [n][22], end_pose [12])."""
     imu = _c(imu).reshape(-1, 7); st = _c(state25).copy(); cov = _c(cov225).reshape(15, 15).copy()
     rows = np.zeros((max(len(imu) - 1, 1), 22)); end = np.zeros(12); n = C.c_int(0)
-    r = load().vba_imu_ekf_propagate(C.c_int(len(imu)), _p(imu), _p(_c(noise12)), C.c_double(scale_gravity), C.c_double(last_pcl_end_time),
-                                     C.c_double(pcl_beg_time), C.c_double(pcl_end_time), _p(st), _p(cov), _p(rows), _p(end), C.byref(n))
+    r = load().vba_imu_ekf_propagate(len(imu), _p(imu), _p(_c(noise12)), scale_gravity, last_pcl_end_time,
+                                     pcl_beg_time, pcl_end_time, _p(st), _p(cov), _p(rows), _p(end), C.byref(n))
     if r:
         raise VbaError(r)
     return st, cov, rows[:n.value].copy(), end
@@ -900,7 +781,7 @@ def init_imu_poses(imu, state_c, state_l, beg_time, scale_gravity=1.0):
     imu = _c(imu).reshape(-1, 7); xc = _c(state_c); xl = _c(state_l)
     m = len(imu)
     out = np.zeros((max(m - 1, 0), 22))
-    st = load().vba_init_imu_poses(C.c_int(m), _p(imu), _p(xc), _p(xl), C.c_double(beg_time), C.c_double(scale_gravity), _p(out))
+    st = load().vba_init_imu_poses(m, _p(imu), _p(xc), _p(xl), beg_time, scale_gravity, _p(out))
     if st:
         raise VbaError(st)
     return out
@@ -909,7 +790,7 @@ def init_imu_poses(imu, state_c, state_l, beg_time, scale_gravity=1.0):
 def init_align_gravity(states):
     """Initialization::align_gravity (voxelslam.cpp:470-497) on a copy of states [n][25]."""
     xs = _c(states).copy()
-    st = load().vba_init_align_gravity(C.c_int(len(xs)), _p(xs))
+    st = load().vba_init_align_gravity(len(xs), _p(xs))
     if st:
         raise VbaError(st)
     return xs
@@ -923,24 +804,24 @@ def _io_chk(st):
 def save_pcd(path, xyz):
     """FileReaderWriter::save_pcd (voxelslam.cpp:166-179): binary PCD of PointXYZI, intensity 0."""
     xyz = _c(xyz).reshape(-1, 3)
-    _io_chk(load().vba_io_save_pcd(os.fsencode(path), C.c_int(len(xyz)), _p(xyz)))
+    _io_chk(load().vba_io_save_pcd(os.fsencode(path), len(xyz), _p(xyz)))
 
 
 def load_pcd(path):
     """pcl::io::loadPCDFile as used by previous_map_read (voxelslam.cpp:337-340) -> (xyz [n,3], intensity [n])."""
     n = C.c_int(0)
-    st = load().vba_io_load_pcd(os.fsencode(path), C.c_int(0), None, None, C.byref(n))
+    st = load().vba_io_load_pcd(os.fsencode(path), 0, None, None, C.byref(n))
     if st not in (0, 7):
         _io_chk(st)
     xyz = np.zeros((max(n.value, 1), 3)); inten = np.zeros(max(n.value, 1))
-    _io_chk(load().vba_io_load_pcd(os.fsencode(path), C.c_int(n.value), _p(xyz), _p(inten), C.byref(n)))
+    _io_chk(load().vba_io_load_pcd(os.fsencode(path), n.value, _p(xyz), _p(inten), C.byref(n)))
     return xyz[:n.value], inten[:n.value]
 
 
 def save_pose(path, states, v6):
     """FileReaderWriter::save_pose (voxelslam.cpp:181-204); writes nothing for fewer than 100 scans."""
     states = _c(states).reshape(-1, 25); v6 = _c(v6).reshape(-1, 6)
-    _io_chk(load().vba_io_save_pose(os.fsencode(path), C.c_int(len(states)), _p(states), _p(v6)))
+    _io_chk(load().vba_io_save_pose(os.fsencode(path), len(states), _p(states), _p(v6)))
 
 
 def kf_export_plan(sizes, interval_size=5_000_000, jump=0):
@@ -952,19 +833,19 @@ def kf_export_plan(sizes, interval_size=5_000_000, jump=0):
     ip = C.POINTER(C.c_int)
     j = C.c_int(); nm = C.c_int()
     kb = np.zeros(n + 1, dtype=np.int64); me = np.zeros(n + 1, dtype=np.int32)
-    _io_chk(load().vba_kf_export_plan(C.c_int(n), sizes.ctypes.data_as(ip), C.c_int64(int(interval_size)), C.c_int(int(jump)), C.byref(j),
-                                      kb.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(n + 1), me.ctypes.data_as(ip), C.byref(nm)))
+    _io_chk(load().vba_kf_export_plan(n, sizes.ctypes.data_as(ip), int(interval_size), int(jump), C.byref(j),
+                                      kb.ctypes.data_as(C.POINTER(C.c_int64)), n + 1, me.ctypes.data_as(ip), C.byref(nm)))
     return j.value, kb, me[:nm.value].copy()
 
 
 def read_lidarstate(path):
     """read_lidarstate (voxelslam.hpp:268-307) -> (states [n,25], v6 [n,6])."""
     n = C.c_int(0)
-    st = load().vba_io_read_lidarstate(os.fsencode(path), C.c_int(0), None, None, C.byref(n))
+    st = load().vba_io_read_lidarstate(os.fsencode(path), 0, None, None, C.byref(n))
     if st not in (0, 7):
         _io_chk(st)
     states = np.zeros((max(n.value, 1), 25)); v6 = np.zeros((max(n.value, 1), 6))
-    _io_chk(load().vba_io_read_lidarstate(os.fsencode(path), C.c_int(n.value), _p(states), _p(v6), C.byref(n)))
+    _io_chk(load().vba_io_read_lidarstate(os.fsencode(path), n.value, _p(states), _p(v6), C.byref(n)))
     return states[:n.value], v6[:n.value]
 
 
@@ -1015,7 +896,7 @@ class Context:
 
     def push_voxels(self, clusters, fix, coe, eig_val, eig_vec, pcr_add):
         a = [_c(x) for x in (clusters, fix, coe, eig_val, eig_vec, pcr_add)]
-        self._chk(self.lib.vba_factor_push_voxels(self.h, C.c_int(len(a[2])), *[_p(x) for x in a]))
+        self._chk(self.lib.vba_factor_push_voxels(self.h, len(a[2]), *[_p(x) for x in a]))
 
     def push_dict(self, f):
         self.push_voxels(f["clusters"], f["fix"], f["coe"], f["eig_val"], f["eig_vec"], f["pcr_add"])
@@ -1024,13 +905,13 @@ class Context:
         end = self.size() if end is None else end
         poses = _c(poses); n = 6 * self.W
         H = np.empty((n, n)); g = np.empty(n); r = C.c_double()
-        self._chk(self.lib.vba_factor_acc_evaluate2(self.h, _p(poses), C.c_int(head), C.c_int(end), _p(H), _p(g), C.byref(r)))
+        self._chk(self.lib.vba_factor_acc_evaluate2(self.h, _p(poses), head, end, _p(H), _p(g), C.byref(r)))
         return H, g, r.value
 
     def evaluate_only_residual(self, poses, head=0, end=None):
         end = self.size() if end is None else end
         poses = _c(poses); r = C.c_double()
-        self._chk(self.lib.vba_factor_evaluate_only_residual(self.h, _p(poses), C.c_int(head), C.c_int(end), C.byref(r)))
+        self._chk(self.lib.vba_factor_evaluate_only_residual(self.h, _p(poses), head, end, C.byref(r)))
         return r.value
 
     def read_back(self):
@@ -1053,14 +934,14 @@ class Context:
     # ---- optimizers
     def last_trace(self):
         rows = np.zeros((64, 5))
-        n = self.lib.vba_last_lm_trace(self.h, _p(rows), C.c_int(64))
+        n = self.lib.vba_last_lm_trace(self.h, _p(rows), 64)
         return rows[:n].copy()
 
     def lidar_ba_damping_iter(self, poses, max_iter=3, thd_num=2):
         """Lidar_BA_Optimizer::damping_iter (voxel_map.hpp:422-497)."""
         poses = _c(poses).copy(); n = 6 * self.W
         H = np.empty((n, n)); resis = np.zeros(2); conv = C.c_int(0)
-        st = self.lib.vba_lidar_ba_damping_iter(self.h, _p(poses), _p(H), _p(resis), C.c_int(max_iter), C.c_int(thd_num), C.byref(conv))
+        st = self.lib.vba_lidar_ba_damping_iter(self.h, _p(poses), _p(H), _p(resis), max_iter, thd_num, C.byref(conv))
         if st == ERR_TOO_FEW_VOXELS:
             return dict(poses=poses, hess=H, resis=resis, converge=False, status=-1, trace=self.last_trace())
         self._chk(st)
@@ -1071,7 +952,7 @@ class Context:
         states = _c(states).copy(); imus = _c(imus).copy()
         n = 15 * self.W + (3 if gravity else 0)
         H = np.empty((n, n)); resis = np.zeros(2)
-        self._chk(self.lib.vba_li_ba_damping_iter(self.h, _p(states), _p(imus), C.c_int(int(gravity)), C.c_int(max_iter), _p(H), _p(resis)))
+        self._chk(self.lib.vba_li_ba_damping_iter(self.h, _p(states), _p(imus), int(gravity), max_iter, _p(H), _p(resis)))
         return dict(states=states, imus=imus, hess=H, resis=resis, trace=self.last_trace())
 
     SOLVE_KINDS = {"lidar": 0, "li": 1, "dense": 2}
@@ -1086,8 +967,8 @@ class Context:
         H = _c(H); g = _c(g); n = len(g)
         nc = 1 if kind == "dense" else (self.opt.lm_spec if 0 < self.opt.lm_spec < 4 else 4)
         dx = np.zeros((nc, n)); q1 = np.zeros(nc)
-        self._chk(self.lib.vba_debug_solve(self.h, C.c_int(self.SOLVE_KINDS[kind]), C.c_int(W), C.c_int(f), _p(H), _p(g),
-                                           C.c_double(u), C.c_double(v), _p(dx), _p(q1)))
+        self._chk(self.lib.vba_debug_solve(self.h, self.SOLVE_KINDS[kind], W, f, _p(H), _p(g),
+                                           u, v, _p(dx), _p(q1)))
         return dx, q1
 
     IMU_FORMS = {"alone": 0, "h2": 1, "h3": 2}
@@ -1100,13 +981,13 @@ class Context:
         W = self.W; n = 15 * W + (3 if gravity else 0)
         f = (self.IMU_FORMS[form] | (4 if trial else 0)) if raw_flags is None else raw_flags
         H = np.zeros((n, n)); g = np.zeros(n); rimu = np.zeros(2); ci = np.zeros((max(W - 1, 1), 15, 15))
-        self._chk(self.lib.vba_debug_li_imu(self.h, C.c_int(W), C.c_int(int(gravity)), C.c_int(f), _p(states), _p(imus), _p(H), _p(g),
+        self._chk(self.lib.vba_debug_li_imu(self.h, W, int(gravity), f, _p(states), _p(imus), _p(H), _p(g),
                                             _p(rimu), _p(ci)))
         return dict(H=H, g=g, rimu=rimu, covinv=ci)
 
     def lm_begin(self, poses, thd_num=2):
         poses = _c(poses)
-        self._chk(self.lib.vba_lm_begin(self.h, _p(poses), C.c_int(thd_num)))
+        self._chk(self.lib.vba_lm_begin(self.h, _p(poses), thd_num))
 
     def lm_iterate(self, sync=True):
         """One LM iteration (loop body voxel_map.hpp:441-494).  sync=False only enqueues the launches."""
@@ -1152,10 +1033,10 @@ class Context:
         po = np.zeros((cap, 3)) if want_pvec else None
         vo = np.zeros((cap, 9)) if want_pvec else None
         self._chk(self.lib.vba_motion_init(
-            self.h, C.c_int(W), pto.ctypes.data_as(ip_), _p(pnt), _p(cv), imo.ctypes.data_as(ip_), _p(imu), _p(bt), _p(ext),
-            C.c_double(dept_err), C.c_double(beam_err), C.c_double(scale_gravity), C.c_int(int(point_notime)), _p(nm), _p(nw),
-            _p(xs), _p(cov), _p(ip), _p(H), C.byref(conv), _p(eig), C.byref(iters), C.byref(relax), _p(log), C.c_int(10),
-            _p(po), _p(vo), pvo.ctypes.data_as(ip_), C.c_int(cap)))
+            self.h, W, pto.ctypes.data_as(ip_), _p(pnt), _p(cv), imo.ctypes.data_as(ip_), _p(imu), _p(bt), _p(ext),
+            dept_err, beam_err, scale_gravity, int(point_notime), _p(nm), _p(nw),
+            _p(xs), _p(cov), _p(ip), _p(H), C.byref(conv), _p(eig), C.byref(iters), C.byref(relax), _p(log), 10,
+            _p(po), _p(vo), pvo.ctypes.data_as(ip_), cap))
         out = dict(converged=conv.value, eigvalue3=eig, iterations=iters.value, thresholds_left_relaxed=relax.value,
                    round_log=log[:iters.value].copy(), states=xs, imu_pre=ip, hess=H, pvec_offsets=pvo)
         if want_pvec:
@@ -1184,10 +1065,10 @@ class Context:
         po = np.zeros((cap, 3)) if want_pvec else None
         vo = np.zeros((cap, 9)) if want_pvec else None
         self._chk(self.lib.vba_motion_init_resident(
-            self.h, C.c_int(W), window.h, imo.ctypes.data_as(ip_), _p(imu), _p(bt), _p(ext),
-            C.c_double(dept_err), C.c_double(beam_err), C.c_double(scale_gravity), C.c_int(int(point_notime)), _p(nm), _p(nw),
-            _p(xs), _p(cov), _p(ip), _p(H), C.byref(conv), _p(eig), C.byref(iters), C.byref(relax), _p(log), C.c_int(10),
-            _p(po), _p(vo), pvo.ctypes.data_as(ip_), C.c_int(cap)))
+            self.h, W, window.h, imo.ctypes.data_as(ip_), _p(imu), _p(bt), _p(ext),
+            dept_err, beam_err, scale_gravity, int(point_notime), _p(nm), _p(nw),
+            _p(xs), _p(cov), _p(ip), _p(H), C.byref(conv), _p(eig), C.byref(iters), C.byref(relax), _p(log), 10,
+            _p(po), _p(vo), pvo.ctypes.data_as(ip_), cap))
         out = dict(converged=conv.value, eigvalue3=eig, iterations=iters.value, thresholds_left_relaxed=relax.value,
                    round_log=log[:iters.value].copy(), states=xs, imu_pre=ip, hess=H, pvec_offsets=pvo)
         if want_pvec:
@@ -1216,8 +1097,7 @@ class Context:
             j = max(int(jump), 1)
             count = sum(int(((s.sizes().astype(np.int64) + j - 1) // j).sum()) for s in stores) - int(begin)
         hs = (C.c_void_p * max(len(stores), 1))(*[(s.h.value if s is not None else None) for s in stores])
-        args = (self.h, C.c_int(len(stores)), hs, inten.ctypes.data_as(C.POINTER(C.c_float)), C.c_int(int(jump)), C.c_int64(int(begin)),
-                C.c_int64(int(count)))
+        args = (self.h, len(stores), hs, inten.ctypes.data_as(C.POINTER(C.c_float)), int(jump), int(begin), int(count))
         if out is not None:
             self._chk(self.lib.vba_kf_export_world(*args, out if isinstance(out, C.c_void_p) else C.c_void_p(int(out))))
             return None
@@ -1245,9 +1125,9 @@ class Context:
             wv = np.ascontiguousarray(np.concatenate([np.reshape(v, (-1, 9)) for v in win_vars]), dtype=np.float64) if win_vars is not None else None
         ip = C.POINTER(C.c_int)
         nf = C.c_int()
-        self._chk(self.lib.vba_loop_update(self.h, lm.h, _p(_c(dx12)) if dx12 is not None else None, C.c_int(k),
+        self._chk(self.lib.vba_loop_update(self.h, lm.h, _p(_c(dx12)) if dx12 is not None else None, k,
                                            off.ctypes.data_as(ip) if off is not None else None, _p(pnt), _p(var), _p(bp),
-                                           C.c_int(len(poses_win)), _p(wp), _p(wv), woff.ctypes.data_as(ip) if woff is not None else None,
+                                           len(poses_win), _p(wp), _p(wv), woff.ctypes.data_as(ip) if woff is not None else None,
                                            _p(poses_win), C.byref(nf)))
         return nf.value
 
@@ -1261,8 +1141,8 @@ class Context:
         bp = _c(bl_poses).reshape(-1, 12) if bl_poses is not None and len(bl_poses) else None
         k = len(bp) if bp is not None else 0
         nf = C.c_int()
-        self._chk(self.lib.vba_scanlog_loop_update(self.h, lm.h, _p(_c(dx12)) if dx12 is not None else None, log.h, C.c_int64(first), C.c_int(k),
-                                                   _p(bp), C.c_int(len(poses_win)), _p(poses_win), C.byref(nf)))
+        self._chk(self.lib.vba_scanlog_loop_update(self.h, lm.h, _p(_c(dx12)) if dx12 is not None else None, log.h, first, k,
+                                                   _p(bp), len(poses_win), _p(poses_win), C.byref(nf)))
         return nf.value
 
     def btc_search_loop_sessions(self, dbs, rows, bits, cur_db, cur_frame=-1):
@@ -1272,27 +1152,27 @@ class Context:
             cur_frame = cur_db.num_frames() + cur_frame
         arr = (C.c_void_p * max(len(dbs), 1))(*[d.h.value for d in dbs])
         res = (BtcResult * max(len(dbs), 1))()
-        self._chk(self.lib.vba_btc_search_loop_sessions(C.c_int(len(dbs)), arr, C.c_int(len(rows)), _p(rows), bp, cur_db.h,
-                                                        C.c_int(cur_frame), res))
+        self._chk(self.lib.vba_btc_search_loop_sessions(len(dbs), arr, len(rows), _p(rows), bp, cur_db.h,
+                                                        cur_frame, res))
         return [_btc_result(res[k]) for k in range(len(dbs))]
 
     # ---- voxel map
     def cut_voxel(self, win_count, pnt_body, pose12, var=None, multi=False):
         pnt_body = _c(pnt_body); pose12 = _c(pose12)
         v = _c(var) if var is not None else None
-        self._chk(self.lib.vba_map_cut_voxel(self.h, C.c_int(win_count), C.c_int(len(pnt_body)), _p(pnt_body), _p(v), _p(pose12), C.c_int(int(multi))))
+        self._chk(self.lib.vba_map_cut_voxel(self.h, win_count, len(pnt_body), _p(pnt_body), _p(v), _p(pose12), int(multi)))
 
     def pvec_update_cut_voxel(self, win_count, pnt_body, var_body, pose12, cov225, multi=False):
         """pvec_update (voxelslam.hpp:242-265) + cut_voxel[_multi], fused on the device."""
         pnt_body = _c(pnt_body); var_body = _c(var_body); pose12 = _c(pose12); cov = _c(cov225)
-        self._chk(self.lib.vba_map_pvec_update_cut_voxel(self.h, C.c_int(win_count), C.c_int(len(pnt_body)), _p(pnt_body), _p(var_body),
-                                                         _p(pose12), _p(cov), C.c_int(int(multi))))
+        self._chk(self.lib.vba_map_pvec_update_cut_voxel(self.h, win_count, len(pnt_body), _p(pnt_body), _p(var_body),
+                                                         _p(pose12), _p(cov), int(multi)))
 
     def pvec_update_cut_voxel_dev(self, win_count, n, d_pnt_body, d_var_body, pose12, cov225, multi=False):
         """The same on DEVICE arrays (addresses as integers, e.g. what ScanFrame.prepare returns): consumed in place."""
         pose12 = _c(pose12); cov = _c(cov225)
-        self._chk(self.lib.vba_map_pvec_update_cut_voxel(self.h, C.c_int(win_count), C.c_int(n), C.c_void_p(d_pnt_body), C.c_void_p(d_var_body),
-                                                         _p(pose12), _p(cov), C.c_int(int(multi))))
+        self._chk(self.lib.vba_map_pvec_update_cut_voxel(self.h, win_count, n, C.c_void_p(d_pnt_body), C.c_void_p(d_var_body),
+                                                         _p(pose12), _p(cov), int(multi)))
 
     def scan_frame(self) -> "ScanFrame":
         return ScanFrame(self)
@@ -1304,53 +1184,53 @@ class Context:
         """var_init (voxelslam.hpp:210-234): returns (pnt_out, var_out)."""
         pnt = _c(pnt); ext = _c(ext_pose12)
         po = np.empty_like(pnt); var = np.empty((len(pnt), 9))
-        self._chk(self.lib.vba_scan_var_init(self.h, C.c_int(len(pnt)), _p(pnt), _p(ext), C.c_double(dept_err), C.c_double(beam_err), _p(po), _p(var)))
+        self._chk(self.lib.vba_scan_var_init(self.h, len(pnt), _p(pnt), _p(ext), dept_err, beam_err, _p(po), _p(var)))
         return po, var
 
     def down_sampling_voxel(self, pnt, voxel_size):
         pnt = _c(pnt); n = len(pnt)
         out = np.empty((max(n, 1), 3)); cnt = np.zeros(max(n, 1), dtype=np.int32); first = np.zeros(max(n, 1), dtype=np.int32)
         m = C.c_int(0)
-        self._chk(self.lib.vba_scan_down_sampling_voxel(self.h, C.c_int(n), _p(pnt), C.c_double(voxel_size), _p(out),
+        self._chk(self.lib.vba_scan_down_sampling_voxel(self.h, n, _p(pnt), voxel_size, _p(out),
                                                         cnt.ctypes.data_as(C.POINTER(C.c_int)), first.ctypes.data_as(C.POINTER(C.c_int)), C.byref(m)))
         return out[:m.value].copy(), cnt[:m.value].copy(), first[:m.value].copy()
 
     def down_sampling_pvec(self, pnt, var, voxel_size):
         pnt = _c(pnt); var = _c(var); n = len(pnt)
         out = np.empty((max(n, 1), 3)); vd = np.empty((max(n, 1), 3)); cnt = np.zeros(max(n, 1), dtype=np.int32); m = C.c_int(0)
-        self._chk(self.lib.vba_scan_down_sampling_pvec(self.h, C.c_int(n), _p(pnt), _p(var), C.c_double(voxel_size), _p(out), _p(vd),
+        self._chk(self.lib.vba_scan_down_sampling_pvec(self.h, n, _p(pnt), _p(var), voxel_size, _p(out), _p(vd),
                                                        cnt.ctypes.data_as(C.POINTER(C.c_int)), C.byref(m)))
         return out[:m.value].copy(), vd[:m.value].copy(), cnt[:m.value].copy()
 
     def down_sampling_close(self, pnt, voxel_size):
         pnt = _c(pnt); n = len(pnt)
         idx = np.zeros(max(n, 1), dtype=np.int32); m = C.c_int(0)
-        self._chk(self.lib.vba_scan_down_sampling_close(self.h, C.c_int(n), _p(pnt), C.c_double(voxel_size), idx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(m)))
+        self._chk(self.lib.vba_scan_down_sampling_close(self.h, n, _p(pnt), voxel_size, idx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(m)))
         return idx[:m.value].copy()
 
     def undistort(self, pnt, curv, imu_poses22, end_pose12, ext_pose12):
         pnt = _c(pnt).copy(); curv = _c(curv); ip = _c(imu_poses22)
-        self._chk(self.lib.vba_scan_undistort(self.h, C.c_int(len(pnt)), _p(pnt), _p(curv), C.c_int(len(ip)), _p(ip), _p(_c(end_pose12)),
+        self._chk(self.lib.vba_scan_undistort(self.h, len(pnt), _p(pnt), _p(curv), len(ip), _p(ip), _p(_c(end_pose12)),
                                               _p(_c(ext_pose12))))
         return pnt
 
     def cut_voxel_fix(self, pnt_world, jour=0.0):
         pnt_world = _c(pnt_world)
-        self._chk(self.lib.vba_map_cut_voxel_fix(self.h, C.c_int(len(pnt_world)), _p(pnt_world), C.c_double(jour)))
+        self._chk(self.lib.vba_map_cut_voxel_fix(self.h, len(pnt_world), _p(pnt_world), jour))
 
     def recut(self, win_count, poses, multi=False):
         poses = _c(poses)
-        self._chk(self.lib.vba_map_recut(self.h, C.c_int(win_count), _p(poses), C.c_int(int(multi))))
+        self._chk(self.lib.vba_map_recut(self.h, win_count, _p(poses), int(multi)))
 
     def margi(self, win_count, poses, jour=0.0):
         poses = _c(poses)
-        self._chk(self.lib.vba_map_margi(self.h, C.c_int(win_count), _p(poses), C.c_double(jour)))
+        self._chk(self.lib.vba_map_margi(self.h, win_count, _p(poses), jour))
 
     def slide(self, mgsize=1):
-        self._chk(self.lib.vba_map_slide(self.h, C.c_int(mgsize)))
+        self._chk(self.lib.vba_map_slide(self.h, mgsize))
 
     def prune(self, jour, dist=700):
-        self._chk(self.lib.vba_map_prune(self.h, C.c_double(jour), C.c_int(dist)))
+        self._chk(self.lib.vba_map_prune(self.h, jour, dist))
 
     def map_reset(self):
         self._chk(self.lib.vba_map_reset(self.h))
@@ -1368,32 +1248,24 @@ class Context:
         return dict(zip(keys, [int(x) for x in out]))
 
     def dump_leaves(self):
-        n = self.lib.vba_map_dump_leaves(self.h, None, C.c_int(0))
-        out = np.zeros((max(n, 0), 39))
-        if n > 0:
-            self.lib.vba_map_dump_leaves(self.h, _p(out), C.c_int(n))
-        return out
+        return _dump_rows(self.lib.vba_map_dump_leaves, self.h, 39)
 
     def dump_plane_var(self):
         """[kx,ky,kz,layer,path, plane_var(36), cov_add upper triangle (45)] per leaf."""
-        n = self.lib.vba_map_dump_plane_var(self.h, None, C.c_int(0))
-        out = np.zeros((max(n, 0), 86))
-        if n > 0:
-            self.lib.vba_map_dump_plane_var(self.h, _p(out), C.c_int(n))
-        return out
+        return _dump_rows(self.lib.vba_map_dump_plane_var, self.h, 86)
 
     # ---- odometry
     def lio_state_estimation(self, pnt_body, var_body, state25, cov225):
         """VOXEL_SLAM::lio_state_estimation (voxelslam.cpp:962-1098).  Returns (ok, state, cov)."""
         pnt_body = _c(pnt_body); var_body = _c(var_body)
         state = _c(state25).copy(); cov = _c(cov225).copy(); ok = C.c_int(0)
-        self._chk(self.lib.vba_odom_lio_state_estimation(self.h, C.c_int(len(pnt_body)), _p(pnt_body), _p(var_body), _p(state), _p(cov), C.byref(ok)))
+        self._chk(self.lib.vba_odom_lio_state_estimation(self.h, len(pnt_body), _p(pnt_body), _p(var_body), _p(state), _p(cov), C.byref(ok)))
         return bool(ok.value), state, cov
 
     def lio_state_estimation_dev(self, n, d_pnt_body, d_var_body, state25, cov225):
         """lio_state_estimation on DEVICE arrays (addresses as integers, e.g. what ScanFrame.prepare returns)."""
         state = _c(state25).copy(); cov = _c(cov225).copy(); ok = C.c_int(0)
-        self._chk(self.lib.vba_odom_lio_state_estimation(self.h, C.c_int(n), C.c_void_p(d_pnt_body), C.c_void_p(d_var_body), _p(state), _p(cov), C.byref(ok)))
+        self._chk(self.lib.vba_odom_lio_state_estimation(self.h, n, C.c_void_p(d_pnt_body), C.c_void_p(d_var_body), _p(state), _p(cov), C.byref(ok)))
         return bool(ok.value), state, cov
 
     def lio_state_estimation_resident(self, n, d_pnt_body, d_var_body, state25, cov225):
@@ -1401,7 +1273,7 @@ class Context:
         read in place.  Returns (ok, state, cov, report) with report a dict: iterations, match_num[4], rot_add[4], tra_add[4] (entries
         of iterations that did not run are zero) and nnt_eig_min."""
         state = _c(state25).copy(); cov = _c(cov225).copy(); ok = C.c_int(0); rep = OdomReport()
-        self._chk(self.lib.vba_odom_lio_state_estimation_resident(self.h, C.c_int(n), C.c_void_p(d_pnt_body), C.c_void_p(d_var_body), _p(state), _p(cov),
+        self._chk(self.lib.vba_odom_lio_state_estimation_resident(self.h, n, C.c_void_p(d_pnt_body), C.c_void_p(d_var_body), _p(state), _p(cov),
                                                                   C.byref(ok), C.byref(rep)))
         report = dict(iterations=rep.iterations, match_num=np.array(rep.match_num[:], dtype=np.int64), rot_add=np.array(rep.rot_add[:]),
                       tra_add=np.array(rep.tra_add[:]), nnt_eig_min=rep.nnt_eig_min)
@@ -1410,7 +1282,7 @@ class Context:
     # ---- multi-GPU / timing
     def lio_state_estimation_kdtree(self, pnt_body, state25, cov225):
         pnt = _c(pnt_body); st = _c(state25).copy(); cov = _c(cov225).copy(); it = C.c_int(0)
-        self._chk(self.lib.vba_odom_lio_state_estimation_kdtree(self.h, C.c_int(len(pnt)), _p(pnt), _p(st), _p(cov), C.byref(it)))
+        self._chk(self.lib.vba_odom_lio_state_estimation_kdtree(self.h, len(pnt), _p(pnt), _p(st), _p(cov), C.byref(it)))
         return it.value, st, cov
 
     def lio_state_estimation_kdtree_resident(self, n, d_pnt_body, state25, cov225):
@@ -1418,7 +1290,7 @@ class Context:
         append and the re-sampling resident on the device.  Returns (iterations, state, cov, report), report as
         in lio_state_estimation_resident (nnt_eig_min is 0: this variant has no nnt)."""
         st = _c(state25).copy(); cov = _c(cov225).copy(); it = C.c_int(0); rep = OdomReport()
-        self._chk(self.lib.vba_odom_lio_state_estimation_kdtree_resident(self.h, C.c_int(n), C.c_void_p(d_pnt_body), _p(st), _p(cov), C.byref(it),
+        self._chk(self.lib.vba_odom_lio_state_estimation_kdtree_resident(self.h, n, C.c_void_p(d_pnt_body), _p(st), _p(cov), C.byref(it),
                                                                          C.byref(rep)))
         report = dict(iterations=rep.iterations, match_num=np.array(rep.match_num[:], dtype=np.int64), rot_add=np.array(rep.rot_add[:]),
                       tra_add=np.array(rep.tra_add[:]), nnt_eig_min=rep.nnt_eig_min)
@@ -1436,8 +1308,8 @@ class Context:
         partial = np.full((nb, 34), np.nan); sums = np.full(34, np.nan); used = C.c_int(-1)
         cand = np.zeros((8, max(n, 1), 5), dtype=np.uint64) if kd else None
         planes = np.full((max(n, 1), 4), np.nan) if kd else None
-        self._chk(self.lib.vba_debug_odom_sums(self.h, C.c_int(self.ODOM_SUMS_KINDS[kind]), C.c_int(n), _p(pnt), None if var is None else _p(var),
-                                               _p(st), _p(cov), C.c_int(slices), _p(partial), _p(sums),
+        self._chk(self.lib.vba_debug_odom_sums(self.h, self.ODOM_SUMS_KINDS[kind], n, _p(pnt), None if var is None else _p(var),
+                                               _p(st), _p(cov), slices, _p(partial), _p(sums),
                                                cand.ctypes.data_as(C.c_void_p) if kd else None, _p(planes) if kd else None, C.byref(used)))
         out = dict(partial=partial, sums=sums)
         if kd:
@@ -1450,11 +1322,11 @@ class Context:
         Returns [n][43] = centre3 | normal3 | radius | plane_var36."""
         rows = _c(rows67).reshape(-1, 67); n = len(rows)
         out = np.full((n, 43), np.nan)
-        self._chk(self.lib.vba_debug_plane_update(self.h, C.c_int(n), _p(rows), _p(out)))
+        self._chk(self.lib.vba_debug_plane_update(self.h, n, _p(rows), _p(out)))
         return out
 
     def kdtree_reserve(self, max_map_points, max_scan_points):
-        self._chk(self.lib.vba_odom_kdtree_reserve(self.h, C.c_int(max_map_points), C.c_int(max_scan_points)))
+        self._chk(self.lib.vba_odom_kdtree_reserve(self.h, max_map_points, max_scan_points))
 
     def kdtree_allocations(self):
         n = C.c_int(); b = C.c_int64()
@@ -1479,8 +1351,8 @@ class Context:
 
     def gba_build(self, clouds, poses, gba_voxel_size, gba_min_eigen_value, gba_eig):
         off, pnt = self._ragged(clouds)
-        self._chk(self.lib.vba_gba_build(self.h, C.c_int(len(clouds)), off.ctypes.data_as(C.POINTER(C.c_int)), _p(pnt), _p(_c(poses)),
-                                         C.c_double(gba_voxel_size), C.c_double(gba_min_eigen_value), _p(_c(gba_eig))))
+        self._chk(self.lib.vba_gba_build(self.h, len(clouds), off.ctypes.data_as(C.POINTER(C.c_int)), _p(pnt), _p(_c(poses)),
+                                         gba_voxel_size, gba_min_eigen_value, _p(_c(gba_eig))))
         return self.size()
 
     def hba_add_edge(self, clouds, poses, gba_voxel_size, gba_min_eigen_value, gba_eig, max_iter, thread_num, want_cloud=True):
@@ -1490,9 +1362,9 @@ class Context:
         edges = np.zeros((W * (W - 1) // 2 + 1, 20)); ne = C.c_int(0)
         cloud = np.zeros((max(len(pnt), 1), 3)); ccnt = np.zeros(max(len(pnt), 1), dtype=np.int32); nc = C.c_int(0)
         rl = np.zeros((max_iter + 1, 2)); nl = C.c_int(0)
-        self._chk(self.lib.vba_hba_add_edge(self.h, C.c_int(W), off.ctypes.data_as(C.POINTER(C.c_int)), _p(pnt), _p(poses),
-                                            C.c_double(gba_voxel_size), C.c_double(gba_min_eigen_value), _p(_c(gba_eig)), C.c_int(max_iter),
-                                            C.c_int(thread_num), _p(edges), C.byref(ne), _p(cloud) if want_cloud else None,
+        self._chk(self.lib.vba_hba_add_edge(self.h, W, off.ctypes.data_as(C.POINTER(C.c_int)), _p(pnt), _p(poses),
+                                            gba_voxel_size, gba_min_eigen_value, _p(_c(gba_eig)), max_iter,
+                                            thread_num, _p(edges), C.byref(ne), _p(cloud) if want_cloud else None,
                                             ccnt.ctypes.data_as(C.POINTER(C.c_int)), C.byref(nc), _p(rl), C.byref(nl)))
         return dict(poses=poses, edges=edges[:ne.value].copy(), cloud=cloud[:nc.value].copy(), cloud_count=ccnt[:nc.value].copy(),
                     resis=rl[:nl.value].copy())
@@ -1507,9 +1379,9 @@ class Context:
         nwin = max(0, (n - wdsize) // mgsize + 1) if n >= wdsize else 0
         cap1 = nwin * (wdsize * (wdsize - 1) // 2) + 1; cap2 = nwin * (nwin - 1) // 2 + 1
         e1 = np.zeros((cap1, 20)); e2 = np.zeros((cap2, 20)); n1 = C.c_int(0); n2 = C.c_int(0)
-        self._chk(self.lib.vba_hba_global(self.h, C.c_int(n), off.ctypes.data_as(C.POINTER(C.c_int)), _p(pnt), _p(_c(poses_x0)), _p(_c(poses_now)),
-                                          C.c_double(gba_voxel_size), C.c_double(gba_min_eigen_value), _p(_c(gba_eig)), C.c_int(total_max_iter),
-                                          C.c_int(wdsize), C.c_int(mgsize), _p(e1), C.c_int(cap1), C.byref(n1), _p(e2), C.c_int(cap2), C.byref(n2)))
+        self._chk(self.lib.vba_hba_global(self.h, n, off.ctypes.data_as(C.POINTER(C.c_int)), _p(pnt), _p(_c(poses_x0)), _p(_c(poses_now)),
+                                          gba_voxel_size, gba_min_eigen_value, _p(_c(gba_eig)), total_max_iter,
+                                          wdsize, mgsize, _p(e1), cap1, C.byref(n1), _p(e2), cap2, C.byref(n2)))
         return e1[:n1.value].copy(), e2[:n2.value].copy()
 
     # ---- diagnostic entries of the any-window path (vba_debug_big_*; tests/test_gpu_big.py)
@@ -1526,7 +1398,7 @@ class Context:
         pcr_add [V][10]) becomes the context's.  raw=True returns the status instead of raising."""
         vptr = self._i32(vptr); efr = self._i32(efr)
         a = [_c(x) for x in (ecl, eig_val, eig_vec, pcr_add)]
-        st = self.lib.vba_debug_big_load(self.h, C.c_int(W), C.c_int(len(vptr) - 1), self._pi(vptr), self._pi(efr), *[_p(x) for x in a])
+        st = self.lib.vba_debug_big_load(self.h, W, len(vptr) - 1, self._pi(vptr), self._pi(efr), *[_p(x) for x in a])
         if raw:
             return st
         self._chk(st)
@@ -1535,8 +1407,8 @@ class Context:
         """vba_debug_big_build: big_build on the clouds, as vba_hba_add_edge runs it for a window of another size -> (V, E)"""
         off, pnt = self._ragged(clouds)
         V = C.c_int(0); E = C.c_int(0)
-        self._chk(self.lib.vba_debug_big_build(self.h, C.c_int(len(clouds)), self._pi(off), _p(pnt), _p(_c(poses)), C.c_double(gba_voxel_size),
-                                               C.c_double(gba_min_eigen_value), _p(_c(gba_eig)), C.byref(V), C.byref(E)))
+        self._chk(self.lib.vba_debug_big_build(self.h, len(clouds), self._pi(off), _p(pnt), _p(_c(poses)), gba_voxel_size,
+                                               gba_min_eigen_value, _p(_c(gba_eig)), C.byref(V), C.byref(E)))
         return V.value, E.value
 
     def debug_big_size(self):
@@ -1558,7 +1430,7 @@ class Context:
         poses = _c(poses); n = 6 * W
         assert poses.size == 12 * W
         H = np.full((n, n), np.nan); g = np.full(n, np.nan); r = C.c_double(np.nan); bd = np.full((W, W, 6), np.nan)
-        self._chk(self.lib.vba_debug_big_hessian(self.h, _p(poses), C.c_int(slices), _p(H), _p(g), C.byref(r), _p(bd)))
+        self._chk(self.lib.vba_debug_big_hessian(self.h, _p(poses), slices, _p(H), _p(g), C.byref(r), _p(bd)))
         return H, g, r.value, bd
 
     def debug_big_residual(self, poses):
@@ -1576,12 +1448,12 @@ class Context:
         e = _c(edges).reshape(-1, 20)
         pr = _c(priors).reshape(-1, 19)
         stats = np.zeros((max(int(n_updates), 1), 3))
-        self._chk(self.lib.vba_pgo_optimize(self.h, C.c_int(len(x)), _p(x), C.c_int(len(e)), _p(e) if len(e) else None, C.c_int(len(pr)),
-                                            _p(pr) if len(pr) else None, C.c_int(int(n_updates)), C.c_double(relin_threshold), _p(stats)))
+        self._chk(self.lib.vba_pgo_optimize(self.h, len(x), _p(x), len(e), _p(e) if len(e) else None, len(pr),
+                                            _p(pr) if len(pr) else None, int(n_updates), relin_threshold, _p(stats)))
         return x, stats
 
     def set_shard(self, rank, n_ranks):
-        self._chk(self.lib.vba_set_shard(self.h, C.c_int(rank), C.c_int(n_ranks)))
+        self._chk(self.lib.vba_set_shard(self.h, rank, n_ranks))
 
     def set_allreduce(self, pyfunc):
         """pyfunc(dev_ptr:int, n_doubles:int, stream:int) -> int; kept alive on the context."""
@@ -1605,7 +1477,7 @@ class Context:
         if world > 1:
             dist.broadcast_object_list(box, src=0)
         uid = C.create_string_buffer(box[0], 128)
-        self._chk(self.lib.vba_rccl_init(self.h, uid, C.c_int(rank), C.c_int(world)))
+        self._chk(self.lib.vba_rccl_init(self.h, uid, rank, world))
 
     def set_torch_allreduce(self, torch, dist):
         """torch.distributed SUM all-reduce (RCCL with backend "nccl", gloo in rehearsals) of the context's device buffers,
@@ -1638,16 +1510,16 @@ class Context:
         self.set_allreduce(hook)
 
     def timing_enable(self, on=True):
-        self.lib.vba_timing_enable(self.h, C.c_int(int(on)))
+        self.lib.vba_timing_enable(self.h, int(on))
 
     def timing_calibration_read(self, n_bytes):
-        self._chk(self.lib.vba_timing_calibration_read(self.h, C.c_size_t(n_bytes)))
+        self._chk(self.lib.vba_timing_calibration_read(self.h, n_bytes))
 
     def timing_select(self, name=None):
         self.lib.vba_timing_select(self.h, name.encode() if name else None)
 
     def timing_sample_every(self, n=1):
-        self.lib.vba_timing_sample_every(self.h, C.c_int(int(n)))
+        self.lib.vba_timing_sample_every(self.h, int(n))
 
     def timing_launch_hessian(self):
         self._chk(self.lib.vba_timing_launch_hessian(self.h))
