@@ -1207,6 +1207,36 @@ int vba_odom_lio_state_estimation_on_state(vba_ctx *ctx, vba_odom_state *st, int
 int vba_map_pvec_update_cut_voxel_on_state(vba_ctx *ctx, vba_odom_state *st, int win_count, int n, const double *d_pnt_body,
                                            const double *d_var_body, int multi);
 
+/* The initialisation odometry on a state object: VOXEL_SLAM::initialization (VS:1450-1534) per scan, after
+ * vba_odom_state_propagate and vba_scan_prepare_on_state. */
+
+/* vba_odom_lio_state_estimation_kdtree_resident (VS:1102-1252) on the state of st and the point-cloud map of ctx.  The image of the
+ * call is built on the device from the state block (P^-1 by the device restatement of the host inverse, every entry divided by 1000,
+ * VS:1135; the first iteration searches): no vba_odom_state_get, no host inverse, no image upload, no vba_odom_state_set.  The
+ * launches behind it are the resident call's.  Crosses the boundary: the arguments in, one download of the result block out; ONE wait,
+ * for that download alone (the copy of x_curr and P back into the state block runs behind it, ordered before whatever reads the block
+ * next).  st holds the updated state and covariance afterwards, state_out [25] (may be NULL) receives the state, the results equal
+ * the resident call's on the values of the block bit for bit.
+ * While the map holds fewer than 100 points the scan only seeds it (VS:1105-1118): the append reads its pose from the block, the
+ * block is not written, *iterations = 0, *report is zeroed; with state_out the 25 doubles of the block are downloaded and that copy
+ * alone is waited for, with state_out == NULL the call returns with everything queued.  n == 0 on a map of 100 points or more:
+ * *iterations = 2, state and covariance keep their bits, the map is re-sampled.
+ * ctx may be another context of the state's device, sharded or not (the point-cloud map is not sharded).  VBA_ERR_BAD_ARG before any
+ * device work, st untouched: a NULL ctx, st or iterations; n < 0; n > 0 with a NULL array; a state on another device.
+ * VBA_ERR_CAPACITY as the resident call.  The scratch is the resident call's: vba_odom_kdtree_reserve and
+ * vba_odom_kdtree_allocations cover this call. */
+int vba_odom_lio_state_estimation_kdtree_on_state(vba_ctx *ctx, vba_odom_state *st, int n, const double *d_pnt_body, int *iterations,
+                                                  vba_odom_report *report, double *state_out);
+/* The published scan of pub_localtraj (VS:37-45): for the n DEVICE points world = x_curr.R p + x_curr.p with the pose read from the
+ * state block on the device, in the order of vba_kf_export_world, ((R[r][0] x + R[r][1] y) + R[r][2] z) + t[r], every product and
+ * sum rounded on its own, each coordinate narrowed to float once; xyzi receives n records x y z intensity of 16 bytes.  *n_out = n.
+ * xyzi is HOST memory (the records pass through ctx's staging buffer, ONE synchronise) or DEVICE memory (16-byte aligned; the call
+ * is stream-ordered and returns with the work queued, no wait).  Crosses the boundary: nothing but the arguments and, to a host
+ * xyzi, the records.  n == 0 succeeds and does nothing.  VBA_ERR_BAD_ARG, nothing queued and xyzi untouched: cap < n, a NULL
+ * argument with n > 0, a NULL ctx, st or n_out, n < 0, a state on another device, a misaligned device xyzi. */
+int vba_odom_state_export_scan(vba_ctx *ctx, vba_odom_state *st, int n, const double *d_pnt_body, float intensity, int64_t cap,
+                               float *xyzi, int64_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -624,11 +624,41 @@ class OdomState {
   void pvec_update_cut_voxel_multi(Context &ctx, const ScanView &scan, int win_count) {
     check(ctx.get(), vba_map_pvec_update_cut_voxel_on_state(ctx.get(), s_, win_count, scan.n, scan.pnt, scan.var, 1));
   }
+  // lio_state_estimation_kdtree (VS:1102-1252) on the resident state and ctx's point-cloud map: returns the iterations,
+  // 0 while the scan only seeds the map; x_out, when given, receives the state (not its covariance) after a seeding scan as well
+  int lio_state_estimation_kdtree(Context &ctx, const ScanView &scan, vba_odom_report *report = nullptr, IMUST *x_out = nullptr) {
+    int iters = 0;
+    check(ctx.get(), vba_odom_lio_state_estimation_kdtree_on_state(ctx.get(), s_, scan.n, scan.pnt, &iters, report, x_out ? &x_out->t : nullptr));
+    return iters;
+  }
+  // the scan that pub_localtraj publishes (VS:37-45): pvec_update's pwld in the pose of the resident state, records x y z intensity
+  void export_scan(Context &ctx, const ScanView &scan, float intensity, std::vector<float> &xyzi) {
+    int64_t n = 0;
+    xyzi.resize((size_t)scan.n * 4);
+    check(ctx.get(), vba_odom_state_export_scan(ctx.get(), s_, scan.n, scan.pnt, intensity, scan.n, xyzi.data(), &n));
+  }
   vba_odom_state *get() const { return s_; }
  private:
   vba_ctx *ctx_;
   vba_odom_state *s_ = nullptr;
 };
+
+// ResultOutput::pub_localtraj (VS:32-58) on a state object: publish_scan(const float *xyzi, int64_t n) receives the scan in world
+// coordinates (VS:37-46), then the path point of VS:48-56 is built from x_curr (the state_out of the update: host bookkeeping) and
+// appended to pcl_path, which publish_path receives whole (VS:57).
+struct PathPoint { float x, y, z, intensity, curvature; };
+template <class PublishScan, class PublishPath>
+inline void pub_localtraj(Context &ctx, OdomState &st, const ScanView &scan, double jour, const IMUST &x_curr, int cur_session,
+                          std::vector<PathPoint> &pcl_path, PublishScan &&publish_scan, PublishPath &&publish_path) {
+  std::vector<float> pl;
+  st.export_scan(ctx, scan, 0.0f, pl);
+  publish_scan((const float *)pl.data(), (int64_t)scan.n);
+  PathPoint ap;
+  ap.x = (float)x_curr.p[0]; ap.y = (float)x_curr.p[1]; ap.z = (float)x_curr.p[2];
+  ap.curvature = (float)jour; ap.intensity = (float)cur_session;
+  pcl_path.push_back(ap);
+  publish_path(pcl_path);
+}
 
 // class IMUEKF (ekf_imu.hpp, "EK"): its fields and call surface without the point loop of the undistortion (EK:135-163), which is
 // ScanFrame::prepare.  A deque holds ImuSample values where the reference holds sensor_msgs::Imu::Ptr.

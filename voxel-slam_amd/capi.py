@@ -669,6 +669,31 @@ class OdomState(_Handle):
         ctx._chk(self.lib.vba_map_pvec_update_cut_voxel_on_state(ctx.h, self.h, win_count, n, C.c_void_p(d_pnt_body),
                                                                  C.c_void_p(d_var_body), int(multi)))
 
+    def lio_state_estimation_kdtree(self, ctx, n, d_pnt_body, want_state=True):
+        """Context.lio_state_estimation_kdtree_resident on the resident state and ``ctx``'s point-cloud map:
+        (iterations, report, state or None); the state object holds state and covariance afterwards.  A seeding call (map below 100
+        points) returns 0 iterations and, with want_state=False, without waiting."""
+        ctx = ctx or self.ctx
+        it = C.c_int(0); rep = OdomReport(); st = np.zeros(25) if want_state else None
+        ctx._chk(self.lib.vba_odom_lio_state_estimation_kdtree_on_state(ctx.h, self.h, n, C.c_void_p(d_pnt_body), C.byref(it), C.byref(rep), _p(st)))
+        report = dict(iterations=rep.iterations, match_num=np.array(rep.match_num[:], dtype=np.int64), rot_add=np.array(rep.rot_add[:]),
+                      tra_add=np.array(rep.tra_add[:]), nnt_eig_min=rep.nnt_eig_min)
+        return it.value, report, st
+
+    def export_scan(self, ctx, n, d_pnt_body, intensity=0.0, out=None):
+        """pub_localtraj's scan (VS:37-45): the n device points in the pose of the resident state as float32 [n][4] records
+        x y z intensity.  With ``out`` (the address of a 16-byte aligned DEVICE buffer of n records) the call is stream-ordered, does
+        not synchronise and returns the record count."""
+        ctx = ctx or self.ctx
+        m = C.c_int64()
+        head = (ctx.h, self.h, n, C.c_void_p(d_pnt_body), intensity, n)
+        if out is not None:
+            ctx._chk(self.lib.vba_odom_state_export_scan(*head, out if isinstance(out, C.c_void_p) else C.c_void_p(int(out)), C.byref(m)))
+            return m.value
+        res = np.zeros((max(n, 1), 4), dtype=np.float32)
+        ctx._chk(self.lib.vba_odom_state_export_scan(*head, res.ctypes.data_as(C.c_void_p), C.byref(m)))
+        return res[:m.value].copy()
+
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 

@@ -7,8 +7,8 @@
 //
 // Every kernel is a thin wrapper over a __device__ body.  The k_kd_*_dev wrappers belong to the device-resident loop:
 // they read the pose from the loop's device state, and first of all its `done` flag (and, the search and the fit, its `refind` flag),
-// returning at once when there is nothing to do.  k_kd_append takes the pose by value: it seeds the map before any loop has run.  No
-// atomics.
+// returning at once when there is nothing to do.  k_kd_append takes the pose by value: it seeds the map before any loop has run, and
+// k_kd_append_blk reads it from a state block in HBM.  No atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vba_common.hpp"
@@ -239,6 +239,15 @@ __global__ __launch_bounds__(256) void k_kd_accum_dev(const vbh::OdomEkf *__rest
 // after the loop: x_curr is final whether or not `done` is set
 __global__ void k_kd_append_dev(const vbh::OdomEkf *__restrict__ S, int n, const double *__restrict__ pts, double *__restrict__ tree_out) {
   kd_append_body(n, pts, kd_pose_of(S), tree_out);
+}
+// the seeding append on a state resident in HBM: the pose is x_curr of the state block [state 25 | P 225], wave-uniform
+__global__ void k_kd_append_blk(const double *__restrict__ blk, int n, const double *__restrict__ pts, double *__restrict__ tree_out) {
+  KdPose X;
+#pragma unroll
+  for (int k = 0; k < 9; k++) X.R[k] = odom_uniform(blk[1 + k]);
+#pragma unroll
+  for (int k = 0; k < 3; k++) X.t[k] = odom_uniform(blk[10 + k]);
+  kd_append_body(n, pts, X, tree_out);
 }
 
 }  // namespace vba

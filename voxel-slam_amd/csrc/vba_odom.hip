@@ -2,8 +2,9 @@
 // vba_odom_lio_state_estimation_kdtree*) with the kernels of vba_kernels_kd.hpp, compiled here and nowhere else, and
 // the scan-to-map update on the voxel map (vba_odom_lio_state_estimation*, §17), whose kernels the map unit compiles
 // (vba_kernels_odom.hpp) and whose loop it queues (map_odom_resident).  And the odometry state resident in HBM (vba_odom_state_*, the
-// IMU propagation vba_imu_ekf_propagate / vba_odom_state_propagate, the update and the insertion on a state object) with
-// the kernels of vba_kernels_imu_ekf.hpp, compiled here and nowhere else.
+// IMU propagation vba_imu_ekf_propagate / vba_odom_state_propagate, the update and the insertion on a state object; the
+// initialisation odometry and the published scan on a state object) with the kernels of vba_kernels_imu_ekf.hpp,
+// compiled here and nowhere else.
 #include "vba_ctx.hpp"
 #include "vba_kernels_kd.hpp"
 #include "vba_kernels_imu_ekf.hpp"
@@ -129,58 +130,94 @@ static void kd_point_loop(hipStream_t s, const vbh::OdomEkf *d_S, int n, int kd_
   hipLaunchKernelGGL(k_kd_accum_dev, dim3(nb), dim3(256), 0, s, d_S, n, d_pts, (const double *)d_pl, d_part);
 }
 
-// One update on a scan in device memory, c->kd_n + n <= 2^28.  With fewer than 100 map points the scan only seeds the map (VS:1105-1118):
-// the append is enqueued, *ran stays false and nothing is waited for.  Otherwise state and cov are updated, the call has completed on
-// return and c->h_odom holds the loop's result block.  Nothing here touches c->d_stage: a caller may keep the scan there.
+// One update on a scan in device memory, c->kd_n + n <= 2^28, in three parts that the host-fed form (kd_odom_core) and the form on a
+// state resident in HBM (vba_odom_lio_state_estimation_kdtree_on_state) share: kd_odom_ensure sizes the map halves and
+// the scratch and says whether the scan only seeds the map (fewer than 100 map points, VS:1105-1118); kd_odom_queue queues the loop,
+// the append and the re-sampling behind an image that is on the device by then; kd_odom_finish takes the new map size from the
+// downloaded result block.
+struct KdPlan {
+  int nb, kd_slices;
+  size_t tot;
+  bool seed, det;
+  int *d_cnt, *d_first;
+  double *d_pl, *d_part;
+  unsigned long long *d_cand;
+  DsWork w;
+};
+static int kd_odom_ensure(vba_ctx *c, int n, KdPlan &p) {
+  p = KdPlan{};
+  p.nb = (n + 255) / 256; p.kd_slices = kd_slices_of(p.nb);
+  p.tot = (size_t)c->kd_n + (size_t)n;
+  int st = kd_reserve(c, p.tot + 16);
+  if (st) return st;
+  p.seed = c->kd_n < 100;
+  if (p.seed) return VBA_OK;
+  if ((st = odom_image_ensure(c)) || (st = kd_scan_ensure(c, (size_t)n)) || (st = kd_ws_ensure(c, p.tot))) return st;
+  p.det = c->opt.deterministic != 0;
+  p.d_cnt = (int *)c->d_kdws.p; p.d_first = (int *)(c->d_kdws + kd_up(c->kdws_pts * sizeof(int)));
+  char *ws = c->d_kdws + 2 * kd_up(c->kdws_pts * sizeof(int));
+  if (2 * kd_up(c->kdws_pts * sizeof(int)) + kf_ws_layout(c, (int)p.tot, p.det, ws, &p.w, &st) > c->d_kdws.n || st) return st ? st : VBA_ERR_CAPACITY;
+  const KdScanLayout L = kd_scan_layout(c->kdscan_pts);
+  p.d_pl = (double *)c->d_kdscan.p; p.d_part = (double *)(c->d_kdscan + L.o_part);
+  p.d_cand = (unsigned long long *)(c->d_kdscan + L.o_cand);
+  return VBA_OK;
+}
+static int kd_odom_queue(vba_ctx *c, int n, const double *d_pts, KdPlan &p) {
+  vbh::OdomEkf *d_S = c->d_odom;
+  hipStream_t s = c->stream;
+  double *tree = c->d_kdtree[c->kd_cur], *tree_out = c->d_kdtree[c->kd_cur ^ 1];
+  for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
+    if (n > 0) kd_point_loop(s, d_S, n, p.kd_slices, d_pts, c->kd_n, tree, p.d_cand, p.d_pl, p.d_part);
+    // n == 0: nb == 0 and d_part may be NULL (no scan scratch was ever needed); the reduction reads nb * 34 doubles, that is none
+    hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, s, d_S, (const double *)p.d_part, p.nb, iter, 1);
+  }
+  // map update VS:1238-1250: the scan appended in the refined pose, map + scan re-sampled on a 0.5 m grid into the other half; the
+  // voxel count lands in the result block
+  if (n > 0) hipLaunchKernelGGL(k_kd_append_dev, dim3(p.nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, tree + (size_t)c->kd_n * 3);
+  p.w.n_out = &d_S->n_map;
+  int st;
+  if ((st = ds_core(c, s, 0, (int)p.tot, tree, nullptr, 9, 4, 0.5, p.det, p.w))) return st;
+  hipLaunchKernelGGL(k_ds_emit, dim3(((int)p.tot + 255) / 256), dim3(256), 0, s, (int)p.tot, (const DsSlot *)p.w.tab, (const int *)p.w.slot, (const int *)p.w.blk, tree_out,
+                     p.d_cnt, p.d_first, (double *)nullptr, 0);
+  HIPCHK(c, hipGetLastError());
+  return VBA_OK;
+}
+// c->h_odom holds the result block of the loop that kd_odom_queue queued
+static int kd_odom_finish(vba_ctx *c, const KdPlan &p) {
+  const vbh::OdomEkf &S = *c->h_odom;
+  if (S.n_map < 1 || (size_t)S.n_map > p.tot) { c->set_error("kd-tree odometry: voxel count of the re-sampled map out of range"); return VBA_ERR_HIP; }
+  c->kd_cur ^= 1; c->kd_n = S.n_map;
+  return VBA_OK;
+}
+
+// The host-fed form.  When the scan only seeds the map the append is enqueued, *ran stays false and nothing is waited for.  Otherwise
+// state and cov are updated, the call has completed on return and c->h_odom holds the loop's result block.  Nothing here touches
+// c->d_stage: a caller may keep the scan there.
 static int kd_odom_core(vba_ctx *c, int n, const double *d_pts, double *state, double *cov, bool *ran) {
   *ran = false;
-  const int nb = (n + 255) / 256, kd_slices = kd_slices_of(nb);
-  const size_t tot = (size_t)c->kd_n + (size_t)n;
-  int st = kd_reserve(c, tot + 16);
+  KdPlan p;
+  int st = kd_odom_ensure(c, n, p);
   if (st) return st;
-  if (c->kd_n < 100) {
+  if (p.seed) {
     if (n > 0) {
       KdPose X;
       std::memcpy(X.R, state + 1, sizeof(X.R)); std::memcpy(X.t, state + 10, sizeof(X.t));
-      hipLaunchKernelGGL(k_kd_append, dim3(nb), dim3(256), 0, c->stream, n, d_pts, X, c->d_kdtree[c->kd_cur] + (size_t)c->kd_n * 3);
+      hipLaunchKernelGGL(k_kd_append, dim3(p.nb), dim3(256), 0, c->stream, n, d_pts, X, c->d_kdtree[c->kd_cur] + (size_t)c->kd_n * 3);
       HIPCHK(c, hipGetLastError());
     }
     c->kd_n += n;
     return VBA_OK;
   }
-  if ((st = odom_image_ensure(c)) || (st = kd_scan_ensure(c, (size_t)n)) || (st = kd_ws_ensure(c, tot))) return st;
-  const bool det = c->opt.deterministic != 0;
-  int *d_cnt = (int *)c->d_kdws.p, *d_first = (int *)(c->d_kdws + kd_up(c->kdws_pts * sizeof(int)));
-  char *ws = c->d_kdws + 2 * kd_up(c->kdws_pts * sizeof(int));
-  DsWork w{};
-  if (2 * kd_up(c->kdws_pts * sizeof(int)) + kf_ws_layout(c, (int)tot, det, ws, &w, &st) > c->d_kdws.n || st) return st ? st : VBA_ERR_CAPACITY;
-  const KdScanLayout L = kd_scan_layout(c->kdscan_pts);
-  double *d_pl = (double *)c->d_kdscan.p, *d_part = (double *)(c->d_kdscan + L.o_part);
-  unsigned long long *d_cand = (unsigned long long *)(c->d_kdscan + L.o_cand);
   vbh::OdomEkf &S = *c->h_odom;
   odom_image_begin(S, state, cov, true);
   vbh::OdomEkf *d_S = c->d_odom;
   hipStream_t s = c->stream;
-  double *tree = c->d_kdtree[c->kd_cur], *tree_out = c->d_kdtree[c->kd_cur ^ 1];
   HIPCHK(c, hipMemcpyAsync(d_S, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
-  for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
-    if (n > 0) kd_point_loop(s, d_S, n, kd_slices, d_pts, c->kd_n, tree, d_cand, d_pl, d_part);
-    // n == 0: nb == 0 and d_part may be NULL (no scan scratch was ever needed); the reduction reads nb * 34 doubles, that is none
-    hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, s, d_S, (const double *)d_part, nb, iter, 1);
-  }
-  // map update VS:1238-1250: the scan appended in the refined pose, map + scan re-sampled on a 0.5 m grid into the other half; the
-  // voxel count lands in the result block
-  if (n > 0) hipLaunchKernelGGL(k_kd_append_dev, dim3(nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, tree + (size_t)c->kd_n * 3);
-  w.n_out = &d_S->n_map;
-  if ((st = ds_core(c, s, 0, (int)tot, tree, nullptr, 9, 4, 0.5, det, w))) return st;
-  hipLaunchKernelGGL(k_ds_emit, dim3(((int)tot + 255) / 256), dim3(256), 0, s, (int)tot, (const DsSlot *)w.tab, (const int *)w.slot, (const int *)w.blk, tree_out, d_cnt,
-                     d_first, (double *)nullptr, 0);
-  HIPCHK(c, hipGetLastError());
+  if ((st = kd_odom_queue(c, n, d_pts, p))) return st;
   const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
   HIPCHK(c, hipMemcpyAsync((char *)&S + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
-  if (S.n_map < 1 || (size_t)S.n_map > tot) { c->set_error("kd-tree odometry: voxel count of the re-sampled map out of range"); return VBA_ERR_HIP; }
-  c->kd_cur ^= 1; c->kd_n = S.n_map;
+  if ((st = kd_odom_finish(c, p))) return st;
   std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
   std::memcpy(cov, S.P_out, sizeof(S.P_out));
   *ran = true;
@@ -525,6 +562,79 @@ int vba_map_pvec_update_cut_voxel_on_state(vba_ctx *c, vba_odom_state *st, int w
   const int r = odom_state_order(st, c->stream, c->err);
   if (r) return r;
   return map_cut_voxel(c->map, c->stream, win_count, n, d_pnt_body, d_var_body, nullptr, multi != 0, c->err, nullptr, st->d_blk.p);
+}
+
+// ---------------------------------------------------------------- the initialisation odometry on a state object
+int vba_odom_lio_state_estimation_kdtree_on_state(vba_ctx *c, vba_odom_state *st, int n, const double *d_pnt_body, int *iterations,
+                                                  vba_odom_report *report, double *state_out) {
+  if (!c || !st || !iterations || n < 0 || (n > 0 && !d_pnt_body) || c->device != st->ctx->device) return VBA_ERR_BAD_ARG;
+  *iterations = 0;
+  if (report) std::memset(report, 0, sizeof(*report));
+  if ((size_t)c->kd_n + (size_t)n > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
+  HIPCHK(c, hipSetDevice(c->device));
+  KdPlan p;
+  int r = kd_odom_ensure(c, n, p);
+  if (r) return r;
+  hipStream_t s = c->stream;
+  if (p.seed) {
+    // the scan only seeds the map: the block is read and not written.  The download of state_out goes ahead of the append, which it
+    // does not depend on, and is all that the host waits for
+    if (state_out && (r = ost_pinned_free(st))) return r;
+    if ((r = odom_state_order(st, s, c->err))) return r;
+    if (state_out) {
+      HIPCHK(c, hipMemcpyAsync(st->h_blk.p, st->d_blk.p, 25 * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIPCHK(c, hipEventRecord(st->res_ev, s));
+    }
+    if (n > 0) {
+      hipLaunchKernelGGL(k_kd_append_blk, dim3(p.nb), dim3(256), 0, s, (const double *)st->d_blk.p, n, d_pnt_body, c->d_kdtree[c->kd_cur] + (size_t)c->kd_n * 3);
+      HIPCHK(c, hipGetLastError());
+    }
+    c->kd_n += n;
+    if (state_out) {
+      HIPCHK(c, hipEventSynchronize(st->res_ev));
+      std::memcpy(state_out, st->h_blk.p, 25 * sizeof(double));
+    }
+    return VBA_OK;
+  }
+  if ((r = odom_state_order(st, s, c->err))) return r;
+  vbh::OdomEkf *d_S = c->d_odom;
+  vbh::OdomEkf &S = *c->h_odom;
+  hipLaunchKernelGGL(k_odom_begin_kd_dev, dim3(1), dim3(256), 0, s, d_S, (const double *)st->d_blk.p);
+  if ((r = kd_odom_queue(c, n, d_pnt_body, p))) return r;
+  // as in vba_odom_lio_state_estimation_on_state: the wait is for the download alone, the copy back into the block runs behind it
+  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
+  HIPCHK(c, hipMemcpyAsync((char *)&S + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipEventRecord(st->res_ev, s));
+  hipLaunchKernelGGL(k_odom_commit_dev, dim3(1), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, st->d_blk.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventSynchronize(st->res_ev));
+  if ((r = kd_odom_finish(c, p))) return r;
+  *iterations = S.iterations;
+  if (report) odom_report_fill(report, S, 0.0);
+  if (state_out) std::memcpy(state_out, &S.x_curr, sizeof(S.x_curr));
+  return VBA_OK;
+}
+
+// pub_localtraj's point loop (VS:37-45) on the scan that the insertion would transform: the pose is read from the state block
+int vba_odom_state_export_scan(vba_ctx *c, vba_odom_state *st, int n, const double *d_pnt_body, float intensity, int64_t cap, float *xyzi,
+                               int64_t *n_out) {
+  if (!c || !st || !n_out || n < 0 || cap < n || (n > 0 && (!d_pnt_body || !xyzi)) || c->device != st->ctx->device) return VBA_ERR_BAD_ARG;
+  *n_out = n;
+  if (n == 0) return VBA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool dev_out = is_device_ptr(xyzi);
+  if (dev_out && ((uintptr_t)xyzi & 15)) { c->set_error("vba_odom_state_export_scan: a device xyzi must be 16-byte aligned"); return VBA_ERR_BAD_ARG; }
+  int r;
+  if (!dev_out && (r = ensure_stage(c, (size_t)n * sizeof(float4)))) return r;
+  if ((r = odom_state_order(st, c->stream, c->err))) return r;
+  float4 *out = dev_out ? (float4 *)xyzi : (float4 *)c->d_stage.p;
+  hipLaunchKernelGGL(k_odom_state_export, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, d_pnt_body, (const double *)st->d_blk.p, intensity, out);
+  HIPCHK(c, hipGetLastError());
+  if (!dev_out) {
+    HIPCHK(c, hipMemcpyAsync(xyzi, out, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return VBA_OK;
 }
 
 }  // extern "C"

@@ -51,6 +51,14 @@
 //           off_time, time_type, filter)], per scan [n_raw, n_words, n_imu, beg_time, x_buf state (25), cov (225)] then the raw message in
 //           n_words doubles (its bytes, padded) and imu[n_imu][7]; output: the initialisation record of mode 3, then per scan
 //           [points kept, retried], then the final map as below
+//   mode 10 (mode 8 with the window's states PRODUCED by the initialisation odometry on a vba::OdomState, VS:1450-1534):
+//           the header and the blocks of mode 8 up to the layout, then ekf noise [12] (cov_gyr, cov_acc, cov_bias_gyr, cov_bias_acc),
+//           x_curr state (25) and cov (225) before the first scan, per scan [n_raw, n_words, n_imu, last_pcl_end_time, pcl_beg_time,
+//           pcl_end_time] then the raw message and imu[n_imu][7].  Per scan: OdomState::propagate, OdomState::prepare at
+//           max(down_size, 0.5) with min_points 0, OdomState::lio_state_estimation_kdtree (x_out -> x_buf), vba::pub_localtraj,
+//           IMU_PRE::push_imu, InitWindow::push; then the InitWindow overload of motion_init and OdomState::set(x_buf.back()).
+//           output: the initialisation record of mode 3 (converge_flag is recorded, not required), then per scan [iterations,
+//           state (25), points kept, retried, records published, sum of their float bits as integers], then the final map as below
 //   output: per optimised window [scan index, W x 25 states, v6[6]] ... then [-1, n_leaves] leaf dump [n][39] plane_var dump [n][86]
 #include "../../include/voxelba_adapter.hpp"
 #include <cmath>
@@ -444,6 +452,81 @@ int main(int argc, char **argv) {
       for (int i = 0; i < win_size; i++) out.insert(out.end(), &x_buf[i].t, &x_buf[i].t + 25);
       out.insert(out.end(), kept.begin(), kept.end());
       k_first = n_scans;                                         // the steady-state continuation is mode 3's
+    }
+
+    if (mode == 10) {                                            // initialization() per scan on a state object (VS:1450-1534)
+      Initialization init;
+      init.point_notime = (int)next(); init.dept_err = next(); init.beam_err = next(); init.scale_gravity = scale_gravity = next();
+      std::memcpy(init.noise_meas, noise, 48); std::memcpy(init.noise_walk, noise + 6, 48);
+      IMUST extrin_para;
+      for (int i = 0; i < 9; i++) extrin_para.R[i] = next();
+      for (int i = 0; i < 3; i++) extrin_para.p[i] = next();
+      const double down_size = next();
+      const int min_points = (int)next(), point_filter_num = (int)next();
+      const double blind = next();
+      vba_scan_layout layout;
+      layout.point_step = (int)next(); layout.off_x = (int)next(); layout.off_y = (int)next(); layout.off_z = (int)next();
+      layout.off_intensity = (int)next(); layout.intensity_type = (int)next(); layout.off_time = (int)next(); layout.time_type = (int)next();
+      layout.filter = (int)next();
+      double ekf_noise[12];
+      for (int i = 0; i < 12; i++) ekf_noise[i] = next();
+      IMUST x0;                                                  // x_curr before the first scan
+      std::memcpy(&x0.t, &in.at(q), 25 * sizeof(double)); q += 25;
+      std::memcpy(x0.cov, &in.at(q), 225 * sizeof(double)); q += 225;
+      ScanFrame frame(ctx);
+      InitWindow pl_origs(ctx);
+      OdomState x_dev(ctx);
+      x_dev.set(x0);
+      std::vector<std::vector<ImuSample>> vec_imus(win_size);
+      std::vector<double> beg_times(win_size), per_scan;
+      std::vector<PathPoint> pcl_path;
+      const double downkd = down_size >= 0.5 ? down_size : 0.5;  // VS:1470
+      for (int i = 0; i < win_size; i++) {
+        const int n_raw = (int)next();
+        const size_t n_words = (size_t)next();
+        const int n_imu = (int)next();
+        const double last_end = next(), beg = next(), end = next();
+        if (n_raw < 0 || n_imu < 0 || (size_t)n_raw * (size_t)layout.point_step > n_words * 8 || q + n_words + (size_t)n_imu * 7 > in.size())
+          throw std::runtime_error("mode 10: the raw message or the IMU rows do not fit the input");
+        frame.decode(n_words ? &in[q] : nullptr, n_raw, layout, point_filter_num, blind);     // pcl_handler; `orig` = its cloud (VS:1458)
+        q += n_words;
+        const double *imu = &in[q];
+        vec_imus[i].resize((size_t)n_imu);
+        for (int j = 0; j < n_imu; j++) { std::memcpy(&vec_imus[i][j], &in.at(q), 7 * sizeof(double)); q += 7; }
+        x_dev.propagate(ekf_noise, scale_gravity, n_imu, imu, last_end, beg, end);            // odom_ekf.process (VS:1460)
+        const ScanView scan = x_dev.prepare(ctx, frame, extrin_para, init.point_notime != 0, downkd, init.dept_err, init.beam_err, 0);   // VS:1470-1474
+        IMUST x_curr = x0;                                       // (x_buf keeps the covariance of x0: the state's stays on the device)
+        const int iters = x_dev.lio_state_estimation_kdtree(ctx, scan, nullptr, &x_curr);     // VS:1476
+        int64_t n_pub = 0;
+        unsigned long long sum = 0;
+        pub_localtraj(ctx, x_dev, scan, 0, x_curr, 0, pcl_path, [&](const float *xyzi, int64_t n) {   // VS:1480-1488
+          n_pub = n;
+          for (int64_t e = 0; e < 4 * n; e++) { uint32_t b; std::memcpy(&b, xyzi + e, 4); sum += b; }
+        }, [](const std::vector<PathPoint> &) {});
+        x_buf.push_back(x_curr);
+        if (i > 0) {                                             // VS:1491-1496
+          std::vector<double> t, g, a;
+          for (const ImuSample &m : vec_imus[i]) { t.push_back(m.t); g.insert(g.end(), m.gyr, m.gyr + 3); a.insert(a.end(), m.acc, m.acc + 3); }
+          imu_pre_buf.push_back(new IMU_PRE(x_buf[i - 1].bg, x_buf[i - 1].ba));
+          imu_pre_buf.back()->push_imu((int)t.size(), t.data(), g.data(), a.data(), noise, noise + 6, scale_gravity);
+        }
+        bool retried = false;
+        const int kept = pl_origs.push(frame, down_size, min_points, &retried);               // VS:1499-1512
+        beg_times[i] = beg;
+        per_scan.push_back(iters);
+        per_scan.insert(per_scan.end(), &x_curr.t, &x_curr.t + 25);
+        per_scan.push_back(kept); per_scan.push_back(retried ? 1.0 : 0.0);
+        per_scan.push_back((double)n_pub); per_scan.push_back((double)sum);
+      }
+      IMUST x_curr;
+      const int ok = init.motion_init(pl_origs, vec_imus, beg_times, &hess, voxhess, x_buf, surf_map, pvec_buf, win_size, x_curr, imu_pre_buf,
+                                      extrin_para);                // whether it converges on odometry-produced states is recorded, not required
+      x_dev.set(x_buf.back());
+      out.push_back(-2.0); out.push_back(ok); out.push_back(init.iterations); out.push_back(init.thresholds_left_relaxed);
+      out.insert(out.end(), init.eigvalue, init.eigvalue + 3);
+      for (int i = 0; i < win_size; i++) out.insert(out.end(), &x_buf[i].t, &x_buf[i].t + 25);
+      out.insert(out.end(), per_scan.begin(), per_scan.end());
+      k_first = n_scans;
     }
 
     for (int k = k_first; k < n_scans; k++) {
