@@ -870,6 +870,48 @@ int vba_kf_export_plan(int n_kf, const int *sizes, int64_t interval_size, int ju
 int vba_kf_export_world(vba_ctx *ctx, int n_stores, vba_kf_store *const *stores, const float *intensity /* [n_stores] */, int jump,
                         int64_t begin, int64_t count, float *xyzi /* [count][4], HOST or DEVICE */);
 
+/* ---- The global map voxel-down-sampled: down_sampling_voxel (TL:201-238) over the exported records, at the
+ * stores' current poses, without the records leaving the device.  Overlap between keyframes is removed: one record per voxel.
+ *
+ * The sequence S is exactly the records vba_kf_export_world(ctx, n_stores, stores, intensity, jump, 0, total, ...) would write:
+ * stores in order, every keyframe's stride restarting at its point 0, world = x0.R p + x0.p at the CURRENT x0 in the uncontracted
+ * order stated there, each coordinate narrowed once to float.  S is never written to memory.
+ * Voxel of a record: TL:209-216 on the FLOAT coordinates: per axis loc = (float)(v / voxel_size), loc < 0 -> loc - 1, truncated
+ * toward zero; 21 bits per axis are kept (the packing of every down-sampler of this library; both quirks are the reference's).
+ * Output: one record per voxel, in ascending index of the voxel's FIRST record in S (first-occurrence order):
+ *   x y z      = (float)(s * (1.0 / (double)cnt)), s the f64 sum of the voxel's float coordinates, cnt their number
+ *   intensity  = that of the voxel's first record
+ *   counts[i]  = cnt                                             (counts may be NULL)
+ * Voxels with cnt < min_count (min_count >= 1) are left out, the order of the rest is unchanged; *n_out = the number kept.
+ * Sum order.  vba_options::deterministic = 1: every sum is the chain ((0 + a_0) + a_1) + ... in the order of S, no f64 atomic is
+ * on the path, and the result of a call is a function of its inputs bit for bit.  Default: f64 atomics form the sums, as in every
+ * other down-sampler here, and two calls may differ.  After the narrowing the order is visible only at a float rounding boundary:
+ * two f64 sums of the same cnt < 2^26 floats differ by less than 2 cnt 2^-53 sum|a|, far below half a float ulp, so the two
+ * results are the same float or adjacent floats.
+ * Capacity: more kept voxels than `cap` is VBA_ERR_CAPACITY with *n_out = the number needed, xyzi and counts untouched;
+ * cap == 0 with xyzi == NULL is the size query (VBA_OK, *n_out set).  An S of 2^31 records or more is VBA_ERR_CAPACITY before any
+ * device work (indices into S are 32-bit in the work arrays; indices into the stores and the output are 64-bit).
+ * xyzi [cap][4] and counts [cap] are both HOST or both DEVICE memory (a device xyzi 16-byte aligned).  The work runs on ctx's
+ * stream.  The host needs the count, so every call waits for the stream once; a device result is then written stream-ordered,
+ * without a second wait; a host result passes through the context's staging buffer (whole, 20 bytes per voxel) and the call returns
+ * when it has arrived.
+ * Work arrays: a table of 16-byte slots and the sums (24 bytes per slot), a power of two >= 2 |S| slots of each (no overflow
+ * path), 4 bytes per record, a deterministic context 12 bytes per record and the sort's scratch more.  They belong to the context,
+ * _reserve(max_points) sizes them, the per-keyframe table and the host staging for an S (and a result) of that length, a call that
+ * needs more doubles them after a synchronise, and nothing is allocated per call.  _allocations: allocations made and bytes
+ * requested for this feature so far (cumulative, as vba_scan_frame_allocations); more than 1024 non-empty keyframes grow the
+ * export's table by doubling, which is counted too.
+ * The stores are only read; the locking rule is that of vba_kf_export_world (a device xyzi: until the work on ctx's stream is done).
+ * VBA_ERR_BAD_ARG before any device work, outputs untouched: the argument errors of vba_kf_export_world (n_stores < 1, a NULL
+ * store or intensity, a store of another device), jump < 1, min_count < 1, cap < 0, a NULL n_out, cap > 0 with a NULL xyzi,
+ * voxel_size < 0.001 (the reference leaves such a cloud alone, TL:203: that caller wants vba_kf_export_world), a misaligned device
+ * xyzi, counts on the other side.  Stores without keyframes and empty keyframes are valid: *n_out = 0. */
+int vba_kf_voxel_export_reserve(vba_ctx *ctx, int64_t max_points);
+int vba_kf_voxel_export_allocations(vba_ctx *ctx, int *n_allocs, int64_t *bytes);
+int vba_kf_voxel_export(vba_ctx *ctx, int n_stores, vba_kf_store *const *stores, const float *intensity /* [n_stores] */, int jump,
+                        double voxel_size, int min_count, int64_t cap, float *xyzi /* [cap][4], HOST or DEVICE */,
+                        int *counts /* [cap], same side as xyzi, may be NULL */, int64_t *n_out);
+
 /* ------------------------------------------------------------------------------------------------
  * Loop-closure map: the counterpart of `map_loop` (VS:2601-2625) and loop_update() (VS:1255-1373), the step that
  * carries a loop closure back into local mapping.  A vba_loop_map owns one second voxel map, created from its context's options

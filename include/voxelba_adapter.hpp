@@ -1036,6 +1036,46 @@ inline int pub_globalmap(Context &ctx, const std::vector<KeyframeStore *> &relc_
   return jump;
 }
 
+// Where a result of n records is cut into messages of at most interval_size records: ends[m] = one past the last record of message
+// m.  One final message always follows the full ones; it is empty only when n == 0 (a cloud is published whatever it holds, VS:153).
+inline std::vector<int64_t> voxel_message_ends(int64_t n, int64_t interval_size) {
+  if (n < 0 || interval_size < 1) throw std::invalid_argument("voxel_message_ends");
+  std::vector<int64_t> ends;
+  int64_t b = 0;
+  while (n - b > interval_size) { b += interval_size; ends.push_back(b); }
+  ends.push_back(n);
+  return ends;
+}
+
+// The global map voxel-down-sampled (vba_kf_voxel_export): the records pub_globalmap would publish at `jump`, one per
+// voxel of voxel_size (the centroid; intensity = the id of the voxel's first record), voxels of fewer than min_count records left
+// out, in messages of at most interval_size records (voxel_message_ends).  publish(const float *xyzi, int64_t n) as pub_globalmap;
+// the caller holds mtx_keyframe.  Two device passes: the size query, then the result.  Returns the number of records.
+template <class Publish>
+inline int64_t pub_globalmap_voxel(Context &ctx, const std::vector<KeyframeStore *> &relc_submaps, const std::vector<int> &ids, double voxel_size,
+                                   Publish &&publish, int min_count = 1, int64_t interval_size = 5000000, int jump = 1) {
+  std::vector<vba_kf_store *> stores;
+  std::vector<float> intensity;
+  for (int id : ids) {
+    stores.push_back(relc_submaps.at((size_t)id)->get());
+    intensity.push_back((float)id);                                             // pp.intensity = id, VS:128
+  }
+  int64_t n = 0;
+  std::vector<float> pl;
+  if (!stores.empty()) {
+    check(ctx.get(), vba_kf_voxel_export(ctx.get(), (int)stores.size(), stores.data(), intensity.data(), jump, voxel_size, min_count, 0, nullptr, nullptr, &n));
+    pl.resize((size_t)n * 4);
+    if (n > 0)
+      check(ctx.get(), vba_kf_voxel_export(ctx.get(), (int)stores.size(), stores.data(), intensity.data(), jump, voxel_size, min_count, n, pl.data(), nullptr, &n));
+  }
+  int64_t b = 0;
+  for (int64_t e : voxel_message_ends(n, interval_size)) {
+    publish((const float *)pl.data() + 4 * b, e - b);
+    b = e;
+  }
+  return n;
+}
+
 // ---- loop closure -> local mapping (voxelba.h "Loop-closure map").  The pose algebra runs here, on the host, one
 // separately rounded product and sum after the other in the order  s = a0*b0; s += a1*b1; s += a2*b2  (compile without contraction
 // to keep it so); the device sees poses that are already moved.
@@ -1070,6 +1110,21 @@ struct ScanPose {   // LR:17-34
   ScanPose(const IMUST &x_, std::shared_ptr<PVec> pvec_) : x(x_), pvec(std::move(pvec_)) {}
   void update(const IMUST &dx) { apply_dx(x, dx); }
 };
+
+// ResultOutput::pub_global_path (VS:90-108), host only: one record x y z intensity per ScanPose of every session in `ids`, in that
+// order; x y z = bl->x.p narrowed to float, intensity = the session's id.  (*relc_bl_buf[id]) are session id's scan poses.
+// publish(const float *xyzi, int64_t n) receives the one message.  Returns the number of records.
+template <class Publish>
+inline int64_t pub_global_path(const std::vector<std::vector<ScanPose *> *> &relc_bl_buf, const std::vector<int> &ids, Publish &&publish) {
+  std::vector<float> pl;
+  for (int id : ids)
+    for (const ScanPose *bl : *relc_bl_buf.at((size_t)id)) {
+      pl.push_back((float)bl->x.p[0]); pl.push_back((float)bl->x.p[1]); pl.push_back((float)bl->x.p[2]);
+      pl.push_back((float)id);
+    }
+  publish((const float *)pl.data(), (int64_t)(pl.size() / 4));
+  return (int64_t)(pl.size() / 4);
+}
 
 // `map_loop` (VS:2601-2625): a second voxel map in HBM.  Destroy it before its Context.
 class LoopMap {

@@ -1130,6 +1130,48 @@ class Context:
         self._chk(self.lib.vba_kf_export_world(*args, res.ctypes.data_as(C.c_void_p)))
         return res
 
+    def kf_export_voxel(self, stores, intensity, jump, voxel_size, min_count=1, cap=None, out=None):
+        """vba_kf_voxel_export on this context's stream: the records kf_export_world(stores, intensity, jump) would return, voxel
+        down-sampled at ``voxel_size`` (one record per voxel in first-occurrence order: the centroid, the intensity of the voxel's
+        first record), voxels of fewer than ``min_count`` records left out.  Returns (xyzi float32 [n][4], counts int32 [n]).
+        ``cap`` None = room for every record (the result cannot be longer); a smaller ``cap`` raises VbaError(ERR_CAPACITY) when
+        more voxels are kept.  With ``out`` = (xyzi address, counts address or None) of DEVICE buffers of ``cap`` entries (xyzi
+        16-byte aligned) the result is written there stream-ordered and the call returns n."""
+        inten = np.ascontiguousarray(intensity, dtype=np.float32).ravel()
+        if len(inten) != len(stores):
+            raise ValueError("one intensity per store")
+        if cap is None:
+            if out is not None:
+                raise ValueError("a device result needs its capacity")
+            j = max(int(jump), 1)
+            cap = sum(int(((s.sizes().astype(np.int64) + j - 1) // j).sum()) for s in stores if s is not None)
+        hs = (C.c_void_p * max(len(stores), 1))(*[(s.h.value if s is not None else None) for s in stores])
+        n = C.c_int64(-1)
+        args = (self.h, len(stores), hs, inten.ctypes.data_as(C.POINTER(C.c_float)), int(jump), float(voxel_size), int(min_count), int(cap))
+        if out is not None:
+            self._chk(self.lib.vba_kf_voxel_export(*args, out[0], out[1], C.byref(n)))
+            return n.value
+        xyzi = np.zeros((max(int(cap), 1), 4), dtype=np.float32); cnt = np.zeros(max(int(cap), 1), dtype=np.int32)
+        self._chk(self.lib.vba_kf_voxel_export(*args, xyzi.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return xyzi[:n.value].copy(), cnt[:n.value].copy()
+
+    def kf_export_voxel_size(self, stores, intensity, jump, voxel_size, min_count=1):
+        """the size query of vba_kf_voxel_export (cap 0, no buffers): the number of voxels kf_export_voxel would keep"""
+        inten = np.ascontiguousarray(intensity, dtype=np.float32).ravel()
+        hs = (C.c_void_p * max(len(stores), 1))(*[s.h.value for s in stores])
+        n = C.c_int64(-1)
+        self._chk(self.lib.vba_kf_voxel_export(self.h, len(stores), hs, inten.ctypes.data_as(C.POINTER(C.c_float)), int(jump), float(voxel_size),
+                                               int(min_count), 0, None, None, C.byref(n)))
+        return n.value
+
+    def kf_export_voxel_reserve(self, max_points):
+        self._chk(self.lib.vba_kf_voxel_export_reserve(self.h, int(max_points)))
+
+    def kf_export_voxel_allocations(self):
+        n = C.c_int(); b = C.c_int64()
+        self._chk(self.lib.vba_kf_voxel_export_allocations(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
     def loop_update(self, lm, poses_win, bl_scans=(), bl_poses=None, bl_vars=None, win_scans=None, win_vars=None, dx12=None):
         """loop_update() (VS:1255-1373) on this context's map: adopt ``lm``, insert the buf_lba2loop scans ``bl_scans`` (list of
         [n_i][3] body points, ``bl_vars`` the matching [n_i][9] or None) at ``bl_poses`` [k][12] as fixed points with covariances,

@@ -152,6 +152,15 @@ struct vba_ctx {
   DevMem<char> d_exp;                                   // keyframes
   DevMem<float4> d_expout;                              // records
   std::vector<long long> exp_first; std::vector<int> exp_kbase;   // host scratch: exported points before every keyframe, keyframes before every store
+  // vba_kf_voxel_export: the work arrays of a sequence of up to `pts` records: the table and the sums (slots_of(pts)
+  // entries each), every record's slot, the workgroup counts with the total behind them, the pinned image of that total; a
+  // deterministic context also holds the sort arrays skey | idx | sidx (sort_stride bytes each) | rocPRIM scratch (tmp_bytes) for
+  // `sort_pts` records.  Grow-only; allocs / bytes count these and what a call or reserve adds to the export's table and staging.
+  struct {
+    size_t pts = 0, sort_pts = 0, sort_stride = 0, tmp_bytes = 0;
+    DevMem<char> tab, sort; DevMem<double> sum; DevMem<unsigned int> slot; DevMem<int> blk; PinMem<int> h_n;
+    int allocs = 0; int64_t bytes = 0;
+  } vx;
   // vba_odom_lio_state_estimation_resident: the loop's device state, its pinned image (parameter block up, result
   // block down; also those of the kd-tree variant, §18) and the point loop's workgroup partials; grow-only
   DevMem<vbh::OdomEkf> d_odom; PinMem<vbh::OdomEkf> h_odom;

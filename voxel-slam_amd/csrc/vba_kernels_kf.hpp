@@ -133,4 +133,140 @@ __global__ __launch_bounds__(256) void k_kf_export(long long i0, long long n, in
   }
 }
 
+// Voxel-down-sampled global map (vba_kf_voxel_export): the gather of k_kf_export fused with the voxel filter of
+// down_sampling_voxel (TL:201-238) over the whole sequence S of exported records; S itself is never written.
+// One table row per NON-EMPTY keyframe of all stores in publication order: the records of S before it, the address of its point 0,
+// its current x0, its store's intensity.  Record i of keyframe k is the point  pnt + 3 (i - first) jump.
+struct VxKf { long long first; const double *pnt; double T[12]; float inten; int pad; };     // 120 bytes
+// The table has >= 2 |S| slots, so the slot is lean: the sums live in an array of their own ([slots][3] doubles, indexed as the table).
+struct alignas(16) VxSlot { unsigned long long key; int cnt, first; };                    // key DS_EMPTY when free
+// A count or emit workgroup owns `per` consecutive records (a multiple of 256) and walks them tile by tile; at most kVxBlocks
+// workgroups, so that the exclusive scan of their counts is k_ds_scan at the size it was written for.
+static constexpr int kVxBlocks = 2048;
+
+// last j in [lo, hi] with tab[j].first <= i
+__device__ __forceinline__ int vx_kf_of(long long i, int lo, int hi, const VxKf *__restrict__ tab) {
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[mid].first <= i) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+// record i of S, a record of keyframe *e: x0.R p + x0.p in kf_apply's order, each coordinate narrowed to float once
+__device__ __forceinline__ void vx_world(const VxKf *__restrict__ e, long long i, int jump, float &x, float &y, float &z) {
+  const double *__restrict__ p = e->pnt + 3 * (size_t)((i - e->first) * (long long)jump);
+  double qx, qy, qz;
+  kf_apply(e->T, p[0], p[1], p[2], qx, qy, qz);
+  x = (float)qx; y = (float)qy; z = (float)qz;
+}
+
+__global__ __launch_bounds__(256) void k_vx_clear(VxSlot *__restrict__ tab, size_t cap) {
+  VxSlot s; s.key = DS_EMPTY; s.cnt = 0; s.first = 0x7fffffff;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < cap; i += (size_t)gridDim.x * 256) tab[i] = s;
+}
+
+// One record of S per lane over a capped, strided grid, the keyframe found as k_kf_export finds it (two lanes search the table for
+// the workgroup's first and last record, every lane between them); then the key of TL:209-216 on the FLOAT coordinates, the
+// open-addressing insert, the voxel's count and first record, the record's slot.  mask = slots - 1 (a power of two >= 2 n: the
+// probe always ends).  DET: no f64 atomics, k_vx_sum_det forms the sums.
+template <bool DET>
+__global__ __launch_bounds__(256) void k_vx_insert(long long n, int nkf, const VxKf *__restrict__ kft, int jump, double voxel_size, VxSlot *__restrict__ tab,
+                                                   unsigned int mask, unsigned int *__restrict__ slot_of, double *__restrict__ sum) {
+  __shared__ int s_k[2];
+  const long long step = (long long)gridDim.x * 256;
+  for (long long base = (long long)blockIdx.x * 256; base < n; base += step) {        // (uniform per workgroup: the barriers below are safe)
+    const long long rem = n - base, cnt = rem < 256 ? rem : 256;
+    if (threadIdx.x < 2) s_k[threadIdx.x] = vx_kf_of(base + (threadIdx.x ? cnt - 1 : 0), 0, nkf - 1, kft);
+    __syncthreads();
+    const int lo = s_k[0], hi = s_k[1];
+    __syncthreads();                                          // s_k is rewritten by the next round
+    if ((long long)threadIdx.x < cnt) {
+      const long long i = base + threadIdx.x;
+      float x, y, z;
+      vx_world(kft + vx_kf_of(i, lo, hi, kft), i, jump, x, y, z);
+      const unsigned long long key = ds_pack(ds_axis_key((double)x, voxel_size), ds_axis_key((double)y, voxel_size), ds_axis_key((double)z, voxel_size));
+      unsigned int h = ds_hash(key) & mask;
+      for (;;) {
+        const unsigned long long old = atomicCAS(&tab[h].key, DS_EMPTY, key);
+        if (old == DS_EMPTY || old == key) break;
+        h = (h + 1) & mask;
+      }
+      atomicAdd(&tab[h].cnt, 1);
+      atomicMin(&tab[h].first, (int)i);
+      slot_of[i] = h;
+      if (!DET) {
+        double *__restrict__ s = sum + 3 * (size_t)h;
+        atomicAdd(s, (double)x); atomicAdd(s + 1, (double)y); atomicAdd(s + 2, (double)z);
+      }
+    }
+  }
+}
+
+// Deterministic mode: (slot, record) pairs sorted by slot with the stable radix sort, so a voxel's records are one run of skey in
+// ascending record index.  The lane on the first position of a run adds the run's float coordinates in that order,
+// ((0 + a_0) + a_1) + ..., recomputing each from the store (24 bytes read against the 16 written and 16 read of a kept record, §23).
+__global__ __launch_bounds__(256) void k_vx_sum_det(long long n, const unsigned int *__restrict__ skey, const int *__restrict__ sidx, const VxSlot *__restrict__ tab,
+                                                    int nkf, const VxKf *__restrict__ kft, int jump, double *__restrict__ sum) {
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const unsigned int h = skey[j];
+  if (j > 0 && skey[j - 1] == h) return;
+  const long long end = j + tab[h].cnt;
+  double sx = 0.0, sy = 0.0, sz = 0.0;
+  int k = 0;                                                  // the records ascend, and so do their keyframes
+  for (long long t = j; t < end; t++) {
+    const long long q = sidx[t];
+    k = vx_kf_of(q, k, nkf - 1, kft);
+    float x, y, z;
+    vx_world(kft + k, q, jump, x, y, z);
+    sx += (double)x; sy += (double)y; sz += (double)z;
+  }
+  double *__restrict__ s = sum + 3 * (size_t)h;
+  s[0] = sx; s[1] = sy; s[2] = sz;
+}
+
+// kept voxel = the first record of a voxel with at least min_count records; blk[b] = kept voxels among workgroup b's records
+__global__ __launch_bounds__(256) void k_vx_count(long long n, long long per, const VxSlot *__restrict__ tab, const unsigned int *__restrict__ slot_of,
+                                                  int min_count, int *__restrict__ blk) {
+  __shared__ int wsum[4];
+  const long long a = (long long)blockIdx.x * per, e = a + per < n ? a + per : n;
+  int c = 0;
+  for (long long i = a + threadIdx.x; i < e; i += 256) {
+    const VxSlot s = tab[slot_of[i]];
+    c += (s.first == (int)i && s.cnt >= min_count) ? 1 : 0;
+  }
+  for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) blk[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// stable compaction of the kept voxels in the order of their first records (k_ds_emit's order); blk = the exclusive scan of
+// k_vx_count's counts.  x y z = (float)(sum * (1 / cnt)), the intensity of the first record's store, counts[pos] = cnt.
+__global__ __launch_bounds__(256) void k_vx_emit(long long n, long long per, const VxSlot *__restrict__ tab, const unsigned int *__restrict__ slot_of,
+                                                 const double *__restrict__ sum, int min_count, const int *__restrict__ blk, int nkf,
+                                                 const VxKf *__restrict__ kft, float4 *__restrict__ out, int *__restrict__ counts) {
+  __shared__ int wsum[4];
+  const long long a = (long long)blockIdx.x * per, e = a + per < n ? a + per : n;
+  int pos0 = blk[blockIdx.x];
+  for (long long b0 = a; b0 < e; b0 += 256) {                 // (uniform per workgroup)
+    const long long i = b0 + threadIdx.x;
+    VxSlot s;
+    unsigned int h = 0;
+    bool f = false;
+    if (i < e) { h = slot_of[i]; s = tab[h]; f = s.first == (int)i && s.cnt >= min_count; }
+    int tot;
+    const int r = det_wg_rank(f, wsum, tot);
+    if (f) {
+      const size_t pos = (size_t)(pos0 + r);
+      const double inv = 1.0 / (double)s.cnt;
+      const double *__restrict__ q = sum + 3 * (size_t)h;
+      out[pos] = make_float4((float)(q[0] * inv), (float)(q[1] * inv), (float)(q[2] * inv), kft[vx_kf_of(i, 0, nkf - 1, kft)].inten);
+      if (counts) counts[pos] = s.cnt;
+    }
+    pos0 += tot;
+    __syncthreads();                                          // wsum is rewritten by the next tile
+  }
+}
+
 }  // namespace vba

@@ -786,3 +786,186 @@ int vba_scanlog_export_world(vba_ctx *c, vba_scanlog *l, int64_t first_seq, int 
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ voxel-down-sampled global map (vba_kf_voxel_export)
+namespace {
+
+inline size_t vx_slots(size_t pts) {                         // a power of two >= 2 pts
+  size_t cap = 1024;
+  while (cap < 2 * pts) cap <<= 1;
+  return cap;
+}
+inline unsigned int vx_key_bits(size_t slots) {
+  unsigned int b = 1;
+  while (((size_t)1 << b) < slots) b++;
+  return b;
+}
+
+// what this feature adds to the export's table and staging counts as its own
+struct VxShared {
+  vba_ctx *c; size_t tab, out;
+  explicit VxShared(vba_ctx *c_) : c(c_), tab(c_->d_exp.n), out(c_->d_expout.n) {}
+  ~VxShared() {
+    if (c->d_exp.n != tab) { c->vx.allocs += 1 + vba_ctx::kExpRing; c->vx.bytes += (int64_t)c->d_exp.n * (1 + vba_ctx::kExpRing); }
+    if (c->d_expout.n != out) { c->vx.allocs++; c->vx.bytes += (int64_t)(c->d_expout.n * sizeof(float4)); }
+  }
+};
+
+template <class M>
+int vx_grow(vba_ctx *c, M &m, size_t want) {
+  if (want <= m.n) return VBA_OK;
+  HIPCHK(c, m.ensure(want));
+  c->vx.allocs++; c->vx.bytes += (int64_t)(want * sizeof(*m.p));
+  return VBA_OK;
+}
+
+// the work arrays for a sequence of n records: as they are when they suffice, else doubled until they do, after a synchronise
+int vx_ensure(vba_ctx *c, size_t n, bool exact) {
+  auto &w = c->vx;
+  const bool det = c->opt.deterministic != 0;
+  int st;
+  if (n > w.pts) {
+    size_t m = (exact || !w.pts) ? n : w.pts;
+    while (m < n) m *= 2;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t slots = vx_slots(m);
+    if ((st = vx_grow(c, w.tab, slots * sizeof(VxSlot))) || (st = vx_grow(c, w.sum, slots * 3)) || (st = vx_grow(c, w.slot, m)) ||
+        (st = vx_grow(c, w.blk, (size_t)kVxBlocks + 1)) || (st = vx_grow(c, w.h_n, 1)))
+      return st;
+    w.pts = m;
+  }
+  if (det) {
+    size_t tmp = 0;
+    HIPCHK(c, sort_pairs_u32(nullptr, tmp, nullptr, nullptr, nullptr, nullptr, w.pts, vx_key_bits(vx_slots(w.pts)), c->stream));
+    if (w.sort_pts < w.pts || w.tmp_bytes < tmp) {
+      const size_t stride = (w.pts * sizeof(int) + 255) & ~(size_t)255;
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      w.sort.reset();
+      w.sort_pts = 0;
+      if ((st = vx_grow(c, w.sort, 3 * stride + tmp))) return st;
+      w.sort_pts = w.pts; w.sort_stride = stride; w.tmp_bytes = tmp;
+    }
+  }
+  return VBA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vba_kf_voxel_export_reserve(vba_ctx *c, int64_t max_points) {
+  if (!c || max_points < 0) return VBA_ERR_BAD_ARG;
+  if (max_points >= ((int64_t)1 << 31)) return VBA_ERR_CAPACITY;
+  if (max_points == 0) return VBA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  VxShared shared(c);
+  int st;
+  if ((st = vx_ensure(c, (size_t)max_points, true))) return st;
+  if ((st = exp_ensure_tab(c, 1))) return st;
+  return exp_ensure_out(c, (size_t)max_points + ((size_t)max_points + 3) / 4);     // a host result of max_points voxels: records, then counts
+}
+
+int vba_kf_voxel_export_allocations(vba_ctx *c, int *n_allocs, int64_t *bytes) {
+  if (!c || !n_allocs || !bytes) return VBA_ERR_BAD_ARG;
+  *n_allocs = c->vx.allocs; *bytes = c->vx.bytes;
+  return VBA_OK;
+}
+
+int vba_kf_voxel_export(vba_ctx *c, int n_stores, vba_kf_store *const *stores, const float *intensity, int jump, double voxel_size, int min_count,
+                        int64_t cap, float *xyzi, int *counts, int64_t *n_out) {
+  if (!c || n_stores < 1 || !stores || !intensity || jump < 1 || min_count < 1 || cap < 0 || !n_out || (cap > 0 && !xyzi) || !(voxel_size >= 0.001))
+    return VBA_ERR_BAD_ARG;
+  for (int s = 0; s < n_stores; s++) if (!stores[s] || stores[s]->ctx->device != c->device) return VBA_ERR_BAD_ARG;
+  const bool query = cap == 0 && !xyzi;
+  const bool dev_out = xyzi && is_device_ptr(xyzi);
+  if (dev_out && ((uintptr_t)xyzi & 15)) { c->set_error("vba_kf_voxel_export: a device xyzi must be 16-byte aligned"); return VBA_ERR_BAD_ARG; }
+  if (xyzi && counts && is_device_ptr(counts) != dev_out) { c->set_error("vba_kf_voxel_export: counts must be on the side of xyzi"); return VBA_ERR_BAD_ARG; }
+  // the sequence S: its length and its non-empty keyframes
+  long long total = 0;
+  size_t nk = 0;
+  for (int s = 0; s < n_stores; s++) {
+    const std::vector<int> &off = stores[s]->off;
+    for (size_t k = 0; k + 1 < off.size(); k++)
+      if (off[k + 1] > off[k]) { total += exp_count((long long)off[k + 1] - off[k], jump); nk++; }
+  }
+  if (total >= (1ll << 31) || nk > (size_t)(1 << 30)) return VBA_ERR_CAPACITY;
+  if (total == 0) { *n_out = 0; return VBA_OK; }
+  HIPCHK(c, hipSetDevice(c->device));
+  VxShared shared(c);
+  int st;
+  if ((st = vx_ensure(c, (size_t)total, false))) return st;
+  if ((st = exp_ensure_tab(c, (nk * sizeof(VxKf) + sizeof(ExpKf) - 1) / sizeof(ExpKf)))) return st;
+  // the per-keyframe table through the export's upload ring
+  const int ring = c->exp_next;
+  c->exp_next = (ring + 1) % vba_ctx::kExpRing;
+  HIPCHK(c, hipEventSynchronize(c->exp_ev[ring]));
+  VxKf *h = (VxKf *)c->h_exp[ring].p;
+  {
+    long long first = 0;
+    size_t g = 0;
+    for (int s = 0; s < n_stores; s++) {
+      const vba_kf_store *S = stores[s];
+      for (size_t k = 0; k + 1 < S->off.size(); k++) {
+        if (S->off[k + 1] <= S->off[k]) continue;
+        VxKf &e = h[g++];
+        e.first = first; e.pnt = (const double *)S->d_pnt + 3 * (size_t)S->off[k]; e.inten = intensity[s]; e.pad = 0;
+        std::memcpy(e.T, S->kf[k].x0, 12 * sizeof(double));
+        first += exp_count((long long)S->off[k + 1] - S->off[k], jump);
+      }
+    }
+  }
+  HIPCHK(c, hipMemcpyAsync(c->d_exp, h, nk * sizeof(VxKf), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->exp_ev[ring], c->stream));
+  const VxKf *d_kft = (const VxKf *)c->d_exp.p;
+  auto &w = c->vx;
+  const bool det = c->opt.deterministic != 0;
+  const long long n = total, nb = (n + 255) / 256;
+  const size_t slots = vx_slots((size_t)n);
+  const unsigned int mask = (unsigned int)(slots - 1);
+  VxSlot *tab = (VxSlot *)w.tab.p;
+  const unsigned grid = (unsigned)std::min<long long>(nb, kExpMaxBlocks);
+  hipLaunchKernelGGL(k_vx_clear, dim3((unsigned)std::min<size_t>(slots / 256, 4 * kExpMaxBlocks)), dim3(256), 0, c->stream, tab, slots);
+  if (det) {
+    unsigned int *skey = (unsigned int *)w.sort.p;
+    int *idx = (int *)(w.sort.p + w.sort_stride), *sidx = (int *)(w.sort.p + 2 * w.sort_stride);
+    hipLaunchKernelGGL(k_vx_insert<true>, dim3(grid), dim3(256), 0, c->stream, n, (int)nk, d_kft, jump, voxel_size, tab, mask, w.slot.p, (double *)nullptr);
+    hipLaunchKernelGGL(k_iota, dim3((unsigned)nb), dim3(256), 0, c->stream, idx, (int)n);
+    size_t tmp = w.tmp_bytes;
+    HIPCHK(c, sort_pairs_u32(w.sort.p + 3 * w.sort_stride, tmp, w.slot.p, skey, idx, sidx, (size_t)n, vx_key_bits(slots), c->stream));
+    hipLaunchKernelGGL(k_vx_sum_det, dim3((unsigned)nb), dim3(256), 0, c->stream, n, skey, sidx, tab, (int)nk, d_kft, jump, w.sum.p);
+  } else {
+    HIPCHK(c, hipMemsetAsync(w.sum.p, 0, slots * 3 * sizeof(double), c->stream));
+    hipLaunchKernelGGL(k_vx_insert<false>, dim3(grid), dim3(256), 0, c->stream, n, (int)nk, d_kft, jump, voxel_size, tab, mask, w.slot.p, w.sum.p);
+  }
+  // count, scan, and the one wait of the call: the host needs the number of kept voxels
+  const long long tiles = (nb + kVxBlocks - 1) / kVxBlocks, per = tiles * 256;
+  const int nblk = (int)((nb + tiles - 1) / tiles);
+  int *d_n = w.blk.p + kVxBlocks;
+  hipLaunchKernelGGL(k_vx_count, dim3(nblk), dim3(256), 0, c->stream, n, per, tab, w.slot.p, min_count, w.blk.p);
+  hipLaunchKernelGGL(k_ds_scan, dim3(1), dim3(256), 0, c->stream, nblk, w.blk.p, d_n);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(w.h_n.p, d_n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const long long m = *w.h_n.p;
+  *n_out = m;
+  if (query) return VBA_OK;
+  if (m > cap) return VBA_ERR_CAPACITY;
+  if (m == 0) return VBA_OK;
+  float4 *out = (float4 *)xyzi;
+  int *cnt = counts;
+  if (!dev_out) {
+    if ((st = exp_ensure_out(c, (size_t)m + ((size_t)m + 3) / 4))) return st;
+    out = c->d_expout.p;
+    cnt = counts ? (int *)(out + m) : nullptr;
+  }
+  hipLaunchKernelGGL(k_vx_emit, dim3(nblk), dim3(256), 0, c->stream, n, per, tab, w.slot.p, w.sum.p, min_count, w.blk.p, (int)nk, d_kft, out, cnt);
+  HIPCHK(c, hipGetLastError());
+  if (!dev_out) {
+    HIPCHK(c, hipMemcpyAsync(xyzi, out, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    if (counts) HIPCHK(c, hipMemcpyAsync(counts, cnt, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return VBA_OK;
+}
+
+}  // extern "C"
