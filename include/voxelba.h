@@ -557,6 +557,18 @@ int vba_debug_odom_sums(vba_ctx *ctx, int kind, int n, const double *pnt_body, c
  *   out [n][43]  centre (3) | normal (3) | radius | plane_var (36, row-major)
  * The stream is drained.  VBA_ERR_BAD_ARG with nothing launched: a NULL pointer, n < 1 or n > 2^20. */
 int vba_debug_plane_update(vba_ctx *ctx, int n, const double *in, double *out);
+/* Diagnostic: one update of vba_pgo_optimize with n_updates = 1, every pass read back (tests/test_gpu_pgo_passes.py).  The plan, the
+ * upload and the launches are the functions the production call runs; arguments, validation and error codes are those of
+ * vba_pgo_optimize, and the caller's input arrays are left as given.  Host outputs, each may be NULL:
+ *   slot [m + n_prior][121]  as k_pgo_linearize left them: Hii (36) | Hjj (36) | Hij (36) | gi (6) | gj (6) | cost
+ *   *n_pairs, pairs [<= m][2]  the distinct node pairs (lower id, higher id), in the order of their blocks
+ *   blk [n + n_pairs][36]    the assembled blocks: the n diagonal ones, then one per pair, rows = the lower node id
+ *   g [n][6], dx [n][6]      the assembled gradient and the solved step
+ *   *cost                    k_pgo_cost's sum
+ *   poses_out [n][12]        theta (+) delta (k_pgo_relin as the last update)
+ * The stream is drained. */
+int vba_debug_pgo_step(vba_ctx *ctx, int n, const double *poses, int m, const double *edges, int n_prior, const double *priors,
+                       double *slot, int *n_pairs, int *pairs, double *blk, double *g, double *dx, double *cost, double *poses_out);
 /* Diagnostic: the passes of the any-window path (csrc/vba_kernels_big.hpp) one at a time on the context's sparse store, the store that
  * vba_hba_add_edge builds and optimises whenever wdsize != win_size (tests/test_gpu_big.py).  The store is CSR over voxels, one entry
  * per occupied (voxel, frame).  Every call drains the stream; none touches the context's LM state, its dense factor store or its map.

@@ -277,3 +277,16 @@ def test_debug_plane_update_refuses_without_a_context(capi):
     rows = np.zeros((1, 67)); out = np.full((1, 43), np.nan)
     st = lib.vba_debug_plane_update(None, C.c_int(1), rows.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
     assert st == capi.ERR_BAD_ARG and np.isnan(out).all()
+
+
+def test_debug_pgo_step_is_exported_typed_and_refuses_without_a_context(capi):
+    """the diagnostic entry of tests/test_gpu_pgo_passes.py: declared with the other vba_debug_*, typed from abi.py, and as
+    vba_pgo_optimize it checks its arguments before it touches a device"""
+    from voxel_slam_amd import abi
+    assert abi.PROTOTYPES["vba_debug_pgo_step"] == "i:pipipip" + "p" * 8
+    assert hasattr(capi.Context, "debug_pgo_step")
+    lib = capi.load()
+    poses = np.zeros((1, 12)); pr = np.zeros((1, 19)); slot = np.full((1, 121), np.nan)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    st = lib.vba_debug_pgo_step(None, C.c_int(1), p(poses), C.c_int(0), None, C.c_int(1), p(pr), p(slot), None, None, None, None, None, None, None)
+    assert st == capi.ERR_BAD_ARG and np.isnan(slot).all()

@@ -167,6 +167,29 @@ def test_debug_plane_update_runs_the_production_device_function():
     assert [f for f in sources() if "k_debug_plane_update" in read(f)] == ["vba_kernels_map.hpp", "vba_map.hip"]
 
 
+def test_debug_pgo_step_runs_the_production_plan_and_launches():
+    """vba_debug_pgo_step pins the production pass: the arithmetic is written once, in the host-and-device header that the kernels and
+    the g++ companion both compile; the plan, the upload and the launches of one update are each one function, called by
+    vba_pgo_optimize and by the diagnostic entry"""
+    math, kern, unit = read("vba_pgo_math.hpp"), read("vba_kernels_pgo.hpp"), read("vba_pgo.hip")
+    assert "__global__" not in math and INCLUDE.findall(math) == [] and "hipStream_t" not in math
+    assert "hip" not in read("vba_pgo_plan.hpp") and INCLUDE.findall(read("vba_pgo_plan.hpp")) == []
+    for fn in ("pgo_coeffs", "pgo_exp", "pgo_log", "pgo_jrinv", "pgo_linearize_factor", "pgo_assemble_block", "pgo_ldl6", "pgo_ldl6_solve",
+               "pgo_seg_elim", "pgo_seg_back", "pgo_skel_scatter_block", "pgo_retract"):
+        assert len(re.findall(r"^VBE_HD \w+ %s\(" % fn, math, re.M)) == 1, fn
+        assert [f for f in sources() if re.search(r"^\w[\w ]* %s\(" % fn, read(f), re.M)] == ["vba_pgo_math.hpp"], fn
+    for call in ("pgo_linearize_factor(v, f);", "pgo_assemble_block(v, b);", "pgo_seg_elim(v, s)", "pgo_seg_back(v, s);",
+                 "pgo_skel_scatter_block(v, b);", "pgo_retract(d, v.theta + (size_t)k * 12);"):
+        assert call in kern, call
+    assert "vba_pgo_math.hpp" in INCLUDE.findall(kern) and [f for f in sources() if "vba_pgo_math.hpp" in INCLUDE.findall(read(f))] == ["vba_kernels_pgo.hpp"]
+    assert len(re.findall(r"hipLaunchKernelGGL\(k_pgo_linearize", unit)) == 1 and len(re.findall(r"= pgo_plan\(", unit)) == 1
+    for entry in (r"^int vba_pgo_optimize\(", r"^int vba_debug_pgo_step\("):
+        body = function_body(unit, entry)
+        assert "pgo_prepare(c, n, poses, m, edges, n_prior, priors," in body and "pgo_update(c, v, " in body and "hipLaunchKernelGGL" not in body
+    host = open(os.path.join(os.path.dirname(CSRC), "..", "tests", "host", "pgo_host.cpp")).read()
+    assert "csrc/vba_pgo_math.hpp" in host and "csrc/vba_pgo_plan.hpp" in host
+
+
 # ---------------------------------------------------------------- the BA core's host side (DESIGN.md, "Source layout": voxelba.hip)
 # a macro definition with its continuation lines: (name, body)
 MACRO = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(\w+)((?:[^\n]*\\\n)*[^\n]*)", re.M)

@@ -1392,6 +1392,21 @@ class Context:
         self._chk(self.lib.vba_debug_plane_update(self.h, n, _p(rows), _p(out)))
         return out
 
+    def debug_pgo_step(self, poses, edges, priors):
+        """vba_debug_pgo_step: one update of pgo_optimize (n_updates = 1) with every pass read back; the inputs are left as given.
+        Returns dict(slot [F][121], pairs [P][2] (int32), blk [n + P][36], g [n][6], dx [n][6], cost, poses [n][12] = theta (+) delta)."""
+        x = _c(poses).reshape(-1, 12); n = len(x)
+        e = _c(edges).reshape(-1, 20); m = len(e)
+        pr = _c(priors).reshape(-1, 19)
+        slot = np.full((m + len(pr), 121), np.nan); npairs = C.c_int(-1)
+        pairs = np.full((max(m, 1), 2), -1, dtype=np.int32); blk = np.full((n + m, 36), np.nan)
+        g = np.full((n, 6), np.nan); dx = np.full((n, 6), np.nan); cost = C.c_double(np.nan); out = np.full((n, 12), np.nan)
+        self._chk(self.lib.vba_debug_pgo_step(self.h, n, _p(x), m, _p(e) if m else None, len(pr), _p(pr) if len(pr) else None,
+                                              _p(slot), C.byref(npairs), pairs.ctypes.data_as(C.c_void_p), _p(blk), _p(g), _p(dx),
+                                              C.byref(cost), _p(out)))
+        P = npairs.value
+        return dict(slot=slot, pairs=pairs[:P].copy(), blk=blk[:n + P].copy(), g=g, dx=dx, cost=cost.value, poses=out)
+
     def kdtree_reserve(self, max_map_points, max_scan_points):
         self._chk(self.lib.vba_odom_kdtree_reserve(self.h, max_map_points, max_scan_points))
 
