@@ -135,6 +135,56 @@ def test_cycles_leave_no_device_memory_behind(inputs):
     assert drift <= PARENT_DRIFT + GRANULE
 
 
+# ---------------------------------------------------------------- the satellites' state ("Source layout": where state lives)
+# (allocations, bytes) of vba_kf_voxel_export_allocations and of vba_odom_kdtree_allocations after the sequence of
+# test_destroy_right_after_one_export, returned by the parent commit's library (the fields still members of vba_ctx) on the same
+# MI355X in the same visit as this commit's: the sequence adds nothing to either counter
+PARENT_VOXEL_EXPORT_ALLOCATIONS = (0, 0)
+PARENT_KDTREE_ALLOCATIONS = (0, 0)
+
+
+def test_context_without_a_satellite_call(inputs):
+    """created and destroyed with its satellite state never touched: the state is made and released with the context"""
+    capi = inputs["capi"]
+    opt = capi.options_from_workload(inputs["wl"])
+    opt.device = 0
+    hip, free = None, []
+    for _ in range(3):
+        ctx = capi.Context(opt)
+        assert ctx.h
+        ctx.close()
+        hip = hip or _hip()
+        free.append(_free_bytes(hip))
+    print("free bytes after each destroy: %s" % free)
+    assert free[1] - free[2] <= GRANULE
+
+
+def test_destroy_right_after_one_export(inputs):
+    """one vba_kf_export_world of a single keyframe of 64 points to host memory, so that the export's ring, its events, the table and
+    the staging exist, and the destroy straight after it: the events go with the satellite state, not by a list in vba_destroy"""
+    capi = inputs["capi"]
+    opt = capi.options_from_workload(inputs["wl"])
+    opt.device = 0
+    g = np.arange(4.0) + 0.25
+    pts = np.ascontiguousarray(np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3))     # one point a voxel
+    pose = np.concatenate([np.eye(3).ravel(), np.zeros(3)])[None]
+    hip, free = None, []
+    for _ in range(2):
+        ctx = capi.Context(opt)
+        store = ctx.kf_store()
+        assert store.build([pts], pose, 0.1, id=0)[0] == 64
+        rec = ctx.kf_export_world([store], [1.0], 1)
+        assert rec.shape == (64, 4) and set(map(tuple, rec[:, :3].tolist())) == set(map(tuple, pts.tolist())) and (rec[:, 3] == 1.0).all()
+        vx, kd = ctx.kf_export_voxel_allocations(), ctx.kdtree_allocations()
+        print("voxel export allocations %s (parent %s), kd-tree allocations %s (parent %s)" % (vx, PARENT_VOXEL_EXPORT_ALLOCATIONS, kd, PARENT_KDTREE_ALLOCATIONS))
+        assert vx == PARENT_VOXEL_EXPORT_ALLOCATIONS and kd == PARENT_KDTREE_ALLOCATIONS
+        ctx.close()                                      # (closes the store first)
+        hip = hip or _hip()
+        free.append(_free_bytes(hip))
+    print("free bytes after each destroy: %s" % free)
+    assert free[0] - free[1] <= GRANULE
+
+
 # ---------------------------------------------------------------- the stores with a view beside their owners
 GBA = dict(gba_voxel_size=2.0, gba_min_eigen_value=0.1, gba_eig=[0.25, 0.25, 0.25, 0.25])
 

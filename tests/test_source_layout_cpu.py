@@ -133,6 +133,79 @@ def test_vba_mem_is_a_shared_header_without_kernels():
     assert [f for f in sources() if f != "vba_ctx.hpp" and "vba_stores.hpp" in INCLUDE.findall(read(f))] == []
 
 
+# ---------------------------------------------------------------- where state lives ("Source layout": vba_sat.hpp, the handle headers)
+HANDLE_HEADERS = ["vba_btc_db.hpp", "vba_kf_store.hpp", "vba_odom_state.hpp", "vba_scanlog.hpp"]
+# what the BA core, the map and global BA never see: the satellites' context state, the handle structs and the two headers those pull
+SATELLITE_ONLY = ["vba_sat.hpp"] + HANDLE_HEADERS + ["vba_btcgen.hpp", "vba_scanlog_ring.hpp"]
+# the fields that left vba_ctx for CtxSat
+MOVED_FIELDS = ("d_kdtree kd_n kd_cur d_kdscan kdscan_pts d_kdws kdws_pts kd_allocs kd_bytes d_odom h_odom d_odom_part d_btcq h_btcq d_btccnt "
+                "d_icp h_icp d_icpkey d_icppart d_pgo d_pgoAb h_exp exp_ev exp_next d_exp d_expout exp_first exp_kbase vx d_init").split()
+
+
+def test_the_slow_units_see_no_satellite_state():
+    assert all(os.path.exists(os.path.join(CSRC, h)) for h in SATELLITE_ONLY)
+    for unit in ("voxelba.hip", "vba_hba.hip"):
+        assert sorted(reached(unit) & set(SATELLITE_ONLY)) == [], unit
+    # the map launches k_odom_state_pose: it takes the declaration, not the state
+    assert sorted(reached("vba_map.hip") & set(SATELLITE_ONLY)) == []
+    assert "vba_odom_state_decl.hpp" in INCLUDE.findall(read("vba_map.hip"))
+    decl = read("vba_odom_state_decl.hpp")
+    assert "k_odom_state_pose" in decl and "struct vba_odom_state" not in decl and reached("vba_odom_state_decl.hpp") == set()
+    assert "vba_ctx.hpp" in reached("voxelba.hip") and "vba_ctx.hpp" in reached("vba_hba.hip") and "vba_ctx.hpp" in reached("vba_map.hip")
+
+
+def test_vba_ctx_holds_the_core_context_alone():
+    text = read("vba_ctx.hpp")
+    assert re.search(r"^struct vba_ctx \{", text, re.M) and re.search(r"^\s*CtxSat \*sat = nullptr;", text, re.M)
+    assert re.findall(r"\bstruct\s+(vba_btc_db|vba_kf_store|vba_scanlog|vba_odom_state)\b", text) == []
+    assert [f for f in MOVED_FIELDS if re.search(r"\b%s\b" % f, text)] == []
+    assert len(MOVED_FIELDS) == 30 and re.search(r"\bvx\b", "} vx;") and not re.search(r"\bd_exp\b", "c->d_expout")
+    assert sorted(reached("vba_ctx.hpp") & set(SATELLITE_ONLY)) == [] and "<mutex>" not in text
+    # each handle struct is defined once, in the header named after it
+    for h in HANDLE_HEADERS:
+        struct = re.compile(r"^struct %s \{" % h[:-4], re.M)
+        assert [f for f in sources() if struct.search(read(f))] == [h], h
+    assert "vba_btcgen.hpp" in INCLUDE.findall(read("vba_btc_db.hpp"))
+    assert "vba_scanlog_ring.hpp" in INCLUDE.findall(read("vba_scanlog.hpp")) and "<mutex>" in read("vba_scanlog.hpp")
+
+
+def test_ctx_sat_has_one_header_and_a_host_only_unit():
+    assert [f for f in sources() if re.search(r"\bstruct\s+CtxSat\s*\{", read(f))] == ["vba_sat.hpp"]
+    members = re.findall(r"^  \} (\w+);", read("vba_sat.hpp"), re.M)
+    assert members == ["kd", "odom", "btc", "pgo", "exp", "vx", "init"]
+    assert "__global__" not in read("vba_sat.hip") and "__global__" not in read("vba_sat.hpp")
+    assert [h for h in reached("vba_sat.hip") if h.startswith("vba_kernels_")] == []
+    assert sorted(INCLUDE.findall(read("vba_sat.hip"))) == ["vba_ctx.hpp", "vba_sat.hpp"]
+    for fn in ("ctx_sat_create", "ctx_sat_release"):
+        assert [f for f in sources() if re.search(r"^(?:int|void) %s\(vba_ctx \*c\) \{" % fn, read(f), re.M)] == ["vba_sat.hip"], fn
+        assert len(re.findall(r"\b%s\(c\)" % fn, read("voxelba.hip"))) == 1, fn
+    # the units that read it are the owners of its members
+    users = sorted(u for u in units() if "vba_sat.hpp" in reached(u + ".hip"))
+    assert users == ["vba_btc", "vba_init", "vba_kf", "vba_odom", "vba_pgo", "vba_sat"]
+    m = re.search(r"^DIAG_UNITS\s*=\s*(.*)$", read("Makefile"), re.M)
+    assert m and "vba_sat" not in m.group(1).split()
+
+
+def test_no_kernel_header_reaches_satellite_state_or_a_handle():
+    assert len(kernel_headers()) >= 10
+    assert {h: sorted((reached(h) | {h}) & set(SATELLITE_ONLY)) for h in kernel_headers() if (reached(h) | {h}) & set(SATELLITE_ONLY)} == {}
+    assert {h: INCLUDE.findall(read(h)) for h in HANDLE_HEADERS + ["vba_sat.hpp"] if any(i.startswith("vba_kernels_") for i in reached(h))} == {}
+
+
+def test_vba_destroy_releases_the_satellites_and_names_no_export_event():
+    body = function_body(read("voxelba.hip"), r"^void vba_destroy\(vba_ctx \*c\) \{")
+    assert "delete c;" in body and "hipStreamDestroy" in body
+    assert "exp" not in re.sub(r"//[^\n]*", "", body)            # (no export event, ring or table by any spelling)
+    # every hipEventDestroy that is left is one of the timing spans'
+    assert re.findall(r"hipEventDestroy\(([^)]*)\)", body) == ["s.a", "s.b"]
+    # released after the stream has drained and before it is destroyed
+    sync, rel, gone = body.index("hipStreamSynchronize(c->stream)"), body.index("ctx_sat_release(c)"), body.index("hipStreamDestroy(c->stream)")
+    assert sync < rel < gone < body.index("delete c;")
+    # the export's events go with their struct
+    exp = function_body(read("vba_sat.hpp"), r"^  struct Exp \{")
+    assert re.search(r"~Exp\(\) \{ for \(hipEvent_t e : ev\) if \(e\) hipEventDestroy\(e\); \}", exp)
+
+
 # ---------------------------------------------------------------- launch plumbing ("Source layout": vba_launch.hpp)
 def sources():
     return sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))

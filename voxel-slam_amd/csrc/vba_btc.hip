@@ -1,6 +1,8 @@
 // Loop retrieval of libvoxelba.so (vba_btc_*): the descriptor database, search and ICP over the kernels of
 // vba_kernels_btc.hpp, and the glue around descriptor generation (vba_btcgen.hip, a unit of its own without floating-point contraction).
 #include "vba_ctx.hpp"
+#include "vba_sat.hpp"
+#include "vba_btc_db.hpp"
 #include "vba_kernels_btc.hpp"
 
 #include <hip/hip_runtime.h>
@@ -121,9 +123,9 @@ int btc_enqueue(vba_btc_db *db, const BtcStds &q, int n, const float *pl, int np
   const BtcIndex ix = db->index();
   int *mq = db->d_m, *md = mq + db->mcap, *mf = md + db->mcap, *pq = mf + db->mcap, *pd = pq + db->mcap;
   if (nf > 0) HIPCHK(c, hipMemsetAsync(db->d_votes, 0, (size_t)nf * sizeof(int), c->stream));
-  k_btc_match<true><<<nb, 256, 0, c->stream>>>(n, q, db->d, ix, cf, c->d_btccnt, db->d_total, db->mcap, mq, md, mf, db->d_votes);
-  k_det_scan<<<1, 1024, 0, c->stream>>>(c->d_btccnt, G, db->d_total, -1, 0, 0);
-  k_btc_match<false><<<nb, 256, 0, c->stream>>>(n, q, db->d, ix, cf, c->d_btccnt, db->d_total, db->mcap, mq, md, mf, db->d_votes);
+  k_btc_match<true><<<nb, 256, 0, c->stream>>>(n, q, db->d, ix, cf, c->sat->btc.d_cnt, db->d_total, db->mcap, mq, md, mf, db->d_votes);
+  k_det_scan<<<1, 1024, 0, c->stream>>>(c->sat->btc.d_cnt, G, db->d_total, -1, 0, 0);
+  k_btc_match<false><<<nb, 256, 0, c->stream>>>(n, q, db->d, ix, cf, c->sat->btc.d_cnt, db->d_total, db->mcap, mq, md, mf, db->d_votes);
   k_btc_select<<<1, 256, 0, c->stream>>>(nf, db->cfg.candidate_num, db->mcap, db->d_total, db->d_votes, db->d_cand, db->d_res);
   k_btc_verify<<<db->cfg.candidate_num, 256, 0, c->stream>>>(q, db->d, cf, db->d_total, db->mcap, mq, md, mf, pq, pd, db->d_cand, db->d_res,
                                                              db->d_cres, pl, npl, db->d_pc, db->d_off);
@@ -164,17 +166,17 @@ int btc_search_run(int n_db, vba_btc_db *const *dbs, int n, const double *rows, 
   vba_ctx *c = dbs[0]->ctx;
   // query upload (once) and the shared count scratch
   const size_t qb = btc_pack_bytes(n);
-  if (qb > c->h_btcq.n) {                                          // (the pinned half is made last)
-    c->d_btcq.reset(); c->h_btcq.reset();
+  if (qb > c->sat->btc.h_q.n) {                                          // (the pinned half is made last)
+    c->sat->btc.d_q.reset(); c->sat->btc.h_q.reset();
     size_t nbytes = 1 << 16;
     while (nbytes < qb) nbytes *= 2;
-    HIPCHK(c, c->d_btcq.ensure(nbytes));
-    HIPCHK(c, c->h_btcq.ensure(nbytes));
+    HIPCHK(c, c->sat->btc.d_q.ensure(nbytes));
+    HIPCHK(c, c->sat->btc.h_q.ensure(nbytes));
   }
-  if ((size_t)27 * n > c->d_btccnt.n) {
+  if ((size_t)27 * n > c->sat->btc.d_cnt.n) {
     size_t m = 8192;
     while (m < (size_t)27 * n) m *= 2;
-    HIPCHK(c, c->d_btccnt.ensure(m));
+    HIPCHK(c, c->sat->btc.d_cnt.ensure(m));
   }
   for (int k = 0; k < n_db; k++) {                                // votes sized by the frames pushed so far
     vba_btc_db *db = dbs[k];
@@ -186,9 +188,9 @@ int btc_search_run(int n_db, vba_btc_db *const *dbs, int n, const double *rows, 
       db->vcap = m;
     }
   }
-  btc_pack(n, rows, bits, c->h_btcq);
-  HIPCHK(c, hipMemcpyAsync(c->d_btcq, c->h_btcq, qb, hipMemcpyHostToDevice, c->stream));
-  const BtcStds q = btc_view(n, c->d_btcq);
+  btc_pack(n, rows, bits, c->sat->btc.h_q);
+  HIPCHK(c, hipMemcpyAsync(c->sat->btc.d_q, c->sat->btc.h_q, qb, hipMemcpyHostToDevice, c->stream));
+  const BtcStds q = btc_view(n, c->sat->btc.d_q);
   const int plo = cur->off[cur_frame], npl = cur->off[cur_frame + 1] - plo;
   const float *pl = cur->d_pc ? cur->d_pc + 6 * (size_t)plo : nullptr;
   for (int k = 0; k < n_db; k++) { const int st = btc_enqueue(dbs[k], q, n, pl, npl); if (st) return st; }
@@ -487,33 +489,33 @@ int vba_btc_icp_normal(vba_btc_db *src_db, int src_frame, vba_btc_db *tar_db, in
   int slices = 1;
   while (slices < ntile && nb * slices * 2 <= 1024) slices *= 2;          // ~1024 workgroups on the 1-NN pass
   if (slices > ntile && ntile > 0) slices = ntile;
-  HIPCHK(c, c->d_icp.ensure(1));
-  HIPCHK(c, c->h_icp.ensure(1));
-  if ((size_t)slices * ns > c->d_icpkey.n) {
+  HIPCHK(c, c->sat->btc.d_icp.ensure(1));
+  HIPCHK(c, c->sat->btc.h_icp.ensure(1));
+  if ((size_t)slices * ns > c->sat->btc.d_icpkey.n) {
     size_t m = 65536;
     while (m < (size_t)slices * ns) m *= 2;
-    HIPCHK(c, c->d_icpkey.grow_keep(m, 0, c->stream));
+    HIPCHK(c, c->sat->btc.d_icpkey.grow_keep(m, 0, c->stream));
   }
-  if ((size_t)nb * BTC_ICP_PART > c->d_icppart.n) {
+  if ((size_t)nb * BTC_ICP_PART > c->sat->btc.d_icppart.n) {
     size_t m = 4096;
     while (m < (size_t)nb * BTC_ICP_PART) m *= 2;
-    HIPCHK(c, c->d_icppart.grow_keep(m, 0, c->stream));
+    HIPCHK(c, c->sat->btc.d_icppart.grow_keep(m, 0, c->stream));
   }
   BtcSpan sp(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));       // (the pinned state block may still be in flight from an earlier call)
-  BtcIcpDev *h = c->h_icp;
+  BtcIcpDev *h = c->sat->btc.h_icp;
   std::memset(h, 0, sizeof(*h));
   for (int k = 0; k < 9; k++) h->R[k] = R[k];
   for (int k = 0; k < 3; k++) h->t[k] = t[k];
   h->paras[0] = 0.2; h->paras[1] = 0.2; h->paras[2] = 0.5; h->paras[3] = 3;
-  HIPCHK(c, hipMemcpyAsync(c->d_icp, h, sizeof(*h), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->sat->btc.d_icp, h, sizeof(*h), hipMemcpyHostToDevice, c->stream));
   for (int it = 0; it < 20; it++) {                  // launches after convergence return at once (BtcIcpDev::done)
-    k_btc_icp_nn<<<dim3(nb, slices), 256, 0, c->stream>>>(ns, src, nt, tar, c->d_icp, c->d_icpkey);
-    k_btc_icp_accum<<<nb, 256, 0, c->stream>>>(ns, src, tar, slices, c->d_icpkey, c->d_icp, c->d_icppart);
-    k_btc_icp_step<<<1, 64, 0, c->stream>>>(nb, c->d_icppart, c->d_icp);
+    k_btc_icp_nn<<<dim3(nb, slices), 256, 0, c->stream>>>(ns, src, nt, tar, c->sat->btc.d_icp, c->sat->btc.d_icpkey);
+    k_btc_icp_accum<<<nb, 256, 0, c->stream>>>(ns, src, tar, slices, c->sat->btc.d_icpkey, c->sat->btc.d_icp, c->sat->btc.d_icppart);
+    k_btc_icp_step<<<1, 64, 0, c->stream>>>(nb, c->sat->btc.d_icppart, c->sat->btc.d_icp);
   }
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(h, c->d_icp, sizeof(*h), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h, c->sat->btc.d_icp, sizeof(*h), hipMemcpyDeviceToHost, c->stream));
   sp.end();
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int k = 0; k < 9; k++) R[k] = h->R[k];

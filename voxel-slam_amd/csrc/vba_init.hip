@@ -1,8 +1,11 @@
 // libvoxelba.so: LiDAR-inertial initialisation (vba_init_imu_poses, vba_init_align_gravity, vba_motion_init, and the device-resident
 // window of raw clouds: vba_init_window_*, vba_motion_init_resident).  The kernels of vba_kernels_init.hpp, compiled
-// here and nowhere else; the map is reached through map_* and the down-sampler's pass through ds_core (vba_ctx.hpp), the LI-BA and
+// here and nowhere else; the map is reached through map_* (vba_ctx.hpp) and the down-sampler's pass through ds_core (vba_kf_store_decl.hpp), the LI-BA and
 // the IMU pre-integration of the BA core (voxelba.hip) through the C ABI.
 #include "vba_ctx.hpp"
+#include "vba_sat.hpp"
+#include "vba_kf_store_decl.hpp"
+#include "vba_scan_frame.hpp"
 #include "vba_kernels_init.hpp"
 #include "vba_hostmath.hpp"
 #include "vba_init_window.hpp"
@@ -71,7 +74,7 @@ static bool init_scan_walks(int i, const int *pt_offsets, const int *imu_offsets
   return !point_notime && imu_offsets[i + 1] - imu_offsets[i] > 1 && pt_offsets[i + 1] > pt_offsets[i];
 }
 
-// The body both entry points share, after motion_init_check.  The clouds are host arrays that are uploaded once into d_init
+// The body both entry points share, after motion_init_check.  The clouds are host arrays that are uploaded once into sat->init.d
 // (vba_motion_init), or, with h_pnt == nullptr, the device arrays d_pnt / d_cv read in place (vba_motion_init_resident).  walk [W]
 // holds the walk's two inputs for every scan that init_scan_walks.
 static int motion_init_impl(vba_ctx *c, int W, const int *pt_offsets, const double *h_pnt, const double *h_curv, const double *d_pnt, const double *d_cv,
@@ -136,8 +139,8 @@ static int motion_init_impl(vba_ctx *c, int W, const int *pt_offsets, const doub
   const size_t b_pnt = upload ? (size_t)np * 24 : 0, b_cv = upload ? (size_t)np * 8 : 0, b_pb = (size_t)n_out * 24, b_var = (size_t)n_out * 72,
                b_pose = (size_t)n_pose * INIT_POSE_LEN * 8, b_sc = (size_t)W * sizeof(InitScan), b_nnt = (size_t)(INIT_NNT_WG * 6 + 16) * 8;
   const size_t need = b_pnt + b_cv + b_pb + b_var + b_pose + b_sc + b_nnt + 64;
-  HIPCHK(c, c->d_init.ensure(need));
-  char *base = c->d_init;
+  HIPCHK(c, c->sat->init.d.ensure(need));
+  char *base = c->sat->init.d;
   if (upload) { d_pnt = (double *)base; d_cv = (double *)(base + b_pnt); }
   double *d_pb = (double *)(base + b_pnt + b_cv), *d_var = (double *)(base + b_pnt + b_cv + b_pb), *d_pose = (double *)(base + b_pnt + b_cv + b_pb + b_var);
   InitScan *d_sc = (InitScan *)(base + b_pnt + b_cv + b_pb + b_var + b_pose);

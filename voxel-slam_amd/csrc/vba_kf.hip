@@ -1,6 +1,10 @@
 // Scan pre-processing (vba_scan_*), the keyframe store (vba_kf_*) and the global map export (vba_kf_export_*)
 // of libvoxelba.so: host drivers of the kernels in vba_kernels_scan.hpp and vba_kernels_kf.hpp.
 #include "vba_ctx.hpp"
+#include "vba_sat.hpp"
+#include "vba_kf_store.hpp"
+#include "vba_btc_db.hpp"
+#include "vba_scanlog.hpp"
 #include "vba_kernels_scan.hpp"
 #include "vba_kernels_kf.hpp"
 
@@ -610,26 +614,26 @@ inline long long exp_count(long long size, long long jump) { return (size + jump
 
 // the table of `entries` keyframes: every image of the pinned ring and the device copy
 int exp_ensure_tab(vba_ctx *c, size_t entries) {
-  for (int i = 0; i < vba_ctx::kExpRing; i++)
-    if (!c->exp_ev[i]) HIPCHK(c, hipEventCreateWithFlags(&c->exp_ev[i], hipEventDisableTiming));
-  const size_t have = c->d_exp.n / sizeof(ExpKf);        // the device copy is made last
+  for (int i = 0; i < CtxSat::Exp::kRing; i++)
+    if (!c->sat->exp.ev[i]) HIPCHK(c, hipEventCreateWithFlags(&c->sat->exp.ev[i], hipEventDisableTiming));
+  const size_t have = c->sat->exp.d.n / sizeof(ExpKf);        // the device copy is made last
   if (entries <= have) return VBA_OK;
   size_t m = have ? have : 1024;
   while (m < entries) m *= 2;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->d_exp.reset();
-  for (auto &h : c->h_exp) h.reset();
-  for (auto &h : c->h_exp) HIPCHK(c, h.ensure(m * sizeof(ExpKf)));
-  HIPCHK(c, c->d_exp.ensure(m * sizeof(ExpKf)));
+  c->sat->exp.d.reset();
+  for (auto &h : c->sat->exp.h) h.reset();
+  for (auto &h : c->sat->exp.h) HIPCHK(c, h.ensure(m * sizeof(ExpKf)));
+  HIPCHK(c, c->sat->exp.d.ensure(m * sizeof(ExpKf)));
   return VBA_OK;
 }
 
 int exp_ensure_out(vba_ctx *c, size_t recs) {
-  if (recs <= c->d_expout.n) return VBA_OK;
-  size_t m = c->d_expout.n ? c->d_expout.n : 65536;
+  if (recs <= c->sat->exp.d_out.n) return VBA_OK;
+  size_t m = c->sat->exp.d_out.n ? c->sat->exp.d_out.n : 65536;
   while (m < recs) m *= 2;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, c->d_expout.ensure(m));
+  HIPCHK(c, c->sat->exp.d_out.ensure(m));
   return VBA_OK;
 }
 
@@ -676,8 +680,8 @@ int vba_kf_export_world(vba_ctx *c, int n_stores, vba_kf_store *const *stores, c
   if (!c || n_stores < 1 || !stores || !intensity || jump < 1 || begin < 0 || count < 0 || (count > 0 && !xyzi)) return VBA_ERR_BAD_ARG;
   for (int s = 0; s < n_stores; s++) if (!stores[s] || stores[s]->ctx->device != c->device) return VBA_ERR_BAD_ARG;
   // exported points before every keyframe of the whole sequence (the plan's kf_begin), keyframes before every store
-  std::vector<long long> &first = c->exp_first;
-  std::vector<int> &kbase = c->exp_kbase;
+  std::vector<long long> &first = c->sat->exp.first;
+  std::vector<int> &kbase = c->sat->exp.kbase;
   first.clear(); kbase.clear();
   long long total = 0;
   for (int s = 0; s < n_stores; s++) {
@@ -700,10 +704,10 @@ int vba_kf_export_world(vba_ctx *c, int n_stores, vba_kf_store *const *stores, c
   int st;
   if ((st = exp_ensure_tab(c, (size_t)nk))) return st;
   if (!dev_out && (st = exp_ensure_out(c, (size_t)(count < kExpChunk ? count : kExpChunk)))) return st;
-  const int slot = c->exp_next;
-  c->exp_next = (slot + 1) % vba_ctx::kExpRing;
-  HIPCHK(c, hipEventSynchronize(c->exp_ev[slot]));             // the upload that last read this image (kExpRing calls ago): long done
-  ExpKf *h = (ExpKf *)c->h_exp[slot].p;
+  const int slot = c->sat->exp.next;
+  c->sat->exp.next = (slot + 1) % CtxSat::Exp::kRing;
+  HIPCHK(c, hipEventSynchronize(c->sat->exp.ev[slot]));             // the upload that last read this image (kRing calls ago): long done
+  ExpKf *h = (ExpKf *)c->sat->exp.h[slot].p;
   for (int s = 0; s < n_stores; s++) {
     const vba_kf_store *S = stores[s];
     for (int g = std::max(ka, kbase[s]); g <= kb && g < kbase[s + 1]; g++) {
@@ -713,12 +717,12 @@ int vba_kf_export_world(vba_ctx *c, int n_stores, vba_kf_store *const *stores, c
       std::memcpy(e.T, S->kf[k].x0, 12 * sizeof(double));
     }
   }
-  HIPCHK(c, hipMemcpyAsync(c->d_exp, h, (size_t)nk * sizeof(ExpKf), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->exp_ev[slot], c->stream));
-  const ExpKf *d_tab = (const ExpKf *)c->d_exp.p;
+  HIPCHK(c, hipMemcpyAsync(c->sat->exp.d, h, (size_t)nk * sizeof(ExpKf), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->sat->exp.ev[slot], c->stream));
+  const ExpKf *d_tab = (const ExpKf *)c->sat->exp.d.p;
   for (long long cb = begin; cb < end; cb += dev_out ? count : kExpChunk) {
     const long long ce = dev_out ? end : std::min(end, cb + kExpChunk);
-    float4 *out = dev_out ? (float4 *)xyzi : c->d_expout.p;                     // the record of cb
+    float4 *out = dev_out ? (float4 *)xyzi : c->sat->exp.d_out.p;                     // the record of cb
     for (int s = 0; s < n_stores; s++) {                       // one launch per store: its point array, its intensity, its rows of the table
       const long long a = std::max(cb, first[kbase[s]]), b = std::min(ce, first[kbase[s + 1]]);
       if (a >= b) continue;
@@ -728,7 +732,7 @@ int vba_kf_export_world(vba_ctx *c, int n_stores, vba_kf_store *const *stores, c
                          d_tab + (g0 - ka), (const double *)stores[s]->d_pnt, jump, intensity[s], out + (a - cb));
     }
     HIPCHK(c, hipGetLastError());
-    if (!dev_out) HIPCHK(c, hipMemcpyAsync(xyzi + 4 * (size_t)(cb - begin), c->d_expout, (size_t)(ce - cb) * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    if (!dev_out) HIPCHK(c, hipMemcpyAsync(xyzi + 4 * (size_t)(cb - begin), c->sat->exp.d_out, (size_t)(ce - cb) * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
   }
   if (!dev_out) HIPCHK(c, hipStreamSynchronize(c->stream));
   return VBA_OK;
@@ -746,7 +750,7 @@ int vba_scanlog_export_world(vba_ctx *c, vba_scanlog *l, int64_t first_seq, int 
   ScanLogView v;
   int st = scanlog_view(l, first_seq, k, INT32_MAX, nullptr, &v);   // the sizes first: cap is checked before any device work
   if (st) return st;
-  std::vector<long long> &first = c->exp_first;
+  std::vector<long long> &first = c->sat->exp.first;
   first.clear();
   long long total = 0;
   for (int i = 0; i < k; i++) { first.push_back(total); total += exp_count((long long)v.rel[i + 1] - v.rel[i], stride); }
@@ -758,27 +762,27 @@ int vba_scanlog_export_world(vba_ctx *c, vba_scanlog *l, int64_t first_seq, int 
   if ((st = exp_ensure_tab(c, (size_t)k))) return st;
   if (!dev_out && (st = exp_ensure_out(c, (size_t)(total < kExpChunk ? total : kExpChunk)))) return st;
   if ((st = scanlog_view(l, first_seq, k, INT32_MAX, c->stream, &v))) return st;   // again, now ordering ctx's stream behind the captures
-  const int slot = c->exp_next;
-  c->exp_next = (slot + 1) % vba_ctx::kExpRing;
-  HIPCHK(c, hipEventSynchronize(c->exp_ev[slot]));
-  ExpKf *h = (ExpKf *)c->h_exp[slot].p;
+  const int slot = c->sat->exp.next;
+  c->sat->exp.next = (slot + 1) % CtxSat::Exp::kRing;
+  HIPCHK(c, hipEventSynchronize(c->sat->exp.ev[slot]));
+  ExpKf *h = (ExpKf *)c->sat->exp.h[slot].p;
   for (int i = 0; i < k; i++) {
     h[i].first = first[i]; h[i].row = v.starts[i];
     std::memcpy(h[i].T, poses + 12 * (size_t)i, 12 * sizeof(double));
   }
-  HIPCHK(c, hipMemcpyAsync(c->d_exp, h, (size_t)k * sizeof(ExpKf), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->exp_ev[slot], c->stream));
-  const ExpKf *d_tab = (const ExpKf *)c->d_exp.p;
+  HIPCHK(c, hipMemcpyAsync(c->sat->exp.d, h, (size_t)k * sizeof(ExpKf), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->sat->exp.ev[slot], c->stream));
+  const ExpKf *d_tab = (const ExpKf *)c->sat->exp.d.p;
   for (long long cb = 0; cb < total; cb += dev_out ? total : kExpChunk) {
     const long long ce = dev_out ? total : std::min(total, cb + kExpChunk);
-    float4 *out = dev_out ? (float4 *)xyzi : c->d_expout.p;
+    float4 *out = dev_out ? (float4 *)xyzi : c->sat->exp.d_out.p;
     // the rows of the table that records cb .. ce - 1 can touch: from the last scan with first <= cb
     const int g0 = (int)(std::upper_bound(first.begin(), first.end(), cb) - first.begin()) - 1;
     const long long nb = (ce - cb + 255) / 256;
     hipLaunchKernelGGL(k_kf_export, dim3((unsigned)std::min<long long>(nb, kExpMaxBlocks)), dim3(256), 0, c->stream, cb, ce - cb, k - g0, d_tab + g0, v.d_pnt,
                        stride, intensity, out);
     HIPCHK(c, hipGetLastError());
-    if (!dev_out) HIPCHK(c, hipMemcpyAsync(xyzi + 4 * (size_t)cb, c->d_expout, (size_t)(ce - cb) * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    if (!dev_out) HIPCHK(c, hipMemcpyAsync(xyzi + 4 * (size_t)cb, c->sat->exp.d_out, (size_t)(ce - cb) * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
   }
   if (!dev_out) HIPCHK(c, hipStreamSynchronize(c->stream));
   else if ((st = scanlog_reader_queued(l, c->stream))) return st;   // the gather is still queued: the next push waits for it
@@ -804,10 +808,10 @@ inline unsigned int vx_key_bits(size_t slots) {
 // what this feature adds to the export's table and staging counts as its own
 struct VxShared {
   vba_ctx *c; size_t tab, out;
-  explicit VxShared(vba_ctx *c_) : c(c_), tab(c_->d_exp.n), out(c_->d_expout.n) {}
+  explicit VxShared(vba_ctx *c_) : c(c_), tab(c_->sat->exp.d.n), out(c_->sat->exp.d_out.n) {}
   ~VxShared() {
-    if (c->d_exp.n != tab) { c->vx.allocs += 1 + vba_ctx::kExpRing; c->vx.bytes += (int64_t)c->d_exp.n * (1 + vba_ctx::kExpRing); }
-    if (c->d_expout.n != out) { c->vx.allocs++; c->vx.bytes += (int64_t)(c->d_expout.n * sizeof(float4)); }
+    if (c->sat->exp.d.n != tab) { c->sat->vx.allocs += 1 + CtxSat::Exp::kRing; c->sat->vx.bytes += (int64_t)c->sat->exp.d.n * (1 + CtxSat::Exp::kRing); }
+    if (c->sat->exp.d_out.n != out) { c->sat->vx.allocs++; c->sat->vx.bytes += (int64_t)(c->sat->exp.d_out.n * sizeof(float4)); }
   }
 };
 
@@ -815,13 +819,13 @@ template <class M>
 int vx_grow(vba_ctx *c, M &m, size_t want) {
   if (want <= m.n) return VBA_OK;
   HIPCHK(c, m.ensure(want));
-  c->vx.allocs++; c->vx.bytes += (int64_t)(want * sizeof(*m.p));
+  c->sat->vx.allocs++; c->sat->vx.bytes += (int64_t)(want * sizeof(*m.p));
   return VBA_OK;
 }
 
 // the work arrays for a sequence of n records: as they are when they suffice, else doubled until they do, after a synchronise
 int vx_ensure(vba_ctx *c, size_t n, bool exact) {
-  auto &w = c->vx;
+  auto &w = c->sat->vx;
   const bool det = c->opt.deterministic != 0;
   int st;
   if (n > w.pts) {
@@ -867,7 +871,7 @@ int vba_kf_voxel_export_reserve(vba_ctx *c, int64_t max_points) {
 
 int vba_kf_voxel_export_allocations(vba_ctx *c, int *n_allocs, int64_t *bytes) {
   if (!c || !n_allocs || !bytes) return VBA_ERR_BAD_ARG;
-  *n_allocs = c->vx.allocs; *bytes = c->vx.bytes;
+  *n_allocs = c->sat->vx.allocs; *bytes = c->sat->vx.bytes;
   return VBA_OK;
 }
 
@@ -896,10 +900,10 @@ int vba_kf_voxel_export(vba_ctx *c, int n_stores, vba_kf_store *const *stores, c
   if ((st = vx_ensure(c, (size_t)total, false))) return st;
   if ((st = exp_ensure_tab(c, (nk * sizeof(VxKf) + sizeof(ExpKf) - 1) / sizeof(ExpKf)))) return st;
   // the per-keyframe table through the export's upload ring
-  const int ring = c->exp_next;
-  c->exp_next = (ring + 1) % vba_ctx::kExpRing;
-  HIPCHK(c, hipEventSynchronize(c->exp_ev[ring]));
-  VxKf *h = (VxKf *)c->h_exp[ring].p;
+  const int ring = c->sat->exp.next;
+  c->sat->exp.next = (ring + 1) % CtxSat::Exp::kRing;
+  HIPCHK(c, hipEventSynchronize(c->sat->exp.ev[ring]));
+  VxKf *h = (VxKf *)c->sat->exp.h[ring].p;
   {
     long long first = 0;
     size_t g = 0;
@@ -914,10 +918,10 @@ int vba_kf_voxel_export(vba_ctx *c, int n_stores, vba_kf_store *const *stores, c
       }
     }
   }
-  HIPCHK(c, hipMemcpyAsync(c->d_exp, h, nk * sizeof(VxKf), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipEventRecord(c->exp_ev[ring], c->stream));
-  const VxKf *d_kft = (const VxKf *)c->d_exp.p;
-  auto &w = c->vx;
+  HIPCHK(c, hipMemcpyAsync(c->sat->exp.d, h, nk * sizeof(VxKf), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipEventRecord(c->sat->exp.ev[ring], c->stream));
+  const VxKf *d_kft = (const VxKf *)c->sat->exp.d.p;
+  auto &w = c->sat->vx;
   const bool det = c->opt.deterministic != 0;
   const long long n = total, nb = (n + 255) / 256;
   const size_t slots = vx_slots((size_t)n);
@@ -955,7 +959,7 @@ int vba_kf_voxel_export(vba_ctx *c, int n_stores, vba_kf_store *const *stores, c
   int *cnt = counts;
   if (!dev_out) {
     if ((st = exp_ensure_out(c, (size_t)m + ((size_t)m + 3) / 4))) return st;
-    out = c->d_expout.p;
+    out = c->sat->exp.d_out.p;
     cnt = counts ? (int *)(out + m) : nullptr;
   }
   hipLaunchKernelGGL(k_vx_emit, dim3(nblk), dim3(256), 0, c->stream, n, per, tab, w.slot.p, w.sum.p, min_count, w.blk.p, (int)nk, d_kft, out, cnt);

@@ -1,6 +1,8 @@
 // Loop-closure map of libvoxelba.so (vba_loop_map_*, vba_loop_update): host code over the map's host API (vba_map.hip)
 // and the keyframe store (vba_kf.hip).
 #include "vba_ctx.hpp"
+#include "vba_kf_store.hpp"
+#include "vba_scanlog.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cstdio>

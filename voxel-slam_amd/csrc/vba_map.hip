@@ -2,6 +2,7 @@
 // loop runs the map's point loop), compiled here and nowhere else, and the map_* host functions that launch them; the other units reach
 // the map through the declarations in vba_ctx.hpp.
 #include "vba_ctx.hpp"
+#include "vba_odom_state_decl.hpp"
 #include "vba_kernels_map.hpp"
 #include "vba_kernels_loop.hpp"
 #include "vba_kernels_odom.hpp"

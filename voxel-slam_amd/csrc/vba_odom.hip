@@ -6,6 +6,9 @@
 // initialisation odometry and the published scan on a state object) with the kernels of vba_kernels_imu_ekf.hpp,
 // compiled here and nowhere else.
 #include "vba_ctx.hpp"
+#include "vba_sat.hpp"
+#include "vba_odom_state.hpp"
+#include "vba_kf_store_decl.hpp"
 #include "vba_kernels_kd.hpp"
 #include "vba_kernels_imu_ekf.hpp"
 #include "vba_hostmath.hpp"
@@ -20,23 +23,23 @@ extern "C" {
 
 // ---------------------------------------------------------------- initialisation odometry on a point-cloud map (vba_kernels_kd.hpp)
 static int kd_reserve(vba_ctx *c, size_t pts) {
-  const size_t have = c->d_kdtree[1].n / 3;             // points; the second half grows last
+  const size_t have = c->sat->kd.d_tree[1].n / 3;             // points; the second half grows last
   if (pts <= have) return VBA_OK;
   size_t cap = have ? have : 65536;
   while (cap < pts) cap *= 2;
-  for (int i = 0; i < 2; i++) HIPCHK(c, c->d_kdtree[i].grow_keep(cap * 3, i == c->kd_cur ? (size_t)c->kd_n * 3 : 0, c->stream));
-  c->kd_allocs += 2; c->kd_bytes += (int64_t)(2 * cap * 3 * sizeof(double));
+  for (int i = 0; i < 2; i++) HIPCHK(c, c->sat->kd.d_tree[i].grow_keep(cap * 3, i == c->sat->kd.cur ? (size_t)c->sat->kd.n * 3 : 0, c->stream));
+  c->sat->kd.allocs += 2; c->sat->kd.bytes += (int64_t)(2 * cap * 3 * sizeof(double));
   return VBA_OK;
 }
 // map slices of the 5-NN search for nb workgroups of scan points: enough workgroups to cover the chip
 static int kd_slices_of(int nb) { return nb >= 512 ? 1 : (nb >= 128 ? 4 : 8); }
-int vba_odom_kdtree_reset(vba_ctx *c) { c->kd_n = 0; return VBA_OK; }
-int vba_odom_kdtree_size(vba_ctx *c) { return c->kd_n; }
+int vba_odom_kdtree_reset(vba_ctx *c) { c->sat->kd.n = 0; return VBA_OK; }
+int vba_odom_kdtree_size(vba_ctx *c) { return c->sat->kd.n; }
 int vba_odom_kdtree_points(vba_ctx *c, double *out) {
-  if (!out && c->kd_n > 0) return VBA_ERR_BAD_ARG;
-  if (c->kd_n == 0) return VBA_OK;
+  if (!out && c->sat->kd.n > 0) return VBA_ERR_BAD_ARG;
+  if (c->sat->kd.n == 0) return VBA_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpyAsync(out, c->d_kdtree[c->kd_cur], (size_t)c->kd_n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out, c->sat->kd.d_tree[c->sat->kd.cur], (size_t)c->sat->kd.n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return VBA_OK;
 }
@@ -44,12 +47,12 @@ int vba_odom_kdtree_points(vba_ctx *c, double *out) {
 // ---------------------------------------------------------------- its EKF loop, resident on the device
 // device state and pinned image of the resident EKF loops (this one and the voxel map's)
 static int odom_image_ensure(vba_ctx *c) {
-  if (c->h_odom) return VBA_OK;                         // the pinned image is made last: complete or empty
-  HIPCHK(c, c->d_odom.ensure(1));
-  const hipError_t e = c->h_odom.ensure(1);
-  if (e != hipSuccess) c->d_odom.reset();
+  if (c->sat->odom.h) return VBA_OK;                         // the pinned image is made last: complete or empty
+  HIPCHK(c, c->sat->odom.d.ensure(1));
+  const hipError_t e = c->sat->odom.h.ensure(1);
+  if (e != hipSuccess) c->sat->odom.d.reset();
   HIPCHK(c, e);
-  c->kd_allocs += 2; c->kd_bytes += (int64_t)(2 * sizeof(vbh::OdomEkf));
+  c->sat->kd.allocs += 2; c->sat->kd.bytes += (int64_t)(2 * sizeof(vbh::OdomEkf));
   return VBA_OK;
 }
 // what a resident entry point reports of the loop's result block
@@ -71,30 +74,30 @@ static KdScanLayout kd_scan_layout(size_t p) {
   return L;
 }
 static int kd_scan_ensure(vba_ctx *c, size_t pts) {
-  if (pts <= c->kdscan_pts) return VBA_OK;
-  size_t cap = c->kdscan_pts ? c->kdscan_pts : 16384;
+  if (pts <= c->sat->kd.scan_pts) return VBA_OK;
+  size_t cap = c->sat->kd.scan_pts ? c->sat->kd.scan_pts : 16384;
   while (cap < pts) cap *= 2;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->d_kdscan.reset(); c->kdscan_pts = 0;
+  c->sat->kd.d_scan.reset(); c->sat->kd.scan_pts = 0;
   const size_t b = kd_scan_layout(cap).bytes;
-  HIPCHK(c, c->d_kdscan.ensure(b));
-  c->kdscan_pts = cap; c->kd_allocs++; c->kd_bytes += (int64_t)b;
+  HIPCHK(c, c->sat->kd.d_scan.ensure(b));
+  c->sat->kd.scan_pts = cap; c->sat->kd.allocs++; c->sat->kd.bytes += (int64_t)b;
   return VBA_OK;
 }
 // scratch sized by map + scan of up to p points: the re-sampler's count [p] | first [p] | work area (the deterministic layout, the larger)
 static int kd_ws_ensure(vba_ctx *c, size_t pts) {
-  if (pts <= c->kdws_pts) return VBA_OK;
+  if (pts <= c->sat->kd.ws_pts) return VBA_OK;
   if (pts > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
-  size_t cap = c->kdws_pts ? c->kdws_pts : 65536;
+  size_t cap = c->sat->kd.ws_pts ? c->sat->kd.ws_pts : 65536;
   while (cap < pts) cap *= 2;
   int st = VBA_OK;
   const size_t ws = kf_ws_layout(c, (int)cap, true, nullptr, nullptr, &st);
   if (st) return st;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->d_kdws.reset(); c->kdws_pts = 0;
+  c->sat->kd.d_ws.reset(); c->sat->kd.ws_pts = 0;
   const size_t b = 2 * kd_up(cap * sizeof(int)) + ws;
-  HIPCHK(c, c->d_kdws.ensure(b));
-  c->kdws_pts = cap; c->kd_allocs++; c->kd_bytes += (int64_t)b;
+  HIPCHK(c, c->sat->kd.d_ws.ensure(b));
+  c->sat->kd.ws_pts = cap; c->sat->kd.allocs++; c->sat->kd.bytes += (int64_t)b;
   return VBA_OK;
 }
 
@@ -108,7 +111,7 @@ int vba_odom_kdtree_reserve(vba_ctx *c, int max_map_points, int max_scan_points)
 }
 int vba_odom_kdtree_allocations(vba_ctx *c, int *n_allocs, int64_t *bytes) {
   if (!c || !n_allocs || !bytes) return VBA_ERR_BAD_ARG;
-  *n_allocs = c->kd_allocs; *bytes = c->kd_bytes;
+  *n_allocs = c->sat->kd.allocs; *bytes = c->sat->kd.bytes;
   return VBA_OK;
 }
 
@@ -130,7 +133,7 @@ static void kd_point_loop(hipStream_t s, const vbh::OdomEkf *d_S, int n, int kd_
   hipLaunchKernelGGL(k_kd_accum_dev, dim3(nb), dim3(256), 0, s, d_S, n, d_pts, (const double *)d_pl, d_part);
 }
 
-// One update on a scan in device memory, c->kd_n + n <= 2^28, in three parts that the host-fed form (kd_odom_core) and the form on a
+// One update on a scan in device memory, c->sat->kd.n + n <= 2^28, in three parts that the host-fed form (kd_odom_core) and the form on a
 // state resident in HBM (vba_odom_lio_state_estimation_kdtree_on_state) share: kd_odom_ensure sizes the map halves and
 // the scratch and says whether the scan only seeds the map (fewer than 100 map points, VS:1105-1118); kd_odom_queue queues the loop,
 // the append and the re-sampling behind an image that is on the device by then; kd_odom_finish takes the new map size from the
@@ -147,33 +150,33 @@ struct KdPlan {
 static int kd_odom_ensure(vba_ctx *c, int n, KdPlan &p) {
   p = KdPlan{};
   p.nb = (n + 255) / 256; p.kd_slices = kd_slices_of(p.nb);
-  p.tot = (size_t)c->kd_n + (size_t)n;
+  p.tot = (size_t)c->sat->kd.n + (size_t)n;
   int st = kd_reserve(c, p.tot + 16);
   if (st) return st;
-  p.seed = c->kd_n < 100;
+  p.seed = c->sat->kd.n < 100;
   if (p.seed) return VBA_OK;
   if ((st = odom_image_ensure(c)) || (st = kd_scan_ensure(c, (size_t)n)) || (st = kd_ws_ensure(c, p.tot))) return st;
   p.det = c->opt.deterministic != 0;
-  p.d_cnt = (int *)c->d_kdws.p; p.d_first = (int *)(c->d_kdws + kd_up(c->kdws_pts * sizeof(int)));
-  char *ws = c->d_kdws + 2 * kd_up(c->kdws_pts * sizeof(int));
-  if (2 * kd_up(c->kdws_pts * sizeof(int)) + kf_ws_layout(c, (int)p.tot, p.det, ws, &p.w, &st) > c->d_kdws.n || st) return st ? st : VBA_ERR_CAPACITY;
-  const KdScanLayout L = kd_scan_layout(c->kdscan_pts);
-  p.d_pl = (double *)c->d_kdscan.p; p.d_part = (double *)(c->d_kdscan + L.o_part);
-  p.d_cand = (unsigned long long *)(c->d_kdscan + L.o_cand);
+  p.d_cnt = (int *)c->sat->kd.d_ws.p; p.d_first = (int *)(c->sat->kd.d_ws + kd_up(c->sat->kd.ws_pts * sizeof(int)));
+  char *ws = c->sat->kd.d_ws + 2 * kd_up(c->sat->kd.ws_pts * sizeof(int));
+  if (2 * kd_up(c->sat->kd.ws_pts * sizeof(int)) + kf_ws_layout(c, (int)p.tot, p.det, ws, &p.w, &st) > c->sat->kd.d_ws.n || st) return st ? st : VBA_ERR_CAPACITY;
+  const KdScanLayout L = kd_scan_layout(c->sat->kd.scan_pts);
+  p.d_pl = (double *)c->sat->kd.d_scan.p; p.d_part = (double *)(c->sat->kd.d_scan + L.o_part);
+  p.d_cand = (unsigned long long *)(c->sat->kd.d_scan + L.o_cand);
   return VBA_OK;
 }
 static int kd_odom_queue(vba_ctx *c, int n, const double *d_pts, KdPlan &p) {
-  vbh::OdomEkf *d_S = c->d_odom;
+  vbh::OdomEkf *d_S = c->sat->odom.d;
   hipStream_t s = c->stream;
-  double *tree = c->d_kdtree[c->kd_cur], *tree_out = c->d_kdtree[c->kd_cur ^ 1];
+  double *tree = c->sat->kd.d_tree[c->sat->kd.cur], *tree_out = c->sat->kd.d_tree[c->sat->kd.cur ^ 1];
   for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
-    if (n > 0) kd_point_loop(s, d_S, n, p.kd_slices, d_pts, c->kd_n, tree, p.d_cand, p.d_pl, p.d_part);
+    if (n > 0) kd_point_loop(s, d_S, n, p.kd_slices, d_pts, c->sat->kd.n, tree, p.d_cand, p.d_pl, p.d_part);
     // n == 0: nb == 0 and d_part may be NULL (no scan scratch was ever needed); the reduction reads nb * 34 doubles, that is none
     hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, s, d_S, (const double *)p.d_part, p.nb, iter, 1);
   }
   // map update VS:1238-1250: the scan appended in the refined pose, map + scan re-sampled on a 0.5 m grid into the other half; the
   // voxel count lands in the result block
-  if (n > 0) hipLaunchKernelGGL(k_kd_append_dev, dim3(p.nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, tree + (size_t)c->kd_n * 3);
+  if (n > 0) hipLaunchKernelGGL(k_kd_append_dev, dim3(p.nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, tree + (size_t)c->sat->kd.n * 3);
   p.w.n_out = &d_S->n_map;
   int st;
   if ((st = ds_core(c, s, 0, (int)p.tot, tree, nullptr, 9, 4, 0.5, p.det, p.w))) return st;
@@ -182,16 +185,16 @@ static int kd_odom_queue(vba_ctx *c, int n, const double *d_pts, KdPlan &p) {
   HIPCHK(c, hipGetLastError());
   return VBA_OK;
 }
-// c->h_odom holds the result block of the loop that kd_odom_queue queued
+// c->sat->odom.h holds the result block of the loop that kd_odom_queue queued
 static int kd_odom_finish(vba_ctx *c, const KdPlan &p) {
-  const vbh::OdomEkf &S = *c->h_odom;
+  const vbh::OdomEkf &S = *c->sat->odom.h;
   if (S.n_map < 1 || (size_t)S.n_map > p.tot) { c->set_error("kd-tree odometry: voxel count of the re-sampled map out of range"); return VBA_ERR_HIP; }
-  c->kd_cur ^= 1; c->kd_n = S.n_map;
+  c->sat->kd.cur ^= 1; c->sat->kd.n = S.n_map;
   return VBA_OK;
 }
 
 // The host-fed form.  When the scan only seeds the map the append is enqueued, *ran stays false and nothing is waited for.  Otherwise
-// state and cov are updated, the call has completed on return and c->h_odom holds the loop's result block.  Nothing here touches
+// state and cov are updated, the call has completed on return and c->sat->odom.h holds the loop's result block.  Nothing here touches
 // c->d_stage: a caller may keep the scan there.
 static int kd_odom_core(vba_ctx *c, int n, const double *d_pts, double *state, double *cov, bool *ran) {
   *ran = false;
@@ -202,15 +205,15 @@ static int kd_odom_core(vba_ctx *c, int n, const double *d_pts, double *state, d
     if (n > 0) {
       KdPose X;
       std::memcpy(X.R, state + 1, sizeof(X.R)); std::memcpy(X.t, state + 10, sizeof(X.t));
-      hipLaunchKernelGGL(k_kd_append, dim3(p.nb), dim3(256), 0, c->stream, n, d_pts, X, c->d_kdtree[c->kd_cur] + (size_t)c->kd_n * 3);
+      hipLaunchKernelGGL(k_kd_append, dim3(p.nb), dim3(256), 0, c->stream, n, d_pts, X, c->sat->kd.d_tree[c->sat->kd.cur] + (size_t)c->sat->kd.n * 3);
       HIPCHK(c, hipGetLastError());
     }
-    c->kd_n += n;
+    c->sat->kd.n += n;
     return VBA_OK;
   }
-  vbh::OdomEkf &S = *c->h_odom;
+  vbh::OdomEkf &S = *c->sat->odom.h;
   odom_image_begin(S, state, cov, true);
-  vbh::OdomEkf *d_S = c->d_odom;
+  vbh::OdomEkf *d_S = c->sat->odom.d;
   hipStream_t s = c->stream;
   HIPCHK(c, hipMemcpyAsync(d_S, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
   if ((st = kd_odom_queue(c, n, d_pts, p))) return st;
@@ -229,11 +232,11 @@ int vba_odom_lio_state_estimation_kdtree_resident(vba_ctx *c, int n, const doubl
   if (!c || n < 0 || (n > 0 && !d_pnt_body) || !state || !cov) return VBA_ERR_BAD_ARG;
   if (iterations) *iterations = 0;
   if (report) std::memset(report, 0, sizeof(*report));
-  if ((size_t)c->kd_n + (size_t)n > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
+  if ((size_t)c->sat->kd.n + (size_t)n > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
   bool ran;
   const int st = kd_odom_core(c, n, d_pnt_body, state, cov, &ran);
   if (st || !ran) return st;
-  const vbh::OdomEkf &S = *c->h_odom;
+  const vbh::OdomEkf &S = *c->sat->odom.h;
   if (iterations) *iterations = S.iterations;
   if (report) odom_report_fill(report, S, 0.0);
   return VBA_OK;
@@ -243,37 +246,37 @@ int vba_odom_lio_state_estimation_kdtree_resident(vba_ctx *c, int n, const doubl
 int vba_odom_lio_state_estimation_kdtree(vba_ctx *c, int n, const double *pnt_body, double *state, double *cov, int *iterations) {
   if (n < 0 || (n > 0 && !pnt_body) || !state || !cov) return VBA_ERR_BAD_ARG;
   if (iterations) *iterations = 0;
-  if ((size_t)c->kd_n + (size_t)n > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
+  if ((size_t)c->sat->kd.n + (size_t)n > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
   int st = ensure_stage(c, (size_t)n * 3 * sizeof(double));
   if (st) return st;
   if (n > 0) HIPCHK(c, hipMemcpyAsync(c->d_stage, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, c->stream));
   bool ran;
   if ((st = kd_odom_core(c, n, (const double *)c->d_stage.p, state, cov, &ran))) return st;
   if (!ran) HIPCHK(c, hipStreamSynchronize(c->stream));                    // seeded: the core only enqueued the append
-  else if (iterations) *iterations = c->h_odom->iterations;
+  else if (iterations) *iterations = c->sat->odom.h->iterations;
   return VBA_OK;
 }
 
 // ---------------------------------------------------------------- odometry scan-to-map (VS:962-1098)
 // One update on a scan in device memory with the iterations resident on the device: the host inverts P once, writes
 // one image, queues the four (point loop, update) pairs and waits once; which of them do any work is decided by the `done` flag in the
-// device state.  state and cov are updated, c->h_odom holds the loop's result block.  Nothing here touches c->d_stage: a caller may keep
+// device state.  state and cov are updated, c->sat->odom.h holds the loop's result block.  Nothing here touches c->d_stage: a caller may keep
 // the scan there.  Runs on this rank's map, whatever n_ranks is.
 static int odom_part_ensure(vba_ctx *c, int n) {
   const size_t need = (size_t)((n + 255) / 256) * 34;
-  if (need > c->d_odom_part.n) {
+  if (need > c->sat->odom.d_part.n) {
     size_t cap = 256 * 34;
     while (cap < need) cap *= 2;
-    HIPCHK(c, c->d_odom_part.ensure(cap));               // idle: the call that used it ended in a synchronise
+    HIPCHK(c, c->sat->odom.d_part.ensure(cap));               // idle: the call that used it ended in a synchronise
   }
   return VBA_OK;
 }
 static int odom_core(vba_ctx *c, int n, const double *d_pts, const double *d_var, double *state, double *cov) {
   int st = odom_image_ensure(c);
   if (st || (st = odom_part_ensure(c, n))) return st;
-  vbh::OdomEkf &S = *c->h_odom;
+  vbh::OdomEkf &S = *c->sat->odom.h;
   odom_image_begin(S, state, cov, false);
-  if ((st = map_odom_resident(c->map, c->stream, c->d_odom, c->h_odom, n, d_pts, d_var, c->d_odom_part, c->err))) return st;
+  if ((st = map_odom_resident(c->map, c->stream, c->sat->odom.d, c->sat->odom.h, n, d_pts, d_var, c->sat->odom.d_part, c->err))) return st;
   std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
   std::memcpy(cov, S.P_out, sizeof(S.P_out));
   return VBA_OK;
@@ -285,7 +288,7 @@ int vba_odom_lio_state_estimation_resident(vba_ctx *c, int n, const double *d_pn
   if (c->n_ranks > 1) { c->set_error("the resident odometry loop has no all-reduce step between its iterations: unsharded contexts only"); return VBA_ERR_UNSUPPORTED; }
   const int st = odom_core(c, n, d_pnt_body, d_var_body, state, cov);
   if (st) return st;
-  const vbh::OdomEkf &S = *c->h_odom;
+  const vbh::OdomEkf &S = *c->sat->odom.h;
   // SelfAdjointEigenSolver(nnt).eigenvalues()[0] < 14 -> false  (VS:1090-1097)
   const double emin = vbh::odom_nnt_eig_min(S.nnt);
   if (ok) *ok = (emin < 14) ? 0 : 1;
@@ -304,7 +307,7 @@ int vba_odom_lio_state_estimation(vba_ctx *c, int n, const double *pnt_body, con
     HIPCHK(c, hipMemcpyAsync(d_var, var_body, (size_t)n * 9 * sizeof(double), hipMemcpyDefault, c->stream));
   }
   if ((st = odom_core(c, n, d_pts, d_var, state, cov))) return st;
-  if (ok) *ok = (vbh::odom_nnt_eig_min(c->h_odom->nnt) < 14) ? 0 : 1;
+  if (ok) *ok = (vbh::odom_nnt_eig_min(c->sat->odom.h->nnt) < 14) ? 0 : 1;
   return VBA_OK;
 }
 
@@ -318,7 +321,7 @@ int vba_debug_odom_sums(vba_ctx *c, int kind, int n, const double *pnt_body, con
   if (!c || !pnt_body || !state || !cov || !partial || !sums || n < 1 || n > (1 << 28)) return VBA_ERR_BAD_ARG;
   if (kind != VBA_ODOM_SUMS_VOXEL && kind != VBA_ODOM_SUMS_KD) return VBA_ERR_BAD_ARG;
   const bool kd = kind == VBA_ODOM_SUMS_KD;
-  if (kd ? (!cand || !planes || slices < 0 || slices > 8 || c->kd_n < 100) : (!var_body || slices != 0)) return VBA_ERR_BAD_ARG;
+  if (kd ? (!cand || !planes || slices < 0 || slices > 8 || c->sat->kd.n < 100) : (!var_body || slices != 0)) return VBA_ERR_BAD_ARG;
   if (!all_finite(state, 25) || !all_finite(cov, 225)) return VBA_ERR_BAD_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   if (!is_device_ptr(pnt_body) && !all_finite(pnt_body, (size_t)n * 3)) return VBA_ERR_BAD_ARG;
@@ -340,16 +343,16 @@ int vba_debug_odom_sums(vba_ctx *c, int kind, int n, const double *pnt_body, con
   HIPCHK(c, hipMemsetAsync(d_out.p, 0, d_out.n * sizeof(double), s));
   HIPCHK(c, hipMemcpyAsync(d_pts, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, s));
   if (!kd) HIPCHK(c, hipMemcpyAsync(d_var, var_body, (size_t)n * 9 * sizeof(double), hipMemcpyDefault, s));
-  vbh::OdomEkf &S = *c->h_odom;
+  vbh::OdomEkf &S = *c->sat->odom.h;
   odom_image_begin(S, state, cov, kd);
   if (kd) {
-    HIPCHK(c, hipMemcpyAsync(c->d_odom.p, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
-    kd_point_loop(s, c->d_odom, n, ns, d_pts, c->kd_n, c->d_kdtree[c->kd_cur], d_cand, d_pl, d_part);
+    HIPCHK(c, hipMemcpyAsync(c->sat->odom.d.p, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
+    kd_point_loop(s, c->sat->odom.d, n, ns, d_pts, c->sat->kd.n, c->sat->kd.d_tree[c->sat->kd.cur], d_cand, d_pl, d_part);
     hipLaunchKernelGGL(k_odom_sums, dim3(1), dim3(256), 0, s, (const double *)d_part, nb, d_sums);
     st = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess ? VBA_OK : VBA_ERR_HIP;
   } else {
     int nb_run = 0;
-    st = map_odom_debug_sums(c->map, s, c->d_odom, c->h_odom, n, d_pts, d_var, d_part, d_sums, &nb_run, c->err);
+    st = map_odom_debug_sums(c->map, s, c->sat->odom.d, c->sat->odom.h, n, d_pts, d_var, d_part, d_sums, &nb_run, c->err);
   }
   if (st) { hipStreamSynchronize(s); return st; }                           // (nothing of this call is left in flight behind a status)
   hipError_t e = hipMemcpy(sums, d_sums, 34 * sizeof(double), hipMemcpyDefault);
@@ -536,10 +539,10 @@ int vba_odom_lio_state_estimation_on_state(vba_ctx *c, vba_odom_state *st, int n
   int r = odom_image_ensure(c);
   if (r || (r = odom_part_ensure(c, n)) || (r = odom_state_order(st, c->stream, c->err))) return r;
   hipStream_t s = c->stream;
-  vbh::OdomEkf *d_S = c->d_odom;
-  vbh::OdomEkf &S = *c->h_odom;
+  vbh::OdomEkf *d_S = c->sat->odom.d;
+  vbh::OdomEkf &S = *c->sat->odom.h;
   hipLaunchKernelGGL(k_odom_begin_dev, dim3(1), dim3(256), 0, s, d_S, (const double *)st->d_blk.p);
-  if ((r = map_odom_queue(c->map, s, d_S, n, d_pnt_body, d_var_body, c->d_odom_part, c->err))) return r;
+  if ((r = map_odom_queue(c->map, s, d_S, n, d_pnt_body, d_var_body, c->sat->odom.d_part, c->err))) return r;
   // the wait is for the download alone: the copy back into the state block runs behind it, ordered before whatever reads the block next
   const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
   HIPCHK(c, hipMemcpyAsync((char *)&S + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, s));
@@ -570,7 +573,7 @@ int vba_odom_lio_state_estimation_kdtree_on_state(vba_ctx *c, vba_odom_state *st
   if (!c || !st || !iterations || n < 0 || (n > 0 && !d_pnt_body) || c->device != st->ctx->device) return VBA_ERR_BAD_ARG;
   *iterations = 0;
   if (report) std::memset(report, 0, sizeof(*report));
-  if ((size_t)c->kd_n + (size_t)n > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
+  if ((size_t)c->sat->kd.n + (size_t)n > ((size_t)1 << 28)) return VBA_ERR_CAPACITY;
   HIPCHK(c, hipSetDevice(c->device));
   KdPlan p;
   int r = kd_odom_ensure(c, n, p);
@@ -586,10 +589,10 @@ int vba_odom_lio_state_estimation_kdtree_on_state(vba_ctx *c, vba_odom_state *st
       HIPCHK(c, hipEventRecord(st->res_ev, s));
     }
     if (n > 0) {
-      hipLaunchKernelGGL(k_kd_append_blk, dim3(p.nb), dim3(256), 0, s, (const double *)st->d_blk.p, n, d_pnt_body, c->d_kdtree[c->kd_cur] + (size_t)c->kd_n * 3);
+      hipLaunchKernelGGL(k_kd_append_blk, dim3(p.nb), dim3(256), 0, s, (const double *)st->d_blk.p, n, d_pnt_body, c->sat->kd.d_tree[c->sat->kd.cur] + (size_t)c->sat->kd.n * 3);
       HIPCHK(c, hipGetLastError());
     }
-    c->kd_n += n;
+    c->sat->kd.n += n;
     if (state_out) {
       HIPCHK(c, hipEventSynchronize(st->res_ev));
       std::memcpy(state_out, st->h_blk.p, 25 * sizeof(double));
@@ -597,8 +600,8 @@ int vba_odom_lio_state_estimation_kdtree_on_state(vba_ctx *c, vba_odom_state *st
     return VBA_OK;
   }
   if ((r = odom_state_order(st, s, c->err))) return r;
-  vbh::OdomEkf *d_S = c->d_odom;
-  vbh::OdomEkf &S = *c->h_odom;
+  vbh::OdomEkf *d_S = c->sat->odom.d;
+  vbh::OdomEkf &S = *c->sat->odom.h;
   hipLaunchKernelGGL(k_odom_begin_kd_dev, dim3(1), dim3(256), 0, s, d_S, (const double *)st->d_blk.p);
   if ((r = kd_odom_queue(c, n, d_pnt_body, p))) return r;
   // as in vba_odom_lio_state_estimation_on_state: the wait is for the download alone, the copy back into the block runs behind it

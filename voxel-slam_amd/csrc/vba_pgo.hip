@@ -3,6 +3,7 @@
 // vba_pgo_plan.hpp; pgo_prepare uploads it, pgo_update launches one update.  vba_debug_pgo_step runs the same two with U = 1 and reads
 // back what each pass left ("What pins the pose-graph passes").
 #include "vba_ctx.hpp"
+#include "vba_sat.hpp"
 #include "vba_kernels_pgo.hpp"
 #include "vba_pgo_plan.hpp"
 
@@ -26,7 +27,7 @@ bool pgo_args_ok(vba_ctx *c, int n, const double *poses, int m, const double *ed
 }
 
 // The plan of the caller's graph, the context's grow-only buffers sized for it, every table uploaded and the result words cleared.
-// v is ready for pgo_update(c, v, 0 .. U - 1); o_res is the offset of cost[U] | mx[U] | cnt[U] | status in c->d_pgo.
+// v is ready for pgo_update(c, v, 0 .. U - 1); o_res is the offset of cost[U] | mx[U] | cnt[U] | status in c->sat->pgo.d.
 int pgo_prepare(vba_ctx *c, int n, const double *poses, int m, const double *edges, int n_prior, const double *priors, int U,
                 double relin_threshold, PgoPlan &P, PgoView &v, size_t &o_res) {
   std::string perr;
@@ -62,9 +63,9 @@ int pgo_prepare(vba_ctx *c, int n, const double *poses, int m, const double *edg
     return VBA_OK;
   };
   const size_t abytes = ((size_t)(NP + 1) * ld + (size_t)(NP + 1) * 8) * 8;
-  if (int r = grow(c->d_pgo, bytes, "graph structure")) return r;
-  if (int r = grow(c->d_pgoAb, abytes, "dense skeleton system (8 (6K)^2 bytes)")) return r;
-  char *d = c->d_pgo;
+  if (int r = grow(c->sat->pgo.d, bytes, "graph structure")) return r;
+  if (int r = grow(c->sat->pgo.d_Ab, abytes, "dense skeleton system (8 (6K)^2 bytes)")) return r;
+  char *d = c->sat->pgo.d;
   v = PgoView{};
   v.n = n; v.F = F; v.NB = NB; v.S = S; v.K = K; v.NSB = NSB; v.U = U; v.NP = NP; v.ld = ld; v.thr = relin_threshold;
   v.theta = (double *)(d + o_theta); v.fz = (const double *)(d + o_fz); v.fi = (const int *)(d + o_fi); v.fj = (const int *)(d + o_fj);
@@ -74,7 +75,7 @@ int pgo_prepare(vba_ctx *c, int n, const double *poses, int m, const double *edg
   v.seg_ecode = (const int *)(d + o_sege); v.seg_ccode = (const int *)(d + o_segc); v.segY = (double *)(d + o_segY);
   v.segout = (double *)(d + o_segout); v.skel_node = (const int *)(d + o_skel); v.sb_pq = (const int *)(d + o_sbpq);
   v.sb_base = (const int *)(d + o_sbbase); v.sb_off = (const int *)(d + o_sboff); v.sb_ent = (const int *)(d + o_sbent);
-  v.Ab = c->d_pgoAb; v.Tb = c->d_pgoAb + (size_t)(NP + 1) * ld; v.dx = (double *)(d + o_dx);
+  v.Ab = c->sat->pgo.d_Ab; v.Tb = c->sat->pgo.d_Ab + (size_t)(NP + 1) * ld; v.dx = (double *)(d + o_dx);
   v.cost = (double *)(d + o_res); v.mx = (unsigned long long *)(d + o_res + (size_t)U * 8); v.cnt = (int *)(d + o_res + (size_t)U * 16);
   v.status = (int *)(d + o_res + (size_t)U * 20);
   hipStream_t st = c->stream;
@@ -137,7 +138,7 @@ int vba_pgo_optimize(vba_ctx *c, int n, double *poses, int m, const double *edge
   PgoView v{};
   size_t o_res = 0;
   if (int r = pgo_prepare(c, n, poses, m, edges, n_prior, priors, U, relin_threshold, P, v, o_res)) return r;
-  char *d = c->d_pgo;
+  char *d = c->sat->pgo.d;
   hipStream_t st = c->stream;
   TimedSpan sp;
   span_begin(c, "pgo", sp);
@@ -174,7 +175,7 @@ int vba_debug_pgo_step(vba_ctx *c, int n, const double *poses, int m, const doub
   PgoView v{};
   size_t o_res = 0;
   if (int r = pgo_prepare(c, n, poses, m, edges, n_prior, priors, 1, 0.0, P, v, o_res)) return r;
-  char *d = c->d_pgo;
+  char *d = c->sat->pgo.d;
   hipStream_t st = c->stream;
   pgo_update(c, v, 0);
   HIPCHK(c, hipGetLastError());

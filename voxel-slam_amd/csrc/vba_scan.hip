@@ -3,6 +3,9 @@
 // map consume in place.  The decode kernels are in vba_kernels_decode.hpp; undistortion, down-sampling and var_init are the kernels of
 // vba_kernels_scan.hpp (compiled in vba_kf.hip), run unchanged on the frame's buffers.
 #include "vba_ctx.hpp"
+#include "vba_odom_state.hpp"
+#include "vba_kf_store_decl.hpp"
+#include "vba_scan_frame.hpp"
 #include "vba_kernels_decode.hpp"
 
 #include <hip/hip_runtime.h>

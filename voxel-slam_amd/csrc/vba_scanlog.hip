@@ -2,6 +2,7 @@
 // keyframes, resident in HBM.  Host drivers of the kernels in vba_kernels_scanlog.hpp over the bookkeeping of vba_scanlog_ring.hpp.
 // Its readers in other units: vba_kf_build_from_log and vba_scanlog_export_world (vba_kf.hip), vba_scanlog_loop_update (vba_loop.hip).
 #include "vba_ctx.hpp"
+#include "vba_scanlog.hpp"
 #include "vba_kernels_scanlog.hpp"
 
 #include <hip/hip_runtime.h>

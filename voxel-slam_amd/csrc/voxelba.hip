@@ -566,6 +566,7 @@ int vba_create(const vba_options *opt, vba_ctx **out) {
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return VBA_ERR_HIP; }
     c->own_stream = true;
   }
+  if (int r = ctx_sat_create(c)) { vba_destroy(c); return r; }
   const int W = opt->win_size, nout = nout_of(W);
   c->fv.W = W;
   if (c->d_poses.ensure((size_t)VBA_MAX_WIN * 12) != hipSuccess || c->d_out.ensure((size_t)nout_tl(W) + 64) != hipSuccess ||
@@ -586,7 +587,7 @@ void vba_destroy(vba_ctx *c) {
   map_free(c->map);
   for (vba_ctx *w : c->hba_workers) vba_destroy(w);
   c->hba_workers.clear();
-  for (hipEvent_t e : c->exp_ev) if (e) hipEventDestroy(e);
+  ctx_sat_release(c);      // the satellites' buffers and events (vba_sat.hpp)
   for (auto &kv : c->spans) for (auto &s : kv.second) { hipEventDestroy(s.a); hipEventDestroy(s.b); }
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
   delete c;      // the buffers free themselves here (vba_mem.hpp), after the stream has been drained
