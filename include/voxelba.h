@@ -234,6 +234,49 @@ int vba_map_dump_leaves(vba_ctx *ctx, double *out, int max_leaves);
  * 86 doubles per leaf: [kx,ky,kz, layer, path, plane_var(36 row-major), cov_add upper triangle (45, row by row)];
  * same leaf set as vba_map_dump_leaves (order not defined).  out == NULL returns the leaf count. */
 int vba_map_dump_plane_var(vba_ctx *ctx, double *out, int max_leaves);
+/* The view of the live local voxel map: OctoTree::tras_display (VM:1765-1827) over every root of surf_map, what the
+ * topics /map_wind and /avoxel show.  The planar leaves come out as records, and with them the window's points that sit in planar
+ * leaves, at the poses given (x_buf).  pl_fixd is not produced (its loop is commented out in the reference).  The map is only read.
+ *
+ * Planes: one record per live leaf with plane.is_plane (VM:1780; the leaves whose column 7 of vba_map_dump_leaves is 1), 16 floats,
+ * formed fresh from the leaf's pcr_add as VM:1771-1773 does (center = v / N, cov = P / N - center center^T, uncontracted), each double
+ * narrowed to float once:
+ *   [0..2] center   [3] half edge of the leaf's cube (2 quater_length)
+ *   [4..6] unit eigenvector of the smallest eigenvalue (sign as the solver leaves it)   [7] layer
+ *   [8..10] sqrt of the eigenvalues, ascending, negative rounding residue clamped to 0   [11] pcr_add.N
+ *   [12..14] voxel_center   [15] pcr_add.N - pcr_fix.N
+ * (the commented-out attributes of VM:1794-1797 are floats 8, 10 / 8, 11 and 15).  plane_key[i] = {kx, ky, kz, layer, path}, the
+ * first five columns of vba_map_dump_leaves.  Order: ascending node id (a stable compaction over the nodes), hence a function of the
+ * map bit for bit under vba_options::deterministic and an unspecified permutation otherwise.
+ * Points: for i = 0 .. win_count - 1 in this order, the points of ring slot mp[i] that sit in a planar leaf, in the order the scan
+ * was inserted with (the slot's own storage groups them by leaf in an order that differs from run to run; the export undoes that, so
+ * the point records are the same bytes in every run and every mode); with flags & 1 every point that sits in a leaf.  Record = x y z intensity: xyz = poses[i].R pnt + poses[i].p in the uncontracted order
+ * ((R0 x + R1 y) + R2 z) + p, each coordinate narrowed to float once (VM:1807-1810), intensity = (float)i.  plane_of_point[j] = index
+ * of the record of that point's leaf in `planes`, -1 for a point of a non-planar leaf (flags & 1 only).  frame_begin[i] = first
+ * record of frame i, frame_begin[win_count] = *n_points: frames are contiguous, a stable compaction of the scan inside each.
+ * xyzi, plane_of_point, planes and plane_key are all HOST or all DEVICE memory (a device xyzi / planes 16-byte aligned); poses,
+ * frame_begin and the counts are host memory.  The work runs on ctx's stream.  The host needs the counts, so every call waits for
+ * the stream once; a device result is then written stream-ordered, without a second wait; a host result passes through the map's
+ * staging buffer and the call returns when it has arrived.
+ * cap_points == 0 with xyzi == NULL, and cap_planes == 0 with planes == NULL, form the size query of their side: the counts (and
+ * frame_begin) are set, nothing of that side is written and no capacity is checked for it.  planes == NULL with plane_of_point !=
+ * NULL is allowed: the indices refer to the order a full call returns.  A result larger than its cap is VBA_ERR_CAPACITY with
+ * *n_points and *n_planes set and every buffer (frame_begin too) untouched; so is a window of 2^31 points or more.
+ * Work arrays: an int per node, an int per 256 nodes and per 256-point workgroup, an int per window point (scan index -> position
+ * in the slot), the counts, and the staging of a host result (20 bytes per point, 104 per plane).  They belong to the context's map, _reserve(max_points, max_planes) sizes them for the map's
+ * current node capacity (or vba_options::max_map_nodes) and a host result of that size, a call that needs more doubles them after
+ * a synchronise, and nothing is allocated per call.  _allocations: allocations made and bytes requested for this feature so far.
+ * VBA_ERR_BAD_ARG before any device work, outputs untouched: a NULL ctx, n_points or n_planes; win_count < 0 or > win_size; NULL
+ * poses with win_count > 0; a negative cap; cap_points > 0 with a NULL xyzi; cap_planes > 0 with planes and plane_key both NULL;
+ * flag bits other than 1; result arrays on different sides; a misaligned device xyzi or planes.  A context without a map, an empty
+ * map or win_count == 0 give zero points and the planes that exist.  A sharded context exports its own leaves, with no collective. */
+int vba_map_display_reserve(vba_ctx *ctx, int64_t max_points, int64_t max_planes);
+int vba_map_display_allocations(vba_ctx *ctx, int *n_allocs, int64_t *bytes);
+int vba_map_display(vba_ctx *ctx, int win_count, const double *poses /* [win_count][12], host: x_buf */, int flags,
+                    int64_t cap_points, float *xyzi /* [cap_points][4] */, int *plane_of_point /* [cap_points] or NULL */,
+                    int64_t *frame_begin /* host, [win_count + 1], or NULL */,
+                    int64_t cap_planes, float *planes /* [cap_planes][16] or NULL */, long long *plane_key /* [cap_planes][5] or NULL */,
+                    int64_t *n_points, int64_t *n_planes);
 
 /* ------------------------------------------------------------------------------------------------
  * Odometry scan-to-map ("next #1").

@@ -9,6 +9,7 @@
 //   class LI_BA_OptimizerGravity VM:717-976  (damping_iter :878)    vba::LI_BA_OptimizerGravity
 //   cut_voxel / cut_voxel_multi / cut_voxel(fix)  VM:1896/1964/2108 vba::VoxelMap::cut_voxel[_multi|_fix]
 //   multi_recut / multi_margi    VS:1682 / VS:1590                  vba::VoxelMap::multi_recut / multi_margi
+//   OctoTree::tras_display       VM:1765-1827                       vba::VoxelMap::tras_display / display, vba::pub_voxelmap
 //   Initialization::motion_init  VS:617-819                         vba::Initialization::motion_init
 //   initialization(), pl_origs   VS:1499-1516                       vba::InitWindow::push + the InitWindow overload of motion_init
 //   build_graph + gtsam::ISAM2   VS:2078-2156, VS:2550-2561          vba::PoseGraph (add_edge LR:147-161, set_state LR:36-43)
@@ -268,6 +269,38 @@ class VoxelMap {
   // moved by dx here) and the window from the outgoing map's scan ring: no point crosses the host boundary
   inline int loop_update(LoopMap &map_loop, const IMUST &dx, ScanLog &log, int64_t first, std::vector<IMUST> &bl_states, std::vector<IMUST> &x_buf,
                          int win_count, IMUST &x_curr, int &g_update);
+  // The view of the live map (vba_map_display): what tras_display collects, with the planes it walks as records
+  struct Display {
+    std::vector<float> xyzi;                 // [n][4] x y z intensity (= the frame's index in the window)
+    std::vector<int> plane_of_point;         // [n] index into planes, -1: the point's leaf is no plane (flags & 1 only)
+    std::vector<int64_t> frame_begin;        // [win_count + 1]
+    std::vector<float> planes;               // [m][16]
+    std::vector<long long> plane_key;        // [m][5] kx ky kz layer path
+    int64_t n_points() const { return (int64_t)(xyzi.size() / 4); }
+    int64_t n_planes() const { return (int64_t)(planes.size() / 16); }
+  };
+  // the first win_count states of x_buf are the window's poses; flags & 1 keeps the points of non-planar leaves too
+  Display display(int win_count, const std::vector<IMUST> &x_buf, int flags = 0) {
+    if (win_count < 0 || (size_t)win_count > x_buf.size()) throw std::invalid_argument("VoxelMap::display: win_count");
+    const std::vector<double> poses = LidarFactor::poses_of(std::vector<IMUST>(x_buf.begin(), x_buf.begin() + win_count));
+    const double *ps = win_count > 0 ? poses.data() : nullptr;
+    Display d;
+    int64_t n = 0, m = 0;
+    d.frame_begin.assign((size_t)win_count + 1, 0);
+    check(c_, vba_map_display(c_, win_count, ps, flags, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, &n, &m));     // the size query
+    d.xyzi.resize((size_t)n * 4); d.plane_of_point.resize((size_t)n); d.planes.resize((size_t)m * 16); d.plane_key.resize((size_t)m * 5);
+    if (n > 0 || m > 0)
+      check(c_, vba_map_display(c_, win_count, ps, flags, n, n > 0 ? d.xyzi.data() : nullptr, n > 0 ? d.plane_of_point.data() : nullptr,
+                                d.frame_begin.data(), m, m > 0 ? d.planes.data() : nullptr, m > 0 ? d.plane_key.data() : nullptr, &n, &m));
+    return d;
+  }
+  // OctoTree::tras_display(win_count, pl_fixd, pl_wind, x_buf) over every root of surf_map (VM:1765-1827):
+  // the window's points that sit in planar leaves are appended to pl_wind as x y z intensity.  pl_fixd is not produced: its loop is
+  // commented out in the reference, which leaves it empty.
+  void tras_display(int win_count, std::vector<float> &pl_wind, const std::vector<IMUST> &x_buf) {
+    const Display d = display(win_count, x_buf, 0);
+    pl_wind.insert(pl_wind.end(), d.xyzi.begin(), d.xyzi.end());
+  }
   vba_ctx *get() const { return c_; }
   size_t size() const { return (size_t)vba_map_num_roots(c_); }
   size_t slide_size() const { return (size_t)vba_map_num_slide_roots(c_); }
@@ -1303,6 +1336,18 @@ inline int64_t pub_localmap(Context &ctx, ScanLog &log, int64_t first, int mgsiz
   check(ctx.get(), vba_scanlog_export_world(ctx.get(), log.get(), first, mgsize, poses.data(), stride, (float)cur_session, cap, pl.data(), &n));
   publish((const float *)pl.data(), n);
   return n;
+}
+
+// The live local map for display, shaped like pub_localmap: what OctoTree::tras_display (VM:1765-1827) collects for /map_wind and
+// what the /avoxel marker of rviz_cfg/back_voxel.rviz shows.  publish_points(const float *xyzi, int64_t n) receives the records
+// x y z intensity (intensity = the frame's index in the window), publish_planes(const float *planes, const long long *keys, int64_t m)
+// the plane records [m][16] and their keys [m][5] (voxelba.h, vba_map_display).  Returns the number of points.
+template <class PublishPoints, class PublishPlanes>
+inline int64_t pub_voxelmap(VoxelMap &vmap, int win_count, const std::vector<IMUST> &x_buf, PublishPoints &&publish_points, PublishPlanes &&publish_planes) {
+  const VoxelMap::Display d = vmap.display(win_count, x_buf, 0);
+  publish_points((const float *)d.xyzi.data(), d.n_points());
+  publish_planes((const float *)d.planes.data(), (const long long *)d.plane_key.data(), d.n_planes());
+  return d.n_points();
 }
 
 // FileReaderWriter::save_pcd (VS:166-179) of scan seq: savename/seq.pcd from the float form read off the device

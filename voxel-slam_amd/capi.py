@@ -1321,6 +1321,47 @@ class Context:
         """[kx,ky,kz,layer,path, plane_var(36), cov_add upper triangle (45)] per leaf."""
         return _dump_rows(self.lib.vba_map_dump_plane_var, self.h, 86)
 
+    def map_display_sizes(self, win_count, poses, all_points=False):
+        """the size query of vba_map_display: (n_points, n_planes, frame_begin int64 [win_count + 1])"""
+        poses = _c(poses).reshape(-1, 12)
+        npt = C.c_int64(-1); npl = C.c_int64(-1); fb = np.zeros(win_count + 1, dtype=np.int64)
+        self._chk(self.lib.vba_map_display(self.h, win_count, _p(poses) if win_count else None, int(bool(all_points)), 0, None, None,
+                                           fb.ctypes.data_as(C.c_void_p), 0, None, None, C.byref(npt), C.byref(npl)))
+        return npt.value, npl.value, fb
+
+    def map_display(self, win_count, poses, all_points=False, device_out=None):
+        """vba_map_display (OctoTree::tras_display over the whole map): the planar leaves and the window's points that sit in them
+        at ``poses`` [win_count][12]; ``all_points`` keeps every point that sits in a leaf.  Returns a dict: xyzi float32 [n][4],
+        plane_of_point int32 [n], frame_begin int64 [win_count + 1], planes float32 [m][16], plane_key int64 [m][5].
+        ``device_out`` = (cap_points, xyzi address, plane_of_point address or None, cap_planes, planes address or None, plane_key
+        address or None) of DEVICE buffers (xyzi / planes 16-byte aligned): the result is written there stream-ordered and the dict
+        holds n_points, n_planes and frame_begin."""
+        poses = _c(poses).reshape(-1, 12)
+        flags = int(bool(all_points))
+        pp = _p(poses) if win_count else None
+        npt = C.c_int64(-1); npl = C.c_int64(-1); fb = np.zeros(win_count + 1, dtype=np.int64)
+        if device_out is not None:
+            cap_pts, d_xyzi, d_pop, cap_pl, d_planes, d_key = device_out
+            self._chk(self.lib.vba_map_display(self.h, win_count, pp, flags, int(cap_pts), d_xyzi, d_pop, fb.ctypes.data_as(C.c_void_p),
+                                               int(cap_pl), d_planes, d_key, C.byref(npt), C.byref(npl)))
+            return {"n_points": npt.value, "n_planes": npl.value, "frame_begin": fb}
+        n, m, _ = self.map_display_sizes(win_count, poses, all_points)
+        xyzi = np.zeros((max(n, 1), 4), dtype=np.float32); pop = np.zeros(max(n, 1), dtype=np.int32)
+        planes = np.zeros((max(m, 1), 16), dtype=np.float32); key = np.zeros((max(m, 1), 5), dtype=np.int64)
+        self._chk(self.lib.vba_map_display(self.h, win_count, pp, flags, max(n, 1), xyzi.ctypes.data_as(C.c_void_p), pop.ctypes.data_as(C.c_void_p),
+                                           fb.ctypes.data_as(C.c_void_p), max(m, 1), planes.ctypes.data_as(C.c_void_p),
+                                           key.ctypes.data_as(C.c_void_p), C.byref(npt), C.byref(npl)))
+        return {"xyzi": xyzi[:npt.value].copy(), "plane_of_point": pop[:npt.value].copy(), "frame_begin": fb,
+                "planes": planes[:npl.value].copy(), "plane_key": key[:npl.value].copy()}
+
+    def map_display_reserve(self, max_points, max_planes):
+        self._chk(self.lib.vba_map_display_reserve(self.h, int(max_points), int(max_planes)))
+
+    def map_display_allocations(self):
+        n = C.c_int(); b = C.c_int64()
+        self._chk(self.lib.vba_map_display_allocations(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
     # ---- odometry
     def lio_state_estimation(self, pnt_body, var_body, state25, cov225):
         """VOXEL_SLAM::lio_state_estimation (voxelslam.cpp:962-1098).  Returns (ok, state, cov)."""

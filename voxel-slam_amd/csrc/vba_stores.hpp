@@ -27,6 +27,9 @@ struct MapMem {
   DevMem<char> d_sort_tmp;       // rocPRIM scratch, sized for max_pts pairs
   DevMem<double> d_gc;           // the 2-double scratch of the sharded map's all-reduce
   DevMem<int> d_whist;           // deterministic mode: the per-workgroup bucket histograms of the stable sort
+  // the display export (vba_map_display.hip): plane index per node, the workgroup counts (nodes, then points), scan index -> position in
+  // the slot per window point, the counts and poses on the device, their pinned partners, the device staging of a host result
+  DevMem<int> disp_nidx, disp_blk, disp_inv, disp_cnt; DevMem<double> disp_poses; PinMem<char> disp_pin; DevMem<char> disp_stage;
 };
 
 struct MapStore : MapMem {
@@ -51,6 +54,7 @@ struct MapStore : MapMem {
   bool thr_override = false;
   double ovr_min_eigen_value = 0.0, ovr_plane_thre[4] = {0.0, 0.0, 0.0, 0.0};
   bool det = false;              // deterministic mode (vba_options::deterministic)
+  int disp_allocs = 0; int64_t disp_bytes = 0;   // vba_map_display_allocations: cumulative, they outlive a map_free
 };
 
 // a fixed insertion whose points and covariances are in HBM already
