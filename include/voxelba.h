@@ -736,6 +736,29 @@ int vba_btc_search_loop_sessions(int n_db, vba_btc_db *const *dbs, int n, const 
  * the pose, updated in place; *ok = the return value, eig = eigenvalues of mat_norm (ascending), *iters = iterations run. */
 int vba_btc_icp_normal(vba_btc_db *src_db, int src_frame, vba_btc_db *tar_db, int tar_frame, double *t, double *R, double icp_eigval,
                        int *ok, double *eig, int *iters);
+/* Diagnostic: ONE iteration of vba_btc_icp_normal, every pass read back (tests/test_gpu_icp_passes.py; declared here, not with the
+ * other vba_debug_* entries, because it takes database handles).  The 1-NN launch, the gate-and-accumulate launch and the step
+ * launch are queued by the host function the loop of vba_btc_icp_normal calls twenty times; the outputs leave the production
+ * kernels through pointers that are null in that loop.  *state is the iteration's state, in and out: vba_btc_icp_normal starts
+ * from (R, t, paras = {0.2, 0.2, 0.5, 3}, everything else 0), and chaining this call from there reproduces it bit for bit.
+ * slices: runs of 256-point tiles the target is cut into for the 1-NN launch; 0 = the call's own choice (what the loop runs),
+ * k >= 1 = k.  With ntile = ceil(nt / 256) and nb = max(ceil(ns / 256), 1), k > max(ntile, 1) or nb * k > 1024 is refused.
+ * Host outputs, each may be NULL, each left as the caller gave it when state->done is set on entry (the launches return at once):
+ *   key [ns]           the merged 1-NN word of every source point: float distance bits << 32 | index in the target cloud, ~0 = none
+ *   gate [ns]          1 where the point passed the four gates and entered the sums
+ *   partial [nb][35]   per workgroup of 256 points: Hess upper (21) | JacT (6) | resi | match_num | mat_norm upper (6)
+ *   sums [35]          the column sums of partial in workgroup order, as the step forms them
+ *   dx [6]             the solved step (rotation | translation)
+ *   *slices_used       the slice count that ran
+ * The stream is drained.  VBA_ERR_BAD_ARG with nothing launched and *state untouched: a NULL database or state, databases of two
+ * contexts, a frame out of range, a slice count outside the plan.  VBA_ERR_UNSUPPORTED: a sharded context. */
+typedef struct vba_btc_icp_state {
+  double R[9], t[3], paras[4];    /* pose (R row-major), thresholds: normal_inc, normal_add, point_to_plane, point_to_point */
+  int is_conv, done, iters, pad;  /* is_converge; the loop has ended; iterations run */
+  double mat[6], eig[3];          /* mat_norm of the last iteration (xx xy xz yy yz zz); its eigenvalues once done is set */
+} vba_btc_icp_state;
+int vba_debug_btc_icp_pass(vba_btc_db *src_db, int src_frame, vba_btc_db *tar_db, int tar_frame, vba_btc_icp_state *state, int slices,
+                           unsigned long long *key, unsigned char *gate, double *partial, double *sums, double *dx, int *slices_used);
 /* candidates of the last search on db (*n = how many; at most cap written) */
 int vba_btc_last_candidates(vba_btc_db *db, int cap, vba_btc_candidate *out, int *n);
 

@@ -338,4 +338,14 @@ def _nn_tree(tree, q32, cloud32):
     dd = dd + d[..., 1] * d[..., 1]
     dd = dd + d[..., 2] * d[..., 2]
     m = dd.min(axis=1, keepdims=True)
-    return np.where(dd == m, cand, np.iinfo(np.int64).max).min(axis=1)
+    out = np.where(dd == m, cand, np.iinfo(np.int64).max).min(axis=1)
+    # k candidates do not answer a query whose last candidate (the farthest in double) still ties the minimum in float (nine or more coincident or
+    # equidistant points, or a float rounding that promotes a farther double-neighbour): those rows by brute force, lowest index
+    if k < len(c):
+        for i in np.nonzero(dd[:, -1] == m[:, 0])[0]:
+            e = q[i][None, :] - c
+            ee = e[:, 0] * e[:, 0]
+            ee = ee + e[:, 1] * e[:, 1]
+            ee = ee + e[:, 2] * e[:, 2]
+            out[i] = int(np.argmin(ee))
+    return out

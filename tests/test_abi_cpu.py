@@ -290,3 +290,19 @@ def test_debug_pgo_step_is_exported_typed_and_refuses_without_a_context(capi):
     p = lambda a: a.ctypes.data_as(C.c_void_p)
     st = lib.vba_debug_pgo_step(None, C.c_int(1), p(poses), C.c_int(0), None, C.c_int(1), p(pr), p(slot), None, None, None, None, None, None, None)
     assert st == capi.ERR_BAD_ARG and np.isnan(slot).all()
+
+
+def test_debug_btc_icp_pass_is_exported_typed_and_refuses_without_a_database(capi):
+    """the diagnostic entry of tests/test_gpu_icp_passes.py: declared next to vba_btc_icp_normal (it takes database handles), typed from
+    abi.py, its state struct the size of the device's, and it checks its arguments before it touches a device"""
+    from voxel_slam_amd import abi
+    assert abi.PROTOTYPES["vba_debug_btc_icp_pass"] == "i:pipipi" + "p" * 6
+    names = list(abi.PROTOTYPES)
+    assert names.index("vba_debug_btc_icp_pass") == names.index("vba_btc_icp_normal") + 1
+    assert hasattr(capi.BtcDb, "debug_icp_pass") and C.sizeof(capi.BtcIcpState) == 216
+    lib = capi.load()
+    st = capi.BtcIcpState.start(np.zeros(3), np.eye(3)); before = bytes(st)
+    sums = np.full(35, np.nan)
+    rc = lib.vba_debug_btc_icp_pass(None, C.c_int(0), None, C.c_int(0), C.byref(st), C.c_int(0), None, None, None,
+                                    sums.ctypes.data_as(C.c_void_p), None, None)
+    assert rc == capi.ERR_BAD_ARG and np.isnan(sums).all() and bytes(st) == before

@@ -263,6 +263,36 @@ def test_debug_pgo_step_runs_the_production_plan_and_launches():
     assert "csrc/vba_pgo_math.hpp" in host and "csrc/vba_pgo_plan.hpp" in host
 
 
+def test_debug_btc_icp_pass_runs_the_production_pass():
+    """vba_debug_btc_icp_pass pins the production iteration: the per-point and per-step arithmetic is written once, in the
+    host-and-device header that the kernels and the g++ companion both compile; the plan and the three launches of one iteration are
+    one function, called by the loop of vba_btc_icp_normal and by the diagnostic entry"""
+    math, kern, unit = read("vba_icp_math.hpp"), read("vba_kernels_btc.hpp"), read("vba_btc.hip")
+    assert "__global__" not in math and "hipStream_t" not in math and "__shfl" not in math
+    assert sorted(INCLUDE.findall(math)) == ["vba_btc_svd.hpp", "vba_hostmath.hpp", "vba_ldlt6.hpp"]
+    for fn in ("btc_norm3", "btc_icp_query", "btc_icp_point", "btc_icp_solve_update", "btc_icp_transition"):
+        assert len(re.findall(r"^BTC_HD [\w() ]+ %s\(" % fn, math, re.M)) == 1, fn
+        assert [f for f in sources() if re.search(r"^\w[\w() ]* %s\(" % fn, read(f), re.M)] == ["vba_icp_math.hpp"], fn
+    for kernel, call in (("k_btc_icp_nn", "btc_icp_query(st->R, st->t, "), ("k_btc_icp_accum", "btc_icp_point(st->R, st->t, st->paras, "),
+                         ("k_btc_icp_step", "btc_icp_solve_update(acc, st->R, st->t, st->mat, dx);"),
+                         ("k_btc_icp_step", "btc_icp_transition(dx, st->paras, &st->is_conv, &st->done, &st->iters);")):
+        assert call in function_body(kern, r"^__global__ __launch_bounds__\(\d+\) void %s\(" % kernel), (kernel, call)
+    assert [f for f in sources() if "vba_icp_math.hpp" in INCLUDE.findall(read(f))] == ["vba_kernels_btc.hpp"]
+    for k in ("k_btc_icp_nn<<<", "k_btc_icp_accum<<<", "k_btc_icp_step<<<"):
+        assert len(re.findall(re.escape(k), unit)) == 1 and k in function_body(unit, r"^static int btc_icp_pass\("), k
+    # the slice plan is a pure function (the entry's refusal touches nothing); the pass plans, sizes and launches
+    plan = function_body(unit, r"^static bool btc_icp_plan\(")
+    assert "grow_keep" not in plan and "c->" not in plan and len(re.findall(r"btc_icp_plan\(cl, ", unit)) == 2
+    body = function_body(unit, r"^static int btc_icp_pass\(")
+    assert "btc_icp_plan(cl, want, &p)" in body and "btc_icp_ensure(c, cl, p)" in body
+    for entry in (r"^int vba_btc_icp_normal\(", r"^int vba_debug_btc_icp_pass\("):
+        body = function_body(unit, entry)
+        assert "btc_icp_pass(c, cl, " in body and "<<<" not in body, entry
+    assert "it < BTC_ICP_ITERS" in function_body(unit, r"^int vba_btc_icp_normal\(")
+    host = open(os.path.join(os.path.dirname(CSRC), "..", "tests", "host", "icp_host.cpp")).read()
+    assert "csrc/vba_icp_math.hpp" in host
+
+
 # ---------------------------------------------------------------- the BA core's host side (DESIGN.md, "Source layout": voxelba.hip)
 # a macro definition with its continuation lines: (name, body)
 MACRO = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(\w+)((?:[^\n]*\\\n)*[^\n]*)", re.M)

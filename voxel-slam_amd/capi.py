@@ -50,6 +50,21 @@ class BtcResult(C.Structure):
     _fields_ = [("loop_id", C.c_int), ("score", C.c_double), ("t", C.c_double * 3), ("R", C.c_double * 9)]
 
 
+class BtcIcpState(C.Structure):
+    """vba_btc_icp_state: the state of one icp_normal iteration"""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("paras", C.c_double * 4), ("is_conv", C.c_int), ("done", C.c_int),
+                ("iters", C.c_int), ("pad", C.c_int), ("mat", C.c_double * 6), ("eig", C.c_double * 3)]
+
+    @classmethod
+    def start(cls, t, R, paras=(0.2, 0.2, 0.5, 3.0), is_conv=0, done=0, iters=0):
+        """the state vba_btc_icp_normal starts from (loop_refine.hpp:62-63), or a caller's"""
+        s = cls()
+        s.R[:] = [float(x) for x in np.reshape(R, 9)]; s.t[:] = [float(x) for x in np.reshape(t, 3)]
+        s.paras[:] = [float(x) for x in paras]
+        s.is_conv, s.done, s.iters = int(is_conv), int(done), int(iters)
+        return s
+
+
 class BtcCandidate(C.Structure):
     _fields_ = [("frame", C.c_int), ("votes", C.c_int), ("match_len", C.c_int), ("max_vote_index", C.c_int),
                 ("max_vote", C.c_int), ("score", C.c_double)]
@@ -212,6 +227,20 @@ class BtcDb:
         self.ctx._chk(self.lib.vba_btc_icp_normal(self.h, src_frame, tar_db.h, tar_frame, _p(tt), _p(RR),
                                                   icp_eigval, C.byref(ok), _p(eig), C.byref(it)))
         return dict(ok=ok.value, t=tt, R=RR, eig=eig, iters=it.value)
+
+    def debug_icp_pass(self, src_frame, tar_db, tar_frame, state, ns, slices=0, prefill=None):
+        """vba_debug_btc_icp_pass: ONE iteration of icp_normal from `state` (a BtcIcpState, left as given); ns = points of the source
+        cloud.  Returns dict(state (the state after the step), key [ns] uint64, gate [ns] uint8, partial [nb][35], sums [35], dx [6],
+        slices).  prefill: the value the float outputs hold before the call (NaN), to see what a call leaves untouched."""
+        nb = max((ns + 255) // 256, 1)
+        fill = np.nan if prefill is None else prefill
+        st = BtcIcpState.from_buffer_copy(state)
+        key = np.zeros(max(ns, 1), dtype=np.uint64); gate = np.full(max(ns, 1), 255, dtype=np.uint8)
+        partial = np.full((nb, 35), fill); sums = np.full(35, fill); dx = np.full(6, fill); used = C.c_int(-1)
+        self.ctx._chk(self.lib.vba_debug_btc_icp_pass(self.h, src_frame, tar_db.h, tar_frame, C.byref(st), slices,
+                                                      key.ctypes.data_as(C.c_void_p), gate.ctypes.data_as(C.c_void_p), _p(partial),
+                                                      _p(sums), _p(dx), C.byref(used)))
+        return dict(state=st, key=key[:ns], gate=gate[:ns], partial=partial, sums=sums, dx=dx, slices=used.value)
 
 
 class _Handle:

@@ -476,31 +476,74 @@ int vba_btc_last_candidates(vba_btc_db *db, int cap, vba_btc_candidate *out, int
   return VBA_OK;
 }
 
+// ---- icp_normal: one iteration is btc_icp_pass, for the loop of vba_btc_icp_normal and for vba_debug_btc_icp_pass alike
+struct BtcIcpClouds { int ns, nt; const float *src, *tar; };
+struct BtcIcpTaps { unsigned long long *key = nullptr; unsigned char *gate = nullptr; double *sums = nullptr, *dx = nullptr; };   // device, null in the loop
+
+static bool btc_icp_frames_ok(const vba_btc_db *src_db, int src_frame, const vba_btc_db *tar_db, int tar_frame) {
+  return src_frame >= 0 && src_frame < (int)src_db->off.size() - 1 && tar_frame >= 0 && tar_frame < (int)tar_db->off.size() - 1;
+}
+static BtcIcpClouds btc_icp_clouds(const vba_btc_db *src_db, int src_frame, const vba_btc_db *tar_db, int tar_frame) {
+  BtcIcpClouds cl;
+  cl.ns = src_db->off[src_frame + 1] - src_db->off[src_frame]; cl.nt = tar_db->off[tar_frame + 1] - tar_db->off[tar_frame];
+  cl.src = src_db->d_pc ? src_db->d_pc + 6 * (size_t)src_db->off[src_frame] : nullptr;
+  cl.tar = tar_db->d_pc ? tar_db->d_pc + 6 * (size_t)tar_db->off[tar_frame] : nullptr;
+  return cl;
+}
+// The plan of a pass: nb workgroups of 256 source points, the target cut into `slices` runs of ceil(ntile / slices) tiles of 256 for
+// the 1-NN launch (about 1024 workgroups).  want = 0: the pass's own choice; k >= 1: k, refused beyond max(ntile, 1) (k_btc_icp_nn
+// would divide the tiles by more slices than there are) and beyond 1024 workgroups.  Touches nothing.
+struct BtcIcpPlan { int nb, slices; };
+static bool btc_icp_plan(const BtcIcpClouds &cl, int want, BtcIcpPlan *p) {
+  const int nb = cl.ns > 0 ? (cl.ns + 255) / 256 : 1, ntile = (cl.nt + 255) / 256;
+  int slices = 1;
+  if (want > 0) {
+    if (want > (ntile > 1 ? ntile : 1) || (long long)nb * want > 1024) return false;
+    slices = want;
+  } else {
+    while (slices < ntile && nb * slices * 2 <= 1024) slices *= 2;          // ~1024 workgroups on the 1-NN pass
+    if (slices > ntile && ntile > 0) slices = ntile;
+  }
+  p->nb = nb; p->slices = slices;
+  return true;
+}
+// the key [slices][ns] and partial [nb][35] buffers of a plan (grow-only; nothing to do once they fit)
+static int btc_icp_ensure(vba_ctx *c, const BtcIcpClouds &cl, const BtcIcpPlan &p) {
+  if ((size_t)p.slices * cl.ns > c->sat->btc.d_icpkey.n) {
+    size_t m = 65536;
+    while (m < (size_t)p.slices * cl.ns) m *= 2;
+    HIPCHK(c, c->sat->btc.d_icpkey.grow_keep(m, 0, c->stream));
+  }
+  if ((size_t)p.nb * BTC_ICP_PART > c->sat->btc.d_icppart.n) {
+    size_t m = 4096;
+    while (m < (size_t)p.nb * BTC_ICP_PART) m *= 2;
+    HIPCHK(c, c->sat->btc.d_icppart.grow_keep(m, 0, c->stream));
+  }
+  return VBA_OK;
+}
+static int btc_icp_pass(vba_ctx *c, const BtcIcpClouds &cl, int want, const BtcIcpTaps &tp, int *slices_used) {
+  BtcIcpPlan p;
+  if (!btc_icp_plan(cl, want, &p)) return VBA_ERR_BAD_ARG;
+  const int st = btc_icp_ensure(c, cl, p);
+  if (st) return st;
+  const int nb = p.nb, slices = p.slices;
+  auto &B = c->sat->btc;
+  k_btc_icp_nn<<<dim3(nb, slices), 256, 0, c->stream>>>(cl.ns, cl.src, cl.nt, cl.tar, B.d_icp, B.d_icpkey);
+  k_btc_icp_accum<<<nb, 256, 0, c->stream>>>(cl.ns, cl.src, cl.tar, slices, B.d_icpkey, B.d_icp, B.d_icppart, tp.key, tp.gate);
+  k_btc_icp_step<<<1, 64, 0, c->stream>>>(nb, B.d_icppart, B.d_icp, tp.sums, tp.dx);
+  if (slices_used) *slices_used = slices;
+  return VBA_OK;
+}
+
 int vba_btc_icp_normal(vba_btc_db *src_db, int src_frame, vba_btc_db *tar_db, int tar_frame, double *t, double *R, double icp_eigval,
                        int *ok, double *eig, int *iters) {   // loop_refine.hpp:47-139
   if (!src_db || !tar_db || !t || !R || src_db->ctx != tar_db->ctx) return VBA_ERR_BAD_ARG;
-  if (src_frame < 0 || src_frame >= (int)src_db->off.size() - 1 || tar_frame < 0 || tar_frame >= (int)tar_db->off.size() - 1) return VBA_ERR_BAD_ARG;
+  if (!btc_icp_frames_ok(src_db, src_frame, tar_db, tar_frame)) return VBA_ERR_BAD_ARG;
   vba_ctx *c = src_db->ctx;
   HIPCHK(c, hipSetDevice(c->device));
-  const int ns = src_db->off[src_frame + 1] - src_db->off[src_frame], nt = tar_db->off[tar_frame + 1] - tar_db->off[tar_frame];
-  const float *src = src_db->d_pc ? src_db->d_pc + 6 * (size_t)src_db->off[src_frame] : nullptr;
-  const float *tar = tar_db->d_pc ? tar_db->d_pc + 6 * (size_t)tar_db->off[tar_frame] : nullptr;
-  const int nb = ns > 0 ? (ns + 255) / 256 : 1, ntile = (nt + 255) / 256;
-  int slices = 1;
-  while (slices < ntile && nb * slices * 2 <= 1024) slices *= 2;          // ~1024 workgroups on the 1-NN pass
-  if (slices > ntile && ntile > 0) slices = ntile;
+  const BtcIcpClouds cl = btc_icp_clouds(src_db, src_frame, tar_db, tar_frame);
   HIPCHK(c, c->sat->btc.d_icp.ensure(1));
   HIPCHK(c, c->sat->btc.h_icp.ensure(1));
-  if ((size_t)slices * ns > c->sat->btc.d_icpkey.n) {
-    size_t m = 65536;
-    while (m < (size_t)slices * ns) m *= 2;
-    HIPCHK(c, c->sat->btc.d_icpkey.grow_keep(m, 0, c->stream));
-  }
-  if ((size_t)nb * BTC_ICP_PART > c->sat->btc.d_icppart.n) {
-    size_t m = 4096;
-    while (m < (size_t)nb * BTC_ICP_PART) m *= 2;
-    HIPCHK(c, c->sat->btc.d_icppart.grow_keep(m, 0, c->stream));
-  }
   BtcSpan sp(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));       // (the pinned state block may still be in flight from an earlier call)
   BtcIcpDev *h = c->sat->btc.h_icp;
@@ -509,10 +552,9 @@ int vba_btc_icp_normal(vba_btc_db *src_db, int src_frame, vba_btc_db *tar_db, in
   for (int k = 0; k < 3; k++) h->t[k] = t[k];
   h->paras[0] = 0.2; h->paras[1] = 0.2; h->paras[2] = 0.5; h->paras[3] = 3;
   HIPCHK(c, hipMemcpyAsync(c->sat->btc.d_icp, h, sizeof(*h), hipMemcpyHostToDevice, c->stream));
-  for (int it = 0; it < 20; it++) {                  // launches after convergence return at once (BtcIcpDev::done)
-    k_btc_icp_nn<<<dim3(nb, slices), 256, 0, c->stream>>>(ns, src, nt, tar, c->sat->btc.d_icp, c->sat->btc.d_icpkey);
-    k_btc_icp_accum<<<nb, 256, 0, c->stream>>>(ns, src, tar, slices, c->sat->btc.d_icpkey, c->sat->btc.d_icp, c->sat->btc.d_icppart);
-    k_btc_icp_step<<<1, 64, 0, c->stream>>>(nb, c->sat->btc.d_icppart, c->sat->btc.d_icp);
+  for (int it = 0; it < BTC_ICP_ITERS; it++) {       // launches after convergence return at once (BtcIcpDev::done)
+    const int st = btc_icp_pass(c, cl, 0, BtcIcpTaps{}, nullptr);
+    if (st) return st;
   }
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(h, c->sat->btc.d_icp, sizeof(*h), hipMemcpyDeviceToHost, c->stream));
@@ -523,6 +565,62 @@ int vba_btc_icp_normal(vba_btc_db *src_db, int src_frame, vba_btc_db *tar_db, in
   if (eig) for (int k = 0; k < 3; k++) eig[k] = h->eig[k];
   if (iters) *iters = h->iters;
   if (ok) *ok = (h->eig[0] > icp_eigval && h->is_conv == 1) ? 1 : 0;
+  return VBA_OK;
+}
+
+static_assert(sizeof(vba_btc_icp_state) == sizeof(BtcIcpDev), "vba_btc_icp_state mirrors BtcIcpDev");
+
+int vba_debug_btc_icp_pass(vba_btc_db *src_db, int src_frame, vba_btc_db *tar_db, int tar_frame, vba_btc_icp_state *state, int slices,
+                           unsigned long long *key, unsigned char *gate, double *partial, double *sums, double *dx, int *slices_used) {
+  if (!src_db || !tar_db || !state || src_db->ctx != tar_db->ctx || slices < 0) return VBA_ERR_BAD_ARG;
+  if (!btc_icp_frames_ok(src_db, src_frame, tar_db, tar_frame)) return VBA_ERR_BAD_ARG;
+  vba_ctx *c = src_db->ctx;
+  if (c->n_ranks > 1) { c->set_error("vba_debug_btc_icp_pass runs the ICP of one device: unsharded contexts only"); return VBA_ERR_UNSUPPORTED; }
+  HIPCHK(c, hipSetDevice(c->device));
+  const BtcIcpClouds cl = btc_icp_clouds(src_db, src_frame, tar_db, tar_frame);
+  BtcIcpPlan plan;
+  if (!btc_icp_plan(cl, slices, &plan)) return VBA_ERR_BAD_ARG;      // a slice count outside the plan: nothing is touched
+  const int nb = plan.nb;
+  int st = btc_icp_ensure(c, cl, plan);                 // (the caller's partial is copied into the production buffer below)
+  if (st) return st;
+  HIPCHK(c, c->sat->btc.d_icp.ensure(1));
+  HIPCHK(c, c->sat->btc.h_icp.ensure(1));
+  // the taps in buffers of this call: [sums 35 | dx 6] doubles, [merged key ns] words, [gate ns] bytes.  Each starts as the caller's
+  // array, so a launch that returns at once leaves the caller's values.
+  const size_t ns = (size_t)cl.ns;
+  DevMem<double> d_out;
+  DevMem<unsigned long long> d_key;
+  DevMem<unsigned char> d_gate;
+  HIPCHK(c, d_out.ensure(BTC_ICP_PART + 6));
+  HIPCHK(c, d_key.ensure(ns ? ns : 1));
+  HIPCHK(c, d_gate.ensure(ns ? ns : 1));
+  hipStream_t s = c->stream;
+  HIPCHK(c, hipStreamSynchronize(s));
+  BtcIcpDev *h = c->sat->btc.h_icp;
+  std::memcpy(h, state, sizeof(*h));
+  HIPCHK(c, hipMemcpyAsync(c->sat->btc.d_icp, h, sizeof(*h), hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemsetAsync(d_out.p, 0, (BTC_ICP_PART + 6) * sizeof(double), s));
+  if (sums) HIPCHK(c, hipMemcpyAsync(d_out.p, sums, BTC_ICP_PART * sizeof(double), hipMemcpyHostToDevice, s));
+  if (dx) HIPCHK(c, hipMemcpyAsync(d_out.p + BTC_ICP_PART, dx, 6 * sizeof(double), hipMemcpyHostToDevice, s));
+  if (partial) HIPCHK(c, hipMemcpyAsync(c->sat->btc.d_icppart, partial, (size_t)nb * BTC_ICP_PART * sizeof(double), hipMemcpyHostToDevice, s));
+  if (key && ns) HIPCHK(c, hipMemcpyAsync(d_key.p, key, ns * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+  if (gate && ns) HIPCHK(c, hipMemcpyAsync(d_gate.p, gate, ns, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipStreamSynchronize(s));                   // (the caller's arrays are pageable: nothing of them stays in flight)
+  BtcIcpTaps taps;
+  taps.key = d_key.p; taps.gate = d_gate.p; taps.sums = d_out.p; taps.dx = d_out.p + BTC_ICP_PART;
+  st = btc_icp_pass(c, cl, slices, taps, slices_used);
+  if (st) { hipStreamSynchronize(s); return st; }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(h, c->sat->btc.d_icp, sizeof(*h), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  hipError_t e = hipSuccess;
+  if (sums) e = hipMemcpy(sums, d_out.p, BTC_ICP_PART * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && dx) e = hipMemcpy(dx, d_out.p + BTC_ICP_PART, 6 * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && partial) e = hipMemcpy(partial, c->sat->btc.d_icppart, (size_t)nb * BTC_ICP_PART * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && key && ns) e = hipMemcpy(key, d_key.p, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && gate && ns) e = hipMemcpy(gate, d_gate.p, ns, hipMemcpyDeviceToHost);
+  HIPCHK(c, e);
+  std::memcpy(state, h, sizeof(*h));
   return VBA_OK;
 }
 

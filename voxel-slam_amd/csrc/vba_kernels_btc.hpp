@@ -20,6 +20,7 @@
 #include "vba_types.hpp"
 #include "vba_common.hpp"
 #include "vba_btc_svd.hpp"
+#include "vba_icp_math.hpp"
 
 namespace vba {
 
@@ -46,11 +47,6 @@ __device__ __forceinline__ int btc_lookup(const BtcIndex &ix, int x, int y, int 
 __device__ __forceinline__ double btc_bsim(unsigned long long a, unsigned long long b, int sa, int sb) {
   BTC_NOCONTRACT
   return 2.0 * (double)__popcll(a & b) / (double)(sa + sb);
-}
-
-__device__ __forceinline__ double btc_norm3(double x, double y, double z) {
-  BTC_NOCONTRACT
-  return sqrt(x * x + y * y + z * z);
 }
 
 // candidate_selector, the search over the 27 cells around each query descriptor (BTC.cpp:1160-1224).  One wave per (query i,
@@ -317,7 +313,9 @@ __global__ void k_btc_scatter(int n, const int *pairs, int *dst) {
 }
 
 // ------------------------------------------------------------------------------------------------ icp_normal (loop_refine.hpp:47-139)
-constexpr int BTC_ICP_PART = 35;   // Hess (21, upper) | JacT (6) | resi | match_num | mat_norm (6)
+// The per-point and per-step arithmetic is vba_icp_math.hpp (shared with the g++ build of the tests); the kernels below own the 1-NN
+// search, the slice plan and the order of the sums.  The outputs marked "tap" are null in vba_btc_icp_normal and are what
+// vba_debug_btc_icp_pass reads back.
 
 // 1-NN of every transformed source point within one slice of the target (gridDim.y slices); key per (slice, point)
 __global__ __launch_bounds__(256) void k_btc_icp_nn(int ns, const float *src, int nt, const float *tar, const BtcIcpDev *st, unsigned long long *key) {
@@ -325,23 +323,19 @@ __global__ __launch_bounds__(256) void k_btc_icp_nn(int ns, const float *src, in
   __shared__ float tx[256], ty[256], tz[256];
   if (st->done) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
-  float qx = 0, qy = 0, qz = 0;
-  if (i < ns) {
-    const double x = src[6 * (size_t)i], y = src[6 * (size_t)i + 1], z = src[6 * (size_t)i + 2];
-    qx = (float)(((st->R[0] * x + st->R[1] * y) + st->R[2] * z) + st->t[0]);
-    qy = (float)(((st->R[3] * x + st->R[4] * y) + st->R[5] * z) + st->t[1]);
-    qz = (float)(((st->R[6] * x + st->R[7] * y) + st->R[8] * z) + st->t[2]);
-  }
+  float q[3] = {0, 0, 0};
+  if (i < ns) btc_icp_query(st->R, st->t, src + 6 * (size_t)i, q);
   const int ntile = (nt + 255) / 256, per = (ntile + (int)gridDim.y - 1) / (int)gridDim.y;
   const int lo = (int)blockIdx.y * per * 256, hi = (lo + per * 256 < nt) ? lo + per * 256 : nt;
-  unsigned long long b = btc_nn_tile(qx, qy, qz, tar, lo < nt ? lo : nt, hi, tx, ty, tz);
+  unsigned long long b = btc_nn_tile(q[0], q[1], q[2], tar, lo < nt ? lo : nt, hi, tx, ty, tz);
   if (b != ~0ull) b += (unsigned)lo;                     // slice-local index -> cloud index (same distance bits)
   if (i < ns) key[(size_t)blockIdx.y * ns + i] = b;
 }
 
-// merge the slices, gate, accumulate the point-to-plane normal equations: per-workgroup partials [nb][35] (fixed tree)
+// merge the slices, gate, accumulate the point-to-plane normal equations: per-workgroup partials [nb][35] (fixed tree).
+// Taps: mkey[ns] the merged key, gate[ns] 1 where the point entered the sums.
 __global__ __launch_bounds__(256) void k_btc_icp_accum(int ns, const float *src, const float *tar, int slices, const unsigned long long *key,
-                                                      const BtcIcpDev *st, double *part) {
+                                                      const BtcIcpDev *st, double *part, unsigned long long *mkey, unsigned char *gate) {
   BTC_NOCONTRACT
   __shared__ double red[4][BTC_ICP_PART];
   if (st->done) return;
@@ -352,39 +346,10 @@ __global__ __launch_bounds__(256) void k_btc_icp_accum(int ns, const float *src,
   if (i < ns) {
     unsigned long long b = ~0ull;
     for (int sl = 0; sl < slices; sl++) { const unsigned long long k = key[(size_t)sl * ns + i]; b = k < b ? k : b; }
-    if (b != ~0ull) {
-      const double *R = st->R, *t = st->t, *pa = st->paras;
-      const float *sp = src + 6 * (size_t)i, *tp = tar + 6 * (size_t)(unsigned)(b & 0xFFFFFFFFull);
-      const double x = sp[0], y = sp[1], z = sp[2];
-      double pi[3], ni[3];
-      for (int r = 0; r < 3; r++) {
-        pi[r] = ((R[3 * r] * x + R[3 * r + 1] * y) + R[3 * r + 2] * z) + t[r];
-        ni[r] = (R[3 * r] * sp[3] + R[3 * r + 1] * (double)sp[4]) + R[3 * r + 2] * (double)sp[5];
-      }
-      const double tn[3] = {tp[3], tp[4], tp[5]};
-      const double dv[3] = {pi[0] - (double)tp[0], pi[1] - (double)tp[1], pi[2] - (double)tp[2]};
-      const double ninc = btc_norm3(ni[0] - tn[0], ni[1] - tn[1], ni[2] - tn[2]), nadd = btc_norm3(ni[0] + tn[0], ni[1] + tn[1], ni[2] + tn[2]);
-      const double p2p = btc_norm3(dv[0], dv[1], dv[2]);
-      const double rr = (tn[0] * dv[0] + tn[1] * dv[1]) + tn[2] * dv[2];
-      if ((ninc < pa[0] || nadd < pa[1]) && fabs(rr) < pa[2] && p2p < pa[3]) {
-        // jac.head(3) = hat(plocal) R^T tni, jac.tail(3) = tni
-        double H[9];   // hat(p) R^T
-        const double hp[9] = {0, -z, y, z, 0, -x, -y, x, 0};
-        for (int r = 0; r < 3; r++)
-          for (int c = 0; c < 3; c++) H[3 * r + c] = (hp[3 * r] * R[3 * c] + hp[3 * r + 1] * R[3 * c + 1]) + hp[3 * r + 2] * R[3 * c + 2];
-        double j[6];
-        for (int r = 0; r < 3; r++) j[r] = (H[3 * r] * tn[0] + H[3 * r + 1] * tn[1]) + H[3 * r + 2] * tn[2];
-        j[3] = tn[0]; j[4] = tn[1]; j[5] = tn[2];
-        int idx = 0;
-        for (int r = 0; r < 6; r++)
-          for (int c = r; c < 6; c++) s[idx++] = j[r] * j[c];
-        for (int r = 0; r < 6; r++) s[21 + r] = j[r] * rr;
-        s[27] = 0.5 * rr * rr;
-        s[28] = 1.0;
-        s[29] = tn[0] * tn[0]; s[30] = tn[0] * tn[1]; s[31] = tn[0] * tn[2];
-        s[32] = tn[1] * tn[1]; s[33] = tn[1] * tn[2]; s[34] = tn[2] * tn[2];
-      }
-    }
+    bool pass = false;
+    if (b != ~0ull) pass = btc_icp_point(st->R, st->t, st->paras, src + 6 * (size_t)i, tar + 6 * (size_t)(unsigned)(b & 0xFFFFFFFFull), s);
+    if (mkey) mkey[i] = b;
+    if (gate) gate[i] = pass ? 1 : 0;
   }
 #pragma unroll
   for (int k = 0; k < BTC_ICP_PART; k++) s[k] = wave_sum(s[k]);
@@ -395,8 +360,9 @@ __global__ __launch_bounds__(256) void k_btc_icp_accum(int ns, const float *src,
 }
 
 // reduce the partials (in workgroup order), solve Hess dxi = -JacT, update the pose, the convergence / parameter switch
-// (loop_refine.hpp:115-134); after the last iteration the eigenvalues of mat_norm (loop_refine.hpp:135-137)
-__global__ __launch_bounds__(64) void k_btc_icp_step(int nb, const double *part, BtcIcpDev *st) {
+// (loop_refine.hpp:115-134); after the last iteration the eigenvalues of mat_norm (loop_refine.hpp:135-137).
+// Taps: sums[35] the reduced partials, dxo[6] the solved step.
+__global__ __launch_bounds__(64) void k_btc_icp_step(int nb, const double *part, BtcIcpDev *st, double *sums, double *dxo) {
   BTC_NOCONTRACT
   __shared__ double acc[BTC_ICP_PART];
   if (st->done) return;
@@ -405,27 +371,14 @@ __global__ __launch_bounds__(64) void k_btc_icp_step(int nb, const double *part,
     double a = 0;
     for (int b = 0; b < nb; b++) a += part[(size_t)b * BTC_ICP_PART + tid];
     acc[tid] = a;
+    if (sums) sums[tid] = a;
   }
   __syncthreads();
   if (tid != 0) return;
-  double H[36], g[6], dx[6];
-  int idx = 0;
-  for (int r = 0; r < 6; r++)
-    for (int c = r; c < 6; c++) { H[6 * r + c] = acc[idx]; H[6 * c + r] = acc[idx]; idx++; }
-  for (int r = 0; r < 6; r++) g[r] = -acc[21 + r];
-  vbh::ldlt_solve_fixed<6>(H, g, dx);
-  double E[9], Rn[9];
-  vbh::so3_exp(dx, E);
-  vbh::m3_mul(st->R, E, Rn);
-  for (int k = 0; k < 9; k++) st->R[k] = Rn[k];
-  for (int k = 0; k < 3; k++) st->t[k] = st->t[k] + dx[3 + k];
-  for (int k = 0; k < 6; k++) st->mat[k] = acc[29 + k];
-  st->iters++;
-  if (btc_norm3(dx[0], dx[1], dx[2]) < 1e-3 && btc_norm3(dx[3], dx[4], dx[5]) < 1e-3) {
-    if (st->is_conv) st->done = 1;
-    else { st->paras[0] = 0.1; st->paras[1] = 0.1; st->paras[2] = 0.1; st->paras[3] = 1; st->is_conv = 1; }
-  }
-  if (st->iters >= 20) st->done = 1;
+  double dx[6];
+  btc_icp_solve_update(acc, st->R, st->t, st->mat, dx);
+  if (dxo) for (int k = 0; k < 6; k++) dxo[k] = dx[k];
+  btc_icp_transition(dx, st->paras, &st->is_conv, &st->done, &st->iters);
   if (st->done) {
     const double *m = st->mat;
     Eig3 e;
