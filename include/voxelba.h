@@ -81,6 +81,13 @@ typedef struct vba_options {
   int hessian_workgroups;           /* persistent workgroups of the Hessian pass, 2..256 (default 256 = one per CU) */
   int residual_vpl_from;            /* residual pass: stores with more voxels use the voxel-per-lane kernel (default 45000) */
   int hessian_compact_tiles;        /* != 0: Hessian pass on occupancy-compact tiles (k_hessian3, W <= 10) instead of dense fixed-size ones; measured slower at the bench size */
+  /* (this field occupies what was alignment padding behind the five ints above: no other field moves, the size is unchanged)
+     Lidar LM iteration on one rank: 0 (default) = the solve and the residual pass of the trial poses share ONE launch (k_lm_trial) where
+     the window's kernel allows it; 2 = always the two launches k_lm_solve_m + k_residual_s.  Results are bit-identical.
+     A residual workgroup of the fused launch waits for the solve's poses for at most 20 ms; one that gives up rejects the step and marks the
+     LM state, and the next call that fetches that state (vba_lm_end with an output, vba_lm_iterate with accepted / stop,
+     vba_lidar_ba_damping_iter) returns VBA_ERR_HIP with vba_last_error naming k_lm_trial. */
+  int lm_trial_launches;
   size_t max_map_nodes;             /* map capacity hints (0 = grow on demand): octree nodes and fixed (marginalised) points the map is */
   size_t max_fix_points;            /* sized for at the first insertion — a session that stays below them never re-allocates (no stalls) */
   int hba_workers;                  /* vba_hba_global on one rank: bottom-layer windows optimised side by side by this many worker contexts (0 = default 4, 1 = one after the other) */

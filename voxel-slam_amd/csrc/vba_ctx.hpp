@@ -89,6 +89,7 @@ struct vba_ctx {
   bool force_collective = false;  // vba_options::force_collective (rehearsal: run the exchange step with one rank)
   int max_blocks_hess = 256;      // vba_options::hessian_workgroups
   int residual_vpl_from = 45000;  // vba_options::residual_vpl_from
+  bool lm_trial_fused = true;     // vba_options::lm_trial_launches != 2: solve + residual pass of the trial poses in one launch (k_lm_trial)
   bool use_h3 = false;            // vba_options::hessian_compact_tiles != 0
   ncclComm_t comm = nullptr;      // RCCL communicator: the exchange step is issued by the library on the context's stream
   bool own_comm = false;

@@ -9,6 +9,7 @@
 #include "vba_types.hpp"
 #include "vba_common.hpp"
 #include "vba_hess_units.hpp"
+#include <type_traits>
 
 namespace vba {
 
@@ -142,19 +143,32 @@ struct ResCfg {
   static_assert(W * 12 <= NT, "one thread per pose scalar");
 };
 
-template <int W, int TV, bool STAMPS>
-__global__ __launch_bounds__((ResCfg<W, TV>::NT)) void k_residual_s(FactorView f, const double *__restrict__ poses, int head, int end,
-                                                                  double *__restrict__ partial, const int *__restrict__ gate,
-                                                                  long long *__restrict__ stamps, LmInit<W> init) {
+// The pass' LDS, one object so that k_lm_trial (vba_kernels_lm.hpp) can overlay it with the solve's.
+template <int W, int TV>
+struct ResLds {                                                 // (every array 16-byte aligned, as arrays of their own are: wide LDS reads)
+  alignas(16) double T[10][W][TV];                              // world-frame cluster of every slot (zeros for empty slots)
+  alignas(16) double S[10][TV];                                 // pcr_add of every voxel
+  alignas(16) double sp[W * 12];
+};
+struct NoRider {};                                              // the stand-alone kernel: poses and gate come from its arguments
+
+// The body of k_residual_s for workgroup `bid` (its first ResCfg::NT threads).  With a RIDER (k_lm_trial: LmTrialRider) the
+// workgroup shares a launch with the solve that produces its poses: `poses`, `gate` and `init` are unused, the rider requests the LM
+// flags with trip 1, the gate is theirs, and in front of the barrier that publishes sp it waits for the solve's hand-off where one is
+// due (see k_lm_trial).  Everything else, the order of every sum included, is the same code.
+template <int W, int TV, bool STAMPS, class RIDER>
+__device__ __forceinline__ void residual_s_body(ResLds<W, TV> &L, const int bid, const FactorView &f, const double *__restrict__ poses, int head, int end,
+                                                double *__restrict__ partial, const int *__restrict__ gate, long long *__restrict__ stamps,
+                                                const LmInit<W> &init, RIDER rider) {
   using C = ResCfg<W, TV>;
-  __shared__ double T[10][W][TV];                               // world-frame cluster of every slot (zeros for empty slots)
-  __shared__ double S[10][TV];                                  // pcr_add of every voxel
-  __shared__ double sp[W * 12];
+  constexpr bool RIDES = !std::is_same<RIDER, NoRider>::value;
+  auto &T = L.T; auto &S = L.S; auto &sp = L.sp;
   // The gate (a flag the previous kernel wrote, ~2 us away on another XCD) and the first round of loads are requested
   // TOGETHER; the early exit is taken only after both are back, so a live pass pays one memory trip here, not two.
-  const int gate_v = gate ? *gate : 1;
+  int gate_v = 1;
+  if constexpr (!RIDES) gate_v = gate ? *gate : 1;
   const int tid = threadIdx.x, vl = tid % TV, fi = tid / TV;
-  const int v = head + blockIdx.x * TV + vl;
+  const int v = head + bid * TV + vl;
   const size_t vs = (size_t)f.vs, fs = (size_t)W * vs;
   const int vc = v < end ? v : end - 1;                         // clamped: trip 1 is issued unconditionally (end > head)
   const int fic = fi < W ? fi : W - 1;
@@ -162,23 +176,42 @@ __global__ __launch_bounds__((ResCfg<W, TV>::NT)) void k_residual_s(FactorView f
   if (STAMPS) st0 = clock64();
   // ---- trip 1: the voxel's occupancy mask, this thread's scalars of the fixed cluster, coe (row 0), the poses
   const unsigned int occm = f.occ[vc];
-  const double pose_s = init.on ? init.x[tid < W * 12 ? tid : 0] : poses[tid < W * 12 ? tid : 0];
+  double pose_s;
+  if constexpr (RIDES) pose_s = rider.request(W * 12, tid);     // the LM flags, and xt as it stands (valid when a candidate was installed)
+  else pose_s = init.on ? init.x[tid < W * 12 ? tid : 0] : poses[tid < W * 12 ? tid : 0];
   double acc[C::KPT];
 #pragma unroll
   for (int j = 0; j < C::KPT; j++) { const int k = fi + j * C::NF; acc[j] = f.fix[(size_t)(k < 10 ? k : 9) * vs + vc]; }
   double coe = f.coe[vc];
   unsigned int occv = occm;
   asm volatile("" : "+v"(occv), "+v"(coe), "+v"(acc[0]));       // keep the loads above the exit (they would be sunk below it)
+  if constexpr (RIDES) gate_v = rider.run();
   if (gate_v == 0) return;
-  if (tid < W * 12) sp[tid] = pose_s;
+  if constexpr (!RIDES) { if (tid < W * 12) sp[tid] = pose_s; }
   // ---- trip 2: the 10 scalars of an occupied slot (an empty slot costs nothing beyond its mask bit)
   const bool occ = fi < W && v < end && ((occv >> fic) & 1u);
   double c[9], n = 0.0;
 #pragma unroll
   for (int k = 0; k < 9; k++) c[k] = occ ? f.cl[(size_t)k * fs + (size_t)fi * vs + v] : 0.0;
   if (occ) n = f.cl[9 * fs + (size_t)fi * vs + v];
+  if constexpr (RIDES) {
+    // trip 2 is in flight and asks nothing of the solve.  A candidate-served step has its poses already; otherwise the workgroup waits
+    // (bounded) for the hand-off and takes the 12 W words with agent-scope loads.  A rider that gives up poisons its partial (the
+    // step is then rejected, never accepted on stale poses), raises the fault word and leaves.
+    if (!rider.have_xt()) {
+#pragma unroll
+      for (int k = 0; k < 9; k++) asm volatile("" : "+v"(c[k]));
+      asm volatile("" : "+v"(n));                                // (the requests stay in front of the wait)
+      if (!rider.wait(tid)) {
+        if (tid == 0) { partial[bid] = __builtin_nan(""); rider.fault(); }
+        return;
+      }
+      pose_s = rider.xt(W * 12, tid);
+    }
+    if (tid < W * 12) sp[tid] = pose_s;
+  }
   __syncthreads();
-  if (init.on && blockIdx.x == 0) lm_init_store_lds<W, C::NT>(sp, init.dst, init.dbg, tid);   // the image from sp: stores only, beside trip 2
+  if constexpr (!RIDES) { if (init.on && bid == 0) lm_init_store_lds<W, C::NT>(sp, init.dst, init.dbg, tid); }   // the image from sp: stores only, beside trip 2
   if (occ) {
     const Cl10 w = cluster_transform_exact(c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], n, sp + 12 * fi);   // tools.hpp:357-363
     T[0][fi][vl] = w.p00; T[1][fi][vl] = w.p10; T[2][fi][vl] = w.p20; T[3][fi][vl] = w.p11; T[4][fi][vl] = w.p21; T[5][fi][vl] = w.p22;
@@ -224,13 +257,21 @@ __global__ __launch_bounds__((ResCfg<W, TV>::NT)) void k_residual_s(FactorView f
   }
   if (tid < 64) {
     r = wave_sum_to_lane63(r);
-    if (tid == 63) partial[blockIdx.x] = r;
-    if (STAMPS && tid == 0 && blockIdx.x < 2048) {
+    if (tid == 63) partial[bid] = r;
+    if (STAMPS && tid == 0 && bid < 2048) {
       st3 = clock64();
-      long long *o = stamps + (size_t)blockIdx.x * 4;
+      long long *o = stamps + (size_t)bid * 4;
       o[0] = st0; o[1] = st1; o[2] = st2; o[3] = st3;
     }
   }
+}
+
+template <int W, int TV, bool STAMPS>
+__global__ __launch_bounds__((ResCfg<W, TV>::NT)) void k_residual_s(FactorView f, const double *__restrict__ poses, int head, int end,
+                                                                  double *__restrict__ partial, const int *__restrict__ gate,
+                                                                  long long *__restrict__ stamps, LmInit<W> init) {
+  __shared__ ResLds<W, TV> L;
+  residual_s_body<W, TV, STAMPS, NoRider>(L, blockIdx.x, f, poses, head, end, partial, gate, stamps, init, NoRider{});
 }
 
 // Voxel-per-lane form of the pass — used for LARGE stores (throughput-bound: V > kResidualVoxelPerLane in voxelba.hip) — for stores in OCCUPANCY-MASK ORDER (what the map's extraction produces, vba_kernels_map.hpp

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include "vba_types.hpp"
 #include "vba_ldlt.hpp"
+#include "vba_kernels_factor.hpp"
 
 namespace vba {
 
@@ -19,7 +20,8 @@ struct LmDev {
   double trace[5 * 64];              // rows [r1, r2, u, v, q1]
   long long stamps[64];              // diagnostic (VBA_DEBUG_SOLVE bit 16)
   // speculative damping (see k_lm_solve_m): trial poses / q1 for the damping values the next LM_SPEC - 1 consecutive rejections would use
-  int spec_n, spec_i, use_spec, pad2;
+  int spec_n, spec_i, use_spec, xt_seq;      // xt_seq: the in-launch hand-off of xt (k_lm_trial): iter + 1 of the solve that stored it
+  int trial_fault, pad3;                     // trial_fault: a rider of k_lm_trial gave up its wait for xt_seq (zero in every healthy call)
   double q1_spec[LM_SPEC];
   double xt_spec[LM_SPEC][VBA_MAX_WIN_DEV * 12];
 };
@@ -133,6 +135,13 @@ __device__ __forceinline__ void so3_exp_dev(const double *w, double *R) {   // t
 // sets use_spec; the next launch of this kernel then returns at once.  An accepted step discards the candidates.  No field a
 // workgroup reads on entry is written inside this kernel, so the workgroups need no ordering among themselves.
 
+// A pose word of the trial state.  PUB: an agent-scope (write-through) store, for consumers inside the same launch (k_lm_trial).
+template <bool PUB>
+__device__ __forceinline__ void lm_xt_store(double *p, double v) {
+  if constexpr (PUB) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else *p = v;
+}
+
 // Index of the diagonal-block remainder E that tl_fetch adds to H(row, col), row <= col < 6W; -1 outside the frame's 6 x 6 block.
 template <int W>
 __host__ __device__ __forceinline__ int tl_eidx(int row, int col) {
@@ -147,10 +156,26 @@ __host__ __device__ __forceinline__ int tl_eidx(int row, int col) {
   return C::EB + 21 * fr + idx;
 }
 
-// dx_out (NULL in the LM loop): dx of candidate b to dx_out[b n ..] (vba_debug_solve).
-template <int W, bool COPY_RAW>
-__global__ __launch_bounds__(256) void k_lm_solve_m(LmDev *s, const double *__restrict__ red, double *__restrict__ raw, double *__restrict__ dx_out) {
-  const int sb = blockIdx.x;
+// The solve's LDS, one object so that k_lm_trial can overlay it with the residual pass' (a workgroup there is one or the other).
+template <int W>
+struct LmSolveLds {
+  static constexpr int n = 6 * W, NP = ((n + 1 + 15) / 16) * 16;
+  alignas(16) double lds[LdltCfg<NP>::DOUBLES];
+  alignas(16) double hd[n];                                   // (every array 16-byte aligned, as arrays of their own are: wide LDS reads)
+  alignas(16) double gs[n];
+  alignas(16) double xs[NP];
+  alignas(16) double dxs[n];
+  alignas(16) double red8[8];
+  alignas(16) int ord[n];
+};
+
+// The body of k_lm_solve_m for damping candidate sb of nspec (the workgroup's first 256 threads).  dx_out (NULL in the LM loop): dx of
+// candidate b to dx_out[b n ..] (vba_debug_solve).  PUBLISH (k_lm_trial): candidate 0 hands xt to the residual workgroups of the SAME
+// launch: the pose words go out as agent-scope (write-through) stores, the storing wave drains them, then one lane stores
+// xt_seq = iter + 1 with an agent-scope atomic store.  Arithmetic and order are the same in both forms.
+template <int W, bool COPY_RAW, bool PUBLISH>
+__device__ __forceinline__ void lm_solve_body(LmSolveLds<W> &L, const int sb, const int nspec, LmDev *s, const double *__restrict__ red, double *__restrict__ raw,
+                                              double *__restrict__ dx_out) {
   using C2 = HessCfg2<W>;
   constexpr int n = 6 * W, NT = 256, NP = ((n + 1 + 15) / 16) * 16, NH = (n + 63) / 64, NU = C2::NU, T16 = C2::NT16;
   using LC = LdltCfg<NP>;
@@ -158,9 +183,8 @@ __global__ __launch_bounds__(256) void k_lm_solve_m(LmDev *s, const double *__re
   // padding (NP >= n + 2: row n + 1 is zero left of its diagonal, and (n + 1, 0) serves the upper triangle of the diagonal tiles)
   constexpr int IMG = NP * (NP + 1) / 2, ZERO = (n + 1) * (n + 2) / 2;
   static_assert(IMG <= LC::LTOT && NP >= n + 2, "the image must lie in the L region: ldlt_mfma writes P while the tiles are read");
-  __shared__ __attribute__((aligned(16))) double lds[LC::DOUBLES];
-  __shared__ double hd[n], gs[n], xs[NP], dxs[n], red8[8];
-  __shared__ int ord[n];
+  double *lds = L.lds, *hd = L.hd, *gs = L.gs, *xs = L.xs, *dxs = L.dxs, *red8 = L.red8;
+  int *ord = L.ord;
   double *Lst = lds, *Tp = Lst + LC::LTOT, *P = Tp + NP * LC::LS, *img = lds;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   // flags first: the gate below waits for these loads only
@@ -314,9 +338,15 @@ __global__ __launch_bounds__(256) void k_lm_solve_m(LmDev *s, const double *__re
 #pragma unroll
       for (int r = 0; r < 3; r++)
 #pragma unroll
-        for (int c = 0; c < 3; c++) Rt[3 * r + c] = R[3 * r] * E[c] + R[3 * r + 1] * E[3 + c] + R[3 * r + 2] * E[6 + c];
+        for (int c = 0; c < 3; c++) lm_xt_store<PUBLISH>(Rt + 3 * r + c, R[3 * r] * E[c] + R[3 * r + 1] * E[3 + c] + R[3 * r + 2] * E[6 + c]);
 #pragma unroll
-      for (int k = 0; k < 3; k++) Rt[9 + k] = R[9 + k] + dxs[6 * lane + 3 + k];
+      for (int k = 0; k < 3; k++) lm_xt_store<PUBLISH>(Rt + 9 + k, R[9 + k] + dxs[6 * lane + 3 + k]);
+    }
+    if constexpr (PUBLISH) {
+      if (sb == 0) {                               // this wave stored every word of xt: drain them, then the flag (one lane)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0) __hip_atomic_store(&s->xt_seq, iter0 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
     }
     if (lane == 63) red8[3] = 0.0;                 // (the wave sum of no rows)
   } else {
@@ -329,9 +359,15 @@ __global__ __launch_bounds__(256) void k_lm_solve_m(LmDev *s, const double *__re
   if (tid == 0) {
     const double q1 = 0.5 * (red8[0] + red8[1] + red8[2] + red8[3]);
     s->q1_spec[sb] = q1;
-    if (sb == 0) { s->q1 = q1; s->spec_n = gridDim.x; s->spec_i = 0; }
+    if (sb == 0) { s->q1 = q1; s->spec_n = nspec; s->spec_i = 0; }
   }
   if (stamps) stamps[5] = clock64();
+}
+
+template <int W, bool COPY_RAW>
+__global__ __launch_bounds__(256) void k_lm_solve_m(LmDev *s, const double *__restrict__ red, double *__restrict__ raw, double *__restrict__ dx_out) {
+  __shared__ LmSolveLds<W> L;
+  lm_solve_body<W, COPY_RAW, false>(L, blockIdx.x, gridDim.x, s, red, raw, dx_out);
 }
 
 // (Round 3 tried two single-wave forms of this solve for n <= 64 — lane i owns row i, no barriers, no tiles — and measured both slower on
@@ -339,6 +375,80 @@ __global__ __launch_bounds__(256) void k_lm_solve_m(LmDev *s, const double *__re
 //  operation costs ~50 cycles with one wave per SIMD, so the 60 pivot steps are a ~350-cycle chain each: readlane, reciprocal + two
 //  Newton steps, scale, first update), rows in LDS with rolled loops 62 us (every read-modify-write of a row element waits for its
 //  own LDS round trip).  The blocked kernel's panel of 8 columns amortises that chain over 8 pivots.)
+
+// ------------------------------------------------------------------------------------------------
+// k_lm_trial: the solve and the residual pass of the trial poses in ONE launch (single rank, slot-parallel residual kernel).
+// The seam between the two is 1 -> all: candidate 0's workgroup produces the 12 W words of xt, every residual workgroup consumes them,
+// and everything else the residual pass reads (occupancy masks, fixed clusters, coe, the occupied slots' scalars) no kernel writes
+// during an LM call.  So the residual workgroups ("riders", blocks nspec ..) are launched WITH the solve (blocks 0 .. nspec - 1,
+// dispatched first), make both of their memory trips while it runs, and then wait for one word:
+//   producer  lm_solve_body<PUBLISH>: xt as agent-scope stores, s_waitcnt vmcnt(0) on the storing wave, xt_seq = iter + 1 (agent-scope
+//             atomic store, one lane).  iter grows with every step that is not stopped, and the call's init image zeroes xt_seq, so the
+//             value a rider waits for is stored by this launch's solve and by nothing earlier.
+//   consumer  one lane per workgroup polls xt_seq (relaxed agent-scope loads, s_sleep between them), the workgroup's barrier publishes
+//             the outcome, then EVERY pose word is read with an agent-scope load (they bypass the CU's L1: no acquire fence needed).
+// No wait where none is due: run_res == 0 (stopped) -> the rider returns after trip 1; use_spec != 0 (the previous Hessian pass
+// installed a candidate, the solve of this launch returns at once) -> xt is valid as launched, and was requested with trip 1.
+// run_res, stop, use_spec and iter were written before the launch and nothing inside it writes them.
+// The wait is bounded: 20 ms of the 100 MHz wall clock (the longest solve this kernel is launched with, W = 10, lasts 20 us: three
+// orders of magnitude; wider windows keep the two launches, voxelba.hip LmTrialFits).  A rider that gives up stores NaN as its
+// partial (r1 - NaN > 0 is false: the step is rejected), sets LmDev::trial_fault, and the next call that fetches the state reports it.
+// The bound only turns a surprise into an error: the riders cannot keep the solve from running, its workgroups are dispatched first.
+constexpr long long kLmTrialWaitTicks = 2000000;            // 20 ms at 100 MHz
+
+struct LmTrialRider {
+  LmDev *s;
+  int *ok_lds;                                              // one LDS word of the workgroup: the poll's outcome
+  int run_res, stop, use_spec, iter;
+  __device__ __forceinline__ double request(int npose, int tid) {
+    run_res = s->run_res; stop = s->stop; use_spec = s->use_spec; iter = s->iter;
+    return __hip_atomic_load(&s->xt[tid < npose ? tid : 0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ int run() const { return (run_res != 0 && stop == 0) ? 1 : 0; }
+  __device__ __forceinline__ bool have_xt() const { return use_spec != 0; }
+  __device__ __forceinline__ bool wait(int tid) const {
+    if (tid == 0) {
+      const int want = iter + 1;
+      int ok = 1;
+      const long long t0 = wall_clock64();
+      while (__hip_atomic_load(&s->xt_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != want) {
+        __builtin_amdgcn_s_sleep(8);
+        if (wall_clock64() - t0 > kLmTrialWaitTicks) { ok = 0; break; }
+      }
+      *ok_lds = ok;
+    }
+    __syncthreads();
+    return *ok_lds != 0;
+  }
+  __device__ __forceinline__ double xt(int npose, int tid) const {
+    return __hip_atomic_load(&s->xt[tid < npose ? tid : 0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ void fault() const { __hip_atomic_store(&s->trial_fault, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+};
+
+template <int W, int TV>
+struct LmTrialCfg {
+  static constexpr int RNT = ResCfg<W, TV>::NT, BS = RNT > 256 ? RNT : 256;     // threads of a rider, of any workgroup
+  union Lds { LmSolveLds<W> solve; ResLds<W, TV> res; };                        // a workgroup is one or the other
+};
+
+// One launch of nspec + residual workgroups; the partials are the residual pass', one per rider in the same order.
+template <int W, bool COPY_RAW = false, int TV = 32>
+__global__ __launch_bounds__((LmTrialCfg<W, TV>::BS)) void k_lm_trial(LmDev *s, const double *__restrict__ red, double *__restrict__ raw, int nspec, FactorView f,
+                                                                    int head, int end, double *__restrict__ partial) {
+  using TC = LmTrialCfg<W, TV>;
+  __shared__ typename TC::Lds L;
+  __shared__ int wait_ok;
+  if ((int)blockIdx.x < nspec) {
+    if (threadIdx.x >= 256) return;                         // (whole waves)
+    lm_solve_body<W, COPY_RAW, true>(L.solve, blockIdx.x, nspec, s, red, raw, nullptr);
+  } else {
+    if (threadIdx.x >= TC::RNT) return;
+    LmInit<W> none;
+    none.on = 0;
+    residual_s_body<W, TV, false, LmTrialRider>(L.res, (int)blockIdx.x - nspec, f, nullptr, head, end, partial, nullptr, nullptr, none, LmTrialRider{s, &wait_ok});
+  }
+}
 
 // Accept / reject bookkeeping of VM:467-494 (one thread).  r2_dev = the reduced residual of the trial poses.
 // nb > 0: r2 is first summed here from the residual pass' nb workgroup partials (single rank: saves one launch);

@@ -560,6 +560,7 @@ int vba_create(const vba_options *opt, vba_ctx **out) {
   c->max_blocks_hess = opt->hessian_workgroups > 0 ? std::min(opt->hessian_workgroups, kMaxBlocksHess) : kMaxBlocksHess;
   if (c->max_blocks_hess < 2) c->max_blocks_hess = 2;      // (LI-BA gives one workgroup's CU to the IMU factors)
   c->residual_vpl_from = opt->residual_vpl_from > 0 ? opt->residual_vpl_from : 45000;
+  c->lm_trial_fused = opt->lm_trial_launches != 2;
   c->use_h3 = opt->hessian_compact_tiles != 0 && opt->deterministic == 0;   // (k_hessian3 adds into LDS with f64 atomics)
   if (opt->stream) { c->stream = (hipStream_t)opt->stream; c->own_stream = false; }
   else {
@@ -756,6 +757,36 @@ int vba_timing_launch_hessian(vba_ctx *c) {
   return VBA_OK;
 }
 
+// k_lm_trial (vba_kernels_lm.hpp) takes the place of the solve + residual pair of a single-rank iteration where its workgroups can all be
+// resident beside the solve.  Windows whose instance would not fit three workgroups of a CU's registers and LDS keep the two launches
+// (LmTrialFits, from the kernel's resource usage: DESIGN.md 5), and so do the multi-rank flow, stores the voxel-per-lane residual kernel
+// serves, an empty store, the diagnostic stamp instances and contexts created with vba_options::lm_trial_launches = 2.
+extern "C++" {
+template <int W>
+struct LmTrialFits { static constexpr bool value = sizeof(typename LmTrialCfg<W, VBA_K4_TV>::Lds) + 16 <= 160 * 1024 / 3 && LmTrialCfg<W, VBA_K4_TV>::BS <= 320; };
+static bool lm_trial_fused(vba_ctx *c, int V, int nb, int copy_raw) {
+  if (!c->lm_trial_fused || copy_raw || V <= 0 || residual_vpl(c, V) || c->lm_init.dbg != 0 || k4_stamps_buffer(c)) return false;
+  bool fits = false;
+  for_window<2, 16>(c->opt.win_size, [&](auto wc) { fits = LmTrialFits<decltype(wc)::value>::value; return VBA_OK; });
+  if (!fits) return false;
+  // every workgroup resident at once: three per CU (registers and LDS, above) on the device's CUs
+  static std::atomic<int> cus[kMaxDevices] = {};
+  const bool known = c->device >= 0 && c->device < kMaxDevices;
+  int n = known ? cus[c->device].load(std::memory_order_relaxed) : 0;
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || n <= 0) return false;
+    if (known) cus[c->device].store(n, std::memory_order_relaxed);
+  }
+  return c->lm_spec + nb <= 3 * n;
+}
+// The fetched LmDev image says whether a rider of k_lm_trial gave up its bounded wait (it never should): the call that fetched it fails.
+static bool lm_trial_fault_seen(vba_ctx *c) {
+  if (c->h_lm->trial_fault == 0) return false;
+  c->set_error("k_lm_trial: a residual workgroup gave up waiting for the solve's trial poses (the step was rejected)");
+  return true;
+}
+}  // extern "C++"
+
 // One trip through the loop body VM:441-494, enqueued without host synchronisation unless the caller asks for the flags.
 int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
   if (!c->lm.active) return VBA_ERR_BAD_ARG;
@@ -772,11 +803,22 @@ int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
     c->lm.pending_update = false;
   }
   if (st) return st;
+  const int nb = residual_nb(c, V);
+  if (!copy_raw && (size_t)nb > c->d_k4part.n) {
+    if (c->d_k4part) HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->d_k4part.ensure(nb > 65536 ? 2 * (size_t)nb : 65536));
+  }
+  const bool fused_trial = lm_trial_fused(c, V, nb, copy_raw);
   TimedSpan sp{};
-  span_begin(c, "solve", sp);
+  span_begin(c, "solve", sp);        // (the fused launch is bracketed as "solve": "residual" spans then cover stand-alone passes only)
   st = for_window<2, 16>(W, [&](auto wc) {
     constexpr int WW = decltype(wc)::value;
-    if (copy_raw) hipLaunchKernelGGL((k_lm_solve_m<WW, true>), dim3(c->lm_spec), dim3(256), 0, c->stream, c->d_lm, c->d_out, c->d_raw, nullptr);
+    if (fused_trial) {
+      if constexpr (LmTrialFits<WW>::value)
+        hipLaunchKernelGGL((k_lm_trial<WW, false, VBA_K4_TV>), dim3(c->lm_spec + nb), dim3(LmTrialCfg<WW, VBA_K4_TV>::BS), 0, c->stream, c->d_lm, c->d_out, c->d_raw, c->lm_spec,
+                           c->fv, 0, V, c->d_k4part.p);
+    }
+    else if (copy_raw) hipLaunchKernelGGL((k_lm_solve_m<WW, true>), dim3(c->lm_spec), dim3(256), 0, c->stream, c->d_lm, c->d_out, c->d_raw, nullptr);
     else hipLaunchKernelGGL((k_lm_solve_m<WW, false>), dim3(c->lm_spec), dim3(256), 0, c->stream, c->d_lm, c->d_out, c->d_raw, nullptr);
     return VBA_OK;
   });
@@ -786,17 +828,14 @@ int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
     st = sharded_trial_step(c, p, V, [&](const double *r) { hipLaunchKernelGGL(k_lm_update, dim3(1), dim3(64), 0, c->stream, c->d_lm, r, 0, W); });
     if (st) return st;
   } else {
-    const int nb = residual_nb(c, V);
-    if ((size_t)nb > c->d_k4part.n) {
-      if (c->d_k4part) HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, c->d_k4part.ensure(nb > 65536 ? 2 * (size_t)nb : 65536));
-    }
     const bool fuse = !no_fuse && !(accepted || stop);
-    TimedSpan s1{};
-    span_begin(c, "residual", s1);
-    st = launch_residual(c, p.xt, p.run_res, 0, V, c->d_k4part);
-    if (st) return st;
-    span_end(c, "residual", s1);
+    if (!fused_trial) {
+      TimedSpan s1{};
+      span_begin(c, "residual", s1);
+      st = launch_residual(c, p.xt, p.run_res, 0, V, c->d_k4part);
+      if (st) return st;
+      span_end(c, "residual", s1);
+    }
     if (fuse) { c->lm.pending_update = true; c->lm.k4_nb = nb; }
     else hipLaunchKernelGGL(k_lm_update, dim3(1), dim3(64), 0, c->stream, c->d_lm, c->d_k4part, nb, W);   // sums the partials itself
   }
@@ -806,6 +845,7 @@ int vba_lm_iterate(vba_ctx *c, int *accepted, int *stop) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (accepted) *accepted = c->h_lm->last_accepted;
     if (stop) *stop = c->h_lm->stop;
+    if (lm_trial_fault_seen(c)) return VBA_ERR_HIP;
   }
   return VBA_OK;
 }
@@ -849,6 +889,7 @@ int vba_lm_end(vba_ctx *c, double *poses, double *hess, double *resis2) {
   c->trace.assign(h->trace, h->trace + 5 * h->n_trace);
   solve_cycles_dump("k_lm_solve_m", h, 8);
   c->lm.active = false;
+  if (lm_trial_fault_seen(c)) return VBA_ERR_HIP;
   return VBA_OK;
 }
 
