@@ -121,6 +121,20 @@ def _small_scene():
     return np.concatenate([g] + posts)
 
 
+@pytest.mark.parametrize("n", [8191, 8192, 8193, 16385])
+def test_point_counts_at_the_scan_chunk_edges(capi, ctx, n):
+    """the voxel pass scans one flag per point with the one-workgroup chunked scan (k_bg_scan: chunks of 8192 entries linked by a
+    carry): a last chunk that is one entry short, full, and one entry long, and a third chunk of one entry.  Six copies of the small
+    scene cut to n points; every voxel start, and so every plane, corner and row, follows from the scanned positions."""
+    scene = np.concatenate([_small_scene() + [14.0 * i, 14.0 * j, 0.0] for i in range(3) for j in range(2)]).astype(np.float32)
+    assert len(scene) > 16385
+    db = make_db(capi, ctx, 0)
+    ref = bg.generate_stds(scene[:n], 0, bg.read_parameters(0))
+    assert len(ref["planes"]) > 0 and len(ref["rows"]) > 0
+    check_equal(db, db.generate_stds(scene[:n], 0), ref, 0)
+    db.close()
+
+
 def test_quirks_on_device(capi, ctx):
     """the section-3 quirks on the device, each on a crafted cloud compared bit for bit with the restatement"""
     cfg = bg.read_parameters(0)

@@ -43,6 +43,27 @@ def test_down_sampling_voxel_parity(oracle, n, voxel):
     ctx.close()
 
 
+@pytest.mark.parametrize("flags", ["all", "alternating"])
+@pytest.mark.parametrize("n", [1, 255 * 256 + 1, 256 * 256 + 1])
+def test_down_sampling_voxel_at_the_scan_edges(oracle, n, flags):
+    """the compaction's one-workgroup scan gives each of its 256 threads ceil(nb / 256) workgroup counts: nb = 1, 256 (one count per
+    thread) and 257 (two per thread, most threads past the end), the last workgroup holding one point.  Every point is the first of
+    its voxel ("all": every flag set, every workgroup full) or every second one is (points 2k and 2k + 1 share voxel k)."""
+    per = 1 if flags == "all" else 2
+    i = np.arange(n)
+    v = i // per
+    pts = np.stack([v % 64, (v // 64) % 64, v // 4096], -1) + 0.25 * (1 + i % per)[:, None]     # voxel size 1: exact in float
+    ctx = _ctx()
+    out, cnt, first = ctx.down_sampling_voxel(pts, 1.0)
+    o_out, o_cnt, o_first = oracle.down_sampling_voxel(pts, 1.0)
+    np.testing.assert_array_equal(o_first, np.arange(0, n, per))       # (the case is what it says)
+    np.testing.assert_array_equal(first, o_first)
+    np.testing.assert_array_equal(cnt, o_cnt)
+    assert cnt.sum() == n and cnt.max() == min(per, n)
+    np.testing.assert_array_equal(out, o_out)                          # one or two exactly representable points per voxel: no rounding
+    ctx.close()
+
+
 def test_down_sampling_voxel_small_leaf_is_identity(oracle):
     rng = np.random.default_rng(3)
     pts = rng.normal(0, 5, (1000, 3)).astype(np.float32).astype(np.float64)

@@ -345,3 +345,58 @@ def test_sharded_trial_step_is_written_once():
     assert len(re.findall(r"lm\.have_hess\)", text)) == 1 and "lm.have_hess)" in function_body(text, r"^bool needs_hessian_pass\(")
     for head in (r"^int vba_lm_iterate\(", r"^static bool li_imu_rides\(", r"^static int li_ba_device\("):
         assert "needs_hessian_pass(c)" in function_body(text, head), head
+
+
+# ---------------------------------------------------------------- compaction, scan and var_world helpers ("Source layout": vba_common.hpp)
+WG_HELPERS = ("wg_rank", "wg_count", "wg_append", "wg_scan_chunked", "wg_scan_strided", "var_world")
+
+
+def kernel_body(name, kernel):
+    return function_body(read(name), r"^__global__ __launch_bounds__\(\d+\) void %s\(" % kernel)
+
+
+def test_workgroup_helpers_are_written_once_in_vba_common():
+    for fn in WG_HELPERS:
+        head = re.compile(r"^(?:\w+ )*(?:void|int) %s\(" % fn, re.M)
+        assert head.search("__device__ __forceinline__ int %s(bool f" % fn) and not head.search("  const int r = %s(f, wsum, tot);" % fn)
+        assert {f: len(head.findall(read(f))) for f in sources() if head.search(read(f))} == {"vba_common.hpp": 1}, fn
+    assert [f for f in sources() if re.search(r"\bdet_wg_rank\b|\bdet_count\b", read(f))] == []
+    assert "__global__" not in read("vba_common.hpp")
+
+
+def test_count_and_emit_kernels_rank_through_the_helpers():
+    for name, kernel, call in (("vba_kernels_scan.hpp", "k_ds_count", "wg_count("), ("vba_kernels_scan.hpp", "k_ds_emit", "wg_rank("),
+                               ("vba_kernels_kf.hpp", "k_kf_emit", "wg_rank("), ("vba_kernels_init.hpp", "k_initw_count", "wg_count("),
+                               ("vba_kernels_init.hpp", "k_initw_gather", "wg_rank("), ("vba_kernels_map.hpp", "k_fix_heads", "wg_append("),
+                               ("vba_kernels_decode.hpp", "k_scan_decode", "wg_count(")):
+        body = kernel_body(name, kernel)
+        assert "__ballot(" not in body and "__popcll(" not in body and body.count(call) == 1, kernel
+    # the emit kernels return their unflagged threads after the helper's barrier, never before it
+    for name, kernel in (("vba_kernels_scan.hpp", "k_ds_emit"), ("vba_kernels_kf.hpp", "k_kf_emit"), ("vba_kernels_init.hpp", "k_initw_gather")):
+        body = kernel_body(name, kernel)
+        assert "return" not in body[:body.index("wg_rank(")] and "if (!f) return;" in body[body.index("wg_rank("):], kernel
+    # the three list appends of the map: one per kernel, on its own counter
+    text = read("vba_kernels_map.hpp")
+    assert re.findall(r"wg_append\(\w+, wbase, &m\.cnt\[(\w+)\]\)", text) == ["CNT_WL", "CNT_SPLIT", "CNT_FACTORS"]
+    assert len(re.findall(r"\bwg_append\(", "".join(read(f) for f in sources()))) == 4          # (and the definition)
+
+
+def test_one_workgroup_scans_are_wrappers():
+    for name, kernel, call in (("vba_kernels_map.hpp", "k_det_scan", "wg_scan_chunked(a, n, buf, wsum)"),
+                               ("vba_btcgen.hip", "k_bg_scan", "wg_scan_chunked(a, n, buf, wsum)"),
+                               ("vba_kernels_scan.hpp", "k_ds_scan", "wg_scan_strided(nb, blk, blk, part)"),
+                               ("vba_kernels_big.hpp", "k_big_scan", "wg_scan_strided(n, in, out, part)")):
+        body = kernel_body(name, kernel)
+        assert "__shfl_up" not in body and not re.search(r"\bfor\b", body) and body.count(call) == 1, kernel
+        assert re.findall(r"part\[", body) in ([], ["part["]), kernel                        # (its declaration at the most)
+    assert "k_det_scan's algorithm" not in read("vba_btcgen.hip")
+
+
+def test_var_world_is_called_by_both_stagings():
+    for name, kernel in (("vba_kernels_init.hpp", "k_init_blur"), ("vba_kernels_map.hpp", "k_scan_to_soa_pvec_update")):
+        body = kernel_body(name, kernel)
+        assert body.count("var_world(") == 1 and "ph[" not in body and "PR[" not in body and "RV[" not in body, kernel
+    fn = function_body(read("vba_common.hpp"), r"^__device__ __forceinline__ void var_world\(")
+    assert "#pragma clang fp contract(off)" in fn and "ph[3 * r]" in fn
+    # the calcBodyVar half stays a twin (default contraction in k_var_init, contract(off) in k_init_blur): DESIGN.md says so
+    assert "#pragma clang fp contract(off)" in kernel_body("vba_kernels_init.hpp", "k_init_blur")

@@ -14,6 +14,7 @@
 //  - neighbours exact in float (squared L2, x then y then z, ties to the earlier index), radius test d^2 < (float)(r r);
 //  - triangle dedupe: the first in (i, m, n) order wins (atomicMin of the emission index per key), output in emission order.
 #include "vba_btcgen.hpp"
+#include "vba_common.hpp"
 #include "vba_mem.hpp"
 #include "vba_btcgen_fit.hpp"
 
@@ -21,8 +22,7 @@
 
 namespace vba {
 
-hipError_t sort_pairs_u32(void *tmp, size_t &tmp_bytes, const unsigned int *keys_in, unsigned int *keys_out, const int *vals_in, int *vals_out,
-                          size_t n, unsigned int end_bit, hipStream_t stream);
+// (sort_pairs_u32: vba_common.hpp)
 hipError_t sort_pairs_u64(void *tmp, size_t &tmp_bytes, const unsigned long long *keys_in, unsigned long long *keys_out, const int *vals_in,
                           int *vals_out, size_t n, unsigned int end_bit, hipStream_t stream);
 
@@ -44,37 +44,14 @@ __device__ __forceinline__ double bg_dec(unsigned long long u) {
   return __longlong_as_double((long long)b);
 }
 
-// exclusive scan of a[0, n) in place by one workgroup of 1024 (k_det_scan's algorithm); the total goes to *total
+// exclusive scan of a[0, n) in place by one workgroup of 1024 (wg_scan_chunked of vba_common.hpp); the total goes to *total
 __global__ __launch_bounds__(1024) void k_bg_scan(int *a, const int *n_in, int n_max, int *total) {
-  constexpr int K = 8, CH = 1024 * K;
-  __shared__ int buf[CH];
+  __shared__ int buf[WG_SCAN_CHUNK];
   __shared__ int wsum[16];
   int n = n_in ? *n_in : n_max;
   if (n > n_max) n = n_max;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int carry = 0;
-  for (int c0 = 0; c0 < n; c0 += CH) {
-#pragma unroll
-    for (int j = 0; j < K; j++) { const int i = c0 + j * 1024 + tid; buf[j * 1024 + tid] = i < n ? a[i] : 0; }
-    __syncthreads();
-    int v[K], loc = 0;
-#pragma unroll
-    for (int j = 0; j < K; j++) { v[j] = buf[tid * K + j]; loc += v[j]; }
-    int incl = loc;
-    for (int off = 1; off < 64; off <<= 1) { const int u = __shfl_up(incl, off, 64); if (lane >= off) incl += u; }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int run = carry + incl - loc, tot = 0;
-    for (int w = 0; w < 16; w++) { const int c = wsum[w]; run += w < wave ? c : 0; tot += c; }
-#pragma unroll
-    for (int j = 0; j < K; j++) { buf[tid * K + j] = run; run += v[j]; }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < K; j++) { const int i = c0 + j * 1024 + tid; if (i < n) a[i] = buf[j * 1024 + tid]; }
-    carry += tot;
-    __syncthreads();
-  }
-  if (tid == 0) *total = carry;
+  const int tot = wg_scan_chunked(a, n, buf, wsum);
+  if (threadIdx.x == 0) *total = tot;
 }
 
 // ---------------------------------------------------------------- voxel pass (init_voxel_map, BTC.cpp:279-320)

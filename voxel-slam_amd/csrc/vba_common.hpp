@@ -1,5 +1,5 @@
 // Inline host/device helpers that the kernel headers of more than one translation unit use: voxel keys, the plane fit's eigen-solver,
-// the exact cluster transform, the workgroup rank of the stable compactions, the keyframe transform.  Nothing here is a kernel, so
+// the exact cluster transform, the workgroup rank, count, append and scan bodies of the compactions, var_world, the keyframe transform.  Nothing here is a kernel, so
 // including it from several units compiles no kernel twice ("source layout").
 #pragma once
 #include <hip/hip_runtime.h>
@@ -213,9 +213,11 @@ __device__ __forceinline__ double odom_uniform(double x) {
   return __hiloint2double(hi, lo);
 }
 
-// rank of a flagged thread among the flagged threads of its 256-thread workgroup (lane order) and the workgroup's count.  Every
-// thread of the workgroup must call it (it synchronises).
-__device__ __forceinline__ int det_wg_rank(bool f, int *wsum, int &tot) {
+// ---------------------------------------------------------------- workgroup compaction and scan ("Source layout")
+// The LDS arrays are the calling kernel's.  Every thread of the workgroup must call these (they synchronise): a kernel returns its
+// unflagged threads after the call, not before.
+// rank of a flagged thread among the flagged threads of its 256-thread workgroup (lane order) and the workgroup's count
+__device__ __forceinline__ int wg_rank(bool f, int *wsum /*[4]*/, int &tot) {
   const unsigned long long mask = __ballot(f);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) wsum[wave] = __popcll(mask);
@@ -224,6 +226,98 @@ __device__ __forceinline__ int det_wg_rank(bool f, int *wsum, int &tot) {
   tot = 0;
   for (int w = 0; w < 4; w++) { const int c = wsum[w]; before += w < wave ? c : 0; tot += c; }
   return before + __popcll(mask & ((1ull << lane) - 1ull));
+}
+// the count pass of a stable compaction: blk[workgroup] = flagged threads of the workgroup
+__device__ __forceinline__ void wg_count(bool f, int *wsum /*[4]*/, int *blk) {
+  int tot;
+  wg_rank(f, wsum, tot);
+  if (threadIdx.x == 0) blk[blockIdx.x] = tot;
+}
+// Append the flagged threads of a 256-thread workgroup to a list whose length is *counter: the list position of a flagged thread
+// (lane order inside the workgroup; the workgroups in the order their atomics land).  ONE returning atomic per workgroup, none when
+// no thread is flagged.
+__device__ __forceinline__ int wg_append(bool f, int *wbase /*[4]*/, int *counter) {
+  const unsigned long long mask = __ballot(f);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) wbase[wave] = __popcll(mask);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int tot = 0;
+    for (int w = 0; w < 4; w++) { const int c = wbase[w]; wbase[w] = tot; tot += c; }
+    const int base = tot ? atomicAdd(counter, tot) : 0;
+    for (int w = 0; w < 4; w++) wbase[w] += base;
+  }
+  __syncthreads();
+  return wbase[wave] + __popcll(mask & ((1ull << lane) - 1ull));
+}
+// Exclusive scan of a[0 .. n) in place by ONE workgroup of 1024, any n: chunks of 8192 entries go through LDS (coalesced loads and
+// stores; thread t scans entries 8t .. 8t+7 of the chunk, wave shuffles and LDS combine the 1024 runs, a carry links the chunks).
+// Returns the total in every thread.  k_det_scan and k_bg_scan are its wrappers.
+constexpr int WG_SCAN_CHUNK = 1024 * 8;
+__device__ __forceinline__ int wg_scan_chunked(int *a, int n, int *buf /*[WG_SCAN_CHUNK]*/, int *wsum /*[16]*/) {
+  constexpr int K = 8, CH = WG_SCAN_CHUNK;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int carry = 0;
+  for (int c0 = 0; c0 < n; c0 += CH) {
+#pragma unroll
+    for (int j = 0; j < K; j++) { const int i = c0 + j * 1024 + tid; buf[j * 1024 + tid] = i < n ? a[i] : 0; }
+    __syncthreads();
+    int v[K], loc = 0;
+#pragma unroll
+    for (int j = 0; j < K; j++) { v[j] = buf[tid * K + j]; loc += v[j]; }
+    int incl = loc;
+    for (int off = 1; off < 64; off <<= 1) { const int u = __shfl_up(incl, off, 64); if (lane >= off) incl += u; }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int run = carry + incl - loc, tot = 0;
+    for (int w = 0; w < 16; w++) { const int c = wsum[w]; run += w < wave ? c : 0; tot += c; }
+#pragma unroll
+    for (int j = 0; j < K; j++) { buf[tid * K + j] = run; run += v[j]; }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < K; j++) { const int i = c0 + j * 1024 + tid; if (i < n) a[i] = buf[j * 1024 + tid]; }
+    carry += tot;
+    __syncthreads();   // (buf and wsum are rewritten by the next chunk)
+  }
+  return carry;
+}
+// Exclusive scan of in[0 .. n) into out[0 .. n) by ONE workgroup of 256 (n <= a few thousand; out may be in): thread t owns the
+// ceil(n / 256) consecutive entries from t * per, thread 0 scans the 256 partial sums.  Returns the total to THREAD 0 (other threads: 0).
+// k_ds_scan and k_big_scan are its wrappers.
+__device__ __forceinline__ int wg_scan_strided(int n, const int *in, int *out, int *part /*[256]*/) {
+  const int t = threadIdx.x, per = (n + 255) / 256;
+  int s = 0, tot = 0;
+  for (int k = 0; k < per; k++) { const int i = t * per + k; if (i < n) s += in[i]; }
+  part[t] = s;
+  __syncthreads();
+  if (t == 0) { for (int k = 0; k < 256; k++) { const int v = part[k]; part[k] = tot; tot += v; } }
+  __syncthreads();
+  int acc = part[t];
+  for (int k = 0; k < per; k++) { const int i = t * per + k; if (i < n) { const int v = in[i]; out[i] = acc; acc += v; } }
+  return tot;
+}
+
+// pvec_update (voxelslam.hpp:242-265): var_world = R var R^T + phat rot_var phat^T + tsl_var for the body point (bx, by, bz), in the
+// reference's operation order, every operation rounded separately.  R row-major (9), cov6 = [rot_var(9) | tsl_var(9)]; out may not
+// alias var.
+__device__ __forceinline__ void var_world(const double *R, const double *cov6, double bx, double by, double bz, const double *var /*9*/, double *out /*9*/) {
+#pragma clang fp contract(off)
+  double RV[9], PR[9];
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int c = 0; c < 3; c++) RV[3 * r + c] = (R[3 * r] * var[c] + R[3 * r + 1] * var[3 + c]) + R[3 * r + 2] * var[6 + c];
+  const double ph[9] = {0, -bz, by, bz, 0, -bx, -by, bx, 0};
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int c = 0; c < 3; c++) PR[3 * r + c] = (ph[3 * r] * cov6[c] + ph[3 * r + 1] * cov6[3 + c]) + ph[3 * r + 2] * cov6[6 + c];
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+      out[3 * r + c] = (((RV[3 * r] * R[3 * c] + RV[3 * r + 1] * R[3 * c + 1]) + RV[3 * r + 2] * R[3 * c + 2]) +
+                        ((PR[3 * r] * ph[3 * c] + PR[3 * r + 1] * ph[3 * c + 1]) + PR[3 * r + 2] * ph[3 * c + 2])) + cov6[9 + 3 * r + c];
 }
 
 // q = ((T[0] x + T[1] y) + T[2] z) + T[9], ... with T = [dR row-major (9), dp (3)]

@@ -368,15 +368,8 @@ __global__ void k_gbab_vcount(GbaBigView g, int *vcnt) {
 }
 __global__ __launch_bounds__(256) void k_big_scan(int n, const int *__restrict__ in, int *__restrict__ out /*[n+1]*/) {   // one workgroup, exclusive
   __shared__ int part[256];
-  const int t = threadIdx.x, per = (n + 255) / 256;
-  int s = 0;
-  for (int k = 0; k < per; k++) { const int i = t * per + k; if (i < n) s += in[i]; }
-  part[t] = s;
-  __syncthreads();
-  if (t == 0) { int acc = 0; for (int k = 0; k < 256; k++) { const int v = part[k]; part[k] = acc; acc += v; } out[n] = acc; }
-  __syncthreads();
-  int acc = part[t];
-  for (int k = 0; k < per; k++) { const int i = t * per + k; if (i < n) { out[i] = acc; acc += in[i]; } }
+  const int tot = wg_scan_strided(n, in, out, part);
+  if (threadIdx.x == 0) out[n] = tot;
 }
 __global__ void k_gbab_fill(GbaBigView g, BigView b, int *fill) {
   const unsigned int s = blockIdx.x * blockDim.x + threadIdx.x;

@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256) void k_btc_verify(BtcStds q, BtcStds d, BtcCfg
     const int k = b + tid;
     const bool f = k < total && mf[k] == frame;
     int tot;
-    const int rk = det_wg_rank(f, wsum, tot);
+    const int rk = wg_rank(f, wsum, tot);
     if (f) { pq[off + run + rk] = mq[k]; pd[off + run + rk] = md[k]; }
     run += tot;
     __syncthreads();

@@ -68,10 +68,7 @@ __global__ __launch_bounds__(256) void k_scan_decode(const unsigned char *__rest
     rec[5 * j] = x; rec[5 * j + 1] = y; rec[5 * j + 2] = z; rec[5 * j + 3] = in; rec[5 * j + 4] = cv;
     key[j] = keep ? scan_time_key(cv) : SCAN_KEY_EMPTY;
   }
-  const unsigned long long m = __ballot(keep);
-  if ((t & 63) == 0) wsum[t >> 6] = __popcll(m);
-  __syncthreads();
-  if (t == 0) blk[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  wg_count(keep, wsum, blk);
 }
 
 // Same grid as k_scan_decode, after k_ds_scan: blk holds the exclusive scan of the workgroup counts, *total the kept points.  The kept
@@ -85,7 +82,7 @@ __global__ __launch_bounds__(256) void k_scan_pairs(int n_raw, int filter, int p
   const unsigned int k = cand ? key[j] : SCAN_KEY_EMPTY;
   const bool f = k != SCAN_KEY_EMPTY;
   int tot;
-  const int rank = det_wg_rank(f, wsum, tot);
+  const int rank = wg_rank(f, wsum, tot);
   if (f) { const int pos = blk[blockIdx.x] + rank; kin[pos] = k; vin[pos] = j; }
   if (i < n_sort && i >= *total) { kin[i] = SCAN_KEY_EMPTY; vin[i] = 0; }
 }

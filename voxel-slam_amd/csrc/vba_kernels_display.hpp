@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void k_disp_nodes(MapView m, int nn, int *__re
   const int id = blockIdx.x * 256 + threadIdx.x;
   const bool f = disp_planar(m, id, nn);
   int tot;
-  const int r = det_wg_rank(f, wsum, tot);
+  const int r = wg_rank(f, wsum, tot);
   if (PASS == 0) { if (threadIdx.x == 0) blk[blockIdx.x] = tot; return; }
   if (id < nn) nidx[id] = f ? blk[blockIdx.x] + r : -1;
 }
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void k_disp_points(MapView m, DispFrames F, in
     if (leaf >= 0) { pi = leaf < nn ? nidx[leaf] : -1; f = all || pi >= 0; }
   }
   int tot;
-  const int r = det_wg_rank(f, wsum, tot);
+  const int r = wg_rank(f, wsum, tot);
   if (PASS == 0) { if (threadIdx.x == 0) blk[b] = tot; return; }
   if (!f) return;
   const size_t j = (size_t)blk[b] + (size_t)r;

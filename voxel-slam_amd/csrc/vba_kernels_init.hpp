@@ -175,19 +175,10 @@ __global__ __launch_bounds__(256) void k_init_blur(int W, int n_out, const InitS
     const double a1[3] = {r * (d1 * b1z - d2 * b1y), r * (d2 * b1x - d0 * b1z), r * (d0 * b1y - d1 * b1x)};
     const double a2[3] = {r * (d1 * b2z - d2 * b2y), r * (d2 * b2x - d0 * b2z), r * (d0 * b2y - d1 * b2x)};
     const double rv = (double)range_var, d[3] = {d0, d1, d2};
-    double vb[9], RV[9], PR[9];
+    double vb[9];
     for (int ii = 0; ii < 3; ii++)
       for (int jj = 0; jj < 3; jj++) vb[3 * ii + jj] = d[ii] * rv * d[jj] + (a1[ii] * dv * a1[jj] + a2[ii] * dv * a2[jj]);
-    const double *R = S.R, *cv6 = S.cov6;
-    for (int rr = 0; rr < 3; rr++)
-      for (int cc = 0; cc < 3; cc++) RV[3 * rr + cc] = (R[3 * rr] * vb[cc] + R[3 * rr + 1] * vb[3 + cc]) + R[3 * rr + 2] * vb[6 + cc];
-    const double ph[9] = {0, -z, y, z, 0, -x, -y, x, 0};
-    for (int rr = 0; rr < 3; rr++)
-      for (int cc = 0; cc < 3; cc++) PR[3 * rr + cc] = (ph[3 * rr] * cv6[cc] + ph[3 * rr + 1] * cv6[3 + cc]) + ph[3 * rr + 2] * cv6[6 + cc];
-    for (int rr = 0; rr < 3; rr++)
-      for (int cc = 0; cc < 3; cc++)
-        vo[3 * rr + cc] = (((RV[3 * rr] * R[3 * cc] + RV[3 * rr + 1] * R[3 * cc + 1]) + RV[3 * rr + 2] * R[3 * cc + 2]) +
-                           ((PR[3 * rr] * ph[3 * cc] + PR[3 * rr + 1] * ph[3 * cc + 1]) + PR[3 * rr + 2] * ph[3 * cc + 2])) + cv6[9 + 3 * rr + cc];
+    var_world(S.R, S.cov6, x, y, z, vb, vo);
   }
   pb[3 * (size_t)o] = x; pb[3 * (size_t)o + 1] = y; pb[3 * (size_t)o + 2] = z;
 }
@@ -205,11 +196,7 @@ __device__ __forceinline__ int initw_kept(const DsSlot *__restrict__ tab, const 
 __global__ __launch_bounds__(256) void k_initw_count(int n, const DsSlot *__restrict__ tab, const int *__restrict__ slot_of, int *__restrict__ blk) {
   __shared__ int wsum[4];
   const int i = blockIdx.x * 256 + threadIdx.x;
-  const int f = (i < n) ? initw_kept(tab, slot_of, i) : 0;
-  const unsigned long long m = __ballot(f);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) blk[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  wg_count(i < n && initw_kept(tab, slot_of, i), wsum, blk);
 }
 // Kept point i goes to row row0 + (kept points below i): ascending stage-0 index, i.e. ascending curvature with ties in message
 // order.  The row is copied as it is (xyz and curvature, bit for bit).  No atomics.
@@ -217,14 +204,11 @@ __global__ __launch_bounds__(256) void k_initw_gather(int n, const DsSlot *__res
                                                       const double *__restrict__ pnt, const double *__restrict__ curv, double *__restrict__ wpnt,
                                                       double *__restrict__ wcurv, long long row0) {
   __shared__ int wsum[4];
-  const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int f = (i < n) ? initw_kept(tab, slot_of, i) : 0;
-  const unsigned long long m = __ballot(f);
-  if (lane == 0) wsum[w] = __popcll(m);
-  __syncthreads();
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const bool f = i < n && initw_kept(tab, slot_of, i);
+  int tot;
+  const int pos = blk[blockIdx.x] + wg_rank(f, wsum, tot);
   if (!f) return;
-  int pos = blk[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int k = 0; k < w; k++) pos += wsum[k];
   const long long r = row0 + (long long)pos;
   wpnt[3 * r] = pnt[3 * (size_t)i]; wpnt[3 * r + 1] = pnt[3 * (size_t)i + 1]; wpnt[3 * r + 2] = pnt[3 * (size_t)i + 2];
   wcurv[r] = curv[i];

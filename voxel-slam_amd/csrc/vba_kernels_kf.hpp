@@ -70,16 +70,13 @@ __global__ __launch_bounds__(256) void k_kf_world(int n, const double *__restric
 __global__ __launch_bounds__(256) void k_kf_emit(int n, const DsSlot *__restrict__ tab, const int *__restrict__ slot_of, const int *__restrict__ blk,
                                                  double *__restrict__ out, float *__restrict__ vout, int *__restrict__ count, int have_var) {
   __shared__ int wsum[4];
-  const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = blockIdx.x * 256 + threadIdx.x;
   DsSlot s;
-  int f = 0;
-  if (i < n) { s = tab[slot_of[i]]; f = (s.first == i) ? 1 : 0; }
-  const unsigned long long m = __ballot(f);
-  if (lane == 0) wsum[w] = __popcll(m);
-  __syncthreads();
+  bool f = false;
+  if (i < n) { s = tab[slot_of[i]]; f = s.first == i; }
+  int tot;
+  const int pos = blk[blockIdx.x] + wg_rank(f, wsum, tot);
   if (!f) return;
-  int pos = blk[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int k = 0; k < w; k++) pos += wsum[k];
   const double inv = 1.0 / (double)s.cnt;
   const size_t b = 3 * (size_t)pos;
   out[b] = (double)(float)(s.sx * inv); out[b + 1] = (double)(float)(s.sy * inv); out[b + 2] = (double)(float)(s.sz * inv);
@@ -256,7 +253,7 @@ __global__ __launch_bounds__(256) void k_vx_emit(long long n, long long per, con
     bool f = false;
     if (i < e) { h = slot_of[i]; s = tab[h]; f = s.first == (int)i && s.cnt >= min_count; }
     int tot;
-    const int r = det_wg_rank(f, wsum, tot);
+    const int r = wg_rank(f, wsum, tot);
     if (f) {
       const size_t pos = (size_t)(pos0 + r);
       const double inv = 1.0 / (double)s.cnt;

@@ -129,46 +129,16 @@ __device__ __forceinline__ int alloc_nodes(const MapView &m, int which_cnt, cons
 // popcount in lane order, wave totals in LDS).  Owners are ranked by the index they are launched over (point index, node id).
 constexpr unsigned int DET_NONE = 0x7F7F7F7Fu;   // hfirst of a slot that no insert is creating a root in (a byte fill)
 
-__device__ __forceinline__ void det_count(bool f, int *wsum, int *blk) {
-  int tot;
-  det_wg_rank(f, wsum, tot);
-  if (threadIdx.x == 0) blk[blockIdx.x] = tot;
-}
-
-// Exclusive scan of a[0 .. n) in place by one workgroup of 1024: chunks of 8192 entries go through LDS (coalesced loads and stores;
-// thread t scans entries 8t .. 8t+7 of the chunk, wave shuffles and LDS combine the 1024 runs, a carry links the chunks); the total
-// goes to cnt[which_out] (which_out < 0: nowhere).  n = n_max, or (which_n >= 0) the number of 256-thread workgroups that covered
-// min(cnt[which_n], cap_n) items — workgroups beyond the live count return before they write their count.
+// Exclusive scan of a[0 .. n) in place by one workgroup of 1024 (wg_scan_chunked); the total goes to cnt[which_out] (which_out < 0:
+// nowhere).  n = n_max, or (which_n >= 0) the number of 256-thread workgroups that covered min(cnt[which_n], cap_n) items —
+// workgroups beyond the live count return before they write their count.
 __global__ __launch_bounds__(1024) void k_det_scan(int *a, int n_max, int *cnt, int which_n, int cap_n, int which_out) {
-  constexpr int K = 8, CH = 1024 * K;
-  __shared__ int buf[CH];
+  __shared__ int buf[WG_SCAN_CHUNK];
   __shared__ int wsum[16];
   int n = n_max;
   if (which_n >= 0) { const int c = cnt[which_n] < cap_n ? cnt[which_n] : cap_n; const int nb = (c + 255) / 256; n = nb < n_max ? nb : n_max; }
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int carry = 0;
-  for (int c0 = 0; c0 < n; c0 += CH) {
-#pragma unroll
-    for (int j = 0; j < K; j++) { const int i = c0 + j * 1024 + tid; buf[j * 1024 + tid] = i < n ? a[i] : 0; }
-    __syncthreads();
-    int v[K], loc = 0;
-#pragma unroll
-    for (int j = 0; j < K; j++) { v[j] = buf[tid * K + j]; loc += v[j]; }
-    int incl = loc;
-    for (int off = 1; off < 64; off <<= 1) { const int u = __shfl_up(incl, off, 64); if (lane >= off) incl += u; }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int run = carry + incl - loc, tot = 0;
-    for (int w = 0; w < 16; w++) { const int c = wsum[w]; run += w < wave ? c : 0; tot += c; }
-#pragma unroll
-    for (int j = 0; j < K; j++) { buf[tid * K + j] = run; run += v[j]; }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < K; j++) { const int i = c0 + j * 1024 + tid; if (i < n) a[i] = buf[j * 1024 + tid]; }
-    carry += tot;
-    __syncthreads();   // (buf and wsum are rewritten by the next chunk)
-  }
-  if (tid == 0 && which_out >= 0) cnt[which_out] = carry;
+  const int tot = wg_scan_chunked(a, n, buf, wsum);
+  if (threadIdx.x == 0 && which_out >= 0) cnt[which_out] = tot;
 }
 
 // After a ranked allocation of cnt[which_n] owners (r-th owner: the r-th entry from the top of the free stack, then fresh storage
@@ -337,9 +307,9 @@ __global__ __launch_bounds__(256) void k_ins_newroots_det(MapView m, MapParams P
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   const int h = p < n ? m.phash[p] : -1;
   const bool first = h >= 0 && m.hfirst[h] == (unsigned int)p;
-  if (PH == 0) { det_count(first, wsum, m.dblk); return; }
+  if (PH == 0) { wg_count(first, wsum, m.dblk); return; }
   int tot;
-  const int r = m.dblk[blockIdx.x] + det_wg_rank(first, wsum, tot);
+  const int r = m.dblk[blockIdx.x] + wg_rank(first, wsum, tot);
   if (!first) return;
   m.hfirst[h] = DET_NONE;
   const int F = m.cnt[CNT_FREE_ROOTS];
@@ -639,18 +609,8 @@ __global__ __launch_bounds__(256) void k_fix_heads(MapView m, int n) {       // 
     const unsigned int key = m.skey_b[i];
     head = key != 0xFFFFFFFFu && ((i == 0) || m.skey_b[i - 1] != key);
   }
-  const unsigned long long mask = __ballot(head);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) wbase[wave] = __popcll(mask);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int tot = 0;
-    for (int w = 0; w < 4; w++) { const int c = wbase[w]; wbase[w] = tot; tot += c; }
-    const int b0 = tot ? atomicAdd(&m.cnt[CNT_WL], tot) : 0;
-    for (int w = 0; w < 4; w++) wbase[w] += b0;
-  }
-  __syncthreads();
-  if (head) m.wl[wbase[wave] + __popcll(mask & ((1ull << lane) - 1ull))] = i;
+  const int r = wg_append(head, wbase, &m.cnt[CNT_WL]);
+  if (head) m.wl[r] = i;
 }
 // link block [qb, qb + len) to the end of leaf's chain (one lane; a leaf is served by one wave per call)
 __device__ __forceinline__ void fix_chain_append(const MapView &m, int leaf, int qb, int len) {
@@ -800,20 +760,10 @@ __global__ __launch_bounds__(256) void k_recut_leaf(MapView m, MapParams P, int 
     subdivide_leaf(m, P, L, epoch, id, base);
     split = true;
   } while (false);
-  if (DET) { det_count(split, wbase, m.dblk); return; }
+  if (DET) { wg_count(split, wbase, m.dblk); return; }
   // the leaves this level split form the work list of k_recut_push (one returning atomic per workgroup; the order carries no meaning)
-  const unsigned long long mask = __ballot(split);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) wbase[wave] = __popcll(mask);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int tot = 0;
-    for (int w = 0; w < 4; w++) { const int c = wbase[w]; wbase[w] = tot; tot += c; }
-    const int base = tot ? atomicAdd(&m.cnt[CNT_SPLIT], tot) : 0;
-    for (int w = 0; w < 4; w++) wbase[w] += base;
-  }
-  __syncthreads();
-  if (split) m.nsl[wbase[wave] + __popcll(mask & ((1ull << lane) - 1ull))] = id;
+  const int r = wg_append(split, wbase, &m.cnt[CNT_SPLIT]);
+  if (split) m.nsl[r] = id;
 }
 
 // Deterministic mode: the leaves this level splits, in ascending id; the r-th takes the r-th block of the fixed sequence (the free-block
@@ -826,7 +776,7 @@ __global__ __launch_bounds__(256) void k_recut_split_det(MapView m, MapParams P,
   if ((int)(blockIdx.x * blockDim.x) >= nn) return;
   const bool f = id < nn && m.ndet[id] != 0;
   int tot;
-  const int r = m.dblk[blockIdx.x] + det_wg_rank(f, wsum, tot);
+  const int r = m.dblk[blockIdx.x] + wg_rank(f, wsum, tot);
   if (!f) return;
   m.ndet[id] = 0;
   const int FB = m.cnt[CNT_FREE_BLOCKS];
@@ -1067,26 +1017,15 @@ __global__ __launch_bounds__(256) void k_extract_count(MapView m, MapParams P, i
   if (take && !(m.f_exist[id] && m.f_plane[id] && m.f_sw[id])) take = false;
   const size_t cp = (size_t)m.cap;
   if (take && neval_at(m, 0, id) / neval_at(m, 1, id) > 0.12) take = false;   // VM:1615
-  if (DET == 1) { det_count(take, wbase, m.dblk); return; }
+  if (DET == 1) { wg_count(take, wbase, m.dblk); return; }
   if (DET == 2) {
     int tot;
-    const int a = m.dblk[blockIdx.x] + det_wg_rank(take, wbase, tot);
+    const int a = m.dblk[blockIdx.x] + wg_rank(take, wbase, tot);
     if (take) { m.nopt[id] = a; m.nflist[a] = id; }
     return;
   }
-  const unsigned long long mask = __ballot(take);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) wbase[wave] = __popcll(mask);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int tot = 0;
-    for (int w = 0; w < 4; w++) { const int c = wbase[w]; wbase[w] = tot; tot += c; }
-    const int base = tot ? atomicAdd(&m.cnt[CNT_FACTORS], tot) : 0;
-    for (int w = 0; w < 4; w++) wbase[w] += base;
-  }
-  __syncthreads();
+  const int a = wg_append(take, wbase, &m.cnt[CNT_FACTORS]);
   if (take) {
-    const int a = wbase[wave] + __popcll(mask & ((1ull << lane) - 1ull));
     m.nopt[id] = a;                                          // opt_state  VM:1626
     m.nflist[a] = id;                                        // (a < number of nodes <= cap)
   }
@@ -1579,9 +1518,9 @@ __global__ __launch_bounds__(256) void k_prune_free_det(MapView m) {
   if ((int)(blockIdx.x * blockDim.x) >= nn) return;
   bool f = id < nn && m.nlayer[id] < 0;
   if (f) f = KIND == 0 ? m.nroot[id] == id : (m.nroot[id] != id && (m.npath[id] & 7) == 0);
-  if (PH == 0) { det_count(f, wsum, m.dblk); return; }
+  if (PH == 0) { wg_count(f, wsum, m.dblk); return; }
   int tot;
-  const int r = m.dblk[blockIdx.x] + det_wg_rank(f, wsum, tot);
+  const int r = m.dblk[blockIdx.x] + wg_rank(f, wsum, tot);
   if (!f) return;
   const int F = m.cnt[KIND == 0 ? CNT_FREE_ROOTS : CNT_FREE_BLOCKS];
   (KIND == 0 ? m.nfree_root : m.nfree_blk)[F - 1 - r] = id;
@@ -1742,9 +1681,9 @@ template <int DET>
 __device__ __forceinline__ int dump_slot(const MapView &m, int id, int nn, int *wsum) {
   const bool f = dump_row(m, id, nn);
   if (DET == 0) return f ? atomicAdd(&m.cnt[CNT_LEAVES], 1) : -1;
-  if (DET == 1) { det_count(f, wsum, m.dblk); return -1; }
+  if (DET == 1) { wg_count(f, wsum, m.dblk); return -1; }
   int tot;
-  const int r = m.dblk[blockIdx.x] + det_wg_rank(f, wsum, tot);
+  const int r = m.dblk[blockIdx.x] + wg_rank(f, wsum, tot);
   return f ? r : -1;
 }
 template <int DET>
@@ -1816,25 +1755,10 @@ __global__ __launch_bounds__(256) void k_scan_to_soa_pvec_update(MapView m, int 
   const size_t mpz = (size_t)m.max_pts;
   if (tid < cnt) {
     const double bx = sp[tid * 3], by = sp[tid * 3 + 1], bz = sp[tid * 3 + 2];
-    const double *R = pose;
-    double v[9], RV[9], PR[9];
+    double v[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) v[k] = sv[tid * 9 + k];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-      for (int c = 0; c < 3; c++) RV[3 * r + c] = (R[3 * r] * v[c] + R[3 * r + 1] * v[3 + c]) + R[3 * r + 2] * v[6 + c];
-    const double ph[9] = {0, -bz, by, bz, 0, -bx, -by, bx, 0};
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-      for (int c = 0; c < 3; c++) PR[3 * r + c] = (ph[3 * r] * cov6[c] + ph[3 * r + 1] * cov6[3 + c]) + ph[3 * r + 2] * cov6[6 + c];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-      for (int c = 0; c < 3; c++)
-        sv[tid * 9 + 3 * r + c] = (((RV[3 * r] * R[3 * c] + RV[3 * r + 1] * R[3 * c + 1]) + RV[3 * r + 2] * R[3 * c + 2]) +
-                                   ((PR[3 * r] * ph[3 * c] + PR[3 * r + 1] * ph[3 * c + 1]) + PR[3 * r + 2] * ph[3 * c + 2])) + cov6[9 + 3 * r + c];
+    var_world(pose, cov6, bx, by, bz, v, sv + tid * 9);
   }
   __syncthreads();
   double *ov = m.pvar + ((size_t)slot * mpz + base) * 9, *op = m.px + ((size_t)slot * mpz + base) * 3;

@@ -95,25 +95,14 @@ __global__ void k_ds_sum_det(int n, const double *__restrict__ pnt, const double
 __global__ __launch_bounds__(256) void k_ds_count(int n, const DsSlot *__restrict__ tab, const int *__restrict__ slot_of, int *__restrict__ blk) {
   __shared__ int wsum[4];
   const int i = blockIdx.x * 256 + threadIdx.x;
-  const int f = (i < n && tab[slot_of[i]].first == i) ? 1 : 0;
-  const unsigned long long m = __ballot(f);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) blk[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  wg_count(i < n && tab[slot_of[i]].first == i, wsum, blk);
 }
 
-// exclusive scan of the block counts by one workgroup (nb <= a few thousand); total -> *n_out
-__global__ __launch_bounds__(256) void k_ds_scan(int nb, int *__restrict__ blk, int *__restrict__ n_out) {
+// exclusive scan of the block counts by one workgroup (nb <= a few thousand), in place; total -> *n_out
+__global__ __launch_bounds__(256) void k_ds_scan(int nb, int *blk, int *__restrict__ n_out) {
   __shared__ int part[256];
-  const int t = threadIdx.x, per = (nb + 255) / 256;
-  int s = 0;
-  for (int k = 0; k < per; k++) { const int b = t * per + k; if (b < nb) s += blk[b]; }
-  part[t] = s;
-  __syncthreads();
-  if (t == 0) { int acc = 0; for (int k = 0; k < 256; k++) { const int v = part[k]; part[k] = acc; acc += v; } *n_out = acc; }
-  __syncthreads();
-  int acc = part[t];
-  for (int k = 0; k < per; k++) { const int b = t * per + k; if (b < nb) { const int v = blk[b]; blk[b] = acc; acc += v; } }
+  const int tot = wg_scan_strided(nb, blk, blk, part);
+  if (threadIdx.x == 0) *n_out = tot;
 }
 
 // stable compaction in first-occurrence order; centroid rounded to float like the PCL cloud it replaces
@@ -122,16 +111,13 @@ __global__ __launch_bounds__(256) void k_ds_scan(int nb, int *__restrict__ blk, 
 __global__ __launch_bounds__(256) void k_ds_emit(int n, const DsSlot *__restrict__ tab, const int *__restrict__ slot_of, const int *__restrict__ blk,
                                                  double *__restrict__ out, int *__restrict__ count, int *__restrict__ first, double *__restrict__ vout, int mode) {
   __shared__ int wsum[4];
-  const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = blockIdx.x * 256 + threadIdx.x;
   DsSlot s;
-  int f = 0;
-  if (i < n) { s = tab[slot_of[i]]; f = (s.first == i) ? 1 : 0; }
-  const unsigned long long m = __ballot(f);
-  if (lane == 0) wsum[w] = __popcll(m);
-  __syncthreads();
+  bool f = false;
+  if (i < n) { s = tab[slot_of[i]]; f = s.first == i; }
+  int tot;
+  const int pos = blk[blockIdx.x] + wg_rank(f, wsum, tot);
   if (!f) return;
-  int pos = blk[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int k = 0; k < w; k++) pos += wsum[k];
   const double inv = 1.0 / (double)s.cnt;
   out[3 * (size_t)pos] = (double)(float)(s.sx * inv);
   out[3 * (size_t)pos + 1] = (double)(float)(s.sy * inv);
