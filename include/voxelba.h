@@ -997,6 +997,52 @@ int vba_kf_voxel_export(vba_ctx *ctx, int n_stores, vba_kf_store *const *stores,
                         double voxel_size, int min_count, int64_t cap, float *xyzi /* [cap][4], HOST or DEVICE */,
                         int *counts /* [cap], same side as xyzi, may be NULL */, int64_t *n_out);
 
+/* ---- The global map as surfels / NDT cells: per voxel of the map above a mean, a covariance and a normal that
+ * points to the sensor, fitted on the device.  What a mesher, a surfel renderer, an NDT registration against a prior map reads.
+ *
+ * Sequence, voxels, order, filter: exactly vba_kf_voxel_export's.  The same sequence S of float records, the same voxel key with
+ * both inherited quirks, one output per voxel in ascending index of the voxel's first record in S, voxels with cnt < min_count left
+ * out, counts[i] = cnt.  For the same arguments *n_out, counts and the order are identical to vba_kf_voxel_export.
+ * Mean: c = s * (1.0 / (double)cnt), s the f64 sum of the voxel's float coordinates; c stays a double.
+ * Covariance, two passes, centred on c: for every member a of the voxel d = (double)a - c; the six products d_i d_j (i <= j, order
+ * xx xy xz yy yz zz) are each rounded on their own, nothing contracted, and summed into M; C = M * (1.0 / (double)cnt);
+ * cov[i] = C as doubles (cov may be NULL).  No raw moment sum(a a^T) / cnt - c c^T is formed anywhere: at the coordinates a long
+ * session reaches it cancels.
+ * Fit: the ascending eigenvalues l0 <= l1 <= l2 of C and the eigenvector of l0, by the library's symmetric 3x3 solver built from
+ * correctly rounded operations only (csrc/vba_eig3.hpp in its IEEE form with cyclic Jacobi sweeps as the fallback, the plane fit of
+ * vba_btc_generate_stds); negative rounding residue in an eigenvalue is clamped to 0.  A host build of csrc/vba_surfel_fit.hpp
+ * without contraction gives the same bits from the same C.
+ * Record, 12 floats (48 bytes), each double narrowed to float once:
+ *   [0..2]  c: the x y z of vba_kf_voxel_export            [3]     intensity of the voxel's first record
+ *   [4..6]  unit eigenvector of l0, the normal             [7..9]  sqrt l0, sqrt l1, sqrt l2
+ *   [10]    l0 / (l0 + l1 + l2), 0 when the trace is 0     [11]    (float)cnt
+ * Orientation: the normal n points toward the sensor, that is toward x0.p of the keyframe of the voxel's FIRST record: when
+ * (n_x (p_x - c_x) + n_y (p_y - c_y)) + n_z (p_z - c_z) < 0, in double and uncontracted, n is negated.  An exactly zero dot product
+ * leaves the sign unspecified.  For cnt < 3 the normal is (0, 0, 0); the other fields are as defined.
+ * Sum order.  vba_options::deterministic = 1: s and M are the chains ((0 + t_0) + t_1) + ... in the order of S, no f64 atomic is on
+ * the path, and the result of a call is a function of its inputs bit for bit.  Default: f64 atomics form s and M, and two calls may
+ * differ in the last bits of c and C and in what the fit makes of those.
+ * Capacity, size query, limits, waits, locking: as vba_kf_voxel_export.  More kept voxels than `cap` is VBA_ERR_CAPACITY with
+ * *n_out = the number needed and every output untouched; cap == 0 with surfels == NULL is the size query; an S of 2^31 records or
+ * more is VBA_ERR_CAPACITY before any device work.  surfels [cap][12], cov [cap][6] and counts [cap] are all HOST or all DEVICE
+ * memory; a device surfels is 16-byte aligned, a device cov 8-byte aligned.  Every call waits for the stream once, for the count; a
+ * device result is then written stream-ordered without a second wait, a host result passes through the context's staging (whole)
+ * and the call returns when it has arrived.
+ * Work memory: the work arrays of vba_kf_voxel_export, shared with it (the two calls may alternate on one context: each call clears
+ * and refills them), and beyond them 52 bytes per KEPT voxel: a row of six f64 moment sums, which become the covariance in place,
+ * and the slot of every output row; nothing of this feature's own is proportional to the table's slots.  A host result adds 52
+ * bytes of staging per kept voxel.  _reserve(max_points, max_voxels) sizes all of it for an S of max_points records and a result of
+ * max_voxels voxels; a call that needs more doubles what is short after a synchronise, and nothing is allocated per call.
+ * _allocations: allocations made and bytes requested so far for the shared work arrays and this feature's own together, cumulative.
+ * VBA_ERR_BAD_ARG before any device work, outputs untouched: the refusals of vba_kf_voxel_export (with surfels in the place of
+ * xyzi), a misaligned device cov, cov on the other side. */
+int vba_kf_surfel_export_reserve(vba_ctx *ctx, int64_t max_points, int64_t max_voxels);
+int vba_kf_surfel_export_allocations(vba_ctx *ctx, int *n_allocs, int64_t *bytes);
+int vba_kf_surfel_export(vba_ctx *ctx, int n_stores, vba_kf_store *const *stores, const float *intensity /* [n_stores] */, int jump,
+                         double voxel_size, int min_count, int64_t cap, float *surfels /* [cap][12], HOST or DEVICE */,
+                         double *cov /* [cap][6], same side as surfels, may be NULL */,
+                         int *counts /* [cap], same side as surfels, may be NULL */, int64_t *n_out);
+
 /* ------------------------------------------------------------------------------------------------
  * Loop-closure map: the counterpart of `map_loop` (VS:2601-2625) and loop_update() (VS:1255-1373), the step that
  * carries a loop closure back into local mapping.  A vba_loop_map owns one second voxel map, created from its context's options

@@ -1109,6 +1109,40 @@ inline int64_t pub_globalmap_voxel(Context &ctx, const std::vector<KeyframeStore
   return n;
 }
 
+// The global map as surfels (vba_kf_surfel_export): one record of 12 floats per voxel of pub_globalmap_voxel (mean,
+// intensity = the id of the voxel's first record, normal toward the sensor, sqrt of the eigenvalues, l0 / trace, count) and its
+// covariance of 6 doubles, voxels of fewer than min_count records left out, cut into messages as pub_globalmap_voxel cuts them.
+// publish(const float *records, const double *cov, int64_t n) receives one message; the caller holds mtx_keyframe.  Two device
+// passes: the size query, then the result.  Returns the number of records.
+template <class Publish>
+inline int64_t pub_globalmap_surfel(Context &ctx, const std::vector<KeyframeStore *> &relc_submaps, const std::vector<int> &ids, double voxel_size,
+                                    Publish &&publish, int min_count = 3, int64_t interval_size = 5000000, int jump = 1) {
+  std::vector<vba_kf_store *> stores;
+  std::vector<float> intensity;
+  for (int id : ids) {
+    stores.push_back(relc_submaps.at((size_t)id)->get());
+    intensity.push_back((float)id);                                             // pp.intensity = id, VS:128
+  }
+  int64_t n = 0;
+  std::vector<float> pl;
+  std::vector<double> cov;
+  if (!stores.empty()) {
+    check(ctx.get(), vba_kf_surfel_export(ctx.get(), (int)stores.size(), stores.data(), intensity.data(), jump, voxel_size, min_count, 0, nullptr, nullptr,
+                                          nullptr, &n));
+    pl.resize((size_t)n * 12);
+    cov.resize((size_t)n * 6);
+    if (n > 0)
+      check(ctx.get(), vba_kf_surfel_export(ctx.get(), (int)stores.size(), stores.data(), intensity.data(), jump, voxel_size, min_count, n, pl.data(),
+                                            cov.data(), nullptr, &n));
+  }
+  int64_t b = 0;
+  for (int64_t e : voxel_message_ends(n, interval_size)) {
+    publish((const float *)pl.data() + 12 * b, (const double *)cov.data() + 6 * b, e - b);
+    b = e;
+  }
+  return n;
+}
+
 // ---- loop closure -> local mapping (voxelba.h "Loop-closure map").  The pose algebra runs here, on the host, one
 // separately rounded product and sum after the other in the order  s = a0*b0; s += a1*b1; s += a2*b2  (compile without contraction
 // to keep it so); the device sees poses that are already moved.

@@ -1202,6 +1202,53 @@ class Context:
         self._chk(self.lib.vba_kf_voxel_export_allocations(self.h, C.byref(n), C.byref(b)))
         return n.value, b.value
 
+    def kf_export_surfel(self, stores, intensity, jump, voxel_size, min_count=3, cap=None, out=None, want_cov=True, want_counts=True):
+        """vba_kf_surfel_export on this context's stream: one surfel per voxel of kf_export_voxel(stores, intensity, jump, voxel_size,
+        min_count), in its order.  Returns (surfels float32 [n][12], cov float64 [n][6] or None, counts int32 [n] or None): the
+        mean, the intensity, the normal toward the sensor, sqrt of the three eigenvalues, l0 / trace and the count; the covariance
+        xx xy xz yy yz zz.  ``cap`` None = room for every record.  With ``out`` = (surfels address, cov address or None, counts
+        address or None) of DEVICE buffers of ``cap`` entries (surfels 16-byte, cov 8-byte aligned) the result is written there
+        stream-ordered and the call returns n."""
+        inten = np.ascontiguousarray(intensity, dtype=np.float32).ravel()
+        if len(inten) != len(stores):
+            raise ValueError("one intensity per store")
+        if cap is None:
+            if out is not None:
+                raise ValueError("a device result needs its capacity")
+            j = max(int(jump), 1)
+            cap = sum(int(((s.sizes().astype(np.int64) + j - 1) // j).sum()) for s in stores if s is not None)
+        hs = (C.c_void_p * max(len(stores), 1))(*[(s.h.value if s is not None else None) for s in stores])
+        n = C.c_int64(-1)
+        args = (self.h, len(stores), hs, inten.ctypes.data_as(C.POINTER(C.c_float)), int(jump), float(voxel_size), int(min_count), int(cap))
+        if out is not None:
+            self._chk(self.lib.vba_kf_surfel_export(*args, out[0], out[1], out[2], C.byref(n)))
+            return n.value
+        rows = max(int(cap), 1)
+        rec = np.zeros((rows, 12), dtype=np.float32)
+        cov = np.zeros((rows, 6), dtype=np.float64) if want_cov else None
+        cnt = np.zeros(rows, dtype=np.int32) if want_counts else None
+        self._chk(self.lib.vba_kf_surfel_export(*args, rec.ctypes.data_as(C.c_void_p), cov.ctypes.data_as(C.c_void_p) if want_cov else None,
+                                                cnt.ctypes.data_as(C.c_void_p) if want_counts else None, C.byref(n)))
+        m = n.value
+        return rec[:m].copy(), (cov[:m].copy() if want_cov else None), (cnt[:m].copy() if want_counts else None)
+
+    def kf_export_surfel_size(self, stores, intensity, jump, voxel_size, min_count=3):
+        """the size query of vba_kf_surfel_export (cap 0, no buffers): the number of surfels kf_export_surfel would return"""
+        inten = np.ascontiguousarray(intensity, dtype=np.float32).ravel()
+        hs = (C.c_void_p * max(len(stores), 1))(*[s.h.value for s in stores])
+        n = C.c_int64(-1)
+        self._chk(self.lib.vba_kf_surfel_export(self.h, len(stores), hs, inten.ctypes.data_as(C.POINTER(C.c_float)), int(jump), float(voxel_size),
+                                                int(min_count), 0, None, None, None, C.byref(n)))
+        return n.value
+
+    def kf_export_surfel_reserve(self, max_points, max_voxels):
+        self._chk(self.lib.vba_kf_surfel_export_reserve(self.h, int(max_points), int(max_voxels)))
+
+    def kf_export_surfel_allocations(self):
+        n = C.c_int(); b = C.c_int64()
+        self._chk(self.lib.vba_kf_surfel_export_allocations(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
     def loop_update(self, lm, poses_win, bl_scans=(), bl_poses=None, bl_vars=None, win_scans=None, win_vars=None, dx12=None):
         """loop_update() (VS:1255-1373) on this context's map: adopt ``lm``, insert the buf_lba2loop scans ``bl_scans`` (list of
         [n_i][3] body points, ``bl_vars`` the matching [n_i][9] or None) at ``bl_poses`` [k][12] as fixed points with covariances,

@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include "vba_common.hpp"
 #include "vba_kernels_scan.hpp"
+#include "vba_vx.hpp"
 
 namespace vba {
 
@@ -132,30 +133,7 @@ __global__ __launch_bounds__(256) void k_kf_export(long long i0, long long n, in
 
 // Voxel-down-sampled global map (vba_kf_voxel_export): the gather of k_kf_export fused with the voxel filter of
 // down_sampling_voxel (TL:201-238) over the whole sequence S of exported records; S itself is never written.
-// One table row per NON-EMPTY keyframe of all stores in publication order: the records of S before it, the address of its point 0,
-// its current x0, its store's intensity.  Record i of keyframe k is the point  pnt + 3 (i - first) jump.
-struct VxKf { long long first; const double *pnt; double T[12]; float inten; int pad; };     // 120 bytes
-// The table has >= 2 |S| slots, so the slot is lean: the sums live in an array of their own ([slots][3] doubles, indexed as the table).
-struct alignas(16) VxSlot { unsigned long long key; int cnt, first; };                    // key DS_EMPTY when free
-// A count or emit workgroup owns `per` consecutive records (a multiple of 256) and walks them tile by tile; at most kVxBlocks
-// workgroups, so that the exclusive scan of their counts is k_ds_scan at the size it was written for.
-static constexpr int kVxBlocks = 2048;
-
-// last j in [lo, hi] with tab[j].first <= i
-__device__ __forceinline__ int vx_kf_of(long long i, int lo, int hi, const VxKf *__restrict__ tab) {
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid].first <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-// record i of S, a record of keyframe *e: x0.R p + x0.p in kf_apply's order, each coordinate narrowed to float once
-__device__ __forceinline__ void vx_world(const VxKf *__restrict__ e, long long i, int jump, float &x, float &y, float &z) {
-  const double *__restrict__ p = e->pnt + 3 * (size_t)((i - e->first) * (long long)jump);
-  double qx, qy, qz;
-  kf_apply(e->T, p[0], p[1], p[2], qx, qy, qz);
-  x = (float)qx; y = (float)qy; z = (float)qz;
-}
+// The per-keyframe table VxKf, the slot VxSlot and the record of S (vx_kf_of, vx_world) are vba_vx.hpp, shared with the surfel passes.
 
 __global__ __launch_bounds__(256) void k_vx_clear(VxSlot *__restrict__ tab, size_t cap) {
   VxSlot s; s.key = DS_EMPTY; s.cnt = 0; s.first = 0x7fffffff;

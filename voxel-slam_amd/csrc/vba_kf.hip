@@ -7,6 +7,7 @@
 #include "vba_scanlog.hpp"
 #include "vba_kernels_scan.hpp"
 #include "vba_kernels_kf.hpp"
+#include "vba_surfel_decl.hpp"
 
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -853,37 +854,11 @@ int vx_ensure(vba_ctx *c, size_t n, bool exact) {
   return VBA_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int vba_kf_voxel_export_reserve(vba_ctx *c, int64_t max_points) {
-  if (!c || max_points < 0) return VBA_ERR_BAD_ARG;
-  if (max_points >= ((int64_t)1 << 31)) return VBA_ERR_CAPACITY;
-  if (max_points == 0) return VBA_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  VxShared shared(c);
-  int st;
-  if ((st = vx_ensure(c, (size_t)max_points, true))) return st;
-  if ((st = exp_ensure_tab(c, 1))) return st;
-  return exp_ensure_out(c, (size_t)max_points + ((size_t)max_points + 3) / 4);     // a host result of max_points voxels: records, then counts
-}
-
-int vba_kf_voxel_export_allocations(vba_ctx *c, int *n_allocs, int64_t *bytes) {
-  if (!c || !n_allocs || !bytes) return VBA_ERR_BAD_ARG;
-  *n_allocs = c->sat->vx.allocs; *bytes = c->sat->vx.bytes;
-  return VBA_OK;
-}
-
-int vba_kf_voxel_export(vba_ctx *c, int n_stores, vba_kf_store *const *stores, const float *intensity, int jump, double voxel_size, int min_count,
-                        int64_t cap, float *xyzi, int *counts, int64_t *n_out) {
-  if (!c || n_stores < 1 || !stores || !intensity || jump < 1 || min_count < 1 || cap < 0 || !n_out || (cap > 0 && !xyzi) || !(voxel_size >= 0.001))
-    return VBA_ERR_BAD_ARG;
-  for (int s = 0; s < n_stores; s++) if (!stores[s] || stores[s]->ctx->device != c->device) return VBA_ERR_BAD_ARG;
-  const bool query = cap == 0 && !xyzi;
-  const bool dev_out = xyzi && is_device_ptr(xyzi);
-  if (dev_out && ((uintptr_t)xyzi & 15)) { c->set_error("vba_kf_voxel_export: a device xyzi must be 16-byte aligned"); return VBA_ERR_BAD_ARG; }
-  if (xyzi && counts && is_device_ptr(counts) != dev_out) { c->set_error("vba_kf_voxel_export: counts must be on the side of xyzi"); return VBA_ERR_BAD_ARG; }
+// The front half that vba_kf_voxel_export and vba_kf_surfel_export share: the sequence S, the per-keyframe table through the export's
+// upload ring, the table clear, the insert (with the sort and the chain sums of a deterministic context), the count, the scan and the
+// one wait of the call.  r.n == 0: nothing to export, no device work was done.
+struct VxFront { long long n = 0, per = 0, m = 0; size_t nk = 0; int nblk = 0; const VxKf *d_kft = nullptr; };
+int vx_front(vba_ctx *c, int n_stores, vba_kf_store *const *stores, const float *intensity, int jump, double voxel_size, int min_count, VxFront &r) {
   // the sequence S: its length and its non-empty keyframes
   long long total = 0;
   size_t nk = 0;
@@ -893,9 +868,8 @@ int vba_kf_voxel_export(vba_ctx *c, int n_stores, vba_kf_store *const *stores, c
       if (off[k + 1] > off[k]) { total += exp_count((long long)off[k + 1] - off[k], jump); nk++; }
   }
   if (total >= (1ll << 31) || nk > (size_t)(1 << 30)) return VBA_ERR_CAPACITY;
-  if (total == 0) { *n_out = 0; return VBA_OK; }
+  if (total == 0) return VBA_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  VxShared shared(c);
   int st;
   if ((st = vx_ensure(c, (size_t)total, false))) return st;
   if ((st = exp_ensure_tab(c, (nk * sizeof(VxKf) + sizeof(ExpKf) - 1) / sizeof(ExpKf)))) return st;
@@ -950,7 +924,51 @@ int vba_kf_voxel_export(vba_ctx *c, int n_stores, vba_kf_store *const *stores, c
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(w.h_n.p, d_n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const long long m = *w.h_n.p;
+  r.n = n; r.per = per; r.m = *w.h_n.p; r.nk = nk; r.nblk = nblk; r.d_kft = d_kft;
+  return VBA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vba_kf_voxel_export_reserve(vba_ctx *c, int64_t max_points) {
+  if (!c || max_points < 0) return VBA_ERR_BAD_ARG;
+  if (max_points >= ((int64_t)1 << 31)) return VBA_ERR_CAPACITY;
+  if (max_points == 0) return VBA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  VxShared shared(c);
+  int st;
+  if ((st = vx_ensure(c, (size_t)max_points, true))) return st;
+  if ((st = exp_ensure_tab(c, 1))) return st;
+  return exp_ensure_out(c, (size_t)max_points + ((size_t)max_points + 3) / 4);     // a host result of max_points voxels: records, then counts
+}
+
+int vba_kf_voxel_export_allocations(vba_ctx *c, int *n_allocs, int64_t *bytes) {
+  if (!c || !n_allocs || !bytes) return VBA_ERR_BAD_ARG;
+  *n_allocs = c->sat->vx.allocs; *bytes = c->sat->vx.bytes;
+  return VBA_OK;
+}
+
+int vba_kf_voxel_export(vba_ctx *c, int n_stores, vba_kf_store *const *stores, const float *intensity, int jump, double voxel_size, int min_count,
+                        int64_t cap, float *xyzi, int *counts, int64_t *n_out) {
+  if (!c || n_stores < 1 || !stores || !intensity || jump < 1 || min_count < 1 || cap < 0 || !n_out || (cap > 0 && !xyzi) || !(voxel_size >= 0.001))
+    return VBA_ERR_BAD_ARG;
+  for (int s = 0; s < n_stores; s++) if (!stores[s] || stores[s]->ctx->device != c->device) return VBA_ERR_BAD_ARG;
+  const bool query = cap == 0 && !xyzi;
+  const bool dev_out = xyzi && is_device_ptr(xyzi);
+  if (dev_out && ((uintptr_t)xyzi & 15)) { c->set_error("vba_kf_voxel_export: a device xyzi must be 16-byte aligned"); return VBA_ERR_BAD_ARG; }
+  if (xyzi && counts && is_device_ptr(counts) != dev_out) { c->set_error("vba_kf_voxel_export: counts must be on the side of xyzi"); return VBA_ERR_BAD_ARG; }
+  VxShared shared(c);
+  VxFront r;
+  int st;
+  if ((st = vx_front(c, n_stores, stores, intensity, jump, voxel_size, min_count, r))) return st;
+  auto &w = c->sat->vx;
+  const long long n = r.n, per = r.per, m = r.m;
+  const size_t nk = r.nk;
+  const int nblk = r.nblk;
+  const VxKf *d_kft = r.d_kft;
+  VxSlot *tab = (VxSlot *)w.tab.p;
   *n_out = m;
   if (query) return VBA_OK;
   if (m > cap) return VBA_ERR_CAPACITY;
@@ -966,6 +984,96 @@ int vba_kf_voxel_export(vba_ctx *c, int n_stores, vba_kf_store *const *stores, c
   HIPCHK(c, hipGetLastError());
   if (!dev_out) {
     HIPCHK(c, hipMemcpyAsync(xyzi, out, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    if (counts) HIPCHK(c, hipMemcpyAsync(counts, cnt, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return VBA_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ surfel / NDT export of the global map (vba_kf_surfel_export)
+namespace {
+
+// the moment rows and row slots of `vox` kept voxels: as they are when they suffice, else doubled until they do, after a synchronise
+int sf_ensure(vba_ctx *c, size_t vox, bool exact) {
+  auto &w = c->sat->vx;
+  if (vox <= w.sf_vox) return VBA_OK;
+  size_t m = (exact || !w.sf_vox) ? vox : w.sf_vox;
+  while (m < vox) m *= 2;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, w.sf_mom.ensure(m * 6));
+  HIPCHK(c, w.sf_row.ensure(m));
+  w.sf_allocs += 2; w.sf_bytes += (int64_t)(m * (6 * sizeof(double) + sizeof(int)));
+  w.sf_vox = m;
+  return VBA_OK;
+}
+
+// float4 entries of the export's staging for a host result of m voxels: records, then counts
+inline size_t sf_staging(size_t m) { return 3 * m + (m + 3) / 4; }
+
+}  // namespace
+
+extern "C" {
+
+int vba_kf_surfel_export_reserve(vba_ctx *c, int64_t max_points, int64_t max_voxels) {
+  if (!c || max_points < 0 || max_voxels < 0) return VBA_ERR_BAD_ARG;
+  if (max_points >= ((int64_t)1 << 31) || max_voxels >= ((int64_t)1 << 31)) return VBA_ERR_CAPACITY;
+  if (max_points == 0 && max_voxels == 0) return VBA_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  VxShared shared(c);
+  int st;
+  if (max_points > 0 && (st = vx_ensure(c, (size_t)max_points, true))) return st;
+  if ((st = exp_ensure_tab(c, 1))) return st;
+  if (max_voxels == 0) return VBA_OK;
+  if ((st = sf_ensure(c, (size_t)max_voxels, true))) return st;
+  return exp_ensure_out(c, sf_staging((size_t)max_voxels));
+}
+
+int vba_kf_surfel_export_allocations(vba_ctx *c, int *n_allocs, int64_t *bytes) {
+  if (!c || !n_allocs || !bytes) return VBA_ERR_BAD_ARG;
+  *n_allocs = c->sat->vx.allocs + c->sat->vx.sf_allocs; *bytes = c->sat->vx.bytes + c->sat->vx.sf_bytes;
+  return VBA_OK;
+}
+
+int vba_kf_surfel_export(vba_ctx *c, int n_stores, vba_kf_store *const *stores, const float *intensity, int jump, double voxel_size, int min_count,
+                         int64_t cap, float *surfels, double *cov, int *counts, int64_t *n_out) {
+  if (!c || n_stores < 1 || !stores || !intensity || jump < 1 || min_count < 1 || cap < 0 || !n_out || (cap > 0 && !surfels) || !(voxel_size >= 0.001))
+    return VBA_ERR_BAD_ARG;
+  for (int s = 0; s < n_stores; s++) if (!stores[s] || stores[s]->ctx->device != c->device) return VBA_ERR_BAD_ARG;
+  const bool query = cap == 0 && !surfels;
+  const bool dev_out = surfels && is_device_ptr(surfels);
+  if (dev_out && ((uintptr_t)surfels & 15)) { c->set_error("vba_kf_surfel_export: a device surfels must be 16-byte aligned"); return VBA_ERR_BAD_ARG; }
+  if (surfels && cov && is_device_ptr(cov) != dev_out) { c->set_error("vba_kf_surfel_export: cov must be on the side of surfels"); return VBA_ERR_BAD_ARG; }
+  if (dev_out && cov && ((uintptr_t)cov & 7)) { c->set_error("vba_kf_surfel_export: a device cov must be 8-byte aligned"); return VBA_ERR_BAD_ARG; }
+  if (surfels && counts && is_device_ptr(counts) != dev_out) { c->set_error("vba_kf_surfel_export: counts must be on the side of surfels"); return VBA_ERR_BAD_ARG; }
+  VxShared shared(c);
+  VxFront r;
+  int st;
+  if ((st = vx_front(c, n_stores, stores, intensity, jump, voxel_size, min_count, r))) return st;
+  const long long m = r.m;
+  *n_out = m;
+  if (query) return VBA_OK;
+  if (m > cap) return VBA_ERR_CAPACITY;
+  if (m == 0) return VBA_OK;
+  if ((st = sf_ensure(c, (size_t)m, false))) return st;
+  if (!dev_out && (st = exp_ensure_out(c, sf_staging((size_t)m)))) return st;
+  auto &w = c->sat->vx;
+  const bool det = c->opt.deterministic != 0;
+  SfPass p;
+  p.n = r.n; p.per = r.per; p.nblk = r.nblk; p.nkf = (int)r.nk; p.jump = jump; p.min_count = min_count; p.m = (int)m;
+  p.kft = r.d_kft; p.tab = (VxSlot *)w.tab.p; p.slot_of = w.slot.p; p.sum = w.sum.p; p.blk = w.blk.p;
+  p.skey = det ? (const unsigned int *)w.sort.p : nullptr;
+  p.sidx = det ? (const int *)(w.sort.p + 2 * w.sort_stride) : nullptr;
+  p.slot_of_row = w.sf_row.p; p.mom = w.sf_mom.p;
+  // a host result: the records and counts through the export's staging, the covariances in place of the moment rows
+  float4 *out = dev_out ? (float4 *)surfels : c->sat->exp.d_out.p;
+  double *dcov = dev_out ? cov : (cov ? w.sf_mom.p : nullptr);
+  int *cnt = dev_out ? counts : (counts ? (int *)(out + 3 * m) : nullptr);
+  HIPCHK(c, (hipError_t)sf_run(p, kExpMaxBlocks, out, dcov, cnt, c->stream));
+  if (!dev_out) {
+    HIPCHK(c, hipMemcpyAsync(surfels, out, (size_t)m * 12 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (cov) HIPCHK(c, hipMemcpyAsync(cov, dcov, (size_t)m * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (counts) HIPCHK(c, hipMemcpyAsync(counts, cnt, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }

@@ -51,11 +51,15 @@ struct CtxSat {
   // (slots_of(pts) entries each), every record's slot, the workgroup counts with the total behind them, the pinned image of that
   // total; a deterministic context also holds the sort arrays skey | idx | sidx (sort_stride bytes each) | rocPRIM scratch
   // (tmp_bytes) for `sort_pts` records.  Grow-only; allocs / bytes count these and what a call or reserve adds to the export's table
-  // and staging.
+  // and staging.  vba_kf_surfel_export runs on the same arrays and adds, for `sf_vox` KEPT voxels, a row of six
+  // moment sums and the slot of every output row; sf_allocs / sf_bytes count those two.
   struct {
     size_t pts = 0, sort_pts = 0, sort_stride = 0, tmp_bytes = 0;
     DevMem<char> tab, sort; DevMem<double> sum; DevMem<unsigned int> slot; DevMem<int> blk; PinMem<int> h_n;
     int allocs = 0; int64_t bytes = 0;
+    size_t sf_vox = 0;
+    DevMem<double> sf_mom; DevMem<int> sf_row;
+    int sf_allocs = 0; int64_t sf_bytes = 0;
   } vx;
   // vba_init.hip, vba_motion_init: raw clouds (uploaded once per call), blurred rows, pose tables
   struct Init {
