@@ -1043,6 +1043,81 @@ int vba_kf_surfel_export(vba_ctx *ctx, int n_stores, vba_kf_store *const *stores
                          double *cov /* [cap][6], same side as surfels, may be NULL */,
                          int *counts /* [cap], same side as surfels, may be NULL */, int64_t *n_out);
 
+/* ---- Registration of a scan against the surfel map: prior-map localisation.  No reference counterpart.
+ *
+ * A vba_surfel_map holds the cells of a surfel export in HBM and works on its context's stream, like a vba_loop_map; sharded
+ * contexts are VBA_ERR_UNSUPPORTED.
+ * Cell: a record of the surfel export with [11] >= min_count.  Mean c = (double)record[0..2] (the floats, so that both build
+ * paths define one map); weight W = (C + sigma^2 I)^-1 from the record's cov, six doubles xx xy xz yy yz zz, by the cofactor
+ * formula of csrc/vba_surfreg_math.hpp (sreg_weight: nothing contracted, the order written there is the definition).
+ * Key: the down-samplers' voxel key of record[0..2] at voxel_size (both inherited quirks, 21 bits per axis), which is the key of
+ * the voxel the record came from.  Two records with one key were not made at this voxel_size: VBA_ERR_BAD_ARG, the map is empty.
+ * Storage: an open-addressing table (ds_hash, linear probing) of the smallest power of two >= 2 n slots of 16 bytes (key, row),
+ * n the records given, and one 64-byte line per cell (float c[3], float cnt, double W[6]) at the record's row.
+ * _build: surfels [n][12] and cov [n][6] both HOST (staged once) or both DEVICE memory of the map's device (read in place, not
+ * kept); n == 0 empties the map.  _build_from_kf runs the surfel export into arrays the map owns (the stores' intensity is not
+ * read; refusals and locking are the export's) and builds from them.  A build waits for the stream once for its status words
+ * (cells, duplicate flag); _build_from_kf before that once for the export's count.  voxel_size >= 0.001, sigma >= 1e-4,
+ * min_count >= 1, n <= 2^30, else VBA_ERR_BAD_ARG with *n_cells untouched.
+ * _reserve(max_cells, max_points): table, cells and record staging for max_cells records, scan staging for max_points points and
+ * the state and partial blocks; afterwards no build or registration within those sizes allocates.  Beyond them a call doubles
+ * what is short after a synchronise.  _allocations: allocations made and bytes requested so far, cumulative. */
+typedef struct vba_surfel_map vba_surfel_map;
+int vba_surfel_map_create(vba_ctx *ctx, vba_surfel_map **m);
+int vba_surfel_map_destroy(vba_surfel_map *m);
+int vba_surfel_map_reserve(vba_surfel_map *m, int64_t max_cells, int64_t max_points);
+int vba_surfel_map_allocations(vba_surfel_map *m, int *n_allocs, int64_t *bytes);
+int vba_surfel_map_build(vba_surfel_map *m, int64_t n, const float *surfels /* [n][12] */, const double *cov /* [n][6] */,
+                         double voxel_size, double sigma, int min_count, int64_t *n_cells);
+int vba_surfel_map_build_from_kf(vba_surfel_map *m, int n_stores, vba_kf_store *const *stores, int jump, double voxel_size,
+                                 double sigma, int min_count, int64_t *n_cells);
+int vba_surfel_map_size(vba_surfel_map *m, int64_t *n_cells, double *voxel_size /* may be NULL */, double *sigma /* may be NULL */);
+/* Diagnostic: the occupied slots of the table in slot order, to HOST arrays of cap entries (each may be NULL): the slot, its key,
+ * the cell's row in the build arrays, the cell's c and cnt (4 floats) and W (6 doubles).  *n_out = the cells, *n_slots = the
+ * table's slots; cap == 0 is the size query, fewer than the cells is VBA_ERR_CAPACITY.  Waits for the stream. */
+int vba_debug_surfel_map_read(vba_surfel_map *m, int64_t cap, int64_t *slot, unsigned long long *key, int *row, float *c4, double *W,
+                              int64_t *n_out, int64_t *n_slots);
+
+/* Gauss-Newton registration of n body-frame points against the map, from the pose (R row-major, t) to the pose it ends at.
+ * pnt [n][3] is HOST memory (staged once) or DEVICE memory of the map's device, read in place: the points of a prepared scan
+ * frame, a slice of a keyframe store's clouds, any array.
+ * Per iteration and point: q[r] = ((R[r][0] x + R[r][1] y) + R[r][2] z) + t[r] in double, uncontracted; the voxel index of
+ * (float)q; candidates: that cell and, for neighbors == 7, its six face neighbours (+-1 on the integer axis index before
+ * packing) in the order own, -x, +x, -y, +y, -z, +z; for each existing candidate d = q - c and m = d^T W d, the smallest m wins,
+ * ties go to the earlier candidate; the point enters the sums when m < gate^2.  With J = [-R hat(p) | I] for the update
+ * R <- R Exp(dphi), t <- t + dt the 29 sums are the upper triangle of J^T W J (21, row-major), J^T W d (6), m / 2 and 1.
+ * Then H delta = -g by the library's 6x6 LDLT, the pose update, and the report slots of the iteration.
+ * End: converged (|dphi| < eps_rot and |dt| < eps_tra after a step); iters == max_iter; lost (fewer than min_matches points
+ * entered the sums: the pose is as it was before that iteration); singular (a non-finite step: the pose is unchanged).  iters
+ * counts the evaluated iterations, the one that ended lost or singular included; matches[i], cost[i] (the sum of m / 2) belong
+ * to iteration i at the pose BEFORE its step, step_rot[i], step_tra[i] are that step's norms (0 where none was taken); H, g are
+ * those of the last evaluated iteration; eig_tt the ascending eigenvalues of its translation block (the sum of W), the degeneracy
+ * figure a caller thresholds.
+ * Order of the sums: a function of n and the inputs alone; no f64 atomic is on the path; two calls return the
+ * same bytes in every mode.  One upload, max_iter gated launch pairs queued at once, one download, one wait.
+ * VBA_ERR_BAD_ARG before any device work, outputs untouched: a NULL m, pnt, p, R or t (rep may be NULL), n < 1, neighbors not 1
+ * or 7, max_iter outside 1..32, gate <= 0, an empty map, pnt on another device.
+ * vba_debug_surfel_reg_pass runs ONE iteration of the same launches with taps that are null in the loop: cell [n] the chosen
+ * cell's row in the build arrays or -1, gate [n] 1 where the point entered the sums, sums [29], dx [6] the step (zeros when none
+ * was taken); R, t leave as the loop would hold them after that iteration.  Every tap is HOST memory and may be NULL. */
+#define VBA_SURFEL_REG_MAX_ITER 32
+typedef struct {
+  double gate;
+  int neighbors, max_iter, min_matches;
+  double eps_rot, eps_tra;
+} vba_surfel_reg_params;
+typedef struct {
+  int iters, converged, lost, singular;
+  int matches[VBA_SURFEL_REG_MAX_ITER];
+  double cost[VBA_SURFEL_REG_MAX_ITER], step_rot[VBA_SURFEL_REG_MAX_ITER], step_tra[VBA_SURFEL_REG_MAX_ITER];
+  double H[21], g[6], eig_tt[3];
+} vba_surfel_reg_report;
+void vba_surfel_reg_default_params(vba_surfel_reg_params *p);   /* 3.0, 7, 30, 50, 1e-5, 1e-5 */
+int vba_surfel_register(vba_surfel_map *m, int64_t n, const double *pnt /* [n][3], HOST or DEVICE */, const vba_surfel_reg_params *p,
+                        double *R /* [9] in/out */, double *t /* [3] in/out */, vba_surfel_reg_report *rep /* may be NULL */);
+int vba_debug_surfel_reg_pass(vba_surfel_map *m, int64_t n, const double *pnt, const vba_surfel_reg_params *p, double *R, double *t,
+                              int *cell, unsigned char *gate, double *sums, double *dx);
+
 /* ------------------------------------------------------------------------------------------------
  * Loop-closure map: the counterpart of `map_loop` (VS:2601-2625) and loop_update() (VS:1255-1373), the step that
  * carries a loop closure back into local mapping.  A vba_loop_map owns one second voxel map, created from its context's options

@@ -1143,6 +1143,73 @@ inline int64_t pub_globalmap_surfel(Context &ctx, const std::vector<KeyframeStor
   return n;
 }
 
+// ---- prior-map localisation (voxelba.h "Registration of a scan against the surfel map").  No reference counterpart:
+// the cells of an earlier session's finished map in HBM, and the registration of a scan or a keyframe against them.  Works on ctx's
+// stream; the caller holds mtx_keyframe while a map is built from stores.  Destroy it before its Context.
+class SurfelMap {
+ public:
+  explicit SurfelMap(Context &ctx) : ctx_(ctx.get()) { check(ctx_, vba_surfel_map_create(ctx_, &m_)); }
+  ~SurfelMap() { vba_surfel_map_destroy(m_); }
+  SurfelMap(const SurfelMap &) = delete;
+  SurfelMap &operator=(const SurfelMap &) = delete;
+  vba_surfel_map *get() const { return m_; }
+  vba_ctx *ctx() const { return ctx_; }
+  void reserve(int64_t max_cells, int64_t max_points) { check(ctx_, vba_surfel_map_reserve(m_, max_cells, max_points)); }
+  // from the messages of pub_globalmap_surfel: records [n][12], cov [n][6] (host or device arrays).  Returns the cells.
+  int64_t build(int64_t n, const float *records, const double *cov, double voxel_size, double sigma = 0.02, int min_count = 5) {
+    int64_t cells = 0;
+    check(ctx_, vba_surfel_map_build(m_, n, records, cov, voxel_size, sigma, min_count, &cells));
+    return cells;
+  }
+  // from the stores, as pub_globalmap_surfel reads them: relc_submaps[id] for every id of `ids`
+  int64_t build(const std::vector<KeyframeStore *> &relc_submaps, const std::vector<int> &ids, double voxel_size, double sigma = 0.02, int min_count = 5,
+                int jump = 1) {
+    std::vector<vba_kf_store *> stores;
+    for (int id : ids) stores.push_back(relc_submaps.at((size_t)id)->get());
+    int64_t cells = 0;
+    check(ctx_, vba_surfel_map_build_from_kf(m_, (int)stores.size(), stores.data(), jump, voxel_size, sigma, min_count, &cells));
+    return cells;
+  }
+  int64_t size() const {
+    int64_t cells = 0;
+    check(ctx_, vba_surfel_map_size(m_, &cells, nullptr, nullptr));
+    return cells;
+  }
+ private:
+  vba_ctx *ctx_ = nullptr;
+  vba_surfel_map *m_ = nullptr;
+};
+
+inline vba_surfel_reg_params surfel_reg_defaults() { vba_surfel_reg_params p; vba_surfel_reg_default_params(&p); return p; }
+
+namespace detail {
+inline bool relocalize_points(SurfelMap &map, int64_t n, const double *d_pnt, IMUST &x, vba_surfel_reg_report *rep, const vba_surfel_reg_params &params) {
+  double R[9], t[3];
+  std::memcpy(R, x.R, 72); std::memcpy(t, x.p, 24);
+  vba_surfel_reg_report local;
+  vba_surfel_reg_report *r = rep ? rep : &local;
+  check(map.ctx(), vba_surfel_register(map.get(), n, d_pnt, &params, R, t, r));
+  const bool ok = r->converged && !r->lost && !r->singular;
+  if (ok) { std::memcpy(x.R, R, 72); std::memcpy(x.p, t, 24); }
+  return ok;
+}
+}  // namespace detail
+
+// x.R, x.p = the pose of the scan in the map's frame, from x as the first guess.  Written only when the registration converged and
+// was neither lost nor singular, which is what it returns; rep->eig_tt[0] is the degeneracy figure to threshold.
+inline bool relocalize(SurfelMap &map, const ScanView &scan, IMUST &x, vba_surfel_reg_report *rep = nullptr,
+                       const vba_surfel_reg_params &params = surfel_reg_defaults()) {
+  return detail::relocalize_points(map, scan.n, scan.pnt, x, rep, params);
+}
+// the same for keyframe kf of a store (of this or another session), read in place
+inline bool relocalize(SurfelMap &map, KeyframeStore &store, int kf, IMUST &x, vba_surfel_reg_report *rep = nullptr,
+                       const vba_surfel_reg_params &params = surfel_reg_defaults()) {
+  const double *d_pnt; const int *off; int n_kf = 0;
+  store.clouds(d_pnt, off, n_kf);
+  if (kf < 0 || kf >= n_kf) throw std::runtime_error("libvoxelba: relocalize: no such keyframe");
+  return detail::relocalize_points(map, off[kf + 1] - off[kf], d_pnt + 3 * (size_t)off[kf], x, rep, params);
+}
+
 // ---- loop closure -> local mapping (voxelba.h "Loop-closure map").  The pose algebra runs here, on the host, one
 // separately rounded product and sum after the other in the order  s = a0*b0; s += a1*b1; s += a2*b2  (compile without contraction
 // to keep it so); the device sees poses that are already moved.

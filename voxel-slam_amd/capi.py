@@ -436,6 +436,98 @@ class LoopMap(_Handle):
         return _dump_rows(self.lib.vba_loop_map_dump_plane_var, self.h, 86)
 
 
+class SurfelRegParams(C.Structure):
+    _fields_ = [("gate", C.c_double), ("neighbors", C.c_int), ("max_iter", C.c_int), ("min_matches", C.c_int),
+                ("eps_rot", C.c_double), ("eps_tra", C.c_double)]
+
+
+class SurfelRegReport(C.Structure):
+    _fields_ = [("iters", C.c_int), ("converged", C.c_int), ("lost", C.c_int), ("singular", C.c_int), ("matches", C.c_int * 32),
+                ("cost", C.c_double * 32), ("step_rot", C.c_double * 32), ("step_tra", C.c_double * 32),
+                ("H", C.c_double * 21), ("g", C.c_double * 6), ("eig_tt", C.c_double * 3)]
+
+
+def surfel_reg_default_params(**kw) -> SurfelRegParams:
+    p = SurfelRegParams()
+    load().vba_surfel_reg_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+class SurfelMap(_Handle):
+    """One vba_surfel_map: the cells of a surfel export in HBM and the registration of a scan against them.
+    Arrays are numpy arrays (host) or integer device addresses."""
+    PREFIX = "vba_surfel_map"
+
+    def reserve(self, max_cells=0, max_points=0):
+        self.ctx._chk(self.lib.vba_surfel_map_reserve(self.h, int(max_cells), int(max_points)))
+
+    def build(self, surfels, cov, voxel_size, sigma=0.02, min_count=5, n=None):
+        """from records float32 [n][12] and cov float64 [n][6] (numpy arrays, or two device addresses with ``n``) -> cells"""
+        nc = C.c_int64(-1)
+        if isinstance(surfels, (int, C.c_void_p)):
+            args = (int(n), surfels, cov)
+        else:
+            rec = np.ascontiguousarray(surfels, dtype=np.float32).reshape(-1, 12); cv = _c(cov).reshape(-1, 6)
+            if len(rec) != len(cv):
+                raise ValueError("one covariance per record")
+            args = (len(rec), rec.ctypes.data_as(C.c_void_p), _p(cv))
+        self.ctx._chk(self.lib.vba_surfel_map_build(self.h, *args, float(voxel_size), float(sigma), int(min_count), C.byref(nc)))
+        return nc.value
+
+    def build_from_kf(self, stores, jump, voxel_size, sigma=0.02, min_count=5):
+        hs = (C.c_void_p * len(stores))(*[s.h for s in stores])
+        nc = C.c_int64(-1)
+        self.ctx._chk(self.lib.vba_surfel_map_build_from_kf(self.h, len(stores), hs, int(jump), float(voxel_size), float(sigma), int(min_count),
+                                                            C.byref(nc)))
+        return nc.value
+
+    def size(self):
+        """(cells, voxel_size, sigma) of the map as built"""
+        nc = C.c_int64(); v = C.c_double(); s = C.c_double()
+        self.ctx._chk(self.lib.vba_surfel_map_size(self.h, C.byref(nc), C.byref(v), C.byref(s)))
+        return nc.value, v.value, s.value
+
+    def read(self):
+        """vba_debug_surfel_map_read -> dict(slots, slot int64 [m], key uint64 [m], row int32 [m], c float32 [m][4], W [m][6]) in
+        slot order"""
+        n = C.c_int64(); ns = C.c_int64()
+        self.ctx._chk(self.lib.vba_debug_surfel_map_read(self.h, 0, None, None, None, None, None, C.byref(n), C.byref(ns)))
+        m = max(n.value, 1)
+        slot = np.zeros(m, np.int64); key = np.zeros(m, np.uint64); row = np.zeros(m, np.int32); c4 = np.zeros((m, 4), np.float32); W = np.zeros((m, 6))
+        self.ctx._chk(self.lib.vba_debug_surfel_map_read(self.h, m, slot.ctypes.data_as(C.c_void_p), key.ctypes.data_as(C.c_void_p),
+                                                         row.ctypes.data_as(C.c_void_p), c4.ctypes.data_as(C.c_void_p), _p(W), C.byref(n), C.byref(ns)))
+        k = n.value
+        return dict(slots=ns.value, slot=slot[:k], key=key[:k], row=row[:k], c=c4[:k], W=W[:k])
+
+    @staticmethod
+    def _pnt(pnt, n):
+        if isinstance(pnt, (int, C.c_void_p)):
+            return int(n), pnt, None
+        a = _c(pnt).reshape(-1, 3)
+        return len(a), _p(a), a
+
+    def register(self, pnt, R, t, params=None, n=None):
+        """vba_surfel_register from the pose (R [3][3], t [3]) -> (R, t, SurfelRegReport); ``pnt`` [n][3] host array, or a device
+        address with ``n``"""
+        p = params if params is not None else surfel_reg_default_params()
+        n, ptr, keep = self._pnt(pnt, n)
+        R = _c(R).reshape(9).copy(); t = _c(t).reshape(3).copy(); rep = SurfelRegReport()
+        self.ctx._chk(self.lib.vba_surfel_register(self.h, n, ptr, C.byref(p), _p(R), _p(t), C.byref(rep)))
+        return R.reshape(3, 3), t, rep
+
+    def debug_pass(self, pnt, R, t, params=None, n=None):
+        """vba_debug_surfel_reg_pass: one iteration -> dict(R, t, cell int32 [n], gate uint8 [n], sums [29], dx [6])"""
+        p = params if params is not None else surfel_reg_default_params()
+        n, ptr, keep = self._pnt(pnt, n)
+        R = _c(R).reshape(9).copy(); t = _c(t).reshape(3).copy()
+        cell = np.full(n, -7, dtype=np.int32); gate = np.full(n, 7, dtype=np.uint8); sums = np.full(29, np.nan); dx = np.full(6, np.nan)
+        self.ctx._chk(self.lib.vba_debug_surfel_reg_pass(self.h, n, ptr, C.byref(p), _p(R), _p(t), cell.ctypes.data_as(C.c_void_p),
+                                                         gate.ctypes.data_as(C.c_void_p), _p(sums), _p(dx)))
+        return dict(R=R.reshape(3, 3), t=t, cell=cell, gate=gate, sums=sums, dx=dx)
+
+
 class ScanLog(_Handle):
     """One vba_scanlog: the marginalised scans of a session (the live ``ScanPose::pvec``) resident in HBM, between the map's scan
     ring and the keyframes.  Scans are numbered 0, 1, 2, ... in push order and released first in, first out."""
@@ -1139,6 +1231,9 @@ class Context:
 
     def loop_map(self) -> "LoopMap":
         return LoopMap(self)
+
+    def surfel_map(self) -> "SurfelMap":
+        return SurfelMap(self)
 
     def kf_export_world(self, stores, intensity, jump, begin=0, count=None, out=None):
         """vba_kf_export_world on this context's stream: exported points [begin, begin + count) of ``stores`` (KeyframeStore objects of

@@ -6,24 +6,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "vba_types.hpp"
+#include "vba_voxel_key.hpp"   // DS_EMPTY, ds_axis_key, ds_pack, ds_hash
 
 namespace vba {
-
-static constexpr unsigned long long DS_EMPTY = ~0ull;
-
-// TL:210-217 on PCL float coordinates; dbl != 0: the pointVar form of VM:45-51 (double coordinates)
-__device__ __forceinline__ long long ds_axis_key(double v, double voxel_size, int dbl = 0) {
-  float loc = (float)((dbl ? v : (double)(float)v) / voxel_size);
-  if (loc < 0) loc = (float)((double)loc - 1.0);
-  return (long long)loc;
-}
-__device__ __forceinline__ unsigned long long ds_pack(long long x, long long y, long long z) {
-  return ((unsigned long long)(x & 0x1FFFFF) << 42) | ((unsigned long long)(y & 0x1FFFFF) << 21) | (unsigned long long)(z & 0x1FFFFF);
-}
-__device__ __forceinline__ unsigned int ds_hash(unsigned long long k) {
-  k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-  return (unsigned int)k;
-}
 
 __global__ void k_ds_clear(DsSlot *__restrict__ tab, int cap) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
