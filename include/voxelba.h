@@ -1485,6 +1485,53 @@ int vba_odom_lio_state_estimation_kdtree_on_state(vba_ctx *ctx, vba_odom_state *
 int vba_odom_state_export_scan(vba_ctx *ctx, vba_odom_state *st, int n, const double *d_pnt_body, float intensity, int64_t cap,
                                float *xyzi, int64_t *n_out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Odometry update against a prior map: localisation mode.  No reference counterpart: the iterated-EKF update of
+ * VOXEL_SLAM::lio_state_estimation (VS:962-1098) with the point-to-distribution residuals of vba_surfel_register in the place of
+ * the point-to-plane residuals of the live voxel map.  After vba::relocalize has found the pose in an earlier session's map, this
+ * call tracks in it: the IMU prediction and its 15 x 15 covariance are the prior, v, bg and ba move through the correlations of
+ * P, and the covariance is updated, none of which vba_surfel_register does.
+ *
+ * Per iteration the point loop is that of vba_surfel_register at the pose of x_curr (query, own cell or own cell and six face
+ * neighbours, smallest m, ties to the earlier candidate, gate m < gate^2, the 29 sums in the same order, bit for bit), and the
+ * step is vba_odom_ekf's on the 34 sums  HTH = sum J^T W J (21),  HTz = -sum J^T W d (6),  sum W (6, where the voxel map has
+ * n n^T),  the count:  the MAP step of the 15-state, with the retraction R <- R Exp(dphi), t <- t + dt both sides assume.  Stop
+ * rule, iteration limit (4) and covariance update are those of VS:1072-1086, unchanged.
+ *   state [25], cov [225]: in/out as in vba_odom_lio_state_estimation.  pnt_body [n][3]: HOST memory (staged once in the map's scan
+ *   staging) or DEVICE memory of the context's device, read in place.
+ *   report: the struct of the voxel-map call; nnt_eig_min is the smallest eigenvalue of the last iteration's sum of W, the
+ *   degeneracy figure.  *ok = 1 iff the last iteration matched at least min_matches points and nnt_eig_min >= min_eig.  State and
+ *   covariance are updated either way, as in the reference; with no match at all the algebra returns the prediction bit for bit.
+ *   n == 0: no point loop is launched, state and covariance keep their bits, iterations == 2, *ok = 0 unless min_matches is 0.
+ * The start must lie within the gate: from 0.05 m / 0.5 deg the four iterations end within the estimator's bias (1e-4 .. 1e-3 m) of
+ * the pose; from 0.2 m / 2 deg only a small part of a scan passes a 3 sigma gate and four iterations do not converge.  That start is
+ * vba_surfel_register's (vba::relocalize), not this call's.
+ * Crosses the boundary: vba_odom_surfel_update uploads the image once (the host inverts P) and downloads the result block once;
+ * _on_state builds the image on the device from the state object (bit for bit the same) and only downloads.  Four gated launch
+ * pairs queued at once, ONE wait.  Order of the sums: a function of n and the inputs alone; no f64 atomic; two calls return the same
+ * bytes in every mode.  Scratch: the context's EKF image and partials (vba_odom_kdtree_allocations counts the image) and the map's
+ * scan staging (vba_surfel_map_reserve); after a first call within the reserved sizes nothing allocates.
+ * VBA_ERR_BAD_ARG before any device work, outputs and the state object untouched: a NULL ctx, m, p, state, cov or st; n < 0;
+ * n > 0 with NULL points; neighbors not 1 or 7; gate <= 0; min_matches < 0; min_eig < 0; an empty map; a map of another context;
+ * points on another device; a state object on another device.  VBA_ERR_UNSUPPORTED: a sharded context.
+ * vba_debug_odom_surfel_sums runs ONE point loop at the pose (R, t) and the reduction of the update launch, with taps to HOST
+ * arrays, each of which may be NULL: partial [nb][34] the workgroups' rows, cost [nb] their sums of m / 2, sums [34], cell [n] the
+ * chosen cell's row or -1, gate [n].  *nb = min(ceil(n / 256), 1024); cap_rows < nb with partial or cost given: VBA_ERR_CAPACITY. */
+typedef struct {
+  double gate;
+  int neighbors, min_matches;
+  double min_eig;
+} vba_surfel_odom_params;
+void vba_surfel_odom_default_params(vba_surfel_odom_params *p);   /* 3.0, 7, 30, 0.0 */
+int vba_odom_surfel_update(vba_ctx *ctx, vba_surfel_map *m, int n, const double *pnt_body /* [n][3], HOST or DEVICE */,
+                           const vba_surfel_odom_params *p, double *state /* [25] in/out */, double *cov /* [225] in/out */, int *ok,
+                           vba_odom_report *report /* may be NULL */);
+int vba_odom_surfel_update_on_state(vba_ctx *ctx, vba_odom_state *st, vba_surfel_map *m, int n, const double *d_pnt_body,
+                                    const vba_surfel_odom_params *p, int *ok, vba_odom_report *report, double *state_out);
+int vba_debug_odom_surfel_sums(vba_ctx *ctx, vba_surfel_map *m, int n, const double *pnt_body, const vba_surfel_odom_params *p,
+                               const double *R, const double *t, int cap_rows, double *partial /* [cap_rows][34] */,
+                               double *cost /* [cap_rows] */, double *sums /* [34] */, int *cell, unsigned char *gate, int *nb);
+
 #ifdef __cplusplus
 }
 #endif

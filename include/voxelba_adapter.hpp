@@ -615,6 +615,7 @@ inline int lio_state_estimation_kdtree(Context &ctx, const ScanView &scan, IMUST
 // ---- the odometry state resident in HBM: x_curr and its covariance stay on the device from one scan to the next;
 // the per-scan chain odom_ekf.process -> prepare -> lio_state_estimation -> pvec_update + cut_voxel_multi (VS:1873-1922) reads and
 // writes them where they lie
+class SurfelMap;
 class OdomState {
  public:
   explicit OdomState(Context &ctx) : ctx_(ctx.get()) { check(ctx_, vba_odom_state_create(ctx_, &s_)); }
@@ -653,6 +654,9 @@ class OdomState {
     check(ctx.get(), vba_odom_lio_state_estimation_on_state(ctx.get(), s_, scan.n, scan.pnt, scan.var, &ok, report, x_out ? &x_out->t : nullptr));
     return ok != 0;
   }
+  // the same update against a prior map (vba::lio_state_estimation_prior below) on the resident state
+  inline bool lio_state_estimation_prior(Context &ctx, SurfelMap &map, const ScanView &scan, const vba_surfel_odom_params &params,
+                                         vba_odom_report *report = nullptr, IMUST *x_out = nullptr);
   // pvec_update + cut_voxel_multi (VS:1903-1920) with the pose and covariance blocks of the resident state
   void pvec_update_cut_voxel_multi(Context &ctx, const ScanView &scan, int win_count) {
     check(ctx.get(), vba_map_pvec_update_cut_voxel_on_state(ctx.get(), s_, win_count, scan.n, scan.pnt, scan.var, 1));
@@ -1208,6 +1212,23 @@ inline bool relocalize(SurfelMap &map, KeyframeStore &store, int kf, IMUST &x, v
   store.clouds(d_pnt, off, n_kf);
   if (kf < 0 || kf >= n_kf) throw std::runtime_error("libvoxelba: relocalize: no such keyframe");
   return detail::relocalize_points(map, off[kf + 1] - off[kf], d_pnt + 3 * (size_t)off[kf], x, rep, params);
+}
+
+// ---- localisation mode (voxelba.h "Odometry update against a prior map"): lio_state_estimation with the cells of a
+// prior map in the place of the live voxel map.  x_curr (state + cov) in/out; returns ok (enough matches, no degenerate direction
+// by params.min_eig); the state is updated either way, as in lio_state_estimation.  The start must lie within the gate (relocalize).
+inline vba_surfel_odom_params surfel_odom_defaults() { vba_surfel_odom_params p; vba_surfel_odom_default_params(&p); return p; }
+inline bool lio_state_estimation_prior(Context &ctx, SurfelMap &map, const ScanView &scan, IMUST &x_curr,
+                                       const vba_surfel_odom_params &params = surfel_odom_defaults(), vba_odom_report *report = nullptr) {
+  int ok = 0;
+  check(ctx.get(), vba_odom_surfel_update(ctx.get(), map.get(), scan.n, scan.pnt, &params, &x_curr.t, x_curr.cov, &ok, report));
+  return ok != 0;
+}
+inline bool OdomState::lio_state_estimation_prior(Context &ctx, SurfelMap &map, const ScanView &scan, const vba_surfel_odom_params &params,
+                                                  vba_odom_report *report, IMUST *x_out) {
+  int ok = 0;
+  check(ctx.get(), vba_odom_surfel_update_on_state(ctx.get(), s_, map.get(), scan.n, scan.pnt, &params, &ok, report, x_out ? &x_out->t : nullptr));
+  return ok != 0;
 }
 
 // ---- loop closure -> local mapping (voxelba.h "Loop-closure map").  The pose algebra runs here, on the host, one

@@ -733,8 +733,26 @@ class OdomReport(C.Structure):
                 ("nnt_eig_min", C.c_double)]
 
 
+class SurfelOdomParams(C.Structure):
+    """vba_surfel_odom_params (include/voxelba.h)."""
+    _fields_ = [("gate", C.c_double), ("neighbors", C.c_int), ("min_matches", C.c_int), ("min_eig", C.c_double)]
+
+
+def surfel_odom_default_params(**kw) -> SurfelOdomParams:
+    p = SurfelOdomParams()
+    load().vba_surfel_odom_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _odom_report(rep):
+    return dict(iterations=rep.iterations, match_num=np.array(rep.match_num[:], dtype=np.int64), rot_add=np.array(rep.rot_add[:]),
+                tra_add=np.array(rep.tra_add[:]), nnt_eig_min=rep.nnt_eig_min)
+
+
 class OdomState(_Handle):
-    """One vba_odom_state: the odometry state and its covariance resident in HBM from one scan to the next, with the pose table of
+    """One vba_odom_state:the odometry state and its covariance resident in HBM from one scan to the next, with the pose table of
     the IMU propagation."""
     PREFIX = "vba_odom_state"
 
@@ -784,6 +802,17 @@ class OdomState(_Handle):
         report = dict(iterations=rep.iterations, match_num=np.array(rep.match_num[:], dtype=np.int64), rot_add=np.array(rep.rot_add[:]),
                       tra_add=np.array(rep.tra_add[:]), nnt_eig_min=rep.nnt_eig_min)
         return bool(ok.value), st, report
+
+    def surfel_update(self, smap, pnt, params=None, n=None, ctx=None):
+        """Context.odom_surfel_update on the resident state: (ok, state, report); ``pnt`` a device address
+        with ``n`` (read in place) or a host array [n][3] (staged in the map); the state object holds state and covariance
+        afterwards."""
+        ctx = ctx or self.ctx
+        p = params if params is not None else surfel_odom_default_params()
+        n, ptr, keep = SurfelMap._pnt(pnt, n)
+        ok = C.c_int(0); rep = OdomReport(); st = np.zeros(25)
+        ctx._chk(self.lib.vba_odom_surfel_update_on_state(ctx.h, self.h, smap.h, n, ptr, C.byref(p), C.byref(ok), C.byref(rep), _p(st)))
+        return bool(ok.value), st, _odom_report(rep)
 
     def pvec_update_cut_voxel(self, win_count, n, d_pnt_body, d_var_body, multi=False, ctx=None):
         """Context.pvec_update_cut_voxel_dev with the pose and covariance blocks of the resident state."""
@@ -1558,6 +1587,29 @@ class Context:
         report = dict(iterations=rep.iterations, match_num=np.array(rep.match_num[:], dtype=np.int64), rot_add=np.array(rep.rot_add[:]),
                       tra_add=np.array(rep.tra_add[:]), nnt_eig_min=rep.nnt_eig_min)
         return bool(ok.value), state, cov, report
+
+    def odom_surfel_update(self, smap, pnt, state25, cov225, params=None, n=None):
+        """vba_odom_surfel_update: the iterated-EKF update of (state, cov) against the cells of ``smap``.
+        ``pnt`` [n][3] host array, or a device address with ``n``.  Returns (ok, state, cov, report), report as in
+        lio_state_estimation_resident with nnt_eig_min the smallest eigenvalue of the last iteration's sum of W."""
+        p = params if params is not None else surfel_odom_default_params()
+        n, ptr, keep = SurfelMap._pnt(pnt, n)
+        state = _c(state25).reshape(25).copy(); cov = _c(cov225).reshape(225).copy(); ok = C.c_int(0); rep = OdomReport()
+        self._chk(self.lib.vba_odom_surfel_update(self.h, smap.h, n, ptr, C.byref(p), _p(state), _p(cov), C.byref(ok), C.byref(rep)))
+        return bool(ok.value), state, cov.reshape(15, 15), _odom_report(rep)
+
+    def debug_odom_surfel_sums(self, smap, pnt, R, t, params=None, n=None):
+        """vba_debug_odom_surfel_sums: ONE point loop of odom_surfel_update at the pose (R, t) -> dict(partial [nb][34], cost [nb],
+        sums [34], cell int32 [n], gate uint8 [n], nb)"""
+        p = params if params is not None else surfel_odom_default_params()
+        n, ptr, keep = SurfelMap._pnt(pnt, n)
+        R = _c(R).reshape(9); t = _c(t).reshape(3)
+        rows = min((n + 255) // 256, 1024)
+        partial = np.full((rows, 34), np.nan); cost = np.full(rows, np.nan); sums = np.full(34, np.nan); nb = C.c_int(-1)
+        cell = np.full(n, -7, dtype=np.int32); gate = np.full(n, 7, dtype=np.uint8)
+        self._chk(self.lib.vba_debug_odom_surfel_sums(self.h, smap.h, n, ptr, C.byref(p), _p(R), _p(t), rows, _p(partial), _p(cost), _p(sums),
+                                                      cell.ctypes.data_as(C.c_void_p), gate.ctypes.data_as(C.c_void_p), C.byref(nb)))
+        return dict(partial=partial, cost=cost, sums=sums, cell=cell, gate=gate, nb=nb.value)
 
     # ---- multi-GPU / timing
     def lio_state_estimation_kdtree(self, pnt_body, state25, cov225):

@@ -204,4 +204,16 @@ __global__ void k_fill_u64(unsigned long long *p, unsigned long long v, size_t n
 // the one-workgroup exclusive scan of the map's stable compactions, also the match-list offsets of vba_btc.hip
 __global__ __launch_bounds__(1024) void k_det_scan(int *a, int n_max, int *cnt, int which_n, int cap_n, int which_out);
 
+// ---------------------------------------------------------------- vba_surfreg.hip
+// What the prior-map odometry update of vba_odom.hip (vba_odom_surfel_update*) needs of a surfel map, whose struct
+// is private to its unit.  surfel_odom_args_ok: the map belongs to c and has cells, and the n points are host memory or memory of
+// c's device.  surfel_odom_stage: *d_pnt = pnt when it is device memory, else the map's scan staging after one stream-ordered copy.
+// surfel_odom_queue: ONE point loop (k_sodom_accum) of n > 0 points on st at the pose of the image d_S; returns nb, the rows [34]
+// of d_partial it writes.  d_cost [nb], d_cell [n], d_gate [n]: taps, null in the loop.
+bool surfel_odom_args_ok(const vba_surfel_map *m, const vba_ctx *c, int n, const double *pnt);
+int surfel_odom_stage(vba_surfel_map *m, int n, const double *pnt, const double **d_pnt);
+int surfel_odom_blocks(int n);
+int surfel_odom_queue(vba_surfel_map *m, hipStream_t st, const vbh::OdomEkf *d_S, int n, const double *d_pnt, double gate, int neighbors,
+                      double *d_partial, double *d_cost, int *d_cell, unsigned char *d_gate);
+
 }  // namespace vba

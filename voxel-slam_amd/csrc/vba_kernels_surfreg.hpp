@@ -1,6 +1,7 @@
-// Kernels of the surfel map and of the registration against it (vba_surfel_map_*, vba_surfel_register), compiled by
-// vba_surfreg.hip without contraction.  The arithmetic is vba_surfreg_math.hpp (shared with the g++ build of the tests); the kernels
-// below own the table build, which workgroup owns which points, and the order of the sums.
+// Kernels of the surfel map, of the registration against it (vba_surfel_map_*, vba_surfel_register) and of the point
+// loop of the odometry update against it (vba_odom_surfel_update, §27), compiled by vba_surfreg.hip without contraction.  The
+// arithmetic is vba_surfreg_math.hpp (shared with the g++ build of the tests); the kernels below own the table build, which
+// workgroup owns which points, and the order of the sums.
 //
 // Order contract of an iteration over n points with nb = min(ceil(n / 256), SREG_MAX_BLOCKS) workgroups of 256: lane l of workgroup
 // b adds its points b * 256 + l, (b + nb) * 256 + l, ... in ascending order into 29 chains; a wave adds its 64 lanes by the xor
@@ -10,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include "vba_common.hpp"
 #include "vba_surfreg_math.hpp"
+#include "vba_odom_ekf.hpp"
 
 namespace vba {
 
@@ -53,13 +55,12 @@ __global__ __launch_bounds__(256) void k_sreg_insert(int n, const float *__restr
   atomicAdd(&status->n_cells, 1);
 }
 
-// One iteration's sums: per-workgroup partials [nb][29].  Taps (null in vba_surfel_register): cellrow[n] the chosen row or -1,
-// gate[n] 1 where the point entered the sums.
-__global__ __launch_bounds__(256) void k_sreg_accum(int n, const double *__restrict__ pnt, SregTable T, const SregState *__restrict__ st,
-                                                   double *__restrict__ part, int *__restrict__ cellrow, unsigned char *__restrict__ gate) {
+// The point loop and the first two levels of the order contract above, written once for k_sreg_accum and k_sodom_accum: the lane
+// chains over this workgroup's points at the pose and gate of st, the butterfly of each wave, the four wave sums in red, and the
+// barrier behind them.  Taps as in k_sreg_accum.  sreg_wg_sum then gives (w0 + w1) + (w2 + w3) of sum k to whichever lane asks.
+__device__ __forceinline__ void sreg_accum_waves(int n, const double *__restrict__ pnt, const SregTable &T, const SregState &st,
+                                                 int *__restrict__ cellrow, unsigned char *__restrict__ gate, double (*red)[SREG_PART]) {
   BTC_NOCONTRACT
-  __shared__ double red[4][SREG_PART];
-  if (st->done) return;
   double s[SREG_PART];
 #pragma unroll
   for (int k = 0; k < SREG_PART; k++) s[k] = 0.0;
@@ -67,7 +68,7 @@ __global__ __launch_bounds__(256) void k_sreg_accum(int n, const double *__restr
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
     const double p[3] = {pnt[3 * (size_t)i], pnt[3 * (size_t)i + 1], pnt[3 * (size_t)i + 2]};
     bool pass;
-    const int row = sreg_point(T, *st, p, s, &pass);
+    const int row = sreg_point(T, st, p, s, &pass);
     if (cellrow) cellrow[i] = row;
     if (gate) gate[i] = pass ? 1 : 0;
   }
@@ -78,8 +79,49 @@ __global__ __launch_bounds__(256) void k_sreg_accum(int n, const double *__restr
     for (int k = 0; k < SREG_PART; k++) red[threadIdx.x >> 6][k] = s[k];
   }
   __syncthreads();
-  if (threadIdx.x < SREG_PART)
-    part[(size_t)blockIdx.x * SREG_PART + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+__device__ __forceinline__ double sreg_wg_sum(const double (*red)[SREG_PART], int k) {
+  BTC_NOCONTRACT
+  return (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+}
+
+// One iteration's sums: per-workgroup partials [nb][29].  Taps (null in vba_surfel_register): cellrow[n] the chosen row or -1,
+// gate[n] 1 where the point entered the sums.
+__global__ __launch_bounds__(256) void k_sreg_accum(int n, const double *__restrict__ pnt, SregTable T, const SregState *__restrict__ st,
+                                                   double *__restrict__ part, int *__restrict__ cellrow, unsigned char *__restrict__ gate) {
+  BTC_NOCONTRACT
+  __shared__ double red[4][SREG_PART];
+  if (st->done) return;
+  sreg_accum_waves(n, pnt, T, *st, cellrow, gate, red);
+  if (threadIdx.x < SREG_PART) part[(size_t)blockIdx.x * SREG_PART + threadIdx.x] = sreg_wg_sum(red, threadIdx.x);
+}
+
+// The point loop of one iteration of the prior-map odometry update (vba_odom_surfel_update): the same points, cells,
+// gate, terms and sums at the pose S->R, S->t of the EKF image, returning at once when the image's stop rule has fired.  One row [34]
+// per workgroup in the layout k_odom_update reduces (vba_odom_ekf.hpp): columns 0..20 the sums 0..20 (J^T W J), 21..26 the negated
+// sums 21..26 (HTz = -J^T W d), 27..32 the sums 15..20 again (the sum of W where the voxel map puts n n^T), 33 the count.  Sum 27
+// (m / 2) goes to cost[workgroup], a tap like cellrow and gate: null in the loop.
+constexpr int SODOM_ROW = 34;
+__global__ __launch_bounds__(256) void k_sodom_accum(int n, const double *__restrict__ pnt, SregTable T, const vbh::OdomEkf *__restrict__ S,
+                                                    double gate2, int neighbors, double *__restrict__ part, double *__restrict__ cost,
+                                                    int *__restrict__ cellrow, unsigned char *__restrict__ gate) {
+  BTC_NOCONTRACT
+  __shared__ double red[4][SREG_PART];
+  if (__builtin_amdgcn_readfirstlane(S->done)) return;
+  SregState X;                                             // what sreg_point reads of a state: pose, gate, candidates
+#pragma unroll
+  for (int k = 0; k < 9; k++) X.R[k] = S->R[k];
+#pragma unroll
+  for (int k = 0; k < 3; k++) X.t[k] = S->t[k];
+  X.gate2 = gate2; X.neighbors = neighbors;
+  sreg_accum_waves(n, pnt, T, X, cellrow, gate, red);
+  const int c = threadIdx.x;
+  if (c < SODOM_ROW) {
+    const int k = c < 27 ? c : (c < 33 ? c - 12 : 28);
+    const double v = sreg_wg_sum(red, k);
+    part[(size_t)blockIdx.x * SODOM_ROW + c] = (c >= 21 && c < 27) ? -v : v;
+  }
+  if (cost && c == 0) cost[blockIdx.x] = sreg_wg_sum(red, 27);
 }
 
 // reduce the partials in workgroup order, step (vba_surfreg_math.hpp), and at the end of the loop the eigenvalues of the

@@ -4,7 +4,8 @@
 // (vba_kernels_odom.hpp) and whose loop it queues (map_odom_resident).  And the odometry state resident in HBM (vba_odom_state_*, the
 // IMU propagation vba_imu_ekf_propagate / vba_odom_state_propagate, the update and the insertion on a state object; the
 // initialisation odometry and the published scan on a state object) with the kernels of vba_kernels_imu_ekf.hpp,
-// compiled here and nowhere else.
+// compiled here and nowhere else.  And the update against a prior surfel map (vba_odom_surfel_update*), whose point
+// loop the surfel-map unit compiles and queues (surfel_odom_queue).
 #include "vba_ctx.hpp"
 #include "vba_sat.hpp"
 #include "vba_odom_state.hpp"
@@ -637,6 +638,132 @@ int vba_odom_state_export_scan(vba_ctx *c, vba_odom_state *st, int n, const doub
     HIPCHK(c, hipMemcpyAsync(xyzi, out, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
+  return VBA_OK;
+}
+
+// ---------------------------------------------------------------- the update against a prior map
+// The iterated-EKF update of the 15-state against the cells of a surfel map: the point loop is k_sodom_accum (vba_surfreg.hip queues
+// it), whose rows k_odom_update reduces and steps on with kd = 0 as it does for the voxel map.  Image, pinned block and partials are
+// the context's (c->sat->odom).
+void vba_surfel_odom_default_params(vba_surfel_odom_params *p) {
+  if (!p) return;
+  p->gate = 3.0; p->neighbors = 7; p->min_matches = 30; p->min_eig = 0.0;
+}
+static bool sodom_params_ok(const vba_surfel_odom_params *p) {
+  return p && (p->neighbors == 1 || p->neighbors == 7) && p->gate > 0.0 && std::isfinite(p->gate) && p->min_matches >= 0 && p->min_eig >= 0.0;
+}
+static int sodom_unsharded(vba_ctx *c, const char *who) {
+  if (c->n_ranks > 1 || c->rank != 0) { c->set_error(std::string(who) + ": sharded contexts are not supported"); return VBA_ERR_UNSUPPORTED; }
+  return VBA_OK;
+}
+// the rows of the context's partials that a point loop of n points writes
+static int sodom_part_ensure(vba_ctx *c, int n) { return odom_part_ensure(c, 256 * surfel_odom_blocks(n)); }
+// the four (point loop, update) pairs on an image that is in d_S by then; n == 0 launches the updates alone, on no partials
+static int sodom_queue(vba_ctx *c, vba_surfel_map *m, int n, const double *d_pnt, const vba_surfel_odom_params *p) {
+  vbh::OdomEkf *d_S = c->sat->odom.d;
+  for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
+    const int nb = n > 0 ? surfel_odom_queue(m, c->stream, d_S, n, d_pnt, p->gate, p->neighbors, c->sat->odom.d_part, nullptr, nullptr, nullptr) : 0;
+    hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, c->stream, d_S, (const double *)c->sat->odom.d_part.p, nb, iter, 0);
+  }
+  HIPCHK(c, hipGetLastError());
+  return VBA_OK;
+}
+// ok and the report from the downloaded result block
+static void sodom_finish(const vbh::OdomEkf &S, const vba_surfel_odom_params *p, int *ok, vba_odom_report *report) {
+  const double emin = vbh::odom_nnt_eig_min(S.nnt);
+  const int last = S.iterations > 0 ? S.match_num[S.iterations - 1] : 0;
+  if (ok) *ok = (last >= p->min_matches && emin >= p->min_eig) ? 1 : 0;
+  if (report) odom_report_fill(report, S, emin);
+}
+
+int vba_odom_surfel_update(vba_ctx *c, vba_surfel_map *m, int n, const double *pnt_body, const vba_surfel_odom_params *p, double *state,
+                           double *cov, int *ok, vba_odom_report *report) {
+  if (!c || !m || !state || !cov || n < 0 || (n > 0 && !pnt_body) || !sodom_params_ok(p) || !surfel_odom_args_ok(m, c, n, pnt_body)) return VBA_ERR_BAD_ARG;
+  int st = sodom_unsharded(c, "vba_odom_surfel_update");
+  if (st) return st;
+  HIPCHK(c, hipSetDevice(c->device));
+  const double *d_pnt;
+  if ((st = odom_image_ensure(c)) || (st = sodom_part_ensure(c, n)) || (st = surfel_odom_stage(m, n, pnt_body, &d_pnt))) return st;
+  vbh::OdomEkf &S = *c->sat->odom.h;
+  vbh::OdomEkf *d_S = c->sat->odom.d;
+  hipStream_t s = c->stream;
+  odom_image_begin(S, state, cov, false);
+  HIPCHK(c, hipMemcpyAsync(d_S, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
+  if ((st = sodom_queue(c, m, n, d_pnt, p))) return st;
+  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
+  HIPCHK(c, hipMemcpyAsync((char *)&S + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
+  std::memcpy(cov, S.P_out, sizeof(S.P_out));
+  sodom_finish(S, p, ok, report);
+  return VBA_OK;
+}
+
+int vba_odom_surfel_update_on_state(vba_ctx *c, vba_odom_state *st, vba_surfel_map *m, int n, const double *d_pnt_body,
+                                    const vba_surfel_odom_params *p, int *ok, vba_odom_report *report, double *state_out) {
+  if (!c || !st || !m || n < 0 || (n > 0 && !d_pnt_body) || !sodom_params_ok(p) || c->device != st->ctx->device ||
+      !surfel_odom_args_ok(m, c, n, d_pnt_body))
+    return VBA_ERR_BAD_ARG;
+  int r = sodom_unsharded(c, "vba_odom_surfel_update_on_state");
+  if (r) return r;
+  HIPCHK(c, hipSetDevice(c->device));
+  const double *d_pnt;
+  if ((r = odom_image_ensure(c)) || (r = sodom_part_ensure(c, n)) || (r = surfel_odom_stage(m, n, d_pnt_body, &d_pnt)) ||
+      (r = odom_state_order(st, c->stream, c->err)))
+    return r;
+  hipStream_t s = c->stream;
+  vbh::OdomEkf *d_S = c->sat->odom.d;
+  vbh::OdomEkf &S = *c->sat->odom.h;
+  hipLaunchKernelGGL(k_odom_begin_dev, dim3(1), dim3(256), 0, s, d_S, (const double *)st->d_blk.p);
+  if ((r = sodom_queue(c, m, n, d_pnt, p))) return r;
+  // as in vba_odom_lio_state_estimation_on_state: the wait is for the download alone, the copy back into the block runs behind it
+  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
+  HIPCHK(c, hipMemcpyAsync((char *)&S + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipEventRecord(st->res_ev, s));
+  hipLaunchKernelGGL(k_odom_commit_dev, dim3(1), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, st->d_blk.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventSynchronize(st->res_ev));
+  sodom_finish(S, p, ok, report);
+  if (state_out) std::memcpy(state_out, &S.x_curr, sizeof(S.x_curr));
+  return VBA_OK;
+}
+
+int vba_debug_odom_surfel_sums(vba_ctx *c, vba_surfel_map *m, int n, const double *pnt_body, const vba_surfel_odom_params *p, const double *R,
+                               const double *t, int cap_rows, double *partial, double *cost, double *sums, int *cell, unsigned char *gate, int *nb_out) {
+  if (!c || !m || !R || !t || n < 1 || !pnt_body || cap_rows < 0 || !sodom_params_ok(p) || !all_finite(R, 9) || !all_finite(t, 3) ||
+      !surfel_odom_args_ok(m, c, n, pnt_body))
+    return VBA_ERR_BAD_ARG;
+  int st = sodom_unsharded(c, "vba_debug_odom_surfel_sums");
+  if (st) return st;
+  const int nb = surfel_odom_blocks(n);
+  if (nb_out) *nb_out = nb;
+  if ((partial || cost) && cap_rows < nb) return VBA_ERR_CAPACITY;
+  HIPCHK(c, hipSetDevice(c->device));
+  const double *d_pnt;
+  if ((st = odom_image_ensure(c)) || (st = sodom_part_ensure(c, n)) || (st = surfel_odom_stage(m, n, pnt_body, &d_pnt))) return st;
+  // the taps in buffers of this call: [sums 34 | cost nb] doubles, [cell n] ints, [gate n] bytes
+  DevMem<double> d_out; DevMem<int> d_cell; DevMem<unsigned char> d_gate;
+  HIPCHK(c, d_out.ensure(34 + (size_t)nb));
+  HIPCHK(c, d_cell.ensure((size_t)n));
+  HIPCHK(c, d_gate.ensure((size_t)n));
+  hipStream_t s = c->stream;
+  // an image of which the point loop reads the pose and the flag alone
+  vbh::OdomEkf &S = *c->sat->odom.h;
+  std::memset(&S, 0, sizeof(S));
+  std::memcpy(S.R, R, sizeof(S.R)); std::memcpy(S.t, t, sizeof(S.t));
+  HIPCHK(c, hipMemcpyAsync(c->sat->odom.d.p, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
+  double *d_part = c->sat->odom.d_part.p;
+  surfel_odom_queue(m, s, c->sat->odom.d, n, d_pnt, p->gate, p->neighbors, d_part, d_out.p + 34, d_cell.p, d_gate.p);
+  hipLaunchKernelGGL(k_odom_sums, dim3(1), dim3(256), 0, s, (const double *)d_part, nb, d_out.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(s));
+  hipError_t e = hipSuccess;
+  if (sums) e = hipMemcpy(sums, d_out.p, 34 * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && cost) e = hipMemcpy(cost, d_out.p + 34, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && partial) e = hipMemcpy(partial, d_part, (size_t)nb * 34 * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && cell) e = hipMemcpy(cell, d_cell.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && gate) e = hipMemcpy(gate, d_gate.p, (size_t)n, hipMemcpyDeviceToHost);
+  HIPCHK(c, e);
   return VBA_OK;
 }
 

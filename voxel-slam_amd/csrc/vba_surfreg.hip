@@ -1,4 +1,5 @@
-// libvoxelba.so, the surfel-map unit: vba_surfel_map_* and vba_surfel_register, kernels in vba_kernels_surfreg.hpp.
+// libvoxelba.so, the surfel-map unit: vba_surfel_map_* and vba_surfel_register, kernels in vba_kernels_surfreg.hpp;
+// also the point loop of the odometry update against a surfel map (§27), queued from vba_odom.hip through surfel_odom_queue.
 // Compiled with -ffp-contract=off (csrc/Makefile): the order and rounding of every operation of the build and of an iteration is
 // part of the interface, and a host build of vba_surfreg_math.hpp gives the device's bits for a cell and for a point.
 #include "vba_ctx.hpp"
@@ -164,6 +165,29 @@ void sreg_fill_state(SregState *h, const vba_surfel_reg_params *p, const double 
 }
 
 }  // namespace
+
+// ---------------------------------------------------------------- for vba_odom.hip (declared in vba_ctx.hpp)
+namespace vba {
+bool surfel_odom_args_ok(const vba_surfel_map *m, const vba_ctx *c, int n, const double *pnt) {
+  if (!m || m->ctx != c || m->n_cells < 1) return false;
+  if (n == 0) return true;
+  const int dev = sreg_device_of(pnt);
+  return dev < 0 || dev == c->device;
+}
+int surfel_odom_stage(vba_surfel_map *m, int n, const double *pnt, const double **d_pnt) {
+  *d_pnt = pnt;
+  if (n == 0 || sreg_device_of(pnt) >= 0) return VBA_OK;
+  return sreg_stage_pnt(m, n, pnt, d_pnt);
+}
+int surfel_odom_blocks(int n) { return sreg_blocks(n); }
+int surfel_odom_queue(vba_surfel_map *m, hipStream_t st, const vbh::OdomEkf *d_S, int n, const double *d_pnt, double gate, int neighbors,
+                      double *d_partial, double *d_cost, int *d_cell, unsigned char *d_gate) {
+  const int nb = sreg_blocks(n);
+  SregTable T; T.tab = m->tab.p; T.cell = m->cell.p; T.mask = m->mask; T.voxel = m->voxel;
+  k_sodom_accum<<<nb, 256, 0, st>>>(n, d_pnt, T, d_S, gate * gate, neighbors, d_partial, d_cost, d_cell, d_gate);
+  return nb;
+}
+}  // namespace vba
 
 extern "C" {
 
