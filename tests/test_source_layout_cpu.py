@@ -400,3 +400,51 @@ def test_var_world_is_called_by_both_stagings():
     assert "#pragma clang fp contract(off)" in fn and "ph[3 * r]" in fn
     # the calcBodyVar half stays a twin (default contraction in k_var_init, contract(off) in k_init_blur): DESIGN.md says so
     assert "#pragma clang fp contract(off)" in kernel_body("vba_kernels_init.hpp", "k_init_blur")
+
+
+# ---------------------------------------------------------------- the frame of an odometry update ("Source layout": vba_odom.hip)
+ODOM_ENTRIES = ("vba_odom_lio_state_estimation_resident", "vba_odom_lio_state_estimation_kdtree_resident", "vba_odom_surfel_update",
+                "vba_odom_lio_state_estimation_on_state", "vba_odom_lio_state_estimation_kdtree_on_state", "vba_odom_surfel_update_on_state")
+
+
+def launches(kernel):
+    """{file: launches of `kernel` in either spelling} over csrc/"""
+    pat = re.compile(r"hipLaunchKernelGGL\(\s*\(?%s\b|\b%s\s*<<<" % (kernel, kernel))
+    assert pat.search("hipLaunchKernelGGL(%s, dim3(1)," % kernel) and pat.search("%s<<<nb, 256, 0, st>>>(n)" % kernel)
+    assert not pat.search("hipLaunchKernelGGL(%s_dev, dim3(1)," % kernel) and not pat.search("// the reduction of %s stored" % kernel)
+    return {f: len(pat.findall(read(f))) for f in sources() if pat.search(read(f))}
+
+
+def test_odometry_frame_is_written_once():
+    assert launches("k_odom_update") == {"vba_odom.hip": 1}
+    assert launches("k_odom_commit_dev") == {"vba_odom.hip": 1}
+    assert launches("k_odom_sums") == {"vba_odom.hip": 1}
+    rng = re.compile(r"offsetof\(\s*vbh::OdomEkf\s*,\s*x_curr\s*\)")
+    assert rng.search("r0 = offsetof(vbh::OdomEkf, x_curr), r1") and not rng.search("offsetof(vbh::OdomEkf, R)")
+    assert {f: len(rng.findall(read(f))) for f in sources() if rng.search(read(f))} == {"vba_odom.hip": 1}
+    unit = read("vba_odom.hip")
+    assert "k_odom_update" in function_body(unit, r"^static int odom_loop_queue\(") and "k_odom_sums" in function_body(unit, r"^static int odom_sums_run\(")
+    assert "k_odom_commit_dev" in function_body(unit, r"^static int odom_end_state\(")
+    assert rng.search(function_body(unit, r"^static int odom_result_download\("))
+
+
+def test_the_map_exports_its_point_loop_alone():
+    gone = re.compile(r"\bmap_odom_(?:resident|queue|debug_sums)\b")
+    assert gone.search("st = map_odom_queue(c->map, s") and not gone.search("nb = map_odom_point_loop(s, st")
+    assert [f for f in sources() if gone.search(read(f))] == []
+    assert re.findall(r"\bmap_odom_\w+", read("vba_ctx.hpp")) == ["map_odom_point_loop"]
+    # the map unit uploads no image and downloads no result block
+    img = re.compile(r"hipMemcpyAsync\([^;]*\bOdomEkf\b")
+    assert img.search("VBA_HIPCHK(err, hipMemcpyAsync(d_S, h_img, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, st));")
+    assert not img.search("hipMemcpyAsync(a, b, n, hipMemcpyDefault, st);\n  const vbh::OdomEkf *d_S;")
+    assert not img.search(read("vba_map.hip")) and img.search(read("vba_odom.hip"))
+    assert sorted(reached("vba_map.hip") & set(SATELLITE_ONLY)) == []
+
+
+def test_odometry_entry_points_run_the_frame():
+    unit = read("vba_odom.hip")
+    launch = re.compile(r"hipLaunchKernelGGL\(\s*k_odom_update\b")
+    assert launch.search(function_body(unit, r"^static int odom_loop_queue\("))        # (the search does see the launch)
+    for entry in ODOM_ENTRIES:
+        body = function_body(unit, r"^int %s\(" % entry)
+        assert len(body) > 300 and not launch.search(body) and "offsetof" not in body, entry

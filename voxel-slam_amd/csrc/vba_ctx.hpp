@@ -185,16 +185,13 @@ int map_stats(MapStore &s, hipStream_t st, long long *out8, std::string &err);
 int map_dump_leaves(MapStore &s, hipStream_t st, double *out, int max_leaves, std::string &err);
 int map_dump_plane_var(MapStore &s, hipStream_t st, double *out, int max_leaves, std::string &err);
 int map_prune(MapStore &s, hipStream_t st, double jour, int dist, std::string &err);
-int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomEkf *h_img, int n, const double *d_pts,
-                      const double *d_var, double *d_partial, std::string &err);
-// its four (point loop, update) pairs alone, on an image that is already in d_S
-int map_odom_queue(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, int n, const double *d_pts, const double *d_var, double *d_partial,
-                   std::string &err);
-int map_odom_debug_sums(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, const vbh::OdomEkf *h_img, int n, const double *d_pts,
-                        const double *d_var, double *d_partial, double *d_sums, int *nb_out, std::string &err);
+// the map's one odometry export: ONE point loop (k_odom_match_dev) at the pose of the image d_S; returns the rows [34] of d_partial
+// it wrote, 0 for n == 0 or a map never allocated.  The frame around it is vba_odom.hip's (odom_loop_queue).
+int map_odom_point_loop(MapStore &s, hipStream_t st, const vbh::OdomEkf *d_S, int n, const double *d_pts, const double *d_var,
+                        double *d_partial);
 int map_debug_plane_update(hipStream_t st, int n, const double *in, double *out, std::string &err);
-// the update launch of the resident EKF loops (vba_kernels_odom.hpp), also the kd-tree variant's in vba_odom.hip, and the launch that
-// stores its sums alone (vba_debug_odom_sums)
+// the update launch of the resident EKF loops and the launch that stores its sums alone (vba_kernels_odom.hpp): compiled by the map
+// unit, launched by the frame in vba_odom.hip and nowhere else
 __global__ __launch_bounds__(256) void k_odom_update(vbh::OdomEkf *S, const double *__restrict__ partial, int nb, int iter, int kd);
 __global__ __launch_bounds__(256) void k_odom_sums(const double *__restrict__ partial, int nb, double *__restrict__ sums);
 int map_fix_source_ensure(MapStore &s, hipStream_t st, size_t nodes, size_t fix, size_t n, std::string &err);

@@ -686,49 +686,15 @@ int map_cut_voxel_fix_source(MapStore &s, hipStream_t st, int n, const FixSource
 }
 
 // ================================================================================================ resident odometry loop (vba_kernels_odom.hpp)
-// One point loop of the resident update, as queued: the match launch over nb workgroups when there is anything to match, else nothing
-// (every sum is zero: the reduction then runs on no partials).  Returns nb, the rows of d_partial the reduction is to read.
-static int map_odom_point_loop(MapStore &s, hipStream_t st, const MapParams &P, const vbh::OdomEkf *d_S, int n, const double *d_pts,
-                               const double *d_var, double *d_partial) {
+// ONE point loop of the resident update at the pose of the image d_S, the map's part of the frame that vba_odom.hip queues: the match
+// launch over nb workgroups when there is anything to match, else nothing (every sum is zero: the reduction then runs on no
+// partials).  Returns nb, the rows of d_partial the reduction is to read.
+int map_odom_point_loop(MapStore &s, hipStream_t st, const vbh::OdomEkf *d_S, int n, const double *d_pts, const double *d_var,
+                        double *d_partial) {
   if (!(n > 0 && s.allocated)) return 0;
   const int nb = (n + 255) / 256;
-  hipLaunchKernelGGL(k_odom_match_dev, dim3(nb), dim3(256), 0, st, s.v, P, d_S, n, d_pts, d_var, d_partial);
+  hipLaunchKernelGGL(k_odom_match_dev, dim3(nb), dim3(256), 0, st, s.v, map_params(s), d_S, n, d_pts, d_var, d_partial);
   return nb;
-}
-int map_odom_queue(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, int n, const double *d_pts, const double *d_var, double *d_partial,
-                   std::string &err) {
-  const MapParams P = map_params(s);
-  for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
-    const int nb = map_odom_point_loop(s, st, P, d_S, n, d_pts, d_var, d_partial);
-    hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, st, d_S, (const double *)d_partial, nb, iter, 0);
-  }
-  VBA_HIPCHK(err, hipGetLastError());
-  return VBA_OK;
-}
-// The whole call on the stream: one upload of the image, (match, update) x 4, one download of the result block, one wait.  h_img
-// is pinned and holds the image on entry and the result block on return.
-int map_odom_resident(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, vbh::OdomEkf *h_img, int n, const double *d_pts,
-                      const double *d_var, double *d_partial, std::string &err) {
-  VBA_HIPCHK(err, hipMemcpyAsync(d_S, h_img, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, st));
-  const int r = map_odom_queue(s, st, d_S, n, d_pts, d_var, d_partial, err);
-  if (r) return r;
-  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
-  VBA_HIPCHK(err, hipMemcpyAsync((char *)h_img + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, st));
-  VBA_HIPCHK(err, hipStreamSynchronize(st));
-  return VBA_OK;
-}
-// vba_debug_odom_sums on the voxel map: the image uploaded, ONE point loop as the call above queues it, the reduction of
-// k_odom_update stored by k_odom_sums, the stream drained.  *nb_out = the rows of d_partial that the loop wrote (0 on a map never
-// allocated).  d_sums: 34 doubles of device memory.
-int map_odom_debug_sums(MapStore &s, hipStream_t st, vbh::OdomEkf *d_S, const vbh::OdomEkf *h_img, int n, const double *d_pts,
-                        const double *d_var, double *d_partial, double *d_sums, int *nb_out, std::string &err) {
-  VBA_HIPCHK(err, hipMemcpyAsync(d_S, h_img, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, st));
-  const int nb = map_odom_point_loop(s, st, map_params(s), d_S, n, d_pts, d_var, d_partial);
-  hipLaunchKernelGGL(k_odom_sums, dim3(1), dim3(256), 0, st, (const double *)d_partial, nb, d_sums);
-  VBA_HIPCHK(err, hipGetLastError());
-  VBA_HIPCHK(err, hipStreamSynchronize(st));
-  *nb_out = nb;
-  return VBA_OK;
 }
 
 // vba_debug_plane_update: plane_update_dev on n caller-supplied leaves, one lane each, on a scratch view of this call (cap = n, ncov

@@ -1,11 +1,12 @@
 // libvoxelba.so: the odometry EKF updates, both variants.  The initialisation odometry on a point-cloud map (vba_odom_kdtree_*,
 // vba_odom_lio_state_estimation_kdtree*) with the kernels of vba_kernels_kd.hpp, compiled here and nowhere else, and
 // the scan-to-map update on the voxel map (vba_odom_lio_state_estimation*, §17), whose kernels the map unit compiles
-// (vba_kernels_odom.hpp) and whose loop it queues (map_odom_resident).  And the odometry state resident in HBM (vba_odom_state_*, the
+// (vba_kernels_odom.hpp) and whose point loop it queues (map_odom_point_loop).  And the odometry state resident in HBM (vba_odom_state_*, the
 // IMU propagation vba_imu_ekf_propagate / vba_odom_state_propagate, the update and the insertion on a state object; the
 // initialisation odometry and the published scan on a state object) with the kernels of vba_kernels_imu_ekf.hpp,
 // compiled here and nowhere else.  And the update against a prior surfel map (vba_odom_surfel_update*), whose point
-// loop the surfel-map unit compiles and queues (surfel_odom_queue).
+// loop the surfel-map unit compiles and queues (surfel_odom_queue).  All of them run in one frame, written once below ("the frame
+// of an update"): a back-end supplies its point loop and its ok rule.
 #include "vba_ctx.hpp"
 #include "vba_sat.hpp"
 #include "vba_odom_state.hpp"
@@ -116,6 +117,13 @@ int vba_odom_kdtree_allocations(vba_ctx *c, int *n_allocs, int64_t *bytes) {
   return VBA_OK;
 }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------- the frame of an update (DESIGN.md "Source layout", §17)
+// Every update, on any map and in either state form, is begin / odom_loop_queue / [what the back-end queues behind the loop] / end on
+// the context's stream, image (c->sat->odom.d), pinned block (c->sat->odom.h) and partials.  A back-end supplies `loop`: queue ONE
+// point loop at the pose of the image, return the rows [34] of partials it wrote.
+//
 // The image of a call: odom_ekf_begin on (state, cov) with cov_inv = P^-1 (VS:987), or in kd mode P^-1 / 1000 entry by entry (VS:1134,
 // VS:1213) and the first iteration searching
 static void odom_image_begin(vbh::OdomEkf &S, const double *state, const double *cov, bool kd) {
@@ -125,6 +133,89 @@ static void odom_image_begin(vbh::OdomEkf &S, const double *state, const double 
   vbh::odom_ekf_begin(S, state, cov, cov_inv);
   if (kd) S.refind = 1;
 }
+static int odom_image_upload(vba_ctx *c) {
+  HIPCHK(c, hipMemcpyAsync(c->sat->odom.d.p, c->sat->odom.h.p, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, c->stream));
+  return VBA_OK;
+}
+// The four (point loop, update) pairs on an image that is on the device by then; which of them do any work is decided by the `done`
+// flag in the image.  A loop that returns 0 rows (n == 0, a map never allocated) leaves the update alone, on no partials: d_part may
+// then be NULL.  kd: the stop rule of the initialisation odometry.
+template <class Loop>
+static int odom_loop_queue(vba_ctx *c, const double *d_part, int kd, Loop loop) {
+  for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
+    const int nb = loop();
+    hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, c->stream, c->sat->odom.d.p, d_part, nb, iter, kd);
+  }
+  HIPCHK(c, hipGetLastError());
+  return VBA_OK;
+}
+// the one download of a call: the result block of the image into the pinned block
+static int odom_result_download(vba_ctx *c) {
+  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
+  HIPCHK(c, hipMemcpyAsync((char *)c->sat->odom.h.p + r0, (const char *)c->sat->odom.d.p + r0, r1 - r0, hipMemcpyDeviceToHost, c->stream));
+  return VBA_OK;
+}
+// The host form: the host inverts P once, writes one image and uploads it; the end downloads the result block, waits once and
+// updates state and cov.  The call has completed on return and c->sat->odom.h holds the loop's result block.  Nothing here touches
+// c->d_stage: a caller may keep the scan there.
+static int odom_begin_host(vba_ctx *c, const double *state, const double *cov, bool kd) {
+  odom_image_begin(*c->sat->odom.h, state, cov, kd);
+  return odom_image_upload(c);
+}
+static int odom_end_host(vba_ctx *c, double *state, double *cov) {
+  const int r = odom_result_download(c);
+  if (r) return r;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const vbh::OdomEkf &S = *c->sat->odom.h;
+  std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
+  std::memcpy(cov, S.P_out, sizeof(S.P_out));
+  return VBA_OK;
+}
+// The form on a state resident in HBM: the image is made from the state block by a kernel behind the block's last
+// user.  The wait of the end is for the download alone: the copy back into the state block runs behind it, ordered before whatever
+// reads the block next.
+static int odom_begin_state(vba_ctx *c, vba_odom_state *st, bool kd) {
+  const int r = odom_state_order(st, c->stream, c->err);
+  if (r) return r;
+  if (kd) hipLaunchKernelGGL(k_odom_begin_kd_dev, dim3(1), dim3(256), 0, c->stream, c->sat->odom.d.p, (const double *)st->d_blk.p);
+  else hipLaunchKernelGGL(k_odom_begin_dev, dim3(1), dim3(256), 0, c->stream, c->sat->odom.d.p, (const double *)st->d_blk.p);
+  return VBA_OK;
+}
+static int odom_end_state(vba_ctx *c, vba_odom_state *st, double *state_out) {
+  const int r = odom_result_download(c);
+  if (r) return r;
+  HIPCHK(c, hipEventRecord(st->res_ev, c->stream));
+  hipLaunchKernelGGL(k_odom_commit_dev, dim3(1), dim3(256), 0, c->stream, (const vbh::OdomEkf *)c->sat->odom.d.p, st->d_blk.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventSynchronize(st->res_ev));
+  if (state_out) std::memcpy(state_out, &c->sat->odom.h->x_curr, sizeof(c->sat->odom.h->x_curr));
+  return VBA_OK;
+}
+// The diagnostic tail: the pinned image uploaded as the caller left it, ONE point loop as odom_loop_queue queues it, the reduction of
+// k_odom_update stored by k_odom_sums into d_sums [34], the stream drained.
+template <class Loop>
+static int odom_sums_run(vba_ctx *c, const double *d_part, double *d_sums, Loop loop) {
+  const int r = odom_image_upload(c);
+  if (r) return r;
+  const int nb = loop();
+  hipLaunchKernelGGL(k_odom_sums, dim3(1), dim3(256), 0, c->stream, d_part, nb, d_sums);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return VBA_OK;
+}
+// the partials of a point loop of up to n points in workgroups of 256 (the voxel map's and, through sodom_part_ensure, the surfel map's)
+static int odom_part_ensure(vba_ctx *c, int n) {
+  const size_t need = (size_t)((n + 255) / 256) * 34;
+  if (need > c->sat->odom.d_part.n) {
+    size_t cap = 256 * 34;
+    while (cap < need) cap *= 2;
+    HIPCHK(c, c->sat->odom.d_part.ensure(cap));               // idle: the call that used it ended in a synchronise
+  }
+  return VBA_OK;
+}
+
+extern "C" {
+
 // One point loop of the kd-tree update, as queued: search per slice, merge + fit, the 28 sums per workgroup.  n > 0.
 static void kd_point_loop(hipStream_t s, const vbh::OdomEkf *d_S, int n, int kd_slices, const double *d_pts, int m, const double *tree,
                           unsigned long long *d_cand, double *d_pl, double *d_part) {
@@ -136,9 +227,8 @@ static void kd_point_loop(hipStream_t s, const vbh::OdomEkf *d_S, int n, int kd_
 
 // One update on a scan in device memory, c->sat->kd.n + n <= 2^28, in three parts that the host-fed form (kd_odom_core) and the form on a
 // state resident in HBM (vba_odom_lio_state_estimation_kdtree_on_state) share: kd_odom_ensure sizes the map halves and
-// the scratch and says whether the scan only seeds the map (fewer than 100 map points, VS:1105-1118); kd_odom_queue queues the loop,
-// the append and the re-sampling behind an image that is on the device by then; kd_odom_finish takes the new map size from the
-// downloaded result block.
+// the scratch and says whether the scan only seeds the map (fewer than 100 map points, VS:1105-1118); kd_odom_queue queues the loop
+// of the frame and behind it the append and the re-sampling; kd_odom_finish takes the new map size from the downloaded result block.
 struct KdPlan {
   int nb, kd_slices;
   size_t tot;
@@ -170,16 +260,16 @@ static int kd_odom_queue(vba_ctx *c, int n, const double *d_pts, KdPlan &p) {
   vbh::OdomEkf *d_S = c->sat->odom.d;
   hipStream_t s = c->stream;
   double *tree = c->sat->kd.d_tree[c->sat->kd.cur], *tree_out = c->sat->kd.d_tree[c->sat->kd.cur ^ 1];
-  for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
+  // n == 0: the point loop is skipped, nb == 0 and d_part may be NULL (no scan scratch was ever needed)
+  int st = odom_loop_queue(c, p.d_part, 1, [&] {
     if (n > 0) kd_point_loop(s, d_S, n, p.kd_slices, d_pts, c->sat->kd.n, tree, p.d_cand, p.d_pl, p.d_part);
-    // n == 0: nb == 0 and d_part may be NULL (no scan scratch was ever needed); the reduction reads nb * 34 doubles, that is none
-    hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, s, d_S, (const double *)p.d_part, p.nb, iter, 1);
-  }
+    return p.nb;
+  });
+  if (st) return st;
   // map update VS:1238-1250: the scan appended in the refined pose, map + scan re-sampled on a 0.5 m grid into the other half; the
   // voxel count lands in the result block
   if (n > 0) hipLaunchKernelGGL(k_kd_append_dev, dim3(p.nb), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, n, d_pts, tree + (size_t)c->sat->kd.n * 3);
   p.w.n_out = &d_S->n_map;
-  int st;
   if ((st = ds_core(c, s, 0, (int)p.tot, tree, nullptr, 9, 4, 0.5, p.det, p.w))) return st;
   hipLaunchKernelGGL(k_ds_emit, dim3(((int)p.tot + 255) / 256), dim3(256), 0, s, (int)p.tot, (const DsSlot *)p.w.tab, (const int *)p.w.slot, (const int *)p.w.blk, tree_out,
                      p.d_cnt, p.d_first, (double *)nullptr, 0);
@@ -195,8 +285,7 @@ static int kd_odom_finish(vba_ctx *c, const KdPlan &p) {
 }
 
 // The host-fed form.  When the scan only seeds the map the append is enqueued, *ran stays false and nothing is waited for.  Otherwise
-// state and cov are updated, the call has completed on return and c->sat->odom.h holds the loop's result block.  Nothing here touches
-// c->d_stage: a caller may keep the scan there.
+// the host form of the frame.
 static int kd_odom_core(vba_ctx *c, int n, const double *d_pts, double *state, double *cov, bool *ran) {
   *ran = false;
   KdPlan p;
@@ -212,18 +301,9 @@ static int kd_odom_core(vba_ctx *c, int n, const double *d_pts, double *state, d
     c->sat->kd.n += n;
     return VBA_OK;
   }
-  vbh::OdomEkf &S = *c->sat->odom.h;
-  odom_image_begin(S, state, cov, true);
-  vbh::OdomEkf *d_S = c->sat->odom.d;
-  hipStream_t s = c->stream;
-  HIPCHK(c, hipMemcpyAsync(d_S, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
-  if ((st = kd_odom_queue(c, n, d_pts, p))) return st;
-  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
-  HIPCHK(c, hipMemcpyAsync((char *)&S + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  if ((st = kd_odom_finish(c, p))) return st;
-  std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
-  std::memcpy(cov, S.P_out, sizeof(S.P_out));
+  if ((st = odom_begin_host(c, state, cov, true)) || (st = kd_odom_queue(c, n, d_pts, p)) || (st = odom_end_host(c, state, cov)) ||
+      (st = kd_odom_finish(c, p)))
+    return st;
   *ran = true;
   return VBA_OK;
 }
@@ -259,28 +339,25 @@ int vba_odom_lio_state_estimation_kdtree(vba_ctx *c, int n, const double *pnt_bo
 }
 
 // ---------------------------------------------------------------- odometry scan-to-map (VS:962-1098)
-// One update on a scan in device memory with the iterations resident on the device: the host inverts P once, writes
-// one image, queues the four (point loop, update) pairs and waits once; which of them do any work is decided by the `done` flag in the
-// device state.  state and cov are updated, c->sat->odom.h holds the loop's result block.  Nothing here touches c->d_stage: a caller may keep
-// the scan there.  Runs on this rank's map, whatever n_ranks is.
-static int odom_part_ensure(vba_ctx *c, int n) {
-  const size_t need = (size_t)((n + 255) / 256) * 34;
-  if (need > c->sat->odom.d_part.n) {
-    size_t cap = 256 * 34;
-    while (cap < need) cap *= 2;
-    HIPCHK(c, c->sat->odom.d_part.ensure(cap));               // idle: the call that used it ended in a synchronise
-  }
-  return VBA_OK;
+// One update on a scan in device memory: the host form of the frame on the map's point loop.  Runs on this rank's map, whatever
+// n_ranks is.
+static int voxel_point_loop(vba_ctx *c, int n, const double *d_pts, const double *d_var, double *d_part) {
+  return map_odom_point_loop(c->map, c->stream, c->sat->odom.d, n, d_pts, d_var, d_part);
+}
+static int voxel_odom_queue(vba_ctx *c, int n, const double *d_pts, const double *d_var) {
+  double *d_part = c->sat->odom.d_part;
+  return odom_loop_queue(c, d_part, 0, [=] { return voxel_point_loop(c, n, d_pts, d_var, d_part); });
+}
+// ok and the report from the downloaded result block: SelfAdjointEigenSolver(nnt).eigenvalues()[0] < 14 -> false  (VS:1090-1097)
+static void voxel_odom_finish(const vbh::OdomEkf &S, int *ok, vba_odom_report *report) {
+  const double emin = vbh::odom_nnt_eig_min(S.nnt);
+  if (ok) *ok = (emin < 14) ? 0 : 1;
+  if (report) odom_report_fill(report, S, emin);
 }
 static int odom_core(vba_ctx *c, int n, const double *d_pts, const double *d_var, double *state, double *cov) {
   int st = odom_image_ensure(c);
-  if (st || (st = odom_part_ensure(c, n))) return st;
-  vbh::OdomEkf &S = *c->sat->odom.h;
-  odom_image_begin(S, state, cov, false);
-  if ((st = map_odom_resident(c->map, c->stream, c->sat->odom.d, c->sat->odom.h, n, d_pts, d_var, c->sat->odom.d_part, c->err))) return st;
-  std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
-  std::memcpy(cov, S.P_out, sizeof(S.P_out));
-  return VBA_OK;
+  if (st || (st = odom_part_ensure(c, n)) || (st = odom_begin_host(c, state, cov, false)) || (st = voxel_odom_queue(c, n, d_pts, d_var))) return st;
+  return odom_end_host(c, state, cov);
 }
 
 int vba_odom_lio_state_estimation_resident(vba_ctx *c, int n, const double *d_pnt_body, const double *d_var_body, double *state, double *cov,
@@ -289,11 +366,7 @@ int vba_odom_lio_state_estimation_resident(vba_ctx *c, int n, const double *d_pn
   if (c->n_ranks > 1) { c->set_error("the resident odometry loop has no all-reduce step between its iterations: unsharded contexts only"); return VBA_ERR_UNSUPPORTED; }
   const int st = odom_core(c, n, d_pnt_body, d_var_body, state, cov);
   if (st) return st;
-  const vbh::OdomEkf &S = *c->sat->odom.h;
-  // SelfAdjointEigenSolver(nnt).eigenvalues()[0] < 14 -> false  (VS:1090-1097)
-  const double emin = vbh::odom_nnt_eig_min(S.nnt);
-  if (ok) *ok = (emin < 14) ? 0 : 1;
-  if (report) odom_report_fill(report, S, emin);
+  voxel_odom_finish(*c->sat->odom.h, ok, report);
   return VBA_OK;
 }
 
@@ -308,7 +381,7 @@ int vba_odom_lio_state_estimation(vba_ctx *c, int n, const double *pnt_body, con
     HIPCHK(c, hipMemcpyAsync(d_var, var_body, (size_t)n * 9 * sizeof(double), hipMemcpyDefault, c->stream));
   }
   if ((st = odom_core(c, n, d_pts, d_var, state, cov))) return st;
-  if (ok) *ok = (vbh::odom_nnt_eig_min(c->sat->odom.h->nnt) < 14) ? 0 : 1;
+  voxel_odom_finish(*c->sat->odom.h, ok, nullptr);
   return VBA_OK;
 }
 
@@ -344,17 +417,12 @@ int vba_debug_odom_sums(vba_ctx *c, int kind, int n, const double *pnt_body, con
   HIPCHK(c, hipMemsetAsync(d_out.p, 0, d_out.n * sizeof(double), s));
   HIPCHK(c, hipMemcpyAsync(d_pts, pnt_body, (size_t)n * 3 * sizeof(double), hipMemcpyDefault, s));
   if (!kd) HIPCHK(c, hipMemcpyAsync(d_var, var_body, (size_t)n * 9 * sizeof(double), hipMemcpyDefault, s));
-  vbh::OdomEkf &S = *c->sat->odom.h;
-  odom_image_begin(S, state, cov, kd);
-  if (kd) {
-    HIPCHK(c, hipMemcpyAsync(c->sat->odom.d.p, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
+  odom_image_begin(*c->sat->odom.h, state, cov, kd);
+  st = odom_sums_run(c, d_part, d_sums, [&] {
+    if (!kd) return voxel_point_loop(c, n, d_pts, d_var, d_part);
     kd_point_loop(s, c->sat->odom.d, n, ns, d_pts, c->sat->kd.n, c->sat->kd.d_tree[c->sat->kd.cur], d_cand, d_pl, d_part);
-    hipLaunchKernelGGL(k_odom_sums, dim3(1), dim3(256), 0, s, (const double *)d_part, nb, d_sums);
-    st = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess ? VBA_OK : VBA_ERR_HIP;
-  } else {
-    int nb_run = 0;
-    st = map_odom_debug_sums(c->map, s, c->sat->odom.d, c->sat->odom.h, n, d_pts, d_var, d_part, d_sums, &nb_run, c->err);
-  }
+    return nb;
+  });
   if (st) { hipStreamSynchronize(s); return st; }                           // (nothing of this call is left in flight behind a status)
   hipError_t e = hipMemcpy(sums, d_sums, 34 * sizeof(double), hipMemcpyDefault);
   if (e == hipSuccess) e = hipMemcpy(partial, d_part, (size_t)nb * 34 * sizeof(double), hipMemcpyDefault);
@@ -538,23 +606,10 @@ int vba_odom_lio_state_estimation_on_state(vba_ctx *c, vba_odom_state *st, int n
   if (c->n_ranks > 1) { c->set_error("the resident odometry loop has no all-reduce step between its iterations: unsharded contexts only"); return VBA_ERR_UNSUPPORTED; }
   HIPCHK(c, hipSetDevice(c->device));
   int r = odom_image_ensure(c);
-  if (r || (r = odom_part_ensure(c, n)) || (r = odom_state_order(st, c->stream, c->err))) return r;
-  hipStream_t s = c->stream;
-  vbh::OdomEkf *d_S = c->sat->odom.d;
-  vbh::OdomEkf &S = *c->sat->odom.h;
-  hipLaunchKernelGGL(k_odom_begin_dev, dim3(1), dim3(256), 0, s, d_S, (const double *)st->d_blk.p);
-  if ((r = map_odom_queue(c->map, s, d_S, n, d_pnt_body, d_var_body, c->sat->odom.d_part, c->err))) return r;
-  // the wait is for the download alone: the copy back into the state block runs behind it, ordered before whatever reads the block next
-  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
-  HIPCHK(c, hipMemcpyAsync((char *)&S + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipEventRecord(st->res_ev, s));
-  hipLaunchKernelGGL(k_odom_commit_dev, dim3(1), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, st->d_blk.p);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventSynchronize(st->res_ev));
-  const double emin = vbh::odom_nnt_eig_min(S.nnt);      // VS:1090-1097
-  if (ok) *ok = (emin < 14) ? 0 : 1;
-  if (report) odom_report_fill(report, S, emin);
-  if (state_out) std::memcpy(state_out, &S.x_curr, sizeof(S.x_curr));
+  if (r || (r = odom_part_ensure(c, n)) || (r = odom_begin_state(c, st, false)) || (r = voxel_odom_queue(c, n, d_pnt_body, d_var_body)) ||
+      (r = odom_end_state(c, st, state_out)))
+    return r;
+  voxel_odom_finish(*c->sat->odom.h, ok, report);
   return VBA_OK;
 }
 
@@ -600,22 +655,11 @@ int vba_odom_lio_state_estimation_kdtree_on_state(vba_ctx *c, vba_odom_state *st
     }
     return VBA_OK;
   }
-  if ((r = odom_state_order(st, s, c->err))) return r;
-  vbh::OdomEkf *d_S = c->sat->odom.d;
-  vbh::OdomEkf &S = *c->sat->odom.h;
-  hipLaunchKernelGGL(k_odom_begin_kd_dev, dim3(1), dim3(256), 0, s, d_S, (const double *)st->d_blk.p);
-  if ((r = kd_odom_queue(c, n, d_pnt_body, p))) return r;
-  // as in vba_odom_lio_state_estimation_on_state: the wait is for the download alone, the copy back into the block runs behind it
-  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
-  HIPCHK(c, hipMemcpyAsync((char *)&S + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipEventRecord(st->res_ev, s));
-  hipLaunchKernelGGL(k_odom_commit_dev, dim3(1), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, st->d_blk.p);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventSynchronize(st->res_ev));
-  if ((r = kd_odom_finish(c, p))) return r;
-  *iterations = S.iterations;
-  if (report) odom_report_fill(report, S, 0.0);
-  if (state_out) std::memcpy(state_out, &S.x_curr, sizeof(S.x_curr));
+  if ((r = odom_begin_state(c, st, true)) || (r = kd_odom_queue(c, n, d_pnt_body, p)) || (r = odom_end_state(c, st, state_out)) ||
+      (r = kd_odom_finish(c, p)))
+    return r;
+  *iterations = c->sat->odom.h->iterations;
+  if (report) odom_report_fill(report, *c->sat->odom.h, 0.0);
   return VBA_OK;
 }
 
@@ -658,15 +702,12 @@ static int sodom_unsharded(vba_ctx *c, const char *who) {
 }
 // the rows of the context's partials that a point loop of n points writes
 static int sodom_part_ensure(vba_ctx *c, int n) { return odom_part_ensure(c, 256 * surfel_odom_blocks(n)); }
-// the four (point loop, update) pairs on an image that is in d_S by then; n == 0 launches the updates alone, on no partials
+// the loop of the frame on the surfel map's point loop; n == 0 launches the updates alone, on no partials
 static int sodom_queue(vba_ctx *c, vba_surfel_map *m, int n, const double *d_pnt, const vba_surfel_odom_params *p) {
-  vbh::OdomEkf *d_S = c->sat->odom.d;
-  for (int iter = 0; iter < vbh::ODOM_EKF_MAX_ITER; iter++) {
-    const int nb = n > 0 ? surfel_odom_queue(m, c->stream, d_S, n, d_pnt, p->gate, p->neighbors, c->sat->odom.d_part, nullptr, nullptr, nullptr) : 0;
-    hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, c->stream, d_S, (const double *)c->sat->odom.d_part.p, nb, iter, 0);
-  }
-  HIPCHK(c, hipGetLastError());
-  return VBA_OK;
+  double *d_part = c->sat->odom.d_part;
+  return odom_loop_queue(c, d_part, 0, [=] {
+    return n > 0 ? surfel_odom_queue(m, c->stream, c->sat->odom.d, n, d_pnt, p->gate, p->neighbors, d_part, nullptr, nullptr, nullptr) : 0;
+  });
 }
 // ok and the report from the downloaded result block
 static void sodom_finish(const vbh::OdomEkf &S, const vba_surfel_odom_params *p, int *ok, vba_odom_report *report) {
@@ -684,18 +725,8 @@ int vba_odom_surfel_update(vba_ctx *c, vba_surfel_map *m, int n, const double *p
   HIPCHK(c, hipSetDevice(c->device));
   const double *d_pnt;
   if ((st = odom_image_ensure(c)) || (st = sodom_part_ensure(c, n)) || (st = surfel_odom_stage(m, n, pnt_body, &d_pnt))) return st;
-  vbh::OdomEkf &S = *c->sat->odom.h;
-  vbh::OdomEkf *d_S = c->sat->odom.d;
-  hipStream_t s = c->stream;
-  odom_image_begin(S, state, cov, false);
-  HIPCHK(c, hipMemcpyAsync(d_S, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
-  if ((st = sodom_queue(c, m, n, d_pnt, p))) return st;
-  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
-  HIPCHK(c, hipMemcpyAsync((char *)&S + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  std::memcpy(state, &S.x_curr, sizeof(S.x_curr));
-  std::memcpy(cov, S.P_out, sizeof(S.P_out));
-  sodom_finish(S, p, ok, report);
+  if ((st = odom_begin_host(c, state, cov, false)) || (st = sodom_queue(c, m, n, d_pnt, p)) || (st = odom_end_host(c, state, cov))) return st;
+  sodom_finish(*c->sat->odom.h, p, ok, report);
   return VBA_OK;
 }
 
@@ -709,22 +740,9 @@ int vba_odom_surfel_update_on_state(vba_ctx *c, vba_odom_state *st, vba_surfel_m
   HIPCHK(c, hipSetDevice(c->device));
   const double *d_pnt;
   if ((r = odom_image_ensure(c)) || (r = sodom_part_ensure(c, n)) || (r = surfel_odom_stage(m, n, d_pnt_body, &d_pnt)) ||
-      (r = odom_state_order(st, c->stream, c->err)))
+      (r = odom_begin_state(c, st, false)) || (r = sodom_queue(c, m, n, d_pnt, p)) || (r = odom_end_state(c, st, state_out)))
     return r;
-  hipStream_t s = c->stream;
-  vbh::OdomEkf *d_S = c->sat->odom.d;
-  vbh::OdomEkf &S = *c->sat->odom.h;
-  hipLaunchKernelGGL(k_odom_begin_dev, dim3(1), dim3(256), 0, s, d_S, (const double *)st->d_blk.p);
-  if ((r = sodom_queue(c, m, n, d_pnt, p))) return r;
-  // as in vba_odom_lio_state_estimation_on_state: the wait is for the download alone, the copy back into the block runs behind it
-  const size_t r0 = offsetof(vbh::OdomEkf, x_curr), r1 = offsetof(vbh::OdomEkf, R);
-  HIPCHK(c, hipMemcpyAsync((char *)&S + r0, (const char *)d_S + r0, r1 - r0, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipEventRecord(st->res_ev, s));
-  hipLaunchKernelGGL(k_odom_commit_dev, dim3(1), dim3(256), 0, s, (const vbh::OdomEkf *)d_S, st->d_blk.p);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventSynchronize(st->res_ev));
-  sodom_finish(S, p, ok, report);
-  if (state_out) std::memcpy(state_out, &S.x_curr, sizeof(S.x_curr));
+  sodom_finish(*c->sat->odom.h, p, ok, report);
   return VBA_OK;
 }
 
@@ -746,17 +764,15 @@ int vba_debug_odom_surfel_sums(vba_ctx *c, vba_surfel_map *m, int n, const doubl
   HIPCHK(c, d_out.ensure(34 + (size_t)nb));
   HIPCHK(c, d_cell.ensure((size_t)n));
   HIPCHK(c, d_gate.ensure((size_t)n));
-  hipStream_t s = c->stream;
   // an image of which the point loop reads the pose and the flag alone
   vbh::OdomEkf &S = *c->sat->odom.h;
   std::memset(&S, 0, sizeof(S));
   std::memcpy(S.R, R, sizeof(S.R)); std::memcpy(S.t, t, sizeof(S.t));
-  HIPCHK(c, hipMemcpyAsync(c->sat->odom.d.p, &S, sizeof(vbh::OdomEkf), hipMemcpyHostToDevice, s));
   double *d_part = c->sat->odom.d_part.p;
-  surfel_odom_queue(m, s, c->sat->odom.d, n, d_pnt, p->gate, p->neighbors, d_part, d_out.p + 34, d_cell.p, d_gate.p);
-  hipLaunchKernelGGL(k_odom_sums, dim3(1), dim3(256), 0, s, (const double *)d_part, nb, d_out.p);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(s));
+  if ((st = odom_sums_run(c, d_part, d_out.p, [&] {
+        return surfel_odom_queue(m, c->stream, c->sat->odom.d, n, d_pnt, p->gate, p->neighbors, d_part, d_out.p + 34, d_cell.p, d_gate.p);
+      })))
+    return st;
   hipError_t e = hipSuccess;
   if (sums) e = hipMemcpy(sums, d_out.p, 34 * sizeof(double), hipMemcpyDeviceToHost);
   if (e == hipSuccess && cost) e = hipMemcpy(cost, d_out.p + 34, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost);
