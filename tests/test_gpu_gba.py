@@ -222,6 +222,92 @@ def test_hba_global_at_scale(oracle):
     np.testing.assert_allclose(s2[:, 2:14], e2[:, 2:14], rtol=0, atol=1e-6)
 
 
+@pytest.fixture(scope="module")
+def small_hba():
+    """25 keyframes x 6000 points, windows of 10 at stride 5: four bottom-layer windows, the smallest shape at which two worker
+    contexts engage (4 >= 2 * 2).  The edges of a fresh context per hba_workers value, computed once."""
+    import voxel_slam_amd  # noqa: F401
+    from voxel_slam_amd import capi, synth
+    nkf, wd, mg = 25, 10, 5
+    wl = dataclasses.replace(synth.CONFIGS["room20k_w4"], name="room_kf", win_size=nkf, n_pts=6000)
+    s = synth.make_scans(wl)
+    clouds = [p.astype(np.float32).astype(np.float64) for p in s["points"]]
+    x0 = synth.poses_flat(s["R0"], s["p0"])
+
+    def context(workers):
+        o = capi.options_from_workload(dataclasses.replace(wl, win_size=wd)); o.hba_workers = workers
+        return capi.Context(o)
+
+    def run(ctx, cl):
+        return ctx.hba_global(cl, x0, x0, GBA["gba_voxel_size"], GBA["gba_min_eigen_value"], GBA["gba_eig"], 2, wd, mg)
+
+    edges = {}
+    for workers in (1, 2):
+        ctx = context(workers)
+        edges[workers] = run(ctx, clouds)
+        ctx.close()
+    return dict(clouds=clouds, x0=x0, wd=wd, mg=mg, context=context, run=run, edges=edges, capi=capi)
+
+
+def _same_edges(a, b):
+    for x, y in zip(a, b):
+        assert x.shape == y.shape
+        np.testing.assert_array_equal(x[:, :2], y[:, :2])
+        np.testing.assert_allclose(x[:, 2:14], y[:, 2:14], rtol=0, atol=1e-6)      # the bar of test_hba_global_at_scale for this comparison
+
+
+def test_hba_global_workers_equal_sequential_at_the_small_shape(small_hba):
+    """Two worker contexts against one window after the other where worker mode first engages."""
+    (w1, w2), (s1, s2) = small_hba["edges"][2], small_hba["edges"][1]
+    assert len(s1) == 4 * 45 and len(s2) == 6
+    _same_edges((w1, w2), (s1, s2))
+
+
+def test_hba_global_failing_window_in_worker_mode(small_hba):
+    """A window that fails in worker mode (keyframes 5..14 see nothing planar: window 1 fails in its LM loop) returns the status it
+    returns one window after the other, and the stopped call leaves the workers and d_hba_all usable: the clean input on the SAME
+    context gives the edges of a fresh context."""
+    capi = small_hba["capi"]
+    bad = list(small_hba["clouds"])
+    rng = np.random.default_rng(0)
+    for i in range(5, 15):
+        bad[i] = rng.normal(0, 3.0, (400, 3)).astype(np.float32).astype(np.float64)
+    status = {}
+    for workers in (1, 2):
+        ctx = small_hba["context"](workers)
+        with pytest.raises(capi.VbaError) as e:
+            small_hba["run"](ctx, bad)
+        status[workers] = e.value.status
+        if workers == 2:
+            _same_edges(small_hba["run"](ctx, small_hba["clouds"]), small_hba["edges"][2])
+        ctx.close()
+    assert status[1] != 0 and status[2] == status[1]
+
+
+@pytest.mark.parametrize("workers", [1, 2])
+def test_hba_global_edge_capacity(small_hba, workers):
+    """cap1 one row short of the result: VBA_ERR_CAPACITY with n_edges1 == cap1; exact: VBA_OK.  Once through the sequential driver's
+    append and once through the collecting walk of the worker driver."""
+    import ctypes as C
+    capi = small_hba["capi"]
+    n1_full, n2_full = len(small_hba["edges"][workers][0]), len(small_hba["edges"][workers][1])
+    off, pnt = capi.Context._ragged(small_hba["clouds"])
+    x0 = np.ascontiguousarray(small_hba["x0"], dtype=np.float64)
+    eig = np.ascontiguousarray(GBA["gba_eig"], dtype=np.float64)
+    dp = C.POINTER(C.c_double)
+    ctx = small_hba["context"](workers)
+    for cap1, want in ((n1_full - 1, capi.ERR_CAPACITY), (n1_full, 0)):
+        e1 = np.zeros((cap1, 20)); e2 = np.zeros((n2_full, 20)); n1 = C.c_int(-1); n2 = C.c_int(-1)
+        st = ctx.lib.vba_hba_global(ctx.h, len(small_hba["clouds"]), off.ctypes.data_as(C.POINTER(C.c_int)), pnt.ctypes.data_as(dp), x0.ctypes.data_as(dp),
+                                    x0.ctypes.data_as(dp), GBA["gba_voxel_size"], GBA["gba_min_eigen_value"], eig.ctypes.data_as(dp), 2,
+                                    small_hba["wd"], small_hba["mg"], e1.ctypes.data_as(dp), cap1, C.byref(n1), e2.ctypes.data_as(dp), n2_full, C.byref(n2))
+        assert st == want and n1.value == cap1
+        np.testing.assert_array_equal(e1[:, :2], small_hba["edges"][workers][0][:cap1, :2])      # the rows that fitted are written
+        if want == 0:
+            assert n2.value == n2_full
+    ctx.close()
+
+
 def test_hba_global_full_length():
     """BASELINE.json configs[4] at its full length on ONE GPU: 2000 keyframes x 50k points (98.5 M points) -> 399 bottom-layer windows
     + the 399-submap top-level BA in one vba_hba_global call; the bottom layer is checked against the oracle on 12 windows spread over

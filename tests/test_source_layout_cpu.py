@@ -402,6 +402,43 @@ def test_var_world_is_called_by_both_stagings():
     assert "#pragma clang fp contract(off)" in kernel_body("vba_kernels_init.hpp", "k_init_blur")
 
 
+# ---------------------------------------------------------------- the drivers of vba_hba_global ("Source layout": vba_hba.hip)
+def test_hba_plan_is_a_device_free_header_of_one_unit():
+    plan = read("vba_hba_plan.hpp")
+    assert "hip" not in plan and INCLUDE.findall(plan) == [] and "vba_ctx" not in plan and "__global__" not in plan
+    assert [f for f in sources() if "vba_hba_plan.hpp" in INCLUDE.findall(read(f))] == ["vba_hba.hip"]
+    host = open(os.path.join(os.path.dirname(CSRC), "..", "tests", "host", "hba_plan_host.cpp")).read()
+    assert "csrc/vba_hba_plan.hpp" in host
+    assert [f for f in sources() if "std::thread" in read(f)] == ["vba_hba_plan.hpp"]
+
+
+def test_hba_global_pieces_are_written_once():
+    unit = read("vba_hba.hip")
+    add_edge = re.compile(r"\bvba_hba_add_edge\(")
+    assert add_edge.search("const int st = vba_hba_add_edge(cx, P.wdsize,") and not add_edge.search("// (vba_gba_build, vba_hba_add_edge, vba_hba_global)")
+    assert call_sites("vba_hba.hip", add_edge) == {"vba_hba_add_edge": 1, "hba_window": 1, "hba_top": 1}         # (its own head, and two calls)
+    shift = re.compile(r"\bo\[[01]\]\s*\+=")
+    assert shift.search("o[0] += start; o[1] += start;") and not shift.search("o[0] = i; o[1] = j;")
+    assert not shift.search(unit)
+    assert call_sites("vba_hba.hip", re.compile(r"\bhba_append_edges\(")) == {"hba_collect": 1, "hba_bottom_sequential": 1, "hba_top": 1}
+    assert len(re.findall(r"^inline int hba_append_edges\(", read("vba_hba_plan.hpp"), re.M)) == 1
+    # the record index is the plan's: no product with meta_chunk in the unit (a byte count for a copy is not an index)
+    product = re.compile(r"\bmeta_chunk\s*\*(?!\s*sizeof\b)|\*\s*(?:\(\w+\)\s*)?(?:\w+(?:\.|->))*meta_chunk\b")
+    assert product.search("meta[(size_t)(w % NR) * meta_chunk + 2]") and product.search("d_meta + P.meta_chunk * (size_t)rank") and product.search("NR * P.meta_chunk")
+    assert not product.search("P.meta_chunk * sizeof(double)") and not product.search("ctx_allgather(c, d_meta, P.meta_chunk)")
+    assert not product.search(unit)
+    # the early stop is wired into the worker driver through the header's pieces, which tests/host/hba_plan_host.cpp runs
+    workers = function_body(unit, r"^static int hba_bottom_workers\(")
+    for call in ("hba_gate(kf_ready, P.win[w].start + P.wdsize, stop_after, w)", "hba_stop_at(stop_after, w)", "hba_upload_wanted(P, stop_after.load(), k0)",
+                 "hba_run_lanes(P.KL, stop_after, work, upload)", "stop_after{P.n_win}"):
+        assert workers.count(call) == 1, call
+    body = function_body(unit, r"^int vba_hba_global\(")
+    assert "hba_plan(" in body and "d_hba_all.ensure(P.need)" in body and "hba_top(" in body
+    for driver in ("hba_bottom_sequential", "hba_bottom_workers", "hba_bottom_replicas"):
+        assert driver + "(" in body and len(re.findall(r"^static int %s\(" % driver, unit, re.M)) == 1, driver
+    assert "for (" not in body and "hipMemcpyAsync" not in body
+
+
 # ---------------------------------------------------------------- the frame of an odometry update ("Source layout": vba_odom.hip)
 ODOM_ENTRIES = ("vba_odom_lio_state_estimation_resident", "vba_odom_lio_state_estimation_kdtree_resident", "vba_odom_surfel_update",
                 "vba_odom_lio_state_estimation_on_state", "vba_odom_lio_state_estimation_kdtree_on_state", "vba_odom_surfel_update_on_state")

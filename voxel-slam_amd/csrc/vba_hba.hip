@@ -5,6 +5,7 @@
 #include "vba_kernels_gba.hpp"
 #include "vba_kernels_big.hpp"
 #include "vba_hostmath.hpp"
+#include "vba_hba_plan.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -13,7 +14,6 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 namespace vba {
@@ -713,236 +713,216 @@ int vba_debug_big_residual(vba_ctx *c, const double *poses, double *r) {
 //                 = the window's down-sampled points in that frame, VS:3084-3089);
 //   top layer     HBA_add_edge over all submaps with their CURRENT poses (VS:3096-3110): edges2.
 // Edge rows carry GLOBAL keyframe indices.  (Queue handling, map switching and the GTSAM pose graph stay with the caller.)
+//
+// The bottom layer has three drivers over one plan (vba_hba_plan.hpp: windows, lanes, the layout of d_hba_all) and shared pieces
+// ("The drivers of vba_hba_global"): hba_window optimises one window into a [n_cloud, n_edges, status | edge rows] record,
+// hba_collect walks the records of the two chunked modes in window order, hba_top is the top-level window.
+static_assert(HBA_PLAN_OK == VBA_OK && HBA_PLAN_ERR_RUNTIME == VBA_ERR_HIP && HBA_PLAN_ERR_CAPACITY == VBA_ERR_CAPACITY, "vba_hba_plan.hpp returns the ABI's statuses");
+
+struct HbaCall {                                    // the caller's arrays and parameters, as vba_hba_global received them
+  int n_kf; const int *offsets; const double *pnt_local, *poses_x0, *poses_now;
+  double voxel_size, min_eig; const double *eig; int total_max_iter;
+  double *edges1; int cap1, *n1; double *edges2; int cap2, *n2;
+};
+struct HbaSubmaps {                                 // global id of every submap's first keyframe, points of its cloud, points of all clouds
+  std::vector<int> first, n; size_t pts = 0;
+  void push(int start, int nc) { first.push_back(start); n.push_back(nc); pts += (size_t)nc; }
+};
+// VBA_HBA_TIMES (diagnostic build): the wall-clock split of the call on stderr, once the bottom layer has succeeded
+struct HbaTimes {
+  bool on; double t0 = 0, t1 = 0;
+  static double now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  explicit HbaTimes(vba_ctx *c) { static const bool want = diag_env("VBA_HBA_TIMES") != nullptr; on = want; if (on) { hipStreamSynchronize(c->stream); t0 = now(); } }
+  void windows_done() { if (on) t1 = now(); }
+  ~HbaTimes() { if (on && t1 > 0) std::fprintf(stderr, "[hba_global] windows %.0f us, top %.0f us (after the upload)\n", t1 - t0, now() - t1); }
+};
+
+// One bottom-layer window on context cx: HBA_add_edge(xs = x0 of the window, max_iter 1, thread_num 2) on the keyframe clouds at d_all,
+// the down-sampled cloud to d_cloud, status, counts and edge rows (window-local indices) into the record.  No exception leaves it.
+static int hba_window(vba_ctx *cx, const HbaPlan &P, int w, const HbaCall &A, const double *d_all, double *d_cloud, double *rec, std::vector<int> &ccnt) try {
+  const int start = P.win[w].start;
+  std::vector<int> off(P.wdsize + 1);
+  for (int i = 0; i <= P.wdsize; i++) off[i] = A.offsets[start + i] - A.offsets[start];
+  std::vector<double> xs(A.poses_x0 + (size_t)start * 12, A.poses_x0 + (size_t)(start + P.wdsize) * 12);
+  int ne = 0, nc = 0;
+  const int st = vba_hba_add_edge(cx, P.wdsize, off.data(), d_all + (size_t)A.offsets[start] * 3, xs.data(), A.voxel_size, A.min_eig, A.eig, 1, 2, rec + 3, &ne,
+                                  d_cloud, ccnt.data(), &nc, nullptr, nullptr);
+  rec[2] = st;
+  if (st == VBA_OK) { rec[0] = nc; rec[1] = ne; }
+  return st;
+} catch (const std::bad_alloc &) {                  // a host allocation of the window is the window's failure: it travels like any other status
+  cx->set_error("vba_hba_global: out of host memory in a bottom-layer window");
+  return (int)(rec[2] = VBA_ERR_CAPACITY);
+} catch (...) {
+  cx->set_error("vba_hba_global: unexpected exception in a bottom-layer window");
+  return (int)(rec[2] = VBA_ERR_HIP);
+}
+static double *hba_chunk_cloud(const HbaPlan &P, double *d_rep, int w) { return d_rep + ((size_t)P.win[w].lane * P.chunk_pts + P.win[w].roff) * 3; }
+
+// The records of the two chunked modes in window order: the first failing window decides (lane_err: the worker lanes' error texts;
+// null: replicas, where the text is the same on every rank); otherwise edges1 with global indices, and every window's cloud from its
+// lane's chunk to the compact submap area that the top level reads.
+static int hba_collect(vba_ctx *c, const HbaPlan &P, const HbaCall &A, const std::vector<double> &meta, double *d_sub, double *d_rep, HbaSubmaps &S,
+                       const std::vector<std::string> *lane_err) {
+  for (int w = 0; w < P.n_win; w++) {
+    const int st = (int)P.rec(meta.data(), w)[2];
+    if (st == VBA_OK) continue;
+    if (st < 0) { c->set_error("vba_hba_global: a bottom-layer window was not run"); return VBA_ERR_HIP; }
+    if (!lane_err) c->set_error("a bottom-layer window failed on one of the ranks");
+    else if (!(*lane_err)[P.win[w].lane].empty()) c->set_error((*lane_err)[P.win[w].lane]);
+    return st;
+  }
+  for (int w = 0; w < P.n_win; w++) {
+    const double *rec = P.rec(meta.data(), w);
+    const int nc = (int)rec[0], start = P.win[w].start;
+    if (hba_append_edges(A.edges1, A.cap1, A.n1, rec + 3, (int)rec[1], [start](double i) { return i + start; })) return VBA_ERR_CAPACITY;
+    if (nc > 0) HIPCHK(c, hipMemcpyAsync(d_sub + S.pts * 3, hba_chunk_cloud(P, d_rep, w), (size_t)nc * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    S.push(start, nc);
+  }
+  return VBA_OK;
+}
+
+// the keyframe clouds go to HBM once (the stride-5 windows overlap: every keyframe is used twice); the worker driver uploads them itself
+static int hba_upload_all(vba_ctx *c, const HbaPlan &P, const HbaCall &A, double *d_all) {
+  if (P.n_all > 0) HIPCHK(c, hipMemcpyAsync(d_all, A.pnt_local, P.n_all * 3 * sizeof(double), hipMemcpyDefault, c->stream));
+  return VBA_OK;
+}
+
+// One window after the other: the submap clouds never leave HBM, every window's down-sampled cloud is written behind the previous one.
+static int hba_bottom_sequential(vba_ctx *c, const HbaPlan &P, const HbaCall &A, double *d_all, double *d_sub, std::vector<int> &ccnt, HbaSubmaps &S) {
+  std::vector<double> rec(P.meta_per);
+  for (int w = 0; w < P.n_win; w++) {
+    const int start = P.win[w].start;
+    const int st = hba_window(c, P, w, A, d_all, d_sub + S.pts * 3, rec.data(), ccnt);
+    if (st) return st;
+    if (hba_append_edges(A.edges1, A.cap1, A.n1, rec.data() + 3, (int)rec[1], [start](double i) { return i + start; })) return VBA_ERR_CAPACITY;
+    S.push(start, (int)rec[0]);
+  }
+  return VBA_OK;
+}
+
+// ONE rank: one window is a chain of small kernels and host round trips that leaves most of the chip idle — KL worker contexts (own
+// stream, own octree and LM state; host threads drive them) optimise windows side by side: lane t takes windows t, t + KL, ... and
+// writes their clouds into its chunk.  The keyframe clouds travel to HBM in chunks on a stream of their own while the first windows
+// are already being optimised (2.4 GB at full length: as long as the windows themselves); a window starts when its keyframes have
+// arrived.  A failing window lowers stop_after: lanes skip the windows above it and the uploader stops behind its keyframes.
+static int hba_bottom_workers(vba_ctx *c, const HbaPlan &P, const HbaCall &A, double *d_all, double *d_sub, double *d_rep, std::vector<double> &meta, HbaSubmaps &S) {
+  while ((int)c->hba_workers.size() < P.KL - 1) {
+    vba_options o = c->opt; o.stream = nullptr; o.device = c->device;
+    vba_ctx *w = nullptr;
+    const int stc = vba_create(&o, &w);
+    if (stc) { c->set_error("vba_hba_global: could not create a worker context"); return stc; }
+    c->hba_workers.push_back(w);
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int w = 0; w < P.n_win; w++) P.rec(meta.data(), w)[2] = -1.0;             // "not run"
+  std::vector<std::string> werr(P.KL);
+  std::atomic<int> kf_ready{0}, stop_after{P.n_win};
+  auto work = [&](int lane) {
+    vba_ctx *cx = lane == 0 ? c : c->hba_workers[lane - 1];
+    hipSetDevice(c->device);
+    std::vector<int> ccnt(P.n_win_max > 0 ? P.n_win_max : 1);                    // (every lane its own, lane 0 too: see vba_hba_global)
+    for (int w = lane; w < P.n_win; w += P.KL) {
+      if (!hba_gate(kf_ready, P.win[w].start + P.wdsize, stop_after, w)) return;
+      if (hba_window(cx, P, w, A, d_all, hba_chunk_cloud(P, d_rep, w), P.rec(meta.data(), w), ccnt) != VBA_OK) { werr[lane] = cx->err; hba_stop_at(stop_after, w); return; }
+    }
+  };
+  // (one uploader: three threads staging chunks in turn moved the pageable copy no faster — 4-5 GB/s either way; at full length
+  //  the call is bound by this copy once the windows overlap it)
+  auto upload = [&]() -> int {
+    hipStream_t up = nullptr;
+    if (hipStreamCreateWithFlags(&up, hipStreamNonBlocking) != hipSuccess) return VBA_ERR_HIP;
+    const int CH = 16;                                                           // keyframes per chunk
+    int st = VBA_OK;
+    for (int k0 = 0; k0 < A.n_kf && st == VBA_OK; k0 += CH) {
+      if (!hba_upload_wanted(P, stop_after.load(), k0)) break;                   // the keyframes of the lowest failing window are up
+      const int k1 = k0 + CH < A.n_kf ? k0 + CH : A.n_kf;
+      const size_t o0 = (size_t)A.offsets[k0] * 3, nb = (size_t)(A.offsets[k1] - A.offsets[k0]) * 3 * sizeof(double);
+      if (nb > 0 && (hipMemcpyAsync(d_all + o0, A.pnt_local + o0, nb, hipMemcpyDefault, up) != hipSuccess || hipStreamSynchronize(up) != hipSuccess)) st = VBA_ERR_HIP;
+      else kf_ready.store(k1, std::memory_order_release);
+    }
+    hipStreamDestroy(up);
+    return st;
+  };
+  const int st = hba_run_lanes(P.KL, stop_after, work, upload);
+  hipSetDevice(c->device);
+  if (st) { c->set_error(st == VBA_ERR_CAPACITY ? "vba_hba_global: out of host memory in a worker lane" : "vba_hba_global: uploading the keyframe clouds or starting the worker lanes failed"); return st; }
+  return hba_collect(c, P, A, meta, d_sub, d_rep, S, &werr);
+}
+
+// More than one rank ("windows are independent problems => replicas across GPUs for the bottom layer"): window w is
+// optimised by rank w % n_ranks with the exchange step switched off; every rank packs its windows' clouds and records into ITS chunk
+// of two buffers, and one ALL-GATHER of each hands every rank all of them (a rank receives each foreign byte once).  A window that
+// fails on one rank travels as its status word: every rank goes on, enters both collectives and all of them return the same error
+// afterwards — no rank is left waiting in a collective.  The top-level window then runs replicated (identical inputs on every rank).
+static int hba_bottom_replicas(vba_ctx *c, const HbaPlan &P, const HbaCall &A, double *d_all, double *d_sub, double *d_rep, double *d_meta, std::vector<int> &ccnt,
+                               std::vector<double> &meta, HbaSubmaps &S) {
+  {
+    struct Restore { vba_ctx *c; bool was; ~Restore() { c->collective_off = was; } } restore{c, c->collective_off};
+    c->collective_off = true;                                                    // the windows' own LM loops must not enter a collective
+    for (int w = 0; w < P.n_win; w++)
+      if (P.win[w].lane == c->rank) hba_window(c, P, w, A, d_all, hba_chunk_cloud(P, d_rep, w), P.rec(meta.data(), w), ccnt);   // its status travels with the gather
+  }
+  if (P.meta_chunk > 0)
+    HIPCHK(c, hipMemcpyAsync(P.lane_recs(d_meta, c->rank), P.lane_recs(meta.data(), c->rank), P.meta_chunk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  int rc = ctx_allgather(c, d_rep, P.chunk_pts * 3);
+  if (rc) return rc;
+  rc = ctx_allgather(c, d_meta, P.meta_chunk);
+  if (rc) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(meta.data(), d_meta, meta.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return hba_collect(c, P, A, meta, d_sub, d_rep, S, nullptr);
+}
+
+// The top-level window over all submaps with their CURRENT poses: edges2, indices looked up in the submaps' first keyframes.
+static int hba_top(vba_ctx *c, const HbaCall &A, const double *d_sub, const HbaSubmaps &S) {
+  const int ns = (int)S.first.size();
+  if (ns < 2) return VBA_OK;
+  std::vector<int> off(ns + 1, 0);
+  for (int i = 0; i < ns; i++) off[i + 1] = off[i] + S.n[i];
+  std::vector<double> xs((size_t)ns * 12), e2((size_t)(ns * (ns - 1) / 2 + 1) * 20);
+  for (int i = 0; i < ns; i++) std::memcpy(&xs[(size_t)i * 12], A.poses_now + (size_t)S.first[i] * 12, 12 * sizeof(double));
+  int ne = 0;
+  const int st = vba_hba_add_edge(c, ns, off.data(), d_sub, xs.data(), A.voxel_size, A.min_eig, A.eig, A.total_max_iter, 5, e2.data(), &ne, nullptr, nullptr, nullptr,
+                                  nullptr, nullptr);
+  if (st) return st;
+  return hba_append_edges(A.edges2, A.cap2, A.n2, e2.data(), ne, [&S](double i) { return (double)S.first[(int)i]; });
+}
+
 int vba_hba_global(vba_ctx *c, int n_kf, const int *offsets, const double *pnt_local, const double *poses_x0, const double *poses_now,
                    double gba_voxel_size, double gba_min_eigen_value, const double *gba_eigen_value_array, int total_max_iter, int wdsize, int mgsize,
-                   double *edges1_out, int cap1, int *n_edges1, double *edges2_out, int cap2, int *n_edges2) {
+                   double *edges1_out, int cap1, int *n_edges1, double *edges2_out, int cap2, int *n_edges2) try {
   if (n_kf < 0 || wdsize < 2 || mgsize < 1 || !offsets || !poses_x0 || !poses_now || !gba_eigen_value_array || !n_edges1 || !n_edges2 ||
       (offsets[n_kf] > 0 && !pnt_local))
     return VBA_ERR_BAD_ARG;
   *n_edges1 = 0; *n_edges2 = 0;
-  std::vector<int> sub_first, sub_n;                // global id of every submap's first keyframe, points of its cloud
-  std::vector<double> edges((size_t)(wdsize * (wdsize - 1) / 2 + 1) * 20);
-  // the keyframe clouds go to HBM once (the stride-5 windows overlap: every keyframe is used twice) and the submap clouds
-  // never leave it: every window's down-sampled cloud is written behind the previous one and the top-level BA reads them there
-  const size_t n_all = (size_t)offsets[n_kf];
-  size_t n_sub_cap = 0, n_win_max = 0;
-  for (int start = 0; start + wdsize <= n_kf; start += mgsize) {
-    const size_t nw = (size_t)(offsets[start + wdsize] - offsets[start]);
-    n_sub_cap += nw; if (nw > n_win_max) n_win_max = nw;
-  }
-  // More than one rank ("windows are independent problems => replicas across GPUs for the bottom layer"): window
-  // wi is optimised by rank wi % n_ranks with the exchange step switched off; every rank packs its windows' clouds and its
-  // [points, edges, status | edge rows] records into ITS chunk of two buffers, and one ALL-GATHER of each hands every rank all of
-  // them (a rank receives each foreign byte once).  A window that fails on one rank travels as its status word: every rank
-  // enters both collectives and all of them return the same error afterwards — no rank is left waiting in a collective.
-  // The top-level window then runs replicated (identical inputs on every rank).
-  const bool replicas = c->collective() && c->n_ranks > 1;
-  int n_win = 0;
-  for (int start = 0; start + wdsize <= n_kf; start += mgsize) n_win++;
-  // ONE rank: the windows are independent problems too, and one window is a chain of small kernels and host round trips that leaves
-  // most of the chip idle — KL worker contexts (own stream, own octree and LM state; host threads drive them) optimise windows
-  // side by side, with the bookkeeping of the replicas: worker t takes windows t, t + KL, ... and writes their clouds into its chunk.
-  const int kl_opt = c->opt.hba_workers > 0 ? (c->opt.hba_workers < 8 ? c->opt.hba_workers : 8) : 4;
-  const int KL = (!replicas && n_win >= 2 * kl_opt) ? kl_opt : 1;
-  const bool local_rep = KL > 1, chunked = replicas || local_rep;
-  const int NR = replicas ? c->n_ranks : KL;
-  const size_t meta_per = 3 + (size_t)(wdsize * (wdsize - 1) / 2) * 20;
-  const size_t win_per_rank = chunked ? (size_t)(n_win + NR - 1) / NR : 0, meta_chunk = meta_per * win_per_rank;
-  std::vector<size_t> rank_cap(NR, 0), win_roff(n_win > 0 ? n_win : 1, 0);      // points capacity per rank chunk, window offset inside it
-  if (chunked) {
-    int w = 0;
-    for (int start = 0; start + wdsize <= n_kf; start += mgsize, w++) {
-      win_roff[w] = rank_cap[w % NR];
-      rank_cap[w % NR] += (size_t)(offsets[start + wdsize] - offsets[start]);
-    }
-  }
-  size_t chunk_pts = 0;
-  for (int r = 0; r < NR; r++) if (rank_cap[r] > chunk_pts) chunk_pts = rank_cap[r];
-  if (!chunked) chunk_pts = 0;
-  const size_t need = (n_all + n_sub_cap + (size_t)NR * chunk_pts) * 3 + (size_t)NR * meta_chunk + 64;
-  HIPCHK(c, c->d_hba_all.ensure(need));
-  double *d_all = c->d_hba_all, *d_sub = c->d_hba_all + n_all * 3;
-  if (n_all > 0 && !local_rep) HIPCHK(c, hipMemcpyAsync(d_all, pnt_local, n_all * 3 * sizeof(double), hipMemcpyDefault, c->stream));   // (the worker path uploads in chunks, under the first windows)
-  std::vector<int> ccnt(n_win_max > 0 ? n_win_max : 1);
-  size_t sub_off = 0;
-  double *d_rep = d_sub + n_sub_cap * 3, *d_meta = d_rep + (size_t)NR * chunk_pts * 3;      // replica mode only
-  std::vector<double> meta((size_t)NR * meta_chunk, 0.0);
-  struct Restore { vba_ctx *c; bool was; ~Restore() { c->collective_off = was; } } restore{c, c->collective_off};
-  if (replicas) c->collective_off = true;                                       // the windows' own LM loops must not enter a collective
-  int wi = -1;
-  static const bool want_times = diag_env("VBA_HBA_TIMES") != nullptr;
-  auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t_g0 = want_times ? (hipStreamSynchronize(c->stream), now()) : 0.0;
-  double t_g1 = 0;
-  if (local_rep) {
-    while ((int)c->hba_workers.size() < KL - 1) {
-      vba_options o = c->opt; o.stream = nullptr; o.device = c->device;
-      vba_ctx *w = nullptr;
-      const int stc = vba_create(&o, &w);
-      if (stc) { c->set_error("vba_hba_global: could not create a worker context"); return stc; }
-      c->hba_workers.push_back(w);
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int w = 0; w < n_win; w++) meta[(size_t)(w % KL) * meta_chunk + meta_per * (size_t)(w / KL) + 2] = -1.0;   // "not run"
-    std::vector<std::string> werr(KL);
-    // the keyframe clouds travel to HBM in chunks on a stream of their own while the first windows are already being optimised
-    // (2.4 GB at full length: as long as the windows themselves); a window starts when its keyframes have arrived
-    std::atomic<int> kf_ready{0}, give_up{0};
-    auto work = [&](int tw) {
-      vba_ctx *cx = tw == 0 ? c : c->hba_workers[tw - 1];
-      hipSetDevice(c->device);
-      std::vector<double> ed(edges.size());
-      std::vector<int> cc(ccnt.size()), off(wdsize + 1);
-      for (int w = tw; w < n_win; w += KL) {
-        const int start = w * mgsize;
-        while (kf_ready.load(std::memory_order_acquire) < start + wdsize && !give_up.load()) std::this_thread::sleep_for(std::chrono::microseconds(20));
-        if (give_up.load()) return;
-        for (int i = 0; i <= wdsize; i++) off[i] = offsets[start + i] - offsets[start];
-        std::vector<double> xs(poses_x0 + (size_t)start * 12, poses_x0 + (size_t)(start + wdsize) * 12);
-        int ne = 0, nc = 0;
-        double *mrec = &meta[(size_t)tw * meta_chunk + meta_per * (size_t)(w / KL)];
-        const int st = vba_hba_add_edge(cx, wdsize, off.data(), d_all + (size_t)offsets[start] * 3, xs.data(), gba_voxel_size, gba_min_eigen_value,
-                                        gba_eigen_value_array, 1, 2, ed.data(), &ne, d_rep + ((size_t)tw * chunk_pts + win_roff[w]) * 3,
-                                        cc.data(), &nc, nullptr, nullptr);
-        mrec[2] = st;
-        if (st != VBA_OK) { werr[tw] = cx->err; return; }
-        mrec[0] = nc; mrec[1] = ne;
-        std::memcpy(mrec + 3, ed.data(), (size_t)ne * 20 * sizeof(double));
-      }
-    };
-    int up_status = VBA_OK;
-    {
-      std::vector<std::thread> th;
-      for (int tw = 0; tw < KL; tw++) th.emplace_back(work, tw);
-      // (one uploader: three threads staging chunks in turn moved the pageable copy no faster — 4-5 GB/s either way; at full
-      //  length the call is bound by this copy once the windows overlap it)
-      hipStream_t up = nullptr;
-      if (hipStreamCreateWithFlags(&up, hipStreamNonBlocking) != hipSuccess) { up_status = VBA_ERR_HIP; give_up.store(1); }
-      const int CH = 16;                                                           // keyframes per chunk
-      for (int k0 = 0; k0 < n_kf && up_status == VBA_OK; k0 += CH) {
-        const int k1 = k0 + CH < n_kf ? k0 + CH : n_kf;
-        const size_t o0 = (size_t)offsets[k0] * 3, nb = (size_t)(offsets[k1] - offsets[k0]) * 3 * sizeof(double);
-        if (nb > 0 && (hipMemcpyAsync(d_all + o0, pnt_local + o0, nb, hipMemcpyDefault, up) != hipSuccess || hipStreamSynchronize(up) != hipSuccess)) {
-          up_status = VBA_ERR_HIP; give_up.store(1); break;
-        }
-        kf_ready.store(k1, std::memory_order_release);
-      }
-      if (up) hipStreamDestroy(up);
-      for (auto &x : th) x.join();
-    }
-    hipSetDevice(c->device);
-    if (up_status != VBA_OK) { c->set_error("vba_hba_global: uploading the keyframe clouds failed"); return up_status; }
-    for (int w = 0; w < n_win; w++) {                                            // the first failing window in window order decides
-      const int stw = (int)meta[(size_t)(w % KL) * meta_chunk + meta_per * (size_t)(w / KL) + 2];
-      if (stw > 0) { if (!werr[w % KL].empty()) c->set_error(werr[w % KL]); return stw; }
-    }
-    for (int w = 0; w < n_win; w++) {
-      const double *mrec = &meta[(size_t)(w % KL) * meta_chunk + meta_per * (size_t)(w / KL)];
-      if ((int)mrec[2] != VBA_OK) { c->set_error("vba_hba_global: a bottom-layer window was not run"); return VBA_ERR_HIP; }
-      const int nc = (int)mrec[0], ne = (int)mrec[1], start = w * mgsize;
-      for (int e = 0; e < ne; e++) {
-        if (*n_edges1 >= cap1) return VBA_ERR_CAPACITY;
-        double *o = edges1_out + (size_t)(*n_edges1) * 20;
-        std::memcpy(o, mrec + 3 + (size_t)e * 20, 20 * sizeof(double));
-        o[0] += start; o[1] += start;
-        (*n_edges1)++;
-      }
-      if (nc > 0) HIPCHK(c, hipMemcpyAsync(d_sub + sub_off * 3, d_rep + ((size_t)(w % KL) * chunk_pts + win_roff[w]) * 3, (size_t)nc * 3 * sizeof(double),
-                                           hipMemcpyDeviceToDevice, c->stream));
-      sub_first.push_back(start);
-      sub_n.push_back(nc);
-      sub_off += (size_t)nc;
-    }
-  }
-  for (int start = 0; !local_rep && start + wdsize <= n_kf; start += mgsize) {
-    std::vector<int> off(wdsize + 1);
-    for (int i = 0; i <= wdsize; i++) off[i] = offsets[start + i] - offsets[start];
-    std::vector<double> xs(poses_x0 + (size_t)start * 12, poses_x0 + (size_t)(start + wdsize) * 12);
-    int ne = 0, nc = 0;
-    wi++;
-    if (replicas) {
-      sub_first.push_back(start);
-      if (wi % NR != c->rank) continue;
-      double *mrec = &meta[(size_t)c->rank * meta_chunk + meta_per * (size_t)(wi / NR)];
-      const int st = vba_hba_add_edge(c, wdsize, off.data(), d_all + (size_t)offsets[start] * 3, xs.data(), gba_voxel_size, gba_min_eigen_value,
-                                      gba_eigen_value_array, 1, 2, edges.data(), &ne, d_rep + ((size_t)c->rank * chunk_pts + win_roff[wi]) * 3,
-                                      ccnt.data(), &nc, nullptr, nullptr);
-      mrec[2] = st;                            // travels with the gather: every rank learns it
-      if (st == VBA_OK) {
-        mrec[0] = nc; mrec[1] = ne;
-        std::memcpy(mrec + 3, edges.data(), (size_t)ne * 20 * sizeof(double));
-      }
-      continue;
-    }
-    int st = vba_hba_add_edge(c, wdsize, off.data(), d_all + (size_t)offsets[start] * 3, xs.data(), gba_voxel_size, gba_min_eigen_value,
-                              gba_eigen_value_array, 1, 2, edges.data(), &ne, d_sub + sub_off * 3, ccnt.data(), &nc, nullptr, nullptr);
-    if (st) return st;
-    for (int e = 0; e < ne; e++) {
-      if (*n_edges1 >= cap1) return VBA_ERR_CAPACITY;
-      double *o = edges1_out + (size_t)(*n_edges1) * 20;
-      std::memcpy(o, &edges[(size_t)e * 20], 20 * sizeof(double));
-      o[0] += start; o[1] += start;
-      (*n_edges1)++;
-    }
-    sub_first.push_back(start);
-    sub_n.push_back(nc);
-    sub_off += (size_t)nc;
-  }
-  if (replicas) {
-    c->collective_off = restore.was;
-    if (meta_chunk > 0)
-      HIPCHK(c, hipMemcpyAsync(d_meta + (size_t)c->rank * meta_chunk, meta.data() + (size_t)c->rank * meta_chunk, meta_chunk * sizeof(double),
-                               hipMemcpyHostToDevice, c->stream));
-    int rc = ctx_allgather(c, d_rep, chunk_pts * 3);
-    if (rc) return rc;
-    rc = ctx_allgather(c, d_meta, meta_chunk);
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpyAsync(meta.data(), d_meta, meta.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int worst = VBA_OK;
-    for (int w = 0; w < n_win; w++) {
-      const int stw = (int)meta[(size_t)(w % NR) * meta_chunk + meta_per * (size_t)(w / NR) + 2];
-      if (stw != VBA_OK && worst == VBA_OK) worst = stw;
-    }
-    if (worst != VBA_OK) { c->set_error("a bottom-layer window failed on one of the ranks"); return worst; }   // the same on every rank
-    for (int w = 0; w < n_win; w++) {
-      const double *mrec = &meta[(size_t)(w % NR) * meta_chunk + meta_per * (size_t)(w / NR)];
-      const int nc = (int)mrec[0], ne = (int)mrec[1], start = sub_first[w];
-      for (int e = 0; e < ne; e++) {
-        if (*n_edges1 >= cap1) return VBA_ERR_CAPACITY;
-        double *o = edges1_out + (size_t)(*n_edges1) * 20;
-        std::memcpy(o, mrec + 3 + (size_t)e * 20, 20 * sizeof(double));
-        o[0] += start; o[1] += start;
-        (*n_edges1)++;
-      }
-      if (nc > 0) HIPCHK(c, hipMemcpyAsync(d_sub + sub_off * 3, d_rep + ((size_t)(w % NR) * chunk_pts + win_roff[w]) * 3, (size_t)nc * 3 * sizeof(double),
-                                           hipMemcpyDeviceToDevice, c->stream));
-      sub_n.push_back(nc);
-      sub_off += (size_t)nc;
-    }
-  }
-  const int ns = (int)sub_first.size();
-  if (want_times) t_g1 = now();
-  struct Report { bool on; double t0, *t1; decltype(now) *clk; ~Report() { if (on) std::fprintf(stderr, "[hba_global] windows %.0f us, top %.0f us (after the upload)\n", *t1 - t0, (*clk)() - *t1); } } report{want_times, t_g0, &t_g1, &now};
-  if (ns >= 2) {
-    std::vector<int> off(ns + 1, 0);
-    for (int i = 0; i < ns; i++) off[i + 1] = off[i] + sub_n[i];
-    std::vector<double> xs((size_t)ns * 12), e2((size_t)(ns * (ns - 1) / 2 + 1) * 20);
-    for (int i = 0; i < ns; i++) std::memcpy(&xs[(size_t)i * 12], poses_now + (size_t)sub_first[i] * 12, 12 * sizeof(double));
-    int ne = 0;
-    int st = vba_hba_add_edge(c, ns, off.data(), d_sub, xs.data(), gba_voxel_size, gba_min_eigen_value, gba_eigen_value_array, total_max_iter, 5,
-                              e2.data(), &ne, nullptr, nullptr, nullptr, nullptr, nullptr);
-    if (st) return st;
-    for (int e = 0; e < ne; e++) {
-      if (*n_edges2 >= cap2) return VBA_ERR_CAPACITY;
-      double *o = edges2_out + (size_t)(*n_edges2) * 20;
-      std::memcpy(o, &e2[(size_t)e * 20], 20 * sizeof(double));
-      o[0] = sub_first[(int)e2[(size_t)e * 20]]; o[1] = sub_first[(int)e2[(size_t)e * 20 + 1]];
-      (*n_edges2)++;
-    }
-  }
-  return VBA_OK;
+  const HbaPlan P = hba_plan(n_kf, offsets, wdsize, mgsize, c->collective() && c->n_ranks > 1 ? c->n_ranks : 1, c->opt.hba_workers);
+  HIPCHK(c, c->d_hba_all.ensure(P.need));
+  double *d_all = c->d_hba_all, *d_sub = d_all + P.off_sub, *d_rep = d_all + P.off_rep, *d_meta = d_all + P.off_meta;
+  const HbaCall A{n_kf, offsets, pnt_local, poses_x0, poses_now, gba_voxel_size, gba_min_eigen_value, gba_eigen_value_array, total_max_iter,
+                  edges1_out, cap1, n_edges1, edges2_out, cap2, n_edges2};
+  int st = P.mode == HBA_WORKERS ? VBA_OK : hba_upload_all(c, P, A, d_all);       // (in one copy; the worker driver uploads in chunks, under its first windows)
+  if (st) return st;
+  HbaTimes times(c);
+  HbaSubmaps S;
+  // The cloud-count scratch of the sequential and the replica driver, then the records of the chunked modes (none one after the other).
+  // Both are allocated here in every mode and live to the end of the call, as they always have.  The worker driver does not use the
+  // scratch (every lane has its own), but its 2 MB decide where glibc trims the heap between the call's 12.7 MB buffers: without
+  // them every second full-length call took 25 ms longer (profiles/README.md).
+  std::vector<int> ccnt(P.n_win_max > 0 ? P.n_win_max : 1);
+  std::vector<double> meta(P.meta_len, 0.0);
+  st = P.mode == HBA_WORKERS ? hba_bottom_workers(c, P, A, d_all, d_sub, d_rep, meta, S)
+     : P.mode == HBA_REPLICAS ? hba_bottom_replicas(c, P, A, d_all, d_sub, d_rep, d_meta, ccnt, meta, S) : hba_bottom_sequential(c, P, A, d_all, d_sub, ccnt, S);
+  if (st) return st;
+  times.windows_done();
+  return hba_top(c, A, d_sub, S);
+} catch (const std::bad_alloc &) {                  // a std::vector of the plan, the records or a driver: nothing crosses the ABI
+  c->set_error("vba_hba_global: out of host memory");
+  return VBA_ERR_CAPACITY;
+} catch (...) {
+  c->set_error("vba_hba_global: unexpected exception");
+  return VBA_ERR_HIP;
 }
 
 }  // extern "C"
